@@ -20,6 +20,10 @@ Multi-GPU (streams are independent: sharded, no data-path collective, NO RCCL):
   * under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`: one rank per GPU; the ranks only
     share a start/stop barrier and the MAX of the elapsed time over the CPU-side gloo backend.
 
+The timed work is exactly --steps steps in one region between barrier + synchronize pairs; `ms_per_step` is that region's wall
+time / --steps and `value` the frames/s it gives. --regions R adds R further regions afterwards, reported under `timing` only.
+--dump-outputs DIR writes the frames of the last timed step (what a caller of the encode receives) as float32 .npy files.
+
 One JSON line on rank 0. Extra objects:
   roofline        - the batched QMF + MDCT work (two kernels around the gain analysis: k_qmf_sub8 + k_mdct_sub; one fused kernel
                     without gain control): algorithmic 16384 B/frame x frames per step / its duration measured with HIP
@@ -528,6 +532,30 @@ def widened_rows(S):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, jobs, rank, world):
+    """The frames each context's last timed step wrote to d_out ([S, F, frame bytes], uint8), as float32 .npy files: `frames`
+    (one context) or `frames_ctx<k>` (k = rank x contexts per rank + index). A context whose frames do not fit its share of
+    DUMP_LIMIT_BYTES is sampled: whole frames at fixed seeded positions, and `<name>_index` holds their flat indices s * F + f."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n_ctx = world * len(jobs)
+    budget = DUMP_LIMIT_BYTES // n_ctx - 4096        # (room for the .npy headers)
+    for i, j in enumerate(jobs):
+        name = "frames" if n_ctx == 1 else f"frames_ctx{rank * len(jobs) + i}"
+        flat = j.d_out.reshape(j.S * j.F, j.fsz)
+        if flat.numel() * 4 <= budget:
+            np.save(os.path.join(out_dir, name + ".npy"), j.d_out.cpu().numpy().astype(np.float32))
+            continue
+        n = budget // (j.fsz * 4 + 8)
+        idx = np.sort(np.random.RandomState(0).choice(j.S * j.F, n, replace=False))
+        rows = flat.index_select(0, torch.from_numpy(idx).to(flat.device)).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), rows.astype(np.float32))
+        np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -540,9 +568,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-side-workloads", action="store_true")
     ap.add_argument("--no-gain", action="store_true")
-    ap.add_argument("--regions", type=int, default=10, help="further timed regions after the contract's K-step one (N = 1): each at least "
-                                                             "--region-ms long, value = the median over all of them")
+    ap.add_argument("--regions", type=int, default=0, help="further timed regions after the --steps one: each at least --region-ms long, "
+                                                            "reported under `timing` (median, min, max); value and ms_per_step stay the --steps region's")
     ap.add_argument("--region-ms", type=float, default=50.0)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the frames of the last timed step to DIR/*.npy (float32, "
+                                                                       "at most 64 MB in all; a fixed seeded sample of frames beyond that)")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the frames after the timed regions")
     ap.add_argument("--runs", type=int, default=0, help="TUNING AID: AT3HIP_OPT_RUNS (runs per stream and channel of the QMF / MDCT kernels)")
     ap.add_argument("--gain-form", type=int, default=0, help="A/B AID: AT3HIP_OPT_GAIN_FORM (0 = the two-wavefront workgroups of the upsampler / "
@@ -567,8 +597,8 @@ def main():
 
     DeviceJob.sync_steps = args.sync_steps
     DeviceJob.timing_every = max(0, args.timing_every)
-    if args.sync_steps or (args.regions == 0 and args.steps < 8 * max(1, args.timing_every)):
-        DeviceJob.timing_every = 1   # a run too short to sample (profiling passes): every step carries its events
+    if args.sync_steps:
+        DeviceJob.timing_every = 1   # (profiling passes): every step carries its events
     DeviceJob.runs = args.runs
     DeviceJob.gain_form = int(args.gain_form)
     DeviceJob.gain_wgs = args.gain_wgs
@@ -636,8 +666,8 @@ def main():
         sclk_contract = j0.enc.sclk_mhz()   # the shader clock under the rate loop of the contract region's last step
     except Exception:   # noqa: BLE001 - diagnostic only
         sclk_contract = None
-    # median of >= 10 runs. Further regions bracketed the same way, each long enough (>= --region-ms) that a
-    # launch hiccup or a clock ramp does not decide the figure; the steps they run are the same steps.
+    # --regions: further regions bracketed the same way, each long enough (>= --region-ms) that a launch hiccup or a clock
+    # ramp does not decide their figure; the steps they run are the same steps. They are reported, not part of the value.
     region_ms = [elapsed / args.steps * 1e3]
     region_steps = args.steps
     k1_ms, stage_sum = [], {}
@@ -661,6 +691,8 @@ def main():
     # one-process multi-GPU run, the timed regions - is what the replay has to repeat to land on the same batch parity
     steps_done = j0.calls
     checksum = j0.checksum()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, jobs, rank, world)   # before isolated_k1 and the replays write d_out again
     try:
         sclk_mhz = j0.enc.sclk_mhz()
     except Exception:   # noqa: BLE001 - diagnostic only
@@ -722,7 +754,7 @@ def main():
 
     if rank == 0:
         med_ms = float(np.median(region_ms))
-        value = n_gpus * S * F / (med_ms * 1e-3)
+        value = n_gpus * S * F / (region_ms[0] * 1e-3)
         k1_avg_ms = float(np.mean(k1_ms)) if k1_ms else iso_ms   # (no timed step in the regions: --timing-every 0)
         achieved, frac = roofline_of(k1_avg_ms, S * F)
         ach_iso, frac_iso = roofline_of(iso_ms, S * F)
@@ -779,7 +811,7 @@ def main():
                 all_counts = pj.get("valu_wave_insts_per_launch_all", {})
                 if all_counts:
                     step_floor = floor_ms(all_counts)
-                    pipe_valu = {"floor_ms_per_step": round(step_floor, 4), "frac": round(step_floor / med_ms, 4),
+                    pipe_valu = {"floor_ms_per_step": round(step_floor, 4), "frac": round(step_floor / region_ms[0], 4),
                                  "vector_wave_instructions_per_step": int(sum(all_counts.values())),
                                  "note": "the whole step against the issue floor of its own vector instruction streams (every kernel of the pipeline, "
                                          "same pricing as roofline.valu_floor_ms; f64 instructions priced like the others, so the true floor is "
@@ -813,9 +845,9 @@ def main():
         line = {
             "metric": "ATRAC3 1024-sample stereo frames/sec", "value": round(value, 1), "unit": "frames/s",
             "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(med_ms, 4), "higher_is_better": True, "scaling": "weak",
+            "ms_per_step": round(region_ms[0], 4), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "value_is": "median of the timed regions (SURVEY 8(d)); the contract's exactly --steps region alone is timing.value_contract_region",
+            "value_is": "the timed region of exactly --steps steps (barrier + synchronize on both sides, max over ranks)",
             "x_realtime": round(value * 1024 / 44100.0, 1),
             "config": {"workload": f"ATRAC3 {cfgname} stereo, {S} streams x {F} frames = {S * F} frames per GPU per step "
                                    f"({'BASELINE configs[1]' if (S, F) == (64, 64) else 'per-GPU shard of BASELINE configs[2]' if (S, F) == (1024, 128) else 'custom'}), "
@@ -869,8 +901,8 @@ def main():
             "pipelining": "three HIP streams inside the context: the heavy front stage (QMF, gain spectra, envelopes) of step i+1, the "
                           "light front stage (curves, energy scales, MDCT) of step i and the back half (psychoacoustics, rate loop, "
                           "packing) of step i overlap; stage_ms are per-step HIP-event spans and overlap in time, total_ms is one step's latency",
-            "timing": {"value_is": "median over the timed regions (SURVEY 8(d)): region 0 is the contract's exactly --steps steps, the others "
-                                   f"are {region_steps} steps each (>= {args.region_ms:g} ms); every region sits between barrier + synchronize pairs, max over ranks",
+            "timing": {"value_is": "region 0, the contract's exactly --steps steps; the others (--regions) are "
+                                   f"{region_steps} steps each (>= {args.region_ms:g} ms), reported here only; every region sits between barrier + synchronize pairs, max over ranks",
                        "regions": len(region_ms), "steps_per_region": [args.steps] + [region_steps] * (len(region_ms) - 1),
                        "ms_per_step_median": round(med_ms, 4), "ms_per_step_min": round(min(region_ms), 4), "ms_per_step_max": round(max(region_ms), 4),
                        "ms_per_step_contract_region": round(region_ms[0], 4),

@@ -544,3 +544,63 @@ def at3p_specs(name, n_frames, channels=2, scale=1.0):
         bands = (bands.astype(np.float64) / (32768.0 / 1.122018)).astype(np.float32)   # float / double, narrowed on the store
         out[:, ch] = at3p_mdct(bands)
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# The oracle's pin (tests/test_pin_on_box.py): the reference's outputs for a slice of test_oracle_vs_ref.py's matrices,
+# stored in tests/golden/pin.npz by tools/gen_golden_pin.py, so that the slice can be re-verified where no reference
+# build exists. Frames are stored whole; the stage taps, which are large, as SHA-256 digests of their bit patterns.
+# ----------------------------------------------------------------------------------------------
+PIN_PATH = os.path.join(ROOT, "tests", "golden", "pin.npz")
+PIN_OPTION_SETS = (("mix", 0, 0), ("burst", 1, 0), ("tones", 0, 1), ("noise", 1, 1))   # signal, no_gain, no_tonal
+PIN_OPTION_BLOCKS = 24
+PIN_CONTAINER_ROWS = ((66150, 192), (93713, 272), (104738, 304), (132300, 384), (146081, 424), (176400, 512), (264600, 768), (352800, 1024))
+PIN_CONTAINER_BFUS = (0, 8)
+
+
+def pin_digest(a):
+    """SHA-256 of an array's bit patterns (float32 as uint32) and its shape, as uint8[32]."""
+    import hashlib
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.float32:
+        a = a.view(np.uint32)
+    h = hashlib.sha256(repr(a.shape).encode())
+    h.update(a.tobytes())
+    return np.frombuffer(h.digest(), dtype=np.uint8)
+
+
+def pin_inputs():
+    """The PCM the pin's encodes run on, by name (regenerated; their digests are stored with the outputs)."""
+    pcm = {f"{name}_{PIN_OPTION_BLOCKS}": SIGNALS[name](PIN_OPTION_BLOCKS) for name, _, _ in PIN_OPTION_SETS}
+    pcm["mix_16"] = SIGNALS["mix"](16)
+    pcm["stress_20"] = pcm_stress(20)
+    return pcm
+
+
+def pin_libm_inputs():
+    """Inputs of the two libm-dependent stage functions (stored in the fixture: the tests read them from there)."""
+    rng = np.random.RandomState(17)
+    flat_in = np.stack([(rng.uniform(0, 1, 1024) ** 4 * scale).astype(np.float32) for scale in (1.0, 1e-3, 1e-6)])
+    return flat_in, np.exp(rng.uniform(-20, 20, 5000)).astype(np.float32)
+
+
+def pin_outputs(codec, flatness_in, log2f_in):
+    """Everything the pin compares, computed by `codec` (the reference when generating, the oracle when testing)."""
+    out = {}
+    pcm = pin_inputs()
+    for k, v in pcm.items():
+        out[f"pcm_{k}"] = pin_digest(v)
+    for br in (LP2, LP4):
+        for name, ng, nt in PIN_OPTION_SETS:
+            frames, taps = codec.encode(pcm[f"{name}_{PIN_OPTION_BLOCKS}"], br, ng, nt, taps=True)
+            out[f"opt_{br}_{name}_frames"] = frames
+            for k in TAP_DTYPE.names:
+                if k != "tonal_pos":   # the reference keeps a pointer into a per-call temporary: not observable
+                    out[f"opt_{br}_{name}_tap_{k}"] = pin_digest(taps[k])
+    for br, _ in PIN_CONTAINER_ROWS:
+        for bfu in PIN_CONTAINER_BFUS:
+            out[f"row_{br}_bfu{bfu}_frames"] = codec.encode(pcm["mix_16"], br, 0, 0, bfu)[0]
+        out[f"row_{br}_stress_frames"] = codec.encode(pcm["stress_20"], br)[0]
+    out["flatness_out"] = np.stack([codec.flatness(e) for e in flatness_in])
+    out["log2f_out"] = np.array([codec.log2f(v) for v in log2f_in], dtype=np.float32)
+    return out

@@ -775,20 +775,22 @@ def test_bench_contract_and_two_context_paths(tmp_path):
 
 @pytest.mark.parametrize("launch", ["one_process", "ranks"])
 def test_eight_context_readiness(launch):
-    """What runs the day an 8-GPU node is available, on this box's single GPU through --device-map 0,0,0,0,0,0,0,0: bench.py
-    --gpus 8 as ONE process (eight contexts, eight host threads, the one_gpu_same_workload regions, the replay of every context's
-    call sequence) and as eight torch.distributed.run ranks (gloo barrier, MAX of the elapsed time, checksums gathered). Every
-    context checks its own shard against the oracle and replays its own sequence; eight seeds give eight distinct checksums."""
+    """What runs the day an 8-GPU node is available, on this box's single GPU through --device-map: bench.py --gpus 8 as ONE
+    process (eight contexts, eight host threads, the one_gpu_same_workload regions, the replay of every context's call sequence)
+    and as torch.distributed.run ranks (gloo barrier, MAX of the elapsed time, checksums gathered). Every context checks its own
+    shard against the oracle and replays its own sequence; distinct seeds give distinct checksums. The ranks are four, not eight:
+    on one shared device no more than six processes may hold it at once, and this test's own process is one of them."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     bench = os.path.join(root, "bench.py")
-    tail = [bench, "--gpus", "8", "--device-map", "0,0,0,0,0,0,0,0", "--steps", "3", "--warmup", "1", "--streams", "64", "--frames", "16",
+    n = 8 if launch == "one_process" else 4
+    tail = [bench, "--gpus", str(n), "--device-map", ",".join(["0"] * n), "--steps", "3", "--warmup", "1", "--streams", "64", "--frames", "16",
             "--regions", "1", "--region-ms", "1", "--no-side-workloads", "--no-cpu-baseline"]
     cmd = [sys.executable] + tail if launch == "one_process" else \
-        [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", "29541"] + tail
+        [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", "29541"] + tail
     def run_once(port):
         c = [a if a != "29541" else str(port) for a in cmd]
         r = subprocess.run(c, capture_output=True, text=True, cwd=root, timeout=900)
@@ -797,16 +799,16 @@ def test_eight_context_readiness(launch):
         assert len(lines) == 1, r.stdout[-2000:]
         return json.loads(lines[0])
     d = run_once(29541)
-    assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["config"]["frames_per_step_all_gpus"] == 8 * 64 * 16
+    assert d["n_gpus"] == n and d["scaling"] == "weak" and d["config"]["frames_per_step_all_gpus"] == n * 64 * 16
     assert d["parity_in_run"] is True
     ctx = d["contexts"]
-    assert len(ctx) == 8 and all(c["ok"] and c["parity_check"]["mismatching_frames"] == 0 for c in ctx)
+    assert len(ctx) == n and all(c["ok"] and c["parity_check"]["mismatching_frames"] == 0 for c in ctx)
     assert all(c["parity_check"]["timed_sequence_replayed_identically"] is True for c in ctx)
-    assert len({c["seed"] for c in ctx}) == 8 and len({c["checksum"] for c in ctx}) == 8
+    assert len({c["seed"] for c in ctx}) == n and len({c["checksum"] for c in ctx}) == n
     if launch == "one_process":
-        assert d["one_gpu_same_workload"]["value"] > 1e5 and sorted(c["rank"] for c in ctx) == [0] * 8
+        assert d["one_gpu_same_workload"]["value"] > 1e5 and sorted(c["rank"] for c in ctx) == [0] * n
     else:
-        assert sorted(c["rank"] for c in ctx) == list(range(8))
+        assert sorted(c["rank"] for c in ctx) == list(range(n))
 
 
 def wild_spread_pcm(nb, seed):

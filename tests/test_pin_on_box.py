@@ -1,13 +1,25 @@
 """The oracle's pin, re-verified ON THE MACHINE THAT MEASURES: a slice of test_oracle_vs_ref.py / test_oracle_golden.py
 marked `gpu` so that the driver's `-m gpu` run proves, on the GPU box (whose libm builds the product's tables at
-at3hip_create), that oracle == reference build (oracle/_ref, travels as a prebuilt .so) == committed golden vectors, and
-that the PRODUCT's host-built tables equal the reference's. The full matrices stay in the CPU suite."""
+at3hip_create), that oracle == the reference's outputs for that slice (tests/golden/pin.npz, written from the reference
+build by tools/gen_golden_pin.py) == committed golden vectors, and that the PRODUCT's host-built tables equal the
+reference's. The full matrices stay in the CPU suite."""
 import numpy as np
 import pytest
 
-from at3_testlib import LP2, LP4, SIGNALS, TAP_DTYPE, have_ref, pcm_stress, ref
+from at3_testlib import LP2, LP4, PIN_CONTAINER_BFUS, PIN_CONTAINER_ROWS, PIN_OPTION_BLOCKS, PIN_OPTION_SETS, PIN_PATH, TAP_DTYPE, have_ref, \
+    pin_outputs, ref
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def pin():
+    return np.load(PIN_PATH)
+
+
+@pytest.fixture(scope="module")
+def oracle_pin(oracle, pin):
+    return pin_outputs(oracle, pin["flatness_in"], pin["log2f_in"])
 
 
 def bits(a):
@@ -15,8 +27,16 @@ def bits(a):
     return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
-def test_reference_build_travelled():
-    assert have_ref(), "oracle/_ref/libat3ref.so is missing on this box: the oracle's pin cannot be re-verified here"
+def test_pin_inputs_reproduce_and_match_reference(oracle_pin, pin):
+    """The PCM the pin's encodes run on is regenerated here bit for bit as the fixture was written from it, and where the
+    reference build is present its outputs are still the stored ones."""
+    for k in pin.files:
+        if k.startswith("pcm_"):
+            assert np.array_equal(oracle_pin[k], pin[k]), k
+    if have_ref():
+        now = pin_outputs(ref(), pin["flatness_in"], pin["log2f_in"])
+        for k, v in now.items():
+            assert np.array_equal(v, pin[k]), k
 
 
 def test_oracle_tables_equal_golden(oracle, golden_stages):
@@ -50,37 +70,28 @@ def test_product_tables_equal_golden(golden_stages):
 
 
 @pytest.mark.parametrize("br", [LP2, LP4])
-def test_oracle_equals_reference_option_sets(oracle, br):
+def test_oracle_equals_reference_option_sets(oracle_pin, pin, br):
     """One signal per option set (frames and stage taps), as test_oracle_vs_ref.py::test_frames_and_taps does for all."""
-    r = ref()
-    for name, (ng, nt) in zip(("mix", "burst", "tones", "noise"), ((0, 0), (1, 0), (0, 1), (1, 1))):
-        pcm = SIGNALS[name](24)
-        fo, to = oracle.encode(pcm, br, ng, nt, taps=True)
-        fr, tr = r.encode(pcm, br, ng, nt, taps=True)
-        assert np.array_equal(fo, fr), (name, ng, nt)
+    for name, ng, nt in PIN_OPTION_SETS:
+        key = f"opt_{br}_{name}"
+        assert np.array_equal(oracle_pin[f"{key}_frames"], pin[f"{key}_frames"]), (name, ng, nt)
+        assert pin[f"{key}_frames"].shape[0] == PIN_OPTION_BLOCKS - 1
         for k in TAP_DTYPE.names:
             if k != "tonal_pos":
-                assert np.array_equal(bits(to[k]), bits(tr[k])), (name, k)
+                assert np.array_equal(oracle_pin[f"{key}_tap_{k}"], pin[f"{key}_tap_{k}"]), (name, k)
 
 
-def test_oracle_equals_reference_container_rows(oracle):
-    r = ref()
-    pcm = SIGNALS["mix"](16)
-    stress = pcm_stress(20)
-    for br, fsz in ((66150, 192), (93713, 272), (104738, 304), (132300, 384), (146081, 424), (176400, 512), (264600, 768), (352800, 1024)):
-        for bfu in (0, 8):
-            fo, fr = oracle.encode(pcm, br, 0, 0, bfu)[0], r.encode(pcm, br, 0, 0, bfu)[0]
+def test_oracle_equals_reference_container_rows(oracle_pin, pin):
+    for br, fsz in PIN_CONTAINER_ROWS:
+        for bfu in PIN_CONTAINER_BFUS:
+            fo, fr = oracle_pin[f"row_{br}_bfu{bfu}_frames"], pin[f"row_{br}_bfu{bfu}_frames"]
             assert fo.shape == (15, fsz) and np.array_equal(fo, fr), (br, bfu)
-        assert np.array_equal(oracle.encode(stress, br)[0], r.encode(stress, br)[0]), br
+        assert np.array_equal(oracle_pin[f"row_{br}_stress_frames"], pin[f"row_{br}_stress_frames"]), br
 
 
-def test_oracle_equals_reference_flatness_and_log2f(oracle):
+def test_oracle_equals_reference_flatness_and_log2f(oracle_pin, pin):
     """The two libm-dependent stage functions (std::log / std::exp in CalcSpectralFlatnessPerBfu, std::log2(float)) on this
-    box's libm: oracle (which calls libm for the first and restates the second) against the reference build."""
-    rng = np.random.RandomState(17)
-    r = ref()
-    for scale in (1.0, 1e-3, 1e-6):
-        e = (rng.uniform(0, 1, 1024) ** 4 * scale).astype(np.float32)
-        assert np.array_equal(bits(oracle.flatness(e)), bits(r.flatness(e)))
-    x = np.exp(rng.uniform(-20, 20, 5000)).astype(np.float32)
-    assert all(np.float32(oracle.log2f(v)).view(np.uint32) == np.float32(r.log2f(v)).view(np.uint32) for v in x)
+    box's libm: oracle (which calls libm for the first and restates the second) against the reference's outputs."""
+    assert pin["flatness_in"].shape == (3, 1024) and pin["log2f_in"].shape == (5000,)
+    assert np.array_equal(bits(oracle_pin["flatness_out"]), bits(pin["flatness_out"]))
+    assert np.array_equal(bits(oracle_pin["log2f_out"]), bits(pin["log2f_out"]))
