@@ -15,7 +15,7 @@ AT3HIP_ASYNC = 4
 OPT_RUNS, OPT_LITERAL_FORMS, OPT_QUANT_TAP, OPT_GAIN_FORM, OPT_GAIN_WGS_PER_CU, OPT_CHAIN, OPT_TIMING_EVERY = 1, 2, 3, 4, 5, 6, 7
 OPT_FLATNESS_LITERAL = OPT_LITERAL_FORMS           # (former name, same number)
 GAIN_FORM_TWO_WAVES, GAIN_FORM_ONE_WAVE = 0, 1
-AT3HIP_VERSION = (1 << 16) | 5                     # include/at3hip.h this stub mirrors: load_library refuses an older library
+AT3HIP_VERSION = (1 << 16) | 6                     # include/at3hip.h this stub mirrors: load_library refuses an older library
 TAP_SPECTRA, TAP_CURVES, TAP_ENERGY_SCALE, TAP_PSY, TAP_LOUDNESS, TAP_QUANT, TAP_CLOCK, TAP_GAIN_ANALYSIS = 1, 2, 3, 4, 5, 6, 7, 8
 LP2 = 132300
 LP4 = 66150
@@ -46,7 +46,11 @@ SYMBOLS = ["at3hip_encode_s16", "at3hip_create", "at3hip_destroy", "at3hip_frame
            "at3hip_host_free", "at3hip_wait_input", "at3hip_wait_frames", "at3hip_get_counters", "at3hip_device_numa_node"]
 # include/at1hip.h
 AT1_SYMBOLS = ["at1hip_create", "at1hip_destroy", "at1hip_last_error", "at1hip_encode", "at1hip_reset", "at1hip_get_timings",
-               "at1hip_read_tap", "at1hip_host_tables", "at1hip_sync"]
+               "at1hip_read_tap", "at1hip_host_tables", "at1hip_sync",
+               # the decoder (ABI 1.6)
+               "at1hip_decoder_create", "at1hip_decoder_destroy", "at1hip_decoder_last_error", "at1hip_decode", "at1hip_decoder_sync",
+               "at1hip_decoder_reset", "at1hip_decoder_get_counters", "at1hip_decoder_set_stream"]
+AT1HIP_DECODE_S16 = 8
 # include/at3phip.h
 AT3P_SYMBOLS = ["at3phip_create", "at3phip_destroy", "at3phip_last_error", "at3phip_reset", "at3phip_pqf_analyse", "at3phip_mdct",
                 "at3phip_pqf_mdct", "at3phip_get_timings", "at3phip_host_tables", "at3phip_write_frames", "at3phip_encode_frames",
@@ -60,6 +64,14 @@ class At1Config(ctypes.Structure):
 
 class At3pConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("channels", "n_streams", "max_frames", "device_id")]
+
+
+class At1DecoderConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("channels", "n_streams", "max_frames", "device_id")]
+
+
+class At1DecoderCounters(ctypes.Structure):
+    _fields_ = [("bad_block_size", ctypes.c_uint64), ("read_past_end", ctypes.c_uint64)]
 
 
 class At1Timings(ctypes.Structure):
@@ -143,6 +155,16 @@ def load_library(path=None):
     lib.at1hip_get_timings.argtypes = [vp, ctypes.POINTER(At1Timings)]
     lib.at1hip_read_tap.argtypes = [vp, i32, vp, ctypes.c_size_t]
     lib.at1hip_host_tables.argtypes = [vp, ctypes.c_size_t]
+    lib.at1hip_decoder_create.argtypes = [ctypes.POINTER(At1DecoderConfig), ctypes.POINTER(vp)]
+    lib.at1hip_decoder_destroy.argtypes = [vp]
+    lib.at1hip_decoder_destroy.restype = None
+    lib.at1hip_decoder_last_error.argtypes = [vp]
+    lib.at1hip_decoder_last_error.restype = ctypes.c_char_p
+    lib.at1hip_decode.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
+    lib.at1hip_decoder_sync.argtypes = [vp]
+    lib.at1hip_decoder_reset.argtypes = [vp]
+    lib.at1hip_decoder_get_counters.argtypes = [vp, ctypes.POINTER(At1DecoderCounters), i32]
+    lib.at1hip_decoder_set_stream.argtypes = [vp, vp]
     lib.at3phip_create.argtypes = [ctypes.POINTER(At3pConfig), ctypes.POINTER(vp)]
     lib.at3phip_destroy.argtypes = [vp]
     lib.at3phip_destroy.restype = None
@@ -449,6 +471,86 @@ class At1Hip:
         t = At1Timings()
         self._check(self.lib.at1hip_get_timings(self.ctx, ctypes.byref(t)), "at1hip_get_timings")
         return {n: getattr(t, n) for n, _ in At1Timings._fields_}
+
+
+class At1HipDecoder:
+    """n_streams TAtrac1Decoder objects decoded side by side on one GPU (include/at1hip.h, the decoder section)."""
+
+    FRAME = 212
+
+    def __init__(self, n_streams=1, max_frames=256, channels=2, device_id=0, lib_path=None):
+        self.lib = load_library(lib_path)
+        self.channels, self.n_streams, self.max_frames = int(channels), int(n_streams), int(max_frames)
+        self.cfg = At1DecoderConfig(self.channels, self.n_streams, self.max_frames, int(device_id))
+        self.ctx = ctypes.c_void_p()
+        rc = self.lib.at1hip_decoder_create(ctypes.byref(self.cfg), ctypes.byref(self.ctx))
+        if rc != 0:
+            self.ctx = None
+            raise At3HipError(f"at1hip_decoder_create failed with {rc} (bad configuration, or no usable MI355X / HIP runtime)")
+
+    def close(self):
+        if getattr(self, "ctx", None):
+            self.lib.at1hip_decoder_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise At3HipError(f"{what} failed ({rc}): {self.lib.at1hip_decoder_last_error(self.ctx).decode()}")
+
+    def reset(self):
+        self._check(self.lib.at1hip_decoder_reset(self.ctx), "at1hip_decoder_reset")
+
+    def decode(self, units, s16=False):
+        """units uint8 [n_streams, n_frames, channels, 212] (host) -> float32 (int16 with s16) [n_streams, n_frames, 512, channels]."""
+        units = np.ascontiguousarray(units, dtype=np.uint8)
+        assert units.ndim == 4 and units.shape[0] == self.n_streams and units.shape[2:] == (self.channels, self.FRAME), units.shape
+        n = units.shape[1]
+        out = np.zeros((self.n_streams, n, 512, self.channels), dtype=np.int16 if s16 else np.float32)
+        self._check(self.lib.at1hip_decode(self.ctx, _vp(units), n, _vp(out), AT1HIP_DECODE_S16 if s16 else 0), "at1hip_decode")
+        return out
+
+    def decode_device(self, units, out, asynchronous=False, ordered=True):
+        """Torch tensors on this decoder's device: units uint8 [n_streams, n, channels, 212] -> out float32 / int16 (s16 output)
+        [n_streams, n, 512, channels]. By default the call is queued on torch's current stream, behind whatever filled `units`
+        there (at1hip_decoder_set_stream; on torch's null default stream the call waits for it instead), and whatever torch queues
+        there afterwards follows it (with asynchronous=True and the null stream: after sync()). ordered=False runs it on the
+        decoder's own non-blocking stream: the caller must then make sure `units` is complete (the caller's race of
+        at3hip.h's DEVICE BUFFERS AND STREAMS)."""
+        import torch
+        assert units.dtype == torch.uint8 and units.is_contiguous() and out.is_contiguous()
+        assert out.dtype in (torch.float32, torch.int16)
+        n = units.shape[1]
+        assert tuple(units.shape) == (self.n_streams, n, self.channels, self.FRAME), tuple(units.shape)
+        assert tuple(out.shape) == (self.n_streams, n, 512, self.channels), tuple(out.shape)
+        flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT1HIP_DECODE_S16 if out.dtype == torch.int16 else 0)
+        flags |= AT3HIP_ASYNC if asynchronous else 0
+        stream = None
+        if ordered:
+            cur = torch.cuda.current_stream(units.device)
+            stream = cur.cuda_stream or None
+            if stream is None:
+                # torch's default stream is the null stream, whose handle (0) means "the decoder's own stream" to
+                # at1hip_decoder_set_stream; the decoder's stream is non-blocking: wait for what torch queued instead
+                cur.synchronize()
+        self._check(self.lib.at1hip_decoder_set_stream(self.ctx, ctypes.c_void_p(stream)), "at1hip_decoder_set_stream")
+        self._check(self.lib.at1hip_decode(self.ctx, ctypes.c_void_p(units.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), flags),
+                    "at1hip_decode")
+
+    def decode_ptr(self, units_ptr, n_frames, out_ptr, flags):
+        """Raw pointers and at1hip_decode flags (benchmarks)."""
+        self._check(self.lib.at1hip_decode(self.ctx, ctypes.c_void_p(units_ptr), int(n_frames), ctypes.c_void_p(out_ptr), int(flags)),
+                    "at1hip_decode")
+
+    def sync(self):
+        self._check(self.lib.at1hip_decoder_sync(self.ctx), "at1hip_decoder_sync")
+
+    def counters(self, reset=False):
+        c = At1DecoderCounters()
+        self._check(self.lib.at1hip_decoder_get_counters(self.ctx, ctypes.byref(c), int(bool(reset))), "at1hip_decoder_get_counters")
+        return {"bad_block_size": int(c.bad_block_size), "read_past_end": int(c.read_past_end)}
 
 
 AT3PHIP_RESIDUAL_SCALE = 16

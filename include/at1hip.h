@@ -1,4 +1,4 @@
-/* at1hip.h - C ABI of the MI355X-native ATRAC1 encode path.
+/* at1hip.h - C ABI of the MI355X-native ATRAC1 encode path and of its decoder (below).
  *
  * Drop-in boundary: what a host shim inside the reference binds in place of the body of the lambda returned by
  * TAtrac1Encoder::GetLambda (atrac1denc.cpp:180-255) - per 512-sample block and channel: analysis filter bank,
@@ -85,6 +85,63 @@ int at1hip_read_tap(at1hip_ctx* ctx, int32_t kind, void* dst, size_t bytes);
  * at1_tables.hpp layout (AT1HIP_TABLES_BYTES). */
 #define AT1HIP_TABLES_BYTES 6904
 int at1hip_host_tables(void* dst, size_t bytes);
+
+/* ---- decoder ---------------------------------------------------------------------------------------------------------------
+ * Drop-in boundary of the reference's `-d` path (main.cpp:343-365): TAtrac1Decoder (atrac1denc.cpp:46-49, 139-177) - per 512-sample
+ * block and channel: bit unpack and dequantisation (TBlockSizeMod::Parse, atrac1.cpp:37-53; TAtrac1Dequantiser::Dequant,
+ * atrac1_dequantiser.cpp:31-72), block-switched IMDCT (TAtrac1MDCT::IMdct, atrac1denc.cpp:103-137), the synthesis filter bank
+ * (Atrac1SynthesisFilterBank::Synthesis, atrac1_qmf.h:46-64) and the clamp to [-1, 1] - for a batch of independent streams, every
+ * frame of a call in parallel. Reading the AEA container (aea.cpp) stays on the host. Bit-identical to the reference. */
+typedef struct at1hip_decoder at1hip_decoder;
+
+typedef struct at1hip_decoder_config {
+    int32_t channels;    /* 1 or 2 (Aea->GetChannelNum()) */
+    int32_t n_streams;   /* independent audio streams decoded side by side */
+    int32_t max_frames;  /* upper bound of frames (one sound unit per channel each) per stream per at1hip_decode call */
+    int32_t device_id;
+} at1hip_decoder_config;
+
+/* Replaces: TAtrac1Decoder::TAtrac1Decoder(TCompressedInputPtr&&) (atrac1denc.cpp:46-49) for n_streams decoders at once.
+ * The context's stream is non-blocking; see DEVICE BUFFERS AND STREAMS in at3hip.h and at1hip_decoder_set_stream. */
+int at1hip_decoder_create(const at1hip_decoder_config* cfg, at1hip_decoder** out);
+void at1hip_decoder_destroy(at1hip_decoder* dec);
+const char* at1hip_decoder_last_error(const at1hip_decoder* dec);
+
+/* 16-bit output: lrintf(x * 32767.0f) of each clamped sample, the float -> PCM_16 conversion with normalisation the reference's
+ * writer leaves to libsndfile (pcm_io_sndfile.cpp:56,114) - a restatement that is not pinned against libsndfile here. */
+#define AT1HIP_DECODE_S16 8u
+
+/* Replaces: n_frames invocations of the lambda of TAtrac1Decoder::GetLambda per stream.
+ *   units [n_streams][n_frames][channels][212] bytes: the frames TAeaInput::ReadFrame delivers, in its order (channel 0 then
+ *         channel 1 of each frame, atrac1denc.cpp:143-145)
+ *   pcm   [n_streams][n_frames][512][channels]: float32 (the lambda's `data`, atrac1denc.cpp:166-173), or int16 with
+ *         AT1HIP_DECODE_S16
+ * flags: AT3HIP_PCM_ON_DEVICE (units are device memory), AT3HIP_OUT_ON_DEVICE (pcm is device memory), AT3HIP_ASYNC (only queue
+ * the call: buffers stay valid until at1hip_decoder_sync), AT1HIP_DECODE_S16. Stream state (the IMDCT overlap, the band buffers,
+ * the filter bank's histories and delay line) carries across calls. A malformed unit - a block-size field that makes a LogCount
+ * negative, or an allocation that reads past the unit's 1696 bits - decodes as a zero spectrum with all bands long, as the
+ * reference's catch does; it is counted (at1hip_decoder_get_counters). */
+int at1hip_decode(at1hip_decoder* dec, const uint8_t* units, int32_t n_frames, void* pcm, uint32_t flags);
+
+/* Waits for everything queued on the decoder. */
+int at1hip_decoder_sync(at1hip_decoder* dec);
+
+/* Back to start-of-stream state for every stream (a fresh TAtrac1Decoder); zeroes the counters. */
+int at1hip_decoder_reset(at1hip_decoder* dec);
+
+/* Units the reference would have rejected with one "Skipping invalid ATRAC1 frame: <what>" line on stderr
+ * (atrac1denc.cpp:154-162), summed over streams and channels since create / reset / the last call with reset = 1. Waits for
+ * queued work. */
+typedef struct at1hip_decoder_counters {
+    uint64_t bad_block_size;   /* "invalid ATRAC1 block size mode" */
+    uint64_t read_past_end;    /* "read past the end of the bitstream" */
+} at1hip_decoder_counters;
+int at1hip_decoder_get_counters(at1hip_decoder* dec, at1hip_decoder_counters* out, int32_t reset);
+
+/* Queue this decoder's work on a caller-provided hipStream_t (NULL = the decoder's own stream): every call is then ordered
+ * behind whatever the caller queued there before it (e.g. the kernel that fills `units`), and work the caller queues there
+ * afterwards follows it. Waits for the decoder's queued work first. The stream must outlive its last call's completion. */
+int at1hip_decoder_set_stream(at1hip_decoder* dec, void* hip_stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -296,10 +296,12 @@ int at3hip_host_tables(void* dst, size_t bytes);
  *        wavefronts per item, 1 = the one-wavefront form, formerly 2 - the legacy value 2 is still accepted and means ONE_WAVE)
  *   1.4  AT3HIP_OPT_CHAIN, at3hip_device_numa_node
  *   1.5  AT3HIP_OPT_TIMING_EVERY
+ *   1.6  the ATRAC1 decoder (at1hip.h): at1hip_decoder_create / _destroy / _last_error / _sync / _reset / _get_counters /
+ *        _set_stream, at1hip_decode, AT1HIP_DECODE_S16
  * A host layer compiled against this header checks at3hip_version() >= AT3HIP_VERSION before it relies on them
  * (atracdenc_amd/host/at3hip_host.hpp and the ctypes stub do). */
 #define AT3HIP_VERSION_MAJOR 1
-#define AT3HIP_VERSION_MINOR 5
+#define AT3HIP_VERSION_MINOR 6
 #define AT3HIP_VERSION ((AT3HIP_VERSION_MAJOR << 16) | AT3HIP_VERSION_MINOR)
 uint32_t at3hip_version(void);
 

@@ -40,6 +40,10 @@ struct uint4 {
     unsigned x, y, z, w;
 };
 static inline uint2 make_uint2(unsigned x, unsigned y) { uint2 r; r.x = x; r.y = y; return r; }
+struct int4 {
+    int x, y, z, w;
+};
+static inline int4 make_int4(int x, int y, int z, int w) { int4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
 
 extern dim3 threadIdx, blockIdx, blockDim, gridDim;
 
