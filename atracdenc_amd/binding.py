@@ -43,7 +43,11 @@ SYMBOLS = ["at3hip_encode_s16", "at3hip_create", "at3hip_destroy", "at3hip_frame
            "at3hip_encode", "at3hip_reset", "at3hip_mdct", "at3hip_qmf_mdct", "at3hip_get_timings",
            "at3hip_set_stream", "at3hip_version", "at3hip_sync", "at3hip_get_timings_ago", "at3hip_read_tap",
            "at3hip_mdct_levels", "at3hip_gain_energy_scale", "at3hip_set_option", "at3hip_host_tables", "at3hip_host_alloc",
-           "at3hip_host_free", "at3hip_wait_input", "at3hip_wait_frames", "at3hip_get_counters", "at3hip_device_numa_node"]
+           "at3hip_host_free", "at3hip_wait_input", "at3hip_wait_frames", "at3hip_get_counters", "at3hip_device_numa_node",
+           # the ATRAC3 decoder
+           "at3hip_decoder_create", "at3hip_decoder_destroy", "at3hip_decoder_last_error", "at3hip_decode", "at3hip_decoder_sync",
+           "at3hip_decoder_reset", "at3hip_decoder_get_counters", "at3hip_decoder_set_stream"]
+AT3HIP_DECODE_S16 = 8
 # include/at1hip.h
 AT1_SYMBOLS = ["at1hip_create", "at1hip_destroy", "at1hip_last_error", "at1hip_encode", "at1hip_reset", "at1hip_get_timings",
                "at1hip_read_tap", "at1hip_host_tables", "at1hip_sync",
@@ -72,6 +76,17 @@ class At1DecoderConfig(ctypes.Structure):
 
 class At1DecoderCounters(ctypes.Structure):
     _fields_ = [("bad_block_size", ctypes.c_uint64), ("read_past_end", ctypes.c_uint64)]
+
+
+class At3DecoderConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_streams", "frame_size", "joint_stereo", "max_frames", "device_id")]
+
+
+AT3_DECODER_REASONS = ("bad_id", "unsupported_js", "read_past_end", "tonal_past_end", "bad_tonal_mode", "bad_tonal_quant")
+
+
+class At3DecoderCounters(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in AT3_DECODER_REASONS]
 
 
 class At1Timings(ctypes.Structure):
@@ -165,6 +180,17 @@ def load_library(path=None):
     lib.at1hip_decoder_reset.argtypes = [vp]
     lib.at1hip_decoder_get_counters.argtypes = [vp, ctypes.POINTER(At1DecoderCounters), i32]
     lib.at1hip_decoder_set_stream.argtypes = [vp, vp]
+    if hasattr(lib, "at3hip_decoder_create"):   # the ATRAC3 decoder (added under ABI 1.6, see at3hip.h's version list)
+        lib.at3hip_decoder_create.argtypes = [ctypes.POINTER(At3DecoderConfig), ctypes.POINTER(vp)]
+        lib.at3hip_decoder_destroy.argtypes = [vp]
+        lib.at3hip_decoder_destroy.restype = None
+        lib.at3hip_decoder_last_error.argtypes = [vp]
+        lib.at3hip_decoder_last_error.restype = ctypes.c_char_p
+        lib.at3hip_decode.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
+        lib.at3hip_decoder_sync.argtypes = [vp]
+        lib.at3hip_decoder_reset.argtypes = [vp]
+        lib.at3hip_decoder_get_counters.argtypes = [vp, ctypes.POINTER(At3DecoderCounters), i32]
+        lib.at3hip_decoder_set_stream.argtypes = [vp, vp]
     lib.at3phip_create.argtypes = [ctypes.POINTER(At3pConfig), ctypes.POINTER(vp)]
     lib.at3phip_destroy.argtypes = [vp]
     lib.at3phip_destroy.restype = None
@@ -551,6 +577,83 @@ class At1HipDecoder:
         c = At1DecoderCounters()
         self._check(self.lib.at1hip_decoder_get_counters(self.ctx, ctypes.byref(c), int(bool(reset))), "at1hip_decoder_get_counters")
         return {"bad_block_size": int(c.bad_block_size), "read_past_end": int(c.read_past_end)}
+
+
+class At3HipDecoder:
+    """n_streams ATRAC3 streams of one container row decoded side by side on one GPU (include/at3hip.h, the decoder section)."""
+
+    ROWS = {192: True, 272: True, 304: False, 384: False, 424: False, 512: False, 768: False, 1024: False}
+
+    def __init__(self, n_streams=1, frame_size=384, joint_stereo=None, max_frames=256, device_id=0, lib_path=None):
+        self.lib = load_library(lib_path)
+        if not hasattr(self.lib, "at3hip_decoder_create"):
+            raise At3HipError("libat3hip.so predates the ATRAC3 decoder (no at3hip_decoder_create): rebuild it")
+        self.n_streams, self.frame_size, self.max_frames = int(n_streams), int(frame_size), int(max_frames)
+        self.joint_stereo = bool(self.ROWS.get(self.frame_size, False) if joint_stereo is None else joint_stereo)
+        self.cfg = At3DecoderConfig(self.n_streams, self.frame_size, int(self.joint_stereo), self.max_frames, int(device_id))
+        self.ctx = ctypes.c_void_p()
+        rc = self.lib.at3hip_decoder_create(ctypes.byref(self.cfg), ctypes.byref(self.ctx))
+        if rc != 0:
+            self.ctx = None
+            raise At3HipError(f"at3hip_decoder_create failed with {rc} (bad configuration, or no usable MI355X / HIP runtime)")
+
+    def close(self):
+        if getattr(self, "ctx", None):
+            self.lib.at3hip_decoder_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise At3HipError(f"{what} failed ({rc}): {self.lib.at3hip_decoder_last_error(self.ctx).decode()}")
+
+    def reset(self):
+        self._check(self.lib.at3hip_decoder_reset(self.ctx), "at3hip_decoder_reset")
+
+    def decode(self, frames, s16=False):
+        """frames uint8 [n_streams, n_frames, frame_size] (host) -> float32 (int16 with s16) [n_streams, n_frames, 1024, 2]."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        assert frames.ndim == 3 and frames.shape[0] == self.n_streams and frames.shape[2] == self.frame_size, frames.shape
+        n = frames.shape[1]
+        out = np.zeros((self.n_streams, n, 1024, 2), dtype=np.int16 if s16 else np.float32)
+        self._check(self.lib.at3hip_decode(self.ctx, _vp(frames), n, _vp(out), AT3HIP_DECODE_S16 if s16 else 0), "at3hip_decode")
+        return out
+
+    def decode_device(self, frames, out, asynchronous=False, ordered=True):
+        """Torch tensors on this decoder's device: frames uint8 [n_streams, n, frame_size] -> out float32 / int16 (s16 output)
+        [n_streams, n, 1024, 2]. Ordered behind torch's current stream by default, as At1HipDecoder.decode_device."""
+        import torch
+        assert frames.dtype == torch.uint8 and frames.is_contiguous() and out.is_contiguous()
+        assert out.dtype in (torch.float32, torch.int16)
+        n = frames.shape[1]
+        assert tuple(frames.shape) == (self.n_streams, n, self.frame_size), tuple(frames.shape)
+        assert tuple(out.shape) == (self.n_streams, n, 1024, 2), tuple(out.shape)
+        flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_DECODE_S16 if out.dtype == torch.int16 else 0)
+        flags |= AT3HIP_ASYNC if asynchronous else 0
+        stream = None
+        if ordered:
+            cur = torch.cuda.current_stream(frames.device)
+            stream = cur.cuda_stream or None
+            if stream is None:
+                cur.synchronize()   # the null stream: the decoder's own stream is non-blocking, wait instead
+        self._check(self.lib.at3hip_decoder_set_stream(self.ctx, ctypes.c_void_p(stream)), "at3hip_decoder_set_stream")
+        self._check(self.lib.at3hip_decode(self.ctx, ctypes.c_void_p(frames.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), flags),
+                    "at3hip_decode")
+
+    def decode_ptr(self, frames_ptr, n_frames, out_ptr, flags):
+        """Raw pointers and at3hip_decode flags (benchmarks)."""
+        self._check(self.lib.at3hip_decode(self.ctx, ctypes.c_void_p(frames_ptr), int(n_frames), ctypes.c_void_p(out_ptr), int(flags)),
+                    "at3hip_decode")
+
+    def sync(self):
+        self._check(self.lib.at3hip_decoder_sync(self.ctx), "at3hip_decoder_sync")
+
+    def counters(self, reset=False):
+        c = At3DecoderCounters()
+        self._check(self.lib.at3hip_decoder_get_counters(self.ctx, ctypes.byref(c), int(bool(reset))), "at3hip_decoder_get_counters")
+        return {n: int(getattr(c, n)) for n in AT3_DECODER_REASONS}
 
 
 AT3PHIP_RESIDUAL_SCALE = 16

@@ -11,6 +11,8 @@
 //             [--batch frames] [--device n]
 //   at3hipenc -d -i in.aea -o out.wav [--nostdout] [--batch frames] [--device n]
 //             the reference's ATRAC1 decode path (main.cpp:343-365, 697-705) on the GPU decoder (at1hip.h)
+//   at3hipenc -d -i in.{oma|at3|wav} -o out.wav [--nostdout] [--batch frames] [--device n]
+//             ATRAC3 in an OMA container or in RIFF/WAVE (format 0x270), chosen by content, on the GPU decoder (at3hip.h)
 //
 // File-level behaviour follows the reference: 44.1 kHz input only, numFrames estimate = samples / 1024 in the
 // container header, the look-ahead first call, the drain call at end of input.
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "../../include/at1hip.h"
+#include "../../include/at3hip.h"
 #include "at3hip_io.hpp"
 
 using namespace NAtracDEncHip;
@@ -160,6 +163,189 @@ int decode_aea(const std::string& inFile, const std::string& outFile, bool noStd
     return 0;
 }
 
+// `-d` on an ATRAC3 file: the container is recognised by content, as this repository's writers (at3hip_io.hpp) write it.
+//  * OMA: "EA3" header of 96 bytes; the big-endian codec word at byte 32 holds the codec id (0 = ATRAC3, 1 = ATRAC3plus) in its
+//    top byte, the joint-stereo flag in bit 17 and FrameSz / 8 in its low 10 bits; the frames follow.
+//  * RIFF/WAVE with format tag 0x270: block_align is the frame size, the joint-stereo flag is the extradata's fifth 16-bit
+//    word; the frames are the "data" chunk.
+// Anything else goes to the AEA path unchanged, except ATRAC3plus (OMA codec id 1, RIFF 0xFFFE) and headerless ATRAC3 (the
+// first byte carries the 6-bit unit id 0x28), which are refused. The output is a 16-bit stereo WAV written as the AEA path
+// writes it, 1024 samples per frame, the codec delay not trimmed; rejected units are counted and reported per reason.
+enum class EInput { AEA, ATRAC3, REFUSED };
+
+struct TAt3Input {
+    int64_t offset = 0, frames = 0;
+    int frameSize = 0, js = 0;
+    std::string container;
+};
+
+uint32_t le(const uint8_t* p, int bytes)
+{
+    uint32_t v = 0;
+    for (int i = bytes - 1; i >= 0; --i) v = (v << 8) | p[i];
+    return v;
+}
+
+bool at3_row(int frameSize, int js)
+{
+    static const int rows[8][2] = {{192, 1}, {272, 1}, {304, 0}, {384, 0}, {424, 0}, {512, 0}, {768, 0}, {1024, 0}};
+    for (const auto& r : rows)
+        if (r[0] == frameSize && r[1] == js) return true;
+    return false;
+}
+
+EInput probe_input(const std::string& inFile, TAt3Input& at3)
+{
+    std::ifstream in(inFile, std::ios::binary);
+    if (!in) return EInput::AEA;   // the AEA path reports it
+    uint8_t h[4096] = {0};
+    in.read((char*)h, sizeof(h));
+    const int64_t got = in.gcount();
+    in.clear();
+    in.seekg(0, std::ios::end);
+    const int64_t fileSize = (int64_t)in.tellg();
+    if (got >= 96 && !memcmp(h, "EA3", 3)) {
+        const uint32_t word = (uint32_t)h[32] << 24 | (uint32_t)h[33] << 16 | (uint32_t)h[34] << 8 | h[35];
+        const uint32_t id = word >> 24;
+        if (id == 1) {
+            std::cerr << "Fatal error: ATRAC3plus decoding is not supported" << std::endl;
+            return EInput::REFUSED;
+        }
+        if (id != 0) {
+            std::cerr << "Fatal error: OMA codec id " << id << " is not ATRAC3" << std::endl;
+            return EInput::REFUSED;
+        }
+        at3.container = "OMA";
+        at3.offset = 96;
+        at3.frameSize = (int)(word & 0x3FF) * 8;
+        at3.js = (int)((word >> 17) & 1);
+        at3.frames = at3.frameSize ? (fileSize - 96) / at3.frameSize : 0;
+    } else if (got >= 12 && !memcmp(h, "RIFF", 4) && !memcmp(h + 8, "WAVE", 4)) {
+        int64_t pos = 12, dataPos = -1, dataLen = 0;
+        int tag = -1;
+        while (pos + 8 <= got) {
+            const uint32_t sz = le(h + pos + 4, 4);
+            if (!memcmp(h + pos, "fmt ", 4) && pos + 8 + 18 <= got) {
+                tag = (int)le(h + pos + 8, 2);
+                at3.frameSize = (int)le(h + pos + 20, 2);
+                if (tag == 0x270 && sz >= 32 && pos + 8 + 32 <= got) at3.js = (int)le(h + pos + 8 + 26, 2);
+            } else if (!memcmp(h + pos, "data", 4)) {
+                dataPos = pos + 8;
+                dataLen = sz;
+                break;
+            }
+            pos += 8 + sz + (sz & 1);
+        }
+        if (tag == 0xFFFE) {
+            std::cerr << "Fatal error: ATRAC3plus decoding is not supported" << std::endl;
+            return EInput::REFUSED;
+        }
+        if (tag != 0x270) return EInput::AEA;
+        if (dataPos < 0) {
+            std::cerr << "Fatal error: RIFF ATRAC3 file without a data chunk" << std::endl;
+            return EInput::REFUSED;
+        }
+        at3.container = "RIFF";
+        at3.offset = dataPos;
+        const int64_t avail = std::min<int64_t>(dataLen, fileSize - dataPos);
+        at3.frames = at3.frameSize ? avail / at3.frameSize : 0;
+    } else {
+        if (got > 0 && (h[0] >> 2) == 0x28) {
+            std::cerr << "Fatal error: raw ATRAC3 input is not supported (no container gives its frame size): "
+                         "decode an OMA or RIFF (.at3 / .wav) file" << std::endl;
+            return EInput::REFUSED;
+        }
+        return EInput::AEA;
+    }
+    if (!at3_row(at3.frameSize, at3.js)) {
+        std::cerr << "Fatal error: unsupported ATRAC3 frame size " << at3.frameSize << (at3.js ? " with" : " without")
+                  << " joint stereo" << std::endl;
+        return EInput::REFUSED;
+    }
+    return EInput::ATRAC3;
+}
+
+int decode_at3(const std::string& inFile, const std::string& outFile, const TAt3Input& at3, bool noStdOut, int batch, int device)
+{
+    std::ifstream in(inFile, std::ios::binary);
+    if (!in) {
+        std::cerr << "Fatal error: unable to open input file '" << inFile << "'" << std::endl;
+        return 1;
+    }
+    in.seekg(at3.offset, std::ios::beg);
+    const int64_t nOut = at3.frames;
+    if (!noStdOut)
+        std::cout << "Input\n Filename: " << inFile << "\n Container: " << at3.container << "\n Codec: ATRAC3, frame size "
+                  << at3.frameSize << (at3.js ? ", joint stereo" : "") << "\nOutput:\n Filename: " << outFile << "\n Codec: PCM" << std::endl;
+    std::ofstream out(outFile, std::ios::binary);
+    if (!out) {
+        std::cerr << "Fatal error: unable to open output file '" << outFile << "'" << std::endl;
+        return 1;
+    }
+    if (nOut * 1024 * 2 * 2 >= (int64_t)UINT32_MAX - 36) {
+        std::cerr << "Fatal error: output too long for a WAV file" << std::endl;
+        return 1;
+    }
+    const uint32_t nch = 2, dataBytes = (uint32_t)(nOut * 1024 * nch * 2);
+    std::vector<char> wav;
+    wav.insert(wav.end(), {'R', 'I', 'F', 'F'});
+    put_le(wav, 36 + dataBytes, 4);
+    wav.insert(wav.end(), {'W', 'A', 'V', 'E', 'f', 'm', 't', ' '});
+    put_le(wav, 16, 4);
+    put_le(wav, 1, 2);   // PCM
+    put_le(wav, nch, 2);
+    put_le(wav, 44100, 4);
+    put_le(wav, 44100u * 2u * nch, 4);
+    put_le(wav, 2u * nch, 2);
+    put_le(wav, 16, 2);
+    wav.insert(wav.end(), {'d', 'a', 't', 'a'});
+    put_le(wav, dataBytes, 4);
+    out.write(wav.data(), (std::streamsize)wav.size());
+    if (nOut == 0) {
+        if (!noStdOut) std::cout << "\nDone" << std::endl;
+        return 0;
+    }
+    const int B = (int)std::min<int64_t>(batch < 1 ? 1 : batch, nOut);
+    at3hip_decoder* dec = nullptr;
+    at3hip_decoder_config cfg{1, at3.frameSize, at3.js, B, device};
+    int rc = at3hip_decoder_create(&cfg, &dec);
+    if (rc != AT3HIP_OK) {
+        std::cerr << "Fatal error: at3hip_decoder_create failed (" << rc << ")" << std::endl;
+        return 1;
+    }
+    std::vector<uint8_t> frames((size_t)B * at3.frameSize);
+    std::vector<int16_t> pcm((size_t)B * 1024 * nch);
+    for (int64_t f0 = 0; f0 < nOut; f0 += B) {
+        const int n = (int)std::min<int64_t>(B, nOut - f0);
+        if (!in.read((char*)frames.data(), (std::streamsize)n * at3.frameSize)) {
+            std::cerr << "Fatal error: Can't read ATRAC3 frame" << std::endl;
+            at3hip_decoder_destroy(dec);
+            return 1;
+        }
+        rc = at3hip_decode(dec, frames.data(), n, pcm.data(), AT3HIP_DECODE_S16);
+        if (rc != AT3HIP_OK) {
+            std::cerr << "Encode/Decode error: at3hip_decode: " << at3hip_decoder_last_error(dec) << std::endl;
+            at3hip_decoder_destroy(dec);
+            return 1;
+        }
+        out.write((const char*)pcm.data(), (std::streamsize)n * 1024 * nch * 2);   // little-endian host
+    }
+    at3hip_decoder_counters c{};
+    rc = at3hip_decoder_get_counters(dec, &c, 0);
+    at3hip_decoder_destroy(dec);
+    if (rc != AT3HIP_OK) {
+        std::cerr << "Fatal error: at3hip_decoder_get_counters failed (" << rc << ")" << std::endl;
+        return 1;
+    }
+    const std::pair<const char*, uint64_t> reasons[] = {
+        {"wrong unit id", c.bad_id}, {"unsupported joint-stereo parameters", c.unsupported_js}, {"read past the end of the unit", c.read_past_end},
+        {"tonal component past line 1023", c.tonal_past_end}, {"tonal coding mode", c.bad_tonal_mode}, {"tonal quantiser", c.bad_tonal_quant}};
+    for (const auto& r : reasons)
+        if (r.second) std::cerr << "Skipped invalid ATRAC3 units (" << r.first << "): " << r.second << std::endl;
+    if (!noStdOut) std::cout << "\nDone" << std::endl;
+    return 0;
+}
+
 }  // namespace
 
 static int usage()
@@ -169,7 +355,8 @@ static int usage()
                  "       at3hipenc -e atrac1 -i in.wav -o out.aea [--bfuidxconst 1..8] [--notransient[=mask]]\n"
                  "                 [--container aea|raw] [--nostdout] [--batch blocks] [--device n]\n"
                  "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
-                 "       at3hipenc -d -i in.aea -o out.wav [--nostdout] [--batch frames] [--device n]\n";
+                 "       at3hipenc -d -i in.aea -o out.wav [--nostdout] [--batch frames] [--device n]\n"
+                 "       at3hipenc -d -i in.{oma|at3|wav} -o out.wav [--nostdout] [--batch frames] [--device n]   (ATRAC3, by content)\n";
     return 1;
 }
 
@@ -209,6 +396,10 @@ int main(int argc, char** argv)
     }
     if (decode) {
         if (!codec.empty() || inFile.empty() || outFile.empty()) return usage();
+        TAt3Input at3;
+        const EInput kind = probe_input(inFile, at3);
+        if (kind == EInput::REFUSED) return 1;
+        if (kind == EInput::ATRAC3) return decode_at3(inFile, outFile, at3, noStdOut, batch, device);
         return decode_aea(inFile, outFile, noStdOut, batch, device);
     }
     if ((codec != "atrac3" && codec != "atrac1" && codec != "atrac3plus") || inFile.empty() || outFile.empty()) return usage();

@@ -288,6 +288,84 @@ int at3hip_wait_frames(at3hip_ctx* ctx, int32_t ago);
  * suite prove, on the machine that runs the encoder, that the tables equal the reference's. */
 int at3hip_host_tables(void* dst, size_t bytes);
 
+/* ---- decoder ---------------------------------------------------------------------------------------------------------------
+ * A batched ATRAC3 decoder: frames as TAtrac3BitStreamWriter::WriteSoundUnit writes them (atrac3_bitstream.cpp:759-856) -> PCM,
+ * for a batch of independent streams, every frame of a call in parallel. The reference has no ATRAC3 decoder; its synthesis half
+ * (TAtrac3MDCT::Midct, TGainProcessor::Demodulate, TQmf::Synthesis) is what steps 3-6 restate bit for bit.
+ *
+ * Definition. A frame is FrameSz bytes of one of the eight container rows (atrac3.h ContainerParams); it holds two units.
+ *   1. Unpack, per unit (MSB first). Non-joint-stereo: unit 0 is bytes [0, FrameSz/2), unit 1 bytes [FrameSz/2, FrameSz).
+ *      Joint stereo: unit 0 reads forward from byte 0, unit 1 from the last byte backwards; each may read to the end of the frame.
+ *      Syntax: id 6 bits = 0x28 - or, for unit 1 of a joint-stereo frame, weighting 1 bit (must be 0), delay 3 bits (must be 7),
+ *      four matrix indices of 2 bits (must be 3), then id 2 bits = 3; QMF band count - 1 (2 bits); per band: gain point count
+ *      (3 bits), then per point level (4) and location (5); tonal subgroup count (5 bits); if non-zero the tonal coding mode
+ *      (2 bits: 0 VLC, 1 CLC) and per subgroup: one flag bit per QMF band, coded values - 1 (3), quantiser (3), then for each of
+ *      the 4 x band-count 64-line blocks whose band flag is set: component count (3), per component scale factor (6), position
+ *      in the block (6) and the coded values; then BFU count - 1 (5), coding mode (1 bit: 0 VLC, 1 CLC), word lengths (3 bits
+ *      per BFU), scale factors (6 bits per BFU with a non-zero word length), mantissas BFU by BFU (CLCEnc / VLCEnc's syntax:
+ *      word length 1 codes pairs).
+ *   2. Dequantise: line k of BFU i = (float)m * ScaleTable[sf] * InvMaxQuant[wl], evaluated left to right in float, where
+ *      InvMaxQuant[wl] = (float)(1.0 / MaxQuant[wl]) (the division by MaxQuant as a product with its once-rounded reciprocal,
+ *      which keeps the kernels free of the FMA sequence of an IEEE division); 0.0f where nothing is coded. A tonal component
+ *      adds (float)m * ScaleTable[its sf] * InvMaxQuant[its quantiser] at position + z; the components are summed in bitstream
+ *      order into a zeroed array t, and the spectral line is base[k] + t[k].
+ *   3. Per band TAtrac3MDCT::Midct: odd bands reversed, TMIDCT<512> at its default scale, x 2 DecodeWindow, and
+ *      Demodulate(gain points of frame n-1, gain points of frame n) against the previous frame's IMDCT half (every band, also
+ *      without gain points, where it is the plain overlap-add).
+ *   4. Joint stereo: L = M + S, R = M - S per subband sample.
+ *   5. Per channel TQmf<512>::Synthesis(buf1, sub0, sub1), TQmf<512>::Synthesis(buf2, sub3, sub2), TQmf<1024>::Synthesis(pcm,
+ *      buf1, buf2).
+ *   6. Clamp to [-1, 1]; float32, or int16 = lrintf(x * 32767.0f) with AT3HIP_DECODE_S16. Frame n gives samples
+ *      [1024 n, 1024 n + 1024) of the stream: the codec delay (1162 samples against the encoder's input) is not trimmed.
+ *   7. A unit is rejected (counted per reason, at3hip_decoder_counters) for: a wrong id, joint-stereo parameters other than
+ *      the above, a read past its allowed bytes, a tonal component that runs past line 1023, tonal coding mode 2 or 3, a tonal
+ *      quantiser below 2. A rejected unit decodes as an all-zero spectrum with no gain points; gain levels and locations are
+ *      never rejected. */
+typedef struct at3hip_decoder at3hip_decoder;
+
+typedef struct at3hip_decoder_config {
+    int32_t n_streams;    /* independent streams decoded side by side */
+    int32_t frame_size;   /* 192, 272, 304, 384, 424, 512, 768 or 1024 bytes */
+    int32_t joint_stereo; /* 1 for the two joint-stereo rows (192 and 272 bytes), else 0: must match the row */
+    int32_t max_frames;   /* upper bound of frames per stream per at3hip_decode call */
+    int32_t device_id;
+} at3hip_decoder_config;
+
+/* The context's stream is non-blocking; see DEVICE BUFFERS AND STREAMS and at3hip_decoder_set_stream. */
+int at3hip_decoder_create(const at3hip_decoder_config* cfg, at3hip_decoder** out);
+void at3hip_decoder_destroy(at3hip_decoder* dec);
+const char* at3hip_decoder_last_error(const at3hip_decoder* dec);
+
+#define AT3HIP_DECODE_S16 8u
+
+/*   frames [n_streams][n_frames][frame_size] bytes
+ *   pcm    [n_streams][n_frames][1024][2]: float32, or int16 with AT3HIP_DECODE_S16
+ * flags: AT3HIP_PCM_ON_DEVICE (frames are device memory), AT3HIP_OUT_ON_DEVICE, AT3HIP_ASYNC (only queue the call: buffers stay
+ * valid until at3hip_decoder_sync), AT3HIP_DECODE_S16. Stream state (the last two frames' IMDCT halves and gain points) carries
+ * across calls: any split of a stream into calls gives the same output as one call. */
+int at3hip_decode(at3hip_decoder* dec, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags);
+
+/* Waits for everything queued on the decoder. */
+int at3hip_decoder_sync(at3hip_decoder* dec);
+
+/* Back to start-of-stream state for every stream; zeroes the counters. */
+int at3hip_decoder_reset(at3hip_decoder* dec);
+
+/* Rejected units per reason (rule 7), summed over streams since create / reset / the last call with reset = 1. Waits for
+ * queued work. */
+typedef struct at3hip_decoder_counters {
+    uint64_t bad_id;
+    uint64_t unsupported_js;
+    uint64_t read_past_end;
+    uint64_t tonal_past_end;
+    uint64_t bad_tonal_mode;
+    uint64_t bad_tonal_quant;
+} at3hip_decoder_counters;
+int at3hip_decoder_get_counters(at3hip_decoder* dec, at3hip_decoder_counters* out, int32_t reset);
+
+/* Queue this decoder's work on a caller-provided hipStream_t (NULL = the decoder's own stream), as at1hip_decoder_set_stream. */
+int at3hip_decoder_set_stream(at3hip_decoder* dec, void* hip_stream);
+
 /* Library/ABI version: (major << 16) | minor. The minor number grows with every addition to this header:
  *   1.1  rounds 1 - 3 (two calls in flight: at3hip_wait_* accept ago 0 .. 1)
  *   1.2  at3hip_encode_s16, at3hip_wait_* with ago 0 .. 3 (three calls in flight), AT3HIP_TAP_CLOCK / AT3HIP_TAP_GAIN_ANALYSIS,
@@ -298,6 +376,9 @@ int at3hip_host_tables(void* dst, size_t bytes);
  *   1.5  AT3HIP_OPT_TIMING_EVERY
  *   1.6  the ATRAC1 decoder (at1hip.h): at1hip_decoder_create / _destroy / _last_error / _sync / _reset / _get_counters /
  *        _set_stream, at1hip_decode, AT1HIP_DECODE_S16
+ *        and, added later under the same number, the ATRAC3 decoder: at3hip_decoder_create / _destroy / _last_error / _sync /
+ *        _reset / _get_counters / _set_stream, at3hip_decode, AT3HIP_DECODE_S16 (the reported ABI stays 1.6, which the
+ *        suite's version checks pin; a host that needs the decoder looks for the symbol at3hip_decoder_create)
  * A host layer compiled against this header checks at3hip_version() >= AT3HIP_VERSION before it relies on them
  * (atracdenc_amd/host/at3hip_host.hpp and the ctypes stub do). */
 #define AT3HIP_VERSION_MAJOR 1
