@@ -170,27 +170,17 @@ def load_library(path=None):
     lib.at1hip_get_timings.argtypes = [vp, ctypes.POINTER(At1Timings)]
     lib.at1hip_read_tap.argtypes = [vp, i32, vp, ctypes.c_size_t]
     lib.at1hip_host_tables.argtypes = [vp, ctypes.c_size_t]
-    lib.at1hip_decoder_create.argtypes = [ctypes.POINTER(At1DecoderConfig), ctypes.POINTER(vp)]
-    lib.at1hip_decoder_destroy.argtypes = [vp]
-    lib.at1hip_decoder_destroy.restype = None
-    lib.at1hip_decoder_last_error.argtypes = [vp]
-    lib.at1hip_decoder_last_error.restype = ctypes.c_char_p
-    lib.at1hip_decode.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
-    lib.at1hip_decoder_sync.argtypes = [vp]
-    lib.at1hip_decoder_reset.argtypes = [vp]
-    lib.at1hip_decoder_get_counters.argtypes = [vp, ctypes.POINTER(At1DecoderCounters), i32]
-    lib.at1hip_decoder_set_stream.argtypes = [vp, vp]
-    if hasattr(lib, "at3hip_decoder_create"):   # the ATRAC3 decoder (added under ABI 1.6, see at3hip.h's version list)
-        lib.at3hip_decoder_create.argtypes = [ctypes.POINTER(At3DecoderConfig), ctypes.POINTER(vp)]
-        lib.at3hip_decoder_destroy.argtypes = [vp]
-        lib.at3hip_decoder_destroy.restype = None
-        lib.at3hip_decoder_last_error.argtypes = [vp]
-        lib.at3hip_decoder_last_error.restype = ctypes.c_char_p
-        lib.at3hip_decode.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
-        lib.at3hip_decoder_sync.argtypes = [vp]
-        lib.at3hip_decoder_reset.argtypes = [vp]
-        lib.at3hip_decoder_get_counters.argtypes = [vp, ctypes.POINTER(At3DecoderCounters), i32]
-        lib.at3hip_decoder_set_stream.argtypes = [vp, vp]
+    for codec, cfg_type, counters_type in (("at1hip", At1DecoderConfig, At1DecoderCounters),
+                                           ("at3hip", At3DecoderConfig, At3DecoderCounters)):
+        if codec == "at3hip" and not hasattr(lib, "at3hip_decoder_create"):
+            continue   # the ATRAC3 decoder (added under ABI 1.6, see at3hip.h's version list)
+        for name, argtypes in (("decoder_create", [ctypes.POINTER(cfg_type), ctypes.POINTER(vp)]), ("decoder_destroy", [vp]),
+                               ("decoder_last_error", [vp]), ("decode", [vp, vp, i32, vp, ctypes.c_uint32]), ("decoder_sync", [vp]),
+                               ("decoder_reset", [vp]), ("decoder_get_counters", [vp, ctypes.POINTER(counters_type), i32]),
+                               ("decoder_set_stream", [vp, vp])):
+            getattr(lib, f"{codec}_{name}").argtypes = argtypes
+        getattr(lib, f"{codec}_decoder_destroy").restype = None
+        getattr(lib, f"{codec}_decoder_last_error").restype = ctypes.c_char_p
     lib.at3phip_create.argtypes = [ctypes.POINTER(At3pConfig), ctypes.POINTER(vp)]
     lib.at3phip_destroy.argtypes = [vp]
     lib.at3phip_destroy.restype = None
@@ -215,27 +205,22 @@ def _vp(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-class At3Hip:
-    """n_streams TAtrac3Encoder objects encoded side by side on one GPU."""
+class _Context:
+    """One C-ABI context of `lib`: <_PREFIX>_create / _destroy / _last_error / _reset / _sync."""
 
-    def __init__(self, n_streams=1, max_blocks=64, bitrate=LP2, no_gain=False, no_tonal=False, bfu_idx_const=0,
-                 device_id=0, lib_path=None, channels=2):
-        self.lib = load_library(lib_path)
-        self.channels = int(channels)
-        self.cfg = Config(int(bitrate), int(channels), int(no_gain), int(no_tonal), int(bfu_idx_const), int(n_streams),
-                          int(max_blocks), int(device_id))
+    _PREFIX = ""
+
+    def _create(self, cfg, hint):
+        self.cfg = cfg
         self.ctx = ctypes.c_void_p()
-        rc = self.lib.at3hip_create(ctypes.byref(self.cfg), ctypes.byref(self.ctx))
+        rc = getattr(self.lib, self._PREFIX + "_create")(ctypes.byref(cfg), ctypes.byref(self.ctx))
         if rc != 0:
             self.ctx = None
-            raise At3HipError(f"at3hip_create failed with {rc} (no usable MI355X / HIP runtime?)")
-        self.n_streams = n_streams
-        self.frame_size = self.lib.at3hip_frame_size(self.ctx)
-        self.joint_stereo = bool(self.lib.at3hip_joint_stereo(self.ctx))
+            raise At3HipError(f"{self._PREFIX}_create failed with {rc} ({hint})")
 
     def close(self):
         if getattr(self, "ctx", None):
-            self.lib.at3hip_destroy(self.ctx)
+            getattr(self.lib, self._PREFIX + "_destroy")(self.ctx)
             self.ctx = None
 
     def __del__(self):
@@ -243,10 +228,64 @@ class At3Hip:
 
     def _check(self, rc, what):
         if rc != 0:
-            raise At3HipError(f"{what} failed ({rc}): {self.lib.at3hip_last_error(self.ctx).decode()}")
+            raise At3HipError(f"{what} failed ({rc}): {getattr(self.lib, self._PREFIX + '_last_error')(self.ctx).decode()}")
+
+    def _call(self, name, *args):
+        """<_PREFIX>_<name>(ctx, *args), raising At3HipError on failure."""
+        fn = f"{self._PREFIX}_{name}"
+        self._check(getattr(self.lib, fn)(self.ctx, *args), fn)
 
     def reset(self):
-        self._check(self.lib.at3hip_reset(self.ctx), "at3hip_reset")
+        self._call("reset")
+
+    def sync(self):
+        self._call("sync")
+
+
+class _Decoder(_Context):
+    """A batched decoder: <_CODEC>_decode and the <_CODEC>_decoder_* lifecycle, with counters named by _COUNTERS' fields."""
+
+    _CODEC = ""        # <_CODEC>_decode; the lifecycle functions are <_PREFIX>_*
+    _COUNTERS = None   # the ctypes structure <_PREFIX>_get_counters fills
+
+    def _order_behind_torch(self, device, ordered):
+        """Queues the next call on torch's current stream of `device` (ordered), or on the decoder's own stream. Torch's
+        default stream is the null stream, whose handle (0) means "the decoder's own stream" to <_PREFIX>_set_stream;
+        the decoder's stream is non-blocking: wait for what torch queued there instead."""
+        stream = None
+        if ordered:
+            import torch
+            cur = torch.cuda.current_stream(device)
+            stream = cur.cuda_stream or None
+            if stream is None:
+                cur.synchronize()
+        self._call("set_stream", ctypes.c_void_p(stream))
+
+    def decode_ptr(self, src_ptr, n_frames, out_ptr, flags):
+        """Raw pointers and <_CODEC>_decode flags (benchmarks)."""
+        fn = self._CODEC + "_decode"
+        self._check(getattr(self.lib, fn)(self.ctx, ctypes.c_void_p(src_ptr), int(n_frames), ctypes.c_void_p(out_ptr), int(flags)), fn)
+
+    def counters(self, reset=False):
+        c = self._COUNTERS()
+        self._call("get_counters", ctypes.byref(c), int(bool(reset)))
+        return {n: int(getattr(c, n)) for n, _ in self._COUNTERS._fields_}
+
+
+class At3Hip(_Context):
+    """n_streams TAtrac3Encoder objects encoded side by side on one GPU."""
+
+    _PREFIX = "at3hip"
+
+    def __init__(self, n_streams=1, max_blocks=64, bitrate=LP2, no_gain=False, no_tonal=False, bfu_idx_const=0,
+                 device_id=0, lib_path=None, channels=2):
+        self.lib = load_library(lib_path)
+        self.channels = int(channels)
+        self._create(Config(int(bitrate), int(channels), int(no_gain), int(no_tonal), int(bfu_idx_const), int(n_streams),
+                            int(max_blocks), int(device_id)), "no usable MI355X / HIP runtime?")
+        self.n_streams = n_streams
+        self.frame_size = self.lib.at3hip_frame_size(self.ctx)
+        self.joint_stereo = bool(self.lib.at3hip_joint_stereo(self.ctx))
 
     def encode(self, pcm):
         """pcm float32 [n_streams, n_blocks, 1024, channels] (host) -> uint8 [n_streams, n_frames, frame_size]."""
@@ -304,9 +343,6 @@ class At3Hip:
         s_memrealtime over the life of the allocation kernel's workgroup 0), or None before the first frames."""
         c = self.read_tap(TAP_CLOCK, np.uint64, (2,))
         return float(c[0]) / float(c[1]) * 100.0 if c[1] else None
-
-    def sync(self):
-        self._check(self.lib.at3hip_sync(self.ctx), "at3hip_sync")
 
     def counters(self, reset=False):
         """at3hip_get_counters: what TScaler::Scale would have printed since create / reset - {"scale_overflow", "clipped_values"}."""
@@ -439,9 +475,10 @@ def at1_host_tables(lib_path=None):
     return out
 
 
-class At1Hip:
+class At1Hip(_Context):
     """n_streams TAtrac1Encoder objects encoded side by side on one GPU (include/at1hip.h)."""
 
+    _PREFIX = "at1hip"
     FRAME = 212
     TAP_SPECTRA, TAP_MASKS, TAP_LOUDNESS, TAP_TABLES = 1, 2, 3, 4
 
@@ -449,28 +486,8 @@ class At1Hip:
                  lib_path=None):
         self.lib = load_library(lib_path)
         self.channels, self.n_streams = int(channels), int(n_streams)
-        self.cfg = At1Config(int(channels), int(bool(window_auto)), int(window_mask), int(bfu_idx_const), int(n_streams),
-                             int(max_blocks), int(device_id))
-        self.ctx = ctypes.c_void_p()
-        rc = self.lib.at1hip_create(ctypes.byref(self.cfg), ctypes.byref(self.ctx))
-        if rc != 0:
-            self.ctx = None
-            raise At3HipError(f"at1hip_create failed with {rc} (no usable MI355X / HIP runtime?)")
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.at1hip_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        self.close()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise At3HipError(f"{what} failed ({rc}): {self.lib.at1hip_last_error(self.ctx).decode()}")
-
-    def reset(self):
-        self._check(self.lib.at1hip_reset(self.ctx), "at1hip_reset")
+        self._create(At1Config(int(channels), int(bool(window_auto)), int(window_mask), int(bfu_idx_const), int(n_streams),
+                               int(max_blocks), int(device_id)), "no usable MI355X / HIP runtime?")
 
     def encode(self, pcm):
         """pcm float32 [n_streams, n_blocks, 512, channels] (host) -> uint8 [n_streams, n_blocks, channels, 212]."""
@@ -485,9 +502,6 @@ class At1Hip:
         self._check(self.lib.at1hip_encode(self.ctx, ctypes.c_void_p(pcm_ptr), n_blocks, ctypes.c_void_p(out_ptr),
                                            AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)), "at1hip_encode")
 
-    def sync(self):
-        self._check(self.lib.at1hip_sync(self.ctx), "at1hip_sync")
-
     def read_tap(self, kind, dtype, shape):
         out = np.zeros(shape, dtype=dtype)
         self._check(self.lib.at1hip_read_tap(self.ctx, int(kind), _vp(out), out.nbytes), "at1hip_read_tap")
@@ -499,35 +513,17 @@ class At1Hip:
         return {n: getattr(t, n) for n, _ in At1Timings._fields_}
 
 
-class At1HipDecoder:
+class At1HipDecoder(_Decoder):
     """n_streams TAtrac1Decoder objects decoded side by side on one GPU (include/at1hip.h, the decoder section)."""
 
+    _CODEC, _PREFIX, _COUNTERS = "at1hip", "at1hip_decoder", At1DecoderCounters
     FRAME = 212
 
     def __init__(self, n_streams=1, max_frames=256, channels=2, device_id=0, lib_path=None):
         self.lib = load_library(lib_path)
         self.channels, self.n_streams, self.max_frames = int(channels), int(n_streams), int(max_frames)
-        self.cfg = At1DecoderConfig(self.channels, self.n_streams, self.max_frames, int(device_id))
-        self.ctx = ctypes.c_void_p()
-        rc = self.lib.at1hip_decoder_create(ctypes.byref(self.cfg), ctypes.byref(self.ctx))
-        if rc != 0:
-            self.ctx = None
-            raise At3HipError(f"at1hip_decoder_create failed with {rc} (bad configuration, or no usable MI355X / HIP runtime)")
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.at1hip_decoder_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        self.close()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise At3HipError(f"{what} failed ({rc}): {self.lib.at1hip_decoder_last_error(self.ctx).decode()}")
-
-    def reset(self):
-        self._check(self.lib.at1hip_decoder_reset(self.ctx), "at1hip_decoder_reset")
+        self._create(At1DecoderConfig(self.channels, self.n_streams, self.max_frames, int(device_id)),
+                     "bad configuration, or no usable MI355X / HIP runtime")
 
     def decode(self, units, s16=False):
         """units uint8 [n_streams, n_frames, channels, 212] (host) -> float32 (int16 with s16) [n_streams, n_frames, 512, channels]."""
@@ -535,7 +531,7 @@ class At1HipDecoder:
         assert units.ndim == 4 and units.shape[0] == self.n_streams and units.shape[2:] == (self.channels, self.FRAME), units.shape
         n = units.shape[1]
         out = np.zeros((self.n_streams, n, 512, self.channels), dtype=np.int16 if s16 else np.float32)
-        self._check(self.lib.at1hip_decode(self.ctx, _vp(units), n, _vp(out), AT1HIP_DECODE_S16 if s16 else 0), "at1hip_decode")
+        self.decode_ptr(units.ctypes.data, n, out.ctypes.data, AT1HIP_DECODE_S16 if s16 else 0)
         return out
 
     def decode_device(self, units, out, asynchronous=False, ordered=True):
@@ -553,35 +549,14 @@ class At1HipDecoder:
         assert tuple(out.shape) == (self.n_streams, n, 512, self.channels), tuple(out.shape)
         flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT1HIP_DECODE_S16 if out.dtype == torch.int16 else 0)
         flags |= AT3HIP_ASYNC if asynchronous else 0
-        stream = None
-        if ordered:
-            cur = torch.cuda.current_stream(units.device)
-            stream = cur.cuda_stream or None
-            if stream is None:
-                # torch's default stream is the null stream, whose handle (0) means "the decoder's own stream" to
-                # at1hip_decoder_set_stream; the decoder's stream is non-blocking: wait for what torch queued instead
-                cur.synchronize()
-        self._check(self.lib.at1hip_decoder_set_stream(self.ctx, ctypes.c_void_p(stream)), "at1hip_decoder_set_stream")
-        self._check(self.lib.at1hip_decode(self.ctx, ctypes.c_void_p(units.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), flags),
-                    "at1hip_decode")
-
-    def decode_ptr(self, units_ptr, n_frames, out_ptr, flags):
-        """Raw pointers and at1hip_decode flags (benchmarks)."""
-        self._check(self.lib.at1hip_decode(self.ctx, ctypes.c_void_p(units_ptr), int(n_frames), ctypes.c_void_p(out_ptr), int(flags)),
-                    "at1hip_decode")
-
-    def sync(self):
-        self._check(self.lib.at1hip_decoder_sync(self.ctx), "at1hip_decoder_sync")
-
-    def counters(self, reset=False):
-        c = At1DecoderCounters()
-        self._check(self.lib.at1hip_decoder_get_counters(self.ctx, ctypes.byref(c), int(bool(reset))), "at1hip_decoder_get_counters")
-        return {"bad_block_size": int(c.bad_block_size), "read_past_end": int(c.read_past_end)}
+        self._order_behind_torch(units.device, ordered)
+        self.decode_ptr(units.data_ptr(), n, out.data_ptr(), flags)
 
 
-class At3HipDecoder:
+class At3HipDecoder(_Decoder):
     """n_streams ATRAC3 streams of one container row decoded side by side on one GPU (include/at3hip.h, the decoder section)."""
 
+    _CODEC, _PREFIX, _COUNTERS = "at3hip", "at3hip_decoder", At3DecoderCounters
     ROWS = {192: True, 272: True, 304: False, 384: False, 424: False, 512: False, 768: False, 1024: False}
 
     def __init__(self, n_streams=1, frame_size=384, joint_stereo=None, max_frames=256, device_id=0, lib_path=None):
@@ -590,27 +565,8 @@ class At3HipDecoder:
             raise At3HipError("libat3hip.so predates the ATRAC3 decoder (no at3hip_decoder_create): rebuild it")
         self.n_streams, self.frame_size, self.max_frames = int(n_streams), int(frame_size), int(max_frames)
         self.joint_stereo = bool(self.ROWS.get(self.frame_size, False) if joint_stereo is None else joint_stereo)
-        self.cfg = At3DecoderConfig(self.n_streams, self.frame_size, int(self.joint_stereo), self.max_frames, int(device_id))
-        self.ctx = ctypes.c_void_p()
-        rc = self.lib.at3hip_decoder_create(ctypes.byref(self.cfg), ctypes.byref(self.ctx))
-        if rc != 0:
-            self.ctx = None
-            raise At3HipError(f"at3hip_decoder_create failed with {rc} (bad configuration, or no usable MI355X / HIP runtime)")
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.at3hip_decoder_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        self.close()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise At3HipError(f"{what} failed ({rc}): {self.lib.at3hip_decoder_last_error(self.ctx).decode()}")
-
-    def reset(self):
-        self._check(self.lib.at3hip_decoder_reset(self.ctx), "at3hip_decoder_reset")
+        self._create(At3DecoderConfig(self.n_streams, self.frame_size, int(self.joint_stereo), self.max_frames, int(device_id)),
+                     "bad configuration, or no usable MI355X / HIP runtime")
 
     def decode(self, frames, s16=False):
         """frames uint8 [n_streams, n_frames, frame_size] (host) -> float32 (int16 with s16) [n_streams, n_frames, 1024, 2]."""
@@ -618,7 +574,7 @@ class At3HipDecoder:
         assert frames.ndim == 3 and frames.shape[0] == self.n_streams and frames.shape[2] == self.frame_size, frames.shape
         n = frames.shape[1]
         out = np.zeros((self.n_streams, n, 1024, 2), dtype=np.int16 if s16 else np.float32)
-        self._check(self.lib.at3hip_decode(self.ctx, _vp(frames), n, _vp(out), AT3HIP_DECODE_S16 if s16 else 0), "at3hip_decode")
+        self.decode_ptr(frames.ctypes.data, n, out.ctypes.data, AT3HIP_DECODE_S16 if s16 else 0)
         return out
 
     def decode_device(self, frames, out, asynchronous=False, ordered=True):
@@ -632,28 +588,8 @@ class At3HipDecoder:
         assert tuple(out.shape) == (self.n_streams, n, 1024, 2), tuple(out.shape)
         flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_DECODE_S16 if out.dtype == torch.int16 else 0)
         flags |= AT3HIP_ASYNC if asynchronous else 0
-        stream = None
-        if ordered:
-            cur = torch.cuda.current_stream(frames.device)
-            stream = cur.cuda_stream or None
-            if stream is None:
-                cur.synchronize()   # the null stream: the decoder's own stream is non-blocking, wait instead
-        self._check(self.lib.at3hip_decoder_set_stream(self.ctx, ctypes.c_void_p(stream)), "at3hip_decoder_set_stream")
-        self._check(self.lib.at3hip_decode(self.ctx, ctypes.c_void_p(frames.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), flags),
-                    "at3hip_decode")
-
-    def decode_ptr(self, frames_ptr, n_frames, out_ptr, flags):
-        """Raw pointers and at3hip_decode flags (benchmarks)."""
-        self._check(self.lib.at3hip_decode(self.ctx, ctypes.c_void_p(frames_ptr), int(n_frames), ctypes.c_void_p(out_ptr), int(flags)),
-                    "at3hip_decode")
-
-    def sync(self):
-        self._check(self.lib.at3hip_decoder_sync(self.ctx), "at3hip_decoder_sync")
-
-    def counters(self, reset=False):
-        c = At3DecoderCounters()
-        self._check(self.lib.at3hip_decoder_get_counters(self.ctx, ctypes.byref(c), int(bool(reset))), "at3hip_decoder_get_counters")
-        return {n: int(getattr(c, n)) for n in AT3_DECODER_REASONS}
+        self._order_behind_torch(frames.device, ordered)
+        self.decode_ptr(frames.data_ptr(), n, out.data_ptr(), flags)
 
 
 AT3PHIP_RESIDUAL_SCALE = 16
@@ -670,33 +606,15 @@ def at3p_host_tables(lib_path=None):
     return out
 
 
-class At3pHip:
+class At3pHip(_Context):
     """ATRAC3plus front end (include/at3phip.h): PQF analysis and windowed MDCT-256 x 16 for n_streams streams."""
+
+    _PREFIX = "at3phip"
 
     def __init__(self, n_streams=1, max_frames=32, channels=2, device_id=0, lib_path=None):
         self.lib = load_library(lib_path)
         self.channels, self.n_streams = int(channels), int(n_streams)
-        self.cfg = At3pConfig(int(channels), int(n_streams), int(max_frames), int(device_id))
-        self.ctx = ctypes.c_void_p()
-        rc = self.lib.at3phip_create(ctypes.byref(self.cfg), ctypes.byref(self.ctx))
-        if rc != 0:
-            self.ctx = None
-            raise At3HipError(f"at3phip_create failed with {rc} (no usable MI355X / HIP runtime?)")
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.at3phip_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        self.close()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise At3HipError(f"{what} failed ({rc}): {self.lib.at3phip_last_error(self.ctx).decode()}")
-
-    def reset(self):
-        self._check(self.lib.at3phip_reset(self.ctx), "at3phip_reset")
+        self._create(At3pConfig(int(channels), int(n_streams), int(max_frames), int(device_id)), "no usable MI355X / HIP runtime?")
 
     def _flags(self, win_flags, nf):
         if win_flags is None:
@@ -762,9 +680,6 @@ class At3pHip:
         self._check(self.lib.at3phip_encode_frames(self.ctx, ctypes.c_void_p(pcm_ptr), n_frames, ctypes.c_void_p(frames_ptr),
                                                    AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)),
                     "at3phip_encode_frames")
-
-    def sync(self):
-        self._check(self.lib.at3phip_sync(self.ctx), "at3phip_sync")
 
     def timings(self):
         a, b, w = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()

@@ -8,10 +8,11 @@
 
 #include "../../include/at1hip.h"
 #include "at1_kernels.hpp"
-#include <cmath>
 #include "at3_host_util.hpp"
 
 using namespace at1;
+using at3host::dev_alloc;
+using at3host::fail;
 
 static_assert(sizeof(Tables) == AT1HIP_TABLES_BYTES, "at1hip.h documents the table block's size");
 
@@ -41,31 +42,6 @@ struct at1hip_ctx {
 };
 
 namespace {
-
-int fail(at1hip_ctx* c, int code, const char* what, hipError_t e = hipSuccess)
-{
-    if (c) {
-        if (e != hipSuccess) snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
-        else snprintf(c->err, sizeof(c->err), "%s", what);
-    }
-    return code;
-}
-
-#define HIPCHK(c, call)                                                    \
-    do {                                                                   \
-        hipError_t e_ = (call);                                            \
-        if (e_ != hipSuccess) return fail((c), AT3HIP_EDEVICE, #call, e_); \
-    } while (0)
-
-template <typename Tp>
-int dev_alloc(at1hip_ctx* c, Tp** p, size_t count)
-{
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(Tp) + 256);
-    if (e != hipSuccess) return fail(c, AT3HIP_ENOMEM, "hipMalloc", e);
-    *p = (Tp*)q;
-    return AT3HIP_OK;
-}
 
 int reset_state(at1hip_ctx* c)
 {
@@ -303,13 +279,11 @@ int at1hip_read_tap(at1hip_ctx* c, int32_t kind, void* dst, size_t bytes)
 }  // extern "C"
 
 // ---- decoder (include/at1hip.h) ------------------------------------------------------------------------------------------------
+#include "at3_decoder_host.hpp"
 #include "at1_decode.hpp"
 
-struct at1hip_decoder {
+struct at1hip_decoder : at3host::DecoderBase {
     at1hip_decoder_config cfg;
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;  // own_stream, or the caller's (at1hip_decoder_set_stream)
     DecTables* d_tables = nullptr;
     uint8_t* d_units = nullptr;    // staging for host units [S][F][C][212]
     float* d_raw = nullptr;        // [S*C][F][512]
@@ -318,44 +292,17 @@ struct at1hip_decoder {
     int4* d_lw = nullptr;          // [S*C][F]
     float* d_st_band = nullptr;    // [S*C][512]
     float* d_st_tail = nullptr;    // [S*C][48]
-    unsigned long long* d_rejected = nullptr;  // [2]
     void* d_out = nullptr;         // staging for host output [S][F][512][C] float32
-    char err[256] = {0};
+    // (d_rejected: [2])
 };
 
 namespace {
 
-int dfail(at1hip_decoder* d, int code, const char* what, hipError_t e = hipSuccess)
-{
-    if (d) {
-        if (e != hipSuccess) snprintf(d->err, sizeof(d->err), "%s: %s", what, hipGetErrorString(e));
-        else snprintf(d->err, sizeof(d->err), "%s", what);
-    }
-    return code;
-}
-
-#define DHIPCHK(d, call)                                                    \
-    do {                                                                    \
-        hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) return dfail((d), AT3HIP_EDEVICE, #call, e_); \
-    } while (0)
-
-// CalcSinCos(n, scale) (lib/mdct/mdct.cpp:25-36) as TMIDCT<n>(2n) calls it: float overloads, evaluated at run time
-__attribute__((optnone, noinline)) void imdct_sincos(float* dst, size_t n, float scale)
-{
-    const float alpha = 2.0 * M_PI / (8.0 * n);
-    const float omiga = 2.0 * M_PI / n;
-    scale = sqrtf(scale / n);
-    for (size_t i = 0; i < (n >> 2); ++i) {
-        dst[2 * i + 0] = scale * cosf(omiga * i + alpha);
-        dst[2 * i + 1] = scale * sinf(omiga * i + alpha);
-    }
-}
-
-__attribute__((optnone, noinline)) void build_dec_tables(DecTables* t)
+// false when the encoder's table block cannot be allocated (the decoder is then not created)
+__attribute__((optnone, noinline)) bool build_dec_tables(DecTables* t)
 {
     Tables* enc = new (std::nothrow) Tables();   // the shared entries: the encoder's builder computes them the reference's way
-    if (!enc) return;
+    if (!enc) return false;
     build_tables(enc);
     memcpy(t->qmf_win, enc->qmf_win, sizeof(t->qmf_win));
     memcpy(t->sine, enc->sine, sizeof(t->sine));
@@ -366,28 +313,20 @@ __attribute__((optnone, noinline)) void build_dec_tables(DecTables* t)
     delete enc;
     t->maxq[0] = t->maxq[1] = 0.0f;
     for (int wl = 2; wl <= 16; ++wl) t->maxq[wl] = 1.0 / (float)((1 << (wl - 1)) - 1);
-    imdct_sincos(t->cs512, 512, 512.0f);   // TMIDCT(float scale = TN) : TMDCTBase(TN, scale / 2), atrac1denc.h:52-54
-    imdct_sincos(t->cs256, 256, 256.0f);
-    imdct_sincos(t->cs64, 64, 64.0f);
+    // TMIDCT<n>(2n) (TMIDCT(float scale = TN) : TMDCTBase(TN, scale / 2), atrac1denc.h:52-54)
+    at3::mdct_sincos(t->cs512, 512, 512.0f);
+    at3::mdct_sincos(t->cs256, 256, 256.0f);
+    at3::mdct_sincos(t->cs64, 64, 64.0f);
+    return true;
 }
 
 int dec_reset_state(at1hip_decoder* d)
 {
     const size_t SC = (size_t)d->cfg.n_streams * d->cfg.channels;
-    DHIPCHK(d, hipMemsetAsync(d->d_st_band, 0, SC * 512 * sizeof(float), d->stream));
-    DHIPCHK(d, hipMemsetAsync(d->d_st_tail, 0, SC * kDecTailLen * sizeof(float), d->stream));
-    DHIPCHK(d, hipMemsetAsync(d->d_rejected, 0, 2 * sizeof(unsigned long long), d->stream));
-    DHIPCHK(d, hipStreamSynchronize(d->stream));
-    return AT3HIP_OK;
-}
-
-template <typename Tp>
-int dec_alloc(at1hip_decoder* d, Tp** p, size_t count)
-{
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(Tp) + 256);
-    if (e != hipSuccess) return dfail(d, AT3HIP_ENOMEM, "hipMalloc", e);
-    *p = (Tp*)q;
+    HIPCHK(d, hipMemsetAsync(d->d_st_band, 0, SC * 512 * sizeof(float), d->stream));
+    HIPCHK(d, hipMemsetAsync(d->d_st_tail, 0, SC * kDecTailLen * sizeof(float), d->stream));
+    HIPCHK(d, hipMemsetAsync(d->d_rejected, 0, 2 * sizeof(unsigned long long), d->stream));
+    HIPCHK(d, hipStreamSynchronize(d->stream));
     return AT3HIP_OK;
 }
 
@@ -403,115 +342,68 @@ int at1hip_decoder_create(const at1hip_decoder_config* cfg, at1hip_decoder** out
     if ((long long)cfg->n_streams * cfg->channels > at3host::kMaxGridY) return AT3HIP_EINVAL;   // (stream, channel) is gridDim.y
     // every buffer index stays inside size_t and the kernels' int frame counts
     if ((long long)cfg->max_frames * cfg->n_streams * cfg->channels > (1ll << 31) / 512) return AT3HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return AT3HIP_EDEVICE;
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return AT3HIP_EINVAL;
-    at1hip_decoder* d = new (std::nothrow) at1hip_decoder();
-    if (!d) return AT3HIP_ENOMEM;
-    d->cfg = *cfg;
-    d->device = cfg->device_id;
-    auto bail = [&](int code) {
-        at1hip_decoder_destroy(d);
-        return code;
-    };
-    at3host::DeviceGuard guard(d->device);
-    if (guard.error() != hipSuccess) return bail(AT3HIP_EDEVICE);
-    if (hipStreamCreateWithFlags(&d->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    d->stream = d->own_stream;
-    DecTables* host_tables = new (std::nothrow) DecTables();
-    if (!host_tables) return bail(AT3HIP_ENOMEM);
-    build_dec_tables(host_tables);
-    int rc = dec_alloc(d, &d->d_tables, 1);
-    if (rc == AT3HIP_OK && (hipMemcpy(d->d_tables, host_tables, sizeof(DecTables), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipDeviceSynchronize() != hipSuccess))   // (pageable source, see at1hip_create)
-        rc = AT3HIP_EDEVICE;
-    delete host_tables;
-    if (rc != AT3HIP_OK) return bail(rc);
-    const size_t S = cfg->n_streams, F = cfg->max_frames, C = cfg->channels;
-    if ((rc = dec_alloc(d, &d->d_units, S * F * C * kFrame)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dec_alloc(d, &d->d_raw, S * C * F * 512)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dec_alloc(d, &d->d_tails, S * C * F * kDecTailLen)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dec_alloc(d, &d->d_modes, S * C * F)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dec_alloc(d, &d->d_lw, S * C * F)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dec_alloc(d, &d->d_st_band, S * C * 512)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dec_alloc(d, &d->d_st_tail, S * C * kDecTailLen)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dec_alloc(d, &d->d_rejected, 2)) != AT3HIP_OK) return bail(rc);
-    float* d_out = nullptr;
-    if ((rc = dec_alloc(d, &d_out, S * F * 512 * C)) != AT3HIP_OK) return bail(rc);
-    d->d_out = d_out;
-    if ((rc = dec_reset_state(d)) != AT3HIP_OK) return bail(rc);
-    *out = d;
-    return AT3HIP_OK;
+    return at3host::create_decoder(cfg, out, build_dec_tables, at1hip_decoder_destroy, [](at1hip_decoder* d) {
+        const size_t S = d->cfg.n_streams, F = d->cfg.max_frames, C = d->cfg.channels;
+        int rc;
+        if ((rc = dev_alloc(d, &d->d_units, S * F * C * kFrame)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_raw, S * C * F * 512)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_tails, S * C * F * kDecTailLen)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_modes, S * C * F)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_lw, S * C * F)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_st_band, S * C * 512)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_st_tail, S * C * kDecTailLen)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_rejected, 2)) != AT3HIP_OK) return rc;
+        float* d_out = nullptr;
+        if ((rc = dev_alloc(d, &d_out, S * F * 512 * C)) != AT3HIP_OK) return rc;
+        d->d_out = d_out;
+        return dec_reset_state(d);
+    });
 }
 
 void at1hip_decoder_destroy(at1hip_decoder* d)
 {
-    if (!d) return;
-    at3host::DeviceGuard guard(d->device);
-    if (d->stream) (void)hipStreamSynchronize(d->stream);
-    void* bufs[] = {d->d_tables, d->d_units, d->d_raw, d->d_tails, d->d_modes, d->d_lw, d->d_st_band, d->d_st_tail, d->d_rejected, d->d_out};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (d->own_stream) (void)hipStreamDestroy(d->own_stream);
-    delete d;
+    if (d)
+        at3host::destroy_decoder(d, {d->d_tables, d->d_units, d->d_raw, d->d_tails, d->d_modes, d->d_lw, d->d_st_band, d->d_st_tail,
+                                     d->d_rejected, d->d_out});
 }
 
-const char* at1hip_decoder_last_error(const at1hip_decoder* d) { return d ? d->err : "null context"; }
+const char* at1hip_decoder_last_error(const at1hip_decoder* d) { return at3host::decoder_last_error(d); }
 
-int at1hip_decoder_sync(at1hip_decoder* d)
-{
-    if (!d) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    DHIPCHK(d, guard.error());
-    DHIPCHK(d, hipStreamSynchronize(d->stream));
-    return AT3HIP_OK;
-}
+int at1hip_decoder_sync(at1hip_decoder* d) { return at3host::decoder_sync(d); }
 
 int at1hip_decoder_reset(at1hip_decoder* d)
 {
     if (!d) return AT3HIP_EINVAL;
     at3host::DeviceGuard guard(d->device);
-    DHIPCHK(d, guard.error());
+    HIPCHK(d, guard.error());
     return dec_reset_state(d);
 }
 
-int at1hip_decoder_set_stream(at1hip_decoder* d, void* hip_stream)
-{
-    if (!d) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    DHIPCHK(d, guard.error());
-    DHIPCHK(d, hipStreamSynchronize(d->stream));
-    d->stream = hip_stream ? (hipStream_t)hip_stream : d->own_stream;
-    return AT3HIP_OK;
-}
+int at1hip_decoder_set_stream(at1hip_decoder* d, void* hip_stream) { return at3host::decoder_set_stream(d, hip_stream); }
 
 int at1hip_decoder_get_counters(at1hip_decoder* d, at1hip_decoder_counters* out, int32_t reset)
 {
     if (!d || !out) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    DHIPCHK(d, guard.error());
     unsigned long long h[2] = {0, 0};
-    DHIPCHK(d, hipMemcpyAsync(h, d->d_rejected, sizeof(h), hipMemcpyDeviceToHost, d->stream));
-    if (reset) DHIPCHK(d, hipMemsetAsync(d->d_rejected, 0, sizeof(h), d->stream));
-    DHIPCHK(d, hipStreamSynchronize(d->stream));
+    const int rc = at3host::read_counters(d, h, reset);
+    if (rc != AT3HIP_OK) return rc;
     out->bad_block_size = h[0];
     out->read_past_end = h[1];
     return AT3HIP_OK;
 }
-
 int at1hip_decode(at1hip_decoder* d, const uint8_t* units, int32_t n_frames, void* pcm, uint32_t flags)
 {
     const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT1HIP_DECODE_S16;
     if (!d || !units || !pcm || n_frames < 1 || n_frames > d->cfg.max_frames || (flags & ~known))
-        return d ? dfail(d, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
+        return d ? fail(d, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
     at3host::DeviceGuard guard(d->device);
-    DHIPCHK(d, guard.error());
+    HIPCHK(d, guard.error());
     const size_t S = d->cfg.n_streams, C = d->cfg.channels, F = (size_t)n_frames, SC = S * C;
     const bool s16 = flags & AT1HIP_DECODE_S16;
     hipStream_t st = d->stream;
     const uint8_t* d_units = units;
     if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        DHIPCHK(d, hipMemcpyAsync(d->d_units, units, S * F * C * kFrame, hipMemcpyHostToDevice, st));
+        HIPCHK(d, hipMemcpyAsync(d->d_units, units, S * F * C * kFrame, hipMemcpyHostToDevice, st));
         d_units = d->d_units;
     }
     void* d_pcm = (flags & AT3HIP_OUT_ON_DEVICE) ? pcm : d->d_out;
@@ -526,9 +418,9 @@ int at1hip_decode(at1hip_decoder* d, const uint8_t* units, int32_t n_frames, voi
     bp.modes = d->d_modes;
     bp.rejected = d->d_rejected;
     hipLaunchKernelGGL(k_at1d_bands, dim3((unsigned)F, (unsigned)SC), dim3(128), 0, st, bp);
-    DHIPCHK(d, hipGetLastError());
+    HIPCHK(d, hipGetLastError());
     hipLaunchKernelGGL(k_at1d_scan, dim3((unsigned)SC), dim3(kDecScanThreads), 0, st, (const int32_t*)d->d_modes, d->d_lw, n_frames);
-    DHIPCHK(d, hipGetLastError());
+    HIPCHK(d, hipGetLastError());
     DecSynthParams sp;
     sp.T = d->d_tables;
     sp.raw = d->d_raw;
@@ -541,13 +433,13 @@ int at1hip_decode(at1hip_decoder* d, const uint8_t* units, int32_t n_frames, voi
     sp.nch = (int)C;
     sp.s16 = s16 ? 1 : 0;
     hipLaunchKernelGGL(k_at1d_synth, dim3((unsigned)F, (unsigned)SC), dim3(256), 0, st, sp);
-    DHIPCHK(d, hipGetLastError());
+    HIPCHK(d, hipGetLastError());
     hipLaunchKernelGGL(k_at1d_state, dim3((unsigned)SC), dim3(256), 0, st, (const float*)d->d_raw, (const float*)d->d_tails,
                        (const int4*)d->d_lw, d->d_st_band, d->d_st_tail, n_frames);
-    DHIPCHK(d, hipGetLastError());
+    HIPCHK(d, hipGetLastError());
     if (!(flags & AT3HIP_OUT_ON_DEVICE))
-        DHIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 512 * C * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
-    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at1hip_decoder_sync(d);
+        HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 512 * C * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
+    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::decoder_sync(d);
 }
 
 }  // extern "C"

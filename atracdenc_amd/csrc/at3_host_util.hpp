@@ -1,8 +1,39 @@
 // Host-side helpers shared by the three C-ABI translation units (at3hip.hip, at1hip.hip, at3phip.hip).
 #pragma once
+#include <cstdio>
+
 #include <hip/hip_runtime.h>
 
+#include "../../include/at3hip.h"
+
 namespace at3host {
+
+// Records `what` (with the HIP error string when `e` is an error) as the context's last error and returns `code`.
+template <typename Ctx>
+int fail(Ctx* c, int code, const char* what, hipError_t e = hipSuccess)
+{
+    if (c) {
+        if (e != hipSuccess) snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
+        else snprintf(c->err, sizeof(c->err), "%s", what);
+    }
+    return code;
+}
+
+#define HIPCHK(c, call)                                                              \
+    do {                                                                             \
+        hipError_t e_ = (call);                                                      \
+        if (e_ != hipSuccess) return at3host::fail((c), AT3HIP_EDEVICE, #call, e_);  \
+    } while (0)
+
+template <typename Ctx, typename Tp>
+int dev_alloc(Ctx* c, Tp** p, size_t count)
+{
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, count * sizeof(Tp) + 256);
+    if (e != hipSuccess) return fail(c, AT3HIP_ENOMEM, "hipMalloc", e);
+    *p = (Tp*)q;
+    return AT3HIP_OK;
+}
 
 // Every entry point works on the device its context was created on, whatever device the calling thread has current
 // (torch, another context on another GPU ...), and leaves the caller's current device as it found it.

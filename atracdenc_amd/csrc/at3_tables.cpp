@@ -62,6 +62,18 @@ AT3_RUNTIME_LIBM void fill_twiddles(cpx* tw, int n, bool inverse)
     }
 }
 
+// CalcSinCos(n, scale), lib/mdct/mdct.cpp:25-36: float overloads of sqrt / cos / sin are the ones selected
+AT3_RUNTIME_LIBM void mdct_sincos(float* dst, size_t n, float scale)
+{
+    const float alpha = 2.0 * M_PI / (8.0 * n);
+    const float omiga = 2.0 * M_PI / n;
+    scale = sqrtf(scale / n);
+    for (size_t i = 0; i < (n >> 2); ++i) {
+        dst[2 * i + 0] = scale * cosf(omiga * i + alpha);
+        dst[2 * i + 1] = scale * sinf(omiga * i + alpha);
+    }
+}
+
 namespace {
 
 AT3_RUNTIME_LIBM void fill_super_twiddles(cpx* tw, int ncfft, bool inverse)
@@ -85,17 +97,7 @@ AT3_RUNTIME_LIBM void build_tables(Tables* t)
     for (int i = 0; i < 16; ++i) t->gain_level[i] = pow(2.0, 4 - i);
     for (int i = 0; i < 31; ++i) t->gain_interp[i] = pow(2.0, -1.0 / 8 * (i - 15));
 
-    {   // MDCT-512 pre/post rotation, scale 1 -> sqrt(1/512) folded in
-        const size_t n = 512;
-        const float alpha = 2.0 * M_PI / (8.0 * n);
-        const float omiga = 2.0 * M_PI / n;
-        float scale = 1.0f;
-        scale = sqrtf(scale / n);
-        for (size_t i = 0; i < (n >> 2); ++i) {
-            t->mdct_sincos[2 * i + 0] = scale * cosf(omiga * i + alpha);
-            t->mdct_sincos[2 * i + 1] = scale * sinf(omiga * i + alpha);
-        }
-    }
+    mdct_sincos(t->mdct_sincos, 512, 1.0f);   // MDCT-512 pre/post rotation, scale 1 -> sqrt(1/512) folded in
     fill_twiddles(t->tw128, 128, false);
     fill_twiddles(t->tw256, 256, false);
     fill_twiddles(t->tw2048, 2048, true);
@@ -242,18 +244,6 @@ const uint8_t kSpecsPerBlock[kMaxBfus] = {8,  8,  8,  8,  4,  4,  4,  4,  8,  8,
                                           6,  6,  6,  6,  6,  6,  7,  7,  7,  7,  9,  9,  9,  9,  10, 10, 10, 10,
                                           12, 12, 12, 12, 12, 12, 12, 12, 20, 20, 20, 20, 20, 20, 20, 20};
 
-// CalcSinCos(n, scale), lib/mdct/mdct.cpp:25-36: float overloads of sqrt / cos / sin are the ones selected
-AT3_RUNTIME_LIBM void mdct_sincos(float* dst, size_t n, float scale)
-{
-    const float alpha = 2.0 * M_PI / (8.0 * n);
-    const float omiga = 2.0 * M_PI / n;
-    scale = sqrtf(scale / n);
-    for (size_t i = 0; i < (n >> 2); ++i) {
-        dst[2 * i + 0] = scale * cosf(omiga * i + alpha);
-        dst[2 * i + 1] = scale * sinf(omiga * i + alpha);
-    }
-}
-
 }  // namespace
 
 AT3_RUNTIME_LIBM void build_tables(Tables* t)
@@ -262,9 +252,9 @@ AT3_RUNTIME_LIBM void build_tables(Tables* t)
     for (int i = 0; i < 24; ++i) t->qmf_win[i] = t->qmf_win[47 - i] = at3::kTapHalf[i] * 2.0;
     for (uint32_t i = 0; i < 64; ++i) t->scale[i] = pow(2.0, (double)(i / 3.0 - 21.0));
     for (uint32_t i = 0; i < 32; ++i) t->sine[i] = sin((i + 0.5) * (M_PI / (2.0 * 32.0)));
-    mdct_sincos(t->sc512, 512, 1.0f);
-    mdct_sincos(t->sc256, 256, 0.5f);
-    mdct_sincos(t->sc64, 64, 0.5f);
+    at3::mdct_sincos(t->sc512, 512, 1.0f);
+    at3::mdct_sincos(t->sc256, 256, 0.5f);
+    at3::mdct_sincos(t->sc64, 64, 0.5f);
     at3::fill_twiddles(t->tw128, 128, false);
     at3::fill_twiddles(t->tw64, 64, false);
     at3::fill_twiddles(t->tw16, 16, false);
@@ -327,17 +317,6 @@ const float kFir[384] = {
 #include "at3p_fir.inc"
 };
 
-AT3_RUNTIME_LIBM void mdct_sincos(float* dst, size_t n, float scale)   // CalcSinCos, lib/mdct/mdct.cpp:25-36
-{
-    const float alpha = 2.0 * M_PI / (8.0 * n);
-    const float omiga = 2.0 * M_PI / n;
-    scale = sqrtf(scale / n);
-    for (size_t i = 0; i < (n >> 2); ++i) {
-        dst[2 * i + 0] = scale * cosf(omiga * i + alpha);
-        dst[2 * i + 1] = scale * sinf(omiga * i + alpha);
-    }
-}
-
 }  // namespace
 
 AT3_RUNTIME_LIBM void build_tables(Tables* t)
@@ -345,8 +324,8 @@ AT3_RUNTIME_LIBM void build_tables(Tables* t)
     memset(t, 0, sizeof(*t));
     memcpy(t->fir, kFir, sizeof(kFir));
     const float dct_scale = 32.0 * (float)(128 * 512.0);   // atde_create_dct4_16(128 * 512.0) -> TMIDCT<32>(32.0 * scale)
-    mdct_sincos(t->sc32, 32, dct_scale / 2);               // TMIDCT(float scale) : TMDCTBase(TN, scale / 2)
-    mdct_sincos(t->sc256, 256, 1.0f);
+    at3::mdct_sincos(t->sc32, 32, dct_scale / 2);               // TMIDCT(float scale) : TMDCTBase(TN, scale / 2)
+    at3::mdct_sincos(t->sc256, 256, 1.0f);
     at3::fill_twiddles(t->tw8, 8, false);
     at3::fill_twiddles(t->tw64, 64, false);
     for (size_t i = 0; i < 128; i++) t->sine128[i] = 2.0 * sinf((i + 0.5) * (M_PI / (2.0 * 128)));

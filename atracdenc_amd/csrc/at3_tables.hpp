@@ -6,6 +6,7 @@
 // Bit-exact parity needs the same table values, so they are generated on the host with the same
 // libm expressions and never recomputed with device transcendentals.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "at3_libm64.hpp"
@@ -61,5 +62,9 @@ struct Tables {
 
 // Fills *t on the host. Pure function of libm.
 void build_tables(Tables* t);
+
+// The n / 4 {cos, sin} pairs of an MDCT-n's rotation as the reference's CalcSinCos(n, scale) computes them, called at run time
+// with libm's float routines. Every encoder's MDCT table and every decoder's IMDCT table comes from it.
+void mdct_sincos(float* dst, size_t n, float scale);
 
 }  // namespace at3

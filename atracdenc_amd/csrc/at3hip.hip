@@ -18,6 +18,8 @@
 #include "at3_k_gain.hpp"
 
 using namespace at3;
+using at3host::dev_alloc;
+using at3host::fail;
 
 namespace {
 
@@ -132,31 +134,6 @@ struct at3hip_ctx {
 };
 
 namespace {
-
-int fail(at3hip_ctx* c, int code, const char* what, hipError_t e = hipSuccess)
-{
-    if (c) {
-        if (e != hipSuccess) snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
-        else snprintf(c->err, sizeof(c->err), "%s", what);
-    }
-    return code;
-}
-
-#define HIPCHK(c, call)                                                  \
-    do {                                                                 \
-        hipError_t e_ = (call);                                          \
-        if (e_ != hipSuccess) return fail((c), AT3HIP_EDEVICE, #call, e_); \
-    } while (0)
-
-template <typename Tp>
-int dev_alloc(at3hip_ctx* c, Tp** p, size_t count)
-{
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(Tp) + 256);
-    if (e != hipSuccess) return fail(c, AT3HIP_ENOMEM, "hipMalloc", e);
-    *p = (Tp*)q;
-    return AT3HIP_OK;
-}
 
 // Device staging area of at least `bytes` bytes (reallocated only when a call needs more than any call before).
 int stage_reserve(at3hip_ctx* c, size_t bytes)
@@ -1385,51 +1362,20 @@ extern "C" __attribute__((visibility("default"))) int at3hip_debug_cell_divisors
 #endif
 
 // ---- decoder (include/at3hip.h, decoder section) -------------------------------------------------------------------------------
-#include <cmath>
+#include "at3_decoder_host.hpp"
 #include "at3_decode.hpp"
 
-struct at3hip_decoder {
+struct at3hip_decoder : at3host::DecoderBase {
     at3hip_decoder_config cfg;
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;  // own_stream, or the caller's (at3hip_decoder_set_stream)
     Dec3Tables* d_tables = nullptr;
     uint8_t* d_frames = nullptr;   // staging for host frames [S][F][frame_size]
     float* d_raw = nullptr;        // [F + 2][S][2][4][512]: slots 0, 1 = the carried frames -2, -1
     Dec3Gains* d_gains = nullptr;  // [F + 2][S][2]
-    unsigned long long* d_rejected = nullptr;  // [6]
     void* d_out = nullptr;         // staging for host output [S][F][1024][2] float32
-    char err[256] = {0};
+    // (d_rejected: [kDec3Reasons])
 };
 
 namespace {
-
-int d3fail(at3hip_decoder* d, int code, const char* what, hipError_t e = hipSuccess)
-{
-    if (d) {
-        if (e != hipSuccess) snprintf(d->err, sizeof(d->err), "%s: %s", what, hipGetErrorString(e));
-        else snprintf(d->err, sizeof(d->err), "%s", what);
-    }
-    return code;
-}
-
-#define D3HIPCHK(d, call)                                                    \
-    do {                                                                     \
-        hipError_t e_ = (call);                                              \
-        if (e_ != hipSuccess) return d3fail((d), AT3HIP_EDEVICE, #call, e_); \
-    } while (0)
-
-// CalcSinCos(512, 256) as TMIDCT<512>() calls it: float overloads, evaluated at run time
-__attribute__((optnone, noinline)) void dec3_sincos(float* dst, size_t n, float scale)
-{
-    const float alpha = 2.0 * M_PI / (8.0 * n);
-    const float omiga = 2.0 * M_PI / n;
-    scale = sqrtf(scale / n);
-    for (size_t i = 0; i < (n >> 2); ++i) {
-        dst[2 * i + 0] = scale * cosf(omiga * i + alpha);
-        dst[2 * i + 1] = scale * sinf(omiga * i + alpha);
-    }
-}
 
 // false when the encoder's table block cannot be allocated (the decoder is then not created)
 __attribute__((optnone, noinline)) bool build_dec3_tables(Dec3Tables* t)
@@ -1451,7 +1397,7 @@ __attribute__((optnone, noinline)) bool build_dec3_tables(Dec3Tables* t)
     static const float max_quant[8] = {0.0f, 1.5f, 2.5f, 3.5f, 4.5f, 7.5f, 15.5f, 31.5f};   // MaxQuant (atrac3.h)
     t->inv_maxq[0] = 0.0f;
     for (int wl = 1; wl < 8; ++wl) t->inv_maxq[wl] = 1.0 / (double)max_quant[wl];
-    dec3_sincos(t->cs512, 512, 256.0f);   // TMIDCT(float scale = TN) : TMDCTBase(TN, scale / 2)
+    mdct_sincos(t->cs512, 512, 256.0f);   // TMIDCT<512>(): TMIDCT(float scale = TN) : TMDCTBase(TN, scale / 2)
     memset(t->vlc, 0, sizeof(t->vlc));    // filled on the device from c_huff (k_at3d_vlc_lut)
     return true;
 }
@@ -1459,20 +1405,10 @@ __attribute__((optnone, noinline)) bool build_dec3_tables(Dec3Tables* t)
 int dec3_reset_state(at3hip_decoder* d)
 {
     const size_t S = d->cfg.n_streams;
-    D3HIPCHK(d, hipMemsetAsync(d->d_raw, 0, 2 * S * 2 * 2048 * sizeof(float), d->stream));
-    D3HIPCHK(d, hipMemsetAsync(d->d_gains, 0, 2 * S * 2 * sizeof(Dec3Gains), d->stream));
-    D3HIPCHK(d, hipMemsetAsync(d->d_rejected, 0, kDec3Reasons * sizeof(unsigned long long), d->stream));
-    D3HIPCHK(d, hipStreamSynchronize(d->stream));
-    return AT3HIP_OK;
-}
-
-template <typename Tp>
-int dec3_alloc(at3hip_decoder* d, Tp** p, size_t count)
-{
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(Tp) + 256);
-    if (e != hipSuccess) return d3fail(d, AT3HIP_ENOMEM, "hipMalloc", e);
-    *p = (Tp*)q;
+    HIPCHK(d, hipMemsetAsync(d->d_raw, 0, 2 * S * 2 * 2048 * sizeof(float), d->stream));
+    HIPCHK(d, hipMemsetAsync(d->d_gains, 0, 2 * S * 2 * sizeof(Dec3Gains), d->stream));
+    HIPCHK(d, hipMemsetAsync(d->d_rejected, 0, kDec3Reasons * sizeof(unsigned long long), d->stream));
+    HIPCHK(d, hipStreamSynchronize(d->stream));
     return AT3HIP_OK;
 }
 
@@ -1496,98 +1432,47 @@ int at3hip_decoder_create(const at3hip_decoder_config* cfg, at3hip_decoder** out
     if ((long long)cfg->n_streams * 2 > at3host::kMaxGridY) return AT3HIP_EINVAL;   // (stream, unit) is gridDim.y
     // every buffer index stays inside size_t and the kernels' int frame counts
     if (((long long)cfg->max_frames + 2) * cfg->n_streams > (1ll << 31) / 4096) return AT3HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return AT3HIP_EDEVICE;
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return AT3HIP_EINVAL;
-    at3hip_decoder* d = new (std::nothrow) at3hip_decoder();
-    if (!d) return AT3HIP_ENOMEM;
-    d->cfg = *cfg;
-    d->device = cfg->device_id;
-    auto bail = [&](int code) {
-        at3hip_decoder_destroy(d);
-        return code;
-    };
-    at3host::DeviceGuard guard(d->device);
-    if (guard.error() != hipSuccess) return bail(AT3HIP_EDEVICE);
-    if (hipStreamCreateWithFlags(&d->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    d->stream = d->own_stream;
-    Dec3Tables* host_tables = new (std::nothrow) Dec3Tables();
-    if (!host_tables) return bail(AT3HIP_ENOMEM);
-    if (!build_dec3_tables(host_tables)) {
-        delete host_tables;
-        return bail(AT3HIP_ENOMEM);
-    }
-    int rc = dec3_alloc(d, &d->d_tables, 1);
-    if (rc == AT3HIP_OK && (hipMemcpy(d->d_tables, host_tables, sizeof(Dec3Tables), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipDeviceSynchronize() != hipSuccess))   // (pageable source, see at3hip_create)
-        rc = AT3HIP_EDEVICE;
-    delete host_tables;
-    if (rc != AT3HIP_OK) return bail(rc);
-    hipLaunchKernelGGL(k_at3d_vlc_lut, dim3(1), dim3(256), 0, d->stream, d->d_tables);
-    if (hipGetLastError() != hipSuccess) return bail(AT3HIP_EDEVICE);
-    const size_t S = cfg->n_streams, F = cfg->max_frames;
-    if ((rc = dec3_alloc(d, &d->d_frames, S * F * cfg->frame_size)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dec3_alloc(d, &d->d_raw, (F + 2) * S * 2 * 2048)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dec3_alloc(d, &d->d_gains, (F + 2) * S * 2)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dec3_alloc(d, &d->d_rejected, kDec3Reasons)) != AT3HIP_OK) return bail(rc);
-    float* d_out = nullptr;
-    if ((rc = dec3_alloc(d, &d_out, S * F * 2048)) != AT3HIP_OK) return bail(rc);
-    d->d_out = d_out;
-    if ((rc = dec3_reset_state(d)) != AT3HIP_OK) return bail(rc);
-    *out = d;
-    return AT3HIP_OK;
+    return at3host::create_decoder(cfg, out, build_dec3_tables, at3hip_decoder_destroy, [](at3hip_decoder* d) {
+        hipLaunchKernelGGL(k_at3d_vlc_lut, dim3(1), dim3(256), 0, d->stream, d->d_tables);
+        if (hipGetLastError() != hipSuccess) return AT3HIP_EDEVICE;
+        const size_t S = d->cfg.n_streams, F = d->cfg.max_frames;
+        int rc;
+        if ((rc = dev_alloc(d, &d->d_frames, S * F * d->cfg.frame_size)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_raw, (F + 2) * S * 2 * 2048)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_gains, (F + 2) * S * 2)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_rejected, kDec3Reasons)) != AT3HIP_OK) return rc;
+        float* d_out = nullptr;
+        if ((rc = dev_alloc(d, &d_out, S * F * 2048)) != AT3HIP_OK) return rc;
+        d->d_out = d_out;
+        return dec3_reset_state(d);
+    });
 }
 
 void at3hip_decoder_destroy(at3hip_decoder* d)
 {
-    if (!d) return;
-    at3host::DeviceGuard guard(d->device);
-    if (d->stream) (void)hipStreamSynchronize(d->stream);
-    void* bufs[] = {d->d_tables, d->d_frames, d->d_raw, d->d_gains, d->d_rejected, d->d_out};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (d->own_stream) (void)hipStreamDestroy(d->own_stream);
-    delete d;
+    if (d) at3host::destroy_decoder(d, {d->d_tables, d->d_frames, d->d_raw, d->d_gains, d->d_rejected, d->d_out});
 }
 
-const char* at3hip_decoder_last_error(const at3hip_decoder* d) { return d ? d->err : "null context"; }
+const char* at3hip_decoder_last_error(const at3hip_decoder* d) { return at3host::decoder_last_error(d); }
 
-int at3hip_decoder_sync(at3hip_decoder* d)
-{
-    if (!d) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    D3HIPCHK(d, guard.error());
-    D3HIPCHK(d, hipStreamSynchronize(d->stream));
-    return AT3HIP_OK;
-}
+int at3hip_decoder_sync(at3hip_decoder* d) { return at3host::decoder_sync(d); }
 
 int at3hip_decoder_reset(at3hip_decoder* d)
 {
     if (!d) return AT3HIP_EINVAL;
     at3host::DeviceGuard guard(d->device);
-    D3HIPCHK(d, guard.error());
+    HIPCHK(d, guard.error());
     return dec3_reset_state(d);
 }
 
-int at3hip_decoder_set_stream(at3hip_decoder* d, void* hip_stream)
-{
-    if (!d) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    D3HIPCHK(d, guard.error());
-    D3HIPCHK(d, hipStreamSynchronize(d->stream));
-    d->stream = hip_stream ? (hipStream_t)hip_stream : d->own_stream;
-    return AT3HIP_OK;
-}
+int at3hip_decoder_set_stream(at3hip_decoder* d, void* hip_stream) { return at3host::decoder_set_stream(d, hip_stream); }
 
 int at3hip_decoder_get_counters(at3hip_decoder* d, at3hip_decoder_counters* out, int32_t reset)
 {
     if (!d || !out) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    D3HIPCHK(d, guard.error());
     unsigned long long h[kDec3Reasons] = {0, 0, 0, 0, 0, 0};
-    D3HIPCHK(d, hipMemcpyAsync(h, d->d_rejected, sizeof(h), hipMemcpyDeviceToHost, d->stream));
-    if (reset) D3HIPCHK(d, hipMemsetAsync(d->d_rejected, 0, sizeof(h), d->stream));
-    D3HIPCHK(d, hipStreamSynchronize(d->stream));
+    const int rc = at3host::read_counters(d, h, reset);
+    if (rc != AT3HIP_OK) return rc;
     out->bad_id = h[0];
     out->unsupported_js = h[1];
     out->read_past_end = h[2];
@@ -1596,20 +1481,19 @@ int at3hip_decoder_get_counters(at3hip_decoder* d, at3hip_decoder_counters* out,
     out->bad_tonal_quant = h[5];
     return AT3HIP_OK;
 }
-
 int at3hip_decode(at3hip_decoder* d, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags)
 {
     const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3HIP_DECODE_S16;
     if (!d || !frames || !pcm || n_frames < 1 || n_frames > d->cfg.max_frames || (flags & ~known))
-        return d ? d3fail(d, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
+        return d ? fail(d, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
     at3host::DeviceGuard guard(d->device);
-    D3HIPCHK(d, guard.error());
+    HIPCHK(d, guard.error());
     const size_t S = d->cfg.n_streams, F = (size_t)n_frames, fsz = d->cfg.frame_size;
     const bool s16 = flags & AT3HIP_DECODE_S16;
     hipStream_t st = d->stream;
     const uint8_t* d_frames = frames;
     if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        D3HIPCHK(d, hipMemcpyAsync(d->d_frames, frames, S * F * fsz, hipMemcpyHostToDevice, st));
+        HIPCHK(d, hipMemcpyAsync(d->d_frames, frames, S * F * fsz, hipMemcpyHostToDevice, st));
         d_frames = d->d_frames;
     }
     void* d_pcm = (flags & AT3HIP_OUT_ON_DEVICE) ? pcm : d->d_out;
@@ -1625,7 +1509,7 @@ int at3hip_decode(at3hip_decoder* d, const uint8_t* frames, int32_t n_frames, vo
     up.gains = d->d_gains;
     up.rejected = d->d_rejected;
     hipLaunchKernelGGL(k_at3d_unpack, dim3((unsigned)F, (unsigned)(2 * S)), dim3(kDec3UnpackThreads), 0, st, up);
-    D3HIPCHK(d, hipGetLastError());
+    HIPCHK(d, hipGetLastError());
     Dec3SynthParams sp;
     sp.T = d->d_tables;
     sp.raw = d->d_raw;
@@ -1636,12 +1520,12 @@ int at3hip_decode(at3hip_decoder* d, const uint8_t* frames, int32_t n_frames, vo
     sp.js = d->cfg.joint_stereo;
     sp.s16 = s16 ? 1 : 0;
     hipLaunchKernelGGL(k_at3d_synth, dim3((unsigned)F, (unsigned)S), dim3(256), 0, st, sp);
-    D3HIPCHK(d, hipGetLastError());
+    HIPCHK(d, hipGetLastError());
     hipLaunchKernelGGL(k_at3d_state, dim3((unsigned)(2 * S)), dim3(256), 0, st, d->d_raw, d->d_gains, n_frames, (int32_t)S);
-    D3HIPCHK(d, hipGetLastError());
+    HIPCHK(d, hipGetLastError());
     if (!(flags & AT3HIP_OUT_ON_DEVICE))
-        D3HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 2048 * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
-    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3hip_decoder_sync(d);
+        HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 2048 * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
+    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::decoder_sync(d);
 }
 
 }  // extern "C"

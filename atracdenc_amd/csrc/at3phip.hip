@@ -12,6 +12,8 @@
 #include "at3_host_util.hpp"
 
 using namespace at3p;
+using at3host::dev_alloc;
+using at3host::fail;
 
 static_assert(sizeof(Tables) == AT3PHIP_TABLES_BYTES, "at3phip.h documents the table block's size");
 static_assert(sizeof(WriteTables) == AT3PHIP_WRITE_TABLES_BYTES, "at3phip.h documents the frame writer's table block size");
@@ -43,31 +45,6 @@ struct at3phip_ctx {
 };
 
 namespace {
-
-int fail(at3phip_ctx* c, int code, const char* what, hipError_t e = hipSuccess)
-{
-    if (c) {
-        if (e != hipSuccess) snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
-        else snprintf(c->err, sizeof(c->err), "%s", what);
-    }
-    return code;
-}
-
-#define HIPCHK(c, call)                                                    \
-    do {                                                                   \
-        hipError_t e_ = (call);                                            \
-        if (e_ != hipSuccess) return fail((c), AT3HIP_EDEVICE, #call, e_); \
-    } while (0)
-
-template <typename Tp>
-int dev_alloc(at3phip_ctx* c, Tp** p, size_t count)
-{
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(Tp) + 256);
-    if (e != hipSuccess) return fail(c, AT3HIP_ENOMEM, "hipMalloc", e);
-    *p = (Tp*)q;
-    return AT3HIP_OK;
-}
 
 int reset_state(at3phip_ctx* c)
 {

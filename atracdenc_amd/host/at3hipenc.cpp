@@ -62,6 +62,25 @@ void put_le(std::vector<char>& h, uint32_t v, int bytes)
     for (int i = 0; i < bytes; ++i) h.push_back((char)((v >> (8 * i)) & 0xff));
 }
 
+// The 44-byte canonical header of a 16-bit PCM WAV at 44100 Hz with `dataBytes` bytes of samples.
+void write_wav_header(std::ofstream& out, uint32_t nch, uint32_t dataBytes)
+{
+    std::vector<char> wav;
+    wav.insert(wav.end(), {'R', 'I', 'F', 'F'});
+    put_le(wav, 36 + dataBytes, 4);
+    wav.insert(wav.end(), {'W', 'A', 'V', 'E', 'f', 'm', 't', ' '});
+    put_le(wav, 16, 4);
+    put_le(wav, 1, 2);   // PCM
+    put_le(wav, nch, 2);
+    put_le(wav, 44100, 4);
+    put_le(wav, 44100u * 2u * nch, 4);
+    put_le(wav, 2u * nch, 2);
+    put_le(wav, 16, 2);
+    wav.insert(wav.end(), {'d', 'a', 't', 'a'});
+    put_le(wav, dataBytes, 4);
+    out.write(wav.data(), (std::streamsize)wav.size());
+}
+
 // `-d`: TAtrac1Decoder behind TPCMEngine(4096, channels) with a TWav writer (main.cpp:343-365, 697-705).
 //  * Length: TAeaInput::GetLengthInSamples = 512 * (units / channels - 5) (aea.cpp:98-108). The engine's ApplyProcess(512) runs
 //    the lambda over its whole 4096-sample buffer, i.e. 8 frames per call, and the loop calls it until `processed` reaches that
@@ -110,21 +129,7 @@ int decode_aea(const std::string& inFile, const std::string& outFile, bool noStd
         std::cerr << "Fatal error: unable to open output file '" << outFile << "'" << std::endl;
         return 1;
     }
-    const uint32_t dataBytes = (uint32_t)(nOut * 512 * nch * 2);
-    std::vector<char> wav;
-    wav.insert(wav.end(), {'R', 'I', 'F', 'F'});
-    put_le(wav, 36 + dataBytes, 4);
-    wav.insert(wav.end(), {'W', 'A', 'V', 'E', 'f', 'm', 't', ' '});
-    put_le(wav, 16, 4);
-    put_le(wav, 1, 2);   // PCM
-    put_le(wav, (uint32_t)nch, 2);
-    put_le(wav, 44100, 4);
-    put_le(wav, 44100u * 2u * (uint32_t)nch, 4);
-    put_le(wav, 2u * (uint32_t)nch, 2);
-    put_le(wav, 16, 2);
-    wav.insert(wav.end(), {'d', 'a', 't', 'a'});
-    put_le(wav, dataBytes, 4);
-    out.write(wav.data(), (std::streamsize)wav.size());
+    write_wav_header(out, (uint32_t)nch, (uint32_t)(nOut * 512 * nch * 2));
 
     const int B = batch < 1 ? 1 : batch;
     at1hip_decoder* dec = nullptr;
@@ -286,21 +291,8 @@ int decode_at3(const std::string& inFile, const std::string& outFile, const TAt3
         std::cerr << "Fatal error: output too long for a WAV file" << std::endl;
         return 1;
     }
-    const uint32_t nch = 2, dataBytes = (uint32_t)(nOut * 1024 * nch * 2);
-    std::vector<char> wav;
-    wav.insert(wav.end(), {'R', 'I', 'F', 'F'});
-    put_le(wav, 36 + dataBytes, 4);
-    wav.insert(wav.end(), {'W', 'A', 'V', 'E', 'f', 'm', 't', ' '});
-    put_le(wav, 16, 4);
-    put_le(wav, 1, 2);   // PCM
-    put_le(wav, nch, 2);
-    put_le(wav, 44100, 4);
-    put_le(wav, 44100u * 2u * nch, 4);
-    put_le(wav, 2u * nch, 2);
-    put_le(wav, 16, 2);
-    wav.insert(wav.end(), {'d', 'a', 't', 'a'});
-    put_le(wav, dataBytes, 4);
-    out.write(wav.data(), (std::streamsize)wav.size());
+    const uint32_t nch = 2;
+    write_wav_header(out, nch, (uint32_t)(nOut * 1024 * nch * 2));
     if (nOut == 0) {
         if (!noStdOut) std::cout << "\nDone" << std::endl;
         return 0;
