@@ -58,7 +58,12 @@ AT1HIP_DECODE_S16 = 8
 # include/at3phip.h
 AT3P_SYMBOLS = ["at3phip_create", "at3phip_destroy", "at3phip_last_error", "at3phip_reset", "at3phip_pqf_analyse", "at3phip_mdct",
                 "at3phip_pqf_mdct", "at3phip_get_timings", "at3phip_host_tables", "at3phip_write_frames", "at3phip_encode_frames",
-                "at3phip_get_write_timing", "at3phip_host_write_tables", "at3phip_sync"]
+                "at3phip_get_write_timing", "at3phip_host_write_tables", "at3phip_sync",
+                "at3phip_decoder_create", "at3phip_decoder_destroy", "at3phip_decoder_last_error", "at3phip_decode",
+                "at3phip_decoder_sync", "at3phip_decoder_reset", "at3phip_decoder_get_counters", "at3phip_decoder_set_stream",
+                "at3phip_decoder_host_tables"]
+AT3PHIP_DECODE_S16 = 8
+AT3PHIP_DECODER_TABLES_BYTES = 67328
 
 
 class At1Config(ctypes.Structure):
@@ -87,6 +92,17 @@ AT3_DECODER_REASONS = ("bad_id", "unsupported_js", "read_past_end", "tonal_past_
 
 class At3DecoderCounters(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in AT3_DECODER_REASONS]
+
+
+class At3pDecoderConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("channels", "n_streams", "max_frames", "device_id")]
+
+
+AT3P_DECODER_REASONS = ("bad_header", "unsupported_syntax", "tonal_present", "bad_code", "read_past_end", "no_terminator")
+
+
+class At3pDecoderCounters(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in AT3P_DECODER_REASONS]
 
 
 class At1Timings(ctypes.Structure):
@@ -171,9 +187,10 @@ def load_library(path=None):
     lib.at1hip_read_tap.argtypes = [vp, i32, vp, ctypes.c_size_t]
     lib.at1hip_host_tables.argtypes = [vp, ctypes.c_size_t]
     for codec, cfg_type, counters_type in (("at1hip", At1DecoderConfig, At1DecoderCounters),
-                                           ("at3hip", At3DecoderConfig, At3DecoderCounters)):
-        if codec == "at3hip" and not hasattr(lib, "at3hip_decoder_create"):
-            continue   # the ATRAC3 decoder (added under ABI 1.6, see at3hip.h's version list)
+                                           ("at3hip", At3DecoderConfig, At3DecoderCounters),
+                                           ("at3phip", At3pDecoderConfig, At3pDecoderCounters)):
+        if codec != "at1hip" and not hasattr(lib, f"{codec}_decoder_create"):
+            continue   # the ATRAC3 and ATRAC3plus decoders (added under ABI 1.6, see at3hip.h's version list)
         for name, argtypes in (("decoder_create", [ctypes.POINTER(cfg_type), ctypes.POINTER(vp)]), ("decoder_destroy", [vp]),
                                ("decoder_last_error", [vp]), ("decode", [vp, vp, i32, vp, ctypes.c_uint32]), ("decoder_sync", [vp]),
                                ("decoder_reset", [vp]), ("decoder_get_counters", [vp, ctypes.POINTER(counters_type), i32]),
@@ -181,6 +198,8 @@ def load_library(path=None):
             getattr(lib, f"{codec}_{name}").argtypes = argtypes
         getattr(lib, f"{codec}_decoder_destroy").restype = None
         getattr(lib, f"{codec}_decoder_last_error").restype = ctypes.c_char_p
+    if hasattr(lib, "at3phip_decoder_host_tables"):
+        lib.at3phip_decoder_host_tables.argtypes = [vp, ctypes.c_size_t]
     lib.at3phip_create.argtypes = [ctypes.POINTER(At3pConfig), ctypes.POINTER(vp)]
     lib.at3phip_destroy.argtypes = [vp]
     lib.at3phip_destroy.restype = None
@@ -590,6 +609,53 @@ class At3HipDecoder(_Decoder):
         flags |= AT3HIP_ASYNC if asynchronous else 0
         self._order_behind_torch(frames.device, ordered)
         self.decode_ptr(frames.data_ptr(), n, out.data_ptr(), flags)
+
+
+class At3pHipDecoder(_Decoder):
+    """n_streams ATRAC3plus streams of 1 or 2 channels decoded side by side on one GPU (include/at3phip.h, the decoder section)."""
+
+    _CODEC, _PREFIX, _COUNTERS = "at3phip", "at3phip_decoder", At3pDecoderCounters
+
+    def __init__(self, n_streams=1, channels=2, max_frames=64, device_id=0, lib_path=None):
+        self.lib = load_library(lib_path)
+        if not hasattr(self.lib, "at3phip_decoder_create"):
+            raise At3HipError("libat3hip.so predates the ATRAC3plus decoder (no at3phip_decoder_create): rebuild it")
+        self.n_streams, self.channels, self.max_frames = int(n_streams), int(channels), int(max_frames)
+        self._create(At3pDecoderConfig(self.channels, self.n_streams, self.max_frames, int(device_id)),
+                     "bad configuration, or no usable MI355X / HIP runtime")
+
+    def decode(self, frames, s16=False):
+        """frames uint8 [n_streams, n_frames, 2048] (host) -> float32 (int16 with s16) [n_streams, n_frames, 2048, channels]."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        assert frames.ndim == 3 and frames.shape[0] == self.n_streams and frames.shape[2] == 2048, frames.shape
+        n = frames.shape[1]
+        out = np.zeros((self.n_streams, n, 2048, self.channels), dtype=np.int16 if s16 else np.float32)
+        self.decode_ptr(frames.ctypes.data, n, out.ctypes.data, AT3PHIP_DECODE_S16 if s16 else 0)
+        return out
+
+    def decode_device(self, frames, out, asynchronous=False, ordered=True):
+        """Torch tensors on this decoder's device: frames uint8 [n_streams, n, 2048] -> out float32 / int16 (s16 output)
+        [n_streams, n, 2048, channels]. Ordered behind torch's current stream by default, as At1HipDecoder.decode_device."""
+        import torch
+        assert frames.dtype == torch.uint8 and frames.is_contiguous() and out.is_contiguous()
+        assert out.dtype in (torch.float32, torch.int16)
+        n = frames.shape[1]
+        assert tuple(frames.shape) == (self.n_streams, n, 2048), tuple(frames.shape)
+        assert tuple(out.shape) == (self.n_streams, n, 2048, self.channels), tuple(out.shape)
+        flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3PHIP_DECODE_S16 if out.dtype == torch.int16 else 0)
+        flags |= AT3HIP_ASYNC if asynchronous else 0
+        self._order_behind_torch(frames.device, ordered)
+        self.decode_ptr(frames.data_ptr(), n, out.data_ptr(), flags)
+
+
+def at3p_decoder_host_tables(lib_path=None):
+    """at3phip_decoder_host_tables (no GPU): the decoder's table block as bytes; its first 2048 are the DCT-IV cosines
+    double[16][16]."""
+    out = np.zeros(AT3PHIP_DECODER_TABLES_BYTES, np.uint8)
+    rc = load_library(lib_path).at3phip_decoder_host_tables(_vp(out), out.nbytes)
+    if rc != 0:
+        raise At3HipError(f"at3phip_decoder_host_tables failed ({rc})")
+    return out
 
 
 AT3PHIP_RESIDUAL_SCALE = 16

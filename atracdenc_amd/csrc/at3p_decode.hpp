@@ -1,0 +1,420 @@
+// ATRAC3plus decode kernels (gfx950): the decoder defined in include/at3phip.h (decoder section) for a batch of streams, every
+// frame of a call in parallel.
+//
+// What a frame needs of its past. Frame n's subband samples are its IMDCT's first half windowed with frame n-1's flags plus
+// frame n-1's second half windowed with the same flags (TAt3pMIDCT::Do). Its PCM is the synthesis filter over those samples and
+// the ring of the last 23 DCT-IV columns of frame n-1, which need frame n-1's samples [105, 128), and so frame n-2's IMDCT tail
+// and flags. So a frame needs the IMDCT outputs of frames n, n-1, n-2 and nothing is scanned:
+//   k_at3pd_unpack  one wavefront per (frame, stream): bit unpack of both channels (one lane), dequantisation, then the 16 x C
+//                   TMIDCT<256> (kissfft order, fft_lds) of the frame; writes the unwindowed IMDCT outputs and the window flags
+//   k_at3pd_synth   one workgroup per (frame, stream, channel): the windows with the (n-1, n) pairing and the overlap-add for
+//                   frame n and for frame n-1's last 23 columns, the rescale, the 151 DCT-IVs in f64, the 12-tap FIR, clamp,
+//                   f32 or s16 output
+//   k_at3pd_state   the call's last two frames become frames -2 and -1 of the next call
+// Every float and double operation is the definition's, in its order, without contraction; no scratch.
+#pragma once
+#include "at3_common.hpp"
+
+namespace at3p {
+
+constexpr int kDecLut2Blocks = 1024;   // second-level VLC blocks (16 entries each); the tables need 887
+
+// Constant tables of the decoder, built on the host (at3phip.hip) with the container's libm.
+struct DecTables {
+    double cos16[16][16];                // [k][n] = cos((M_PI / 16) * ((double)n + 0.5) * ((double)k + 0.5)), the "dct4" of the synthesis
+    float fir[384];                      // at3p_fir.inc: ff_ipqf_coeffs1[t][i] = fir[12 i + t], ff_ipqf_coeffs2[t][i] = fir[192 + 12 i + t]
+    float cs256[128];                    // TMIDCT<256>(): CalcSinCos(256, 128)
+    cpx tw64[64];                        // kissfft forward twiddles of the 64-point core
+    float sine128[128], sine64[64];      // SineWin128, SineWin64
+    float mant[8];                       // atrac3p_mant_tab
+    float scale[64];                     // NAt3p::TScaleTable::ScaleTable
+    uint8_t spec_tab[56][2];             // group_size | num_coeffs << 4, bits | is_signed << 4 of spectra tables 0..55
+    uint16_t wl_vlc[4][8];               // code | length << 12
+    uint8_t qu_to_sb[32], sb_powgrps[16];
+    // spectra tables 0..55: lut1[t][next 8 bits] = symbol | length << 8 (length 1..8), or 0x8000 | block for longer codes, whose
+    // entry is lut2[block][the 4 bits after those 8] = symbol | length << 8; length 0 = no code
+    uint16_t lut1[56][256];
+    uint16_t lut2[kDecLut2Blocks][16];
+};
+
+constexpr int kDecReasons = 6;   // at3phip_decoder_counters order
+enum { kRpOk = 0, kRpBadHeader, kRpUnsupported, kRpTonal, kRpBadCode, kRpReadPastEnd, kRpNoTerminator };
+
+// The raw / flags records of a call are frame-major with two leading slots, so that the carried frames -2 and -1 sit at the
+// same place whatever the number of frames of the call: record (slot, stream, channel) at (slot * S + s) * C + ch.
+__device__ __forceinline__ size_t decp_rec(int slot, int s, int ch, int S, int C) { return ((size_t)slot * S + s) * C + ch; }
+
+struct DecUnpackParams {
+    const DecTables* T;
+    const uint8_t* frames;        // [S][F][2048]
+    int32_t n_frames, n_streams, nch;
+    float* raw;                   // records of [16][256] floats: the TMIDCT<256> output per subband
+    uint16_t* flags;              // records: steep-window bits
+    unsigned long long* rejected; // [6]
+};
+
+// MSB-first reader over the frame staged in LDS as big-endian words (zero past the frame); reads must end within 16384 bits.
+// The two words around the read position are kept in a register.
+struct DecpBits {
+    const uint32_t* w;
+    int pos, bad, wi;
+    uint64_t win;
+    __device__ __forceinline__ explicit DecpBits(const uint32_t* words)
+        : w(words), pos(0), bad(0), wi(0), win(((uint64_t)words[0] << 32) | words[1]) {}
+    __device__ __forceinline__ uint32_t peek(int n) const { return (uint32_t)((win << (pos - 32 * wi)) >> (64 - n)); }
+    __device__ __forceinline__ void advance(int n)   // n <= 32
+    {
+        pos += n;
+        if ((pos >> 5) != wi) {
+            ++wi;
+            win = (win << 32) | w[wi + 1];
+        }
+    }
+    __device__ __forceinline__ uint32_t rd(int n)
+    {
+        if (bad || pos + n > 2048 * 8) {
+            bad = 1;
+            return 0;
+        }
+        const uint32_t v = peek(n);
+        advance(n);
+        return v;
+    }
+};
+
+__device__ __forceinline__ int decp_wl_vlc(DecpBits& b, const uint16_t* tab, int& invalid)
+{
+    if (b.bad) return 0;
+    const uint32_t v = b.peek(8);
+    for (int sym = 0; sym < 8; ++sym) {
+        const int len = tab[sym] >> 12, code = tab[sym] & 0xfff;
+        if (len && (int)(v >> (8 - len)) == code) {
+            if (b.pos + len > 2048 * 8) {
+                b.bad = 1;
+                return 0;
+            }
+            b.advance(len);
+            return sym;
+        }
+    }
+    invalid = 1;
+    return 0;
+}
+
+__device__ __forceinline__ int decp_spec_vlc(DecpBits& b, const DecTables* T, int t, int& invalid)
+{
+    if (b.bad) return 0;
+    const uint32_t v = b.peek(12);
+    uint32_t e = T->lut1[t][v >> 4];
+    if (e & 0x8000u) e = T->lut2[e & 0x7fffu][v & 15u];
+    const int len = (int)(e >> 8);
+    if (!len) {
+        invalid = 1;
+        return 0;
+    }
+    if (b.pos + len > 2048 * 8) {
+        b.bad = 1;
+        return 0;
+    }
+    b.advance(len);
+    return (int)(e & 0xffu);
+}
+
+// The frame's syntax (include/at3phip.h, step 1) and its dequantisation (step 2) on one lane; spec (LDS) is zero on entry.
+__device__ __forceinline__ int decp_parse(DecpBits& b, const DecTables* T, int C, float* spec, uint8_t (*wl)[32], uint8_t (*sf)[32],
+                                       uint8_t (*tab)[32], uint16_t* winf)
+{
+    int invalid = 0;
+#define DECP_CHK()                              \
+    do {                                        \
+        if (b.bad) return kRpReadPastEnd;       \
+        if (invalid) return kRpBadCode;         \
+    } while (0)
+    if (b.rd(1) != 0) return kRpBadHeader;
+    if ((int)b.rd(2) != C - 1) return kRpBadHeader;
+    const int nqu = (int)b.rd(5) + 1;
+    if (b.rd(1) != 0) return kRpUnsupported;
+    {
+        if (b.rd(2) != 3 || b.rd(2) != 0 || b.rd(2) != 0) return kRpUnsupported;
+        const int idx = (int)b.rd(2);
+        int w = (int)b.rd(3);
+        wl[0][0] = (uint8_t)w;
+        for (int i = 1; i < nqu; ++i) {
+            w = (w + decp_wl_vlc(b, T->wl_vlc[idx], invalid)) & 7;
+            wl[0][i] = (uint8_t)w;
+        }
+        DECP_CHK();
+    }
+    if (C == 2) {
+        if (b.rd(2) != 1 || b.rd(2) != 0) return kRpUnsupported;
+        const int idx = (int)b.rd(2);
+        for (int i = 0; i < nqu; ++i) wl[1][i] = (uint8_t)((wl[0][i] + decp_wl_vlc(b, T->wl_vlc[idx], invalid)) & 7);
+        DECP_CHK();
+    }
+    for (int ch = 0; ch < C; ++ch)
+        for (int i = 0; i < nqu; ++i)
+            if (wl[ch][i] == 0) return kRpBadCode;
+    for (int ch = 0; ch < C; ++ch) {
+        if (b.rd(2) != 0) return kRpUnsupported;
+        for (int i = 0; i < nqu; ++i) sf[ch][i] = (uint8_t)b.rd(6);
+        DECP_CHK();
+    }
+    const int full = (int)b.rd(1);
+    for (int ch = 0; ch < C; ++ch) {
+        if (b.rd(1) != 0 || b.rd(2) != 0 || b.rd(1) != 0) return kRpUnsupported;
+        for (int i = 0; i < nqu; ++i) tab[ch][i] = (uint8_t)b.rd(full + 2);
+        DECP_CHK();
+    }
+    for (int ch = 0; ch < C; ++ch) {
+        float* sp = spec + 2048 * ch;
+        for (int qu = 0; qu < nqu; ++qu) {
+            const int w = wl[ch][qu], t = w - 1 + 7 * tab[ch][qu];
+            const int gsz = T->spec_tab[t][0] & 15, nc = T->spec_tab[t][0] >> 4;
+            const int cbits = T->spec_tab[t][1] & 15, is_signed = T->spec_tab[t][1] >> 4;
+            const float mant = T->mant[w], scale = T->scale[sf[ch][qu]];
+            const int start = at3p_qu_start(qu), n = at3p_qu_start(qu + 1) - start;
+            for (int pos = 0; pos < n;) {
+                if (gsz != 1 && b.rd(1) == 0) {
+                    DECP_CHK();
+                    pos += gsz * nc;
+                    continue;
+                }
+                for (int j = 0; j < gsz; ++j) {
+                    const int val = decp_spec_vlc(b, T, t, invalid);
+                    DECP_CHK();
+                    for (int i = 0; i < nc; ++i, ++pos) {
+                        int m = (val >> (cbits * i)) & ((1 << cbits) - 1);
+                        if (is_signed) {
+                            m = (int)((uint32_t)m << (32 - cbits)) >> (32 - cbits);
+                        } else if (m != 0 && b.rd(1)) {
+                            m = -m;
+                        }
+                        DECP_CHK();
+                        sp[start + pos] = (float)m * mant * scale;
+                    }
+                }
+            }
+        }
+        const int npw = T->sb_powgrps[T->qu_to_sb[nqu - 1]];
+        for (int i = 0; i < npw; ++i) {
+            const uint32_t lev = b.rd(4);
+            DECP_CHK();
+            if (lev != 15) return kRpUnsupported;
+        }
+    }
+    if (C == 2) {
+        const uint32_t sn = b.rd(2);
+        DECP_CHK();
+        if (sn != 0) return kRpUnsupported;
+    }
+    const int sb_bits = T->qu_to_sb[31] + 1;
+    for (int ch = 0; ch < C; ++ch) {
+        uint32_t w = 0;
+        if (b.rd(1)) {
+            if (b.rd(1) == 0) {
+                w = 0xffffu;
+            } else {
+                for (int i = 0; i < sb_bits; ++i) w |= b.rd(1) << i;
+            }
+        }
+        DECP_CHK();
+        winf[ch] = (uint16_t)w;
+    }
+    for (int ch = 0; ch < C; ++ch) {
+        const uint32_t g = b.rd(1);
+        DECP_CHK();
+        if (g) return kRpUnsupported;
+    }
+    const uint32_t tonal = b.rd(1);
+    DECP_CHK();
+    if (tonal) return kRpTonal;
+    const uint32_t noise = b.rd(1);
+    DECP_CHK();
+    if (noise) return kRpUnsupported;
+    const uint32_t term = b.rd(2);
+    DECP_CHK();
+    if (term != 3) return kRpNoTerminator;
+#undef DECP_CHK
+    return kRpOk;
+}
+
+constexpr int kDecUnpackThreads = 64;   // one wavefront per frame: the parse is one lane, so frames in flight per CU count
+
+__global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack(DecUnpackParams p)
+{
+    constexpr int NT = kDecUnpackThreads;
+    __shared__ uint32_t s_w[512 + 2];                              // the frame, big-endian words, two zero words behind
+    __shared__ __attribute__((aligned(16))) float s_spec[2][2048];   // the dequantised spectra
+    __shared__ __attribute__((aligned(16))) cpx s_f[32 * 64];       // the 16 x C 64-point FFTs
+    __shared__ uint8_t s_wl[2][32], s_sf[2][32], s_tab[2][32];
+    __shared__ uint16_t s_win[2];
+    __shared__ int s_reason;
+
+    const DecTables* T = p.T;
+    const int f = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, C = p.nch;
+    const uint8_t* frame = p.frames + ((size_t)s * p.n_frames + f) * 2048;
+    for (int i = tid; i < 512 + 2; i += NT) {   // byte loads: a caller's device buffer need not be word-aligned
+        uint32_t w = 0;
+        if (i < 512)
+            for (int k = 0; k < 4; ++k) w = (w << 8) | frame[4 * i + k];
+        s_w[i] = w;
+    }
+    for (int i = tid; i < 2 * 2048; i += NT) (&s_spec[0][0])[i] = 0.0f;
+    if (tid < 2) s_win[tid] = 0;
+    __syncthreads();
+    if (tid == 0) {
+        DecpBits b(s_w);
+        const int why = decp_parse(b, T, C, &s_spec[0][0], s_wl, s_sf, s_tab, s_win);
+        s_reason = why;
+        if (why) atomicAdd(&p.rejected[why - 1], 1ull);
+    }
+    __syncthreads();
+    const bool rejected = s_reason != kRpOk;
+    if (tid < C) p.flags[decp_rec(f + 2, s, tid, p.n_streams, C)] = rejected ? (uint16_t)0 : s_win[tid];
+    // TMIDCT<256> pre-rotation per subband (odd subbands: SwapArray folded into the index), into the FFT's leaf order; a
+    // rejected frame has a zero spectrum
+    const float* cs = T->cs256;
+    for (int j = tid; j < C * 1024; j += NT) {
+        const int ch = j >> 10, band = (j >> 6) & 15, k2 = j & 63, n = 2 * k2;
+        const int a = band & 1 ? 127 - n : n, bb = band & 1 ? n : 127 - n;
+        const float* sp = &s_spec[ch][band * 128];
+        const float r0 = rejected ? 0.0f : sp[a];
+        const float i0 = rejected ? 0.0f : sp[bb];
+        const float c = cs[n], sn = cs[n + 1];
+        cpx v;
+        v.r = -2.0f * (i0 * sn + r0 * c);
+        v.i = -2.0f * (i0 * c - r0 * sn);
+        s_f[(ch * 16 + band) * 64 + at3::fft_leaf_pos<64>(k2)] = v;
+    }
+    __syncthreads();
+    at3::fft_lds<64, false>(s_f, 64, 16 * C, T->tw64, tid, NT);
+    // post-rotation (mdct.h): the whole Buf[256] of each subband
+    for (int j = tid; j < C * 1024; j += NT) {
+        const int ch = j >> 10, band = (j >> 6) & 15, k2 = j & 63, n = 2 * k2;
+        const cpx v = s_f[j];
+        const float c = cs[n], sn = cs[n + 1];
+        const float r1 = v.r * c + v.i * sn, i1 = v.r * sn - v.i * c;
+        float* o = p.raw + decp_rec(f + 2, s, ch, p.n_streams, C) * 4096 + band * 256;
+        if (n < 64) {
+            o[191 - n] = r1;
+            o[192 + n] = r1;
+            o[64 + n] = i1;
+            o[63 - n] = -i1;
+        } else {
+            o[191 - n] = r1;
+            o[n - 64] = -r1;
+            o[64 + n] = i1;
+            o[319 - n] = i1;
+        }
+    }
+}
+
+struct DecSynthParams {
+    const DecTables* T;
+    const float* raw;
+    const uint16_t* flags;
+    void* out;                    // [S][F][2048][C] float or int16
+    int32_t n_frames, n_streams, nch, s16;
+};
+
+constexpr int kDecHist = 23;              // frame n-1's DCT-IV columns the FIR reaches
+constexpr int kDecCols = 128 + kDecHist;
+
+// the windowed first half (x = inv[j]) and second half (y = inv[128 + j]) of TAt3pMIDCT::Do, flags `fl` of subband b
+__device__ __forceinline__ float decp_win_first(const DecTables* T, float x, uint32_t fl, int b, int j)
+{
+    if ((fl >> b) & 1u) return j < 32 ? 0.0f : j < 96 ? x * T->sine64[j - 32] : x * 2.0f;
+    return x * T->sine128[j];
+}
+__device__ __forceinline__ float decp_win_second(const DecTables* T, float y, uint32_t fl, int b, int j)
+{
+    if ((fl >> b) & 1u) return j < 32 ? y * 2.0f : j < 96 ? y * T->sine64[95 - j] : 0.0f;
+    return y * T->sine128[127 - j];
+}
+
+__global__ __launch_bounds__(256) void k_at3pd_synth(DecSynthParams p)
+{
+    __shared__ float s_x[16][kDecCols + 1];   // rescaled subband samples: column c = frame n-1's sample 105 + c (c < 23), else frame n's c - 23
+    __shared__ float s_d[kDecCols][16];       // the DCT-IV outputs per column (idct_out)
+    __shared__ float s_fir[384];
+
+    const DecTables* T = p.T;
+    const int f = blockIdx.x, sc = blockIdx.y, tid = threadIdx.x, C = p.nch, S = p.n_streams;
+    const int s = sc / C, ch = sc - s * C;
+    const uint32_t fl2 = p.flags[decp_rec(f, s, ch, S, C)];       // frame n-2
+    const uint32_t fl1 = p.flags[decp_rec(f + 1, s, ch, S, C)];   // frame n-1
+    const float* r0 = p.raw + decp_rec(f, s, ch, S, C) * 4096;
+    const float* r1 = p.raw + decp_rec(f + 1, s, ch, S, C) * 4096;
+    const float* r2 = p.raw + decp_rec(f + 2, s, ch, S, C) * 4096;
+    for (int i = tid; i < 384; i += 256) s_fir[i] = T->fir[i];
+    const float rescale = (float)(32768.0 / 1.122018);
+    for (int i = tid; i < 16 * kDecCols; i += 256) {
+        const int b = i / kDecCols, c = i - b * kDecCols;
+        float v;
+        if (c < kDecHist) {
+            const int j = 128 - kDecHist + c;
+            v = decp_win_first(T, r1[b * 256 + j], fl2, b, j) + decp_win_second(T, r0[b * 256 + 128 + j], fl2, b, j);
+        } else {
+            const int j = c - kDecHist;
+            v = decp_win_first(T, r2[b * 256 + j], fl1, b, j) + decp_win_second(T, r1[b * 256 + 128 + j], fl1, b, j);
+        }
+        s_x[b][c] = v * rescale;
+    }
+    __syncthreads();
+    // dct4: out[15 - k] = (float)(sum_n (double)x[n] * cos16[k][n] * (1.0 / 1024)), the sum in order, each step rounded
+    {
+        const int k = tid & 15;
+        double cr[16];
+#pragma unroll
+        for (int n = 0; n < 16; ++n) cr[n] = T->cos16[k][n];
+        for (int c = tid >> 4; c < kDecCols; c += 16) {
+            double sum = 0.0;
+#pragma unroll
+            for (int n = 0; n < 16; ++n) sum += (double)s_x[n][c] * cr[n];
+            s_d[c][15 - k] = (float)(sum * (1.0 / 1024));
+        }
+    }
+    __syncthreads();
+    // the FIR: output o = 16 s + i sums 12 taps over the columns 2t and 2t + 1 back, from +0.0f, in tap order
+    const size_t F = p.n_frames;
+    for (int o = tid; o < 2048; o += 256) {
+        const int sm = o >> 4, i = o & 15, cs = sm + kDecHist;
+        float acc = 0.0f;
+        if (i < 8) {
+#pragma unroll
+            for (int t = 0; t < 12; ++t) {
+                const float a = s_d[cs - 2 * t][i + 8] * s_fir[12 * i + t];
+                const float d = s_d[cs - 2 * t - 1][7 - i] * s_fir[192 + 12 * i + t];
+                acc = acc + (a + d);
+            }
+        } else {
+            const int ii = i - 8;
+#pragma unroll
+            for (int t = 0; t < 12; ++t) {
+                const float e = s_d[cs - 2 * t][15 - ii] * s_fir[12 * i + t];
+                const float g = s_d[cs - 2 * t - 1][ii] * s_fir[192 + 12 * i + t];
+                acc = acc + (e + g);
+            }
+        }
+        acc = acc > 1.0f ? 1.0f : acc;
+        acc = acc < -1.0f ? -1.0f : acc;
+        const size_t idx = (((size_t)s * F + f) * 2048 + o) * C + ch;
+        if (p.s16) ((int16_t*)p.out)[idx] = (int16_t)__float2int_rn(acc * 32767.0f);
+        else ((float*)p.out)[idx] = acc;
+    }
+}
+
+// The call's last two frames (slots F, F + 1) become slots 0 and 1 of the next call.
+__global__ __launch_bounds__(256) void k_at3pd_state(float* raw, uint16_t* flags, int32_t n_frames, int32_t n_streams, int32_t nch)
+{
+    __shared__ float s_raw[2][4096];
+    __shared__ uint16_t s_fl[2];
+    const int sc = blockIdx.x, s = sc / nch, ch = sc - s * nch, tid = threadIdx.x;
+    for (int i = tid; i < 8192; i += 256) s_raw[i >> 12][i & 4095] = raw[decp_rec(n_frames + (i >> 12), s, ch, n_streams, nch) * 4096 + (i & 4095)];
+    if (tid < 2) s_fl[tid] = flags[decp_rec(n_frames + tid, s, ch, n_streams, nch)];
+    __syncthreads();
+    for (int i = tid; i < 8192; i += 256) raw[decp_rec(i >> 12, s, ch, n_streams, nch) * 4096 + (i & 4095)] = s_raw[i >> 12][i & 4095];
+    if (tid < 2) flags[decp_rec(tid, s, ch, n_streams, nch)] = s_fl[tid];
+}
+
+}  // namespace at3p

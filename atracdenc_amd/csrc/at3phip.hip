@@ -417,3 +417,201 @@ int at3phip_host_tables(void* dst, size_t bytes)
 }
 
 }  // extern "C"
+
+// ---- decoder (include/at3phip.h, decoder section) ------------------------------------------------------------------------------
+#include <cmath>
+
+#include "at3_decoder_host.hpp"
+#include "at3p_decode.hpp"
+
+static_assert(sizeof(DecTables) == AT3PHIP_DECODER_TABLES_BYTES, "at3phip.h documents the decoder's table block size");
+
+struct at3phip_decoder : at3host::DecoderBase {
+    at3phip_decoder_config cfg;
+    DecTables* d_tables = nullptr;
+    uint8_t* d_frames = nullptr;   // staging for host frames [S][F][2048]
+    float* d_raw = nullptr;        // [F + 2][S][C][16][256]: slots 0, 1 = the carried frames -2, -1
+    uint16_t* d_flags = nullptr;   // [F + 2][S][C]
+    void* d_out = nullptr;         // staging for host output [S][F][2048][C] float32
+    // (d_rejected: [kDecReasons])
+};
+
+namespace {
+
+#include "at3p_mant.inc"
+
+// The decoder's table block: the shared entries from the encoder's builder, the cosines of the synthesis's DCT-IV with the
+// host's libm (never constant-folded: optnone), and the two-level VLC look-up expanded from the frame writer's code tables.
+// false when the encoder's table block cannot be allocated (the decoder is then not created).
+__attribute__((optnone, noinline)) bool build_decp_tables(DecTables* t)
+{
+    memset(t, 0, sizeof(*t));
+    Tables* enc = new (std::nothrow) Tables();
+    if (!enc) return false;
+    build_tables(enc);
+    memcpy(t->fir, enc->fir, sizeof(t->fir));
+    memcpy(t->tw64, enc->tw64, sizeof(t->tw64));
+    memcpy(t->sine128, enc->sine128, sizeof(t->sine128));
+    memcpy(t->sine64, enc->sine64, sizeof(t->sine64));
+    delete enc;
+    for (int k = 0; k < 16; ++k)
+        for (int n = 0; n < 16; ++n) t->cos16[k][n] = cos((M_PI / 16) * ((double)n + 0.5) * ((double)k + 0.5));
+    at3::mdct_sincos(t->cs256, 256, 128.0f);   // TMIDCT<256>(): TMIDCT(float scale = TN) : TMDCTBase(TN, scale / 2)
+    memcpy(t->mant, AT3P_MANT, sizeof(t->mant));
+    memcpy(t->scale, AT3P_SCALE, sizeof(t->scale));
+    memcpy(t->spec_tab, AT3P_SPEC_TAB, sizeof(t->spec_tab));
+    memcpy(t->wl_vlc, AT3P_WL_VLC, sizeof(t->wl_vlc));
+    memcpy(t->qu_to_sb, AT3P_QU_TO_SB, sizeof(t->qu_to_sb));
+    memcpy(t->sb_powgrps, AT3P_SB_POWGRPS, sizeof(t->sb_powgrps));
+    int blocks = 0;
+    for (int tb = 0; tb < 56; ++tb) {
+        for (int sym = 0; sym < AT3P_VLC_OFF[tb + 1] - AT3P_VLC_OFF[tb]; ++sym) {
+            const uint16_t e = AT3P_VLC[AT3P_VLC_OFF[tb] + sym];
+            const int len = e >> 12, code = e & 0xfff;
+            const uint16_t entry = (uint16_t)(sym | (len << 8));
+            if (!len) continue;
+            if (len <= 8) {
+                for (int x = 0; x < (1 << (8 - len)); ++x) t->lut1[tb][(code << (8 - len)) | x] = entry;
+                continue;
+            }
+            const int pre = code >> (len - 8);
+            if (!(t->lut1[tb][pre] & 0x8000u)) {
+                if (blocks == kDecLut2Blocks) return false;
+                t->lut1[tb][pre] = (uint16_t)(0x8000u | blocks++);
+            }
+            uint16_t* blk = t->lut2[t->lut1[tb][pre] & 0x7fffu];
+            const int low = code & ((1 << (len - 8)) - 1);   // the code's bits after the first 8
+            for (int x = 0; x < (1 << (12 - len)); ++x) blk[(low << (12 - len)) | x] = entry;
+        }
+    }
+    return true;
+}
+
+int decp_reset_state(at3phip_decoder* d)
+{
+    const size_t S = d->cfg.n_streams, C = d->cfg.channels;
+    HIPCHK(d, hipMemsetAsync(d->d_raw, 0, 2 * S * C * 4096 * sizeof(float), d->stream));
+    HIPCHK(d, hipMemsetAsync(d->d_flags, 0, 2 * S * C * sizeof(uint16_t), d->stream));
+    HIPCHK(d, hipMemsetAsync(d->d_rejected, 0, kDecReasons * sizeof(unsigned long long), d->stream));
+    HIPCHK(d, hipStreamSynchronize(d->stream));
+    return AT3HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int at3phip_decoder_create(const at3phip_decoder_config* cfg, at3phip_decoder** out)
+{
+    if (!cfg || !out) return AT3HIP_EINVAL;
+    *out = nullptr;
+    if ((cfg->channels != 1 && cfg->channels != 2) || cfg->n_streams < 1 || cfg->max_frames < 1) return AT3HIP_EINVAL;
+    if ((long long)cfg->n_streams * cfg->channels > at3host::kMaxGridY) return AT3HIP_EINVAL;   // (stream, channel) is gridDim.y
+    // every buffer index stays inside size_t and the kernels' int frame counts
+    if (((long long)cfg->max_frames + 2) * cfg->n_streams * cfg->channels > (1ll << 31) / 16) return AT3HIP_EINVAL;
+    return at3host::create_decoder(cfg, out, build_decp_tables, at3phip_decoder_destroy, [](at3phip_decoder* d) {
+        const size_t S = d->cfg.n_streams, F = d->cfg.max_frames, C = d->cfg.channels;
+        int rc;
+        if ((rc = dev_alloc(d, &d->d_frames, S * F * 2048)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_raw, (F + 2) * S * C * 4096)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_flags, (F + 2) * S * C)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_rejected, kDecReasons)) != AT3HIP_OK) return rc;
+        float* d_out = nullptr;
+        if ((rc = dev_alloc(d, &d_out, S * F * 2048 * C)) != AT3HIP_OK) return rc;
+        d->d_out = d_out;
+        return decp_reset_state(d);
+    });
+}
+
+void at3phip_decoder_destroy(at3phip_decoder* d)
+{
+    if (d) at3host::destroy_decoder(d, {d->d_tables, d->d_frames, d->d_raw, d->d_flags, d->d_rejected, d->d_out});
+}
+
+const char* at3phip_decoder_last_error(const at3phip_decoder* d) { return at3host::decoder_last_error(d); }
+
+int at3phip_decoder_sync(at3phip_decoder* d) { return at3host::decoder_sync(d); }
+
+int at3phip_decoder_reset(at3phip_decoder* d)
+{
+    if (!d) return AT3HIP_EINVAL;
+    at3host::DeviceGuard guard(d->device);
+    HIPCHK(d, guard.error());
+    return decp_reset_state(d);
+}
+
+int at3phip_decoder_set_stream(at3phip_decoder* d, void* hip_stream) { return at3host::decoder_set_stream(d, hip_stream); }
+
+int at3phip_decoder_get_counters(at3phip_decoder* d, at3phip_decoder_counters* out, int32_t reset)
+{
+    if (!d || !out) return AT3HIP_EINVAL;
+    unsigned long long h[kDecReasons] = {0, 0, 0, 0, 0, 0};
+    const int rc = at3host::read_counters(d, h, reset);
+    if (rc != AT3HIP_OK) return rc;
+    out->bad_header = h[0];
+    out->unsupported_syntax = h[1];
+    out->tonal_present = h[2];
+    out->bad_code = h[3];
+    out->read_past_end = h[4];
+    out->no_terminator = h[5];
+    return AT3HIP_OK;
+}
+
+int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags)
+{
+    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3PHIP_DECODE_S16;
+    if (!d || !frames || !pcm || n_frames < 1 || n_frames > d->cfg.max_frames || (flags & ~known))
+        return d ? fail(d, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
+    at3host::DeviceGuard guard(d->device);
+    HIPCHK(d, guard.error());
+    const size_t S = d->cfg.n_streams, F = (size_t)n_frames, C = d->cfg.channels;
+    const bool s16 = flags & AT3PHIP_DECODE_S16;
+    hipStream_t st = d->stream;
+    const uint8_t* d_frames = frames;
+    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
+        HIPCHK(d, hipMemcpyAsync(d->d_frames, frames, S * F * 2048, hipMemcpyHostToDevice, st));
+        d_frames = d->d_frames;
+    }
+    void* d_pcm = (flags & AT3HIP_OUT_ON_DEVICE) ? pcm : d->d_out;
+
+    DecUnpackParams up;
+    up.T = d->d_tables;
+    up.frames = d_frames;
+    up.n_frames = n_frames;
+    up.n_streams = (int)S;
+    up.nch = (int)C;
+    up.raw = d->d_raw;
+    up.flags = d->d_flags;
+    up.rejected = d->d_rejected;
+    hipLaunchKernelGGL(k_at3pd_unpack, dim3((unsigned)F, (unsigned)S), dim3(kDecUnpackThreads), 0, st, up);
+    HIPCHK(d, hipGetLastError());
+    DecSynthParams sp;
+    sp.T = d->d_tables;
+    sp.raw = d->d_raw;
+    sp.flags = d->d_flags;
+    sp.out = d_pcm;
+    sp.n_frames = n_frames;
+    sp.n_streams = (int)S;
+    sp.nch = (int)C;
+    sp.s16 = s16 ? 1 : 0;
+    hipLaunchKernelGGL(k_at3pd_synth, dim3((unsigned)F, (unsigned)(S * C)), dim3(256), 0, st, sp);
+    HIPCHK(d, hipGetLastError());
+    hipLaunchKernelGGL(k_at3pd_state, dim3((unsigned)(S * C)), dim3(256), 0, st, d->d_raw, d->d_flags, n_frames, (int32_t)S, (int32_t)C);
+    HIPCHK(d, hipGetLastError());
+    if (!(flags & AT3HIP_OUT_ON_DEVICE))
+        HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 2048 * C * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
+    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::decoder_sync(d);
+}
+
+int at3phip_decoder_host_tables(void* dst, size_t bytes)
+{
+    if (!dst || bytes != sizeof(DecTables)) return AT3HIP_EINVAL;
+    DecTables* t = new (std::nothrow) DecTables();
+    if (!t) return AT3HIP_ENOMEM;
+    const bool ok = build_decp_tables(t);
+    if (ok) memcpy(dst, t, sizeof(DecTables));
+    delete t;
+    return ok ? AT3HIP_OK : AT3HIP_ENOMEM;
+}
+
+}  // extern "C"

@@ -176,11 +176,11 @@ int decode_aea(const std::string& inFile, const std::string& outFile, bool noStd
 // Anything else goes to the AEA path unchanged, except ATRAC3plus (OMA codec id 1, RIFF 0xFFFE) and headerless ATRAC3 (the
 // first byte carries the 6-bit unit id 0x28), which are refused. The output is a 16-bit stereo WAV written as the AEA path
 // writes it, 1024 samples per frame, the codec delay not trimmed; rejected units are counted and reported per reason.
-enum class EInput { AEA, ATRAC3, REFUSED };
+enum class EInput { AEA, ATRAC3, ATRAC3PLUS, REFUSED };
 
 struct TAt3Input {
     int64_t offset = 0, frames = 0;
-    int frameSize = 0, js = 0;
+    int frameSize = 0, js = 0, channels = 2;
     std::string container;
 };
 
@@ -212,9 +212,19 @@ EInput probe_input(const std::string& inFile, TAt3Input& at3)
     if (got >= 96 && !memcmp(h, "EA3", 3)) {
         const uint32_t word = (uint32_t)h[32] << 24 | (uint32_t)h[33] << 16 | (uint32_t)h[34] << 8 | h[35];
         const uint32_t id = word >> 24;
-        if (id == 1) {
-            std::cerr << "Fatal error: ATRAC3plus decoding is not supported" << std::endl;
-            return EInput::REFUSED;
+        if (id == 1) {   // ATRAC3plus: channel id in bits 10-12, (FrameSz - 8) / 8 in the low 10 bits
+            const int chId = (int)((word >> 10) & 7), frameBytes = (int)(word & 0x3FF) * 8 + 8;
+            if ((chId != 1 && chId != 2) || frameBytes != 2048) {
+                std::cerr << "Fatal error: ATRAC3plus decoding is not supported for channel id " << chId << ", frame size "
+                          << frameBytes << std::endl;
+                return EInput::REFUSED;
+            }
+            at3.container = "OMA";
+            at3.offset = 96;
+            at3.frameSize = 2048;
+            at3.channels = chId;
+            at3.frames = (fileSize - 96) / 2048;
+            return EInput::ATRAC3PLUS;
         }
         if (id != 0) {
             std::cerr << "Fatal error: OMA codec id " << id << " is not ATRAC3" << std::endl;
@@ -228,11 +238,17 @@ EInput probe_input(const std::string& inFile, TAt3Input& at3)
     } else if (got >= 12 && !memcmp(h, "RIFF", 4) && !memcmp(h + 8, "WAVE", 4)) {
         int64_t pos = 12, dataPos = -1, dataLen = 0;
         int tag = -1;
+        bool at3pGuid = false;
         while (pos + 8 <= got) {
             const uint32_t sz = le(h + pos + 4, 4);
             if (!memcmp(h + pos, "fmt ", 4) && pos + 8 + 18 <= got) {
                 tag = (int)le(h + pos + 8, 2);
+                at3.channels = (int)le(h + pos + 10, 2);
                 at3.frameSize = (int)le(h + pos + 20, 2);
+                // WAVE_FORMAT_EXTENSIBLE: the ATRAC3plus sub-format GUID at byte 24 of the format (at3hip_io.hpp)
+                static const uint8_t kAt3pGuid[16] = {0xBF, 0xAA, 0x23, 0xE9, 0x58, 0xCB, 0x71, 0x44,
+                                                      0xA1, 0x19, 0xFF, 0xFA, 0x01, 0xE4, 0xCE, 0x62};
+                if (tag == 0xFFFE && sz >= 40 && pos + 8 + 40 <= got) at3pGuid = !memcmp(h + pos + 8 + 24, kAt3pGuid, 16);
                 if (tag == 0x270 && sz >= 32 && pos + 8 + 32 <= got) at3.js = (int)le(h + pos + 8 + 26, 2);
             } else if (!memcmp(h + pos, "data", 4)) {
                 dataPos = pos + 8;
@@ -242,8 +258,19 @@ EInput probe_input(const std::string& inFile, TAt3Input& at3)
             pos += 8 + sz + (sz & 1);
         }
         if (tag == 0xFFFE) {
-            std::cerr << "Fatal error: ATRAC3plus decoding is not supported" << std::endl;
-            return EInput::REFUSED;
+            if (!at3pGuid || at3.frameSize != 2048 || (at3.channels != 1 && at3.channels != 2)) {
+                std::cerr << "Fatal error: ATRAC3plus decoding is not supported for " << (at3pGuid ? "" : "a sub-format other than ATRAC3plus, ")
+                          << at3.channels << " channels, block align " << at3.frameSize << std::endl;
+                return EInput::REFUSED;
+            }
+            if (dataPos < 0) {
+                std::cerr << "Fatal error: RIFF ATRAC3plus file without a data chunk" << std::endl;
+                return EInput::REFUSED;
+            }
+            at3.container = "RIFF";
+            at3.offset = dataPos;
+            at3.frames = std::min<int64_t>(dataLen, fileSize - dataPos) / 2048;
+            return EInput::ATRAC3PLUS;
         }
         if (tag != 0x270) return EInput::AEA;
         if (dataPos < 0) {
@@ -338,6 +365,77 @@ int decode_at3(const std::string& inFile, const std::string& outFile, const TAt3
     return 0;
 }
 
+// `-d` on an ATRAC3plus OMA / RIFF file: a 16-bit WAV with the stream's channel count, 2048 samples per frame, the codec delay
+// (2416 samples) not trimmed; rejected frames are counted and reported per reason.
+int decode_at3p(const std::string& inFile, const std::string& outFile, const TAt3Input& at3, bool noStdOut, int batch, int device)
+{
+    std::ifstream in(inFile, std::ios::binary);
+    if (!in) {
+        std::cerr << "Fatal error: unable to open input file '" << inFile << "'" << std::endl;
+        return 1;
+    }
+    in.seekg(at3.offset, std::ios::beg);
+    const int64_t nOut = at3.frames;
+    const uint32_t nch = (uint32_t)at3.channels;
+    if (!noStdOut)
+        std::cout << "Input\n Filename: " << inFile << "\n Container: " << at3.container << "\n Codec: ATRAC3plus, " << nch
+                  << (nch == 1 ? " channel" : " channels") << "\nOutput:\n Filename: " << outFile << "\n Codec: PCM" << std::endl;
+    std::ofstream out(outFile, std::ios::binary);
+    if (!out) {
+        std::cerr << "Fatal error: unable to open output file '" << outFile << "'" << std::endl;
+        return 1;
+    }
+    if (nOut * 2048 * nch * 2 >= (int64_t)UINT32_MAX - 36) {
+        std::cerr << "Fatal error: output too long for a WAV file" << std::endl;
+        return 1;
+    }
+    write_wav_header(out, nch, (uint32_t)(nOut * 2048 * nch * 2));
+    if (nOut == 0) {
+        if (!noStdOut) std::cout << "\nDone" << std::endl;
+        return 0;
+    }
+    const int B = (int)std::min<int64_t>(batch < 1 ? 1 : batch, nOut);
+    at3phip_decoder* dec = nullptr;
+    at3phip_decoder_config cfg{(int32_t)nch, 1, B, device};
+    int rc = at3phip_decoder_create(&cfg, &dec);
+    if (rc != AT3HIP_OK) {
+        std::cerr << "Fatal error: at3phip_decoder_create failed (" << rc << ")" << std::endl;
+        return 1;
+    }
+    std::vector<uint8_t> frames((size_t)B * 2048);
+    std::vector<int16_t> pcm((size_t)B * 2048 * nch);
+    for (int64_t f0 = 0; f0 < nOut; f0 += B) {
+        const int n = (int)std::min<int64_t>(B, nOut - f0);
+        if (!in.read((char*)frames.data(), (std::streamsize)n * 2048)) {
+            std::cerr << "Fatal error: Can't read ATRAC3plus frame" << std::endl;
+            at3phip_decoder_destroy(dec);
+            return 1;
+        }
+        rc = at3phip_decode(dec, frames.data(), n, pcm.data(), AT3PHIP_DECODE_S16);
+        if (rc != AT3HIP_OK) {
+            std::cerr << "Encode/Decode error: at3phip_decode: " << at3phip_decoder_last_error(dec) << std::endl;
+            at3phip_decoder_destroy(dec);
+            return 1;
+        }
+        out.write((const char*)pcm.data(), (std::streamsize)n * 2048 * nch * 2);   // little-endian host
+    }
+    at3phip_decoder_counters c{};
+    rc = at3phip_decoder_get_counters(dec, &c, 0);
+    at3phip_decoder_destroy(dec);
+    if (rc != AT3HIP_OK) {
+        std::cerr << "Fatal error: at3phip_decoder_get_counters failed (" << rc << ")" << std::endl;
+        return 1;
+    }
+    const std::pair<const char*, uint64_t> reasons[] = {
+        {"bad header or block type", c.bad_header}, {"unsupported syntax element", c.unsupported_syntax},
+        {"tonal block present", c.tonal_present}, {"invalid code or out-of-range value", c.bad_code},
+        {"read past the end of the frame", c.read_past_end}, {"missing terminator", c.no_terminator}};
+    for (const auto& r : reasons)
+        if (r.second) std::cerr << "Skipped invalid ATRAC3plus frames (" << r.first << "): " << r.second << std::endl;
+    if (!noStdOut) std::cout << "\nDone" << std::endl;
+    return 0;
+}
+
 }  // namespace
 
 static int usage()
@@ -348,7 +446,7 @@ static int usage()
                  "                 [--container aea|raw] [--nostdout] [--batch blocks] [--device n]\n"
                  "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
                  "       at3hipenc -d -i in.aea -o out.wav [--nostdout] [--batch frames] [--device n]\n"
-                 "       at3hipenc -d -i in.{oma|at3|wav} -o out.wav [--nostdout] [--batch frames] [--device n]   (ATRAC3, by content)\n";
+                 "       at3hipenc -d -i in.{oma|at3|wav} -o out.wav [--nostdout] [--batch frames] [--device n]   (ATRAC3 / ATRAC3plus, by content)\n";
     return 1;
 }
 
@@ -392,6 +490,7 @@ int main(int argc, char** argv)
         const EInput kind = probe_input(inFile, at3);
         if (kind == EInput::REFUSED) return 1;
         if (kind == EInput::ATRAC3) return decode_at3(inFile, outFile, at3, noStdOut, batch, device);
+        if (kind == EInput::ATRAC3PLUS) return decode_at3p(inFile, outFile, at3, noStdOut, batch, device);
         return decode_aea(inFile, outFile, noStdOut, batch, device);
     }
     if ((codec != "atrac3" && codec != "atrac1" && codec != "atrac3plus") || inFile.empty() || outFile.empty()) return usage();

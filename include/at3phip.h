@@ -96,6 +96,105 @@ int at3phip_host_tables(void* dst, size_t bytes);
 #define AT3PHIP_WRITE_TABLES_BYTES 41384
 int at3phip_host_write_tables(void* dst, size_t bytes);
 
+/* ---- decoder ---------------------------------------------------------------------------------------------------------------
+ * A batched ATRAC3plus decoder: frames as TAt3PBitStream::WriteFrame writes them without a tonal block (at3p_bitstream.cpp:
+ * 101-726) -> PCM, for a batch of independent streams, every frame of a call in parallel. The reference has no ATRAC3plus decoder;
+ * steps 1, 2 and 4 are this project's definition, steps 3 and 5 restate the reference's synthesis half bit for bit.
+ *
+ * Definition. A frame is AT3PHIP_FRAME_BYTES (2048) bytes holding one channel unit of `channels` channels; it gives 2048 samples
+ * per channel.
+ *   1. Unpack, MSB first, in the writer's order (every "must" failing rejects the frame, rule 7):
+ *      - 1 bit, must be 0; block type (2 bits), must be channels - 1; quant units - 1 (5 bits) = nqu - 1; mute (1 bit), must be 0.
+ *      - Word lengths (TWordLenEncoder, :170-252). Channel 0: mode (2 bits, must be 3), weight index and coded values (2 bits
+ *        each, must be 0), a table index i (2 bits), wl0[0] (3 bits), then per further unit a code of AT3P_WL_VLC[i]:
+ *        wl0[q] = (wl0[q-1] + d) & 7. Channel 1: mode (2 bits, must be 1), 2 bits (must be 0), a table index i (2 bits), then per
+ *        unit a code d of AT3P_WL_VLC[i]: wl1[q] = (wl0[q] + d) & 7.
+ *        Decision: a word length of 0 (never written: allocTable's minimum is 1) is an out-of-range value and rejects the frame.
+ *      - Scale-factor indices (TSfIdxEncoder, :254-276): per channel mode (2 bits, must be 0), then 6 bits per unit.
+ *      - Code-table indices (:278-306): the full-table flag f (1 bit); per channel table type (1 bit), mode (2 bits) and
+ *        coded-values flag (1 bit), all must be 0, then an index of f + 2 bits per unit.
+ *      - Per channel, the spectra (EncodeQuSpectra, :310-373): unit q is coded with spectra table wl - 1 + 7 * index
+ *        (atrac3p_spectra_tabs: group size, coefficients per code, bits, signedness); each group of a table whose group size is
+ *        not 1 is preceded by a flag bit, 0 = the group is all zero; a code carries its coefficients in `bits`-bit fields from the
+ *        low end (two's complement for signed tables); an unsigned table puts one sign bit (1 = negative) after the code per
+ *        non-zero coefficient, in coefficient order. Then 4 x subband_to_num_powgrps[qu_to_subband[nqu - 1]] bits of power
+ *        compensation levels, each must be 15.
+ *      - Stereo: swap / negate (2 bits), must be 0. Per channel the window shape: 0 = all sine; 1 0 = all 16 subbands steep;
+ *        1 1 = one bit per subband b = 0..15 (1 = steep). Decision: 16 bits whatever nqu, the writer's layout: its tonal part is
+ *        formed once, in the pass with 32 units (sbNum = qu_to_subband[31] + 1, at3p_bitstream.cpp:663-684), so reading
+ *        qu_to_subband[nqu - 1] + 1 bits would misread its frames with fewer units.
+ *      - Per channel gain compensation (1 bit), must be 0; the tonal flag (1 bit), must be 0; the noise flag (1 bit), must be 0;
+ *        the terminator (2 bits), must be 3. Bits after it are ignored.
+ *   2. Dequantise: line k of unit q = (float)m * atrac3p_mant_tab[wl] * ScaleTable[sf], left to right in float (no FMA); lines of
+ *      no coded unit are +0.0f. Unit boundaries are TScaleTable::SpecsPerBlock's.
+ *   3. Per channel TAt3pMIDCT::Do (at3p_mdct.cpp:103-152): odd subbands reversed, TMIDCT<256> at its default scale, frame n's
+ *      first half windowed with frame n-1's flags and its second half with frame n's, overlap-added with frame n-1's windowed
+ *      second half.
+ *   4. Rescale: every subband sample times (float)(32768.0 / 1.122018), one float multiply (undoes EncodeFrame's division,
+ *      at3p.cpp:143-147).
+ *   5. Per channel ff_atrac3p_ipqf (atrac3plus_pqf/ut/atrac3plusdsp.c): per subband sample column the DCT-IV "dct4" in double,
+ *      sum += x[n] * cos((M_PI / 16) * ((double)n + 0.5) * ((double)k + 0.5)) for n = 0..15 (each product and sum rounded, no
+ *      FMA; the cosines from the host's libm), stored reversed as (float)(sum * (1.0 / 1024)); a 24-row history ring
+ *      (mod23_lut is a mod-24 table: lut[0] = 23, lut[25] = 0), so a frame's first samples reach back 23 columns into frame n-1;
+ *      the 12-tap FIR in float, out = out + ((h1 * c1) + (h2 * c2)) tap by tap from +0.0f.
+ *   6. Clamp to [-1, 1]; float32, or int16 = lrintf(x * 32767.0f) with AT3PHIP_DECODE_S16. Frame n gives samples
+ *      [2048 n, 2048 n + 2048) of the stream: the codec delay (2416 samples against at3phip_encode_frames' input: one frame of
+ *      the transform and the filter bank's 368) is not trimmed.
+ *   7. A frame is rejected (counted per reason, at3phip_decoder_counters) for: a bad first bit or block type; a syntax element
+ *      outside what the writer emits (mute, modes, power levels other than 15, swap / negate, gain compensation, noise); a
+ *      tonal block; an invalid code or an out-of-range value (every code table is complete, so this is a word length of 0);
+ *      a read past the frame's 2048 bytes; a terminator other than 3. A rejected frame decodes as a zero spectrum in every
+ *      channel with all-sine windows, and those are the flags frame n+1 pairs with. */
+typedef struct at3phip_decoder at3phip_decoder;
+
+typedef struct at3phip_decoder_config {
+    int32_t channels;     /* 1 or 2: must match the frames' block type */
+    int32_t n_streams;    /* independent streams decoded side by side */
+    int32_t max_frames;   /* upper bound of frames per stream per at3phip_decode call */
+    int32_t device_id;
+} at3phip_decoder_config;
+
+/* The context's stream is non-blocking; see DEVICE BUFFERS AND STREAMS (at3hip.h) and at3phip_decoder_set_stream. */
+int at3phip_decoder_create(const at3phip_decoder_config* cfg, at3phip_decoder** out);
+void at3phip_decoder_destroy(at3phip_decoder* dec);
+const char* at3phip_decoder_last_error(const at3phip_decoder* dec);
+
+#define AT3PHIP_DECODE_S16 8u   /* the bit of AT3HIP_DECODE_S16 */
+
+/*   frames [n_streams][n_frames][2048] bytes
+ *   pcm    [n_streams][n_frames][2048][channels]: float32, or int16 with AT3PHIP_DECODE_S16
+ * flags: AT3HIP_PCM_ON_DEVICE (frames are device memory), AT3HIP_OUT_ON_DEVICE, AT3HIP_ASYNC (only queue the call: buffers stay
+ * valid until at3phip_decoder_sync), AT3PHIP_DECODE_S16. Stream state (the last two frames' IMDCT outputs and window flags)
+ * carries across calls: any split of a stream into calls gives the same output as one call. */
+int at3phip_decode(at3phip_decoder* dec, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags);
+
+/* Waits for everything queued on the decoder. */
+int at3phip_decoder_sync(at3phip_decoder* dec);
+
+/* Back to start-of-stream state for every stream; zeroes the counters. */
+int at3phip_decoder_reset(at3phip_decoder* dec);
+
+/* Rejected frames per reason (rule 7), summed over streams since create / reset / the last call with reset = 1. Waits for
+ * queued work. */
+typedef struct at3phip_decoder_counters {
+    uint64_t bad_header;
+    uint64_t unsupported_syntax;
+    uint64_t tonal_present;
+    uint64_t bad_code;
+    uint64_t read_past_end;
+    uint64_t no_terminator;
+} at3phip_decoder_counters;
+int at3phip_decoder_get_counters(at3phip_decoder* dec, at3phip_decoder_counters* out, int32_t reset);
+
+/* Queue this decoder's work on a caller-provided hipStream_t (NULL = the decoder's own stream), as at3hip_decoder_set_stream. */
+int at3phip_decoder_set_stream(at3phip_decoder* dec, void* hip_stream);
+
+/* The decoder's constant tables as at3phip_decoder_create builds them, on the host (no GPU needed); the block starts with the
+ * DCT-IV cosines double[16][16] ([k][n]), so that their bits can be pinned on each machine. bytes = AT3PHIP_DECODER_TABLES_BYTES.
+ * The decoder is part of ABI 1.6 (see at3hip.h): a host that needs it looks for the symbol at3phip_decoder_create. */
+#define AT3PHIP_DECODER_TABLES_BYTES 67328
+int at3phip_decoder_host_tables(void* dst, size_t bytes);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

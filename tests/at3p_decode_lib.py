@@ -1,0 +1,456 @@
+"""Helpers of the ATRAC3plus decoder's tests, golden generator and benchmark (TEST INFRASTRUCTURE: nothing under atracdenc_amd/
+imports this module).
+
+  * CpuDecoder: the C restatement tests/host/at3p_decode_cpu.c (the decoder of include/at3phip.h), compiled on first use into a
+    temporary directory with the reference's arithmetic flags (gcc -O2 -ffp-contract=off -fno-fast-math).
+  * ref_back_half: the restatement's steps 1-2 (unpack, dequantise) followed by the REFERENCE's TAt3pMIDCT::Do (step 3) and
+    ff_atrac3p_ipqf (step 5, through oracle/_ref's at3pref_ipqf), with the definition's rescale (step 4) and clamp (step 6)
+    between and after them. TAt3pMIDCT::Do is run by a small driver compiled at generation time against the reference's headers
+    and oracle/_ref/libat3ref.so. Nothing of the reference is stored in the repository.
+  * FrameWriter / crafted_frames / mutate_frames: frames from their fields, malformed and extreme inputs.
+"""
+import ctypes
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+from at3_testlib import REF_SO, _vp, at3p_mdct, at3p_pqf, at3p_signal
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CPU_SRC = os.path.join(HERE, "host", "at3p_decode_cpu.c")
+CFLAGS = ["-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]
+REF_SRC = "/root/reference/src"
+FRAME = 2048
+REASONS = ("bad_header", "unsupported_syntax", "tonal_present", "bad_code", "read_past_end", "no_terminator")
+SIGNAL_NAMES = ("noise", "burst", "tones", "silence", "mix", "stress")
+# the codec's end-to-end delay in samples: output sample t of the decoder (frames from the stream's first encoded frame) is input
+# sample t - DELAY of the encoder (at3phip_encode_frames); measured on the restatement (test_round_trip_delay)
+DELAY = 2416
+RESCALE = np.float32(32768.0 / 1.122018)
+
+QU_START = [0, 16, 32, 48, 64, 80, 96, 112, 128, 160, 192, 224, 256, 288, 320, 352, 384, 448, 512, 576, 640, 704, 768, 896, 1024,
+            1152, 1280, 1408, 1536, 1664, 1792, 1920, 2048]
+QU_TO_SB = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 4, 4, 5, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15]
+SB_POWGRPS = [1, 2, 2, 3, 3, 3, 4, 4, 4, 4, 4, 5, 5, 5, 5, 5]
+
+FIELDS_DTYPE = np.dtype([("reason", "<i4"), ("n_qu", "<i4"), ("full_table", "<i4"), ("wl", "<i4", (2, 32)), ("sf", "<i4", (2, 32)),
+                         ("tab", "<i4", (2, 32)), ("win", "<i4", (2,))])
+
+_cpu_so = None
+
+
+def cpu_lib(outdir=None):
+    """ctypes handle of the restatement (built once per process, into `outdir` or a fresh temporary directory)."""
+    global _cpu_so
+    if _cpu_so is None:
+        d = str(outdir or tempfile.mkdtemp(prefix="at3pdec_"))
+        so = os.path.join(d, "libat3pdecode_cpu.so")
+        subprocess.check_call(["gcc", "-std=gnu11", *CFLAGS, "-shared", "-o", so, CPU_SRC, "-lm"])
+        _cpu_so = so
+    lib = ctypes.CDLL(_cpu_so)
+    lib.at3pd_state_bytes.restype = ctypes.c_size_t
+    lib.at3pd_fields_bytes.restype = ctypes.c_size_t
+    lib.at3pd_reset.argtypes = [ctypes.c_void_p]
+    lib.at3pd_unpack_frame.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.at3pd_decode.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_void_p]
+    lib.at3pd_test_reverse_pairing.argtypes = [ctypes.c_int]
+    lib.at3pd_tables.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    assert lib.at3pd_fields_bytes() == FIELDS_DTYPE.itemsize
+    return lib
+
+
+class CpuDecoder:
+    """One stream of the C restatement; state carries across decode() calls."""
+
+    def __init__(self, channels, lib=None):
+        self.lib = lib or cpu_lib()
+        self.channels = int(channels)
+        self.state = np.zeros(self.lib.at3pd_state_bytes(), np.uint8)
+        self.rejected = np.zeros(len(REASONS), np.uint64)
+        self.reset()
+
+    def reset(self):
+        self.lib.at3pd_reset(_vp(self.state))
+        self.rejected[:] = 0
+
+    def decode(self, frames, fields=False):
+        """frames [N][2048] uint8 -> pcm [N][2048][channels] float32 (and the frames' fields [N] with fields=True)"""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        assert frames.ndim == 2 and frames.shape[1] == FRAME, frames.shape
+        n = frames.shape[0]
+        pcm = np.zeros((n, FRAME, self.channels), np.float32)
+        fl = np.zeros(n, FIELDS_DTYPE) if fields else None
+        self.lib.at3pd_decode(_vp(self.state), self.channels, _vp(frames), n, _vp(pcm), _vp(self.rejected),
+                              _vp(fl) if fields else None)
+        return (pcm, fl) if fields else pcm
+
+
+def cpu_decode(frames, channels, fields=False, reverse_pairing=False):
+    """from start-of-stream state: (pcm [N][2048][channels], rejected per reason [6] int64[, fields])"""
+    d = CpuDecoder(channels)
+    d.lib.at3pd_test_reverse_pairing(int(reverse_pairing))
+    try:
+        r = d.decode(frames, fields)
+    finally:
+        d.lib.at3pd_test_reverse_pairing(0)
+    pcm, fl = r if fields else (r, None)
+    out = (pcm, d.rejected.astype(np.int64).copy())
+    return out + (fl,) if fields else out
+
+
+def unpack(frames, channels, lib=None):
+    """steps 1-2 of the restatement: (spectra [N][channels][2048] float32, window flags [N][channels] uint16, fields [N])"""
+    lib = lib or cpu_lib()
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n = frames.shape[0]
+    specs = np.zeros((n, channels, FRAME), np.float32)
+    win = np.zeros((n, channels), np.uint16)
+    fl = np.zeros(n, FIELDS_DTYPE)
+    for f in range(n):
+        lib.at3pd_unpack_frame(_vp(frames[f]), channels, _vp(specs[f]), _vp(win[f]), _vp(fl[f:f + 1]))
+    return specs, win, fl
+
+
+def host_tables(lib=None):
+    """(cos16 [16][16] float64, sine128 float32, sine64 float32) as the restatement builds them"""
+    lib = lib or cpu_lib()
+    c = np.zeros((16, 16), np.float64)
+    s128, s64 = np.zeros(128, np.float32), np.zeros(64, np.float32)
+    lib.at3pd_tables(_vp(c), _vp(s128), _vp(s64))
+    return c, s128, s64
+
+
+def specs_with_windows(name, n_frames, channels, flags, scale=1.0):
+    """EncodeFrame's residual spectra of a test signal with the given steep-window flags [n_frames][channels]"""
+    out = np.zeros((n_frames, channels, FRAME), np.float32)
+    for ch in range(channels):
+        bands = at3p_pqf(at3p_signal(name, n_frames, channel=ch, scale=scale))
+        bands = (bands.astype(np.float64) / (32768.0 / 1.122018)).astype(np.float32)
+        out[:, ch] = at3p_mdct(bands, flags[:, ch])
+    return out
+
+
+# ---- the reference's back half --------------------------------------------------------------------------------------------
+REF_DRIVER = r"""
+#include "atrac/at3p/at3p_mdct.h"
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+using namespace NAtracDEnc;
+// argv = n specs.f32 win.u16 out.f32: one channel, specs [n][2048], win [n] -> subband samples [n][16][128] of TAt3pMIDCT::Do
+int main(int argc, char** argv)
+{
+    if (argc != 5) return 2;
+    const int n = atoi(argv[1]);
+    std::vector<float> specs((size_t)n * 2048), out((size_t)n * 2048);
+    std::vector<uint16_t> win(n);
+    FILE* f = fopen(argv[2], "rb");
+    if (fread(specs.data(), sizeof(float), specs.size(), f) != specs.size()) return 3;
+    fclose(f);
+    f = fopen(argv[3], "rb");
+    if (fread(win.data(), sizeof(uint16_t), win.size(), f) != win.size()) return 3;
+    fclose(f);
+    TAt3pMIDCT midct;
+    static TAt3pMIDCT::THistBuf hist;   // zeroed, all-sine flags
+    for (int fr = 0; fr < n; ++fr) {
+        TAt3pMIDCT::TPcmBandsData p;
+        for (int b = 0; b < 16; ++b) p[b] = &out[(size_t)fr * 2048 + b * 128];
+        TAt3pMDCTWin w;
+        for (int b = 0; b < 16; ++b)
+            if ((win[fr] >> b) & 1) w.SetSteepWin(b);
+        midct.Do(&specs[(size_t)fr * 2048], p, hist, w);
+    }
+    f = fopen(argv[4], "wb");
+    fwrite(out.data(), sizeof(float), out.size(), f);
+    fclose(f);
+    return 0;
+}
+"""
+
+_ref_driver = None
+
+
+def have_ref_back_half():
+    return os.path.exists(REF_SO) and os.path.isdir(REF_SRC)
+
+
+def ref_driver(outdir=None):
+    global _ref_driver
+    if _ref_driver is None:
+        d = outdir or tempfile.mkdtemp(prefix="at3pdref_")
+        src = os.path.join(d, "at3p_ref_midct.cpp")
+        with open(src, "w") as f:
+            f.write(REF_DRIVER)
+        exe = os.path.join(d, "at3p_ref_midct")
+        libdir = os.path.dirname(REF_SO)
+        inc = [f"-I{REF_SRC}", f"-I{REF_SRC}/lib", f"-I{REF_SRC}/lib/liboma/include", f"-I{REF_SRC}/lib/fft/kissfft_impl"]
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-w", "-DNDEBUG", *inc, src, "-o", exe, f"-L{libdir}", "-lat3ref",
+                               f"-Wl,-rpath,{libdir}"])
+        _ref_driver = exe
+    return _ref_driver
+
+
+def ref_back_half(frames, channels):
+    """(pcm [N][2048][channels] float32, rejected per reason, fields): the restatement's unpack, the reference's synthesis"""
+    specs, win, fl = unpack(frames, channels)
+    rejected = np.array([(fl["reason"] == k + 1).sum() for k in range(len(REASONS))], np.int64)
+    n = specs.shape[0]
+    pcm = np.zeros((n, FRAME, channels), np.float32)
+    with tempfile.TemporaryDirectory(prefix="at3pdref_run_") as d:
+        for ch in range(channels):
+            sp, wp, op = (os.path.join(d, x) for x in ("specs.f32", "win.u16", "out.f32"))
+            np.ascontiguousarray(specs[:, ch]).tofile(sp)
+            np.ascontiguousarray(win[:, ch]).tofile(wp)
+            subprocess.run([ref_driver(), str(n), sp, wp, op], check=True)
+            sub = np.fromfile(op, np.float32).reshape(n, 16, 128)
+            sub = sub * RESCALE                                   # step 4, one float multiply
+            lib = ctypes.CDLL(REF_SO)
+            out = np.zeros((n, FRAME), np.float32)
+            sub = np.ascontiguousarray(sub, np.float32)
+            lib.at3pref_ipqf(_vp(sub), n, _vp(out))
+            pcm[:, :, ch] = np.clip(out, np.float32(-1.0), np.float32(1.0))
+    return pcm, rejected, fl
+
+
+# ---- crafted frames -------------------------------------------------------------------------------------------------------
+def _vlc_tables():
+    """(spectra [56] {symbol: (code, len)}, word-length [4] {symbol: (code, len)}) from the generated table file"""
+    import re
+    t = open(os.path.join(HERE, "..", "atracdenc_amd", "csrc", "at3p_vlc.inc")).read()
+    offs = [int(x) for x in re.search(r"AT3P_VLC_OFF\[113\] = \{([^}]*)\}", t).group(1).split(",")]
+    body = t[t.index("AT3P_VLC[AT3P_VLC_TOTAL] = {"):]
+    body = body[body.index("{") + 1:body.index("};")]
+    v = [int(x, 16) for x in re.findall(r"0x[0-9a-f]+", body)]
+    spec = [{s: (e & 0xfff, e >> 12) for s, e in enumerate(v[offs[i]:offs[i + 1]]) if e >> 12} for i in range(56)]
+    body = t[t.index("AT3P_WL_VLC[4][8] = {"):]
+    body = body[body.index("{") + 1:body.index("};")]
+    w = [int(x, 16) for x in re.findall(r"0x[0-9a-f]+", body)]
+    wl = [{s: (w[8 * i + s] & 0xfff, w[8 * i + s] >> 12) for s in range(8) if w[8 * i + s] >> 12} for i in range(4)]
+    tab = t[t.index("AT3P_SPEC_TAB[112][2] = {"):]
+    tab = tab[tab.index("{") + 1:tab.index("};")]
+    pairs = [int(x, 16) for x in re.findall(r"0x[0-9a-f]+", tab)]
+    info = [(pairs[2 * i] & 15, pairs[2 * i] >> 4, pairs[2 * i + 1] & 15, pairs[2 * i + 1] >> 4) for i in range(112)]
+    return spec, wl, info
+
+
+_VLC = None
+
+
+def vlc_tables():
+    global _VLC
+    if _VLC is None:
+        _VLC = _vlc_tables()
+    return _VLC
+
+
+class BitWriter:
+    def __init__(self, nbytes=FRAME):
+        self.buf = bytearray(nbytes)
+        self.pos = 0
+
+    def put(self, v, n):
+        for k in range(n - 1, -1, -1):
+            if self.pos < len(self.buf) * 8 and (v >> k) & 1:
+                self.buf[self.pos >> 3] |= 0x80 >> (self.pos & 7)
+            self.pos += 1
+
+
+def make_frame(channels, nqu=4, wl=None, sf=None, tab=None, mant=None, full_table=1, win=(0, 0), first_bit=0, block_type=None,
+               mute=0, wl_modes=None, sf_mode=0, ct_fields=(0, 0, 0), zero_groups=False, powlev=15, swap_negate=0, gain=0,
+               tonal=0, noise=0, term=3, win_bits=None, truncate=None):
+    """One frame from its fields (include/at3phip.h, step 1). wl / sf / tab: [channels][nqu]; mant(ch, qu, k) -> the integer
+    mantissa of line k of the unit (must fit the unit's table); zero_groups: code every group with a group flag as all zero.
+    win: per channel a flag word (0 -> '0', 0xffff -> '1 0', else '1 1' + 16 bits) unless win_bits gives the raw bits.
+    truncate: drop every bit from this position on (a frame that ends early). The remaining arguments override what the writer
+    emits, for the rejection cases."""
+    spec_t, wl_t, info = vlc_tables()
+    wl = wl if wl is not None else [[4] * nqu for _ in range(channels)]
+    sf = sf if sf is not None else [[40] * nqu for _ in range(channels)]
+    tab = tab if tab is not None else [[0] * nqu for _ in range(channels)]
+    w = BitWriter()
+    w.put(first_bit, 1)
+    w.put(channels - 1 if block_type is None else block_type, 2)
+    w.put(nqu - 1, 5)
+    w.put(mute, 1)
+    modes = wl_modes or ((3, 0, 0), (1, 0))
+    # channel 0: deltas to the previous unit, with the table that codes them all
+    d0 = [(wl[0][i] - wl[0][i - 1]) & 7 for i in range(1, nqu)]
+    idx0 = next(i for i in range(4) if all(d in wl_t[i] for d in d0))
+    for m in modes[0]:
+        w.put(m, 2)
+    w.put(idx0, 2)
+    w.put(wl[0][0], 3)
+    for d in d0:
+        w.put(*wl_t[idx0][d])
+    if channels == 2:
+        d1 = [(wl[1][i] - wl[0][i]) & 7 for i in range(nqu)]
+        idx1 = next(i for i in range(4) if all(d in wl_t[i] for d in d1))
+        for m in modes[1]:
+            w.put(m, 2)
+        w.put(idx1, 2)
+        for d in d1:
+            w.put(*wl_t[idx1][d])
+    for ch in range(channels):
+        w.put(sf_mode, 2)
+        for i in range(nqu):
+            w.put(sf[ch][i], 6)
+    w.put(full_table, 1)
+    for ch in range(channels):
+        w.put(ct_fields[0], 1)
+        w.put(ct_fields[1], 2)
+        w.put(ct_fields[2], 1)
+        for i in range(nqu):
+            w.put(tab[ch][i], full_table + 2)
+    for ch in range(channels):
+        for qu in range(nqu):
+            if wl[ch][qu] == 0:
+                continue
+            t = wl[ch][qu] - 1 + 7 * tab[ch][qu]
+            gs, nc, cb, signed = info[t]
+            n = QU_START[qu + 1] - QU_START[qu]
+            vals = [mant(ch, qu, k) if mant else 0 for k in range(n)]
+            pos = 0
+            while pos < n:
+                if gs != 1:
+                    grp = vals[pos:pos + gs * nc]
+                    if zero_groups and not any(grp):
+                        w.put(0, 1)
+                        pos += gs * nc
+                        continue
+                    w.put(1, 1)
+                for _ in range(gs):
+                    sym, signs = 0, []
+                    for i in range(nc):
+                        m = vals[pos]
+                        pos += 1
+                        if signed:
+                            assert -(1 << (cb - 1)) <= m < (1 << (cb - 1)), (m, cb)
+                            sym |= (m & ((1 << cb) - 1)) << (cb * i)
+                        else:
+                            assert abs(m) < (1 << cb), (m, cb)
+                            sym |= abs(m) << (cb * i)
+                            if m:
+                                signs.append(1 if m < 0 else 0)
+                    w.put(*spec_t[t][sym])
+                    for s in signs:
+                        w.put(s, 1)
+        for _ in range(SB_POWGRPS[QU_TO_SB[nqu - 1]]):
+            w.put(powlev, 4)
+    if channels == 2:
+        w.put(swap_negate, 2)
+    for ch in range(channels):
+        if win_bits is not None:
+            for bit in win_bits[ch]:
+                w.put(bit, 1)
+        elif win[ch] == 0:
+            w.put(0, 1)
+        elif win[ch] == 0xffff:
+            w.put(2, 2)
+        else:
+            w.put(3, 2)
+            for i in range(16):
+                w.put((win[ch] >> i) & 1, 1)
+    for ch in range(channels):
+        w.put(gain, 1)
+    w.put(tonal, 1)
+    w.put(noise, 1)
+    w.put(term, 2)
+    buf = bytearray(w.buf)
+    if truncate is not None:
+        for p in range(truncate, FRAME * 8):
+            buf[p >> 3] &= ~(0x80 >> (p & 7)) & 0xff
+    return np.frombuffer(bytes(buf), np.uint8)
+
+
+def _small_mant(ch, qu, k):
+    v = ((k * 5 + qu * 3 + ch) % 5) - 2   # -2 .. 2: fits every table of word length >= 2
+    return v
+
+
+def crafted_frames(channels, seed):
+    """Malformed and extreme frames [N][2048] and what each pins: every rejection reason, group flag 0, full-table flag 0, the
+    word-length-0 decision, full-scale spectra that clamp, and seeded random bytes."""
+    rng = np.random.default_rng(seed)
+    C = channels
+    frames, what = [], []
+
+    def add(tag, fr):
+        frames.append(np.asarray(fr, np.uint8))
+        what.append(tag)
+
+    nq = 6
+    base = dict(nqu=nq, wl=[[3] * nq for _ in range(C)], sf=[[30 + q for q in range(nq)] for _ in range(C)], mant=_small_mant)
+    add("ok", make_frame(C, **base))
+    add("bad_first_bit", make_frame(C, first_bit=1, **base))
+    add("bad_block_type", make_frame(C, block_type=(C % 2), **base))
+    add("block_type_3", make_frame(C, block_type=3, **base))
+    add("mute", make_frame(C, mute=1, **base))
+    add("wl_mode", make_frame(C, wl_modes=((2, 0, 0), (1, 0)), **base))
+    if C == 2:
+        add("wl_mode_ch1", make_frame(C, wl_modes=((3, 0, 0), (0, 0)), **base))
+    add("sf_mode", make_frame(C, sf_mode=1, **base))
+    add("ct_type", make_frame(C, ct_fields=(1, 0, 0), **base))
+    add("ct_mode", make_frame(C, ct_fields=(0, 2, 0), **base))
+    add("powlev", make_frame(C, powlev=14, **base))
+    if C == 2:
+        add("swap_negate", make_frame(C, swap_negate=1, **base))
+    add("gain_comp", make_frame(C, gain=1, **base))
+    add("tonal", make_frame(C, tonal=1, **base))
+    add("noise", make_frame(C, noise=1, **base))
+    add("terminator", make_frame(C, term=1, **base))
+    add("wl_zero", make_frame(C, nqu=nq, wl=[[3, 3, 0, 3, 3, 3] for _ in range(C)], sf=base["sf"], mant=_small_mant))
+    add("wl_zero_first", make_frame(C, nqu=nq, wl=[[0, 3, 3, 3, 3, 3] for _ in range(C)], sf=base["sf"], mant=_small_mant))
+    # read past the end: a frame that keeps on coding units at full length, cut short
+    big = dict(nqu=32, wl=[[7] * 32 for _ in range(C)], sf=[[50] * 32 for _ in range(C)],
+               mant=lambda ch, qu, k: (24 + (k * 7 + qu) % 8) * (1 if k % 2 else -1))
+    add("read_past_end", make_frame(C, **big))   # longer than 2048 bytes: the writer drops the rest
+    # group flag 0 and full-table flag 0
+    # (word lengths 1, 2, 6, 7 with tables 1, 7, 7, 7 code groups of 2 or 4 symbols)
+    sparse = lambda ch, qu, k: (1 if qu % 2 == 0 and k < 3 else 0)
+    wlg = [[(1, 2, 6, 7)[q % 4] for q in range(12)] for _ in range(C)]
+    tabs = [[1 if w == 1 else 7 for w in wlg[ch]] for ch in range(C)]
+    add("group_flag_0", make_frame(C, nqu=12, wl=wlg, sf=[[45] * 12 for _ in range(C)], tab=tabs, mant=sparse, zero_groups=True))
+    add("full_table_0", make_frame(C, nqu=12, wl=[[(q % 7) + 1 for q in range(12)] for _ in range(C)],
+                                   sf=[[40 + q for q in range(12)] for _ in range(C)], tab=[[q % 4 for q in range(12)] for _ in range(C)],
+                                   mant=lambda ch, qu, k: (k % 3) - 1, full_table=0))
+    add("wl_deltas", make_frame(C, nqu=20, wl=[[(1 + 3 * q) % 7 + 1 for q in range(20)], [(2 + 5 * q) % 7 + 1 for q in range(20)]][:C],
+                                sf=[[20 + 2 * q for q in range(20)] for _ in range(C)], mant=lambda ch, qu, k: (k % 3) - 1))
+    # window syntax: '1 1' with mixed bits, '1 0'
+    add("win_mixed", make_frame(C, win=(0x5a3c, 0x0f0f), **base))
+    add("win_steep", make_frame(C, win=(0xffff, 0xffff), **base))
+    # full scale: scale factor 63 and large mantissas: far beyond +-1, clamps
+    add("clamp", make_frame(C, nqu=8, wl=[[7] * 8 for _ in range(C)], sf=[[63] * 8 for _ in range(C)],
+                            mant=lambda ch, qu, k: 7 if (k + qu) % 2 else -7))
+    for _ in range(3):
+        add("random", rng.integers(0, 256, FRAME, dtype=np.uint8))
+    for _ in range(3):   # random bits behind a valid header
+        r = rng.integers(0, 256, FRAME, dtype=np.uint8)
+        r[0] = (r[0] & 0x1F) | ((C - 1) << 5)
+        add("random_body", r)
+    return np.ascontiguousarray(np.stack(frames)), what
+
+
+def mutate_frames(frames, rng, n_flips=3, span=None):
+    """copies of `frames` with n_flips random bits flipped each (in the first `span` bits when given)"""
+    out = frames.copy()
+    lim = span or out.shape[1] * 8
+    for f in range(out.shape[0]):
+        for _ in range(n_flips):
+            p = int(rng.integers(0, lim))
+            out[f, p >> 3] ^= 0x80 >> (p & 7)
+    return out
+
+
+# ---- files -----------------------------------------------------------------------------------------------------------------
+def oma_bytes(frames, channels, channel_id=None, frame_bytes=FRAME):
+    """an ATRAC3plus OMA file as at3hip_io.hpp's TOmaOutput writes it: 96-byte EA3 header (codec id 1), then the frames"""
+    h = bytearray(96)
+    h[0:3] = b"EA3"
+    h[3], h[5], h[6], h[7] = 1, 96, 0xFF, 0xFF
+    cid = channels if channel_id is None else channel_id
+    word = (1 << 24) | (1 << 13) | (cid << 10) | ((frame_bytes - 8) // 8)
+    h[32:36] = word.to_bytes(4, "big")
+    return bytes(h) + np.ascontiguousarray(frames, np.uint8).tobytes()
