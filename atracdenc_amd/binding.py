@@ -61,9 +61,11 @@ AT3P_SYMBOLS = ["at3phip_create", "at3phip_destroy", "at3phip_last_error", "at3p
                 "at3phip_get_write_timing", "at3phip_host_write_tables", "at3phip_sync",
                 "at3phip_decoder_create", "at3phip_decoder_destroy", "at3phip_decoder_last_error", "at3phip_decode",
                 "at3phip_decoder_sync", "at3phip_decoder_reset", "at3phip_decoder_get_counters", "at3phip_decoder_set_stream",
-                "at3phip_decoder_host_tables"]
+                "at3phip_decoder_host_tables", "at3phip_decoder_host_tone_tables"]
 AT3PHIP_DECODE_S16 = 8
+AT3PHIP_DECODE_TONES = 16
 AT3PHIP_DECODER_TABLES_BYTES = 67328
+AT3PHIP_DECODER_TONE_TABLES_BYTES = 9504
 
 
 class At1Config(ctypes.Structure):
@@ -200,6 +202,8 @@ def load_library(path=None):
         getattr(lib, f"{codec}_decoder_last_error").restype = ctypes.c_char_p
     if hasattr(lib, "at3phip_decoder_host_tables"):
         lib.at3phip_decoder_host_tables.argtypes = [vp, ctypes.c_size_t]
+    if hasattr(lib, "at3phip_decoder_host_tone_tables"):
+        lib.at3phip_decoder_host_tone_tables.argtypes = [vp, ctypes.c_size_t]
     lib.at3phip_create.argtypes = [ctypes.POINTER(At3pConfig), ctypes.POINTER(vp)]
     lib.at3phip_destroy.argtypes = [vp]
     lib.at3phip_destroy.restype = None
@@ -624,18 +628,27 @@ class At3pHipDecoder(_Decoder):
         self._create(At3pDecoderConfig(self.channels, self.n_streams, self.max_frames, int(device_id)),
                      "bad configuration, or no usable MI355X / HIP runtime")
 
-    def decode(self, frames, s16=False):
-        """frames uint8 [n_streams, n_frames, 2048] (host) -> float32 (int16 with s16) [n_streams, n_frames, 2048, channels]."""
+    def _tones_flag(self, tones):
+        if not tones:
+            return 0
+        if not hasattr(self.lib, "at3phip_decoder_host_tone_tables"):
+            raise At3HipError("libat3hip.so predates tonal-block decoding (no at3phip_decoder_host_tone_tables): rebuild it")
+        return AT3PHIP_DECODE_TONES
+
+    def decode(self, frames, s16=False, tones=False):
+        """frames uint8 [n_streams, n_frames, 2048] (host) -> float32 (int16 with s16) [n_streams, n_frames, 2048, channels].
+        tones: decode tonal blocks (AT3PHIP_DECODE_TONES) instead of rejecting their frames."""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
         assert frames.ndim == 3 and frames.shape[0] == self.n_streams and frames.shape[2] == 2048, frames.shape
         n = frames.shape[1]
         out = np.zeros((self.n_streams, n, 2048, self.channels), dtype=np.int16 if s16 else np.float32)
-        self.decode_ptr(frames.ctypes.data, n, out.ctypes.data, AT3PHIP_DECODE_S16 if s16 else 0)
+        self.decode_ptr(frames.ctypes.data, n, out.ctypes.data, (AT3PHIP_DECODE_S16 if s16 else 0) | self._tones_flag(tones))
         return out
 
-    def decode_device(self, frames, out, asynchronous=False, ordered=True):
+    def decode_device(self, frames, out, asynchronous=False, ordered=True, tones=False):
         """Torch tensors on this decoder's device: frames uint8 [n_streams, n, 2048] -> out float32 / int16 (s16 output)
-        [n_streams, n, 2048, channels]. Ordered behind torch's current stream by default, as At1HipDecoder.decode_device."""
+        [n_streams, n, 2048, channels]. Ordered behind torch's current stream by default, as At1HipDecoder.decode_device.
+        tones as in decode."""
         import torch
         assert frames.dtype == torch.uint8 and frames.is_contiguous() and out.is_contiguous()
         assert out.dtype in (torch.float32, torch.int16)
@@ -643,7 +656,7 @@ class At3pHipDecoder(_Decoder):
         assert tuple(frames.shape) == (self.n_streams, n, 2048), tuple(frames.shape)
         assert tuple(out.shape) == (self.n_streams, n, 2048, self.channels), tuple(out.shape)
         flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3PHIP_DECODE_S16 if out.dtype == torch.int16 else 0)
-        flags |= AT3HIP_ASYNC if asynchronous else 0
+        flags |= (AT3HIP_ASYNC if asynchronous else 0) | self._tones_flag(tones)
         self._order_behind_torch(frames.device, ordered)
         self.decode_ptr(frames.data_ptr(), n, out.data_ptr(), flags)
 
@@ -655,6 +668,19 @@ def at3p_decoder_host_tables(lib_path=None):
     rc = load_library(lib_path).at3phip_decoder_host_tables(_vp(out), out.nbytes)
     if rc != 0:
         raise At3HipError(f"at3phip_decoder_host_tables failed ({rc})")
+    return out
+
+
+AT3P_TONE_TABLES_DTYPE = np.dtype([("sine", "<f4", 2048), ("hann", "<f4", 256), ("amp_sf", "<f4", 64), ("vlc", "<u2", 16)])
+assert AT3P_TONE_TABLES_DTYPE.itemsize == AT3PHIP_DECODER_TONE_TABLES_BYTES
+
+
+def at3p_decoder_host_tone_tables(lib_path=None):
+    """at3phip_decoder_host_tone_tables (no GPU): the tone synthesis' tables as a record of AT3P_TONE_TABLES_DTYPE."""
+    out = np.zeros((), AT3P_TONE_TABLES_DTYPE)
+    rc = load_library(lib_path).at3phip_decoder_host_tone_tables(_vp(out), out.nbytes)
+    if rc != 0:
+        raise At3HipError(f"at3phip_decoder_host_tone_tables failed ({rc})")
     return out
 
 

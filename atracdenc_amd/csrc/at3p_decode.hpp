@@ -10,7 +10,11 @@
 //   k_at3pd_synth   one workgroup per (frame, stream, channel): the windows with the (n-1, n) pairing and the overlap-add for
 //                   frame n and for frame n-1's last 23 columns, the rescale, the 151 DCT-IVs in f64, the 12-tap FIR, clamp,
 //                   f32 or s16 output
-//   k_at3pd_state   the call's last two frames become frames -2 and -1 of the next call
+//   k_at3pd_state   the call's last two frames become frames -2 and -1 of the next call, its last three tonal records
+//                   records -3 .. -1
+// Tonal blocks (AT3PHIP_DECODE_TONES): the unpack lane also parses the tonal block into a TonalRec per (frame, stream); step 4b
+// runs in k_at3pd_synth. Frame n's samples need the records of frames n, n-1 (waves) and n-2 (frame n-1's envelope); frame n-1's
+// last 23 samples need those of frames n-1 .. n-3, so four records are read and three are carried.
 // Every float and double operation is the definition's, in its order, without contraction; no scratch.
 #pragma once
 #include "at3_common.hpp"
@@ -37,6 +41,34 @@ struct DecTables {
     uint16_t lut2[kDecLut2Blocks][16];
 };
 
+// The tone synthesis' tables (ff_atrac3p_init_dsp_static), built on the host with its libm.
+struct DecToneTables {
+    float sine[2048];   // sine_table: (float)sin(2 pi i / 2048)
+    float hann[256];    // hann_window: (float)((1.0 - cos(2 pi i / 256)) * 0.5)
+    float amp_sf[64];   // amp_sf_tab: exp2f((i - 3) / 4.0f)
+    uint16_t vlc[16];   // AT3P_TONE_BANDS_VLC: the code of NumToneBands - 1
+};
+
+// One frame's tonal block after ApplyFilter's bookkeeping (include/at3phip.h, step 1 with AT3PHIP_DECODE_TONES). sp / ep are
+// the envelope's start / stop point + 1, 0 when absent (pend_env's start_pos -1 / stop_pos 32), so that a zeroed record is a frame
+// without a tonal block.
+struct TonalBand {
+    uint8_t nw, start_index, sp, ep;
+};
+constexpr int kMaxWaves = 48;
+struct TonalRec {
+    uint32_t present;
+    TonalBand band[2][16];
+    uint32_t wave[kMaxWaves];   // freq | amp_sf << 10 | phase << 16
+};
+constexpr int kTonalWords = sizeof(TonalRec) / 4;
+static_assert(sizeof(TonalRec) % 4 == 0, "TonalRec is copied as words");
+constexpr int kTonalCarry = 3;   // records -3 .. -1 lead a call's records
+
+// record of frame f (f = -3 .. -1: the carried ones) of stream s
+template <typename Rec>
+__device__ __forceinline__ Rec* decp_tonal_rec(Rec* t, int f, int s, int S) { return t + (size_t)(f + kTonalCarry) * S + s; }
+
 constexpr int kDecReasons = 6;   // at3phip_decoder_counters order
 enum { kRpOk = 0, kRpBadHeader, kRpUnsupported, kRpTonal, kRpBadCode, kRpReadPastEnd, kRpNoTerminator };
 
@@ -51,6 +83,9 @@ struct DecUnpackParams {
     float* raw;                   // records of [16][256] floats: the TMIDCT<256> output per subband
     uint16_t* flags;              // records: steep-window bits
     unsigned long long* rejected; // [6]
+    TonalRec* tonal;              // [F + 3][S]: record f + 3 = frame f
+    const uint16_t* tone_vlc;     // AT3P_TONE_BANDS_VLC
+    int32_t tones;                // AT3PHIP_DECODE_TONES
 };
 
 // MSB-first reader over the frame staged in LDS as big-endian words (zero past the frame); reads must end within 16384 bits.
@@ -120,9 +155,148 @@ __device__ __forceinline__ int decp_spec_vlc(DecpBits& b, const DecTables* T, in
     return (int)(e & 0xffu);
 }
 
+__device__ __forceinline__ int decp_bits_for(uint32_t x) { return x ? 32 - __builtin_clz(x) : 1; }   // GetFirstSetBit(x) + 1
+
+// A code of AT3P_TONE_BANDS_VLC (16 symbols, at most 6 bits, a complete prefix code).
+__device__ __forceinline__ int decp_tone_vlc(DecpBits& b, const uint16_t* tab, int& invalid)
+{
+    if (b.bad) return 0;
+    const uint32_t v = b.peek(8);
+    for (int sym = 0; sym < 16; ++sym) {
+        const int len = tab[sym] >> 12, code = tab[sym] & 0xfff;
+        if (len && (int)(v >> (8 - len)) == code) {
+            if (b.pos + len > 2048 * 8) {
+                b.bad = 1;
+                return 0;
+            }
+            b.advance(len);
+            return sym;
+        }
+    }
+    invalid = 1;
+    return 0;
+}
+
+// The tonal block (include/at3phip.h, step 1 with AT3PHIP_DECODE_TONES) into r, which is zero on entry; r holds
+// the block after ApplyFilter's bookkeeping (start indices, shared bands, the leader swap) when kRpOk is returned.
+__device__ __forceinline__ int decp_tonal(DecpBits& b, const uint16_t* tone_vlc, int C, TonalRec* r)
+{
+    int invalid = 0;
+#define DECP_CHK()                              \
+    do {                                        \
+        if (b.bad) return kRpReadPastEnd;       \
+        if (invalid) return kRpBadCode;         \
+    } while (0)
+#define DECP_MUST(n, val)                                   \
+    do {                                                    \
+        const uint32_t v_ = b.rd(n);                        \
+        DECP_CHK();                                         \
+        if (v_ != (uint32_t)(val)) return kRpUnsupported;   \
+    } while (0)
+    DECP_MUST(1, 1);   // amplitude mode 1
+    const int nb = decp_tone_vlc(b, tone_vlc, invalid) + 1;
+    DECP_CHK();
+    uint32_t shared = 0;
+    int leader = 0;
+    if (C == 2) {
+        if (b.rd(1)) {
+            if (b.rd(1) == 0) {
+                shared = (1u << nb) - 1u;
+            } else {
+                for (int i = 0; i < nb; ++i) shared |= b.rd(1) << i;
+            }
+        }
+        DECP_CHK();
+        if (b.rd(1)) {
+            DECP_MUST(1, 0);   // '1 1 x': never written
+            leader = 1;
+        }
+        DECP_MUST(1, 0);       // invert-phase flags
+    }
+    int nwav = 0;
+    for (int ch = 0; ch < C; ++ch) {
+        TonalBand* bd = r->band[ch];
+        const uint32_t skip = ch ? shared : 0u;
+        if (ch) DECP_MUST(1, 0);   // envelope copy
+        for (int i = 0; i < nb; ++i) {
+            if ((skip >> i) & 1u) continue;
+            if (b.rd(1)) bd[i].sp = (uint8_t)(b.rd(5) + 1);
+            if (b.rd(1)) bd[i].ep = (uint8_t)(b.rd(5) + 1);
+        }
+        DECP_MUST(ch + 1, 0);      // num-waves mode
+        for (int i = 0; i < nb; ++i) {
+            if ((skip >> i) & 1u) continue;
+            const int n = (int)b.rd(4);
+            bd[i].nw = (uint8_t)n;
+            bd[i].start_index = (uint8_t)(nwav < kMaxWaves ? nwav : kMaxWaves);
+            nwav += n;
+        }
+        DECP_CHK();
+        if (nwav > kMaxWaves) return kRpBadCode;
+        if (ch) DECP_MUST(1, 0);   // delta to the leader
+        for (int i = 0; i < nb; ++i) {
+            const int n = bd[i].nw;
+            if (((skip >> i) & 1u) || !n) continue;
+            uint32_t* w = r->wave + bd[i].start_index;
+            const int desc = n > 1 ? (int)b.rd(1) : 0;
+            if (!desc) {
+                uint32_t prev = b.rd(10);
+                w[0] = prev;
+                for (int j = 1; j < n; ++j) {
+                    uint32_t cur;
+                    if (prev < 512) {
+                        cur = b.rd(10);
+                    } else {
+                        const int nbits = decp_bits_for(1023u - prev);
+                        cur = b.rd(nbits) + 1024u - (1u << nbits);
+                    }
+                    w[j] = cur;
+                    prev = cur;
+                }
+            } else {
+                uint32_t prev = b.rd(10);
+                w[n - 1] = prev;
+                for (int j = n - 2; j >= 0; --j) {
+                    const uint32_t cur = b.rd(decp_bits_for(prev));
+                    w[j] = cur;
+                    prev = cur;
+                }
+            }
+            DECP_CHK();
+        }
+        DECP_MUST(ch + 1, 0);      // amplitude mode
+        for (int i = 0; i < nb; ++i) {
+            const int n = bd[i].nw;
+            if ((skip >> i) & 1u) continue;
+            for (int j = 0; j < n; ++j) r->wave[bd[i].start_index + j] |= b.rd(6) << 10;
+        }
+        DECP_CHK();
+        for (int i = 0; i < nb; ++i) {
+            const int n = bd[i].nw;
+            if ((skip >> i) & 1u) continue;
+            for (int j = 0; j < n; ++j) r->wave[bd[i].start_index + j] |= b.rd(5) << 16;
+        }
+        DECP_CHK();
+    }
+    if (C == 2)
+        for (int i = 0; i < nb; ++i) {
+            if ((shared >> i) & 1u) r->band[1][i] = r->band[0][i];
+            if (leader) {
+                const TonalBand t = r->band[0][i];
+                r->band[0][i] = r->band[1][i];
+                r->band[1][i] = t;
+            }
+        }
+    r->present = 1;
+#undef DECP_MUST
+#undef DECP_CHK
+    return kRpOk;
+}
+
 // The frame's syntax (include/at3phip.h, step 1) and its dequantisation (step 2) on one lane; spec (LDS) is zero on entry.
+// With tonal_rec (AT3PHIP_DECODE_TONES) a tonal block is parsed into it, else it rejects the frame.
 __device__ __forceinline__ int decp_parse(DecpBits& b, const DecTables* T, int C, float* spec, uint8_t (*wl)[32], uint8_t (*sf)[32],
-                                       uint8_t (*tab)[32], uint16_t* winf)
+                                       uint8_t (*tab)[32], uint16_t* winf, const uint16_t* tone_vlc, TonalRec* tonal_rec)
 {
     int invalid = 0;
 #define DECP_CHK()                              \
@@ -227,7 +401,11 @@ __device__ __forceinline__ int decp_parse(DecpBits& b, const DecTables* T, int C
     }
     const uint32_t tonal = b.rd(1);
     DECP_CHK();
-    if (tonal) return kRpTonal;
+    if (tonal) {
+        if (!tonal_rec) return kRpTonal;
+        const int why = decp_tonal(b, tone_vlc, C, tonal_rec);
+        if (why) return why;
+    }
     const uint32_t noise = b.rd(1);
     DECP_CHK();
     if (noise) return kRpUnsupported;
@@ -249,6 +427,7 @@ __global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack(DecUnpackPar
     __shared__ uint8_t s_wl[2][32], s_sf[2][32], s_tab[2][32];
     __shared__ uint16_t s_win[2];
     __shared__ int s_reason;
+    __shared__ TonalRec s_tone;
 
     const DecTables* T = p.T;
     const int f = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, C = p.nch;
@@ -261,16 +440,21 @@ __global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack(DecUnpackPar
     }
     for (int i = tid; i < 2 * 2048; i += NT) (&s_spec[0][0])[i] = 0.0f;
     if (tid < 2) s_win[tid] = 0;
+    for (int i = tid; i < kTonalWords; i += NT) ((uint32_t*)&s_tone)[i] = 0u;
     __syncthreads();
     if (tid == 0) {
         DecpBits b(s_w);
-        const int why = decp_parse(b, T, C, &s_spec[0][0], s_wl, s_sf, s_tab, s_win);
+        const int why = decp_parse(b, T, C, &s_spec[0][0], s_wl, s_sf, s_tab, s_win, p.tone_vlc, p.tones ? &s_tone : nullptr);
         s_reason = why;
         if (why) atomicAdd(&p.rejected[why - 1], 1ull);
     }
     __syncthreads();
     const bool rejected = s_reason != kRpOk;
     if (tid < C) p.flags[decp_rec(f + 2, s, tid, p.n_streams, C)] = rejected ? (uint16_t)0 : s_win[tid];
+    {   // the frame's tonal record; none for a rejected frame
+        uint32_t* rec = (uint32_t*)decp_tonal_rec(p.tonal, f, s, p.n_streams);
+        for (int i = tid; i < kTonalWords; i += NT) rec[i] = rejected ? 0u : ((const uint32_t*)&s_tone)[i];
+    }
     // TMIDCT<256> pre-rotation per subband (odd subbands: SwapArray folded into the index), into the FFT's leaf order; a
     // rejected frame has a zero spectrum
     const float* cs = T->cs256;
@@ -315,7 +499,101 @@ struct DecSynthParams {
     const uint16_t* flags;
     void* out;                    // [S][F][2048][C] float or int16
     int32_t n_frames, n_streams, nch, s16;
+    const TonalRec* tonal;        // as DecUnpackParams::tonal
+    const DecToneTables* TT;
+    int32_t tones;                // step 4b
 };
+
+// ---- step 4b: ff_atrac3p_generate_tones for the band of frame k, tones_info = record k, tones_info_prev = record k-1 ----------
+struct DecpEnv {
+    int hs, s, he, e;   // has_start_point, start_pos, has_stop_point, stop_pos
+};
+
+// curr_env of record k's band (nx) from its pend_env and record k-1's (nw), as ff_atrac3p_generate_tones reconstructs it
+__device__ __forceinline__ DecpEnv decp_curr_env(TonalBand nx, TonalBand nw)
+{
+    const int nx_start = (int)nx.sp - 1, nx_stop = nx.ep ? (int)nx.ep - 1 : 32;
+    DecpEnv r;
+    if (nx.sp && nx_start < nx_stop) {
+        r.hs = 1;
+        r.s = nx_start + 32;
+    } else if (nw.sp) {
+        r.hs = 1;
+        r.s = (int)nw.sp - 1;
+    } else {
+        r.hs = 0;
+        r.s = 0;
+    }
+    if (nw.ep && (int)nw.ep - 1 >= r.s) {
+        r.he = 1;
+        r.e = (int)nw.ep - 1;
+    } else if (nx.ep) {
+        r.he = 1;
+        r.e = nx_stop + 32;
+    } else {
+        r.he = 0;
+        r.e = 64;
+    }
+    return r;
+}
+
+// What generate_tones does for one band: region 1 = record k-1's waves at reg_offset 128, region 2 = record k's at 0.
+struct DecpToneJob {
+    int active;          // the function runs for this band
+    int n1, i1, n2, i2;  // waves synthesised (0 = the region stays zero) and the first wave's index
+    int h1, h2;          // the Hann multiplies of the two regions
+    DecpEnv e1, e2;
+};
+
+__device__ __forceinline__ DecpToneJob decp_tone_job(const TonalRec* rk, const TonalRec* rk1, const TonalRec* rk2, int ch, int b)
+{
+    const TonalBand nx = rk->band[ch][b], nw = rk1->band[ch][b], pv = rk2->band[ch][b];
+    DecpToneJob j;
+    j.active = (rk->present || rk1->present) && (nx.nw || nw.nw);
+    j.e2 = decp_curr_env(nx, nw);
+    j.e1 = decp_curr_env(nw, pv);   // what the function stored for record k-1 when frame k-1 ran (it ran: nw.nw != 0)
+    const int reg1 = j.e1.e < 32 ? 0 : 1, reg2 = j.e2.s >= 32 ? 0 : 1;
+    j.n1 = nw.nw && reg1 ? nw.nw : 0;
+    j.n2 = nx.nw && reg2 ? nx.nw : 0;
+    j.i1 = nw.start_index;
+    j.i2 = nx.start_index;
+    if (nw.nw && nx.nw && reg1 && reg2) {
+        j.h1 = 1;
+        j.h2 = 1;
+    } else {
+        j.h1 = nw.nw && !j.e1.he;
+        j.h2 = nx.nw && !j.e2.hs;
+    }
+    return j;
+}
+
+// waves_synth's sample i of a region: the waves in order, each out += sine_table[pos] * amp in double, then the envelope
+__device__ __forceinline__ float decp_waves(const DecToneTables* TT, const uint32_t* wave, int n, const DecpEnv& e, int reg, int i)
+{
+    float v = 0.0f;
+    for (int w = 0; w < n; ++w) {
+        const uint32_t wv = wave[w];
+        const int inc = (int)(wv & 1023u), sf = (int)((wv >> 10) & 63u), ph = (int)((wv >> 16) & 31u);
+        const double amp = (double)TT->amp_sf[sf];
+        const int pos = ((ph << 6) + (i - (reg ^ 128)) * inc) & 2047;   // (pos0 + i * inc) & 2047
+        v = (float)((double)v + (double)TT->sine[pos] * amp);
+    }
+    if (e.hs) {
+        const int pos = (e.s << 2) - reg;
+        if (pos > 0 && pos <= 128) {
+            if (i < pos) v = 0.0f;
+            else if (i < pos + 4 && (!e.he || e.s != e.e)) v = v * TT->hann[32 * (i - pos)];
+        }
+    }
+    if (e.he) {
+        const int pos = ((e.e + 1) << 2) - reg;
+        if (pos > 0 && pos <= 128) {
+            if (i >= pos) v = 0.0f;
+            else if (i >= pos - 4) v = v * TT->hann[32 * (pos - 1 - i)];
+        }
+    }
+    return v;
+}
 
 constexpr int kDecHist = 23;              // frame n-1's DCT-IV columns the FIR reaches
 constexpr int kDecCols = 128 + kDecHist;
@@ -359,6 +637,33 @@ __global__ __launch_bounds__(256) void k_at3pd_synth(DecSynthParams p)
             v = decp_win_first(T, r2[b * 256 + j], fl1, b, j) + decp_win_second(T, r1[b * 256 + 128 + j], fl1, b, j);
         }
         s_x[b][c] = v * rescale;
+    }
+    if (p.tones) {   // step 4b for frame n (role 0) and for frame n-1's last 23 samples (role 1)
+        __shared__ DecpToneJob s_job[2][16];
+        __shared__ uint32_t s_wave[3][kMaxWaves];   // the waves of records n, n-1, n-2
+        const DecToneTables* TT = p.TT;
+        if (tid < 32) {
+            const int role = tid >> 4, b = tid & 15;
+            s_job[role][b] = decp_tone_job(decp_tonal_rec(p.tonal, f - role, s, S), decp_tonal_rec(p.tonal, f - 1 - role, s, S),
+                                           decp_tonal_rec(p.tonal, f - 2 - role, s, S), ch, b);
+        }
+        for (int i = tid; i < 3 * kMaxWaves; i += 256) {
+            const int d = i / kMaxWaves;
+            s_wave[d][i - d * kMaxWaves] = decp_tonal_rec(p.tonal, f - d, s, S)->wave[i - d * kMaxWaves];
+        }
+        __syncthreads();
+        for (int i = tid; i < 16 * kDecCols; i += 256) {
+            const int b = i / kDecCols, c = i - b * kDecCols;
+            const int role = c < kDecHist ? 1 : 0, j = c < kDecHist ? 128 - kDecHist + c : c - kDecHist;
+            const DecpToneJob& J = s_job[role][b];
+            if (!J.active) continue;
+            float w1 = J.n1 ? decp_waves(TT, &s_wave[role + 1][J.i1], J.n1, J.e1, 128, j) : 0.0f;
+            float w2 = J.n2 ? decp_waves(TT, &s_wave[role][J.i2], J.n2, J.e2, 0, j) : 0.0f;
+            if (J.h1) w1 = w1 * TT->hann[128 + j];
+            if (J.h2) w2 = w2 * TT->hann[j];
+            const float g = 0.0f - (w1 + w2);
+            s_x[b][c] = s_x[b][c] - g;
+        }
     }
     __syncthreads();
     // dct4: out[15 - k] = (float)(sum_n (double)x[n] * cos16[k][n] * (1.0 / 1024)), the sum in order, each step rounded
@@ -404,17 +709,30 @@ __global__ __launch_bounds__(256) void k_at3pd_synth(DecSynthParams p)
     }
 }
 
-// The call's last two frames (slots F, F + 1) become slots 0 and 1 of the next call.
-__global__ __launch_bounds__(256) void k_at3pd_state(float* raw, uint16_t* flags, int32_t n_frames, int32_t n_streams, int32_t nch)
+// The call's last two frames (slots F, F + 1) become slots 0 and 1 of the next call, and its last three tonal records (slots F ..
+// F + 2) slots 0 .. 2.
+__global__ __launch_bounds__(256) void k_at3pd_state(float* raw, uint16_t* flags, TonalRec* tonal, int32_t n_frames, int32_t n_streams,
+                                                     int32_t nch)
 {
     __shared__ float s_raw[2][4096];
     __shared__ uint16_t s_fl[2];
+    __shared__ uint32_t s_tone[kTonalCarry][kTonalWords];
     const int sc = blockIdx.x, s = sc / nch, ch = sc - s * nch, tid = threadIdx.x;
     for (int i = tid; i < 8192; i += 256) s_raw[i >> 12][i & 4095] = raw[decp_rec(n_frames + (i >> 12), s, ch, n_streams, nch) * 4096 + (i & 4095)];
     if (tid < 2) s_fl[tid] = flags[decp_rec(n_frames + tid, s, ch, n_streams, nch)];
+    if (ch == 0)
+        for (int i = tid; i < kTonalCarry * kTonalWords; i += 256) {
+            const int k = i / kTonalWords;
+            s_tone[k][i - k * kTonalWords] = ((const uint32_t*)decp_tonal_rec(tonal, n_frames - kTonalCarry + k, s, n_streams))[i - k * kTonalWords];
+        }
     __syncthreads();
     for (int i = tid; i < 8192; i += 256) raw[decp_rec(i >> 12, s, ch, n_streams, nch) * 4096 + (i & 4095)] = s_raw[i >> 12][i & 4095];
     if (tid < 2) flags[decp_rec(tid, s, ch, n_streams, nch)] = s_fl[tid];
+    if (ch == 0)
+        for (int i = tid; i < kTonalCarry * kTonalWords; i += 256) {
+            const int k = i / kTonalWords;
+            ((uint32_t*)decp_tonal_rec(tonal, k - kTonalCarry, s, n_streams))[i - k * kTonalWords] = s_tone[k][i - k * kTonalWords];
+        }
 }
 
 }  // namespace at3p

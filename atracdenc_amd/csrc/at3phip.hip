@@ -425,6 +425,7 @@ int at3phip_host_tables(void* dst, size_t bytes)
 #include "at3p_decode.hpp"
 
 static_assert(sizeof(DecTables) == AT3PHIP_DECODER_TABLES_BYTES, "at3phip.h documents the decoder's table block size");
+static_assert(sizeof(DecToneTables) == AT3PHIP_DECODER_TONE_TABLES_BYTES, "at3phip.h documents the tone table block size");
 
 struct at3phip_decoder : at3host::DecoderBase {
     at3phip_decoder_config cfg;
@@ -432,6 +433,8 @@ struct at3phip_decoder : at3host::DecoderBase {
     uint8_t* d_frames = nullptr;   // staging for host frames [S][F][2048]
     float* d_raw = nullptr;        // [F + 2][S][C][16][256]: slots 0, 1 = the carried frames -2, -1
     uint16_t* d_flags = nullptr;   // [F + 2][S][C]
+    TonalRec* d_tonal = nullptr;   // [F + 3][S]: slots 0 .. 2 = the carried records of frames -3 .. -1
+    DecToneTables* d_tone_tables = nullptr;
     void* d_out = nullptr;         // staging for host output [S][F][2048][C] float32
     // (d_rejected: [kDecReasons])
 };
@@ -439,6 +442,17 @@ struct at3phip_decoder : at3host::DecoderBase {
 namespace {
 
 #include "at3p_mant.inc"
+#include "at3p_tone_vlc.inc"
+
+// The tone synthesis' tables as ff_atrac3p_init_dsp_static builds them, with the host's libm (never constant-folded: optnone).
+__attribute__((optnone, noinline)) void build_decp_tone_tables(DecToneTables* t)
+{
+    memset(t, 0, sizeof(*t));
+    for (int i = 0; i < 2048; ++i) t->sine[i] = (float)sin(2 * M_PI * i / 2048);
+    for (int i = 0; i < 256; ++i) t->hann[i] = (float)((1.0f - cos(2 * M_PI * i / 256.0f)) * 0.5f);
+    for (int i = 0; i < 64; ++i) t->amp_sf[i] = exp2f((i - 3) / 4.0f);
+    memcpy(t->vlc, AT3P_TONE_BANDS_VLC, sizeof(t->vlc));
+}
 
 // The decoder's table block: the shared entries from the encoder's builder, the cosines of the synthesis's DCT-IV with the
 // host's libm (never constant-folded: optnone), and the two-level VLC look-up expanded from the frame writer's code tables.
@@ -492,6 +506,7 @@ int decp_reset_state(at3phip_decoder* d)
     const size_t S = d->cfg.n_streams, C = d->cfg.channels;
     HIPCHK(d, hipMemsetAsync(d->d_raw, 0, 2 * S * C * 4096 * sizeof(float), d->stream));
     HIPCHK(d, hipMemsetAsync(d->d_flags, 0, 2 * S * C * sizeof(uint16_t), d->stream));
+    HIPCHK(d, hipMemsetAsync(d->d_tonal, 0, kTonalCarry * S * sizeof(TonalRec), d->stream));   // no tonal block
     HIPCHK(d, hipMemsetAsync(d->d_rejected, 0, kDecReasons * sizeof(unsigned long long), d->stream));
     HIPCHK(d, hipStreamSynchronize(d->stream));
     return AT3HIP_OK;
@@ -516,6 +531,17 @@ int at3phip_decoder_create(const at3phip_decoder_config* cfg, at3phip_decoder** 
         if ((rc = dev_alloc(d, &d->d_raw, (F + 2) * S * C * 4096)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_flags, (F + 2) * S * C)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_rejected, kDecReasons)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_tonal, (F + kTonalCarry) * S)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_tone_tables, 1)) != AT3HIP_OK) return rc;
+        {
+            DecToneTables* h = new (std::nothrow) DecToneTables();
+            if (!h) return fail(d, AT3HIP_ENOMEM, "out of host memory");
+            build_decp_tone_tables(h);
+            hipError_t e = hipMemcpy(d->d_tone_tables, h, sizeof(DecToneTables), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipDeviceSynchronize();   // (pageable source, as the decoder's table block)
+            delete h;
+            HIPCHK(d, e);
+        }
         float* d_out = nullptr;
         if ((rc = dev_alloc(d, &d_out, S * F * 2048 * C)) != AT3HIP_OK) return rc;
         d->d_out = d_out;
@@ -525,7 +551,8 @@ int at3phip_decoder_create(const at3phip_decoder_config* cfg, at3phip_decoder** 
 
 void at3phip_decoder_destroy(at3phip_decoder* d)
 {
-    if (d) at3host::destroy_decoder(d, {d->d_tables, d->d_frames, d->d_raw, d->d_flags, d->d_rejected, d->d_out});
+    if (d) at3host::destroy_decoder(d, {d->d_tables, d->d_frames, d->d_raw, d->d_flags, d->d_rejected, d->d_out, d->d_tonal,
+                                            d->d_tone_tables});
 }
 
 const char* at3phip_decoder_last_error(const at3phip_decoder* d) { return at3host::decoder_last_error(d); }
@@ -559,13 +586,14 @@ int at3phip_decoder_get_counters(at3phip_decoder* d, at3phip_decoder_counters* o
 
 int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags)
 {
-    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3PHIP_DECODE_S16;
+    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES;
     if (!d || !frames || !pcm || n_frames < 1 || n_frames > d->cfg.max_frames || (flags & ~known))
         return d ? fail(d, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
     at3host::DeviceGuard guard(d->device);
     HIPCHK(d, guard.error());
     const size_t S = d->cfg.n_streams, F = (size_t)n_frames, C = d->cfg.channels;
     const bool s16 = flags & AT3PHIP_DECODE_S16;
+    const int tones = (flags & AT3PHIP_DECODE_TONES) ? 1 : 0;
     hipStream_t st = d->stream;
     const uint8_t* d_frames = frames;
     if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
@@ -583,6 +611,9 @@ int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, 
     up.raw = d->d_raw;
     up.flags = d->d_flags;
     up.rejected = d->d_rejected;
+    up.tonal = d->d_tonal;
+    up.tone_vlc = d->d_tone_tables->vlc;
+    up.tones = tones;
     hipLaunchKernelGGL(k_at3pd_unpack, dim3((unsigned)F, (unsigned)S), dim3(kDecUnpackThreads), 0, st, up);
     HIPCHK(d, hipGetLastError());
     DecSynthParams sp;
@@ -594,9 +625,13 @@ int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, 
     sp.n_streams = (int)S;
     sp.nch = (int)C;
     sp.s16 = s16 ? 1 : 0;
+    sp.tonal = d->d_tonal;
+    sp.TT = d->d_tone_tables;
+    sp.tones = tones;
     hipLaunchKernelGGL(k_at3pd_synth, dim3((unsigned)F, (unsigned)(S * C)), dim3(256), 0, st, sp);
     HIPCHK(d, hipGetLastError());
-    hipLaunchKernelGGL(k_at3pd_state, dim3((unsigned)(S * C)), dim3(256), 0, st, d->d_raw, d->d_flags, n_frames, (int32_t)S, (int32_t)C);
+    hipLaunchKernelGGL(k_at3pd_state, dim3((unsigned)(S * C)), dim3(256), 0, st, d->d_raw, d->d_flags, d->d_tonal, n_frames, (int32_t)S,
+                       (int32_t)C);
     HIPCHK(d, hipGetLastError());
     if (!(flags & AT3HIP_OUT_ON_DEVICE))
         HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 2048 * C * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
@@ -612,6 +647,13 @@ int at3phip_decoder_host_tables(void* dst, size_t bytes)
     if (ok) memcpy(dst, t, sizeof(DecTables));
     delete t;
     return ok ? AT3HIP_OK : AT3HIP_ENOMEM;
+}
+
+int at3phip_decoder_host_tone_tables(void* dst, size_t bytes)
+{
+    if (!dst || bytes != sizeof(DecToneTables)) return AT3HIP_EINVAL;
+    build_decp_tone_tables((DecToneTables*)dst);
+    return AT3HIP_OK;
 }
 
 }  // extern "C"

@@ -411,7 +411,7 @@ int decode_at3p(const std::string& inFile, const std::string& outFile, const TAt
             at3phip_decoder_destroy(dec);
             return 1;
         }
-        rc = at3phip_decode(dec, frames.data(), n, pcm.data(), AT3PHIP_DECODE_S16);
+        rc = at3phip_decode(dec, frames.data(), n, pcm.data(), AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES);
         if (rc != AT3HIP_OK) {
             std::cerr << "Encode/Decode error: at3phip_decode: " << at3phip_decoder_last_error(dec) << std::endl;
             at3phip_decoder_destroy(dec);

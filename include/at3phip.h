@@ -142,9 +142,44 @@ int at3phip_host_write_tables(void* dst, size_t bytes);
  *      the transform and the filter bank's 368) is not trimmed.
  *   7. A frame is rejected (counted per reason, at3phip_decoder_counters) for: a bad first bit or block type; a syntax element
  *      outside what the writer emits (mute, modes, power levels other than 15, swap / negate, gain compensation, noise); a
- *      tonal block; an invalid code or an out-of-range value (every code table is complete, so this is a word length of 0);
+ *      tonal block (unless AT3PHIP_DECODE_TONES); an invalid code or an out-of-range value (every code table is complete, so this is a word length of 0);
  *      a read past the frame's 2048 bytes; a terminator other than 3. A rejected frame decodes as a zero spectrum in every
  *      channel with all-sine windows, and those are the flags frame n+1 pairs with. */
+/* TONAL BLOCKS (AT3PHIP_DECODE_TONES). The sine waves the reference encoder's GHA analysis subtracted from the subband signal
+ * (at3p.cpp:118-170, TGhaProcessorBase::ApplyFilter) are added back. Without the flag every step above stands as written.
+ *   1. Unpack: when the tonal flag is 1 it is followed, in the order of TTonalComponentEncoder::WriteTonalBlock and
+ *      CreateFreqBitPack (at3p_bitstream.cpp:41-95, 487-629), by:
+ *      - the amplitude mode (1 bit), must be 1; NumToneBands - 1 as a code of HuffTabs.NumToneBands (at3p_tone_vlc.inc);
+ *      - stereo: the tone-sharing flags (0 = none, 1 0 = all, 1 1 + one bit per band); the leader flag as a one-band flag set,
+ *        0 or 1 0. Decision: 1 0 swaps channels 0 and 1 for every tone band, as ApplyFilter does; 1 1 (never written) must not
+ *        occur. Then the invert-phase flags (1 bit), must be 0;
+ *      - per channel (channel 1 skips every shared band): channel 1's envelope-copy bit, must be 0; per band the envelope's
+ *        start and stop point, each a presence bit and 5 bits when present; the num-waves mode (ch + 1 bits), must be 0, then
+ *        4 bits of wave count per band; channel 1's delta-to-leader bit, must be 0; per band with waves its frequencies: an
+ *        order bit (only with 2 or more waves; 0 = ascending). Ascending: the first in 10 bits, then each after a predecessor
+ *        p < 512 in 10 bits, else in b = GetFirstSetBit(1023 - p) + 1 bits as f - (1024 - 2^b). Descending: the last wave's in
+ *        10 bits, then towards the first each in GetFirstSetBit(p) + 1 bits (GetFirstSetBit(0) = 0). Then the amplitude mode
+ *        (ch + 1 bits), must be 0, 6 bits of amp_sf per wave, and 5 bits of phase per wave, band by band.
+ *      A "must" failing counts as unsupported_syntax, more than 48 waves in the frame as bad_code, a read past the frame as
+ *      read_past_end; tonal_present does not count. Decision: NumToneBands may exceed the quant unit count (the writer aborts
+ *      instead of writing such a frame): the synthesis is defined for all 16 subbands.
+ *      Per-frame state, as ApplyFilter keeps it: every frame starts with no waves in all 16 bands of both channels; an absent
+ *      start point is start_pos -1, an absent stop point stop_pos 32; start_index is assigned band by band, channel 0 first;
+ *      a shared band of channel 1 copies channel 0's record, and the leader swap follows the copy. tones_present is 0 for a frame
+ *      without a tonal block, a rejected frame and any frame decoded without the flag.
+ *   4b. Between steps 4 and 5, per channel and subband sb = 0..15 (every subband, coded or not), where
+ *      ff_atrac3p_generate_tones' condition holds (frame n or n-1 has tones present, and the band has waves in frame n or n-1):
+ *      let g be that function's output on a zero-filled 128-sample buffer, with tones_info = frame n's block and
+ *      tones_info_prev = frame n-1's (its curr_env reconstructed as the function reconstructed it for frame n-1), so
+ *      g = 0.0f - (wavreg1 + wavreg2). The rescaled sample s becomes s - g[i]; elsewhere it is left alone. Frame n's block goes
+ *      with frame n's subband samples (the overlap of spectra n-1 and n): the encoder writes the previous call's block.
+ *      Numerics: amp = (double)amp_sf_tab[amp_sf] (amplitude mode 1); every out += sine_table[pos] * amp is a double multiply
+ *      and a double add rounded to float, wave by wave in order; pos = (64 phase + i inc) & 2047 at offset 128 and
+ *      (64 phase + (i - 128) inc) & 2047 at offset 0; the envelopes' Hann multiplies and the overlap are float; no FMA. The
+ *      tables (sine_table[2048], hann_window[256], amp_sf_tab[64]) are ff_atrac3p_init_dsp_static's, built with the host's libm
+ *      (at3phip_decoder_host_tone_tables).
+ *   Stream state gains the last three frames' tonal records; calls without the flag leave records without waves, and step 4b
+ *   runs only in calls with the flag. */
 typedef struct at3phip_decoder at3phip_decoder;
 
 typedef struct at3phip_decoder_config {
@@ -160,6 +195,7 @@ void at3phip_decoder_destroy(at3phip_decoder* dec);
 const char* at3phip_decoder_last_error(const at3phip_decoder* dec);
 
 #define AT3PHIP_DECODE_S16 8u   /* the bit of AT3HIP_DECODE_S16 */
+#define AT3PHIP_DECODE_TONES 16u   /* decode tonal blocks: rule 7 no longer rejects them (TONAL BLOCKS below) */
 
 /*   frames [n_streams][n_frames][2048] bytes
  *   pcm    [n_streams][n_frames][2048][channels]: float32, or int16 with AT3PHIP_DECODE_S16
@@ -194,6 +230,12 @@ int at3phip_decoder_set_stream(at3phip_decoder* dec, void* hip_stream);
  * The decoder is part of ABI 1.6 (see at3hip.h): a host that needs it looks for the symbol at3phip_decoder_create. */
 #define AT3PHIP_DECODER_TABLES_BYTES 67328
 int at3phip_decoder_host_tables(void* dst, size_t bytes);
+
+/* The tone synthesis' tables as at3phip_decoder_create builds them, on the host (no GPU needed): float sine_table[2048],
+ * float hann_window[256], float amp_sf_tab[64], then the 16 uint16 codes of NumToneBands - 1 (code | length << 12).
+ * bytes = AT3PHIP_DECODER_TONE_TABLES_BYTES. Still ABI 1.6: a host that needs AT3PHIP_DECODE_TONES looks for this symbol. */
+#define AT3PHIP_DECODER_TONE_TABLES_BYTES 9504
+int at3phip_decoder_host_tone_tables(void* dst, size_t bytes);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
