@@ -110,7 +110,6 @@ struct FrontParams {
     int32_t n_frames, nch;
     int32_t first;       // call starts at the stream start: the detectors' LastEnergy is 0.0
     int32_t window_auto, window_mask;
-    int32_t debug;       // AT1HIP_DEBUG_STOP: leave the kernel after phase n (timing experiments only)
     float* specs;        // [S][F][nch][512] MDCT spectrum (kept for the tap interface)
     float* values;       // [S][F][nch][512] scaled mantissa sources, BFU after BFU
     float* energy;       // [S][F][nch][52]
@@ -243,7 +242,6 @@ __global__ __launch_bounds__(64) void k_at1_front(FrontParams p)
     if (lane == 63) s_dhi[292] = 0.0f;   // HPFBuffer[BlockSz + 20] is never written: the sample after the block reads as 0
     wave_sync();
 
-    if (p.debug == 1) return;
     // Atrac1AnalysisFilterBank::Analysis (atrac/at1/atrac1_qmf.h:37-43): Qmf1 over the PCM ...
 #pragma unroll
     for (int round = 0; round < 2; ++round) {
@@ -266,7 +264,6 @@ __global__ __launch_bounds__(64) void k_at1_front(FrontParams p)
         }
     }
     wave_sync();
-    if (p.debug == 2) return;
     // ... Qmf2 over its lower half; the upper half is delayed by 39 samples
     if (lane < 41) {
         // outputs q = -36 + 4 lane + r; the first pair read is lower-band index 2 q - 46 = 8 lane - 118, buffer index 8 lane
@@ -285,7 +282,6 @@ __global__ __launch_bounds__(64) void k_at1_front(FrontParams p)
         s_dmid[164] = 0.0f;
     }
     wave_sync();
-    if (p.debug == 3) return;
     int mask = p.window_mask;
     if (p.window_auto) {
         // TTransientDetector::HPFilter (transient_detector.cpp:48-66) for this unit (512 outputs: a round of 64 stays inside
@@ -346,7 +342,6 @@ __global__ __launch_bounds__(64) void k_at1_front(FrontParams p)
         wave_sync();   // the filter output is dead: its storage becomes the FFT buffer
     }
 
-    if (p.debug == 4) return;
     // the lane's FFT twiddles (their indices depend on the window mask only) are requested before the pre-rotation
     const at3::cpx* tw128 = T->tw128;   // tw128 | tw64 | tw16 are contiguous
     const int f_bsel = lane < 32 ? 2 : lane < 48 ? 0 : 1;
@@ -401,7 +396,6 @@ __global__ __launch_bounds__(64) void k_at1_front(FrontParams p)
         s_f[(b == 0 ? 0 : b == 1 ? 64 : 128) + 16 * k + leaf] = v;
     }
     wave_sync();
-    if (p.debug == 5) return;
     {
         // All three bands' transforms at once: a radix-4 stage has 32 butterflies in the high band (one 128-point or
         // eight 16-point transforms) and 16 each in the low and middle bands (one 64-point or four 16-point) - 64 lanes.
@@ -434,7 +428,6 @@ __global__ __launch_bounds__(64) void k_at1_front(FrontParams p)
             wave_sync();
         }
     }
-    if (p.debug == 6) return;
     // post-rotation (mdct.h:89-101), the high band's short-window gain and the mirrored bands (atrac1denc.cpp:92-97)
 #pragma unroll
     for (int round = 0; round < 4; ++round) {
@@ -464,7 +457,6 @@ __global__ __launch_bounds__(64) void k_at1_front(FrontParams p)
     }
     wave_sync();
 
-    if (p.debug == 7) return;
     // the spectrum leaves for HBM; the per-channel loudness (an ordered sum over its 512 lines) is k_at1_loud's
 #pragma unroll
     for (int r = 0; r < 2; ++r)

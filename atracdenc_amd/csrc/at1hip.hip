@@ -19,7 +19,6 @@ static_assert(sizeof(Tables) == AT1HIP_TABLES_BYTES, "at1hip.h documents the tab
 struct at1hip_ctx {
     at1hip_config cfg;
     int device = 0;
-    int debug_stop = 0;           // AT1HIP_DEBUG_STOP, honoured by -DAT3HIP_DEBUG_KNOBS builds only
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {};
     bool tm_pending = false;      // a call's stage events have not been read yet (AT3HIP_ASYNC)
@@ -77,9 +76,6 @@ int at1hip_create(const at1hip_config* cfg, at1hip_ctx** out)
     if (!c) return AT3HIP_ENOMEM;
     c->cfg = *cfg;
     c->device = cfg->device_id;
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (const char* dbg = getenv("AT1HIP_DEBUG_STOP")) c->debug_stop = atoi(dbg);
-#endif
     int rc = AT3HIP_OK;
     auto bail = [&](int code) {
         at1hip_destroy(c);
@@ -169,7 +165,6 @@ int at1hip_encode(at1hip_ctx* c, const float* pcm, int32_t n_blocks, uint8_t* ou
     fp.first = c->blocks_fed == 0;
     fp.window_auto = c->cfg.window_auto ? 1 : 0;
     fp.window_mask = c->cfg.window_mask;
-    fp.debug = c->debug_stop;
     fp.specs = c->d_specs;
     fp.values = c->d_values;
     fp.energy = c->d_energy;

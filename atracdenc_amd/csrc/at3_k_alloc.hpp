@@ -24,37 +24,6 @@
 
 namespace at3 {
 
-// Profiling builds (-DAT3HIP_DEBUG_KNOBS): every wavefront of k_alloc_pack stamps its phase boundaries with the shader-cycle
-// counter and adds the cycles it spent per phase to AT3HIP_TAP_CLOCK's slots 2.. (tools/alloc_phase_cycles.sh) - where a
-// wavefront's LIFE goes, measured on the real path (the stage exits of debug_stop leave the unit cache empty, so what follows
-// them is not the real bisection).
-#ifdef AT3HIP_DEBUG_KNOBS
-struct PhaseClock {
-    unsigned long long last;
-    unsigned long long* slots;   // this wavefront's row of 12 counters (256 rows, by workgroup index: no contention to speak of)
-    unsigned long long* item;    // the first 16384 workgroups also keep their own 12 (tools/alloc_item_times.sh)
-};
-#define AT3_PH_END(pc, k)                                                                    \
-    do {                                                                                     \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();                          \
-        if ((pc).slots && threadIdx.x == 0) atomicAdd((pc).slots + (k), t_ - (pc).last);     \
-        if ((pc).item && threadIdx.x == 0) (pc).item[k] += t_ - (pc).last;                   \
-        (pc).last = t_;                                                                      \
-    } while (0)
-#else
-struct PhaseClock {};
-#define AT3_PH_END(pc, k) ((void)0)
-#endif
-// -DAT3_LOOP_PHASES (with AT3HIP_DEBUG_KNOBS; tools/alloc_loop_phases.sh): the rate loop's own parts instead of the units' - slots 5..9 =
-// trip head + memo look-up, allocation + tonal side information, sums + decision, record + comparison + interval, BFU drops; slot 10 = units + emission
-#ifdef AT3_LOOP_PHASES
-#define AT3_UPH(pc, k, kl) do { if ((kl) >= 0) AT3_PH_END(pc, kl); } while (0)
-#define AT3_LPH(pc, k) AT3_PH_END(pc, k)
-#else
-#define AT3_UPH(pc, k, kl) AT3_PH_END(pc, k)
-#define AT3_LPH(pc, k) ((void)0)
-#endif
-
 // SIMT harness only (tools/emu, AT3_EMU_HOST): the rate loop counts what it does - and checks every lower bound of unit_bounds
 // against the bits compute_units finds later - in g_alloc_stats (tools/emu/emu_runtime.cpp; printed and asserted by run_emu.py):
 // 0 trips, 1 hits of exact records, 2 evaluations in place of bound records, 3 evaluations, 4 unit_bounds calls, 5 their units,
@@ -298,9 +267,8 @@ __device__ __forceinline__ float ordered_square_sum(const float* v, int n)
 //     (Pairs at wordlen 1: the pair table grows with either |m|, so the pair of the smaller magnitudes bounds it.)
 // Rounding and lengths in one go, sixteen lines per lane in registers: nothing is stored but the counts; no lane conditions.
 // The rows of lb sit in lanes 8..15 of the lane table's length words (tab_row reads lanes 0..7). Wave-uniform call.
-__device__ __forceinline__ void unit_bounds(AllocLds& L, const LaneTab& tab, uint32_t need, int bits, int lane_, PhaseClock& pc)
+__device__ __forceinline__ void unit_bounds(AllocLds& L, const LaneTab& tab, uint32_t need, int bits, int lane_)
 {
-    AT3_UPH(pc, 4, 7);
     // (the lane conditions below are formed here, where they are used: hoisted in front of the rate loop they would sit in scalar
     // registers the loop does not have - it already parks some of its masks in vector lanes)
     const int lane = opaque_lane_value(lane_);
@@ -356,17 +324,15 @@ __device__ __forceinline__ void unit_bounds(AllocLds& L, const LaneTab& tab, uin
         unit_cost_store(L, tab, h, wl, vb, lane);
     }
     wave_sync();
-    AT3_UPH(pc, 5, 10);
 }
 
 // Quantise the units {(b, wl_b) : bit b of `need`}, wl_b = lane b's `bits` (QuantMantisas + CLC/VLC cost,
 // atrac3_bitstream.cpp:154-173, atrac_scale.cpp:40-130). Lane b keeps BFU b's e1 in `my_e1` (from BFU 19 on formed here, on first use). Wave-uniform call.
-__device__ __forceinline__ void compute_units(AllocLds& L, const LaneTab& tab, uint32_t need, int bits, float& my_e1, int lane_, float* qerr, PhaseClock& pc, int dbg = 0)
+__device__ __forceinline__ void compute_units(AllocLds& L, const LaneTab& tab, uint32_t need, int bits, float& my_e1, int lane_, float* qerr)
 {
     // (lane constants - addresses, masks - are formed where they are used: since the bounds the call is rare (once or twice per channel-frame), and
     // hoisted in front of the rate loop they would hold registers across it that the loop's own code is short of)
     const int lane = opaque_lane_value(lane_);
-    AT3_UPH(pc, 4, 7);
     // ---- (1) mantissa = lrint(value * MaxQuant[wl]) for the lines of the needed BFUs; energy-adaptive candidate codes ----
     // Four rounds of four lines per lane, line0 = 256 round + 4 lane: a wavefront's 16-byte LDS accesses are one contiguous
     // kilobyte (sixteen lines per lane, the first layout, put every fourth lane on the same banks).
@@ -420,10 +386,6 @@ __device__ __forceinline__ void compute_units(AllocLds& L, const LaneTab& tab, u
         }
     }
     wave_sync();
-    AT3_UPH(pc, 5, -1);
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (dbg == 9) return;
-#endif
     // ---- (2) e2 = sum of (mantissa / mul)^2, strictly in line order: one lane per unit ----
     const bool mine = lane < 32 && ((need >> lane) & 1u);
     const int my_start = bfu_start(lane & 31), my_n = bfu_start((lane & 31) + 1) - my_start;
@@ -467,20 +429,12 @@ __device__ __forceinline__ void compute_units(AllocLds& L, const LaneTab& tab, u
         my_e2 = acc;
     }
     wave_sync();   // the terms' storage becomes the key list and the candidate records
-    AT3_UPH(pc, 6, -1);
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (dbg == 10) return;
-#endif
     // ---- (3) energy-adaptive re-rounding of the new units above BFU 18 (atrac_scale.cpp:66-128) ----
     // A line is a candidate when it passes the side test of the pass that will run (skipped candidates change no state),
     // and the pass visits the candidates by ascending |delta|: the position of a candidate is the number of keys of its unit
     // below its own. Units are walked one after the other (uniform), a unit's lines by the lanes; the candidate's rank, its
     // current |mantissa| and the sign its new mantissa would get go into a 16-bit record at the rank's position.
-#ifdef AT3HIP_DEBUG_KNOBS
-    const uint32_t ea_need = dbg == 5 ? 0u : (need & 0xfff80000u);
-#else
     const uint32_t ea_need = need & 0xfff80000u;
-#endif
 
     int my_nc = 0;   // lane 19 + ub: candidates of its unit
     if (ea_need) {
@@ -608,7 +562,6 @@ __device__ __forceinline__ void compute_units(AllocLds& L, const LaneTab& tab, u
             if (lane == bfu) my_nc = cnt_u;
             wave_sync();   // the key list is reused by the next unit
         }
-        AT3_UPH(pc, 7, -1);
         // equal keys among listed candidates: libstdc++'s std::sort order decides (rare). The order of equal elements
         // depends on the whole array the reference sorts, so the full |delta| < 0.25 list is rebuilt, sorted with the
         // restated algorithm and then filtered.
@@ -649,9 +602,6 @@ __device__ __forceinline__ void compute_units(AllocLds& L, const LaneTab& tab, u
         // the sequential pass, one lane per unit: only |mantissa| enters the energy bookkeeping - the re-rounded code is
         // |m0| + 1 (e2 < e1; a zero becomes +-1) or |m0| - 1 (e2 > e1), atrac_scale.cpp:86-118; the ordered part per
         // candidate is ex = (e2 - d0) + d1 and the test, everything else is ready before the chain reaches it
-#ifdef AT3HIP_DEBUG_KNOBS
-        if (dbg == 6) my_nc = 0;
-#endif
         if (mine && lane > 18 && my_nc > 0) {
             const float e1 = my_e1;
             float e2 = my_e2;
@@ -700,7 +650,6 @@ __device__ __forceinline__ void compute_units(AllocLds& L, const LaneTab& tab, u
         }
     }
     wave_sync();
-    AT3_UPH(pc, 8, -1);
     // ---- (4) VLC cost of the final mantissas; (5) cache entries ----
     VlcRow row_h[4];   // (the four rounds' length rows requested together)
 #pragma unroll
@@ -728,7 +677,6 @@ __device__ __forceinline__ void compute_units(AllocLds& L, const LaneTab& tab, u
     }
     if (mine && qerr) qerr[(bits - 1) * 32 + lane] = my_e1 / my_e2;   // BFUs >= 10: nothing but the QUANT tap looks at their energy error
     wave_sync();
-    AT3_UPH(pc, 9, 10);
 }
 
 // The 70 units of BFUs 0..9 (8 or 16 lines each, no energy-adaptive pass below BFU 19), one lane per unit: ConsiderEnergyErr
@@ -911,15 +859,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
         clk_t0 = __builtin_amdgcn_s_memtime();
         clk_r0 = __builtin_amdgcn_s_memrealtime();
     }
-    PhaseClock pc;
-#ifdef AT3HIP_DEBUG_KNOBS
-    pc.last = __builtin_amdgcn_s_memtime();
-    pc.slots = p.clk ? p.clk + 16 + (blockIdx.x & 255u) * 12u : nullptr;
-    const unsigned long long item_r0 = __builtin_amdgcn_s_memrealtime();   // per-item life (100 MHz): tools/alloc_item_times.sh
-    pc.item = (p.clk && blockIdx.x < 16384u) ? p.clk + 16 + 2 * 256 * 12 + 2 * 16384 + 12 * blockIdx.x : nullptr;
-    if (pc.item && lane == 0)
-        for (int k = 0; k < 12; ++k) pc.item[k] = 0ull;
-#endif
     const int ch = (int)(cf & 1);
     const int fo = (int)((cf >> 1) % n_out);
     const int s = (int)((cf >> 1) / n_out);
@@ -1046,25 +985,16 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
         }
     }
     __syncthreads();
-    AT3_PH_END(pc, 0);
     // lane b < 19: e1 of BFU b. From BFU 19 on e1 is only read by the energy-adaptive pass of one of the BFU's units (its lane
     // forms it then, compute_units; -1 = not yet) - the pass runs for the final allocation's units and few others, the two 128-line
     // BFUs are mostly dropped before that, and their chain of additions is four times the longest one here
     float my_e1 = -1.0f;
     if (lane < 19) my_e1 = ordered_square_sum(L.val + bfu_start(lane), bfu_start(lane + 1) - bfu_start(lane));
     __syncthreads();
-    AT3_PH_END(pc, 1);
     // units of the first ten BFUs at every wordlen: ConsiderEnergyErr (atrac3_bitstream.cpp:241-257) looks at their energy
     // errors whatever the allocation, and they are 96 lines in all
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug_stop == 1) return;
-#endif
     const LaneTab tab = lane_tab(lane);
     small_units(L, tab, lane, my_e1);
-    AT3_PH_END(pc, 2);
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug_stop == 2) return;
-#endif
     // lane i: bit wl set = the cache holds the VLC bits of unit (BFU i, wl); bit 8 + wl set = it holds them or a lower bound (unit_bounds)
     uint32_t valid = lane < 10 ? 0xfefeu : 0u;
     // ---- TConfigure: spread (sequential float sums, every lane computes the same value) ----
@@ -1173,7 +1103,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
     wave_sync();
     for (int k = lane; k < 7 * kChgWords; k += 64) L.chg[k] = 0u;   // (same bytes as the energy errors, dead from here on)
     wave_sync();
-    AT3_PH_END(pc, 3);
     // ---- rate loop: TConfigure / TAlloc under the bisection driver (uniform control flow) ----
     int num_bfu = p.bfu_idx_const ? p.bfu_idx_const : 32;
     if (target < 101) {
@@ -1242,7 +1171,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
             // decided - and for the same one after BFUs were dropped, as long as it still decides it - but not for an
             // evaluation that ends the bisection, which needs the bits themselves: those are evaluated again, in place)
             const uint32_t hit_nz = hit ? (uint32_t)__builtin_amdgcn_readlane((int)m_nz, hit_k) : 0u;
-            AT3_LPH(pc, 5);
             AT3_STAT(0, 1);
             if (hit && (hit_nz >> 8) == 0u) {
                 acc = (uint32_t)__builtin_amdgcn_readlane((int)m_acc, hit_k);
@@ -1287,7 +1215,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
                 const uint32_t group_bands = (uint32_t)(__popcll(m0) + __popcll(m1) + __popcll(m2) + __popcll(m3));
                 if (groups) tonal_bits = 5u + 2u + 10u * groups + 12u * group_bands + members;
             }
-            AT3_LPH(pc, 6);
             // The units this allocation asks for (TEncCache, atrac_enc_cache.cpp) are brought in only as far as the comparison with
             // the target needs them: spec bits = 3 per BFU + 6 per coded BFU + min(CLC, VLC) are at most the CLC bits (known from the
             // wordlens alone) and at least min(CLC, a lower bound of the VLC bits). unit_bounds gives a close lower bound of a new
@@ -1296,13 +1223,8 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
             // bits: the frame is coded from it.
             {
                 const uint32_t need = (uint32_t)__ballot(lane < 32 && bits != 0 && !((valid >> (8 + bits)) & 1u));
-#ifdef AT3HIP_DEBUG_KNOBS
-                if (need && p.debug_stop == 4) {   // the loop without the units (their cache entries stay zero)
-                    if (lane < 32 && ((need >> lane) & 1u)) valid |= 0x101u << bits;
-                } else
-#endif
                 if (need) {
-                    unit_bounds(L, tab, need, bits, lane, pc);
+                    unit_bounds(L, tab, need, bits, lane);
                     AT3_STAT(4, 1); AT3_STAT(5, __popc(need));
                     if (lane < 32 && ((need >> lane) & 1u)) valid |= (lane < 19 ? 0x101u : 0x100u) << bits;
                 }
@@ -1325,30 +1247,23 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
                     }
                 }
                 if (kind == 0u) {
-#if defined(AT3_EMU_HOST) || defined(AT3HIP_DEBUG_KNOBS)
+#ifdef AT3_EMU_HOST
                     const uint32_t bound_i = s_cost[cost_at];
 #endif
-                    compute_units(L, tab, inexact, bits, my_e1, lane, qerr, pc, p.debug_stop);
+                    compute_units(L, tab, inexact, bits, my_e1, lane, qerr);
                     AT3_STAT(6, 1); AT3_STAT(7, __popc(inexact));
-#if defined(AT3_EMU_HOST) || defined(AT3HIP_DEBUG_KNOBS)
+#ifdef AT3_EMU_HOST
                     // every lower bound the loop decided with against the bits that now replace it: none may exceed them (the SIMT harness
-                    // asserts `bad 0`; profiling builds count the same on the hardware - AT3HIP_TAP_CLOCK words 13 / 14, tools/fuzz_gpu.py --bounds)
+                    // asserts `bad 0`)
                     const unsigned long long above = __ballot(lane < 32 && ((inexact >> lane) & 1u) && bound_i > (uint32_t)s_cost[cost_at]);
                     AT3_STAT(11, __popc(inexact));
                     AT3_STAT(12, __popcll(above));
-#ifndef AT3_EMU_HOST
-                    if (p.clk && lane == 0) {
-                        atomicAdd(p.clk + 13, (unsigned long long)__popc(inexact));
-                        if (above) atomicAdd(p.clk + 14, (unsigned long long)__popcll(above));
-                    }
-#endif
 #endif
                     if (lane < 32 && ((inexact >> lane) & 1u)) valid |= 1u << bits;
                     rsum = row_allreduce_add(clc_i | ((bits ? (uint32_t)s_cost[cost_at] : 0u) << 13));
                     acc = (uint32_t)__builtin_amdgcn_readlane((int)rsum, 0) + (uint32_t)__builtin_amdgcn_readlane((int)rsum, 16);
                 }
             }
-            AT3_LPH(pc, 7);
             if (hit || memo_n < 64) {
                 rec_lane = hit ? hit_k : memo_n;
                 if (lane == rec_lane) {
@@ -1395,7 +1310,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
                     }
                 }
             }
-            AT3_LPH(pc, 8);
             if (!done) continue;
             final_lam = lam;
             const int last_alloc = (p.bfu_idx_const || num_bfu <= 1) ? 1
@@ -1453,14 +1367,9 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
             }
             break;
         }
-        AT3_LPH(pc, 9);
         if (!restart) break;
     }
     if (!bits_current) bits = (lane < num_bfu) ? alloc_bits(A, gate, tcount, gmap, final_lam) : 0;   // (mode is the last evaluation's)
-    AT3_PH_END(pc, 4);
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug_stop == 3) return;
-#endif
     if (p.quant) {   // the QUANT tap: the units whose bits the cache holds at the end (err e1 / e2, cost CLC | VLC << 13; zero = not computed, or a bound only)
         QuantRec* qr = p.quant + cf;
         if (lane < 32) s_alloc[lane] = (uint8_t)(valid & 0xfeu);
@@ -1560,9 +1469,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
         put_bits(s_words, pos + 5, (uint32_t)mode, 1);
     }
     pos += 6;
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug_stop == 7) return;
-#endif
     const unsigned long long nzmask = __ballot(elane < num_bfu && bits != 0);
     if (elane < num_bfu) put_bits(s_words, pos + 3 * elane, (uint32_t)bits, 3);
     pos += 3 * num_bfu;
@@ -1644,9 +1550,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
         if (fill > 0 && cur < kBitWords) atomicOr(&s_words[cur], (uint32_t)(acc >> 32));
     }
     __syncthreads();
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug_stop == 8) return;
-#endif
 
     // ---- frame assembly (atrac3_bitstream.cpp:826-834): ch0 bytes, then ch1 (byte-reversed when JS) ----
     uint8_t* frame = p.out + ((size_t)s * n_out + fo) * p.frame_sz;
@@ -1665,15 +1568,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_alloc_pack(BackParam
         p.clk[0] = __builtin_amdgcn_s_memtime() - clk_t0;
         p.clk[1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
     }
-#ifdef AT3HIP_DEBUG_KNOBS
-    AT3_PH_END(pc, 10);
-    if (pc.slots && lane == 0) atomicAdd(pc.slots + 11, 1ull);   // wavefronts counted
-    if (p.clk && lane == 0 && blockIdx.x < 16384u) {
-        unsigned long long* it = p.clk + 16 + 2 * 256 * 12 + 2 * blockIdx.x;
-        it[0] = item_r0;
-        it[1] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
 }
 
 }  // namespace at3

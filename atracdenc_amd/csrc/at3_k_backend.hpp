@@ -35,7 +35,6 @@ struct BackParams {
                              // for; err is zero for those AND for units of BFUs >= 10 whose cost the rate loop only ever needed as unit_bounds gives it (exact below
                              // BFU 19, where there is no energy-adaptive pass): compute_units, which forms e1 / e2, never ran for them (include/at3hip.h)
     int flat_literal;        // AT3HIP_OPT_LITERAL_FORMS: every flatness measure by the literal per-line form (test aid; same results)
-    int debug_stop;          // profiling aid (env AT3HIP_DEBUG_STOP, -DAT3HIP_DEBUG_KNOBS builds): stage exits of k_alloc_pack
     unsigned long long* counters;   // [2] at3hip_get_counters: blocks TScaler::Scale would report as "Scale error", values it would report as
                                     // "clipping" (atrac_scale.cpp:150-153, 163-167); added to by k_psy, null = not counted
     int one_channel;         // one input channel (the pipeline runs on (x, x) pairs): only channel 0 is what the reference scales

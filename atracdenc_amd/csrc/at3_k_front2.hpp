@@ -32,14 +32,8 @@ namespace at3 {
 // so one read instruction (fixed group offset) touches consecutive slots in consecutive work-items: conflict free.
 // Inside a group the two floats of a pair are swapped, (x[2k+1], x[2k]): the operand order of the packed tap product.
 constexpr int kHist8 = 48;
-#ifndef K1_PCM_H
-#define K1_PCM_H 74
-#endif
-#ifndef K1_S1_H
-#define K1_S1_H 42
-#endif
-constexpr int kPcmH8 = K1_PCM_H;    // slots per plane, >= 67 and = 2 mod 8 (planes 32 bytes out of phase for the 16-byte stores)
-constexpr int kS1H8 = K1_S1_H;     // >= 35
+constexpr int kPcmH8 = 74;    // slots per plane, >= 67 and = 2 mod 8 (planes 32 bytes out of phase for the 16-byte stores)
+constexpr int kS1H8 = 42;     // >= 35
 constexpr int kPcmRing8 = 16 * kPcmH8;   // floats per channel
 constexpr int kS1Ring8 = 16 * kS1H8;     // floats per (channel, half)
 
@@ -461,12 +455,10 @@ __device__ __forceinline__ f2 rot_pre(f2 a, f2 cs)
 // gain_processor.h:87-121), else 1. `scratch` = the row's kRowScratch4 16-byte slots. Returns the lane's sixteen
 // spectral lines as the four 16-byte stores of mdct_rows_store (odd bands already reversed: see the end of the function).
 // WAVE-UNIFORM: every lane of the wavefront must call (DPP and wave-level rendezvous inside).
-// XORS: the exchange scratch without its spare chunks - quad q's sixteen slots at 16 q, slot index ^ 4 in odd quads (the
-// same bank phase the padded layout gets from its 20-slot stride) - 64 instead of 80 slots per row.
-template <bool XORS>
+// Quad q's sixteen exchange slots start at 20 q (the spare chunk of kRowScratch4 staggers the quads' bank phase).
 __device__ __forceinline__ int xslot(int quad, int idx)
 {
-    return XORS ? 16 * quad + (idx ^ ((quad & 1) << 2)) : 20 * quad + idx;
+    return 20 * quad + idx;
 }
 // The fold of mdct.h:64-86 in its two halves. A frame's FFT inputs are sums and differences of products of the NEW half's samples
 // (A = (r0a, i0b) per q3) and of the windowed OVERLAP (B = (i0a, r0b) per q3): a run that starts in the middle of a stream can form A
@@ -496,10 +488,8 @@ __device__ __forceinline__ void mdct_fold_new(const MdctTab& tab, float (&pw)[4]
         }
     }
 }
-template <bool XORS>
 __device__ __forceinline__ void mdct_row_transform(const MdctTab& tab, const f2 (&tw2)[3], const float (&A)[4][2], const float (&B)[4][2], float4* scratch, int L, float4 (&slots)[4]);
 
-template <bool XORS = false>
 __device__ __forceinline__ void mdct_row_frame(const MdctTab& tab, const f2 (&tw2)[3], float (&pw)[4][4], const float (&X)[4][4], float inv_scale,
                                                float4* scratch, int L, bool emit, float4 (&slots)[4])
 {
@@ -507,11 +497,10 @@ __device__ __forceinline__ void mdct_row_frame(const MdctTab& tab, const f2 (&tw
     if (emit) mdct_fold_old(pw, inv_scale, B);
     mdct_fold_new(tab, pw, X, L, emit, A);
     if (!emit) return;   // priming block: only the overlap is wanted (uniform per wavefront)
-    mdct_row_transform<XORS>(tab, tw2, A, B, scratch, L, slots);
+    mdct_row_transform(tab, tw2, A, B, scratch, L, slots);
 }
 
 // The transform proper: pre-rotation (mdct.h:76-86), the 128-point FFT in the row's sixteen lanes, post-rotation, store order.
-template <bool XORS>
 __device__ __forceinline__ void mdct_row_transform(const MdctTab& tab, const f2 (&tw2)[3], const float (&A)[4][2], const float (&B)[4][2], float4* scratch, int L, float4 (&slots)[4])
 {
     const int q1 = L >> 2, q2 = L & 3;
@@ -533,13 +522,13 @@ __device__ __forceinline__ void mdct_row_transform(const MdctTab& tab, const f2 
     // exchange 1: butterfly k = 2 q2 + kappa of the m = 8 pass takes element k of the four lanes of the quad
     {
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) scratch[xslot<XORS>(q1, 4 * q2 + (jj ^ q2))] = make_float4(z[2 * jj].x, z[2 * jj].y, z[2 * jj + 1].x, z[2 * jj + 1].y);
+        for (int jj = 0; jj < 4; ++jj) scratch[xslot(q1, 4 * q2 + (jj ^ q2))] = make_float4(z[2 * jj].x, z[2 * jj].y, z[2 * jj + 1].x, z[2 * jj + 1].y);
     }
     wave_sync();
     f2 y[2][4];   // [kappa][i]
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float4 v = scratch[xslot<XORS>(q1, 4 * i + (q2 ^ i))];
+        const float4 v = scratch[xslot(q1, 4 * i + (q2 ^ i))];
         y[0][i] = f2lo(v);
         y[1][i] = f2hi(v);
     }
@@ -552,13 +541,13 @@ __device__ __forceinline__ void mdct_row_transform(const MdctTab& tab, const f2 
     // exchange 2: butterfly k = 8 a + 2 q2 + kappa of the m = 32 pass takes (kappa, i = a) of the lanes (i', q2)
     {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) scratch[xslot<XORS>(q2, 4 * q1 + (i ^ q1))] = make_float4(y[0][i].x, y[0][i].y, y[1][i].x, y[1][i].y);
+        for (int i = 0; i < 4; ++i) scratch[xslot(q2, 4 * q1 + (i ^ q1))] = make_float4(y[0][i].x, y[0][i].y, y[1][i].x, y[1][i].y);
     }
     wave_sync();
     f2 u[2][4];   // [kappa][i']
 #pragma unroll
     for (int ip = 0; ip < 4; ++ip) {
-        const float4 v = scratch[xslot<XORS>(q2, 4 * ip + (q1 ^ ip))];
+        const float4 v = scratch[xslot(q2, 4 * ip + (q1 ^ ip))];
         u[0][ip] = f2lo(v);
         u[1][ip] = f2hi(v);
     }
@@ -761,66 +750,22 @@ __global__ __launch_bounds__(64 * NW) void k_mdct_sub(MdctSubParams p, const Tab
 // overlap. The wavefront runs stage 1, stage 2 and the four bands' transforms of a block back to back; its subbands
 // and exchange scratch reuse the rings that are dead at that point (the PCM ring after stage 1, the stage-1 rings after
 // stage 2), 10 KB of LDS per wavefront in all. A workgroup is four independent wavefronts sharing the MDCT table.
-#ifndef K1_ATTR
-#define K1_ATTR
-#endif
-#ifndef K1_NW
-#define K1_NW 4
-#endif
-#ifndef K1_EARLY
-#define K1_EARLY 0
-#endif
-#ifndef K1_XOR
-#define K1_XOR 0
-#endif
-#ifndef K1_FETCH_AT
-#define K1_FETCH_AT 0
-#endif
-#ifndef K1_OPAQUE
-#define K1_OPAQUE (K1_NW > 4)
-#endif
-#if K1_OPAQUE
-#define K1_LANE(l) opaque_lane_value(l)
-#else
-#define K1_LANE(l) (l)
-#endif
-constexpr int kFusedWaves = K1_NW;          // wavefronts per workgroup of the fused kernel (they share the MDCT table)
-constexpr bool kFusedEarlyTile = K1_EARLY;  // the next tile moves into the PCM ring as soon as the subbands were gathered
-constexpr bool kFusedXor = K1_XOR;          // exchange scratch without spare chunks (64 slots per row)
-constexpr int kFusedRowScratch4 = kFusedXor ? 64 : kRowScratch4;
-// Where the exchange scratch of the four rows starts (in floats from the PCM ring's start): behind the block's subbands when
-// it may use the ring's tail, at the stage-1 rings when the next tile moves into the PCM ring before the transform.
-constexpr int kFusedScratchAt = kFusedEarlyTile ? kPcmRing8 : 4 * 264;
+constexpr int kFusedWaves = 4;   // wavefronts per workgroup of the fused kernel (they share the MDCT table)
+constexpr int kFusedScratchAt = 4 * 264;   // where the rows' exchange scratch starts (floats from the PCM ring's start): behind the block's subbands
 static_assert(kPcmRing8 >= 4 * 264, "the block's subbands reuse the PCM ring");
-static_assert((kPcmRing8 + 2 * kS1Ring8 - kFusedScratchAt) * sizeof(float) >= sizeof(float4) * 4 * kFusedRowScratch4, "the exchange scratch reuses the rings");
-#ifdef K1_STAMPS
-#define K1_STAMP(k) do { const unsigned t_ = (unsigned)__builtin_amdgcn_s_memtime(); ph[k] += t_ - t_prev; t_prev = t_; } while (0)
-#else
-#define K1_STAMP(k) do { } while (0)
-#endif
-__global__ __launch_bounds__(64 * kFusedWaves) K1_ATTR void k_qmf_mdct8(FrontParams p, const Tables* T, int n_waves)
+static_assert((kPcmRing8 + 2 * kS1Ring8 - kFusedScratchAt) * sizeof(float) >= sizeof(float4) * 4 * kRowScratch4, "the exchange scratch reuses the rings");
+__global__ __launch_bounds__(64 * kFusedWaves) void k_qmf_mdct8(FrontParams p, const Tables* T, int n_waves)
 {
     constexpr int NW = kFusedWaves;
-#ifdef K1_TAB_GLOBAL
-    const MdctTab& s_tab = *reinterpret_cast<const MdctTab*>(&T->mdct_tab[0][0][0]);
-#else
     __shared__ __attribute__((aligned(16))) MdctTab s_tab;
-#endif
     __shared__ __attribute__((aligned(16))) QmfLdsW s_q[NW];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = (int)__builtin_amdgcn_readfirstlane((unsigned)tid >> 6);   // (uniform: the run's indices, bounds and base addresses live in scalar registers)
     // The shared table is asked for first and stored behind the run's prologue - the wavefront's first PCM requests do not queue up
     // behind a workgroup rendezvous. (A wavefront past the end of the launch runs the last run's prologue, which writes nothing but
     // its own LDS, and leaves after the rendezvous.)
-#ifndef K1_TAB_GLOBAL
     const MdctTabRegs tab_regs = mdct_tab_request<64 * NW>(T, tid);
     __builtin_amdgcn_sched_barrier(0);
-#endif
-#ifdef K1_STAMPS
-    unsigned ph[7] = {0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long t_begin = __builtin_amdgcn_s_memtime(), r_begin = __builtin_amdgcn_s_memrealtime();
-    unsigned t_prev = (unsigned)t_begin;
-#endif
     const int W0 = blockIdx.x * NW + wave;
     const bool live = W0 < n_waves;
     QmfLdsW& S = s_q[wave];
@@ -877,45 +822,27 @@ __global__ __launch_bounds__(64 * kFusedWaves) K1_ATTR void k_qmf_mdct8(FrontPar
     for (int j = 0; j < 3; ++j) tw2[j] = ld2(T->tw128 + 16 * (j + 1));
     float (*sub)[264] = reinterpret_cast<float (*)[264]>(S.pcm);            // [band][256 + pad], after stage 1
     qmf_prologue<false>(S, q, S.pcm + kPrologueTmp, Wp, b0, b_last, lane);
-#ifndef K1_TAB_GLOBAL
     mdct_tab_store<64 * NW>(s_tab, tab_regs, tid);
     __syncthreads();   // the only workgroup-level rendezvous: the shared table
-#endif
     if (!live) return;   // (never in a chained launch: its grid is whole groups)
-    K1_STAMP(0);
-    // Per-lane LDS and HBM offsets are formed again in every block, phase by phase, from a lane index the optimiser cannot see
-    // through (opaque_lane_value): hoisted in front of the loop - where the compiler puts anything loop-invariant - they were
-    // fifty registers held for the whole run, the difference between three and four wavefronts per SIMD.
     const float* frame_base = p.specs + ((size_t)s * n_out * 2 + ch) * 1024;
     for (int blk = b0; blk <= b_last; ++blk) {
-        {
-            const int ln = K1_LANE(lane);
-            if (!kFusedEarlyTile && blk > b0) {
-                // the ring held the previous block's subbands until its transform had gathered them: now the tile
-                // (fetched one block ago) and the FIR histories move in
-                pcm_hist_store(S, q, ln);   // the tail of the previous tile, before tile_store replaces the copy in registers
-                tile_store(S, q, ln);
-            }
-            if (blk > b0) {
-                s1_hist_store(S, q, ln);
-                wave_sync();
-            }
-            if (K1_FETCH_AT == 0 && blk + 1 <= b_last) tile_fetch(q, blk + 1, ln);   // lands during this block's arithmetic
-        }
-        K1_STAMP(1);
-        {
-            const int ln = K1_LANE(lane);
-            qmf_stage1(S, Wp, ln);
+        if (blk > b0) {
+            // the ring held the previous block's subbands until its transform had gathered them: now the tile
+            // (fetched one block ago) and the FIR histories move in
+            pcm_hist_store(S, q, lane);   // the tail of the previous tile, before tile_store replaces the copy in registers
+            tile_store(S, q, lane);
+            s1_hist_store(S, q, lane);
             wave_sync();
-            s1_hist_fetch(S, q, ln);
-            if (K1_FETCH_AT == 1 && blk + 1 <= b_last) tile_fetch(q, blk + 1, ln);   // lands during stage 2
         }
-        K1_STAMP(2);
+        if (blk + 1 <= b_last) tile_fetch(q, blk + 1, lane);   // lands during this block's arithmetic
+        qmf_stage1(S, Wp, lane);
+        wave_sync();
+        s1_hist_fetch(S, q, lane);
         {
-            const int ln = K1_LANE(lane);
-            const int which = ln >> 5, g = ln & 31;
+            const int which = lane >> 5, g = lane & 31;
             float lo[8], up[8];
-            qmf_stage2(S, Wp, ln, lo, up);
+            qmf_stage2(S, Wp, lane, lo, up);
             wave_sync();   // every lane is done with the rings (the exchange scratch and the subbands overwrite them)
             float4* o0 = reinterpret_cast<float4*>(&sub[which ? 3 : 0][8 * g]);
             float4* o1 = reinterpret_cast<float4*>(&sub[which ? 2 : 1][8 * g]);
@@ -925,44 +852,27 @@ __global__ __launch_bounds__(64 * kFusedWaves) K1_ATTR void k_qmf_mdct8(FrontPar
             o1[1] = make_float4(up[4], up[5], up[6], up[7]);
         }
         wave_sync();
-        K1_STAMP(3);
         {
             const int f = blk + 1;
+            const int band = lane >> 4, L = lane & 15;
             float X[4][4];
-            {
-                const int ln = K1_LANE(lane);
-                const int band = ln >> 4, L = ln & 15;
-                const int b = (L >> 2) + 4 * (L & 3);
-                row_gather([&](int i) { return *reinterpret_cast<const f2*>(&sub[band][i]); }, b, X);
-                wave_sync();
-                if (kFusedEarlyTile && blk < b_last) {
-                    // the subbands are in registers: the next tile (requested earlier in this block) and the tail of this one move into the ring
-                    pcm_hist_store(S, q, ln);
-                    tile_store(S, q, ln);
-                }
-            }
-            K1_STAMP(4);
-            const bool emit = blk > b0;
+            row_gather([&](int i) { return *reinterpret_cast<const f2*>(&sub[band][i]); }, (L >> 2) + 4 * (L & 3), X);
+            wave_sync();
             float* frame_ch = const_cast<float*>(frame_base) + (size_t)(f - p.f0) * 2048;
-            if (emit) {
+            if (blk > b0) {
                 float4 slots[4];
-                {
-                    const int ln = K1_LANE(lane);
-                    const int band = ln >> 4, L = ln & 15;
-                    float4* scratch = reinterpret_cast<float4*>(S.pcm + kFusedScratchAt) + band * kFusedRowScratch4;   // after stage 2 (and the gather)
-                    mdct_row_frame<kFusedXor>(s_tab, tw2, pw, X, 1.0f, scratch, L, true, slots);
-                }
-                mdct_rows_store(frame_ch, slots, K1_LANE(lane));
+                float4* scratch = reinterpret_cast<float4*>(S.pcm + kFusedScratchAt) + band * kRowScratch4;   // after stage 2 (and the gather)
+                mdct_row_frame(s_tab, tw2, pw, X, 1.0f, scratch, L, true, slots);
+                mdct_rows_store(frame_ch, slots, lane);
             } else {
                 float A[4][2];
-                mdct_fold_new(s_tab, pw, X, K1_LANE(lane) & 15, deferred, A);
+                mdct_fold_new(s_tab, pw, X, L, deferred, A);
                 if (deferred) {
-                    float4* park = reinterpret_cast<float4*>(frame_ch) + 2 * K1_LANE(lane);
+                    float4* park = reinterpret_cast<float4*>(frame_ch) + 2 * lane;
                     park[0] = make_float4(A[0][0], A[0][1], A[1][0], A[1][1]);
                     park[1] = make_float4(A[2][0], A[2][1], A[3][0], A[3][1]);
                 }
             }
-            K1_STAMP(5);
         }
     }
     if (p.chain) {
@@ -983,39 +893,18 @@ __global__ __launch_bounds__(64 * kFusedWaves) K1_ATTR void k_qmf_mdct8(FrontPar
             const float4* park = reinterpret_cast<const float4*>(frame_ch) + 2 * lane;
             const float4 a0 = park[0], a1 = park[1];
             const float A[4][2] = {{a0.x, a0.y}, {a0.z, a0.w}, {a1.x, a1.y}, {a1.z, a1.w}};
-#ifdef K1_SABOTAGE
-            const float B[4][2] = {{h0.x, h0.y}, {h0.z, h0.w}, {h1.x, h1.y}, {h1.z, 0.0f}};
-#else
             const float B[4][2] = {{h0.x, h0.y}, {h0.z, h0.w}, {h1.x, h1.y}, {h1.z, h1.w}};
-#endif
-            // (the exchange scratch lies behind the hand-over in this wavefront's own rings; the lane's stores below come after its own loads of
-            // the parked half: the compiler keeps that order - they may alias - and a lane only overwrites what it and its mirror lane parked)
+            // (the exchange scratch lies behind the hand-over in this wavefront's own rings.) The stores below overwrite other lanes'
+            // parked halves - band-0 lane L stores floats 4 L + 64 j, which lanes L / 2 + 8 j parked - and are still safe: every park load
+            // of the wavefront completes before any of its stores, which depend on the loaded values.
             float4 slots[4];
             const int band = lane >> 4, L = lane & 15;
-            float4* scratch = reinterpret_cast<float4*>(S.pcm + kFusedScratchAt) + band * kFusedRowScratch4;
+            float4* scratch = reinterpret_cast<float4*>(S.pcm + kFusedScratchAt) + band * kRowScratch4;
             wave_sync();
-            mdct_row_transform<kFusedXor>(s_tab, tw2, A, B, scratch, L, slots);
+            mdct_row_transform(s_tab, tw2, A, B, scratch, L, slots);
             mdct_rows_store(frame_ch, slots, lane);
         }
     }
-    K1_STAMP(6);
-#ifdef K1_STAMPS
-    if (p.clk && lane == 0) {
-        unsigned long long* row = p.clk + 16 + (W0 & 255) * 24;   // (256 rows of 24 words: the space of k_alloc_pack's and k_gain_analysis1's phase rows)
-        for (int k = 0; k < 6; ++k) atomicAdd(row + k, (unsigned long long)ph[k]);
-        atomicAdd(row + 6, __builtin_amdgcn_s_memtime() - t_begin);
-        atomicAdd(row + 7, __builtin_amdgcn_s_memrealtime() - r_begin);
-        atomicAdd(row + 8, 1ull);
-        atomicAdd(row + 9, (unsigned long long)(b_last - b0 + 1));
-        atomicAdd(row + 10, (unsigned long long)ph[6]);
-        // when the row's wavefronts of this launch started and ended (100 MHz): words 12 .. 15 keep max(~first start), max(last start), max(~first end), max(last end)
-        const unsigned long long r_end = __builtin_amdgcn_s_memrealtime();
-        atomicMax(row + 12, ~r_begin);
-        atomicMax(row + 13, r_begin);
-        atomicMax(row + 14, ~r_end);
-        atomicMax(row + 15, r_end);
-    }
-#endif
 }
 
 }  // namespace at3

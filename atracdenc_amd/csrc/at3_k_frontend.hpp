@@ -26,9 +26,7 @@ struct FrontParams {
     int frame_runs;          // fused kernel: runs per (stream, channel) the output frames are cut into
     int js;
     int sub_runs;            // k_qmf_sub8: runs per (stream, channel) the n_blocks + 2 blocks are cut into
-    int debug;               // profiling aid (env AT3HIP_DEBUG_FRONT, debug builds): 3 = skip the energy-scale chains
     int chain;               // fused kernel: runs of one (stream, channel) chained in workgroups (see k_qmf_mdct8), frame_runs a multiple of the workgroup's wavefronts
-    unsigned long long* clk; // profiling builds (-DK1_STAMPS): per-phase cycle sums of the fused kernel's wavefronts (AT3HIP_TAP_CLOCK), else null
 };
 
 // The divisors of the eight samples of cell `cell / 8` under a curve given as its two 8-byte halves (n, level[7] |
@@ -77,11 +75,6 @@ __device__ __forceinline__ void cell_divisors_packed(uint64_t lo, uint64_t hi, c
 // and two over the previous one (its "next overlap" scale, which the reference carries forward as
 // PrevOverlapGainScale). The frame's modulated bands are taken two at a time: all 64 lanes produce the 2 x 5 x 256
 // terms (four samples each), then ten lanes run the ten ordered sums side by side.
-#ifndef GES_SPLIT
-#define GES_SPLIT 1
-#endif
-constexpr int kGesSplit = GES_SPLIT;       // workgroups per frame (1, 2 or 4), each taking 8 / kGesSplit of its bands: the pairs of a workgroup run one after another
-constexpr int kGesBands = 8 / kGesSplit;
 constexpr int kGesRow = 260;   // row stride of the term lists: the ten chain lanes read ten rows at once, in different banks
 __global__ __launch_bounds__(64) void k_gain_energy_scale(FrontParams p, const Tables* T, int n_frames_total)
 {
@@ -93,7 +86,7 @@ __global__ __launch_bounds__(64) void k_gain_energy_scale(FrontParams p, const T
     __shared__ __attribute__((aligned(16))) Curve s_cv[8][2];
     __shared__ float s_gi[32];
     const int lane = threadIdx.x;
-    const int sf = blockIdx.x / kGesSplit, part = blockIdx.x % kGesSplit;   // `part`: which kGesBands bands of the frame's eight (channel-major)
+    const int sf = blockIdx.x;
     if (sf >= n_frames_total) return;
     const int nfr = p.n_blocks - p.f0;
     const int f = p.f0 + sf % nfr;
@@ -101,7 +94,7 @@ __global__ __launch_bounds__(64) void k_gain_energy_scale(FrontParams p, const T
     const int b = f - 1;   // the block this frame's new half comes from
     // lanes 0..7: the band's two curves as 16-byte words; their point lists are later walked from LDS
     uint4 w_cur = {0u, 0u, 0u, 0u}, w_prev = {0u, 0u, 0u, 0u};
-    const bool mine = lane >= part * kGesBands && lane < (part + 1) * kGesBands;   // lane = band index c for the curve loads
+    const bool mine = lane < 8;   // lane = band index c (channel-major) for the curve loads
     if (mine) {
         w_cur = *reinterpret_cast<const uint4*>(p.curves + ((size_t)s * p.n_blocks + f) * 8 + lane);
         w_prev = *reinterpret_cast<const uint4*>((f - 1 < 0) ? &p.state[(size_t)s * 8 + lane].prev_curve
@@ -112,7 +105,7 @@ __global__ __launch_bounds__(64) void k_gain_energy_scale(FrontParams p, const T
     const uint32_t active = (uint32_t)__ballot(mine && (((w_cur.x | w_prev.x) & 0xffu) != 0u));   // Curve::n is the first byte
     float* out8 = p.ges + ((size_t)s * p.n_blocks + f) * 8;
     if (mine && !((active >> lane) & 1u)) out8[lane] = 1.0f;   // no modulation on either side: every ratio is exactly 1
-    if (active == 0u || p.debug == 3) return;
+    if (active == 0u) return;
     // (most frames leave above: the tables are fetched only by those that modulate something)
     if (lane < 32) s_gi[lane] = T->gain_interp[lane < 31 ? lane : 30];
     const float4 wn4 = *reinterpret_cast<const float4*>(T->enc_win + 4 * lane);         // EncodeWindow[i], i = 4 lane + k

@@ -26,9 +26,7 @@ struct GainParams {
     int f0;
     int js;
     int n_streams;
-    int debug;   // profiling aid (env AT3HIP_DEBUG_GAIN): k_gain_curve returns early at stage N
     int literal; // AT3HIP_OPT_LITERAL_FORMS: k_gain_spec's energy sums as the reference's two 257-term chains for every item
-    unsigned long long* clk;   // profiling builds: 256 rows of 12 per-phase cycle counters of k_gain_analysis1 (tools/gain_phase_cycles.sh)
 };
 
 constexpr int kLowCutBin = 38;  // ceil(800 * 512 / 11025)
@@ -324,9 +322,6 @@ __global__ __launch_bounds__(64) void k_gain_spec(GainParams p, const Tables* T,
 #pragma unroll
     for (int q = 0; q < 15; ++q) tw_l[q] = ld2(&T->spec16_tw[q][L]);
     __builtin_amdgcn_sched_barrier(0);
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug == 21) return;
-#endif
     // passes m = 1 (all twiddles tw[0]) and m = 4 (butterfly k: tw[16 k], tw[32 k], tw[48 k], the same in every lane)
     {
         const f2 w0 = ld2(&T->tw256[0]);
@@ -360,9 +355,6 @@ __global__ __launch_bounds__(64) void k_gain_spec(GainParams p, const Tables* T,
         for (int j = 0; j < 4; ++j) bfly4<false>(b[4 * j], b[4 * j + 1], b[4 * j + 2], b[4 * j + 3], tw_l[3 + 3 * j], tw_l[4 + 3 * j], tw_l[5 + 3 * j]);
     }
     // now b[q + 4 j] = F[L + 16 (j + 4 q)]: F[L + 16 jj] = b[(jj >> 2) + 4 (jj & 3)]
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug == 22) return;
-#endif
     // 2. kiss_fftr post-processing -> 257 bins: this lane's k = L + 16 jj, jj = 0..7, each with its partner 256 - k, whose F
     // is element 15 - jj of lane (16 - L) % 16 - for L = 0 element 16 - jj of the lane itself
     f2 fa[8], fb[8];   // freq[k], freq[256 - k]
@@ -418,9 +410,6 @@ __global__ __launch_bounds__(64) void k_gain_spec(GainParams p, const Tables* T,
         }
         if (L == 0) st2(&bins[128 - kLowCutBin], f128);
     }
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug == 23) return;
-#endif
     // highFreqRatio (transient_spectral_upsampler.cpp:99-118): two ordered f64 sums over the 257 bin energies, the second
     // one weighted with the squared high-pass response (0 below bin 38, 1 from bin 40 on), and the f32 of their quotient.
     //
@@ -491,9 +480,6 @@ __global__ __launch_bounds__(64) void k_gain_spec(GainParams p, const Tables* T,
         for (int k = 257 + L; k < 304; k += 16) S.e[k] = 0.0;
     }
     wave_sync();
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug == 24) return;
-#endif
     double acc = 0.0;
     if (lane < 8) {
         const int it = lane >> 1, kind = lane & 1;
@@ -551,9 +537,6 @@ __global__ __launch_bounds__(128) void k_gain_analysis(GainParams p, const Table
     GainRec* rec = p.rec + (((size_t)s * p.n_blocks + f) * 2 + ch) * 3 + band;
     // below 5 % high-band energy the reference drops the band before the upsampler output is looked at
     // (atrac3denc.cpp:319-327): nothing downstream reads the other fields of such a record
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug == 11) return;   // launch cost alone
-#endif
     // Loads return in issue order. The item's gate goes first and the bins and input twiddles right behind it, in the same round
     // trip: a workgroup that passes the gate (they all do on busy material) has its leaves' inputs arriving while it tests the
     // ratio, one that fails leaves after the one latency it always paid. The 27 twiddles of the later passes are requested after
@@ -572,13 +555,6 @@ __global__ __launch_bounds__(128) void k_gain_analysis(GainParams p, const Table
     const Tw32_128 tw_b = irfft_tw_32_128(T->gain_tw, tid);
     const Tw512<128> tw_c = irfft_tw_512<128>(T->gain_tw, tid);
     __builtin_amdgcn_sched_barrier(0);
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug == 12) {   // launch + the fetches
-        float sink = bin0.r + bin1.i + stw_in0.r + stw_in1.i + hpf1 + hpf2 + tw_b.a[0].x + tw_b.w[3][2].y + tw_c.w[0][0].x + tw_c.w[3][2].y;
-        if (sink == 12345.678f) rec->target = sink;
-        return;
-    }
-#endif
     // 3. kiss_fftri input. Only bins 38..256 survive the high-pass, so tmpbuf is non-zero at k in [38,256] and
     //    [1792,2010]; each of those meets an exact zero in its radix-2 leaf butterfly (x +- 0*w), whose two outputs
     //    are therefore stored directly.
@@ -619,28 +595,16 @@ __global__ __launch_bounds__(128) void k_gain_analysis(GainParams p, const Table
     }
     __syncthreads();
     // inverse transform: 128 radix-16 units per pass pair, one per work-item
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug == 13) return;
-#endif
 
     if (wave == 0) irfft_pass_2_8<0>(L.f, T->tw2048, lane);
     else irfft_pass_2_8<1>(L.f, T->tw2048, lane);
     __syncthreads();
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug == 14) return;
-#endif
 
     irfft_pass_32_128(L.f, tw_b, tid);
     __syncthreads();
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug == 15) return;
-#endif
 
     irfft_pass_512<128>(L.f, tw_c, tid);
     __syncthreads();
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (p.debug == 16) return;
-#endif
 
 
     // 4. AnalyzeGain over the upsampled samples [1024, 3072): 256 micro-chunks of 8 (4 per lane), 32 sub-frames of 64
@@ -702,17 +666,6 @@ __global__ __launch_bounds__(128) void k_gain_analysis(GainParams p, const Table
         rec->hi[lane] = m[6];
     }
 }
-
-#ifdef AT3HIP_DEBUG_KNOBS
-#define AT3_GPH_END(k)                                                                   \
-    do {                                                                                 \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();                      \
-        if (ph_slots && threadIdx.x == 0) atomicAdd(ph_slots + (k), t_ - ph_last);       \
-        ph_last = t_;                                                                    \
-    } while (0)
-#else
-#define AT3_GPH_END(k) ((void)0)
-#endif
 
 // ---- the same second half as ONE wavefront per item (round 4) ---------------------------------------------------------
 // The 2048-point inverse core lives in the registers of the 64 lanes, 32 points per lane; what the passes exchange crosses
@@ -778,15 +731,10 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_gain_analysis1(GainP
     const int s = wg / nfr;
     GainRec* rec = p.rec + (((size_t)s * p.n_blocks + f) * 2 + ch) * 3 + band;
     // below 5 % high-band energy the reference drops the band before the upsampler output is looked at (atrac3denc.cpp:319-327)
-#ifdef AT3HIP_DEBUG_KNOBS
-    unsigned long long ph_last = __builtin_amdgcn_s_memtime();
-    unsigned long long* ph_slots = p.clk ? p.clk + (blockIdx.x & 255u) * 12u : nullptr;
-#endif
     const float hfr = rec->hfr;
     if (hfr < 0.05f) return;
     const cpx* bins = p.bins + item * kGainBins;
     const cpx* tw = T->tw2048;
-    AT3_GPH_END(0);
 
     // Every table value a wavefront needs is requested one stage AHEAD of its use (a stage computes for a few thousand cycles,
     // a fetch that is asked for where it is needed costs the wavefront about as much again: with four wavefronts per SIMD in the
@@ -857,7 +805,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_gain_analysis1(GainP
         }
         if (lane == 0) la256 = leaf(b256, s256, 256, false);
     }
-    AT3_GPH_END(1);
     // the units' results after passes m = 32 / 128, element i of unit u at y[u][i]
     f2 y[2][16];
     f2 twc[2][4][3];   // pass m = 512: tw[(q + 1) kk] of butterfly kk = 2 j + u + 32 (4 R + t), 512 contiguous bytes per fetch
@@ -878,7 +825,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_gain_analysis1(GainP
         for (int g = 1; g < 4; ++g) bfly4_inv_sparse<true>(x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3], a1[kappa], a3[kappa]);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) bfly4<true>(x[jj], x[jj + 4], x[jj + 8], x[jj + 12], w8[kappa][jj][0], w8[kappa][jj][1], w8[kappa][jj][2]);
-        AT3_GPH_END(2);
         // exchange 1: x[i'] is slot 32 G + kappa + 2 i'; unit (G2 = R, k = 2 jk + kappa) of the next passes wants offset k of blocks 16 R + i
         cpx* row = L.x + R * kGa1RowSlots;
 #pragma unroll
@@ -895,7 +841,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_gain_analysis1(GainP
             }
         }
         wave_sync();   // (the buffer takes the other parity next, then the outputs)
-        AT3_GPH_END(3);
         // passes m = 32 (fstride 16, butterfly k) and m = 128 (fstride 4, butterflies k + 32 jj) of unit (R, k = 2 j + kappa)
 #pragma unroll
         for (int g = 0; g < 4; ++g) bfly4<true>(b[4 * g], b[4 * g + 1], b[4 * g + 2], b[4 * g + 3], twb[0], twb[1], twb[2]);
@@ -917,7 +862,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_gain_analysis1(GainP
                     for (int q = 0; q < 3; ++q) twc[u][t][q] = ld2(&T->ga1_twc[4 * u + t][q][lane]);
         }
         AT3_STAGE();
-        AT3_GPH_END(4);
     }
     // ---- exchange 2: y[u][i] is slot 512 R + (2 j + u) + 32 i; butterfly kk = 2 j + u + 32 i of pass m = 512 wants it from every row.
     // Rows R and R ^ 2 trade their halves i >= 8 / i < 8, then rows R and R ^ 1 the quarters: afterwards y[u][4 q + t] is
@@ -933,7 +877,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_gain_analysis1(GainP
             swap_f2<false>(y[u][t], y[u][4 + t]);
             swap_f2<false>(y[u][8 + t], y[u][12 + t]);
         }
-    AT3_GPH_END(5);
     // ---- pass m = 512 (fstride 1) and exchange 3: only the middle half of the upsampled frame is analysed (outputs kk + 512, kk + 1024)
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -945,7 +888,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_gain_analysis1(GainP
             st2(L.out + kGa1SubStride * (16 + i) + 2 * j + u, y[u][8 + t]);   // slot 1024 + kk: sub-frame 16 + i
         }
     wave_sync();
-    AT3_GPH_END(6);
     // ---- AnalyzeGain over the upsampled samples [1024, 3072) (transient_detector.cpp:95-136): 256 micro-chunks of 8 samples (four
     // per lane), 32 sub-frames of 64; complex output jj holds the real samples 2 jj, 2 jj + 1
     const float norm = 1.0f / 4096.0f;
@@ -968,7 +910,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_gain_analysis1(GainP
         L.micro[c] = sqrtf(acc);
     }
     wave_sync();
-    AT3_GPH_END(7);
     if (lane < 32) {
         const cpx* src = L.out + kGa1SubStride * lane;
         f2 x[32];
@@ -1000,10 +941,6 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_gain_analysis1(GainP
         rec->lo[sf] = m[2];
         rec->hi[sf] = m[6];
     }
-#ifdef AT3HIP_DEBUG_KNOBS
-    AT3_GPH_END(8);
-    if (ph_slots && lane == 0) atomicAdd(ph_slots + 11, 1ull);
-#endif
 }
 
 // CalcCurve's target for one item: the plateau target (transient_detector.cpp:178-238, 284-297), the mean gain (the quartiles
@@ -1349,7 +1286,6 @@ __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* 
 
     // ---- CalcCurve (transient_detector.cpp:299-482) ----
     const bool active = valid && !(hfr < 0.05f) && !(target < 1e-6f) && !(savedLastLevel < 1e-6f);
-    if (p.debug == 1) return;
     // An item without curve points after CalcCurve ends as "no_curve" whatever the later stages say
     // (atrac3denc.cpp:395-400), and most items are like that: a wavefront whose two items are both out stops here.
     if (__ballot(active) == 0ull) {
@@ -1504,7 +1440,6 @@ __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* 
         pts.loc[i] = (i < pts.n) ? s_tloc[grp][i] : 0;
     }
     const bool have = pts.n > 0;   // else "skip: no_curve" (atrac3denc.cpp:395-400)
-    if (p.debug == 2) return;
     if (__ballot(have) == 0ull) {
         if (valid && j == 0) {
             Curve out;
@@ -1576,12 +1511,14 @@ __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* 
             changed = true;
         }
     }
-    if (p.debug == 3) return;
     // both scores are evaluated unconditionally (wave-uniform control flow) and TOGETHER; used only when `changed`
     float scoreBefore, scoreAfter;
     early_mismatch_score_pair(L2, gi, in_j, in_next, target, before, pts, s_tmp[grp], s_pts[grp], s_filt[grp], reinterpret_cast<float*>(s_tloc[grp]),
                               reinterpret_cast<float*>(s_tdelta[grp]), s_pts2[grp], j, scoreBefore, scoreAfter);
-    if (p.debug == 5) { if (scoreBefore + scoreAfter == 12345.0f) *dst = Curve(); return; }
+    // (both scores are complete here: left free, the compiler interleaves the scoring with the decision below, and the kernel
+    // needs 231 VGPRs - two wavefronts per SIMD instead of five)
+    scoreBefore = __uint_as_float((uint32_t)opaque_lane_value((int)__float_as_uint(scoreBefore)));
+    scoreAfter = __uint_as_float((uint32_t)opaque_lane_value((int)__float_as_uint(scoreAfter)));
     if (changed) {
         bool keepByBoundary = false;
         if (p0ok) {

@@ -37,13 +37,8 @@ struct DevBuf {
 
 }  // namespace
 
-// AT3HIP_TAP_CLOCK: 16 header words, 2 x 256 rows of 12 per-phase cycle sums (k_alloc_pack, k_gain_analysis1), then, in profiling
-// builds, the entry and exit times (100 MHz) of k_alloc_pack's first 16384 workgroups
-#ifdef AT3HIP_DEBUG_KNOBS
-constexpr size_t kClkWords = 16 + 2 * 256 * 12 + 2 * 16384 + 12 * 16384;   // (... and their own per-phase cycles)
-#else
-constexpr size_t kClkWords = 16;   // release builds write words 0 and 1 only (the phase rows exist in profiling builds)
-#endif
+// AT3HIP_TAP_CLOCK: 16 words, of which k_alloc_pack writes words 0 and 1
+constexpr size_t kClkWords = 16;
 struct at3hip_ctx {
     at3hip_config cfg;
     int frame_sz = 0;
@@ -104,9 +99,6 @@ struct at3hip_ctx {
     size_t lds_per_cu = 0;     // hipDeviceProp_t::maxSharedMemoryPerMultiProcessor; the whole-round LDS padding below is tuned for 160 KB
     int wgs_per_cu = 3;        // resident workgroups per CU of the QMF kernel this context uses (k_qmf_sub8 or the fused one)
     int wgs_per_cu_mdct = 3;   // the same of k_mdct_sub
-    int alloc_lds_pad = 0;     // dynamic LDS added to k_alloc_pack's launch: sets how many of its workgroups share a CU
-    int dbg_pad[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // AT3HIP_DEBUG_KNOBS builds: dynamic LDS added to other launches (AT3HIP_PAD_*), co-residency experiments
-    int dbg_front = 0, dbg_gain = 0, dbg_stop = 0;   // AT3HIP_DEBUG_* (profiling aids), honoured by -DAT3HIP_DEBUG_KNOBS builds only
 
     Tables* d_tables = nullptr;
     float* d_pcm_in = nullptr;       // one-channel contexts: the samples as (x, x) pairs [S][max_blocks][1024][2]
@@ -299,7 +291,7 @@ size_t analysis_lds_pad(const at3hip_ctx* c, long long n_wgs)
     // k_alloc_pack wavefront, and the step was 0.8 % slower for every CU carrying that lodger - tools/ab_step.sh, --gain-wgs)
     // Since k_mdct_sub's workgroups are three wavefronts (20.3 KB) the fat slot is 22.5 KB, SEVEN per CU: what counts is that the slot ONE retiring
     // analysis workgroup frees takes a workgroup of the light stage - with mdct at 25.5 KB that needed the 26 KB slots of six per CU (a 2 KB larger
-    // mdct block cost the step 5 %: AT3HIP_PAD_MDCT, EXPERIMENTS round 5), now seven fit the same launches (+1.2 % on the step, `tones` +2 %;
+    // mdct block cost the step 5 %: EXPERIMENTS round 5), now seven fit the same launches (+1.2 % on the step, `tones` +2 %;
     // 23.3 KB slots, which leave under 1 KB of the CU, lose 7 %). The choice is still scored as the six-per-CU one it replaces.
     static const LdsChoice kChoice[3] = {{9, 0}, {8, 3328}, {6, 5632}};
     return whole_rounds_pad(c, n_wgs, kChoice, 3, true);   // (equally whole rounds: the fewer, fatter slots measured better)
@@ -378,17 +370,6 @@ int at3hip_create(const at3hip_config* cfg, at3hip_ctx** out)
     };
     at3host::DeviceGuard guard(c->device);
     if (guard.error() != hipSuccess) return bail(AT3HIP_EDEVICE);
-#ifdef AT3HIP_DEBUG_KNOBS
-    if (const char* e = getenv("AT3HIP_DEBUG_FRONT")) c->dbg_front = atoi(e);
-    {
-        static const char* const kPadEnv[8] = {"AT3HIP_PAD_QMF", "AT3HIP_PAD_MDCT", "AT3HIP_PAD_CURVE", "AT3HIP_PAD_GES", "AT3HIP_PAD_TAIL", "AT3HIP_PAD_LOUD", "AT3HIP_PAD_PSY", "AT3HIP_PAD_SCAN"};
-        for (int i = 0; i < 8; ++i)
-            if (const char* e = getenv(kPadEnv[i])) c->dbg_pad[i] = atoi(e);
-    }
-    if (const char* e = getenv("AT3HIP_DEBUG_GAIN")) c->dbg_gain = atoi(e);
-    if (const char* e = getenv("AT3HIP_DEBUG_STOP")) c->dbg_stop = atoi(e);
-    if (const char* e = getenv("AT3HIP_ALLOC_PAD")) c->alloc_lds_pad = atoi(e);
-#endif
     {
         // The back half's stream gets the higher priority: its rate loop is the longest kernel of a call and fills every CU's
         // LDS, so a front-half workgroup placed between two of its rounds only delays it, while the front-half kernels of the
@@ -475,7 +456,7 @@ int at3hip_create(const at3hip_config* cfg, at3hip_ctx** out)
     if ((rc = dev_alloc(c, &c->d_loud_state, S)) != AT3HIP_OK) return bail(rc);
     if ((rc = dev_alloc(c, &c->d_out, S * B * (size_t)c->frame_sz)) != AT3HIP_OK) return bail(rc);
     if ((rc = dev_alloc(c, &c->d_clk, kClkWords)) != AT3HIP_OK) return bail(rc);
-    if (hipMemsetAsync(c->d_clk, 0, (kClkWords) * sizeof(unsigned long long), c->stream) != hipSuccess) return bail(AT3HIP_EDEVICE);   // (reset_state below waits for the stream)
+    if (hipMemsetAsync(c->d_clk, 0, kClkWords * sizeof(unsigned long long), c->stream) != hipSuccess) return bail(AT3HIP_EDEVICE);   // (reset_state below waits for the stream)
     if ((rc = dev_alloc(c, &c->d_counters, 2)) != AT3HIP_OK) return bail(rc);   // (zeroed by reset_state)
     if ((rc = reset_state(c)) != AT3HIP_OK) return bail(rc);
     hipDeviceProp_t prop;
@@ -821,7 +802,7 @@ int encode_impl(at3hip_ctx* c, const void* pcm_any, bool s16, int32_t n_blocks, 
         fp.js = c->js;
         fp.sub_runs = pick_runs(c, n_blocks, c->wgs_per_cu, 0.35, 4);
         const int n_waves = S * 2 * fp.sub_runs;
-        hipLaunchKernelGGL(k_qmf_sub8, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), (size_t)c->dbg_pad[0], st, fp, c->d_tables, n_waves);
+        hipLaunchKernelGGL(k_qmf_sub8, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, st, fp, c->d_tables, n_waves);
     }
     if (n_out > 0) {
         FrontParams fp;
@@ -842,13 +823,11 @@ int encode_impl(at3hip_ctx* c, const void* pcm_any, bool s16, int32_t n_blocks, 
             fp.chain = cut.chain;
         }
         fp.sub_runs = 0;
-        fp.debug = c->dbg_front;
-        fp.clk = nullptr;
         fp.js = c->js;
         auto launch_qmf_sub = [&] {
             fp.sub_runs = pick_runs(c, n_blocks, c->wgs_per_cu, 0.35, 4);
             const int n_waves = S * 2 * fp.sub_runs;   // one wavefront per (stream, channel, run)
-            hipLaunchKernelGGL(k_qmf_sub8, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), (size_t)c->dbg_pad[0], st, fp, c->d_tables, n_waves);
+            hipLaunchKernelGGL(k_qmf_sub8, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, st, fp, c->d_tables, n_waves);
         };
         if (gain) {
             GainParams gp;
@@ -861,9 +840,7 @@ int encode_impl(at3hip_ctx* c, const void* pcm_any, bool s16, int32_t n_blocks, 
             gp.f0 = f0;
             gp.js = c->js;
             gp.n_streams = S;
-            gp.debug = c->dbg_gain;
             gp.literal = c->flat_literal;
-            gp.clk = c->d_clk + 16 + 256 * 12;
             launch_qmf_sub();
             if (timed) HIPCHK(c, hipEventRecord(ev[1], st));
             // PCM history and subband tail: the next call's heavy stage needs nothing else from this one. (Round 6: moved behind the gain analysis - off the
@@ -881,10 +858,10 @@ int encode_impl(at3hip_ctx* c, const void* pcm_any, bool s16, int32_t n_blocks, 
             if (timed) HIPCHK(c, hipEventRecord(ev[2], st));
             HIPCHK(c, hipEventRecord(c->ev_heavy_done[slot], st));
             HIPCHK(c, hipStreamWaitEvent(md, c->ev_heavy_done[slot], 0));   // the light stage starts when this call's heavy stage is done
-            hipLaunchKernelGGL(k_gain_tail, dim3((unsigned)((S * n_out * 6 + 7) / 8)), dim3(256), (size_t)c->dbg_pad[4], md, gp, S * n_out * 6);
-            hipLaunchKernelGGL(k_gain_scan, dim3(S * 6), dim3(64), (size_t)c->dbg_pad[7], md, gp, S);
-            hipLaunchKernelGGL(k_gain_curve, dim3((S * n_out * 6 + 7) / 8), dim3(256), (size_t)c->dbg_pad[2], md, gp, c->d_tables, S);
-            hipLaunchKernelGGL(k_gain_energy_scale, dim3(S * n_out * kGesSplit), dim3(64), (size_t)c->dbg_pad[3], md, fp, c->d_tables, S * n_out);
+            hipLaunchKernelGGL(k_gain_tail, dim3((unsigned)((S * n_out * 6 + 7) / 8)), dim3(256), 0, md, gp, S * n_out * 6);
+            hipLaunchKernelGGL(k_gain_scan, dim3(S * 6), dim3(64), 0, md, gp, S);
+            hipLaunchKernelGGL(k_gain_curve, dim3((S * n_out * 6 + 7) / 8), dim3(256), 0, md, gp, c->d_tables, S);
+            hipLaunchKernelGGL(k_gain_energy_scale, dim3(S * n_out), dim3(64), 0, md, fp, c->d_tables, S * n_out);
         } else {
             if (split) launch_qmf_sub();   // joint stereo without gain control: the QMF kernel, timed as qmf_ms
             if (timed) HIPCHK(c, hipEventRecord(ev[1], st));
@@ -908,10 +885,10 @@ int encode_impl(at3hip_ctx* c, const void* pcm_any, bool s16, int32_t n_blocks, 
             const bool fat_slots = c->gain_form != AT3HIP_GAIN_FORM_ONE_WAVE && analysis_lds_pad(c, (long long)S * n_out * 6) != 0;   // (the one-wavefront form's launch has no fat slots)
             if (fat_slots) {
                 if (c->js) hipLaunchKernelGGL((k_mdct_sub<true, 3>), dim3((unsigned)((mp.n_waves + 2) / 3)), dim3(192), 0, md, mp, c->d_tables);
-                else hipLaunchKernelGGL((k_mdct_sub<false, 3>), dim3((unsigned)((mp.n_waves + 2) / 3)), dim3(192), (size_t)c->dbg_pad[1], md, mp, c->d_tables);
+                else hipLaunchKernelGGL((k_mdct_sub<false, 3>), dim3((unsigned)((mp.n_waves + 2) / 3)), dim3(192), 0, md, mp, c->d_tables);
             } else {
                 if (c->js) hipLaunchKernelGGL((k_mdct_sub<true, 4>), dim3((unsigned)((mp.n_waves + 3) / 4)), dim3(256), 0, md, mp, c->d_tables);
-                else hipLaunchKernelGGL((k_mdct_sub<false, 4>), dim3((unsigned)((mp.n_waves + 3) / 4)), dim3(256), (size_t)c->dbg_pad[1], md, mp, c->d_tables);
+                else hipLaunchKernelGGL((k_mdct_sub<false, 4>), dim3((unsigned)((mp.n_waves + 3) / 4)), dim3(256), 0, md, mp, c->d_tables);
             }
         } else {
             const int n_waves = S * 2 * fp.frame_runs;
@@ -940,7 +917,7 @@ int encode_impl(at3hip_ctx* c, const void* pcm_any, bool s16, int32_t n_blocks, 
         // (Round 6, each an 8 - 11 % LOSS on the step although it shortens a chain: the loudness sums and k_psy queued behind the MDCT on the light stage's stream
         // (no event hop between the streams in front of them); k_gain_energy_scale on this stream beside the MDCT; TrackLoudness inside k_psy (no k_loudness
         // launch); k_loud_sum in 22 KB blocks that fit a slot one retiring analysis workgroup frees. EXPERIMENTS.md: the step's schedule is one of several
-        // stable ones, tools/event_timeline.py shows which.)
+        // stable ones.)
         HIPCHK(c, hipStreamWaitEvent(bk, c->ev_mdct_done[slot], 0));
         if (timed) HIPCHK(c, hipEventRecord(ev[5], bk));
         BackParams bp;
@@ -960,16 +937,15 @@ int encode_impl(at3hip_ctx* c, const void* pcm_any, bool s16, int32_t n_blocks, 
         bp.bfu_idx_const = c->cfg.bfu_idx_const;
         bp.mono_js = (c->cfg.channels == 1 && c->js) ? 1 : 0;
         bp.flat_literal = c->flat_literal;
-        bp.debug_stop = c->dbg_stop;
         bp.quant = c->d_quant;
         bp.clk = c->d_clk;
         bp.counters = c->d_counters;
         bp.one_channel = c->cfg.channels == 1 ? 1 : 0;
-        hipLaunchKernelGGL(k_loud_sum, dim3((unsigned)((S * n_out * 2 + kLoudCf - 1) / kLoudCf)), dim3(256), (size_t)c->dbg_pad[5], bk, bp, c->d_tables, S * n_out * 2);
-        hipLaunchKernelGGL(k_psy, dim3((S * n_out * 2 + kPsyCf - 1) / kPsyCf), dim3(256), (size_t)c->dbg_pad[6], bk, bp, c->d_tables, S * n_out * 2);
+        hipLaunchKernelGGL(k_loud_sum, dim3((unsigned)((S * n_out * 2 + kLoudCf - 1) / kLoudCf)), dim3(256), 0, bk, bp, c->d_tables, S * n_out * 2);
+        hipLaunchKernelGGL(k_psy, dim3((S * n_out * 2 + kPsyCf - 1) / kPsyCf), dim3(256), 0, bk, bp, c->d_tables, S * n_out * 2);
         if (timed) HIPCHK(c, hipEventRecord(ev[6], bk));
         hipLaunchKernelGGL(k_loudness, dim3(S), dim3(64), 0, bk, bp);
-        hipLaunchKernelGGL(k_alloc_pack, dim3(S * n_out * 2), dim3(64), (size_t)c->alloc_lds_pad, bk, bp, c->d_tables);
+        hipLaunchKernelGGL(k_alloc_pack, dim3(S * n_out * 2), dim3(64), 0, bk, bp, c->d_tables);
         if (timed) HIPCHK(c, hipEventRecord(ev[7], bk));
         if (!(flags & AT3HIP_OUT_ON_DEVICE))
             HIPCHK(c, hipMemcpyAsync(out_frames, c->d_out, (size_t)S * n_out * c->frame_sz, hipMemcpyDeviceToHost, bk));
@@ -1039,7 +1015,7 @@ int at3hip_read_tap(at3hip_ctx* c, int32_t kind, void* dst, size_t bytes)
         case AT3HIP_TAP_LOUDNESS: src = c->d_loud; cap = S * B * sizeof(float); break;
         case AT3HIP_TAP_QUANT: src = c->d_quant; cap = c->d_quant ? S * B * 2 * sizeof(QuantRec) : 0; break;
         case AT3HIP_TAP_GAIN_ANALYSIS: src = c->d_rec_b[par]; cap = c->d_rec_b[par] ? S * B * 6 * sizeof(GainRec) : 0; break;
-        case AT3HIP_TAP_CLOCK: src = c->d_clk; cap = (kClkWords) * sizeof(unsigned long long); break;   // (from slot 16 on: 256 rows of per-phase cycles of k_alloc_pack, then of k_gain_analysis1; profiling builds)
+        case AT3HIP_TAP_CLOCK: src = c->d_clk; cap = kClkWords * sizeof(unsigned long long); break;
         default: return fail(c, AT3HIP_EINVAL, "unknown tap");
     }
     if (!src || bytes > cap) return fail(c, AT3HIP_EINVAL, "tap not available or request too large");
@@ -1064,24 +1040,6 @@ int at3hip_get_counters(at3hip_ctx* c, at3hip_counters* out, int32_t reset)
     }
     return AT3HIP_OK;
 }
-
-#if defined(AT3HIP_DEBUG_KNOBS) || defined(AT3HIP_DEBUG_EVENTS)
-// PROFILING BUILDS ONLY (-DAT3HIP_DEBUG_EVENTS: the release kernels + this entry point; not in include/at3hip.h): milliseconds from event `ia` of the call
-// `ago_a` calls back to event `ib` of the call `ago_b` calls back (events 0 .. 7 of a call: before QMF, after QMF, after the gain analysis, after the curves /
-// energy scales, after the MDCT, back half's start, after k_psy, after the rate loop) - the pipelined step's timeline WITHOUT a tracer (tools/event_timeline.py):
-// rocprofv3 serialises what it traces, and this pipeline's schedule does not survive that.
-__attribute__((visibility("default"))) int at3hip_debug_event_ms(at3hip_ctx* c, int32_t ago_a, int32_t ia, int32_t ago_b, int32_t ib, float* ms)
-{
-    if (!c || !ms || ago_a < 0 || ago_b < 0 || ago_a >= at3hip_ctx::kSlots || ago_b >= at3hip_ctx::kSlots || ago_a >= c->enc_calls || ago_b >= c->enc_calls ||
-        ia < 0 || ia > 7 || ib < 0 || ib > 7)
-        return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    const int rc = drain(c);
-    if (rc != AT3HIP_OK) return rc;
-    const int sa = (int)((c->enc_calls - 1 - ago_a) % at3hip_ctx::kSlots), sb = (int)((c->enc_calls - 1 - ago_b) % at3hip_ctx::kSlots);
-    return hipEventElapsedTime(ms, c->ev[sa][ia], c->ev[sb][ib]) == hipSuccess ? AT3HIP_OK : AT3HIP_EDEVICE;
-}
-#endif
 
 int at3hip_get_timings_ago(at3hip_ctx* c, int32_t ago, at3hip_timings* out)
 {
@@ -1257,14 +1215,6 @@ int at3hip_qmf_mdct(at3hip_ctx* c, const float* pcm, int32_t n_blocks, float* sp
     fp.ges = nullptr;
     fp.sub = nullptr;
     fp.sub_runs = 0;
-    fp.debug = 0;
-#ifdef K1_STAMPS
-    fp.clk = c->d_clk;
-    for (int r = 0; r < 256; r += 64)   // (the launch's own first / last starts and ends: words 12 .. 15 of every row)
-        HIPCHK(c, hipMemset2DAsync(c->d_clk + 16 + 12 + r * 24, 24 * sizeof(unsigned long long), 0, 4 * sizeof(unsigned long long), 64, st));
-#else
-    fp.clk = nullptr;
-#endif
     fp.n_blocks = n_blocks;
     fp.f0 = 1;
     const int n_out = n_blocks - 1;
@@ -1314,8 +1264,8 @@ int at3hip_qmf_mdct(at3hip_ctx* c, const float* pcm, int32_t n_blocks, float* sp
 
 }  // extern "C"
 
-#if defined(AT3_EMU_HOST) || defined(AT3HIP_DEBUG_KNOBS)
-// TEST AND PROFILING BUILDS ONLY (the SIMT harness, -DAT3HIP_DEBUG_KNOBS; not in include/at3hip.h): the divisors of all 256 samples under n arbitrary
+#ifdef AT3_EMU_HOST
+// SIMT HARNESS BUILDS ONLY (not in include/at3hip.h): the divisors of all 256 samples under n arbitrary
 // curves (16 bytes each: n, level[7], loc[7], pad - any byte values) from the select walk the pipeline's kernels use (cell_divisors_packed) and from the
 // sample-by-sample restatement of TGainProcessor::Modulate (curve_divisor), side by side: tests/test_kernels_simt_harness.py compares the bit patterns.
 namespace {
