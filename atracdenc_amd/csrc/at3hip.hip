@@ -554,8 +554,18 @@ int at3hip_host_alloc(at3hip_ctx* c, size_t bytes, void** out)
 
 int at3hip_device_numa_node(int32_t device_id)
 {
+    // an ordinal the runtime does not know is answered here: a failed runtime call would stay behind as the thread's last
+    // error, which the caller's next kernel launch check (torch's, for one) then reports as its own
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) {
+        (void)hipGetLastError();
+        return -1;
+    }
     char bus[32] = {0};
-    if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), device_id) != hipSuccess || !bus[0]) return -1;
+    if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), device_id) != hipSuccess || !bus[0]) {
+        (void)hipGetLastError();
+        return -1;
+    }
     for (char* q = bus; *q; ++q)
         if (*q >= 'A' && *q <= 'F') *q = (char)(*q - 'A' + 'a');   // sysfs spells the address in lower case
     char path[96];

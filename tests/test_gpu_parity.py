@@ -714,10 +714,11 @@ def test_caller_stream_and_async_pipeline(hip, oracle):
     side = torch.cuda.Stream()
     enc.set_stream(side.cuda_stream)
     host = torch.from_numpy(whole)
-    outs = [torch.zeros((S, nb, enc.frame_size), dtype=torch.uint8, device="cuda") for _ in range(calls)]
     pcms = []
     counts = []
     with torch.cuda.stream(side):
+        # the outputs are zero-filled on the stream the library writes them from: the fills come first
+        outs = [torch.zeros((S, nb, enc.frame_size), dtype=torch.uint8, device="cuda") for _ in range(calls)]
         for k in range(calls):
             # device-side production of the call's PCM on the SAME stream the encoder will read it from
             x = host[:, k * nb:(k + 1) * nb].to("cuda", non_blocking=True)
@@ -1037,3 +1038,9 @@ def test_device_numa_node_query(hip):
     if node >= 0:
         assert os.path.exists(f"/sys/devices/system/node/node{node}/cpulist")
     assert lib.at3hip_device_numa_node(1000) == -1
+    assert lib.at3hip_device_numa_node(-1) == -1
+    # and leaves no runtime error behind for the caller's next launch check (torch's reported it as its own)
+    import torch
+    x = torch.ones(4, device="cuda") * 2
+    torch.cuda.synchronize()
+    assert x.sum().item() == 8
