@@ -21,10 +21,16 @@ Multi-GPU (streams are independent: sharded, no data-path collective, NO RCCL):
     share a start/stop barrier and the MAX of the elapsed time over the CPU-side gloo backend.
 
 The timed work is exactly --steps steps in one region between barrier + synchronize pairs; `ms_per_step` is that region's wall
-time / --steps and `value` the frames/s it gives. --regions R adds R further regions afterwards, reported under `timing` only.
---dump-outputs DIR writes the frames of the last timed step (what a caller of the encode receives) as float32 .npy files.
+time / --steps and `value` the frames/s it gives. --dump-outputs DIR writes the frames of the last timed step (what a caller of
+the encode receives) as float32 .npy files.
 
-One JSON line on rank 0. Extra objects:
+A plain run does only that: set-up, --warmup steps, the timed region, --dump-outputs, and one JSON line with the headline
+fields (a one-process N > 1 run keeps `one_gpu_same_workload`: its steps on device 0 come before the timed region and are part
+of the sequence the timed steps continue). Everything else the benchmark measures or checks runs only with --full, after the
+timed region: --regions R further regions (reported under `timing` only), the checksum, the replay of every context's sequence
+and its oracle check (`parity_in_run`), the roofline and stage figures, and on one GPU the objects below.
+
+One JSON line on rank 0. Extra objects (--full):
   roofline        - the batched QMF + MDCT work (two kernels around the gain analysis: k_qmf_sub8 + k_mdct_sub; one fused kernel
                     without gain control): algorithmic 16384 B/frame x frames per step / its duration measured with HIP
                     events on the ctx stream inside the timed region (where it co-runs with the previous step's back half);
@@ -556,6 +562,28 @@ def dump_outputs(out_dir, jobs, rank, world):
         np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
 
 
+def headline(args, n_gpus, S, F, fsz, mode, ms_per_step):
+    """The fields of the JSON line that a plain run prints: the contract region's rate and what it was measured on."""
+    value = n_gpus * S * F / (ms_per_step * 1e-3)
+    cfgname = {384: "LP2 132 kbps", 192: "LP4 66 kbps joint stereo"}.get(fsz, f"{fsz} B/frame")
+    return {
+        "metric": "ATRAC3 1024-sample stereo frames/sec", "value": round(value, 1), "unit": "frames/s",
+        "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "value_is": "the timed region of exactly --steps steps (barrier + synchronize on both sides, max over ranks)",
+        "x_realtime": round(value * 1024 / 44100.0, 1),
+        "config": {"workload": f"ATRAC3 {cfgname} stereo, {S} streams x {F} frames = {S * F} frames per GPU per step "
+                               f"({'BASELINE configs[1]' if (S, F) == (64, 64) else 'per-GPU shard of BASELINE configs[2]' if (S, F) == (1024, 128) else 'custom'}), "
+                               f"'{args.input}' PCM resident in HBM, frames written to HBM (PCIe excluded)",
+                   "streams_per_gpu": S, "frames_per_stream_per_step": F, "frames_per_step_all_gpus": n_gpus * S * F,
+                   "frame_bytes": fsz, "input": args.input,
+                   "gain_control": not args.no_gain, "tonal_components": True, "parallelism": f"streams/{n_gpus}",
+                   "launch": mode, "collectives": "none (no RCCL); start/stop barrier only"},
+        "per_gpu_value": round(value / n_gpus, 1),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -565,15 +593,18 @@ def main():
     ap.add_argument("--frames", type=int, default=0, help="frames per stream per step (default: 64 at N=1, 128 at N>1)")
     ap.add_argument("--bitrate", type=int, default=LP2)
     ap.add_argument("--input", choices=["noise", "burst", "tones"], default="noise")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-workloads", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed region, everything besides the headline: further regions, "
+                                                        "checksum, replay and oracle check, roofline and stage figures, CPU baseline, "
+                                                        "side workloads, host-fed and widened rows")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-side-workloads", action="store_true", help="(--full) skip other_workloads, host_pipeline* and widened_rows")
     ap.add_argument("--no-gain", action="store_true")
-    ap.add_argument("--regions", type=int, default=0, help="further timed regions after the --steps one: each at least --region-ms long, "
+    ap.add_argument("--regions", type=int, default=0, help="(--full) further timed regions after the --steps one: each at least --region-ms long, "
                                                             "reported under `timing` (median, min, max); value and ms_per_step stay the --steps region's")
     ap.add_argument("--region-ms", type=float, default=50.0)
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the frames of the last timed step to DIR/*.npy (float32, "
                                                                        "at most 64 MB in all; a fixed seeded sample of frames beyond that)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the frames after the timed regions")
+    ap.add_argument("--no-parity", action="store_true", help="(--full) skip the oracle check of the frames after the timed regions")
     ap.add_argument("--runs", type=int, default=0, help="TUNING AID: AT3HIP_OPT_RUNS (runs per stream and channel of the QMF / MDCT kernels)")
     ap.add_argument("--gain-form", type=int, default=0, help="A/B AID: AT3HIP_OPT_GAIN_FORM (0 = the two-wavefront workgroups of the upsampler / "
                                                              "AnalyzeGain kernel, 1 = one wavefront per item; same results)")
@@ -592,6 +623,8 @@ def main():
         name, S, F, br, kind, steps, warmup, no_gain, prior = (json.loads(args.one_side_workload) + [0])[:9]
         print(json.dumps(side_workload(name, S, F, br, kind, steps, warmup, no_gain=bool(no_gain), prior=int(prior))))
         return
+    if args.regions > 0 and not args.full:
+        ap.error("--regions belongs to --full")
 
     import torch
 
@@ -650,7 +683,8 @@ def main():
 
     one_gpu_ref = None
     if world == 1 and n_gpus > 1:
-        # like-for-like reference for the scaling figure: the same per-GPU shard on device 0 ALONE, same step count
+        # like-for-like reference for the scaling figure: the same per-GPU shard on device 0 ALONE, same step count. A plain run
+        # keeps it too: device 0's encoder carries its state across these steps into the timed region, so they decide its frames
         timed_region(jobs[:1], min(args.steps, 5), None)
         dt1 = timed_region(jobs[:1], args.steps, None)
         one_gpu_ref = {"value": round(S * F * args.steps / dt1, 1), "unit": "frames/s", "ms_per_step": round(dt1 / args.steps * 1e3, 4),
@@ -661,6 +695,22 @@ def main():
     elapsed = timed_region(jobs, args.steps, dist)
     _dbg_loud(jobs[0], "contract region")
     elapsed = at3dist.max_over_ranks(elapsed, dist, device="cpu")
+    if not args.full:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, jobs, rank, world)
+        if rank == 0:
+            line = headline(args, n_gpus, S, F, fsz, mode, elapsed / args.steps * 1e3)
+            if args.sync_steps:
+                line["INVALID_profiling_run"] = "--sync-steps: calls were not pipelined; not a throughput measurement"
+            if one_gpu_ref is not None:
+                line["one_gpu_same_workload"] = one_gpu_ref
+            print(json.dumps(line))
+        for j in jobs:
+            j.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     j0 = jobs[0]
     try:
         sclk_contract = j0.enc.sclk_mhz()   # the shader clock under the rate loop of the contract region's last step
@@ -754,7 +804,6 @@ def main():
 
     if rank == 0:
         med_ms = float(np.median(region_ms))
-        value = n_gpus * S * F / (region_ms[0] * 1e-3)
         k1_avg_ms = float(np.mean(k1_ms)) if k1_ms else iso_ms   # (no timed step in the regions: --timing-every 0)
         achieved, frac = roofline_of(k1_avg_ms, S * F)
         ach_iso, frac_iso = roofline_of(iso_ms, S * F)
@@ -841,22 +890,8 @@ def main():
                                                             "workload; not measured in this run)"}
             except Exception:
                 profile_isolated = {}
-        cfgname = {384: "LP2 132 kbps", 192: "LP4 66 kbps joint stereo"}.get(fsz, f"{fsz} B/frame")
-        line = {
-            "metric": "ATRAC3 1024-sample stereo frames/sec", "value": round(value, 1), "unit": "frames/s",
-            "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(region_ms[0], 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "value_is": "the timed region of exactly --steps steps (barrier + synchronize on both sides, max over ranks)",
-            "x_realtime": round(value * 1024 / 44100.0, 1),
-            "config": {"workload": f"ATRAC3 {cfgname} stereo, {S} streams x {F} frames = {S * F} frames per GPU per step "
-                                   f"({'BASELINE configs[1]' if (S, F) == (64, 64) else 'per-GPU shard of BASELINE configs[2]' if (S, F) == (1024, 128) else 'custom'}), "
-                                   f"'{args.input}' PCM resident in HBM, frames written to HBM (PCIe excluded)",
-                       "streams_per_gpu": S, "frames_per_stream_per_step": F, "frames_per_step_all_gpus": n_gpus * S * F,
-                       "frame_bytes": fsz, "input": args.input,
-                       "gain_control": not args.no_gain, "tonal_components": True, "parallelism": f"streams/{n_gpus}",
-                       "launch": mode, "collectives": "none (no RCCL); start/stop barrier only"},
-            "per_gpu_value": round(value / n_gpus, 1),
+        line = headline(args, n_gpus, S, F, fsz, mode, region_ms[0])
+        line.update({
             "roofline": {"bound": "hbm",
                          "kernel": ("k_qmf_sub8 + k_mdct_sub: the batched QMF tree and the windowed MDCT-512 as the two kernels on either side of "
                                     "the gain analysis (which needs every block's subbands before any curve exists); durations summed")
@@ -915,7 +950,7 @@ def main():
                        "value_contract_region": round(n_gpus * S * F / (region_ms[0] * 1e-3), 1),
                        "lone_call": getattr(j0, "lone_call", None)},
             "checksum": checksum,
-        }
+        })
         if parity is not None:
             sums = [c["checksum"] for c in contexts]
             line["parity_in_run"] = bool(len(contexts) == n_gpus and all(c["ok"] for c in contexts) and len(set(sums)) == len(sums))

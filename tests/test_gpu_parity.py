@@ -739,9 +739,10 @@ def test_caller_stream_and_async_pipeline(hip, oracle):
 
 
 def test_bench_contract_and_two_context_paths(tmp_path):
-    """bench.py prints ONE JSON line with the contract's fields (N = 1, a short run), and both multi-device code paths -
-    one process driving two contexts from two host threads, and two torch.distributed.run ranks with a gloo barrier - run
-    to completion on this box's single GPU through the --device-map test aid (their lines say so)."""
+    """bench.py prints ONE JSON line with the contract's fields (N = 1, a short run; the roofline with --full, which a plain
+    run leaves out), and both multi-device code paths - one process driving two contexts from two host threads, and two
+    torch.distributed.run ranks with a gloo barrier - run to completion on this box's single GPU through the --device-map test
+    aid (their lines say so)."""
     import json
     import os
     import subprocess
@@ -756,9 +757,17 @@ def test_bench_contract_and_two_context_paths(tmp_path):
         assert len(lines) == 1, r.stdout[-2000:]
         return json.loads(lines[0])
 
-    d = last_json([sys.executable, bench, "--steps", "4", "--warmup", "1", "--no-side-workloads", "--no-cpu-baseline"])
-    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-                "dtype", "data", "config", "roofline"):
+    contract = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                "dtype", "data", "config")
+    plain = last_json([sys.executable, bench, "--steps", "4", "--warmup", "1"])
+    for key in contract:
+        assert key in plain, key
+    assert plain["n_gpus"] == 1 and plain["steps"] == 4 and plain["warmup"] == 1 and plain["higher_is_better"] is True and plain["value"] > 1e6
+    assert plain["dtype"] == "f32" and "workload" in plain["config"]
+    assert not {"roofline", "checksum", "parity_in_run", "cpu_baseline", "other_workloads"} & set(plain)
+
+    d = last_json([sys.executable, bench, "--full", "--steps", "4", "--warmup", "1", "--no-side-workloads", "--no-cpu-baseline"])
+    for key in contract + ("roofline",):
         assert key in d, key
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["higher_is_better"] is True and d["value"] > 1e6
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(d["roofline"])
@@ -789,7 +798,7 @@ def test_eight_context_readiness(launch):
     bench = os.path.join(root, "bench.py")
     n = 8 if launch == "one_process" else 4
     tail = [bench, "--gpus", str(n), "--device-map", ",".join(["0"] * n), "--steps", "3", "--warmup", "1", "--streams", "64", "--frames", "16",
-            "--regions", "1", "--region-ms", "1", "--no-side-workloads", "--no-cpu-baseline"]
+            "--full", "--regions", "1", "--region-ms", "1", "--no-side-workloads", "--no-cpu-baseline"]
     cmd = [sys.executable] + tail if launch == "one_process" else \
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", "29541"] + tail
     def run_once(port):

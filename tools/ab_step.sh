@@ -4,6 +4,6 @@
 for rep in 1 2 3; do
 for V in "$@"; do
   L=${V%%|*}; F=${V#*|}; [ "$F" = "$V" ] && F=""
-  AT3HIP_LIB=$PWD/$L python bench.py --no-side-workloads --no-cpu-baseline --no-parity --regions 4 $F 2>/dev/null | tail -1 | python -c "
+  AT3HIP_LIB=$PWD/$L python bench.py --full --no-side-workloads --no-cpu-baseline --no-parity --regions 4 $F 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('%-44s %10.0f frames/s  %.4f ms  (min %.4f)' % ('$V'[-44:], d['value'], d['ms_per_step'], d['timing']['ms_per_step_min']))"
 done; done

@@ -14,7 +14,7 @@ for f in glob.glob("/tmp/tl/**/*.db", recursive=True):
     ks = [(n.split('(')[0].replace('at3::','').replace('void ','')[:22], s, e) for n, s, e in rows if 'at3::k_' in n]
     print("kernels in trace:", len(rows), "at3:", len(ks))
     if not ks: continue
-    # the steady part of the pipelined region: the middle of the kernel list by count (the run ends with isolated steps)
+    # the steady part of the pipelined region: the middle of the kernel list by count (away from the warm-up and the drain)
     ks = ks[len(ks) // 4: len(ks) * 6 // 10]
     ivs = sorted((s, e) for _, s, e in ks)
     busy = 0; cur_s, cur_e = ivs[0]
