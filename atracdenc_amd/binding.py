@@ -46,7 +46,11 @@ SYMBOLS = ["at3hip_encode_s16", "at3hip_create", "at3hip_destroy", "at3hip_frame
            "at3hip_host_free", "at3hip_wait_input", "at3hip_wait_frames", "at3hip_get_counters", "at3hip_device_numa_node",
            # the ATRAC3 decoder
            "at3hip_decoder_create", "at3hip_decoder_destroy", "at3hip_decoder_last_error", "at3hip_decode", "at3hip_decoder_sync",
-           "at3hip_decoder_reset", "at3hip_decoder_get_counters", "at3hip_decoder_set_stream"]
+           "at3hip_decoder_reset", "at3hip_decoder_get_counters", "at3hip_decoder_set_stream",
+           # the resampler (include/at3hip_resample.h, listed in at3hip.h's version notes)
+           "at3hip_resampler_create", "at3hip_resampler_destroy", "at3hip_resampler_last_error", "at3hip_resampler_reset",
+           "at3hip_resampler_max_out", "at3hip_resampler_process", "at3hip_resampler_flush", "at3hip_resampler_sync",
+           "at3hip_resampler_set_stream", "at3hip_resampler_shape", "at3hip_resampler_host_tables"]
 AT3HIP_DECODE_S16 = 8
 # include/at1hip.h
 AT1_SYMBOLS = ["at1hip_create", "at1hip_destroy", "at1hip_last_error", "at1hip_encode", "at1hip_reset", "at1hip_get_timings",
@@ -107,6 +111,10 @@ class At3pDecoderCounters(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in AT3P_DECODER_REASONS]
 
 
+class ResamplerConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("in_rate", "out_rate", "channels", "n_streams", "max_in", "device_id")]
+
+
 class At1Timings(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("total_ms", "front_ms", "scan_ms", "pack_ms")]
 
@@ -115,7 +123,7 @@ def build_library(verbose=False):
     """Compile libat3hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fvisibility=hidden", "-fPIC", "-shared",
            "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-o", LIB_PATH, os.path.join(CSRC, "at3hip.hip"), os.path.join(CSRC, "at1hip.hip"), os.path.join(CSRC, "at3phip.hip"),
-           os.path.join(CSRC, "at3_tables.cpp")]
+           os.path.join(CSRC, "resample.hip"), os.path.join(CSRC, "at3_tables.cpp")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -218,6 +226,17 @@ def load_library(path=None):
     lib.at3phip_get_write_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     lib.at3phip_host_write_tables.argtypes = [vp, ctypes.c_size_t]
     lib.at3phip_sync.argtypes = [vp]
+    if hasattr(lib, "at3hip_resampler_create"):   # the resampler (added under ABI 1.6, see at3hip.h's version list)
+        i32p = ctypes.POINTER(i32)
+        for name, argtypes in (("create", [ctypes.POINTER(ResamplerConfig), ctypes.POINTER(vp)]), ("destroy", [vp]),
+                               ("last_error", [vp]), ("reset", [vp]), ("max_out", [vp]),
+                               ("process", [vp, vp, i32, vp, i32p, ctypes.c_uint32]), ("flush", [vp, vp, i32p, ctypes.c_uint32]),
+                               ("sync", [vp]), ("set_stream", [vp, vp]), ("shape", [i32, i32, i32p, i32p, i32p]),
+                               ("host_tables", [i32, i32, vp, ctypes.c_size_t])):
+            getattr(lib, "at3hip_resampler_" + name).argtypes = argtypes
+        lib.at3hip_resampler_destroy.restype = None
+        lib.at3hip_resampler_last_error.restype = ctypes.c_char_p
+        lib.at3hip_resampler_max_out.restype = i32
     _lib_cache[path] = lib
     return lib
 
@@ -776,3 +795,95 @@ class At3pHip(_Context):
         self._check(self.lib.at3phip_get_timings(self.ctx, ctypes.byref(a), ctypes.byref(b)), "at3phip_get_timings")
         self._check(self.lib.at3phip_get_write_timing(self.ctx, ctypes.byref(w)), "at3phip_get_write_timing")
         return {"pqf_ms": a.value, "mdct_ms": b.value, "write_ms": w.value}
+
+
+def _resampler_lib(lib_path):
+    lib = load_library(lib_path)
+    if not hasattr(lib, "at3hip_resampler_create"):
+        raise At3HipError("libat3hip.so predates the resampler (no at3hip_resampler_create): rebuild it")
+    return lib
+
+
+def resampler_shape(in_rate, out_rate, lib_path=None):
+    """at3hip_resampler_shape (no GPU): (L phases, M input step, K taps per phase) of a supported pair."""
+    L, M, K = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    rc = _resampler_lib(lib_path).at3hip_resampler_shape(int(in_rate), int(out_rate), ctypes.byref(L), ctypes.byref(M), ctypes.byref(K))
+    if rc != 0:
+        raise At3HipError(f"at3hip_resampler_shape({in_rate}, {out_rate}) failed ({rc}): unsupported pair")
+    return L.value, M.value, K.value
+
+
+def resampler_host_tables(in_rate, out_rate, lib_path=None):
+    """at3hip_resampler_host_tables (no GPU): the filter table hp float32 [L][K] as at3hip_resampler_create builds it."""
+    L, _, K = resampler_shape(in_rate, out_rate, lib_path)
+    out = np.zeros((L, K), np.float32)
+    rc = _resampler_lib(lib_path).at3hip_resampler_host_tables(int(in_rate), int(out_rate), _vp(out), out.nbytes)
+    if rc != 0:
+        raise At3HipError(f"at3hip_resampler_host_tables failed ({rc})")
+    return out
+
+
+class HipResampler(_Context):
+    """n_streams streams of 1 or 2 channels converted from in_rate to out_rate side by side on one GPU
+    (include/at3hip_resample.h). Every stream of a call takes the same number of input samples."""
+
+    _PREFIX = "at3hip_resampler"
+
+    def __init__(self, in_rate, out_rate, channels=2, n_streams=1, max_in=1 << 16, device_id=0, lib_path=None):
+        self.lib = _resampler_lib(lib_path)
+        self.in_rate, self.out_rate = int(in_rate), int(out_rate)
+        self.channels, self.n_streams, self.max_in = int(channels), int(n_streams), int(max_in)
+        self._create(ResamplerConfig(self.in_rate, self.out_rate, self.channels, self.n_streams, self.max_in, int(device_id)),
+                     "unsupported rates or configuration, or no usable MI355X / HIP runtime")
+        self.max_out = int(self.lib.at3hip_resampler_max_out(self.ctx))
+        self.L, self.M, self.K = resampler_shape(self.in_rate, self.out_rate, lib_path)
+
+    def process_ptr(self, in_ptr, n_in, out_ptr, flags):
+        """Raw pointers and at3hip_resampler_process flags; returns the outputs per stream."""
+        n = ctypes.c_int32()
+        self._check(self.lib.at3hip_resampler_process(self.ctx, ctypes.c_void_p(in_ptr), int(n_in), ctypes.c_void_p(out_ptr),
+                                                      ctypes.byref(n), int(flags)), "at3hip_resampler_process")
+        return n.value
+
+    def flush_ptr(self, out_ptr, flags):
+        n = ctypes.c_int32()
+        self._check(self.lib.at3hip_resampler_flush(self.ctx, ctypes.c_void_p(out_ptr), ctypes.byref(n), int(flags)),
+                    "at3hip_resampler_flush")
+        return n.value
+
+    def process(self, pcm):
+        """pcm float32 [n_streams, n_in, channels] (host) -> float32 [n_streams, n_out, channels]"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
+        out = np.zeros((self.n_streams, self.max_out, self.channels), np.float32)
+        n = self.process_ptr(pcm.ctypes.data, pcm.shape[1], out.ctypes.data, 0)
+        return np.ascontiguousarray(out.reshape(-1)[: self.n_streams * n * self.channels].reshape(self.n_streams, n, self.channels))
+
+    def flush(self):
+        """The remaining outputs of every stream, float32 [n_streams, n_out, channels]; then the start state."""
+        out = np.zeros((self.n_streams, self.max_out, self.channels), np.float32)
+        n = self.flush_ptr(out.ctypes.data, 0)
+        return np.ascontiguousarray(out.reshape(-1)[: self.n_streams * n * self.channels].reshape(self.n_streams, n, self.channels))
+
+    def _device_out(self, out, device):
+        import torch
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.device == device
+        assert out.numel() >= self.n_streams * self.max_out * self.channels, tuple(out.shape)
+
+    def process_device(self, pcm, out, asynchronous=False, ordered=True):
+        """Torch tensors on this resampler's device: pcm float32 [n_streams, n_in, channels] -> out float32 with room for
+        max_out samples per stream; outputs are written as [n_streams][n][channels] from out's start. Returns n. Ordered
+        behind torch's current stream by default, as the decoders' decode_device."""
+        import torch
+        assert pcm.dtype == torch.float32 and pcm.is_contiguous()
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, tuple(pcm.shape)
+        self._device_out(out, pcm.device)
+        _Decoder._order_behind_torch(self, pcm.device, ordered)
+        flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)
+        return self.process_ptr(pcm.data_ptr(), pcm.shape[1], out.data_ptr(), flags)
+
+    def flush_device(self, out, asynchronous=False, ordered=True):
+        """flush into a torch tensor, as process_device; returns n."""
+        self._device_out(out, out.device)
+        _Decoder._order_behind_torch(self, out.device, ordered)
+        return self.flush_ptr(out.data_ptr(), AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0))

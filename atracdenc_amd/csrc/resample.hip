@@ -1,0 +1,473 @@
+// The batched sample-rate converter (include/at3hip_resample.h): table builder, the k_resample kernel and the C ABI.
+//
+// Kernel layout. Output n = q L + r has i = q M + floor(r M / L) and phase (r M) mod L, so the outputs
+// of one residue r share their phase and their input windows lie exactly M samples apart. A workgroup takes a tile of Q
+// consecutive q (Q <= 64) of one stream: it stages the tile's input span (Q M + K - 1 samples, every channel) in LDS once,
+// then each wavefront takes residues r = w, w + 8, ... with lane j on q = q0 + j. The taps are then wave-uniform (vector
+// loads of one address per wavefront, global_load_dwordx4 through the caches, tables of every size alike) and every lane runs
+// the definition's fmaf chain over its own window in LDS. Lane j's window starts at j M + u: with M even the span is stored with one pad sample after every M samples,
+// so that consecutive lanes sit M + 1 (odd) samples apart and a ds_read_b64 / ds_read_b32 of a wavefront touches every bank
+// once per half-wave.
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <type_traits>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/at3hip_resample.h"
+#include "at3_host_util.hpp"
+
+using at3host::dev_alloc;
+using at3host::fail;
+
+namespace {
+
+constexpr int kThreads = 512;              // 8 wavefronts per workgroup
+constexpr int kLdsBytes = 80 * 1024;       // two workgroups per CU
+constexpr int kMaxQ = 64;                  // q per tile: one per lane
+
+struct Shape {
+    int L, M, K;
+};
+
+bool rate_ok(int hz)
+{
+    static const int kRates[] = {8000, 11025, 16000, 22050, 24000, 32000, 48000, 88200, 96000, 176400, 192000};
+    for (int r : kRates)
+        if (hz == r) return true;
+    return false;
+}
+
+int gcd_int(int a, int b)
+{
+    while (b) {
+        const int t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+bool shape_of(int in, int out, Shape* s)
+{
+    if (!((in == 44100 && rate_ok(out)) || (out == 44100 && rate_ok(in)))) return false;
+    const int g = gcd_int(in, out);
+    const int f_lo = in < out ? in : out;
+    s->L = out / g;
+    s->M = in / g;
+    s->K = 2 * (int)((72ll * in + f_lo - 1) / f_lo);
+    return true;
+}
+
+double bessel_i0(double x)
+{
+    const double q = (x / 2) * (x / 2);
+    double t = 1.0, sum = 0.0;
+    sum += t;
+    for (int m = 1; m < 40; ++m) {
+        t = t * q / ((double)m * m);
+        sum += t;
+    }
+    return sum;
+}
+
+// hp[L][K] of the definition (at3hip_resample.h), in double, rounded once. optnone: the host compiler must not fold or
+// reassociate what the restatement computes step by step.
+__attribute__((optnone, noinline)) void build_table(int in, int out, const Shape& s, float* hp)
+{
+    const int f_lo = in < out ? in : out;
+    const double fc = 0.47675 * f_lo / in;
+    const double beta = 0.1102 * (100.0 - 8.7);
+    const double i0_beta = bessel_i0(beta);
+    const int half = s.K / 2;
+    for (int p = 0; p < s.L; ++p)
+        for (int k = 0; k < s.K; ++k) {
+            const double d = (double)(k - (half - 1)) - (double)p / s.L;
+            const double x = 2 * fc * d;
+            const double sinc = x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x);
+            const double r = d / half;
+            double w = 1 - r * r;
+            if (w < 0) w = 0;
+            hp[(size_t)p * s.K + k] = (float)(2 * fc * sinc * bessel_i0(beta * sqrt(w)) / i0_beta);
+        }
+}
+
+struct ResampleParams {
+    const float* hist;    // [S][K][C]: input samples T_old - K .. T_old - 1 of each stream (read)
+    float* hist_next;     // [S][K][C]: samples T_new - K .. T_new - 1 (written by the first workgroup of each stream)
+    const float* in;      // [S][n_in][C]
+    float* out;           // [S][n_out][C]
+    const float* hp;      // [L][K]
+    long long t_old;      // input samples of each stream before this call
+    long long n0;         // first output of this call
+    int n_in, n_out;
+    int L, M, K;
+    int Q, pad;           // q per tile; pad samples after every M in LDS (0 or 1)
+};
+
+// Input sample a of a stream (absolute index): zeros before the start and from T_new on; unneeded samples older than the
+// history also read as zeros (only outputs this call does not emit reach them).
+template <int C>
+__device__ __forceinline__ void sample(const ResampleParams& p, const float* hist, const float* in, long long a, float* v)
+{
+    const long long t_new = p.t_old + p.n_in;
+    if (a < 0 || a >= t_new || a < p.t_old - p.K) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = 0.0f;
+    } else if (a < p.t_old) {
+        const float* s = hist + (a - (p.t_old - p.K)) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = s[c];
+    } else {
+        const float* s = in + (a - p.t_old) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = s[c];
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(kThreads) void k_resample(ResampleParams p)
+{
+    using V = typename std::conditional<C == 2, float2, float>::type;
+    __shared__ V sx[kLdsBytes / sizeof(V)];
+    const size_t s = blockIdx.y;
+    const float* hist = p.hist + s * (size_t)p.K * C;
+    const float* in = p.in + s * (size_t)p.n_in * C;
+    const int tid = threadIdx.x;
+
+    if (blockIdx.x == 0) {   // the history the next call reads
+        float* hn = p.hist_next + s * (size_t)p.K * C;
+        for (int j = tid; j < p.K; j += kThreads) {
+            float v[C];
+            sample<C>(p, hist, in, p.t_old + p.n_in - p.K + j, v);
+#pragma unroll
+            for (int c = 0; c < C; ++c) hn[(size_t)j * C + c] = v[c];
+        }
+    }
+    if (p.n_out == 0) return;
+
+    const long long q_lo = p.n0 / p.L;
+    const long long q0 = q_lo + (long long)blockIdx.x * p.Q;
+    const long long n_end = p.n0 + p.n_out;
+    if (q0 * p.L >= n_end) return;
+    const int half = p.K / 2;
+    const long long s0 = q0 * p.M - (half - 1);   // absolute index of the span's first sample
+    const int span = p.Q * p.M + p.K - 1;
+    for (int j = tid; j < span; j += kThreads) {
+        float v[C];
+        sample<C>(p, hist, in, s0 + j, v);
+        V w;
+        if constexpr (C == 2) w = make_float2(v[0], v[1]);
+        else w = v[0];
+        sx[j + p.pad * (j / p.M)] = w;
+    }
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    const long long q = q0 + lane;
+    float* out = p.out + s * (size_t)p.n_out * C;
+    const V* xl = sx + lane * (p.M + p.pad);
+    for (int r = wave; r < p.L; r += kThreads / 64) {
+        const long long n = q * p.L + r;
+        if (lane >= p.Q || n < p.n0 || n >= n_end) continue;
+        const int rm = r * p.M;
+        const int u0 = rm / p.L;             // floor(r M / L): the window's offset in the lane's span
+        const float* h = p.hp + (size_t)(rm % p.L) * p.K;
+        float acc[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = 0.0f;
+        int k = 0, u = u0;
+        while (k < p.K) {   // segments between the pad samples (one segment when pad = 0)
+            const int seg = p.pad ? (u / p.M + 1) * p.M - u : p.K;
+            const int k_end = min(p.K, k + seg);
+            const V* x = xl + u + p.pad * (u / p.M);
+            u += k_end - k;
+            for (; k + 4 <= k_end; k += 4, x += 4) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const float hk = h[k + t];
+                    const V xv = x[t];
+                    if constexpr (C == 2) {
+                        acc[0] = __builtin_fmaf(hk, xv.x, acc[0]);
+                        acc[1] = __builtin_fmaf(hk, xv.y, acc[1]);
+                    } else {
+                        acc[0] = __builtin_fmaf(hk, xv, acc[0]);
+                    }
+                }
+            }
+            for (; k < k_end; ++k, ++x) {
+                const float hk = h[k];
+                const V xv = x[0];
+                if constexpr (C == 2) {
+                    acc[0] = __builtin_fmaf(hk, xv.x, acc[0]);
+                    acc[1] = __builtin_fmaf(hk, xv.y, acc[1]);
+                } else {
+                    acc[0] = __builtin_fmaf(hk, xv, acc[0]);
+                }
+            }
+        }
+        float* o = out + (size_t)(n - p.n0) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) o[c] = acc[c];
+    }
+}
+
+}  // namespace
+
+struct at3hip_resampler {
+    at3hip_resampler_config cfg;
+    Shape sh;
+    int Q = 0, pad = 0, max_out = 0;
+    int device = 0;
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;   // own_stream, or the caller's (at3hip_resampler_set_stream)
+    float* d_hp = nullptr;          // [L][K]
+    float* d_hist[2] = {nullptr, nullptr};   // [S][K][C], read / written alternately
+    int cur = 0;
+    float* d_in = nullptr;          // staging for host input  [S][max_in][C], allocated by the first call that needs it
+    float* d_out = nullptr;         // staging for host output [S][max_out][C], likewise
+    long long t_in = 0;             // input samples received per stream since the start
+    long long t_out = 0;            // outputs emitted per stream since the start
+    char err[256] = {0};
+};
+
+namespace {
+
+// ceil(a L / M) for a > 0, else 0: the outputs whose i is below a
+long long outputs_below(long long a, const Shape& s) { return a <= 0 ? 0 : (a * s.L + s.M - 1) / s.M; }
+
+void destroy(at3hip_resampler* r)
+{
+    {
+        at3host::DeviceGuard guard(r->device);
+        if (r->stream) (void)hipStreamSynchronize(r->stream);
+        for (void* b : {(void*)r->d_hp, (void*)r->d_hist[0], (void*)r->d_hist[1], (void*)r->d_in, (void*)r->d_out})
+            if (b) (void)hipFree(b);
+        if (r->own_stream) (void)hipStreamDestroy(r->own_stream);
+    }
+    delete r;
+}
+
+// Queues one call: n_in new samples (device memory), outputs [t_out, n_end) into out (device memory).
+int launch(at3hip_resampler* r, const float* in, int n_in, long long n_end, float* out)
+{
+    const int C = r->cfg.channels;
+    const Shape& sh = r->sh;
+    ResampleParams p;
+    p.hist = r->d_hist[r->cur];
+    p.hist_next = r->d_hist[r->cur ^ 1];
+    p.in = in;
+    p.out = out;
+    p.hp = r->d_hp;
+    p.t_old = r->t_in;
+    p.n0 = r->t_out;
+    p.n_in = n_in;
+    p.n_out = (int)(n_end - r->t_out);
+    p.L = sh.L;
+    p.M = sh.M;
+    p.K = sh.K;
+    p.Q = r->Q;
+    p.pad = r->pad;
+    long long tiles = 1;
+    if (p.n_out > 0) tiles = ((n_end - 1) / sh.L - r->t_out / sh.L) / r->Q + 1;
+    const dim3 grid((unsigned)tiles, (unsigned)r->cfg.n_streams);
+    if (C == 2) hipLaunchKernelGGL(k_resample<2>, grid, dim3(kThreads), 0, r->stream, p);
+    else hipLaunchKernelGGL(k_resample<1>, grid, dim3(kThreads), 0, r->stream, p);
+    HIPCHK(r, hipGetLastError());
+    r->cur ^= 1;
+    r->t_in += n_in;
+    r->t_out = n_end;
+    return AT3HIP_OK;
+}
+
+int finish(at3hip_resampler* r, float* out, int n_out, uint32_t flags)
+{
+    if (!(flags & AT3HIP_OUT_ON_DEVICE) && n_out > 0)
+        HIPCHK(r, hipMemcpyAsync(out, r->d_out, (size_t)r->cfg.n_streams * n_out * r->cfg.channels * sizeof(float),
+                                 hipMemcpyDeviceToHost, r->stream));
+    if (flags & AT3HIP_ASYNC) return AT3HIP_OK;
+    HIPCHK(r, hipStreamSynchronize(r->stream));
+    return AT3HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int at3hip_resampler_shape(int32_t in_rate, int32_t out_rate, int32_t* phases, int32_t* step, int32_t* taps)
+{
+    Shape s;
+    if (!shape_of(in_rate, out_rate, &s)) return AT3HIP_EINVAL;
+    if (phases) *phases = s.L;
+    if (step) *step = s.M;
+    if (taps) *taps = s.K;
+    return AT3HIP_OK;
+}
+
+int at3hip_resampler_host_tables(int32_t in_rate, int32_t out_rate, void* dst, size_t bytes)
+{
+    Shape s;
+    if (!dst || !shape_of(in_rate, out_rate, &s) || bytes != (size_t)s.L * s.K * sizeof(float)) return AT3HIP_EINVAL;
+    build_table(in_rate, out_rate, s, (float*)dst);
+    return AT3HIP_OK;
+}
+
+int at3hip_resampler_create(const at3hip_resampler_config* cfg, at3hip_resampler** out)
+{
+    if (!cfg || !out) return AT3HIP_EINVAL;
+    *out = nullptr;
+    Shape sh;
+    if (!shape_of(cfg->in_rate, cfg->out_rate, &sh)) return AT3HIP_EINVAL;
+    if ((cfg->channels != 1 && cfg->channels != 2) || cfg->n_streams < 1 || cfg->max_in < 1) return AT3HIP_EINVAL;
+    if (cfg->n_streams > at3host::kMaxGridY) return AT3HIP_EINVAL;   // the stream is gridDim.y
+    // LDS: the largest tile whose span (plus pads) fits; at least one q per tile
+    const int C = cfg->channels, pad = (sh.M % 2 == 0) ? 1 : 0;
+    int Q = kMaxQ;
+    while (Q > 1) {
+        const long long span = (long long)Q * sh.M + sh.K - 1;
+        if ((span + pad * (span / sh.M) + 1) * C * (long long)sizeof(float) <= kLdsBytes) break;
+        --Q;
+    }
+    {
+        const long long span = (long long)Q * sh.M + sh.K - 1;
+        if ((span + pad * (span / sh.M) + 1) * C * (long long)sizeof(float) > kLdsBytes) return AT3HIP_EINVAL;
+    }
+    const long long cap_process = ((long long)cfg->max_in * sh.L + sh.M - 1) / sh.M;
+    const long long cap_flush = ((long long)(sh.K / 2) * sh.L + sh.M - 1) / sh.M;
+    const long long max_out = cap_process > cap_flush ? cap_process : cap_flush;
+    if (max_out > INT32_MAX) return AT3HIP_EINVAL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return AT3HIP_EDEVICE;
+    if (cfg->device_id < 0 || cfg->device_id >= ndev) return AT3HIP_EINVAL;
+    at3hip_resampler* r = new (std::nothrow) at3hip_resampler();
+    if (!r) return AT3HIP_ENOMEM;
+    r->cfg = *cfg;
+    r->sh = sh;
+    r->Q = Q;
+    r->pad = pad;
+    r->max_out = (int)max_out;
+    r->device = cfg->device_id;
+    auto bail = [&](int code) {
+        destroy(r);
+        return code;
+    };
+    at3host::DeviceGuard guard(r->device);
+    if (guard.error() != hipSuccess) return bail(AT3HIP_EDEVICE);
+    if (hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(AT3HIP_EDEVICE);
+    r->stream = r->own_stream;
+    const size_t S = cfg->n_streams, table = (size_t)sh.L * sh.K;
+    float* host = new (std::nothrow) float[table];
+    if (!host) return bail(AT3HIP_ENOMEM);
+    build_table(cfg->in_rate, cfg->out_rate, sh, host);
+    int rc = dev_alloc(r, &r->d_hp, table);
+    if (rc == AT3HIP_OK && (hipMemcpy(r->d_hp, host, table * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+                            hipDeviceSynchronize() != hipSuccess))   // (pageable source, see at3hip_create)
+        rc = AT3HIP_EDEVICE;
+    delete[] host;
+    if (rc != AT3HIP_OK) return bail(rc);
+    for (int b = 0; b < 2; ++b)
+        if ((rc = dev_alloc(r, &r->d_hist[b], S * sh.K * C)) != AT3HIP_OK) return bail(rc);
+    for (int b = 0; b < 2; ++b)
+        if (hipMemsetAsync(r->d_hist[b], 0, S * sh.K * C * sizeof(float), r->stream) != hipSuccess) return bail(AT3HIP_EDEVICE);
+    if (hipStreamSynchronize(r->stream) != hipSuccess) return bail(AT3HIP_EDEVICE);
+    *out = r;
+    return AT3HIP_OK;
+}
+
+void at3hip_resampler_destroy(at3hip_resampler* r)
+{
+    if (r) destroy(r);
+}
+
+const char* at3hip_resampler_last_error(const at3hip_resampler* r) { return r ? r->err : "null context"; }
+
+int at3hip_resampler_reset(at3hip_resampler* r)
+{
+    if (!r) return AT3HIP_EINVAL;
+    // the history is read only for samples T_old - K .. T_old - 1 of a stream: at T = 0 nothing of it, so the counters are the state
+    r->t_in = 0;
+    r->t_out = 0;
+    return AT3HIP_OK;
+}
+
+int32_t at3hip_resampler_max_out(const at3hip_resampler* r) { return r ? r->max_out : AT3HIP_EINVAL; }
+
+int at3hip_resampler_process(at3hip_resampler* r, const float* in, int32_t n_in, float* out, int32_t* n_out, uint32_t flags)
+{
+    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC;
+    if (!r) return AT3HIP_EINVAL;
+    if (!out || !n_out || (n_in > 0 && !in) || n_in < 0 || n_in > r->cfg.max_in || (flags & ~known))
+        return fail(r, AT3HIP_EINVAL, "bad argument");
+    at3host::DeviceGuard guard(r->device);
+    HIPCHK(r, guard.error());
+    const int C = r->cfg.channels;
+    const size_t S = r->cfg.n_streams;
+    // staging for host memory, allocated by the first call that takes or gives host memory: device buffers never need it
+    if (n_in > 0 && !(flags & AT3HIP_PCM_ON_DEVICE) && !r->d_in) {
+        const int rc = dev_alloc(r, &r->d_in, S * (size_t)r->cfg.max_in * C);
+        if (rc != AT3HIP_OK) return rc;
+    }
+    if (!(flags & AT3HIP_OUT_ON_DEVICE) && !r->d_out) {
+        const int rc = dev_alloc(r, &r->d_out, S * (size_t)r->max_out * C);
+        if (rc != AT3HIP_OK) return rc;
+    }
+    const float* d_in = in;
+    if (n_in > 0 && !(flags & AT3HIP_PCM_ON_DEVICE)) {
+        HIPCHK(r, hipMemcpyAsync(r->d_in, in, S * n_in * C * sizeof(float), hipMemcpyHostToDevice, r->stream));
+        d_in = r->d_in;
+    }
+    if (n_in == 0) d_in = r->d_hist[r->cur];   // (never read)
+    const long long n_end_new = outputs_below(r->t_in + n_in - r->sh.K / 2, r->sh);
+    const long long n_end = n_end_new > r->t_out ? n_end_new : r->t_out;
+    const int count = (int)(n_end - r->t_out);
+    float* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? out : r->d_out;
+    const int rc = launch(r, d_in, n_in, n_end, d_out);
+    if (rc != AT3HIP_OK) return rc;
+    *n_out = count;
+    return finish(r, out, count, flags);
+}
+
+int at3hip_resampler_flush(at3hip_resampler* r, float* out, int32_t* n_out, uint32_t flags)
+{
+    const uint32_t known = AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3HIP_PCM_ON_DEVICE;
+    if (!r) return AT3HIP_EINVAL;
+    if (!out || !n_out || (flags & ~known)) return fail(r, AT3HIP_EINVAL, "bad argument");
+    at3host::DeviceGuard guard(r->device);
+    HIPCHK(r, guard.error());
+    const long long n_end = outputs_below(r->t_in, r->sh);
+    const int count = (int)(n_end - r->t_out);
+    if (!(flags & AT3HIP_OUT_ON_DEVICE) && !r->d_out) {
+        const int rc = dev_alloc(r, &r->d_out, (size_t)r->cfg.n_streams * r->max_out * r->cfg.channels);
+        if (rc != AT3HIP_OK) return rc;
+    }
+    float* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? out : r->d_out;
+    const int rc = launch(r, r->d_hist[r->cur], 0, n_end, d_out);   // (no input: never read)
+    if (rc != AT3HIP_OK) return rc;
+    *n_out = count;
+    r->t_in = 0;
+    r->t_out = 0;
+    return finish(r, out, count, flags);
+}
+
+int at3hip_resampler_sync(at3hip_resampler* r)
+{
+    if (!r) return AT3HIP_EINVAL;
+    at3host::DeviceGuard guard(r->device);
+    HIPCHK(r, guard.error());
+    HIPCHK(r, hipStreamSynchronize(r->stream));
+    return AT3HIP_OK;
+}
+
+int at3hip_resampler_set_stream(at3hip_resampler* r, void* hip_stream)
+{
+    if (!r) return AT3HIP_EINVAL;
+    at3host::DeviceGuard guard(r->device);
+    HIPCHK(r, guard.error());
+    HIPCHK(r, hipStreamSynchronize(r->stream));
+    r->stream = hip_stream ? (hipStream_t)hip_stream : r->own_stream;
+    return AT3HIP_OK;
+}
+
+}  // extern "C"

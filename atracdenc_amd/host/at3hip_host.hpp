@@ -34,6 +34,7 @@
 
 #include "../../include/at1hip.h"
 #include "../../include/at3hip.h"
+#include "../../include/at3hip_resample.h"
 #include "../../include/at3phip.h"
 
 namespace NAtracDEncHip {
@@ -693,6 +694,94 @@ private:
     std::vector<float> Pending;
     std::vector<std::vector<char>> Ready;
     size_t Calls = 0, Written = 0;
+};
+
+// ---- sample-rate conversion (include/at3hip_resample.h) ------------------------------------------------------------------
+// One at3hip_resampler of one stream, owned.
+class TResampler {
+public:
+    TResampler(int inRate, int outRate, int channels, int maxIn, int device) : Channels(channels)
+    {
+        CheckLibraryVersion();
+        at3hip_resampler_config cfg{inRate, outRate, channels, 1, maxIn, device};
+        const int rc = at3hip_resampler_create(&cfg, &R);
+        if (rc != AT3HIP_OK)
+            throw std::runtime_error("at3hip_resampler_create(" + std::to_string(inRate) + " -> " + std::to_string(outRate) +
+                                     ") failed (" + std::to_string(rc) + ")");
+        Out.resize((size_t)at3hip_resampler_max_out(R) * channels);
+    }
+    ~TResampler()
+    {
+        if (R) at3hip_resampler_destroy(R);
+    }
+    TResampler(const TResampler&) = delete;
+    TResampler& operator=(const TResampler&) = delete;
+
+    // n sample frames of interleaved input; appends the outputs they complete to `dst`
+    void Process(const float* in, int32_t n, std::vector<float>& dst) { Append(at3hip_resampler_process(R, in, n, Out.data(), &N, 0), dst); }
+    // the remaining outputs; then the start state
+    void Flush(std::vector<float>& dst) { Append(at3hip_resampler_flush(R, Out.data(), &N, 0), dst); }
+
+private:
+    void Append(int rc, std::vector<float>& dst)
+    {
+        if (rc != AT3HIP_OK) throw std::runtime_error(std::string("at3hip_resampler: ") + at3hip_resampler_last_error(R));
+        dst.insert(dst.end(), Out.begin(), Out.begin() + (size_t)N * Channels);
+    }
+    at3hip_resampler* R = nullptr;
+    int Channels;
+    int32_t N = 0;
+    std::vector<float> Out;
+};
+
+// A PCM source at another rate, converted to `outRate` in chunks of kChunk input samples and flushed at the source's end. TSrc
+// has GetChannelNum / GetSampleRate / GetTotalSamples and Read(float*, frames) as TWavSource (at3hip_io.hpp); so does this.
+template <class TSrc>
+class TResampledSource {
+public:
+    static constexpr int kChunk = 1 << 16;
+
+    TResampledSource(TSrc& src, int outRate, int device)
+        : Src(src), Rate(outRate), Rs((int)src.GetSampleRate(), outRate, (int)src.GetChannelNum(), kChunk, device),
+          In((size_t)kChunk * src.GetChannelNum())
+    {
+        int32_t L = 0, M = 0;
+        at3hip_resampler_shape((int32_t)src.GetSampleRate(), outRate, &L, &M, nullptr);
+        Total = (src.GetTotalSamples() * (uint64_t)L + (uint64_t)M - 1) / (uint64_t)M;   // ceil(N L / M)
+    }
+
+    size_t GetChannelNum() const { return Src.GetChannelNum(); }
+    size_t GetSampleRate() const { return (size_t)Rate; }
+    uint64_t GetTotalSamples() const { return Total; }
+
+    size_t Read(float* dst, size_t frames)
+    {
+        const size_t C = Src.GetChannelNum();
+        while (Buf.size() / C - Pos < frames && !Done) {
+            Buf.erase(Buf.begin(), Buf.begin() + Pos * C);
+            Pos = 0;
+            const size_t n = Src.Read(In.data(), kChunk);
+            if (n) {
+                Rs.Process(In.data(), (int32_t)n, Buf);
+            } else {
+                Rs.Flush(Buf);
+                Done = true;
+            }
+        }
+        const size_t n = std::min(frames, Buf.size() / C - Pos);
+        std::copy(Buf.begin() + Pos * C, Buf.begin() + (Pos + n) * C, dst);
+        Pos += n;
+        return n;
+    }
+
+private:
+    TSrc& Src;
+    int Rate;
+    TResampler Rs;
+    std::vector<float> In, Buf;
+    size_t Pos = 0;
+    uint64_t Total = 0;
+    bool Done = false;
 };
 
 }  // namespace NAtracDEncHip

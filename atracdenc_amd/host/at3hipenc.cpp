@@ -9,13 +9,18 @@
 //             [--container aea|raw] [--nostdout] [--batch blocks] [--device n]
 //   at3hipenc -e atrac3plus -i in.wav -o out.{oma|at3|wav|raw|dat} [--container oma|riff|raw] [--nostdout]
 //             [--batch frames] [--device n]
+//   --resample (all three encoders): a WAV at 8 .. 192 kHz (at3hip_resample.h's list) is converted to 44.1 kHz on the GPU
+//             first; the container headers count ceil(N 44100 / rate) samples. A 44.1 kHz input is encoded as without it.
+//   --rate hz (every decoder): the decoded audio is converted to hz (at3hip_resample.h's list) on the GPU, clamped to [-1, 1] and
+//             written as lrintf(x * 32767.0f); the WAV counts ceil(N hz / 44100) samples. --rate 44100 writes what -d writes alone.
 //   at3hipenc -d -i in.aea -o out.wav [--nostdout] [--batch frames] [--device n]
 //             the reference's ATRAC1 decode path (main.cpp:343-365, 697-705) on the GPU decoder (at1hip.h)
 //   at3hipenc -d -i in.{oma|at3|wav} -o out.wav [--nostdout] [--batch frames] [--device n]
 //             ATRAC3 in an OMA container or in RIFF/WAVE (format 0x270), chosen by content, on the GPU decoder (at3hip.h)
 //
-// File-level behaviour follows the reference: 44.1 kHz input only, numFrames estimate = samples / 1024 in the
+// File-level behaviour follows the reference: 44.1 kHz input only (without --resample), numFrames estimate = samples / 1024 in the
 // container header, the look-ahead first call, the drain call at end of input.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +29,7 @@
 
 #include <cstdint>
 #include <fstream>
+#include <memory>
 #include <vector>
 
 #include "../../include/at1hip.h"
@@ -63,7 +69,7 @@ void put_le(std::vector<char>& h, uint32_t v, int bytes)
 }
 
 // The 44-byte canonical header of a 16-bit PCM WAV at 44100 Hz with `dataBytes` bytes of samples.
-void write_wav_header(std::ofstream& out, uint32_t nch, uint32_t dataBytes)
+void write_wav_header(std::ofstream& out, uint32_t nch, uint32_t dataBytes, uint32_t rate = 44100)
 {
     std::vector<char> wav;
     wav.insert(wav.end(), {'R', 'I', 'F', 'F'});
@@ -72,14 +78,72 @@ void write_wav_header(std::ofstream& out, uint32_t nch, uint32_t dataBytes)
     put_le(wav, 16, 4);
     put_le(wav, 1, 2);   // PCM
     put_le(wav, nch, 2);
-    put_le(wav, 44100, 4);
-    put_le(wav, 44100u * 2u * nch, 4);
+    put_le(wav, rate, 4);
+    put_le(wav, rate * 2u * nch, 4);
     put_le(wav, 2u * nch, 2);
     put_le(wav, 16, 2);
     wav.insert(wav.end(), {'d', 'a', 't', 'a'});
     put_le(wav, dataBytes, 4);
     out.write(wav.data(), (std::streamsize)wav.size());
 }
+
+// The encoders' input: the WAV file at 44.1 kHz, or with --resample a WAV file at any rate at3hip_resample.h supports, converted
+// to 44.1 kHz on the GPU (TResampledSource). Without the flag any other rate is refused, as the reference refuses it (main.cpp:281).
+struct TEncodeInput {
+    TWavSource File;
+    std::unique_ptr<TResampledSource<TWavSource>> Conv;
+
+    TEncodeInput(const std::string& path, bool resample, int device) : File(path)
+    {
+        if (File.GetSampleRate() == 44100) return;
+        if (!resample) throw std::runtime_error("unsupported sample rate");
+        Conv.reset(new TResampledSource<TWavSource>(File, 44100, device));
+    }
+    size_t GetChannelNum() const { return File.GetChannelNum(); }
+    size_t GetSampleRate() const { return Conv ? Conv->GetSampleRate() : File.GetSampleRate(); }
+    uint64_t GetTotalSamples() const { return Conv ? Conv->GetTotalSamples() : File.GetTotalSamples(); }   // ceil(N 44100 / in)
+    size_t Read(float* dst, size_t frames) { return Conv ? Conv->Read(dst, frames) : File.Read(dst, frames); }
+};
+
+// `-d ... --rate <hz>`: the decoder's float output (44.1 kHz, already clamped) converted to another rate on the GPU
+// (at3hip_resample.h), clamped to [-1, 1] again and written as lrintf(x * 32767.0f), the rule of the 44.1 kHz output. The WAV
+// header counts ceil(N rate / 44100) samples for the N decoded ones; Finish() writes the converter's tail.
+class TRateWriter {
+public:
+    TRateWriter(std::ofstream& out, int rate, int nch, int maxIn, int device) : Out(out), Rs(44100, rate, nch, maxIn, device) {}
+
+    // the samples a decoded stream of n at 44.1 kHz gives at `rate`; -1 for an unsupported rate
+    static int64_t Samples(int64_t n, int rate)
+    {
+        int32_t L = 0, M = 0;
+        if (at3hip_resampler_shape(44100, rate, &L, &M, nullptr) != AT3HIP_OK) return -1;
+        return (n * L + M - 1) / M;
+    }
+    void Write(const float* pcm, int32_t n)
+    {
+        Buf.clear();
+        Rs.Process(pcm, n, Buf);
+        Emit();
+    }
+    void Finish()
+    {
+        Buf.clear();
+        Rs.Flush(Buf);
+        Emit();
+    }
+
+private:
+    void Emit()
+    {
+        S16.resize(Buf.size());
+        for (size_t i = 0; i < Buf.size(); ++i) S16[i] = (int16_t)lrintf(std::min(1.0f, std::max(-1.0f, Buf[i])) * 32767.0f);
+        Out.write((const char*)S16.data(), (std::streamsize)S16.size() * 2);   // little-endian host
+    }
+    std::ofstream& Out;
+    TResampler Rs;
+    std::vector<float> Buf;
+    std::vector<int16_t> S16;
+};
 
 // `-d`: TAtrac1Decoder behind TPCMEngine(4096, channels) with a TWav writer (main.cpp:343-365, 697-705).
 //  * Length: TAeaInput::GetLengthInSamples = 512 * (units / channels - 5) (aea.cpp:98-108). The engine's ApplyProcess(512) runs
@@ -91,7 +155,7 @@ void write_wav_header(std::ofstream& out, uint32_t nch, uint32_t dataBytes)
 //    SF_FORMAT_WAV | SF_FORMAT_PCM_16 with normalisation, which stores lrintf(x * 32767.0f) behind a 44-byte canonical header.
 //    That rule and the header are a restatement of libsndfile's documented behaviour, not pinned against it here; the float
 //    samples the conversion starts from are pinned against the reference (tests/golden/at1_decode.npz).
-int decode_aea(const std::string& inFile, const std::string& outFile, bool noStdOut, int batch, int device)
+int decode_aea(const std::string& inFile, const std::string& outFile, bool noStdOut, int batch, int device, int rate)
 {
     std::ifstream in(inFile, std::ios::binary);
     if (!in) {
@@ -129,9 +193,16 @@ int decode_aea(const std::string& inFile, const std::string& outFile, bool noStd
         std::cerr << "Fatal error: unable to open output file '" << outFile << "'" << std::endl;
         return 1;
     }
-    write_wav_header(out, (uint32_t)nch, (uint32_t)(nOut * 512 * nch * 2));
+    const int64_t nSamples = rate ? TRateWriter::Samples(nOut * 512, rate) : nOut * 512;
+    if (rate && nSamples * nch * 2 >= (int64_t)UINT32_MAX - 36) {
+        std::cerr << "Fatal error: output too long for a WAV file" << std::endl;
+        return 1;
+    }
+    write_wav_header(out, (uint32_t)nch, (uint32_t)(nSamples * nch * 2), rate ? (uint32_t)rate : 44100u);
 
     const int B = batch < 1 ? 1 : batch;
+    // (before the decoder: the converter may refuse, and nothing is then left to free)
+    std::unique_ptr<TRateWriter> rw(rate ? new TRateWriter(out, rate, nch, B * 512, device) : nullptr);
     at1hip_decoder* dec = nullptr;
     at1hip_decoder_config cfg{nch, 1, B, device};
     int rc = at1hip_decoder_create(&cfg, &dec);
@@ -143,6 +214,7 @@ int decode_aea(const std::string& inFile, const std::string& outFile, bool noStd
     const int64_t nReport = complete < calls ? frames : nOut;
     std::vector<uint8_t> units((size_t)B * nch * AT1HIP_FRAME_SIZE);
     std::vector<int16_t> pcm((size_t)B * 512 * nch);
+    std::vector<float> pcmf(rate ? (size_t)B * 512 * nch : 0);
     for (int64_t f0 = 0; f0 < nReport; f0 += B) {
         const int n = (int)std::min<int64_t>(B, nReport - f0);
         in.read((char*)units.data(), (std::streamsize)n * nch * AT1HIP_FRAME_SIZE);
@@ -151,15 +223,17 @@ int decode_aea(const std::string& inFile, const std::string& outFile, bool noStd
                 std::cerr << "Skipping invalid ATRAC1 frame: " << what << std::endl;
         const int nDec = (int)std::min<int64_t>(n, nOut - f0);
         if (nDec <= 0) break;
-        rc = at1hip_decode(dec, units.data(), nDec, pcm.data(), AT1HIP_DECODE_S16);
+        rc = rw ? at1hip_decode(dec, units.data(), nDec, pcmf.data(), 0) : at1hip_decode(dec, units.data(), nDec, pcm.data(), AT1HIP_DECODE_S16);
         if (rc != AT3HIP_OK) {
             std::cerr << "Encode/Decode error: at1hip_decode: " << at1hip_decoder_last_error(dec) << std::endl;
             at1hip_decoder_destroy(dec);
             return 1;
         }
-        out.write((const char*)pcm.data(), (std::streamsize)nDec * 512 * nch * 2);   // little-endian host
+        if (rw) rw->Write(pcmf.data(), nDec * 512);
+        else out.write((const char*)pcm.data(), (std::streamsize)nDec * 512 * nch * 2);   // little-endian host
     }
     at1hip_decoder_destroy(dec);
+    if (rw) rw->Finish();
     if (complete < calls) {
         std::cerr << "Aea IO fatal error: Can't read AEA frame" << std::endl;
         return 1;
@@ -297,7 +371,8 @@ EInput probe_input(const std::string& inFile, TAt3Input& at3)
     return EInput::ATRAC3;
 }
 
-int decode_at3(const std::string& inFile, const std::string& outFile, const TAt3Input& at3, bool noStdOut, int batch, int device)
+int decode_at3(const std::string& inFile, const std::string& outFile, const TAt3Input& at3, bool noStdOut, int batch, int device,
+               int rate)
 {
     std::ifstream in(inFile, std::ios::binary);
     if (!in) {
@@ -319,12 +394,19 @@ int decode_at3(const std::string& inFile, const std::string& outFile, const TAt3
         return 1;
     }
     const uint32_t nch = 2;
-    write_wav_header(out, nch, (uint32_t)(nOut * 1024 * nch * 2));
+    const int64_t nSamples = rate ? TRateWriter::Samples(nOut * 1024, rate) : nOut * 1024;
+    if (nSamples * nch * 2 >= (int64_t)UINT32_MAX - 36) {
+        std::cerr << "Fatal error: output too long for a WAV file" << std::endl;
+        return 1;
+    }
+    write_wav_header(out, nch, (uint32_t)(nSamples * nch * 2), rate ? (uint32_t)rate : 44100u);
     if (nOut == 0) {
         if (!noStdOut) std::cout << "\nDone" << std::endl;
         return 0;
     }
     const int B = (int)std::min<int64_t>(batch < 1 ? 1 : batch, nOut);
+    // (before the decoder: the converter may refuse, and nothing is then left to free)
+    std::unique_ptr<TRateWriter> rw(rate ? new TRateWriter(out, rate, (int)nch, B * 1024, device) : nullptr);
     at3hip_decoder* dec = nullptr;
     at3hip_decoder_config cfg{1, at3.frameSize, at3.js, B, device};
     int rc = at3hip_decoder_create(&cfg, &dec);
@@ -334,6 +416,7 @@ int decode_at3(const std::string& inFile, const std::string& outFile, const TAt3
     }
     std::vector<uint8_t> frames((size_t)B * at3.frameSize);
     std::vector<int16_t> pcm((size_t)B * 1024 * nch);
+    std::vector<float> pcmf(rate ? (size_t)B * 1024 * nch : 0);
     for (int64_t f0 = 0; f0 < nOut; f0 += B) {
         const int n = (int)std::min<int64_t>(B, nOut - f0);
         if (!in.read((char*)frames.data(), (std::streamsize)n * at3.frameSize)) {
@@ -341,14 +424,16 @@ int decode_at3(const std::string& inFile, const std::string& outFile, const TAt3
             at3hip_decoder_destroy(dec);
             return 1;
         }
-        rc = at3hip_decode(dec, frames.data(), n, pcm.data(), AT3HIP_DECODE_S16);
+        rc = rw ? at3hip_decode(dec, frames.data(), n, pcmf.data(), 0) : at3hip_decode(dec, frames.data(), n, pcm.data(), AT3HIP_DECODE_S16);
         if (rc != AT3HIP_OK) {
             std::cerr << "Encode/Decode error: at3hip_decode: " << at3hip_decoder_last_error(dec) << std::endl;
             at3hip_decoder_destroy(dec);
             return 1;
         }
-        out.write((const char*)pcm.data(), (std::streamsize)n * 1024 * nch * 2);   // little-endian host
+        if (rw) rw->Write(pcmf.data(), n * 1024);
+        else out.write((const char*)pcm.data(), (std::streamsize)n * 1024 * nch * 2);   // little-endian host
     }
+    if (rw) rw->Finish();
     at3hip_decoder_counters c{};
     rc = at3hip_decoder_get_counters(dec, &c, 0);
     at3hip_decoder_destroy(dec);
@@ -367,7 +452,8 @@ int decode_at3(const std::string& inFile, const std::string& outFile, const TAt3
 
 // `-d` on an ATRAC3plus OMA / RIFF file: a 16-bit WAV with the stream's channel count, 2048 samples per frame, the codec delay
 // (2416 samples) not trimmed; rejected frames are counted and reported per reason.
-int decode_at3p(const std::string& inFile, const std::string& outFile, const TAt3Input& at3, bool noStdOut, int batch, int device)
+int decode_at3p(const std::string& inFile, const std::string& outFile, const TAt3Input& at3, bool noStdOut, int batch, int device,
+                int rate)
 {
     std::ifstream in(inFile, std::ios::binary);
     if (!in) {
@@ -385,16 +471,19 @@ int decode_at3p(const std::string& inFile, const std::string& outFile, const TAt
         std::cerr << "Fatal error: unable to open output file '" << outFile << "'" << std::endl;
         return 1;
     }
-    if (nOut * 2048 * nch * 2 >= (int64_t)UINT32_MAX - 36) {
+    const int64_t nSamples = rate ? TRateWriter::Samples(nOut * 2048, rate) : nOut * 2048;
+    if (nSamples * nch * 2 >= (int64_t)UINT32_MAX - 36) {
         std::cerr << "Fatal error: output too long for a WAV file" << std::endl;
         return 1;
     }
-    write_wav_header(out, nch, (uint32_t)(nOut * 2048 * nch * 2));
+    write_wav_header(out, nch, (uint32_t)(nSamples * nch * 2), rate ? (uint32_t)rate : 44100u);
     if (nOut == 0) {
         if (!noStdOut) std::cout << "\nDone" << std::endl;
         return 0;
     }
     const int B = (int)std::min<int64_t>(batch < 1 ? 1 : batch, nOut);
+    // (before the decoder: the converter may refuse, and nothing is then left to free)
+    std::unique_ptr<TRateWriter> rw(rate ? new TRateWriter(out, rate, (int)nch, B * 2048, device) : nullptr);
     at3phip_decoder* dec = nullptr;
     at3phip_decoder_config cfg{(int32_t)nch, 1, B, device};
     int rc = at3phip_decoder_create(&cfg, &dec);
@@ -404,6 +493,7 @@ int decode_at3p(const std::string& inFile, const std::string& outFile, const TAt
     }
     std::vector<uint8_t> frames((size_t)B * 2048);
     std::vector<int16_t> pcm((size_t)B * 2048 * nch);
+    std::vector<float> pcmf(rate ? (size_t)B * 2048 * nch : 0);
     for (int64_t f0 = 0; f0 < nOut; f0 += B) {
         const int n = (int)std::min<int64_t>(B, nOut - f0);
         if (!in.read((char*)frames.data(), (std::streamsize)n * 2048)) {
@@ -411,14 +501,17 @@ int decode_at3p(const std::string& inFile, const std::string& outFile, const TAt
             at3phip_decoder_destroy(dec);
             return 1;
         }
-        rc = at3phip_decode(dec, frames.data(), n, pcm.data(), AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES);
+        rc = rw ? at3phip_decode(dec, frames.data(), n, pcmf.data(), AT3PHIP_DECODE_TONES)
+                : at3phip_decode(dec, frames.data(), n, pcm.data(), AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES);
         if (rc != AT3HIP_OK) {
             std::cerr << "Encode/Decode error: at3phip_decode: " << at3phip_decoder_last_error(dec) << std::endl;
             at3phip_decoder_destroy(dec);
             return 1;
         }
-        out.write((const char*)pcm.data(), (std::streamsize)n * 2048 * nch * 2);   // little-endian host
+        if (rw) rw->Write(pcmf.data(), n * 2048);
+        else out.write((const char*)pcm.data(), (std::streamsize)n * 2048 * nch * 2);   // little-endian host
     }
+    if (rw) rw->Finish();
     at3phip_decoder_counters c{};
     rc = at3phip_decoder_get_counters(dec, &c, 0);
     at3phip_decoder_destroy(dec);
@@ -445,18 +538,20 @@ static int usage()
                  "       at3hipenc -e atrac1 -i in.wav -o out.aea [--bfuidxconst 1..8] [--notransient[=mask]]\n"
                  "                 [--container aea|raw] [--nostdout] [--batch blocks] [--device n]\n"
                  "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
+                 "       (every encoder: --resample converts an input at 8 .. 192 kHz to 44.1 kHz first)\n"
                  "       at3hipenc -d -i in.aea -o out.wav [--nostdout] [--batch frames] [--device n]\n"
-                 "       at3hipenc -d -i in.{oma|at3|wav} -o out.wav [--nostdout] [--batch frames] [--device n]   (ATRAC3 / ATRAC3plus, by content)\n";
+                 "       at3hipenc -d -i in.{oma|at3|wav} -o out.wav [--nostdout] [--batch frames] [--device n]   (ATRAC3 / ATRAC3plus, by content)\n"
+                 "       (every decoder: --rate hz writes the WAV at 8 .. 192 kHz instead of 44.1 kHz)\n";
     return 1;
 }
 
 int main(int argc, char** argv)
 {
-    std::string inFile, outFile, codec, container;
+    std::string inFile, outFile, codec, container, rateArg;
     uint32_t bitrate = 0, bfuIdxConst = 0;
-    bool noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false;
+    bool noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false, resample = false;
     uint32_t winMask = 0;
-    int batch = 256, device = 0;
+    int batch = 256, device = 0, rate = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](const char* what) -> const char* {
@@ -475,6 +570,14 @@ int main(int argc, char** argv)
         else if (a == "--notonal") noTonal = true;
         else if (a == "--nogaincontrol") noGain = true;
         else if (a == "--nostdout") noStdOut = true;
+        else if (a == "--resample") resample = true;
+        else if (a == "--rate") {   // a positive decimal number, else refused below as an unsupported rate
+            const char* v = need("--rate");
+            rateArg = v;
+            char* end = nullptr;
+            const long x = strtol(v, &end, 10);
+            rate = (*v && !*end && x > 0 && x <= 1000000) ? (int)x : -1;
+        }
         else if (a.rfind("--notransient", 0) == 0 && (a.size() == 13 || a[13] == '=')) {   // optional_argument, main.cpp:568-577
             noTransient = true;
             if (a.size() > 14) winMask = (uint32_t)atoi(a.c_str() + 14);
@@ -489,15 +592,24 @@ int main(int argc, char** argv)
         TAt3Input at3;
         const EInput kind = probe_input(inFile, at3);
         if (kind == EInput::REFUSED) return 1;
-        if (kind == EInput::ATRAC3) return decode_at3(inFile, outFile, at3, noStdOut, batch, device);
-        if (kind == EInput::ATRAC3PLUS) return decode_at3p(inFile, outFile, at3, noStdOut, batch, device);
-        return decode_aea(inFile, outFile, noStdOut, batch, device);
+        if (rate == 44100) rate = 0;   // the decoders' own rate: written as without --rate
+        if (rate && TRateWriter::Samples(0, rate) < 0) {
+            std::cerr << "Fatal error: unsupported output rate " << rateArg << " (at3hip_resample.h lists the rates)" << std::endl;
+            return 1;
+        }
+        try {
+            if (kind == EInput::ATRAC3) return decode_at3(inFile, outFile, at3, noStdOut, batch, device, rate);
+            if (kind == EInput::ATRAC3PLUS) return decode_at3p(inFile, outFile, at3, noStdOut, batch, device, rate);
+            return decode_aea(inFile, outFile, noStdOut, batch, device, rate);
+        } catch (const std::exception& ex) {
+            std::cerr << "Fatal error: " << ex.what() << std::endl;
+            return 1;
+        }
     }
-    if ((codec != "atrac3" && codec != "atrac1" && codec != "atrac3plus") || inFile.empty() || outFile.empty()) return usage();
+    if ((codec != "atrac3" && codec != "atrac1" && codec != "atrac3plus") || inFile.empty() || outFile.empty() || rate) return usage();
     if (codec == "atrac3plus") {
         try {
-            TWavSource wav(inFile);
-            if (wav.GetSampleRate() != 44100) throw std::runtime_error("unsupported sample rate");
+            TEncodeInput wav(inFile, resample, device);
             const size_t numChannels = wav.GetChannelNum();
             const uint64_t totalSamples = wav.GetTotalSamples();
             const uint64_t numFrames = totalSamples / 2048;   // main.cpp:440
@@ -536,8 +648,7 @@ int main(int argc, char** argv)
             return 1;
         }
         try {
-            TWavSource wav(inFile);
-            if (wav.GetSampleRate() != 44100) throw std::runtime_error("unsupported sample rate");
+            TEncodeInput wav(inFile, resample, device);
             const size_t numChannels = wav.GetChannelNum();
             const uint64_t totalSamples = wav.GetTotalSamples();
             const uint64_t numFrames = numChannels * totalSamples / 512;   // main.cpp:312
@@ -583,8 +694,7 @@ int main(int argc, char** argv)
         return 1;
     }
     try {
-        TWavSource wav(inFile);
-        if (wav.GetSampleRate() != 44100) throw std::runtime_error("unsupported sample rate");
+        TEncodeInput wav(inFile, resample, device);
         const size_t numChannels = wav.GetChannelNum();
         const uint64_t totalSamples = wav.GetTotalSamples();
         const uint64_t numFrames = totalSamples / 1024;

@@ -382,6 +382,10 @@ int at3hip_decoder_set_stream(at3hip_decoder* dec, void* hip_stream);
  *        and, added later under the same number, the ATRAC3plus decoder (at3phip.h): at3phip_decoder_create / _destroy /
  *        _last_error / _sync / _reset / _get_counters / _set_stream, at3phip_decode, at3phip_decoder_host_tables,
  *        AT3PHIP_DECODE_S16 (detected by the symbol at3phip_decoder_create)
+ *        and, added later under the same number, the resampler (at3hip_resample.h): at3hip_resampler_create(),
+ *        at3hip_resampler_destroy(), at3hip_resampler_last_error(), at3hip_resampler_reset(), at3hip_resampler_max_out(),
+ *        at3hip_resampler_process(), at3hip_resampler_flush(), at3hip_resampler_sync(), at3hip_resampler_set_stream(),
+ *        at3hip_resampler_shape(), at3hip_resampler_host_tables() (detected by the symbol at3hip_resampler_create)
  * A host layer compiled against this header checks at3hip_version() >= AT3HIP_VERSION before it relies on them
  * (atracdenc_amd/host/at3hip_host.hpp and the ctypes stub do). */
 #define AT3HIP_VERSION_MAJOR 1
