@@ -22,6 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CPU_SRC = os.path.join(HERE, "host", "at1_decode_cpu.c")
 CFLAGS = ["-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]
 UNIT = 212
+GOLDEN = os.path.join(HERE, "golden", "at1_decode.npz")
 
 
 def build_cpu_decoder(outdir):
@@ -238,6 +239,30 @@ def crafted_units(nch, seed):
 def random_modes(shape, rng):
     """Valid block-size fields: low / mid in 0..2, high in 0..3 (LogCount 2, 1, 0 / 3, 2, 1, 0)."""
     return np.stack([rng.integers(0, 3, shape), rng.integers(0, 3, shape), rng.integers(0, 4, shape)], -1)
+
+
+# ---- the fuzz inputs of the GPU tests and of the SIMT-harness tests (the same bytes from the same seeds) ----------------------
+def fuzz_units(nch, n_streams, n_frames, seed):
+    """valid reference-shaped units (the goldens' encoder output with rewritten block sizes) mixed with random and malformed ones"""
+    rng = np.random.default_rng(seed)
+    g = np.load(GOLDEN)
+    pool = np.concatenate([g[f"{n}_units"] for n in g["cases"] if f"_ch{nch}" in n and not n.startswith("random")])
+    pool = np.concatenate([pool, crafted_units(nch, seed)])
+    idx = rng.integers(0, pool.shape[0], (n_streams, n_frames))
+    units = pool[idx]
+    units = np.where(rng.random((n_streams, n_frames, 1, 1)) < 0.5, set_block_modes(units, random_modes(units.shape[:3], rng)), units)
+    noise = rng.integers(0, 256, units.shape, dtype=np.uint8)
+    return np.where(rng.random((n_streams, n_frames, 1, 1)) < 0.25, noise, units).astype(np.uint8)
+
+
+def cpu_ref(cpu, units):
+    """[S][N][C][212] -> ([S][N][512][C], rejected counts summed over streams)"""
+    outs, rej = [], np.zeros(2, np.uint64)
+    for s in range(units.shape[0]):
+        d = CpuDecoder(units.shape[2], cpu)
+        outs.append(d.decode(units[s]))
+        rej += d.rejected
+    return np.stack(outs), rej.tolist()
 
 
 # ---- files -----------------------------------------------------------------------------------------------------------------

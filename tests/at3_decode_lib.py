@@ -21,6 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CPU_SRC = os.path.join(HERE, "host", "at3_decode_cpu.c")
 CFLAGS = ["-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]
 REF_SRC = "/root/reference/src"
+GOLDEN = os.path.join(HERE, "golden", "at3_decode.npz")
 
 # the eight container rows (atrac3.h: ContainerParams): bitrate, frame size, joint stereo
 ROWS = ((66150, 192, True), (93713, 272, True), (104738, 304, False), (132300, 384, False), (146081, 424, False),
@@ -388,6 +389,33 @@ def mutate_frames(frames, rng, n_flips=3):
             p = int(rng.integers(0, out.shape[1] * 8))
             out[f, p >> 3] ^= 0x80 >> (p & 7)
     return out
+
+
+# ---- the fuzz inputs of the GPU tests and of the SIMT-harness tests (the same bytes from the same seeds) ----------------------
+def fuzz_frames(golden, fsz, n_streams, n_frames, seed):
+    """encoder frames of the row, the same with a few bits flipped, crafted frames and random bytes, shuffled per stream"""
+    rng = np.random.default_rng(seed)
+    pool = np.concatenate([golden[f"{c}_frames"] for c in golden["cases"] if int(golden[f"{c}_row"][0]) == fsz])
+    out = np.empty((n_streams, n_frames, fsz), np.uint8)
+    for s in range(n_streams):
+        enc = pool[rng.integers(0, pool.shape[0], n_frames)]
+        kind = rng.integers(0, 4, n_frames)
+        mut = mutate_frames(enc, rng, n_flips=int(rng.integers(1, 6)))
+        rnd = rng.integers(0, 256, (n_frames, fsz), dtype=np.uint8)
+        out[s] = np.where((kind == 0)[:, None], enc, np.where((kind == 1)[:, None], mut, rnd))
+        k = min(n_frames, 8)
+        out[s, :k] = crafted_frames(fsz, fsz in (192, 272), seed=seed + s)[:k]
+    return out
+
+
+def cpu_ref(frames, fsz, js):
+    """[S][N][fsz] -> ([S][N][1024][2], rejected per reason summed over streams)"""
+    outs, rej = [], np.zeros(len(REASONS), np.int64)
+    for s in range(frames.shape[0]):
+        d = CpuDecoder(fsz, js)
+        outs.append(d.decode(frames[s]))
+        rej += d.rejected.astype(np.int64)
+    return np.stack(outs), rej.tolist()
 
 
 # ---- files -----------------------------------------------------------------------------------------------------------------

@@ -23,6 +23,7 @@ CPU_SRC = os.path.join(HERE, "host", "at3p_decode_cpu.c")
 CFLAGS = ["-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]
 REF_SRC = "/root/reference/src"
 FRAME = 2048
+GOLDEN = os.path.join(HERE, "golden", "at3p_decode.npz")
 REASONS = ("bad_header", "unsupported_syntax", "tonal_present", "bad_code", "read_past_end", "no_terminator")
 SIGNAL_NAMES = ("noise", "burst", "tones", "silence", "mix", "stress")
 # the codec's end-to-end delay in samples: output sample t of the decoder (frames from the stream's first encoded frame) is input
@@ -442,6 +443,23 @@ def mutate_frames(frames, rng, n_flips=3, span=None):
             p = int(rng.integers(0, lim))
             out[f, p >> 3] ^= 0x80 >> (p & 7)
     return out
+
+
+# ---- the fuzz inputs of the GPU tests and of the SIMT-harness tests (the same bytes from the same seeds) ----------------------
+def fuzz_streams(g, names, nch, seed=None, n_streams=4, n_plain=12, n_head=12, n_crafted=8):
+    """[n_streams][n_plain + n_head + n_crafted][2048]: per stream, golden frames with flipped bits, golden frames with flips
+    confined to the header fields, and crafted frames. The defaults (seed 1234 + nch, 4 x 32 frames) are the streams of the
+    GPU suite's test_fuzz_equals_restatement."""
+    rng = np.random.default_rng(1234 + nch if seed is None else seed)
+    base = np.concatenate([g[f"{n}_frames"] for n in names if int(g[f"{n}_channels"]) == nch and n.startswith(("sig_", "win_"))])
+    crafted, _ = crafted_frames(nch, seed=77 + nch)
+    streams = []
+    for k in range(n_streams):
+        pick = base[rng.integers(0, base.shape[0], n_plain + n_head)]
+        # flips anywhere, and flips confined to the first 600 bits (header, word lengths, scale factors, table indices)
+        streams.append(np.concatenate([mutate_frames(pick[:n_plain], rng, n_flips=1 + k % 4), mutate_frames(pick[n_plain:], rng, 2, span=600),
+                                       crafted[rng.integers(0, crafted.shape[0], n_crafted)]]))
+    return np.stack(streams)
 
 
 # ---- files -----------------------------------------------------------------------------------------------------------------

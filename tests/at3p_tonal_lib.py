@@ -19,10 +19,11 @@ import tempfile
 import numpy as np
 
 from at3_testlib import REF_SO, _vp
-from at3p_decode_lib import CFLAGS, FRAME, REASONS, RESCALE, BitWriter, make_frame, ref_driver, REF_SRC
+from at3p_decode_lib import CFLAGS, FRAME, REASONS, RESCALE, BitWriter, make_frame, mutate_frames, ref_driver, REF_SRC
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 TONAL_SRC = os.path.join(HERE, "host", "at3p_tonal_cpu.c")
+GOLDEN = os.path.join(HERE, "golden", "at3p_tonal.npz")
 REC_INTS = 1 + 2 * 16 * 6 + 3 * 48
 TONE_VLC = None
 
@@ -229,6 +230,48 @@ def random_block(rng, channels, nb=None, max_total=48):
             row.append({"start": st, "stop": sp, "waves": waves})
         bands.append(row)
     return {"nb": nb, "shared": shared, "leader": bool(channels == 2 and rng.random() < 0.4), "bands": bands}
+
+
+# ---- the inputs of the GPU tests and of the SIMT-harness tests (the same bytes from the same seeds) ---------------------------
+def side_by_side(g, names, nch):
+    cases = [n for n in names if int(g[f"{n}_channels"]) == nch]
+    nf = max(g[f"{n}_frames"].shape[0] for n in cases)
+    frames = np.zeros((len(cases), nf, 2048), np.uint8)   # zero frames past a case's end: rejected, decoded after its PCM
+    for i, n in enumerate(cases):
+        fr = g[f"{n}_frames"]
+        frames[i, :fr.shape[0]] = fr
+    return cases, frames
+
+
+def plain(nch):
+    """a frame without a tonal block"""
+    return make_frame(nch, nqu=6, wl=[[3] * 6 for _ in range(nch)], sf=[[30] * 6 for _ in range(nch)],
+                      mant=lambda ch, qu, k: (k % 3) - 1)
+
+
+def pool(rng, nch, n):
+    frames = []
+    while len(frames) < n:
+        b = random_block(rng, nch)
+        for row in b["bands"]:
+            for bd in row:
+                bd["waves"] = [(f, int(rng.integers(0, 40)), p) for f, _, p in bd["waves"]]
+        fr = make_tonal_frame(nch, b, seed=len(frames))
+        if fr is not None:
+            frames.append(fr)
+    return np.stack(frames)
+
+
+def fuzz_tonal_streams(nch, streams, nf, seed=None):
+    """[streams][nf][2048] drawn from a pool of random tonal blocks, some with flipped bits, some without a tonal block (seed
+    1000 + nch by default: the streams of the GPU suite's test_fuzzed_tonal_frames_equal_restatement)"""
+    rng = np.random.default_rng(1000 + nch if seed is None else seed)
+    pl = pool(rng, nch, 96)
+    pl = np.concatenate([pl, mutate_frames(pl[:32], rng, n_flips=2)])
+    frames = pl[rng.integers(0, pl.shape[0], (streams, nf))]
+    is_plain = rng.random((streams, nf)) < 0.15
+    frames[is_plain] = plain(nch)
+    return frames
 
 
 # ---- the reference's tone synthesis ----------------------------------------------------------------------------------------

@@ -9,12 +9,10 @@ import pytest
 
 import atracdenc_amd
 from atracdenc_amd import At1Hip, At1HipDecoder, At3HipError
-from at1_decode_lib import CpuDecoder, cpu_lib, crafted_units, random_modes, read_wav, s16_of, set_block_modes, write_aea
+from at1_decode_lib import GOLDEN, CpuDecoder, cpu_lib, cpu_ref, fuzz_units, random_modes, read_wav, s16_of, set_block_modes, write_aea
 from at3_testlib import ROOT, SIGNALS, at1_blocks, pcm_stress, pin_digest
 
 pytestmark = pytest.mark.gpu
-
-GOLDEN = os.path.join(ROOT, "tests", "golden", "at1_decode.npz")
 
 
 @pytest.fixture(scope="module")
@@ -31,16 +29,6 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def cpu_ref(cpu, units):
-    """[S][N][C][212] -> ([S][N][512][C], rejected counts summed over streams)"""
-    outs, rej = [], np.zeros(2, np.uint64)
-    for s in range(units.shape[0]):
-        d = CpuDecoder(units.shape[2], cpu)
-        outs.append(d.decode(units[s]))
-        rej += d.rejected
-    return np.stack(outs), rej.tolist()
-
-
 def test_goldens_bit_identical(golden):
     for name in golden["cases"]:
         units = golden[f"{name}_units"]
@@ -54,22 +42,9 @@ def test_goldens_bit_identical(golden):
         assert [c["bad_block_size"], c["read_past_end"]] == golden[f"{name}_rejected"].tolist(), name
 
 
-def _fuzz_units(nch, n_streams, n_frames, seed):
-    """valid reference-shaped units (the goldens' encoder output with rewritten block sizes) mixed with random and malformed ones"""
-    rng = np.random.default_rng(seed)
-    g = np.load(GOLDEN)
-    pool = np.concatenate([g[f"{n}_units"] for n in g["cases"] if f"_ch{nch}" in n and not n.startswith("random")])
-    pool = np.concatenate([pool, crafted_units(nch, seed)])
-    idx = rng.integers(0, pool.shape[0], (n_streams, n_frames))
-    units = pool[idx]
-    units = np.where(rng.random((n_streams, n_frames, 1, 1)) < 0.5, set_block_modes(units, random_modes(units.shape[:3], rng)), units)
-    noise = rng.integers(0, 256, units.shape, dtype=np.uint8)
-    return np.where(rng.random((n_streams, n_frames, 1, 1)) < 0.25, noise, units).astype(np.uint8)
-
-
 @pytest.mark.parametrize("nch", [1, 2])
 def test_fuzz_equals_restatement(cpu, nch):
-    units = _fuzz_units(nch, 6, 600, seed=40 + nch)
+    units = fuzz_units(nch, 6, 600, seed=40 + nch)
     exp, rej = cpu_ref(cpu, units)
     dec = At1HipDecoder(n_streams=6, max_frames=600, channels=nch)
     got = dec.decode(units)
@@ -81,7 +56,7 @@ def test_fuzz_equals_restatement(cpu, nch):
 
 
 def test_splits_reset_and_counters(cpu):
-    units = _fuzz_units(2, 3, 300, seed=7)
+    units = fuzz_units(2, 3, 300, seed=7)
     exp, rej = cpu_ref(cpu, units)
     dec = At1HipDecoder(n_streams=3, max_frames=300, channels=2)
     for cuts in ([1, 7, 64, 100, 128], [299, 1], [13] * 23 + [1]):
@@ -101,7 +76,7 @@ def test_splits_reset_and_counters(cpu):
 
 def test_device_tensors_ordered_and_queued(cpu):
     import torch
-    units = _fuzz_units(2, 4, 256, seed=9)
+    units = fuzz_units(2, 4, 256, seed=9)
     exp, _ = cpu_ref(cpu, units)
     dec = At1HipDecoder(n_streams=4, max_frames=256, channels=2)
     # ordered (default): the units are produced on torch's current stream right before the call

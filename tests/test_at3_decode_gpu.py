@@ -7,12 +7,10 @@ import numpy as np
 import pytest
 
 from atracdenc_amd import At3Hip, At3HipDecoder, At3HipError
-from at3_decode_lib import REASONS, ROWS, CpuDecoder, crafted_frames, mutate_frames
+from at3_decode_lib import GOLDEN, REASONS, ROWS, cpu_ref, fuzz_frames
 from at3_testlib import ROOT, SIGNALS, pin_digest
 
 pytestmark = pytest.mark.gpu
-
-GOLDEN = os.path.join(ROOT, "tests", "golden", "at3_decode.npz")
 
 
 @pytest.fixture(scope="module")
@@ -26,16 +24,6 @@ def bits(a):
 
 def s16_of(pcm):
     return np.rint(pcm.astype(np.float32) * np.float32(32767.0)).astype(np.int16)
-
-
-def cpu_ref(frames, fsz, js):
-    """[S][N][fsz] -> ([S][N][1024][2], rejected per reason summed over streams)"""
-    outs, rej = [], np.zeros(len(REASONS), np.int64)
-    for s in range(frames.shape[0]):
-        d = CpuDecoder(fsz, js)
-        outs.append(d.decode(frames[s]))
-        rej += d.rejected.astype(np.int64)
-    return np.stack(outs), rej.tolist()
 
 
 def counts(dec):
@@ -58,26 +46,10 @@ def test_goldens_bit_identical(golden):
         assert c == golden[f"{name}_rejected"].tolist(), name
 
 
-def _fuzz_frames(golden, fsz, n_streams, n_frames, seed):
-    """encoder frames of the row, the same with a few bits flipped, crafted frames and random bytes, shuffled per stream"""
-    rng = np.random.default_rng(seed)
-    pool = np.concatenate([golden[f"{c}_frames"] for c in golden["cases"] if int(golden[f"{c}_row"][0]) == fsz])
-    out = np.empty((n_streams, n_frames, fsz), np.uint8)
-    for s in range(n_streams):
-        enc = pool[rng.integers(0, pool.shape[0], n_frames)]
-        kind = rng.integers(0, 4, n_frames)
-        mut = mutate_frames(enc, rng, n_flips=int(rng.integers(1, 6)))
-        rnd = rng.integers(0, 256, (n_frames, fsz), dtype=np.uint8)
-        out[s] = np.where((kind == 0)[:, None], enc, np.where((kind == 1)[:, None], mut, rnd))
-        k = min(n_frames, 8)
-        out[s, :k] = crafted_frames(fsz, fsz in (192, 272), seed=seed + s)[:k]
-    return out
-
-
 @pytest.mark.parametrize("row", ROWS, ids=[str(r[1]) for r in ROWS])
 def test_fuzz_equals_restatement(golden, row):
     _, fsz, js = row
-    frames = _fuzz_frames(golden, fsz, 3, 96, seed=fsz)
+    frames = fuzz_frames(golden, fsz, 3, 96, seed=fsz)
     exp, rej = cpu_ref(frames, fsz, js)
     dec = At3HipDecoder(n_streams=3, frame_size=fsz, max_frames=96)
     got = dec.decode(frames)
@@ -90,7 +62,7 @@ def test_fuzz_equals_restatement(golden, row):
 
 def test_splits_reset_and_counters(golden):
     fsz, js = 192, True
-    frames = _fuzz_frames(golden, fsz, 2, 120, seed=77)
+    frames = fuzz_frames(golden, fsz, 2, 120, seed=77)
     exp, rej = cpu_ref(frames, fsz, js)
     dec = At3HipDecoder(n_streams=2, frame_size=fsz, max_frames=120)
     rng = np.random.default_rng(5)
@@ -108,7 +80,7 @@ def test_splits_reset_and_counters(golden):
 def test_device_tensors_ordered_and_queued(golden):
     import torch
     fsz, js = 384, False
-    frames = _fuzz_frames(golden, fsz, 4, 200, seed=9)
+    frames = fuzz_frames(golden, fsz, 4, 200, seed=9)
     exp, _ = cpu_ref(frames, fsz, js)
     dec = At3HipDecoder(n_streams=4, frame_size=fsz, max_frames=200)
     src = torch.from_numpy(frames).cuda()
@@ -160,7 +132,7 @@ def test_s16_output_is_lrintf_of_float(golden):
 def test_long_stream(golden):
     fsz, js = 272, True
     n = 65536
-    frames = _fuzz_frames(golden, fsz, 1, n, seed=3)
+    frames = fuzz_frames(golden, fsz, 1, n, seed=3)
     exp, rej = cpu_ref(frames, fsz, js)
     dec = At3HipDecoder(n_streams=1, frame_size=fsz, max_frames=n)
     got = dec.decode(frames)

@@ -8,12 +8,10 @@ import wave
 import numpy as np
 import pytest
 
-from at3_testlib import ROOT, at3p_signal, pin_digest
-from at3p_decode_lib import DELAY, REASONS, CpuDecoder, cpu_decode, crafted_frames, mutate_frames
+from at3_testlib import at3p_signal, pin_digest
+from at3p_decode_lib import DELAY, GOLDEN, REASONS, CpuDecoder, cpu_decode, fuzz_streams
 
 pytestmark = pytest.mark.gpu
-
-GOLDEN = os.path.join(ROOT, "tests", "golden", "at3p_decode.npz")
 
 
 @pytest.fixture(scope="module")
@@ -62,16 +60,7 @@ def cpu_frames_silence(nch):
 @pytest.mark.parametrize("nch", [1, 2])
 def test_fuzz_equals_restatement(golden, nch):
     g, names = golden
-    rng = np.random.default_rng(1234 + nch)
-    base = np.concatenate([g[f"{n}_frames"] for n in names if int(g[f"{n}_channels"]) == nch and n.startswith(("sig_", "win_"))])
-    crafted, _ = crafted_frames(nch, seed=77 + nch)
-    streams = []
-    for k in range(4):
-        pick = base[rng.integers(0, base.shape[0], 24)]
-        # flips anywhere, and flips confined to the first 600 bits (header, word lengths, scale factors, table indices)
-        streams.append(np.concatenate([mutate_frames(pick[:12], rng, n_flips=1 + k), mutate_frames(pick[12:], rng, 2, span=600),
-                                       crafted[rng.integers(0, crafted.shape[0], 8)]]))
-    frames = np.stack(streams)
+    frames = fuzz_streams(g, names, nch)
     dec = _dec(nch, n_streams=frames.shape[0], max_frames=frames.shape[1])
     got = dec.decode(frames)
     counters = dec.counters()

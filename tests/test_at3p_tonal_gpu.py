@@ -9,12 +9,12 @@ import numpy as np
 import pytest
 
 import at3p_tonal_lib as L
-from at3_testlib import ROOT, pin_digest
-from at3p_decode_lib import REASONS, mutate_frames, oma_bytes
+from at3_testlib import pin_digest
+from at3p_decode_lib import REASONS, oma_bytes
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(ROOT, "tests", "golden", "at3p_tonal.npz")
+GOLDEN = L.GOLDEN
 
 
 @pytest.fixture(scope="module")
@@ -28,20 +28,10 @@ def _dec(nch, n_streams=1, max_frames=64):
     return atracdenc_amd.At3pHipDecoder(n_streams=n_streams, channels=nch, max_frames=max_frames, device_id=0)
 
 
-def _side_by_side(g, names, nch):
-    cases = [n for n in names if int(g[f"{n}_channels"]) == nch]
-    nf = max(g[f"{n}_frames"].shape[0] for n in cases)
-    frames = np.zeros((len(cases), nf, 2048), np.uint8)   # zero frames past a case's end: rejected, decoded after its PCM
-    for i, n in enumerate(cases):
-        fr = g[f"{n}_frames"]
-        frames[i, :fr.shape[0]] = fr
-    return cases, frames
-
-
 @pytest.mark.parametrize("nch", [1, 2])
 def test_tonal_goldens_bit_identical(golden, nch):
     g, names = golden
-    cases, frames = _side_by_side(g, names, nch)
+    cases, frames = L.side_by_side(g, names, nch)
     dec = _dec(nch, n_streams=len(cases), max_frames=frames.shape[1])
     pcm = dec.decode(frames, tones=True)
     c = dec.counters()
@@ -95,35 +85,10 @@ def test_any_split_and_reset_equal_one_call(golden):
     dec.close()
 
 
-def _plain(nch):
-    """a frame without a tonal block"""
-    from at3p_decode_lib import make_frame
-    return make_frame(nch, nqu=6, wl=[[3] * 6 for _ in range(nch)], sf=[[30] * 6 for _ in range(nch)],
-                      mant=lambda ch, qu, k: (k % 3) - 1)
-
-
-def _pool(rng, nch, n):
-    frames = []
-    while len(frames) < n:
-        b = L.random_block(rng, nch)
-        for row in b["bands"]:
-            for bd in row:
-                bd["waves"] = [(f, int(rng.integers(0, 40)), p) for f, _, p in bd["waves"]]
-        fr = L.make_tonal_frame(nch, b, seed=len(frames))
-        if fr is not None:
-            frames.append(fr)
-    return np.stack(frames)
-
-
 @pytest.mark.parametrize("nch,streams,nf", [(1, 64, 400), (2, 256, 400)])
 def test_fuzzed_tonal_frames_equal_restatement(nch, streams, nf):
     """streams x nf frames drawn from a pool of random tonal blocks, some with flipped bits, some without a tonal block"""
-    rng = np.random.default_rng(1000 + nch)
-    pool = _pool(rng, nch, 96)
-    pool = np.concatenate([pool, mutate_frames(pool[:32], rng, n_flips=2)])
-    frames = pool[rng.integers(0, pool.shape[0], (streams, nf))]
-    plain = rng.random((streams, nf)) < 0.15
-    frames[plain] = _plain(nch)
+    frames = L.fuzz_tonal_streams(nch, streams, nf)
     dec = _dec(nch, n_streams=streams, max_frames=nf)
     pcm = dec.decode(frames, tones=True)
     c = dec.counters()
@@ -140,7 +105,7 @@ def test_fuzzed_tonal_frames_equal_restatement(nch, streams, nf):
 def test_device_tensors_and_async_calls(golden):
     import torch
     g, names = golden
-    cases, frames = _side_by_side(g, names, 2)
+    cases, frames = L.side_by_side(g, names, 2)
     dec = _dec(2, n_streams=len(cases), max_frames=frames.shape[1])
     want = dec.decode(frames, tones=True)
     dec.reset()

@@ -5,13 +5,18 @@ The harness is test infrastructure like the oracle: the product library never co
 strict form here (-O0 + EMU_STRICT): besides comparing results it aborts when the lanes of a wavefront reach a cross-lane
 exchange (ballot, readlane, ds_bpermute, DPP, wave-level rendezvous) from two DIFFERENT calls, i.e. when such a read
 sits inside divergent control flow - a class of mistake the GPU tolerates until the compiler or the data change.
+
+The decoders and the resampler go through the same harness in tests/test_decoders_simt_harness.py. The default runs of the
+encoders' drivers are repeated at the end of this module with the wavefronts of every workgroup visited in descending order
+(EMU_ORDER=reverse): a missing __syncthreads() between a producer and a consumer wavefront shows in one of the two orders.
 """
 import os
 import re
-import subprocess
 import sys
 
 import pytest
+
+from simt_harness_lib import Children, assert_clean, build_strict, run_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
@@ -20,26 +25,17 @@ pytestmark = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's 
 
 
 def _run(script, *args, timeout=900):
-    env = dict(os.environ, EMU_STRICT="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "emu", script), *args], capture_output=True, text=True,
-                       timeout=timeout, env=env, cwd=ROOT)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-4000:]
+    rc, out = run_script(script, args, timeout=timeout)
+    assert rc == 0, out[-4000:]
     return out
 
 
-def _assert_clean(out, min_cases):
-    counts = re.findall(r"(?:mismatching frames|bad) (\d+)", out)
-    assert len(counts) >= min_cases, out[-4000:]
-    assert all(c == "0" for c in counts), out[-4000:]
+_assert_clean = assert_clean
 
 
 @pytest.fixture(scope="module")
 def harness():
-    sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
-    import run_emu
-    run_emu.build(strict=True)
-    return run_emu.EMU
+    return build_strict()   # (once per session: tests/test_decoders_simt_harness.py uses the same library)
 
 
 def test_atrac3_kernels(harness):
@@ -121,3 +117,35 @@ def test_atrac3plus_front_kernels(harness):
 
 def test_atrac3plus_frame_kernels(harness):
     _assert_clean(_run("run_emu_at3p_write.py", "--nobuild"), 26)
+
+
+# ---- the same default runs with the wavefronts of a workgroup in descending order ------------------------------------------------
+AT3_SIGNALS = ("noise", "burst", "tones", "silence", "mix", "stress")   # run_emu.py's default list, one child per signal
+
+
+@pytest.fixture(scope="module")
+def reversed_runs(harness):
+    rev = {"EMU_ORDER": "reverse"}
+    jobs = {name: ("run_emu.py", ["--strict", "--nobuild", name], rev) for name in AT3_SIGNALS}
+    for script in ("run_emu_at1.py", "run_emu_at3p.py", "run_emu_at3p_write.py"):
+        jobs[script] = (script, ["--nobuild"], rev)
+    c = Children(jobs)
+    yield c
+    c.close()
+
+
+def test_atrac3_kernels_reversed_wavefront_order(reversed_runs):
+    for name in AT3_SIGNALS:
+        _assert_clean(reversed_runs.output(name), 12)   # (72 in all, as test_atrac3_kernels)
+
+
+def test_atrac1_kernels_reversed_wavefront_order(reversed_runs):
+    _assert_clean(reversed_runs.output("run_emu_at1.py"), 24 * 4)
+
+
+def test_atrac3plus_front_kernels_reversed_wavefront_order(reversed_runs):
+    _assert_clean(reversed_runs.output("run_emu_at3p.py"), 12)
+
+
+def test_atrac3plus_frame_kernels_reversed_wavefront_order(reversed_runs):
+    _assert_clean(reversed_runs.output("run_emu_at3p_write.py"), 26)

@@ -7,56 +7,16 @@ import pytest
 import atracdenc_amd
 from atracdenc_amd import At3Hip, At3HipError, HipResampler
 from atracdenc_amd.binding import AT3HIP_ASYNC, AT3HIP_OUT_ON_DEVICE, AT3HIP_PCM_ON_DEVICE, ResamplerConfig
-from resample_lib import PAIRS, CpuResampler, n_outputs, shape
+from resample_lib import PAIRS, CpuResampler, bits_equal, n_outputs, run_split, shape, signal
 
 pytestmark = pytest.mark.gpu
 
 GB = 1 << 30
 
 
-def signal(kind, n, channels, seed, rate=48000):
-    rng = np.random.RandomState(seed)
-    t = np.arange(n)
-    if kind == "noise":
-        x = rng.uniform(-1, 1, (n, channels))
-    elif kind == "sweep":   # full scale, 20 Hz up to the rate's Nyquist
-        f = 20 * (rate / 2 / 20) ** (t / n)
-        ph = 2 * np.pi * np.cumsum(f) / rate
-        x = np.stack([np.sin(ph + c) for c in range(channels)], axis=-1)
-    elif kind == "silence":
-        x = np.zeros((n, channels))
-    elif kind == "subnormal":   # subnormals, signed zeros and the smallest normals
-        x = rng.choice(np.array([1e-39, -1e-40, 1.4e-45, -0.0, 0.0, 1.2e-38, -3e-39], np.float32), (n, channels))
-        x = x * rng.uniform(0.5, 1.5, (n, channels)).astype(np.float32)
-    else:
-        raise ValueError(kind)
-    return np.ascontiguousarray(x, np.float32)
-
-
 def restated(pair, x, channels):
     """the whole converted stream of x [n][channels]"""
     return CpuResampler(*pair, channels).whole(x)
-
-
-def bits_equal(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
-
-def run_split(r, xs, cuts):
-    """xs [S][T][C] through r in calls ending at `cuts`, then flush; checks n_out against the host-computed count"""
-    L, M, K = r.L, r.M, r.K
-    parts, at = [], 0
-    for cut in cuts:
-        got = r.process(xs[:, at:cut])
-        a = cut - K // 2
-        emitted = sum(p.shape[1] for p in parts)
-        assert got.shape[1] == (-(-a * L // M) if a > 0 else 0) - emitted
-        parts.append(got)
-        at = cut
-    tail = r.flush()
-    assert tail.shape[1] == n_outputs(at, r.in_rate, r.out_rate) - sum(p.shape[1] for p in parts)
-    parts.append(tail)
-    return np.concatenate(parts, axis=1)
 
 
 @pytest.mark.parametrize("pair", PAIRS, ids=[f"{a}-{b}" for a, b in PAIRS])

@@ -1,6 +1,11 @@
 // DEVELOPMENT HARNESS ONLY - see hip/hip_runtime.h in this directory.
 #include "hip/hip_runtime.h"
 #include <dlfcn.h>
+#include <sys/mman.h>
+#include <unistd.h>
+
+#include <map>
+#include <mutex>
 // k_alloc_pack's harness-only counters (at3_k_alloc.hpp: AT3_STAT)
 extern "C" { unsigned long long g_alloc_stats[16] = {0}; }
 
@@ -38,6 +43,38 @@ struct Wave {
 };
 std::vector<Wave> g_waves;
 
+// EMU_FENCE: 0 off, 1 high (guard page directly after the allocation), 2 low (directly before it)
+int fence_mode()
+{
+    static const int mode = [] {
+        const char* e = getenv("EMU_FENCE");
+        if (!e || !*e) return 0;
+        if (!strcmp(e, "high")) return 1;
+        if (!strcmp(e, "low")) return 2;
+        fprintf(stderr, "emu: EMU_FENCE must be high or low, not '%s'\n", e);
+        abort();
+    }();
+    return mode;
+}
+// EMU_ORDER=reverse: the wavefronts of a workgroup are visited in descending order
+bool reverse_order()
+{
+    static const bool rev = [] {
+        const char* e = getenv("EMU_ORDER");
+        if (!e || !*e) return false;
+        if (!strcmp(e, "reverse")) return true;
+        fprintf(stderr, "emu: EMU_ORDER must be reverse, not '%s'\n", e);
+        abort();
+    }();
+    return rev;
+}
+struct Mapping {
+    void* base;
+    size_t bytes;
+};
+std::map<void*, Mapping> g_fenced;   // allocation -> its mapping (guard page included)
+std::mutex g_fenced_mu;
+
 void yield_to_scheduler() { swapcontext(&g_fibers[g_cur].ctx, &g_main); }
 
 void trampoline()
@@ -57,6 +94,40 @@ void trampoline()
     swapcontext(&f.ctx, &g_main);
 }
 }  // namespace
+
+void* emu_device_alloc(size_t n)
+{
+    const int mode = fence_mode();
+    if (mode == 0) {
+        void* p = malloc(n);
+        if (p) memset(p, 0xCD, n);
+        return p;
+    }
+    const size_t page = (size_t)sysconf(_SC_PAGESIZE);
+    const size_t body = mode == 1 ? (n + 3) / 4 * 4 : n;   // high: a word past the request is the guard page already
+    const size_t body_pages = (body + page - 1) / page * page + (body == 0 ? page : 0);
+    char* base = (char*)mmap(nullptr, body_pages + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+    if (base == (char*)MAP_FAILED) return nullptr;
+    char* guard = mode == 1 ? base + body_pages : base;
+    char* first = mode == 1 ? base : base + page;
+    memset(first, 0xCD, body_pages);
+    if (mprotect(guard, page, PROT_NONE) != 0) { munmap(base, body_pages + page); return nullptr; }
+    void* p = mode == 1 ? (void*)(guard - body) : (void*)first;
+    std::lock_guard<std::mutex> lock(g_fenced_mu);
+    g_fenced[p] = Mapping{base, body_pages + page};
+    return p;
+}
+
+void emu_device_free(void* p)
+{
+    if (!p) return;
+    if (fence_mode() == 0) { free(p); return; }
+    std::lock_guard<std::mutex> lock(g_fenced_mu);
+    auto it = g_fenced.find(p);
+    if (it == g_fenced.end()) { fprintf(stderr, "emu: hipFree of %p, which hipMalloc did not return\n", p); abort(); }
+    munmap(it->second.base, it->second.bytes);
+    g_fenced.erase(it);
+}
 
 #define EMU_WAIT(what) do { Fiber& f_ = g_fibers[g_cur]; f_.wait = what; f_.wait_pc = __builtin_return_address(0); f_.hist[++f_.hist_n % 16] = f_.wait_pc; } while (0)
 
@@ -188,13 +259,17 @@ void emu_launch(const char* name, dim3 grid, dim3 block, const std::function<voi
                 unsigned long long spins = 0;
                 while (alive) {
                     alive = 0;
-                    for (unsigned t = 0; t < nthr; ++t) {
-                        Fiber& f = g_fibers[t];
-                        if (f.done) continue;
-                        g_cur = (int)t;
-                        threadIdx = dim3(t % block.x, (t / block.x) % block.y, t / (block.x * block.y));
-                        swapcontext(&g_main, &f.ctx);
-                        if (!f.done) ++alive;
+                    const unsigned nwaves = (nthr + 63) / 64;
+                    for (unsigned wi = 0; wi < nwaves; ++wi) {
+                        const unsigned wv = reverse_order() ? nwaves - 1 - wi : wi;
+                        for (unsigned t = wv * 64; t < nthr && t < (wv + 1) * 64; ++t) {
+                            Fiber& f = g_fibers[t];
+                            if (f.done) continue;
+                            g_cur = (int)t;
+                            threadIdx = dim3(t % block.x, (t / block.x) % block.y, t / (block.x * block.y));
+                            swapcontext(&g_main, &f.ctx);
+                            if (!f.done) ++alive;
+                        }
                     }
                     if (++spins > 300000ull) { fprintf(stderr, "emu: deadlock (divergent barrier?) in %s, workgroup %u of %u\n", name, bx, grid.x);
                         for (unsigned t = 0; t < nthr; ++t)

@@ -1,11 +1,27 @@
-// DEVELOPMENT HARNESS ONLY (tools/emu): a tiny single-threaded SIMT emulator that lets the unmodified
-// kernel sources under atracdenc_amd/csrc be compiled with g++ and stepped through on a CPU-only
-// machine (this build container has no GPU). It is NOT part of the product, is never shipped in
-// libat3hip.so, and no test or benchmark result is produced with it - it only shortens the
-// edit/debug loop for kernel *logic* (indexing, barriers, state machines) before a gpurun call.
+// TEST HARNESS (tools/emu): a tiny single-threaded SIMT emulator that lets the unmodified kernel sources under
+// atracdenc_amd/csrc be compiled for the host and stepped through lane by lane on a machine without a GPU. It is NOT part
+// of the product and is never shipped in libat3hip.so. Two test modules produce results with it,
+// tests/test_kernels_simt_harness.py (the encoders) and tests/test_decoders_simt_harness.py (the decoders and the resampler):
+// they are the parity gate of the GPU-less suite, and the run_emu*.py scripts next to this directory are their drivers. No
+// benchmark number is produced with it.
 //
 // Model: one workgroup at a time; each work-item is a ucontext fiber; __syncthreads() yields to a
 // round-robin scheduler. __shared__ becomes `static` (one workgroup alive at a time).
+//
+// Checks a GPU run does not make:
+//   * EMU_STRICT=1 (with the -O0 build): a cross-lane exchange reached from two different calls aborts (emu_runtime.cpp).
+//   * LDS is filled with 0xCD before every workgroup, every device allocation with 0xCD when it is made.
+//   * EMU_FENCE=high|low (read when the library loads; off by default): hipMalloc maps every allocation with an inaccessible
+//     page directly after it (high; the size is rounded up to 4 bytes only) or directly before it (low), hipFree unmaps it.
+//     A kernel that reads or writes one word outside a buffer ends the process with a signal. Host build only.
+//     Under `high` an allocation is therefore aligned to 4 bytes only, where hipMalloc gives 256: alignment is given up on
+//     purpose, since a buffer that ends at the page cannot also begin on a 16-byte boundary for every size. The float4 /
+//     int4 of this header are plain structs and the strict build is -O0, so no access here needs more; a kernel that
+//     comes to rely on a wider alignment of a device buffer would trap under `high` without being wrong.
+//   * EMU_ORDER=reverse (off by default): the scheduler visits the wavefronts of a workgroup in descending order (lanes
+//     inside a wavefront stay ascending: the hardware runs them in lockstep and the sources rely on it). A missing
+//     __syncthreads() between a low-numbered producer wavefront and a high-numbered consumer shows in one of the two
+//     orders; results must have identical bits in both.
 #pragma once
 #define AT3_EMU_HOST 1
 #include <ucontext.h>
@@ -30,6 +46,7 @@ struct float2 {
 struct float4 {
     float x, y, z, w;
 };
+static inline float2 make_float2(float x, float y) { float2 r; r.x = x; r.y = y; return r; }
 static inline float4 make_float4(float x, float y, float z, float w) { float4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
 
 
@@ -63,6 +80,7 @@ void emu_syncthreads();
 static inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 static inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 static inline unsigned int __umul24(unsigned int a, unsigned int b) { return (a & 0xffffffu) * (b & 0xffffffu); }
+static inline int min(int a, int b) { return b < a ? b : a; }
 static inline int __float2int_rn(float f) { return (int)lrintf(f); }
 static inline long long __double_as_longlong(double d) { long long v; memcpy(&v, &d, 8); return v; }
 static inline double __longlong_as_double(long long v) { double d; memcpy(&d, &v, 8); return d; }
@@ -97,11 +115,16 @@ static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuc
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)malloc(8); return hipSuccess; }
 static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0; return hipSuccess; }
-static inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); memset(*p, 0xCD, n); return *p ? hipSuccess : hipErrorUnknown; }
+// device allocations: poisoned with 0xCD, and under EMU_FENCE placed against a guard page (emu_runtime.cpp)
+// (C linkage: tools/emu/run_emu_decode.py allocates exactly-sized caller buffers with them, which the product's own
+// allocations, padded by dev_alloc, are not)
+extern "C" void* emu_device_alloc(size_t n);
+extern "C" void emu_device_free(void* p);
+static inline hipError_t hipMalloc(void** p, size_t n) { *p = emu_device_alloc(n); return *p ? hipSuccess : hipErrorUnknown; }
 #define hipHostMallocDefault 0u
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n); return *p ? hipSuccess : hipErrorUnknown; }
 static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
-static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+static inline hipError_t hipFree(void* p) { emu_device_free(p); return hipSuccess; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""DEVELOPMENT HARNESS: run the kernel sources through the CPU SIMT emulator (tools/emu) and diff
-against the oracle. Not a test, not a benchmark - only a debugging aid for a GPU-less container."""
+"""Run the ATRAC3 encoder's kernel sources through the CPU SIMT emulator (tools/emu) and diff against the oracle: the driver of
+tests/test_kernels_simt_harness.py, and a debugging aid on a machine without a GPU. build() compiles the harness library that
+the other run_emu*.py drivers load as well. Not a benchmark."""
 import ctypes, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -20,6 +21,7 @@ def build(strict=False):
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3hip.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/at1hip.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3phip.hip"),
+                           os.path.join(ROOT, "atracdenc_amd/csrc/resample.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3_tables.cpp"),
                            os.path.join(ROOT, "tools/emu/emu_runtime.cpp")])
 
