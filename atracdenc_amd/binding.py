@@ -50,7 +50,11 @@ SYMBOLS = ["at3hip_encode_s16", "at3hip_create", "at3hip_destroy", "at3hip_frame
            # the resampler (include/at3hip_resample.h, listed in at3hip.h's version notes)
            "at3hip_resampler_create", "at3hip_resampler_destroy", "at3hip_resampler_last_error", "at3hip_resampler_reset",
            "at3hip_resampler_max_out", "at3hip_resampler_process", "at3hip_resampler_flush", "at3hip_resampler_sync",
-           "at3hip_resampler_set_stream", "at3hip_resampler_shape", "at3hip_resampler_host_tables"]
+           "at3hip_resampler_set_stream", "at3hip_resampler_shape", "at3hip_resampler_host_tables",
+           # the loudness and true-peak meter (include/at3hip_loudness.h, listed in at3hip.h's version notes)
+           "at3hip_loudness_create", "at3hip_loudness_destroy", "at3hip_loudness_last_error", "at3hip_loudness_reset",
+           "at3hip_loudness_sync", "at3hip_loudness_set_stream", "at3hip_loudness_process", "at3hip_loudness_finish",
+           "at3hip_loudness_read_hops", "at3hip_loudness_apply", "at3hip_loudness_gate", "at3hip_loudness_gain"]
 AT3HIP_DECODE_S16 = 8
 # include/at1hip.h
 AT1_SYMBOLS = ["at1hip_create", "at1hip_destroy", "at1hip_last_error", "at1hip_encode", "at1hip_reset", "at1hip_get_timings",
@@ -115,6 +119,26 @@ class ResamplerConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("in_rate", "out_rate", "channels", "n_streams", "max_in", "device_id")]
 
 
+class LoudnessConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("channels", "n_streams", "max_in", "max_hops", "true_peak", "device_id")]
+
+
+class LoudnessResult(ctypes.Structure):
+    _fields_ = [("integrated", ctypes.c_double), ("momentary_max", ctypes.c_double), ("short_term_max", ctypes.c_double),
+                ("sample_peak", ctypes.c_float * 2), ("true_peak", ctypes.c_float * 2), ("n_samples", ctypes.c_int64),
+                ("n_hops", ctypes.c_int32), ("n_blocks_kept", ctypes.c_int32)]
+
+    def as_dict(self):
+        """plain Python values; sample_peak / true_peak as numpy float32 [2]"""
+        d = {n: getattr(self, n) for n in ("integrated", "momentary_max", "short_term_max", "n_samples", "n_hops", "n_blocks_kept")}
+        d["sample_peak"] = np.array(self.sample_peak[:], np.float32)
+        d["true_peak"] = np.array(self.true_peak[:], np.float32)
+        return d
+
+
+LOUDNESS_HOP = 4410
+
+
 class At1Timings(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("total_ms", "front_ms", "scan_ms", "pack_ms")]
 
@@ -123,7 +147,7 @@ def build_library(verbose=False):
     """Compile libat3hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fvisibility=hidden", "-fPIC", "-shared",
            "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-o", LIB_PATH, os.path.join(CSRC, "at3hip.hip"), os.path.join(CSRC, "at1hip.hip"), os.path.join(CSRC, "at3phip.hip"),
-           os.path.join(CSRC, "resample.hip"), os.path.join(CSRC, "at3_tables.cpp")]
+           os.path.join(CSRC, "resample.hip"), os.path.join(CSRC, "loudness.hip"), os.path.join(CSRC, "at3_tables.cpp")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -237,6 +261,16 @@ def load_library(path=None):
         lib.at3hip_resampler_destroy.restype = None
         lib.at3hip_resampler_last_error.restype = ctypes.c_char_p
         lib.at3hip_resampler_max_out.restype = i32
+    if hasattr(lib, "at3hip_loudness_create"):   # the loudness meter (added under ABI 1.6, see at3hip.h's version list)
+        f32p, resp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(LoudnessResult)
+        for name, argtypes in (("create", [ctypes.POINTER(LoudnessConfig), ctypes.POINTER(vp)]), ("destroy", [vp]),
+                               ("last_error", [vp]), ("reset", [vp]), ("sync", [vp]), ("set_stream", [vp, vp]),
+                               ("process", [vp, vp, i32, ctypes.c_uint32]), ("finish", [vp, resp]),
+                               ("read_hops", [vp, i32, vp, ctypes.c_size_t]), ("apply", [vp, vp, i32, vp, vp, ctypes.c_uint32]),
+                               ("gate", [vp, i32, i32, resp]), ("gain", [resp, ctypes.c_double, ctypes.c_double, f32p])):
+            getattr(lib, "at3hip_loudness_" + name).argtypes = argtypes
+        lib.at3hip_loudness_destroy.restype = None
+        lib.at3hip_loudness_last_error.restype = ctypes.c_char_p
     _lib_cache[path] = lib
     return lib
 
@@ -887,3 +921,116 @@ class HipResampler(_Context):
         self._device_out(out, out.device)
         _Decoder._order_behind_torch(self, out.device, ordered)
         return self.flush_ptr(out.data_ptr(), AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0))
+
+
+def _loudness_lib(lib_path):
+    lib = load_library(lib_path)
+    if not hasattr(lib, "at3hip_loudness_create"):
+        raise At3HipError("libat3hip.so predates the loudness meter (no at3hip_loudness_create): rebuild it")
+    return lib
+
+
+def loudness_gate(z, lib_path=None):
+    """at3hip_loudness_gate (no GPU): hop sums z float64 [n_hops][channels] -> LoudnessResult with integrated, momentary_max,
+    short_term_max, n_hops and n_blocks_kept set (peaks and n_samples zero)."""
+    z = np.ascontiguousarray(z, np.float64)
+    assert z.ndim == 2 and z.shape[1] in (1, 2), z.shape
+    r = LoudnessResult()
+    rc = _loudness_lib(lib_path).at3hip_loudness_gate(_vp(z), z.shape[0], z.shape[1], ctypes.byref(r))
+    if rc != 0:
+        raise At3HipError(f"at3hip_loudness_gate failed ({rc})")
+    return r
+
+
+def loudness_gain(result, target_lufs, ceiling_db=-1.0, lib_path=None):
+    """at3hip_loudness_gain (no GPU): the float32 gain that brings `result` (a LoudnessResult) to target_lufs with its peak
+    (the true peak if it was measured, else the sample peak) at or below ceiling_db dBFS; 1.0 for a stream without loudness."""
+    g = ctypes.c_float()
+    if not isinstance(result, LoudnessResult):   # (a structure of the same layout)
+        result = LoudnessResult.from_buffer_copy(bytes(result))
+    rc = _loudness_lib(lib_path).at3hip_loudness_gain(ctypes.byref(result), float(target_lufs), float(ceiling_db), ctypes.byref(g))
+    if rc != 0:
+        raise At3HipError(f"at3hip_loudness_gain failed ({rc})")
+    return np.float32(g.value)
+
+
+class HipLoudness(_Context):
+    """n_streams streams of 1 or 2 channels at 44.1 kHz metered side by side on one GPU (include/at3hip_loudness.h): BS.1770
+    hop sums, sample peak and, with true_peak=True, the 4x oversampled peak; finish() gates on the host. Every stream of a call
+    takes the same number of samples.
+
+    Stream ordering (at3hip.h, DEVICE BUFFERS AND STREAMS): the meter reads and writes device buffers on its own non-blocking
+    stream, which waits for no other stream. The *_device methods therefore queue the call on torch's current stream by
+    default (ordered=True, through at3hip_loudness_set_stream; on the null stream they wait for it instead); with ordered=False
+    whatever produces the buffer must be complete before the call. With asynchronous=True the buffers must stay valid until
+    sync() or finish()."""
+
+    _PREFIX = "at3hip_loudness"
+
+    def __init__(self, channels=2, n_streams=1, max_in=1 << 16, max_hops=36000, true_peak=False, device_id=0, lib_path=None):
+        self.lib = _loudness_lib(lib_path)
+        self.channels, self.n_streams, self.max_in, self.max_hops = int(channels), int(n_streams), int(max_in), int(max_hops)
+        self.true_peak = bool(true_peak)
+        self.n_samples = 0   # per stream since the start / the last finish() or reset()
+        self._create(LoudnessConfig(self.channels, self.n_streams, self.max_in, self.max_hops, int(self.true_peak), int(device_id)),
+                     "unsupported configuration, or no usable MI355X / HIP runtime")
+
+    def reset(self):
+        self._call("reset")
+        self.n_samples = 0
+
+    def process_ptr(self, in_ptr, n_in, flags):
+        """Raw pointer and at3hip_loudness_process flags."""
+        self._call("process", ctypes.c_void_p(in_ptr), int(n_in), int(flags))
+        self.n_samples += int(n_in)
+
+    def process(self, pcm):
+        """pcm float32 [n_streams, n_in, channels] (host)"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
+        self.process_ptr(pcm.ctypes.data, pcm.shape[1], 0)
+
+    def process_device(self, pcm, asynchronous=False, ordered=True):
+        """pcm: torch float32 [n_streams, n_in, channels] on this meter's device (see the class docstring for the ordering)."""
+        import torch
+        assert pcm.dtype == torch.float32 and pcm.is_contiguous()
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, tuple(pcm.shape)
+        _Decoder._order_behind_torch(self, pcm.device, ordered)
+        self.process_ptr(pcm.data_ptr(), pcm.shape[1], AT3HIP_PCM_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0))
+
+    def hops(self):
+        """the hop sums so far, float64 [n_streams, n_hops, channels] (at3hip_loudness_read_hops; waits for queued work)"""
+        out = np.zeros((self.n_streams, self.n_samples // LOUDNESS_HOP, self.channels), np.float64)
+        for s in range(self.n_streams):
+            self._call("read_hops", s, _vp(out[s]), out[s].nbytes)
+        return out
+
+    def finish(self):
+        """Waits, gates, and returns one LoudnessResult per stream; the meter is then at its start state."""
+        res = (LoudnessResult * self.n_streams)()
+        self._call("finish", res)
+        self.n_samples = 0
+        return list(res)
+
+    def apply_ptr(self, in_ptr, n_in, gains, out_ptr, flags):
+        gains = np.ascontiguousarray(gains, np.float32)
+        assert gains.shape == (self.n_streams,), gains.shape
+        self._call("apply", ctypes.c_void_p(in_ptr), int(n_in), _vp(gains), ctypes.c_void_p(out_ptr), int(flags))
+
+    def apply(self, pcm, gains):
+        """pcm float32 [n_streams, n_in, channels] (host), gains float32 [n_streams] -> pcm * gains[:, None, None] as float32"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
+        out = np.zeros_like(pcm)
+        self.apply_ptr(pcm.ctypes.data, pcm.shape[1], gains, out.ctypes.data, 0)
+        return out
+
+    def apply_device(self, pcm, gains, out, asynchronous=False, ordered=True):
+        """Torch tensors on this meter's device: out = pcm * gains[stream] (out may be pcm); ordering as process_device."""
+        import torch
+        assert pcm.dtype == torch.float32 and pcm.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous()
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, tuple(pcm.shape)
+        assert out.device == pcm.device and out.numel() >= pcm.numel()
+        _Decoder._order_behind_torch(self, pcm.device, ordered)
+        self.apply_ptr(pcm.data_ptr(), pcm.shape[1], gains, out.data_ptr(),
+                       AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0))

@@ -34,6 +34,7 @@
 
 #include "../../include/at1hip.h"
 #include "../../include/at3hip.h"
+#include "../../include/at3hip_loudness.h"
 #include "../../include/at3hip_resample.h"
 #include "../../include/at3phip.h"
 
@@ -519,6 +520,8 @@ public:
         for (int i = 0; i < nf; ++i)
             Oma->WriteFrame(std::vector<char>(frames.begin() + (size_t)i * fsz, frames.begin() + (size_t)(i + 1) * fsz));
     }
+    // TScaler::Scale's overflow diagnostics for what has been encoded so far (TAtrac3EncoderBatch::Counters)
+    at3hip_counters Counters() { return Batch.Counters(); }
 
 private:
     TCompressedOutputPtr Oma;
@@ -782,6 +785,99 @@ private:
     size_t Pos = 0;
     uint64_t Total = 0;
     bool Done = false;
+};
+
+// ---- loudness and peak (include/at3hip_loudness.h) ------------------------------------------------------------------------
+// One at3hip_loudness of one stream, owned: Process the 44.1 kHz samples the encoder will see, Finish, then Gain gives the one
+// constant that brings the stream to a target loudness under a peak ceiling, and Apply multiplies by it.
+class TLoudnessMeter {
+public:
+    static constexpr int kChunk = 1 << 16;
+
+    // maxSamples: the most samples Process will see before Finish (bounds the hops the context keeps)
+    TLoudnessMeter(int channels, uint64_t maxSamples, bool truePeak, int device) : Channels(channels)
+    {
+        CheckLibraryVersion();
+        at3hip_loudness_config cfg{channels, 1, kChunk, (int32_t)(maxSamples / AT3HIP_LOUDNESS_HOP + 1), truePeak ? 1 : 0, device};
+        const int rc = at3hip_loudness_create(&cfg, &L);
+        if (rc != AT3HIP_OK) throw std::runtime_error("at3hip_loudness_create failed (" + std::to_string(rc) + ")");
+    }
+    ~TLoudnessMeter()
+    {
+        if (L) at3hip_loudness_destroy(L);
+    }
+    TLoudnessMeter(const TLoudnessMeter&) = delete;
+    TLoudnessMeter& operator=(const TLoudnessMeter&) = delete;
+
+    // n sample frames of interleaved input
+    void Process(const float* in, size_t n)
+    {
+        for (size_t at = 0; at < n; at += kChunk)
+            Check(at3hip_loudness_process(L, in + at * Channels, (int32_t)std::min<size_t>(kChunk, n - at), 0));
+    }
+    // every sample of a source (GetChannelNum / Read as TWavSource)
+    template <class TSrc>
+    void ProcessAll(TSrc& src)
+    {
+        std::vector<float> buf((size_t)kChunk * Channels);
+        while (const size_t n = src.Read(buf.data(), kChunk)) Process(buf.data(), n);
+    }
+    at3hip_loudness_result Finish()
+    {
+        at3hip_loudness_result r{};
+        Check(at3hip_loudness_finish(L, &r));
+        return r;
+    }
+    static float Gain(const at3hip_loudness_result& r, double targetLufs, double ceilingDb)
+    {
+        float g = 1.0f;
+        at3hip_loudness_gain(&r, targetLufs, ceilingDb, &g);
+        return g;
+    }
+    // the peak the gain rule uses: the larger channel's true peak if it was measured, else the larger sample peak
+    static float Peak(const at3hip_loudness_result& r)
+    {
+        const bool measured = r.true_peak[0] != 0.0f || r.true_peak[1] != 0.0f;
+        const float* p = measured ? r.true_peak : r.sample_peak;
+        return std::max(p[0], p[1]);
+    }
+    // pcm[i] *= g for n sample frames, on the GPU
+    void Apply(float* pcm, size_t n, float g)
+    {
+        for (size_t at = 0; at < n; at += kChunk)
+            Check(at3hip_loudness_apply(L, pcm + at * Channels, (int32_t)std::min<size_t>(kChunk, n - at), &g, pcm + at * Channels, 0));
+    }
+
+private:
+    void Check(int rc)
+    {
+        if (rc != AT3HIP_OK) throw std::runtime_error(std::string("at3hip_loudness: ") + at3hip_loudness_last_error(L));
+    }
+    at3hip_loudness* L = nullptr;
+    int Channels;
+};
+
+// A PCM source times one constant (TLoudnessMeter::Apply). TSrc as for TResampledSource, and so is this: with both in use this
+// one sits behind the converter, so that the samples scaled are the 44.1 kHz samples that were metered.
+template <class TSrc>
+class TScaledSource {
+public:
+    TScaledSource(TSrc& src, float gain, int device) : Src(src), Gain(gain), Meter((int)src.GetChannelNum(), 0, false, device) {}
+
+    size_t GetChannelNum() const { return Src.GetChannelNum(); }
+    size_t GetSampleRate() const { return Src.GetSampleRate(); }
+    uint64_t GetTotalSamples() const { return Src.GetTotalSamples(); }
+    size_t Read(float* dst, size_t frames)
+    {
+        const size_t n = Src.Read(dst, frames);
+        Meter.Apply(dst, n, Gain);
+        return n;
+    }
+
+private:
+    TSrc& Src;
+    float Gain;
+    TLoudnessMeter Meter;
 };
 
 }  // namespace NAtracDEncHip

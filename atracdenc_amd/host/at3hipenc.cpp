@@ -11,6 +11,12 @@
 //             [--batch frames] [--device n]
 //   --resample (all three encoders): a WAV at 8 .. 192 kHz (at3hip_resample.h's list) is converted to 44.1 kHz on the GPU
 //             first; the container headers count ceil(N 44100 / rate) samples. A 44.1 kHz input is encoded as without it.
+//   --loudness LUFS [--peak dBFS] [--truepeak] (all three encoders): pass one meters the 44.1 kHz samples the encoder will see
+//             (after --resample) on the GPU (at3hip_loudness.h: BS.1770 integrated loudness, sample peak or with --truepeak the 4x
+//             oversampled peak), pass two encodes them times the one gain that reaches the target with the peak at or below
+//             --peak (default -1.0). Prints `loudness: I <x> LUFS, peak <y> dBFS, gain <z> dB` unless --nostdout, and for atrac3
+//             `clipping: <n> blocks, <m> values` after the encode (at3hip_get_counters).
+//   at3hipenc --measure -i in.wav [--resample] [--truepeak]: prints the meter's result and writes nothing.
 //   --rate hz (every decoder): the decoded audio is converted to hz (at3hip_resample.h's list) on the GPU, clamped to [-1, 1] and
 //             written as lrintf(x * 32767.0f); the WAV counts ceil(N hz / 44100) samples. --rate 44100 writes what -d writes alone.
 //   at3hipenc -d -i in.aea -o out.wav [--nostdout] [--batch frames] [--device n]
@@ -89,11 +95,11 @@ void write_wav_header(std::ofstream& out, uint32_t nch, uint32_t dataBytes, uint
 
 // The encoders' input: the WAV file at 44.1 kHz, or with --resample a WAV file at any rate at3hip_resample.h supports, converted
 // to 44.1 kHz on the GPU (TResampledSource). Without the flag any other rate is refused, as the reference refuses it (main.cpp:281).
-struct TEncodeInput {
+struct TRateInput {
     TWavSource File;
     std::unique_ptr<TResampledSource<TWavSource>> Conv;
 
-    TEncodeInput(const std::string& path, bool resample, int device) : File(path)
+    TRateInput(const std::string& path, bool resample, int device) : File(path)
     {
         if (File.GetSampleRate() == 44100) return;
         if (!resample) throw std::runtime_error("unsupported sample rate");
@@ -103,6 +109,50 @@ struct TEncodeInput {
     size_t GetSampleRate() const { return Conv ? Conv->GetSampleRate() : File.GetSampleRate(); }
     uint64_t GetTotalSamples() const { return Conv ? Conv->GetTotalSamples() : File.GetTotalSamples(); }   // ceil(N 44100 / in)
     size_t Read(float* dst, size_t frames) { return Conv ? Conv->Read(dst, frames) : File.Read(dst, frames); }
+};
+
+// --loudness / --peak / --truepeak
+struct TLevel {
+    bool On = false, TruePeak = false, NoStdOut = false;
+    double Target = 0.0, Ceiling = -1.0;
+};
+
+// Pass one of --loudness, and all of --measure: the 44.1 kHz samples an encoder would see (after --resample) through the meter
+// (at3hip_loudness.h).
+at3hip_loudness_result measure_input(const std::string& path, bool resample, int device, bool truePeak)
+{
+    TRateInput in(path, resample, device);
+    TLoudnessMeter meter((int)in.GetChannelNum(), in.GetTotalSamples(), truePeak, device);
+    meter.ProcessAll(in);
+    return meter.Finish();
+}
+
+double db_of(double linear) { return 20.0 * std::log10(linear); }
+
+// The encoders' input with --loudness: pass one meters the file, pass two (this object's Read) hands the encoder the same
+// samples times the one gain that brings them to the target loudness with the peak at or below the ceiling (TScaledSource
+// behind the converter). Without the flag this is TRateInput.
+struct TEncodeInput {
+    TRateInput Base;
+    std::unique_ptr<TScaledSource<TRateInput>> Scaled;
+
+    TEncodeInput(const std::string& path, bool resample, int device, const TLevel& level) : Base(path, resample, device)
+    {
+        if (!level.On) return;
+        const at3hip_loudness_result r = measure_input(path, resample, device, level.TruePeak);
+        const float g = TLoudnessMeter::Gain(r, level.Target, level.Ceiling);
+        if (!level.NoStdOut) {
+            char line[160];
+            snprintf(line, sizeof(line), "loudness: I %.2f LUFS, peak %.2f dBFS, gain %.2f dB", r.integrated,
+                     db_of((double)TLoudnessMeter::Peak(r)), db_of((double)g));
+            std::cout << line << std::endl;
+        }
+        Scaled.reset(new TScaledSource<TRateInput>(Base, g, device));
+    }
+    size_t GetChannelNum() const { return Base.GetChannelNum(); }
+    size_t GetSampleRate() const { return Base.GetSampleRate(); }
+    uint64_t GetTotalSamples() const { return Base.GetTotalSamples(); }
+    size_t Read(float* dst, size_t frames) { return Scaled ? Scaled->Read(dst, frames) : Base.Read(dst, frames); }
 };
 
 // `-d ... --rate <hz>`: the decoder's float output (44.1 kHz, already clamped) converted to another rate on the GPU
@@ -539,6 +589,8 @@ static int usage()
                  "                 [--container aea|raw] [--nostdout] [--batch blocks] [--device n]\n"
                  "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
                  "       (every encoder: --resample converts an input at 8 .. 192 kHz to 44.1 kHz first)\n"
+                 "       (every encoder: --loudness LUFS [--peak dBFS] [--truepeak] brings the input to a programme loudness first)\n"
+                 "       at3hipenc --measure -i in.wav [--resample] [--truepeak]   (prints loudness and peaks, writes nothing)\n"
                  "       at3hipenc -d -i in.aea -o out.wav [--nostdout] [--batch frames] [--device n]\n"
                  "       at3hipenc -d -i in.{oma|at3|wav} -o out.wav [--nostdout] [--batch frames] [--device n]   (ATRAC3 / ATRAC3plus, by content)\n"
                  "       (every decoder: --rate hz writes the WAV at 8 .. 192 kHz instead of 44.1 kHz)\n";
@@ -552,6 +604,8 @@ int main(int argc, char** argv)
     bool noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false, resample = false;
     uint32_t winMask = 0;
     int batch = 256, device = 0, rate = 0;
+    bool measure = false, peakGiven = false;
+    TLevel level;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](const char* what) -> const char* {
@@ -571,6 +625,16 @@ int main(int argc, char** argv)
         else if (a == "--nogaincontrol") noGain = true;
         else if (a == "--nostdout") noStdOut = true;
         else if (a == "--resample") resample = true;
+        else if (a == "--loudness") {
+            level.On = true;
+            level.Target = atof(need("--loudness"));
+        }
+        else if (a == "--peak") {
+            peakGiven = true;
+            level.Ceiling = atof(need("--peak"));
+        }
+        else if (a == "--truepeak") level.TruePeak = true;
+        else if (a == "--measure") measure = true;
         else if (a == "--rate") {   // a positive decimal number, else refused below as an unsupported rate
             const char* v = need("--rate");
             rateArg = v;
@@ -587,8 +651,25 @@ int main(int argc, char** argv)
         else if (a == "--device") device = atoi(need("--device"));
         else return usage();
     }
+    level.NoStdOut = noStdOut;
+    if (measure) {   // prints the meter's result, writes nothing
+        if (decode || !codec.empty() || inFile.empty() || !outFile.empty() || level.On || peakGiven || rate) return usage();
+        try {
+            const at3hip_loudness_result r = measure_input(inFile, resample, device, level.TruePeak);
+            char line[256];
+            int n = snprintf(line, sizeof(line), "loudness: I %.2f LUFS, M max %.2f LUFS, S max %.2f LUFS, sample peak %.2f dBFS", r.integrated,
+                             r.momentary_max, r.short_term_max, db_of((double)std::max(r.sample_peak[0], r.sample_peak[1])));
+            if (level.TruePeak)
+                snprintf(line + n, sizeof(line) - (size_t)n, ", true peak %.2f dBFS", db_of((double)std::max(r.true_peak[0], r.true_peak[1])));
+            std::cout << line << std::endl;
+        } catch (const std::exception& ex) {
+            std::cerr << "Fatal error: " << ex.what() << std::endl;
+            return 1;
+        }
+        return 0;
+    }
     if (decode) {
-        if (!codec.empty() || inFile.empty() || outFile.empty()) return usage();
+        if (!codec.empty() || inFile.empty() || outFile.empty() || level.On || peakGiven || level.TruePeak) return usage();
         TAt3Input at3;
         const EInput kind = probe_input(inFile, at3);
         if (kind == EInput::REFUSED) return 1;
@@ -607,9 +688,10 @@ int main(int argc, char** argv)
         }
     }
     if ((codec != "atrac3" && codec != "atrac1" && codec != "atrac3plus") || inFile.empty() || outFile.empty() || rate) return usage();
+    if (!level.On && (peakGiven || level.TruePeak)) return usage();   // --peak and --truepeak belong to --loudness (or --measure)
     if (codec == "atrac3plus") {
         try {
-            TEncodeInput wav(inFile, resample, device);
+            TEncodeInput wav(inFile, resample, device, level);
             const size_t numChannels = wav.GetChannelNum();
             const uint64_t totalSamples = wav.GetTotalSamples();
             const uint64_t numFrames = totalSamples / 2048;   // main.cpp:440
@@ -648,7 +730,7 @@ int main(int argc, char** argv)
             return 1;
         }
         try {
-            TEncodeInput wav(inFile, resample, device);
+            TEncodeInput wav(inFile, resample, device, level);
             const size_t numChannels = wav.GetChannelNum();
             const uint64_t totalSamples = wav.GetTotalSamples();
             const uint64_t numFrames = numChannels * totalSamples / 512;   // main.cpp:312
@@ -694,7 +776,7 @@ int main(int argc, char** argv)
         return 1;
     }
     try {
-        TEncodeInput wav(inFile, resample, device);
+        TEncodeInput wav(inFile, resample, device, level);
         const size_t numChannels = wav.GetChannelNum();
         const uint64_t totalSamples = wav.GetTotalSamples();
         const uint64_t numFrames = totalSamples / 1024;
@@ -743,6 +825,10 @@ int main(int argc, char** argv)
             std::cerr << "No more data to read from input" << std::endl;
         }
         encoder.Flush();
+        if (level.On && !noStdOut) {   // what TScaler::Scale would still have clamped after the gain (at3hip_get_counters)
+            const at3hip_counters c = encoder.Counters();
+            std::cout << "clipping: " << c.scale_overflow << " blocks, " << c.clipped_values << " values" << std::endl;
+        }
         if (!noStdOut) std::cout << "\nDone" << std::endl;
     } catch (const std::exception& ex) {
         std::cerr << "Fatal error: " << ex.what() << std::endl;

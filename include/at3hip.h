@@ -386,6 +386,10 @@ int at3hip_decoder_set_stream(at3hip_decoder* dec, void* hip_stream);
  *        at3hip_resampler_destroy(), at3hip_resampler_last_error(), at3hip_resampler_reset(), at3hip_resampler_max_out(),
  *        at3hip_resampler_process(), at3hip_resampler_flush(), at3hip_resampler_sync(), at3hip_resampler_set_stream(),
  *        at3hip_resampler_shape(), at3hip_resampler_host_tables() (detected by the symbol at3hip_resampler_create)
+ *        and, added later under the same number, the loudness and true-peak meter (at3hip_loudness.h): at3hip_loudness_create(),
+ *        at3hip_loudness_destroy(), at3hip_loudness_last_error(), at3hip_loudness_reset(), at3hip_loudness_sync(),
+ *        at3hip_loudness_set_stream(), at3hip_loudness_process(), at3hip_loudness_finish(), at3hip_loudness_read_hops(),
+ *        at3hip_loudness_apply(), at3hip_loudness_gate(), at3hip_loudness_gain() (detected by the symbol at3hip_loudness_create)
  * A host layer compiled against this header checks at3hip_version() >= AT3HIP_VERSION before it relies on them
  * (atracdenc_amd/host/at3hip_host.hpp and the ctypes stub do). */
 #define AT3HIP_VERSION_MAJOR 1
