@@ -91,9 +91,7 @@ int at1hip_create(const at1hip_config* cfg, at1hip_ctx** out)
     if (!host_tables) return bail(AT3HIP_ENOMEM);
     build_tables(host_tables);
     rc = dev_alloc(c, &c->d_tables, 1);
-    if (rc == AT3HIP_OK && (hipMemcpy(c->d_tables, host_tables, sizeof(Tables), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipDeviceSynchronize() != hipSuccess))   // (pageable source: the transfer may still be running when the copy returns, at3hip_create)
-        rc = AT3HIP_EDEVICE;
+    if (rc == AT3HIP_OK) rc = at3host::upload_table(c->d_tables, host_tables, sizeof(Tables));
     delete host_tables;
     if (rc != AT3HIP_OK) return bail(rc);
 
@@ -358,13 +356,13 @@ int at1hip_decoder_create(const at1hip_decoder_config* cfg, at1hip_decoder** out
 void at1hip_decoder_destroy(at1hip_decoder* d)
 {
     if (d)
-        at3host::destroy_decoder(d, {d->d_tables, d->d_units, d->d_raw, d->d_tails, d->d_modes, d->d_lw, d->d_st_band, d->d_st_tail,
+        at3host::destroy_engine(d, {d->d_tables, d->d_units, d->d_raw, d->d_tails, d->d_modes, d->d_lw, d->d_st_band, d->d_st_tail,
                                      d->d_rejected, d->d_out});
 }
 
-const char* at1hip_decoder_last_error(const at1hip_decoder* d) { return at3host::decoder_last_error(d); }
+const char* at1hip_decoder_last_error(const at1hip_decoder* d) { return at3host::engine_last_error(d); }
 
-int at1hip_decoder_sync(at1hip_decoder* d) { return at3host::decoder_sync(d); }
+int at1hip_decoder_sync(at1hip_decoder* d) { return at3host::engine_sync(d); }
 
 int at1hip_decoder_reset(at1hip_decoder* d)
 {
@@ -374,7 +372,7 @@ int at1hip_decoder_reset(at1hip_decoder* d)
     return dec_reset_state(d);
 }
 
-int at1hip_decoder_set_stream(at1hip_decoder* d, void* hip_stream) { return at3host::decoder_set_stream(d, hip_stream); }
+int at1hip_decoder_set_stream(at1hip_decoder* d, void* hip_stream) { return at3host::engine_set_stream(d, hip_stream); }
 
 int at1hip_decoder_get_counters(at1hip_decoder* d, at1hip_decoder_counters* out, int32_t reset)
 {
@@ -434,7 +432,7 @@ int at1hip_decode(at1hip_decoder* d, const uint8_t* units, int32_t n_frames, voi
     HIPCHK(d, hipGetLastError());
     if (!(flags & AT3HIP_OUT_ON_DEVICE))
         HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 512 * C * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
-    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::decoder_sync(d);
+    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::engine_sync(d);
 }
 
 }  // extern "C"

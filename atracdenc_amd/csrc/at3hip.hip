@@ -1410,12 +1410,12 @@ int at3hip_decoder_create(const at3hip_decoder_config* cfg, at3hip_decoder** out
 
 void at3hip_decoder_destroy(at3hip_decoder* d)
 {
-    if (d) at3host::destroy_decoder(d, {d->d_tables, d->d_frames, d->d_raw, d->d_gains, d->d_rejected, d->d_out});
+    if (d) at3host::destroy_engine(d, {d->d_tables, d->d_frames, d->d_raw, d->d_gains, d->d_rejected, d->d_out});
 }
 
-const char* at3hip_decoder_last_error(const at3hip_decoder* d) { return at3host::decoder_last_error(d); }
+const char* at3hip_decoder_last_error(const at3hip_decoder* d) { return at3host::engine_last_error(d); }
 
-int at3hip_decoder_sync(at3hip_decoder* d) { return at3host::decoder_sync(d); }
+int at3hip_decoder_sync(at3hip_decoder* d) { return at3host::engine_sync(d); }
 
 int at3hip_decoder_reset(at3hip_decoder* d)
 {
@@ -1425,7 +1425,7 @@ int at3hip_decoder_reset(at3hip_decoder* d)
     return dec3_reset_state(d);
 }
 
-int at3hip_decoder_set_stream(at3hip_decoder* d, void* hip_stream) { return at3host::decoder_set_stream(d, hip_stream); }
+int at3hip_decoder_set_stream(at3hip_decoder* d, void* hip_stream) { return at3host::engine_set_stream(d, hip_stream); }
 
 int at3hip_decoder_get_counters(at3hip_decoder* d, at3hip_decoder_counters* out, int32_t reset)
 {
@@ -1485,7 +1485,7 @@ int at3hip_decode(at3hip_decoder* d, const uint8_t* frames, int32_t n_frames, vo
     HIPCHK(d, hipGetLastError());
     if (!(flags & AT3HIP_OUT_ON_DEVICE))
         HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 2048 * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
-    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::decoder_sync(d);
+    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::engine_sync(d);
 }
 
 }  // extern "C"

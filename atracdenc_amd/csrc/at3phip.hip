@@ -149,9 +149,7 @@ int at3phip_create(const at3phip_config* cfg, at3phip_ctx** out)
     if (!host_tables) return bail(AT3HIP_ENOMEM);
     build_tables(host_tables);
     rc = dev_alloc(c, &c->d_tables, 1);
-    if (rc == AT3HIP_OK && (hipMemcpy(c->d_tables, host_tables, sizeof(Tables), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipDeviceSynchronize() != hipSuccess))   // (pageable source: the transfer may still be running when the copy returns, at3hip_create)
-        rc = AT3HIP_EDEVICE;
+    if (rc == AT3HIP_OK) rc = at3host::upload_table(c->d_tables, host_tables, sizeof(Tables));
     delete host_tables;
     if (rc != AT3HIP_OK) return bail(rc);
     const size_t S = cfg->n_streams, F = cfg->max_frames, C = cfg->channels;
@@ -174,7 +172,7 @@ int at3phip_create(const at3phip_config* cfg, at3phip_ctx** out)
         if (!wt) return bail(AT3HIP_ENOMEM);
         build_write_tables(wt);
         rc = dev_alloc(c, &c->d_wtables, 1);
-        if (rc == AT3HIP_OK && (hipMemcpy(c->d_wtables, wt, sizeof(WriteTables), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) rc = AT3HIP_EDEVICE;
+        if (rc == AT3HIP_OK) rc = at3host::upload_table(c->d_wtables, wt, sizeof(WriteTables));
         delete wt;
         if (rc != AT3HIP_OK) return bail(rc);
     }
@@ -551,13 +549,13 @@ int at3phip_decoder_create(const at3phip_decoder_config* cfg, at3phip_decoder** 
 
 void at3phip_decoder_destroy(at3phip_decoder* d)
 {
-    if (d) at3host::destroy_decoder(d, {d->d_tables, d->d_frames, d->d_raw, d->d_flags, d->d_rejected, d->d_out, d->d_tonal,
+    if (d) at3host::destroy_engine(d, {d->d_tables, d->d_frames, d->d_raw, d->d_flags, d->d_rejected, d->d_out, d->d_tonal,
                                             d->d_tone_tables});
 }
 
-const char* at3phip_decoder_last_error(const at3phip_decoder* d) { return at3host::decoder_last_error(d); }
+const char* at3phip_decoder_last_error(const at3phip_decoder* d) { return at3host::engine_last_error(d); }
 
-int at3phip_decoder_sync(at3phip_decoder* d) { return at3host::decoder_sync(d); }
+int at3phip_decoder_sync(at3phip_decoder* d) { return at3host::engine_sync(d); }
 
 int at3phip_decoder_reset(at3phip_decoder* d)
 {
@@ -567,7 +565,7 @@ int at3phip_decoder_reset(at3phip_decoder* d)
     return decp_reset_state(d);
 }
 
-int at3phip_decoder_set_stream(at3phip_decoder* d, void* hip_stream) { return at3host::decoder_set_stream(d, hip_stream); }
+int at3phip_decoder_set_stream(at3phip_decoder* d, void* hip_stream) { return at3host::engine_set_stream(d, hip_stream); }
 
 int at3phip_decoder_get_counters(at3phip_decoder* d, at3phip_decoder_counters* out, int32_t reset)
 {
@@ -635,7 +633,7 @@ int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, 
     HIPCHK(d, hipGetLastError());
     if (!(flags & AT3HIP_OUT_ON_DEVICE))
         HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 2048 * C * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
-    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::decoder_sync(d);
+    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::engine_sync(d);
 }
 
 int at3phip_decoder_host_tables(void* dst, size_t bytes)

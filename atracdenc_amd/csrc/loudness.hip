@@ -22,7 +22,6 @@
 // Every index that scales with the batch is 64-bit. The f64 path holds no FMA (-ffp-contract=off) and no kernel uses scratch.
 #include <cmath>
 #include <cstring>
-#include <new>
 #include <type_traits>
 #include <vector>
 
@@ -380,11 +379,8 @@ __attribute__((optnone, noinline)) float gain_of(const at3hip_loudness_result* r
 
 }  // namespace
 
-struct at3hip_loudness {
+struct at3hip_loudness : at3host::EngineBase {
     at3hip_loudness_config cfg;
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;            // own_stream, or the caller's (at3hip_loudness_set_stream)
     float* d_carry[2] = {nullptr, nullptr};  // [S][kWindow][C], read / written alternately
     int cur = 0;
     double* d_z = nullptr;                   // [max_hops][S][C]
@@ -395,25 +391,11 @@ struct at3hip_loudness {
     float* d_out = nullptr;                  // staging for at3hip_loudness_apply's host output, likewise
     long long t = 0;                         // samples received per stream since the start
     long long q_done = 0;                    // q below this have had their four outputs taken (true_peak)
-    char err[256] = {0};
 };
 
 namespace {
 
 long long carry_base(long long t) { const long long h = t / kHop; return kHop * (h > 2 ? h - 2 : 0); }
-
-void destroy(at3hip_loudness* l)
-{
-    {
-        at3host::DeviceGuard guard(l->device);
-        if (l->stream) (void)hipStreamSynchronize(l->stream);
-        for (void* b : {(void*)l->d_carry[0], (void*)l->d_carry[1], (void*)l->d_z, (void*)l->d_peaks, (void*)l->d_hp, (void*)l->d_gain,
-                        (void*)l->d_in, (void*)l->d_out})
-            if (b) (void)hipFree(b);
-        if (l->own_stream) (void)hipStreamDestroy(l->own_stream);
-    }
-    delete l;
-}
 
 int clear_state(at3hip_loudness* l)
 {
@@ -515,46 +497,31 @@ int at3hip_loudness_create(const at3hip_loudness_config* cfg, at3hip_loudness** 
         (cfg->true_peak != 0 && cfg->true_peak != 1))
         return AT3HIP_EINVAL;
     if (cfg->n_streams > at3host::kMaxGridY) return AT3HIP_EINVAL;   // the stream is gridDim.y
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return AT3HIP_EDEVICE;
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return AT3HIP_EINVAL;
-    at3hip_loudness* l = new (std::nothrow) at3hip_loudness();
-    if (!l) return AT3HIP_ENOMEM;
-    l->cfg = *cfg;
-    l->device = cfg->device_id;
-    auto bail = [&](int code) {
-        destroy(l);
-        return code;
-    };
-    at3host::DeviceGuard guard(l->device);
-    if (guard.error() != hipSuccess) return bail(AT3HIP_EDEVICE);
-    if (hipStreamCreateWithFlags(&l->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    l->stream = l->own_stream;
-    const size_t S = cfg->n_streams, C = cfg->channels;
-    int rc;
-    for (int b = 0; b < 2; ++b)
-        if ((rc = dev_alloc(l, &l->d_carry[b], S * kWindow * C)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(l, &l->d_z, (size_t)cfg->max_hops * S * C)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(l, &l->d_peaks, S * 4)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(l, &l->d_gain, S)) != AT3HIP_OK) return bail(rc);
-    if (cfg->true_peak) {
-        float host[kPhases * kTaps];
-        if (at3hip_resampler_host_tables(44100, 176400, host, sizeof(host)) != AT3HIP_OK) return bail(AT3HIP_EINVAL);
-        if ((rc = dev_alloc(l, &l->d_hp, (size_t)kPhases * kTaps)) != AT3HIP_OK) return bail(rc);
-        if (hipMemcpy(l->d_hp, host, sizeof(host), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-            return bail(AT3HIP_EDEVICE);   // (pageable source, see at3hip_create)
-    }
-    if (clear_state(l) != AT3HIP_OK || hipStreamSynchronize(l->stream) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    *out = l;
-    return AT3HIP_OK;
+    return at3host::create_engine(cfg->device_id, out, at3hip_loudness_destroy, [&](at3hip_loudness* l) {
+        l->cfg = *cfg;
+        const size_t S = cfg->n_streams, C = cfg->channels;
+        int rc;
+        for (int b = 0; b < 2; ++b)
+            if ((rc = dev_alloc(l, &l->d_carry[b], S * kWindow * C)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(l, &l->d_z, (size_t)cfg->max_hops * S * C)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(l, &l->d_peaks, S * 4)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(l, &l->d_gain, S)) != AT3HIP_OK) return rc;
+        if (cfg->true_peak) {
+            float host[kPhases * kTaps];
+            if (at3hip_resampler_host_tables(44100, 176400, host, sizeof(host)) != AT3HIP_OK) return AT3HIP_EINVAL;
+            if ((rc = dev_alloc(l, &l->d_hp, (size_t)kPhases * kTaps)) != AT3HIP_OK) return rc;
+            if ((rc = at3host::upload_table(l->d_hp, host, sizeof(host))) != AT3HIP_OK) return rc;
+        }
+        return clear_state(l) != AT3HIP_OK || hipStreamSynchronize(l->stream) != hipSuccess ? AT3HIP_EDEVICE : AT3HIP_OK;
+    });
 }
 
 void at3hip_loudness_destroy(at3hip_loudness* l)
 {
-    if (l) destroy(l);
+    if (l) at3host::destroy_engine(l, {l->d_carry[0], l->d_carry[1], l->d_z, l->d_peaks, l->d_hp, l->d_gain, l->d_in, l->d_out});
 }
 
-const char* at3hip_loudness_last_error(const at3hip_loudness* l) { return l ? l->err : "null context"; }
+const char* at3hip_loudness_last_error(const at3hip_loudness* l) { return at3host::engine_last_error(l); }
 
 int at3hip_loudness_reset(at3hip_loudness* l)
 {
@@ -657,30 +624,11 @@ int at3hip_loudness_apply(at3hip_loudness* l, const float* in, int32_t n_in, con
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_scale, dim3((unsigned)blocks, (unsigned)S), dim3(kScaleThreads), 0, l->stream, d_in, d_out, l->d_gain, n, vec);
     HIPCHK(l, hipGetLastError());
-    if (!(flags & AT3HIP_OUT_ON_DEVICE))
-        HIPCHK(l, hipMemcpyAsync(out, l->d_out, S * n * sizeof(float), hipMemcpyDeviceToHost, l->stream));
-    if (flags & AT3HIP_ASYNC) return AT3HIP_OK;
-    HIPCHK(l, hipStreamSynchronize(l->stream));
-    return AT3HIP_OK;
+    return at3host::copy_out_and_wait(l, out, l->d_out, S * n * sizeof(float), flags);
 }
 
-int at3hip_loudness_sync(at3hip_loudness* l)
-{
-    if (!l) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(l->device);
-    HIPCHK(l, guard.error());
-    HIPCHK(l, hipStreamSynchronize(l->stream));
-    return AT3HIP_OK;
-}
+int at3hip_loudness_sync(at3hip_loudness* l) { return at3host::engine_sync(l); }
 
-int at3hip_loudness_set_stream(at3hip_loudness* l, void* hip_stream)
-{
-    if (!l) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(l->device);
-    HIPCHK(l, guard.error());
-    HIPCHK(l, hipStreamSynchronize(l->stream));
-    l->stream = hip_stream ? (hipStream_t)hip_stream : l->own_stream;
-    return AT3HIP_OK;
-}
+int at3hip_loudness_set_stream(at3hip_loudness* l, void* hip_stream) { return at3host::engine_set_stream(l, hip_stream); }
 
 }  // extern "C"

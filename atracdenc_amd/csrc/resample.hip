@@ -216,13 +216,10 @@ __global__ __launch_bounds__(kThreads) void k_resample(ResampleParams p)
 
 }  // namespace
 
-struct at3hip_resampler {
+struct at3hip_resampler : at3host::EngineBase {
     at3hip_resampler_config cfg;
     Shape sh;
     int Q = 0, pad = 0, max_out = 0;
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;   // own_stream, or the caller's (at3hip_resampler_set_stream)
     float* d_hp = nullptr;          // [L][K]
     float* d_hist[2] = {nullptr, nullptr};   // [S][K][C], read / written alternately
     int cur = 0;
@@ -230,25 +227,12 @@ struct at3hip_resampler {
     float* d_out = nullptr;         // staging for host output [S][max_out][C], likewise
     long long t_in = 0;             // input samples received per stream since the start
     long long t_out = 0;            // outputs emitted per stream since the start
-    char err[256] = {0};
 };
 
 namespace {
 
 // ceil(a L / M) for a > 0, else 0: the outputs whose i is below a
 long long outputs_below(long long a, const Shape& s) { return a <= 0 ? 0 : (a * s.L + s.M - 1) / s.M; }
-
-void destroy(at3hip_resampler* r)
-{
-    {
-        at3host::DeviceGuard guard(r->device);
-        if (r->stream) (void)hipStreamSynchronize(r->stream);
-        for (void* b : {(void*)r->d_hp, (void*)r->d_hist[0], (void*)r->d_hist[1], (void*)r->d_in, (void*)r->d_out})
-            if (b) (void)hipFree(b);
-        if (r->own_stream) (void)hipStreamDestroy(r->own_stream);
-    }
-    delete r;
-}
 
 // Queues one call: n_in new samples (device memory), outputs [t_out, n_end) into out (device memory).
 int launch(at3hip_resampler* r, const float* in, int n_in, long long n_end, float* out)
@@ -284,12 +268,7 @@ int launch(at3hip_resampler* r, const float* in, int n_in, long long n_end, floa
 
 int finish(at3hip_resampler* r, float* out, int n_out, uint32_t flags)
 {
-    if (!(flags & AT3HIP_OUT_ON_DEVICE) && n_out > 0)
-        HIPCHK(r, hipMemcpyAsync(out, r->d_out, (size_t)r->cfg.n_streams * n_out * r->cfg.channels * sizeof(float),
-                                 hipMemcpyDeviceToHost, r->stream));
-    if (flags & AT3HIP_ASYNC) return AT3HIP_OK;
-    HIPCHK(r, hipStreamSynchronize(r->stream));
-    return AT3HIP_OK;
+    return at3host::copy_out_and_wait(r, out, r->d_out, (size_t)r->cfg.n_streams * n_out * r->cfg.channels * sizeof(float), flags);
 }
 
 }  // namespace
@@ -338,50 +317,34 @@ int at3hip_resampler_create(const at3hip_resampler_config* cfg, at3hip_resampler
     const long long cap_flush = ((long long)(sh.K / 2) * sh.L + sh.M - 1) / sh.M;
     const long long max_out = cap_process > cap_flush ? cap_process : cap_flush;
     if (max_out > INT32_MAX) return AT3HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return AT3HIP_EDEVICE;
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return AT3HIP_EINVAL;
-    at3hip_resampler* r = new (std::nothrow) at3hip_resampler();
-    if (!r) return AT3HIP_ENOMEM;
-    r->cfg = *cfg;
-    r->sh = sh;
-    r->Q = Q;
-    r->pad = pad;
-    r->max_out = (int)max_out;
-    r->device = cfg->device_id;
-    auto bail = [&](int code) {
-        destroy(r);
-        return code;
-    };
-    at3host::DeviceGuard guard(r->device);
-    if (guard.error() != hipSuccess) return bail(AT3HIP_EDEVICE);
-    if (hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    r->stream = r->own_stream;
-    const size_t S = cfg->n_streams, table = (size_t)sh.L * sh.K;
-    float* host = new (std::nothrow) float[table];
-    if (!host) return bail(AT3HIP_ENOMEM);
-    build_table(cfg->in_rate, cfg->out_rate, sh, host);
-    int rc = dev_alloc(r, &r->d_hp, table);
-    if (rc == AT3HIP_OK && (hipMemcpy(r->d_hp, host, table * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipDeviceSynchronize() != hipSuccess))   // (pageable source, see at3hip_create)
-        rc = AT3HIP_EDEVICE;
-    delete[] host;
-    if (rc != AT3HIP_OK) return bail(rc);
-    for (int b = 0; b < 2; ++b)
-        if ((rc = dev_alloc(r, &r->d_hist[b], S * sh.K * C)) != AT3HIP_OK) return bail(rc);
-    for (int b = 0; b < 2; ++b)
-        if (hipMemsetAsync(r->d_hist[b], 0, S * sh.K * C * sizeof(float), r->stream) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    if (hipStreamSynchronize(r->stream) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    *out = r;
-    return AT3HIP_OK;
+    return at3host::create_engine(cfg->device_id, out, at3hip_resampler_destroy, [&](at3hip_resampler* r) {
+        r->cfg = *cfg;
+        r->sh = sh;
+        r->Q = Q;
+        r->pad = pad;
+        r->max_out = (int)max_out;
+        const size_t S = cfg->n_streams, table = (size_t)sh.L * sh.K;
+        float* host = new (std::nothrow) float[table];
+        if (!host) return AT3HIP_ENOMEM;
+        build_table(cfg->in_rate, cfg->out_rate, sh, host);
+        int rc = dev_alloc(r, &r->d_hp, table);
+        if (rc == AT3HIP_OK) rc = at3host::upload_table(r->d_hp, host, table * sizeof(float));
+        delete[] host;
+        if (rc != AT3HIP_OK) return rc;
+        for (int b = 0; b < 2; ++b)
+            if ((rc = dev_alloc(r, &r->d_hist[b], S * sh.K * C)) != AT3HIP_OK) return rc;
+        for (int b = 0; b < 2; ++b)
+            if (hipMemsetAsync(r->d_hist[b], 0, S * sh.K * C * sizeof(float), r->stream) != hipSuccess) return AT3HIP_EDEVICE;
+        return hipStreamSynchronize(r->stream) != hipSuccess ? AT3HIP_EDEVICE : AT3HIP_OK;
+    });
 }
 
 void at3hip_resampler_destroy(at3hip_resampler* r)
 {
-    if (r) destroy(r);
+    if (r) at3host::destroy_engine(r, {r->d_hp, r->d_hist[0], r->d_hist[1], r->d_in, r->d_out});
 }
 
-const char* at3hip_resampler_last_error(const at3hip_resampler* r) { return r ? r->err : "null context"; }
+const char* at3hip_resampler_last_error(const at3hip_resampler* r) { return at3host::engine_last_error(r); }
 
 int at3hip_resampler_reset(at3hip_resampler* r)
 {
@@ -451,23 +414,8 @@ int at3hip_resampler_flush(at3hip_resampler* r, float* out, int32_t* n_out, uint
     return finish(r, out, count, flags);
 }
 
-int at3hip_resampler_sync(at3hip_resampler* r)
-{
-    if (!r) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(r->device);
-    HIPCHK(r, guard.error());
-    HIPCHK(r, hipStreamSynchronize(r->stream));
-    return AT3HIP_OK;
-}
+int at3hip_resampler_sync(at3hip_resampler* r) { return at3host::engine_sync(r); }
 
-int at3hip_resampler_set_stream(at3hip_resampler* r, void* hip_stream)
-{
-    if (!r) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(r->device);
-    HIPCHK(r, guard.error());
-    HIPCHK(r, hipStreamSynchronize(r->stream));
-    r->stream = hip_stream ? (hipStream_t)hip_stream : r->own_stream;
-    return AT3HIP_OK;
-}
+int at3hip_resampler_set_stream(at3hip_resampler* r, void* hip_stream) { return at3host::engine_set_stream(r, hip_stream); }
 
 }  // extern "C"

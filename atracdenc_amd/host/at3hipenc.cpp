@@ -26,6 +26,10 @@
 //
 // File-level behaviour follows the reference: 44.1 kHz input only (without --resample), numFrames estimate = samples / 1024 in the
 // container header, the look-ahead first call, the drain call at end of input.
+//
+// Structure: every `-e` runs through encode<TCodec> and every `-d` through run_decode<D>; what differs between the codecs is
+// the description struct (TAtrac1Encode ..., TAt1Decode ...) each driver is instantiated with.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -67,6 +71,12 @@ const char* at1_unit_fault(const uint8_t* u)
         end += (wl ? wl + 1 : 0) * spb[b];
     }
     return end > AT1HIP_FRAME_SIZE * 8 ? "read past the end of the bitstream" : nullptr;   // TBitStream::Read, bitstream.cpp:73-74
+}
+
+int fatal(const std::string& what)
+{
+    std::cerr << "Fatal error: " << what << std::endl;
+    return 1;
 }
 
 void put_le(std::vector<char>& h, uint32_t v, int bytes)
@@ -195,6 +205,85 @@ private:
     std::vector<int16_t> S16;
 };
 
+// The command line.
+struct TOptions {
+    std::string inFile, outFile, codec, container, rateArg;
+    uint32_t bitrate = 0, bfuIdxConst = 0, winMask = 0;
+    bool noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false, resample = false, measure = false, peakGiven = false;
+    int batch = 256, device = 0, rate = 0;
+    TLevel level;
+};
+
+// ---- `-d` -------------------------------------------------------------------------------------------------------------------
+// One driver (run_decode) runs every decoder; a decoder is a description (TAt1Decode, TAt3Decode, TAt3pDecode below) with
+//   Api, the C entry points' prefix, and Create / Decode / LastError / Destroy (/ GetCounters), the entry points themselves
+//   Samples per frame and channel, FrameBytes per frame (every channel), Channels, Config(batch, device)
+//   S16 / Float, the decode flags of the 16-bit output and of the float output that feeds --rate
+//   InputLines, the banner's lines about the input, FrameText for "Can't read <FrameText>" (and Skipped, Reasons(counters))
+// nOut frames are decoded, nRead >= nOut are read, B at a time (0: an empty file, nothing to create); inspect(frames, n) sees
+// every batch read, report(decoder) runs after the last one and ends the run with status 1 when it returns false.
+template <typename D, typename TInspect, typename TReport>
+int run_decode(const D& d, std::ifstream& in, const TOptions& o, int64_t nOut, int64_t nRead, int B, TInspect inspect, TReport report)
+{
+    if (!o.noStdOut)
+        std::cout << "Input\n Filename: " << o.inFile << "\n" << d.InputLines << "\nOutput:\n Filename: " << o.outFile << "\n Codec: PCM" << std::endl;
+    std::ofstream out(o.outFile, std::ios::binary);
+    if (!out) return fatal("unable to open output file '" + o.outFile + "'");
+    const uint32_t nch = (uint32_t)d.Channels;
+    const int64_t nSamples = o.rate ? TRateWriter::Samples(nOut * D::Samples, o.rate) : nOut * D::Samples;
+    if (nSamples * nch * 2 >= (int64_t)UINT32_MAX - 36) return fatal("output too long for a WAV file");
+    write_wav_header(out, nch, (uint32_t)(nSamples * nch * 2), o.rate ? (uint32_t)o.rate : 44100u);
+    if (B == 0) {
+        if (!o.noStdOut) std::cout << "\nDone" << std::endl;
+        return 0;
+    }
+    // (before the decoder: the converter may refuse, and nothing is then left to free)
+    std::unique_ptr<TRateWriter> rw(o.rate ? new TRateWriter(out, o.rate, (int)nch, B * D::Samples, o.device) : nullptr);
+    typename D::THandle* made = nullptr;
+    const auto cfg = d.Config(B, o.device);
+    int rc = D::Create(&cfg, &made);
+    if (rc != AT3HIP_OK) return fatal(std::string(D::Api) + "_decoder_create failed (" + std::to_string(rc) + ")");
+    const std::unique_ptr<typename D::THandle, void (*)(typename D::THandle*)> dec(made, D::Destroy);
+    std::vector<uint8_t> frames((size_t)B * d.FrameBytes);
+    std::vector<int16_t> pcm((size_t)B * D::Samples * nch);
+    std::vector<float> pcmf(rw ? (size_t)B * D::Samples * nch : 0);
+    for (int64_t f0 = 0; f0 < nRead; f0 += B) {
+        const int n = (int)std::min<int64_t>(B, nRead - f0);
+        if (!in.read((char*)frames.data(), (std::streamsize)n * d.FrameBytes)) return fatal(std::string("Can't read ") + D::FrameText);
+        inspect(frames.data(), n);
+        const int nDec = (int)std::min<int64_t>(n, nOut - f0);
+        if (nDec <= 0) break;
+        rc = rw ? D::Decode(dec.get(), frames.data(), nDec, pcmf.data(), D::Float) : D::Decode(dec.get(), frames.data(), nDec, pcm.data(), D::S16);
+        if (rc != AT3HIP_OK) {
+            std::cerr << "Encode/Decode error: " << D::Api << "_decode: " << D::LastError(dec.get()) << std::endl;
+            return 1;
+        }
+        if (rw) rw->Write(pcmf.data(), nDec * D::Samples);
+        else out.write((const char*)pcm.data(), (std::streamsize)nDec * D::Samples * nch * 2);   // little-endian host
+    }
+    if (rw) rw->Finish();
+    if (!report(dec.get())) return 1;
+    if (!o.noStdOut) std::cout << "\nDone" << std::endl;
+    return 0;
+}
+
+// Report of the decoders that count what they reject: one line per reason that occurred.
+template <typename D>
+bool report_rejections(typename D::THandle* dec)
+{
+    typename D::TCounters c{};
+    const int rc = D::GetCounters(dec, &c, 0);
+    if (rc != AT3HIP_OK) {
+        std::cerr << "Fatal error: " << D::Api << "_decoder_get_counters failed (" << rc << ")" << std::endl;
+        return false;
+    }
+    for (const auto& r : D::Reasons(c))
+        if (r.second) std::cerr << D::Skipped << " (" << r.first << "): " << r.second << std::endl;
+    return true;
+}
+
+using TReasons = std::vector<std::pair<const char*, uint64_t>>;
+
 // `-d`: TAtrac1Decoder behind TPCMEngine(4096, channels) with a TWav writer (main.cpp:343-365, 697-705).
 //  * Length: TAeaInput::GetLengthInSamples = 512 * (units / channels - 5) (aea.cpp:98-108). The engine's ApplyProcess(512) runs
 //    the lambda over its whole 4096-sample buffer, i.e. 8 frames per call, and the loop calls it until `processed` reaches that
@@ -205,27 +294,27 @@ private:
 //    SF_FORMAT_WAV | SF_FORMAT_PCM_16 with normalisation, which stores lrintf(x * 32767.0f) behind a 44-byte canonical header.
 //    That rule and the header are a restatement of libsndfile's documented behaviour, not pinned against it here; the float
 //    samples the conversion starts from are pinned against the reference (tests/golden/at1_decode.npz).
-int decode_aea(const std::string& inFile, const std::string& outFile, bool noStdOut, int batch, int device, int rate)
+struct TAt1Decode {
+    using THandle = at1hip_decoder;
+    static constexpr const char *Api = "at1hip", *FrameText = "AEA frame";
+    static constexpr auto Create = at1hip_decoder_create;
+    static constexpr auto Decode = at1hip_decode;
+    static constexpr auto LastError = at1hip_decoder_last_error;
+    static constexpr auto Destroy = at1hip_decoder_destroy;
+    static constexpr int Samples = 512;
+    static constexpr uint32_t S16 = AT1HIP_DECODE_S16, Float = 0;
+    int Channels, FrameBytes;
+    std::string InputLines;
+    at1hip_decoder_config Config(int batch, int device) const { return {Channels, 1, batch, device}; }
+};
+
+int decode_aea(std::ifstream& in, const TOptions& o)
 {
-    std::ifstream in(inFile, std::ios::binary);
-    if (!in) {
-        std::cerr << "Fatal error: unable to open input file '" << inFile << "'" << std::endl;
-        return 1;
-    }
     std::vector<char> hdr(2048);
-    if (!in.read(hdr.data(), (std::streamsize)hdr.size())) {
-        std::cerr << "Fatal error: Can't read AEA header" << std::endl;
-        return 1;
-    }
-    if (!(hdr[0] == 0x00 && hdr[1] == 0x08 && hdr[2] == 0x00 && hdr[3] == 0x00 && hdr[264] < 3)) {   // TAeaInput::ReadMeta
-        std::cerr << "Fatal error: invalid AEA header" << std::endl;
-        return 1;
-    }
+    if (!in.read(hdr.data(), (std::streamsize)hdr.size())) return fatal("Can't read AEA header");
+    if (!(hdr[0] == 0x00 && hdr[1] == 0x08 && hdr[2] == 0x00 && hdr[3] == 0x00 && hdr[264] < 3)) return fatal("invalid AEA header");   // TAeaInput::ReadMeta
     const int nch = hdr[264];
-    if (nch < 1) {
-        std::cerr << "Fatal error: AEA header gives no channels" << std::endl;
-        return 1;
-    }
+    if (nch < 1) return fatal("AEA header gives no channels");
     in.seekg(0, std::ios::end);
     const int64_t fileSize = (int64_t)in.tellg();
     in.seekg(2048, std::ios::beg);
@@ -233,63 +322,20 @@ int decode_aea(const std::string& inFile, const std::string& outFile, bool noStd
     const int64_t calls = frames >= 5 ? std::max<int64_t>(1, (frames - 5 + 7) / 8) : INT64_MAX;
     const int64_t complete = std::min<int64_t>(calls, frames / 8);
     const int64_t nOut = 8 * complete;
-    if (!noStdOut) {
-        hdr[19] = 0;
-        std::cout << "Input\n Filename: " << inFile << "\n Name: " << std::string(&hdr[4]) << "\n Channels: " << nch
-                  << "\nOutput:\n Filename: " << outFile << "\n Codec: PCM" << std::endl;
-    }
-    std::ofstream out(outFile, std::ios::binary);
-    if (!out) {
-        std::cerr << "Fatal error: unable to open output file '" << outFile << "'" << std::endl;
-        return 1;
-    }
-    const int64_t nSamples = rate ? TRateWriter::Samples(nOut * 512, rate) : nOut * 512;
-    if (rate && nSamples * nch * 2 >= (int64_t)UINT32_MAX - 36) {
-        std::cerr << "Fatal error: output too long for a WAV file" << std::endl;
-        return 1;
-    }
-    write_wav_header(out, (uint32_t)nch, (uint32_t)(nSamples * nch * 2), rate ? (uint32_t)rate : 44100u);
-
-    const int B = batch < 1 ? 1 : batch;
-    // (before the decoder: the converter may refuse, and nothing is then left to free)
-    std::unique_ptr<TRateWriter> rw(rate ? new TRateWriter(out, rate, nch, B * 512, device) : nullptr);
-    at1hip_decoder* dec = nullptr;
-    at1hip_decoder_config cfg{nch, 1, B, device};
-    int rc = at1hip_decoder_create(&cfg, &dec);
-    if (rc != AT3HIP_OK) {
-        std::cerr << "Fatal error: at1hip_decoder_create failed (" << rc << ")" << std::endl;
-        return 1;
-    }
+    hdr[19] = 0;
+    const TAt1Decode d{nch, nch * AT1HIP_FRAME_SIZE, " Name: " + std::string(&hdr[4]) + "\n Channels: " + std::to_string(nch)};
     // frames the failing call could still read report their faults before ReadFrame throws
-    const int64_t nReport = complete < calls ? frames : nOut;
-    std::vector<uint8_t> units((size_t)B * nch * AT1HIP_FRAME_SIZE);
-    std::vector<int16_t> pcm((size_t)B * 512 * nch);
-    std::vector<float> pcmf(rate ? (size_t)B * 512 * nch : 0);
-    for (int64_t f0 = 0; f0 < nReport; f0 += B) {
-        const int n = (int)std::min<int64_t>(B, nReport - f0);
-        in.read((char*)units.data(), (std::streamsize)n * nch * AT1HIP_FRAME_SIZE);
-        for (int i = 0; i < n * nch; ++i)
-            if (const char* what = at1_unit_fault(&units[(size_t)i * AT1HIP_FRAME_SIZE]))
-                std::cerr << "Skipping invalid ATRAC1 frame: " << what << std::endl;
-        const int nDec = (int)std::min<int64_t>(n, nOut - f0);
-        if (nDec <= 0) break;
-        rc = rw ? at1hip_decode(dec, units.data(), nDec, pcmf.data(), 0) : at1hip_decode(dec, units.data(), nDec, pcm.data(), AT1HIP_DECODE_S16);
-        if (rc != AT3HIP_OK) {
-            std::cerr << "Encode/Decode error: at1hip_decode: " << at1hip_decoder_last_error(dec) << std::endl;
-            at1hip_decoder_destroy(dec);
-            return 1;
-        }
-        if (rw) rw->Write(pcmf.data(), nDec * 512);
-        else out.write((const char*)pcm.data(), (std::streamsize)nDec * 512 * nch * 2);   // little-endian host
-    }
-    at1hip_decoder_destroy(dec);
-    if (rw) rw->Finish();
-    if (complete < calls) {
-        std::cerr << "Aea IO fatal error: Can't read AEA frame" << std::endl;
-        return 1;
-    }
-    if (!noStdOut) std::cout << "\nDone" << std::endl;
-    return 0;
+    return run_decode(
+        d, in, o, nOut, complete < calls ? frames : nOut, o.batch < 1 ? 1 : o.batch,
+        [nch](const uint8_t* units, int n) {
+            for (int i = 0; i < n * nch; ++i)
+                if (const char* what = at1_unit_fault(units + (size_t)i * AT1HIP_FRAME_SIZE))
+                    std::cerr << "Skipping invalid ATRAC1 frame: " << what << std::endl;
+        },
+        [&](at1hip_decoder*) {   // (no counters: the faults were reported per unit)
+            if (complete < calls) std::cerr << "Aea IO fatal error: Can't read AEA frame" << std::endl;
+            return complete >= calls;
+        });
 }
 
 // `-d` on an ATRAC3 file: the container is recognised by content, as this repository's writers (at3hip_io.hpp) write it.
@@ -326,7 +372,7 @@ bool at3_row(int frameSize, int js)
 EInput probe_input(const std::string& inFile, TAt3Input& at3)
 {
     std::ifstream in(inFile, std::ios::binary);
-    if (!in) return EInput::AEA;   // the AEA path reports it
+    if (!in) return EInput::AEA;   // main reports it
     uint8_t h[4096] = {0};
     in.read((char*)h, sizeof(h));
     const int64_t got = in.gcount();
@@ -421,161 +467,214 @@ EInput probe_input(const std::string& inFile, TAt3Input& at3)
     return EInput::ATRAC3;
 }
 
-int decode_at3(const std::string& inFile, const std::string& outFile, const TAt3Input& at3, bool noStdOut, int batch, int device,
-               int rate)
-{
-    std::ifstream in(inFile, std::ios::binary);
-    if (!in) {
-        std::cerr << "Fatal error: unable to open input file '" << inFile << "'" << std::endl;
-        return 1;
+struct TAt3Decode {
+    using THandle = at3hip_decoder;
+    using TCounters = at3hip_decoder_counters;
+    static constexpr const char *Api = "at3hip", *FrameText = "ATRAC3 frame", *Skipped = "Skipped invalid ATRAC3 units";
+    static constexpr auto Create = at3hip_decoder_create;
+    static constexpr auto Decode = at3hip_decode;
+    static constexpr auto LastError = at3hip_decoder_last_error;
+    static constexpr auto GetCounters = at3hip_decoder_get_counters;
+    static constexpr auto Destroy = at3hip_decoder_destroy;
+    static constexpr int Samples = 1024;
+    static constexpr uint32_t S16 = AT3HIP_DECODE_S16, Float = 0;
+    int Channels = 2, FrameBytes, Js;
+    std::string InputLines;
+
+    explicit TAt3Decode(const TAt3Input& f)
+        : FrameBytes(f.frameSize), Js(f.js),
+          InputLines(" Container: " + f.container + "\n Codec: ATRAC3, frame size " + std::to_string(f.frameSize) + (f.js ? ", joint stereo" : ""))
+    {
     }
-    in.seekg(at3.offset, std::ios::beg);
-    const int64_t nOut = at3.frames;
-    if (!noStdOut)
-        std::cout << "Input\n Filename: " << inFile << "\n Container: " << at3.container << "\n Codec: ATRAC3, frame size "
-                  << at3.frameSize << (at3.js ? ", joint stereo" : "") << "\nOutput:\n Filename: " << outFile << "\n Codec: PCM" << std::endl;
-    std::ofstream out(outFile, std::ios::binary);
-    if (!out) {
-        std::cerr << "Fatal error: unable to open output file '" << outFile << "'" << std::endl;
-        return 1;
+    at3hip_decoder_config Config(int batch, int device) const { return {1, FrameBytes, Js, batch, device}; }
+    static TReasons Reasons(const TCounters& c)
+    {
+        return {{"wrong unit id", c.bad_id}, {"unsupported joint-stereo parameters", c.unsupported_js}, {"read past the end of the unit", c.read_past_end},
+                {"tonal component past line 1023", c.tonal_past_end}, {"tonal coding mode", c.bad_tonal_mode}, {"tonal quantiser", c.bad_tonal_quant}};
     }
-    if (nOut * 1024 * 2 * 2 >= (int64_t)UINT32_MAX - 36) {
-        std::cerr << "Fatal error: output too long for a WAV file" << std::endl;
-        return 1;
-    }
-    const uint32_t nch = 2;
-    const int64_t nSamples = rate ? TRateWriter::Samples(nOut * 1024, rate) : nOut * 1024;
-    if (nSamples * nch * 2 >= (int64_t)UINT32_MAX - 36) {
-        std::cerr << "Fatal error: output too long for a WAV file" << std::endl;
-        return 1;
-    }
-    write_wav_header(out, nch, (uint32_t)(nSamples * nch * 2), rate ? (uint32_t)rate : 44100u);
-    if (nOut == 0) {
-        if (!noStdOut) std::cout << "\nDone" << std::endl;
-        return 0;
-    }
-    const int B = (int)std::min<int64_t>(batch < 1 ? 1 : batch, nOut);
-    // (before the decoder: the converter may refuse, and nothing is then left to free)
-    std::unique_ptr<TRateWriter> rw(rate ? new TRateWriter(out, rate, (int)nch, B * 1024, device) : nullptr);
-    at3hip_decoder* dec = nullptr;
-    at3hip_decoder_config cfg{1, at3.frameSize, at3.js, B, device};
-    int rc = at3hip_decoder_create(&cfg, &dec);
-    if (rc != AT3HIP_OK) {
-        std::cerr << "Fatal error: at3hip_decoder_create failed (" << rc << ")" << std::endl;
-        return 1;
-    }
-    std::vector<uint8_t> frames((size_t)B * at3.frameSize);
-    std::vector<int16_t> pcm((size_t)B * 1024 * nch);
-    std::vector<float> pcmf(rate ? (size_t)B * 1024 * nch : 0);
-    for (int64_t f0 = 0; f0 < nOut; f0 += B) {
-        const int n = (int)std::min<int64_t>(B, nOut - f0);
-        if (!in.read((char*)frames.data(), (std::streamsize)n * at3.frameSize)) {
-            std::cerr << "Fatal error: Can't read ATRAC3 frame" << std::endl;
-            at3hip_decoder_destroy(dec);
-            return 1;
-        }
-        rc = rw ? at3hip_decode(dec, frames.data(), n, pcmf.data(), 0) : at3hip_decode(dec, frames.data(), n, pcm.data(), AT3HIP_DECODE_S16);
-        if (rc != AT3HIP_OK) {
-            std::cerr << "Encode/Decode error: at3hip_decode: " << at3hip_decoder_last_error(dec) << std::endl;
-            at3hip_decoder_destroy(dec);
-            return 1;
-        }
-        if (rw) rw->Write(pcmf.data(), n * 1024);
-        else out.write((const char*)pcm.data(), (std::streamsize)n * 1024 * nch * 2);   // little-endian host
-    }
-    if (rw) rw->Finish();
-    at3hip_decoder_counters c{};
-    rc = at3hip_decoder_get_counters(dec, &c, 0);
-    at3hip_decoder_destroy(dec);
-    if (rc != AT3HIP_OK) {
-        std::cerr << "Fatal error: at3hip_decoder_get_counters failed (" << rc << ")" << std::endl;
-        return 1;
-    }
-    const std::pair<const char*, uint64_t> reasons[] = {
-        {"wrong unit id", c.bad_id}, {"unsupported joint-stereo parameters", c.unsupported_js}, {"read past the end of the unit", c.read_past_end},
-        {"tonal component past line 1023", c.tonal_past_end}, {"tonal coding mode", c.bad_tonal_mode}, {"tonal quantiser", c.bad_tonal_quant}};
-    for (const auto& r : reasons)
-        if (r.second) std::cerr << "Skipped invalid ATRAC3 units (" << r.first << "): " << r.second << std::endl;
-    if (!noStdOut) std::cout << "\nDone" << std::endl;
-    return 0;
-}
+};
 
 // `-d` on an ATRAC3plus OMA / RIFF file: a 16-bit WAV with the stream's channel count, 2048 samples per frame, the codec delay
 // (2416 samples) not trimmed; rejected frames are counted and reported per reason.
-int decode_at3p(const std::string& inFile, const std::string& outFile, const TAt3Input& at3, bool noStdOut, int batch, int device,
-                int rate)
+struct TAt3pDecode {
+    using THandle = at3phip_decoder;
+    using TCounters = at3phip_decoder_counters;
+    static constexpr const char *Api = "at3phip", *FrameText = "ATRAC3plus frame", *Skipped = "Skipped invalid ATRAC3plus frames";
+    static constexpr auto Create = at3phip_decoder_create;
+    static constexpr auto Decode = at3phip_decode;
+    static constexpr auto LastError = at3phip_decoder_last_error;
+    static constexpr auto GetCounters = at3phip_decoder_get_counters;
+    static constexpr auto Destroy = at3phip_decoder_destroy;
+    static constexpr int Samples = 2048;
+    static constexpr uint32_t S16 = AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES, Float = AT3PHIP_DECODE_TONES;
+    int Channels, FrameBytes = 2048;
+    std::string InputLines;
+
+    explicit TAt3pDecode(const TAt3Input& f)
+        : Channels(f.channels), InputLines(" Container: " + f.container + "\n Codec: ATRAC3plus, " + std::to_string(f.channels) +
+                                           (f.channels == 1 ? " channel" : " channels"))
+    {
+    }
+    at3phip_decoder_config Config(int batch, int device) const { return {Channels, 1, batch, device}; }
+    static TReasons Reasons(const TCounters& c)
+    {
+        return {{"bad header or block type", c.bad_header}, {"unsupported syntax element", c.unsupported_syntax},
+                {"tonal block present", c.tonal_present}, {"invalid code or out-of-range value", c.bad_code},
+                {"read past the end of the frame", c.read_past_end}, {"missing terminator", c.no_terminator}};
+    }
+};
+
+// A file whose container gave the payload's offset and frame count (ATRAC3, ATRAC3plus): every frame is read and decoded,
+// rejected ones are counted.
+template <typename D>
+int decode_container(const D& d, std::ifstream& in, const TAt3Input& f, const TOptions& o)
 {
-    std::ifstream in(inFile, std::ios::binary);
-    if (!in) {
-        std::cerr << "Fatal error: unable to open input file '" << inFile << "'" << std::endl;
-        return 1;
+    in.seekg(f.offset, std::ios::beg);
+    return run_decode(d, in, o, f.frames, f.frames, (int)std::min<int64_t>(o.batch < 1 ? 1 : o.batch, f.frames),
+                      [](const uint8_t*, int) {}, report_rejections<D>);
+}
+
+// ---- `-e` -------------------------------------------------------------------------------------------------------------------
+// The container of the output: what --container names, among `allowed`, or without it what `select` makes of the file's name.
+EContainer container_of(const TOptions& o, EContainer (*select)(const std::string&), std::initializer_list<EContainer> allowed)
+{
+    static const std::pair<const char*, EContainer> names[] = {
+        {"oma", EContainer::OMA}, {"riff", EContainer::RIFF}, {"raw", EContainer::RAW}, {"aea", EContainer::AEA}};
+    if (o.container.empty()) return select(o.outFile);
+    for (const auto& c : names)
+        if (o.container == c.first && std::find(allowed.begin(), allowed.end(), c.second) != allowed.end()) return c.second;
+    throw std::runtime_error("unrecognized container: " + o.container);
+}
+
+// One driver (encode) runs every encoder; an encoder is a description (TAtrac1Encode, TAtrac3Encode, TAtrac3PlusEncode below)
+// made from the options and the input's channel count, with
+//   Block, the samples of one ApplyProcess call, and NumFrames(samples, channels), the container header's estimate
+//   CheckOptions(o): the codec's range messages, before the input is opened
+//   Output(o, channels, numFrames), the container writer, and Encoder(out, o), the encoder object (at3hip_host.hpp)
+//   InputLine and CodecLines(): the banner follows the reference's main.cpp, which differs between the codecs
+//   Report(encoder, o): what the codec prints after the encode
+struct TAtrac1Encode {
+    static constexpr size_t Block = 512;
+    static constexpr const char* InputLine = "Input";
+    static uint64_t NumFrames(uint64_t samples, size_t channels) { return channels * samples / 512; }   // main.cpp:312
+    static bool CheckOptions(const TOptions& o)
+    {
+        if (o.bfuIdxConst > 8) std::cerr << "ATRAC1 mode, --bfuidxconst is a index of max used BFU. Values [1;8] is allowed\n";
+        return o.bfuIdxConst <= 8;
     }
-    in.seekg(at3.offset, std::ios::beg);
-    const int64_t nOut = at3.frames;
-    const uint32_t nch = (uint32_t)at3.channels;
-    if (!noStdOut)
-        std::cout << "Input\n Filename: " << inFile << "\n Container: " << at3.container << "\n Codec: ATRAC3plus, " << nch
-                  << (nch == 1 ? " channel" : " channels") << "\nOutput:\n Filename: " << outFile << "\n Codec: PCM" << std::endl;
-    std::ofstream out(outFile, std::ios::binary);
-    if (!out) {
-        std::cerr << "Fatal error: unable to open output file '" << outFile << "'" << std::endl;
-        return 1;
+    TAtrac1Encode(const TOptions&, size_t) {}
+    TCompressedOutputPtr Output(const TOptions& o, size_t channels, uint32_t numFrames) const
+    {
+        return CreateAtrac1Output(container_of(o, SelectAtrac1Container, {EContainer::AEA, EContainer::RAW}), o.outFile, channels, numFrames);
     }
-    const int64_t nSamples = rate ? TRateWriter::Samples(nOut * 2048, rate) : nOut * 2048;
-    if (nSamples * nch * 2 >= (int64_t)UINT32_MAX - 36) {
-        std::cerr << "Fatal error: output too long for a WAV file" << std::endl;
-        return 1;
+    std::string CodecLines() const { return "ATRAC1"; }
+    TAtrac1Encoder Encoder(TCompressedOutputPtr&& out, const TOptions& o)
+    {
+        const auto mode = o.noTransient ? TAtrac1EncodeSettings::EWindowMode::EWM_NOTRANSIENT : TAtrac1EncodeSettings::EWindowMode::EWM_AUTO;
+        return TAtrac1Encoder(std::move(out), TAtrac1EncodeSettings(o.bfuIdxConst, mode, o.winMask), o.batch, o.device);
     }
-    write_wav_header(out, nch, (uint32_t)(nSamples * nch * 2), rate ? (uint32_t)rate : 44100u);
-    if (nOut == 0) {
-        if (!noStdOut) std::cout << "\nDone" << std::endl;
-        return 0;
-    }
-    const int B = (int)std::min<int64_t>(batch < 1 ? 1 : batch, nOut);
-    // (before the decoder: the converter may refuse, and nothing is then left to free)
-    std::unique_ptr<TRateWriter> rw(rate ? new TRateWriter(out, rate, (int)nch, B * 2048, device) : nullptr);
-    at3phip_decoder* dec = nullptr;
-    at3phip_decoder_config cfg{(int32_t)nch, 1, B, device};
-    int rc = at3phip_decoder_create(&cfg, &dec);
-    if (rc != AT3HIP_OK) {
-        std::cerr << "Fatal error: at3phip_decoder_create failed (" << rc << ")" << std::endl;
-        return 1;
-    }
-    std::vector<uint8_t> frames((size_t)B * 2048);
-    std::vector<int16_t> pcm((size_t)B * 2048 * nch);
-    std::vector<float> pcmf(rate ? (size_t)B * 2048 * nch : 0);
-    for (int64_t f0 = 0; f0 < nOut; f0 += B) {
-        const int n = (int)std::min<int64_t>(B, nOut - f0);
-        if (!in.read((char*)frames.data(), (std::streamsize)n * 2048)) {
-            std::cerr << "Fatal error: Can't read ATRAC3plus frame" << std::endl;
-            at3phip_decoder_destroy(dec);
-            return 1;
+    void Report(TAtrac1Encoder&, const TOptions&) const {}
+};
+
+struct TAtrac3Encode {
+    static constexpr size_t Block = 1024;
+    static constexpr const char* InputLine = "Input:";
+    static uint64_t NumFrames(uint64_t samples, size_t) { return samples / 1024; }
+    static bool CheckOptions(const TOptions& o)
+    {
+        if (o.bitrate && (o.bitrate < 32 || o.bitrate > 384)) {
+            std::cerr << "bitrate must be in [32;384]\n";
+            return false;
         }
-        rc = rw ? at3phip_decode(dec, frames.data(), n, pcmf.data(), AT3PHIP_DECODE_TONES)
-                : at3phip_decode(dec, frames.data(), n, pcm.data(), AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES);
-        if (rc != AT3HIP_OK) {
-            std::cerr << "Encode/Decode error: at3phip_decode: " << at3phip_decoder_last_error(dec) << std::endl;
-            at3phip_decoder_destroy(dec);
-            return 1;
+        if (o.bfuIdxConst > 32) std::cerr << "bfuidxconst must be in [1;32]\n";
+        return o.bfuIdxConst <= 32;
+    }
+    TAtrac3EncoderSettings Settings;
+    uint32_t FrameSize = 0;
+    bool Js = false;
+
+    TAtrac3Encode(const TOptions& o, size_t channels)
+    {
+        Settings.Bitrate = o.bitrate * 1024;   // the tool's kbit value reaches the settings as value * 1024 (main.cpp:676)
+        Settings.NoGainControll = o.noGain;
+        Settings.NoTonalComponents = o.noTonal;
+        Settings.SourceChannels = (uint8_t)channels;
+        Settings.BfuIdxConst = o.bfuIdxConst;
+        // container parameters come from the encoder context (GetContainerParamsForBitrate)
+        at3hip_config probe{};
+        probe.bitrate = (int32_t)Settings.Bitrate;
+        probe.channels = (int32_t)channels;
+        probe.n_streams = 1;
+        probe.max_blocks = 1;
+        probe.device_id = o.device;
+        at3hip_ctx* pc = nullptr;
+        Check(at3hip_create(&probe, &pc), nullptr, "at3hip_create");
+        FrameSize = (uint32_t)at3hip_frame_size(pc);
+        Js = at3hip_joint_stereo(pc) != 0;
+        at3hip_destroy(pc);
+    }
+    TCompressedOutputPtr Output(const TOptions& o, size_t channels, uint32_t numFrames) const
+    {
+        const EContainer c = container_of(o, SelectAtrac3Container, {EContainer::OMA, EContainer::RIFF, EContainer::RAW});
+        return CreateAtrac3Output(c, o.outFile, channels, numFrames, FrameSize, Js);
+    }
+    std::string CodecLines() const { return "ATRAC3\n Bitrate: " + std::to_string(FrameSize == 384 ? 132300 : FrameSize * 44100u * 8u / 1024u); }
+    TAtrac3Encoder Encoder(TCompressedOutputPtr&& out, const TOptions& o) { return TAtrac3Encoder(std::move(out), std::move(Settings), o.batch, o.device); }
+    void Report(TAtrac3Encoder& encoder, const TOptions& o) const
+    {
+        if (!o.level.On || o.noStdOut) return;   // what TScaler::Scale would still have clamped after the gain (at3hip_get_counters)
+        const at3hip_counters c = encoder.Counters();
+        std::cout << "clipping: " << c.scale_overflow << " blocks, " << c.clipped_values << " values" << std::endl;
+    }
+};
+
+struct TAtrac3PlusEncode {
+    static constexpr size_t Block = 2048;
+    static constexpr const char* InputLine = "Input:";
+    static uint64_t NumFrames(uint64_t samples, size_t) { return samples / 2048; }   // main.cpp:440
+    static bool CheckOptions(const TOptions&) { return true; }
+    size_t Channels;
+
+    TAtrac3PlusEncode(const TOptions&, size_t channels) : Channels(channels) {}
+    TCompressedOutputPtr Output(const TOptions& o, size_t channels, uint32_t numFrames) const
+    {
+        const EContainer c = container_of(o, SelectAtrac3PlusContainer, {EContainer::OMA, EContainer::RIFF, EContainer::RAW});
+        return CreateAtrac3PlusOutput(c, o.outFile, channels, numFrames, 2048);
+    }
+    std::string CodecLines() const { return "ATRAC3Plus"; }
+    TAt3PEncoder Encoder(TCompressedOutputPtr&& out, const TOptions& o) { return TAt3PEncoder(std::move(out), (int)Channels, o.batch > 64 ? 64 : o.batch, o.device); }
+    void Report(TAt3PEncoder&, const TOptions&) const {}
+};
+
+template <typename TCodec>
+int encode(const TOptions& o)
+{
+    if (!TCodec::CheckOptions(o)) return 1;
+    try {
+        TEncodeInput wav(o.inFile, o.resample, o.device, o.level);
+        const size_t numChannels = wav.GetChannelNum();
+        const uint64_t totalSamples = wav.GetTotalSamples();
+        TCodec codec(o, numChannels);
+        TCompressedOutputPtr out = codec.Output(o, numChannels, (uint32_t)TCodec::NumFrames(totalSamples, numChannels));
+        if (!o.noStdOut)
+            std::cout << TCodec::InputLine << "\n Filename: " << o.inFile << "\n Channels: " << numChannels << "\n SampleRate: " << wav.GetSampleRate()
+                      << "\n Duration (sec): " << totalSamples / wav.GetSampleRate() << "\nOutput:\n Filename: " << o.outFile
+                      << "\n Codec: " << codec.CodecLines() << std::endl;
+        TPCMEngine engine(4096, numChannels, [&wav](float* dst, size_t frames) { return wav.Read(dst, frames); });
+        auto encoder = codec.Encoder(std::move(out), o);
+        auto lambda = encoder.GetLambda();
+        try {
+            while (totalSamples > engine.ApplyProcess(TCodec::Block, lambda)) {
+            }
+        } catch (const TNoDataToRead&) {
+            std::cerr << "No more data to read from input" << std::endl;
         }
-        if (rw) rw->Write(pcmf.data(), n * 2048);
-        else out.write((const char*)pcm.data(), (std::streamsize)n * 2048 * nch * 2);   // little-endian host
+        encoder.Flush();
+        codec.Report(encoder, o);
+        if (!o.noStdOut) std::cout << "\nDone" << std::endl;
+    } catch (const std::exception& ex) {
+        return fatal(ex.what());
     }
-    if (rw) rw->Finish();
-    at3phip_decoder_counters c{};
-    rc = at3phip_decoder_get_counters(dec, &c, 0);
-    at3phip_decoder_destroy(dec);
-    if (rc != AT3HIP_OK) {
-        std::cerr << "Fatal error: at3phip_decoder_get_counters failed (" << rc << ")" << std::endl;
-        return 1;
-    }
-    const std::pair<const char*, uint64_t> reasons[] = {
-        {"bad header or block type", c.bad_header}, {"unsupported syntax element", c.unsupported_syntax},
-        {"tonal block present", c.tonal_present}, {"invalid code or out-of-range value", c.bad_code},
-        {"read past the end of the frame", c.read_past_end}, {"missing terminator", c.no_terminator}};
-    for (const auto& r : reasons)
-        if (r.second) std::cerr << "Skipped invalid ATRAC3plus frames (" << r.first << "): " << r.second << std::endl;
-    if (!noStdOut) std::cout << "\nDone" << std::endl;
     return 0;
 }
 
@@ -599,13 +698,7 @@ static int usage()
 
 int main(int argc, char** argv)
 {
-    std::string inFile, outFile, codec, container, rateArg;
-    uint32_t bitrate = 0, bfuIdxConst = 0;
-    bool noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false, resample = false;
-    uint32_t winMask = 0;
-    int batch = 256, device = 0, rate = 0;
-    bool measure = false, peakGiven = false;
-    TLevel level;
+    TOptions o;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](const char* what) -> const char* {
@@ -615,224 +708,78 @@ int main(int argc, char** argv)
             }
             return argv[++i];
         };
-        if (a == "-e" || a == "--encode") codec = need("-e");
-        else if (a == "-d" || a == "--decode") decode = true;
-        else if (a == "-i") inFile = need("-i");
-        else if (a == "-o") outFile = need("-o");
-        else if (a == "--bitrate") bitrate = (uint32_t)atoi(need("--bitrate"));
-        else if (a == "--bfuidxconst") bfuIdxConst = (uint32_t)atoi(need("--bfuidxconst"));
-        else if (a == "--notonal") noTonal = true;
-        else if (a == "--nogaincontrol") noGain = true;
-        else if (a == "--nostdout") noStdOut = true;
-        else if (a == "--resample") resample = true;
+        if (a == "-e" || a == "--encode") o.codec = need("-e");
+        else if (a == "-d" || a == "--decode") o.decode = true;
+        else if (a == "-i") o.inFile = need("-i");
+        else if (a == "-o") o.outFile = need("-o");
+        else if (a == "--bitrate") o.bitrate = (uint32_t)atoi(need("--bitrate"));
+        else if (a == "--bfuidxconst") o.bfuIdxConst = (uint32_t)atoi(need("--bfuidxconst"));
+        else if (a == "--notonal") o.noTonal = true;
+        else if (a == "--nogaincontrol") o.noGain = true;
+        else if (a == "--nostdout") o.noStdOut = true;
+        else if (a == "--resample") o.resample = true;
         else if (a == "--loudness") {
-            level.On = true;
-            level.Target = atof(need("--loudness"));
+            o.level.On = true;
+            o.level.Target = atof(need("--loudness"));
         }
         else if (a == "--peak") {
-            peakGiven = true;
-            level.Ceiling = atof(need("--peak"));
+            o.peakGiven = true;
+            o.level.Ceiling = atof(need("--peak"));
         }
-        else if (a == "--truepeak") level.TruePeak = true;
-        else if (a == "--measure") measure = true;
+        else if (a == "--truepeak") o.level.TruePeak = true;
+        else if (a == "--measure") o.measure = true;
         else if (a == "--rate") {   // a positive decimal number, else refused below as an unsupported rate
             const char* v = need("--rate");
-            rateArg = v;
+            o.rateArg = v;
             char* end = nullptr;
             const long x = strtol(v, &end, 10);
-            rate = (*v && !*end && x > 0 && x <= 1000000) ? (int)x : -1;
+            o.rate = (*v && !*end && x > 0 && x <= 1000000) ? (int)x : -1;
         }
         else if (a.rfind("--notransient", 0) == 0 && (a.size() == 13 || a[13] == '=')) {   // optional_argument, main.cpp:568-577
-            noTransient = true;
-            if (a.size() > 14) winMask = (uint32_t)atoi(a.c_str() + 14);
+            o.noTransient = true;
+            if (a.size() > 14) o.winMask = (uint32_t)atoi(a.c_str() + 14);
         }
-        else if (a == "--container") container = need("--container");
-        else if (a == "--batch") batch = atoi(need("--batch"));
-        else if (a == "--device") device = atoi(need("--device"));
+        else if (a == "--container") o.container = need("--container");
+        else if (a == "--batch") o.batch = atoi(need("--batch"));
+        else if (a == "--device") o.device = atoi(need("--device"));
         else return usage();
     }
-    level.NoStdOut = noStdOut;
-    if (measure) {   // prints the meter's result, writes nothing
-        if (decode || !codec.empty() || inFile.empty() || !outFile.empty() || level.On || peakGiven || rate) return usage();
+    o.level.NoStdOut = o.noStdOut;
+    if (o.measure) {   // prints the meter's result, writes nothing
+        if (o.decode || !o.codec.empty() || o.inFile.empty() || !o.outFile.empty() || o.level.On || o.peakGiven || o.rate) return usage();
         try {
-            const at3hip_loudness_result r = measure_input(inFile, resample, device, level.TruePeak);
+            const at3hip_loudness_result r = measure_input(o.inFile, o.resample, o.device, o.level.TruePeak);
             char line[256];
             int n = snprintf(line, sizeof(line), "loudness: I %.2f LUFS, M max %.2f LUFS, S max %.2f LUFS, sample peak %.2f dBFS", r.integrated,
                              r.momentary_max, r.short_term_max, db_of((double)std::max(r.sample_peak[0], r.sample_peak[1])));
-            if (level.TruePeak)
+            if (o.level.TruePeak)
                 snprintf(line + n, sizeof(line) - (size_t)n, ", true peak %.2f dBFS", db_of((double)std::max(r.true_peak[0], r.true_peak[1])));
             std::cout << line << std::endl;
         } catch (const std::exception& ex) {
-            std::cerr << "Fatal error: " << ex.what() << std::endl;
-            return 1;
+            return fatal(ex.what());
         }
         return 0;
     }
-    if (decode) {
-        if (!codec.empty() || inFile.empty() || outFile.empty() || level.On || peakGiven || level.TruePeak) return usage();
+    if (o.decode) {
+        if (!o.codec.empty() || o.inFile.empty() || o.outFile.empty() || o.level.On || o.peakGiven || o.level.TruePeak) return usage();
         TAt3Input at3;
-        const EInput kind = probe_input(inFile, at3);
+        const EInput kind = probe_input(o.inFile, at3);
         if (kind == EInput::REFUSED) return 1;
-        if (rate == 44100) rate = 0;   // the decoders' own rate: written as without --rate
-        if (rate && TRateWriter::Samples(0, rate) < 0) {
-            std::cerr << "Fatal error: unsupported output rate " << rateArg << " (at3hip_resample.h lists the rates)" << std::endl;
-            return 1;
-        }
+        if (o.rate == 44100) o.rate = 0;   // the decoders' own rate: written as without --rate
+        if (o.rate && TRateWriter::Samples(0, o.rate) < 0) return fatal("unsupported output rate " + o.rateArg + " (at3hip_resample.h lists the rates)");
+        std::ifstream in(o.inFile, std::ios::binary);
+        if (!in) return fatal("unable to open input file '" + o.inFile + "'");
         try {
-            if (kind == EInput::ATRAC3) return decode_at3(inFile, outFile, at3, noStdOut, batch, device, rate);
-            if (kind == EInput::ATRAC3PLUS) return decode_at3p(inFile, outFile, at3, noStdOut, batch, device, rate);
-            return decode_aea(inFile, outFile, noStdOut, batch, device, rate);
+            if (kind == EInput::ATRAC3) return decode_container(TAt3Decode(at3), in, at3, o);
+            if (kind == EInput::ATRAC3PLUS) return decode_container(TAt3pDecode(at3), in, at3, o);
+            return decode_aea(in, o);
         } catch (const std::exception& ex) {
-            std::cerr << "Fatal error: " << ex.what() << std::endl;
-            return 1;
+            return fatal(ex.what());
         }
     }
-    if ((codec != "atrac3" && codec != "atrac1" && codec != "atrac3plus") || inFile.empty() || outFile.empty() || rate) return usage();
-    if (!level.On && (peakGiven || level.TruePeak)) return usage();   // --peak and --truepeak belong to --loudness (or --measure)
-    if (codec == "atrac3plus") {
-        try {
-            TEncodeInput wav(inFile, resample, device, level);
-            const size_t numChannels = wav.GetChannelNum();
-            const uint64_t totalSamples = wav.GetTotalSamples();
-            const uint64_t numFrames = totalSamples / 2048;   // main.cpp:440
-            EContainer cont;
-            if (container.empty()) cont = SelectAtrac3PlusContainer(outFile);
-            else if (container == "oma") cont = EContainer::OMA;
-            else if (container == "riff") cont = EContainer::RIFF;
-            else if (container == "raw") cont = EContainer::RAW;
-            else throw std::runtime_error("unrecognized container: " + container);
-            TCompressedOutputPtr out = CreateAtrac3PlusOutput(cont, outFile, numChannels, (uint32_t)numFrames, 2048);
-            if (!noStdOut)
-                std::cout << "Input:\n Filename: " << inFile << "\n Channels: " << numChannels << "\n SampleRate: " << wav.GetSampleRate()
-                          << "\n Duration (sec): " << totalSamples / wav.GetSampleRate() << "\nOutput:\n Filename: " << outFile
-                          << "\n Codec: ATRAC3Plus" << std::endl;
-            TPCMEngine engine(4096, numChannels, [&wav](float* dst, size_t frames) { return wav.Read(dst, frames); });
-            TAt3PEncoder encoder(std::move(out), (int)numChannels, batch > 64 ? 64 : batch, device);
-            auto lambda = encoder.GetLambda();
-            uint64_t processed = 0;
-            try {
-                while (totalSamples > (processed = engine.ApplyProcess(2048, lambda))) {
-                }
-            } catch (const TNoDataToRead&) {
-                std::cerr << "No more data to read from input" << std::endl;
-            }
-            encoder.Flush();
-            if (!noStdOut) std::cout << "\nDone" << std::endl;
-        } catch (const std::exception& ex) {
-            std::cerr << "Fatal error: " << ex.what() << std::endl;
-            return 1;
-        }
-        return 0;
-    }
-    if (codec == "atrac1") {
-        if (bfuIdxConst > 8) {
-            std::cerr << "ATRAC1 mode, --bfuidxconst is a index of max used BFU. Values [1;8] is allowed\n";
-            return 1;
-        }
-        try {
-            TEncodeInput wav(inFile, resample, device, level);
-            const size_t numChannels = wav.GetChannelNum();
-            const uint64_t totalSamples = wav.GetTotalSamples();
-            const uint64_t numFrames = numChannels * totalSamples / 512;   // main.cpp:312
-            EContainer cont;
-            if (container.empty()) cont = SelectAtrac1Container(outFile);
-            else if (container == "aea") cont = EContainer::AEA;
-            else if (container == "raw") cont = EContainer::RAW;
-            else throw std::runtime_error("unrecognized container: " + container);
-            TCompressedOutputPtr out = CreateAtrac1Output(cont, outFile, numChannels, (uint32_t)numFrames);
-            if (!noStdOut)
-                std::cout << "Input\n Filename: " << inFile << "\n Channels: " << numChannels << "\n SampleRate: " << wav.GetSampleRate()
-                          << "\n Duration (sec): " << totalSamples / wav.GetSampleRate() << "\nOutput:\n Filename: " << outFile
-                          << "\n Codec: ATRAC1" << std::endl;
-            TPCMEngine engine(4096, numChannels, [&wav](float* dst, size_t frames) { return wav.Read(dst, frames); });
-            TAtrac1Encoder encoder(std::move(out),
-                                   TAtrac1EncodeSettings(bfuIdxConst,
-                                                         noTransient ? TAtrac1EncodeSettings::EWindowMode::EWM_NOTRANSIENT
-                                                                     : TAtrac1EncodeSettings::EWindowMode::EWM_AUTO,
-                                                         winMask),
-                                   batch, device);
-            auto lambda = encoder.GetLambda();
-            uint64_t processed = 0;
-            try {
-                while (totalSamples > (processed = engine.ApplyProcess(512, lambda))) {
-                }
-            } catch (const TNoDataToRead&) {
-                std::cerr << "No more data to read from input" << std::endl;
-            }
-            encoder.Flush();
-            if (!noStdOut) std::cout << "\nDone" << std::endl;
-        } catch (const std::exception& ex) {
-            std::cerr << "Fatal error: " << ex.what() << std::endl;
-            return 1;
-        }
-        return 0;
-    }
-    if (bitrate && (bitrate < 32 || bitrate > 384)) {
-        std::cerr << "bitrate must be in [32;384]\n";
-        return 1;
-    }
-    if (bfuIdxConst > 32) {
-        std::cerr << "bfuidxconst must be in [1;32]\n";
-        return 1;
-    }
-    try {
-        TEncodeInput wav(inFile, resample, device, level);
-        const size_t numChannels = wav.GetChannelNum();
-        const uint64_t totalSamples = wav.GetTotalSamples();
-        const uint64_t numFrames = totalSamples / 1024;
-
-        TAtrac3EncoderSettings settings;
-        settings.Bitrate = bitrate * 1024;   // the tool's kbit value reaches the settings as value * 1024 (main.cpp:676)
-        settings.NoGainControll = noGain;
-        settings.NoTonalComponents = noTonal;
-        settings.SourceChannels = (uint8_t)numChannels;
-        settings.BfuIdxConst = bfuIdxConst;
-
-        // container parameters come from the encoder context (GetContainerParamsForBitrate)
-        at3hip_config probe{};
-        probe.bitrate = (int32_t)settings.Bitrate;
-        probe.channels = (int32_t)numChannels;
-        probe.n_streams = 1;
-        probe.max_blocks = 1;
-        probe.device_id = device;
-        at3hip_ctx* pc = nullptr;
-        Check(at3hip_create(&probe, &pc), nullptr, "at3hip_create");
-        const uint32_t frameSize = (uint32_t)at3hip_frame_size(pc);
-        const bool js = at3hip_joint_stereo(pc) != 0;
-        at3hip_destroy(pc);
-
-        EContainer cont;
-        if (container.empty()) cont = SelectAtrac3Container(outFile);
-        else if (container == "oma") cont = EContainer::OMA;
-        else if (container == "riff") cont = EContainer::RIFF;
-        else if (container == "raw") cont = EContainer::RAW;
-        else throw std::runtime_error("unrecognized container: " + container);
-
-        TCompressedOutputPtr out = CreateAtrac3Output(cont, outFile, numChannels, (uint32_t)numFrames, frameSize, js);
-        if (!noStdOut)
-            std::cout << "Input:\n Filename: " << inFile << "\n Channels: " << numChannels << "\n SampleRate: " << wav.GetSampleRate()
-                      << "\n Duration (sec): " << totalSamples / wav.GetSampleRate() << "\nOutput:\n Filename: " << outFile
-                      << "\n Codec: ATRAC3\n Bitrate: " << (frameSize == 384 ? 132300 : frameSize * 44100u * 8u / 1024u) << std::endl;
-
-        TPCMEngine engine(4096, numChannels, [&wav](float* dst, size_t frames) { return wav.Read(dst, frames); });
-        TAtrac3Encoder encoder(std::move(out), std::move(settings), batch, device);
-        auto lambda = encoder.GetLambda();
-        uint64_t processed = 0;
-        try {
-            while (totalSamples > (processed = engine.ApplyProcess(1024, lambda))) {
-            }
-        } catch (const TNoDataToRead&) {
-            std::cerr << "No more data to read from input" << std::endl;
-        }
-        encoder.Flush();
-        if (level.On && !noStdOut) {   // what TScaler::Scale would still have clamped after the gain (at3hip_get_counters)
-            const at3hip_counters c = encoder.Counters();
-            std::cout << "clipping: " << c.scale_overflow << " blocks, " << c.clipped_values << " values" << std::endl;
-        }
-        if (!noStdOut) std::cout << "\nDone" << std::endl;
-    } catch (const std::exception& ex) {
-        std::cerr << "Fatal error: " << ex.what() << std::endl;
-        return 1;
-    }
-    return 0;
+    if ((o.codec != "atrac3" && o.codec != "atrac1" && o.codec != "atrac3plus") || o.inFile.empty() || o.outFile.empty() || o.rate) return usage();
+    if (!o.level.On && (o.peakGiven || o.level.TruePeak)) return usage();   // --peak and --truepeak belong to --loudness (or --measure)
+    if (o.codec == "atrac3plus") return encode<TAtrac3PlusEncode>(o);
+    if (o.codec == "atrac1") return encode<TAtrac1Encode>(o);
+    return encode<TAtrac3Encode>(o);
 }
