@@ -54,11 +54,14 @@ SYMBOLS = ["at3hip_encode_s16", "at3hip_create", "at3hip_destroy", "at3hip_frame
            # the loudness and true-peak meter (include/at3hip_loudness.h, listed in at3hip.h's version notes)
            "at3hip_loudness_create", "at3hip_loudness_destroy", "at3hip_loudness_last_error", "at3hip_loudness_reset",
            "at3hip_loudness_sync", "at3hip_loudness_set_stream", "at3hip_loudness_process", "at3hip_loudness_finish",
-           "at3hip_loudness_read_hops", "at3hip_loudness_apply", "at3hip_loudness_gate", "at3hip_loudness_gain"]
+           "at3hip_loudness_read_hops", "at3hip_loudness_apply", "at3hip_loudness_gate", "at3hip_loudness_gain",
+           # 16-bit PCM input of the resampler and the meter (listed in at3hip.h's version notes)
+           "at3hip_resampler_process_s16", "at3hip_loudness_process_s16", "at3hip_loudness_apply_s16"]
 AT3HIP_DECODE_S16 = 8
+AT3HIP_RESAMPLE_OUT_S16 = 8                        # include/at3hip_resample.h: 16-bit output of the resampler
 # include/at1hip.h
 AT1_SYMBOLS = ["at1hip_create", "at1hip_destroy", "at1hip_last_error", "at1hip_encode", "at1hip_reset", "at1hip_get_timings",
-               "at1hip_read_tap", "at1hip_host_tables", "at1hip_sync",
+               "at1hip_read_tap", "at1hip_host_tables", "at1hip_sync", "at1hip_encode_short",
                # the decoder (ABI 1.6)
                "at1hip_decoder_create", "at1hip_decoder_destroy", "at1hip_decoder_last_error", "at1hip_decode", "at1hip_decoder_sync",
                "at1hip_decoder_reset", "at1hip_decoder_get_counters", "at1hip_decoder_set_stream"]
@@ -66,7 +69,7 @@ AT1HIP_DECODE_S16 = 8
 # include/at3phip.h
 AT3P_SYMBOLS = ["at3phip_create", "at3phip_destroy", "at3phip_last_error", "at3phip_reset", "at3phip_pqf_analyse", "at3phip_mdct",
                 "at3phip_pqf_mdct", "at3phip_get_timings", "at3phip_host_tables", "at3phip_write_frames", "at3phip_encode_frames",
-                "at3phip_get_write_timing", "at3phip_host_write_tables", "at3phip_sync",
+                "at3phip_get_write_timing", "at3phip_host_write_tables", "at3phip_sync", "at3phip_encode_frames_short",
                 "at3phip_decoder_create", "at3phip_decoder_destroy", "at3phip_decoder_last_error", "at3phip_decode",
                 "at3phip_decoder_sync", "at3phip_decoder_reset", "at3phip_decoder_get_counters", "at3phip_decoder_set_stream",
                 "at3phip_decoder_host_tables", "at3phip_decoder_host_tone_tables"]
@@ -213,6 +216,10 @@ def load_library(path=None):
     lib.at1hip_last_error.argtypes = [vp]
     lib.at1hip_last_error.restype = ctypes.c_char_p
     lib.at1hip_encode.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
+    if hasattr(lib, "at1hip_encode_short"):   # 16-bit PCM input (added under ABI 1.6, see at3hip.h's version list)
+        lib.at1hip_encode_short.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
+    if hasattr(lib, "at3phip_encode_frames_short"):
+        lib.at3phip_encode_frames_short.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
     lib.at1hip_reset.argtypes = [vp]
     lib.at1hip_sync.argtypes = [vp]
     lib.at1hip_get_timings.argtypes = [vp, ctypes.POINTER(At1Timings)]
@@ -261,6 +268,8 @@ def load_library(path=None):
         lib.at3hip_resampler_destroy.restype = None
         lib.at3hip_resampler_last_error.restype = ctypes.c_char_p
         lib.at3hip_resampler_max_out.restype = i32
+        if hasattr(lib, "at3hip_resampler_process_s16"):   # 16-bit PCM input
+            lib.at3hip_resampler_process_s16.argtypes = [vp, vp, i32, vp, i32p, ctypes.c_uint32]
     if hasattr(lib, "at3hip_loudness_create"):   # the loudness meter (added under ABI 1.6, see at3hip.h's version list)
         f32p, resp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(LoudnessResult)
         for name, argtypes in (("create", [ctypes.POINTER(LoudnessConfig), ctypes.POINTER(vp)]), ("destroy", [vp]),
@@ -271,12 +280,23 @@ def load_library(path=None):
             getattr(lib, "at3hip_loudness_" + name).argtypes = argtypes
         lib.at3hip_loudness_destroy.restype = None
         lib.at3hip_loudness_last_error.restype = ctypes.c_char_p
+        if hasattr(lib, "at3hip_loudness_process_s16"):   # 16-bit PCM input
+            lib.at3hip_loudness_process_s16.argtypes = [vp, vp, i32, ctypes.c_uint32]
+            lib.at3hip_loudness_apply_s16.argtypes = [vp, vp, i32, vp, vp, ctypes.c_uint32]
     _lib_cache[path] = lib
     return lib
 
 
 def _vp(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _s16_entry(lib, name):
+    """the 16-bit entry point `name` of lib; a library that predates it is an error (there is no widening on the host instead)"""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise At3HipError(f"libat3hip.so predates 16-bit PCM input (no {name}): rebuild it")
+    return fn
 
 
 class _Context:
@@ -573,8 +593,30 @@ class At1Hip(_Context):
         return out
 
     def encode_device(self, pcm_ptr, n_blocks, out_ptr, asynchronous=False):
+        """Device-resident float32 PCM / frames (raw pointers). The context's stream is non-blocking (at3hip.h, DEVICE BUFFERS
+        AND STREAMS): it waits for no other stream, so whatever produces the PCM must be complete before the call, and with
+        asynchronous=True (AT3HIP_ASYNC) both buffers stay untouched until sync()."""
         self._check(self.lib.at1hip_encode(self.ctx, ctypes.c_void_p(pcm_ptr), n_blocks, ctypes.c_void_p(out_ptr),
                                            AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)), "at1hip_encode")
+
+    def encode_s16(self, pcm):
+        """pcm int16 [n_streams, n_blocks, 512, channels] (host) -> uint8 [n_streams, n_blocks, channels, 212]
+        (at1hip_encode_short): the frames of encode() on pcm / 32768 as float32, bit for bit; the samples cross the bus as
+        16-bit and are widened by the first kernel. Calls of both kinds may alternate."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (512, self.channels), pcm.shape
+        nb = pcm.shape[1]
+        out = np.zeros((self.n_streams, nb, self.channels, self.FRAME), dtype=np.uint8)
+        self._check(_s16_entry(self.lib, "at1hip_encode_short")(self.ctx, _vp(pcm), nb, _vp(out), 0), "at1hip_encode_short")
+        return out
+
+    def encode_device_s16(self, pcm_ptr, n_blocks, out_ptr, asynchronous=False):
+        """Device-resident int16 PCM / frames (raw pointers; the PCM needs only 2-byte alignment). The context's stream is
+        non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): it waits for no other stream, so whatever produces the PCM must be
+        complete before the call, and with asynchronous=True (AT3HIP_ASYNC) both buffers stay untouched until sync()."""
+        self._check(_s16_entry(self.lib, "at1hip_encode_short")(
+            self.ctx, ctypes.c_void_p(pcm_ptr), n_blocks, ctypes.c_void_p(out_ptr),
+            AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)), "at1hip_encode_short")
 
     def read_tap(self, kind, dtype, shape):
         out = np.zeros(shape, dtype=dtype)
@@ -819,10 +861,31 @@ class At3pHip(_Context):
         return out
 
     def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
-        """asynchronous=True only queues the call (AT3HIP_ASYNC): sync() before the frames are read."""
+        """asynchronous=True only queues the call (AT3HIP_ASYNC): sync() before the frames are read. The context's streams are
+        non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): they wait for no other stream, so whatever produces the PCM must be
+        complete before the call."""
         self._check(self.lib.at3phip_encode_frames(self.ctx, ctypes.c_void_p(pcm_ptr), n_frames, ctypes.c_void_p(frames_ptr),
                                                    AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)),
                     "at3phip_encode_frames")
+
+    def encode_frames_s16(self, pcm):
+        """pcm int16 [S, F, 2048, C] (host) -> frames uint8 [S, F, 2048] (at3phip_encode_frames_short): the frames of
+        encode_frames() on pcm / 32768 as float32, bit for bit; the samples cross the bus as 16-bit and are widened by the
+        filter bank. Calls of both kinds may alternate."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (2048, self.channels), pcm.shape
+        nf = pcm.shape[1]
+        out = np.zeros((self.n_streams, nf, 2048), np.uint8)
+        self._check(_s16_entry(self.lib, "at3phip_encode_frames_short")(self.ctx, _vp(pcm), nf, _vp(out), 0), "at3phip_encode_frames_short")
+        return out
+
+    def encode_frames_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
+        """Device-resident int16 PCM / frames (raw pointers; the PCM needs only 2-byte alignment). The context's streams are
+        non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): they wait for no other stream, so whatever produces the PCM must
+        be complete before the call, and with asynchronous=True (AT3HIP_ASYNC) both buffers stay untouched until sync()."""
+        self._check(_s16_entry(self.lib, "at3phip_encode_frames_short")(
+            self.ctx, ctypes.c_void_p(pcm_ptr), n_frames, ctypes.c_void_p(frames_ptr),
+            AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)), "at3phip_encode_frames_short")
 
     def timings(self):
         a, b, w = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
@@ -873,7 +936,9 @@ class HipResampler(_Context):
         self.L, self.M, self.K = resampler_shape(self.in_rate, self.out_rate, lib_path)
 
     def process_ptr(self, in_ptr, n_in, out_ptr, flags):
-        """Raw pointers and at3hip_resampler_process flags; returns the outputs per stream."""
+        """Raw pointers and at3hip_resampler_process flags (AT3HIP_RESAMPLE_OUT_S16: out is int16); returns the outputs per
+        stream. The resampler's stream is non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): it waits for no other stream, so
+        whatever produces a device buffer must be complete before the call (or share the stream given to set_stream)."""
         n = ctypes.c_int32()
         self._check(self.lib.at3hip_resampler_process(self.ctx, ctypes.c_void_p(in_ptr), int(n_in), ctypes.c_void_p(out_ptr),
                                                       ctypes.byref(n), int(flags)), "at3hip_resampler_process")
@@ -885,19 +950,49 @@ class HipResampler(_Context):
                     "at3hip_resampler_flush")
         return n.value
 
-    def process(self, pcm):
-        """pcm float32 [n_streams, n_in, channels] (host) -> float32 [n_streams, n_out, channels]"""
-        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
-        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
-        out = np.zeros((self.n_streams, self.max_out, self.channels), np.float32)
-        n = self.process_ptr(pcm.ctypes.data, pcm.shape[1], out.ctypes.data, 0)
+    def process_s16_ptr(self, in_ptr, n_in, out_ptr, flags):
+        """Raw pointers and at3hip_resampler_process_s16 flags (int16 input, 2-byte alignment is enough; out float32, or int16
+        with AT3HIP_RESAMPLE_OUT_S16); returns the outputs per stream. The resampler's stream is non-blocking (at3hip.h, DEVICE
+        BUFFERS AND STREAMS): it waits for no other stream, so whatever produces a device buffer must be complete before the
+        call (or share the stream given to set_stream), and with AT3HIP_ASYNC the buffers stay untouched until sync()."""
+        n = ctypes.c_int32()
+        self._check(_s16_entry(self.lib, "at3hip_resampler_process_s16")(
+            self.ctx, ctypes.c_void_p(in_ptr), int(n_in), ctypes.c_void_p(out_ptr), ctypes.byref(n), int(flags)),
+            "at3hip_resampler_process_s16")
+        return n.value
+
+    def _host_out(self, out_s16):
+        return np.zeros((self.n_streams, self.max_out, self.channels), np.int16 if out_s16 else np.float32)
+
+    def _trim(self, out, n):
         return np.ascontiguousarray(out.reshape(-1)[: self.n_streams * n * self.channels].reshape(self.n_streams, n, self.channels))
 
-    def flush(self):
-        """The remaining outputs of every stream, float32 [n_streams, n_out, channels]; then the start state."""
-        out = np.zeros((self.n_streams, self.max_out, self.channels), np.float32)
-        n = self.flush_ptr(out.ctypes.data, 0)
-        return np.ascontiguousarray(out.reshape(-1)[: self.n_streams * n * self.channels].reshape(self.n_streams, n, self.channels))
+    def process(self, pcm, out_s16=False):
+        """pcm float32 [n_streams, n_in, channels] (host) -> float32 [n_streams, n_out, channels]; with out_s16=True int16,
+        lrintf(clamp(x, -1, 1) * 32767) of the float output (AT3HIP_RESAMPLE_OUT_S16). A blocking call on the resampler's own
+        non-blocking stream (at3hip.h, DEVICE BUFFERS AND STREAMS): host memory in, host memory out, complete on return."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
+        out = self._host_out(out_s16)
+        n = self.process_ptr(pcm.ctypes.data, pcm.shape[1], out.ctypes.data, AT3HIP_RESAMPLE_OUT_S16 if out_s16 else 0)
+        return self._trim(out, n)
+
+    def process_s16(self, pcm, out_s16=False):
+        """pcm int16 [n_streams, n_in, channels] (host) -> what process() gives on pcm / 32768 as float32, bit for bit
+        (at3hip_resampler_process_s16): the samples cross the bus as 16-bit and are widened by the kernel. Calls of both kinds
+        may alternate. Blocking, as process()."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
+        out = self._host_out(out_s16)
+        n = self.process_s16_ptr(pcm.ctypes.data, pcm.shape[1], out.ctypes.data, AT3HIP_RESAMPLE_OUT_S16 if out_s16 else 0)
+        return self._trim(out, n)
+
+    def flush(self, out_s16=False):
+        """The remaining outputs of every stream, float32 (int16 with out_s16=True) [n_streams, n_out, channels]; then the start
+        state. Blocking, as process()."""
+        out = self._host_out(out_s16)
+        n = self.flush_ptr(out.ctypes.data, AT3HIP_RESAMPLE_OUT_S16 if out_s16 else 0)
+        return self._trim(out, n)
 
     def _device_out(self, out, device):
         import torch
@@ -990,6 +1085,23 @@ class HipLoudness(_Context):
         assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
         self.process_ptr(pcm.ctypes.data, pcm.shape[1], 0)
 
+    def process_s16_ptr(self, in_ptr, n_in, flags):
+        """Raw pointer (int16 samples, 2-byte alignment is enough) and at3hip_loudness_process_s16 flags; stream ordering as in
+        the class docstring: the meter's non-blocking stream waits for no other stream."""
+        self._check(_s16_entry(self.lib, "at3hip_loudness_process_s16")(self.ctx, ctypes.c_void_p(in_ptr), int(n_in), int(flags)),
+                    "at3hip_loudness_process_s16")
+        self.n_samples += int(n_in)
+
+    def process_s16(self, pcm):
+        """pcm int16 [n_streams, n_in, channels] (host): what process() measures on pcm / 32768 as float32, bit for bit
+        (at3hip_loudness_process_s16); the samples cross the bus as 16-bit and are widened by the kernels. Calls of both kinds
+        may alternate. A blocking call on the meter's own non-blocking stream (see the class docstring). Measured: the meter is
+        compute-bound and its hop kernel takes 1.5 times as long on 16-bit samples, so from host memory this is 1.1 times as
+        fast as process(), and on device-resident floats process_device() is the faster call."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
+        self.process_s16_ptr(pcm.ctypes.data, pcm.shape[1], 0)
+
     def process_device(self, pcm, asynchronous=False, ordered=True):
         """pcm: torch float32 [n_streams, n_in, channels] on this meter's device (see the class docstring for the ordering)."""
         import torch
@@ -1023,6 +1135,22 @@ class HipLoudness(_Context):
         assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
         out = np.zeros_like(pcm)
         self.apply_ptr(pcm.ctypes.data, pcm.shape[1], gains, out.ctypes.data, 0)
+        return out
+
+    def apply_s16_ptr(self, in_ptr, n_in, gains, out_ptr, flags):
+        """Raw pointers (int16 in, float32 out) and at3hip_loudness_apply_s16 flags; stream ordering as in the class docstring."""
+        gains = np.ascontiguousarray(gains, np.float32)
+        assert gains.shape == (self.n_streams,), gains.shape
+        self._check(_s16_entry(self.lib, "at3hip_loudness_apply_s16")(self.ctx, ctypes.c_void_p(in_ptr), int(n_in), _vp(gains),
+                                                                      ctypes.c_void_p(out_ptr), int(flags)), "at3hip_loudness_apply_s16")
+
+    def apply_s16(self, pcm, gains):
+        """pcm int16 [n_streams, n_in, channels] (host), gains float32 [n_streams] -> (pcm / 32768 as float32) * gains[:, None, None]
+        as float32 (at3hip_loudness_apply_s16). A blocking call on the meter's own non-blocking stream (see the class docstring)."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
+        out = np.zeros(pcm.shape, np.float32)
+        self.apply_s16_ptr(pcm.ctypes.data, pcm.shape[1], gains, out.ctypes.data, 0)
         return out
 
     def apply_device(self, pcm, gains, out, asynchronous=False, ordered=True):

@@ -10,6 +10,7 @@
 #pragma once
 #include "at1_tables.hpp"
 #include "at3_common.hpp"
+#include "at3_pcm_in.hpp"
 
 namespace at1 {
 
@@ -105,7 +106,7 @@ __device__ __forceinline__ float at1_log10f(const LogfTab* L, float x)
 
 struct FrontParams {
     const Tables* T;
-    const float* pcm;    // [S][n_frames * 512][nch]
+    const void* pcm;     // [S][n_frames * 512][nch], float or int16_t: the kernel's template parameter
     const float* hist;   // [S][512][nch]: the PCM block before this call's first one
     int32_t n_frames, nch;
     int32_t first;       // call starts at the stream start: the detectors' LastEnergy is 0.0
@@ -172,6 +173,8 @@ __device__ __forceinline__ float mdct_in(const float* src, const float* sine, in
 // rendezvous only (the LDS pipeline executes one wavefront's instructions in order), the rotation tables, the window and
 // the logarithm's table are read where they are used (they stay in the L1 of a CU that runs nothing else) and the
 // scale-factor table lives in the lanes: 11 KB of LDS per unit, fourteen units per CU.
+// Pcm: the type of the call's PCM, float or int16_t (at3_pcm_in.hpp); the carried block p.hist is float for both.
+template <typename Pcm>
 __global__ __launch_bounds__(64) void k_at1_front(FrontParams p)
 {
     // Two regions are reused once their first tenant is dead: the PCM window becomes the spectrum; the first QMF stage's
@@ -208,14 +211,22 @@ __global__ __launch_bounds__(64) void k_at1_front(FrontParams p)
     const double logf_v = (&T->logf_tab[0][0])[lane < 36 ? lane : 35];   // 16 x 2 table entries, ln 2, three coefficients
     __builtin_amdgcn_sched_barrier(0);
     {
+        const size_t row_len = (size_t)p.n_frames * 512 * nch;
+        const Pcm* const row = static_cast<const Pcm*>(p.pcm) + (size_t)s * row_len;   // the stream's samples of this call
+        const bool pairs = at3::pcm_pairs(row);
         float v[13];
 #pragma unroll
         for (int r = 0; r < 13; ++r) {
             const int j = lane + 64 * r;
             const int t = 512 * f - 288 + j;
-            v[r] = j >= 800 ? 0.0f
-                 : t >= 0   ? p.pcm[((size_t)s * p.n_frames * 512 + t) * nch + ch]
-                            : p.hist[((size_t)s * 512 + (512 + t)) * nch + ch];
+            if constexpr (std::is_same<Pcm, float>::value)
+                v[r] = j >= 800 ? 0.0f
+                     : t >= 0   ? static_cast<const float*>(p.pcm)[((size_t)s * p.n_frames * 512 + t) * nch + ch]
+                                : p.hist[((size_t)s * 512 + (512 + t)) * nch + ch];
+            else
+                v[r] = j >= 800 ? 0.0f
+                     : t >= 0   ? at3::pcm_at(row, (size_t)t * nch + ch, row_len, pairs)
+                                : p.hist[((size_t)s * 512 + (512 + t)) * nch + ch];
         }
 #pragma unroll
         for (int r = 0; r < 13; ++r)
@@ -872,13 +883,20 @@ __global__ __launch_bounds__(256) void k_at1_alloc_pack(PackParams p)
 }
 
 // carry the last PCM block of the call
-__global__ void k_at1_state(const float* pcm, float* hist, int n_frames, int nch, int n_streams)
+template <typename T>
+__global__ void k_at1_state(const T* pcm, float* hist, int n_frames, int nch, int n_streams)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int per = 512 * nch;
     if (i >= n_streams * per) return;
     const int s = i / per, r = i - s * per;
-    hist[i] = pcm[((size_t)s * n_frames + (n_frames - 1)) * per + r];
+    if constexpr (std::is_same<T, float>::value) {
+        hist[i] = pcm[((size_t)s * n_frames + (n_frames - 1)) * per + r];
+    } else {
+        const size_t row_len = (size_t)n_frames * per;
+        const T* const row = pcm + (size_t)s * row_len;
+        hist[i] = at3::pcm_at(row, (size_t)(n_frames - 1) * per + r, row_len, at3::pcm_pairs(row));
+    }
 }
 
 }  // namespace at1

@@ -24,6 +24,7 @@ struct at1hip_ctx {
     bool tm_pending = false;      // a call's stage events have not been read yet (AT3HIP_ASYNC)
     Tables* d_tables = nullptr;
     float* d_pcm_in = nullptr;    // staging for host PCM [S][max_blocks][512][nch]
+    int16_t* d_pcm_s16 = nullptr; // the same as 16-bit samples, allocated by the first at1hip_encode_short that takes host memory
     float* d_hist = nullptr;      // [S][512][nch] last PCM block of the previous call
     float* d_specs = nullptr;     // [S][B][nch][512]
     float* d_values = nullptr;    // [S][B][nch][512]
@@ -117,7 +118,7 @@ void at1hip_destroy(at1hip_ctx* c)
     if (!c) return;
     at3host::DeviceGuard guard(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void* bufs[] = {c->d_tables, c->d_pcm_in, c->d_hist,       c->d_specs,      c->d_values, c->d_energy,
+    void* bufs[] = {c->d_tables, c->d_pcm_in, c->d_pcm_s16, c->d_hist,       c->d_specs,      c->d_values, c->d_energy,
                     c->d_sfi,    c->d_mask,   c->d_loud_ch,    c->d_loud_state, c->d_loud_track, c->d_out};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -137,8 +138,16 @@ int at1hip_reset(at1hip_ctx* c)
     return reset_state(c);
 }
 
-int at1hip_encode(at1hip_ctx* c, const float* pcm, int32_t n_blocks, uint8_t* out_frames, uint32_t flags)
+}  // extern "C"
+
+namespace {
+
+// at1hip_encode (T = float) and at1hip_encode_short (T = int16_t): the sample type is the front kernel's and the state kernel's
+// template parameter, everything behind them is shared.
+template <typename T>
+int encode_impl(at1hip_ctx* c, const T* pcm, int32_t n_blocks, uint8_t* out_frames, uint32_t flags)
 {
+    constexpr bool kShort = sizeof(T) == sizeof(int16_t);
     if (!c || !pcm || !out_frames || n_blocks < 1 || n_blocks > c->cfg.max_blocks)
         return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
     at3host::DeviceGuard guard(c->device);
@@ -146,10 +155,20 @@ int at1hip_encode(at1hip_ctx* c, const float* pcm, int32_t n_blocks, uint8_t* ou
     const size_t S = c->cfg.n_streams, C = c->cfg.channels, F = (size_t)n_blocks;
     hipStream_t st = c->stream;
     const bool timed = !(flags & AT3HIP_ASYNC);   // a queued call carries no stage-timing events (not free between the kernels): its timings read zero
-    const float* d_pcm = pcm;
+    const T* d_pcm = pcm;
     if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(c, hipMemcpyAsync(c->d_pcm_in, pcm, S * F * 512 * C * sizeof(float), hipMemcpyHostToDevice, st));
-        d_pcm = c->d_pcm_in;
+        T* staging;
+        if constexpr (kShort) {   // 16-bit samples cross the bus as they are (half the bytes) and are widened by the front kernel's loads
+            if (!c->d_pcm_s16) {
+                const int rc = dev_alloc(c, &c->d_pcm_s16, S * (size_t)c->cfg.max_blocks * 512 * C);
+                if (rc != AT3HIP_OK) return rc;
+            }
+            staging = c->d_pcm_s16;
+        } else {
+            staging = c->d_pcm_in;
+        }
+        HIPCHK(c, hipMemcpyAsync(staging, pcm, S * F * 512 * C * sizeof(T), hipMemcpyHostToDevice, st));
+        d_pcm = staging;
     }
     uint8_t* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? out_frames : c->d_out;
 
@@ -169,7 +188,7 @@ int at1hip_encode(at1hip_ctx* c, const float* pcm, int32_t n_blocks, uint8_t* ou
     fp.sfi = c->d_sfi;
     fp.mask = c->d_mask;
     fp.loud_ch = c->d_loud_ch;
-    hipLaunchKernelGGL(k_at1_front, dim3((unsigned)F, (unsigned)(S * C)), dim3(64), 0, st, fp);
+    hipLaunchKernelGGL(k_at1_front<T>, dim3((unsigned)F, (unsigned)(S * C)), dim3(64), 0, st, fp);
     HIPCHK(c, hipGetLastError());
     LoudParams lp;
     lp.T = c->d_tables;
@@ -178,7 +197,7 @@ int at1hip_encode(at1hip_ctx* c, const float* pcm, int32_t n_blocks, uint8_t* ou
     lp.n_units = (int32_t)(S * F * C);
     hipLaunchKernelGGL(k_at1_loud, dim3((unsigned)((S * F * C + kAt1LoudUnits - 1) / kAt1LoudUnits)), dim3(256), 0, st, lp);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_at1_state, dim3((unsigned)((S * 512 * C + 255) / 256)), dim3(256), 0, st, d_pcm, c->d_hist, n_blocks, (int)C,
+    hipLaunchKernelGGL(k_at1_state<T>, dim3((unsigned)((S * 512 * C + 255) / 256)), dim3(256), 0, st, d_pcm, c->d_hist, n_blocks, (int)C,
                        (int)S);
     if (timed) HIPCHK(c, hipEventRecord(c->ev[1], st));
 
@@ -216,6 +235,20 @@ int at1hip_encode(at1hip_ctx* c, const float* pcm, int32_t n_blocks, uint8_t* ou
     // AT3HIP_ASYNC: the call is queued (one stream: consecutive calls follow each other on the device without the host in between);
     // at1hip_sync waits and reads the last call's timings
     return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at1hip_sync(c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int at1hip_encode(at1hip_ctx* c, const float* pcm, int32_t n_blocks, uint8_t* out_frames, uint32_t flags)
+{
+    return encode_impl(c, pcm, n_blocks, out_frames, flags);
+}
+
+int at1hip_encode_short(at1hip_ctx* c, const int16_t* pcm, int32_t n_blocks, uint8_t* out_frames, uint32_t flags)
+{
+    return encode_impl(c, pcm, n_blocks, out_frames, flags);
 }
 
 int at1hip_sync(at1hip_ctx* c)

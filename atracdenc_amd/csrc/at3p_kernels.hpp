@@ -8,6 +8,7 @@
 // k_at3p_state after them. Float operations are the reference's, in its order, without contraction.
 #pragma once
 #include "at3_common.hpp"
+#include "at3_pcm_in.hpp"
 #include "at3p_tables.hpp"
 
 namespace at3p {
@@ -20,12 +21,15 @@ constexpr int kOverlap = 368;    // PROTO_SZ - SUBBANDS_NUM
 
 struct PqfParams {
     const Tables* T;
-    const float* pcm;       // [S][F][2048][nch] interleaved (what TAt3PEnc::EncodeFrame receives, at3p.cpp:93-97)
+    const void* pcm;        // [S][F][2048][nch] interleaved (what TAt3PEnc::EncodeFrame receives, at3p.cpp:93-97), float or int16_t:
+                            // the kernel's template parameter
     const float* hist;      // [S][nch][368]: the last 368 samples of the previous call
     float* bands;           // [S][F][nch][16][128]
     int32_t n_frames, nch;
 };
 
+// Pcm: the type of the call's PCM, float or int16_t (at3_pcm_in.hpp); the carried samples p.hist are float for both.
+template <typename Pcm>
 __global__ __launch_bounds__(256) void k_at3p_pqf(PqfParams p)
 {
     __shared__ __attribute__((aligned(16))) float s_x[kFrame + kOverlap];   // later: the frame's 16 x 128 output
@@ -62,10 +66,19 @@ __global__ __launch_bounds__(256) void k_at3p_pqf(PqfParams p)
         for (int i = 0; i < kIt; ++i) {
             const int j0 = tid + 256 * i, j = j0 < kTot ? j0 : kTot - 1;
             const int t = j - kOverlap;   // sample index inside the frame
-            const float* src = (t >= 0) ? &p.pcm[(((size_t)s * p.n_frames + f) * kFrame + t) * nch + ch]
-                             : (f > 0)  ? &p.pcm[(((size_t)s * p.n_frames + f - 1) * kFrame + kFrame + t) * nch + ch]
-                                        : &p.hist[((size_t)s * nch + ch) * kOverlap + j];
-            v[i] = *src;
+            if constexpr (std::is_same<Pcm, float>::value) {
+                const float* const pcm = static_cast<const float*>(p.pcm);
+                const float* src = (t >= 0) ? &pcm[(((size_t)s * p.n_frames + f) * kFrame + t) * nch + ch]
+                                 : (f > 0)  ? &pcm[(((size_t)s * p.n_frames + f - 1) * kFrame + kFrame + t) * nch + ch]
+                                            : &p.hist[((size_t)s * nch + ch) * kOverlap + j];
+                v[i] = *src;
+            } else {   // the stream's samples of this call are one row: sample f * 2048 + t of it, or the carried float
+                const size_t row_len = (size_t)p.n_frames * kFrame * nch;
+                const Pcm* const row = static_cast<const Pcm*>(p.pcm) + (size_t)s * row_len;
+                const long long at = (long long)f * kFrame + t;
+                v[i] = at >= 0 ? at3::pcm_at(row, (size_t)at * nch + ch, row_len, at3::pcm_pairs(row))
+                               : p.hist[((size_t)s * nch + ch) * kOverlap + j];
+            }
         }
 #pragma unroll
         for (int i = 0; i < kIt; ++i)
@@ -249,12 +262,19 @@ __global__ __launch_bounds__(256) void k_at3p_mdct(MdctParams p)
 }
 
 // carried state after a call: the last 368 input samples (PQF) / the windowed first halves of the last frame (MDCT)
-__global__ void k_at3p_pqf_state(const float* pcm, float* hist, int n_frames, int nch, int n_streams)
+template <typename T>
+__global__ void k_at3p_pqf_state(const T* pcm, float* hist, int n_frames, int nch, int n_streams)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_streams * nch * kOverlap) return;
     const int j = i % kOverlap, sc = i / kOverlap, ch = sc % nch, s = sc / nch;
-    hist[i] = pcm[(((size_t)s * n_frames + n_frames - 1) * kFrame + (kFrame - kOverlap) + j) * nch + ch];
+    if constexpr (std::is_same<T, float>::value) {
+        hist[i] = pcm[(((size_t)s * n_frames + n_frames - 1) * kFrame + (kFrame - kOverlap) + j) * nch + ch];
+    } else {
+        const size_t row_len = (size_t)n_frames * kFrame * nch;
+        const T* const row = pcm + (size_t)s * row_len;
+        hist[i] = at3::pcm_at(row, ((size_t)(n_frames - 1) * kFrame + (kFrame - kOverlap) + j) * nch + ch, row_len, at3::pcm_pairs(row));
+    }
 }
 __global__ void k_at3p_mdct_state(MdctParams p, float* hist, int n_streams)
 {

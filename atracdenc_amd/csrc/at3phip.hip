@@ -25,6 +25,7 @@ struct at3phip_ctx {
     hipEvent_t ev[5] = {};
     Tables* d_tables = nullptr;
     float* d_pcm_in = nullptr;     // staging for host PCM   [S][F][2048][nch]
+    int16_t* d_pcm_s16 = nullptr;  // the same as 16-bit samples, allocated by the first at3phip_encode_frames_short that takes host memory
     float* d_bands = nullptr;      // subband samples        [S][F][nch][16][128]
     float* d_specs = nullptr;      // staging for host specs [S][F][nch][2048]
     uint16_t* d_flags = nullptr;   // [S][F][nch]
@@ -63,7 +64,8 @@ int quiesce(at3phip_ctx* c)
     return AT3HIP_OK;
 }
 
-int launch_pqf(at3phip_ctx* c, const float* d_pcm, int n_frames, float* d_bands)
+template <typename T>
+int launch_pqf(at3phip_ctx* c, const T* d_pcm, int n_frames, float* d_bands)
 {
     const size_t S = c->cfg.n_streams, C = c->cfg.channels;
     PqfParams pp;
@@ -73,9 +75,9 @@ int launch_pqf(at3phip_ctx* c, const float* d_pcm, int n_frames, float* d_bands)
     pp.bands = d_bands;
     pp.n_frames = n_frames;
     pp.nch = (int)C;
-    hipLaunchKernelGGL(k_at3p_pqf, dim3((unsigned)n_frames, (unsigned)(S * C)), dim3(256), 0, c->stream, pp);
+    hipLaunchKernelGGL(k_at3p_pqf<T>, dim3((unsigned)n_frames, (unsigned)(S * C)), dim3(256), 0, c->stream, pp);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_at3p_pqf_state, dim3((unsigned)((S * C * kOverlap + 255) / 256)), dim3(256), 0, c->stream, d_pcm, c->d_pqf_hist,
+    hipLaunchKernelGGL(k_at3p_pqf_state<T>, dim3((unsigned)((S * C * kOverlap + 255) / 256)), dim3(256), 0, c->stream, d_pcm, c->d_pqf_hist,
                        n_frames, (int)C, (int)S);
     HIPCHK(c, hipGetLastError());
     return AT3HIP_OK;
@@ -193,7 +195,7 @@ void at3phip_destroy(at3phip_ctx* c)
         if (c->ev_write_done[q]) (void)hipEventDestroy(c->ev_write_done[q]);
     }
     if (c->write_stream) (void)hipStreamDestroy(c->write_stream);
-    void* bufs[] = {c->d_tables, c->d_pcm_in, c->d_bands, c->d_specs, c->d_flags, c->d_pqf_hist, c->d_mdct_hist, c->d_wtables, c->d_frames};
+    void* bufs[] = {c->d_tables, c->d_pcm_in, c->d_pcm_s16, c->d_bands, c->d_specs, c->d_flags, c->d_pqf_hist, c->d_mdct_hist, c->d_wtables, c->d_frames};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (auto& e : c->ev)
@@ -322,17 +324,35 @@ int at3phip_write_frames(at3phip_ctx* c, const float* specs, int32_t n_frames, c
     return AT3HIP_OK;
 }
 
-int at3phip_encode_frames(at3phip_ctx* c, const float* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
+}  // extern "C"
+
+namespace {
+
+// at3phip_encode_frames (T = float) and at3phip_encode_frames_short (T = int16_t): the sample type is the filter bank's and its
+// state kernel's template parameter, everything behind them is shared.
+template <typename T>
+int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
 {
+    constexpr bool kShort = sizeof(T) == sizeof(int16_t);
     if (!c || !pcm || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
     at3host::DeviceGuard guard(c->device);
     HIPCHK(c, guard.error());
     const size_t items = (size_t)c->cfg.n_streams * n_frames;
     const size_t n = items * c->cfg.channels * 2048;
-    const float* d_pcm = pcm;
+    const T* d_pcm = pcm;
     if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(c, hipMemcpyAsync(c->d_pcm_in, pcm, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        d_pcm = c->d_pcm_in;
+        T* staging;
+        if constexpr (kShort) {   // 16-bit samples cross the bus as they are (half the bytes) and are widened by the filter bank's loads
+            if (!c->d_pcm_s16) {
+                const int rc = dev_alloc(c, &c->d_pcm_s16, (size_t)c->cfg.n_streams * c->cfg.max_frames * c->cfg.channels * 2048);
+                if (rc != AT3HIP_OK) return rc;
+            }
+            staging = c->d_pcm_s16;
+        } else {
+            staging = c->d_pcm_in;
+        }
+        HIPCHK(c, hipMemcpyAsync(staging, pcm, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+        d_pcm = staging;
     }
     uint8_t* d_frames = (flags & AT3HIP_OUT_ON_DEVICE) ? frames : c->d_frames;
     const int par = (int)(c->enc_calls & 1);
@@ -364,6 +384,20 @@ int at3phip_encode_frames(at3phip_ctx* c, const float* pcm, int32_t n_frames, ui
     if (!timed) c->pqf_ms = c->mdct_ms = c->write_ms = 0.0f;
     if (flags & AT3HIP_ASYNC) return AT3HIP_OK;   // at3phip_sync is the completion point
     return at3phip_sync(c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int at3phip_encode_frames(at3phip_ctx* c, const float* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
+{
+    return encode_frames_impl(c, pcm, n_frames, frames, flags);
+}
+
+int at3phip_encode_frames_short(at3phip_ctx* c, const int16_t* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
+{
+    return encode_frames_impl(c, pcm, n_frames, frames, flags);
 }
 
 int at3phip_sync(at3phip_ctx* c)

@@ -30,6 +30,7 @@
 #include "../../include/at3hip_loudness.h"
 #include "../../include/at3hip_resample.h"
 #include "at3_host_util.hpp"
+#include "at3_pcm_in.hpp"
 
 using at3host::dev_alloc;
 using at3host::fail;
@@ -54,7 +55,7 @@ static_assert(kTile * kTiles == kWindow && kTile * kSumTile == 2 * kHop, "tiles 
 struct MeterParams {
     const float* carry;      // [S][kWindow][C]: samples base .. t_old - 1 of each stream (read)
     float* carry_next;       // [S][kWindow][C]: samples base_next .. t_old + n_in - 1 (written by k_carry)
-    const float* in;         // [S][n_in][C]
+    const void* in;          // [S][n_in][C], float or int16_t: the kernels' template parameter T
     double* z;               // [max_hops][S][C]
     unsigned* peaks;         // [S][2][2]: bits of the sample peak and of the largest |u|, per channel
     const float* hp;         // [4][144]
@@ -76,7 +77,72 @@ __device__ __forceinline__ const float* element_ptr(const MeterParams& p, size_t
 {
     const long long told = p.t_old * C, lo = p.base * C, hi = told + (long long)p.n_in * C - 1;
     const long long at = idx < lo ? lo : (idx > hi ? hi : idx);
-    return at >= told ? p.in + s * (size_t)p.n_in * C + (size_t)(at - told) : p.carry + s * (size_t)kWindow * C + (size_t)(at - lo);
+    return at >= told ? static_cast<const float*>(p.in) + s * (size_t)p.n_in * C + (size_t)(at - told) : p.carry + s * (size_t)kWindow * C + (size_t)(at - lo);
+}
+
+// What element_ptr's address holds, in two steps so that a run of loads stays in flight before the first value is used:
+// element_bits is the load, element_value makes the float of it. For floats the bits are the value. 16-bit input (T = int16_t)
+// is widened in element_value; the carry buffer is float for both kinds of call. A row of 16-bit samples that starts 4-byte
+// aligned and has an even number of samples is read as 32-bit sample pairs (PAIRS): the address is selected first - the pair's
+// dword in the row, or the float in the carry buffer - and ONE dword load follows, as for floats. Otherwise a fetch is two
+// 16-bit loads, again from addresses selected first (the sample itself, or the two halves of the carried float). Which form a call takes is decided once per kernel from its arguments (all_pairs: with the call's pointer
+// 4-byte aligned and n_in * C even, every stream's row is aligned and even - every stereo call behind an aligned pointer, and
+// mono calls of even length), so no branch sits between the loads, no lane diverges and no load reaches outside its row.
+template <typename T>
+struct ElementBits { using type = uint32_t; };
+template <>
+struct ElementBits<float> { using type = float; };
+
+template <typename T>
+__device__ __forceinline__ bool all_pairs(const MeterParams& p, int C)
+{
+    return sizeof(T) == sizeof(int16_t) && ((uintptr_t)p.in & 3u) == 0 && ((long long)p.n_in * C) % 2 == 0;
+}
+
+template <int C, typename T, bool PAIRS>
+__device__ __forceinline__ typename ElementBits<T>::type element_bits(const MeterParams& p, size_t s, long long idx)
+{
+    if constexpr (std::is_same<T, float>::value) {
+        return *element_ptr<C>(p, s, idx);
+    } else {
+        const long long told = p.t_old * C, lo = p.base * C, hi = told + (long long)p.n_in * C - 1;
+        const long long at = idx < lo ? lo : (idx > hi ? hi : idx);
+        const size_t n = (size_t)p.n_in * C;
+        const T* const row = static_cast<const T*>(p.in) + s * n;
+        const uint32_t* const carry = reinterpret_cast<const uint32_t*>(p.carry) + s * (size_t)kWindow * C;
+        if constexpr (PAIRS) {
+            const uint32_t* const src = at >= told ? reinterpret_cast<const uint32_t*>(row) + ((size_t)(at - told) >> 1) : carry + (size_t)(at - lo);
+            return *src;
+        } else {
+            // two 16-bit loads from addresses selected first: the sample twice (element_value takes either half), or the halves
+            // of the carried float
+            const uint16_t* const a = at >= told ? reinterpret_cast<const uint16_t*>(row) + (size_t)(at - told)
+                                                 : reinterpret_cast<const uint16_t*>(carry + (size_t)(at - lo));
+            const uint16_t* const b = at >= told ? a : a + 1;
+            return (uint32_t)*a | ((uint32_t)*b << 16);
+        }
+    }
+}
+
+template <int C, typename T>
+__device__ __forceinline__ float element_value(const MeterParams& p, long long idx, typename ElementBits<T>::type bits)
+{
+    if constexpr (std::is_same<T, float>::value) {
+        return bits;
+    } else {
+        const long long told = p.t_old * C, lo = p.base * C, hi = told + (long long)p.n_in * C - 1;
+        const long long at = idx < lo ? lo : (idx > hi ? hi : idx);
+        const int v = (int16_t)(((at - told) & 1) ? (bits >> 16) : (bits & 0xffffu));
+        return at >= told ? (float)v * 0x1p-15f : __uint_as_float(bits);
+    }
+}
+
+// pairs: all_pairs<T>(p, C), computed once by the kernel
+template <int C, typename T>
+__device__ __forceinline__ float element_raw(const MeterParams& p, size_t s, long long idx, bool pairs)
+{
+    if constexpr (std::is_same<T, float>::value) return element_value<C, T>(p, idx, element_bits<C, T, false>(p, s, idx));
+    else return element_value<C, T>(p, idx, pairs ? element_bits<C, T, true>(p, s, idx) : element_bits<C, T, false>(p, s, idx));
 }
 
 template <int C>
@@ -85,10 +151,10 @@ __device__ __forceinline__ bool element_is_zero(const MeterParams& p, long long 
     return idx < 0 || idx >= (p.t_old + p.n_in) * C;
 }
 
-template <int C>
-__device__ __forceinline__ float element(const MeterParams& p, size_t s, long long idx)
+template <int C, typename T>
+__device__ __forceinline__ float element(const MeterParams& p, size_t s, long long idx, bool pairs)
 {
-    const float v = *element_ptr<C>(p, s, idx);
+    const float v = element_raw<C, T>(p, s, idx, pairs);
     return element_is_zero<C>(p, idx) ? 0.0f : v;
 }
 
@@ -112,13 +178,14 @@ struct Chain {
     }
 };
 
-template <int C>
+template <int C, typename T>
 __global__ __launch_bounds__(kHopThreads) void k_hops(MeterParams p)
 {
     __shared__ float sx[2][64 * kRowFloats];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
+    const bool pairs = all_pairs<T>(p, C);
     const int n_new = p.h_new - p.h_old;                         // new hops per stream
     const long long n_rows = (long long)p.n_streams * n_new;     // (stream, hop) pairs of this call
     const long long row0 = (long long)blockIdx.x * (64 / C);     // this workgroup's first pair
@@ -150,19 +217,28 @@ __global__ __launch_bounds__(kHopThreads) void k_hops(MeterParams p)
     for (int t = 0; t <= kTiles; ++t) {
         if (wave > 0 && t < kTiles) {   // stage tile t: every load of this wavefront first, then the selects and the LDS stores
             float* dst = sx[t & 1];
-            float v[kPerWave][kLoads];
+            typename ElementBits<T>::type v[kPerWave][kLoads];
+            if (pairs) {   // (never for floats)
 #pragma unroll
-            for (int i = 0; i < kPerWave; ++i)
+                for (int i = 0; i < kPerWave; ++i)
 #pragma unroll
-                for (int k = 0; k < kLoads; ++k) v[i][k] = *element_ptr<C>(p, row_s[i], row_first[i] + (long long)t * kElems + lane + 64 * k);
+                    for (int k = 0; k < kLoads; ++k) v[i][k] = element_bits<C, T, true>(p, row_s[i], row_first[i] + (long long)t * kElems + lane + 64 * k);
+            } else {
+#pragma unroll
+                for (int i = 0; i < kPerWave; ++i)
+#pragma unroll
+                    for (int k = 0; k < kLoads; ++k) v[i][k] = element_bits<C, T, false>(p, row_s[i], row_first[i] + (long long)t * kElems + lane + 64 * k);
+            }
 #pragma unroll
             for (int i = 0; i < kPerWave; ++i) {
                 const int r = wave - 1 + 3 * i;
                 if (r < kRows && row0 + r < n_rows) {
 #pragma unroll
                     for (int k = 0; k < kLoads; ++k)
-                        if (lane + 64 * k < kElems)
-                            dst[r * kRow + lane + 64 * k] = element_is_zero<C>(p, row_first[i] + (long long)t * kElems + lane + 64 * k) ? 0.0f : v[i][k];
+                        if (lane + 64 * k < kElems) {
+                            const long long idx = row_first[i] + (long long)t * kElems + lane + 64 * k;
+                            dst[r * kRow + lane + 64 * k] = element_is_zero<C>(p, idx) ? 0.0f : element_value<C, T>(p, idx, v[i][k]);
+                        }
                 }
             }
         }
@@ -192,7 +268,7 @@ __global__ __launch_bounds__(kHopThreads) void k_hops(MeterParams p)
     }
 }
 
-template <int C>
+template <int C, typename T>
 __global__ __launch_bounds__(kCarryThreads) void k_carry(MeterParams p)
 {
     __shared__ unsigned red[2];
@@ -200,6 +276,7 @@ __global__ __launch_bounds__(kCarryThreads) void k_carry(MeterParams p)
     const int tid = threadIdx.x;
     if (tid < 2) red[tid] = 0;
     __syncthreads();
+    const bool pairs = all_pairs<T>(p, C);
     const long long t_new = p.t_old + p.n_in;
     const long long keep = (t_new - p.base_next) * C;   // floats the next call may read
     long long tail = (long long)p.h_new * kHop;         // the new samples that no complete hop holds start here
@@ -208,7 +285,7 @@ __global__ __launch_bounds__(kCarryThreads) void k_carry(MeterParams p)
     unsigned peak = 0;   // (the stride is even: a thread stays on one channel)
     for (long long i = (long long)blockIdx.x * kCarryThreads + tid; i < keep; i += (long long)kCarryBlocks * kCarryThreads) {
         const long long idx = p.base_next * C + i;
-        const float v = element<C>(p, s, idx);
+        const float v = element<C, T>(p, s, idx, pairs);
         dst[i] = v;
         if (idx >= tail * C) {
             const unsigned m = magnitude_bits(v);
@@ -220,20 +297,21 @@ __global__ __launch_bounds__(kCarryThreads) void k_carry(MeterParams p)
     if (tid < C && red[tid]) atomicMax(&p.peaks[(s * 2 + 0) * 2 + tid], red[tid]);
 }
 
-template <int C>
+template <int C, typename T>
 __global__ __launch_bounds__(kPeakThreads) void k_true_peak(MeterParams p)
 {
     using V = typename std::conditional<C == 2, float2, float>::type;
     __shared__ V sx[kPeakQ + kTaps];
     const size_t s = blockIdx.y;
     const int tid = threadIdx.x;
+    const bool pairs = all_pairs<T>(p, C);
     const long long q0 = p.q_lo + (long long)blockIdx.x * kPeakQ;
     // samples q0 - 71 .. q0 + 255 + 72 (output q reads x[q + k - 71], k < 144)
     const long long first = q0 - (kTaps / 2 - 1);
     for (int j = tid; j < kPeakQ + kTaps - 1; j += kPeakThreads) {
         V w;
-        if constexpr (C == 2) w = make_float2(element<C>(p, s, (first + j) * 2), element<C>(p, s, (first + j) * 2 + 1));
-        else w = element<C>(p, s, first + j);
+        if constexpr (C == 2) w = make_float2(element<C, T>(p, s, (first + j) * 2, pairs), element<C, T>(p, s, (first + j) * 2 + 1, pairs));
+        else w = element<C, T>(p, s, first + j, pairs);
         sx[j] = w;
     }
     __syncthreads();
@@ -285,16 +363,36 @@ __global__ __launch_bounds__(kPeakThreads) void k_true_peak(MeterParams p)
     }
 }
 
-// out[s][i] = in[s][i] * gain[s] for i < n (floats per stream); vec: every stream's floats start 16-byte aligned and n % 4 == 0
-__global__ __launch_bounds__(kScaleThreads) void k_scale(const float* in, float* out, const float* gain, long long n, int vec)
+// out[s][i] = in[s][i] * gain[s] for i < n (samples per stream); vec: n % 4 == 0 and every stream's four-sample groups are
+// aligned (16 bytes of floats, 8 bytes of 16-bit samples; the output 16 bytes). A 16-bit sample is widened first:
+// out = ((float)s * 0x1p-15f) * gain.
+template <typename T>
+__global__ __launch_bounds__(kScaleThreads) void k_scale(const T* in, float* out, const float* gain, long long n, int vec)
 {
     const size_t s = blockIdx.y;
     const float g = gain[s];
-    const float* src = in + s * (size_t)n;
+    const T* src = in + s * (size_t)n;
     float* dst = out + s * (size_t)n;
     const long long stride = (long long)gridDim.x * kScaleThreads;
     const long long i0 = (long long)blockIdx.x * kScaleThreads + threadIdx.x;
-    if (vec) {
+    if constexpr (!std::is_same<T, float>::value) {
+        if (vec) {
+            const uint2* src4 = (const uint2*)src;
+            float4* dst4 = (float4*)dst;
+            for (long long i = i0; i < n / 4; i += stride) {
+                const uint2 w = src4[i];
+                float4 v;
+                v.x = ((float)(int16_t)(w.x & 0xffffu) * 0x1p-15f) * g;
+                v.y = ((float)(int16_t)(w.x >> 16) * 0x1p-15f) * g;
+                v.z = ((float)(int16_t)(w.y & 0xffffu) * 0x1p-15f) * g;
+                v.w = ((float)(int16_t)(w.y >> 16) * 0x1p-15f) * g;
+                dst4[i] = v;
+            }
+        } else {
+            const bool pairs = at3::pcm_pairs(src);
+            for (long long i = i0; i < n; i += stride) dst[i] = at3::pcm_at(src, (size_t)i, (size_t)n, pairs) * g;
+        }
+    } else if (vec) {
         const float4* src4 = (const float4*)src;
         float4* dst4 = (float4*)dst;
         for (long long i = i0; i < n / 4; i += stride) {
@@ -388,6 +486,7 @@ struct at3hip_loudness : at3host::EngineBase {
     float* d_hp = nullptr;                   // [4][144], only with true_peak
     float* d_gain = nullptr;                 // [S]
     float* d_in = nullptr;                   // staging for host input [S][max_in][C], allocated by the first call that needs it
+    int16_t* d_in_s16 = nullptr;             // the same as 16-bit samples, allocated by the first *_s16 call that takes host memory
     float* d_out = nullptr;                  // staging for at3hip_loudness_apply's host output, likewise
     long long t = 0;                         // samples received per stream since the start
     long long q_done = 0;                    // q below this have had their four outputs taken (true_peak)
@@ -406,7 +505,8 @@ int clear_state(at3hip_loudness* l)
 }
 
 // Queues the kernels of one call: n_in new samples per stream (device memory); flush: the converter's outputs up to the end.
-int launch(at3hip_loudness* l, const float* in, int n_in, bool flush)
+template <typename T>
+int launch(at3hip_loudness* l, const T* in, int n_in, bool flush)
 {
     const int C = l->cfg.channels, S = l->cfg.n_streams;
     MeterParams p;
@@ -430,22 +530,22 @@ int launch(at3hip_loudness* l, const float* in, int n_in, bool flush)
         const long long rows = (long long)S * (p.h_new - p.h_old);
         const long long blocks = (rows + 64 / C - 1) / (64 / C);
         if (rows > INT32_MAX) return fail(l, AT3HIP_EINVAL, "too many hops in one call");   // (k_hops divides rows in 32 bits)
-        if (C == 2) hipLaunchKernelGGL(k_hops<2>, dim3((unsigned)blocks), dim3(kHopThreads), 0, l->stream, p);
-        else hipLaunchKernelGGL(k_hops<1>, dim3((unsigned)blocks), dim3(kHopThreads), 0, l->stream, p);
+        if (C == 2) hipLaunchKernelGGL((k_hops<2, T>), dim3((unsigned)blocks), dim3(kHopThreads), 0, l->stream, p);
+        else hipLaunchKernelGGL((k_hops<1, T>), dim3((unsigned)blocks), dim3(kHopThreads), 0, l->stream, p);
         HIPCHK(l, hipGetLastError());
     }
     if (l->cfg.true_peak && p.q_hi > p.q_lo) {
         const long long tiles = (p.q_hi - p.q_lo + kPeakQ - 1) / kPeakQ;
         const dim3 grid((unsigned)tiles, (unsigned)S);
-        if (C == 2) hipLaunchKernelGGL(k_true_peak<2>, grid, dim3(kPeakThreads), 0, l->stream, p);
-        else hipLaunchKernelGGL(k_true_peak<1>, grid, dim3(kPeakThreads), 0, l->stream, p);
+        if (C == 2) hipLaunchKernelGGL((k_true_peak<2, T>), grid, dim3(kPeakThreads), 0, l->stream, p);
+        else hipLaunchKernelGGL((k_true_peak<1, T>), grid, dim3(kPeakThreads), 0, l->stream, p);
         HIPCHK(l, hipGetLastError());
         l->q_done = p.q_hi;
     }
     if (n_in > 0) {
         const dim3 grid(kCarryBlocks, (unsigned)S);
-        if (C == 2) hipLaunchKernelGGL(k_carry<2>, grid, dim3(kCarryThreads), 0, l->stream, p);
-        else hipLaunchKernelGGL(k_carry<1>, grid, dim3(kCarryThreads), 0, l->stream, p);
+        if (C == 2) hipLaunchKernelGGL((k_carry<2, T>), grid, dim3(kCarryThreads), 0, l->stream, p);
+        else hipLaunchKernelGGL((k_carry<1, T>), grid, dim3(kCarryThreads), 0, l->stream, p);
         HIPCHK(l, hipGetLastError());
         l->cur ^= 1;
         l->t = t_new;
@@ -453,22 +553,85 @@ int launch(at3hip_loudness* l, const float* in, int n_in, bool flush)
     return AT3HIP_OK;
 }
 
-int stage_in(at3hip_loudness* l, const float* in, int n_in, uint32_t flags, const float** d_in)
+template <typename T>
+int stage_in(at3hip_loudness* l, const T* in, int n_in, uint32_t flags, const T** d_in)
 {
     const size_t S = l->cfg.n_streams, C = l->cfg.channels;
     *d_in = in;
     if (n_in == 0) {
-        *d_in = l->d_carry[l->cur];   // (never read)
+        *d_in = reinterpret_cast<const T*>(l->d_carry[l->cur]);   // (never read)
         return AT3HIP_OK;
     }
     if (flags & AT3HIP_PCM_ON_DEVICE) return AT3HIP_OK;
-    if (!l->d_in) {   // staging for host memory, allocated by the first call that takes host memory
-        const int rc = dev_alloc(l, &l->d_in, S * (size_t)l->cfg.max_in * C);
-        if (rc != AT3HIP_OK) return rc;
+    T* staging;   // staging for host memory, allocated by the first call that takes host memory of its kind
+    if constexpr (sizeof(T) == sizeof(int16_t)) {   // 16-bit samples cross the bus as they are and are widened by the kernels' loads
+        if (!l->d_in_s16) {
+            const int rc = dev_alloc(l, &l->d_in_s16, S * (size_t)l->cfg.max_in * C);
+            if (rc != AT3HIP_OK) return rc;
+        }
+        staging = l->d_in_s16;
+    } else {
+        if (!l->d_in) {
+            const int rc = dev_alloc(l, &l->d_in, S * (size_t)l->cfg.max_in * C);
+            if (rc != AT3HIP_OK) return rc;
+        }
+        staging = l->d_in;
     }
-    HIPCHK(l, hipMemcpyAsync(l->d_in, in, S * n_in * C * sizeof(float), hipMemcpyHostToDevice, l->stream));
-    *d_in = l->d_in;
+    HIPCHK(l, hipMemcpyAsync(staging, in, S * n_in * C * sizeof(T), hipMemcpyHostToDevice, l->stream));
+    *d_in = staging;
     return AT3HIP_OK;
+}
+
+// at3hip_loudness_process (T = float) and at3hip_loudness_process_s16 (T = int16_t)
+template <typename T>
+int process_impl(at3hip_loudness* l, const T* in, int32_t n_in, uint32_t flags)
+{
+    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_ASYNC;
+    if (!l) return AT3HIP_EINVAL;
+    if ((n_in > 0 && !in) || n_in < 0 || n_in > l->cfg.max_in || (flags & ~known)) return fail(l, AT3HIP_EINVAL, "bad argument");
+    if ((l->t + n_in) / kHop > l->cfg.max_hops) return fail(l, AT3HIP_EINVAL, "more hops than max_hops");
+    at3host::DeviceGuard guard(l->device);
+    HIPCHK(l, guard.error());
+    const T* d_in = nullptr;
+    int rc = stage_in(l, in, n_in, flags, &d_in);
+    if (rc != AT3HIP_OK) return rc;
+    if ((rc = launch(l, d_in, n_in, false)) != AT3HIP_OK) return rc;
+    if (flags & AT3HIP_ASYNC) return AT3HIP_OK;
+    HIPCHK(l, hipStreamSynchronize(l->stream));
+    return AT3HIP_OK;
+}
+
+// at3hip_loudness_apply (T = float) and at3hip_loudness_apply_s16 (T = int16_t)
+template <typename T>
+int apply_impl(at3hip_loudness* l, const T* in, int32_t n_in, const float* gains, float* out, uint32_t flags)
+{
+    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC;
+    if (!l) return AT3HIP_EINVAL;
+    if (!gains || (n_in > 0 && (!in || !out)) || n_in < 0 || n_in > l->cfg.max_in || (flags & ~known))
+        return fail(l, AT3HIP_EINVAL, "bad argument");
+    if (n_in == 0) return AT3HIP_OK;
+    at3host::DeviceGuard guard(l->device);
+    HIPCHK(l, guard.error());
+    const size_t S = l->cfg.n_streams, C = l->cfg.channels;
+    const T* d_in = nullptr;
+    const int rc = stage_in(l, in, n_in, flags, &d_in);
+    if (rc != AT3HIP_OK) return rc;
+    float* d_out = out;
+    if (!(flags & AT3HIP_OUT_ON_DEVICE)) {
+        if (!l->d_out) {
+            const int rc2 = dev_alloc(l, &l->d_out, S * (size_t)l->cfg.max_in * C);
+            if (rc2 != AT3HIP_OK) return rc2;
+        }
+        d_out = l->d_out;
+    }
+    HIPCHK(l, hipMemcpyAsync(l->d_gain, gains, S * sizeof(float), hipMemcpyHostToDevice, l->stream));
+    const long long n = (long long)n_in * C;
+    const int vec = n % 4 == 0 && (uintptr_t)d_in % (4 * sizeof(T)) == 0 && (uintptr_t)d_out % 16 == 0;
+    long long blocks = ((vec ? n / 4 : n) + kScaleThreads - 1) / kScaleThreads;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_scale<T>, dim3((unsigned)blocks, (unsigned)S), dim3(kScaleThreads), 0, l->stream, d_in, d_out, l->d_gain, n, vec);
+    HIPCHK(l, hipGetLastError());
+    return at3host::copy_out_and_wait(l, out, l->d_out, S * n * sizeof(float), flags);
 }
 
 }  // namespace
@@ -518,7 +681,7 @@ int at3hip_loudness_create(const at3hip_loudness_config* cfg, at3hip_loudness** 
 
 void at3hip_loudness_destroy(at3hip_loudness* l)
 {
-    if (l) at3host::destroy_engine(l, {l->d_carry[0], l->d_carry[1], l->d_z, l->d_peaks, l->d_hp, l->d_gain, l->d_in, l->d_out});
+    if (l) at3host::destroy_engine(l, {l->d_carry[0], l->d_carry[1], l->d_z, l->d_peaks, l->d_hp, l->d_gain, l->d_in, l->d_in_s16, l->d_out});
 }
 
 const char* at3hip_loudness_last_error(const at3hip_loudness* l) { return at3host::engine_last_error(l); }
@@ -532,22 +695,9 @@ int at3hip_loudness_reset(at3hip_loudness* l)
     return clear_state(l);
 }
 
-int at3hip_loudness_process(at3hip_loudness* l, const float* in, int32_t n_in, uint32_t flags)
-{
-    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_ASYNC;
-    if (!l) return AT3HIP_EINVAL;
-    if ((n_in > 0 && !in) || n_in < 0 || n_in > l->cfg.max_in || (flags & ~known)) return fail(l, AT3HIP_EINVAL, "bad argument");
-    if ((l->t + n_in) / kHop > l->cfg.max_hops) return fail(l, AT3HIP_EINVAL, "more hops than max_hops");
-    at3host::DeviceGuard guard(l->device);
-    HIPCHK(l, guard.error());
-    const float* d_in = nullptr;
-    int rc = stage_in(l, in, n_in, flags, &d_in);
-    if (rc != AT3HIP_OK) return rc;
-    if ((rc = launch(l, d_in, n_in, false)) != AT3HIP_OK) return rc;
-    if (flags & AT3HIP_ASYNC) return AT3HIP_OK;
-    HIPCHK(l, hipStreamSynchronize(l->stream));
-    return AT3HIP_OK;
-}
+int at3hip_loudness_process(at3hip_loudness* l, const float* in, int32_t n_in, uint32_t flags) { return process_impl(l, in, n_in, flags); }
+
+int at3hip_loudness_process_s16(at3hip_loudness* l, const int16_t* in, int32_t n_in, uint32_t flags) { return process_impl(l, in, n_in, flags); }
 
 int at3hip_loudness_read_hops(at3hip_loudness* l, int32_t stream, void* dst, size_t bytes)
 {
@@ -571,7 +721,7 @@ int at3hip_loudness_finish(at3hip_loudness* l, at3hip_loudness_result* results)
     HIPCHK(l, guard.error());
     const size_t S = l->cfg.n_streams, C = l->cfg.channels, H = (size_t)(l->t / kHop);
     if (l->cfg.true_peak) {   // the converter's last outputs, zeros past the end
-        const int rc = launch(l, l->d_carry[l->cur], 0, true);
+        const int rc = launch(l, (const float*)l->d_carry[l->cur], 0, true);
         if (rc != AT3HIP_OK) return rc;
     }
     std::vector<double> z(H * S * C), zs(H * C);
@@ -598,33 +748,12 @@ int at3hip_loudness_finish(at3hip_loudness* l, at3hip_loudness_result* results)
 
 int at3hip_loudness_apply(at3hip_loudness* l, const float* in, int32_t n_in, const float* gains, float* out, uint32_t flags)
 {
-    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC;
-    if (!l) return AT3HIP_EINVAL;
-    if (!gains || (n_in > 0 && (!in || !out)) || n_in < 0 || n_in > l->cfg.max_in || (flags & ~known))
-        return fail(l, AT3HIP_EINVAL, "bad argument");
-    if (n_in == 0) return AT3HIP_OK;
-    at3host::DeviceGuard guard(l->device);
-    HIPCHK(l, guard.error());
-    const size_t S = l->cfg.n_streams, C = l->cfg.channels;
-    const float* d_in = nullptr;
-    const int rc = stage_in(l, in, n_in, flags, &d_in);
-    if (rc != AT3HIP_OK) return rc;
-    float* d_out = out;
-    if (!(flags & AT3HIP_OUT_ON_DEVICE)) {
-        if (!l->d_out) {
-            const int rc2 = dev_alloc(l, &l->d_out, S * (size_t)l->cfg.max_in * C);
-            if (rc2 != AT3HIP_OK) return rc2;
-        }
-        d_out = l->d_out;
-    }
-    HIPCHK(l, hipMemcpyAsync(l->d_gain, gains, S * sizeof(float), hipMemcpyHostToDevice, l->stream));
-    const long long n = (long long)n_in * C;
-    const int vec = n % 4 == 0 && (uintptr_t)d_in % 16 == 0 && (uintptr_t)d_out % 16 == 0;
-    long long blocks = ((vec ? n / 4 : n) + kScaleThreads - 1) / kScaleThreads;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_scale, dim3((unsigned)blocks, (unsigned)S), dim3(kScaleThreads), 0, l->stream, d_in, d_out, l->d_gain, n, vec);
-    HIPCHK(l, hipGetLastError());
-    return at3host::copy_out_and_wait(l, out, l->d_out, S * n * sizeof(float), flags);
+    return apply_impl(l, in, n_in, gains, out, flags);
+}
+
+int at3hip_loudness_apply_s16(at3hip_loudness* l, const int16_t* in, int32_t n_in, const float* gains, float* out, uint32_t flags)
+{
+    return apply_impl(l, in, n_in, gains, out, flags);
 }
 
 int at3hip_loudness_sync(at3hip_loudness* l) { return at3host::engine_sync(l); }

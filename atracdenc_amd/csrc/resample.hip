@@ -17,6 +17,7 @@
 
 #include "../../include/at3hip_resample.h"
 #include "at3_host_util.hpp"
+#include "at3_pcm_in.hpp"
 
 using at3host::dev_alloc;
 using at3host::fail;
@@ -96,8 +97,8 @@ __attribute__((optnone, noinline)) void build_table(int in, int out, const Shape
 struct ResampleParams {
     const float* hist;    // [S][K][C]: input samples T_old - K .. T_old - 1 of each stream (read)
     float* hist_next;     // [S][K][C]: samples T_new - K .. T_new - 1 (written by the first workgroup of each stream)
-    const float* in;      // [S][n_in][C]
-    float* out;           // [S][n_out][C]
+    const void* in;       // [S][n_in][C], float or int16_t: the kernel's template parameter TI
+    void* out;            // [S][n_out][C], float or int16_t: TO
     const float* hp;      // [L][K]
     long long t_old;      // input samples of each stream before this call
     long long n0;         // first output of this call
@@ -108,8 +109,10 @@ struct ResampleParams {
 
 // Input sample a of a stream (absolute index): zeros before the start and from T_new on; unneeded samples older than the
 // history also read as zeros (only outputs this call does not emit reach them).
-template <int C>
-__device__ __forceinline__ void sample(const ResampleParams& p, const float* hist, const float* in, long long a, float* v)
+// in: the stream's row of this call, float or 16-bit (at3_pcm_in.hpp: a stereo sample is then one 32-bit load where the row is
+// 4-byte aligned); the history is float for both.
+template <int C, typename TI>
+__device__ __forceinline__ void sample(const ResampleParams& p, const float* hist, const TI* in, bool pairs, long long a, float* v)
 {
     const long long t_new = p.t_old + p.n_in;
     if (a < 0 || a >= t_new || a < p.t_old - p.K) {
@@ -119,28 +122,40 @@ __device__ __forceinline__ void sample(const ResampleParams& p, const float* his
         const float* s = hist + (a - (p.t_old - p.K)) * C;
 #pragma unroll
         for (int c = 0; c < C; ++c) v[c] = s[c];
-    } else {
+    } else if constexpr (std::is_same<TI, float>::value) {
         const float* s = in + (a - p.t_old) * C;
 #pragma unroll
         for (int c = 0; c < C; ++c) v[c] = s[c];
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = at3::pcm_at(in, (size_t)(a - p.t_old) * C + c, (size_t)p.n_in * C, pairs);
     }
 }
 
-template <int C>
+// The output's 16-bit form is the decoders' (AT3HIP_RESAMPLE_OUT_S16): lrintf(clamp(x, -1, 1) * 32767.0f).
+__device__ __forceinline__ void store_out(float* o, float x) { *o = x; }
+__device__ __forceinline__ void store_out(int16_t* o, float x)
+{
+    const float y = x < -1.0f ? -1.0f : (x > 1.0f ? 1.0f : x);
+    *o = (int16_t)__float2int_rn(y * 32767.0f);
+}
+
+template <int C, typename TI, typename TO>
 __global__ __launch_bounds__(kThreads) void k_resample(ResampleParams p)
 {
     using V = typename std::conditional<C == 2, float2, float>::type;
     __shared__ V sx[kLdsBytes / sizeof(V)];
     const size_t s = blockIdx.y;
     const float* hist = p.hist + s * (size_t)p.K * C;
-    const float* in = p.in + s * (size_t)p.n_in * C;
+    const TI* in = static_cast<const TI*>(p.in) + s * (size_t)p.n_in * C;
+    const bool pairs = at3::pcm_pairs(in);
     const int tid = threadIdx.x;
 
     if (blockIdx.x == 0) {   // the history the next call reads
         float* hn = p.hist_next + s * (size_t)p.K * C;
         for (int j = tid; j < p.K; j += kThreads) {
             float v[C];
-            sample<C>(p, hist, in, p.t_old + p.n_in - p.K + j, v);
+            sample<C>(p, hist, in, pairs, p.t_old + p.n_in - p.K + j, v);
 #pragma unroll
             for (int c = 0; c < C; ++c) hn[(size_t)j * C + c] = v[c];
         }
@@ -156,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void k_resample(ResampleParams p)
     const int span = p.Q * p.M + p.K - 1;
     for (int j = tid; j < span; j += kThreads) {
         float v[C];
-        sample<C>(p, hist, in, s0 + j, v);
+        sample<C>(p, hist, in, pairs, s0 + j, v);
         V w;
         if constexpr (C == 2) w = make_float2(v[0], v[1]);
         else w = v[0];
@@ -167,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void k_resample(ResampleParams p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const long long q = q0 + lane;
-    float* out = p.out + s * (size_t)p.n_out * C;
+    TO* out = static_cast<TO*>(p.out) + s * (size_t)p.n_out * C;
     const V* xl = sx + lane * (p.M + p.pad);
     for (int r = wave; r < p.L; r += kThreads / 64) {
         const long long n = q * p.L + r;
@@ -208,9 +223,9 @@ __global__ __launch_bounds__(kThreads) void k_resample(ResampleParams p)
                 }
             }
         }
-        float* o = out + (size_t)(n - p.n0) * C;
+        TO* o = out + (size_t)(n - p.n0) * C;
 #pragma unroll
-        for (int c = 0; c < C; ++c) o[c] = acc[c];
+        for (int c = 0; c < C; ++c) store_out(o + c, acc[c]);
     }
 }
 
@@ -224,7 +239,8 @@ struct at3hip_resampler : at3host::EngineBase {
     float* d_hist[2] = {nullptr, nullptr};   // [S][K][C], read / written alternately
     int cur = 0;
     float* d_in = nullptr;          // staging for host input  [S][max_in][C], allocated by the first call that needs it
-    float* d_out = nullptr;         // staging for host output [S][max_out][C], likewise
+    int16_t* d_in_s16 = nullptr;    // the same as 16-bit samples, allocated by the first at3hip_resampler_process_s16 that needs it
+    float* d_out = nullptr;         // staging for host output [S][max_out][C], likewise (16-bit output uses its first half)
     long long t_in = 0;             // input samples received per stream since the start
     long long t_out = 0;            // outputs emitted per stream since the start
 };
@@ -234,8 +250,16 @@ namespace {
 // ceil(a L / M) for a > 0, else 0: the outputs whose i is below a
 long long outputs_below(long long a, const Shape& s) { return a <= 0 ? 0 : (a * s.L + s.M - 1) / s.M; }
 
-// Queues one call: n_in new samples (device memory), outputs [t_out, n_end) into out (device memory).
-int launch(at3hip_resampler* r, const float* in, int n_in, long long n_end, float* out)
+template <int C, typename TI>
+void launch_kernel(const at3hip_resampler* r, const dim3& grid, const ResampleParams& p, bool out_s16)
+{
+    if (out_s16) hipLaunchKernelGGL((k_resample<C, TI, int16_t>), grid, dim3(kThreads), 0, r->stream, p);
+    else hipLaunchKernelGGL((k_resample<C, TI, float>), grid, dim3(kThreads), 0, r->stream, p);
+}
+
+// Queues one call: n_in new samples (device memory), outputs [t_out, n_end) into out (device memory; int16_t with out_s16).
+template <typename TI>
+int launch(at3hip_resampler* r, const TI* in, int n_in, long long n_end, void* out, bool out_s16)
 {
     const int C = r->cfg.channels;
     const Shape& sh = r->sh;
@@ -257,8 +281,8 @@ int launch(at3hip_resampler* r, const float* in, int n_in, long long n_end, floa
     long long tiles = 1;
     if (p.n_out > 0) tiles = ((n_end - 1) / sh.L - r->t_out / sh.L) / r->Q + 1;
     const dim3 grid((unsigned)tiles, (unsigned)r->cfg.n_streams);
-    if (C == 2) hipLaunchKernelGGL(k_resample<2>, grid, dim3(kThreads), 0, r->stream, p);
-    else hipLaunchKernelGGL(k_resample<1>, grid, dim3(kThreads), 0, r->stream, p);
+    if (C == 2) launch_kernel<2, TI>(r, grid, p, out_s16);
+    else launch_kernel<1, TI>(r, grid, p, out_s16);
     HIPCHK(r, hipGetLastError());
     r->cur ^= 1;
     r->t_in += n_in;
@@ -266,9 +290,58 @@ int launch(at3hip_resampler* r, const float* in, int n_in, long long n_end, floa
     return AT3HIP_OK;
 }
 
-int finish(at3hip_resampler* r, float* out, int n_out, uint32_t flags)
+int finish(at3hip_resampler* r, void* out, int n_out, uint32_t flags)
 {
-    return at3host::copy_out_and_wait(r, out, r->d_out, (size_t)r->cfg.n_streams * n_out * r->cfg.channels * sizeof(float), flags);
+    const size_t elem = (flags & AT3HIP_RESAMPLE_OUT_S16) ? sizeof(int16_t) : sizeof(float);
+    return at3host::copy_out_and_wait(r, out, r->d_out, (size_t)r->cfg.n_streams * n_out * r->cfg.channels * elem, flags);
+}
+
+// at3hip_resampler_process (TI = float) and at3hip_resampler_process_s16 (TI = int16_t)
+template <typename TI>
+int process_impl(at3hip_resampler* r, const TI* in, int32_t n_in, void* out, int32_t* n_out, uint32_t flags)
+{
+    constexpr bool kShort = sizeof(TI) == sizeof(int16_t);
+    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3HIP_RESAMPLE_OUT_S16;
+    if (!r) return AT3HIP_EINVAL;
+    if (!out || !n_out || (n_in > 0 && !in) || n_in < 0 || n_in > r->cfg.max_in || (flags & ~known))
+        return fail(r, AT3HIP_EINVAL, "bad argument");
+    at3host::DeviceGuard guard(r->device);
+    HIPCHK(r, guard.error());
+    const int C = r->cfg.channels;
+    const size_t S = r->cfg.n_streams;
+    // staging for host memory, allocated by the first call that takes or gives host memory: device buffers never need it
+    const TI* d_in = in;
+    if (n_in > 0 && !(flags & AT3HIP_PCM_ON_DEVICE)) {
+        TI* staging;
+        if constexpr (kShort) {   // 16-bit samples cross the bus as they are and are widened by the kernel's loads
+            if (!r->d_in_s16) {
+                const int rc = dev_alloc(r, &r->d_in_s16, S * (size_t)r->cfg.max_in * C);
+                if (rc != AT3HIP_OK) return rc;
+            }
+            staging = r->d_in_s16;
+        } else {
+            if (!r->d_in) {
+                const int rc = dev_alloc(r, &r->d_in, S * (size_t)r->cfg.max_in * C);
+                if (rc != AT3HIP_OK) return rc;
+            }
+            staging = r->d_in;
+        }
+        HIPCHK(r, hipMemcpyAsync(staging, in, S * n_in * C * sizeof(TI), hipMemcpyHostToDevice, r->stream));
+        d_in = staging;
+    }
+    if (!(flags & AT3HIP_OUT_ON_DEVICE) && !r->d_out) {
+        const int rc = dev_alloc(r, &r->d_out, S * (size_t)r->max_out * C);
+        if (rc != AT3HIP_OK) return rc;
+    }
+    if (n_in == 0) d_in = reinterpret_cast<const TI*>(r->d_hist[r->cur]);   // (never read)
+    const long long n_end_new = outputs_below(r->t_in + n_in - r->sh.K / 2, r->sh);
+    const long long n_end = n_end_new > r->t_out ? n_end_new : r->t_out;
+    const int count = (int)(n_end - r->t_out);
+    void* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? out : (void*)r->d_out;
+    const int rc = launch(r, d_in, n_in, n_end, d_out, (flags & AT3HIP_RESAMPLE_OUT_S16) != 0);
+    if (rc != AT3HIP_OK) return rc;
+    *n_out = count;
+    return finish(r, out, count, flags);
 }
 
 }  // namespace
@@ -341,7 +414,7 @@ int at3hip_resampler_create(const at3hip_resampler_config* cfg, at3hip_resampler
 
 void at3hip_resampler_destroy(at3hip_resampler* r)
 {
-    if (r) at3host::destroy_engine(r, {r->d_hp, r->d_hist[0], r->d_hist[1], r->d_in, r->d_out});
+    if (r) at3host::destroy_engine(r, {r->d_hp, r->d_hist[0], r->d_hist[1], r->d_in, r->d_in_s16, r->d_out});
 }
 
 const char* at3hip_resampler_last_error(const at3hip_resampler* r) { return at3host::engine_last_error(r); }
@@ -359,42 +432,17 @@ int32_t at3hip_resampler_max_out(const at3hip_resampler* r) { return r ? r->max_
 
 int at3hip_resampler_process(at3hip_resampler* r, const float* in, int32_t n_in, float* out, int32_t* n_out, uint32_t flags)
 {
-    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC;
-    if (!r) return AT3HIP_EINVAL;
-    if (!out || !n_out || (n_in > 0 && !in) || n_in < 0 || n_in > r->cfg.max_in || (flags & ~known))
-        return fail(r, AT3HIP_EINVAL, "bad argument");
-    at3host::DeviceGuard guard(r->device);
-    HIPCHK(r, guard.error());
-    const int C = r->cfg.channels;
-    const size_t S = r->cfg.n_streams;
-    // staging for host memory, allocated by the first call that takes or gives host memory: device buffers never need it
-    if (n_in > 0 && !(flags & AT3HIP_PCM_ON_DEVICE) && !r->d_in) {
-        const int rc = dev_alloc(r, &r->d_in, S * (size_t)r->cfg.max_in * C);
-        if (rc != AT3HIP_OK) return rc;
-    }
-    if (!(flags & AT3HIP_OUT_ON_DEVICE) && !r->d_out) {
-        const int rc = dev_alloc(r, &r->d_out, S * (size_t)r->max_out * C);
-        if (rc != AT3HIP_OK) return rc;
-    }
-    const float* d_in = in;
-    if (n_in > 0 && !(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(r, hipMemcpyAsync(r->d_in, in, S * n_in * C * sizeof(float), hipMemcpyHostToDevice, r->stream));
-        d_in = r->d_in;
-    }
-    if (n_in == 0) d_in = r->d_hist[r->cur];   // (never read)
-    const long long n_end_new = outputs_below(r->t_in + n_in - r->sh.K / 2, r->sh);
-    const long long n_end = n_end_new > r->t_out ? n_end_new : r->t_out;
-    const int count = (int)(n_end - r->t_out);
-    float* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? out : r->d_out;
-    const int rc = launch(r, d_in, n_in, n_end, d_out);
-    if (rc != AT3HIP_OK) return rc;
-    *n_out = count;
-    return finish(r, out, count, flags);
+    return process_impl(r, in, n_in, out, n_out, flags);
+}
+
+int at3hip_resampler_process_s16(at3hip_resampler* r, const int16_t* in, int32_t n_in, void* out, int32_t* n_out, uint32_t flags)
+{
+    return process_impl(r, in, n_in, out, n_out, flags);
 }
 
 int at3hip_resampler_flush(at3hip_resampler* r, float* out, int32_t* n_out, uint32_t flags)
 {
-    const uint32_t known = AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3HIP_PCM_ON_DEVICE;
+    const uint32_t known = AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3HIP_PCM_ON_DEVICE | AT3HIP_RESAMPLE_OUT_S16;
     if (!r) return AT3HIP_EINVAL;
     if (!out || !n_out || (flags & ~known)) return fail(r, AT3HIP_EINVAL, "bad argument");
     at3host::DeviceGuard guard(r->device);
@@ -405,8 +453,8 @@ int at3hip_resampler_flush(at3hip_resampler* r, float* out, int32_t* n_out, uint
         const int rc = dev_alloc(r, &r->d_out, (size_t)r->cfg.n_streams * r->max_out * r->cfg.channels);
         if (rc != AT3HIP_OK) return rc;
     }
-    float* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? out : r->d_out;
-    const int rc = launch(r, r->d_hist[r->cur], 0, n_end, d_out);   // (no input: never read)
+    void* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? (void*)out : (void*)r->d_out;
+    const int rc = launch(r, (const float*)r->d_hist[r->cur], 0, n_end, d_out, (flags & AT3HIP_RESAMPLE_OUT_S16) != 0);   // (no input: never read)
     if (rc != AT3HIP_OK) return rc;
     *n_out = count;
     r->t_in = 0;

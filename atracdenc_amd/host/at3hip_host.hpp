@@ -602,6 +602,21 @@ public:
             Aea->WriteFrame(std::vector<char>(units.begin() + i * AT1HIP_FRAME_SIZE, units.begin() + (i + 1) * AT1HIP_FRAME_SIZE));
     }
 
+    // nBlocks blocks of 16-bit PCM [nBlocks][512][channels] (at1hip_encode_short: a sample s is s / 32768.0f, widened on the
+    // device), behind whatever the lambda has buffered: the units are those of the lambda on these floats. At most batchBlocks
+    // blocks go into one call.
+    void EncodeS16(const int16_t* pcm, int nBlocks)
+    {
+        Flush();
+        std::vector<uint8_t> units((size_t)BatchBlocks * Channels * AT1HIP_FRAME_SIZE);
+        for (int at = 0; at < nBlocks; at += BatchBlocks) {
+            const int nb = std::min(BatchBlocks, nBlocks - at);
+            Check1(at1hip_encode_short(Ctx, pcm + (size_t)at * BlockFloats, nb, units.data(), 0), Ctx, "at1hip_encode_short");
+            for (size_t i = 0; i < (size_t)nb * Channels; ++i)
+                Aea->WriteFrame(std::vector<char>(units.begin() + i * AT1HIP_FRAME_SIZE, units.begin() + (i + 1) * AT1HIP_FRAME_SIZE));
+        }
+    }
+
 private:
     TCompressedOutputPtr Aea;
     const TAtrac1EncodeSettings Settings;
@@ -653,6 +668,25 @@ public:
             if ((int)(Pending.size() / FrameFloats) == BatchFrames) Flush();
             return first ? EProcessResult::LOOK_AHEAD : EProcessResult::PROCESSED;
         };
+    }
+
+    // nFrames frames of 16-bit PCM [nFrames][2048][channels] (at3phip_encode_frames_short: a sample s is s / 32768.0f, widened
+    // on the device), behind whatever the lambda has buffered; they count as nFrames calls of the lambda on these floats, so the
+    // look-ahead schedule is kept (true when the first of them was the stream's first call). At most batchFrames frames go
+    // into one call.
+    bool EncodeS16(const int16_t* pcm, int nFrames)
+    {
+        Flush();
+        const bool first = Calls == 0 && nFrames > 0;
+        std::vector<uint8_t> frames((size_t)BatchFrames * AT3PHIP_FRAME_BYTES);
+        for (int at = 0; at < nFrames; at += BatchFrames) {
+            const int nf = std::min(BatchFrames, nFrames - at);
+            Chk(at3phip_encode_frames_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), 0), "at3phip_encode_frames_short");
+            for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES);
+            Calls += (size_t)nf;
+            Flush();
+        }
+        return first;
     }
 
     // Encodes what is buffered and writes the frames that are due: after n calls, n - 1 frames have been written.
@@ -724,12 +758,27 @@ public:
     void Process(const float* in, int32_t n, std::vector<float>& dst) { Append(at3hip_resampler_process(R, in, n, Out.data(), &N, 0), dst); }
     // the remaining outputs; then the start state
     void Flush(std::vector<float>& dst) { Append(at3hip_resampler_flush(R, Out.data(), &N, 0), dst); }
+    // 16-bit input (at3hip_resampler_process_s16: a sample s is s / 32768.0f, widened on the device), float output
+    void ProcessS16(const int16_t* in, int32_t n, std::vector<float>& dst) { Append(at3hip_resampler_process_s16(R, in, n, Out.data(), &N, 0), dst); }
+    // 16-bit output (AT3HIP_RESAMPLE_OUT_S16: lrintf(clamp(x, -1, 1) * 32767.0f), the decoders' rule) of float and of 16-bit input
+    void Process(const float* in, int32_t n, std::vector<int16_t>& dst)
+    {
+        Append(at3hip_resampler_process(R, in, n, Out.data(), &N, AT3HIP_RESAMPLE_OUT_S16), dst);
+    }
+    void ProcessS16(const int16_t* in, int32_t n, std::vector<int16_t>& dst)
+    {
+        Append(at3hip_resampler_process_s16(R, in, n, Out.data(), &N, AT3HIP_RESAMPLE_OUT_S16), dst);
+    }
+    void Flush(std::vector<int16_t>& dst) { Append(at3hip_resampler_flush(R, Out.data(), &N, AT3HIP_RESAMPLE_OUT_S16), dst); }
 
 private:
-    void Append(int rc, std::vector<float>& dst)
+    template <class T>
+    void Append(int rc, std::vector<T>& dst)   // (16-bit outputs lie in the front of the float buffer)
     {
         if (rc != AT3HIP_OK) throw std::runtime_error(std::string("at3hip_resampler: ") + at3hip_resampler_last_error(R));
-        dst.insert(dst.end(), Out.begin(), Out.begin() + (size_t)N * Channels);
+        const size_t at = dst.size();
+        dst.resize(at + (size_t)N * Channels);
+        memcpy(dst.data() + at, Out.data(), (size_t)N * Channels * sizeof(T));
     }
     at3hip_resampler* R = nullptr;
     int Channels;
@@ -815,6 +864,12 @@ public:
         for (size_t at = 0; at < n; at += kChunk)
             Check(at3hip_loudness_process(L, in + at * Channels, (int32_t)std::min<size_t>(kChunk, n - at), 0));
     }
+    // the same for 16-bit PCM (at3hip_loudness_process_s16: a sample s is s / 32768.0f, widened on the device)
+    void ProcessS16(const int16_t* in, size_t n)
+    {
+        for (size_t at = 0; at < n; at += kChunk)
+            Check(at3hip_loudness_process_s16(L, in + at * Channels, (int32_t)std::min<size_t>(kChunk, n - at), 0));
+    }
     // every sample of a source (GetChannelNum / Read as TWavSource)
     template <class TSrc>
     void ProcessAll(TSrc& src)
@@ -846,6 +901,13 @@ public:
     {
         for (size_t at = 0; at < n; at += kChunk)
             Check(at3hip_loudness_apply(L, pcm + at * Channels, (int32_t)std::min<size_t>(kChunk, n - at), &g, pcm + at * Channels, 0));
+    }
+
+    // out[i] = (pcm[i] / 32768.0f) * g for n sample frames of 16-bit PCM, on the GPU (at3hip_loudness_apply_s16)
+    void ApplyS16(const int16_t* pcm, size_t n, float g, float* out)
+    {
+        for (size_t at = 0; at < n; at += kChunk)
+            Check(at3hip_loudness_apply_s16(L, pcm + at * Channels, (int32_t)std::min<size_t>(kChunk, n - at), &g, out + at * Channels, 0));
     }
 
 private:

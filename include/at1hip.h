@@ -61,6 +61,14 @@ const char* at1hip_last_error(const at1hip_ctx* ctx);
  * overlap, detector energies, loudness) is carried between calls. */
 int at1hip_encode(at1hip_ctx* ctx, const float* pcm, int32_t n_blocks, uint8_t* out_frames, uint32_t flags);
 
+/* at1hip_encode for 16-bit PCM: pcm [n_streams][n_blocks][512][channels] int16, layout, flags, limits and error codes as
+ * above. A sample s is taken as the float (float)s * 0x1p-15f (exact, = s / 32768.0f: the rule of at3hip_encode_s16 and of the
+ * reference's WAV reader), so the frames are, bit for bit, those of at1hip_encode on these floats. The samples are widened by
+ * the first kernel's loads: host memory crosses the bus as 16-bit (half the bytes; its staging buffer is allocated by the
+ * first such call) and no float copy is written on the device. Calls of both kinds may alternate on one context: the carried
+ * state is float. A device pointer needs only int16_t alignment. Added under ABI 1.6: a host looks for this symbol. */
+int at1hip_encode_short(at1hip_ctx* ctx, const int16_t* pcm, int32_t n_blocks, uint8_t* out_frames, uint32_t flags);
+
 /* Waits for everything queued on the ctx. (A queued call records no stage-timing events - they are not free between the kernels -: the
  * timings then read zero; a synchronous call is timed.) */
 int at1hip_sync(at1hip_ctx* ctx);

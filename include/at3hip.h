@@ -390,6 +390,12 @@ int at3hip_decoder_set_stream(at3hip_decoder* dec, void* hip_stream);
  *        at3hip_loudness_destroy(), at3hip_loudness_last_error(), at3hip_loudness_reset(), at3hip_loudness_sync(),
  *        at3hip_loudness_set_stream(), at3hip_loudness_process(), at3hip_loudness_finish(), at3hip_loudness_read_hops(),
  *        at3hip_loudness_apply(), at3hip_loudness_gate(), at3hip_loudness_gain() (detected by the symbol at3hip_loudness_create)
+ *        and, added later under the same number, 16-bit PCM at every engine's input (a sample s is (float)s * 0x1p-15f, the rule
+ *        of at3hip_encode_s16, widened by the first kernel's loads): at1hip_encode_short (at1hip.h), at3phip_encode_frames_short
+ *        (at3phip.h), at3hip_resampler_process_s16() with AT3HIP_RESAMPLE_OUT_S16 for 16-bit output (at3hip_resample.h),
+ *        at3hip_loudness_process_s16() and at3hip_loudness_apply_s16() (at3hip_loudness.h); each detected by its symbol. One
+ *        change for existing entry points: at3hip_resampler_process() and at3hip_resampler_flush() rejected flag bit 8 with
+ *        AT3HIP_EINVAL before and now take it as AT3HIP_RESAMPLE_OUT_S16 (a library with at3hip_resampler_process_s16 does)
  * A host layer compiled against this header checks at3hip_version() >= AT3HIP_VERSION before it relies on them
  * (atracdenc_amd/host/at3hip_host.hpp and the ctypes stub do). */
 #define AT3HIP_VERSION_MAJOR 1

@@ -112,6 +112,21 @@ int at3hip_loudness_read_hops(at3hip_loudness* l, int32_t stream, void* dst, siz
  * at3hip_loudness_process. out may be in. Touches no meter state. */
 int at3hip_loudness_apply(at3hip_loudness* l, const float* in, int32_t n_in, const float* gains, float* out, uint32_t flags);
 
+/* at3hip_loudness_process and at3hip_loudness_apply for 16-bit PCM: in [n_streams][n_in][channels] int16; layout, flags, limits
+ * and error codes as for the float calls. A sample s is taken as the float (float)s * 0x1p-15f (exact, = s / 32768.0f: the rule
+ * of at3hip_encode_s16), so hop sums, peaks and results are, bit for bit, those of the float call on these floats, and
+ * at3hip_loudness_apply_s16 gives out = ((float)s * 0x1p-15f) * gains[stream] as float32 (out cannot be in). The samples are
+ * widened by the kernels' loads: host memory crosses the bus as 16-bit (half the bytes; its staging buffer is allocated by the
+ * first such call) and no float copy is written on the device. Calls of both kinds may alternate on one meter: the carried
+ * samples are float. A device pointer needs only int16_t alignment (a mono stream's row starts at s * n_in * 2 bytes). Added
+ * under ABI 1.6: a host looks for these symbols.
+ * What it gains (measured): at3hip_loudness_process is compute-bound, and its hop kernel takes 1.5 times as
+ * long on 16-bit samples as on floats; from host memory the 16-bit call is 1.1 times as fast as the float call, on samples that
+ * are in device memory as floats already the float call is the faster one. at3hip_loudness_apply_s16 is twice as fast as
+ * at3hip_loudness_apply from host memory. */
+int at3hip_loudness_process_s16(at3hip_loudness* l, const int16_t* in, int32_t n_in, uint32_t flags);
+int at3hip_loudness_apply_s16(at3hip_loudness* l, const int16_t* in, int32_t n_in, const float* gains, float* out, uint32_t flags);
+
 /* The gating of the definition on the host (no GPU needed): z [n_hops][channels] double -> integrated, momentary_max,
  * short_term_max, n_hops and n_blocks_kept of *result; its other fields are left as they are. */
 int at3hip_loudness_gate(const double* z, int32_t n_hops, int32_t channels, at3hip_loudness_result* result);

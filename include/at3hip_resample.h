@@ -68,6 +68,20 @@ int32_t at3hip_resampler_max_out(const at3hip_resampler* r);
  * flags: AT3HIP_PCM_ON_DEVICE (in is device memory), AT3HIP_OUT_ON_DEVICE, AT3HIP_ASYNC (only queue the call: in stays valid
  * and out is not read until at3hip_resampler_sync). *n_out is set before the call returns, also with AT3HIP_ASYNC. */
 int at3hip_resampler_process(at3hip_resampler* r, const float* in, int32_t n_in, float* out, int32_t* n_out, uint32_t flags);
+/* 16-bit output, the same bit as the decoders' *_DECODE_S16 flags: accepted by at3hip_resampler_process, at3hip_resampler_process_s16
+ * and at3hip_resampler_flush. out is then int16 [n_streams][*n_out][channels], every sample lrintf(clamp(x, -1, 1) * 32767.0f) of
+ * the float output x (the decoders' rule, behind a clamp). at3hip_resampler_process and at3hip_resampler_flush keep their
+ * float* out prototypes: a caller casts its int16_t pointer. A library that predates at3hip_resampler_process_s16 rejects the bit
+ * with AT3HIP_EINVAL in both: look for that symbol before setting it. */
+#define AT3HIP_RESAMPLE_OUT_S16 8u
+/* at3hip_resampler_process for 16-bit input: in [n_streams][n_in][channels] int16; layout, flags, limits and error codes as
+ * above, out float32, or int16 with AT3HIP_RESAMPLE_OUT_S16. A sample s is taken as the float (float)s * 0x1p-15f (exact,
+ * = s / 32768.0f: the rule of at3hip_encode_s16), so the outputs are, bit for bit, those of the float call on these floats. The
+ * samples are widened by the kernel's loads: host memory crosses the bus as 16-bit (half the bytes; its staging buffer is
+ * allocated by the first such call) and no float copy is written on the device. Calls of both kinds may alternate on one
+ * resampler: the carried history is float. A device pointer needs only int16_t alignment (a mono stream's row starts at
+ * s * n_in * 2 bytes). Added under ABI 1.6: a host looks for this symbol. */
+int at3hip_resampler_process_s16(at3hip_resampler* r, const int16_t* in, int32_t n_in, void* out, int32_t* n_out, uint32_t flags);
 /* The remaining outputs of every stream (zeros past the end of the input); then the start state. flags as above. */
 int at3hip_resampler_flush(at3hip_resampler* r, float* out, int32_t* n_out, uint32_t flags);
 /* Waits for everything queued on the resampler. */

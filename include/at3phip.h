@@ -75,6 +75,13 @@ int at3phip_write_frames(at3phip_ctx* ctx, const float* specs, int32_t n_frames,
  * tonal analysis that finds nothing; frame f holds input frame f (the reference's two-frame look-ahead delay is the
  * host's to add, see atracdenc_amd/host/at3hip_host.hpp). pcm as in at3phip_pqf_analyse, frames as above. */
 int at3phip_encode_frames(at3phip_ctx* ctx, const float* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags);
+/* The same for 16-bit PCM: pcm [n_streams][n_frames][2048][channels] int16, layout, flags, limits and error codes as above. A
+ * sample s is taken as the float (float)s * 0x1p-15f (exact, = s / 32768.0f: the rule of at3hip_encode_s16), so the frames are,
+ * bit for bit, those of the float call on these floats. The samples are widened by the filter bank's loads: host memory crosses
+ * the bus as 16-bit (half the bytes; its staging buffer is allocated by the first such call) and no float copy is written on
+ * the device. Calls of both kinds may alternate on one context: the carried state is float. A device pointer needs only int16_t
+ * alignment. Added under ABI 1.6: a host looks for this symbol. */
+int at3phip_encode_frames_short(at3phip_ctx* ctx, const int16_t* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags);
 /* With AT3HIP_ASYNC in `flags` at3phip_encode_frames only queues the call (pcm must stay valid, frames must not be read)
  * and the frame writer of one call runs beside the filter bank and transform of the next (its own stream, spectra
  * double-buffered); at3phip_sync waits for everything queued. Without the flag the call waits itself. A queued call records no

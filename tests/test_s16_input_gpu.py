@@ -1,0 +1,354 @@
+"""16-bit PCM at the input of the ATRAC1 encoder, the ATRAC3plus encoder, the resampler and the loudness meter (at1hip_encode_short,
+at3phip_encode_frames_short, at3hip_resampler_process_s16 with AT3HIP_RESAMPLE_OUT_S16, at3hip_loudness_process_s16 /
+_apply_s16): every 16-bit entry point gives, bit for bit, what the float entry point gives on the widened input
+((float)s * 0x1p-15f), also with the two kinds of call alternating on one context, from host memory and from device pointers
+that are only int16_t aligned. Every comparison is of bit patterns."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import s16_lib as S
+from atracdenc_amd import At1Hip, At3pHip, HipLoudness, HipResampler
+from atracdenc_amd.binding import AT3HIP_OUT_ON_DEVICE, AT3HIP_PCM_ON_DEVICE, AT3HIP_RESAMPLE_OUT_S16
+
+pytestmark = pytest.mark.gpu
+
+EINVAL = -1
+HOP = 4410
+DEV = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE
+
+
+def assert_same(got, want, what):
+    assert S.same_bits(got, want), what
+
+
+class DevPcm:
+    """int16 samples in device memory, `lead` sample frames into their allocation (lead = 1: a mono buffer is then only 2-byte
+    aligned); the copy is complete when the constructor returns (the engines' streams wait for no other stream)"""
+
+    def __init__(self, p16, lead):
+        import torch
+        p16 = np.ascontiguousarray(p16)
+        skip = lead * p16.shape[-1]
+        self.t = torch.zeros(skip + p16.size, dtype=torch.int16, device="cuda")
+        self.t[skip:] = torch.from_numpy(p16.reshape(-1)).cuda()
+        torch.cuda.synchronize()
+        self.ptr = self.t.data_ptr() + 2 * skip
+
+
+def dev_out(shape, dtype):
+    import torch
+    t = torch.zeros(shape, dtype=dtype, device="cuda")
+    torch.cuda.synchronize()
+    return t
+
+
+# ---- ATRAC1 --------------------------------------------------------------------------------------------------------------------
+AT1_CALLS = ((0, 3), (3, 5))   # blocks of the first and of the second call
+
+
+@pytest.fixture(scope="module", params=[1, 2])
+def at1_case(request):
+    """(channels, int16 PCM [3][5][512][C], its widened floats, the all-float context's frames per call)"""
+    C = request.param
+    p16 = S.pcm16(3, 5 * 512, C, seed=100 + C, quiet=(600, 1500)).reshape(3, 5, 512, C)
+    pf = S.widen(p16)
+    ref = At1Hip(n_streams=3, max_blocks=3, channels=C, window_auto=True)
+    try:
+        want = [ref.encode(pf[:, a:b]) for a, b in AT1_CALLS]
+    finally:
+        ref.close()
+    return C, p16, pf, want
+
+
+@pytest.mark.parametrize("kinds", ["ss", "sf", "fs"])
+def test_at1_host(at1_case, kinds):
+    """all 16-bit, 16-bit then float, float then 16-bit against the all-float context; the burst behind the silence really takes
+    the transient path (a short-window block in the masks tap)"""
+    C, p16, pf, want = at1_case
+    enc = At1Hip(n_streams=3, max_blocks=3, channels=C, window_auto=True)
+    try:
+        short_windows = 0
+        for (a, b), kind, w in zip(AT1_CALLS, kinds, want):
+            got = enc.encode_s16(p16[:, a:b]) if kind == "s" else enc.encode(pf[:, a:b])
+            assert_same(got, w, (kinds, a))
+            short_windows += int((enc.read_tap(At1Hip.TAP_MASKS, np.int32, (3, b - a, C)) != 0).sum())
+        assert short_windows > 0
+    finally:
+        enc.close()
+
+
+@pytest.mark.parametrize("lead", [0, 1])
+def test_at1_device_pointers(at1_case, lead):
+    """device-resident 16-bit PCM, at the start of its allocation and a single sample frame into it"""
+    import torch
+    C, p16, pf, want = at1_case
+    enc = At1Hip(n_streams=3, max_blocks=3, channels=C, window_auto=True)
+    try:
+        for (a, b), w in zip(AT1_CALLS, want):
+            src, out = DevPcm(p16[:, a:b], lead), dev_out(w.shape, torch.uint8)
+            enc.encode_device_s16(src.ptr, b - a, out.data_ptr())
+            assert_same(out.cpu().numpy(), w, (lead, a))
+    finally:
+        enc.close()
+
+
+# ---- ATRAC3plus ----------------------------------------------------------------------------------------------------------------
+AT3P_CALLS = ((0, 2), (2, 3))
+
+
+@pytest.fixture(scope="module", params=[1, 2])
+def at3p_case(request):
+    C = request.param
+    p16 = S.pcm16(2, 3 * 2048, C, seed=200 + C, quiet=(2500, 3300)).reshape(2, 3, 2048, C)
+    pf = S.widen(p16)
+    ref = At3pHip(n_streams=2, max_frames=2, channels=C)
+    try:
+        want = [ref.encode_frames(pf[:, a:b]) for a, b in AT3P_CALLS]
+    finally:
+        ref.close()
+    return C, p16, pf, want
+
+
+@pytest.mark.parametrize("kinds", ["ss", "sf", "fs"])
+def test_at3p_host(at3p_case, kinds):
+    C, p16, pf, want = at3p_case
+    enc = At3pHip(n_streams=2, max_frames=2, channels=C)
+    try:
+        for (a, b), kind, w in zip(AT3P_CALLS, kinds, want):
+            got = enc.encode_frames_s16(p16[:, a:b]) if kind == "s" else enc.encode_frames(pf[:, a:b])
+            assert_same(got, w, (kinds, a))
+    finally:
+        enc.close()
+
+
+@pytest.mark.parametrize("lead", [0, 1])
+def test_at3p_device_pointers(at3p_case, lead):
+    import torch
+    C, p16, pf, want = at3p_case
+    enc = At3pHip(n_streams=2, max_frames=2, channels=C)
+    try:
+        for (a, b), w in zip(AT3P_CALLS, want):
+            src, out = DevPcm(p16[:, a:b], lead), dev_out(w.shape, torch.uint8)
+            enc.encode_frames_device_s16(src.ptr, b - a, out.data_ptr())
+            assert_same(out.cpu().numpy(), w, (lead, a))
+    finally:
+        enc.close()
+
+
+# ---- resampler -----------------------------------------------------------------------------------------------------------------
+RS_CUTS = ((0, 1001), (1001, 1334))   # n_in 1001, then 333 (odd: a mono stream's row is only 2-byte aligned), then the flush
+RATES = [(48000, 44100), (44100, 48000), (8000, 44100), (44100, 8000)]
+
+
+@pytest.fixture(scope="module", params=[(r, c) for r in RATES for c in (1, 2)], ids=lambda p: f"{p[0][0]}-{p[0][1]}-ch{p[1]}")
+def rs_case(request):
+    """(rates, channels, int16 [3][1334][C] with stream 1 a full-scale square wave, its floats, the float path's outputs)"""
+    (fin, fout), C = request.param
+    p16 = S.pcm16(3, 1334, C, seed=300 + C + fin // 1000)
+    p16[1] = S.square16(1334, C, period=100)
+    pf = S.widen(p16)
+    ref = HipResampler(fin, fout, channels=C, n_streams=3, max_in=1001)
+    try:
+        want = [ref.process(pf[:, a:b]) for a, b in RS_CUTS] + [ref.flush()]
+    finally:
+        ref.close()
+    return (fin, fout), C, p16, pf, want
+
+
+def test_resampler_float_out(rs_case):
+    (fin, fout), C, p16, pf, want = rs_case
+    r = HipResampler(fin, fout, channels=C, n_streams=3, max_in=1001)
+    try:
+        for kinds in ("ss", "sf", "fs"):
+            got = [r.process_s16(p16[:, a:b]) if k == "s" else r.process(pf[:, a:b]) for (a, b), k in zip(RS_CUTS, kinds)] + [r.flush()]
+            for i, (g, w) in enumerate(zip(got, want)):
+                assert g.shape[1] == w.shape[1], (kinds, i)
+                assert_same(g, w, (kinds, i))
+    finally:
+        r.close()
+
+
+def test_resampler_s16_out(rs_case):
+    """AT3HIP_RESAMPLE_OUT_S16 on the float-in and on the 16-bit-in calls and on the flush; the square wave overshoots 1, so the
+    clamp is exercised"""
+    (fin, fout), C, p16, pf, want = rs_case
+    assert max(float(w.max()) for w in want if w.size) > 1.0
+    r = HipResampler(fin, fout, channels=C, n_streams=3, max_in=1001)
+    try:
+        for kinds in ("ss", "ff", "sf"):
+            got = [r.process_s16(p16[:, a:b], out_s16=True) if k == "s" else r.process(pf[:, a:b], out_s16=True)
+                   for (a, b), k in zip(RS_CUTS, kinds)] + [r.flush(out_s16=True)]
+            for i, (g, w) in enumerate(zip(got, want)):
+                assert g.dtype == np.int16
+                assert_same(g, S.out_s16_of(w), (kinds, i))
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("lead", [0, 1])
+def test_resampler_device_pointers(rs_case, lead):
+    import torch
+    (fin, fout), C, p16, pf, want = rs_case
+    r = HipResampler(fin, fout, channels=C, n_streams=3, max_in=1001)
+    try:
+        for (a, b), w in zip(RS_CUTS, want):
+            src, out = DevPcm(p16[:, a:b], lead), dev_out((3, r.max_out, C), torch.int16)
+            n = r.process_s16_ptr(src.ptr, b - a, out.data_ptr(), DEV | AT3HIP_RESAMPLE_OUT_S16)
+            assert n == w.shape[1]
+            assert_same(out.cpu().numpy().reshape(-1)[: 3 * n * C].reshape(3, n, C), S.out_s16_of(w), (lead, a))
+    finally:
+        r.close()
+
+
+# ---- loudness ------------------------------------------------------------------------------------------------------------------
+LD_CUTS = ((0, 5000), (5000, 5000 + 3 * HOP + 7), (5000 + 3 * HOP + 7, 5000 + 3 * HOP + 8))   # 5000, 3 * 4410 + 7 and 1 samples
+LD_T = LD_CUTS[-1][1]
+
+
+@pytest.fixture(scope="module", params=[1, 2])
+def ld_case(request):
+    C = request.param
+    p16 = S.pcm16(2, LD_T, C, seed=400 + C, quiet=(7000, 9000))
+    pf = S.widen(p16)
+    ref = HipLoudness(channels=C, n_streams=2, max_in=3 * HOP + 7, max_hops=4, true_peak=True)
+    try:
+        for a, b in LD_CUTS:
+            ref.process(pf[:, a:b])
+        want = (ref.hops(), ref.finish())
+    finally:
+        ref.close()
+    return C, p16, pf, want
+
+
+def assert_meter(m, want, what):
+    z, res = m.hops(), m.finish()
+    assert_same(z, want[0], (what, "z"))
+    for i, (g, w) in enumerate(zip(res, want[1])):
+        assert S.result_mismatches(g, w) == [], (what, i)
+
+
+def test_loudness_host(ld_case):
+    C, p16, pf, want = ld_case
+    assert want[0].shape[1] == 4 and want[1][0].true_peak[0] > 0
+    m = HipLoudness(channels=C, n_streams=2, max_in=3 * HOP + 7, max_hops=4, true_peak=True)
+    try:
+        for kinds in ("sss", "sfs", "fsf"):
+            for (a, b), k in zip(LD_CUTS, kinds):
+                if k == "s":
+                    m.process_s16(p16[:, a:b])
+                else:
+                    m.process(pf[:, a:b])
+            assert_meter(m, want, kinds)
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("lead", [0, 1])
+def test_loudness_device_pointers(ld_case, lead):
+    C, p16, pf, want = ld_case
+    m = HipLoudness(channels=C, n_streams=2, max_in=3 * HOP + 7, max_hops=4, true_peak=True)
+    try:
+        for a, b in LD_CUTS:
+            src = DevPcm(p16[:, a:b], lead)
+            m.process_s16_ptr(src.ptr, b - a, AT3HIP_PCM_ON_DEVICE)
+        assert_meter(m, want, lead)
+    finally:
+        m.close()
+
+
+def test_loudness_apply_s16(ld_case):
+    """a gain that is no power of two; lengths that take the four-sample form and the scalar form, host and device memory"""
+    import torch
+    C, p16, pf, want = ld_case
+    g = np.array([0.7371, 1.913], np.float32)
+    m = HipLoudness(channels=C, n_streams=2, max_in=3 * HOP + 7, max_hops=4)
+    try:
+        for n in (5000, 3 * HOP + 7, 1):
+            w = m.apply(pf[:, :n], g)
+            assert_same(w, pf[:, :n] * g[:, None, None], n)
+            assert_same(m.apply_s16(p16[:, :n], g), w, n)
+            for lead in (0, 1):
+                src, out = DevPcm(p16[:, :n], lead), dev_out(w.shape, torch.float32)
+                m.apply_s16_ptr(src.ptr, n, g, out.data_ptr(), DEV)
+                assert_same(out.cpu().numpy(), w, (n, lead))
+    finally:
+        m.close()
+
+
+# ---- arguments -----------------------------------------------------------------------------------------------------------------
+def test_bad_arguments_leave_the_contexts_usable():
+    """NULL input and a count above the create-time limit are AT3HIP_EINVAL; the next good call gives what a fresh context gives"""
+    vp = ctypes.c_void_p
+    n = ctypes.c_int32()
+    p16 = S.pcm16(1, 2048, 2, seed=7)
+    pf = S.widen(p16)
+
+    enc = At1Hip(n_streams=1, max_blocks=2, channels=2)
+    ref = At1Hip(n_streams=1, max_blocks=2, channels=2)
+    try:
+        out = np.zeros((1, 3, 2, 212), np.uint8)
+        big = np.zeros((1, 3, 512, 2), np.int16)
+        assert enc.lib.at1hip_encode_short(enc.ctx, None, 1, vp(out.ctypes.data), 0) == EINVAL
+        assert enc.lib.at1hip_encode_short(enc.ctx, vp(big.ctypes.data), 3, vp(out.ctypes.data), 0) == EINVAL
+        assert_same(enc.encode_s16(p16.reshape(1, 4, 512, 2)[:, :2]), ref.encode(pf.reshape(1, 4, 512, 2)[:, :2]), "at1")
+    finally:
+        enc.close()
+        ref.close()
+
+    enc = At3pHip(n_streams=1, max_frames=1, channels=2)
+    ref = At3pHip(n_streams=1, max_frames=1, channels=2)
+    try:
+        out = np.zeros((1, 2, 2048), np.uint8)
+        big = np.zeros((1, 2, 2048, 2), np.int16)
+        assert enc.lib.at3phip_encode_frames_short(enc.ctx, None, 1, vp(out.ctypes.data), 0) == EINVAL
+        assert enc.lib.at3phip_encode_frames_short(enc.ctx, vp(big.ctypes.data), 2, vp(out.ctypes.data), 0) == EINVAL
+        assert_same(enc.encode_frames_s16(p16.reshape(1, 1, 2048, 2)), ref.encode_frames(pf.reshape(1, 1, 2048, 2)), "at3p")
+    finally:
+        enc.close()
+        ref.close()
+
+    r = HipResampler(48000, 44100, channels=2, n_streams=1, max_in=1000)
+    ref = HipResampler(48000, 44100, channels=2, n_streams=1, max_in=1000)
+    try:
+        out = np.zeros((1, r.max_out, 2), np.float32)
+        assert r.lib.at3hip_resampler_process_s16(r.ctx, None, 10, vp(out.ctypes.data), ctypes.byref(n), 0) == EINVAL
+        assert r.lib.at3hip_resampler_process_s16(r.ctx, vp(p16.ctypes.data), 1001, vp(out.ctypes.data), ctypes.byref(n), 0) == EINVAL
+        assert_same(r.process_s16(p16[:, :1000]), ref.process(pf[:, :1000]), "resampler")
+    finally:
+        r.close()
+        ref.close()
+
+    m = HipLoudness(channels=2, n_streams=1, max_in=1000, max_hops=1)
+    ref = HipLoudness(channels=2, n_streams=1, max_in=1000, max_hops=1)
+    try:
+        g = np.array([0.31], np.float32)
+        out = np.zeros((1, 1001, 2), np.float32)
+        assert m.lib.at3hip_loudness_process_s16(m.ctx, None, 10, 0) == EINVAL
+        assert m.lib.at3hip_loudness_process_s16(m.ctx, vp(p16.ctypes.data), 1001, 0) == EINVAL
+        assert m.lib.at3hip_loudness_apply_s16(m.ctx, None, 10, vp(g.ctypes.data), vp(out.ctypes.data), 0) == EINVAL
+        assert m.lib.at3hip_loudness_apply_s16(m.ctx, vp(p16.ctypes.data), 1001, vp(g.ctypes.data), vp(out.ctypes.data), 0) == EINVAL
+        m.process_s16(p16[:, :1000])
+        ref.process(pf[:, :1000])
+        assert S.result_mismatches(m.finish()[0], ref.finish()[0]) == []
+        assert_same(m.apply_s16(p16[:, :1000], g), ref.apply(pf[:, :1000], g), "apply")
+    finally:
+        m.close()
+        ref.close()
+
+
+# ---- the C++ mirror ------------------------------------------------------------------------------------------------------------
+def test_host_cpp_shim_s16(tmp_path):
+    """The 16-bit entry points of the C++ mirror (atracdenc_amd/host/at3hip_host.hpp) against its float entry points: the
+    stand-alone program tests/host/test_host_shim_s16.cpp, which this test is about, built and run once."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "test_host_shim_s16")
+    libdir = os.path.join(root, "atracdenc_amd")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(root, "tests", "host", "test_host_shim_s16.cpp"), "-o", exe,
+                           f"-L{libdir}", "-lat3hip", f"-Wl,-rpath,{libdir}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "HOST SHIM S16 TEST OK\n" in out.stdout, out.stdout
