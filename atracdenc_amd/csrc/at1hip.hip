@@ -16,10 +16,8 @@ using at3host::fail;
 
 static_assert(sizeof(Tables) == AT1HIP_TABLES_BYTES, "at1hip.h documents the table block's size");
 
-struct at1hip_ctx {
+struct at1hip_ctx : at3host::EngineBase {   // (no at1hip_set_stream: stream == own_stream)
     at1hip_config cfg;
-    int device = 0;
-    hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {};
     bool tm_pending = false;      // a call's stage events have not been read yet (AT3HIP_ASYNC)
     Tables* d_tables = nullptr;
@@ -38,7 +36,6 @@ struct at1hip_ctx {
     long long blocks_fed = 0;
     int last_blocks = 0;
     at1hip_timings tm = {};
-    char err[256] = {0};
 };
 
 namespace {
@@ -47,13 +44,8 @@ int reset_state(at1hip_ctx* c)
 {
     const size_t S = c->cfg.n_streams;
     HIPCHK(c, hipMemsetAsync(c->d_hist, 0, S * 512 * c->cfg.channels * sizeof(float), c->stream));
-    float* init = (float*)malloc(S * sizeof(float));
-    if (!init) return fail(c, AT3HIP_ENOMEM, "malloc");
-    for (size_t i = 0; i < S; ++i) init[i] = 0.006f;  // LoudFactor, atrac1denc.h:101-102
-    hipError_t e = hipMemcpyAsync(c->d_loud_state, init, S * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    free(init);
-    if (e != hipSuccess) return fail(c, AT3HIP_EDEVICE, "state upload", e);
+    const int rc = at3host::fill_and_wait(c, c->d_loud_state, S, 0.006f);   // LoudFactor, atrac1denc.h:101-102
+    if (rc != AT3HIP_OK) return rc;
     c->blocks_fed = 0;
     return AT3HIP_OK;
 }
@@ -70,65 +62,40 @@ int at1hip_create(const at1hip_config* cfg, at1hip_ctx** out)
         cfg->bfu_idx_const > 8 || cfg->window_mask < 0 || cfg->window_mask > 7)
         return AT3HIP_EINVAL;
     if ((long long)cfg->n_streams * cfg->channels > at3host::kMaxGridY) return AT3HIP_EINVAL;   // (stream, channel) is gridDim.y
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return AT3HIP_EDEVICE;
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return AT3HIP_EINVAL;
-    at1hip_ctx* c = new (std::nothrow) at1hip_ctx();
-    if (!c) return AT3HIP_ENOMEM;
-    c->cfg = *cfg;
-    c->device = cfg->device_id;
-    int rc = AT3HIP_OK;
-    auto bail = [&](int code) {
-        at1hip_destroy(c);
-        return code;
-    };
-    at3host::DeviceGuard guard(c->device);
-    if (guard.error() != hipSuccess) return bail(AT3HIP_EDEVICE);
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    for (auto& e : c->ev)
-        if (hipEventCreate(&e) != hipSuccess) return bail(AT3HIP_EDEVICE);
-
-    Tables* host_tables = new (std::nothrow) Tables();
-    if (!host_tables) return bail(AT3HIP_ENOMEM);
-    build_tables(host_tables);
-    rc = dev_alloc(c, &c->d_tables, 1);
-    if (rc == AT3HIP_OK) rc = at3host::upload_table(c->d_tables, host_tables, sizeof(Tables));
-    delete host_tables;
-    if (rc != AT3HIP_OK) return bail(rc);
-
-    const size_t S = cfg->n_streams, B = cfg->max_blocks, C = cfg->channels;
-    if ((rc = dev_alloc(c, &c->d_pcm_in, S * B * 512 * C)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_hist, S * 512 * C)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_specs, S * B * C * 512)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_values, S * B * C * 512)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_energy, S * B * C * kMaxBfus)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_sfi, S * B * C * 64)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_mask, S * B * C)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_loud_ch, S * B * C)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_loud_state, S)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_loud_track, S * B)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_out, S * B * C * kFrame)) != AT3HIP_OK) return bail(rc);
-    if ((rc = reset_state(c)) != AT3HIP_OK) return bail(rc);
-    *out = c;
-    return AT3HIP_OK;
+    return at3host::create_engine(cfg->device_id, out, at1hip_destroy, [cfg](at1hip_ctx* c) {
+        c->cfg = *cfg;
+        for (auto& e : c->ev)
+            if (hipEventCreate(&e) != hipSuccess) return AT3HIP_EDEVICE;
+        int rc = at3host::make_device_tables(c, &c->d_tables, [](Tables* t) { build_tables(t); return true; });
+        if (rc != AT3HIP_OK) return rc;
+        const size_t S = cfg->n_streams, B = cfg->max_blocks, C = cfg->channels;
+        if ((rc = dev_alloc(c, &c->d_pcm_in, S * B * 512 * C)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_hist, S * 512 * C)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_specs, S * B * C * 512)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_values, S * B * C * 512)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_energy, S * B * C * kMaxBfus)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_sfi, S * B * C * 64)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_mask, S * B * C)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_loud_ch, S * B * C)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_loud_state, S)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_loud_track, S * B)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_out, S * B * C * kFrame)) != AT3HIP_OK) return rc;
+        return reset_state(c);
+    });
 }
 
 void at1hip_destroy(at1hip_ctx* c)
 {
-    if (!c) return;
-    at3host::DeviceGuard guard(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void* bufs[] = {c->d_tables, c->d_pcm_in, c->d_pcm_s16, c->d_hist,       c->d_specs,      c->d_values, c->d_energy,
-                    c->d_sfi,    c->d_mask,   c->d_loud_ch,    c->d_loud_state, c->d_loud_track, c->d_out};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (auto& e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c)
+        at3host::destroy_engine(c, {c->d_tables, c->d_pcm_in, c->d_pcm_s16, c->d_hist, c->d_specs, c->d_values, c->d_energy, c->d_sfi, c->d_mask,
+                                    c->d_loud_ch, c->d_loud_state, c->d_loud_track, c->d_out},
+                                {}, [c] {
+                                    for (hipEvent_t e : c->ev)
+                                        if (e) (void)hipEventDestroy(e);
+                                });
 }
 
-const char* at1hip_last_error(const at1hip_ctx* c) { return c ? c->err : "null context"; }
+const char* at1hip_last_error(const at1hip_ctx* c) { return at3host::engine_last_error(c); }
 
 int at1hip_reset(at1hip_ctx* c)
 {

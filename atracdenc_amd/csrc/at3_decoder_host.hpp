@@ -12,19 +12,15 @@ struct DecoderBase : EngineBase {
     unsigned long long* d_rejected = nullptr;   // the decoder's rejection counters
 };
 
-// *_decoder_create after the decoder's own configuration checks: create_engine on cfg->device_id, whose setup builds the
-// decoder's table block on the host with build_tables (false: out of memory), uploads it to d_tables, then runs setup(d) for
-// the decoder's buffers and state.
+// *_decoder_create after the decoder's own configuration checks: create_engine on cfg->device_id, whose setup makes the
+// decoder's table block d_tables with build_tables (false: out of memory), then runs setup(d) for the decoder's buffers and
+// state.
 template <typename Dec, typename Cfg, typename Tables, typename Setup>
 int create_decoder(const Cfg* cfg, Dec** out, bool (*build_tables)(Tables*), void (*destroy)(Dec*), Setup setup)
 {
     return create_engine(cfg->device_id, out, destroy, [&](Dec* d) {
         d->cfg = *cfg;
-        Tables* host_tables = new (std::nothrow) Tables();
-        if (!host_tables) return AT3HIP_ENOMEM;
-        int rc = build_tables(host_tables) ? dev_alloc(d, &d->d_tables, 1) : AT3HIP_ENOMEM;
-        if (rc == AT3HIP_OK) rc = upload_table(d->d_tables, host_tables, sizeof(Tables));
-        delete host_tables;
+        const int rc = make_device_tables(d, &d->d_tables, build_tables);
         return rc != AT3HIP_OK ? rc : setup(d);
     });
 }

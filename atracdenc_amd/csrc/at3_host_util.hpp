@@ -1,9 +1,11 @@
 // Host-side helpers shared by the C-ABI translation units (at3hip.hip, at1hip.hip, at3phip.hip, resample.hip, loudness.hip):
-// error recording, device allocation, the device guard, and the engine base - what every context with one stream (the three
-// decoders, the resampler, the loudness meter) does the same way: create prologue, table upload, destroy, sync, set_stream,
-// last_error and the tail of a call that gives host memory. The decoders' further shared part is at3_decoder_host.hpp.
+// error recording, device allocation, the device guard, and the engine base - what every context (the three encoders, the
+// three decoders, the resampler, the loudness meter) does the same way: create prologue, table upload, destroy, last_error,
+// and for those with one stream sync, set_stream and the tail of a call that gives host memory. The decoders' further shared
+// part is at3_decoder_host.hpp.
 #pragma once
 #include <cstdio>
+#include <cstdlib>
 #include <initializer_list>
 #include <new>
 
@@ -66,7 +68,7 @@ private:
 
 constexpr int kMaxGridY = 65535;   // gridDim.y / gridDim.z limit of the HIP launch interface
 
-// The part of a context every single-stream engine has; an engine's context derives from it.
+// The part of a context every engine has; an engine's context derives from it.
 struct EngineBase {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -74,11 +76,11 @@ struct EngineBase {
     char err[256] = {0};
 };
 
-// *_create after the engine's own configuration checks. Checks device_id, makes the engine on that device with a non-blocking
-// stream of its own, then runs setup(e) for its tables, buffers and state. A failure destroys the half-made engine and returns
-// the code.
-template <typename Eng, typename Destroy, typename Setup>
-int create_engine(int device_id, Eng** out, Destroy destroy, Setup setup)
+// *_create after the engine's own configuration checks. Checks device_id, makes the engine on that device with a stream of its
+// own - make_stream(&own_stream), by default a non-blocking one -, then runs setup(e) for its further streams, tables, buffers
+// and state. A failure destroys the half-made engine and returns the code.
+template <typename Eng, typename Destroy, typename Setup, typename MakeStream>
+int create_engine(int device_id, Eng** out, Destroy destroy, Setup setup, MakeStream make_stream)
 {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return AT3HIP_EDEVICE;
@@ -88,7 +90,7 @@ int create_engine(int device_id, Eng** out, Destroy destroy, Setup setup)
     e->device = device_id;
     DeviceGuard guard(e->device);
     int rc = AT3HIP_EDEVICE;
-    if (guard.error() == hipSuccess && hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking) == hipSuccess) {
+    if (guard.error() == hipSuccess && make_stream(&e->own_stream) == hipSuccess) {
         e->stream = e->own_stream;
         rc = setup(e);
     }
@@ -99,27 +101,70 @@ int create_engine(int device_id, Eng** out, Destroy destroy, Setup setup)
     *out = e;
     return AT3HIP_OK;
 }
+template <typename Eng, typename Destroy, typename Setup>
+int create_engine(int device_id, Eng** out, Destroy destroy, Setup setup)
+{
+    return create_engine(device_id, out, destroy, setup, [](hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); });
+}
 
-// Uploads a table built in pageable host memory: the blocking copy may return once the data is staged, so the device is
-// drained before anything on a non-blocking stream can read the table (see at3hip_create).
+// Uploads a table built in pageable host memory. From pageable memory a blocking copy may return once the data is STAGED: the
+// transfer itself may then still run on the null stream, which the contexts' non-blocking streams do not wait for. As a
+// precaution - no wrong table has been observed - the device is drained here, once per table, before anything can read it.
 inline int upload_table(void* dst, const void* src, size_t bytes)
 {
     if (hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return AT3HIP_EDEVICE;
     return AT3HIP_OK;
 }
 
-// *_destroy of a non-null engine: waits for its stream, frees `bufs` and its own stream, deletes it.
-template <typename Eng>
-void destroy_engine(Eng* e, std::initializer_list<void*> bufs)
+// A table block of a context: allocated on the host, filled by build(block) (false: out of memory), uploaded to a device
+// allocation of its own (*d_tables), freed on the host.
+template <typename Ctx, typename Tables, typename Build>
+int make_device_tables(Ctx* c, Tables** d_tables, Build build)
+{
+    Tables* host_tables = new (std::nothrow) Tables();
+    if (!host_tables) return AT3HIP_ENOMEM;
+    int rc = build(host_tables) ? dev_alloc(c, d_tables, 1) : AT3HIP_ENOMEM;
+    if (rc == AT3HIP_OK) rc = upload_table(*d_tables, host_tables, sizeof(Tables));
+    delete host_tables;
+    return rc;
+}
+
+// Fills the device array d[0 .. n) with `value` on the engine's stream and waits for it.
+inline int fill_and_wait(EngineBase* e, float* d, size_t n, float value)
+{
+    float* init = (float*)malloc(n * sizeof(float));
+    if (!init) return fail(e, AT3HIP_ENOMEM, "malloc");
+    for (size_t i = 0; i < n; ++i) init[i] = value;
+    hipError_t err = hipMemcpyAsync(d, init, n * sizeof(float), hipMemcpyHostToDevice, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    free(init);
+    if (err != hipSuccess) return fail(e, AT3HIP_EDEVICE, "state upload", err);
+    return AT3HIP_OK;
+}
+
+// *_destroy of a non-null engine, half-made ones included: waits for its stream and for `streams` (further ones of its own),
+// frees `bufs`, runs destroy_events() for the engine's events, destroys `streams` and its own stream, deletes it.
+template <typename Eng, typename DestroyEvents>
+void destroy_engine(Eng* e, std::initializer_list<void*> bufs, std::initializer_list<hipStream_t> streams, DestroyEvents destroy_events)
 {
     {
         DeviceGuard guard(e->device);
         if (e->stream) (void)hipStreamSynchronize(e->stream);
+        for (hipStream_t s : streams)
+            if (s) (void)hipStreamSynchronize(s);
         for (void* b : bufs)
             if (b) (void)hipFree(b);
+        destroy_events();
+        for (hipStream_t s : streams)
+            if (s) (void)hipStreamDestroy(s);
         if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     }
     delete e;
+}
+template <typename Eng>
+void destroy_engine(Eng* e, std::initializer_list<void*> bufs)
+{
+    destroy_engine(e, bufs, {}, [] {});
 }
 
 inline const char* engine_last_error(const EngineBase* e) { return e ? e->err : "null context"; }

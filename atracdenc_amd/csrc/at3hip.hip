@@ -39,58 +39,68 @@ struct DevBuf {
 
 // AT3HIP_TAP_CLOCK: 16 words, of which k_alloc_pack writes words 0 and 1
 constexpr size_t kClkWords = 16;
-struct at3hip_ctx {
+struct at3hip_ctx : at3host::EngineBase {
+    // An event of the context's own, and whether anything has been recorded on it yet: waiting for a fresh one is no call at all.
+    struct Event {
+        hipEvent_t ev = nullptr;
+        bool recorded = false;
+        hipError_t record(hipStream_t s)
+        {
+            const hipError_t e = hipEventRecord(ev, s);
+            if (e == hipSuccess) recorded = true;
+            return e;
+        }
+        hipError_t make_wait(hipStream_t s) const { return recorded ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }   // `s` waits for the last record
+        hipError_t host_wait() const { return recorded ? hipEventSynchronize(ev) : hipSuccess; }
+    };
+
     at3hip_config cfg;
     int frame_sz = 0;
     int js = 0;
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;        // front half: QMF, gain control, fused QMF+MDCT, carried state
+    // The back half of call N only consumes what the front half of call N produced (spectra, curves, energy scales),
+    // and the front half of call N+1 only depends on the front half of call N (carried state): the two halves run on
+    // HIP streams of their own (three with gain control, see mid_stream below), buffers that cross between them are double-buffered by call parity, and consecutive calls overlap.
+    // (EngineBase::stream: the front half - QMF, gain control, fused QMF+MDCT, carried state)
     hipStream_t back_stream = nullptr;   // back half: psychoacoustics, quantisation, rate loop, packing
     // With gain control the front half is two stages: the heavy one (QMF, spectra of the gain analysis, upsampled envelopes)
     // depends only on the PCM, the light one (curve context scan, curves, energy scales, MDCT) on it and on the previous
     // call's light stage. The light stage is a chain of short latency-bound kernels; on a stream of its own it runs under
     // the next call's heavy stage and the current call's back half instead of holding the GPU nearly idle between them.
     hipStream_t mid_stream = nullptr;
-    float* d_sub_b[2] = {nullptr, nullptr};      // subbands, by call parity (the heavy stage runs one call ahead)
-    GainRec* d_rec_b[2] = {nullptr, nullptr};
-    hipEvent_t ev_mid_done[2] = {};              // light stage finished with the parity's subbands and gain records
-    bool mid_done_valid[2] = {false, false};
-    hipEvent_t mid_done_of[2] = {};              // the event that says so for the parity's last call: its ev_mdct_done, or ev_mid_done (not owned)
-    // The back half of call N only consumes what the front half of call N produced (spectra, curves, energy scales),
-    // and the front half of call N+1 only depends on the front half of call N (carried state): the two halves run on
-    // HIP streams of their own (three with gain control, see mid_stream below), buffers that cross between them are double-buffered by call parity, and consecutive calls overlap.
-    static constexpr int kSlots = 32;    // timing history (events per call)
-    hipEvent_t ev[kSlots][8] = {};
-    hipEvent_t ev_front_done = nullptr;  // everything the most recent call queued on `stream` (which may be the caller's)
-    bool front_done_valid = false;
     // Host PCM: staged through a copy stream into device staging that is double-buffered by call parity, so that the
     // H2D copy of call N+1 runs beside the kernels of call N (pinned host memory: at3hip_host_alloc).
     hipStream_t h2d_stream = nullptr;
-    float* d_pcm_in_b[2] = {nullptr, nullptr};      // [S][max_blocks][1024][channels]
-    int16_t* d_s16_b[2] = {nullptr, nullptr};       // the same as 16-bit samples (at3hip_encode_s16 with host memory), by call parity
-    hipEvent_t ev_h2d[2] = {};                      // the parity's PCM has arrived
-    hipEvent_t ev_pcm_free[2] = {};                 // the parity's staging has been consumed (front half done with it)
-    bool pcm_free_valid[2] = {false, false};
-    bool h2d_valid[2] = {false, false};
-    hipEvent_t ev_back_done[2] = {};     // back half finished with the parity's cross buffers (the ev_host_out of that call: not owned)
-    // what the HOST waits for (at3hip_wait_input / at3hip_wait_frames), per call in a ring of four: the parity events above are
+
+    // ---- events; the context owns all of them but the two `*_of` handles (for_each_event lists them in creation order) ----
+    hipEvent_t ev_h2d[2] = {};           // by call parity: the parity's PCM has arrived in its staging (copy stream -> front stream)
+    Event pcm_free[2];                   // by call parity: the staging has been consumed, the front half is done with it (front stream -> copy stream)
+    static constexpr int kSlots = 32;    // timing history (events per call)
+    hipEvent_t ev[kSlots][8] = {};       // a call's stage timestamps
+    Event front_done;                    // everything the most recent call queued on `stream` when that is the caller's (at3hip_destroy)
+    hipEvent_t ev_heavy_done[kSlots] = {}, ev_mdct_done[kSlots] = {};   // a call's own hand-overs between its streams: heavy -> light stage, front -> back half
+    // what the HOST waits for (at3hip_wait_input / at3hip_wait_frames), per call in a ring of four: the parity events are
     // re-recorded by the call after next, so a caller with three calls in flight would wait for the newest of them
     static constexpr int kHostRing = 4;
-    hipEvent_t ev_host_in[kHostRing] = {}, ev_host_out[kHostRing] = {};
-    bool host_in_valid[kHostRing] = {}, host_out_valid[kHostRing] = {};
-    bool back_done_valid[2] = {false, false};
+    Event host_in[kHostRing];            // the call's host PCM has been copied (nothing recorded: the call copied none)
+    Event host_out[kHostRing];           // the call's frames are out and its back half is done (nothing recorded: the call produced none)
+    hipEvent_t ev_mid_done[2] = {};      // by call parity: light stage of a call WITHOUT frames finished
+    // What the next call of the same parity waits for before it reuses the parity's buffers; null: nothing yet.
+    hipEvent_t mid_done_of[2] = {};      // light stage done with the subbands and gain records: the call's ev_mdct_done, or ev_mid_done (light -> heavy stage)
+    hipEvent_t back_done_of[2] = {};     // back half done with the spectra, curves and energy scales: the call's host_out (back half -> light stage)
+
+    float* d_sub_b[2] = {nullptr, nullptr};      // subbands, by call parity (the heavy stage runs one call ahead)
+    GainRec* d_rec_b[2] = {nullptr, nullptr};
+    float* d_pcm_in_b[2] = {nullptr, nullptr};      // host PCM staging [S][max_blocks][1024][channels]
+    int16_t* d_s16_b[2] = {nullptr, nullptr};       // the same as 16-bit samples (at3hip_encode_s16 with host memory), by call parity
     long long enc_calls = 0;             // at3hip_encode calls so far
     int last_slot = -1;                  // slot of the most recent call that produced frames
     bool slot_has_frames[kSlots] = {};
     int slot_k1_launches[kSlots] = {};   // kernels the QMF + MDCT work of the slot's call was spread over (1 = fused, 2)
-    char err[256] = {0};
     long long blocks_fed = 0;   // per stream
     int chain_mode = 0;      // AT3HIP_OPT_CHAIN: 0 = chosen per call, 1 = never, 2 = whenever the geometry allows
     int timing_every = 1;    // AT3HIP_OPT_TIMING_EVERY: stage timings on every Nth call with frames (0 = never)
     unsigned timing_tick = 0;
     bool slot_timed[kSlots] = {};
-    hipEvent_t ev_heavy_done[kSlots] = {}, ev_mdct_done[kSlots] = {};   // a call's own hand-overs between its streams (no timestamps)
     int runs_override = 0;   // AT3HIP_OPT_RUNS: runs per (stream, channel) of the front-end kernels (tuning aid; output is invariant)
     int flat_literal = 0;    // AT3HIP_OPT_LITERAL_FORMS
     int gain_form = AT3HIP_GAIN_FORM_TWO_WAVES;   // AT3HIP_OPT_GAIN_FORM: the two-wavefront workgroups (default) or one wavefront per item (k_gain_analysis1)
@@ -323,16 +333,31 @@ int reset_state(at3hip_ctx* c)
     HIPCHK(c, hipMemsetAsync(c->d_state, 0, S * 8 * sizeof(BandState), c->stream));
     if (c->d_sub_tail) HIPCHK(c, hipMemsetAsync(c->d_sub_tail, 0, S * 8 * 512 * sizeof(float), c->stream));   // silence before the stream
     HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 2 * sizeof(unsigned long long), c->stream));
-    float* init = (float*)malloc(S * sizeof(float));
-    if (!init) return fail(c, AT3HIP_ENOMEM, "malloc");
-    for (size_t i = 0; i < S; ++i) init[i] = 0.006f;  // LoudFactor, atrac3denc.h:115-116
-    hipError_t e = hipMemcpyAsync(c->d_loud_state, init, S * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    free(init);
-    if (e != hipSuccess) return fail(c, AT3HIP_EDEVICE, "state upload", e);
+    const int rc = at3host::fill_and_wait(c, c->d_loud_state, S, 0.006f);   // LoudFactor, atrac3denc.h:115-116
+    if (rc != AT3HIP_OK) return rc;
     c->blocks_fed = 0;
     c->hist_cur = 0;
     return AT3HIP_OK;
+}
+
+// Every event the context owns, in the order at3hip_create makes them: f(event, creation flags) until one returns false.
+template <typename F>
+bool for_each_event(at3hip_ctx* c, F f)
+{
+    const unsigned untimed = hipEventDisableTiming;
+    for (int q = 0; q < 2; ++q)
+        if (!f(c->ev_h2d[q], untimed) || !f(c->pcm_free[q].ev, untimed)) return false;
+    for (auto& row : c->ev)
+        for (auto& e : row)
+            if (!f(e, 0u)) return false;
+    if (!f(c->front_done.ev, untimed)) return false;
+    for (int q = 0; q < at3hip_ctx::kSlots; ++q)
+        if (!f(c->ev_heavy_done[q], untimed) || !f(c->ev_mdct_done[q], untimed)) return false;
+    for (int q = 0; q < at3hip_ctx::kHostRing; ++q)
+        if (!f(c->host_in[q].ev, untimed) || !f(c->host_out[q].ev, untimed)) return false;
+    for (auto& e : c->ev_mid_done)
+        if (!f(e, untimed)) return false;
+    return true;
 }
 
 }  // namespace
@@ -350,120 +375,78 @@ int at3hip_create(const at3hip_config* cfg, at3hip_ctx** out)
         return AT3HIP_EINVAL;
     // the largest grid is one workgroup per (stream, frame, channel, band < 3); gridDim.x is a 31-bit quantity
     if ((long long)cfg->n_streams * cfg->max_blocks * 6 > 0x7fffffffLL) return AT3HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return AT3HIP_EDEVICE;
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return AT3HIP_EINVAL;
-    at3hip_ctx* c = new (std::nothrow) at3hip_ctx();
-    if (!c) return AT3HIP_ENOMEM;
-    c->cfg = *cfg;
-    c->device = cfg->device_id;
-    const uint32_t br = cfg->bitrate == 0 ? 132300u : (uint32_t)cfg->bitrate;
-    int idx = 0;
-    while (idx < 7 && kContainer[idx].bitrate < br) ++idx;  // lower_bound, atrac3.cpp:47-53
-    c->frame_sz = kContainer[idx].frame_sz;
-    c->js = kContainer[idx].js;
-
-    int rc = AT3HIP_OK;
-    auto bail = [&](int code) {
-        at3hip_destroy(c);
-        return code;
-    };
-    at3host::DeviceGuard guard(c->device);
-    if (guard.error() != hipSuccess) return bail(AT3HIP_EDEVICE);
-    {
-        // The back half's stream gets the higher priority: its rate loop is the longest kernel of a call and fills every CU's
-        // LDS, so a front-half workgroup placed between two of its rounds only delays it, while the front-half kernels of the
-        // NEXT call have a whole rate loop's time to spare (measured with the three streams: back high / front low beats
-        // the opposite by 0.7 % on white noise, 3-4 % on `tones` and LP4, 6.5 % on `burst`; equal priorities sit between).
-        int prio_lo = 0, prio_hi = 0;
+    // The back half's stream gets the higher priority: its rate loop is the longest kernel of a call and fills every CU's
+    // LDS, so a front-half workgroup placed between two of its rounds only delays it, while the front-half kernels of the
+    // NEXT call have a whole rate loop's time to spare (measured with the three streams: back high / front low beats
+    // the opposite by 0.7 % on white noise, 3-4 % on `tones` and LP4, 6.5 % on `burst`; equal priorities sit between).
+    int prio_lo = 0, prio_hi = 0;
+    auto make_front_stream = [&](hipStream_t* own) {
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);   // lo = numerically greatest = lowest priority
-        if (hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, prio_lo) != hipSuccess) return bail(AT3HIP_EDEVICE);
-        if (hipStreamCreateWithPriority(&c->back_stream, hipStreamNonBlocking, prio_hi) != hipSuccess) return bail(AT3HIP_EDEVICE);
+        return hipStreamCreateWithPriority(own, hipStreamNonBlocking, prio_lo);
+    };
+    auto setup = [&](at3hip_ctx* c) {
+        c->cfg = *cfg;
+        const uint32_t br = cfg->bitrate == 0 ? 132300u : (uint32_t)cfg->bitrate;
+        int idx = 0;
+        while (idx < 7 && kContainer[idx].bitrate < br) ++idx;  // lower_bound, atrac3.cpp:47-53
+        c->frame_sz = kContainer[idx].frame_sz;
+        c->js = kContainer[idx].js;
+
+        // All streams are made before any event, table or buffer, in this order.
+        if (hipStreamCreateWithPriority(&c->back_stream, hipStreamNonBlocking, prio_hi) != hipSuccess) return AT3HIP_EDEVICE;
         // The light front stage (curve context, curves, energy scales, MDCT) sits on the step's critical path - the next rate
         // loop waits for its spectra - while the heavy stage it shares the chip with (the NEXT step's spectra and envelopes,
         // whose workgroups fill the LDS) has a whole rate loop of slack: high priority lets its short kernels take the
         // slots the heavy stage's workgroups free (+3 % on the step; a middle priority does nothing).
-        if (!cfg->no_gain_control && hipStreamCreateWithPriority(&c->mid_stream, hipStreamNonBlocking, prio_hi) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    }
-    // (Round 6 tried creating the copy stream only at the first call that copies from host memory - one claim less on the runtime's few hardware queues for
-    // contexts fed from device memory. Created that late it shares a hardware queue with one of the kernel streams and the host-fed pipeline halves:
-    // 12.4 -> 6.3 M frames/s with 16-bit samples. It is created here, right behind the kernel streams.)
-    if (hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    for (int q = 0; q < 2; ++q)
-        if (hipEventCreateWithFlags(&c->ev_h2d[q], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_pcm_free[q], hipEventDisableTiming) != hipSuccess)
-            return bail(AT3HIP_EDEVICE);
-    c->stream = c->own_stream;
-    for (auto& row : c->ev)
-        for (auto& e : row)
-            if (hipEventCreate(&e) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    if (hipEventCreateWithFlags(&c->ev_front_done, hipEventDisableTiming) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    for (int q = 0; q < at3hip_ctx::kSlots; ++q)
-        if (hipEventCreateWithFlags(&c->ev_heavy_done[q], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_mdct_done[q], hipEventDisableTiming) != hipSuccess)
-            return bail(AT3HIP_EDEVICE);
-    for (int q = 0; q < at3hip_ctx::kHostRing; ++q)
-        if (hipEventCreateWithFlags(&c->ev_host_in[q], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_host_out[q], hipEventDisableTiming) != hipSuccess)
-            return bail(AT3HIP_EDEVICE);
-    for (auto& e : c->ev_mid_done)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return bail(AT3HIP_EDEVICE);
+        if (!cfg->no_gain_control && hipStreamCreateWithPriority(&c->mid_stream, hipStreamNonBlocking, prio_hi) != hipSuccess) return AT3HIP_EDEVICE;
+        // (Round 6 tried creating the copy stream only at the first call that copies from host memory - one claim less on the runtime's few hardware queues for
+        // contexts fed from device memory. Created that late it shares a hardware queue with one of the kernel streams and the host-fed pipeline halves:
+        // 12.4 -> 6.3 M frames/s with 16-bit samples. It is created here, right behind the kernel streams.)
+        if (hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking) != hipSuccess) return AT3HIP_EDEVICE;
+        if (!for_each_event(c, [](hipEvent_t& e, unsigned flags) { return (flags ? hipEventCreateWithFlags(&e, flags) : hipEventCreate(&e)) == hipSuccess; }))
+            return AT3HIP_EDEVICE;
 
-    const size_t S = cfg->n_streams, B = cfg->max_blocks;
-    Tables* host_tables = new (std::nothrow) Tables();
-    if (!host_tables) return bail(AT3HIP_ENOMEM);
-    build_tables(host_tables);
-    rc = dev_alloc(c, &c->d_tables, 1);
-    if (rc == AT3HIP_OK) {
-        // From pageable memory a blocking copy may return once the data is STAGED: the transfer itself then still runs on the null stream, which the
-        // context's non-blocking streams do not wait for. Seen with eight processes on one device: the first call of a fresh process summed its
-        // loudness with a curve that had not arrived yet (TrackLoudness state in the millions, silent frames until the stream was reset) - the
-        // device is drained here, once, before anything can read the tables.
-        hipError_t e = hipMemcpy(c->d_tables, host_tables, sizeof(Tables), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) rc = AT3HIP_EDEVICE;
-    }
-    delete host_tables;
-    if (rc != AT3HIP_OK) return bail(rc);
+        const size_t S = cfg->n_streams, B = cfg->max_blocks;
+        int rc = at3host::make_device_tables(c, &c->d_tables, [](Tables* t) { build_tables(t); return true; });
+        if (rc != AT3HIP_OK) return rc;
 
-    if (cfg->channels == 1 && (rc = dev_alloc(c, &c->d_pcm_in, S * B * 2048)) != AT3HIP_OK) return bail(rc);
-    // (the host-PCM staging pair is allocated by the first call that hands over host memory)
-    if ((rc = dev_alloc(c, &c->d_hist[0], S * kHist * 2)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_hist[1], S * kHist * 2)) != AT3HIP_OK) return bail(rc);
-    // subbands go through HBM when gain control analyses them, and for joint stereo (the M/S matrixing needs both channels'
-    // subbands, which the one-channel wavefronts of the fused kernel do not have)
-    if (!cfg->no_gain_control || c->js) {
-        if ((rc = dev_alloc(c, &c->d_sub, S * 8 * (B + 2) * 256)) != AT3HIP_OK) return bail(rc);
-        if ((rc = dev_alloc(c, &c->d_sub_tail, S * 8 * 512)) != AT3HIP_OK) return bail(rc);
-    }
-    if (!cfg->no_gain_control) {
-        if ((rc = dev_alloc(c, &c->d_rec, S * B * 6)) != AT3HIP_OK) return bail(rc);
-        c->d_rec_b[0] = c->d_rec;
-        c->d_sub_b[0] = c->d_sub;
-        if ((rc = dev_alloc(c, &c->d_rec_b[1], S * B * 6)) != AT3HIP_OK) return bail(rc);
-        if ((rc = dev_alloc(c, &c->d_sub_b[1], S * 8 * (B + 2) * 256)) != AT3HIP_OK) return bail(rc);
-        if ((rc = dev_alloc(c, &c->d_bins, S * B * 6 * kGainBins)) != AT3HIP_OK) return bail(rc);
-        for (int q = 0; q < 2; ++q)
-            if ((rc = dev_alloc(c, &c->d_ges[q], S * B * 8)) != AT3HIP_OK) return bail(rc);
-    }
-    if ((rc = dev_alloc(c, &c->d_state, S * 8)) != AT3HIP_OK) return bail(rc);
-    for (int q = 0; q < 2; ++q) {
-        if ((rc = dev_alloc(c, &c->d_curves[q], S * B * 8)) != AT3HIP_OK) return bail(rc);
-        if ((rc = dev_alloc(c, &c->d_specs[q], S * B * 2048)) != AT3HIP_OK) return bail(rc);
-    }
-    if ((rc = dev_alloc(c, &c->d_psy, S * B * 2)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_loud, S * B)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_loud_state, S)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_out, S * B * (size_t)c->frame_sz)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_clk, kClkWords)) != AT3HIP_OK) return bail(rc);
-    if (hipMemsetAsync(c->d_clk, 0, kClkWords * sizeof(unsigned long long), c->stream) != hipSuccess) return bail(AT3HIP_EDEVICE);   // (reset_state below waits for the stream)
-    if ((rc = dev_alloc(c, &c->d_counters, 2)) != AT3HIP_OK) return bail(rc);   // (zeroed by reset_state)
-    if ((rc = reset_state(c)) != AT3HIP_OK) return bail(rc);
-    hipDeviceProp_t prop;
-    const bool have_prop = hipGetDeviceProperties(&prop, c->device) == hipSuccess;
-    c->n_cus = (have_prop && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    c->lds_per_cu = have_prop ? (size_t)prop.maxSharedMemoryPerMultiProcessor : 0;
-    {
+        if (cfg->channels == 1 && (rc = dev_alloc(c, &c->d_pcm_in, S * B * 2048)) != AT3HIP_OK) return rc;
+        // (the host-PCM staging pair is allocated by the first call that hands over host memory)
+        if ((rc = dev_alloc(c, &c->d_hist[0], S * kHist * 2)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_hist[1], S * kHist * 2)) != AT3HIP_OK) return rc;
+        // subbands go through HBM when gain control analyses them, and for joint stereo (the M/S matrixing needs both channels'
+        // subbands, which the one-channel wavefronts of the fused kernel do not have)
+        if (!cfg->no_gain_control || c->js) {
+            if ((rc = dev_alloc(c, &c->d_sub, S * 8 * (B + 2) * 256)) != AT3HIP_OK) return rc;
+            if ((rc = dev_alloc(c, &c->d_sub_tail, S * 8 * 512)) != AT3HIP_OK) return rc;
+        }
+        if (!cfg->no_gain_control) {
+            if ((rc = dev_alloc(c, &c->d_rec, S * B * 6)) != AT3HIP_OK) return rc;
+            c->d_rec_b[0] = c->d_rec;
+            c->d_sub_b[0] = c->d_sub;
+            if ((rc = dev_alloc(c, &c->d_rec_b[1], S * B * 6)) != AT3HIP_OK) return rc;
+            if ((rc = dev_alloc(c, &c->d_sub_b[1], S * 8 * (B + 2) * 256)) != AT3HIP_OK) return rc;
+            if ((rc = dev_alloc(c, &c->d_bins, S * B * 6 * kGainBins)) != AT3HIP_OK) return rc;
+            for (int q = 0; q < 2; ++q)
+                if ((rc = dev_alloc(c, &c->d_ges[q], S * B * 8)) != AT3HIP_OK) return rc;
+        }
+        if ((rc = dev_alloc(c, &c->d_state, S * 8)) != AT3HIP_OK) return rc;
+        for (int q = 0; q < 2; ++q) {
+            if ((rc = dev_alloc(c, &c->d_curves[q], S * B * 8)) != AT3HIP_OK) return rc;
+            if ((rc = dev_alloc(c, &c->d_specs[q], S * B * 2048)) != AT3HIP_OK) return rc;
+        }
+        if ((rc = dev_alloc(c, &c->d_psy, S * B * 2)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_loud, S * B)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_loud_state, S)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_out, S * B * (size_t)c->frame_sz)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_clk, kClkWords)) != AT3HIP_OK) return rc;
+        if (hipMemsetAsync(c->d_clk, 0, kClkWords * sizeof(unsigned long long), c->stream) != hipSuccess) return AT3HIP_EDEVICE;   // (reset_state below waits for the stream)
+        if ((rc = dev_alloc(c, &c->d_counters, 2)) != AT3HIP_OK) return rc;   // (zeroed by reset_state)
+        if ((rc = reset_state(c)) != AT3HIP_OK) return rc;
+        hipDeviceProp_t prop;
+        const bool have_prop = hipGetDeviceProperties(&prop, c->device) == hipSuccess;
+        c->n_cus = (have_prop && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+        c->lds_per_cu = have_prop ? (size_t)prop.maxSharedMemoryPerMultiProcessor : 0;
         int nb = 0;
         const bool gain = !c->cfg.no_gain_control;
         const hipError_t e = (gain || c->js) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_qmf_sub8, 256, 0)
@@ -473,60 +456,37 @@ int at3hip_create(const at3hip_config* cfg, at3hip_ctx** out)
         nb = 0;
         c->wgs_per_cu_mdct = ((c->js ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_mdct_sub<true, 4>), 256, 0)
                                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_mdct_sub<false, 4>), 256, 0)) == hipSuccess && nb > 0) ? nb : 3;   // (wavefronts per SIMD, pick_runs' unit: the same three for the three-wavefront form, four workgroups per CU)
-    }
-    *out = c;
-    return AT3HIP_OK;
+        return AT3HIP_OK;
+    };
+    return at3host::create_engine(cfg->device_id, out, at3hip_destroy, setup, make_front_stream);
 }
 
 void at3hip_destroy(at3hip_ctx* c)
 {
     if (!c) return;
-    at3host::DeviceGuard guard(c->device);
-    // only the context's own streams are waited for: a caller-owned stream (at3hip_set_stream) may already be gone. What
-    // the last call queued there (the carried-state update writes buffers freed below) is covered by an event, which
-    // outlives the stream
-    if (c->front_done_valid) (void)hipEventSynchronize(c->ev_front_done);
-    if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    if (c->mid_stream) (void)hipStreamSynchronize(c->mid_stream);
-    if (c->back_stream) (void)hipStreamSynchronize(c->back_stream);
-    if (c->d_rec_b[1]) (void)hipFree(c->d_rec_b[1]);
-    if (c->d_sub_b[1]) (void)hipFree(c->d_sub_b[1]);
-    void* bufs[] = {c->d_tables,    c->d_pcm_in,    c->d_hist[0],  c->d_hist[1],  c->d_sub,    c->d_rec,    c->d_state, c->d_curves[0],
-                    c->d_curves[1], c->d_specs[0],  c->d_specs[1], c->d_ges[0],   c->d_ges[1], c->d_psy,    c->d_loud,  c->d_loud_state,
-                    c->d_out,       c->d_quant,     c->d_stage,    c->d_sub_tail, c->d_bins,     c->d_clk,      c->d_counters};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (auto& row : c->ev)
-        for (auto& e : row)
-            if (e) (void)hipEventDestroy(e);
-    if (c->h2d_stream) (void)hipStreamSynchronize(c->h2d_stream);
-    for (int q = 0; q < 2; ++q) {
-        if (c->d_pcm_in_b[q]) (void)hipFree(c->d_pcm_in_b[q]);
-        if (c->d_s16_b[q]) (void)hipFree(c->d_s16_b[q]);
-        if (c->ev_h2d[q]) (void)hipEventDestroy(c->ev_h2d[q]);
-        if (c->ev_pcm_free[q]) (void)hipEventDestroy(c->ev_pcm_free[q]);
+    {
+        // only the context's own streams are waited for: a caller-owned stream (at3hip_set_stream) may already be gone. What
+        // the last call queued there (the carried-state update writes buffers freed below) is covered by an event, which
+        // outlives the stream
+        at3host::DeviceGuard guard(c->device);
+        (void)c->front_done.host_wait();
     }
-    if (c->h2d_stream) (void)hipStreamDestroy(c->h2d_stream);
-    if (c->ev_front_done) (void)hipEventDestroy(c->ev_front_done);
-    for (auto& e : c->ev_heavy_done)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_mdct_done)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_host_in)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_host_out)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_mid_done)
-        if (e) (void)hipEventDestroy(e);
-    if (c->mid_stream) (void)hipStreamDestroy(c->mid_stream);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    if (c->back_stream) (void)hipStreamDestroy(c->back_stream);
-    delete c;
+    c->stream = c->own_stream;   // (destroy_engine waits for `stream`: it must not be the caller's any more)
+    at3host::destroy_engine(c, {c->d_tables,    c->d_pcm_in,    c->d_hist[0],    c->d_hist[1],    c->d_sub,       c->d_sub_b[1], c->d_rec,   c->d_rec_b[1],
+                                c->d_state,     c->d_curves[0], c->d_curves[1],  c->d_specs[0],   c->d_specs[1],  c->d_ges[0],   c->d_ges[1], c->d_psy,
+                                c->d_loud,      c->d_loud_state, c->d_out,       c->d_quant,      c->d_stage,     c->d_sub_tail, c->d_bins,  c->d_clk,
+                                c->d_counters,  c->d_pcm_in_b[0], c->d_pcm_in_b[1], c->d_s16_b[0], c->d_s16_b[1]},
+                            {c->mid_stream, c->back_stream, c->h2d_stream}, [c] {
+                                for_each_event(c, [](hipEvent_t& e, unsigned) {
+                                    if (e) (void)hipEventDestroy(e);
+                                    return true;
+                                });
+                            });
 }
 
 int at3hip_frame_size(const at3hip_ctx* c) { return c ? c->frame_sz : AT3HIP_EINVAL; }
 int at3hip_joint_stereo(const at3hip_ctx* c) { return c ? c->js : AT3HIP_EINVAL; }
-const char* at3hip_last_error(const at3hip_ctx* c) { return c ? c->err : "null context"; }
+const char* at3hip_last_error(const at3hip_ctx* c) { return at3host::engine_last_error(c); }
 
 int at3hip_set_stream(at3hip_ctx* c, void* hip_stream)
 {
@@ -594,7 +554,7 @@ int at3hip_wait_input(at3hip_ctx* c, int32_t ago)
     at3host::DeviceGuard guard(c->device);
     HIPCHK(c, guard.error());
     const int q = (int)((c->enc_calls - 1 - ago) % at3hip_ctx::kHostRing);
-    if (c->host_in_valid[q]) HIPCHK(c, hipEventSynchronize(c->ev_host_in[q]));
+    HIPCHK(c, c->host_in[q].host_wait());
     return AT3HIP_OK;
 }
 
@@ -604,7 +564,7 @@ int at3hip_wait_frames(at3hip_ctx* c, int32_t ago)
     at3host::DeviceGuard guard(c->device);
     HIPCHK(c, guard.error());
     const int q = (int)((c->enc_calls - 1 - ago) % at3hip_ctx::kHostRing);
-    if (c->host_out_valid[q]) HIPCHK(c, hipEventSynchronize(c->ev_host_out[q]));
+    HIPCHK(c, c->host_out[q].host_wait());
     return AT3HIP_OK;
 }
 
@@ -700,294 +660,375 @@ int at3hip_encode_s16(at3hip_ctx* c, const int16_t* pcm, int32_t n_blocks, uint8
 
 namespace {
 
-int encode_impl(at3hip_ctx* c, const void* pcm_any, bool s16, int32_t n_blocks, uint8_t* out_frames, int32_t* n_frames_out, uint32_t flags)
-{
-    const float* pcm = (const float*)pcm_any;   // (float samples unless s16)
-    if (!c || !pcm_any || n_blocks < 1 || n_blocks > c->cfg.max_blocks) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    const int S = c->cfg.n_streams;
-    const int f0 = (c->blocks_fed == 0) ? 1 : 0;
-    const int n_out = n_blocks - f0;
-    if (n_out > 0 && !out_frames) return fail(c, AT3HIP_EINVAL, "out_frames is null");
-    // k_s16_to_f32 reads the caller's device pointer sixteen bytes at a time
-    if (s16 && (flags & AT3HIP_PCM_ON_DEVICE) && ((uintptr_t)pcm_any & 15u) != 0) return fail(c, AT3HIP_EINVAL, "16-bit device PCM must be 16-byte aligned");
-    hipStream_t st = c->stream;
-    const bool gain = !c->cfg.no_gain_control;
+// What one at3hip_encode / at3hip_encode_s16 call works with: its geometry, its places in the context's rings, its streams and
+// the buffers of its parity.
+struct EncodeCall {
+    int n_blocks, f0, n_out;   // blocks given; 1 when the stream starts with this call (its first block only primes the look-ahead); frames produced
+    uint32_t flags;
+    int par, slot, hq;         // call parity (the double buffers), slot in the timing history, slot in the host-visible event ring
+    bool gain, split;          // gain control; QMF and MDCT as two kernels with the subbands in HBM between them (gain control or joint stereo)
+    bool staged;               // the call's float samples live in this parity's staging buffer
+    bool timed;                // the call records its stage timestamps
+    hipStream_t st, md, bk;    // the heavy front stage, the light one (see at3hip_ctx::mid_stream; without gain control md == st), the back half
+    hipEvent_t* ev;            // the slot's eight stage timestamps
+    const float* d_pcm;        // the samples in device memory as pairs, [S][n_blocks][1024][2]
+    const float* hist;         // the PCM history in front of them
+    float* hist_next;          // and where the carried-state update leaves the next call's
+    float* d_sub;              // the parity's buffers
+    GainRec* d_rec;
+    Curve* d_curves;
+    float* d_specs;
+    float* d_ges;
+    uint8_t* d_out;            // the frames: the caller's device memory, or the staging of host output
+};
 
-    const int par = (int)(c->enc_calls & 1);
-    const float* d_pcm = pcm;
-    const size_t n_in = (size_t)S * n_blocks * 1024 * c->cfg.channels;
+// PCM staging: host samples through the copy stream into the parity's staging, 16-bit samples to floats, one channel to pairs.
+// Leaves k.d_pcm.
+int stage_pcm(at3hip_ctx* c, EncodeCall& k, const void* pcm_any, bool s16)
+{
+    const int S = c->cfg.n_streams, par = k.par;
+    const float* pcm = (const float*)pcm_any;   // (float samples unless s16)
+    const size_t n_in = (size_t)S * k.n_blocks * 1024 * c->cfg.channels;
+    const size_t n_max = (size_t)S * c->cfg.max_blocks * 1024 * c->cfg.channels;
     const float* d_staged = pcm;   // the call's PCM in device memory, [S][n_blocks][1024][channels]
-    const int hq = (int)(c->enc_calls % at3hip_ctx::kHostRing);   // this call's slot in the host-visible event ring
-    bool host_in_recorded = false, host_out_recorded = false;
-    const bool staged = s16 || !(flags & AT3HIP_PCM_ON_DEVICE);   // the call's float samples live in this parity's staging buffer
-    if (staged && !c->d_pcm_in_b[par]) {
-        const int rc = dev_alloc(c, &c->d_pcm_in_b[par], (size_t)S * c->cfg.max_blocks * 1024 * c->cfg.channels);
+    if (k.staged && !c->d_pcm_in_b[par]) {
+        const int rc = dev_alloc(c, &c->d_pcm_in_b[par], n_max);
         if (rc != AT3HIP_OK) return rc;
     }
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
+    if (!(k.flags & AT3HIP_PCM_ON_DEVICE)) {
         // host memory: the copy runs on its own stream into this parity's staging buffer - beside the previous call's
         // kernels when the memory is pinned - and the front half waits for its arrival. 16-bit samples cross the bus as they
         // are (half the bytes: the host-fed rate is bound by them) and become floats on the device, on the same stream.
         if (s16 && !c->d_s16_b[par]) {
-            const int rc = dev_alloc(c, &c->d_s16_b[par], (size_t)S * c->cfg.max_blocks * 1024 * c->cfg.channels);
+            const int rc = dev_alloc(c, &c->d_s16_b[par], n_max);
             if (rc != AT3HIP_OK) return rc;
         }
-        if (c->pcm_free_valid[par]) HIPCHK(c, hipStreamWaitEvent(c->h2d_stream, c->ev_pcm_free[par], 0));
+        HIPCHK(c, c->pcm_free[par].make_wait(c->h2d_stream));
         if (s16) HIPCHK(c, hipMemcpyAsync(c->d_s16_b[par], pcm_any, n_in * sizeof(int16_t), hipMemcpyHostToDevice, c->h2d_stream));
         else HIPCHK(c, hipMemcpyAsync(c->d_pcm_in_b[par], pcm, n_in * sizeof(float), hipMemcpyHostToDevice, c->h2d_stream));
         HIPCHK(c, hipEventRecord(c->ev_h2d[par], c->h2d_stream));
-        c->h2d_valid[par] = true;
-        HIPCHK(c, hipEventRecord(c->ev_host_in[hq], c->h2d_stream));
-        host_in_recorded = true;
-        HIPCHK(c, hipStreamWaitEvent(st, c->ev_h2d[par], 0));
+        HIPCHK(c, c->host_in[k.hq].record(c->h2d_stream));
+        HIPCHK(c, hipStreamWaitEvent(k.st, c->ev_h2d[par], 0));
         // (the conversion runs on the front stream, not behind the copy: the copy stream carries nothing but copies, back to back)
-        if (s16) hipLaunchKernelGGL(k_s16_to_f32, dim3((unsigned)((n_in / 8 + 255) / 256)), dim3(256), 0, st, c->d_s16_b[par], c->d_pcm_in_b[par], n_in / 8);
+        if (s16) hipLaunchKernelGGL(k_s16_to_f32, dim3((unsigned)((n_in / 8 + 255) / 256)), dim3(256), 0, k.st, c->d_s16_b[par], c->d_pcm_in_b[par], n_in / 8);
         d_staged = c->d_pcm_in_b[par];
     } else if (s16) {
         // 16-bit samples already in HBM: converted on the front stream (which also carries everything that reads the staging)
-        hipLaunchKernelGGL(k_s16_to_f32, dim3((unsigned)((n_in / 8 + 255) / 256)), dim3(256), 0, st, (const int16_t*)pcm_any, c->d_pcm_in_b[par], n_in / 8);
+        hipLaunchKernelGGL(k_s16_to_f32, dim3((unsigned)((n_in / 8 + 255) / 256)), dim3(256), 0, k.st, (const int16_t*)pcm_any, c->d_pcm_in_b[par], n_in / 8);
         d_staged = c->d_pcm_in_b[par];
     }
-    d_pcm = d_staged;
+    k.d_pcm = d_staged;
     if (c->cfg.channels == 1) {
         // "No mono mode for atrac3, just make duplicate of first channel" (atrac3_bitstream.cpp:836-843): the one-channel
         // frame is two identical sound units, i.e. the discrete-stereo frame of L = R (TrackLoudness' 0.02 l equals
         // 0.01 (l + l) exactly). The samples are duplicated in HBM and the stereo pipeline runs unchanged.
         // Joint-stereo containers: M = (x + x) / 2 = x exactly, so the M unit is the mono unit (gain analysis, loudness
         // with 0.02 l and all); the rate/pack kernel replaces the S unit by the empty element of atrac3denc.cpp:843-849.
-        const size_t n = (size_t)S * n_blocks * 1024;
-        hipLaunchKernelGGL(k_mono_to_pairs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_staged, c->d_pcm_in, n);
-        d_pcm = c->d_pcm_in;
-    }
-    uint8_t* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? out_frames : c->d_out;
-    const float* hist = c->d_hist[c->hist_cur];
-    float* hist_next = c->d_hist[c->hist_cur ^ 1];
-    hipStream_t bk = c->back_stream;
-    const int slot = (int)(c->enc_calls % at3hip_ctx::kSlots);
-    hipEvent_t* ev = c->ev[slot];
-    Curve* d_curves = c->d_curves[par];
-    float* d_specs = c->d_specs[par];
-    float* d_ges = c->d_ges[par];
-    c->slot_has_frames[slot] = false;
-    // The timing events sit between the kernels of the three streams; at 4096 frames a step recording all eight takes 3.3 % longer than one recording none
-    // (EXPERIMENTS.md, round 6), so a caller that only samples the stage timings asks for every Nth call.
-    const bool timed = n_out > 0 && c->timing_every > 0 && (c->timing_tick++ % (unsigned)c->timing_every) == 0;
-    c->slot_timed[slot] = timed;
-    auto launch_state = [&](hipStream_t on, int parts) {
-        StateParams sp;
-        sp.pcm = d_pcm;
-        sp.hist_in = hist;
-        sp.hist_out = hist_next;
-        sp.curves = c->d_curves[par];
-        sp.state = c->d_state;
-        sp.sub = (gain || c->js) ? (gain ? c->d_sub_b[par] : c->d_sub) : nullptr;
-        sp.sub_tail = c->d_sub_tail;
-        sp.n_blocks = n_blocks;
-        sp.n_streams = S;
-        sp.parts = parts;
-        hipLaunchKernelGGL(k_state_update, dim3((unsigned)(((kHist + 255) / 256) * S)), dim3(256), 0, on, sp);
-    };
-
-    // With gain control: `st` carries the heavy stage, `md` the light one (see at3hip_ctx::mid_stream); otherwise md == st.
-    hipStream_t md = gain ? c->mid_stream : st;
-    float* d_sub = gain ? c->d_sub_b[par] : c->d_sub;
-    GainRec* d_rec = gain ? c->d_rec_b[par] : c->d_rec;
-    // the light stage of the call before the previous one must be done with this parity's subbands and gain records
-    if (gain && c->mid_done_valid[par]) HIPCHK(c, hipStreamWaitEvent(st, c->mid_done_of[par], 0));
-    if (timed) HIPCHK(c, hipEventRecord(ev[0], st));
-    // the back half of the call before the previous one must be done with this parity's spectra / curves / scales
-    if (c->back_done_valid[par]) HIPCHK(c, hipStreamWaitEvent(md, c->ev_back_done[par], 0));
-    HIPCHK(c, hipMemsetAsync(d_curves, 0, (size_t)S * n_blocks * 8 * sizeof(Curve), md));
-    if (n_out == 0 && (gain || c->js)) {
-        // a call that only primes the look-ahead still has to leave its subbands behind for the next call's look-back
-        FrontParams fp = {};
-        fp.pcm = d_pcm;
-        fp.hist = hist;
-        fp.sub = d_sub;
-        fp.sub_tail = c->d_sub_tail;
-        fp.n_blocks = n_blocks;
-        fp.f0 = f0;
-        fp.js = c->js;
-        fp.sub_runs = pick_runs(c, n_blocks, c->wgs_per_cu, 0.35, 4);
-        const int n_waves = S * 2 * fp.sub_runs;
-        hipLaunchKernelGGL(k_qmf_sub8, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, st, fp, c->d_tables, n_waves);
-    }
-    if (n_out > 0) {
-        FrontParams fp;
-        fp.pcm = d_pcm;
-        fp.hist = hist;
-        fp.curves = d_curves;
-        fp.state = c->d_state;
-        fp.specs = d_specs;
-        fp.ges = d_ges;
-        fp.sub = d_sub;
-        fp.sub_tail = c->d_sub_tail;
-        fp.n_blocks = n_blocks;
-        fp.f0 = f0;
-        const bool split = gain || c->js;   // QMF and MDCT as two kernels with the subbands in HBM between them
-        {
-            const FusedCut cut = split ? FusedCut{0, 0} : pick_fused(c, n_out);
-            fp.frame_runs = cut.runs;
-            fp.chain = cut.chain;
-        }
-        fp.sub_runs = 0;
-        fp.js = c->js;
-        auto launch_qmf_sub = [&] {
-            fp.sub_runs = pick_runs(c, n_blocks, c->wgs_per_cu, 0.35, 4);
-            const int n_waves = S * 2 * fp.sub_runs;   // one wavefront per (stream, channel, run)
-            hipLaunchKernelGGL(k_qmf_sub8, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, st, fp, c->d_tables, n_waves);
-        };
-        if (gain) {
-            GainParams gp;
-            gp.sub = d_sub;
-            gp.rec = d_rec;
-            gp.bins = c->d_bins;
-            gp.state = c->d_state;
-            gp.curves = d_curves;
-            gp.n_blocks = n_blocks;
-            gp.f0 = f0;
-            gp.js = c->js;
-            gp.n_streams = S;
-            gp.literal = c->flat_literal;
-            launch_qmf_sub();
-            if (timed) HIPCHK(c, hipEventRecord(ev[1], st));
-            // PCM history and subband tail: the next call's heavy stage needs nothing else from this one. (Round 6: moved behind the gain analysis - off the
-            // chain QMF -> spectra -> analysis - it cost the step 8 %: the next call's QMF kernel follows it on this stream and then misses the window
-            // between the analysis and the next rate loop in which it gets its only undisturbed microseconds. EXPERIMENTS.md.)
-            launch_state(st, 1);
-            {
-                const long long spec_wgs = (long long)S * ((n_out + 3) / 4) * 6;   // (four consecutive frames of one (stream, channel, band) per wavefront)
-                hipLaunchKernelGGL(k_gain_spec, dim3((unsigned)spec_wgs), dim3(64), spec_lds_pad(c, spec_wgs), st, gp, c->d_tables, S * n_out * 6);
-            }
-            // default: the two-wavefront form. The one-wavefront form is 11 % faster alone (89 against 101 us at 4096 frames) and
-            // leaves the pipelined step 2 % slower at that size, equal at the 1024 x 128 shard (profiles/EXPERIMENTS.md)
-            if (c->gain_form != AT3HIP_GAIN_FORM_ONE_WAVE) hipLaunchKernelGGL(k_gain_analysis, dim3(S * n_out * 6), dim3(128), analysis_lds_pad(c, (long long)S * n_out * 6), st, gp, c->d_tables);
-            else hipLaunchKernelGGL(k_gain_analysis1, dim3(S * n_out * 6), dim3(64), analysis1_lds_pad(c, (long long)S * n_out * 6), st, gp, c->d_tables);   // one wavefront per item
-            if (timed) HIPCHK(c, hipEventRecord(ev[2], st));
-            HIPCHK(c, hipEventRecord(c->ev_heavy_done[slot], st));
-            HIPCHK(c, hipStreamWaitEvent(md, c->ev_heavy_done[slot], 0));   // the light stage starts when this call's heavy stage is done
-            hipLaunchKernelGGL(k_gain_tail, dim3((unsigned)((S * n_out * 6 + 7) / 8)), dim3(256), 0, md, gp, S * n_out * 6);
-            hipLaunchKernelGGL(k_gain_scan, dim3(S * 6), dim3(64), 0, md, gp, S);
-            hipLaunchKernelGGL(k_gain_curve, dim3((S * n_out * 6 + 7) / 8), dim3(256), 0, md, gp, c->d_tables, S);
-            hipLaunchKernelGGL(k_gain_energy_scale, dim3(S * n_out), dim3(64), 0, md, fp, c->d_tables, S * n_out);
-        } else {
-            if (split) launch_qmf_sub();   // joint stereo without gain control: the QMF kernel, timed as qmf_ms
-            if (timed) HIPCHK(c, hipEventRecord(ev[1], st));
-            if (timed) HIPCHK(c, hipEventRecord(ev[2], st));
-        }
-        if (timed) HIPCHK(c, hipEventRecord(ev[3], md));
-        if (split) {
-            // the subbands are in HBM (k_qmf_sub8 wrote them: for the gain analysis, or for the M/S matrixing)
-            MdctSubParams mp;
-            mp.sub = d_sub;
-            mp.curves = gain ? d_curves : nullptr;
-            mp.state = c->d_state;
-            mp.specs = d_specs;
-            mp.n_blocks = n_blocks;
-            mp.f0 = f0;
-            mp.js = c->js;
-            mp.frame_runs = pick_runs(c, n_out, c->wgs_per_cu_mdct, 0.3);
-            mp.n_waves = S * 2 * mp.frame_runs;
-            // three wavefronts per workgroup (20.3 KB) where k_gain_analysis' launch is padded to fat slots - a light-stage workgroup must fit the slot
-            // one retiring analysis workgroup frees (analysis_lds_pad) -, four (25.5 KB; one table copy per four runs) where it fills the chip unpadded
-            const bool fat_slots = c->gain_form != AT3HIP_GAIN_FORM_ONE_WAVE && analysis_lds_pad(c, (long long)S * n_out * 6) != 0;   // (the one-wavefront form's launch has no fat slots)
-            if (fat_slots) {
-                if (c->js) hipLaunchKernelGGL((k_mdct_sub<true, 3>), dim3((unsigned)((mp.n_waves + 2) / 3)), dim3(192), 0, md, mp, c->d_tables);
-                else hipLaunchKernelGGL((k_mdct_sub<false, 3>), dim3((unsigned)((mp.n_waves + 2) / 3)), dim3(192), 0, md, mp, c->d_tables);
-            } else {
-                if (c->js) hipLaunchKernelGGL((k_mdct_sub<true, 4>), dim3((unsigned)((mp.n_waves + 3) / 4)), dim3(256), 0, md, mp, c->d_tables);
-                else hipLaunchKernelGGL((k_mdct_sub<false, 4>), dim3((unsigned)((mp.n_waves + 3) / 4)), dim3(256), 0, md, mp, c->d_tables);
-            }
-        } else {
-            const int n_waves = S * 2 * fp.frame_runs;
-            hipLaunchKernelGGL(k_qmf_mdct8, dim3((unsigned)((n_waves + kFusedWaves - 1) / kFusedWaves)), dim3(64 * kFusedWaves), 0, st, fp, c->d_tables, n_waves);
-        }
-        if (timed) HIPCHK(c, hipEventRecord(ev[4], md));
-        HIPCHK(c, hipEventRecord(c->ev_mdct_done[slot], md));
-        c->slot_k1_launches[slot] = split ? 2 : 1;
-    }
-    if (gain) {
-        if (n_out == 0) launch_state(st, 1);   // (with frames it followed the QMF kernel)
-        launch_state(md, 2);                     // last curves: the light stage's own hand-over
-        // with frames the MDCT kernel was the last reader of the parity's subbands and gain records (the update above touches the curves and
-        // the band states, which only this stream reads and writes): its event serves, one record less between the kernels
-        if (n_out > 0) c->mid_done_of[par] = c->ev_mdct_done[slot];
-        else {
-            HIPCHK(c, hipEventRecord(c->ev_mid_done[par], md));
-            c->mid_done_of[par] = c->ev_mid_done[par];
-        }
-        c->mid_done_valid[par] = true;
-    } else {
-        launch_state(st, 3);
-    }
-    if (n_out > 0) {
-        // ---- back half, on its own stream, after the fused kernel of THIS call ----
-        // (Round 6, each an 8 - 11 % LOSS on the step although it shortens a chain: the loudness sums and k_psy queued behind the MDCT on the light stage's stream
-        // (no event hop between the streams in front of them); k_gain_energy_scale on this stream beside the MDCT; TrackLoudness inside k_psy (no k_loudness
-        // launch); k_loud_sum in 22 KB blocks that fit a slot one retiring analysis workgroup frees. EXPERIMENTS.md: the step's schedule is one of several
-        // stable ones.)
-        HIPCHK(c, hipStreamWaitEvent(bk, c->ev_mdct_done[slot], 0));
-        if (timed) HIPCHK(c, hipEventRecord(ev[5], bk));
-        BackParams bp;
-        bp.specs = d_specs;
-        bp.ges = gain ? d_ges : nullptr;
-        bp.curves = d_curves;
-        bp.psy = c->d_psy;
-        bp.loud = c->d_loud;
-        bp.loud_state = c->d_loud_state;
-        bp.out = d_out;
-        bp.n_blocks = n_blocks;
-        bp.f0 = f0;
-        bp.n_streams = S;
-        bp.no_tonal = c->cfg.no_tonal;
-        bp.js = c->js;
-        bp.frame_sz = c->frame_sz;
-        bp.bfu_idx_const = c->cfg.bfu_idx_const;
-        bp.mono_js = (c->cfg.channels == 1 && c->js) ? 1 : 0;
-        bp.flat_literal = c->flat_literal;
-        bp.quant = c->d_quant;
-        bp.clk = c->d_clk;
-        bp.counters = c->d_counters;
-        bp.one_channel = c->cfg.channels == 1 ? 1 : 0;
-        hipLaunchKernelGGL(k_loud_sum, dim3((unsigned)((S * n_out * 2 + kLoudCf - 1) / kLoudCf)), dim3(256), 0, bk, bp, c->d_tables, S * n_out * 2);
-        hipLaunchKernelGGL(k_psy, dim3((S * n_out * 2 + kPsyCf - 1) / kPsyCf), dim3(256), 0, bk, bp, c->d_tables, S * n_out * 2);
-        if (timed) HIPCHK(c, hipEventRecord(ev[6], bk));
-        hipLaunchKernelGGL(k_loudness, dim3(S), dim3(64), 0, bk, bp);
-        hipLaunchKernelGGL(k_alloc_pack, dim3(S * n_out * 2), dim3(64), 0, bk, bp, c->d_tables);
-        if (timed) HIPCHK(c, hipEventRecord(ev[7], bk));
-        if (!(flags & AT3HIP_OUT_ON_DEVICE))
-            HIPCHK(c, hipMemcpyAsync(out_frames, c->d_out, (size_t)S * n_out * c->frame_sz, hipMemcpyDeviceToHost, bk));
-        // one event per call on this stream: the frames are out (at3hip_wait_frames) and the back half is done with the parity's buffers
-        HIPCHK(c, hipEventRecord(c->ev_host_out[hq], bk));
-        c->ev_back_done[par] = c->ev_host_out[hq];
-        c->back_done_valid[par] = true;
-        host_out_recorded = true;
-        c->slot_has_frames[slot] = true;
-        c->last_slot = slot;
-    }
-    if (c->stream != c->own_stream) {   // (at3hip_destroy waits for the context's own streams themselves)
-        HIPCHK(c, hipEventRecord(c->ev_front_done, st));
-        c->front_done_valid = true;
-    }
-    if (staged) {   // (the PCM is read by the first stage and by the carried-state update, both on `st`)
-        HIPCHK(c, hipEventRecord(c->ev_pcm_free[par], st));
-        c->pcm_free_valid[par] = true;
-    }
-    HIPCHK(c, hipGetLastError());
-    c->host_in_valid[hq] = host_in_recorded;     // (a call without a host copy / without frames has nothing to wait for)
-    c->host_out_valid[hq] = host_out_recorded;
-    c->hist_cur ^= 1;
-    c->blocks_fed += n_blocks;
-    c->enc_calls++;
-    if (n_frames_out) *n_frames_out = n_out;
-    if (!(flags & AT3HIP_ASYNC)) {
-        const int rc = drain(c);
-        if (rc != AT3HIP_OK) return rc;
-        if (n_out > 0) read_timings(c, slot, &c->tm);
+        const size_t n = (size_t)S * k.n_blocks * 1024;
+        hipLaunchKernelGGL(k_mono_to_pairs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k.st, d_staged, c->d_pcm_in, n);
+        k.d_pcm = c->d_pcm_in;
     }
     return AT3HIP_OK;
+}
+
+// The carried-state update on stream `on`: PCM history and subband tail (parts & 1), last curves and band states (parts & 2).
+void launch_state(at3hip_ctx* c, const EncodeCall& k, hipStream_t on, int parts)
+{
+    StateParams sp;
+    sp.pcm = k.d_pcm;
+    sp.hist_in = k.hist;
+    sp.hist_out = k.hist_next;
+    sp.curves = k.d_curves;
+    sp.state = c->d_state;
+    sp.sub = k.split ? k.d_sub : nullptr;
+    sp.sub_tail = c->d_sub_tail;
+    sp.n_blocks = k.n_blocks;
+    sp.n_streams = c->cfg.n_streams;
+    sp.parts = parts;
+    hipLaunchKernelGGL(k_state_update, dim3((unsigned)(((kHist + 255) / 256) * c->cfg.n_streams)), dim3(256), 0, on, sp);
+}
+
+// k_qmf_sub8 on the heavy stage's stream: the subbands of all the call's blocks to HBM, one wavefront per (stream, channel, run).
+void launch_qmf_sub(at3hip_ctx* c, const EncodeCall& k, FrontParams& fp)
+{
+    fp.sub_runs = pick_runs(c, k.n_blocks, c->wgs_per_cu, 0.35, 4);
+    const int n_waves = c->cfg.n_streams * 2 * fp.sub_runs;
+    hipLaunchKernelGGL(k_qmf_sub8, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, k.st, fp, c->d_tables, n_waves);
+}
+
+// A call that only primes the look-ahead (n_out == 0) still has to leave its subbands behind for the next call's look-back.
+void launch_qmf_sub_priming(at3hip_ctx* c, const EncodeCall& k)
+{
+    FrontParams fp = {};
+    fp.pcm = k.d_pcm;
+    fp.hist = k.hist;
+    fp.sub = k.d_sub;
+    fp.sub_tail = c->d_sub_tail;
+    fp.n_blocks = k.n_blocks;
+    fp.f0 = k.f0;
+    fp.js = c->js;
+    launch_qmf_sub(c, k, fp);
+}
+
+// The front half's parameters of a call with frames; the cut of the fused kernel where that is the one to run.
+FrontParams front_params(at3hip_ctx* c, const EncodeCall& k)
+{
+    FrontParams fp;
+    fp.pcm = k.d_pcm;
+    fp.hist = k.hist;
+    fp.curves = k.d_curves;
+    fp.state = c->d_state;
+    fp.specs = k.d_specs;
+    fp.ges = k.d_ges;
+    fp.sub = k.d_sub;
+    fp.sub_tail = c->d_sub_tail;
+    fp.n_blocks = k.n_blocks;
+    fp.f0 = k.f0;
+    const FusedCut cut = k.split ? FusedCut{0, 0} : pick_fused(c, k.n_out);
+    fp.frame_runs = cut.runs;
+    fp.chain = cut.chain;
+    fp.sub_runs = 0;
+    fp.js = c->js;
+    return fp;
+}
+
+// k_mdct_sub on the light stage's stream: the subbands are in HBM (k_qmf_sub8 wrote them: for the gain analysis, or for the M/S matrixing).
+void launch_mdct_sub(at3hip_ctx* c, const EncodeCall& k)
+{
+    const int S = c->cfg.n_streams;
+    MdctSubParams mp;
+    mp.sub = k.d_sub;
+    mp.curves = k.gain ? k.d_curves : nullptr;
+    mp.state = c->d_state;
+    mp.specs = k.d_specs;
+    mp.n_blocks = k.n_blocks;
+    mp.f0 = k.f0;
+    mp.js = c->js;
+    mp.frame_runs = pick_runs(c, k.n_out, c->wgs_per_cu_mdct, 0.3);
+    mp.n_waves = S * 2 * mp.frame_runs;
+    // three wavefronts per workgroup (20.3 KB) where k_gain_analysis' launch is padded to fat slots - a light-stage workgroup must fit the slot
+    // one retiring analysis workgroup frees (analysis_lds_pad) -, four (25.5 KB; one table copy per four runs) where it fills the chip unpadded
+    const bool fat_slots = c->gain_form != AT3HIP_GAIN_FORM_ONE_WAVE && analysis_lds_pad(c, (long long)S * k.n_out * 6) != 0;   // (the one-wavefront form's launch has no fat slots)
+    if (fat_slots) {
+        if (c->js) hipLaunchKernelGGL((k_mdct_sub<true, 3>), dim3((unsigned)((mp.n_waves + 2) / 3)), dim3(192), 0, k.md, mp, c->d_tables);
+        else hipLaunchKernelGGL((k_mdct_sub<false, 3>), dim3((unsigned)((mp.n_waves + 2) / 3)), dim3(192), 0, k.md, mp, c->d_tables);
+    } else {
+        if (c->js) hipLaunchKernelGGL((k_mdct_sub<true, 4>), dim3((unsigned)((mp.n_waves + 3) / 4)), dim3(256), 0, k.md, mp, c->d_tables);
+        else hipLaunchKernelGGL((k_mdct_sub<false, 4>), dim3((unsigned)((mp.n_waves + 3) / 4)), dim3(256), 0, k.md, mp, c->d_tables);
+    }
+}
+
+// What every front half starts with: the waits that hand the parity's buffers over to this call, its first timestamp, the zeroed curves.
+int front_open(at3hip_ctx* c, const EncodeCall& k)
+{
+    // the light stage of the call before the previous one must be done with this parity's subbands and gain records
+    if (k.gain && c->mid_done_of[k.par]) HIPCHK(c, hipStreamWaitEvent(k.st, c->mid_done_of[k.par], 0));
+    if (k.timed) HIPCHK(c, hipEventRecord(k.ev[0], k.st));
+    // the back half of the call before the previous one must be done with this parity's spectra / curves / scales
+    if (c->back_done_of[k.par]) HIPCHK(c, hipStreamWaitEvent(k.md, c->back_done_of[k.par], 0));
+    HIPCHK(c, hipMemsetAsync(k.d_curves, 0, (size_t)c->cfg.n_streams * k.n_blocks * 8 * sizeof(Curve), k.md));
+    return AT3HIP_OK;
+}
+
+// What every front half with frames ends with: its last timestamp and the hand-over of the spectra to the back half.
+int front_close(at3hip_ctx* c, const EncodeCall& k)
+{
+    if (k.timed) HIPCHK(c, hipEventRecord(k.ev[4], k.md));
+    HIPCHK(c, hipEventRecord(c->ev_mdct_done[k.slot], k.md));
+    c->slot_k1_launches[k.slot] = k.split ? 2 : 1;
+    return AT3HIP_OK;
+}
+
+// The front half with gain control: the heavy stage on k.st, the light one on k.md, and what the parity's next call waits for.
+int front_with_gain(at3hip_ctx* c, const EncodeCall& k)
+{
+    const int S = c->cfg.n_streams, n_out = k.n_out, par = k.par;
+    hipStream_t st = k.st, md = k.md;
+    int rc = front_open(c, k);
+    if (rc != AT3HIP_OK) return rc;
+    if (n_out == 0) {
+        launch_qmf_sub_priming(c, k);
+        launch_state(c, k, st, 1);
+        launch_state(c, k, md, 2);   // last curves: the light stage's own hand-over
+        HIPCHK(c, hipEventRecord(c->ev_mid_done[par], md));
+        c->mid_done_of[par] = c->ev_mid_done[par];
+        return AT3HIP_OK;
+    }
+    FrontParams fp = front_params(c, k);
+    GainParams gp;
+    gp.sub = k.d_sub;
+    gp.rec = k.d_rec;
+    gp.bins = c->d_bins;
+    gp.state = c->d_state;
+    gp.curves = k.d_curves;
+    gp.n_blocks = k.n_blocks;
+    gp.f0 = k.f0;
+    gp.js = c->js;
+    gp.n_streams = S;
+    gp.literal = c->flat_literal;
+    launch_qmf_sub(c, k, fp);
+    if (k.timed) HIPCHK(c, hipEventRecord(k.ev[1], st));
+    // PCM history and subband tail: the next call's heavy stage needs nothing else from this one. (Round 6: moved behind the gain analysis - off the
+    // chain QMF -> spectra -> analysis - it cost the step 8 %: the next call's QMF kernel follows it on this stream and then misses the window
+    // between the analysis and the next rate loop in which it gets its only undisturbed microseconds. EXPERIMENTS.md.)
+    launch_state(c, k, st, 1);
+    const long long spec_wgs = (long long)S * ((n_out + 3) / 4) * 6;   // (four consecutive frames of one (stream, channel, band) per wavefront)
+    hipLaunchKernelGGL(k_gain_spec, dim3((unsigned)spec_wgs), dim3(64), spec_lds_pad(c, spec_wgs), st, gp, c->d_tables, S * n_out * 6);
+    // default: the two-wavefront form. The one-wavefront form is 11 % faster alone (89 against 101 us at 4096 frames) and
+    // leaves the pipelined step 2 % slower at that size, equal at the 1024 x 128 shard (profiles/EXPERIMENTS.md)
+    if (c->gain_form != AT3HIP_GAIN_FORM_ONE_WAVE) hipLaunchKernelGGL(k_gain_analysis, dim3(S * n_out * 6), dim3(128), analysis_lds_pad(c, (long long)S * n_out * 6), st, gp, c->d_tables);
+    else hipLaunchKernelGGL(k_gain_analysis1, dim3(S * n_out * 6), dim3(64), analysis1_lds_pad(c, (long long)S * n_out * 6), st, gp, c->d_tables);   // one wavefront per item
+    if (k.timed) HIPCHK(c, hipEventRecord(k.ev[2], st));
+    HIPCHK(c, hipEventRecord(c->ev_heavy_done[k.slot], st));
+    HIPCHK(c, hipStreamWaitEvent(md, c->ev_heavy_done[k.slot], 0));   // the light stage starts when this call's heavy stage is done
+    hipLaunchKernelGGL(k_gain_tail, dim3((unsigned)((S * n_out * 6 + 7) / 8)), dim3(256), 0, md, gp, S * n_out * 6);
+    hipLaunchKernelGGL(k_gain_scan, dim3(S * 6), dim3(64), 0, md, gp, S);
+    hipLaunchKernelGGL(k_gain_curve, dim3((S * n_out * 6 + 7) / 8), dim3(256), 0, md, gp, c->d_tables, S);
+    hipLaunchKernelGGL(k_gain_energy_scale, dim3(S * n_out), dim3(64), 0, md, fp, c->d_tables, S * n_out);
+    if (k.timed) HIPCHK(c, hipEventRecord(k.ev[3], md));
+    launch_mdct_sub(c, k);
+    if ((rc = front_close(c, k)) != AT3HIP_OK) return rc;
+    launch_state(c, k, md, 2);   // last curves: the light stage's own hand-over
+    // the MDCT kernel was the last reader of the parity's subbands and gain records (the update above touches the curves and
+    // the band states, which only this stream reads and writes): its event serves, one record less between the kernels
+    c->mid_done_of[par] = c->ev_mdct_done[k.slot];
+    return AT3HIP_OK;
+}
+
+// The front half without gain control, all of it on k.st: the fused QMF + MDCT kernel, or for joint stereo the two kernels.
+int front_without_gain(at3hip_ctx* c, const EncodeCall& k)
+{
+    hipStream_t st = k.st;
+    int rc = front_open(c, k);
+    if (rc != AT3HIP_OK) return rc;
+    if (k.n_out == 0 && k.split) launch_qmf_sub_priming(c, k);
+    if (k.n_out > 0) {
+        FrontParams fp = front_params(c, k);
+        if (k.split) launch_qmf_sub(c, k, fp);   // joint stereo without gain control: the QMF kernel, timed as qmf_ms
+        if (k.timed) HIPCHK(c, hipEventRecord(k.ev[1], st));
+        if (k.timed) HIPCHK(c, hipEventRecord(k.ev[2], st));
+        if (k.timed) HIPCHK(c, hipEventRecord(k.ev[3], st));
+        if (k.split) {
+            launch_mdct_sub(c, k);
+        } else {
+            const int n_waves = c->cfg.n_streams * 2 * fp.frame_runs;
+            hipLaunchKernelGGL(k_qmf_mdct8, dim3((unsigned)((n_waves + kFusedWaves - 1) / kFusedWaves)), dim3(64 * kFusedWaves), 0, st, fp, c->d_tables, n_waves);
+        }
+        if ((rc = front_close(c, k)) != AT3HIP_OK) return rc;
+    }
+    launch_state(c, k, st, 3);
+    return AT3HIP_OK;
+}
+
+// The back half of a call with frames, on its own stream, after the MDCT (or the fused kernel) of THIS call.
+// (Round 6, each an 8 - 11 % LOSS on the step although it shortens a chain: the loudness sums and k_psy queued behind the MDCT on the light stage's stream
+// (no event hop between the streams in front of them); k_gain_energy_scale on this stream beside the MDCT; TrackLoudness inside k_psy (no k_loudness
+// launch); k_loud_sum in 22 KB blocks that fit a slot one retiring analysis workgroup frees. EXPERIMENTS.md: the step's schedule is one of several
+// stable ones.)
+int back_half(at3hip_ctx* c, const EncodeCall& k, uint8_t* out_frames)
+{
+    const int S = c->cfg.n_streams, n_out = k.n_out;
+    hipStream_t bk = k.bk;
+    HIPCHK(c, hipStreamWaitEvent(bk, c->ev_mdct_done[k.slot], 0));
+    if (k.timed) HIPCHK(c, hipEventRecord(k.ev[5], bk));
+    BackParams bp;
+    bp.specs = k.d_specs;
+    bp.ges = k.gain ? k.d_ges : nullptr;
+    bp.curves = k.d_curves;
+    bp.psy = c->d_psy;
+    bp.loud = c->d_loud;
+    bp.loud_state = c->d_loud_state;
+    bp.out = k.d_out;
+    bp.n_blocks = k.n_blocks;
+    bp.f0 = k.f0;
+    bp.n_streams = S;
+    bp.no_tonal = c->cfg.no_tonal;
+    bp.js = c->js;
+    bp.frame_sz = c->frame_sz;
+    bp.bfu_idx_const = c->cfg.bfu_idx_const;
+    bp.mono_js = (c->cfg.channels == 1 && c->js) ? 1 : 0;
+    bp.flat_literal = c->flat_literal;
+    bp.quant = c->d_quant;
+    bp.clk = c->d_clk;
+    bp.counters = c->d_counters;
+    bp.one_channel = c->cfg.channels == 1 ? 1 : 0;
+    hipLaunchKernelGGL(k_loud_sum, dim3((unsigned)((S * n_out * 2 + kLoudCf - 1) / kLoudCf)), dim3(256), 0, bk, bp, c->d_tables, S * n_out * 2);
+    hipLaunchKernelGGL(k_psy, dim3((S * n_out * 2 + kPsyCf - 1) / kPsyCf), dim3(256), 0, bk, bp, c->d_tables, S * n_out * 2);
+    if (k.timed) HIPCHK(c, hipEventRecord(k.ev[6], bk));
+    hipLaunchKernelGGL(k_loudness, dim3(S), dim3(64), 0, bk, bp);
+    hipLaunchKernelGGL(k_alloc_pack, dim3(S * n_out * 2), dim3(64), 0, bk, bp, c->d_tables);
+    if (k.timed) HIPCHK(c, hipEventRecord(k.ev[7], bk));
+    if (!(k.flags & AT3HIP_OUT_ON_DEVICE))
+        HIPCHK(c, hipMemcpyAsync(out_frames, c->d_out, (size_t)S * n_out * c->frame_sz, hipMemcpyDeviceToHost, bk));
+    // one event per call on this stream: the frames are out (at3hip_wait_frames) and the back half is done with the parity's buffers
+    HIPCHK(c, c->host_out[k.hq].record(bk));
+    c->back_done_of[k.par] = c->host_out[k.hq].ev;
+    c->slot_has_frames[k.slot] = true;
+    c->last_slot = k.slot;
+    return AT3HIP_OK;
+}
+
+// The end of a call: the events that cover what it left on the front stream, the context's counters, and the wait unless AT3HIP_ASYNC.
+int finish_call(at3hip_ctx* c, const EncodeCall& k, int32_t* n_frames_out)
+{
+    if (c->stream != c->own_stream) HIPCHK(c, c->front_done.record(k.st));   // (at3hip_destroy waits for the context's own streams themselves)
+    if (k.staged) HIPCHK(c, c->pcm_free[k.par].record(k.st));   // (the PCM is read by the first stage and by the carried-state update, both on `st`)
+    HIPCHK(c, hipGetLastError());
+    c->host_in[k.hq].recorded = !(k.flags & AT3HIP_PCM_ON_DEVICE);   // (a call without a host copy / without frames leaves its slot of the ring
+    c->host_out[k.hq].recorded = k.n_out > 0;                         // with nothing to wait for)
+    c->hist_cur ^= 1;
+    c->blocks_fed += k.n_blocks;
+    c->enc_calls++;
+    if (n_frames_out) *n_frames_out = k.n_out;
+    if (!(k.flags & AT3HIP_ASYNC)) {
+        const int rc = drain(c);
+        if (rc != AT3HIP_OK) return rc;
+        if (k.n_out > 0) read_timings(c, k.slot, &c->tm);
+    }
+    return AT3HIP_OK;
+}
+
+int encode_impl(at3hip_ctx* c, const void* pcm_any, bool s16, int32_t n_blocks, uint8_t* out_frames, int32_t* n_frames_out, uint32_t flags)
+{
+    if (!c || !pcm_any || n_blocks < 1 || n_blocks > c->cfg.max_blocks) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
+    at3host::DeviceGuard guard(c->device);
+    HIPCHK(c, guard.error());
+    EncodeCall k;
+    k.n_blocks = n_blocks;
+    k.f0 = (c->blocks_fed == 0) ? 1 : 0;
+    k.n_out = n_blocks - k.f0;
+    k.flags = flags;
+    if (k.n_out > 0 && !out_frames) return fail(c, AT3HIP_EINVAL, "out_frames is null");
+    // k_s16_to_f32 reads the caller's device pointer sixteen bytes at a time
+    if (s16 && (flags & AT3HIP_PCM_ON_DEVICE) && ((uintptr_t)pcm_any & 15u) != 0) return fail(c, AT3HIP_EINVAL, "16-bit device PCM must be 16-byte aligned");
+    k.par = (int)(c->enc_calls & 1);
+    k.slot = (int)(c->enc_calls % at3hip_ctx::kSlots);
+    k.hq = (int)(c->enc_calls % at3hip_ctx::kHostRing);
+    k.gain = !c->cfg.no_gain_control;
+    k.split = k.gain || c->js;
+    k.staged = s16 || !(flags & AT3HIP_PCM_ON_DEVICE);
+    k.st = c->stream;
+    k.md = k.gain ? c->mid_stream : k.st;
+    k.bk = c->back_stream;
+    k.ev = c->ev[k.slot];
+    k.hist = c->d_hist[c->hist_cur];
+    k.hist_next = c->d_hist[c->hist_cur ^ 1];
+    k.d_sub = k.gain ? c->d_sub_b[k.par] : c->d_sub;
+    k.d_rec = k.gain ? c->d_rec_b[k.par] : c->d_rec;
+    k.d_curves = c->d_curves[k.par];
+    k.d_specs = c->d_specs[k.par];
+    k.d_ges = c->d_ges[k.par];
+    k.d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? out_frames : c->d_out;
+    int rc = stage_pcm(c, k, pcm_any, s16);
+    if (rc != AT3HIP_OK) return rc;
+    c->slot_has_frames[k.slot] = false;
+    // The timing events sit between the kernels of the three streams; at 4096 frames a step recording all eight takes 3.3 % longer than one recording none
+    // (EXPERIMENTS.md, round 6), so a caller that only samples the stage timings asks for every Nth call.
+    k.timed = k.n_out > 0 && c->timing_every > 0 && (c->timing_tick++ % (unsigned)c->timing_every) == 0;
+    c->slot_timed[k.slot] = k.timed;
+    rc = k.gain ? front_with_gain(c, k) : front_without_gain(c, k);
+    if (rc == AT3HIP_OK && k.n_out > 0) rc = back_half(c, k, out_frames);
+    return rc != AT3HIP_OK ? rc : finish_call(c, k, n_frames_out);
 }
 
 }  // namespace

@@ -18,10 +18,8 @@ using at3host::fail;
 static_assert(sizeof(Tables) == AT3PHIP_TABLES_BYTES, "at3phip.h documents the table block's size");
 static_assert(sizeof(WriteTables) == AT3PHIP_WRITE_TABLES_BYTES, "at3phip.h documents the frame writer's table block size");
 
-struct at3phip_ctx {
+struct at3phip_ctx : at3host::EngineBase {   // (no at3phip_set_stream: stream == own_stream)
     at3phip_config cfg;
-    int device = 0;
-    hipStream_t stream = nullptr;
     hipEvent_t ev[5] = {};
     Tables* d_tables = nullptr;
     float* d_pcm_in = nullptr;     // staging for host PCM   [S][F][2048][nch]
@@ -42,7 +40,6 @@ struct at3phip_ctx {
     long long enc_calls = 0;
     bool ev_from_encode = false;   // the timing events were last recorded by at3phip_encode_frames (at3phip_sync may read all of them)
     float pqf_ms = 0.0f, mdct_ms = 0.0f, write_ms = 0.0f;
-    char err[256] = {0};
 };
 
 namespace {
@@ -120,6 +117,54 @@ int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint1
     return AT3HIP_OK;
 }
 
+// A stage-level entry point (at3phip_pqf_analyse, at3phip_mdct, at3phip_pqf_mdct, at3phip_write_frames): which buffers it
+// stages and which of the context's events bracket its launches.
+struct StageOut {
+    void* host;            // null: an optional output the caller did not ask for
+    const void* staging;
+    size_t bytes;
+};
+struct Stage {
+    const void* in;        // the input, copied to in_staging unless AT3HIP_PCM_ON_DEVICE
+    void* in_staging;
+    size_t in_bytes;
+    StageOut out[2];       // the outputs, copied from their staging unless AT3HIP_OUT_ON_DEVICE
+    int first_ev;          // step k runs between ev[first_ev + k] and ev[first_ev + k + 1] ...
+    float at3phip_ctx::*ms[2];   // ... and its time is read into this member (null: no such step)
+};
+
+// Runs a stage on the main stream and waits: stage-in, launch(step) per step between its events, stage-out, wait, timings. Of
+// the filter bank's and the transform's times the ones this call did not measure read zero.
+template <typename Launch>
+int run_stage(at3phip_ctx* c, uint32_t flags, const Stage& s, Launch launch)
+{
+    at3host::DeviceGuard guard(c->device);
+    HIPCHK(c, guard.error());
+    if (int qrc = quiesce(c)) return qrc;
+    if (!(flags & AT3HIP_PCM_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(s.in_staging, s.in, s.in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev[s.first_ev], c->stream));
+    // (from here the timing events are no longer all at3phip_encode_frames': a later at3phip_sync must not mix them with an older encode's)
+    c->ev_from_encode = false;
+    for (int step = 0; step < 2 && s.ms[step]; ++step) {
+        const int rc = launch(step);
+        if (rc != AT3HIP_OK) return rc;
+        HIPCHK(c, hipEventRecord(c->ev[s.first_ev + step + 1], c->stream));
+    }
+    if (!(flags & AT3HIP_OUT_ON_DEVICE))
+        for (const StageOut& o : s.out)
+            if (o.host) HIPCHK(c, hipMemcpyAsync(o.host, o.staging, o.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    bool pqf = false, mdct = false;
+    for (int step = 0; step < 2 && s.ms[step]; ++step) {
+        (void)hipEventElapsedTime(&(c->*s.ms[step]), c->ev[s.first_ev + step], c->ev[s.first_ev + step + 1]);
+        pqf |= s.ms[step] == &at3phip_ctx::pqf_ms;
+        mdct |= s.ms[step] == &at3phip_ctx::mdct_ms;
+    }
+    if (!pqf) c->pqf_ms = 0.0f;
+    if (!mdct) c->mdct_ms = 0.0f;
+    return AT3HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -130,81 +175,46 @@ int at3phip_create(const at3phip_config* cfg, at3phip_ctx** out)
     *out = nullptr;
     if ((cfg->channels != 1 && cfg->channels != 2) || cfg->n_streams < 1 || cfg->max_frames < 1) return AT3HIP_EINVAL;
     if ((long long)cfg->n_streams * cfg->channels > at3host::kMaxGridY) return AT3HIP_EINVAL;   // (stream, channel) is gridDim.y
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return AT3HIP_EDEVICE;
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return AT3HIP_EINVAL;
-    at3phip_ctx* c = new (std::nothrow) at3phip_ctx();
-    if (!c) return AT3HIP_ENOMEM;
-    c->cfg = *cfg;
-    c->device = cfg->device_id;
-    int rc = AT3HIP_OK;
-    auto bail = [&](int code) {
-        at3phip_destroy(c);
-        return code;
-    };
-    at3host::DeviceGuard guard(c->device);
-    if (guard.error() != hipSuccess) return bail(AT3HIP_EDEVICE);
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    for (auto& e : c->ev)
-        if (hipEventCreate(&e) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    Tables* host_tables = new (std::nothrow) Tables();
-    if (!host_tables) return bail(AT3HIP_ENOMEM);
-    build_tables(host_tables);
-    rc = dev_alloc(c, &c->d_tables, 1);
-    if (rc == AT3HIP_OK) rc = at3host::upload_table(c->d_tables, host_tables, sizeof(Tables));
-    delete host_tables;
-    if (rc != AT3HIP_OK) return bail(rc);
-    const size_t S = cfg->n_streams, F = cfg->max_frames, C = cfg->channels;
-    if ((rc = dev_alloc(c, &c->d_pcm_in, S * F * C * 2048)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_bands, S * F * C * 2048)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_specs, S * F * C * 2048)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_flags, S * F * C)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_pqf_hist, S * C * kOverlap)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_mdct_hist, S * C * 2048)) != AT3HIP_OK) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_frames, S * F * kFrameBytes)) != AT3HIP_OK) return bail(rc);
-    c->d_specs_b[0] = c->d_specs;
-    if ((rc = dev_alloc(c, &c->d_specs_b[1], S * F * C * 2048)) != AT3HIP_OK) return bail(rc);
-    if (hipStreamCreateWithFlags(&c->write_stream, hipStreamNonBlocking) != hipSuccess) return bail(AT3HIP_EDEVICE);
-    for (int q = 0; q < 2; ++q)
-        if (hipEventCreateWithFlags(&c->ev_specs[q], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_write_done[q], hipEventDisableTiming) != hipSuccess)
-            return bail(AT3HIP_EDEVICE);
-    {
-        WriteTables* wt = new (std::nothrow) WriteTables();
-        if (!wt) return bail(AT3HIP_ENOMEM);
-        build_write_tables(wt);
-        rc = dev_alloc(c, &c->d_wtables, 1);
-        if (rc == AT3HIP_OK) rc = at3host::upload_table(c->d_wtables, wt, sizeof(WriteTables));
-        delete wt;
-        if (rc != AT3HIP_OK) return bail(rc);
-    }
-    if ((rc = reset_state(c)) != AT3HIP_OK) return bail(rc);
-    *out = c;
-    return AT3HIP_OK;
+    // (the order counts, see at3hip_create: the main stream with its events, tables and buffers, then the writer's stream with its events)
+    return at3host::create_engine(cfg->device_id, out, at3phip_destroy, [cfg](at3phip_ctx* c) {
+        c->cfg = *cfg;
+        for (auto& e : c->ev)
+            if (hipEventCreate(&e) != hipSuccess) return AT3HIP_EDEVICE;
+        int rc = at3host::make_device_tables(c, &c->d_tables, [](Tables* t) { build_tables(t); return true; });
+        if (rc != AT3HIP_OK) return rc;
+        const size_t S = cfg->n_streams, F = cfg->max_frames, C = cfg->channels;
+        if ((rc = dev_alloc(c, &c->d_pcm_in, S * F * C * 2048)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_bands, S * F * C * 2048)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_specs, S * F * C * 2048)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_flags, S * F * C)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_pqf_hist, S * C * kOverlap)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_mdct_hist, S * C * 2048)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(c, &c->d_frames, S * F * kFrameBytes)) != AT3HIP_OK) return rc;
+        c->d_specs_b[0] = c->d_specs;
+        if ((rc = dev_alloc(c, &c->d_specs_b[1], S * F * C * 2048)) != AT3HIP_OK) return rc;
+        if (hipStreamCreateWithFlags(&c->write_stream, hipStreamNonBlocking) != hipSuccess) return AT3HIP_EDEVICE;
+        for (int q = 0; q < 2; ++q)
+            if (hipEventCreateWithFlags(&c->ev_specs[q], hipEventDisableTiming) != hipSuccess ||
+                hipEventCreateWithFlags(&c->ev_write_done[q], hipEventDisableTiming) != hipSuccess)
+                return AT3HIP_EDEVICE;
+        rc = at3host::make_device_tables(c, &c->d_wtables, [](WriteTables* t) { build_write_tables(t); return true; });
+        return rc != AT3HIP_OK ? rc : reset_state(c);
+    });
 }
 
 void at3phip_destroy(at3phip_ctx* c)
 {
-    if (!c) return;
-    at3host::DeviceGuard guard(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->write_stream) (void)hipStreamSynchronize(c->write_stream);
-    if (c->d_specs_b[1]) (void)hipFree(c->d_specs_b[1]);
-    for (int q = 0; q < 2; ++q) {
-        if (c->ev_specs[q]) (void)hipEventDestroy(c->ev_specs[q]);
-        if (c->ev_write_done[q]) (void)hipEventDestroy(c->ev_write_done[q]);
-    }
-    if (c->write_stream) (void)hipStreamDestroy(c->write_stream);
-    void* bufs[] = {c->d_tables, c->d_pcm_in, c->d_pcm_s16, c->d_bands, c->d_specs, c->d_flags, c->d_pqf_hist, c->d_mdct_hist, c->d_wtables, c->d_frames};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (auto& e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c)
+        at3host::destroy_engine(c, {c->d_tables, c->d_pcm_in, c->d_pcm_s16, c->d_bands, c->d_specs, c->d_specs_b[1], c->d_flags, c->d_pqf_hist,
+                                    c->d_mdct_hist, c->d_wtables, c->d_frames},
+                                {c->write_stream}, [c] {
+                                    for (hipEvent_t e : {c->ev[0], c->ev[1], c->ev[2], c->ev[3], c->ev[4], c->ev_specs[0], c->ev_specs[1],
+                                                         c->ev_write_done[0], c->ev_write_done[1]})
+                                        if (e) (void)hipEventDestroy(e);
+                                });
 }
 
-const char* at3phip_last_error(const at3phip_ctx* c) { return c ? c->err : "null context"; }
+const char* at3phip_last_error(const at3phip_ctx* c) { return at3host::engine_last_error(c); }
 
 int at3phip_reset(at3phip_ctx* c)
 {
@@ -218,110 +228,45 @@ int at3phip_reset(at3phip_ctx* c)
 int at3phip_pqf_analyse(at3phip_ctx* c, const float* pcm, int32_t n_frames, float* bands, uint32_t flags)
 {
     if (!c || !pcm || !bands || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    if (int qrc = quiesce(c)) return qrc;
-    const size_t n = (size_t)c->cfg.n_streams * n_frames * c->cfg.channels * 2048;
-    const float* d_pcm = pcm;
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(c, hipMemcpyAsync(c->d_pcm_in, pcm, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        d_pcm = c->d_pcm_in;
-    }
+    const size_t bytes = (size_t)c->cfg.n_streams * n_frames * c->cfg.channels * 2048 * sizeof(float);
+    const float* d_pcm = (flags & AT3HIP_PCM_ON_DEVICE) ? pcm : c->d_pcm_in;
     float* d_bands = (flags & AT3HIP_OUT_ON_DEVICE) ? bands : c->d_bands;
-    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    c->ev_from_encode = false;
-    int rc = launch_pqf(c, d_pcm, n_frames, d_bands);
-    if (rc != AT3HIP_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    if (!(flags & AT3HIP_OUT_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(bands, c->d_bands, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipEventElapsedTime(&c->pqf_ms, c->ev[0], c->ev[1]);
-    c->mdct_ms = 0.0f;
-    return AT3HIP_OK;
+    const Stage stage = {pcm, c->d_pcm_in, bytes, {{bands, c->d_bands, bytes}}, 0, {&at3phip_ctx::pqf_ms}};
+    return run_stage(c, flags, stage, [&](int) { return launch_pqf(c, d_pcm, n_frames, d_bands); });
 }
 
 int at3phip_mdct(at3phip_ctx* c, const float* bands, int32_t n_frames, const uint16_t* win_flags, float* specs, uint32_t flags)
 {
     if (!c || !bands || !specs || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    if (int qrc = quiesce(c)) return qrc;
-    const size_t n = (size_t)c->cfg.n_streams * n_frames * c->cfg.channels * 2048;
-    const float* d_bands = bands;
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(c, hipMemcpyAsync(c->d_bands, bands, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        d_bands = c->d_bands;
-    }
+    const size_t bytes = (size_t)c->cfg.n_streams * n_frames * c->cfg.channels * 2048 * sizeof(float);
+    const float* d_bands = (flags & AT3HIP_PCM_ON_DEVICE) ? bands : c->d_bands;
     float* d_specs = (flags & AT3HIP_OUT_ON_DEVICE) ? specs : c->d_specs;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    c->ev_from_encode = false;
-    int rc = launch_mdct(c, d_bands, n_frames, win_flags, d_specs, flags);
-    if (rc != AT3HIP_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    if (!(flags & AT3HIP_OUT_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(specs, c->d_specs, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipEventElapsedTime(&c->mdct_ms, c->ev[1], c->ev[2]);
-    c->pqf_ms = 0.0f;
-    return AT3HIP_OK;
+    const Stage stage = {bands, c->d_bands, bytes, {{specs, c->d_specs, bytes}}, 1, {&at3phip_ctx::mdct_ms}};
+    return run_stage(c, flags, stage, [&](int) { return launch_mdct(c, d_bands, n_frames, win_flags, d_specs, flags); });
 }
 
 int at3phip_pqf_mdct(at3phip_ctx* c, const float* pcm, int32_t n_frames, const uint16_t* win_flags, float* bands, float* specs, uint32_t flags)
 {
     if (!c || !pcm || !specs || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    if (int qrc = quiesce(c)) return qrc;
-    const size_t n = (size_t)c->cfg.n_streams * n_frames * c->cfg.channels * 2048;
-    const float* d_pcm = pcm;
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(c, hipMemcpyAsync(c->d_pcm_in, pcm, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        d_pcm = c->d_pcm_in;
-    }
+    const size_t bytes = (size_t)c->cfg.n_streams * n_frames * c->cfg.channels * 2048 * sizeof(float);
+    const float* d_pcm = (flags & AT3HIP_PCM_ON_DEVICE) ? pcm : c->d_pcm_in;
     const bool out_dev = (flags & AT3HIP_OUT_ON_DEVICE) != 0;
-    float* d_bands = (out_dev && bands) ? bands : c->d_bands;
+    float* d_bands = (out_dev && bands) ? bands : c->d_bands;   // (the subbands are optional)
     float* d_specs = out_dev ? specs : c->d_specs;
-    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    c->ev_from_encode = false;
-    int rc = launch_pqf(c, d_pcm, n_frames, d_bands);
-    if (rc != AT3HIP_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    rc = launch_mdct(c, d_bands, n_frames, win_flags, d_specs, flags);
-    if (rc != AT3HIP_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    if (!out_dev) {
-        if (bands) HIPCHK(c, hipMemcpyAsync(bands, c->d_bands, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(specs, c->d_specs, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipEventElapsedTime(&c->pqf_ms, c->ev[0], c->ev[1]);
-    (void)hipEventElapsedTime(&c->mdct_ms, c->ev[1], c->ev[2]);
-    return AT3HIP_OK;
+    const Stage stage = {pcm, c->d_pcm_in, bytes, {{bands, c->d_bands, bytes}, {specs, c->d_specs, bytes}}, 0, {&at3phip_ctx::pqf_ms, &at3phip_ctx::mdct_ms}};
+    return run_stage(c, flags, stage, [&](int step) {
+        return step == 0 ? launch_pqf(c, d_pcm, n_frames, d_bands) : launch_mdct(c, d_bands, n_frames, win_flags, d_specs, flags);
+    });
 }
 
 int at3phip_write_frames(at3phip_ctx* c, const float* specs, int32_t n_frames, const uint16_t* win_flags, uint8_t* frames, uint32_t flags)
 {
     if (!c || !specs || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    if (int qrc = quiesce(c)) return qrc;
     const size_t items = (size_t)c->cfg.n_streams * n_frames;
-    const size_t n = items * c->cfg.channels * 2048;
-    const float* d_specs = specs;
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(c, hipMemcpyAsync(c->d_specs, specs, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        d_specs = c->d_specs;
-    }
+    const float* d_specs = (flags & AT3HIP_PCM_ON_DEVICE) ? specs : c->d_specs;
     uint8_t* d_frames = (flags & AT3HIP_OUT_ON_DEVICE) ? frames : c->d_frames;
-    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    int rc = launch_write(c, d_specs, n_frames, win_flags, d_frames);
-    if (rc != AT3HIP_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-    if (!(flags & AT3HIP_OUT_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(frames, c->d_frames, items * kFrameBytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipEventElapsedTime(&c->write_ms, c->ev[2], c->ev[3]);
-    c->pqf_ms = c->mdct_ms = 0.0f;
-    c->ev_from_encode = false;   // ev[2], ev[3] now belong to this call: a later at3phip_sync must not mix them with an older encode's
-    return AT3HIP_OK;
+    const Stage stage = {specs, c->d_specs, items * c->cfg.channels * 2048 * sizeof(float), {{frames, c->d_frames, items * kFrameBytes}}, 2, {&at3phip_ctx::write_ms}};
+    return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames); });
 }
 
 }  // extern "C"

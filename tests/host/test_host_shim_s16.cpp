@@ -30,6 +30,30 @@ static int fails = 0;
         }                                                              \
     } while (0)
 
+// Only in a build of the library's sources through the CPU SIMT harness (tools/emu/emu_runtime.cpp): n more device allocations
+// succeed, every later one is refused. Against libat3hip.so the symbol is absent and the part that uses it is skipped.
+extern "C" void emu_fail_alloc_after(long n) __attribute__((weak));
+
+// Refuses every device allocation of create(cfg) in turn: each time the create must report AT3HIP_ENOMEM, give no context and
+// have released the half-made one (the sanitizers this program is run under see a leak or a double free). Returns the
+// number of allocations of a create that succeeds.
+template <class Cfg, class Ctx>
+static int HalfMadeCreates(int (*create)(const Cfg*, Ctx**), void (*destroy)(Ctx*), const Cfg& cfg)
+{
+    for (int n = 0; n < 100; ++n) {
+        emu_fail_alloc_after(n);
+        Ctx* c = nullptr;
+        const int rc = create(&cfg, &c);
+        emu_fail_alloc_after(-1);
+        if (rc == AT3HIP_OK) {
+            destroy(c);
+            return n;
+        }
+        EXPECT(rc == AT3HIP_ENOMEM && c == nullptr);
+    }
+    return -1;
+}
+
 template <class T>
 static bool SameBytes(const std::vector<T>& a, const std::vector<T>& b)
 {
@@ -65,6 +89,25 @@ int main()
         return fails ? 1 : 0;
     }
     at1hip_destroy(ctx);
+
+    if (emu_fail_alloc_after) {   // ---- creates that fail half-way, for the three encoders ----
+        at3phip_config p3{};
+        p3.channels = 2;
+        p3.n_streams = 2;
+        p3.max_frames = 2;
+        at3hip_config c3{};
+        c3.channels = 2;
+        c3.n_streams = 2;
+        c3.max_blocks = 2;
+        at3hip_config c3m = c3;   // one channel, joint stereo, no gain control: the other set of buffers and streams
+        c3m.channels = 1;
+        c3m.bitrate = 66150;
+        c3m.no_gain_control = 1;
+        const int n1 = HalfMadeCreates(at1hip_create, at1hip_destroy, probe), np = HalfMadeCreates(at3phip_create, at3phip_destroy, p3);
+        const int n3 = HalfMadeCreates(at3hip_create, at3hip_destroy, c3), n3m = HalfMadeCreates(at3hip_create, at3hip_destroy, c3m);
+        EXPECT(n1 > 0 && np > 0 && n3 > 0 && n3m > 0);
+        printf("half-made creates: %d (at1hip), %d (at3phip), %d and %d (at3hip) allocations refused in turn\n", n1, np, n3, n3m);
+    }
 
     // full-range noise with both extremes, a silence and a full-scale burst behind it
     const int C = 2, n = 5 * 2048;   // sample frames

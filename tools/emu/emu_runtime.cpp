@@ -4,8 +4,10 @@
 #include <sys/mman.h>
 #include <unistd.h>
 
+#include <cstdarg>
 #include <map>
 #include <mutex>
+#include <string>
 // k_alloc_pack's harness-only counters (at3_k_alloc.hpp: AT3_STAT)
 extern "C" { unsigned long long g_alloc_stats[16] = {0}; }
 
@@ -25,6 +27,9 @@ struct Fiber {
 };
 constexpr size_t kStack = 256 * 1024;
 std::vector<Fiber> g_fibers;
+struct FiberStacks {   // (defined behind g_fibers: runs before the vector goes, so a leak check at exit sees the product's leaks only)
+    ~FiberStacks() { for (Fiber& f : g_fibers) free(f.stack); }
+} g_fiber_stacks;
 ucontext_t g_main;
 const std::function<void()>* g_body = nullptr;
 int g_cur = -1;
@@ -95,8 +100,15 @@ void trampoline()
 }
 }  // namespace
 
+// emu_fail_alloc_after(n): n more device allocations succeed, every later one is refused (n < 0: none is). A stand-alone
+// program walks the *_create paths that destroy a half-made context with it (tests/host/test_host_shim_s16.cpp).
+static long g_allocs_left = -1;
+extern "C" void emu_fail_alloc_after(long n) { g_allocs_left = n; }
+
 void* emu_device_alloc(size_t n)
 {
+    if (g_allocs_left == 0) return nullptr;
+    if (g_allocs_left > 0) --g_allocs_left;
     const int mode = fence_mode();
     if (mode == 0) {
         void* p = malloc(n);
@@ -128,6 +140,121 @@ void emu_device_free(void* p)
     munmap(it->second.base, it->second.bytes);
     g_fenced.erase(it);
 }
+
+// ---- streams, events, copies: objects of their own, and the EMU_TRACE call trace (hip/hip_runtime.h) ----
+struct emu_event {
+    int ordinal;
+};
+namespace {
+std::mutex g_trace_mu;
+std::map<void*, int> g_streams;       // the streams made here -> ordinal in creation order
+std::map<void*, size_t> g_alloc_bytes;   // (traced runs only) what hipFree gives back
+int g_n_streams = 0, g_n_events = 0;
+
+FILE* trace_file()
+{
+    static FILE* f = [] {
+        const char* e = getenv("EMU_TRACE");
+        return (e && *e) ? fopen(e, "a") : (FILE*)nullptr;
+    }();
+    return f;
+}
+void trace(const char* fmt, ...)
+{
+    FILE* f = trace_file();
+    if (!f) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(f, fmt, ap);
+    va_end(ap);
+    fputc('\n', f);
+    fflush(f);
+}
+std::string sname(hipStream_t s)
+{
+    std::lock_guard<std::mutex> lock(g_trace_mu);
+    auto it = g_streams.find(s);
+    return it == g_streams.end() ? std::string(s ? "caller" : "null") : "s" + std::to_string(it->second);
+}
+std::string ename(hipEvent_t e) { return e ? "e" + std::to_string(e->ordinal) : std::string("null"); }
+const char* kname(hipMemcpyKind k) { return k == hipMemcpyHostToDevice ? "h2d" : k == hipMemcpyDeviceToHost ? "d2h" : "d2d"; }
+
+hipError_t make_stream(hipStream_t* s, unsigned flags, const int* priority)
+{
+    *s = malloc(8);
+    if (!*s) return hipErrorUnknown;
+    int n;
+    {
+        std::lock_guard<std::mutex> lock(g_trace_mu);
+        n = g_streams[*s] = g_n_streams++;
+    }
+    if (priority) trace("stream_create s%d flags=%u priority=%d", n, flags, *priority);
+    else trace("stream_create s%d flags=%u priority=default", n, flags);
+    return hipSuccess;
+}
+}  // namespace
+
+hipError_t hipStreamCreate(hipStream_t* s) { return make_stream(s, 0, nullptr); }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned flags) { return make_stream(s, flags, nullptr); }
+hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned flags, int priority) { return make_stream(s, flags, &priority); }
+hipError_t hipStreamDestroy(hipStream_t s)
+{
+    trace("stream_destroy %s", sname(s).c_str());
+    std::lock_guard<std::mutex> lock(g_trace_mu);
+    if (g_streams.erase(s)) free(s);
+    return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t s) { trace("stream_sync %s", sname(s).c_str()); return hipSuccess; }
+hipError_t hipDeviceSynchronize() { trace("device_sync"); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags)
+{
+    *e = (hipEvent_t)malloc(sizeof(emu_event));
+    if (!*e) return hipErrorUnknown;
+    {
+        std::lock_guard<std::mutex> lock(g_trace_mu);
+        (*e)->ordinal = g_n_events++;
+    }
+    trace("event_create %s flags=%u", ename(*e).c_str(), flags);
+    return hipSuccess;
+}
+hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, 0); }
+hipError_t hipEventDestroy(hipEvent_t e) { trace("event_destroy %s", ename(e).c_str()); free(e); return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { trace("event_record %s %s", ename(e).c_str(), sname(s).c_str()); return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t e) { trace("event_sync %s", ename(e).c_str()); return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { trace("stream_wait %s %s", sname(s).c_str(), ename(e).c_str()); return hipSuccess; }
+
+hipError_t hipMalloc(void** p, size_t n)
+{
+    *p = emu_device_alloc(n);
+    if (trace_file()) {
+        trace("malloc %zu", n);
+        std::lock_guard<std::mutex> lock(g_trace_mu);
+        if (*p) g_alloc_bytes[*p] = n;
+    }
+    return *p ? hipSuccess : hipErrorUnknown;
+}
+hipError_t hipFree(void* p)
+{
+    if (trace_file()) {
+        size_t n = 0;
+        {
+            std::lock_guard<std::mutex> lock(g_trace_mu);
+            auto it = g_alloc_bytes.find(p);
+            if (it != g_alloc_bytes.end()) { n = it->second; g_alloc_bytes.erase(it); }
+        }
+        trace("free %zu", n);
+    }
+    emu_device_free(p);
+    return hipSuccess;
+}
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind kind) { trace("memcpy %s %zu", kname(kind), n); memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t st)
+{
+    trace("memcpy_async %s %zu %s", kname(kind), n, sname(st).c_str());
+    memcpy(d, s, n);
+    return hipSuccess;
+}
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) { trace("memset_async %zu %s", n, sname(st).c_str()); memset(d, v, n); return hipSuccess; }
 
 #define EMU_WAIT(what) do { Fiber& f_ = g_fibers[g_cur]; f_.wait = what; f_.wait_pc = __builtin_return_address(0); f_.hist[++f_.hist_n % 16] = f_.wait_pc; } while (0)
 
@@ -225,8 +352,12 @@ __attribute__((noinline)) int emu_update_dpp(int old, int src, int ctrl, int row
     return (int)all[row * 16 + srcpos];
 }
 
-void emu_launch(const char* name, dim3 grid, dim3 block, const std::function<void()>& body)
+void emu_launch(const char* name, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const std::function<void()>& body)
 {
+    // one kernel at a time: the scheduler's state is global, and a host program may launch from several threads
+    static std::mutex launch_mu;
+    std::lock_guard<std::mutex> launch_lock(launch_mu);
+    trace("launch %s grid=(%u,%u,%u) block=(%u,%u,%u) lds=%zu %s", name, grid.x, grid.y, grid.z, block.x, block.y, block.z, lds_bytes, sname(stream).c_str());
     const unsigned nthr = block.x * block.y * block.z;
     if (g_fibers.size() < nthr) {
         const size_t old = g_fibers.size();

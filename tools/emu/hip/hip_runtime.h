@@ -99,35 +99,41 @@ static inline const char* hipGetErrorString(hipError_t) { return "emu error"; }
 static inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 static inline hipError_t hipSetDevice(int) { return hipSuccess; }
 static inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
-static inline hipError_t hipStreamCreate(hipStream_t* s) { *s = (void*)1; return hipSuccess; }
+// Streams, events and everything queued on them are out of line (emu_runtime.cpp): every stream and event is an object of its
+// own, and with EMU_TRACE=<file> in the environment when the library loads each of these calls appends one line to that file
+// (streams and events by their ordinal in creation order, byte counts, launch geometry; never a pointer). A stream handle that
+// was not made here - a caller's - is traced as `caller`. tools/emu/run_emu_trace.py pins the host code's call sequence with it.
+// The priority range is 0 (lowest) .. -1, so that a trace tells a low-priority stream from a high-priority one.
 #define hipStreamNonBlocking 1
-static inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = 0; return hipSuccess; }
-static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (void*)1; return hipSuccess; }
-static inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (void*)1; return hipSuccess; }
-static inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
-static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
-static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t)malloc(8); return hipSuccess; }
-static inline hipError_t hipEventDestroy(hipEvent_t e) { free(e); return hipSuccess; }
-static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
 #define hipEventDisableTiming 2
-static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)malloc(8); return hipSuccess; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
+static inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = -1; return hipSuccess; }
+hipError_t hipStreamCreate(hipStream_t* s);
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned flags);
+hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned flags, int priority);
+hipError_t hipStreamDestroy(hipStream_t s);
+hipError_t hipStreamSynchronize(hipStream_t s);
+hipError_t hipDeviceSynchronize();
+hipError_t hipEventCreate(hipEvent_t* e);
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags);
+hipError_t hipEventDestroy(hipEvent_t e);
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s);
+hipError_t hipEventSynchronize(hipEvent_t e);
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned);
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0; return hipSuccess; }
 // device allocations: poisoned with 0xCD, and under EMU_FENCE placed against a guard page (emu_runtime.cpp)
 // (C linkage: tools/emu/run_emu_decode.py allocates exactly-sized caller buffers with them, which the product's own
 // allocations, padded by dev_alloc, are not)
 extern "C" void* emu_device_alloc(size_t n);
 extern "C" void emu_device_free(void* p);
-static inline hipError_t hipMalloc(void** p, size_t n) { *p = emu_device_alloc(n); return *p ? hipSuccess : hipErrorUnknown; }
+extern "C" void emu_fail_alloc_after(long n);   // n more allocations succeed, the later ones are refused (n < 0: none is)
+hipError_t hipMalloc(void** p, size_t n);
 #define hipHostMallocDefault 0u
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n); return *p ? hipSuccess : hipErrorUnknown; }
 static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
-static inline hipError_t hipFree(void* p) { emu_device_free(p); return hipSuccess; }
-static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
+hipError_t hipFree(void* p);
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind kind);
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t st);
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st);
 static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
 struct hipDeviceProp_t { int multiProcessorCount; size_t maxSharedMemoryPerMultiProcessor; };
 static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { p->multiProcessorCount = 4; p->maxSharedMemoryPerMultiProcessor = 160u * 1024u; return hipSuccess; }
@@ -177,6 +183,6 @@ static inline unsigned __builtin_amdgcn_mbcnt_hi(unsigned mask, unsigned v) { co
 static inline int __popcll(unsigned long long x) { return __builtin_popcountll(x); }
 static inline int __popc(unsigned x) { return __builtin_popcount(x); }
 
-void emu_launch(const char* name, dim3 grid, dim3 block, const std::function<void()>& body);
+void emu_launch(const char* name, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const std::function<void()>& body);
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    emu_launch(#kernel, (grid), (block), [&]() { kernel(__VA_ARGS__); })
+    emu_launch(#kernel, (grid), (block), (shmem), (stream), [&]() { kernel(__VA_ARGS__); })

@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""DEVELOPMENT HARNESS: the HOST code of the three encoders through the CPU SIMT emulator (tools/emu) with its call trace on
+(EMU_TRACE, hip/hip_runtime.h): which runtime call, on which stream, with which event, byte count and launch geometry. Each
+case runs one fixed script of calls in a child process and its trace is compared with tests/golden/host_trace/<case>.txt -
+the driver of tests/test_host_call_trace.py. `--write` writes the goldens instead. The samples are silence: the host code
+never looks at them. Runs of event creations with consecutive ordinals are folded into one line. Up to `# destroy` the order
+of the calls is compared; of *_destroy, every wait and every release it makes (each sorted: the order among them says nothing).
+The joint-stereo-with-gain and the one-channel case differ from the first one in their launches only and run a short script."""
+import ctypes, os, re, subprocess, sys, tempfile
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
+import numpy as np
+import run_emu
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "host_trace")
+DEV = 1 | 2   # AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE: in the harness any host array is "device" memory
+CALLER = 0x1000   # a stream handle the harness did not make (never dereferenced)
+S = 2
+
+
+def destroy(enc):
+    with open(os.environ["EMU_TRACE"], "a") as f:   # (the harness appends and flushes line by line)
+        f.write("# destroy\n")
+    enc.close()
+
+
+def at3_case(bitrate, no_gain, channels=2, prime_only=False, short=False):
+    def run():
+        from atracdenc_amd import binding as b
+        enc = b.At3Hip(n_streams=S, max_blocks=4, bitrate=bitrate, no_gain=no_gain, channels=channels, lib_path=run_emu.EMU)
+        f32 = np.zeros((S, 4, 1024, channels), np.float32)
+        i16 = np.zeros((S, 4, 1024, channels), np.int16)
+        out = np.zeros((S, 4, enc.frame_size), np.uint8)
+        if prime_only:   # one block on a fresh context: nothing but the look-ahead is primed (n_out == 0)
+            enc.encode(f32[:, :1])
+            destroy(enc)
+            return
+        enc.encode(f32[:, :3]); enc.encode(f32[:, :2])                 # host float: the priming call, then parity 1
+        if short:   # one host int16 call, one queued call on device pointers
+            enc.encode_s16(i16[:, :2])
+            enc.encode_device(f32.ctypes.data, 2, out.ctypes.data, asynchronous=True); enc.sync()
+            enc.reset()
+            destroy(enc)
+            return
+        enc.encode_s16(i16[:, :2]); enc.encode_s16(i16[:, :2])         # host int16, both parities
+        for _ in range(3): enc.encode_device(f32.ctypes.data, 2, out.ctypes.data, asynchronous=True)
+        enc.wait_input(1); enc.wait_frames(1); enc.sync()
+        enc.set_stream(CALLER); enc.encode_device(f32.ctypes.data, 2, out.ctypes.data); enc.set_stream(0)
+        enc.set_option(b.OPT_GAIN_FORM, b.GAIN_FORM_ONE_WAVE); enc.encode_device(f32.ctypes.data, 2, out.ctypes.data)
+        enc.set_option(b.OPT_GAIN_FORM, b.GAIN_FORM_TWO_WAVES)
+        enc.set_option(b.OPT_TIMING_EVERY, 2)
+        for _ in range(3): enc.encode_device(f32.ctypes.data, 2, out.ctypes.data)
+        enc.reset()
+        destroy(enc)
+    return run
+
+
+def at1_case():
+    from atracdenc_amd import binding as b
+    enc = b.At1Hip(n_streams=S, max_blocks=2, channels=2, lib_path=run_emu.EMU)
+    f32 = np.zeros((S, 2, 512, 2), np.float32)
+    out = np.zeros((S, 2, 2, 212), np.uint8)
+    enc.encode(f32); enc.encode(f32[:, :1])
+    enc.encode_s16(np.zeros((S, 2, 512, 2), np.int16))
+    enc.encode_device(f32.ctypes.data, 2, out.ctypes.data, asynchronous=True); enc.sync()
+    enc.read_tap(b.At1Hip.TAP_MASKS, np.int32, (S, 2, 2))
+    enc.reset()
+    destroy(enc)
+
+
+def at3p_case():
+    from atracdenc_amd import binding as b
+    enc = b.At3pHip(n_streams=S, max_frames=2, channels=2, lib_path=run_emu.EMU)
+    vp = lambda a: ctypes.c_void_p(a.ctypes.data)
+    pcm = np.zeros((S, 2, 2048, 2), np.float32)
+    bands = enc.pqf(pcm)
+    specs = enc.mdct(bands)
+    enc.pqf_mdct(pcm)
+    frames = enc.write_frames(specs)
+    lib, c = enc.lib, enc.ctx
+    enc._check(lib.at3phip_pqf_analyse(c, vp(pcm), 2, vp(bands), DEV), "at3phip_pqf_analyse")
+    enc._check(lib.at3phip_mdct(c, vp(bands), 2, None, vp(specs), DEV), "at3phip_mdct")
+    enc._check(lib.at3phip_pqf_mdct(c, vp(pcm), 2, None, vp(bands), vp(specs), DEV), "at3phip_pqf_mdct")
+    enc._check(lib.at3phip_write_frames(c, vp(specs), 2, None, vp(frames), DEV), "at3phip_write_frames")
+    for _ in range(3): enc.encode_frames_device(pcm.ctypes.data, 2, frames.ctypes.data, asynchronous=True)
+    enc.sync()
+    enc.encode_frames_s16(np.zeros((S, 2, 2048, 2), np.int16))
+    enc.reset()
+    destroy(enc)
+
+
+def cases():
+    from atracdenc_amd.binding import LP2, LP4
+    return {"at3_lp2_gain": at3_case(LP2, 0), "at3_lp2_nogain": at3_case(LP2, 1), "at3_lp4_gain": at3_case(LP4, 0, short=True),
+            "at3_lp4_nogain": at3_case(LP4, 1), "at3_mono_lp2": at3_case(LP2, 0, channels=1, short=True),
+            "at3_prime_gain": at3_case(LP2, 0, prime_only=True), "at3_prime_nogain": at3_case(LP2, 1, prime_only=True),
+            "at1": at1_case, "at3p": at3p_case}
+
+
+def fold(lines):
+    """event_create / event_destroy lines with consecutive ordinals and equal flags become `event_create e4..e259 flags=0`"""
+    out, run = [], None   # run: [verb, first, last, rest]
+    def flush():
+        if run: out.append(f"{run[0]} e{run[1]}{'..e%d' % run[2] if run[2] != run[1] else ''}{run[3]}")
+    for ln in lines:
+        m = re.fullmatch(r"(event_create|event_destroy) e(\d+)(.*)", ln)
+        if m and run and run[0] == m.group(1) and run[3] == m.group(3) and int(m.group(2)) == run[2] + 1:
+            run[2] += 1
+            continue
+        flush()
+        run = [m.group(1), int(m.group(2)), int(m.group(2)), m.group(3)] if m else None
+        if not m: out.append(ln)
+    flush()
+    return out
+
+
+def canonical(lines):
+    cut = lines.index("# destroy")
+    key = lambda ln: (ln.split()[0], [int(n) for n in re.findall(r"\d+", ln)])
+    waits = sorted((ln for ln in lines[cut + 1:] if "sync" in ln), key=key)
+    releases = sorted((ln for ln in lines[cut + 1:] if "sync" not in ln), key=key)
+    return fold(lines[:cut + 1]) + waits + fold(releases)
+
+
+def trace_of(case):
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "trace.txt")
+        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", case], env=dict(os.environ, EMU_TRACE=path), cwd=ROOT)
+        with open(path) as f:
+            return canonical(f.read().splitlines())
+
+
+if __name__ == "__main__":
+    if "--child" in sys.argv:
+        cases()[sys.argv[sys.argv.index("--child") + 1]]()
+        sys.exit(0)
+    if "--nobuild" not in sys.argv: run_emu.build()
+    write = "--write" in sys.argv
+    for case in [a for a in sys.argv[1:] if not a.startswith("--")] or list(cases()):
+        got = trace_of(case)
+        golden = os.path.join(GOLDEN, case + ".txt")
+        if write:
+            os.makedirs(GOLDEN, exist_ok=True)
+            with open(golden, "w") as f:
+                f.write("\n".join(got) + "\n")
+            print(f"{case}: wrote {len(got)} lines")
+            continue
+        with open(golden) as f:
+            want = f.read().splitlines()
+        first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+        bad = sum(a != b for a, b in zip(got, want)) + abs(len(got) - len(want))
+        head = next(i for i, ln in enumerate(got) if not ln.startswith("stream_create"))
+        print(f"{case}: begins with {'; '.join(got[:head])}; then {got[head].split()[0]}")
+        print(f"{case}: {len(got)} calls traced, golden {len(want)}: bad {bad}")
+        if bad:
+            for i in range(max(0, first - 3), min(max(len(got), len(want)), first + 6)):
+                print(f"  line {i + 1}: got  {got[i] if i < len(got) else '-'}\n  {' ' * len(str(i + 1))}       want {want[i] if i < len(want) else '-'}")
