@@ -9,6 +9,11 @@
 
 namespace at3 {
 
+// float -> int toward zero for an operand that may be a NaN or out of range, where a plain C cast is undefined (and x86 answers INT_MIN):
+// v_cvt_i32_f32's rule on the device - 0 for a NaN, saturation at INT_MIN / INT_MAX - and the same rule, spelled out, in the CPU harness
+// (tools/emu/hip/hip_runtime.h), so that both compile one meaning.
+__device__ __forceinline__ int f2i_rz(float x) { return __float2int_rz(x); }
+
 // PCM history kept per stream between calls: two full blocks (MDCT overlap source + look-behind of the
 // gain analysis) plus the 138-sample reach of the two-stage 48-tap QMF, rounded up.
 constexpr int kHist = 2304;

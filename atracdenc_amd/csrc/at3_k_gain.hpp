@@ -1087,11 +1087,14 @@ __device__ inline int relation_to_idx(float x)
         x = 1.0f / fmaxf(x, 0.00048828125f);
         return 4 + (int)first_set_bit((uint32_t)x);
     }
-    x = fminf(x, 16.0f);
-    return 4 - (int)first_set_bit((uint32_t)x);
+    // A NaN ratio (an envelope of NaNs or infinities) comes here: the reference's std::min(x, 16.0f) keeps it, and its conversion gives
+    // a word without a set bit on the x86-64 baseline - index 4 (oracle/at3_oracle.c: relation_to_idx). v_min_f32 would answer 16.
+    x = (16.0f < x) ? 16.0f : x;
+    return 4 - (int)first_set_bit((uint32_t)at3::f2i_rz(x));   // (v_cvt_i32_f32: 0 for a NaN; 1 .. 16 otherwise)
 }
 
 // atrac3denc.h:44-52 (1.0 / x in double then narrowed == correctly rounded float quotient)
+// (the operands of both casts are finite and in 1 .. 2048: fmaxf / fminf answer their constant for a NaN, which is the oracle's statement too)
 __device__ inline int relation_to_idx_hdr(float x)
 {
     if (x <= 0.5f) {

@@ -57,6 +57,11 @@ struct at3hip_ctx : at3host::EngineBase {
     at3hip_config cfg;
     int frame_sz = 0;
     int js = 0;
+    // The M/S matrixing (atrac3denc.cpp:665-677) runs for two input channels only. A one-channel context in a joint-stereo container takes
+    // its (x, x) pairs through the front half unmatrixed, as the reference does: (x + x) * 0.5 is x only while x + x is finite, and a subband
+    // sample above FLT_MAX / 2 (input near +-FLT_MAX) would leave the front half as an infinity the reference never forms. The second
+    // channel is then a copy of the first; the rate / pack kernel replaces its sound unit by the empty element either way (mono_js).
+    int ms = 0;
     // The back half of call N only consumes what the front half of call N produced (spectra, curves, energy scales),
     // and the front half of call N+1 only depends on the front half of call N (carried state): the two halves run on
     // HIP streams of their own (three with gain control, see mid_stream below), buffers that cross between them are double-buffered by call parity, and consecutive calls overlap.
@@ -391,6 +396,7 @@ int at3hip_create(const at3hip_config* cfg, at3hip_ctx** out)
         while (idx < 7 && kContainer[idx].bitrate < br) ++idx;  // lower_bound, atrac3.cpp:47-53
         c->frame_sz = kContainer[idx].frame_sz;
         c->js = kContainer[idx].js;
+        c->ms = c->js && cfg->channels == 2;
 
         // All streams are made before any event, table or buffer, in this order.
         if (hipStreamCreateWithPriority(&c->back_stream, hipStreamNonBlocking, prio_hi) != hipSuccess) return AT3HIP_EDEVICE;
@@ -766,7 +772,7 @@ void launch_qmf_sub_priming(at3hip_ctx* c, const EncodeCall& k)
     fp.sub_tail = c->d_sub_tail;
     fp.n_blocks = k.n_blocks;
     fp.f0 = k.f0;
-    fp.js = c->js;
+    fp.js = c->ms;
     launch_qmf_sub(c, k, fp);
 }
 
@@ -788,7 +794,7 @@ FrontParams front_params(at3hip_ctx* c, const EncodeCall& k)
     fp.frame_runs = cut.runs;
     fp.chain = cut.chain;
     fp.sub_runs = 0;
-    fp.js = c->js;
+    fp.js = c->ms;
     return fp;
 }
 
@@ -803,17 +809,17 @@ void launch_mdct_sub(at3hip_ctx* c, const EncodeCall& k)
     mp.specs = k.d_specs;
     mp.n_blocks = k.n_blocks;
     mp.f0 = k.f0;
-    mp.js = c->js;
+    mp.js = c->ms;
     mp.frame_runs = pick_runs(c, k.n_out, c->wgs_per_cu_mdct, 0.3);
     mp.n_waves = S * 2 * mp.frame_runs;
     // three wavefronts per workgroup (20.3 KB) where k_gain_analysis' launch is padded to fat slots - a light-stage workgroup must fit the slot
     // one retiring analysis workgroup frees (analysis_lds_pad) -, four (25.5 KB; one table copy per four runs) where it fills the chip unpadded
     const bool fat_slots = c->gain_form != AT3HIP_GAIN_FORM_ONE_WAVE && analysis_lds_pad(c, (long long)S * k.n_out * 6) != 0;   // (the one-wavefront form's launch has no fat slots)
     if (fat_slots) {
-        if (c->js) hipLaunchKernelGGL((k_mdct_sub<true, 3>), dim3((unsigned)((mp.n_waves + 2) / 3)), dim3(192), 0, k.md, mp, c->d_tables);
+        if (c->ms) hipLaunchKernelGGL((k_mdct_sub<true, 3>), dim3((unsigned)((mp.n_waves + 2) / 3)), dim3(192), 0, k.md, mp, c->d_tables);
         else hipLaunchKernelGGL((k_mdct_sub<false, 3>), dim3((unsigned)((mp.n_waves + 2) / 3)), dim3(192), 0, k.md, mp, c->d_tables);
     } else {
-        if (c->js) hipLaunchKernelGGL((k_mdct_sub<true, 4>), dim3((unsigned)((mp.n_waves + 3) / 4)), dim3(256), 0, k.md, mp, c->d_tables);
+        if (c->ms) hipLaunchKernelGGL((k_mdct_sub<true, 4>), dim3((unsigned)((mp.n_waves + 3) / 4)), dim3(256), 0, k.md, mp, c->d_tables);
         else hipLaunchKernelGGL((k_mdct_sub<false, 4>), dim3((unsigned)((mp.n_waves + 3) / 4)), dim3(256), 0, k.md, mp, c->d_tables);
     }
 }
@@ -863,7 +869,7 @@ int front_with_gain(at3hip_ctx* c, const EncodeCall& k)
     gp.curves = k.d_curves;
     gp.n_blocks = k.n_blocks;
     gp.f0 = k.f0;
-    gp.js = c->js;
+    gp.js = c->ms;
     gp.n_streams = S;
     gp.literal = c->flat_literal;
     launch_qmf_sub(c, k, fp);

@@ -53,6 +53,12 @@ const char* at1hip_last_error(const at1hip_ctx* ctx);
 
 /* Replaces: n_blocks invocations of the lambda of TAtrac1Encoder::GetLambda per stream.
  *   pcm        [n_streams][n_blocks][512][channels] float32, interleaved, +-1.0 (pcmengin.h:173-184)
+ *              Any float is accepted (NaN, +-infinity, +-FLT_MAX, overflowing or subnormal samples): the call succeeds, the sound
+ *              units and the loudness tap of every stream are bit for bit the reference's for that stream alone (no exception
+ *              known: tests/test_float_domain_gpu.py), and no other stream of the call is touched. A NaN or an infinity changes
+ *              the 2 or 3 sound units whose QMF history and MDCT overlap hold it; a block of finite samples of 1e15 and more also
+ *              raises the carried loudness, and with window_auto every later sound unit of that stream differs from the clean
+ *              encode until at1hip_reset.
  *   out_frames [n_streams][n_blocks][channels][212] bytes: the buffers handed to ICompressedOutput::WriteFrame, in the
  *              reference's order (channel 0 then channel 1 of each block, atrac1denc.cpp:249-251)
  * flags: AT3HIP_PCM_ON_DEVICE / AT3HIP_OUT_ON_DEVICE as for at3hip_encode; AT3HIP_ASYNC only queues the call (buffers must stay

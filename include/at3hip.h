@@ -105,6 +105,17 @@ const char* at3hip_last_error(const at3hip_ctx* ctx);
  * Stream state (QMF history, look-ahead, MDCT overlap, gain-curve context, loudness) is carried
  * between calls, so a stream may be fed in pieces. As in the reference the very first block of a
  * stream only primes the look-ahead (LOOK_AHEAD, atrac3denc.cpp:715-718): the first call returns
+ *
+ * SAMPLES OUTSIDE THE FLOAT DOMAIN. Any float is accepted: NaN of any payload, +-infinity, +-FLT_MAX, values whose squares or
+ * filter sums overflow float32, subnormals. The call succeeds, touches no memory outside its buffers, and every stream's frames
+ * and the counters of at3hip_get_counters are, bit for bit, what the reference encoder (x86-64 baseline build) produces for
+ * that stream alone - no exception is known (tests/test_float_domain_gpu.py, tests/float_domain_lib.py: EXCEPTIONS is empty).
+ * Such a sample never reaches another stream of the call. Within its own stream the reference's damage is the contract:
+ *   - a NaN or an infinity changes the frames whose QMF history, look-ahead or MDCT overlap contain it - 3 to 5 frames around
+ *     the block (measured on the reference: DESIGN.md section 16) - and nothing later;
+ *   - a FINITE sample large enough to make a spectrum overflow (from about 1e15) also raises the carried track loudness
+ *     (atrac3denc.cpp:833-841), which decays by 0.98 per frame: every later frame of that stream differs from the clean encode
+ *     until at3hip_reset. Scale overflows and clipped values are counted as for any input above full scale.
  * n_blocks-1 frames per stream, later calls n_blocks. */
 int at3hip_encode(at3hip_ctx* ctx, const float* pcm, int32_t n_blocks, uint8_t* out_frames,
                   int32_t* n_frames_out, uint32_t flags);

@@ -98,6 +98,13 @@ int at3hip_loudness_sync(at3hip_loudness* l);
 /* Queue this meter's work on a caller-provided hipStream_t (NULL = its own stream), as at3hip_decoder_set_stream. */
 int at3hip_loudness_set_stream(at3hip_loudness* l, void* hip_stream);
 
+/* SAMPLES OUTSIDE THE FLOAT DOMAIN. Any float is accepted, and every field of the result is the definition's (doubles and floats as
+ * bit patterns; a NaN where the definition gives a NaN, sign and payload unspecified): tests/test_float_domain_gpu.py, no exception
+ * known. A NaN or an infinity makes NaN the hop sums of the hop that holds it and of the two hops that warm up on it; blocks with a
+ * NaN sum fail the gates and are left out, later hops are exact. sample_peak and true_peak compare magnitudes as bit patterns, so
+ * a NaN in a channel IS that channel's peak (at3hip_loudness_gain then returns what the definition computes from it: check the
+ * peaks with isfinite before trusting a gain). Finite samples whose squares pass DBL_MAX cannot occur; those that are merely huge
+ * give a huge, finite loudness. at3hip_loudness_apply is one float multiply per sample. No stream affects another. */
 /*   in [n_streams][n_in][channels] float32, 0 <= n_in <= max_in
  * flags: AT3HIP_PCM_ON_DEVICE (in is device memory), AT3HIP_ASYNC (only queue the call: in stays valid until
  * at3hip_loudness_sync or at3hip_loudness_finish). A call that would complete more than max_hops hops is AT3HIP_EINVAL. */

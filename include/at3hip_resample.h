@@ -63,6 +63,11 @@ int at3hip_resampler_reset(at3hip_resampler* r);
 /* Output capacity per stream of one process or flush call: max(ceil(max_in L / M), ceil((K/2) L / M)). */
 int32_t at3hip_resampler_max_out(const at3hip_resampler* r);
 
+/* SAMPLES OUTSIDE THE FLOAT DOMAIN. Any float is accepted. An output is the definition's sum over K input samples in float32, so a NaN
+ * or a sum that passes through inf - inf makes NaN the outputs whose K taps reach it (of unspecified sign and payload), an infinity
+ * or an overflowing sum gives infinities, and the first output whose taps lie past the sample is exact again; every other output,
+ * and every other stream of the call, has the definition's bits (tests/test_float_domain_gpu.py; no exception known). With
+ * AT3HIP_RESAMPLE_OUT_S16 a NaN output is written as 0 and an infinite one as +-32767. */
 /*   in  [n_streams][n_in][channels] float32, 0 <= n_in <= max_in
  *   out [n_streams][*n_out][channels] float32 (room for at3hip_resampler_max_out samples per stream)
  * flags: AT3HIP_PCM_ON_DEVICE (in is device memory), AT3HIP_OUT_ON_DEVICE, AT3HIP_ASYNC (only queue the call: in stays valid

@@ -42,6 +42,11 @@ int at3phip_reset(at3phip_ctx* ctx);
 
 /* Replaces: at3plus_pqf_do_analyse(ctx, in, out) (atrac/atrac3plus_pqf/atrac3plus_pqf.c:130-147) per channel and frame.
  *   pcm   [n_streams][n_frames][2048][channels] float32 interleaved (the `data` of EncodeFrame, at3p.cpp:93-97)
+ *         Any float is accepted (NaN, +-infinity, +-FLT_MAX, overflowing or subnormal samples): subbands, spectra and the frames
+ *         of at3phip_encode_frames are those of the reference's PQF, MDCT and writer for that stream alone (floats as bit patterns;
+ *         where they are NaN, a NaN of unspecified sign and payload), no other stream of the call is touched, and the stream is
+ *         itself again with the first frame whose PQF history (one frame) and MDCT overlap no longer hold the sample: 2 or 3
+ *         frames in all. No exception is known (tests/test_float_domain_gpu.py).
  *   bands [n_streams][n_frames][channels][16][128] float32: 16 subbands x 128 samples
  * flags: AT3HIP_PCM_ON_DEVICE / AT3HIP_OUT_ON_DEVICE. The 368-sample filter history is carried between calls. */
 int at3phip_pqf_analyse(at3phip_ctx* ctx, const float* pcm, int32_t n_frames, float* bands, uint32_t flags);

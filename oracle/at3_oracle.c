@@ -678,13 +678,19 @@ static uint16_t first_set_bit(uint32_t x)
     return r;
 }
 
-/* transient_detector.cpp:141-149 (the static variant used inside CalcCurve) */
+/* transient_detector.cpp:141-149 (the static variant used inside CalcCurve).
+ * A NaN ratio (an all-NaN or all-infinite envelope: inf / inf) takes the second branch, where std::min(x, 16.0f) = (16.0f < x) ? 16.0f : x
+ * keeps it - fminf would answer 16 and index 0 - and static_cast<uint32_t>(NaN) is then what the reference build makes of it: the x86-64
+ * baseline converts through the 64-bit cvttss2si, whose "integer indefinite" 0x8000000000000000 has the low word 0, i.e. no set bit and
+ * index 4, "no gain change". Stated here without the cast, which is undefined in C. Every other value is in range: the first branch's
+ * operand is at most 2048 (x = -inf included), the second's at most 16. */
 static uint16_t relation_to_idx(float x)
 {
     if (x <= 0.5f) {
         x = 1.0f / fmaxf(x, 0.00048828125f);
         return 4u + first_set_bit((uint32_t)x);
     } else {
+        if (x != x) return 4u;
         x = fminf(x, 16.0f);
         return 4u - first_set_bit((uint32_t)x);
     }

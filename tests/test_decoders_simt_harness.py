@@ -38,7 +38,8 @@ ENV = {"default": {}, "high": {"EMU_FENCE": "high"}, "low": {"EMU_FENCE": "low"}
 JOBS = ([(m, "at1_fuzz:2") for m in ("default", "reverse")] + [("default", c) for c in LARGE + ["at1_state"]] +
         [(m, c) for c in FUZZ[1:] + GOLDENS + RESAMPLE for m in ("default", "reverse")] +
         [(m, c) for c in GOLDENS + RESAMPLE + SINGLE for m in ("high", "low")] +
-        [("default", c) for c in ("at3_state", "at3p_state", "at1_s16", "at3_s16", "at3p_s16")])
+        [("default", c) for c in ("at3_state", "at3p_state", "at1_s16", "at3_s16", "at3p_s16")] +
+        [(m, "resample_domain") for m in ("high", "low", "reverse")])
 assert len(set(JOBS)) == len(JOBS)
 
 
@@ -113,6 +114,14 @@ def test_resampler_bit_identical_to_restatement(children, case, n):
     several tiles that begins and ends inside a q, so that tile 0 begins before n0 and the last tile ends after n_end;
     caller-owned buffers of exact size; eleven streams."""
     check(children, "default", case, n)
+
+
+@pytest.mark.parametrize("mode", ["high", "low", "reverse"])
+def test_resampler_float_domain(children, mode):
+    """resample_domain: tests/float_domain_lib.py's streams (NaN, infinities, +-FLT_MAX, overflowing and subnormal samples) side
+    by side, 48000 <-> 44100, 1 and 2 channels, float and 16-bit output (a NaN gives 0, an infinity +-32767), against the
+    restatement of each stream alone: with guard pages on either side of every buffer, and in reversed wavefront order."""
+    check(children, mode, "resample_domain", 8)
 
 
 # ---- 6. guard pages -----------------------------------------------------------------------------------------------------------

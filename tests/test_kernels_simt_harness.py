@@ -149,3 +149,52 @@ def test_atrac3plus_front_kernels_reversed_wavefront_order(reversed_runs):
 
 def test_atrac3plus_frame_kernels_reversed_wavefront_order(reversed_runs):
     _assert_clean(reversed_runs.output("run_emu_at3p_write.py"), 26)
+
+
+# ---- the edges of the float domain --------------------------------------------------------------------------------------------
+# tests/float_domain_lib.py's streams (NaN, infinities, +-FLT_MAX, samples whose energy sums overflow f32, subnormals in block 3 of
+# 12), one stream per pattern side by side, each against the oracle's encode of that stream alone. The harness converts float to
+# int as the hardware does (tools/emu/hip/hip_runtime.h), and every buffer ends at a guard page (EMU_FENCE=high) in the first
+# order: an index that leaves its table ends the child with a signal here, not a GPU. tests/test_float_domain_gpu.py runs what
+# has passed here.
+DOMAIN_AT3 = ("domain:clean,nan1,inf_pair,max1", "domain:nan_block,max_alt,inf_left,mixed", "domain:nan_bits,e19_alt,e15,subnormal")
+DOMAIN_MODES = {"fence": {"EMU_FENCE": "high"}, "reverse": {"EMU_ORDER": "reverse"}}
+
+
+@pytest.fixture(scope="module")
+def domain_runs(harness):
+    jobs = {}
+    for mode, env in DOMAIN_MODES.items():
+        jobs[mode, "run_emu_at1.py"] = ("run_emu_at1.py", ["--nobuild", "domain"], env)
+        for part in DOMAIN_AT3:
+            jobs[mode, part] = ("run_emu.py", ["--strict", "--nobuild", part], env)
+        for script in ("run_emu_at3p.py", "run_emu_at3p_write.py"):
+            jobs[mode, script] = (script, ["--nobuild", "domain"], env)
+    c = Children(jobs)
+    yield c
+    c.close()
+
+
+@pytest.mark.parametrize("mode", list(DOMAIN_MODES))
+def test_atrac3_float_domain(domain_runs, mode):
+    """LP2 and LP4, every tool and none, whole and as 5 + 1 + 6 blocks: frames and overflow counters; the one-channel joint-stereo
+    context on clean, nan1 and max_alt (a subband sample above FLT_MAX / 2 must not pass through the M/S matrixing)."""
+    n = 0
+    for part in DOMAIN_AT3:
+        out = domain_runs.output((mode, part))
+        _assert_clean(out, 16)
+        n += len(re.findall(r"ch=1 split", out))
+    assert n == 4   # (both parts that hold one of the one-channel patterns ran that case, whole and split)
+
+
+@pytest.mark.parametrize("mode", list(DOMAIN_MODES))
+def test_atrac1_float_domain(domain_runs, mode):
+    """auto and short windows x 1 and 2 channels, whole and as 10 + 2 + 12 blocks: sound units and the loudness tap"""
+    _assert_clean(domain_runs.output((mode, "run_emu_at1.py")), 16)
+
+
+@pytest.mark.parametrize("mode", list(DOMAIN_MODES))
+def test_atrac3plus_float_domain(domain_runs, mode):
+    """subbands and spectra of pqf_mdct, and the frames of encode_frames whole and as 2 + 1 + 3, mono and stereo"""
+    _assert_clean(domain_runs.output((mode, "run_emu_at3p.py")), 4)
+    _assert_clean(domain_runs.output((mode, "run_emu_at3p_write.py")), 4)

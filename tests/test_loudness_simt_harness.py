@@ -15,7 +15,9 @@ pytestmark = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's 
 
 CASES = {"meter:1": 8, "meter:2": 8, "edges": 7, "scale": 1}   # comparisons per case
 ENV = {"default": {}, "high": {"EMU_FENCE": "high"}, "low": {"EMU_FENCE": "low"}, "reverse": {"EMU_ORDER": "reverse"}}
-JOBS = [(m, c) for c in CASES for m in ENV]
+DOMAIN = {"domain:1": 6, "domain:2": 6}   # tests/float_domain_lib.py's streams: NaN, infinities, +-FLT_MAX, overflow, subnormals
+JOBS = [(m, c) for c in DOMAIN for m in ("high", "reverse")] + [(m, c) for c in CASES for m in ENV]
+CASES_ALL = dict(CASES, **DOMAIN)
 
 
 @pytest.fixture(scope="module")
@@ -29,7 +31,7 @@ def children():
 def check(children, mode, case):
     out = children.output((mode, case))
     assert f"\n{case} done" in out, out[-4000:]
-    assert_clean(out, CASES[case])
+    assert_clean(out, CASES_ALL[case])
 
 
 @pytest.mark.parametrize("case", list(CASES))
@@ -50,3 +52,12 @@ def test_guard_pages(children, fence, case):
 @pytest.mark.parametrize("case", list(CASES))
 def test_reversed_wavefront_order(children, case):
     check(children, "reverse", case)
+
+
+@pytest.mark.parametrize("mode", ["high", "reverse"])
+@pytest.mark.parametrize("case", list(DOMAIN))
+def test_float_domain(children, mode, case):
+    """domain:C: one stream per pattern of tests/float_domain_lib.py side by side, 1.2 s each, true peak on, one call and three:
+    hop sums, every field of the results and apply's samples against the restatement of each stream alone (floats as bit
+    patterns, a NaN against a NaN), with a guard page after every buffer, and in reversed wavefront order."""
+    check(children, mode, case)

@@ -81,7 +81,11 @@ static inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4);
 static inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 static inline unsigned int __umul24(unsigned int a, unsigned int b) { return (a & 0xffffffu) * (b & 0xffffffu); }
 static inline int min(int a, int b) { return b < a ? b : a; }
-static inline int __float2int_rn(float f) { return (int)lrintf(f); }
+// float -> int as the hardware converts (v_rndne_f32 + v_cvt_i32_f32): round to nearest even, NaN -> 0, saturation at
+// INT_MIN / INT_MAX. (x86's cvtss2si answers INT_MIN for a NaN and for every value out of range: the harness must not.)
+static inline int emu_cvt_i32_f32(float f) { return f != f ? 0 : f >= 2147483648.0f ? INT32_MAX : f <= -2147483648.0f ? INT32_MIN : (int)f; }
+static inline int __float2int_rn(float f) { return emu_cvt_i32_f32(nearbyintf(f)); }
+static inline int __float2int_rz(float f) { return emu_cvt_i32_f32(f); }
 static inline long long __double_as_longlong(double d) { long long v; memcpy(&v, &d, 8); return v; }
 static inline double __longlong_as_double(long long v) { double d; memcpy(&d, &v, 8); return d; }
 template <typename T, typename U> static inline T atomicAdd(T* p, U v) { T o = *p; *p = o + (T)v; return o; }

@@ -26,10 +26,32 @@ def build(strict=False):
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3_tables.cpp"),
                            os.path.join(ROOT, "tools/emu/emu_runtime.cpp")])
 
+def domain(arg):
+    # domain[:pattern,...]: tests/float_domain_lib.py's streams (NaN, infinities, +-FLT_MAX, overflowing and subnormal samples in block 3
+    # of 12), one stream per pattern side by side in one context, whole and as 5 + 1 + 6 blocks, each stream against the oracle's encode
+    # of that stream alone; the one-channel joint-stereo case on its own patterns
+    import float_domain_lib as FD
+    want = tuple(arg.split(":")[1].split(",")) if ":" in arg else None
+    for br, ng, nt, nch, names in FD.AT3_CASES:
+        names = tuple(n for n in names if want is None or n in want)
+        if not names: continue
+        exp, counts = FD.at3_expect(br, ng, nt, nch, names)
+        clean = FD.at3_expect(br, ng, nt, nch, ("clean",))[0][0]
+        for split in (None, FD.AT3_SPLIT):
+            t = time.time()
+            got, cnt = FD.at3_run(EMU, br, ng, nt, nch, names, split)
+            bad = FD.rows_bad(got, exp, "at3", names, clean)
+            print(f"domain   br={br} nogain={ng} notonal={nt} ch={nch} split={split}: {len(names)} streams, mismatching frames {len(bad)} {bad} ({time.time()-t:.1f}s)")
+            print(f"domain   overflow counters {cnt} (oracle {tuple(counts.sum(0))}): bad {int(cnt != tuple(counts.sum(0)))}", flush=True)
+
 if __name__ == "__main__":
     strict = "--strict" in sys.argv
     if strict: os.environ["EMU_STRICT"] = "1"
     if "--nobuild" not in sys.argv: build(strict)
+    for a in [a for a in sys.argv[1:] if a.split(":")[0] == "domain"]:
+        domain(a)
+        sys.argv.remove(a)
+        if not [a for a in sys.argv[1:] if not a.startswith("--")]: sys.exit(0)
     gain_form = next((int(a.split("=")[1]) for a in sys.argv[1:] if a.startswith("--gain-form=")), 0)   # AT3HIP_OPT_GAIN_FORM
     names = [a for a in sys.argv[1:] if not a.startswith("--")] or ["noise", "burst", "tones", "silence", "mix", "stress"]
     nb = 6

@@ -8,8 +8,25 @@ from at3_testlib import SIGNALS, AT1_MODES, at1_blocks, at1_oracle_encode, pcm_s
 from atracdenc_amd.binding import At1Hip
 import run_emu
 
+def domain():
+    # tests/float_domain_lib.py's streams (NaN, infinities, +-FLT_MAX, overflowing and subnormal samples), one stream per pattern side by
+    # side, whole and as 10 + 2 + 12 blocks: sound units and the loudness tap against the oracle's encode of each stream alone
+    import float_domain_lib as FD
+    for mode, nch in FD.AT1_CASES:
+        exp, eloud = FD.at1_expect(mode, nch)
+        clean = exp[FD.NAMES.index("clean")]
+        for split in (None, FD.AT1_SPLIT):
+            t = time.time()
+            got, loud = FD.at1_run(run_emu.EMU, mode, nch, split=split)
+            bad = FD.rows_bad(got, exp, "at1", FD.NAMES, clean)
+            lbad = [n for i, n in enumerate(FD.NAMES) if ("at1", n) not in FD.EXCEPTIONS and FD.floats_match(loud[i], eloud[i]).any()]
+            print(f"domain  nch={nch} {mode:10s} split={split}: frames bad {len(bad)} {bad} loud bad {len(lbad)} {lbad} ({time.time()-t:.1f}s)", flush=True)
+
 if __name__ == "__main__":
     if "--nobuild" not in sys.argv: run_emu.build()
+    if "domain" in sys.argv:
+        domain()
+        sys.exit(0)
     names = [a for a in sys.argv[1:] if not a.startswith("--")] or ["mix", "burst", "stress"]
     gens = dict(SIGNALS); gens["stress"] = pcm_stress
     nb = 6

@@ -8,8 +8,32 @@ from at3_testlib import at3p_signal, at3p_pqf, at3p_mdct
 from atracdenc_amd.binding import At3pHip
 import run_emu
 
+def domain():
+    # tests/float_domain_lib.py's streams through at3phip_pqf_mdct with the residual scale: subbands and spectra against the oracle (floats by
+    # FD.floats_match: bit patterns, a NaN against a NaN)
+    import float_domain_lib as FD
+    for nch in (2, 1):
+        t = time.time()
+        pcm = FD.at3p_batch(nch)
+        enc = At3pHip(n_streams=pcm.shape[0], max_frames=pcm.shape[1], channels=nch, lib_path=run_emu.EMU)
+        parts = [enc.pqf_mdct(pcm[:, a:b], None, True) for a, b in ((0, 2), (2, 6))]
+        enc.close()
+        bands = np.concatenate([p[0] for p in parts], axis=1); specs = np.concatenate([p[1] for p in parts], axis=1)
+        bad_b, bad_s = [], []
+        for s, name in enumerate(FD.NAMES):
+            for c in range(nch):
+                eb = at3p_pqf(np.ascontiguousarray(pcm[s, :, :, c]))
+                with np.errstate(all="ignore"):
+                    es = at3p_mdct((eb.astype(np.float64) / (32768.0 / 1.122018)).astype(np.float32))
+                if FD.floats_match(bands[s, :, c], eb).any(): bad_b.append(name)
+                if FD.floats_match(specs[s, :, c], es).any(): bad_s.append(name)
+        print(f"domain nch={nch}: bands bad {len(bad_b)} {bad_b} specs bad {len(bad_s)} {bad_s} ({time.time()-t:.1f}s)", flush=True)
+
 if __name__ == "__main__":
     if "--nobuild" not in sys.argv: run_emu.build()
+    if "domain" in sys.argv:
+        domain()
+        sys.exit(0)
     nf = 5
     rng = np.random.RandomState(2)
     for nch in (2, 1):

@@ -8,8 +8,22 @@ from at3_testlib import at3p_specs, at3p_write_frames, at3p_signal
 from atracdenc_amd.binding import At3pHip
 import run_emu
 
+def domain():
+    # tests/float_domain_lib.py's streams through at3phip_encode_frames, whole and as 2 + 1 + 3 frames, against the oracle's PQF -> MDCT -> writer
+    import float_domain_lib as FD
+    for nch in (2, 1):
+        exp = FD.at3p_expect(nch)
+        clean = exp[FD.NAMES.index("clean")]
+        for split in (None, FD.AT3P_SPLIT):
+            t = time.time()
+            bad = FD.rows_bad(FD.at3p_run(run_emu.EMU, nch, split=split), exp, "at3p", FD.NAMES, clean)
+            print(f"domain nch={nch} split={split}: mismatching frames {len(bad)} {bad} ({time.time()-t:.1f}s)", flush=True)
+
 if __name__ == "__main__":
     if "--nobuild" not in sys.argv: run_emu.build()
+    if "domain" in sys.argv:
+        domain()
+        sys.exit(0)
     nf = 4
     rng = np.random.RandomState(4)
     for nch in (2, 1):

@@ -633,6 +633,21 @@ def resample_edges():
     report("resample 11 streams", sum(not RS.bits_equal(got[i], restated(pair, xs[i], 2)) for i in range(11)), t0)
 
 
+def resample_domain():
+    """tests/float_domain_lib.py's streams (NaN, infinities, +-FLT_MAX, overflowing and subnormal samples) side by side: both directions between
+    48000 and 44100, 1 and 2 channels, float and 16-bit output, one call and three, against the restatement of each stream alone"""
+    import float_domain_lib as FD
+    for pair in FD.RESAMPLE_PAIRS:
+        for channels in (1, 2):
+            exp = FD.resample_expect(pair, channels)
+            for s16 in (False, True):
+                t0 = time.time()
+                bad = 0
+                for cuts in ((FD.RESAMPLE_T,), FD.RESAMPLE_CUTS):
+                    bad += len(FD.resample_bad(FD.resample_run(EMU, pair, channels, s16, cuts=cuts), exp, s16))
+                report(f"resample domain {pair[0]}-{pair[1]} ch{channels} s16={int(s16)}", bad, t0)
+
+
 # cases that take an argument are named case:argument (a channel count, or which half of the rows / pairs: 0 or 1)
 CASES = {"at1_goldens": at1_goldens, "at3_goldens": at3_goldens, "at3p_goldens": at3p_goldens, "at3p_tonal_goldens": at3p_tonal_goldens,
          "at1_fuzz:1": at1_fuzz, "at1_fuzz:2": at1_fuzz, "at3_fuzz:0": at3_fuzz, "at3_fuzz:1": at3_fuzz,
@@ -642,7 +657,8 @@ CASES = {"at1_goldens": at1_goldens, "at3_goldens": at3_goldens, "at3p_goldens":
          "at1_state": at1_state, "at3_state": at3_state, "at3p_state": at3p_state,
          "at1_s16": at1_s16, "at3_s16": at3_s16, "at3p_s16": at3p_s16,
          "at1_single": at1_single, "at3_single": at3_single, "at3p_single": at3p_single,
-         "resample_pairs:0": resample_pairs, "resample_pairs:1": resample_pairs, "resample_edges": resample_edges}
+         "resample_pairs:0": resample_pairs, "resample_pairs:1": resample_pairs, "resample_edges": resample_edges,
+         "resample_domain": resample_domain}
 
 if __name__ == "__main__":
     names = [a for a in sys.argv[1:] if not a.startswith("--")]

@@ -113,7 +113,19 @@ def scale():
     report("loudness apply", bad, t0)
 
 
-CASES = {"meter:1": meter, "meter:2": meter, "edges": edges, "scale": scale}
+def domain(channels):
+    """tests/float_domain_lib.py's streams (NaN, infinities, +-FLT_MAX, overflowing and subnormal samples) side by side, 1.2 s each, true peak
+    on, one call and three: hop sums, every field of the results and apply's samples against the restatement of each stream alone"""
+    import float_domain_lib as FD
+    exp = FD.meter_expect(channels)
+    for cuts in ((FD.METER_T,), FD.METER_CUTS):
+        t0 = time.time()
+        bad = FD.meter_bad(FD.meter_run(EMU, channels, cuts=cuts), exp)
+        for what in ("z", "results", "apply"):
+            report(f"loudness domain ch{channels} cuts {cuts} {what} {bad[what]}", len(bad[what]), t0)
+
+
+CASES = {"domain:1": domain, "domain:2": domain, "meter:1": meter, "meter:2": meter, "edges": edges, "scale": scale}
 
 if __name__ == "__main__":
     names = [a for a in sys.argv[1:] if not a.startswith("--")]
