@@ -39,41 +39,10 @@ class Timings(ctypes.Structure):
                                                "alloc_ms")] + [("qmf_mdct_launches", ctypes.c_int32)]
 
 
-SYMBOLS = ["at3hip_encode_s16", "at3hip_create", "at3hip_destroy", "at3hip_frame_size", "at3hip_joint_stereo", "at3hip_last_error",
-           "at3hip_encode", "at3hip_reset", "at3hip_mdct", "at3hip_qmf_mdct", "at3hip_get_timings",
-           "at3hip_set_stream", "at3hip_version", "at3hip_sync", "at3hip_get_timings_ago", "at3hip_read_tap",
-           "at3hip_mdct_levels", "at3hip_gain_energy_scale", "at3hip_set_option", "at3hip_host_tables", "at3hip_host_alloc",
-           "at3hip_host_free", "at3hip_wait_input", "at3hip_wait_frames", "at3hip_get_counters", "at3hip_device_numa_node",
-           # the ATRAC3 decoder
-           "at3hip_decoder_create", "at3hip_decoder_destroy", "at3hip_decoder_last_error", "at3hip_decode", "at3hip_decoder_sync",
-           "at3hip_decoder_reset", "at3hip_decoder_get_counters", "at3hip_decoder_set_stream",
-           # the resampler (include/at3hip_resample.h, listed in at3hip.h's version notes)
-           "at3hip_resampler_create", "at3hip_resampler_destroy", "at3hip_resampler_last_error", "at3hip_resampler_reset",
-           "at3hip_resampler_max_out", "at3hip_resampler_process", "at3hip_resampler_flush", "at3hip_resampler_sync",
-           "at3hip_resampler_set_stream", "at3hip_resampler_shape", "at3hip_resampler_host_tables",
-           # the loudness and true-peak meter (include/at3hip_loudness.h, listed in at3hip.h's version notes)
-           "at3hip_loudness_create", "at3hip_loudness_destroy", "at3hip_loudness_last_error", "at3hip_loudness_reset",
-           "at3hip_loudness_sync", "at3hip_loudness_set_stream", "at3hip_loudness_process", "at3hip_loudness_finish",
-           "at3hip_loudness_read_hops", "at3hip_loudness_apply", "at3hip_loudness_gate", "at3hip_loudness_gain",
-           # 16-bit PCM input of the resampler and the meter (listed in at3hip.h's version notes)
-           "at3hip_resampler_process_s16", "at3hip_loudness_process_s16", "at3hip_loudness_apply_s16"]
 AT3HIP_DECODE_S16 = 8
 AT3HIP_RESAMPLE_OUT_S16 = 8                        # include/at3hip_resample.h: 16-bit output of the resampler
-# include/at1hip.h
-AT1_SYMBOLS = ["at1hip_create", "at1hip_destroy", "at1hip_last_error", "at1hip_encode", "at1hip_reset", "at1hip_get_timings",
-               "at1hip_read_tap", "at1hip_host_tables", "at1hip_sync", "at1hip_encode_short",
-               # the decoder (ABI 1.6)
-               "at1hip_decoder_create", "at1hip_decoder_destroy", "at1hip_decoder_last_error", "at1hip_decode", "at1hip_decoder_sync",
-               "at1hip_decoder_reset", "at1hip_decoder_get_counters", "at1hip_decoder_set_stream"]
-AT1HIP_DECODE_S16 = 8
-# include/at3phip.h
-AT3P_SYMBOLS = ["at3phip_create", "at3phip_destroy", "at3phip_last_error", "at3phip_reset", "at3phip_pqf_analyse", "at3phip_mdct",
-                "at3phip_pqf_mdct", "at3phip_get_timings", "at3phip_host_tables", "at3phip_write_frames", "at3phip_encode_frames",
-                "at3phip_get_write_timing", "at3phip_host_write_tables", "at3phip_sync", "at3phip_encode_frames_short",
-                "at3phip_decoder_create", "at3phip_decoder_destroy", "at3phip_decoder_last_error", "at3phip_decode",
-                "at3phip_decoder_sync", "at3phip_decoder_reset", "at3phip_decoder_get_counters", "at3phip_decoder_set_stream",
-                "at3phip_decoder_host_tables", "at3phip_decoder_host_tone_tables"]
-AT3PHIP_DECODE_S16 = 8
+AT1HIP_DECODE_S16 = 8                              # include/at1hip.h
+AT3PHIP_DECODE_S16 = 8                             # include/at3phip.h
 AT3PHIP_DECODE_TONES = 16
 AT3PHIP_DECODER_TABLES_BYTES = 67328
 AT3PHIP_DECODER_TONE_TABLES_BYTES = 9504
@@ -146,6 +115,77 @@ class At1Timings(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("total_ms", "front_ms", "scan_ms", "pack_ms")]
 
 
+_RC, _VP, _I32, _U32, _SZ, _STR = ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_char_p
+_P = ctypes.POINTER
+_I32P, _F32P, _RESP = _P(_I32), _P(ctypes.c_float), _P(LoudnessResult)
+# name -> (restype, argtypes) of every exported function: load_library applies it, the three symbol lists are its names
+PROTOTYPES = {
+    # include/at3hip.h: the ATRAC3 encoder
+    "at3hip_version": (_U32, []), "at3hip_device_numa_node": (_RC, [_I32]),
+    "at3hip_create": (_RC, [_P(Config), _P(_VP)]), "at3hip_destroy": (None, [_VP]), "at3hip_last_error": (_STR, [_VP]),
+    "at3hip_reset": (_RC, [_VP]), "at3hip_sync": (_RC, [_VP]), "at3hip_set_stream": (_RC, [_VP, _VP]),
+    "at3hip_frame_size": (_RC, [_VP]), "at3hip_joint_stereo": (_RC, [_VP]), "at3hip_set_option": (_RC, [_VP, _I32, _I32]),
+    "at3hip_encode": (_RC, [_VP, _VP, _I32, _VP, _I32P, _U32]), "at3hip_encode_s16": (_RC, [_VP, _VP, _I32, _VP, _I32P, _U32]),
+    "at3hip_wait_input": (_RC, [_VP, _I32]), "at3hip_wait_frames": (_RC, [_VP, _I32]),
+    "at3hip_mdct": (_RC, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _U32]),
+    "at3hip_mdct_levels": (_RC, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _U32]),
+    "at3hip_gain_energy_scale": (_RC, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _U32]),
+    "at3hip_qmf_mdct": (_RC, [_VP, _VP, _I32, _VP, _U32]), "at3hip_read_tap": (_RC, [_VP, _I32, _VP, _SZ]),
+    "at3hip_get_timings": (_RC, [_VP, _P(Timings)]), "at3hip_get_timings_ago": (_RC, [_VP, _I32, _P(Timings)]),
+    "at3hip_get_counters": (_RC, [_VP, _P(Counters), _I32]), "at3hip_host_tables": (_RC, [_VP, _SZ]),
+    "at3hip_host_alloc": (_RC, [_VP, _SZ, _P(_VP)]), "at3hip_host_free": (_RC, [_VP, _VP]),
+    # include/at3hip.h: the ATRAC3 decoder
+    "at3hip_decoder_create": (_RC, [_P(At3DecoderConfig), _P(_VP)]), "at3hip_decoder_destroy": (None, [_VP]),
+    "at3hip_decoder_last_error": (_STR, [_VP]), "at3hip_decoder_reset": (_RC, [_VP]), "at3hip_decoder_sync": (_RC, [_VP]),
+    "at3hip_decoder_set_stream": (_RC, [_VP, _VP]), "at3hip_decode": (_RC, [_VP, _VP, _I32, _VP, _U32]),
+    "at3hip_decoder_get_counters": (_RC, [_VP, _P(At3DecoderCounters), _I32]),
+    # include/at3hip_resample.h (listed in at3hip.h's version notes)
+    "at3hip_resampler_create": (_RC, [_P(ResamplerConfig), _P(_VP)]), "at3hip_resampler_destroy": (None, [_VP]),
+    "at3hip_resampler_last_error": (_STR, [_VP]), "at3hip_resampler_reset": (_RC, [_VP]), "at3hip_resampler_sync": (_RC, [_VP]),
+    "at3hip_resampler_set_stream": (_RC, [_VP, _VP]), "at3hip_resampler_max_out": (_I32, [_VP]),
+    "at3hip_resampler_process": (_RC, [_VP, _VP, _I32, _VP, _I32P, _U32]),
+    "at3hip_resampler_process_s16": (_RC, [_VP, _VP, _I32, _VP, _I32P, _U32]),
+    "at3hip_resampler_flush": (_RC, [_VP, _VP, _I32P, _U32]),
+    "at3hip_resampler_shape": (_RC, [_I32, _I32, _I32P, _I32P, _I32P]), "at3hip_resampler_host_tables": (_RC, [_I32, _I32, _VP, _SZ]),
+    # include/at3hip_loudness.h (listed in at3hip.h's version notes)
+    "at3hip_loudness_create": (_RC, [_P(LoudnessConfig), _P(_VP)]), "at3hip_loudness_destroy": (None, [_VP]),
+    "at3hip_loudness_last_error": (_STR, [_VP]), "at3hip_loudness_reset": (_RC, [_VP]), "at3hip_loudness_sync": (_RC, [_VP]),
+    "at3hip_loudness_set_stream": (_RC, [_VP, _VP]),
+    "at3hip_loudness_process": (_RC, [_VP, _VP, _I32, _U32]), "at3hip_loudness_process_s16": (_RC, [_VP, _VP, _I32, _U32]),
+    "at3hip_loudness_apply": (_RC, [_VP, _VP, _I32, _VP, _VP, _U32]), "at3hip_loudness_apply_s16": (_RC, [_VP, _VP, _I32, _VP, _VP, _U32]),
+    "at3hip_loudness_finish": (_RC, [_VP, _RESP]), "at3hip_loudness_read_hops": (_RC, [_VP, _I32, _VP, _SZ]),
+    "at3hip_loudness_gate": (_RC, [_VP, _I32, _I32, _RESP]), "at3hip_loudness_gain": (_RC, [_RESP, ctypes.c_double, ctypes.c_double, _F32P]),
+    # include/at1hip.h: the ATRAC1 encoder
+    "at1hip_create": (_RC, [_P(At1Config), _P(_VP)]), "at1hip_destroy": (None, [_VP]), "at1hip_last_error": (_STR, [_VP]),
+    "at1hip_reset": (_RC, [_VP]), "at1hip_sync": (_RC, [_VP]),
+    "at1hip_encode": (_RC, [_VP, _VP, _I32, _VP, _U32]), "at1hip_encode_short": (_RC, [_VP, _VP, _I32, _VP, _U32]),
+    "at1hip_get_timings": (_RC, [_VP, _P(At1Timings)]), "at1hip_read_tap": (_RC, [_VP, _I32, _VP, _SZ]),
+    "at1hip_host_tables": (_RC, [_VP, _SZ]),
+    # include/at1hip.h: the ATRAC1 decoder
+    "at1hip_decoder_create": (_RC, [_P(At1DecoderConfig), _P(_VP)]), "at1hip_decoder_destroy": (None, [_VP]),
+    "at1hip_decoder_last_error": (_STR, [_VP]), "at1hip_decoder_reset": (_RC, [_VP]), "at1hip_decoder_sync": (_RC, [_VP]),
+    "at1hip_decoder_set_stream": (_RC, [_VP, _VP]), "at1hip_decode": (_RC, [_VP, _VP, _I32, _VP, _U32]),
+    "at1hip_decoder_get_counters": (_RC, [_VP, _P(At1DecoderCounters), _I32]),
+    # include/at3phip.h: the ATRAC3plus encoder
+    "at3phip_create": (_RC, [_P(At3pConfig), _P(_VP)]), "at3phip_destroy": (None, [_VP]), "at3phip_last_error": (_STR, [_VP]),
+    "at3phip_reset": (_RC, [_VP]), "at3phip_sync": (_RC, [_VP]),
+    "at3phip_pqf_analyse": (_RC, [_VP, _VP, _I32, _VP, _U32]), "at3phip_mdct": (_RC, [_VP, _VP, _I32, _VP, _VP, _U32]),
+    "at3phip_pqf_mdct": (_RC, [_VP, _VP, _I32, _VP, _VP, _VP, _U32]), "at3phip_write_frames": (_RC, [_VP, _VP, _I32, _VP, _VP, _U32]),
+    "at3phip_encode_frames": (_RC, [_VP, _VP, _I32, _VP, _U32]), "at3phip_encode_frames_short": (_RC, [_VP, _VP, _I32, _VP, _U32]),
+    "at3phip_get_timings": (_RC, [_VP, _F32P, _F32P]), "at3phip_get_write_timing": (_RC, [_VP, _F32P]),
+    "at3phip_host_tables": (_RC, [_VP, _SZ]), "at3phip_host_write_tables": (_RC, [_VP, _SZ]),
+    # include/at3phip.h: the ATRAC3plus decoder
+    "at3phip_decoder_create": (_RC, [_P(At3pDecoderConfig), _P(_VP)]), "at3phip_decoder_destroy": (None, [_VP]),
+    "at3phip_decoder_last_error": (_STR, [_VP]), "at3phip_decoder_reset": (_RC, [_VP]), "at3phip_decoder_sync": (_RC, [_VP]),
+    "at3phip_decoder_set_stream": (_RC, [_VP, _VP]), "at3phip_decode": (_RC, [_VP, _VP, _I32, _VP, _U32]),
+    "at3phip_decoder_get_counters": (_RC, [_VP, _P(At3pDecoderCounters), _I32]),
+    "at3phip_decoder_host_tables": (_RC, [_VP, _SZ]), "at3phip_decoder_host_tone_tables": (_RC, [_VP, _SZ]),
+}
+SYMBOLS = [n for n in PROTOTYPES if n.startswith("at3hip_")]
+AT1_SYMBOLS = [n for n in PROTOTYPES if n.startswith("at1hip_")]
+AT3P_SYMBOLS = [n for n in PROTOTYPES if n.startswith("at3phip_")]
+
+
 def build_library(verbose=False):
     """Compile libat3hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fvisibility=hidden", "-fPIC", "-shared",
@@ -174,115 +214,15 @@ def load_library(path=None):
         raise At3HipError(f"{path} not found: build it with atracdenc_amd.build_library() / __graft_entry__.build(); "
                           "there is no CPU fallback")
     lib = ctypes.CDLL(path)
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
     lib.at3hip_version.restype = ctypes.c_uint32
     have = lib.at3hip_version()
     # same major number, and every entry point / option / wait depth this stub relies on (at3hip.h lists them per minor number)
     if have >> 16 != AT3HIP_VERSION >> 16 or have < AT3HIP_VERSION:
         raise At3HipError(f"{path} implements at3hip ABI {have >> 16}.{have & 0xffff}, this binding needs {AT3HIP_VERSION >> 16}.{AT3HIP_VERSION & 0xffff}: rebuild it")
-    lib.at3hip_create.argtypes = [ctypes.POINTER(Config), ctypes.POINTER(vp)]
-    lib.at3hip_create.restype = ctypes.c_int
-    lib.at3hip_destroy.argtypes = [vp]
-    lib.at3hip_destroy.restype = None
-    lib.at3hip_frame_size.argtypes = [vp]
-    lib.at3hip_joint_stereo.argtypes = [vp]
-    lib.at3hip_last_error.argtypes = [vp]
-    lib.at3hip_last_error.restype = ctypes.c_char_p
-    lib.at3hip_encode.argtypes = [vp, vp, i32, vp, ctypes.POINTER(i32), ctypes.c_uint32]
-    lib.at3hip_encode_s16.argtypes = [vp, vp, i32, vp, ctypes.POINTER(i32), ctypes.c_uint32]
-    lib.at3hip_reset.argtypes = [vp]
-    lib.at3hip_mdct.argtypes = [vp, vp, vp, vp, vp, vp, i32, ctypes.c_uint32]
-    lib.at3hip_mdct_levels.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, ctypes.c_uint32]
-    lib.at3hip_gain_energy_scale.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, ctypes.c_uint32]
-    lib.at3hip_qmf_mdct.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
-    lib.at3hip_get_timings.argtypes = [vp, ctypes.POINTER(Timings)]
-    lib.at3hip_set_stream.argtypes = [vp, vp]
-    lib.at3hip_sync.argtypes = [vp]
-    lib.at3hip_set_option.argtypes = [vp, i32, i32]
-    lib.at3hip_host_tables.argtypes = [vp, ctypes.c_size_t]
-    lib.at3hip_device_numa_node.argtypes = [i32]
-    lib.at3hip_device_numa_node.restype = ctypes.c_int
-    lib.at3hip_host_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
-    lib.at3hip_host_free.argtypes = [vp, vp]
-    lib.at3hip_wait_input.argtypes = [vp, i32]
-    lib.at3hip_wait_frames.argtypes = [vp, i32]
-    lib.at3hip_read_tap.argtypes = [vp, i32, vp, ctypes.c_size_t]
-    lib.at3hip_get_timings_ago.argtypes = [vp, i32, ctypes.POINTER(Timings)]
-    lib.at3hip_get_counters.argtypes = [vp, ctypes.POINTER(Counters), i32]
-    lib.at3hip_version.restype = ctypes.c_uint32
-    lib.at1hip_create.argtypes = [ctypes.POINTER(At1Config), ctypes.POINTER(vp)]
-    lib.at1hip_destroy.argtypes = [vp]
-    lib.at1hip_destroy.restype = None
-    lib.at1hip_last_error.argtypes = [vp]
-    lib.at1hip_last_error.restype = ctypes.c_char_p
-    lib.at1hip_encode.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
-    if hasattr(lib, "at1hip_encode_short"):   # 16-bit PCM input (added under ABI 1.6, see at3hip.h's version list)
-        lib.at1hip_encode_short.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
-    if hasattr(lib, "at3phip_encode_frames_short"):
-        lib.at3phip_encode_frames_short.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
-    lib.at1hip_reset.argtypes = [vp]
-    lib.at1hip_sync.argtypes = [vp]
-    lib.at1hip_get_timings.argtypes = [vp, ctypes.POINTER(At1Timings)]
-    lib.at1hip_read_tap.argtypes = [vp, i32, vp, ctypes.c_size_t]
-    lib.at1hip_host_tables.argtypes = [vp, ctypes.c_size_t]
-    for codec, cfg_type, counters_type in (("at1hip", At1DecoderConfig, At1DecoderCounters),
-                                           ("at3hip", At3DecoderConfig, At3DecoderCounters),
-                                           ("at3phip", At3pDecoderConfig, At3pDecoderCounters)):
-        if codec != "at1hip" and not hasattr(lib, f"{codec}_decoder_create"):
-            continue   # the ATRAC3 and ATRAC3plus decoders (added under ABI 1.6, see at3hip.h's version list)
-        for name, argtypes in (("decoder_create", [ctypes.POINTER(cfg_type), ctypes.POINTER(vp)]), ("decoder_destroy", [vp]),
-                               ("decoder_last_error", [vp]), ("decode", [vp, vp, i32, vp, ctypes.c_uint32]), ("decoder_sync", [vp]),
-                               ("decoder_reset", [vp]), ("decoder_get_counters", [vp, ctypes.POINTER(counters_type), i32]),
-                               ("decoder_set_stream", [vp, vp])):
-            getattr(lib, f"{codec}_{name}").argtypes = argtypes
-        getattr(lib, f"{codec}_decoder_destroy").restype = None
-        getattr(lib, f"{codec}_decoder_last_error").restype = ctypes.c_char_p
-    if hasattr(lib, "at3phip_decoder_host_tables"):
-        lib.at3phip_decoder_host_tables.argtypes = [vp, ctypes.c_size_t]
-    if hasattr(lib, "at3phip_decoder_host_tone_tables"):
-        lib.at3phip_decoder_host_tone_tables.argtypes = [vp, ctypes.c_size_t]
-    lib.at3phip_create.argtypes = [ctypes.POINTER(At3pConfig), ctypes.POINTER(vp)]
-    lib.at3phip_destroy.argtypes = [vp]
-    lib.at3phip_destroy.restype = None
-    lib.at3phip_last_error.argtypes = [vp]
-    lib.at3phip_last_error.restype = ctypes.c_char_p
-    lib.at3phip_reset.argtypes = [vp]
-    lib.at3phip_pqf_analyse.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
-    lib.at3phip_mdct.argtypes = [vp, vp, i32, vp, vp, ctypes.c_uint32]
-    lib.at3phip_pqf_mdct.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.c_uint32]
-    lib.at3phip_get_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
-    lib.at3phip_host_tables.argtypes = [vp, ctypes.c_size_t]
-    lib.at3phip_write_frames.argtypes = [vp, vp, i32, vp, vp, ctypes.c_uint32]
-    lib.at3phip_encode_frames.argtypes = [vp, vp, i32, vp, ctypes.c_uint32]
-    lib.at3phip_get_write_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-    lib.at3phip_host_write_tables.argtypes = [vp, ctypes.c_size_t]
-    lib.at3phip_sync.argtypes = [vp]
-    if hasattr(lib, "at3hip_resampler_create"):   # the resampler (added under ABI 1.6, see at3hip.h's version list)
-        i32p = ctypes.POINTER(i32)
-        for name, argtypes in (("create", [ctypes.POINTER(ResamplerConfig), ctypes.POINTER(vp)]), ("destroy", [vp]),
-                               ("last_error", [vp]), ("reset", [vp]), ("max_out", [vp]),
-                               ("process", [vp, vp, i32, vp, i32p, ctypes.c_uint32]), ("flush", [vp, vp, i32p, ctypes.c_uint32]),
-                               ("sync", [vp]), ("set_stream", [vp, vp]), ("shape", [i32, i32, i32p, i32p, i32p]),
-                               ("host_tables", [i32, i32, vp, ctypes.c_size_t])):
-            getattr(lib, "at3hip_resampler_" + name).argtypes = argtypes
-        lib.at3hip_resampler_destroy.restype = None
-        lib.at3hip_resampler_last_error.restype = ctypes.c_char_p
-        lib.at3hip_resampler_max_out.restype = i32
-        if hasattr(lib, "at3hip_resampler_process_s16"):   # 16-bit PCM input
-            lib.at3hip_resampler_process_s16.argtypes = [vp, vp, i32, vp, i32p, ctypes.c_uint32]
-    if hasattr(lib, "at3hip_loudness_create"):   # the loudness meter (added under ABI 1.6, see at3hip.h's version list)
-        f32p, resp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(LoudnessResult)
-        for name, argtypes in (("create", [ctypes.POINTER(LoudnessConfig), ctypes.POINTER(vp)]), ("destroy", [vp]),
-                               ("last_error", [vp]), ("reset", [vp]), ("sync", [vp]), ("set_stream", [vp, vp]),
-                               ("process", [vp, vp, i32, ctypes.c_uint32]), ("finish", [vp, resp]),
-                               ("read_hops", [vp, i32, vp, ctypes.c_size_t]), ("apply", [vp, vp, i32, vp, vp, ctypes.c_uint32]),
-                               ("gate", [vp, i32, i32, resp]), ("gain", [resp, ctypes.c_double, ctypes.c_double, f32p])):
-            getattr(lib, "at3hip_loudness_" + name).argtypes = argtypes
-        lib.at3hip_loudness_destroy.restype = None
-        lib.at3hip_loudness_last_error.restype = ctypes.c_char_p
-        if hasattr(lib, "at3hip_loudness_process_s16"):   # 16-bit PCM input
-            lib.at3hip_loudness_process_s16.argtypes = [vp, vp, i32, ctypes.c_uint32]
-            lib.at3hip_loudness_apply_s16.argtypes = [vp, vp, i32, vp, vp, ctypes.c_uint32]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name, None)   # what was added under ABI 1.6 is detected by symbol (at3hip.h's version list): see _need
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     _lib_cache[path] = lib
     return lib
 
@@ -291,23 +231,41 @@ def _vp(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-def _s16_entry(lib, name):
-    """the 16-bit entry point `name` of lib; a library that predates it is an error (there is no widening on the host instead)"""
+def _need(lib, name):
+    """the function `name` of lib; a library that predates it is an error (nothing is emulated on the host instead)"""
     fn = getattr(lib, name, None)
     if fn is None:
-        raise At3HipError(f"libat3hip.so predates 16-bit PCM input (no {name}): rebuild it")
+        raise At3HipError(f"libat3hip.so predates {name}: rebuild it")
     return fn
 
 
+def _lib_call(lib_path, name, *args, why=""):
+    """`name`(*args) of the library for a function that takes no context, raising At3HipError on failure."""
+    rc = _need(load_library(lib_path), name)(*args)
+    if rc != 0:
+        raise At3HipError(f"{name} failed ({rc}){why}")
+
+
+def _host_tables(lib_path, name, out, *args):
+    """fills `out` with the table block that `name` builds on this host (no GPU involved)"""
+    _lib_call(lib_path, name, *args, _vp(out), out.nbytes, why=f": the table block is {out.nbytes} bytes here")
+    return out
+
+
+def _device_flags(asynchronous):
+    return AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)
+
+
 class _Context:
-    """One C-ABI context of `lib`: <_PREFIX>_create / _destroy / _last_error / _reset / _sync."""
+    """One C-ABI context of `lib`: <_PREFIX>_create / _destroy / _last_error / _reset / _sync. Every call into the library
+    that takes the context goes through _call (a status) or _value (a plain number)."""
 
     _PREFIX = ""
 
     def _create(self, cfg, hint):
         self.cfg = cfg
         self.ctx = ctypes.c_void_p()
-        rc = getattr(self.lib, self._PREFIX + "_create")(ctypes.byref(cfg), ctypes.byref(self.ctx))
+        rc = _need(self.lib, self._PREFIX + "_create")(ctypes.byref(cfg), ctypes.byref(self.ctx))
         if rc != 0:
             self.ctx = None
             raise At3HipError(f"{self._PREFIX}_create failed with {rc} ({hint})")
@@ -324,10 +282,14 @@ class _Context:
         if rc != 0:
             raise At3HipError(f"{what} failed ({rc}): {getattr(self.lib, self._PREFIX + '_last_error')(self.ctx).decode()}")
 
-    def _call(self, name, *args):
-        """<_PREFIX>_<name>(ctx, *args), raising At3HipError on failure."""
-        fn = f"{self._PREFIX}_{name}"
-        self._check(getattr(self.lib, fn)(self.ctx, *args), fn)
+    def _call(self, name, *args, prefix=None):
+        """<_PREFIX>_<name>(ctx, *args), raising At3HipError with that function's name on failure (prefix: instead of _PREFIX)."""
+        fn = f"{prefix or self._PREFIX}_{name}"
+        self._check(_need(self.lib, fn)(self.ctx, *args), fn)
+
+    def _value(self, name):
+        """<_PREFIX>_<name>(ctx) of a function that returns a number, not a status."""
+        return _need(self.lib, f"{self._PREFIX}_{name}")(self.ctx)
 
     def reset(self):
         self._call("reset")
@@ -335,17 +297,10 @@ class _Context:
     def sync(self):
         self._call("sync")
 
-
-class _Decoder(_Context):
-    """A batched decoder: <_CODEC>_decode and the <_CODEC>_decoder_* lifecycle, with counters named by _COUNTERS' fields."""
-
-    _CODEC = ""        # <_CODEC>_decode; the lifecycle functions are <_PREFIX>_*
-    _COUNTERS = None   # the ctypes structure <_PREFIX>_get_counters fills
-
     def _order_behind_torch(self, device, ordered):
-        """Queues the next call on torch's current stream of `device` (ordered), or on the decoder's own stream. Torch's
-        default stream is the null stream, whose handle (0) means "the decoder's own stream" to <_PREFIX>_set_stream;
-        the decoder's stream is non-blocking: wait for what torch queued there instead."""
+        """Queues the next call on torch's current stream of `device` (ordered), or on the context's own stream. Torch's
+        default stream is the null stream, whose handle (0) means "the context's own stream" to <_PREFIX>_set_stream;
+        the context's stream is non-blocking: wait for what torch queued there instead."""
         stream = None
         if ordered:
             import torch
@@ -355,15 +310,58 @@ class _Decoder(_Context):
                 cur.synchronize()
         self._call("set_stream", ctypes.c_void_p(stream))
 
+
+class _Decoder(_Context):
+    """A batched decoder: <_CODEC>_decode and the <_CODEC>_decoder_* lifecycle, with counters named by _COUNTERS' fields.
+    A subclass gives _shapes(); its decode / decode_device are _decode / _decode_device under its own argument names."""
+
+    _CODEC = ""        # <_CODEC>_decode; the lifecycle functions are <_PREFIX>_*
+    _COUNTERS = None   # the ctypes structure <_PREFIX>_get_counters fills
+
+    def _shapes(self):
+        """(shape of one frame's bytes, shape of one frame's samples): what follows [n_streams, n_frames]"""
+        raise NotImplementedError
+
     def decode_ptr(self, src_ptr, n_frames, out_ptr, flags):
         """Raw pointers and <_CODEC>_decode flags (benchmarks)."""
-        fn = self._CODEC + "_decode"
-        self._check(getattr(self.lib, fn)(self.ctx, ctypes.c_void_p(src_ptr), int(n_frames), ctypes.c_void_p(out_ptr), int(flags)), fn)
+        self._call("decode", ctypes.c_void_p(src_ptr), int(n_frames), ctypes.c_void_p(out_ptr), int(flags), prefix=self._CODEC)
+
+    def _decode(self, frames, s16, flags=0):
+        """host uint8 [n_streams, n_frames, *frame bytes] -> float32 (int16 with s16) [n_streams, n_frames, *frame samples];
+        the three <_CODEC>_DECODE_S16 flags are one number"""
+        src, dst = self._shapes()
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        assert frames.ndim == 2 + len(src) and frames.shape[0] == self.n_streams and frames.shape[2:] == src, frames.shape
+        n = frames.shape[1]
+        out = np.zeros((self.n_streams, n) + dst, dtype=np.int16 if s16 else np.float32)
+        self.decode_ptr(frames.ctypes.data, n, out.ctypes.data, (AT3HIP_DECODE_S16 if s16 else 0) | flags)
+        return out
+
+    def _decode_device(self, frames, out, asynchronous, ordered, flags=0):
+        """torch tensors of the shapes of _decode on this decoder's device"""
+        import torch
+        src, dst = self._shapes()
+        assert frames.dtype == torch.uint8 and frames.is_contiguous() and out.is_contiguous()
+        assert out.dtype in (torch.float32, torch.int16)
+        n = frames.shape[1]
+        assert tuple(frames.shape) == (self.n_streams, n) + src, tuple(frames.shape)
+        assert tuple(out.shape) == (self.n_streams, n) + dst, tuple(out.shape)
+        flags |= _device_flags(asynchronous) | (AT3HIP_DECODE_S16 if out.dtype == torch.int16 else 0)
+        self._order_behind_torch(frames.device, ordered)
+        self.decode_ptr(frames.data_ptr(), n, out.data_ptr(), flags)
 
     def counters(self, reset=False):
         c = self._COUNTERS()
         self._call("get_counters", ctypes.byref(c), int(bool(reset)))
         return {n: int(getattr(c, n)) for n, _ in self._COUNTERS._fields_}
+
+
+def _curves(n_points, level, loc):
+    """the three optional gain-curve arrays as int32 (kept alive by the caller) and their pointers"""
+    if n_points is None:
+        return (), (None, None, None)
+    arrays = tuple(np.ascontiguousarray(a, dtype=np.int32) for a in (n_points, level, loc))
+    return arrays, tuple(_vp(a) for a in arrays)
 
 
 class At3Hip(_Context):
@@ -378,48 +376,46 @@ class At3Hip(_Context):
         self._create(Config(int(bitrate), int(channels), int(no_gain), int(no_tonal), int(bfu_idx_const), int(n_streams),
                             int(max_blocks), int(device_id)), "no usable MI355X / HIP runtime?")
         self.n_streams = n_streams
-        self.frame_size = self.lib.at3hip_frame_size(self.ctx)
-        self.joint_stereo = bool(self.lib.at3hip_joint_stereo(self.ctx))
+        self.frame_size = self._value("frame_size")
+        self.joint_stereo = bool(self._value("joint_stereo"))
 
-    def encode(self, pcm):
-        """pcm float32 [n_streams, n_blocks, 1024, channels] (host) -> uint8 [n_streams, n_frames, frame_size]."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+    def encode_ptr(self, pcm_ptr, n_blocks, out_ptr, flags):
+        """Raw pointers (float32 PCM) and at3hip_encode flags; returns frames per stream."""
+        nf = ctypes.c_int32()
+        self._call("encode", ctypes.c_void_p(pcm_ptr), int(n_blocks), ctypes.c_void_p(out_ptr), ctypes.byref(nf), int(flags))
+        return nf.value
+
+    def encode_s16_ptr(self, pcm_ptr, n_blocks, out_ptr, flags):
+        """Raw pointers (int16 PCM) and at3hip_encode_s16 flags; returns frames per stream."""
+        nf = ctypes.c_int32()
+        self._call("encode_s16", ctypes.c_void_p(pcm_ptr), int(n_blocks), ctypes.c_void_p(out_ptr), ctypes.byref(nf), int(flags))
+        return nf.value
+
+    def _encode_host(self, pcm, dtype, raw):
+        pcm = np.ascontiguousarray(pcm, dtype=dtype)
         assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (1024, self.channels), pcm.shape
         nb = pcm.shape[1]
         out = np.zeros((self.n_streams, nb, self.frame_size), dtype=np.uint8)
-        nf = ctypes.c_int32()
-        self._check(self.lib.at3hip_encode(self.ctx, _vp(pcm), nb, _vp(out), ctypes.byref(nf), 0), "at3hip_encode")
-        n = nf.value
+        n = raw(pcm.ctypes.data, nb, out.ctypes.data, 0)
         return np.ascontiguousarray(out.reshape(-1)[: self.n_streams * n * self.frame_size].reshape(
             self.n_streams, n, self.frame_size))
 
+    def encode(self, pcm):
+        """pcm float32 [n_streams, n_blocks, 1024, channels] (host) -> uint8 [n_streams, n_frames, frame_size]."""
+        return self._encode_host(pcm, np.float32, self.encode_ptr)
+
     def encode_s16(self, pcm):
         """pcm int16 [n_streams, n_blocks, 1024, channels] (host) -> uint8 [n_streams, n_frames, frame_size] (at3hip_encode_s16)."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (1024, self.channels), pcm.shape
-        nb = pcm.shape[1]
-        out = np.zeros((self.n_streams, nb, self.frame_size), dtype=np.uint8)
-        nf = ctypes.c_int32()
-        self._check(self.lib.at3hip_encode_s16(self.ctx, _vp(pcm), nb, _vp(out), ctypes.byref(nf), 0), "at3hip_encode_s16")
-        n = nf.value
-        return np.ascontiguousarray(out.reshape(-1)[: self.n_streams * n * self.frame_size].reshape(self.n_streams, n, self.frame_size))
-
-    def encode_device_s16(self, pcm_ptr, n_blocks, out_ptr, asynchronous=False):
-        """Device-resident int16 PCM / out (raw pointers). Returns frames per stream."""
-        nf = ctypes.c_int32()
-        flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)
-        self._check(self.lib.at3hip_encode_s16(self.ctx, ctypes.c_void_p(pcm_ptr), n_blocks, ctypes.c_void_p(out_ptr),
-                                               ctypes.byref(nf), flags), "at3hip_encode_s16")
-        return nf.value
+        return self._encode_host(pcm, np.int16, self.encode_s16_ptr)
 
     def encode_device(self, pcm_ptr, n_blocks, out_ptr, asynchronous=False):
         """Device-resident PCM/out (raw pointers, e.g. torch tensor .data_ptr()). Returns frames per stream.
         asynchronous=True only queues the work (AT3HIP_ASYNC): call sync() before the frames are read."""
-        nf = ctypes.c_int32()
-        flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)
-        self._check(self.lib.at3hip_encode(self.ctx, ctypes.c_void_p(pcm_ptr), n_blocks, ctypes.c_void_p(out_ptr),
-                                           ctypes.byref(nf), flags), "at3hip_encode")
-        return nf.value
+        return self.encode_ptr(pcm_ptr, n_blocks, out_ptr, _device_flags(asynchronous))
+
+    def encode_device_s16(self, pcm_ptr, n_blocks, out_ptr, asynchronous=False):
+        """Device-resident int16 PCM / out (raw pointers). Returns frames per stream."""
+        return self.encode_s16_ptr(pcm_ptr, n_blocks, out_ptr, _device_flags(asynchronous))
 
     PSY_DTYPE = np.dtype([("loud_ch", "<f4"), ("n_tonal", "<i4"), ("sfi", "u1", 32), ("energy", "<f4", 32),
                           ("tonal", [("pos", "<u2"), ("bfu", "u1"), ("len", "u1"), ("sfi", "u1"), ("pad", "u1", 3),
@@ -429,7 +425,7 @@ class At3Hip(_Context):
     def read_tap(self, kind, dtype, shape):
         """Stage tap of the most recent encode call (AT3HIP_TAP_*), as a numpy array of `dtype` and `shape`."""
         out = np.zeros(shape, dtype=dtype)
-        self._check(self.lib.at3hip_read_tap(self.ctx, int(kind), _vp(out), out.nbytes), "at3hip_read_tap")
+        self._call("read_tap", int(kind), _vp(out), out.nbytes)
         return out
 
     def sclk_mhz(self):
@@ -441,14 +437,14 @@ class At3Hip(_Context):
     def counters(self, reset=False):
         """at3hip_get_counters: what TScaler::Scale would have printed since create / reset - {"scale_overflow", "clipped_values"}."""
         c = Counters()
-        self._check(self.lib.at3hip_get_counters(self.ctx, ctypes.byref(c), int(bool(reset))), "at3hip_get_counters")
+        self._call("get_counters", ctypes.byref(c), int(bool(reset)))
         return {"scale_overflow": int(c.scale_overflow), "clipped_values": int(c.clipped_values)}
 
     def host_alloc(self, shape, dtype):
         """Page-locked host array (at3hip_host_alloc); free it with host_free(array) before close()."""
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
         p = ctypes.c_void_p()
-        self._check(self.lib.at3hip_host_alloc(self.ctx, n, ctypes.byref(p)), "at3hip_host_alloc")
+        self._call("host_alloc", n, ctypes.byref(p))
         buf = (ctypes.c_char * n).from_address(p.value)
         a = np.frombuffer(buf, dtype=dtype).reshape(shape)
         self._pinned = getattr(self, "_pinned", {})
@@ -456,57 +452,48 @@ class At3Hip(_Context):
         return a
 
     def host_free(self, a):
-        p = self._pinned.pop(a.ctypes.data)
-        self._check(self.lib.at3hip_host_free(self.ctx, p), "at3hip_host_free")
+        self._call("host_free", self._pinned.pop(a.ctypes.data))
 
     def encode_host_async(self, pcm, out):
         """Queues one call on host arrays (pinned ones overlap copies and kernels); returns frames per stream. `out` is valid
         after wait_frames(ago) / sync(), `pcm` may be refilled after wait_input(ago)."""
-        nf = ctypes.c_int32()
-        fn = self.lib.at3hip_encode_s16 if pcm.dtype == np.int16 else self.lib.at3hip_encode
-        self._check(fn(self.ctx, _vp(pcm), pcm.shape[1], _vp(out), ctypes.byref(nf), AT3HIP_ASYNC), "at3hip_encode")
-        return nf.value
+        raw = self.encode_s16_ptr if pcm.dtype == np.int16 else self.encode_ptr
+        return raw(pcm.ctypes.data, pcm.shape[1], out.ctypes.data, AT3HIP_ASYNC)
 
     def wait_input(self, ago=0):
-        self._check(self.lib.at3hip_wait_input(self.ctx, int(ago)), "at3hip_wait_input")
+        self._call("wait_input", int(ago))
 
     def wait_frames(self, ago=0):
-        self._check(self.lib.at3hip_wait_frames(self.ctx, int(ago)), "at3hip_wait_frames")
+        self._call("wait_frames", int(ago))
 
     def set_option(self, option, value):
         """AT3HIP_OPT_*: work partitioning / equivalent-form switches; results never change."""
-        self._check(self.lib.at3hip_set_option(self.ctx, int(option), int(value)), "at3hip_set_option")
+        self._call("set_option", int(option), int(value))
 
     def set_stream(self, hip_stream):
         """Queue the front half on the caller's HIP stream (a hipStream_t handle, e.g. torch.cuda.Stream().cuda_stream);
         0 / None goes back to the context's own stream."""
-        self._check(self.lib.at3hip_set_stream(self.ctx, ctypes.c_void_p(int(hip_stream) if hip_stream else None)), "at3hip_set_stream")
+        self._call("set_stream", ctypes.c_void_p(int(hip_stream) if hip_stream else None))
 
     def timings_ago(self, ago):
         t = Timings()
-        self._check(self.lib.at3hip_get_timings_ago(self.ctx, int(ago), ctypes.byref(t)), "at3hip_get_timings_ago")
+        self._call("get_timings_ago", int(ago), ctypes.byref(t))
         return {n: getattr(t, n) for n, _ in Timings._fields_}
 
     def qmf_mdct_device(self, pcm_ptr, n_blocks, specs_ptr):
-        self._check(self.lib.at3hip_qmf_mdct(self.ctx, ctypes.c_void_p(pcm_ptr), n_blocks, ctypes.c_void_p(specs_ptr),
-                                             AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE), "at3hip_qmf_mdct")
+        self._call("qmf_mdct", ctypes.c_void_p(pcm_ptr), n_blocks, ctypes.c_void_p(specs_ptr), _device_flags(False))
 
     def mdct(self, bands, n_points=None, level=None, loc=None, max_levels=False):
         """Batched TAtrac3MDCT::Mdct. bands float32 [n,4,512] -> (specs [n,1024], mutated bands[, max levels [n,4]])."""
         bands = np.ascontiguousarray(bands, dtype=np.float32).copy()
         n = bands.shape[0]
         specs = np.zeros((n, 1024), dtype=np.float32)
-        curves = (None, None, None)
-        if n_points is not None:
-            n_points = np.ascontiguousarray(n_points, dtype=np.int32)
-            level = np.ascontiguousarray(level, dtype=np.int32)
-            loc = np.ascontiguousarray(loc, dtype=np.int32)
-            curves = (_vp(n_points), _vp(level), _vp(loc))
+        keep, curves = _curves(n_points, level, loc)
         if max_levels:
             mx = np.zeros((n, 4), dtype=np.float32)
-            self._check(self.lib.at3hip_mdct_levels(self.ctx, _vp(bands), _vp(specs), _vp(mx), *curves, n, 0), "at3hip_mdct_levels")
+            self._call("mdct_levels", _vp(bands), _vp(specs), _vp(mx), *curves, n, 0)
             return specs, bands, mx
-        self._check(self.lib.at3hip_mdct(self.ctx, _vp(bands), _vp(specs), *curves, n, 0), "at3hip_mdct")
+        self._call("mdct", _vp(bands), _vp(specs), *curves, n, 0)
         return specs, bands
 
     def gain_energy_scale(self, prev_overlap, cur_input, prev_scale, n_points=None, level=None, loc=None):
@@ -517,19 +504,13 @@ class At3Hip(_Context):
         prev_scale = np.ascontiguousarray(prev_scale, dtype=np.float32)
         n = prev_overlap.shape[0]
         out = np.zeros((n, 4), dtype=np.float32)
-        curves = (None, None, None)
-        if n_points is not None:
-            n_points = np.ascontiguousarray(n_points, dtype=np.int32)
-            level = np.ascontiguousarray(level, dtype=np.int32)
-            loc = np.ascontiguousarray(loc, dtype=np.int32)
-            curves = (_vp(n_points), _vp(level), _vp(loc))
-        self._check(self.lib.at3hip_gain_energy_scale(self.ctx, _vp(prev_overlap), _vp(cur_input), *curves, _vp(prev_scale),
-                                                      _vp(out), n, 0), "at3hip_gain_energy_scale")
+        keep, curves = _curves(n_points, level, loc)
+        self._call("gain_energy_scale", _vp(prev_overlap), _vp(cur_input), *curves, _vp(prev_scale), _vp(out), n, 0)
         return out
 
     def timings(self):
         t = Timings()
-        self._check(self.lib.at3hip_get_timings(self.ctx, ctypes.byref(t)), "at3hip_get_timings")
+        self._call("get_timings", ctypes.byref(t))
         return {n: getattr(t, n) for n, _ in Timings._fields_}
 
 
@@ -546,11 +527,7 @@ AT3_TABLES_DTYPE = np.dtype([("qmf_win", "<f4", 48), ("scale", "<f4", 64), ("enc
 
 def at3_host_tables(lib_path=None):
     """The ATRAC3 constant tables as the library builds them on this host (no GPU involved)."""
-    out = np.zeros((), dtype=AT3_TABLES_DTYPE)
-    rc = load_library(lib_path).at3hip_host_tables(_vp(out), out.nbytes)
-    if rc != 0:
-        raise At3HipError(f"at3hip_host_tables failed ({rc}): table block is {out.nbytes} bytes here")
-    return out
+    return _host_tables(lib_path, "at3hip_host_tables", np.zeros((), dtype=AT3_TABLES_DTYPE))
 
 
 AT1_TABLES_DTYPE = np.dtype([("qmf_win", "<f4", 48), ("scale", "<f4", 64), ("sine", "<f4", 32), ("sc512", "<f4", 256),
@@ -562,11 +539,7 @@ assert AT1_TABLES_DTYPE.itemsize == 6904
 
 def at1_host_tables(lib_path=None):
     """The ATRAC1 constant tables as the library builds them on the host (no GPU involved)."""
-    out = np.zeros((), dtype=AT1_TABLES_DTYPE)
-    rc = load_library(lib_path).at1hip_host_tables(_vp(out), out.nbytes)
-    if rc != 0:
-        raise At3HipError(f"at1hip_host_tables failed ({rc})")
-    return out
+    return _host_tables(lib_path, "at1hip_host_tables", np.zeros((), dtype=AT1_TABLES_DTYPE))
 
 
 class At1Hip(_Context):
@@ -583,49 +556,51 @@ class At1Hip(_Context):
         self._create(At1Config(int(channels), int(bool(window_auto)), int(window_mask), int(bfu_idx_const), int(n_streams),
                                int(max_blocks), int(device_id)), "no usable MI355X / HIP runtime?")
 
-    def encode(self, pcm):
-        """pcm float32 [n_streams, n_blocks, 512, channels] (host) -> uint8 [n_streams, n_blocks, channels, 212]."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+    def encode_ptr(self, pcm_ptr, n_blocks, out_ptr, flags):
+        """Raw pointers (float32 PCM) and at1hip_encode flags."""
+        self._call("encode", ctypes.c_void_p(pcm_ptr), int(n_blocks), ctypes.c_void_p(out_ptr), int(flags))
+
+    def encode_s16_ptr(self, pcm_ptr, n_blocks, out_ptr, flags):
+        """Raw pointers (int16 PCM, 2-byte alignment is enough) and at1hip_encode_short flags."""
+        self._call("encode_short", ctypes.c_void_p(pcm_ptr), int(n_blocks), ctypes.c_void_p(out_ptr), int(flags))
+
+    def _encode_host(self, pcm, dtype, raw):
+        pcm = np.ascontiguousarray(pcm, dtype=dtype)
         assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (512, self.channels), pcm.shape
         nb = pcm.shape[1]
         out = np.zeros((self.n_streams, nb, self.channels, self.FRAME), dtype=np.uint8)
-        self._check(self.lib.at1hip_encode(self.ctx, _vp(pcm), nb, _vp(out), 0), "at1hip_encode")
+        raw(pcm.ctypes.data, nb, out.ctypes.data, 0)
         return out
 
-    def encode_device(self, pcm_ptr, n_blocks, out_ptr, asynchronous=False):
-        """Device-resident float32 PCM / frames (raw pointers). The context's stream is non-blocking (at3hip.h, DEVICE BUFFERS
-        AND STREAMS): it waits for no other stream, so whatever produces the PCM must be complete before the call, and with
-        asynchronous=True (AT3HIP_ASYNC) both buffers stay untouched until sync()."""
-        self._check(self.lib.at1hip_encode(self.ctx, ctypes.c_void_p(pcm_ptr), n_blocks, ctypes.c_void_p(out_ptr),
-                                           AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)), "at1hip_encode")
+    def encode(self, pcm):
+        """pcm float32 [n_streams, n_blocks, 512, channels] (host) -> uint8 [n_streams, n_blocks, channels, 212]."""
+        return self._encode_host(pcm, np.float32, self.encode_ptr)
 
     def encode_s16(self, pcm):
         """pcm int16 [n_streams, n_blocks, 512, channels] (host) -> uint8 [n_streams, n_blocks, channels, 212]
         (at1hip_encode_short): the frames of encode() on pcm / 32768 as float32, bit for bit; the samples cross the bus as
         16-bit and are widened by the first kernel. Calls of both kinds may alternate."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (512, self.channels), pcm.shape
-        nb = pcm.shape[1]
-        out = np.zeros((self.n_streams, nb, self.channels, self.FRAME), dtype=np.uint8)
-        self._check(_s16_entry(self.lib, "at1hip_encode_short")(self.ctx, _vp(pcm), nb, _vp(out), 0), "at1hip_encode_short")
-        return out
+        return self._encode_host(pcm, np.int16, self.encode_s16_ptr)
+
+    def encode_device(self, pcm_ptr, n_blocks, out_ptr, asynchronous=False):
+        """Device-resident float32 PCM / frames (raw pointers). The context's stream is non-blocking (at3hip.h, DEVICE BUFFERS
+        AND STREAMS): it waits for no other stream, so whatever produces the PCM must be complete before the call, and with
+        asynchronous=True (AT3HIP_ASYNC) both buffers stay untouched until sync()."""
+        self.encode_ptr(pcm_ptr, n_blocks, out_ptr, _device_flags(asynchronous))
 
     def encode_device_s16(self, pcm_ptr, n_blocks, out_ptr, asynchronous=False):
-        """Device-resident int16 PCM / frames (raw pointers; the PCM needs only 2-byte alignment). The context's stream is
-        non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): it waits for no other stream, so whatever produces the PCM must be
-        complete before the call, and with asynchronous=True (AT3HIP_ASYNC) both buffers stay untouched until sync()."""
-        self._check(_s16_entry(self.lib, "at1hip_encode_short")(
-            self.ctx, ctypes.c_void_p(pcm_ptr), n_blocks, ctypes.c_void_p(out_ptr),
-            AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)), "at1hip_encode_short")
+        """Device-resident int16 PCM / frames (raw pointers; the PCM needs only 2-byte alignment). Stream ordering and what
+        stays untouched until sync() as in encode_device."""
+        self.encode_s16_ptr(pcm_ptr, n_blocks, out_ptr, _device_flags(asynchronous))
 
     def read_tap(self, kind, dtype, shape):
         out = np.zeros(shape, dtype=dtype)
-        self._check(self.lib.at1hip_read_tap(self.ctx, int(kind), _vp(out), out.nbytes), "at1hip_read_tap")
+        self._call("read_tap", int(kind), _vp(out), out.nbytes)
         return out
 
     def timings(self):
         t = At1Timings()
-        self._check(self.lib.at1hip_get_timings(self.ctx, ctypes.byref(t)), "at1hip_get_timings")
+        self._call("get_timings", ctypes.byref(t))
         return {n: getattr(t, n) for n, _ in At1Timings._fields_}
 
 
@@ -641,14 +616,12 @@ class At1HipDecoder(_Decoder):
         self._create(At1DecoderConfig(self.channels, self.n_streams, self.max_frames, int(device_id)),
                      "bad configuration, or no usable MI355X / HIP runtime")
 
+    def _shapes(self):
+        return (self.channels, self.FRAME), (512, self.channels)
+
     def decode(self, units, s16=False):
         """units uint8 [n_streams, n_frames, channels, 212] (host) -> float32 (int16 with s16) [n_streams, n_frames, 512, channels]."""
-        units = np.ascontiguousarray(units, dtype=np.uint8)
-        assert units.ndim == 4 and units.shape[0] == self.n_streams and units.shape[2:] == (self.channels, self.FRAME), units.shape
-        n = units.shape[1]
-        out = np.zeros((self.n_streams, n, 512, self.channels), dtype=np.int16 if s16 else np.float32)
-        self.decode_ptr(units.ctypes.data, n, out.ctypes.data, AT1HIP_DECODE_S16 if s16 else 0)
-        return out
+        return self._decode(units, s16)
 
     def decode_device(self, units, out, asynchronous=False, ordered=True):
         """Torch tensors on this decoder's device: units uint8 [n_streams, n, channels, 212] -> out float32 / int16 (s16 output)
@@ -657,16 +630,7 @@ class At1HipDecoder(_Decoder):
         there afterwards follows it (with asynchronous=True and the null stream: after sync()). ordered=False runs it on the
         decoder's own non-blocking stream: the caller must then make sure `units` is complete (the caller's race of
         at3hip.h's DEVICE BUFFERS AND STREAMS)."""
-        import torch
-        assert units.dtype == torch.uint8 and units.is_contiguous() and out.is_contiguous()
-        assert out.dtype in (torch.float32, torch.int16)
-        n = units.shape[1]
-        assert tuple(units.shape) == (self.n_streams, n, self.channels, self.FRAME), tuple(units.shape)
-        assert tuple(out.shape) == (self.n_streams, n, 512, self.channels), tuple(out.shape)
-        flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT1HIP_DECODE_S16 if out.dtype == torch.int16 else 0)
-        flags |= AT3HIP_ASYNC if asynchronous else 0
-        self._order_behind_torch(units.device, ordered)
-        self.decode_ptr(units.data_ptr(), n, out.data_ptr(), flags)
+        self._decode_device(units, out, asynchronous, ordered)
 
 
 class At3HipDecoder(_Decoder):
@@ -677,35 +641,22 @@ class At3HipDecoder(_Decoder):
 
     def __init__(self, n_streams=1, frame_size=384, joint_stereo=None, max_frames=256, device_id=0, lib_path=None):
         self.lib = load_library(lib_path)
-        if not hasattr(self.lib, "at3hip_decoder_create"):
-            raise At3HipError("libat3hip.so predates the ATRAC3 decoder (no at3hip_decoder_create): rebuild it")
         self.n_streams, self.frame_size, self.max_frames = int(n_streams), int(frame_size), int(max_frames)
         self.joint_stereo = bool(self.ROWS.get(self.frame_size, False) if joint_stereo is None else joint_stereo)
         self._create(At3DecoderConfig(self.n_streams, self.frame_size, int(self.joint_stereo), self.max_frames, int(device_id)),
                      "bad configuration, or no usable MI355X / HIP runtime")
 
+    def _shapes(self):
+        return (self.frame_size,), (1024, 2)
+
     def decode(self, frames, s16=False):
         """frames uint8 [n_streams, n_frames, frame_size] (host) -> float32 (int16 with s16) [n_streams, n_frames, 1024, 2]."""
-        frames = np.ascontiguousarray(frames, dtype=np.uint8)
-        assert frames.ndim == 3 and frames.shape[0] == self.n_streams and frames.shape[2] == self.frame_size, frames.shape
-        n = frames.shape[1]
-        out = np.zeros((self.n_streams, n, 1024, 2), dtype=np.int16 if s16 else np.float32)
-        self.decode_ptr(frames.ctypes.data, n, out.ctypes.data, AT3HIP_DECODE_S16 if s16 else 0)
-        return out
+        return self._decode(frames, s16)
 
     def decode_device(self, frames, out, asynchronous=False, ordered=True):
         """Torch tensors on this decoder's device: frames uint8 [n_streams, n, frame_size] -> out float32 / int16 (s16 output)
         [n_streams, n, 1024, 2]. Ordered behind torch's current stream by default, as At1HipDecoder.decode_device."""
-        import torch
-        assert frames.dtype == torch.uint8 and frames.is_contiguous() and out.is_contiguous()
-        assert out.dtype in (torch.float32, torch.int16)
-        n = frames.shape[1]
-        assert tuple(frames.shape) == (self.n_streams, n, self.frame_size), tuple(frames.shape)
-        assert tuple(out.shape) == (self.n_streams, n, 1024, 2), tuple(out.shape)
-        flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_DECODE_S16 if out.dtype == torch.int16 else 0)
-        flags |= AT3HIP_ASYNC if asynchronous else 0
-        self._order_behind_torch(frames.device, ordered)
-        self.decode_ptr(frames.data_ptr(), n, out.data_ptr(), flags)
+        self._decode_device(frames, out, asynchronous, ordered)
 
 
 class At3pHipDecoder(_Decoder):
@@ -715,53 +666,36 @@ class At3pHipDecoder(_Decoder):
 
     def __init__(self, n_streams=1, channels=2, max_frames=64, device_id=0, lib_path=None):
         self.lib = load_library(lib_path)
-        if not hasattr(self.lib, "at3phip_decoder_create"):
-            raise At3HipError("libat3hip.so predates the ATRAC3plus decoder (no at3phip_decoder_create): rebuild it")
         self.n_streams, self.channels, self.max_frames = int(n_streams), int(channels), int(max_frames)
         self._create(At3pDecoderConfig(self.channels, self.n_streams, self.max_frames, int(device_id)),
                      "bad configuration, or no usable MI355X / HIP runtime")
 
+    def _shapes(self):
+        return (2048,), (2048, self.channels)
+
     def _tones_flag(self, tones):
+        """AT3PHIP_DECODE_TONES for `tones`; a library has tonal-block decoding if it has the tone tables"""
         if not tones:
             return 0
-        if not hasattr(self.lib, "at3phip_decoder_host_tone_tables"):
-            raise At3HipError("libat3hip.so predates tonal-block decoding (no at3phip_decoder_host_tone_tables): rebuild it")
+        _need(self.lib, "at3phip_decoder_host_tone_tables")
         return AT3PHIP_DECODE_TONES
 
     def decode(self, frames, s16=False, tones=False):
         """frames uint8 [n_streams, n_frames, 2048] (host) -> float32 (int16 with s16) [n_streams, n_frames, 2048, channels].
         tones: decode tonal blocks (AT3PHIP_DECODE_TONES) instead of rejecting their frames."""
-        frames = np.ascontiguousarray(frames, dtype=np.uint8)
-        assert frames.ndim == 3 and frames.shape[0] == self.n_streams and frames.shape[2] == 2048, frames.shape
-        n = frames.shape[1]
-        out = np.zeros((self.n_streams, n, 2048, self.channels), dtype=np.int16 if s16 else np.float32)
-        self.decode_ptr(frames.ctypes.data, n, out.ctypes.data, (AT3PHIP_DECODE_S16 if s16 else 0) | self._tones_flag(tones))
-        return out
+        return self._decode(frames, s16, self._tones_flag(tones))
 
     def decode_device(self, frames, out, asynchronous=False, ordered=True, tones=False):
         """Torch tensors on this decoder's device: frames uint8 [n_streams, n, 2048] -> out float32 / int16 (s16 output)
         [n_streams, n, 2048, channels]. Ordered behind torch's current stream by default, as At1HipDecoder.decode_device.
         tones as in decode."""
-        import torch
-        assert frames.dtype == torch.uint8 and frames.is_contiguous() and out.is_contiguous()
-        assert out.dtype in (torch.float32, torch.int16)
-        n = frames.shape[1]
-        assert tuple(frames.shape) == (self.n_streams, n, 2048), tuple(frames.shape)
-        assert tuple(out.shape) == (self.n_streams, n, 2048, self.channels), tuple(out.shape)
-        flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3PHIP_DECODE_S16 if out.dtype == torch.int16 else 0)
-        flags |= (AT3HIP_ASYNC if asynchronous else 0) | self._tones_flag(tones)
-        self._order_behind_torch(frames.device, ordered)
-        self.decode_ptr(frames.data_ptr(), n, out.data_ptr(), flags)
+        self._decode_device(frames, out, asynchronous, ordered, self._tones_flag(tones))
 
 
 def at3p_decoder_host_tables(lib_path=None):
     """at3phip_decoder_host_tables (no GPU): the decoder's table block as bytes; its first 2048 are the DCT-IV cosines
     double[16][16]."""
-    out = np.zeros(AT3PHIP_DECODER_TABLES_BYTES, np.uint8)
-    rc = load_library(lib_path).at3phip_decoder_host_tables(_vp(out), out.nbytes)
-    if rc != 0:
-        raise At3HipError(f"at3phip_decoder_host_tables failed ({rc})")
-    return out
+    return _host_tables(lib_path, "at3phip_decoder_host_tables", np.zeros(AT3PHIP_DECODER_TABLES_BYTES, np.uint8))
 
 
 AT3P_TONE_TABLES_DTYPE = np.dtype([("sine", "<f4", 2048), ("hann", "<f4", 256), ("amp_sf", "<f4", 64), ("vlc", "<u2", 16)])
@@ -770,11 +704,7 @@ assert AT3P_TONE_TABLES_DTYPE.itemsize == AT3PHIP_DECODER_TONE_TABLES_BYTES
 
 def at3p_decoder_host_tone_tables(lib_path=None):
     """at3phip_decoder_host_tone_tables (no GPU): the tone synthesis' tables as a record of AT3P_TONE_TABLES_DTYPE."""
-    out = np.zeros((), AT3P_TONE_TABLES_DTYPE)
-    rc = load_library(lib_path).at3phip_decoder_host_tone_tables(_vp(out), out.nbytes)
-    if rc != 0:
-        raise At3HipError(f"at3phip_decoder_host_tone_tables failed ({rc})")
-    return out
+    return _host_tables(lib_path, "at3phip_decoder_host_tone_tables", np.zeros((), AT3P_TONE_TABLES_DTYPE))
 
 
 AT3PHIP_RESIDUAL_SCALE = 16
@@ -784,11 +714,7 @@ assert AT3P_TABLES_DTYPE.itemsize == 3456
 
 
 def at3p_host_tables(lib_path=None):
-    out = np.zeros((), dtype=AT3P_TABLES_DTYPE)
-    rc = load_library(lib_path).at3phip_host_tables(_vp(out), out.nbytes)
-    if rc != 0:
-        raise At3HipError(f"at3phip_host_tables failed ({rc})")
-    return out
+    return _host_tables(lib_path, "at3phip_host_tables", np.zeros((), dtype=AT3P_TABLES_DTYPE))
 
 
 class At3pHip(_Context):
@@ -801,19 +727,44 @@ class At3pHip(_Context):
         self.channels, self.n_streams = int(channels), int(n_streams)
         self._create(At3pConfig(int(channels), int(n_streams), int(max_frames), int(device_id)), "no usable MI355X / HIP runtime?")
 
+    # one raw method per entry point: pointers (None: absent), a frame count and the function's flags
+    def pqf_ptr(self, pcm_ptr, n_frames, bands_ptr, flags):
+        self._call("pqf_analyse", ctypes.c_void_p(pcm_ptr), int(n_frames), ctypes.c_void_p(bands_ptr), int(flags))
+
+    def mdct_ptr(self, bands_ptr, n_frames, win_flags_ptr, specs_ptr, flags):
+        self._call("mdct", ctypes.c_void_p(bands_ptr), int(n_frames), ctypes.c_void_p(win_flags_ptr), ctypes.c_void_p(specs_ptr),
+                   int(flags))
+
+    def pqf_mdct_ptr(self, pcm_ptr, n_frames, win_flags_ptr, bands_ptr, specs_ptr, flags):
+        self._call("pqf_mdct", ctypes.c_void_p(pcm_ptr), int(n_frames), ctypes.c_void_p(win_flags_ptr), ctypes.c_void_p(bands_ptr),
+                   ctypes.c_void_p(specs_ptr), int(flags))
+
+    def write_frames_ptr(self, specs_ptr, n_frames, win_flags_ptr, frames_ptr, flags):
+        self._call("write_frames", ctypes.c_void_p(specs_ptr), int(n_frames), ctypes.c_void_p(win_flags_ptr),
+                   ctypes.c_void_p(frames_ptr), int(flags))
+
+    def encode_frames_ptr(self, pcm_ptr, n_frames, frames_ptr, flags):
+        """Raw pointers (float32 PCM) and at3phip_encode_frames flags."""
+        self._call("encode_frames", ctypes.c_void_p(pcm_ptr), int(n_frames), ctypes.c_void_p(frames_ptr), int(flags))
+
+    def encode_frames_s16_ptr(self, pcm_ptr, n_frames, frames_ptr, flags):
+        """Raw pointers (int16 PCM, 2-byte alignment is enough) and at3phip_encode_frames_short flags."""
+        self._call("encode_frames_short", ctypes.c_void_p(pcm_ptr), int(n_frames), ctypes.c_void_p(frames_ptr), int(flags))
+
     def _flags(self, win_flags, nf):
+        """win_flags as uint16 [n_streams, nf, channels] (kept alive by the caller) and its address, or (None, None)"""
         if win_flags is None:
             return None, None
         fl = np.ascontiguousarray(win_flags, dtype=np.uint16)
         assert fl.shape == (self.n_streams, nf, self.channels), fl.shape
-        return fl, _vp(fl)
+        return fl, fl.ctypes.data
 
     def pqf(self, pcm):
         """pcm float32 [S, F, 2048, C] -> subbands [S, F, C, 16, 128]."""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (2048, self.channels), pcm.shape
         out = np.zeros((self.n_streams, pcm.shape[1], self.channels, 16, 128), np.float32)
-        self._check(self.lib.at3phip_pqf_analyse(self.ctx, _vp(pcm), pcm.shape[1], _vp(out), 0), "at3phip_pqf_analyse")
+        self.pqf_ptr(pcm.ctypes.data, pcm.shape[1], out.ctypes.data, 0)
         return out
 
     def mdct(self, bands, win_flags=None, residual_scale=False):
@@ -822,8 +773,7 @@ class At3pHip(_Context):
         nf = bands.shape[1]
         fl, flp = self._flags(win_flags, nf)
         out = np.zeros((self.n_streams, nf, self.channels, 2048), np.float32)
-        self._check(self.lib.at3phip_mdct(self.ctx, _vp(bands), nf, flp, _vp(out), AT3PHIP_RESIDUAL_SCALE if residual_scale else 0),
-                    "at3phip_mdct")
+        self.mdct_ptr(bands.ctypes.data, nf, flp, out.ctypes.data, AT3PHIP_RESIDUAL_SCALE if residual_scale else 0)
         return out
 
     def pqf_mdct(self, pcm, win_flags=None, residual_scale=False, want_bands=True):
@@ -832,13 +782,12 @@ class At3pHip(_Context):
         fl, flp = self._flags(win_flags, nf)
         bands = np.zeros((self.n_streams, nf, self.channels, 16, 128), np.float32) if want_bands else None
         specs = np.zeros((self.n_streams, nf, self.channels, 2048), np.float32)
-        self._check(self.lib.at3phip_pqf_mdct(self.ctx, _vp(pcm), nf, flp, _vp(bands) if want_bands else None, _vp(specs),
-                                              AT3PHIP_RESIDUAL_SCALE if residual_scale else 0), "at3phip_pqf_mdct")
+        self.pqf_mdct_ptr(pcm.ctypes.data, nf, flp, bands.ctypes.data if want_bands else None, specs.ctypes.data,
+                          AT3PHIP_RESIDUAL_SCALE if residual_scale else 0)
         return bands, specs
 
     def pqf_mdct_device(self, pcm_ptr, n_frames, specs_ptr):
-        self._check(self.lib.at3phip_pqf_mdct(self.ctx, ctypes.c_void_p(pcm_ptr), n_frames, None, None, ctypes.c_void_p(specs_ptr),
-                                              AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE), "at3phip_pqf_mdct")
+        self.pqf_mdct_ptr(pcm_ptr, n_frames, None, None, specs_ptr, _device_flags(False))
 
     def write_frames(self, specs, win_flags=None):
         """ScaleFrame + WriteFrame without tonal block: specs [S, F, C, 2048], win_flags uint16 [S, F, C] or None
@@ -848,76 +797,57 @@ class At3pHip(_Context):
         nf = specs.shape[1]
         fl, flp = self._flags(win_flags, nf)
         out = np.zeros((self.n_streams, nf, 2048), np.uint8)
-        self._check(self.lib.at3phip_write_frames(self.ctx, _vp(specs), nf, flp, _vp(out), 0), "at3phip_write_frames")
+        self.write_frames_ptr(specs.ctypes.data, nf, flp, out.ctypes.data, 0)
+        return out
+
+    def _encode_frames_host(self, pcm, dtype, raw):
+        pcm = np.ascontiguousarray(pcm, dtype=dtype)
+        assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (2048, self.channels), pcm.shape
+        nf = pcm.shape[1]
+        out = np.zeros((self.n_streams, nf, 2048), np.uint8)
+        raw(pcm.ctypes.data, nf, out.ctypes.data, 0)
         return out
 
     def encode_frames(self, pcm):
         """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, 2048] (tonal analysis finding nothing; no look-ahead delay)."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
-        assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (2048, self.channels), pcm.shape
-        nf = pcm.shape[1]
-        out = np.zeros((self.n_streams, nf, 2048), np.uint8)
-        self._check(self.lib.at3phip_encode_frames(self.ctx, _vp(pcm), nf, _vp(out), 0), "at3phip_encode_frames")
-        return out
-
-    def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
-        """asynchronous=True only queues the call (AT3HIP_ASYNC): sync() before the frames are read. The context's streams are
-        non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): they wait for no other stream, so whatever produces the PCM must be
-        complete before the call."""
-        self._check(self.lib.at3phip_encode_frames(self.ctx, ctypes.c_void_p(pcm_ptr), n_frames, ctypes.c_void_p(frames_ptr),
-                                                   AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)),
-                    "at3phip_encode_frames")
+        return self._encode_frames_host(pcm, np.float32, self.encode_frames_ptr)
 
     def encode_frames_s16(self, pcm):
         """pcm int16 [S, F, 2048, C] (host) -> frames uint8 [S, F, 2048] (at3phip_encode_frames_short): the frames of
         encode_frames() on pcm / 32768 as float32, bit for bit; the samples cross the bus as 16-bit and are widened by the
         filter bank. Calls of both kinds may alternate."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (2048, self.channels), pcm.shape
-        nf = pcm.shape[1]
-        out = np.zeros((self.n_streams, nf, 2048), np.uint8)
-        self._check(_s16_entry(self.lib, "at3phip_encode_frames_short")(self.ctx, _vp(pcm), nf, _vp(out), 0), "at3phip_encode_frames_short")
-        return out
+        return self._encode_frames_host(pcm, np.int16, self.encode_frames_s16_ptr)
+
+    def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
+        """asynchronous=True only queues the call (AT3HIP_ASYNC): sync() before the frames are read, and both buffers stay
+        untouched until then. The context's streams are non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): they wait for no
+        other stream, so whatever produces the PCM must be complete before the call."""
+        self.encode_frames_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous))
 
     def encode_frames_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
-        """Device-resident int16 PCM / frames (raw pointers; the PCM needs only 2-byte alignment). The context's streams are
-        non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): they wait for no other stream, so whatever produces the PCM must
-        be complete before the call, and with asynchronous=True (AT3HIP_ASYNC) both buffers stay untouched until sync()."""
-        self._check(_s16_entry(self.lib, "at3phip_encode_frames_short")(
-            self.ctx, ctypes.c_void_p(pcm_ptr), n_frames, ctypes.c_void_p(frames_ptr),
-            AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)), "at3phip_encode_frames_short")
+        """Device-resident int16 PCM / frames (raw pointers; the PCM needs only 2-byte alignment). Stream ordering and what
+        stays untouched until sync() as in encode_frames_device."""
+        self.encode_frames_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous))
 
     def timings(self):
         a, b, w = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-        self._check(self.lib.at3phip_get_timings(self.ctx, ctypes.byref(a), ctypes.byref(b)), "at3phip_get_timings")
-        self._check(self.lib.at3phip_get_write_timing(self.ctx, ctypes.byref(w)), "at3phip_get_write_timing")
+        self._call("get_timings", ctypes.byref(a), ctypes.byref(b))
+        self._call("get_write_timing", ctypes.byref(w))
         return {"pqf_ms": a.value, "mdct_ms": b.value, "write_ms": w.value}
-
-
-def _resampler_lib(lib_path):
-    lib = load_library(lib_path)
-    if not hasattr(lib, "at3hip_resampler_create"):
-        raise At3HipError("libat3hip.so predates the resampler (no at3hip_resampler_create): rebuild it")
-    return lib
 
 
 def resampler_shape(in_rate, out_rate, lib_path=None):
     """at3hip_resampler_shape (no GPU): (L phases, M input step, K taps per phase) of a supported pair."""
     L, M, K = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-    rc = _resampler_lib(lib_path).at3hip_resampler_shape(int(in_rate), int(out_rate), ctypes.byref(L), ctypes.byref(M), ctypes.byref(K))
-    if rc != 0:
-        raise At3HipError(f"at3hip_resampler_shape({in_rate}, {out_rate}) failed ({rc}): unsupported pair")
+    _lib_call(lib_path, "at3hip_resampler_shape", int(in_rate), int(out_rate), ctypes.byref(L), ctypes.byref(M), ctypes.byref(K),
+              why=f": {in_rate} -> {out_rate} is an unsupported pair")
     return L.value, M.value, K.value
 
 
 def resampler_host_tables(in_rate, out_rate, lib_path=None):
     """at3hip_resampler_host_tables (no GPU): the filter table hp float32 [L][K] as at3hip_resampler_create builds it."""
     L, _, K = resampler_shape(in_rate, out_rate, lib_path)
-    out = np.zeros((L, K), np.float32)
-    rc = _resampler_lib(lib_path).at3hip_resampler_host_tables(int(in_rate), int(out_rate), _vp(out), out.nbytes)
-    if rc != 0:
-        raise At3HipError(f"at3hip_resampler_host_tables failed ({rc})")
-    return out
+    return _host_tables(lib_path, "at3hip_resampler_host_tables", np.zeros((L, K), np.float32), int(in_rate), int(out_rate))
 
 
 class HipResampler(_Context):
@@ -927,12 +857,12 @@ class HipResampler(_Context):
     _PREFIX = "at3hip_resampler"
 
     def __init__(self, in_rate, out_rate, channels=2, n_streams=1, max_in=1 << 16, device_id=0, lib_path=None):
-        self.lib = _resampler_lib(lib_path)
+        self.lib = load_library(lib_path)
         self.in_rate, self.out_rate = int(in_rate), int(out_rate)
         self.channels, self.n_streams, self.max_in = int(channels), int(n_streams), int(max_in)
         self._create(ResamplerConfig(self.in_rate, self.out_rate, self.channels, self.n_streams, self.max_in, int(device_id)),
                      "unsupported rates or configuration, or no usable MI355X / HIP runtime")
-        self.max_out = int(self.lib.at3hip_resampler_max_out(self.ctx))
+        self.max_out = int(self._value("max_out"))
         self.L, self.M, self.K = resampler_shape(self.in_rate, self.out_rate, lib_path)
 
     def process_ptr(self, in_ptr, n_in, out_ptr, flags):
@@ -940,25 +870,20 @@ class HipResampler(_Context):
         stream. The resampler's stream is non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): it waits for no other stream, so
         whatever produces a device buffer must be complete before the call (or share the stream given to set_stream)."""
         n = ctypes.c_int32()
-        self._check(self.lib.at3hip_resampler_process(self.ctx, ctypes.c_void_p(in_ptr), int(n_in), ctypes.c_void_p(out_ptr),
-                                                      ctypes.byref(n), int(flags)), "at3hip_resampler_process")
-        return n.value
-
-    def flush_ptr(self, out_ptr, flags):
-        n = ctypes.c_int32()
-        self._check(self.lib.at3hip_resampler_flush(self.ctx, ctypes.c_void_p(out_ptr), ctypes.byref(n), int(flags)),
-                    "at3hip_resampler_flush")
+        self._call("process", ctypes.c_void_p(in_ptr), int(n_in), ctypes.c_void_p(out_ptr), ctypes.byref(n), int(flags))
         return n.value
 
     def process_s16_ptr(self, in_ptr, n_in, out_ptr, flags):
         """Raw pointers and at3hip_resampler_process_s16 flags (int16 input, 2-byte alignment is enough; out float32, or int16
-        with AT3HIP_RESAMPLE_OUT_S16); returns the outputs per stream. The resampler's stream is non-blocking (at3hip.h, DEVICE
-        BUFFERS AND STREAMS): it waits for no other stream, so whatever produces a device buffer must be complete before the
-        call (or share the stream given to set_stream), and with AT3HIP_ASYNC the buffers stay untouched until sync()."""
+        with AT3HIP_RESAMPLE_OUT_S16); returns the outputs per stream. Stream ordering as in process_ptr, and with AT3HIP_ASYNC
+        the buffers stay untouched until sync()."""
         n = ctypes.c_int32()
-        self._check(_s16_entry(self.lib, "at3hip_resampler_process_s16")(
-            self.ctx, ctypes.c_void_p(in_ptr), int(n_in), ctypes.c_void_p(out_ptr), ctypes.byref(n), int(flags)),
-            "at3hip_resampler_process_s16")
+        self._call("process_s16", ctypes.c_void_p(in_ptr), int(n_in), ctypes.c_void_p(out_ptr), ctypes.byref(n), int(flags))
+        return n.value
+
+    def flush_ptr(self, out_ptr, flags):
+        n = ctypes.c_int32()
+        self._call("flush", ctypes.c_void_p(out_ptr), ctypes.byref(n), int(flags))
         return n.value
 
     def _host_out(self, out_s16):
@@ -967,25 +892,24 @@ class HipResampler(_Context):
     def _trim(self, out, n):
         return np.ascontiguousarray(out.reshape(-1)[: self.n_streams * n * self.channels].reshape(self.n_streams, n, self.channels))
 
+    def _process_host(self, pcm, dtype, raw, out_s16):
+        pcm = np.ascontiguousarray(pcm, dtype=dtype)
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
+        out = self._host_out(out_s16)
+        n = raw(pcm.ctypes.data, pcm.shape[1], out.ctypes.data, AT3HIP_RESAMPLE_OUT_S16 if out_s16 else 0)
+        return self._trim(out, n)
+
     def process(self, pcm, out_s16=False):
         """pcm float32 [n_streams, n_in, channels] (host) -> float32 [n_streams, n_out, channels]; with out_s16=True int16,
         lrintf(clamp(x, -1, 1) * 32767) of the float output (AT3HIP_RESAMPLE_OUT_S16). A blocking call on the resampler's own
         non-blocking stream (at3hip.h, DEVICE BUFFERS AND STREAMS): host memory in, host memory out, complete on return."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
-        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
-        out = self._host_out(out_s16)
-        n = self.process_ptr(pcm.ctypes.data, pcm.shape[1], out.ctypes.data, AT3HIP_RESAMPLE_OUT_S16 if out_s16 else 0)
-        return self._trim(out, n)
+        return self._process_host(pcm, np.float32, self.process_ptr, out_s16)
 
     def process_s16(self, pcm, out_s16=False):
         """pcm int16 [n_streams, n_in, channels] (host) -> what process() gives on pcm / 32768 as float32, bit for bit
         (at3hip_resampler_process_s16): the samples cross the bus as 16-bit and are widened by the kernel. Calls of both kinds
         may alternate. Blocking, as process()."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
-        out = self._host_out(out_s16)
-        n = self.process_s16_ptr(pcm.ctypes.data, pcm.shape[1], out.ctypes.data, AT3HIP_RESAMPLE_OUT_S16 if out_s16 else 0)
-        return self._trim(out, n)
+        return self._process_host(pcm, np.int16, self.process_s16_ptr, out_s16)
 
     def flush(self, out_s16=False):
         """The remaining outputs of every stream, float32 (int16 with out_s16=True) [n_streams, n_out, channels]; then the start
@@ -1007,22 +931,14 @@ class HipResampler(_Context):
         assert pcm.dtype == torch.float32 and pcm.is_contiguous()
         assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, tuple(pcm.shape)
         self._device_out(out, pcm.device)
-        _Decoder._order_behind_torch(self, pcm.device, ordered)
-        flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0)
-        return self.process_ptr(pcm.data_ptr(), pcm.shape[1], out.data_ptr(), flags)
+        self._order_behind_torch(pcm.device, ordered)
+        return self.process_ptr(pcm.data_ptr(), pcm.shape[1], out.data_ptr(), _device_flags(asynchronous))
 
     def flush_device(self, out, asynchronous=False, ordered=True):
         """flush into a torch tensor, as process_device; returns n."""
         self._device_out(out, out.device)
-        _Decoder._order_behind_torch(self, out.device, ordered)
+        self._order_behind_torch(out.device, ordered)
         return self.flush_ptr(out.data_ptr(), AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0))
-
-
-def _loudness_lib(lib_path):
-    lib = load_library(lib_path)
-    if not hasattr(lib, "at3hip_loudness_create"):
-        raise At3HipError("libat3hip.so predates the loudness meter (no at3hip_loudness_create): rebuild it")
-    return lib
 
 
 def loudness_gate(z, lib_path=None):
@@ -1031,9 +947,7 @@ def loudness_gate(z, lib_path=None):
     z = np.ascontiguousarray(z, np.float64)
     assert z.ndim == 2 and z.shape[1] in (1, 2), z.shape
     r = LoudnessResult()
-    rc = _loudness_lib(lib_path).at3hip_loudness_gate(_vp(z), z.shape[0], z.shape[1], ctypes.byref(r))
-    if rc != 0:
-        raise At3HipError(f"at3hip_loudness_gate failed ({rc})")
+    _lib_call(lib_path, "at3hip_loudness_gate", _vp(z), z.shape[0], z.shape[1], ctypes.byref(r))
     return r
 
 
@@ -1043,9 +957,7 @@ def loudness_gain(result, target_lufs, ceiling_db=-1.0, lib_path=None):
     g = ctypes.c_float()
     if not isinstance(result, LoudnessResult):   # (a structure of the same layout)
         result = LoudnessResult.from_buffer_copy(bytes(result))
-    rc = _loudness_lib(lib_path).at3hip_loudness_gain(ctypes.byref(result), float(target_lufs), float(ceiling_db), ctypes.byref(g))
-    if rc != 0:
-        raise At3HipError(f"at3hip_loudness_gain failed ({rc})")
+    _lib_call(lib_path, "at3hip_loudness_gain", ctypes.byref(result), float(target_lufs), float(ceiling_db), ctypes.byref(g))
     return np.float32(g.value)
 
 
@@ -1063,7 +975,7 @@ class HipLoudness(_Context):
     _PREFIX = "at3hip_loudness"
 
     def __init__(self, channels=2, n_streams=1, max_in=1 << 16, max_hops=36000, true_peak=False, device_id=0, lib_path=None):
-        self.lib = _loudness_lib(lib_path)
+        self.lib = load_library(lib_path)
         self.channels, self.n_streams, self.max_in, self.max_hops = int(channels), int(n_streams), int(max_in), int(max_hops)
         self.true_peak = bool(true_peak)
         self.n_samples = 0   # per stream since the start / the last finish() or reset()
@@ -1079,18 +991,21 @@ class HipLoudness(_Context):
         self._call("process", ctypes.c_void_p(in_ptr), int(n_in), int(flags))
         self.n_samples += int(n_in)
 
-    def process(self, pcm):
-        """pcm float32 [n_streams, n_in, channels] (host)"""
-        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
-        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
-        self.process_ptr(pcm.ctypes.data, pcm.shape[1], 0)
-
     def process_s16_ptr(self, in_ptr, n_in, flags):
         """Raw pointer (int16 samples, 2-byte alignment is enough) and at3hip_loudness_process_s16 flags; stream ordering as in
         the class docstring: the meter's non-blocking stream waits for no other stream."""
-        self._check(_s16_entry(self.lib, "at3hip_loudness_process_s16")(self.ctx, ctypes.c_void_p(in_ptr), int(n_in), int(flags)),
-                    "at3hip_loudness_process_s16")
+        self._call("process_s16", ctypes.c_void_p(in_ptr), int(n_in), int(flags))
         self.n_samples += int(n_in)
+
+    def _host_pcm(self, pcm, dtype):
+        pcm = np.ascontiguousarray(pcm, dtype=dtype)
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
+        return pcm
+
+    def process(self, pcm):
+        """pcm float32 [n_streams, n_in, channels] (host)"""
+        pcm = self._host_pcm(pcm, np.float32)
+        self.process_ptr(pcm.ctypes.data, pcm.shape[1], 0)
 
     def process_s16(self, pcm):
         """pcm int16 [n_streams, n_in, channels] (host): what process() measures on pcm / 32768 as float32, bit for bit
@@ -1098,8 +1013,7 @@ class HipLoudness(_Context):
         may alternate. A blocking call on the meter's own non-blocking stream (see the class docstring). Measured: the meter is
         compute-bound and its hop kernel takes 1.5 times as long on 16-bit samples, so from host memory this is 1.1 times as
         fast as process(), and on device-resident floats process_device() is the faster call."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
+        pcm = self._host_pcm(pcm, np.int16)
         self.process_s16_ptr(pcm.ctypes.data, pcm.shape[1], 0)
 
     def process_device(self, pcm, asynchronous=False, ordered=True):
@@ -1107,7 +1021,7 @@ class HipLoudness(_Context):
         import torch
         assert pcm.dtype == torch.float32 and pcm.is_contiguous()
         assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, tuple(pcm.shape)
-        _Decoder._order_behind_torch(self, pcm.device, ordered)
+        self._order_behind_torch(pcm.device, ordered)
         self.process_ptr(pcm.data_ptr(), pcm.shape[1], AT3HIP_PCM_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0))
 
     def hops(self):
@@ -1124,34 +1038,34 @@ class HipLoudness(_Context):
         self.n_samples = 0
         return list(res)
 
-    def apply_ptr(self, in_ptr, n_in, gains, out_ptr, flags):
+    def _gains(self, gains):
         gains = np.ascontiguousarray(gains, np.float32)
         assert gains.shape == (self.n_streams,), gains.shape
-        self._call("apply", ctypes.c_void_p(in_ptr), int(n_in), _vp(gains), ctypes.c_void_p(out_ptr), int(flags))
+        return gains
 
-    def apply(self, pcm, gains):
-        """pcm float32 [n_streams, n_in, channels] (host), gains float32 [n_streams] -> pcm * gains[:, None, None] as float32"""
-        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
-        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
-        out = np.zeros_like(pcm)
-        self.apply_ptr(pcm.ctypes.data, pcm.shape[1], gains, out.ctypes.data, 0)
-        return out
+    def apply_ptr(self, in_ptr, n_in, gains, out_ptr, flags):
+        gains = self._gains(gains)
+        self._call("apply", ctypes.c_void_p(in_ptr), int(n_in), _vp(gains), ctypes.c_void_p(out_ptr), int(flags))
 
     def apply_s16_ptr(self, in_ptr, n_in, gains, out_ptr, flags):
         """Raw pointers (int16 in, float32 out) and at3hip_loudness_apply_s16 flags; stream ordering as in the class docstring."""
-        gains = np.ascontiguousarray(gains, np.float32)
-        assert gains.shape == (self.n_streams,), gains.shape
-        self._check(_s16_entry(self.lib, "at3hip_loudness_apply_s16")(self.ctx, ctypes.c_void_p(in_ptr), int(n_in), _vp(gains),
-                                                                      ctypes.c_void_p(out_ptr), int(flags)), "at3hip_loudness_apply_s16")
+        gains = self._gains(gains)
+        self._call("apply_s16", ctypes.c_void_p(in_ptr), int(n_in), _vp(gains), ctypes.c_void_p(out_ptr), int(flags))
+
+    def _apply_host(self, pcm, gains, dtype, raw):
+        pcm = self._host_pcm(pcm, dtype)
+        out = np.zeros(pcm.shape, np.float32)
+        raw(pcm.ctypes.data, pcm.shape[1], gains, out.ctypes.data, 0)
+        return out
+
+    def apply(self, pcm, gains):
+        """pcm float32 [n_streams, n_in, channels] (host), gains float32 [n_streams] -> pcm * gains[:, None, None] as float32"""
+        return self._apply_host(pcm, gains, np.float32, self.apply_ptr)
 
     def apply_s16(self, pcm, gains):
         """pcm int16 [n_streams, n_in, channels] (host), gains float32 [n_streams] -> (pcm / 32768 as float32) * gains[:, None, None]
         as float32 (at3hip_loudness_apply_s16). A blocking call on the meter's own non-blocking stream (see the class docstring)."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, pcm.shape
-        out = np.zeros(pcm.shape, np.float32)
-        self.apply_s16_ptr(pcm.ctypes.data, pcm.shape[1], gains, out.ctypes.data, 0)
-        return out
+        return self._apply_host(pcm, gains, np.int16, self.apply_s16_ptr)
 
     def apply_device(self, pcm, gains, out, asynchronous=False, ordered=True):
         """Torch tensors on this meter's device: out = pcm * gains[stream] (out may be pcm); ordering as process_device."""
@@ -1159,6 +1073,5 @@ class HipLoudness(_Context):
         assert pcm.dtype == torch.float32 and pcm.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous()
         assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, tuple(pcm.shape)
         assert out.device == pcm.device and out.numel() >= pcm.numel()
-        _Decoder._order_behind_torch(self, pcm.device, ordered)
-        self.apply_ptr(pcm.data_ptr(), pcm.shape[1], gains, out.data_ptr(),
-                       AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0))
+        self._order_behind_torch(pcm.device, ordered)
+        self.apply_ptr(pcm.data_ptr(), pcm.shape[1], gains, out.data_ptr(), _device_flags(asynchronous))

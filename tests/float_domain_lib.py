@@ -209,7 +209,6 @@ AT3_CASES = ((132300, 0, 0, 2, NAMES), (132300, 1, 1, 2, NAMES), (66150, 0, 0, 2
 
 def at3_run(lib_path, br, ng, nt, channels=2, names=NAMES, split=None):
     """(frames [S, 11, frame_size], (scale_overflow, clipped_values)) of one context over the batch, fed whole or as `split`"""
-    import ctypes
     from atracdenc_amd.binding import At3Hip
     pcm = np.ascontiguousarray(at3_batch(names)[..., :channels])
     S, nb = pcm.shape[:2]
@@ -219,10 +218,7 @@ def at3_run(lib_path, br, ng, nt, channels=2, names=NAMES, split=None):
         for k in (split or (nb,)):
             piece = np.ascontiguousarray(pcm[:, at:at + k])
             out = _sent(S * k * fs, np.uint8)
-            nf = ctypes.c_int32()
-            enc._check(enc.lib.at3hip_encode(enc.ctx, piece.ctypes.data_as(ctypes.c_void_p), k, out.ctypes.data_as(ctypes.c_void_p),
-                                             ctypes.byref(nf), 0), "at3hip_encode")
-            n = nf.value
+            n = enc.encode_ptr(piece.ctypes.data, k, out.ctypes.data, 0)
             assert (out[S * n * fs:] == SENT_U8).all(), "bytes past the packed frames were written"
             parts.append(out[:S * n * fs].reshape(S, n, fs))
             at += k
@@ -252,7 +248,6 @@ AT1_CASES = (("auto", 2), ("auto", 1), ("short", 2), ("short", 1))   # (mode, ch
 
 def at1_run(lib_path, mode, nch, names=NAMES, split=None):
     """(sound units [S, 24, nch, 212], loudness tap [S, 24]) of one context"""
-    import ctypes
     from at3_testlib import AT1_MODES
     from atracdenc_amd.binding import At1Hip
     pcm = at1_batch(nch, names)
@@ -264,8 +259,7 @@ def at1_run(lib_path, mode, nch, names=NAMES, split=None):
         for k in (split or (nb,)):
             piece = np.ascontiguousarray(pcm[:, at:at + k])
             out = _sent((S, k, nch, 212), np.uint8)
-            enc._check(enc.lib.at1hip_encode(enc.ctx, piece.ctypes.data_as(ctypes.c_void_p), k, out.ctypes.data_as(ctypes.c_void_p), 0),
-                       "at1hip_encode")
+            enc.encode_ptr(piece.ctypes.data, k, out.ctypes.data, 0)
             units.append(out)
             loud.append(enc.read_tap(At1Hip.TAP_LOUDNESS, np.float32, (S, k)))
             at += k
@@ -288,7 +282,6 @@ AT3P_SPLIT = (2, 1, 3)
 
 def at3p_run(lib_path, nch, names=NAMES, split=None):
     """frames [S, 6, 2048] of encode_frames"""
-    import ctypes
     from atracdenc_amd.binding import At3pHip
     pcm = at3p_batch(nch, names)
     S, nf = pcm.shape[:2]
@@ -298,8 +291,7 @@ def at3p_run(lib_path, nch, names=NAMES, split=None):
         for k in (split or (nf,)):
             piece = np.ascontiguousarray(pcm[:, at:at + k])
             out = _sent((S, k, 2048), np.uint8)
-            enc._check(enc.lib.at3phip_encode_frames(enc.ctx, piece.ctypes.data_as(ctypes.c_void_p), k,
-                                                     out.ctypes.data_as(ctypes.c_void_p), 0), "at3phip_encode_frames")
+            enc.encode_frames_ptr(piece.ctypes.data, k, out.ctypes.data, 0)
             parts.append(out)
             at += k
     finally:

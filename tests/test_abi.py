@@ -28,6 +28,32 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
 
 
+def test_every_symbol_has_a_prototype():
+    """binding.PROTOTYPES is the one place prototypes come from: after load_library every listed function has argtypes, no
+    *_destroy returns a value, every *_last_error returns a string, and the three symbol lists are exactly the table's names,
+    which are exactly what the library exports (so an entry that goes missing is noticed here, not at a call)."""
+    import ctypes
+    import subprocess
+    import atracdenc_amd
+    if not os.path.exists(atracdenc_amd.LIB_PATH):
+        atracdenc_amd.build_library()
+    lib = atracdenc_amd.load_library()
+    b = atracdenc_amd.binding
+    names = b.SYMBOLS + b.AT1_SYMBOLS + b.AT3P_SYMBOLS
+    assert len(names) == len(set(names)) and set(names) == set(b.PROTOTYPES)
+    out = subprocess.check_output(["nm", "-D", "--defined-only", atracdenc_amd.LIB_PATH], text=True)
+    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert exported == set(b.PROTOTYPES), sorted(exported ^ set(b.PROTOTYPES))
+    for name in names:
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None, name
+        if name.endswith("_destroy"):
+            assert fn.restype is None, name
+        if name.endswith("_last_error"):
+            assert fn.restype is ctypes.c_char_p, name
+    assert sum(n.endswith("_destroy") for n in names) == sum(n.endswith("_last_error") for n in names) == 8
+
+
 def test_library_exports_nothing_but_the_c_abi():
     """Built with -fvisibility=hidden and csrc/exports.map: `nm -D` shows the three C ABIs of include/ and nothing else
     (no kernel stubs, no table builders, no C++ symbols)."""

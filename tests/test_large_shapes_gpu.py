@@ -8,7 +8,6 @@ sentinel before the call (0xA5 bytes, NaN floats, 0x5A5A samples), so a region t
 streams go through a small context, and that small run is itself checked against the CPU oracle or the C restatement. Then
 every replica of the large output is compared with its small-run counterpart on the device, every element (floats as bit
 patterns), and the counters of the large run must be the replica-weighted sum of the per-stream counts."""
-import ctypes
 import os
 
 import numpy as np
@@ -145,12 +144,10 @@ def _at3_oracle(oracle, pcm, br, ng):
 
 def _at3_encode(enc, pcm_ptr, nb, out, s16=False, host=False):
     """one synchronous call into a sentinel-filled output; returns frames per stream"""
-    nf = ctypes.c_int32()
-    fn = enc.lib.at3hip_encode_s16 if s16 else enc.lib.at3hip_encode
+    raw = enc.encode_s16_ptr if s16 else enc.encode_ptr
     flags = 0 if host else AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE
     outp = out.ctypes.data if host else out.data_ptr()
-    enc._check(fn(enc.ctx, ctypes.c_void_p(pcm_ptr), nb, ctypes.c_void_p(outp), ctypes.byref(nf), flags), "at3hip_encode")
-    return nf.value
+    return raw(pcm_ptr, nb, outp, flags)
 
 
 @pytest.mark.parametrize("mode", ["lp2_gain_tonal", "lp2_no_gain", "lp4_joint_stereo"])

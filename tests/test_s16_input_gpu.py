@@ -3,13 +3,12 @@ at3phip_encode_frames_short, at3hip_resampler_process_s16 with AT3HIP_RESAMPLE_O
 _apply_s16): every 16-bit entry point gives, bit for bit, what the float entry point gives on the widened input
 ((float)s * 0x1p-15f), also with the two kinds of call alternating on one context, from host memory and from device pointers
 that are only int16_t aligned. Every comparison is of bit patterns."""
-import ctypes
 
 import numpy as np
 import pytest
 
 import s16_lib as S
-from atracdenc_amd import At1Hip, At3pHip, HipLoudness, HipResampler
+from atracdenc_amd import At1Hip, At3HipError, At3pHip, HipLoudness, HipResampler
 from atracdenc_amd.binding import AT3HIP_OUT_ON_DEVICE, AT3HIP_PCM_ON_DEVICE, AT3HIP_RESAMPLE_OUT_S16
 
 pytestmark = pytest.mark.gpu
@@ -21,6 +20,11 @@ DEV = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE
 
 def assert_same(got, want, what):
     assert S.same_bits(got, want), what
+
+
+def einval(function):
+    """the call inside returns AT3HIP_EINVAL: the raw methods raise with the function's name and its status"""
+    return pytest.raises(At3HipError, match=rf"^{function} failed \({EINVAL}\)")
 
 
 class DevPcm:
@@ -280,8 +284,6 @@ def test_loudness_apply_s16(ld_case):
 # ---- arguments -----------------------------------------------------------------------------------------------------------------
 def test_bad_arguments_leave_the_contexts_usable():
     """NULL input and a count above the create-time limit are AT3HIP_EINVAL; the next good call gives what a fresh context gives"""
-    vp = ctypes.c_void_p
-    n = ctypes.c_int32()
     p16 = S.pcm16(1, 2048, 2, seed=7)
     pf = S.widen(p16)
 
@@ -290,8 +292,10 @@ def test_bad_arguments_leave_the_contexts_usable():
     try:
         out = np.zeros((1, 3, 2, 212), np.uint8)
         big = np.zeros((1, 3, 512, 2), np.int16)
-        assert enc.lib.at1hip_encode_short(enc.ctx, None, 1, vp(out.ctypes.data), 0) == EINVAL
-        assert enc.lib.at1hip_encode_short(enc.ctx, vp(big.ctypes.data), 3, vp(out.ctypes.data), 0) == EINVAL
+        with einval("at1hip_encode_short"):
+            enc.encode_s16_ptr(None, 1, out.ctypes.data, 0)
+        with einval("at1hip_encode_short"):
+            enc.encode_s16_ptr(big.ctypes.data, 3, out.ctypes.data, 0)
         assert_same(enc.encode_s16(p16.reshape(1, 4, 512, 2)[:, :2]), ref.encode(pf.reshape(1, 4, 512, 2)[:, :2]), "at1")
     finally:
         enc.close()
@@ -302,8 +306,10 @@ def test_bad_arguments_leave_the_contexts_usable():
     try:
         out = np.zeros((1, 2, 2048), np.uint8)
         big = np.zeros((1, 2, 2048, 2), np.int16)
-        assert enc.lib.at3phip_encode_frames_short(enc.ctx, None, 1, vp(out.ctypes.data), 0) == EINVAL
-        assert enc.lib.at3phip_encode_frames_short(enc.ctx, vp(big.ctypes.data), 2, vp(out.ctypes.data), 0) == EINVAL
+        with einval("at3phip_encode_frames_short"):
+            enc.encode_frames_s16_ptr(None, 1, out.ctypes.data, 0)
+        with einval("at3phip_encode_frames_short"):
+            enc.encode_frames_s16_ptr(big.ctypes.data, 2, out.ctypes.data, 0)
         assert_same(enc.encode_frames_s16(p16.reshape(1, 1, 2048, 2)), ref.encode_frames(pf.reshape(1, 1, 2048, 2)), "at3p")
     finally:
         enc.close()
@@ -313,8 +319,10 @@ def test_bad_arguments_leave_the_contexts_usable():
     ref = HipResampler(48000, 44100, channels=2, n_streams=1, max_in=1000)
     try:
         out = np.zeros((1, r.max_out, 2), np.float32)
-        assert r.lib.at3hip_resampler_process_s16(r.ctx, None, 10, vp(out.ctypes.data), ctypes.byref(n), 0) == EINVAL
-        assert r.lib.at3hip_resampler_process_s16(r.ctx, vp(p16.ctypes.data), 1001, vp(out.ctypes.data), ctypes.byref(n), 0) == EINVAL
+        with einval("at3hip_resampler_process_s16"):
+            r.process_s16_ptr(None, 10, out.ctypes.data, 0)
+        with einval("at3hip_resampler_process_s16"):
+            r.process_s16_ptr(p16.ctypes.data, 1001, out.ctypes.data, 0)
         assert_same(r.process_s16(p16[:, :1000]), ref.process(pf[:, :1000]), "resampler")
     finally:
         r.close()
@@ -325,10 +333,14 @@ def test_bad_arguments_leave_the_contexts_usable():
     try:
         g = np.array([0.31], np.float32)
         out = np.zeros((1, 1001, 2), np.float32)
-        assert m.lib.at3hip_loudness_process_s16(m.ctx, None, 10, 0) == EINVAL
-        assert m.lib.at3hip_loudness_process_s16(m.ctx, vp(p16.ctypes.data), 1001, 0) == EINVAL
-        assert m.lib.at3hip_loudness_apply_s16(m.ctx, None, 10, vp(g.ctypes.data), vp(out.ctypes.data), 0) == EINVAL
-        assert m.lib.at3hip_loudness_apply_s16(m.ctx, vp(p16.ctypes.data), 1001, vp(g.ctypes.data), vp(out.ctypes.data), 0) == EINVAL
+        with einval("at3hip_loudness_process_s16"):
+            m.process_s16_ptr(None, 10, 0)
+        with einval("at3hip_loudness_process_s16"):
+            m.process_s16_ptr(p16.ctypes.data, 1001, 0)
+        with einval("at3hip_loudness_apply_s16"):
+            m.apply_s16_ptr(None, 10, g, out.ctypes.data, 0)
+        with einval("at3hip_loudness_apply_s16"):
+            m.apply_s16_ptr(p16.ctypes.data, 1001, g, out.ctypes.data, 0)
         m.process_s16(p16[:, :1000])
         ref.process(pf[:, :1000])
         assert S.result_mismatches(m.finish()[0], ref.finish()[0]) == []

@@ -6,7 +6,7 @@ the driver of tests/test_host_call_trace.py. `--write` writes the goldens instea
 never looks at them. Runs of event creations with consecutive ordinals are folded into one line. Up to `# destroy` the order
 of the calls is compared; of *_destroy, every wait and every release it makes (each sorted: the order among them says nothing).
 The joint-stereo-with-gain and the one-channel case differ from the first one in their launches only and run a short script."""
-import ctypes, os, re, subprocess, sys, tempfile
+import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
 import numpy as np
@@ -71,17 +71,16 @@ def at1_case():
 def at3p_case():
     from atracdenc_amd import binding as b
     enc = b.At3pHip(n_streams=S, max_frames=2, channels=2, lib_path=run_emu.EMU)
-    vp = lambda a: ctypes.c_void_p(a.ctypes.data)
+    at = lambda a: a.ctypes.data
     pcm = np.zeros((S, 2, 2048, 2), np.float32)
     bands = enc.pqf(pcm)
     specs = enc.mdct(bands)
     enc.pqf_mdct(pcm)
     frames = enc.write_frames(specs)
-    lib, c = enc.lib, enc.ctx
-    enc._check(lib.at3phip_pqf_analyse(c, vp(pcm), 2, vp(bands), DEV), "at3phip_pqf_analyse")
-    enc._check(lib.at3phip_mdct(c, vp(bands), 2, None, vp(specs), DEV), "at3phip_mdct")
-    enc._check(lib.at3phip_pqf_mdct(c, vp(pcm), 2, None, vp(bands), vp(specs), DEV), "at3phip_pqf_mdct")
-    enc._check(lib.at3phip_write_frames(c, vp(specs), 2, None, vp(frames), DEV), "at3phip_write_frames")
+    enc.pqf_ptr(at(pcm), 2, at(bands), DEV)
+    enc.mdct_ptr(at(bands), 2, None, at(specs), DEV)
+    enc.pqf_mdct_ptr(at(pcm), 2, None, at(bands), at(specs), DEV)
+    enc.write_frames_ptr(at(specs), 2, None, at(frames), DEV)
     for _ in range(3): enc.encode_frames_device(pcm.ctypes.data, 2, frames.ctypes.data, asynchronous=True)
     enc.sync()
     enc.encode_frames_s16(np.zeros((S, 2, 2048, 2), np.int16))

@@ -19,7 +19,6 @@ The rounds alternate between this build and the parent build (float calls only: 
 spread of a figure is the range of its per-round medians. A child is a fresh process: the measuring process itself never opens
 the GPU."""
 import argparse
-import ctypes
 import json
 import os
 import subprocess
@@ -43,7 +42,6 @@ def child(lib_path, kinds, reps):
     import torch
     from atracdenc_amd.binding import At1Hip, At3pHip, HipLoudness, HipResampler
     dev = torch.device("cuda:0")
-    vp = ctypes.c_void_p
     rng = np.random.RandomState(1)
 
     def timed(queue, sync):
@@ -79,35 +77,34 @@ def child(lib_path, kinds, reps):
     a1 = At1Hip(n_streams=S, max_blocks=64, channels=2, lib_path=lib_path)
     a1_out = torch.zeros((S, 64, 2, 212), dtype=torch.uint8, device=dev)
     engines["at1_encode"] = (a1, S * 64 * 512 * 2, S * 64, "unit_pairs", {
-        "float": lambda p, f: a1._check(a1.lib.at1hip_encode(a1.ctx, vp(p), 64, vp(a1_out.data_ptr()), f | OUT_ON_DEVICE | ASYNC), "at1hip_encode"),
-        "s16": lambda p, f: a1._check(a1.lib.at1hip_encode_short(a1.ctx, vp(p), 64, vp(a1_out.data_ptr()), f | OUT_ON_DEVICE | ASYNC), "at1hip_encode_short")})
+        "float": lambda p, f: a1.encode_ptr(p, 64, a1_out.data_ptr(), f | OUT_ON_DEVICE | ASYNC),
+        "s16": lambda p, f: a1.encode_s16_ptr(p, 64, a1_out.data_ptr(), f | OUT_ON_DEVICE | ASYNC)})
     ap = At3pHip(n_streams=S, max_frames=16, channels=2, lib_path=lib_path)
     ap_out = torch.zeros((S, 16, 2048), dtype=torch.uint8, device=dev)
     engines["at3p_encode_frames"] = (ap, S * 16 * 2048 * 2, S * 16, "frames", {
-        "float": lambda p, f: ap._check(ap.lib.at3phip_encode_frames(ap.ctx, vp(p), 16, vp(ap_out.data_ptr()), f | OUT_ON_DEVICE | ASYNC), "at3phip_encode_frames"),
-        "s16": lambda p, f: ap._check(ap.lib.at3phip_encode_frames_short(ap.ctx, vp(p), 16, vp(ap_out.data_ptr()), f | OUT_ON_DEVICE | ASYNC), "at3phip_encode_frames_short")})
+        "float": lambda p, f: ap.encode_frames_ptr(p, 16, ap_out.data_ptr(), f | OUT_ON_DEVICE | ASYNC),
+        "s16": lambda p, f: ap.encode_frames_s16_ptr(p, 16, ap_out.data_ptr(), f | OUT_ON_DEVICE | ASYNC)})
     n_rs = 32768
     rs = HipResampler(48000, 44100, channels=2, n_streams=S, max_in=n_rs, lib_path=lib_path)
     rs_out = torch.zeros((S, rs.max_out, 2), dtype=torch.float32, device=dev)
-    n_out = ctypes.c_int32()
     engines["resampler_48000_44100"] = (rs, S * n_rs * 2, S * n_rs, "input_samples", {
-        "float": lambda p, f: rs._check(rs.lib.at3hip_resampler_process(rs.ctx, vp(p), n_rs, vp(rs_out.data_ptr()), ctypes.byref(n_out), f | OUT_ON_DEVICE | ASYNC), "at3hip_resampler_process"),
-        "s16": lambda p, f: rs._check(rs.lib.at3hip_resampler_process_s16(rs.ctx, vp(p), n_rs, vp(rs_out.data_ptr()), ctypes.byref(n_out), f | OUT_ON_DEVICE | ASYNC), "at3hip_resampler_process_s16")})
+        "float": lambda p, f: rs.process_ptr(p, n_rs, rs_out.data_ptr(), f | OUT_ON_DEVICE | ASYNC),
+        "s16": lambda p, f: rs.process_s16_ptr(p, n_rs, rs_out.data_ptr(), f | OUT_ON_DEVICE | ASYNC)})
     n_ld = 65536
     ld = HipLoudness(channels=2, n_streams=S, max_in=n_ld, max_hops=n_ld // 4410, true_peak=False, lib_path=lib_path)
 
-    def meter(name):
+    def meter(process_ptr):
         def queue(p, f):
-            ld._check(ld.lib.at3hip_loudness_reset(ld.ctx), "at3hip_loudness_reset")
-            ld._check(getattr(ld.lib, name)(ld.ctx, vp(p), n_ld, f | ASYNC), name)
+            ld.reset()
+            process_ptr(p, n_ld, f | ASYNC)
         return queue
 
-    engines["loudness_process"] = (ld, S * n_ld * 2, S * n_ld, "samples", {"float": meter("at3hip_loudness_process"), "s16": meter("at3hip_loudness_process_s16")})
+    engines["loudness_process"] = (ld, S * n_ld * 2, S * n_ld, "samples", {"float": meter(ld.process_ptr), "s16": meter(ld.process_s16_ptr)})
     ld_out = torch.zeros((S, n_ld, 2), dtype=torch.float32, device=dev)
     gains = np.full(S, 0.7371, np.float32)
     engines["loudness_apply"] = (ld, S * n_ld * 2, S * n_ld, "samples", {
-        "float": lambda p, f: ld._check(ld.lib.at3hip_loudness_apply(ld.ctx, vp(p), n_ld, vp(gains.ctypes.data), vp(ld_out.data_ptr()), f | OUT_ON_DEVICE | ASYNC), "at3hip_loudness_apply"),
-        "s16": lambda p, f: ld._check(ld.lib.at3hip_loudness_apply_s16(ld.ctx, vp(p), n_ld, vp(gains.ctypes.data), vp(ld_out.data_ptr()), f | OUT_ON_DEVICE | ASYNC), "at3hip_loudness_apply_s16")})
+        "float": lambda p, f: ld.apply_ptr(p, n_ld, gains, ld_out.data_ptr(), f | OUT_ON_DEVICE | ASYNC),
+        "s16": lambda p, f: ld.apply_s16_ptr(p, n_ld, gains, ld_out.data_ptr(), f | OUT_ON_DEVICE | ASYNC)})
 
     result = {}
     for name, (ctx, n, units, unit_name, queues) in engines.items():
