@@ -171,6 +171,7 @@ PROTOTYPES = {
     "at3phip_reset": (_RC, [_VP]), "at3phip_sync": (_RC, [_VP]),
     "at3phip_pqf_analyse": (_RC, [_VP, _VP, _I32, _VP, _U32]), "at3phip_mdct": (_RC, [_VP, _VP, _I32, _VP, _VP, _U32]),
     "at3phip_pqf_mdct": (_RC, [_VP, _VP, _I32, _VP, _VP, _VP, _U32]), "at3phip_write_frames": (_RC, [_VP, _VP, _I32, _VP, _VP, _U32]),
+    "at3phip_write_frames_tonal": (_RC, [_VP, _VP, _I32, _VP, _VP, _VP, _U32]),
     "at3phip_encode_frames": (_RC, [_VP, _VP, _I32, _VP, _U32]), "at3phip_encode_frames_short": (_RC, [_VP, _VP, _I32, _VP, _U32]),
     "at3phip_get_timings": (_RC, [_VP, _F32P, _F32P]), "at3phip_get_write_timing": (_RC, [_VP, _F32P]),
     "at3phip_host_tables": (_RC, [_VP, _SZ]), "at3phip_host_write_tables": (_RC, [_VP, _SZ]),
@@ -717,6 +718,42 @@ def at3p_host_tables(lib_path=None):
     return _host_tables(lib_path, "at3phip_host_tables", np.zeros((), dtype=AT3P_TABLES_DTYPE))
 
 
+# at3phip_tonal_block: one frame's tonal block for at3phip_write_frames_tonal (all zero: no tonal block)
+AT3P_TONAL_BLOCK_DTYPE = np.dtype([("num_tone_bands", "u1"), ("second_is_leader", "u1"), ("tone_sharing", "<u2"),
+                                   ("band", [("n_waves", "u1"), ("start", "u1"), ("stop", "u1"), ("reserved", "u1")], (2, 16)),
+                                   ("wave", "<u4", 48)])
+assert AT3P_TONAL_BLOCK_DTYPE.itemsize == 324
+
+
+def pack_tonal_blocks(blocks, channels):
+    """Records of AT3P_TONAL_BLOCK_DTYPE, shaped like `blocks`, from (nested lists of) blocks in dict form, None standing for
+    "no tonal block": {"nb": NumToneBands, "shared": [nb] bools, "leader": bool, "bands": [ch][nb] {"start": None | 0..31,
+    "stop": None | 0..31, "waves": [(FreqIndex, AmpSf, PhaseIndex)]}}. Nothing is checked here (values are masked to their
+    fields' widths): the contract is at3phip_write_frames_tonal's."""
+    if isinstance(blocks, (list, tuple)):
+        return np.stack([pack_tonal_blocks(b, channels) for b in blocks]) if len(blocks) else np.zeros(0, AT3P_TONAL_BLOCK_DTYPE)
+    rec = np.zeros((), AT3P_TONAL_BLOCK_DTYPE)
+    b = blocks
+    if b is None:
+        return rec
+    nb = int(b["nb"])
+    rec["num_tone_bands"] = nb & 0xff
+    rec["second_is_leader"] = int(b.get("leader", False)) & 0xff
+    rec["tone_sharing"] = sum(int(bool(x)) << i for i, x in enumerate(b.get("shared", [])[:16]))
+    at = 0
+    for ch in range(channels):
+        for i, bd in enumerate(b["bands"][ch][:16]):
+            band = rec["band"][ch, i]
+            band["n_waves"] = len(bd["waves"]) & 0xff
+            band["start"] = 0 if bd["start"] is None else (int(bd["start"]) + 1) & 0xff
+            band["stop"] = 0 if bd["stop"] is None else (int(bd["stop"]) + 1) & 0xff
+            for fq, sf, ph in bd["waves"]:
+                if at < 48:
+                    rec["wave"][at] = (int(fq) | int(sf) << 10 | int(ph) << 16) & 0xffffffff
+                at += 1
+    return rec
+
+
 class At3pHip(_Context):
     """ATRAC3plus front end (include/at3phip.h): PQF analysis and windowed MDCT-256 x 16 for n_streams streams."""
 
@@ -742,6 +779,10 @@ class At3pHip(_Context):
     def write_frames_ptr(self, specs_ptr, n_frames, win_flags_ptr, frames_ptr, flags):
         self._call("write_frames", ctypes.c_void_p(specs_ptr), int(n_frames), ctypes.c_void_p(win_flags_ptr),
                    ctypes.c_void_p(frames_ptr), int(flags))
+
+    def write_frames_tonal_ptr(self, specs_ptr, n_frames, win_flags_ptr, tonal_ptr, frames_ptr, flags):
+        self._call("write_frames_tonal", ctypes.c_void_p(specs_ptr), int(n_frames), ctypes.c_void_p(win_flags_ptr),
+                   ctypes.c_void_p(tonal_ptr), ctypes.c_void_p(frames_ptr), int(flags))
 
     def encode_frames_ptr(self, pcm_ptr, n_frames, frames_ptr, flags):
         """Raw pointers (float32 PCM) and at3phip_encode_frames flags."""
@@ -789,15 +830,21 @@ class At3pHip(_Context):
     def pqf_mdct_device(self, pcm_ptr, n_frames, specs_ptr):
         self.pqf_mdct_ptr(pcm_ptr, n_frames, None, None, specs_ptr, _device_flags(False))
 
-    def write_frames(self, specs, win_flags=None):
-        """ScaleFrame + WriteFrame without tonal block: specs [S, F, C, 2048], win_flags uint16 [S, F, C] or None
+    def write_frames(self, specs, win_flags=None, tonal=None):
+        """ScaleFrame + WriteFrame: specs [S, F, C, 2048], win_flags uint16 [S, F, C] or None, tonal records of
+        AT3P_TONAL_BLOCK_DTYPE [S, F] (pack_tonal_blocks) or None: no frame carries a tonal block (at3phip_write_frames)
         -> frames uint8 [S, F, 2048]."""
         specs = np.ascontiguousarray(specs, dtype=np.float32)
         assert specs.ndim == 4 and specs.shape[0] == self.n_streams and specs.shape[2:] == (self.channels, 2048), specs.shape
         nf = specs.shape[1]
         fl, flp = self._flags(win_flags, nf)
         out = np.zeros((self.n_streams, nf, 2048), np.uint8)
-        self.write_frames_ptr(specs.ctypes.data, nf, flp, out.ctypes.data, 0)
+        if tonal is None:
+            self.write_frames_ptr(specs.ctypes.data, nf, flp, out.ctypes.data, 0)
+        else:
+            tonal = np.ascontiguousarray(tonal, dtype=AT3P_TONAL_BLOCK_DTYPE)
+            assert tonal.shape == (self.n_streams, nf), tonal.shape
+            self.write_frames_tonal_ptr(specs.ctypes.data, nf, flp, tonal.ctypes.data, out.ctypes.data, 0)
         return out
 
     def _encode_frames_host(self, pcm, dtype, raw):

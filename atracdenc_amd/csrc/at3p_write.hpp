@@ -1,7 +1,9 @@
-// ATRAC3plus frame writer without tonal block (gfx950), SURVEY.md 8(f) row f4, second half:
+// ATRAC3plus frame writer (gfx950), SURVEY.md 8(f) row f4, second half:
 //   k_at3p_write  TScaler<NAt3p::TScaleTable>::ScaleFrame (atrac/atrac_scale.cpp:141-191) and
 //                 TAt3PBitStream::WriteFrame(channels, nullptr, sces) (atrac/at3p/at3p_bitstream.cpp:99-470, 630-726)
-//                 for one (stream, frame) per workgroup, both channels.
+//                 for one (stream, frame) per workgroup, both channels;
+//   k_at3p_write_tonal  the same kernel template with a record per frame: WriteFrame(channels, &block, sces) with
+//                 the record's block (:41-93, 487-629).
 // The reference gives every quant unit a fixed word length (TConfigure's table), so nothing but the NUMBER of quant units
 // is searched: it starts at 32 and drops to 28, 27, ... while the frame is over 16381 bits (CheckFrameDone under the
 // repeat protocol of lib/bs_encode/encode.cpp:100-130). A unit's mantissas and its cheapest code table do not depend on
@@ -139,6 +141,26 @@ struct WriteParams {
     const uint16_t* flags;     // [items][nch] steep-window bits per subband, or nullptr (all sine)
     uint8_t* out;              // [items][2048]
     int32_t nch, n_items;
+    static constexpr bool kTonal = false;
+};
+
+// One frame's tonal block, the fields of TAt3PGhaData that WriteTonalBlock reads (= at3phip_tonal_block, include/at3phip.h).
+// A point of the envelope is stored + 1 (0: EMPTY_POINT), so that a zeroed record is a frame without a tonal block; the waves
+// lie band by band, channel 0's bands first, as TWavesChannel::WaveParams holds them.
+constexpr int kTonalMaxWaves = 48, kTonalMaxBandWaves = 15;
+struct TonalBlock {
+    uint8_t num_tone_bands, second_is_leader;
+    uint16_t tone_sharing;             // bit b = ToneSharing[b]
+    uint8_t band[2][16][4];            // n_waves, start + 1, stop + 1, 0
+    uint32_t wave[kTonalMaxWaves];     // FreqIndex | AmpSf << 10 | PhaseIndex << 16
+};
+constexpr int kTonalBlockWords = sizeof(TonalBlock) / 4;
+static_assert(sizeof(TonalBlock) == 324, "the record is read as 81 words");
+
+struct WriteParamsTonal : WriteParams {
+    const TonalBlock* tonal;   // [items]
+    uint16_t tone_vlc[16];     // HuffTabs.NumToneBands: code | length << 12 of NumToneBands - 1
+    static constexpr bool kTonal = true;
 };
 
 __device__ __forceinline__ void frame_put(uint32_t* words, int pos, uint32_t val, int n)   // n in 1..23
@@ -250,8 +272,168 @@ __device__ __forceinline__ void emit_chunk(const WriteTables* W, const int (&q)[
     }
 }
 
-__global__ __launch_bounds__(256) void k_at3p_write(WriteParams p)
+
+// ---- the tonal block (TTonalComponentEncoder::WriteTonalBlock and CreateFreqBitPack, at3p_bitstream.cpp:41-93, 487-629) ----
+// Wavefront 0 prices the block before the unit count is chosen and writes it afterwards, one element per lane: lanes 0..31
+// are the band slots (channel lane / 16, band lane % 16: envelope, wave count, order bit), lanes 0..47 then the waves
+// (frequency code, amplitude, phase), lanes 48..50 the fields around them. Positions come from wave prefix sums and stay in
+// the lane's registers (TonalPlan) until the frame's other parts are placed.
+struct TonalPlan {
+    int bits;                      // of the block (0: none); wave-uniform
+    int pos_share;                 // of the sharing flags, relative to the block's first bit; wave-uniform
+    int env_pos, cnt_pos, ord_pos; // band slot: envelope points, wave count, order bit (-1: none)
+    int desc;
+    int f_pos, f_bits, a_pos, p_pos;   // wave: frequency code, amplitude, phase (-1: no wave)
+    uint32_t f_code;
+};
+
+__device__ __forceinline__ int tonal_fsb1(uint32_t x) { return x ? 32 - __builtin_clz(x) : 1; }   // GetFirstSetBit(x) + 1
+// the bits of wave t > 0 of a band in ascending order, after the predecessor `prev` (:59-67)
+__device__ __forceinline__ int tonal_asc_bits(uint32_t prev) { return prev < 512u ? 10 : tonal_fsb1(1023u - prev); }
+// FreqIndex of wave `idx` of the record (the index kept inside the record whatever the counts say)
+__device__ __forceinline__ uint32_t tonal_freq(const uint32_t* rec, int idx)
 {
+    return rec[33 + (idx < 0 ? 0 : idx >= kTonalMaxWaves ? kTonalMaxWaves - 1 : idx)] & 1023u;
+}
+
+__device__ __forceinline__ void tonal_price(const uint32_t* rec, int nch, int lane, const uint16_t* tone_vlc, TonalPlan* pl)
+{
+    const uint32_t w0 = rec[0];
+    const int nb = (int)(w0 & 0xffu) > 16 ? 16 : (int)(w0 & 0xffu);
+    const uint32_t share = nch == 2 ? (w0 >> 16) & ((1u << nb) - 1u) : 0u;
+    // ---- band slots ----
+    const int ch = (lane >> 4) & 1, b = lane & 15;
+    const bool own = lane < 32 && ch < nch && b < nb && !(ch == 1 && ((share >> b) & 1u));
+    const uint32_t bw = rec[1 + (lane & 31)];
+    int nw = own ? (int)(bw & 0xffu) : 0;
+    if (nw > kTonalMaxBandWaves) nw = kTonalMaxBandWaves;
+    const int sp = (int)((bw >> 8) & 0xffu), ep = (int)((bw >> 16) & 0xffu);
+    const int envb = own ? (sp ? 6 : 1) + (ep ? 6 : 1) : 0;
+    const int v1 = envb | ((own ? 1 : 0) << 10) | (nw << 16);   // envelope bits (<= 384), bands (<= 32), waves
+    const int incl1 = at3::wave_inclusive_scan(v1, lane);
+    const int t1a = __builtin_amdgcn_readlane(incl1, 15), t1b = __builtin_amdgcn_readlane(incl1, 31) - t1a;   // per channel
+    const int ex1 = incl1 - v1 - (ch ? t1a : 0);                // the fields before this band within its channel
+    const int ws = (incl1 >> 16) - nw;                          // the band's first wave in the record
+    int tot_a = 10, tot_d = 10;
+    for (int t = 1; t < nw; ++t) {
+        tot_a += tonal_asc_bits(tonal_freq(rec, ws + t - 1));
+        tot_d += tonal_fsb1(tonal_freq(rec, ws + t));
+    }
+    const int desc = (nw > 1 && !(tot_a < tot_d)) ? 1 : 0;      // ascending only when strictly cheaper (:88)
+    const int fb = nw == 0 ? 0 : (nw > 1 ? 1 : 0) + (desc ? tot_d : tot_a);
+    const int incl2 = at3::wave_inclusive_scan(fb, lane);
+    const int t2a = __builtin_amdgcn_readlane(incl2, 15), t2b = __builtin_amdgcn_readlane(incl2, 31) - t2a;
+    const int ex2 = incl2 - fb - (ch ? t2a : 0);
+    // ---- the block's layout (all wave-uniform) ----
+    const int n_share = __builtin_popcount(share);
+    const int share_bits = n_share == 0 ? 1 : n_share == nb ? 2 : 2 + nb;
+    const int leader_bits = ((w0 >> 8) & 0xffu) ? 2 : 1;
+    const int vlc_len = nb ? (int)(tone_vlc[nb - 1] >> 12) : 0;
+    const int head = 1 + vlc_len + (nch == 2 ? share_bits + leader_bits + 1 : 0);
+    // a channel's part from its first bit: [envelope copy flag] envelopes, num-waves mode, wave counts, [delta-to-leader flag]
+    // frequencies, amplitude mode, amplitudes, phases
+    const int cnt0 = (t1a & 0x3ff) + 1, cnt1 = 1 + (t1b & 0x3ff) + 2;
+    const int f0 = cnt0 + 4 * ((t1a >> 10) & 0x3f), f1 = cnt1 + 4 * ((t1b >> 10) & 0x3f) + 1;
+    const int a0 = f0 + t2a + 1, a1 = f1 + t2b + 2;
+    const int p0 = a0 + 6 * (t1a >> 16), p1 = a1 + 6 * (t1b >> 16);
+    const int cs1 = head + p0 + 5 * (t1a >> 16);                // channel 1's first bit; channel 0's is `head`
+    pl->bits = nb ? (nch == 2 ? cs1 + p1 + 5 * (t1b >> 16) : cs1) : 0;
+    pl->pos_share = 1 + vlc_len;
+    pl->env_pos = own ? (ch ? cs1 + 1 : head) + (ex1 & 0x3ff) : -1;
+    pl->cnt_pos = (ch ? cs1 + cnt1 : head + cnt0) + 4 * ((ex1 >> 10) & 0x3f);
+    const int band_f = (ch ? cs1 + f1 : head + f0) + ex2;
+    const int band_w = ex1 >> 16;                       // waves before this band within its channel
+    pl->ord_pos = nw > 1 ? band_f : -1;
+    pl->desc = desc;
+    // ---- waves: wave `lane` finds its band slot, then its place in the band's three lists ----
+    int slot = 0;
+    for (int k = 0; k < 32; ++k) {
+        const int ws_k = __builtin_amdgcn_readlane(ws, k), nw_k = __builtin_amdgcn_readlane(nw, k);
+        if (lane >= ws_k && lane < ws_k + nw_k) slot = k;
+    }
+    const int s_ws = __builtin_amdgcn_ds_bpermute(4 * slot, ws), s_nw = __builtin_amdgcn_ds_bpermute(4 * slot, nw);
+    const int s_desc = __builtin_amdgcn_ds_bpermute(4 * slot, desc), s_f = __builtin_amdgcn_ds_bpermute(4 * slot, band_f);
+    const int s_w = __builtin_amdgcn_ds_bpermute(4 * slot, band_w), s_ch = slot >> 4;
+    const bool is_wave = lane < kTonalMaxWaves && lane >= s_ws && lane < s_ws + s_nw;
+    pl->f_pos = pl->a_pos = pl->p_pos = -1;
+    pl->f_bits = 0;
+    pl->f_code = 0u;
+    if (is_wave) {
+        const int i = lane - s_ws;
+        const uint32_t f = rec[33 + lane] & 1023u;
+        int off_a = 0, off_d = 0;                       // the bits written before this wave's code in either order
+        for (int t = 0; t < s_nw; ++t) {
+            if (t < i) off_a += t == 0 ? 10 : tonal_asc_bits(tonal_freq(rec, s_ws + t - 1));
+            if (t > i) off_d += t == s_nw - 1 ? 10 : tonal_fsb1(tonal_freq(rec, s_ws + t + 1));
+        }
+        if (s_desc) {
+            pl->f_bits = i == s_nw - 1 ? 10 : tonal_fsb1(tonal_freq(rec, lane + 1));
+            pl->f_code = f;
+            pl->f_pos = s_f + 1 + off_d;
+        } else {
+            const uint32_t prev = i ? tonal_freq(rec, lane - 1) : 0u;
+            pl->f_bits = i ? tonal_asc_bits(prev) : 10;
+            pl->f_code = (i && prev >= 512u) ? f - (1024u - (1u << pl->f_bits)) : f;
+            pl->f_pos = s_f + (s_nw > 1 ? 1 : 0) + off_a;
+        }
+        pl->a_pos = (s_ch ? cs1 + a1 : head + a0) + 6 * (s_w + i);
+        pl->p_pos = (s_ch ? cs1 + p1 : head + p0) + 5 * (s_w + i);
+    }
+}
+
+// The block at bit `at` of the frame (behind the tonal flag). Mode fields, channel 1's envelope-copy and delta flags and the
+// invert-phase flag are zero bits: the frame starts zeroed.
+__device__ __forceinline__ void tonal_emit(uint32_t* out, int at, const uint32_t* rec, int nch, int lane, const uint16_t* tone_vlc, const TonalPlan& pl)
+{
+    if (pl.bits == 0) return;
+    const uint32_t w0 = rec[0];
+    const int nb = (int)(w0 & 0xffu) > 16 ? 16 : (int)(w0 & 0xffu);
+    if (lane < 32) {
+        const uint32_t bw = rec[1 + lane];
+        if (pl.env_pos >= 0) {
+            const int sp = (int)((bw >> 8) & 0xffu), ep = (int)((bw >> 16) & 0xffu);
+            if (sp) frame_put(out, at + pl.env_pos, 0x20u | (uint32_t)(sp - 1), 6);
+            if (ep) frame_put(out, at + pl.env_pos + (sp ? 6 : 1), 0x20u | (uint32_t)(ep - 1), 6);
+            const uint32_t nw = (bw & 0xffu) > (uint32_t)kTonalMaxBandWaves ? (uint32_t)kTonalMaxBandWaves : (bw & 0xffu);
+            frame_put(out, at + pl.cnt_pos, nw, 4);
+        }
+        if (pl.ord_pos >= 0) frame_put(out, at + pl.ord_pos, (uint32_t)pl.desc, 1);
+    }
+    if (pl.f_pos >= 0) {
+        const uint32_t w = rec[33 + lane];
+        frame_put(out, at + pl.f_pos, pl.f_code, pl.f_bits);
+        frame_put(out, at + pl.a_pos, (w >> 10) & 63u, 6);
+        frame_put(out, at + pl.p_pos, (w >> 16) & 31u, 5);
+    }
+    if (lane == 48) {   // amplitude mode 1, NumToneBands
+        const uint32_t e = tone_vlc[nb - 1];
+        frame_put(out, at, 1u, 1);
+        frame_put(out, at + 1, e & 0xfffu, (int)(e >> 12));
+    }
+    if (lane == 49 && nch == 2) {   // WriteSubbandFlags (:487-507) for the sharing flags and the leader flag
+        const uint32_t share = (w0 >> 16) & ((1u << nb) - 1u);
+        const int n_share = __builtin_popcount(share);
+        int pos = at + pl.pos_share;
+        if (n_share == nb) {
+            frame_put(out, pos, 2u, 2);
+            pos += 2;
+        } else if (n_share) {
+            frame_put(out, pos, 3u, 2);
+            for (int i = 0; i < nb; ++i) frame_put(out, pos + 2 + i, (share >> i) & 1u, 1);
+            pos += 2 + nb;
+        } else {
+            pos += 1;
+        }
+        if ((w0 >> 8) & 0xffu) frame_put(out, pos, 2u, 2);
+    }
+}
+
+// The writer for frames without tonal records (P = WriteParams) and with a record per frame (P = WriteParamsTonal; all zero: no
+// tonal block).
+template <typename P>
+__global__ __launch_bounds__(256) void k_at3p_write_with(P p)
+{
+    constexpr bool kTonal = P::kTonal;
     __shared__ uint32_t s_out[kFrameBytes / 4];
     __shared__ uint16_t s_cbits[256][8];     // bits of each 16-line chunk under each of the eight candidate tables
     __shared__ uint32_t s_qbits[2][32][8];   // the same per quant unit
@@ -265,6 +447,7 @@ __global__ __launch_bounds__(256) void k_at3p_write(WriteParams p)
     __shared__ uint32_t s_off[256];          // and their exclusive prefix sums per channel
     __shared__ uint32_t s_info[56];
     __shared__ uint32_t s_len4[(kLenEntries + 7) / 8];
+    __shared__ uint32_t s_rec[kTonal ? kTonalBlockWords : 1];   // the frame's tonal record
 
     const WriteTables* W = p.W;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -307,6 +490,9 @@ __global__ __launch_bounds__(256) void k_at3p_write(WriteParams p)
             s_scale[tid] = scale_v;
         }
         if (tid >= 64 && tid < 120) s_info[tid - 64] = info_v;
+        if constexpr (kTonal) {
+            if (tid >= 128 && tid < 128 + kTonalBlockWords) s_rec[tid - 128] = reinterpret_cast<const uint32_t*>(p.tonal + item)[tid - 128];
+        }
 #pragma unroll
         for (int i = 0; i < kLenIt; ++i)
             if (tid + 256 * i < kLenWords) s_len4[tid + 256 * i] = len_v[i];
@@ -410,8 +596,13 @@ __global__ __launch_bounds__(256) void k_at3p_write(WriteParams p)
         fl[k] = p.flags ? p.flags[item * nch + k] : 0u;
         win_bits[k] = fl[k] == 0u ? 1 : ((fl[k] & 0xffu) == 0xffu ? 2 : 18);   // IsAllSteep keeps its mask in a uint8_t
     }
-    const int tonal_bits = (nch == 2 ? 2 : 0) + win_bits[0] + win_bits[1] + nch + 1 + 1 + 2;
+    int tonal_bits = (nch == 2 ? 2 : 0) + win_bits[0] + win_bits[1] + nch + 1 + 1 + 2;
+    [[maybe_unused]] TonalPlan plan;
     if (wave == 0) {
+        if constexpr (kTonal) {   // the block counts in CheckFrameDone (:631-644): it is priced before the units are counted
+            tonal_price(s_rec, nch, lane, p.tone_vlc, &plan);
+            tonal_bits += plan.bits;
+        }
         const int q = lane & 31;
         int v = (lane < 32) ? (int)(s_best[0][q] + (nch == 2 ? s_best[1][q] : 0u)) : 0;
         v = at3::wave_inclusive_scan(v, lane);   // lane n - 1: the spectra of the first n units
@@ -465,7 +656,7 @@ __global__ __launch_bounds__(256) void k_at3p_write(WriteParams p)
         run.finish();
     }
     if (c == 0 && active) frame_put(s_out, ch_base[ch] + ch_total[ch], (1u << pw) - 1u, pw);   // (15, 4) per power group
-    if (tid == 65) {
+    if (kTonal ? tid == 50 : tid == 65) {
         int pos = ch_base[nch - 1] + ch_total[nch - 1] + pw;
         if (nch == 2) pos += 2;   // swap_channels, negate_coeffs
         for (int k = 0; k < nch; ++k) {
@@ -477,13 +668,27 @@ __global__ __launch_bounds__(256) void k_at3p_write(WriteParams p)
             }
             pos += win_bits[k];
         }
-        pos += nch + 1 + 1;   // gain compensation per channel, no tonal block, no noise info
+        if constexpr (kTonal) {
+            pos += nch;           // gain compensation per channel
+            if (plan.bits) frame_put(s_out, pos, 1u, 1);
+            pos += 1 + plan.bits + 1;   // the tonal flag and block, no noise info
+        } else {
+            pos += nch + 1 + 1;   // gain compensation per channel, no tonal block, no noise info
+        }
         frame_put(s_out, pos, 3u, 2);
+    }
+    if constexpr (kTonal) {
+        if (wave == 0)
+            tonal_emit(s_out, ch_base[nch - 1] + ch_total[nch - 1] + pw + (nch == 2 ? 2 : 0) + win_bits[0] + win_bits[1] + nch + 1, s_rec, nch,
+                       lane, p.tone_vlc, plan);
     }
     __syncthreads();
     uint32_t* dst = reinterpret_cast<uint32_t*>(p.out + item * kFrameBytes);
     dst[tid] = __builtin_bswap32(s_out[tid]);
     dst[256 + tid] = __builtin_bswap32(s_out[256 + tid]);
 }
+// the two instantiations under the names they are launched by
+constexpr auto k_at3p_write = k_at3p_write_with<WriteParams>;
+constexpr auto k_at3p_write_tonal = k_at3p_write_with<WriteParamsTonal>;
 
 }  // namespace at3p

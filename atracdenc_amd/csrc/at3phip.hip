@@ -17,6 +17,11 @@ using at3host::fail;
 
 static_assert(sizeof(Tables) == AT3PHIP_TABLES_BYTES, "at3phip.h documents the table block's size");
 static_assert(sizeof(WriteTables) == AT3PHIP_WRITE_TABLES_BYTES, "at3phip.h documents the frame writer's table block size");
+// at3phip_tonal_block is the writer's record, field for field
+static_assert(sizeof(at3phip_tonal_block) == sizeof(TonalBlock) && offsetof(at3phip_tonal_block, tone_sharing) == offsetof(TonalBlock, tone_sharing) &&
+                  offsetof(at3phip_tonal_block, band) == offsetof(TonalBlock, band) && offsetof(at3phip_tonal_block, wave) == offsetof(TonalBlock, wave) &&
+                  sizeof(at3phip_tonal_band) == 4 && AT3PHIP_TONAL_MAX_WAVES == kTonalMaxWaves && AT3PHIP_TONAL_MAX_BAND_WAVES == kTonalMaxBandWaves,
+              "at3phip.h documents the tonal record's layout");
 
 struct at3phip_ctx : at3host::EngineBase {   // (no at3phip_set_stream: stream == own_stream)
     at3phip_config cfg;
@@ -31,6 +36,7 @@ struct at3phip_ctx : at3host::EngineBase {   // (no at3phip_set_stream: stream =
     float* d_mdct_hist = nullptr;  // [S][nch][16][128]
     WriteTables* d_wtables = nullptr;
     uint8_t* d_frames = nullptr;   // staging for host frames [S][F][2048]
+    TonalBlock* d_tonal = nullptr; // the tonal records of a call [S][F], allocated by the first at3phip_write_frames_tonal that has any
     // at3phip_encode_frames: the frame writer only needs the spectra of ITS call, so it runs on a stream of its own behind
     // an event and the next call's filter bank and transform overlap it; the spectra in between are double-buffered
     hipStream_t write_stream = nullptr;
@@ -43,6 +49,8 @@ struct at3phip_ctx : at3host::EngineBase {   // (no at3phip_set_stream: stream =
 };
 
 namespace {
+
+#include "at3p_tone_vlc.inc"
 
 int reset_state(at3phip_ctx* c)
 {
@@ -100,21 +108,63 @@ int launch_mdct(at3phip_ctx* c, const float* d_bands, int n_frames, const uint16
     return AT3HIP_OK;
 }
 
-int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint16_t* win_flags, uint8_t* d_frames, hipStream_t on = nullptr)
+// tonal: the call's records [S][n_frames] in host memory, already checked (check_tonal), or null: the writer without records
+int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint16_t* win_flags, uint8_t* d_frames, hipStream_t on = nullptr,
+                 const at3phip_tonal_block* tonal = nullptr)
 {
     const size_t S = c->cfg.n_streams, C = c->cfg.channels;
     if (!on) on = c->stream;
     if (win_flags) HIPCHK(c, hipMemcpyAsync(c->d_flags, win_flags, S * n_frames * C * sizeof(uint16_t), hipMemcpyHostToDevice, on));
-    WriteParams wp;
+    WriteParamsTonal wp;
     wp.W = c->d_wtables;
     wp.specs = d_specs;
     wp.flags = win_flags ? c->d_flags : nullptr;
     wp.out = d_frames;
     wp.nch = (int)C;
     wp.n_items = (int)(S * n_frames);
-    hipLaunchKernelGGL(k_at3p_write, dim3((unsigned)(S * n_frames)), dim3(256), 0, on, wp);
+    if (tonal) {
+        if (!c->d_tonal) {
+            const int rc = dev_alloc(c, &c->d_tonal, S * (size_t)c->cfg.max_frames);
+            if (rc != AT3HIP_OK) return rc;
+        }
+        HIPCHK(c, hipMemcpyAsync(c->d_tonal, tonal, S * n_frames * sizeof(TonalBlock), hipMemcpyHostToDevice, on));
+        wp.tonal = c->d_tonal;
+        memcpy(wp.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(wp.tone_vlc));
+        hipLaunchKernelGGL(k_at3p_write_tonal, dim3((unsigned)(S * n_frames)), dim3(256), 0, on, wp);
+    } else {
+        hipLaunchKernelGGL(k_at3p_write, dim3((unsigned)(S * n_frames)), dim3(256), 0, on, static_cast<const WriteParams&>(wp));
+    }
     HIPCHK(c, hipGetLastError());
     return AT3HIP_OK;
+}
+
+// The contract of at3phip_tonal_block for one record of a context with `channels` channels: null, or the field that breaks it.
+const char* check_tonal(const at3phip_tonal_block& t, int channels)
+{
+    const int nb = t.num_tone_bands;
+    if (nb == 0) return nullptr;   // no tonal block: nothing else is read
+    if (nb > 16) return "num_tone_bands above 16";
+    if (t.second_is_leader > 1) return "second_is_leader above 1";
+    if (channels == 1 && t.second_is_leader) return "second_is_leader in a mono context";
+    if (channels == 1 && t.tone_sharing) return "tone_sharing in a mono context";
+    int at = 0;
+    for (int ch = 0; ch < channels; ++ch)
+        for (int b = 0; b < nb; ++b) {
+            const at3phip_tonal_band& bd = t.band[ch][b];
+            if (ch == 1 && ((t.tone_sharing >> b) & 1)) {
+                if (bd.n_waves) return "n_waves of a shared band of channel 1";
+                continue;
+            }
+            if (bd.start > 32) return "start above 32 (point 31)";
+            if (bd.stop > 32) return "stop above 32 (point 31)";
+            if (bd.n_waves > AT3PHIP_TONAL_MAX_BAND_WAVES) return "n_waves above 15";
+            if (at + bd.n_waves > AT3PHIP_TONAL_MAX_WAVES) return "more than 48 waves";
+            for (int i = 0; i < bd.n_waves; ++i, ++at) {
+                if (t.wave[at] >> 21) return "wave outside FreqIndex 0..1023, AmpSf 0..63, PhaseIndex 0..31";
+                if (i && (t.wave[at] & 1023u) < (t.wave[at - 1] & 1023u)) return "FreqIndex decreasing within a band";
+            }
+        }
+    return nullptr;
 }
 
 // A stage-level entry point (at3phip_pqf_analyse, at3phip_mdct, at3phip_pqf_mdct, at3phip_write_frames): which buffers it
@@ -206,7 +256,7 @@ void at3phip_destroy(at3phip_ctx* c)
 {
     if (c)
         at3host::destroy_engine(c, {c->d_tables, c->d_pcm_in, c->d_pcm_s16, c->d_bands, c->d_specs, c->d_specs_b[1], c->d_flags, c->d_pqf_hist,
-                                    c->d_mdct_hist, c->d_wtables, c->d_frames},
+                                    c->d_mdct_hist, c->d_wtables, c->d_frames, c->d_tonal},
                                 {c->write_stream}, [c] {
                                     for (hipEvent_t e : {c->ev[0], c->ev[1], c->ev[2], c->ev[3], c->ev[4], c->ev_specs[0], c->ev_specs[1],
                                                          c->ev_write_done[0], c->ev_write_done[1]})
@@ -261,12 +311,31 @@ int at3phip_pqf_mdct(at3phip_ctx* c, const float* pcm, int32_t n_frames, const u
 
 int at3phip_write_frames(at3phip_ctx* c, const float* specs, int32_t n_frames, const uint16_t* win_flags, uint8_t* frames, uint32_t flags)
 {
+    return at3phip_write_frames_tonal(c, specs, n_frames, win_flags, nullptr, frames, flags);
+}
+
+int at3phip_write_frames_tonal(at3phip_ctx* c, const float* specs, int32_t n_frames, const uint16_t* win_flags, const at3phip_tonal_block* tonal,
+                               uint8_t* frames, uint32_t flags)
+{
     if (!c || !specs || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
+    bool any = false;   // records without a block are the writer without records
+    if (tonal)
+        for (int s = 0; s < c->cfg.n_streams; ++s)
+            for (int f = 0; f < n_frames; ++f) {
+                const at3phip_tonal_block& t = tonal[(size_t)s * n_frames + f];
+                any |= t.num_tone_bands != 0;
+                if (const char* why = check_tonal(t, c->cfg.channels)) {
+                    char msg[160];
+                    snprintf(msg, sizeof(msg), "tonal block of stream %d, frame %d: %s", s, f, why);
+                    return fail(c, AT3HIP_EINVAL, msg);
+                }
+            }
+    if (!any) tonal = nullptr;
     const size_t items = (size_t)c->cfg.n_streams * n_frames;
     const float* d_specs = (flags & AT3HIP_PCM_ON_DEVICE) ? specs : c->d_specs;
     uint8_t* d_frames = (flags & AT3HIP_OUT_ON_DEVICE) ? frames : c->d_frames;
     const Stage stage = {specs, c->d_specs, items * c->cfg.channels * 2048 * sizeof(float), {{frames, c->d_frames, items * kFrameBytes}}, 2, {&at3phip_ctx::write_ms}};
-    return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames); });
+    return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames, nullptr, tonal); });
 }
 
 }  // extern "C"
@@ -419,7 +488,6 @@ struct at3phip_decoder : at3host::DecoderBase {
 namespace {
 
 #include "at3p_mant.inc"
-#include "at3p_tone_vlc.inc"
 
 // The tone synthesis' tables as ff_atrac3p_init_dsp_static builds them, with the host's libm (never constant-folded: optnone).
 __attribute__((optnone, noinline)) void build_decp_tone_tables(DecToneTables* t)

@@ -634,10 +634,37 @@ private:
 // encodes the frame BEFORE the current one (PrevBuf, at3p.cpp:115-160), so the first call returns LOOK_AHEAD, the second
 // writes a silent frame and call k >= 2 writes input frame k - 2; this class keeps that schedule. Frames are encoded
 // `batchFrames` at a time like the encoders above and flushed in order.
+//
+// With a tonal analyser (IAt3PGhaProcessor, shaped like IGhaProcessor::DoAnalize, at3p_gha.h:69-78) the class runs
+// EncodeFrame's whole schedule under TAt3PSettings::UseGha: per batch one at3phip_pqf_analyse, then per call the analyser on the
+// host - current and next subband buffers const, the previous ones (PrevBuf, what the transform takes) writable -, one
+// at3phip_mdct with AT3PHIP_RESIDUAL_SCALE on the possibly modified previous buffers (zeros without GHA_WRITE_RESIUDAL), one
+// at3phip_write_frames_tonal. PrevBuf becomes the current buffer under GHA_PASS_INPUT and zeros otherwise; the block returned
+// for call k is written with call k + 1 (`delay`, at3p.cpp:128-176) and only under GHA_WRITE_TONAL. Without an analyser nothing
+// changes: same calls, same bytes.
+struct TAt3PSettings {   // TAt3PEnc::TSettings::UseGha (atrac3p.h:29-47)
+    enum GhaProcessingFlags : uint8_t { GHA_PASS_INPUT = 1, GHA_WRITE_TONAL = 1 << 1, GHA_WRITE_RESIUDAL = 1 << 2,
+                                        GHA_ENABLED = GHA_PASS_INPUT | GHA_WRITE_TONAL | GHA_WRITE_RESIUDAL };
+    uint8_t UseGha = GHA_ENABLED;
+};
+
+class IAt3PGhaProcessor {
+public:
+    using TBufPtr = std::array<const float*, 2>;   // {current, next}: a channel's subband samples [16][128]
+    virtual ~IAt3PGhaProcessor() {}
+    // b1 / b2: channel 0 / 1 (nulls in mono); w1 / w2: the channels' previous buffers, which the analyser may rewrite (w2 null in
+    // mono); raw1Cur / raw2Cur: the current frame's PCM per channel [2048], before the filter bank. Returns the frame's tonal
+    // block, valid until the next call, or null.
+    virtual const at3phip_tonal_block* DoAnalize(TBufPtr b1, TBufPtr b2, float* w1, float* w2, const float* raw1Cur,
+                                                 const float* raw2Cur) = 0;
+};
+
 class TAt3PEncoder {
 public:
-    TAt3PEncoder(TCompressedOutputPtr&& out, int channels, int batchFrames = 64, int deviceId = 0)
-        : Out(std::move(out)), Channels((size_t)channels), BatchFrames(batchFrames), FrameFloats((size_t)AT3PHIP_FRAME * (size_t)channels)
+    TAt3PEncoder(TCompressedOutputPtr&& out, int channels, int batchFrames = 64, int deviceId = 0, TAt3PSettings settings = TAt3PSettings(),
+                 IAt3PGhaProcessor* gha = nullptr)
+        : Out(std::move(out)), Channels((size_t)channels), BatchFrames(batchFrames), FrameFloats((size_t)AT3PHIP_FRAME * (size_t)channels),
+          Settings(settings), Gha(gha)
     {
         at3phip_config cfg{};
         cfg.channels = channels;
@@ -678,6 +705,15 @@ public:
     {
         Flush();
         const bool first = Calls == 0 && nFrames > 0;
+        if (Gha) {   // the analyser takes float PCM: the same floats as the device's widening, through the float schedule
+            for (int at = 0; at < nFrames; at += BatchFrames) {
+                const size_t n = (size_t)std::min(BatchFrames, nFrames - at) * FrameFloats;
+                for (size_t i = 0; i < n; ++i) Pending.push_back((float)pcm[(size_t)at * FrameFloats + i] * 0x1p-15f);
+                Calls += n / FrameFloats;
+                Flush();
+            }
+            return first;
+        }
         std::vector<uint8_t> frames((size_t)BatchFrames * AT3PHIP_FRAME_BYTES);
         for (int at = 0; at < nFrames; at += BatchFrames) {
             const int nf = std::min(BatchFrames, nFrames - at);
@@ -693,6 +729,10 @@ public:
     void Flush()
     {
         const int nf = (int)(Pending.size() / FrameFloats);
+        if (Gha) {
+            if (nf > 0) FlushAnalysed(nf);
+            return;
+        }
         if (nf > 0) {
             std::vector<uint8_t> frames((size_t)nf * AT3PHIP_FRAME_BYTES);
             Chk(at3phip_encode_frames(Ctx, Pending.data(), nf, frames.data(), 0), "at3phip_encode_frames");
@@ -716,6 +756,50 @@ private:
     {
         if (rc != AT3HIP_OK) throw std::runtime_error(std::string(what) + ": " + at3phip_last_error(Ctx));
     }
+    // The calls that buffered the `nf` pending frames, EncodeFrame by EncodeFrame (at3p.cpp:89-180). Call k >= 1 transforms and
+    // writes PrevBuf, which holds input frame k - 2 (or zeros) as call k's analysis left it.
+    void FlushAnalysed(int nf)
+    {
+        const size_t C = Channels, N = AT3PHIP_FRAME;
+        std::vector<float> bands((size_t)nf * FrameFloats);
+        Chk(at3phip_pqf_analyse(Ctx, Pending.data(), nf, bands.data(), 0), "at3phip_pqf_analyse");
+        if (PrevBuf.empty()) {
+            PrevBuf.assign(FrameFloats, 0.0f);
+            CurBuf.assign(FrameFloats, 0.0f);
+            RawCur.assign(FrameFloats, 0.0f);
+        }
+        const size_t first = Calls - (size_t)nf;   // the call that buffered Pending's first frame
+        std::vector<float> prevs;                  // what each writing call transforms [calls][C][16][128]
+        std::vector<at3phip_tonal_block> blocks;   // and the block it writes
+        for (int i = 0; i < nf; ++i) {
+            const float* next = bands.data() + (size_t)i * FrameFloats;
+            if (first + (size_t)i > 0) {
+                const at3phip_tonal_block* found = Gha->DoAnalize({CurBuf.data(), next}, {C == 2 ? CurBuf.data() + N : nullptr, C == 2 ? next + N : nullptr},
+                                                                  PrevBuf.data(), C == 2 ? PrevBuf.data() + N : nullptr, RawCur.data(),
+                                                                  C == 2 ? RawCur.data() + N : nullptr);
+                prevs.insert(prevs.end(), PrevBuf.begin(), PrevBuf.end());
+                blocks.push_back(Delay);
+                if (Settings.UseGha & TAt3PSettings::GHA_PASS_INPUT) PrevBuf = CurBuf;
+                else std::fill(PrevBuf.begin(), PrevBuf.end(), 0.0f);
+                if (found && (Settings.UseGha & TAt3PSettings::GHA_WRITE_TONAL)) Delay = *found;
+                else Delay = at3phip_tonal_block{};
+            }
+            CurBuf.assign(next, next + FrameFloats);
+            for (size_t ch = 0; ch < C; ++ch)
+                for (size_t k = 0; k < N; ++k) RawCur[ch * N + k] = Pending[(size_t)i * FrameFloats + k * C + ch];
+        }
+        Pending.clear();
+        const int calls = (int)blocks.size();
+        if (calls == 0) return;
+        if (!(Settings.UseGha & TAt3PSettings::GHA_WRITE_RESIUDAL)) std::fill(prevs.begin(), prevs.end(), 0.0f);
+        std::vector<float> specs(prevs.size());
+        std::vector<uint8_t> frames((size_t)calls * AT3PHIP_FRAME_BYTES);
+        Chk(at3phip_mdct(Ctx, prevs.data(), calls, nullptr, specs.data(), AT3PHIP_RESIDUAL_SCALE), "at3phip_mdct");
+        Chk(at3phip_write_frames_tonal(Ctx, specs.data(), calls, nullptr, blocks.data(), frames.data(), 0), "at3phip_write_frames_tonal");
+        for (int i = 0; i < calls; ++i)
+            Out->WriteFrame(std::vector<char>(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES));
+        Written += (size_t)calls;
+    }
     std::vector<char> SilentFrame()   // an all-zero spectrum through the frame writer (the encoder's PrevBuf starts zeroed)
     {
         std::vector<float> specs(FrameFloats, 0.0f);
@@ -731,6 +815,10 @@ private:
     std::vector<float> Pending;
     std::vector<std::vector<char>> Ready;
     size_t Calls = 0, Written = 0;
+    const TAt3PSettings Settings;
+    IAt3PGhaProcessor* const Gha;                 // not owned; null: the analysis finds nothing
+    std::vector<float> PrevBuf, CurBuf, RawCur;   // [C][16][128] / [C][2048]: TChannelCtx's PrevBuf, CurBuf and RawCurBuf
+    at3phip_tonal_block Delay{};                  // `delay`: the block the next call writes
 };
 
 // ---- sample-rate conversion (include/at3hip_resample.h) ------------------------------------------------------------------

@@ -1,9 +1,10 @@
 /* at3phip.h - C ABI of the MI355X-native ATRAC3plus path: the 16-band polyphase analysis
  * filter and the windowed MDCT-256 x 16 that turn PCM into the 2048-line spectrum (at3p.cpp:93-99, 139-159), and the
- * frame writer that scales and packs it when there is no tonal block (at3p.cpp:159-163: ScaleFrame, then
- * TAt3PBitStream::WriteFrame(channels, nullptr, sces)). The tonal (GHA) analysis between them needs libgha, an
- * un-vendored submodule of the reference, and is not part of this row: at3phip_encode_frames is the encoder with that
- * analysis finding nothing. Same library (libat3hip.so) and error codes as at3hip.h.
+ * frame writer that scales and packs it, with or without a tonal block (at3p.cpp:159-163: ScaleFrame, then
+ * TAt3PBitStream::WriteFrame(channels, p, sces)). The tonal (GHA) analysis between them needs libgha, an
+ * un-vendored submodule of the reference, and is not part of this row: its result comes from the caller
+ * (at3phip_write_frames_tonal), and at3phip_encode_frames is the encoder with that analysis finding nothing. Same library
+ * (libat3hip.so) and error codes as at3hip.h.
  */
 #ifndef AT3PHIP_H
 #define AT3PHIP_H
@@ -74,6 +75,53 @@ int at3phip_pqf_mdct(at3phip_ctx* ctx, const float* pcm, int32_t n_frames, const
 #define AT3PHIP_FRAME_BYTES 2048
 int at3phip_write_frames(at3phip_ctx* ctx, const float* specs, int32_t n_frames, const uint16_t* win_flags, uint8_t* frames,
                          uint32_t flags);
+
+/* TONAL BLOCKS IN THE WRITER. One frame's tonal block: the fields of TAt3PGhaData (atrac/at3p/at3p_gha.h:30-67) that
+ * TTonalComponentEncoder::WriteTonalBlock reads, as a fixed-size record of 324 bytes. An all-zero record means "no tonal block";
+ * so does any record with num_tone_bands = 0, whose other fields are not read. Layout:
+ *   num_tone_bands    NumToneBands, 0..16
+ *   second_is_leader  SecondIsLeader, 0 or 1
+ *   tone_sharing      bit b = ToneSharing[b]; bits at or above num_tone_bands are not read
+ *   band[ch][b]       band b < num_tone_bands of channel ch (WaveSbInfos[b]): n_waves = WaveNums, 0..15; start / stop = the
+ *                     envelope's point + 1, so 1..32 for the points 0..31 and 0 for EMPTY_POINT; reserved is not read. Bands at
+ *                     or above num_tone_bands, channel 1 of a mono context and the envelope of a shared band are not read.
+ *   wave[i]           WaveParams as AT3PHIP_TONAL_WAVE packs them (FreqIndex 0..1023 | AmpSf 0..63 << 10 | PhaseIndex 0..31 << 16;
+ *                     AmpIndex is not written by the reference): channel 0's bands in order, then channel 1's, each band's
+ *                     n_waves entries side by side (WaveIndex is the running sum); at most 48 in all.
+ * The contract, checked on the host before anything is queued (AT3HIP_EINVAL, the last error naming stream, frame and field):
+ * the ranges above; FreqIndex non-decreasing within a band, which CreateFreqBitPack assumes (its codes are differences to
+ * 1024 - 2^b); a shared band of channel 1 has no waves of its own; tone_sharing and second_is_leader are 0 in a mono context. */
+#define AT3PHIP_TONAL_MAX_WAVES 48
+#define AT3PHIP_TONAL_MAX_BAND_WAVES 15
+#define AT3PHIP_TONAL_WAVE(freq, amp_sf, phase) ((uint32_t)(freq) | (uint32_t)(amp_sf) << 10 | (uint32_t)(phase) << 16)
+typedef struct at3phip_tonal_band {
+    uint8_t n_waves, start, stop, reserved;
+} at3phip_tonal_band;
+typedef struct at3phip_tonal_block {
+    uint8_t num_tone_bands, second_is_leader;
+    uint16_t tone_sharing;
+    at3phip_tonal_band band[2][16];
+    uint32_t wave[AT3PHIP_TONAL_MAX_WAVES];
+} at3phip_tonal_block;
+
+/* Replaces: ScaleFrame as above and TAt3PBitStream::WriteFrame(channels, &block, sces) per frame, or WriteFrame(channels,
+ * nullptr, sces) for a record without a block: byte for byte the reference's frame, with the block written by
+ * WriteTonalBlock and CreateFreqBitPack (at3p_bitstream.cpp:41-93, 487-629).
+ *   specs, win_flags, frames, flags  exactly as in at3phip_write_frames
+ *   tonal  [n_streams][n_frames] records in host memory, like win_flags; NULL = no frame has a block (at3phip_write_frames)
+ * What the reference does and this call keeps: the frame's tail (window shapes, gain-compensation bits, tonal flag and block,
+ * noise flag, terminator) is formed once, in the pass with 32 quant units, and its bits count in CheckFrameDone, so a block
+ * lowers the number of quant units a loud frame keeps; ascending frequency order is chosen only when strictly cheaper; the
+ * num-waves and amplitude mode fields are 0 in ch + 1 bits. The block is the analysis of the frame BEFORE the spectrum's
+ * (TAt3PEnc::EncodeFrame writes the previous call's block, at3p.cpp:128-176): pairing records with spectra is the host's.
+ * The reference aborts when, on a repeated pass, NumToneBands exceeds the quant unit count (at3p_bitstream.cpp:652-656), that is
+ * when 16 units and the tail do not fit the frame. That branch cannot be reached: in stereo the first 16 units cost at most
+ * 6639 bits with everything in front of the tail (a unit's cheapest table is never dearer than any one of its eight), the
+ * largest tail at most 1624 bits, and a frame holds 16381; mono needs less (tests/test_at3p_tonal_write_cpu.py works the
+ * figures out from at3p_vlc.inc and the word-length table).
+ * Added under ABI 1.6: a host looks for this symbol. */
+int at3phip_write_frames_tonal(at3phip_ctx* ctx, const float* specs, int32_t n_frames, const uint16_t* win_flags,
+                               const at3phip_tonal_block* tonal, uint8_t* frames, uint32_t flags);
 
 /* PCM to frames: at3phip_pqf_mdct with AT3PHIP_RESIDUAL_SCALE and sine windows, then at3phip_write_frames, everything in
  * between staying in HBM. This is TAt3PEnc::EncodeFrame (at3p.cpp:89-170) with GHA_PASS_INPUT | GHA_WRITE_RESIUDAL and a
