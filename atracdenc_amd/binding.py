@@ -173,8 +173,11 @@ PROTOTYPES = {
     "at3phip_pqf_mdct": (_RC, [_VP, _VP, _I32, _VP, _VP, _VP, _U32]), "at3phip_write_frames": (_RC, [_VP, _VP, _I32, _VP, _VP, _U32]),
     "at3phip_write_frames_tonal": (_RC, [_VP, _VP, _I32, _VP, _VP, _VP, _U32]),
     "at3phip_encode_frames": (_RC, [_VP, _VP, _I32, _VP, _U32]), "at3phip_encode_frames_short": (_RC, [_VP, _VP, _I32, _VP, _U32]),
+    "at3phip_analyse_tones": (_RC, [_VP, _VP, _I32, _VP, _VP, _U32]),
+    "at3phip_encode_frames_tonal": (_RC, [_VP, _VP, _I32, _VP, _U32]), "at3phip_encode_frames_tonal_short": (_RC, [_VP, _VP, _I32, _VP, _U32]),
     "at3phip_get_timings": (_RC, [_VP, _F32P, _F32P]), "at3phip_get_write_timing": (_RC, [_VP, _F32P]),
     "at3phip_host_tables": (_RC, [_VP, _SZ]), "at3phip_host_write_tables": (_RC, [_VP, _SZ]),
+    "at3phip_host_tone_find_tables": (_RC, [_VP, _SZ]),
     # include/at3phip.h: the ATRAC3plus decoder
     "at3phip_decoder_create": (_RC, [_P(At3pDecoderConfig), _P(_VP)]), "at3phip_decoder_destroy": (None, [_VP]),
     "at3phip_decoder_last_error": (_STR, [_VP]), "at3phip_decoder_reset": (_RC, [_VP]), "at3phip_decoder_sync": (_RC, [_VP]),
@@ -754,6 +757,17 @@ def pack_tonal_blocks(blocks, channels):
     return rec
 
 
+# at3phip_host_tone_find_tables: the tone analysis' tables (include/at3phip.h, FINDING TONES); tw is [256][2] (re, im)
+AT3P_TONE_FIND_TABLES_DTYPE = np.dtype([("sine", "<f4", 2048), ("hann", "<f4", 256), ("amp_sf", "<f4", 64), ("tw", "<f4", (256, 2)),
+                                        ("thr", "<f8", 64), ("rs", "<f8", 1024), ("rc", "<f8", 1024)])
+assert AT3P_TONE_FIND_TABLES_DTYPE.itemsize == 28416
+
+
+def at3p_host_tone_find_tables(lib_path=None):
+    """at3phip_host_tone_find_tables (no GPU): the tone analysis' tables as a record of AT3P_TONE_FIND_TABLES_DTYPE."""
+    return _host_tables(lib_path, "at3phip_host_tone_find_tables", np.zeros((), AT3P_TONE_FIND_TABLES_DTYPE))
+
+
 class At3pHip(_Context):
     """ATRAC3plus front end (include/at3phip.h): PQF analysis and windowed MDCT-256 x 16 for n_streams streams."""
 
@@ -791,6 +805,19 @@ class At3pHip(_Context):
     def encode_frames_s16_ptr(self, pcm_ptr, n_frames, frames_ptr, flags):
         """Raw pointers (int16 PCM, 2-byte alignment is enough) and at3phip_encode_frames_short flags."""
         self._call("encode_frames_short", ctypes.c_void_p(pcm_ptr), int(n_frames), ctypes.c_void_p(frames_ptr), int(flags))
+
+    def analyse_tones_ptr(self, bands_ptr, n_frames, blocks_ptr, residual_ptr, flags):
+        """Raw pointers (the records are host memory; None: not wanted) and at3phip_analyse_tones flags."""
+        self._call("analyse_tones", ctypes.c_void_p(bands_ptr), int(n_frames), ctypes.c_void_p(blocks_ptr), ctypes.c_void_p(residual_ptr),
+                   int(flags))
+
+    def encode_frames_tonal_ptr(self, pcm_ptr, n_frames, frames_ptr, flags):
+        """Raw pointers (float32 PCM) and at3phip_encode_frames_tonal flags."""
+        self._call("encode_frames_tonal", ctypes.c_void_p(pcm_ptr), int(n_frames), ctypes.c_void_p(frames_ptr), int(flags))
+
+    def encode_frames_tonal_s16_ptr(self, pcm_ptr, n_frames, frames_ptr, flags):
+        """Raw pointers (int16 PCM) and at3phip_encode_frames_tonal_short flags."""
+        self._call("encode_frames_tonal_short", ctypes.c_void_p(pcm_ptr), int(n_frames), ctypes.c_void_p(frames_ptr), int(flags))
 
     def _flags(self, win_flags, nf):
         """win_flags as uint16 [n_streams, nf, channels] (kept alive by the caller) and its address, or (None, None)"""
@@ -864,6 +891,42 @@ class At3pHip(_Context):
         encode_frames() on pcm / 32768 as float32, bit for bit; the samples cross the bus as 16-bit and are widened by the
         filter bank. Calls of both kinds may alternate."""
         return self._encode_frames_host(pcm, np.int16, self.encode_frames_s16_ptr)
+
+    def analyse_tones(self, bands):
+        """bands float32 [S, F, C, 16, 128] (what pqf() returns) -> (blocks of AT3P_TONAL_BLOCK_DTYPE [S, F], residual
+        [S, F, C, 16, 128]): at3phip_analyse_tones, slot f holding the block of (frame f-1, frame f) and the residual of frame
+        f-1; the last frame and block carry over to the next call."""
+        bands = np.ascontiguousarray(bands, dtype=np.float32)
+        assert bands.ndim == 5 and bands.shape[0] == self.n_streams and bands.shape[2:] == (self.channels, 16, 128), bands.shape
+        nf = bands.shape[1]
+        blocks = np.zeros((self.n_streams, nf), AT3P_TONAL_BLOCK_DTYPE)
+        resid = np.zeros_like(bands)
+        self.analyse_tones_ptr(bands.ctypes.data, nf, blocks.ctypes.data, resid.ctypes.data, 0)
+        return blocks, resid
+
+    def analyse_tones_device(self, bands_ptr, n_frames, residual_ptr):
+        """Device-resident subband samples and residual (raw pointers) -> the blocks [S, F] (host memory). The call waits; whatever
+        produces the samples must be complete before it (see encode_frames_device)."""
+        blocks = np.zeros((self.n_streams, int(n_frames)), AT3P_TONAL_BLOCK_DTYPE)
+        self.analyse_tones_ptr(bands_ptr, n_frames, blocks.ctypes.data, residual_ptr, _device_flags(False))
+        return blocks
+
+    def encode_frames_tonal(self, pcm):
+        """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, 2048] with the tone analysis (at3phip_encode_frames_tonal): frame f
+        of the stream holds the residual of input frame f-1 and the block of frame f-2, so one trailing frame of silence flushes."""
+        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr)
+
+    def encode_frames_tonal_s16(self, pcm):
+        """The same for int16 PCM (at3phip_encode_frames_tonal_short): the frames of encode_frames_tonal() on pcm / 32768."""
+        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr)
+
+    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
+        """Device-resident float32 PCM / frames; ordering and what stays untouched until sync() as in encode_frames_device."""
+        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous))
+
+    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
+        """Device-resident int16 PCM / frames, as encode_frames_tonal_device."""
+        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous))
 
     def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
         """asynchronous=True only queues the call (AT3HIP_ASYNC): sync() before the frames are read, and both buffers stay

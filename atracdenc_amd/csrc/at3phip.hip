@@ -1,4 +1,5 @@
 // C ABI of the ATRAC3plus front end (include/at3phip.h): context, device buffers, kernel launches.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -9,6 +10,7 @@
 #include "../../include/at3phip.h"
 #include "at3p_kernels.hpp"
 #include "at3p_write.hpp"
+#include "at3p_gha.hpp"
 #include "at3_host_util.hpp"
 
 using namespace at3p;
@@ -22,6 +24,10 @@ static_assert(sizeof(at3phip_tonal_block) == sizeof(TonalBlock) && offsetof(at3p
                   offsetof(at3phip_tonal_block, band) == offsetof(TonalBlock, band) && offsetof(at3phip_tonal_block, wave) == offsetof(TonalBlock, wave) &&
                   sizeof(at3phip_tonal_band) == 4 && AT3PHIP_TONAL_MAX_WAVES == kTonalMaxWaves && AT3PHIP_TONAL_MAX_BAND_WAVES == kTonalMaxBandWaves,
               "at3phip.h documents the tonal record's layout");
+static_assert(sizeof(ToneFindTables) == AT3PHIP_TONE_FIND_TABLES_BYTES, "at3phip.h documents the tone analysis' table block size");
+static_assert(AT3PHIP_TONE_MAX_BAND_WAVES == kToneBandWaves && AT3PHIP_TONE_FINE_SPAN == kToneSpan && AT3PHIP_TONE_PEAK_RATIO == 16.0 &&
+                  AT3PHIP_TONE_MIN_AMP == 8.0,
+              "at3phip.h names the constants of at3p_gha.hpp");
 
 struct at3phip_ctx : at3host::EngineBase {   // (no at3phip_set_stream: stream == own_stream)
     at3phip_config cfg;
@@ -37,6 +43,14 @@ struct at3phip_ctx : at3host::EngineBase {   // (no at3phip_set_stream: stream =
     WriteTables* d_wtables = nullptr;
     uint8_t* d_frames = nullptr;   // staging for host frames [S][F][2048]
     TonalBlock* d_tonal = nullptr; // the tonal records of a call [S][F], allocated by the first at3phip_write_frames_tonal that has any
+    // the tone analysis (at3p_gha.hpp): tables, buffers and state, all set up by the first call that analyses (ensure_tones)
+    ToneFindTables* d_tone_tables = nullptr;
+    ToneCand* d_tone_cand = nullptr;             // [S][F][nch][16][3]
+    TonalBlock* d_tone_blocks = nullptr;         // [S][F]
+    TonalBlock* d_tone_writer[2] = {nullptr, nullptr};   // [S][F] each: the writer's records, double-buffered like the spectra
+    float* d_tone_resid = nullptr;               // [S][F][nch][16][128]
+    float* d_tone_prev = nullptr;                // state: the last frame's subband samples [S][nch][16][128]
+    TonalBlock* d_tone_last = nullptr;           // state: the last block [S]
     // at3phip_encode_frames: the frame writer only needs the spectra of ITS call, so it runs on a stream of its own behind
     // an event and the next call's filter bank and transform overlap it; the spectra in between are double-buffered
     hipStream_t write_stream = nullptr;
@@ -57,6 +71,10 @@ int reset_state(at3phip_ctx* c)
     const size_t S = c->cfg.n_streams, C = c->cfg.channels;
     HIPCHK(c, hipMemsetAsync(c->d_pqf_hist, 0, S * C * kOverlap * sizeof(float), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_mdct_hist, 0, S * C * 2048 * sizeof(float), c->stream));
+    if (c->d_tone_last) {   // the tone analysis has been used: a zero frame before the stream, no block
+        HIPCHK(c, hipMemsetAsync(c->d_tone_prev, 0, S * C * 2048 * sizeof(float), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_tone_last, 0, S * sizeof(TonalBlock), c->stream));
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return AT3HIP_OK;
 }
@@ -108,9 +126,10 @@ int launch_mdct(at3phip_ctx* c, const float* d_bands, int n_frames, const uint16
     return AT3HIP_OK;
 }
 
-// tonal: the call's records [S][n_frames] in host memory, already checked (check_tonal), or null: the writer without records
+// tonal: the call's records [S][n_frames] in host memory, already checked (check_tonal), or null: the writer without records.
+// d_records: the same in device memory, as the tone analysis left them (valid by construction).
 int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint16_t* win_flags, uint8_t* d_frames, hipStream_t on = nullptr,
-                 const at3phip_tonal_block* tonal = nullptr)
+                 const at3phip_tonal_block* tonal = nullptr, const TonalBlock* d_records = nullptr)
 {
     const size_t S = c->cfg.n_streams, C = c->cfg.channels;
     if (!on) on = c->stream;
@@ -122,7 +141,11 @@ int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint1
     wp.out = d_frames;
     wp.nch = (int)C;
     wp.n_items = (int)(S * n_frames);
-    if (tonal) {
+    if (d_records) {
+        wp.tonal = d_records;
+        memcpy(wp.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(wp.tone_vlc));
+        hipLaunchKernelGGL(k_at3p_write_tonal, dim3((unsigned)(S * n_frames)), dim3(256), 0, on, wp);
+    } else if (tonal) {
         if (!c->d_tonal) {
             const int rc = dev_alloc(c, &c->d_tonal, S * (size_t)c->cfg.max_frames);
             if (rc != AT3HIP_OK) return rc;
@@ -134,6 +157,82 @@ int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint1
     } else {
         hipLaunchKernelGGL(k_at3p_write, dim3((unsigned)(S * n_frames)), dim3(256), 0, on, static_cast<const WriteParams&>(wp));
     }
+    HIPCHK(c, hipGetLastError());
+    return AT3HIP_OK;
+}
+
+// The tone analysis' tables with the host's libm (never constant-folded: optnone), as the decoder's tone tables are built.
+__attribute__((optnone, noinline)) void build_tone_find_tables(ToneFindTables* t)
+{
+    memset(t, 0, sizeof(*t));
+    for (int i = 0; i < 2048; ++i) t->sine[i] = (float)sin(2 * M_PI * i / 2048);
+    for (int i = 0; i < 256; ++i) t->hann[i] = (float)((1.0f - cos(2 * M_PI * i / 256.0f)) * 0.5f);
+    for (int i = 0; i < 64; ++i) t->amp_sf[i] = exp2f((i - 3) / 4.0f);
+    const double pi = 3.141592653589793238462643383279502884197169399375105820974944;   // kiss_fft.c:357-363
+    for (int i = 0; i < 256; ++i) {
+        const double ph = -2 * pi * i / 256;
+        t->tw[i].r = (float)cos(ph);
+        t->tw[i].i = (float)sin(ph);
+    }
+    for (int i = 0; i < 64; ++i) {
+        const double a = (double)t->amp_sf[i] * exp2(-0.125);
+        t->thr[i] = a * a;
+    }
+    for (int f = 0; f < 1024; ++f) {   // the projections' normalisers: sums over t = 0 .. 255 in order
+        double ns = 0, nc = 0;
+        for (int k = 0; k < 256; ++k) {
+            const int pos = ((k - 128) * f) & 2047;
+            const double sn = (double)t->sine[pos], cs = (double)t->sine[(pos + 512) & 2047];
+            ns = ns + (double)t->hann[k] * (sn * sn);
+            nc = nc + (double)t->hann[k] * (cs * cs);
+        }
+        t->rs[f] = ns > 0 ? 1.0 / ns : 0.0;
+        t->rc[f] = nc > 0 ? 1.0 / nc : 0.0;
+    }
+}
+
+// Tables, buffers and start-of-stream state of the tone analysis, on the first call that needs them (at3phip_create's runtime
+// calls stay what they were).
+int ensure_tones(at3phip_ctx* c)
+{
+    if (c->d_tone_tables) return AT3HIP_OK;
+    const size_t S = c->cfg.n_streams, F = c->cfg.max_frames, C = c->cfg.channels;
+    int rc;
+    if (!c->d_tone_cand && (rc = dev_alloc(c, &c->d_tone_cand, S * F * C * 16 * kToneBandWaves)) != AT3HIP_OK) return rc;
+    if (!c->d_tone_blocks && (rc = dev_alloc(c, &c->d_tone_blocks, S * F)) != AT3HIP_OK) return rc;
+    for (auto& w : c->d_tone_writer)
+        if (!w && (rc = dev_alloc(c, &w, S * F)) != AT3HIP_OK) return rc;
+    if (!c->d_tone_resid && (rc = dev_alloc(c, &c->d_tone_resid, S * F * C * 2048)) != AT3HIP_OK) return rc;
+    if (!c->d_tone_prev && (rc = dev_alloc(c, &c->d_tone_prev, S * C * 2048)) != AT3HIP_OK) return rc;
+    if (!c->d_tone_last && (rc = dev_alloc(c, &c->d_tone_last, S)) != AT3HIP_OK) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_tone_prev, 0, S * C * 2048 * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_tone_last, 0, S * sizeof(TonalBlock), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return at3host::make_device_tables(c, &c->d_tone_tables, [](ToneFindTables* t) { build_tone_find_tables(t); return true; });
+}
+
+// Steps 1-8 on d_bands: the blocks into d_tone_blocks, the residuals into d_resid, the writer's records (or none) into d_writer.
+int launch_tones(at3phip_ctx* c, const float* d_bands, int n_frames, float* d_resid, TonalBlock* d_writer)
+{
+    const unsigned S = (unsigned)c->cfg.n_streams, C = (unsigned)c->cfg.channels, F = (unsigned)n_frames;
+    ToneParams tp;
+    tp.T = c->d_tone_tables;
+    tp.bands = d_bands;
+    tp.prev_x = c->d_tone_prev;
+    tp.cand = c->d_tone_cand;
+    tp.blocks = c->d_tone_blocks;
+    tp.last = c->d_tone_last;
+    tp.writer = d_writer;
+    tp.resid = d_resid;
+    tp.n_frames = n_frames;
+    tp.nch = (int)C;
+    hipLaunchKernelGGL(k_at3p_tone_find, dim3(F * 4, S * C), dim3(256), 0, c->stream, tp);   // (slot, four subbands) x (stream, channel)
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_at3p_tone_select, dim3(F, S), dim3(128), 0, c->stream, tp);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_at3p_tone_sub, dim3(F, S * C), dim3(256), 0, c->stream, tp);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_at3p_tone_state, dim3(S), dim3(256), 0, c->stream, tp, c->d_tone_prev);
     HIPCHK(c, hipGetLastError());
     return AT3HIP_OK;
 }
@@ -256,7 +355,8 @@ void at3phip_destroy(at3phip_ctx* c)
 {
     if (c)
         at3host::destroy_engine(c, {c->d_tables, c->d_pcm_in, c->d_pcm_s16, c->d_bands, c->d_specs, c->d_specs_b[1], c->d_flags, c->d_pqf_hist,
-                                    c->d_mdct_hist, c->d_wtables, c->d_frames, c->d_tonal},
+                                    c->d_mdct_hist, c->d_wtables, c->d_frames, c->d_tonal, c->d_tone_tables, c->d_tone_cand, c->d_tone_blocks,
+                                    c->d_tone_writer[0], c->d_tone_writer[1], c->d_tone_resid, c->d_tone_prev, c->d_tone_last},
                                 {c->write_stream}, [c] {
                                     for (hipEvent_t e : {c->ev[0], c->ev[1], c->ev[2], c->ev[3], c->ev[4], c->ev_specs[0], c->ev_specs[1],
                                                          c->ev_write_done[0], c->ev_write_done[1]})
@@ -344,13 +444,19 @@ namespace {
 
 // at3phip_encode_frames (T = float) and at3phip_encode_frames_short (T = int16_t): the sample type is the filter bank's and its
 // state kernel's template parameter, everything behind them is shared.
-template <typename T>
+// kTones: at3phip_encode_frames_tonal(_short): the tone analysis between the filter bank and the transform, the transform on
+// its residual, the writer with its records.
+template <typename T, bool kTones = false>
 int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
 {
     constexpr bool kShort = sizeof(T) == sizeof(int16_t);
     if (!c || !pcm || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
     at3host::DeviceGuard guard(c->device);
     HIPCHK(c, guard.error());
+    if constexpr (kTones) {
+        const int rc = ensure_tones(c);
+        if (rc != AT3HIP_OK) return rc;
+    }
     const size_t items = (size_t)c->cfg.n_streams * n_frames;
     const size_t n = items * c->cfg.channels * 2048;
     const T* d_pcm = pcm;
@@ -381,13 +487,19 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     int rc = launch_pqf(c, d_pcm, n_frames, c->d_bands);
     if (rc != AT3HIP_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    rc = launch_mdct(c, c->d_bands, n_frames, nullptr, d_specs, AT3PHIP_RESIDUAL_SCALE);   // sine windows: EncodeFrame's default Win
+    const float* d_mdct_in = c->d_bands;
+    if constexpr (kTones) {   // (its time counts as the transform's)
+        rc = launch_tones(c, c->d_bands, n_frames, c->d_tone_resid, c->d_tone_writer[par]);
+        if (rc != AT3HIP_OK) return rc;
+        d_mdct_in = c->d_tone_resid;
+    }
+    rc = launch_mdct(c, d_mdct_in, n_frames, nullptr, d_specs, AT3PHIP_RESIDUAL_SCALE);   // sine windows: EncodeFrame's default Win
     if (rc != AT3HIP_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     HIPCHK(c, hipEventRecord(c->ev_specs[par], c->stream));
     HIPCHK(c, hipStreamWaitEvent(ws, c->ev_specs[par], 0));
     if (timed) HIPCHK(c, hipEventRecord(c->ev[4], ws));
-    rc = launch_write(c, d_specs, n_frames, nullptr, d_frames, ws);
+    rc = launch_write(c, d_specs, n_frames, nullptr, d_frames, ws, nullptr, kTones ? c->d_tone_writer[par] : nullptr);
     if (rc != AT3HIP_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[3], ws));
     if (!(flags & AT3HIP_OUT_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(frames, c->d_frames, items * kFrameBytes, hipMemcpyDeviceToHost, ws));
@@ -412,6 +524,49 @@ int at3phip_encode_frames(at3phip_ctx* c, const float* pcm, int32_t n_frames, ui
 int at3phip_encode_frames_short(at3phip_ctx* c, const int16_t* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
 {
     return encode_frames_impl(c, pcm, n_frames, frames, flags);
+}
+
+int at3phip_encode_frames_tonal(at3phip_ctx* c, const float* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
+{
+    return encode_frames_impl<float, true>(c, pcm, n_frames, frames, flags);
+}
+
+int at3phip_encode_frames_tonal_short(at3phip_ctx* c, const int16_t* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
+{
+    return encode_frames_impl<int16_t, true>(c, pcm, n_frames, frames, flags);
+}
+
+int at3phip_analyse_tones(at3phip_ctx* c, const float* bands, int32_t n_frames, at3phip_tonal_block* blocks, float* residual, uint32_t flags)
+{
+    if (!c || !bands || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
+    at3host::DeviceGuard guard(c->device);
+    HIPCHK(c, guard.error());
+    if (int qrc = quiesce(c)) return qrc;
+    int rc = ensure_tones(c);
+    if (rc != AT3HIP_OK) return rc;
+    const size_t items = (size_t)c->cfg.n_streams * n_frames;
+    const size_t bytes = items * c->cfg.channels * 2048 * sizeof(float);
+    const float* d_bands = bands;
+    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
+        HIPCHK(c, hipMemcpyAsync(c->d_bands, bands, bytes, hipMemcpyHostToDevice, c->stream));
+        d_bands = c->d_bands;
+    }
+    const bool out_dev = (flags & AT3HIP_OUT_ON_DEVICE) != 0;
+    float* d_resid = (out_dev && residual) ? residual : c->d_tone_resid;
+    c->ev_from_encode = false;
+    rc = launch_tones(c, d_bands, n_frames, d_resid, nullptr);
+    if (rc != AT3HIP_OK) return rc;
+    if (blocks) HIPCHK(c, hipMemcpyAsync(blocks, c->d_tone_blocks, items * sizeof(TonalBlock), hipMemcpyDeviceToHost, c->stream));
+    if (residual && !out_dev) HIPCHK(c, hipMemcpyAsync(residual, c->d_tone_resid, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return AT3HIP_OK;
+}
+
+int at3phip_host_tone_find_tables(void* dst, size_t bytes)
+{
+    if (!dst || bytes != sizeof(ToneFindTables)) return AT3HIP_EINVAL;
+    build_tone_find_tables((ToneFindTables*)dst);
+    return AT3HIP_OK;
 }
 
 int at3phip_sync(at3phip_ctx* c)

@@ -659,13 +659,227 @@ public:
                                                  const float* raw2Cur) = 0;
 };
 
+
+// The tone analysis of include/at3phip.h (FINDING TONES, steps 1-8) on the CPU, as plain C++ with no GPU: what
+// at3phip_encode_frames_tonal computes, behind the mirror's analyser interface. A call receives previous, current and next; the
+// block it returns is written with the previous buffer's spectrum one call later, so it analyses the pair (previous as passed in,
+// current), ignores next, and subtracts from the previous buffer: this block fading in, the block of the call before fading out.
+// Every sum runs in the header's order; compile without floating-point contraction (no FMA), like the kernels.
+// The same analysis is written out in atracdenc_amd/csrc/at3p_gha.hpp (the kernels) and tests/host/at3p_gha_cpu.c (the C
+// restatement): the three change together.
+class TAt3PToneAnalyser : public IAt3PGhaProcessor {
+public:
+    explicit TAt3PToneAnalyser(int channels) : Channels(channels)
+    {
+        if (at3phip_host_tone_find_tables(&T, sizeof(T)) != AT3HIP_OK) throw std::runtime_error("at3phip_host_tone_find_tables failed");
+    }
+    const at3phip_tonal_block* DoAnalize(TBufPtr b1, TBufPtr b2, float* w1, float* w2, const float*, const float*) override
+    {
+        const float* cur[2] = {b1[0], b2[0]};
+        float* prev[2] = {w1, w2};
+        TWave w[2 * 16 * AT3PHIP_TONE_MAX_BAND_WAVES];
+        int nw = 0;
+        for (int ch = 0; ch < Channels; ++ch)
+            for (int sb = 0; sb < 16; ++sb) {
+                float x[256];
+                std::copy(prev[ch] + sb * 128, prev[ch] + sb * 128 + 128, x);
+                std::copy(cur[ch] + sb * 128, cur[ch] + sb * 128 + 128, x + 128);
+                const int got = FindBand(x, w + nw);
+                for (int i = 0; i < got; ++i) {
+                    w[nw + i].Ch = ch;
+                    w[nw + i].Sb = sb;
+                }
+                nw += got;
+            }
+        const at3phip_tonal_block before = Block;
+        Select(w, nw);
+        for (int ch = 0; ch < Channels; ++ch)
+            for (int sb = 0; sb < 16; ++sb) Subtract(before, Block, ch, sb, prev[ch] + sb * 128);
+        return &Block;
+    }
+
+private:
+    struct TTables {   // the block of at3phip_host_tone_find_tables
+        float Sine[2048], Hann[256], AmpSf[64], Tw[256][2];
+        double Thr[64], Rs[1024], Rc[1024];
+    };
+    static_assert(sizeof(TTables) == AT3PHIP_TONE_FIND_TABLES_BYTES, "the table block's documented size");
+    struct TWave {
+        int Ch, Sb, Freq, AmpSf, Phase;
+        double A2;
+        bool Keep;
+    };
+    struct TCpx {
+        float r, i;
+    };
+    // the kissfft-order forward FFT for n = 4^k (kf_work and kf_bfly4, kiss_fft.c:42-90, 238-302)
+    void Fft(TCpx* out, const TCpx* in, int n, int fstride) const
+    {
+        const int m = n / 4;
+        if (m == 1) {
+            for (int q = 0; q < 4; ++q) out[q] = in[q * fstride];
+        } else {
+            for (int q = 0; q < 4; ++q) Fft(out + q * m, in + q * fstride, m, fstride * 4);
+        }
+        auto mul = [this](TCpx a, int t) {
+            TCpx r;
+            r.r = a.r * T.Tw[t][0] - a.i * T.Tw[t][1];
+            r.i = a.r * T.Tw[t][1] + a.i * T.Tw[t][0];
+            return r;
+        };
+        for (int k = 0; k < m; ++k) {
+            const TCpx s0 = mul(out[m + k], k * fstride), s1 = mul(out[2 * m + k], 2 * k * fstride), s2 = mul(out[3 * m + k], 3 * k * fstride);
+            TCpx s5, s3, s4;
+            s5.r = out[k].r - s1.r; s5.i = out[k].i - s1.i;
+            out[k].r += s1.r; out[k].i += s1.i;
+            s3.r = s0.r + s2.r; s3.i = s0.i + s2.i;
+            s4.r = s0.r - s2.r; s4.i = s0.i - s2.i;
+            out[2 * m + k].r = out[k].r - s3.r; out[2 * m + k].i = out[k].i - s3.i;
+            out[k].r += s3.r; out[k].i += s3.i;
+            out[m + k].r = s5.r + s4.i; out[m + k].i = s5.i - s4.r;
+            out[3 * m + k].r = s5.r - s4.i; out[3 * m + k].i = s5.i + s4.r;
+        }
+    }
+    // steps 1-5 for one subband: at most AT3PHIP_TONE_MAX_BAND_WAVES waves
+    int FindBand(const float* x, TWave* out) const
+    {
+        constexpr int kMax = AT3PHIP_TONE_MAX_BAND_WAVES, kSpan = AT3PHIP_TONE_FINE_SPAN;
+        float y[256], P[129];
+        TCpx in[256], F[256];
+        for (int t = 0; t < 256; ++t) {
+            y[t] = x[t] * T.Hann[t];
+            in[t].r = y[t];
+            in[t].i = 0.0f;
+        }
+        Fft(F, in, 256, 1);
+        for (int k = 0; k <= 128; ++k) P[k] = F[k].r * F[k].r + F[k].i * F[k].i;
+        float sum = 0.0f;
+        for (int k = 1; k <= 127; ++k) sum = sum + P[k];
+        const double floorP = AT3PHIP_TONE_PEAK_RATIO * ((double)sum / 127.0);
+        int ck[kMax], nc = 0;
+        for (int k = 0; k <= 128; ++k) {   // (the spectrum of a real signal is even about bins 0 and 128)
+            if (!(P[k] > P[k == 0 ? 1 : k - 1] && P[k] >= P[k == 128 ? 127 : k + 1] && (double)P[k] >= floorP)) continue;
+            int at = nc;   // by descending power; an equal power stays behind the lower k
+            while (at > 0 && P[k] > P[ck[at - 1]]) --at;
+            if (at >= kMax) continue;
+            for (int j = nc < kMax ? nc : kMax - 1; j > at; --j) ck[j] = ck[j - 1];
+            ck[at] = k;
+            if (nc < kMax) ++nc;
+        }
+        int n = 0;
+        for (int c = 0; c < nc; ++c) {
+            const int lo = std::max(1, 8 * ck[c] - kSpan), hi = std::min(1023, 8 * ck[c] + kSpan);
+            int bf = -1;
+            double bs = 0, bc = 0, bp = 0;
+            for (int f = lo; f <= hi; ++f) {
+                double S = 0, C = 0;
+                for (int t = 0; t < 256; ++t) {
+                    const int pos = ((t - 128) * f) & 2047;
+                    S = S + (double)y[t] * (double)T.Sine[pos];
+                    C = C + (double)y[t] * (double)T.Sine[(pos + 512) & 2047];
+                }
+                const double pw = (S * S) * T.Rs[f] + (C * C) * T.Rc[f];
+                if (bf < 0 || pw > bp) {
+                    bf = f;
+                    bs = S;
+                    bc = C;
+                    bp = pw;
+                }
+            }
+            if (bf < 0) continue;
+            const double ca = bs * T.Rs[bf], cb = bc * T.Rc[bf];   // x[t] = ca sin + cb cos, by least squares under the window
+            const double a2 = ca * ca + cb * cb;
+            if (!(a2 >= AT3PHIP_TONE_MIN_AMP * AT3PHIP_TONE_MIN_AMP)) continue;
+            int sf = 0;
+            for (int i = 0; i < 64; ++i)
+                if (a2 >= T.Thr[i]) sf = i;
+            int ph = 0;
+            double bv = 0;
+            for (int q = 0; q < 32; ++q) {
+                const double v = ca * (double)T.Sine[(64 * q + 512) & 2047] + cb * (double)T.Sine[64 * q];
+                if (q == 0 || v > bv) {
+                    ph = q;
+                    bv = v;
+                }
+            }
+            out[n].Freq = bf;
+            out[n].AmpSf = sf;
+            out[n].Phase = ph;
+            out[n].A2 = a2;
+            ++n;
+        }
+        return n;
+    }
+    static bool Before(const TWave& a, const TWave& b)   // the record's order: channel, band, frequency index
+    {
+        return a.Ch != b.Ch ? a.Ch < b.Ch : a.Sb != b.Sb ? a.Sb < b.Sb : a.Freq < b.Freq;
+    }
+    // steps 6-7
+    void Select(TWave* w, int nw)
+    {
+        Block = at3phip_tonal_block{};
+        for (int i = 0; i < nw; ++i) {
+            int rank = 0;
+            for (int j = 0; j < nw; ++j)
+                if (j != i && (w[j].A2 > w[i].A2 || (w[j].A2 == w[i].A2 && Before(w[j], w[i])))) ++rank;
+            w[i].Keep = rank < AT3PHIP_TONAL_MAX_WAVES;
+        }
+        for (int i = 0; i < nw; ++i) {
+            if (!w[i].Keep) continue;
+            int at = 0;
+            for (int j = 0; j < nw; ++j)
+                if (w[j].Keep && Before(w[j], w[i])) ++at;
+            Block.wave[at] = AT3PHIP_TONAL_WAVE(w[i].Freq, w[i].AmpSf, w[i].Phase);
+            Block.band[w[i].Ch][w[i].Sb].n_waves++;
+            Block.num_tone_bands = (uint8_t)std::max<int>(Block.num_tone_bands, w[i].Sb + 1);
+        }
+    }
+    // a band's waves at the samples of one frame (the decoder's step 4b without an envelope): reg = 128 fading out, 0 fading in
+    void Waves(const at3phip_tonal_block& b, int ch, int sb, int reg, float* out) const
+    {
+        int first = 0;
+        for (int c = 0; c <= ch; ++c)   // channel 0's bands go first
+            for (int k = 0; k < (c < ch ? 16 : sb); ++k) first += b.band[c][k].n_waves;
+        for (int wn = 0; wn < b.band[ch][sb].n_waves; ++wn) {
+            const uint32_t wv = b.wave[first + wn];
+            const double amp = (double)T.AmpSf[(wv >> 10) & 63u];
+            const int inc = (int)(wv & 1023u);
+            int pos = ((int)(((wv >> 16) & 31u) << 6) - (reg ^ 128) * inc) & 2047;
+            for (int i = 0; i < 128; ++i) {
+                out[i] = (float)((double)out[i] + (double)T.Sine[pos] * amp);
+                pos = (pos + inc) & 2047;
+            }
+        }
+    }
+    // step 8 for one band: ApplyFilter's out -= wavreg1 + wavreg2
+    void Subtract(const at3phip_tonal_block& before, const at3phip_tonal_block& now, int ch, int sb, float* x) const
+    {
+        const int n1 = before.band[ch][sb].n_waves, n2 = now.band[ch][sb].n_waves;
+        if (!n1 && !n2) return;
+        float w1[128] = {0}, w2[128] = {0};
+        Waves(before, ch, sb, 128, w1);
+        Waves(now, ch, sb, 0, w2);
+        for (int i = 0; i < 128; ++i) {
+            if (n1) w1[i] = w1[i] * T.Hann[128 + i];
+            if (n2) w2[i] = w2[i] * T.Hann[i];
+            x[i] -= w1[i] + w2[i];
+        }
+    }
+    const int Channels;
+    TTables T;
+    at3phip_tonal_block Block{};   // the last block found
+};
+
 class TAt3PEncoder {
 public:
+    // deviceTones: the tone analysis on the GPU (at3phip_encode_frames_tonal, a batch per call) instead of an analyser on the
+    // host: byte for byte the frames of this class around TAt3PToneAnalyser with UseGha = GHA_ENABLED. `gha` must then be null.
     TAt3PEncoder(TCompressedOutputPtr&& out, int channels, int batchFrames = 64, int deviceId = 0, TAt3PSettings settings = TAt3PSettings(),
-                 IAt3PGhaProcessor* gha = nullptr)
+                 IAt3PGhaProcessor* gha = nullptr, bool deviceTones = false)
         : Out(std::move(out)), Channels((size_t)channels), BatchFrames(batchFrames), FrameFloats((size_t)AT3PHIP_FRAME * (size_t)channels),
-          Settings(settings), Gha(gha)
+          Settings(settings), Gha(gha), DeviceTones(deviceTones)
     {
+        if (deviceTones && gha) throw std::invalid_argument("TAt3PEncoder: deviceTones takes no host analyser");
         at3phip_config cfg{};
         cfg.channels = channels;
         cfg.n_streams = 1;
@@ -717,7 +931,8 @@ public:
         std::vector<uint8_t> frames((size_t)BatchFrames * AT3PHIP_FRAME_BYTES);
         for (int at = 0; at < nFrames; at += BatchFrames) {
             const int nf = std::min(BatchFrames, nFrames - at);
-            Chk(at3phip_encode_frames_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), 0), "at3phip_encode_frames_short");
+            if (DeviceTones) Chk(at3phip_encode_frames_tonal_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), 0), "at3phip_encode_frames_tonal_short");
+            else Chk(at3phip_encode_frames_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), 0), "at3phip_encode_frames_short");
             for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES);
             Calls += (size_t)nf;
             Flush();
@@ -735,13 +950,16 @@ public:
         }
         if (nf > 0) {
             std::vector<uint8_t> frames((size_t)nf * AT3PHIP_FRAME_BYTES);
-            Chk(at3phip_encode_frames(Ctx, Pending.data(), nf, frames.data(), 0), "at3phip_encode_frames");
+            if (DeviceTones) Chk(at3phip_encode_frames_tonal(Ctx, Pending.data(), nf, frames.data(), 0), "at3phip_encode_frames_tonal");
+            else Chk(at3phip_encode_frames(Ctx, Pending.data(), nf, frames.data(), 0), "at3phip_encode_frames");
             Pending.clear();
             for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES);
         }
-        // call k (0-based) is answered with: nothing (k = 0), silence (k = 1), input frame k - 2
+        // call k (0-based) is answered with: nothing (k = 0), silence (k = 1), input frame k - 2; with deviceTones the analysis lags
+        // one frame itself (its frame f holds the residual of input frame f - 1), so call k >= 1 is answered with its frame k - 1
+        // and the stream's last frame stays behind, as it does on the host
         while (Written + 1 < Calls) {
-            if (Written == 0) {
+            if (Written == 0 && !DeviceTones) {
                 Out->WriteFrame(SilentFrame());
             } else {
                 Out->WriteFrame(std::move(Ready.front()));
@@ -817,6 +1035,7 @@ private:
     size_t Calls = 0, Written = 0;
     const TAt3PSettings Settings;
     IAt3PGhaProcessor* const Gha;                 // not owned; null: the analysis finds nothing
+    const bool DeviceTones;                       // the analysis runs on the GPU
     std::vector<float> PrevBuf, CurBuf, RawCur;   // [C][16][128] / [C][2048]: TChannelCtx's PrevBuf, CurBuf and RawCurBuf
     at3phip_tonal_block Delay{};                  // `delay`: the block the next call writes
 };

@@ -409,6 +409,8 @@ int at3hip_decoder_set_stream(at3hip_decoder* dec, void* hip_stream);
  *        AT3HIP_EINVAL before and now take it as AT3HIP_RESAMPLE_OUT_S16 (a library with at3hip_resampler_process_s16 does)
  *        and, added later under the same number, the ATRAC3plus frame writer with tonal blocks: at3phip_write_frames_tonal and
  *        at3phip_tonal_block (at3phip.h), detected by the symbol
+ *        and, added later under the same number, the ATRAC3plus tone analysis (at3phip.h, FINDING TONES): at3phip_analyse_tones,
+ *        at3phip_encode_frames_tonal, at3phip_encode_frames_tonal_short, at3phip_host_tone_find_tables; each detected by its symbol
  * A host layer compiled against this header checks at3hip_version() >= AT3HIP_VERSION before it relies on them
  * (atracdenc_amd/host/at3hip_host.hpp and the ctypes stub do). */
 #define AT3HIP_VERSION_MAJOR 1

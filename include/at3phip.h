@@ -2,9 +2,9 @@
  * filter and the windowed MDCT-256 x 16 that turn PCM into the 2048-line spectrum (at3p.cpp:93-99, 139-159), and the
  * frame writer that scales and packs it, with or without a tonal block (at3p.cpp:159-163: ScaleFrame, then
  * TAt3PBitStream::WriteFrame(channels, p, sces)). The tonal (GHA) analysis between them needs libgha, an
- * un-vendored submodule of the reference, and is not part of this row: its result comes from the caller
- * (at3phip_write_frames_tonal), and at3phip_encode_frames is the encoder with that analysis finding nothing. Same library
- * (libat3hip.so) and error codes as at3hip.h.
+ * un-vendored submodule of the reference: its result comes from the caller (at3phip_write_frames_tonal) or from this project's
+ * own analysis (FINDING TONES below: at3phip_encode_frames_tonal), and at3phip_encode_frames is the encoder with that analysis
+ * finding nothing. Same library (libat3hip.so) and error codes as at3hip.h.
  */
 #ifndef AT3PHIP_H
 #define AT3PHIP_H
@@ -135,6 +135,91 @@ int at3phip_encode_frames(at3phip_ctx* ctx, const float* pcm, int32_t n_frames, 
  * the device. Calls of both kinds may alternate on one context: the carried state is float. A device pointer needs only int16_t
  * alignment. Added under ABI 1.6: a host looks for this symbol. */
 int at3phip_encode_frames_short(at3phip_ctx* ctx, const int16_t* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags);
+/* FINDING TONES. The analysis between the filter bank and the transform that TAt3PEnc::EncodeFrame leaves to libgha (at3p.cpp:
+ * 118-170), an un-vendored submodule of the reference: there is nothing to restate, so steps 1-8 are this project's definition,
+ * pinned bit for bit to tests/host/at3p_gha_cpu.c and anchored to the round trip of tests/test_at3p_gha_cpu.py.
+ *
+ * Definition. Input: the subband samples at3phip_pqf_analyse writes, [16][128] per channel and frame, in the scale they have
+ * there. Tables: sine_table[2048], hann_window[256], amp_sf_tab[64] of the decoder (at3phip_decoder_host_tone_tables), the
+ * forward twiddles tw[i] = ((float)cos(ph), (float)sin(ph)), ph = -2 pi i / 256 in double (kiss_fft.c:357-363), and
+ * thr[i] = a * a, a = (double)amp_sf_tab[i] * exp2(-0.125), in double, and the projections' normalisers of steps 4 and 5,
+ * rs[f] = 1.0 / sum over t of (double)hann_window[t] * (s * s), s = (double)sine_table[((t - 128) f) & 2047], and rc[f] the same with
+ * sine_table[((t - 128) f + 512) & 2047], summed from 0.0 for t = 0..255 in order; all built on the host
+ * (at3phip_host_tone_find_tables). Away from the ends rs and rc are 1 / 64 to a few parts in a thousand; within a bin or two of
+ * frequency index 0 or 1024 the sine's mirror image falls into the window's main lobe and they are what keeps the amplitude right.
+ * Block T_m of frame m describes Hann-windowed sines over the 256 samples x[0..255] = subband b of frame m, then subband b of
+ * frame m+1: what the decoder synthesises for it (block m fades in over frame m, out over frame m+1, phases refer to sample 128).
+ * Per channel and subband, all 16; float and double operations as written, each rounded, no FMA:
+ *   1. y[t] = x[t] * hann_window[t] (float).
+ *   2. Coarse spectrum: the 256-point forward FFT of (y[t], 0.0f) in float, in kissfft's order for 256 = 4 x 4 x 4 x 4
+ *      (kf_work and kf_bfly4, kiss_fft.c:42-90, 238-302, with the twiddles above); P[k] = re * re + im * im (float), k = 0..128.
+ *      Bin k is frequency index 8 k.
+ *   3. Candidates: sum = P[1] + P[2] + ... + P[127] in float, in this order; floor = 16.0 * ((double)sum / 127.0) in double. A bin
+ *      k in 0..128 is a candidate when P[k] > P[k-1], P[k] >= P[k+1] and (double)P[k] >= floor, with P[-1] = P[1] and
+ *      P[129] = P[127] (the spectrum of a real signal is even about bins 0 and 128; without the two end bins no sine within half
+ *      a bin of either end, and no frequency index above 1015, could be found). The AT3PHIP_TONE_MAX_BAND_WAVES (3) candidates
+ *      of largest P are kept, the lower k on equal P; they go on in descending order of P.
+ *   4. Fine search per candidate, for every frequency index f in max(1, 8 k - 7) .. min(1023, 8 k + 7):
+ *      S(f) = sum over t of (double)y[t] * (double)sine_table[((t - 128) f) & 2047],
+ *      C(f) = the same with sine_table[((t - 128) f + 512) & 2047], both from 0.0 for t = 0..255 in order. The f of largest
+ *      (S * S) * rs[f] + (C * C) * rc[f] (double: the energy the fit of step 5 explains) is taken, the lowest on a tie.
+ *   5. a = S * rs[f], b = C * rc[f]: the least-squares fit x[t] = a sin + b cos under the window (the window and the phases are
+ *      symmetric about sample 128, so sine and cosine are orthogonal under it). A2 = a * a + b * b. The wave is kept when
+ *      A2 >= 8.0 * 8.0. AmpSf = the largest i with A2 >= thr[i] (0 when there is none). PhaseIndex = the p in 0..31 of largest
+ *      a * (double)sine_table[(64 p + 512) & 2047] + b * (double)sine_table[64 p], the lowest on a tie.
+ *   6. Frame budget: the kept waves of the frame, both channels together, ranked by A2 descending, equal A2 by channel, then
+ *      band, then frequency index; the first AT3PHIP_TONAL_MAX_WAVES (48) stay.
+ *   7. The at3phip_tonal_block: a band's waves by ascending FreqIndex (two candidates are at least 2 bins apart, so their
+ *      refined indices differ); num_tone_bands = the highest band holding a wave in either channel, plus 1; no envelope point
+ *      (start = stop = 0), no sharing, no leader. A frame without waves gives the all-zero record.
+ *   8. Residual: r_m = x_m - (T_m fading in + T_{m-1} fading out): ff_atrac3p_generate_tones as TGhaProcessorBase::ApplyFilter
+ *      uses it, out -= wavreg1 + wavreg2, with the numerics of the decoder's step 4b (tests/host/at3p_tonal_cpu.c,
+ *      at3pt_apply_filter). A band without waves in both blocks is left as it is.
+ *   9. The frame that carries r_m's spectrum carries block T_{m-1} (the transform delays by one frame: the decoder's frame n
+ *      gives input frame n-1). State at reset: a zero frame before the stream and no block before T_{-1}, which is found from
+ *      (zeros, frame 0) like any other.
+ * The constants are those of the prototype whose round-trip figures DESIGN.md section 17 lists; changing one changes the
+ * definition. Against that prototype the definition admits the end bins in step 3 and normalises by rs and rc instead of 1 / 64
+ * in steps 4 and 5: both only matter next to frequency index 0 or 1024, and the round-trip figures stay within 0.5 dB of it. Out of this definition: envelope points, sharing and the leader flag, any psychoacoustic veto. */
+#define AT3PHIP_TONE_PEAK_RATIO 16.0      /* step 3: a candidate's power over the mean power */
+#define AT3PHIP_TONE_MAX_BAND_WAVES 3     /* step 3: candidates per channel and subband */
+#define AT3PHIP_TONE_FINE_SPAN 7          /* step 4: frequency indices searched on either side of 8 k */
+#define AT3PHIP_TONE_MIN_AMP 8.0          /* step 5: the smallest amplitude kept, in subband sample units */
+
+/* Steps 1-8 on caller-supplied subband samples: the stage tap of at3phip_encode_frames_tonal.
+ *   bands     [n_streams][n_frames][channels][16][128] float32 as at3phip_pqf_analyse writes them (flags & AT3HIP_PCM_ON_DEVICE:
+ *             device memory)
+ *   blocks    [n_streams][n_frames] records, host memory: slot f = the block of (the frame before frame f, frame f), the record
+ *             the writer pairs with the NEXT residual; may be NULL
+ *   residual  [n_streams][n_frames][channels][16][128] float32: slot f = the residual of the frame before frame f (a frame's
+ *             block needs its successor, so the engine lags one frame); not divided by 32768 / 1.122018; may be NULL
+ *             (flags & AT3HIP_OUT_ON_DEVICE: device memory)
+ * State carried per stream between calls, of this function and of at3phip_encode_frames_tonal alike: the last frame's subband
+ * samples and the last block; at3phip_reset clears it. Its buffers and tables are set up by the first call that needs them, not
+ * by at3phip_create. Any float is accepted: every table index is masked, comparisons with a NaN are false (no candidate, no
+ * wave). Added under ABI 1.6: a host looks for this symbol. */
+int at3phip_analyse_tones(at3phip_ctx* ctx, const float* bands, int32_t n_frames, at3phip_tonal_block* blocks, float* residual,
+                          uint32_t flags);
+
+/* PCM to frames with the analysis: at3phip_pqf_analyse, steps 1-8, at3phip_mdct with AT3PHIP_RESIDUAL_SCALE and sine windows on
+ * the residual, and the writer of at3phip_write_frames_tonal taking its records from device memory (valid by construction: no
+ * host check); everything in between stays in HBM. Counted over the stream's life, output frame f holds the spectrum of residual
+ * f-1 and block T_{f-2}: one frame later than at3phip_encode_frames, so ONE TRAILING FRAME OF SILENCE flushes the stream. Byte
+ * for byte the frames of the host mirror's TAt3PEncoder with TAt3PToneAnalyser plugged in (atracdenc_amd/host/at3hip_host.hpp).
+ * Where no wave is found and the carried state holds none, the frames are at3phip_encode_frames', one frame later. pcm, frames,
+ * flags, AT3HIP_ASYNC / at3phip_sync and at3phip_reset as for at3phip_encode_frames; calls of the two kinds share the filter
+ * bank's and the transform's state but not the lag, so a stream stays with one of them between resets.
+ * Added under ABI 1.6: a host looks for this symbol. */
+int at3phip_encode_frames_tonal(at3phip_ctx* ctx, const float* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags);
+/* The same for 16-bit PCM, widened in the filter bank's loads by the rule of at3phip_encode_frames_short. */
+int at3phip_encode_frames_tonal_short(at3phip_ctx* ctx, const int16_t* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags);
+
+/* The analysis' tables as the first tonal call builds them, on the host (no GPU needed): float sine_table[2048],
+ * float hann_window[256], float amp_sf_tab[64], float tw[256][2], double thr[64], double rs[1024], double rc[1024].
+ * bytes = AT3PHIP_TONE_FIND_TABLES_BYTES. */
+#define AT3PHIP_TONE_FIND_TABLES_BYTES 28416
+int at3phip_host_tone_find_tables(void* dst, size_t bytes);
+
 /* With AT3HIP_ASYNC in `flags` at3phip_encode_frames only queues the call (pcm must stay valid, frames must not be read)
  * and the frame writer of one call runs beside the filter bank and transform of the next (its own stream, spectra
  * double-buffered); at3phip_sync waits for everything queued. Without the flag the call waits itself. A queued call records no
