@@ -111,6 +111,16 @@ class LoudnessResult(ctypes.Structure):
 LOUDNESS_HOP = 4410
 
 
+class LimitStats(ctypes.Structure):
+    """at3hip_limit_stats: min_sum / LIMIT_FULL is the smallest smoothed gain of the run, n_limited of n_out outputs were reduced"""
+    _fields_ = [("min_sum", ctypes.c_int64), ("n_limited", ctypes.c_int64), ("n_out", ctypes.c_int64)]
+
+
+LIMIT_LOOKAHEAD, LIMIT_HOLD = 220, 2205
+LIMIT_FULL = (LIMIT_LOOKAHEAD + 1) << 30
+AT3HIP_LIMIT_TRUE_PEAK = 1
+
+
 class At1Timings(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("total_ms", "front_ms", "scan_ms", "pack_ms")]
 
@@ -155,6 +165,9 @@ PROTOTYPES = {
     "at3hip_loudness_apply": (_RC, [_VP, _VP, _I32, _VP, _VP, _U32]), "at3hip_loudness_apply_s16": (_RC, [_VP, _VP, _I32, _VP, _VP, _U32]),
     "at3hip_loudness_finish": (_RC, [_VP, _RESP]), "at3hip_loudness_read_hops": (_RC, [_VP, _I32, _VP, _SZ]),
     "at3hip_loudness_gate": (_RC, [_VP, _I32, _I32, _RESP]), "at3hip_loudness_gain": (_RC, [_RESP, ctypes.c_double, ctypes.c_double, _F32P]),
+    "at3hip_loudness_limit_start": (_RC, [_VP, _VP, ctypes.c_float, _U32]), "at3hip_loudness_limit_delay": (_I32, [_U32]),
+    "at3hip_loudness_limit": (_RC, [_VP, _VP, _I32, _VP, _I32P, _U32]), "at3hip_loudness_limit_s16": (_RC, [_VP, _VP, _I32, _VP, _I32P, _U32]),
+    "at3hip_loudness_limit_flush": (_RC, [_VP, _VP, _I32P, _U32]), "at3hip_loudness_limit_stats": (_RC, [_VP, _P(LimitStats)]),
     # include/at1hip.h: the ATRAC1 encoder
     "at1hip_create": (_RC, [_P(At1Config), _P(_VP)]), "at1hip_destroy": (None, [_VP]), "at1hip_last_error": (_STR, [_VP]),
     "at1hip_reset": (_RC, [_VP]), "at1hip_sync": (_RC, [_VP]),
@@ -1185,3 +1198,70 @@ class HipLoudness(_Context):
         assert out.device == pcm.device and out.numel() >= pcm.numel()
         self._order_behind_torch(pcm.device, ordered)
         self.apply_ptr(pcm.data_ptr(), pcm.shape[1], gains, out.data_ptr(), _device_flags(asynchronous))
+
+    # ---- the look-ahead limiter (at3hip_loudness.h, "The look-ahead limiter") ----
+    def limit_delay(self, true_peak=False):
+        """the latency in samples (at3hip_loudness_limit_delay; no GPU)"""
+        return int(_need(self.lib, "at3hip_loudness_limit_delay")(AT3HIP_LIMIT_TRUE_PEAK if true_peak else 0))
+
+    def limit_start(self, gains, ceiling, true_peak=False):
+        """Begins a limiter run: gains float32 [n_streams] (finite, >= 0), ceiling linear (finite, > 0), detector on the samples
+        or, with true_peak, on the 4x oversampled signal too. The run lasts until limit_flush() or reset()."""
+        gains = self._gains(gains)
+        self._call("limit_start", _vp(gains), ctypes.c_float(ceiling), AT3HIP_LIMIT_TRUE_PEAK if true_peak else 0)
+
+    def limit_ptr(self, in_ptr, n_in, out_ptr, flags, s16=False):
+        """Raw pointers and at3hip_loudness_limit (or, with s16, _limit_s16) flags; returns the outputs per stream."""
+        n = ctypes.c_int32()
+        self._call("limit_s16" if s16 else "limit", ctypes.c_void_p(in_ptr), int(n_in), ctypes.c_void_p(out_ptr), ctypes.byref(n), int(flags))
+        return n.value
+
+    def limit_flush_ptr(self, out_ptr, flags):
+        n = ctypes.c_int32()
+        self._call("limit_flush", ctypes.c_void_p(out_ptr), ctypes.byref(n), int(flags))
+        return n.value
+
+    def _limit_host(self, pcm, dtype):
+        pcm = self._host_pcm(pcm, dtype)
+        out = np.zeros(pcm.shape, np.float32)
+        n = self.limit_ptr(pcm.ctypes.data, pcm.shape[1], out.ctypes.data, 0, s16=dtype is np.int16)
+        return np.ascontiguousarray(out.reshape(-1)[: self.n_streams * n * self.channels].reshape(self.n_streams, n, self.channels))
+
+    def limit(self, pcm):
+        """pcm float32 [n_streams, n_in, channels] (host) -> the outputs this call completes, float32 [n_streams, n_out, channels]
+        (n_out <= n_in: the limiter holds back limit_delay() samples until limit_flush)"""
+        return self._limit_host(pcm, np.float32)
+
+    def limit_s16(self, pcm):
+        """limit() for int16 samples, taken as pcm / 32768 in float32 (at3hip_loudness_limit_s16); the output is float32"""
+        return self._limit_host(pcm, np.int16)
+
+    def limit_flush(self):
+        """the held-back outputs, float32 [n_streams, n_out, channels]; ends the run (limit_stats() stays readable)"""
+        out = np.zeros((self.n_streams, LIMIT_LOOKAHEAD + 72, self.channels), np.float32)
+        n = self.limit_flush_ptr(out.ctypes.data, 0)
+        return np.ascontiguousarray(out.reshape(-1)[: self.n_streams * n * self.channels].reshape(self.n_streams, n, self.channels))
+
+    def limit_stats(self):
+        """one LimitStats per stream for the run begun by the last limit_start (waits for queued work)"""
+        st = (LimitStats * self.n_streams)()
+        self._call("limit_stats", st)
+        return list(st)
+
+    def limit_device(self, pcm, out, asynchronous=False, ordered=True):
+        """Torch tensors on this meter's device: pcm float32 or int16 [n_streams, n_in, channels]; out float32, contiguous, with
+        room for n_streams * n_in * channels values, not overlapping pcm. Returns n_out: the outputs are out's first
+        n_streams * n_out * channels values as [n_streams, n_out, channels]. Ordering as process_device."""
+        import torch
+        assert pcm.dtype in (torch.float32, torch.int16) and pcm.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous()
+        assert pcm.ndim == 3 and pcm.shape[0] == self.n_streams and pcm.shape[2] == self.channels, tuple(pcm.shape)
+        assert out.device == pcm.device and out.numel() >= pcm.numel()
+        self._order_behind_torch(pcm.device, ordered)
+        return self.limit_ptr(pcm.data_ptr(), pcm.shape[1], out.data_ptr(), _device_flags(asynchronous), s16=pcm.dtype == torch.int16)
+
+    def limit_flush_device(self, out, asynchronous=False, ordered=True):
+        """limit_flush into a torch float32 tensor with room for n_streams * limit_delay() * channels values; returns n_out."""
+        import torch
+        assert out.dtype == torch.float32 and out.is_contiguous()
+        self._order_behind_torch(out.device, ordered)
+        return self.limit_flush_ptr(out.data_ptr(), AT3HIP_OUT_ON_DEVICE | (AT3HIP_ASYNC if asynchronous else 0))

@@ -1,5 +1,5 @@
 // The batched loudness and true-peak meter (include/at3hip_loudness.h): the k_hops, k_carry, k_true_peak and k_scale kernels,
-// the host gating and the C ABI.
+// the host gating and the C ABI. The look-ahead limiter on the same context is loudness_limit.hpp, included at the end.
 //
 // Kernel layout.
 //   k_hops       one lane per (stream, hop, channel) runs the definition's chain: 13 230 steps of two f64 biquads over the
@@ -490,6 +490,17 @@ struct at3hip_loudness : at3host::EngineBase {
     float* d_out = nullptr;                  // staging for at3hip_loudness_apply's host output, likewise
     long long t = 0;                         // samples received per stream since the start
     long long q_done = 0;                    // q below this have had their four outputs taken (true_peak)
+    // the limiter (loudness_limit.hpp); its buffers are allocated by the first at3hip_loudness_limit_start
+    uint32_t* d_lim_q[2] = {nullptr, nullptr};       // [S][2645 + max_in]: carried and new q, read / written alternately
+    float* d_lim_x[2] = {nullptr, nullptr};          // [S][292][C]: carried samples, likewise
+    float* d_lim_gain = nullptr;                     // [S]
+    unsigned long long* d_lim_stats = nullptr;       // [S][2]
+    float* d_lim_out = nullptr;                      // staging for host output, allocated by the first call that needs it
+    int lim_cur = 0;
+    bool lim_on = false;                             // between a start and its flush (or a reset)
+    uint32_t lim_flags = 0;
+    float lim_ceiling = 0.0f;
+    long long lim_t = 0, lim_qd = 0, lim_em = 0;     // samples received, q computed, outputs emitted per stream
 };
 
 namespace {
@@ -681,7 +692,8 @@ int at3hip_loudness_create(const at3hip_loudness_config* cfg, at3hip_loudness** 
 
 void at3hip_loudness_destroy(at3hip_loudness* l)
 {
-    if (l) at3host::destroy_engine(l, {l->d_carry[0], l->d_carry[1], l->d_z, l->d_peaks, l->d_hp, l->d_gain, l->d_in, l->d_in_s16, l->d_out});
+    if (l) at3host::destroy_engine(l, {l->d_carry[0], l->d_carry[1], l->d_z, l->d_peaks, l->d_hp, l->d_gain, l->d_in, l->d_in_s16, l->d_out,
+                                       l->d_lim_q[0], l->d_lim_q[1], l->d_lim_x[0], l->d_lim_x[1], l->d_lim_gain, l->d_lim_stats, l->d_lim_out});
 }
 
 const char* at3hip_loudness_last_error(const at3hip_loudness* l) { return at3host::engine_last_error(l); }
@@ -692,6 +704,7 @@ int at3hip_loudness_reset(at3hip_loudness* l)
     at3host::DeviceGuard guard(l->device);
     HIPCHK(l, guard.error());
     // the carry is read only for samples the counters say were received: the counters and the peaks are the state
+    l->lim_on = false;   // (a limiter run ends here; its statistics stay readable)
     return clear_state(l);
 }
 
@@ -761,3 +774,5 @@ int at3hip_loudness_sync(at3hip_loudness* l) { return at3host::engine_sync(l); }
 int at3hip_loudness_set_stream(at3hip_loudness* l, void* hip_stream) { return at3host::engine_set_stream(l, hip_stream); }
 
 }  // extern "C"
+
+#include "loudness_limit.hpp"

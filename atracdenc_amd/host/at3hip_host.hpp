@@ -1249,4 +1249,77 @@ private:
     TLoudnessMeter Meter;
 };
 
+// A PCM source times one constant and through the look-ahead limiter (at3hip_loudness_limit_*: the gain may exceed what the
+// peak allows, the limiter holds the ceiling). As TScaledSource it sits behind the converter and hands out exactly the
+// source's number of samples: the limiter's latency is taken up here, the held-back samples come with the flush at the
+// source's end.
+template <class TSrc>
+class TLimitedSource {
+public:
+    static constexpr int kChunk = 1 << 16;
+
+    TLimitedSource(TSrc& src, float gain, float ceiling, bool truePeak, int device)
+        : Src(src), Channels((int)src.GetChannelNum()), In((size_t)kChunk * src.GetChannelNum())
+    {
+        CheckLibraryVersion();
+        at3hip_loudness_config cfg{Channels, 1, kChunk, 1, 0, device};
+        const int rc = at3hip_loudness_create(&cfg, &L);
+        if (rc != AT3HIP_OK) throw std::runtime_error("at3hip_loudness_create failed (" + std::to_string(rc) + ")");
+        Check(at3hip_loudness_limit_start(L, &gain, ceiling, truePeak ? AT3HIP_LIMIT_TRUE_PEAK : 0u));
+        Out.resize((size_t)std::max<int32_t>(kChunk, at3hip_loudness_limit_delay(AT3HIP_LIMIT_TRUE_PEAK)) * Channels);
+    }
+    ~TLimitedSource()
+    {
+        if (L) at3hip_loudness_destroy(L);
+    }
+    TLimitedSource(const TLimitedSource&) = delete;
+    TLimitedSource& operator=(const TLimitedSource&) = delete;
+
+    size_t GetChannelNum() const { return Src.GetChannelNum(); }
+    size_t GetSampleRate() const { return Src.GetSampleRate(); }
+    uint64_t GetTotalSamples() const { return Src.GetTotalSamples(); }
+
+    size_t Read(float* dst, size_t frames)
+    {
+        const size_t C = (size_t)Channels;
+        while (Buf.size() / C - Pos < frames && !Done) {
+            Buf.erase(Buf.begin(), Buf.begin() + Pos * C);
+            Pos = 0;
+            const size_t n = Src.Read(In.data(), kChunk);
+            int32_t got = 0;
+            if (n) {
+                Check(at3hip_loudness_limit(L, In.data(), (int32_t)n, Out.data(), &got, 0));
+            } else {
+                Check(at3hip_loudness_limit_flush(L, Out.data(), &got, 0));
+                Done = true;
+            }
+            Buf.insert(Buf.end(), Out.begin(), Out.begin() + (size_t)got * C);
+        }
+        const size_t n = std::min(frames, Buf.size() / C - Pos);
+        std::copy(Buf.begin() + Pos * C, Buf.begin() + (Pos + n) * C, dst);
+        Pos += n;
+        return n;
+    }
+
+    // the run's statistics so far (all of it once Read has returned 0 or every sample)
+    at3hip_limit_stats Stats()
+    {
+        at3hip_limit_stats st{};
+        Check(at3hip_loudness_limit_stats(L, &st));
+        return st;
+    }
+
+private:
+    void Check(int rc)
+    {
+        if (rc != AT3HIP_OK) throw std::runtime_error(std::string("at3hip_loudness: ") + at3hip_loudness_last_error(L));
+    }
+    TSrc& Src;
+    int Channels;
+    at3hip_loudness* L = nullptr;
+    std::vector<float> In, Out, Buf;
+    size_t Pos = 0;
+    bool Done = false;
+};
+
 }  // namespace NAtracDEncHip

@@ -14,7 +14,9 @@
 //   --loudness LUFS [--peak dBFS] [--truepeak] (all three encoders): pass one meters the 44.1 kHz samples the encoder will see
 //             (after --resample) on the GPU (at3hip_loudness.h: BS.1770 integrated loudness, sample peak or with --truepeak the 4x
 //             oversampled peak), pass two encodes them times the one gain that reaches the target with the peak at or below
-//             --peak (default -1.0). Prints `loudness: I <x> LUFS, peak <y> dBFS, gain <z> dB` unless --nostdout, and for atrac3
+//             --peak (default -1.0); with --limit the gain is the one to the target alone and the look-ahead limiter of
+//             at3hip_loudness.h holds the ceiling (detector: the samples, or with --truepeak the 4x oversampled signal too), and
+//             one more line, `limiter: max reduction <x> dB, limited <y> %`, follows the encode. Prints `loudness: I <x> LUFS, peak <y> dBFS, gain <z> dB` unless --nostdout, and for atrac3
 //             `clipping: <n> blocks, <m> values` after the encode (at3hip_get_counters).
 //   at3hipenc --measure -i in.wav [--resample] [--truepeak]: prints the meter's result and writes nothing.
 //   --rate hz (every decoder): the decoded audio is converted to hz (at3hip_resample.h's list) on the GPU, clamped to [-1, 1] and
@@ -121,9 +123,9 @@ struct TRateInput {
     size_t Read(float* dst, size_t frames) { return Conv ? Conv->Read(dst, frames) : File.Read(dst, frames); }
 };
 
-// --loudness / --peak / --truepeak
+// --loudness / --peak / --truepeak / --limit
 struct TLevel {
-    bool On = false, TruePeak = false, NoStdOut = false;
+    bool On = false, TruePeak = false, NoStdOut = false, Limit = false;
     double Target = 0.0, Ceiling = -1.0;
 };
 
@@ -141,28 +143,42 @@ double db_of(double linear) { return 20.0 * std::log10(linear); }
 
 // The encoders' input with --loudness: pass one meters the file, pass two (this object's Read) hands the encoder the same
 // samples times the one gain that brings them to the target loudness with the peak at or below the ceiling (TScaledSource
-// behind the converter). Without the flag this is TRateInput.
+// behind the converter). With --limit the gain is the one to the target alone and the look-ahead limiter holds the ceiling
+// (TLimitedSource; the detector is the true-peak one with --truepeak). Without --loudness this is TRateInput.
 struct TEncodeInput {
     TRateInput Base;
     std::unique_ptr<TScaledSource<TRateInput>> Scaled;
+    std::unique_ptr<TLimitedSource<TRateInput>> Limited;
 
     TEncodeInput(const std::string& path, bool resample, int device, const TLevel& level) : Base(path, resample, device)
     {
         if (!level.On) return;
         const at3hip_loudness_result r = measure_input(path, resample, device, level.TruePeak);
-        const float g = TLoudnessMeter::Gain(r, level.Target, level.Ceiling);
+        // (--limit: a ceiling that never binds leaves the gain to the target alone)
+        const float g = TLoudnessMeter::Gain(r, level.Target, level.Limit ? 400.0 : level.Ceiling);
         if (!level.NoStdOut) {
             char line[160];
             snprintf(line, sizeof(line), "loudness: I %.2f LUFS, peak %.2f dBFS, gain %.2f dB", r.integrated,
                      db_of((double)TLoudnessMeter::Peak(r)), db_of((double)g));
             std::cout << line << std::endl;
         }
-        Scaled.reset(new TScaledSource<TRateInput>(Base, g, device));
+        if (level.Limit) Limited.reset(new TLimitedSource<TRateInput>(Base, g, (float)std::pow(10.0, level.Ceiling / 20.0), level.TruePeak, device));
+        else Scaled.reset(new TScaledSource<TRateInput>(Base, g, device));
+    }
+    // --limit: `limiter: max reduction <x> dB, limited <y> %` once the input has been read
+    void Report(const TLevel& level)
+    {
+        if (!Limited || level.NoStdOut) return;
+        const at3hip_limit_stats st = Limited->Stats();
+        char line[160];
+        snprintf(line, sizeof(line), "limiter: max reduction %.2f dB, limited %.2f %%", -db_of((double)st.min_sum / (double)AT3HIP_LIMIT_FULL),
+                 st.n_out ? 100.0 * (double)st.n_limited / (double)st.n_out : 0.0);
+        std::cout << line << std::endl;
     }
     size_t GetChannelNum() const { return Base.GetChannelNum(); }
     size_t GetSampleRate() const { return Base.GetSampleRate(); }
     uint64_t GetTotalSamples() const { return Base.GetTotalSamples(); }
-    size_t Read(float* dst, size_t frames) { return Scaled ? Scaled->Read(dst, frames) : Base.Read(dst, frames); }
+    size_t Read(float* dst, size_t frames) { return Limited ? Limited->Read(dst, frames) : Scaled ? Scaled->Read(dst, frames) : Base.Read(dst, frames); }
 };
 
 // `-d ... --rate <hz>`: the decoder's float output (44.1 kHz, already clamped) converted to another rate on the GPU
@@ -674,6 +690,7 @@ int encode(const TOptions& o)
         }
         encoder.Flush();
         codec.Report(encoder, o);
+        wav.Report(o.level);
         if (!o.noStdOut) std::cout << "\nDone" << std::endl;
     } catch (const std::exception& ex) {
         return fatal(ex.what());
@@ -692,7 +709,8 @@ static int usage()
                  "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--tones] [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
                  "                 (--tones: find sine waves on the GPU and write them as tonal blocks)\n"
                  "       (every encoder: --resample converts an input at 8 .. 192 kHz to 44.1 kHz first)\n"
-                 "       (every encoder: --loudness LUFS [--peak dBFS] [--truepeak] brings the input to a programme loudness first)\n"
+                 "       (every encoder: --loudness LUFS [--peak dBFS] [--truepeak] brings the input to a programme loudness first;\n"
+                 "        with --limit the gain reaches the target and a look-ahead limiter holds the peak)\n"
                  "       at3hipenc --measure -i in.wav [--resample] [--truepeak]   (prints loudness and peaks, writes nothing)\n"
                  "       at3hipenc -d -i in.aea -o out.wav [--nostdout] [--batch frames] [--device n]\n"
                  "       at3hipenc -d -i in.{oma|at3|wav} -o out.wav [--nostdout] [--batch frames] [--device n]   (ATRAC3 / ATRAC3plus, by content)\n"
@@ -732,6 +750,7 @@ int main(int argc, char** argv)
             o.level.Ceiling = atof(need("--peak"));
         }
         else if (a == "--truepeak") o.level.TruePeak = true;
+        else if (a == "--limit") o.level.Limit = true;
         else if (a == "--measure") o.measure = true;
         else if (a == "--rate") {   // a positive decimal number, else refused below as an unsupported rate
             const char* v = need("--rate");
@@ -751,7 +770,7 @@ int main(int argc, char** argv)
     }
     o.level.NoStdOut = o.noStdOut;
     if (o.measure) {   // prints the meter's result, writes nothing
-        if (o.decode || !o.codec.empty() || o.inFile.empty() || !o.outFile.empty() || o.level.On || o.peakGiven || o.rate) return usage();
+        if (o.decode || !o.codec.empty() || o.inFile.empty() || !o.outFile.empty() || o.level.On || o.level.Limit || o.peakGiven || o.rate) return usage();
         try {
             const at3hip_loudness_result r = measure_input(o.inFile, o.resample, o.device, o.level.TruePeak);
             char line[256];
@@ -766,7 +785,7 @@ int main(int argc, char** argv)
         return 0;
     }
     if (o.decode) {
-        if (!o.codec.empty() || o.inFile.empty() || o.outFile.empty() || o.level.On || o.peakGiven || o.level.TruePeak) return usage();
+        if (!o.codec.empty() || o.inFile.empty() || o.outFile.empty() || o.level.On || o.level.Limit || o.peakGiven || o.level.TruePeak) return usage();
         TAt3Input at3;
         const EInput kind = probe_input(o.inFile, at3);
         if (kind == EInput::REFUSED) return 1;
@@ -783,7 +802,7 @@ int main(int argc, char** argv)
         }
     }
     if ((o.codec != "atrac3" && o.codec != "atrac1" && o.codec != "atrac3plus") || o.inFile.empty() || o.outFile.empty() || o.rate) return usage();
-    if (!o.level.On && (o.peakGiven || o.level.TruePeak)) return usage();   // --peak and --truepeak belong to --loudness (or --measure)
+    if (!o.level.On && (o.peakGiven || o.level.TruePeak || o.level.Limit)) return usage();   // --peak, --truepeak and --limit belong to --loudness (--truepeak also to --measure)
     if (o.tones && o.codec != "atrac3plus") return usage();   // the tone analysis is ATRAC3plus'
     if (o.codec == "atrac3plus") return encode<TAtrac3PlusEncode>(o);
     if (o.codec == "atrac1") return encode<TAtrac1Encode>(o);

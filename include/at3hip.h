@@ -411,6 +411,9 @@ int at3hip_decoder_set_stream(at3hip_decoder* dec, void* hip_stream);
  *        at3phip_tonal_block (at3phip.h), detected by the symbol
  *        and, added later under the same number, the ATRAC3plus tone analysis (at3phip.h, FINDING TONES): at3phip_analyse_tones,
  *        at3phip_encode_frames_tonal, at3phip_encode_frames_tonal_short, at3phip_host_tone_find_tables; each detected by its symbol
+ *        and, added later under the same number, the look-ahead limiter on the meter's context (at3hip_loudness.h):
+ *        at3hip_loudness_limit_start(), at3hip_loudness_limit(), at3hip_loudness_limit_s16(), at3hip_loudness_limit_flush(),
+ *        at3hip_loudness_limit_stats(), at3hip_loudness_limit_delay() (detected by the symbol at3hip_loudness_limit_start)
  * A host layer compiled against this header checks at3hip_version() >= AT3HIP_VERSION before it relies on them
  * (atracdenc_amd/host/at3hip_host.hpp and the ctypes stub do). */
 #define AT3HIP_VERSION_MAJOR 1

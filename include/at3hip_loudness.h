@@ -42,6 +42,41 @@
  *     peak = the larger channel's true peak if it was measured, else the larger sample peak; g = 1.0f when integrated is
  *     -HUGE_VAL or peak is 0. Applying it is one float multiply per sample.
  *
+ * The look-ahead limiter (at3hip_loudness_limit_*). A second definition of this project's own, restated by tests/host/limiter_cpu.c
+ * and pinned to the GPU bit for bit. It stands between the gain and the encoder: the gain alone (at3hip_loudness_apply) leaves
+ * peaks above the ceiling, one constant gain under the ceiling lets one click set the level of a whole file. 44.1 kHz, 1 or 2
+ * channels, every stream of a call takes the same n_in. A stream has a gain g (finite, >= 0) and all streams one ceiling c
+ * (finite, > 0), floats, fixed from at3hip_loudness_limit_start until at3hip_loudness_limit_flush. Every output sample depends on
+ * a bounded window of the input and everything that depends on an order of evaluation is integer arithmetic, so the result does
+ * not depend on how the work is cut into tiles or calls. x_c[n] is sample n of channel c of the T samples between start and
+ * flush; x_c[n] = +0.0f for n < 0 and n >= T.
+ *   1 Detector. m[n] = the largest magnitude over the channels' |x_c[n]| and, in true-peak mode (AT3HIP_LIMIT_TRUE_PEAK), also
+ *     over the four converter outputs u_c[4n + p], p = 0 .. 3, of the 44100 -> 176400 converter of at3hip_resample.h:
+ *     acc = +0.0f; for k = 0 .. 143 ascending: acc = fmaf(h[p][k], x_c[n + k - 71], acc) (the table and chain of the meter's true
+ *     peak). Magnitudes are compared as the float's bits with the sign cleared, so a NaN is the largest.
+ *   2 Required gain. e = (double)g * (double)m[n] (exact); r[n] = e > (double)c ? (double)c / e : 1.0 (an IEEE double division);
+ *     q[n] = (uint32)(r[n] * 2^30) truncated, 0 <= q <= 2^30. q[n] = 2^30 for n < 0 and for n >= T (decided here: past the flush
+ *     the detector is not evaluated, although the converter's ringing of the last samples reaches there).
+ *   3 Look-ahead and hold. w[n] = min(q[n - H .. n + A]), A = AT3HIP_LIMIT_LOOKAHEAD = 220 samples (5 ms), H = AT3HIP_LIMIT_HOLD =
+ *     2205 samples (50 ms); w is defined for every integer n through the extension of q.
+ *   4 Smoothing. S[n] = w[n - A] + ... + w[n], an exact 64-bit integer sum of A + 1 = 221 terms. Each w[j] of it covers q[n], so
+ *     S[n] / AT3HIP_LIMIT_FULL <= r[n], AT3HIP_LIMIT_FULL = 221 * 2^30.
+ *   5 Output. s = (double)S[n] / (double)AT3HIP_LIMIT_FULL (an IEEE double division) converted to float rounding toward zero;
+ *     t = (x_c[n] * g) * s, two float multiplies, the first one at3hip_loudness_apply's; y_c[n] = t > c ? c : (t < -c ? -c : t)
+ *     (a NaN t passes). Where S[n] = AT3HIP_LIMIT_FULL, s is 1.0f and y is apply's output bit for bit unless that exceeds c.
+ *   6 Streaming. Latency D = A samples, in true-peak mode A + 72 (at3hip_loudness_limit_delay): after T' samples were received a
+ *     stream has emitted max(0, T' - D) outputs; at3hip_loudness_limit_flush emits the rest, to T in all, and ends the run. Any
+ *     split of the input into calls, calls shorter than the filter and empty calls included, gives the same samples.
+ *   7 Statistics per stream since the start: min S[n] over the outputs emitted (AT3HIP_LIMIT_FULL when there is none) and the
+ *     number of outputs with S[n] < AT3HIP_LIMIT_FULL. 20 log10(min S / AT3HIP_LIMIT_FULL) is the largest reduction in dB.
+ *   8 Outside the float domain. Any float sample is accepted. A NaN sample is m[n] for its n (in true-peak mode for the 144 n
+ *     whose filter reads it), e is NaN, the comparison fails and r = 1: the NaN does not limit and passes through step 5 as
+ *     NaN. An infinite sample (with g > 0) gives e = inf and q = 0 with the sample detector: S reaches 0 around it, t = inf * 0 =
+ *     NaN at the sample itself and +-0 around it. In true-peak mode the filter turns an infinity into infinities or (inf - inf)
+ *     NaNs at the 144 n around it: q = 0 where the largest magnitude is an infinity, r = 1 where it is a NaN. With g = 0,
+ *     e = 0 * inf = NaN and r = 1. Finite samples whose product with g overflows give e's exact double, q = 0 or close to it,
+ *     and t = +-inf * s, clamped to +-c unless s is 0 (then NaN). No stream affects another.
+ *
  * The meter is part of ABI 1.6 (see at3hip.h): a host that needs it looks for the symbol at3hip_loudness_create.
  */
 #ifndef AT3HIP_LOUDNESS_H
@@ -133,6 +168,42 @@ int at3hip_loudness_apply(at3hip_loudness* l, const float* in, int32_t n_in, con
  * at3hip_loudness_apply from host memory. */
 int at3hip_loudness_process_s16(at3hip_loudness* l, const int16_t* in, int32_t n_in, uint32_t flags);
 int at3hip_loudness_apply_s16(at3hip_loudness* l, const int16_t* in, int32_t n_in, const float* gains, float* out, uint32_t flags);
+
+/* THE LIMITER (the definition above, "The look-ahead limiter"). New calls on the meter's context; they touch no meter state and
+ * the meter's calls touch no limiter state, except that at3hip_loudness_reset also ends a limiter run. Their tables and buffers
+ * are allocated by the first at3hip_loudness_limit_start. Added under ABI 1.6: a host looks for the symbol
+ * at3hip_loudness_limit_start. Calls are queued behind earlier calls on the meter's stream and honour at3hip_loudness_set_stream. */
+#define AT3HIP_LIMIT_LOOKAHEAD 220              /* A */
+#define AT3HIP_LIMIT_HOLD 2205                  /* H */
+#define AT3HIP_LIMIT_FULL 237296943104LL        /* (A + 1) * 2^30: S of an unlimited sample */
+#define AT3HIP_LIMIT_TRUE_PEAK 1u               /* flag of at3hip_loudness_limit_start / _limit_delay: the 4x oversampled detector */
+
+typedef struct at3hip_limit_stats {
+    int64_t min_sum;     /* min S[n] over the outputs emitted; AT3HIP_LIMIT_FULL when nothing was limited */
+    int64_t n_limited;   /* outputs with S[n] < AT3HIP_LIMIT_FULL */
+    int64_t n_out;       /* outputs emitted */
+} at3hip_limit_stats;
+
+/* The latency D in samples for these start flags (host only, no context). */
+int32_t at3hip_loudness_limit_delay(uint32_t flags);
+/* Begins a run for every stream: gains[n_streams] (host memory, read before the call returns; each finite and >= 0), ceiling
+ * finite and > 0, flags 0 or AT3HIP_LIMIT_TRUE_PEAK. AT3HIP_EINVAL for anything else and while a run is open (between a start
+ * and its flush or at3hip_loudness_reset). Clears the statistics. */
+int at3hip_loudness_limit_start(at3hip_loudness* l, const float* gains, float ceiling, uint32_t flags);
+/* in [n_streams][n_in][channels] float32, 0 <= n_in <= max_in; out [n_streams][*n_out][channels] float32, where *n_out =
+ * max(0, T' - D) - max(0, T' - n_in - D) <= n_in is set before the call returns (T' = samples received with this call): an out of
+ * n_in samples per stream always suffices. flags: AT3HIP_PCM_ON_DEVICE, AT3HIP_OUT_ON_DEVICE, AT3HIP_ASYNC as for
+ * at3hip_loudness_apply. out cannot be in: an output sample lies D samples behind its input sample, so the kernels would
+ * overwrite input other workgroups still read; device buffers of one call that overlap are AT3HIP_EINVAL. */
+int at3hip_loudness_limit(at3hip_loudness* l, const float* in, int32_t n_in, float* out, int32_t* n_out, uint32_t flags);
+/* The same for 16-bit PCM, a sample s taken as (float)s * 0x1p-15f in the kernels' loads (the rule of at3hip_encode_s16); the
+ * output is float32. Calls of both kinds may alternate in one run. */
+int at3hip_loudness_limit_s16(at3hip_loudness* l, const int16_t* in, int32_t n_in, float* out, int32_t* n_out, uint32_t flags);
+/* Emits the last *n_out = min(T, D) outputs of every stream, out [n_streams][*n_out][channels] (room for D samples per stream
+ * suffices), and ends the run; the statistics stay readable until the next start. flags: AT3HIP_OUT_ON_DEVICE, AT3HIP_ASYNC. */
+int at3hip_loudness_limit_flush(at3hip_loudness* l, float* out, int32_t* n_out, uint32_t flags);
+/* Waits for the queued calls and fills stats[n_streams] for the run begun by the last start. */
+int at3hip_loudness_limit_stats(at3hip_loudness* l, at3hip_limit_stats* stats);
 
 /* The gating of the definition on the host (no GPU needed): z [n_hops][channels] double -> integrated, momentary_max,
  * short_term_max, n_hops and n_blocks_kept of *result; its other fields are left as they are. */
