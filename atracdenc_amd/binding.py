@@ -190,7 +190,7 @@ PROTOTYPES = {
     "at3phip_encode_frames_tonal": (_RC, [_VP, _VP, _I32, _VP, _U32]), "at3phip_encode_frames_tonal_short": (_RC, [_VP, _VP, _I32, _VP, _U32]),
     "at3phip_get_timings": (_RC, [_VP, _F32P, _F32P]), "at3phip_get_write_timing": (_RC, [_VP, _F32P]),
     "at3phip_host_tables": (_RC, [_VP, _SZ]), "at3phip_host_write_tables": (_RC, [_VP, _SZ]),
-    "at3phip_host_tone_find_tables": (_RC, [_VP, _SZ]),
+    "at3phip_host_tone_find_tables": (_RC, [_VP, _SZ]), "at3phip_host_tone_gates": (_RC, [_VP, _I32, _I32, _VP]),
     # include/at3phip.h: the ATRAC3plus decoder
     "at3phip_decoder_create": (_RC, [_P(At3pDecoderConfig), _P(_VP)]), "at3phip_decoder_destroy": (None, [_VP]),
     "at3phip_decoder_last_error": (_STR, [_VP]), "at3phip_decoder_reset": (_RC, [_VP]), "at3phip_decoder_sync": (_RC, [_VP]),
@@ -781,6 +781,22 @@ def at3p_host_tone_find_tables(lib_path=None):
     return _host_tables(lib_path, "at3phip_host_tone_find_tables", np.zeros((), AT3P_TONE_FIND_TABLES_DTYPE))
 
 
+AT3PHIP_TONES_GATED = 32   # flag of the tonal calls: the analysis with envelope points (include/at3phip.h, GATES)
+
+
+def at3p_host_tone_gates(bands, lib_path=None):
+    """at3phip_host_tone_gates (no GPU): bands float32 [F, C, 16, 128] of one stream -> the frames' gates uint8 [F, C, 16]
+    (0: none, 1..31: onset at that cell, 0x80 | p: offset with last active cell p). A library without the symbol predates
+    AT3PHIP_TONES_GATED."""
+    bands = np.ascontiguousarray(bands, dtype=np.float32)
+    assert bands.ndim == 4 and bands.shape[1] in (1, 2) and bands.shape[2:] == (16, 128), bands.shape
+    out = np.zeros(bands.shape[:3], np.uint8)
+    rc = _need(load_library(lib_path), "at3phip_host_tone_gates")(_vp(bands), bands.shape[0], bands.shape[1], _vp(out))
+    if rc != 0:
+        raise At3HipError(f"at3phip_host_tone_gates failed ({rc})")
+    return out
+
+
 class At3pHip(_Context):
     """ATRAC3plus front end (include/at3phip.h): PQF analysis and windowed MDCT-256 x 16 for n_streams streams."""
 
@@ -887,12 +903,12 @@ class At3pHip(_Context):
             self.write_frames_tonal_ptr(specs.ctypes.data, nf, flp, tonal.ctypes.data, out.ctypes.data, 0)
         return out
 
-    def _encode_frames_host(self, pcm, dtype, raw):
+    def _encode_frames_host(self, pcm, dtype, raw, flags=0):
         pcm = np.ascontiguousarray(pcm, dtype=dtype)
         assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (2048, self.channels), pcm.shape
         nf = pcm.shape[1]
         out = np.zeros((self.n_streams, nf, 2048), np.uint8)
-        raw(pcm.ctypes.data, nf, out.ctypes.data, 0)
+        raw(pcm.ctypes.data, nf, out.ctypes.data, flags)
         return out
 
     def encode_frames(self, pcm):
@@ -905,41 +921,43 @@ class At3pHip(_Context):
         filter bank. Calls of both kinds may alternate."""
         return self._encode_frames_host(pcm, np.int16, self.encode_frames_s16_ptr)
 
-    def analyse_tones(self, bands):
+    def analyse_tones(self, bands, gated=False):
         """bands float32 [S, F, C, 16, 128] (what pqf() returns) -> (blocks of AT3P_TONAL_BLOCK_DTYPE [S, F], residual
         [S, F, C, 16, 128]): at3phip_analyse_tones, slot f holding the block of (frame f-1, frame f) and the residual of frame
-        f-1; the last frame and block carry over to the next call."""
+        f-1; the last frame and block carry over to the next call. gated: AT3PHIP_TONES_GATED, onsets and offsets become the
+        records' envelope points (a stream stays with one mode between resets)."""
         bands = np.ascontiguousarray(bands, dtype=np.float32)
         assert bands.ndim == 5 and bands.shape[0] == self.n_streams and bands.shape[2:] == (self.channels, 16, 128), bands.shape
         nf = bands.shape[1]
         blocks = np.zeros((self.n_streams, nf), AT3P_TONAL_BLOCK_DTYPE)
         resid = np.zeros_like(bands)
-        self.analyse_tones_ptr(bands.ctypes.data, nf, blocks.ctypes.data, resid.ctypes.data, 0)
+        self.analyse_tones_ptr(bands.ctypes.data, nf, blocks.ctypes.data, resid.ctypes.data, AT3PHIP_TONES_GATED if gated else 0)
         return blocks, resid
 
-    def analyse_tones_device(self, bands_ptr, n_frames, residual_ptr):
+    def analyse_tones_device(self, bands_ptr, n_frames, residual_ptr, gated=False):
         """Device-resident subband samples and residual (raw pointers) -> the blocks [S, F] (host memory). The call waits; whatever
         produces the samples must be complete before it (see encode_frames_device)."""
         blocks = np.zeros((self.n_streams, int(n_frames)), AT3P_TONAL_BLOCK_DTYPE)
-        self.analyse_tones_ptr(bands_ptr, n_frames, blocks.ctypes.data, residual_ptr, _device_flags(False))
+        self.analyse_tones_ptr(bands_ptr, n_frames, blocks.ctypes.data, residual_ptr, _device_flags(False) | (AT3PHIP_TONES_GATED if gated else 0))
         return blocks
 
-    def encode_frames_tonal(self, pcm):
+    def encode_frames_tonal(self, pcm, gated=False):
         """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, 2048] with the tone analysis (at3phip_encode_frames_tonal): frame f
-        of the stream holds the residual of input frame f-1 and the block of frame f-2, so one trailing frame of silence flushes."""
-        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr)
+        of the stream holds the residual of input frame f-1 and the block of frame f-2, so one trailing frame of silence flushes.
+        gated: AT3PHIP_TONES_GATED, as in analyse_tones()."""
+        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr, AT3PHIP_TONES_GATED if gated else 0)
 
-    def encode_frames_tonal_s16(self, pcm):
+    def encode_frames_tonal_s16(self, pcm, gated=False):
         """The same for int16 PCM (at3phip_encode_frames_tonal_short): the frames of encode_frames_tonal() on pcm / 32768."""
-        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr)
+        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr, AT3PHIP_TONES_GATED if gated else 0)
 
-    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
+    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False):
         """Device-resident float32 PCM / frames; ordering and what stays untouched until sync() as in encode_frames_device."""
-        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous))
+        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | (AT3PHIP_TONES_GATED if gated else 0))
 
-    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
+    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False):
         """Device-resident int16 PCM / frames, as encode_frames_tonal_device."""
-        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous))
+        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | (AT3PHIP_TONES_GATED if gated else 0))
 
     def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
         """asynchronous=True only queues the call (AT3HIP_ASYNC): sync() before the frames are read, and both buffers stay

@@ -26,7 +26,7 @@ static_assert(sizeof(at3phip_tonal_block) == sizeof(TonalBlock) && offsetof(at3p
               "at3phip.h documents the tonal record's layout");
 static_assert(sizeof(ToneFindTables) == AT3PHIP_TONE_FIND_TABLES_BYTES, "at3phip.h documents the tone analysis' table block size");
 static_assert(AT3PHIP_TONE_MAX_BAND_WAVES == kToneBandWaves && AT3PHIP_TONE_FINE_SPAN == kToneSpan && AT3PHIP_TONE_PEAK_RATIO == 16.0 &&
-                  AT3PHIP_TONE_MIN_AMP == 8.0,
+                  AT3PHIP_TONE_MIN_AMP == 8.0 && AT3PHIP_TONE_GATE_MIN == kToneGateMin && AT3PHIP_TONE_GATE_RATIO == kToneGateRatio,
               "at3phip.h names the constants of at3p_gha.hpp");
 
 struct at3phip_ctx : at3host::EngineBase {   // (no at3phip_set_stream: stream == own_stream)
@@ -50,7 +50,7 @@ struct at3phip_ctx : at3host::EngineBase {   // (no at3phip_set_stream: stream =
     TonalBlock* d_tone_writer[2] = {nullptr, nullptr};   // [S][F] each: the writer's records, double-buffered like the spectra
     float* d_tone_resid = nullptr;               // [S][F][nch][16][128]
     float* d_tone_prev = nullptr;                // state: the last frame's subband samples [S][nch][16][128]
-    TonalBlock* d_tone_last = nullptr;           // state: the last block [S]
+    TonalBlock* d_tone_last = nullptr;           // state: the last block [S], then the block before it [S] (its points: GATES)
     // at3phip_encode_frames: the frame writer only needs the spectra of ITS call, so it runs on a stream of its own behind
     // an event and the next call's filter bank and transform overlap it; the spectra in between are double-buffered
     hipStream_t write_stream = nullptr;
@@ -73,7 +73,7 @@ int reset_state(at3phip_ctx* c)
     HIPCHK(c, hipMemsetAsync(c->d_mdct_hist, 0, S * C * 2048 * sizeof(float), c->stream));
     if (c->d_tone_last) {   // the tone analysis has been used: a zero frame before the stream, no block
         HIPCHK(c, hipMemsetAsync(c->d_tone_prev, 0, S * C * 2048 * sizeof(float), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_tone_last, 0, S * sizeof(TonalBlock), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_tone_last, 0, 2 * S * sizeof(TonalBlock), c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return AT3HIP_OK;
@@ -204,15 +204,16 @@ int ensure_tones(at3phip_ctx* c)
         if (!w && (rc = dev_alloc(c, &w, S * F)) != AT3HIP_OK) return rc;
     if (!c->d_tone_resid && (rc = dev_alloc(c, &c->d_tone_resid, S * F * C * 2048)) != AT3HIP_OK) return rc;
     if (!c->d_tone_prev && (rc = dev_alloc(c, &c->d_tone_prev, S * C * 2048)) != AT3HIP_OK) return rc;
-    if (!c->d_tone_last && (rc = dev_alloc(c, &c->d_tone_last, S)) != AT3HIP_OK) return rc;
+    if (!c->d_tone_last && (rc = dev_alloc(c, &c->d_tone_last, 2 * S)) != AT3HIP_OK) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_tone_prev, 0, S * C * 2048 * sizeof(float), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_tone_last, 0, S * sizeof(TonalBlock), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_tone_last, 0, 2 * S * sizeof(TonalBlock), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return at3host::make_device_tables(c, &c->d_tone_tables, [](ToneFindTables* t) { build_tone_find_tables(t); return true; });
 }
 
 // Steps 1-8 on d_bands: the blocks into d_tone_blocks, the residuals into d_resid, the writer's records (or none) into d_writer.
-int launch_tones(at3phip_ctx* c, const float* d_bands, int n_frames, float* d_resid, TonalBlock* d_writer)
+// gated: AT3PHIP_TONES_GATED (steps G1-G5).
+int launch_tones(at3phip_ctx* c, const float* d_bands, int n_frames, float* d_resid, TonalBlock* d_writer, bool gated)
 {
     const unsigned S = (unsigned)c->cfg.n_streams, C = (unsigned)c->cfg.channels, F = (unsigned)n_frames;
     ToneParams tp;
@@ -226,11 +227,16 @@ int launch_tones(at3phip_ctx* c, const float* d_bands, int n_frames, float* d_re
     tp.resid = d_resid;
     tp.n_frames = n_frames;
     tp.nch = (int)C;
-    hipLaunchKernelGGL(k_at3p_tone_find, dim3(F * 4, S * C), dim3(256), 0, c->stream, tp);   // (slot, four subbands) x (stream, channel)
+    tp.n_streams = (int)S;
+    tp.gated = gated ? 1 : 0;
+    // (slot, four subbands) x (stream, channel)
+    if (gated) hipLaunchKernelGGL(k_at3p_tone_find<true>, dim3(F * 4, S * C), dim3(256), 0, c->stream, tp);
+    else hipLaunchKernelGGL(k_at3p_tone_find<false>, dim3(F * 4, S * C), dim3(256), 0, c->stream, tp);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_at3p_tone_select, dim3(F, S), dim3(128), 0, c->stream, tp);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_at3p_tone_sub, dim3(F, S * C), dim3(256), 0, c->stream, tp);
+    if (gated) hipLaunchKernelGGL(k_at3p_tone_sub<true>, dim3(F, S * C), dim3(256), 0, c->stream, tp);
+    else hipLaunchKernelGGL(k_at3p_tone_sub<false>, dim3(F, S * C), dim3(256), 0, c->stream, tp);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_at3p_tone_state, dim3(S), dim3(256), 0, c->stream, tp, c->d_tone_prev);
     HIPCHK(c, hipGetLastError());
@@ -489,7 +495,7 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     if (timed) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     const float* d_mdct_in = c->d_bands;
     if constexpr (kTones) {   // (its time counts as the transform's)
-        rc = launch_tones(c, c->d_bands, n_frames, c->d_tone_resid, c->d_tone_writer[par]);
+        rc = launch_tones(c, c->d_bands, n_frames, c->d_tone_resid, c->d_tone_writer[par], (flags & AT3PHIP_TONES_GATED) != 0);
         if (rc != AT3HIP_OK) return rc;
         d_mdct_in = c->d_tone_resid;
     }
@@ -554,7 +560,7 @@ int at3phip_analyse_tones(at3phip_ctx* c, const float* bands, int32_t n_frames, 
     const bool out_dev = (flags & AT3HIP_OUT_ON_DEVICE) != 0;
     float* d_resid = (out_dev && residual) ? residual : c->d_tone_resid;
     c->ev_from_encode = false;
-    rc = launch_tones(c, d_bands, n_frames, d_resid, nullptr);
+    rc = launch_tones(c, d_bands, n_frames, d_resid, nullptr, (flags & AT3PHIP_TONES_GATED) != 0);
     if (rc != AT3HIP_OK) return rc;
     if (blocks) HIPCHK(c, hipMemcpyAsync(blocks, c->d_tone_blocks, items * sizeof(TonalBlock), hipMemcpyDeviceToHost, c->stream));
     if (residual && !out_dev) HIPCHK(c, hipMemcpyAsync(residual, c->d_tone_resid, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -566,6 +572,50 @@ int at3phip_host_tone_find_tables(void* dst, size_t bytes)
 {
     if (!dst || bytes != sizeof(ToneFindTables)) return AT3HIP_EINVAL;
     build_tone_find_tables((ToneFindTables*)dst);
+    return AT3HIP_OK;
+}
+
+// G1 of include/at3phip.h on the host: k_at3p_tone_find's gate, operation for operation (this file is compiled without contraction)
+int at3phip_host_tone_gates(const float* bands, int32_t n_frames, int32_t channels, uint8_t* out)
+{
+    if (!bands || !out || n_frames < 0 || channels < 1 || channels > 2) return AT3HIP_EINVAL;
+    for (size_t i = 0; i < (size_t)n_frames * channels * 16; ++i) {
+        const float* x = bands + i * 128;
+        double P[33], e[32];
+        P[0] = 0.0;
+        for (int j = 0; j < 32; ++j) {
+            float v = x[4 * j] * x[4 * j];
+            v = v + x[4 * j + 1] * x[4 * j + 1];
+            v = v + x[4 * j + 2] * x[4 * j + 2];
+            v = v + x[4 * j + 3] * x[4 * j + 3];
+            e[j] = (double)v;
+            P[j + 1] = P[j] + e[j];
+        }
+        int bs = 0;
+        double bd = 0.0, before = 0.0, after = 0.0;
+        for (int s = kToneGateMin; s <= 32 - kToneGateMin; ++s) {
+            const double b = P[s] / (double)s, a = (P[32] - P[s]) / (double)(32 - s);
+            const double d = fabs(a - b);
+            if (bs == 0 || d > bd) {
+                bs = s;
+                bd = d;
+                before = b;
+                after = a;
+            }
+        }
+        // the loud side holds at least MIN loud cells next to the split: each over R times the quiet side's mean, and not zero
+        uint8_t gate = 0;
+        if (after >= kToneGateRatio * before && after > 0.0) {
+            bool ok = true;
+            for (int j = bs; j < bs + kToneGateMin; ++j) ok = ok && e[j] >= kToneGateRatio * before && e[j] > 0.0;
+            if (ok) gate = (uint8_t)bs;
+        } else if (before >= kToneGateRatio * after && before > 0.0) {
+            bool ok = true;
+            for (int j = bs - kToneGateMin; j < bs; ++j) ok = ok && e[j] >= kToneGateRatio * after && e[j] > 0.0;
+            if (ok) gate = (uint8_t)(0x80 | (bs - 1));
+        }
+        out[i] = gate;
+    }
     return AT3HIP_OK;
 }
 

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -667,9 +668,11 @@ public:
 // Every sum runs in the header's order; compile without floating-point contraction (no FMA), like the kernels.
 // The same analysis is written out in atracdenc_amd/csrc/at3p_gha.hpp (the kernels) and tests/host/at3p_gha_cpu.c (the C
 // restatement): the three change together.
+// gated: the analysis with AT3PHIP_TONES_GATED (the header's GATES, G1-G5; tests/host/at3p_gha_gate_cpu.c): onsets and offsets
+// become the blocks' envelope points.
 class TAt3PToneAnalyser : public IAt3PGhaProcessor {
 public:
-    explicit TAt3PToneAnalyser(int channels) : Channels(channels)
+    explicit TAt3PToneAnalyser(int channels, bool gated = false) : Channels(channels), Gated(gated)
     {
         if (at3phip_host_tone_find_tables(&T, sizeof(T)) != AT3HIP_OK) throw std::runtime_error("at3phip_host_tone_find_tables failed");
     }
@@ -678,23 +681,44 @@ public:
         const float* cur[2] = {b1[0], b2[0]};
         float* prev[2] = {w1, w2};
         TWave w[2 * 16 * AT3PHIP_TONE_MAX_BAND_WAVES];
-        int nw = 0;
+        int nw = 0, gate[2][16] = {};
         for (int ch = 0; ch < Channels; ++ch)
             for (int sb = 0; sb < 16; ++sb) {
                 float x[256];
                 std::copy(prev[ch] + sb * 128, prev[ch] + sb * 128 + 128, x);
                 std::copy(cur[ch] + sb * 128, cur[ch] + sb * 128 + 128, x + 128);
-                const int got = FindBand(x, w + nw);
+                int lo = 0, hi = 63;
+                bool event = false;
+                if (Gated) {   // G1 for both frames, G3
+                    const int g0 = Gate(x), g1 = Gate(x + 128);
+                    gate[ch][sb] = g1;
+                    if (g0 | g1) {
+                        const TEnv e = CurrEnv(GateBand(g1), GateBand(g0));
+                        event = true;
+                        lo = e.Hs ? e.S : 0;
+                        hi = e.He ? e.E : 63;
+                    }
+                }
+                const int got = FindBand(x, w + nw, event, lo, hi);
                 for (int i = 0; i < got; ++i) {
                     w[nw + i].Ch = ch;
                     w[nw + i].Sb = sb;
                 }
                 nw += got;
             }
-        const at3phip_tonal_block before = Block;
+        const at3phip_tonal_block older = Older, before = Block;
         Select(w, nw);
+        for (int ch = 0; ch < Channels; ++ch)   // G2: the second frame's event is the block's point pair, wave or no wave
+            for (int sb = 0; sb < 16; ++sb) {
+                const int g = gate[ch][sb];
+                if (!g) continue;
+                if (g < 0x80) Block.band[ch][sb].start = (uint8_t)(g + 1);
+                else Block.band[ch][sb].stop = (uint8_t)((g & 31) + 1);
+                Block.num_tone_bands = (uint8_t)std::max<int>(Block.num_tone_bands, sb + 1);
+            }
         for (int ch = 0; ch < Channels; ++ch)
-            for (int sb = 0; sb < 16; ++sb) Subtract(before, Block, ch, sb, prev[ch] + sb * 128);
+            for (int sb = 0; sb < 16; ++sb) Subtract(older, before, Block, ch, sb, prev[ch] + sb * 128);
+        Older = before;
         return &Block;
     }
 
@@ -712,6 +736,64 @@ private:
     struct TCpx {
         float r, i;
     };
+    // an envelope as ff_atrac3p_generate_tones keeps it: has_start_point, start_pos, has_stop_point, stop_pos
+    struct TEnv {
+        int Hs, S, He, E;
+    };
+    // curr_env of a block's band (nx: its start and stop, the record's "+1" convention) after the block before's (nw), as
+    // ff_atrac3p_generate_tones reconstructs it (decp_curr_env in the kernels)
+    static TEnv CurrEnv(at3phip_tonal_band nx, at3phip_tonal_band nw)
+    {
+        const int nxStart = (int)nx.start - 1, nxStop = nx.stop ? (int)nx.stop - 1 : 32;
+        TEnv r;
+        if (nx.start && nxStart < nxStop) r.Hs = 1, r.S = nxStart + 32;
+        else if (nw.start) r.Hs = 1, r.S = (int)nw.start - 1;
+        else r.Hs = 0, r.S = 0;
+        if (nw.stop && (int)nw.stop - 1 >= r.S) r.He = 1, r.E = (int)nw.stop - 1;
+        else if (nx.stop) r.He = 1, r.E = nxStop + 32;
+        else r.He = 0, r.E = 64;
+        return r;
+    }
+    static at3phip_tonal_band GateBand(int g)
+    {
+        at3phip_tonal_band b{};
+        if (g > 0 && g < 0x80) b.start = (uint8_t)(g + 1);
+        if (g >= 0x80) b.stop = (uint8_t)((g & 31) + 1);
+        return b;
+    }
+    // G1: one frame's gate for one subband
+    static int Gate(const float* x)
+    {
+        double P[33], e[32];
+        P[0] = 0.0;
+        for (int j = 0; j < 32; ++j) {
+            float v = x[4 * j] * x[4 * j];
+            v = v + x[4 * j + 1] * x[4 * j + 1];
+            v = v + x[4 * j + 2] * x[4 * j + 2];
+            v = v + x[4 * j + 3] * x[4 * j + 3];
+            e[j] = (double)v;
+            P[j + 1] = P[j] + e[j];
+        }
+        int bs = 0;
+        double bd = 0, before = 0, after = 0;
+        for (int s = AT3PHIP_TONE_GATE_MIN; s <= 32 - AT3PHIP_TONE_GATE_MIN; ++s) {
+            const double b = P[s] / (double)s, a = (P[32] - P[s]) / (double)(32 - s);
+            const double d = std::fabs(a - b);
+            if (bs == 0 || d > bd) bs = s, bd = d, before = b, after = a;
+        }
+        // the loud side holds at least MIN loud cells next to the split: each over R times the quiet side's mean, and not zero
+        if (after >= AT3PHIP_TONE_GATE_RATIO * before && after > 0.0) {
+            for (int j = bs; j < bs + AT3PHIP_TONE_GATE_MIN; ++j)
+                if (!(e[j] >= AT3PHIP_TONE_GATE_RATIO * before && e[j] > 0.0)) return 0;
+            return bs;
+        }
+        if (before >= AT3PHIP_TONE_GATE_RATIO * after && before > 0.0) {
+            for (int j = bs - AT3PHIP_TONE_GATE_MIN; j < bs; ++j)
+                if (!(e[j] >= AT3PHIP_TONE_GATE_RATIO * after && e[j] > 0.0)) return 0;
+            return 0x80 | (bs - 1);
+        }
+        return 0;
+    }
     // the kissfft-order forward FFT for n = 4^k (kf_work and kf_bfly4, kiss_fft.c:42-90, 238-302)
     void Fft(TCpx* out, const TCpx* in, int n, int fstride) const
     {
@@ -740,14 +822,17 @@ private:
             out[3 * m + k].r = s5.r - s4.i; out[3 * m + k].i = s5.i + s4.r;
         }
     }
-    // steps 1-5 for one subband: at most AT3PHIP_TONE_MAX_BAND_WAVES waves
-    int FindBand(const float* x, TWave* out) const
+    // steps 1-5 for one subband: at most AT3PHIP_TONE_MAX_BAND_WAVES waves. event: G4 over the cells [lo, hi] of G3
+    int FindBand(const float* x, TWave* out, bool event, int lo, int hi) const
     {
         constexpr int kMax = AT3PHIP_TONE_MAX_BAND_WAVES, kSpan = AT3PHIP_TONE_FINE_SPAN;
-        float y[256], P[129];
+        if (event && hi - lo + 1 < AT3PHIP_TONE_GATE_MIN) return 0;
+        const int t0 = 4 * lo, t1 = 4 * hi + 3;
+        float y[256], wnd[256], P[129];
         TCpx in[256], F[256];
         for (int t = 0; t < 256; ++t) {
-            y[t] = x[t] * T.Hann[t];
+            wnd[t] = event && (t < t0 || t > t1) ? 0.0f : T.Hann[t];
+            y[t] = x[t] * wnd[t];
             in[t].r = y[t];
             in[t].i = 0.0f;
         }
@@ -768,17 +853,33 @@ private:
         }
         int n = 0;
         for (int c = 0; c < nc; ++c) {
-            const int lo = std::max(1, 8 * ck[c] - kSpan), hi = std::min(1023, 8 * ck[c] + kSpan);
+            const int flo = std::max(1, 8 * ck[c] - kSpan), fhi = std::min(1023, 8 * ck[c] + kSpan);
             int bf = -1;
-            double bs = 0, bc = 0, bp = 0;
-            for (int f = lo; f <= hi; ++f) {
+            double bs = 0, bc = 0, bp = 0;   // (with an event: a and b in the places of S and C)
+            for (int f = flo; f <= fhi; ++f) {
                 double S = 0, C = 0;
                 for (int t = 0; t < 256; ++t) {
                     const int pos = ((t - 128) * f) & 2047;
                     S = S + (double)y[t] * (double)T.Sine[pos];
                     C = C + (double)y[t] * (double)T.Sine[(pos + 512) & 2047];
                 }
-                const double pw = (S * S) * T.Rs[f] + (C * C) * T.Rc[f];
+                double pw = (S * S) * T.Rs[f] + (C * C) * T.Rc[f];
+                if (event) {   // G4: the 2 x 2 normal equations under the gated window
+                    double gss = 0, gcc = 0, gsc = 0;
+                    for (int t = t0; t <= t1; ++t) {
+                        const int pos = ((t - 128) * f) & 2047;
+                        const double sn = (double)T.Sine[pos], cs = (double)T.Sine[(pos + 512) & 2047];
+                        gss = gss + (double)wnd[t] * (sn * sn);
+                        gcc = gcc + (double)wnd[t] * (cs * cs);
+                        gsc = gsc + (double)wnd[t] * (sn * cs);
+                    }
+                    const double det = gss * gcc - gsc * gsc;
+                    if (!(det > 0.0)) continue;
+                    const double a = (S * gcc - C * gsc) / det, b = (C * gss - S * gsc) / det;
+                    pw = a * S + b * C;
+                    S = a;
+                    C = b;
+                }
                 if (bf < 0 || pw > bp) {
                     bf = f;
                     bs = S;
@@ -787,7 +888,8 @@ private:
                 }
             }
             if (bf < 0) continue;
-            const double ca = bs * T.Rs[bf], cb = bc * T.Rc[bf];   // x[t] = ca sin + cb cos, by least squares under the window
+            // x[t] = ca sin + cb cos, by least squares under the window
+            const double ca = event ? bs : bs * T.Rs[bf], cb = event ? bc : bc * T.Rc[bf];
             const double a2 = ca * ca + cb * cb;
             if (!(a2 >= AT3PHIP_TONE_MIN_AMP * AT3PHIP_TONE_MIN_AMP)) continue;
             int sf = 0;
@@ -834,8 +936,9 @@ private:
             Block.num_tone_bands = (uint8_t)std::max<int>(Block.num_tone_bands, w[i].Sb + 1);
         }
     }
-    // a band's waves at the samples of one frame (the decoder's step 4b without an envelope): reg = 128 fading out, 0 fading in
-    void Waves(const at3phip_tonal_block& b, int ch, int sb, int reg, float* out) const
+    // a band's waves at the samples of one frame under the envelope e (waves_synth of the decoder's step 4b): reg = 128 fading
+    // out, 0 fading in
+    void Waves(const at3phip_tonal_block& b, int ch, int sb, const TEnv& e, int reg, float* out) const
     {
         int first = 0;
         for (int c = 0; c <= ch; ++c)   // channel 0's bands go first
@@ -850,36 +953,61 @@ private:
                 pos = (pos + inc) & 2047;
             }
         }
+        if (e.Hs) {
+            const int pos = (e.S << 2) - reg;
+            if (pos > 0 && pos <= 128) {
+                for (int i = 0; i < pos; ++i) out[i] = 0.0f;
+                if (!e.He || e.S != e.E)
+                    for (int k = 0; k < 4 && pos + k < 128; ++k) out[pos + k] = out[pos + k] * T.Hann[32 * k];
+            }
+        }
+        if (e.He) {
+            const int pos = ((e.E + 1) << 2) - reg;
+            if (pos > 0 && pos <= 128) {
+                for (int k = 0; k < 4; ++k) out[pos - 4 + k] = out[pos - 4 + k] * T.Hann[96 - 32 * k];
+                for (int i = pos; i < 128; ++i) out[i] = 0.0f;
+            }
+        }
     }
-    // step 8 for one band: ApplyFilter's out -= wavreg1 + wavreg2
-    void Subtract(const at3phip_tonal_block& before, const at3phip_tonal_block& now, int ch, int sb, float* x) const
+    // step 8 / G5 for one band: ApplyFilter's out -= wavreg1 + wavreg2 as ff_atrac3p_generate_tones forms them for the block
+    // `now` after `before`, whose own envelope follows from `older`'s points
+    void Subtract(const at3phip_tonal_block& older, const at3phip_tonal_block& before, const at3phip_tonal_block& now, int ch, int sb,
+                  float* x) const
     {
         const int n1 = before.band[ch][sb].n_waves, n2 = now.band[ch][sb].n_waves;
         if (!n1 && !n2) return;
+        const TEnv e2 = CurrEnv(now.band[ch][sb], before.band[ch][sb]), e1 = CurrEnv(before.band[ch][sb], older.band[ch][sb]);
+        const bool reg1 = e1.E >= 32, reg2 = e2.S < 32;
         float w1[128] = {0}, w2[128] = {0};
-        Waves(before, ch, sb, 128, w1);
-        Waves(now, ch, sb, 0, w2);
+        if (n1 && reg1) Waves(before, ch, sb, e1, 128, w1);
+        if (n2 && reg2) Waves(now, ch, sb, e2, 0, w2);
+        const bool both = n1 && n2 && reg1 && reg2;
+        const bool h1 = both || (n1 && !e1.He), h2 = both || (n2 && !e2.Hs);
         for (int i = 0; i < 128; ++i) {
-            if (n1) w1[i] = w1[i] * T.Hann[128 + i];
-            if (n2) w2[i] = w2[i] * T.Hann[i];
+            if (h1) w1[i] = w1[i] * T.Hann[128 + i];
+            if (h2) w2[i] = w2[i] * T.Hann[i];
             x[i] -= w1[i] + w2[i];
         }
     }
     const int Channels;
+    const bool Gated;
     TTables T;
     at3phip_tonal_block Block{};   // the last block found
+    at3phip_tonal_block Older{};   // and the one before it: its points decide the last block's envelope
 };
 
 class TAt3PEncoder {
 public:
     // deviceTones: the tone analysis on the GPU (at3phip_encode_frames_tonal, a batch per call) instead of an analyser on the
     // host: byte for byte the frames of this class around TAt3PToneAnalyser with UseGha = GHA_ENABLED. `gha` must then be null.
+    // deviceGated: that analysis with AT3PHIP_TONES_GATED, byte for byte TAt3PToneAnalyser(channels, true)'s frames.
     TAt3PEncoder(TCompressedOutputPtr&& out, int channels, int batchFrames = 64, int deviceId = 0, TAt3PSettings settings = TAt3PSettings(),
-                 IAt3PGhaProcessor* gha = nullptr, bool deviceTones = false)
+                 IAt3PGhaProcessor* gha = nullptr, bool deviceTones = false, bool deviceGated = false)
         : Out(std::move(out)), Channels((size_t)channels), BatchFrames(batchFrames), FrameFloats((size_t)AT3PHIP_FRAME * (size_t)channels),
-          Settings(settings), Gha(gha), DeviceTones(deviceTones)
+          Settings(settings), Gha(gha), DeviceTones(deviceTones), ToneFlags(deviceGated ? AT3PHIP_TONES_GATED : 0u)
     {
         if (deviceTones && gha) throw std::invalid_argument("TAt3PEncoder: deviceTones takes no host analyser");
+        if (deviceGated && !deviceTones) throw std::invalid_argument("TAt3PEncoder: deviceGated needs deviceTones");
         at3phip_config cfg{};
         cfg.channels = channels;
         cfg.n_streams = 1;
@@ -931,7 +1059,7 @@ public:
         std::vector<uint8_t> frames((size_t)BatchFrames * AT3PHIP_FRAME_BYTES);
         for (int at = 0; at < nFrames; at += BatchFrames) {
             const int nf = std::min(BatchFrames, nFrames - at);
-            if (DeviceTones) Chk(at3phip_encode_frames_tonal_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), 0), "at3phip_encode_frames_tonal_short");
+            if (DeviceTones) Chk(at3phip_encode_frames_tonal_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), ToneFlags), "at3phip_encode_frames_tonal_short");
             else Chk(at3phip_encode_frames_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), 0), "at3phip_encode_frames_short");
             for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES);
             Calls += (size_t)nf;
@@ -950,7 +1078,7 @@ public:
         }
         if (nf > 0) {
             std::vector<uint8_t> frames((size_t)nf * AT3PHIP_FRAME_BYTES);
-            if (DeviceTones) Chk(at3phip_encode_frames_tonal(Ctx, Pending.data(), nf, frames.data(), 0), "at3phip_encode_frames_tonal");
+            if (DeviceTones) Chk(at3phip_encode_frames_tonal(Ctx, Pending.data(), nf, frames.data(), ToneFlags), "at3phip_encode_frames_tonal");
             else Chk(at3phip_encode_frames(Ctx, Pending.data(), nf, frames.data(), 0), "at3phip_encode_frames");
             Pending.clear();
             for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES);
@@ -1036,6 +1164,7 @@ private:
     const TAt3PSettings Settings;
     IAt3PGhaProcessor* const Gha;                 // not owned; null: the analysis finds nothing
     const bool DeviceTones;                       // the analysis runs on the GPU
+    const uint32_t ToneFlags;                     // and with these flags (AT3PHIP_TONES_GATED)
     std::vector<float> PrevBuf, CurBuf, RawCur;   // [C][16][128] / [C][2048]: TChannelCtx's PrevBuf, CurBuf and RawCurBuf
     at3phip_tonal_block Delay{};                  // `delay`: the block the next call writes
 };

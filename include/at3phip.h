@@ -180,11 +180,60 @@ int at3phip_encode_frames_short(at3phip_ctx* ctx, const int16_t* pcm, int32_t n_
  *      (zeros, frame 0) like any other.
  * The constants are those of the prototype whose round-trip figures DESIGN.md section 17 lists; changing one changes the
  * definition. Against that prototype the definition admits the end bins in step 3 and normalises by rs and rc instead of 1 / 64
- * in steps 4 and 5: both only matter next to frequency index 0 or 1024, and the round-trip figures stay within 0.5 dB of it. Out of this definition: envelope points, sharing and the leader flag, any psychoacoustic veto. */
+ * in steps 4 and 5: both only matter next to frequency index 0 or 1024, and the round-trip figures stay within 0.5 dB of it. Out of this definition: envelope points, sharing and the leader flag, any psychoacoustic veto.
+ *
+ * GATES (AT3PHIP_TONES_GATED in `flags`; without the flag steps 1-9 stand as written and no output changes a byte). A block
+ * describes its sines over two whole frames; a sine that starts or stops inside one of them is gated with the block's envelope
+ * points, which the writer and the decoder already carry. A cell is 4 subband samples: a frame has 32, a block 64, cell j of a
+ * block covering x[4 j .. 4 j + 3]. Float and double operations as written, each rounded, no FMA:
+ *  G1. The gate of a frame, per channel and subband, from that frame's 128 samples x alone. e[j] = ((x[4j] * x[4j] + x[4j+1] *
+ *      x[4j+1]) + x[4j+2] * x[4j+2]) + x[4j+3] * x[4j+3] in float, j = 0..31. P[0] = 0.0, P[j+1] = P[j] + (double)e[j] in double.
+ *      For each split s in MIN .. 32 - MIN (MIN = AT3PHIP_TONE_GATE_MIN = 4 cells, the reference's "do not encode too short
+ *      frame" rule, at3p_gha.cpp, len < 4): before(s) = P[s] / (double)s, after(s) = (P[32] - P[s]) / (double)(32 - s),
+ *      d(s) = fabs(after - before). The candidate is s = MIN, replaced in ascending order by every s whose d is greater than the
+ *      candidate's (so the largest d, the lowest s on a tie). With R = AT3PHIP_TONE_GATE_RATIO the candidate is an onset at s when
+ *      after >= R * before and after > 0.0; else an offset with last active cell s - 1 when before >= R * after and before > 0.0;
+ *      else the frame has no event (so never with a NaN energy). Added to make MIN hold for the loud side itself (a burst shorter
+ *      than MIN cells is no event, and a gate never opens over cells that hold nothing): an onset also needs (double)e[j] >=
+ *      R * before and e[j] > 0 for each of j = s .. s + MIN - 1, an offset (double)e[j] >= R * after and e[j] > 0 for each of
+ *      j = s - MIN .. s - 1; failing that the frame has no event. At most one event per frame, channel and subband; a sine that
+ *      starts and stops inside one frame is out of scope. As a byte: 0 = none, 1..31 = onset at s, 0x80 | p = offset with last
+ *      active cell p.
+ *  G2. What is written. The event of frame m+1 is the band's point pair in block T_m (start = s + 1 or stop = p + 1, the record's
+ *      "+1" convention; the other point 0): the decoder adds 32 to the pend_env of the block it belongs to, which puts the point
+ *      into that block's second half. Points are written whenever the gate fires, with or without a wave in the band, and
+ *      num_tone_bands = the highest band holding a wave or a point in either channel, plus 1: every block's envelope then follows
+ *      from the gates of its own two frames, and the slots of a call stay independent of one another.
+ *  G3. A block's active interval [lo, hi] in cells is the curr_env that ff_atrac3p_generate_tones reconstructs for the block from
+ *      its own points and those of the block before (decoder section, step 4b; decp_curr_env in the kernels): lo = start_pos with
+ *      a start point, else 0; hi = stop_pos with a stop point, else 63. So an onset at s in the second frame gives [32 + s, 63];
+ *      an offset at p in the first frame gives [0, p] when the second frame has no onset; an onset at s in the first frame and an
+ *      offset at p in the second give [s, 32 + p]. An offset at p in the first frame FOLLOWED by an onset at s in the second gives
+ *      [32 + s, 63]: the syntax holds one interval per block and the decoder keeps the later one; the analysis follows it. A
+ *      block whose interval has fewer than MIN cells (hi - lo + 1 < MIN) gets no wave in that band.
+ *  G4. The gated fit. A band without an event in either of its block's two frames runs steps 1-5 as written, rs and rc included.
+ *      Otherwise: step 1 is y[t] = x[t] * w[t], w[t] = hann_window[t] for 4 lo <= t <= 4 hi + 3 and +0.0f elsewhere; steps 2 and
+ *      3 run on that y; in step 4 S(f) and C(f) are summed as written and, beside them, from 0.0 for t = 4 lo .. 4 hi + 3 in
+ *      order, Gss = sum of (double)w[t] * (sn * sn), Gcc = sum of (double)w[t] * (cs * cs), Gsc = sum of (double)w[t] * (sn * cs),
+ *      sn = (double)sine_table[((t - 128) f) & 2047], cs = (double)sine_table[((t - 128) f + 512) & 2047]; det = Gss * Gcc -
+ *      Gsc * Gsc; a = (S * Gcc - C * Gsc) / det, b = (C * Gss - S * Gsc) / det (the 2 x 2 normal equations of the least-squares
+ *      fit under w: sine and cosine are no longer orthogonal under a one-sided window). An f whose det is not greater than 0.0 is
+ *      passed over; the f of largest a * S + b * C is taken, the lowest on a tie; a candidate left without an f gives no wave.
+ *      Step 5 takes that f's a and b; A2, the amplitude floor, AmpSf, PhaseIndex and steps 6-7 stay as they are (step 7 with the
+ *      points of G2). The decoder does not Hann-window a gated region whose neighbour block has no wave there, and fades a gate
+ *      over 4 samples; the analysis weighs with Hann times gate regardless. The mismatch costs efficiency, never correctness:
+ *  G5. Step 8 subtracts exactly what the decoder's step 4b adds for these records, envelopes included (one device function,
+ *      decp_waves, serves both).
+ * The state carried per stream gains the block before the last one (its points decide the last block's envelope). */
 #define AT3PHIP_TONE_PEAK_RATIO 16.0      /* step 3: a candidate's power over the mean power */
 #define AT3PHIP_TONE_MAX_BAND_WAVES 3     /* step 3: candidates per channel and subband */
 #define AT3PHIP_TONE_FINE_SPAN 7          /* step 4: frequency indices searched on either side of 8 k */
 #define AT3PHIP_TONE_MIN_AMP 8.0          /* step 5: the smallest amplitude kept, in subband sample units */
+#define AT3PHIP_TONE_GATE_MIN 4           /* G1, G3: the fewest cells on either side of a split, and in an interval that gets a wave */
+#define AT3PHIP_TONE_GATE_RATIO 16.0      /* G1: the mean cell energy after an onset (before an offset) over the other side's */
+/* flag of at3phip_analyse_tones, at3phip_encode_frames_tonal and at3phip_encode_frames_tonal_short: the analysis with GATES. A
+ * stream stays with one mode between resets. Still ABI 1.6: a host that needs it looks for the symbol at3phip_host_tone_gates. */
+#define AT3PHIP_TONES_GATED 32u
 
 /* Steps 1-8 on caller-supplied subband samples: the stage tap of at3phip_encode_frames_tonal.
  *   bands     [n_streams][n_frames][channels][16][128] float32 as at3phip_pqf_analyse writes them (flags & AT3HIP_PCM_ON_DEVICE:
@@ -219,6 +268,11 @@ int at3phip_encode_frames_tonal_short(at3phip_ctx* ctx, const int16_t* pcm, int3
  * bytes = AT3PHIP_TONE_FIND_TABLES_BYTES. */
 #define AT3PHIP_TONE_FIND_TABLES_BYTES 28416
 int at3phip_host_tone_find_tables(void* dst, size_t bytes);
+
+/* G1 on the host (no GPU needed): bands [n_frames][channels][16][128] float32 of one stream, out [n_frames][channels][16] bytes,
+ * each frame's gate as G1 codes it (0 = none, 1..31 = onset at s, 0x80 | p = offset with last active cell p). A library that has
+ * this symbol takes AT3PHIP_TONES_GATED. */
+int at3phip_host_tone_gates(const float* bands, int32_t n_frames, int32_t channels, uint8_t* out);
 
 /* With AT3HIP_ASYNC in `flags` at3phip_encode_frames only queues the call (pcm must stay valid, frames must not be read)
  * and the frame writer of one call runs beside the filter bank and transform of the next (its own stream, spectra
