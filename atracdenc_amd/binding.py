@@ -191,6 +191,7 @@ PROTOTYPES = {
     "at3phip_get_timings": (_RC, [_VP, _F32P, _F32P]), "at3phip_get_write_timing": (_RC, [_VP, _F32P]),
     "at3phip_host_tables": (_RC, [_VP, _SZ]), "at3phip_host_write_tables": (_RC, [_VP, _SZ]),
     "at3phip_host_tone_find_tables": (_RC, [_VP, _SZ]), "at3phip_host_tone_gates": (_RC, [_VP, _I32, _I32, _VP]),
+    "at3phip_host_tone_flags": (_U32, []),
     # include/at3phip.h: the ATRAC3plus decoder
     "at3phip_decoder_create": (_RC, [_P(At3pDecoderConfig), _P(_VP)]), "at3phip_decoder_destroy": (None, [_VP]),
     "at3phip_decoder_last_error": (_STR, [_VP]), "at3phip_decoder_reset": (_RC, [_VP]), "at3phip_decoder_sync": (_RC, [_VP]),
@@ -797,6 +798,19 @@ def at3p_host_tone_gates(bands, lib_path=None):
     return out
 
 
+AT3PHIP_TONES_SHARED = 64   # flag of the tonal calls: twin bands of a stereo frame are written once (include/at3phip.h, SHARING)
+
+
+def at3p_host_tone_flags(lib_path=None):
+    """at3phip_host_tone_flags (no GPU): the mask of analysis flags the library understands. A library without the symbol
+    predates AT3PHIP_TONES_SHARED."""
+    return int(_need(load_library(lib_path), "at3phip_host_tone_flags")())
+
+
+def _tone_flags(gated, shared):
+    return (AT3PHIP_TONES_GATED if gated else 0) | (AT3PHIP_TONES_SHARED if shared else 0)
+
+
 class At3pHip(_Context):
     """ATRAC3plus front end (include/at3phip.h): PQF analysis and windowed MDCT-256 x 16 for n_streams streams."""
 
@@ -921,43 +935,44 @@ class At3pHip(_Context):
         filter bank. Calls of both kinds may alternate."""
         return self._encode_frames_host(pcm, np.int16, self.encode_frames_s16_ptr)
 
-    def analyse_tones(self, bands, gated=False):
+    def analyse_tones(self, bands, gated=False, shared=False):
         """bands float32 [S, F, C, 16, 128] (what pqf() returns) -> (blocks of AT3P_TONAL_BLOCK_DTYPE [S, F], residual
         [S, F, C, 16, 128]): at3phip_analyse_tones, slot f holding the block of (frame f-1, frame f) and the residual of frame
         f-1; the last frame and block carry over to the next call. gated: AT3PHIP_TONES_GATED, onsets and offsets become the
-        records' envelope points (a stream stays with one mode between resets)."""
+        records' envelope points; shared: AT3PHIP_TONES_SHARED, a band that both channels of a stereo frame hold identically is
+        written and counted once (a stream stays with one mode between resets)."""
         bands = np.ascontiguousarray(bands, dtype=np.float32)
         assert bands.ndim == 5 and bands.shape[0] == self.n_streams and bands.shape[2:] == (self.channels, 16, 128), bands.shape
         nf = bands.shape[1]
         blocks = np.zeros((self.n_streams, nf), AT3P_TONAL_BLOCK_DTYPE)
         resid = np.zeros_like(bands)
-        self.analyse_tones_ptr(bands.ctypes.data, nf, blocks.ctypes.data, resid.ctypes.data, AT3PHIP_TONES_GATED if gated else 0)
+        self.analyse_tones_ptr(bands.ctypes.data, nf, blocks.ctypes.data, resid.ctypes.data, _tone_flags(gated, shared))
         return blocks, resid
 
-    def analyse_tones_device(self, bands_ptr, n_frames, residual_ptr, gated=False):
+    def analyse_tones_device(self, bands_ptr, n_frames, residual_ptr, gated=False, shared=False):
         """Device-resident subband samples and residual (raw pointers) -> the blocks [S, F] (host memory). The call waits; whatever
         produces the samples must be complete before it (see encode_frames_device)."""
         blocks = np.zeros((self.n_streams, int(n_frames)), AT3P_TONAL_BLOCK_DTYPE)
-        self.analyse_tones_ptr(bands_ptr, n_frames, blocks.ctypes.data, residual_ptr, _device_flags(False) | (AT3PHIP_TONES_GATED if gated else 0))
+        self.analyse_tones_ptr(bands_ptr, n_frames, blocks.ctypes.data, residual_ptr, _device_flags(False) | _tone_flags(gated, shared))
         return blocks
 
-    def encode_frames_tonal(self, pcm, gated=False):
+    def encode_frames_tonal(self, pcm, gated=False, shared=False):
         """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, 2048] with the tone analysis (at3phip_encode_frames_tonal): frame f
         of the stream holds the residual of input frame f-1 and the block of frame f-2, so one trailing frame of silence flushes.
-        gated: AT3PHIP_TONES_GATED, as in analyse_tones()."""
-        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr, AT3PHIP_TONES_GATED if gated else 0)
+        gated: AT3PHIP_TONES_GATED, shared: AT3PHIP_TONES_SHARED, as in analyse_tones()."""
+        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr, _tone_flags(gated, shared))
 
-    def encode_frames_tonal_s16(self, pcm, gated=False):
+    def encode_frames_tonal_s16(self, pcm, gated=False, shared=False):
         """The same for int16 PCM (at3phip_encode_frames_tonal_short): the frames of encode_frames_tonal() on pcm / 32768."""
-        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr, AT3PHIP_TONES_GATED if gated else 0)
+        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr, _tone_flags(gated, shared))
 
-    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False):
+    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False):
         """Device-resident float32 PCM / frames; ordering and what stays untouched until sync() as in encode_frames_device."""
-        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | (AT3PHIP_TONES_GATED if gated else 0))
+        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared))
 
-    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False):
+    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False):
         """Device-resident int16 PCM / frames, as encode_frames_tonal_device."""
-        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | (AT3PHIP_TONES_GATED if gated else 0))
+        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared))
 
     def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
         """asynchronous=True only queues the call (AT3HIP_ASYNC): sync() before the frames are read, and both buffers stay

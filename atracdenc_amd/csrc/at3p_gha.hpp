@@ -10,6 +10,10 @@
 // the bands that have an event and hands the second frame's gate to k_at3p_tone_select, which writes the points;
 // k_at3p_tone_sub<true> applies the records' envelopes (the decoder's own functions, at3p_tone_synth.hpp), for which the block
 // before the last one is carried as well. k_at3p_tone_find<false> and k_at3p_tone_sub<false> are the kernels without any of it.
+// SHARING (AT3PHIP_TONES_SHARED, steps S1-S5 of the header, stereo only): k_at3p_tone_select<true> decides the twin bands, keeps
+// channel 1's waves of those bands out of the budget and writes the sharing word; k_at3p_tone_sub<., true> resolves channel 1's
+// band through each record's own sharing word. The <false> instances are the kernels without any of it; k_at3p_tone_find and
+// k_at3p_tone_state are the same for both (the carried records hold their sharing words).
 // The analysis is written out three times and the three change together: here, in the C restatement tests/host/at3p_gha_cpu.c
 // and in the host mirror's TAt3PToneAnalyser (atracdenc_amd/host/at3hip_host.hpp); the table builder is build_tone_find_tables.
 #pragma once
@@ -309,12 +313,15 @@ __global__ __launch_bounds__(256) void k_at3p_tone_find(ToneParams p)
     }
 }
 
+// kShared: S2-S4 of a stereo context (only launched with nch = 2)
+template <bool kShared>
 __global__ __launch_bounds__(128) void k_at3p_tone_select(ToneParams p)
 {
     __shared__ double s_a2[kToneFrameWaves];
     __shared__ uint32_t s_key[kToneFrameWaves], s_wave[kToneFrameWaves], s_ok[kToneFrameWaves];
     __shared__ uint32_t s_rec[kTonalBlockWords];
     __shared__ uint32_t s_top;
+    __shared__ uint32_t s_gate[2 * 16], s_twin;   // kShared only: the bands' gate bytes, and bit b = band b is a twin
 
     const int f = blockIdx.x, s = blockIdx.y, nch = p.nch, tid = threadIdx.x;
     const size_t item = (size_t)s * p.n_frames + f;
@@ -324,6 +331,7 @@ __global__ __launch_bounds__(128) void k_at3p_tone_select(ToneParams p)
 
     if (tid < kTonalBlockWords) s_rec[tid] = 0u;
     if (tid == 0) s_top = 0u;
+    if (kShared && tid == 0) s_twin = 0u;
     if (mine) {
         ToneCand c;
         c.a2 = 0.0;
@@ -335,8 +343,35 @@ __global__ __launch_bounds__(128) void k_at3p_tone_select(ToneParams p)
         s_key[tid] = (uint32_t)ch << 16 | (uint32_t)sb << 12 | (c.wave & 1023u);   // the record's order: channel, band, frequency index
         s_ok[tid] = c.valid & 1u;
         gate = p.gated ? (c.valid >> 8) & 0xffu : 0u;   // (only a band's first slot carries one)
+        if (kShared && rest == sb * kToneBandWaves) s_gate[ch * 16 + sb] = gate;
     }
     __syncthreads();
+    if constexpr (kShared) {
+        if (tid < 16) {   // S2: one lane per band; the words as sets (a band's words differ from one another), the points by their gate bytes
+            const uint32_t* ok0 = s_ok + tid * kToneBandWaves;
+            const uint32_t* ok1 = ok0 + 16 * kToneBandWaves;
+            const uint32_t* w0 = s_wave + tid * kToneBandWaves;
+            const uint32_t* w1 = w0 + 16 * kToneBandWaves;
+            uint32_t n0 = 0u, n1 = 0u;
+            bool same = s_gate[tid] == s_gate[16 + tid];
+#pragma unroll
+            for (int i = 0; i < kToneBandWaves; ++i) {
+                n0 += ok0[i];
+                n1 += ok1[i];
+                bool found = false;
+#pragma unroll
+                for (int j = 0; j < kToneBandWaves; ++j) found = found || (ok1[j] && w1[j] == w0[i]);
+                same = same && (!ok0[i] || found);
+            }
+            if (same && n0 == n1) atomicOr(&s_twin, 1u << tid);
+        }
+        __syncthreads();
+        if (mine && ch == 1 && ((s_twin >> sb) & 1u)) {   // S3, S4: channel 1's waves of a twin band leave the population, and its point is not written
+            s_ok[tid] = 0u;
+            gate = 0u;
+        }
+        __syncthreads();
+    }
     if (gate) {   // G2: the point, with or without a wave in the band: byte 1 of the band's word is start + 1, byte 2 stop + 1
         atomicAdd(&s_rec[1 + ch * 16 + sb], gate < 0x80u ? (gate + 1u) << 8 : ((gate & 31u) + 1u) << 16);
         atomicMax(&s_top, (uint32_t)sb + 1u);
@@ -365,7 +400,8 @@ __global__ __launch_bounds__(128) void k_at3p_tone_select(ToneParams p)
         atomicMax(&s_top, (uint32_t)sb + 1u);
     }
     __syncthreads();
-    if (tid == 0) s_rec[0] = s_top;   // num_tone_bands (the highest band with a wave or a point, plus 1); second_is_leader and tone_sharing stay 0
+    // num_tone_bands (the highest band with a wave or a point, plus 1); second_is_leader stays 0, and so does tone_sharing without S4
+    if (tid == 0) s_rec[0] = kShared ? s_top | (s_twin & ((1u << s_top) - 1u)) << 16 : s_top;
     __syncthreads();
     if (tid < kTonalBlockWords) {
         const uint32_t v = s_rec[tid];
@@ -374,9 +410,17 @@ __global__ __launch_bounds__(128) void k_at3p_tone_select(ToneParams p)
     }
 }
 
-// band b of channel ch of a record's words as the decoder's TonalBand
+// S5: the channel whose band b a record's channel ch uses: channel 0's where the record shares the band
+__device__ __forceinline__ int tone_rec_channel(uint32_t word0, int ch, int b)
+{
+    return ch == 1 && ((word0 >> (16 + b)) & 1u) ? 0 : ch;
+}
+
+// band b of channel ch of a record's words as the decoder's TonalBand; kShared: through the record's sharing word
+template <bool kShared = false>
 __device__ __forceinline__ TonalBand tone_rec_band(const uint32_t* rec, int ch, int b)
 {
+    if constexpr (kShared) ch = tone_rec_channel(rec[0], ch, b);
     int first = 0;   // the band's first wave: the waves of every band before it, channel 0's bands first
     for (int j = 0; j < ch * 16 + b; ++j) first += (int)(rec[1 + j] & 0xffu);
     const uint32_t word = rec[1 + ch * 16 + b];
@@ -392,7 +436,8 @@ __device__ __forceinline__ TonalBand tone_rec_band(const uint32_t* rec, int ch, 
 }
 
 // kGated = false: no record of the stream holds a point, and none is looked for
-template <bool kGated>
+// kShared = false: no record of the stream shares a band
+template <bool kGated, bool kShared>
 __global__ __launch_bounds__(256) void k_at3p_tone_sub(ToneParams p)
 {
     __shared__ uint32_t s_cur[kTonalBlockWords], s_old[kTonalBlockWords];
@@ -410,12 +455,13 @@ __global__ __launch_bounds__(256) void k_at3p_tone_sub(ToneParams p)
         s_old[tid] = reinterpret_cast<const uint32_t*>(f > 0 ? cur - 1 : p.last + s)[tid];
     }
     __syncthreads();
-    if (tid < 32) s_band[tid >> 4][tid & 15] = tone_rec_band(tid < 16 ? s_old : s_cur, ch, tid & 15);
+    if (tid < 32) s_band[tid >> 4][tid & 15] = tone_rec_band<kShared>(tid < 16 ? s_old : s_cur, ch, tid & 15);
     __syncthreads();
     if (tid < 16) {   // step 8 / G5: what the decoder's step 4b does with these records
         // the block before the old one: its points decide the old block's envelope
         const TonalBlock* older = f > 1 ? cur - 2 : f == 1 ? p.last + s : p.last + p.n_streams + s;
-        const uint32_t word = kGated ? reinterpret_cast<const uint32_t*>(older)[1 + ch * 16 + tid] : 0u;
+        const uint32_t* ow = reinterpret_cast<const uint32_t*>(older);
+        const uint32_t word = kGated ? ow[1 + (kShared ? tone_rec_channel(ow[0], ch, tid) : ch) * 16 + tid] : 0u;
         TonalBand pv;
         pv.nw = 0;
         pv.start_index = 0;

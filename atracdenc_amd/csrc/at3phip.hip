@@ -212,10 +212,11 @@ int ensure_tones(at3phip_ctx* c)
 }
 
 // Steps 1-8 on d_bands: the blocks into d_tone_blocks, the residuals into d_resid, the writer's records (or none) into d_writer.
-// gated: AT3PHIP_TONES_GATED (steps G1-G5).
-int launch_tones(at3phip_ctx* c, const float* d_bands, int n_frames, float* d_resid, TonalBlock* d_writer, bool gated)
+// flags: AT3PHIP_TONES_GATED (steps G1-G5), AT3PHIP_TONES_SHARED (steps S1-S5; a mono context has nothing to share).
+int launch_tones(at3phip_ctx* c, const float* d_bands, int n_frames, float* d_resid, TonalBlock* d_writer, uint32_t flags)
 {
     const unsigned S = (unsigned)c->cfg.n_streams, C = (unsigned)c->cfg.channels, F = (unsigned)n_frames;
+    const bool gated = (flags & AT3PHIP_TONES_GATED) != 0, shared = (flags & AT3PHIP_TONES_SHARED) != 0 && C == 2;
     ToneParams tp;
     tp.T = c->d_tone_tables;
     tp.bands = d_bands;
@@ -233,10 +234,17 @@ int launch_tones(at3phip_ctx* c, const float* d_bands, int n_frames, float* d_re
     if (gated) hipLaunchKernelGGL(k_at3p_tone_find<true>, dim3(F * 4, S * C), dim3(256), 0, c->stream, tp);
     else hipLaunchKernelGGL(k_at3p_tone_find<false>, dim3(F * 4, S * C), dim3(256), 0, c->stream, tp);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_at3p_tone_select, dim3(F, S), dim3(128), 0, c->stream, tp);
+    if (shared) hipLaunchKernelGGL(k_at3p_tone_select<true>, dim3(F, S), dim3(128), 0, c->stream, tp);
+    else hipLaunchKernelGGL(k_at3p_tone_select<false>, dim3(F, S), dim3(128), 0, c->stream, tp);
     HIPCHK(c, hipGetLastError());
-    if (gated) hipLaunchKernelGGL(k_at3p_tone_sub<true>, dim3(F, S * C), dim3(256), 0, c->stream, tp);
-    else hipLaunchKernelGGL(k_at3p_tone_sub<false>, dim3(F, S * C), dim3(256), 0, c->stream, tp);
+    if (shared) {
+        if (gated) hipLaunchKernelGGL((k_at3p_tone_sub<true, true>), dim3(F, S * C), dim3(256), 0, c->stream, tp);
+        else hipLaunchKernelGGL((k_at3p_tone_sub<false, true>), dim3(F, S * C), dim3(256), 0, c->stream, tp);
+    } else if (gated) {
+        hipLaunchKernelGGL((k_at3p_tone_sub<true, false>), dim3(F, S * C), dim3(256), 0, c->stream, tp);
+    } else {
+        hipLaunchKernelGGL((k_at3p_tone_sub<false, false>), dim3(F, S * C), dim3(256), 0, c->stream, tp);
+    }
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_at3p_tone_state, dim3(S), dim3(256), 0, c->stream, tp, c->d_tone_prev);
     HIPCHK(c, hipGetLastError());
@@ -495,7 +503,7 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     if (timed) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     const float* d_mdct_in = c->d_bands;
     if constexpr (kTones) {   // (its time counts as the transform's)
-        rc = launch_tones(c, c->d_bands, n_frames, c->d_tone_resid, c->d_tone_writer[par], (flags & AT3PHIP_TONES_GATED) != 0);
+        rc = launch_tones(c, c->d_bands, n_frames, c->d_tone_resid, c->d_tone_writer[par], flags);
         if (rc != AT3HIP_OK) return rc;
         d_mdct_in = c->d_tone_resid;
     }
@@ -560,7 +568,7 @@ int at3phip_analyse_tones(at3phip_ctx* c, const float* bands, int32_t n_frames, 
     const bool out_dev = (flags & AT3HIP_OUT_ON_DEVICE) != 0;
     float* d_resid = (out_dev && residual) ? residual : c->d_tone_resid;
     c->ev_from_encode = false;
-    rc = launch_tones(c, d_bands, n_frames, d_resid, nullptr, (flags & AT3PHIP_TONES_GATED) != 0);
+    rc = launch_tones(c, d_bands, n_frames, d_resid, nullptr, flags);
     if (rc != AT3HIP_OK) return rc;
     if (blocks) HIPCHK(c, hipMemcpyAsync(blocks, c->d_tone_blocks, items * sizeof(TonalBlock), hipMemcpyDeviceToHost, c->stream));
     if (residual && !out_dev) HIPCHK(c, hipMemcpyAsync(residual, c->d_tone_resid, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -617,6 +625,11 @@ int at3phip_host_tone_gates(const float* bands, int32_t n_frames, int32_t channe
         out[i] = gate;
     }
     return AT3HIP_OK;
+}
+
+uint32_t at3phip_host_tone_flags(void)
+{
+    return AT3PHIP_TONES_GATED | AT3PHIP_TONES_SHARED;
 }
 
 int at3phip_sync(at3phip_ctx* c)

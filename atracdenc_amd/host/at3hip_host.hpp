@@ -670,9 +670,11 @@ public:
 // restatement): the three change together.
 // gated: the analysis with AT3PHIP_TONES_GATED (the header's GATES, G1-G5; tests/host/at3p_gha_gate_cpu.c): onsets and offsets
 // become the blocks' envelope points.
+// shared: the analysis with AT3PHIP_TONES_SHARED (the header's SHARING, S1-S5; tests/host/at3p_gha_share_cpu.c): a band that both
+// channels hold identically is counted and written once. Nothing in a mono analyser.
 class TAt3PToneAnalyser : public IAt3PGhaProcessor {
 public:
-    explicit TAt3PToneAnalyser(int channels, bool gated = false) : Channels(channels), Gated(gated)
+    explicit TAt3PToneAnalyser(int channels, bool gated = false, bool shared = false) : Channels(channels), Gated(gated), Shared(shared && channels == 2)
     {
         if (at3phip_host_tone_find_tables(&T, sizeof(T)) != AT3HIP_OK) throw std::runtime_error("at3phip_host_tone_find_tables failed");
     }
@@ -707,15 +709,22 @@ public:
                 nw += got;
             }
         const at3phip_tonal_block older = Older, before = Block;
+        bool twin[16] = {};
+        if (Shared) {   // S2, then S3: channel 1's waves of the twin bands leave the population
+            for (int sb = 0; sb < 16; ++sb) twin[sb] = Twin(w, nw, gate[0][sb], gate[1][sb], sb);
+            nw = (int)(std::remove_if(w, w + nw, [&](const TWave& v) { return v.Ch == 1 && twin[v.Sb]; }) - w);
+        }
         Select(w, nw);
         for (int ch = 0; ch < Channels; ++ch)   // G2: the second frame's event is the block's point pair, wave or no wave
             for (int sb = 0; sb < 16; ++sb) {
                 const int g = gate[ch][sb];
-                if (!g) continue;
+                if (!g || (ch == 1 && twin[sb])) continue;   // (S4: a twin band of channel 1 stays all zero)
                 if (g < 0x80) Block.band[ch][sb].start = (uint8_t)(g + 1);
                 else Block.band[ch][sb].stop = (uint8_t)((g & 31) + 1);
                 Block.num_tone_bands = (uint8_t)std::max<int>(Block.num_tone_bands, sb + 1);
             }
+        for (int sb = 0; sb < Block.num_tone_bands; ++sb)   // S4
+            if (twin[sb]) Block.tone_sharing |= (uint16_t)(1u << sb);
         for (int ch = 0; ch < Channels; ++ch)
             for (int sb = 0; sb < 16; ++sb) Subtract(older, before, Block, ch, sb, prev[ch] + sb * 128);
         Older = before;
@@ -916,6 +925,22 @@ private:
     {
         return a.Ch != b.Ch ? a.Ch < b.Ch : a.Sb != b.Sb ? a.Sb < b.Sb : a.Freq < b.Freq;
     }
+    // S2: the words of band sb's waves are the same set in both channels, and so are the points G2 writes for the gates g0, g1
+    static bool Twin(const TWave* w, int nw, int g0, int g1, int sb)
+    {
+        auto within = [&](int a, int b) {   // every word of channel a's band is one of channel b's
+            for (int i = 0; i < nw; ++i) {
+                if (w[i].Ch != a || w[i].Sb != sb) continue;
+                bool found = false;
+                for (int j = 0; j < nw; ++j)
+                    found = found || (w[j].Ch == b && w[j].Sb == sb && AT3PHIP_TONAL_WAVE(w[j].Freq, w[j].AmpSf, w[j].Phase) == AT3PHIP_TONAL_WAVE(w[i].Freq, w[i].AmpSf, w[i].Phase));
+                if (!found) return false;
+            }
+            return true;
+        };
+        const at3phip_tonal_band e0 = GateBand(g0), e1 = GateBand(g1);
+        return within(0, 1) && within(1, 0) && e0.start == e1.start && e0.stop == e1.stop;
+    }
     // steps 6-7
     void Select(TWave* w, int nw)
     {
@@ -940,6 +965,7 @@ private:
     // out, 0 fading in
     void Waves(const at3phip_tonal_block& b, int ch, int sb, const TEnv& e, int reg, float* out) const
     {
+        ch = Src(b, ch, sb);
         int first = 0;
         for (int c = 0; c <= ch; ++c)   // channel 0's bands go first
             for (int k = 0; k < (c < ch ? 16 : sb); ++k) first += b.band[c][k].n_waves;
@@ -971,12 +997,14 @@ private:
     }
     // step 8 / G5 for one band: ApplyFilter's out -= wavreg1 + wavreg2 as ff_atrac3p_generate_tones forms them for the block
     // `now` after `before`, whose own envelope follows from `older`'s points
+    // S5: each record is resolved through its own sharing word (Src)
     void Subtract(const at3phip_tonal_block& older, const at3phip_tonal_block& before, const at3phip_tonal_block& now, int ch, int sb,
                   float* x) const
     {
-        const int n1 = before.band[ch][sb].n_waves, n2 = now.band[ch][sb].n_waves;
+        const at3phip_tonal_band &bo = older.band[Src(older, ch, sb)][sb], &bb = before.band[Src(before, ch, sb)][sb], &bn = now.band[Src(now, ch, sb)][sb];
+        const int n1 = bb.n_waves, n2 = bn.n_waves;
         if (!n1 && !n2) return;
-        const TEnv e2 = CurrEnv(now.band[ch][sb], before.band[ch][sb]), e1 = CurrEnv(before.band[ch][sb], older.band[ch][sb]);
+        const TEnv e2 = CurrEnv(bn, bb), e1 = CurrEnv(bb, bo);
         const bool reg1 = e1.E >= 32, reg2 = e2.S < 32;
         float w1[128] = {0}, w2[128] = {0};
         if (n1 && reg1) Waves(before, ch, sb, e1, 128, w1);
@@ -989,8 +1017,10 @@ private:
             x[i] -= w1[i] + w2[i];
         }
     }
+    // the channel whose band sb a record's channel ch uses: channel 0's where the record shares the band
+    static int Src(const at3phip_tonal_block& b, int ch, int sb) { return ch == 1 && ((b.tone_sharing >> sb) & 1) ? 0 : ch; }
     const int Channels;
-    const bool Gated;
+    const bool Gated, Shared;
     TTables T;
     at3phip_tonal_block Block{};   // the last block found
     at3phip_tonal_block Older{};   // and the one before it: its points decide the last block's envelope
@@ -1001,13 +1031,15 @@ public:
     // deviceTones: the tone analysis on the GPU (at3phip_encode_frames_tonal, a batch per call) instead of an analyser on the
     // host: byte for byte the frames of this class around TAt3PToneAnalyser with UseGha = GHA_ENABLED. `gha` must then be null.
     // deviceGated: that analysis with AT3PHIP_TONES_GATED, byte for byte TAt3PToneAnalyser(channels, true)'s frames.
+    // deviceShared: with AT3PHIP_TONES_SHARED, byte for byte TAt3PToneAnalyser(channels, deviceGated, true)'s frames.
     TAt3PEncoder(TCompressedOutputPtr&& out, int channels, int batchFrames = 64, int deviceId = 0, TAt3PSettings settings = TAt3PSettings(),
-                 IAt3PGhaProcessor* gha = nullptr, bool deviceTones = false, bool deviceGated = false)
+                 IAt3PGhaProcessor* gha = nullptr, bool deviceTones = false, bool deviceGated = false, bool deviceShared = false)
         : Out(std::move(out)), Channels((size_t)channels), BatchFrames(batchFrames), FrameFloats((size_t)AT3PHIP_FRAME * (size_t)channels),
-          Settings(settings), Gha(gha), DeviceTones(deviceTones), ToneFlags(deviceGated ? AT3PHIP_TONES_GATED : 0u)
+          Settings(settings), Gha(gha), DeviceTones(deviceTones), ToneFlags((deviceGated ? AT3PHIP_TONES_GATED : 0u) | (deviceShared ? AT3PHIP_TONES_SHARED : 0u))
     {
         if (deviceTones && gha) throw std::invalid_argument("TAt3PEncoder: deviceTones takes no host analyser");
         if (deviceGated && !deviceTones) throw std::invalid_argument("TAt3PEncoder: deviceGated needs deviceTones");
+        if (deviceShared && !deviceTones) throw std::invalid_argument("TAt3PEncoder: deviceShared needs deviceTones");
         at3phip_config cfg{};
         cfg.channels = channels;
         cfg.n_streams = 1;
@@ -1164,7 +1196,7 @@ private:
     const TAt3PSettings Settings;
     IAt3PGhaProcessor* const Gha;                 // not owned; null: the analysis finds nothing
     const bool DeviceTones;                       // the analysis runs on the GPU
-    const uint32_t ToneFlags;                     // and with these flags (AT3PHIP_TONES_GATED)
+    const uint32_t ToneFlags;                     // and with these flags (AT3PHIP_TONES_GATED, AT3PHIP_TONES_SHARED)
     std::vector<float> PrevBuf, CurBuf, RawCur;   // [C][16][128] / [C][2048]: TChannelCtx's PrevBuf, CurBuf and RawCurBuf
     at3phip_tonal_block Delay{};                  // `delay`: the block the next call writes
 };

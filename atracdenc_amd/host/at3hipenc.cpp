@@ -7,7 +7,7 @@
 //             [--nogaincontrol] [--container oma|riff|raw] [--nostdout] [--batch blocks] [--device n]
 //   at3hipenc -e atrac1 -i in.wav -o out.{aea|raw|dat} [--bfuidxconst 1..8] [--notransient[=mask]]
 //             [--container aea|raw] [--nostdout] [--batch blocks] [--device n]
-//   at3hipenc -e atrac3plus -i in.wav -o out.{oma|at3|wav|raw|dat} [--tones [--gate]] [--container oma|riff|raw] [--nostdout]
+//   at3hipenc -e atrac3plus -i in.wav -o out.{oma|at3|wav|raw|dat} [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout]
 //             [--batch frames] [--device n]
 //   --resample (all three encoders): a WAV at 8 .. 192 kHz (at3hip_resample.h's list) is converted to 44.1 kHz on the GPU
 //             first; the container headers count ceil(N 44100 / rate) samples. A 44.1 kHz input is encoded as without it.
@@ -225,7 +225,7 @@ private:
 struct TOptions {
     std::string inFile, outFile, codec, container, rateArg;
     uint32_t bitrate = 0, bfuIdxConst = 0, winMask = 0;
-    bool tones = false, gate = false, noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false, resample = false, measure = false, peakGiven = false;
+    bool tones = false, gate = false, share = false, noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false, resample = false, measure = false, peakGiven = false;
     int batch = 256, device = 0, rate = 0;
     TLevel level;
 };
@@ -659,8 +659,8 @@ struct TAtrac3PlusEncode {
     }
     std::string CodecLines() const { return "ATRAC3Plus"; }
     TAt3PEncoder Encoder(TCompressedOutputPtr&& out, const TOptions& o)
-    {   // --tones: the tone analysis of at3phip_encode_frames_tonal (--gate: with AT3PHIP_TONES_GATED); the frame count is the plain encode's
-        return TAt3PEncoder(std::move(out), (int)Channels, o.batch > 64 ? 64 : o.batch, o.device, TAt3PSettings(), nullptr, o.tones, o.gate);
+    {   // --tones: the tone analysis of at3phip_encode_frames_tonal (--gate: with AT3PHIP_TONES_GATED, --share: with AT3PHIP_TONES_SHARED); the frame count is the plain encode's
+        return TAt3PEncoder(std::move(out), (int)Channels, o.batch > 64 ? 64 : o.batch, o.device, TAt3PSettings(), nullptr, o.tones, o.gate, o.share);
     }
     void Report(TAt3PEncoder&, const TOptions&) const {}
 };
@@ -706,9 +706,10 @@ static int usage()
                  "                 [--container oma|riff|raw] [--nostdout] [--batch blocks] [--device n]\n"
                  "       at3hipenc -e atrac1 -i in.wav -o out.aea [--bfuidxconst 1..8] [--notransient[=mask]]\n"
                  "                 [--container aea|raw] [--nostdout] [--batch blocks] [--device n]\n"
-                 "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--tones [--gate]] [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
+                 "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
                  "                 (--tones: find sine waves on the GPU and write them as tonal blocks; --gate: with envelope points at\n"
-                 "                  their onsets and offsets)\n"
+                 "                  their onsets and offsets; --share: a band that both channels of a stereo input hold identically is\n"
+                 "                  written once)\n"
                  "       (every encoder: --resample converts an input at 8 .. 192 kHz to 44.1 kHz first)\n"
                  "       (every encoder: --loudness LUFS [--peak dBFS] [--truepeak] brings the input to a programme loudness first;\n"
                  "        with --limit the gain reaches the target and a look-ahead limiter holds the peak)\n"
@@ -740,6 +741,7 @@ int main(int argc, char** argv)
         else if (a == "--notonal") o.noTonal = true;
         else if (a == "--tones") o.tones = true;
         else if (a == "--gate") o.gate = true;
+        else if (a == "--share") o.share = true;
         else if (a == "--nogaincontrol") o.noGain = true;
         else if (a == "--nostdout") o.noStdOut = true;
         else if (a == "--resample") o.resample = true;
@@ -805,7 +807,7 @@ int main(int argc, char** argv)
     }
     if ((o.codec != "atrac3" && o.codec != "atrac1" && o.codec != "atrac3plus") || o.inFile.empty() || o.outFile.empty() || o.rate) return usage();
     if (!o.level.On && (o.peakGiven || o.level.TruePeak || o.level.Limit)) return usage();   // --peak, --truepeak and --limit belong to --loudness (--truepeak also to --measure)
-    if (o.gate && !o.tones) return usage();                   // the gates are the tone analysis'
+    if ((o.gate || o.share) && !o.tones) return usage();      // the gates and the sharing are the tone analysis'
     if (o.tones && o.codec != "atrac3plus") return usage();   // the tone analysis is ATRAC3plus'
     if (o.codec == "atrac3plus") return encode<TAtrac3PlusEncode>(o);
     if (o.codec == "atrac1") return encode<TAtrac1Encode>(o);

@@ -410,7 +410,8 @@ int at3hip_decoder_set_stream(at3hip_decoder* dec, void* hip_stream);
  *        and, added later under the same number, the ATRAC3plus frame writer with tonal blocks: at3phip_write_frames_tonal and
  *        at3phip_tonal_block (at3phip.h), detected by the symbol
  *        and, added later under the same number, the ATRAC3plus tone analysis (at3phip.h, FINDING TONES): at3phip_analyse_tones,
- *        at3phip_encode_frames_tonal, at3phip_encode_frames_tonal_short, at3phip_host_tone_find_tables; each detected by its symbol
+ *        at3phip_encode_frames_tonal, at3phip_encode_frames_tonal_short, at3phip_host_tone_find_tables; each detected by its symbol; its flags AT3PHIP_TONES_GATED and AT3PHIP_TONES_SHARED by the
+ *        symbols at3phip_host_tone_gates and at3phip_host_tone_flags
  *        and, added later under the same number, the look-ahead limiter on the meter's context (at3hip_loudness.h):
  *        at3hip_loudness_limit_start(), at3hip_loudness_limit(), at3hip_loudness_limit_s16(), at3hip_loudness_limit_flush(),
  *        at3hip_loudness_limit_stats(), at3hip_loudness_limit_delay() (detected by the symbol at3hip_loudness_limit_start)

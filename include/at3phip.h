@@ -180,7 +180,7 @@ int at3phip_encode_frames_short(at3phip_ctx* ctx, const int16_t* pcm, int32_t n_
  *      (zeros, frame 0) like any other.
  * The constants are those of the prototype whose round-trip figures DESIGN.md section 17 lists; changing one changes the
  * definition. Against that prototype the definition admits the end bins in step 3 and normalises by rs and rc instead of 1 / 64
- * in steps 4 and 5: both only matter next to frequency index 0 or 1024, and the round-trip figures stay within 0.5 dB of it. Out of this definition: envelope points, sharing and the leader flag, any psychoacoustic veto.
+ * in steps 4 and 5: both only matter next to frequency index 0 or 1024, and the round-trip figures stay within 0.5 dB of it. Out of steps 1-9: envelope points (GATES below add them), sharing (SHARING below adds it), the leader flag, any psychoacoustic veto.
  *
  * GATES (AT3PHIP_TONES_GATED in `flags`; without the flag steps 1-9 stand as written and no output changes a byte). A block
  * describes its sines over two whole frames; a sine that starts or stops inside one of them is gated with the block's envelope
@@ -224,7 +224,34 @@ int at3phip_encode_frames_short(at3phip_ctx* ctx, const int16_t* pcm, int32_t n_
  *      over 4 samples; the analysis weighs with Hann times gate regardless. The mismatch costs efficiency, never correctness:
  *  G5. Step 8 subtracts exactly what the decoder's step 4b adds for these records, envelopes included (one device function,
  *      decp_waves, serves both).
- * The state carried per stream gains the block before the last one (its points decide the last block's envelope). */
+ * The state carried per stream gains the block before the last one (its points decide the last block's envelope).
+ *
+ * SHARING (AT3PHIP_TONES_SHARED in `flags`, alone or with AT3PHIP_TONES_GATED; without the flag everything above stands as written
+ * and no output changes a byte). A frame holds at most 48 waves for both channels together, and a wave that both channels hold
+ * identically counts against that budget twice and is written twice; the syntax lets channel 1 take a band from channel 0
+ * (tone_sharing), which the writer and the decoder already carry. The reference's analysis shares as well (at3p_gha.cpp,
+ * FillFolowerRes), by frequency alone, which changes what the follower decodes; here a band is shared only when nothing changes:
+ *  S1. Scope: stereo contexts. In a mono context the flag is accepted and changes nothing.
+ *  S2. Twin bands, decided on the output of step 5 (with gates: of G1-G4), before the frame budget. For channel c and band b let
+ *      W_c(b) be the set of the band's kept waves as their packed words, AT3PHIP_TONAL_WAVE(FreqIndex, AmpSf, PhaseIndex), and
+ *      E_c(b) the band's point pair (start, stop) as G2 writes it, (0, 0) without gates. Band b is a twin when W_0(b) = W_1(b) as
+ *      sets (the candidates of step 3 are ordered by power, which may differ between the channels where the words do not) and
+ *      E_0(b) = E_1(b). Two bands without a wave and with equal points are twins.
+ *  S3. Budget: step 6 ranks channel 0's kept waves of every band and channel 1's kept waves of the bands that are not twins, in
+ *      the order it has (A2 descending, then channel, band, frequency index); the first 48 stay. A twin band of channel 1 has
+ *      whatever channel 0's band keeps after the cut.
+ *  S4. Record: tone_sharing bit b = twin(b) for b < num_tone_bands and 0 above; band[1][b] of a twin band is all zero (no count,
+ *      no point) and contributes no entry to wave[]; second_is_leader stays 0; num_tone_bands is the highest band holding a wave
+ *      or a point, plus 1, as before. Whether a band is a twin is not looked at again after the cut.
+ *  S5. Residual (step 8 / G5): in a twin band channel 1 subtracts channel 0's waves under channel 0's envelope, which is what the
+ *      decoder adds after copying the band. Each of the three records a slot touches - this slot's, the one before, and the one
+ *      before that, whose points decide the older envelope - is resolved through its own tone_sharing. The carried state is the
+ *      same records as before, so any split into calls gives the same bytes.
+ * Consequence: twin bands hold equal words and equal points, so where the budget does not bind (the frame's waves, counted as in
+ * step 6, are at most 48) the records with and without the flag describe the same synthesis in both channels and the residuals
+ * are equal bit for bit; the flag then changes nothing but the tonal block's bits (and, through them, the quant units a loud
+ * frame keeps). Where the budget binds, the waves it no longer counts twice go to the next strongest.
+ * Out of this definition: the leader flag (with equal twins it buys nothing), phase-inverted and near-match sharing. */
 #define AT3PHIP_TONE_PEAK_RATIO 16.0      /* step 3: a candidate's power over the mean power */
 #define AT3PHIP_TONE_MAX_BAND_WAVES 3     /* step 3: candidates per channel and subband */
 #define AT3PHIP_TONE_FINE_SPAN 7          /* step 4: frequency indices searched on either side of 8 k */
@@ -234,6 +261,9 @@ int at3phip_encode_frames_short(at3phip_ctx* ctx, const int16_t* pcm, int32_t n_
 /* flag of at3phip_analyse_tones, at3phip_encode_frames_tonal and at3phip_encode_frames_tonal_short: the analysis with GATES. A
  * stream stays with one mode between resets. Still ABI 1.6: a host that needs it looks for the symbol at3phip_host_tone_gates. */
 #define AT3PHIP_TONES_GATED 32u
+/* flag of the same three calls: the analysis with SHARING; may be combined with AT3PHIP_TONES_GATED. A stream stays with one mode
+ * between resets. Still ABI 1.6: a host that needs it asks at3phip_host_tone_flags. */
+#define AT3PHIP_TONES_SHARED 64u
 
 /* Steps 1-8 on caller-supplied subband samples: the stage tap of at3phip_encode_frames_tonal.
  *   bands     [n_streams][n_frames][channels][16][128] float32 as at3phip_pqf_analyse writes them (flags & AT3HIP_PCM_ON_DEVICE:
@@ -273,6 +303,10 @@ int at3phip_host_tone_find_tables(void* dst, size_t bytes);
  * each frame's gate as G1 codes it (0 = none, 1..31 = onset at s, 0x80 | p = offset with last active cell p). A library that has
  * this symbol takes AT3PHIP_TONES_GATED. */
 int at3phip_host_tone_gates(const float* bands, int32_t n_frames, int32_t channels, uint8_t* out);
+
+/* The analysis flags this library understands, as a mask (no GPU needed): AT3PHIP_TONES_GATED | AT3PHIP_TONES_SHARED. A library
+ * without this symbol predates AT3PHIP_TONES_SHARED. */
+uint32_t at3phip_host_tone_flags(void);
 
 /* With AT3HIP_ASYNC in `flags` at3phip_encode_frames only queues the call (pcm must stay valid, frames must not be read)
  * and the frame writer of one call runs beside the filter bank and transform of the next (its own stream, spectra
