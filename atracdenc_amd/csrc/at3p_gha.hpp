@@ -14,8 +14,8 @@
 // channel 1's waves of those bands out of the budget and writes the sharing word; k_at3p_tone_sub<., true> resolves channel 1's
 // band through each record's own sharing word. The <false> instances are the kernels without any of it; k_at3p_tone_find and
 // k_at3p_tone_state are the same for both (the carried records hold their sharing words).
-// The analysis is written out three times and the three change together: here, in the C restatement tests/host/at3p_gha_cpu.c
-// and in the host mirror's TAt3PToneAnalyser (atracdenc_amd/host/at3hip_host.hpp); the table builder is build_tone_find_tables.
+// These kernels and the host mirror's TAt3PToneAnalyser (atracdenc_amd/host/at3hip_host.hpp) are each pinned bit for bit to one C
+// restatement, tests/host/at3p_gha_cpu.c: a change to the definition changes all three. The table builder is build_tone_find_tables.
 #pragma once
 #include "at3p_kernels.hpp"
 #include "at3p_write.hpp"

@@ -666,12 +666,13 @@ public:
 // block it returns is written with the previous buffer's spectrum one call later, so it analyses the pair (previous as passed in,
 // current), ignores next, and subtracts from the previous buffer: this block fading in, the block of the call before fading out.
 // Every sum runs in the header's order; compile without floating-point contraction (no FMA), like the kernels.
-// The same analysis is written out in atracdenc_amd/csrc/at3p_gha.hpp (the kernels) and tests/host/at3p_gha_cpu.c (the C
-// restatement): the three change together.
-// gated: the analysis with AT3PHIP_TONES_GATED (the header's GATES, G1-G5; tests/host/at3p_gha_gate_cpu.c): onsets and offsets
-// become the blocks' envelope points.
-// shared: the analysis with AT3PHIP_TONES_SHARED (the header's SHARING, S1-S5; tests/host/at3p_gha_share_cpu.c): a band that both
-// channels hold identically is counted and written once. Nothing in a mono analyser.
+// The same analysis is written out in atracdenc_amd/csrc/at3p_gha.hpp (the kernels); both are pinned bit for bit to one C
+// restatement, tests/host/at3p_gha_cpu.c, and a change to the definition changes all of them.
+// gated: the analysis with AT3PHIP_TONES_GATED (the header's GATES, G1-G5): onsets and offsets become the blocks' envelope
+// points. G1 itself is the library's at3phip_host_tone_gates, which is compiled without contraction whatever this header's user
+// compiles with.
+// shared: the analysis with AT3PHIP_TONES_SHARED (the header's SHARING, S1-S5): a band that both channels hold identically is
+// counted and written once. Nothing in a mono analyser.
 class TAt3PToneAnalyser : public IAt3PGhaProcessor {
 public:
     explicit TAt3PToneAnalyser(int channels, bool gated = false, bool shared = false) : Channels(channels), Gated(gated), Shared(shared && channels == 2)
@@ -683,23 +684,23 @@ public:
         const float* cur[2] = {b1[0], b2[0]};
         float* prev[2] = {w1, w2};
         TWave w[2 * 16 * AT3PHIP_TONE_MAX_BAND_WAVES];
-        int nw = 0, gate[2][16] = {};
+        int nw = 0;
+        uint8_t gatePrev[2][16] = {}, gateCur[2][16] = {};   // G1 for both frames, before anything is subtracted from the previous one
+        for (int ch = 0; Gated && ch < Channels; ++ch)
+            if (at3phip_host_tone_gates(prev[ch], 1, 1, gatePrev[ch]) != AT3HIP_OK || at3phip_host_tone_gates(cur[ch], 1, 1, gateCur[ch]) != AT3HIP_OK)
+                throw std::runtime_error("at3phip_host_tone_gates failed");
         for (int ch = 0; ch < Channels; ++ch)
             for (int sb = 0; sb < 16; ++sb) {
                 float x[256];
                 std::copy(prev[ch] + sb * 128, prev[ch] + sb * 128 + 128, x);
                 std::copy(cur[ch] + sb * 128, cur[ch] + sb * 128 + 128, x + 128);
+                const int g0 = gatePrev[ch][sb], g1 = gateCur[ch][sb];
                 int lo = 0, hi = 63;
-                bool event = false;
-                if (Gated) {   // G1 for both frames, G3
-                    const int g0 = Gate(x), g1 = Gate(x + 128);
-                    gate[ch][sb] = g1;
-                    if (g0 | g1) {
-                        const TEnv e = CurrEnv(GateBand(g1), GateBand(g0));
-                        event = true;
-                        lo = e.Hs ? e.S : 0;
-                        hi = e.He ? e.E : 63;
-                    }
+                const bool event = (g0 | g1) != 0;
+                if (event) {   // G3
+                    const TEnv e = CurrEnv(GateBand(g1), GateBand(g0));
+                    lo = e.Hs ? e.S : 0;
+                    hi = e.He ? e.E : 63;
                 }
                 const int got = FindBand(x, w + nw, event, lo, hi);
                 for (int i = 0; i < got; ++i) {
@@ -711,13 +712,13 @@ public:
         const at3phip_tonal_block older = Older, before = Block;
         bool twin[16] = {};
         if (Shared) {   // S2, then S3: channel 1's waves of the twin bands leave the population
-            for (int sb = 0; sb < 16; ++sb) twin[sb] = Twin(w, nw, gate[0][sb], gate[1][sb], sb);
+            for (int sb = 0; sb < 16; ++sb) twin[sb] = Twin(w, nw, gateCur[0][sb], gateCur[1][sb], sb);
             nw = (int)(std::remove_if(w, w + nw, [&](const TWave& v) { return v.Ch == 1 && twin[v.Sb]; }) - w);
         }
         Select(w, nw);
         for (int ch = 0; ch < Channels; ++ch)   // G2: the second frame's event is the block's point pair, wave or no wave
             for (int sb = 0; sb < 16; ++sb) {
-                const int g = gate[ch][sb];
+                const int g = gateCur[ch][sb];
                 if (!g || (ch == 1 && twin[sb])) continue;   // (S4: a twin band of channel 1 stays all zero)
                 if (g < 0x80) Block.band[ch][sb].start = (uint8_t)(g + 1);
                 else Block.band[ch][sb].stop = (uint8_t)((g & 31) + 1);
@@ -769,39 +770,6 @@ private:
         if (g > 0 && g < 0x80) b.start = (uint8_t)(g + 1);
         if (g >= 0x80) b.stop = (uint8_t)((g & 31) + 1);
         return b;
-    }
-    // G1: one frame's gate for one subband
-    static int Gate(const float* x)
-    {
-        double P[33], e[32];
-        P[0] = 0.0;
-        for (int j = 0; j < 32; ++j) {
-            float v = x[4 * j] * x[4 * j];
-            v = v + x[4 * j + 1] * x[4 * j + 1];
-            v = v + x[4 * j + 2] * x[4 * j + 2];
-            v = v + x[4 * j + 3] * x[4 * j + 3];
-            e[j] = (double)v;
-            P[j + 1] = P[j] + e[j];
-        }
-        int bs = 0;
-        double bd = 0, before = 0, after = 0;
-        for (int s = AT3PHIP_TONE_GATE_MIN; s <= 32 - AT3PHIP_TONE_GATE_MIN; ++s) {
-            const double b = P[s] / (double)s, a = (P[32] - P[s]) / (double)(32 - s);
-            const double d = std::fabs(a - b);
-            if (bs == 0 || d > bd) bs = s, bd = d, before = b, after = a;
-        }
-        // the loud side holds at least MIN loud cells next to the split: each over R times the quiet side's mean, and not zero
-        if (after >= AT3PHIP_TONE_GATE_RATIO * before && after > 0.0) {
-            for (int j = bs; j < bs + AT3PHIP_TONE_GATE_MIN; ++j)
-                if (!(e[j] >= AT3PHIP_TONE_GATE_RATIO * before && e[j] > 0.0)) return 0;
-            return bs;
-        }
-        if (before >= AT3PHIP_TONE_GATE_RATIO * after && before > 0.0) {
-            for (int j = bs - AT3PHIP_TONE_GATE_MIN; j < bs; ++j)
-                if (!(e[j] >= AT3PHIP_TONE_GATE_RATIO * after && e[j] > 0.0)) return 0;
-            return 0x80 | (bs - 1);
-        }
-        return 0;
     }
     // the kissfft-order forward FFT for n = 4^k (kf_work and kf_bfly4, kiss_fft.c:42-90, 238-302)
     void Fft(TCpx* out, const TCpx* in, int n, int fstride) const

@@ -301,7 +301,8 @@ int at3phip_host_tone_find_tables(void* dst, size_t bytes);
 
 /* G1 on the host (no GPU needed): bands [n_frames][channels][16][128] float32 of one stream, out [n_frames][channels][16] bytes,
  * each frame's gate as G1 codes it (0 = none, 1..31 = onset at s, 0x80 | p = offset with last active cell p). A library that has
- * this symbol takes AT3PHIP_TONES_GATED. */
+ * this symbol takes AT3PHIP_TONES_GATED. The host mirror's TAt3PToneAnalyser (atracdenc_amd/host/at3hip_host.hpp) gates through
+ * this function, as it takes its tables from the one above; it is pinned to the restatement tests/host/at3p_gha_cpu.c. */
 int at3phip_host_tone_gates(const float* bands, int32_t n_frames, int32_t channels, uint8_t* out);
 
 /* The analysis flags this library understands, as a mask (no GPU needed): AT3PHIP_TONES_GATED | AT3PHIP_TONES_SHARED. A library

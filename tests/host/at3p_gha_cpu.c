@@ -1,9 +1,16 @@
-/* TEST INFRASTRUCTURE ONLY - a C restatement of the ATRAC3plus tone analysis defined in include/at3phip.h (FINDING TONES, steps
- * 1-8): one stream, frame after frame. The residual of step 8 is at3pt_apply_filter's generate_tones (at3p_tonal_cpu.c, included
- * here) fed with the records this file finds. The same analysis is written out in atracdenc_amd/csrc/at3p_gha.hpp (the kernels)
- * and in TAt3PToneAnalyser (atracdenc_amd/host/at3hip_host.hpp): the three change together. Compiled by the tests with gcc -O2 -fPIC -ffp-contract=off -fno-fast-math. */
+/* TEST INFRASTRUCTURE ONLY - the C restatement of the ATRAC3plus tone analysis defined in include/at3phip.h (FINDING TONES: steps
+ * 1-8, the GATES G1-G5 and the SHARING S1-S5): one stream, frame after frame, under any combination of AT3PHIP_TONES_GATED and
+ * AT3PHIP_TONES_SHARED. The interval of G3 is the curr_env that generate_tones (at3p_tonal_cpu.c, included here) reconstructs,
+ * read back from that function; the residual of steps 8, G5 and S5 is the same function fed with the records this file finds,
+ * points included, after the decoder's own copy of channel 0's shared bands. The analysis is written out in two more places,
+ * atracdenc_amd/csrc/at3p_gha.hpp (the kernels) and TAt3PToneAnalyser (the host mirror, atracdenc_amd/host/at3hip_host.hpp),
+ * and both are pinned to this file. Compiled by the tests with gcc -O2 -fPIC -ffp-contract=off -fno-fast-math. */
 #include "at3p_tonal_cpu.c"
 #include "../../include/at3phip.h"
+
+#ifndef AT3PG_GATE_RATIO   /* (the measurement that chose R compiles this file with the other candidates) */
+#define AT3PG_GATE_RATIO AT3PHIP_TONE_GATE_RATIO
+#endif
 
 typedef struct { float r, i; } gcpx;
 
@@ -77,13 +84,78 @@ static void gfft(gcpx* out, const gcpx* in, int n, int fstride)
 
 typedef struct { int valid, ch, sb, freq, amp_sf, phase; double a2; } gwave;
 
-/* steps 1-5 for one subband: x = 256 samples; at most AT3PHIP_TONE_MAX_BAND_WAVES waves, by descending coarse power */
-static int find_band(const float* x, gwave* out)
+/* G1 for one subband of one frame: 0 = none, 1..31 = onset at s, 0x80 | p = offset with last active cell p */
+static int gate_band(const float* x)
 {
-    float y[256], P[129];
+    float e[32];
+    double P[33];
+    for (int j = 0; j < 32; ++j) {
+        float v = x[4 * j] * x[4 * j];
+        v = v + x[4 * j + 1] * x[4 * j + 1];
+        v = v + x[4 * j + 2] * x[4 * j + 2];
+        v = v + x[4 * j + 3] * x[4 * j + 3];
+        e[j] = v;
+    }
+    P[0] = 0.0;
+    for (int j = 0; j < 32; ++j) P[j + 1] = P[j] + (double)e[j];
+    int bs = 0;
+    double bd = 0, bb = 0, ba = 0;
+    for (int s = AT3PHIP_TONE_GATE_MIN; s <= 32 - AT3PHIP_TONE_GATE_MIN; ++s) {
+        const double before = P[s] / (double)s, after = (P[32] - P[s]) / (double)(32 - s);
+        const double d = fabs(after - before);
+        if (bs == 0 || d > bd) { bs = s; bd = d; bb = before; ba = after; }
+    }
+    /* the loud side holds at least MIN loud cells next to the split: each over R times the quiet side's mean, and not zero */
+    if (ba >= (double)AT3PG_GATE_RATIO * bb && ba > 0.0) {
+        for (int j = bs; j < bs + AT3PHIP_TONE_GATE_MIN; ++j)
+            if (!((double)e[j] >= (double)AT3PG_GATE_RATIO * bb && (double)e[j] > 0.0)) return 0;
+        return bs;
+    }
+    if (bb >= (double)AT3PG_GATE_RATIO * ba && bb > 0.0) {
+        for (int j = bs - AT3PHIP_TONE_GATE_MIN; j < bs; ++j)
+            if (!((double)e[j] >= (double)AT3PG_GATE_RATIO * ba && (double)e[j] > 0.0)) return 0;
+        return 0x80 | (bs - 1);
+    }
+    return 0;
+}
+
+static void gate_to_pend(int g, tenv* e)
+{
+    e->has_start = g > 0 && g < 0x80;
+    e->start = e->has_start ? g : -1;
+    e->has_stop = g >= 0x80;
+    e->stop = e->has_stop ? (g & 31) : 32;
+}
+
+/* G3: the cells [lo, hi] of the block whose first frame has gate g0 and whose second frame has gate g1: the curr_env
+ * generate_tones reconstructs for a record with g1's points after a record with g0's */
+static void gate_interval(int g0, int g1, int* lo, int* hi)
+{
+    static trec prev, cur;   /* no waves: the function only reconstructs the envelope */
+    float scratch[128] = {0};
+    memset(&prev, 0, sizeof(prev));
+    memset(&cur, 0, sizeof(cur));
+    gate_to_pend(g0, &prev.band[0][0].pend);
+    gate_to_pend(g1, &cur.band[0][0].pend);
+    generate_tones(&prev, &cur, 0, 0, scratch, 1);
+    const tenv* c = &cur.band[0][0].curr;
+    *lo = c->has_start ? c->start : 0;
+    *hi = c->has_stop ? c->stop : 63;
+}
+
+/* steps 1-5 for one subband: x = 256 samples; at most AT3PHIP_TONE_MAX_BAND_WAVES waves, by descending coarse power. A band
+ * without an event is analysed under the whole Hann window, each projection normalised on its own (rs, rc). A band with one
+ * (G4) is analysed under hann[t] inside the cells [lo, hi] and +0.0f outside, where sine and cosine are no longer orthogonal:
+ * the fit solves the 2 x 2 normal equations under that window. */
+static int find_band(const float* x, int event, int lo, int hi, gwave* out)
+{
+    if (event && hi - lo + 1 < AT3PHIP_TONE_GATE_MIN) return 0;
+    const int t0 = event ? 4 * lo : 0, t1 = event ? 4 * hi + 3 : 255;
+    float y[256], wnd[256], P[129];
     gcpx in[256], F[256];
     for (int t = 0; t < 256; ++t) {
-        y[t] = x[t] * TT.hann[t];
+        wnd[t] = t >= t0 && t <= t1 ? TT.hann[t] : 0.0f;
+        y[t] = x[t] * wnd[t];
         in[t].r = y[t];
         in[t].i = 0.0f;
     }
@@ -106,22 +178,39 @@ static int find_band(const float* x, gwave* out)
     }
     int n = 0;
     for (int c = 0; c < nc; ++c) {
-        const int lo = 8 * ck[c] - AT3PHIP_TONE_FINE_SPAN < 1 ? 1 : 8 * ck[c] - AT3PHIP_TONE_FINE_SPAN;
-        const int hi = 8 * ck[c] + AT3PHIP_TONE_FINE_SPAN > 1023 ? 1023 : 8 * ck[c] + AT3PHIP_TONE_FINE_SPAN;
+        const int flo = 8 * ck[c] - AT3PHIP_TONE_FINE_SPAN < 1 ? 1 : 8 * ck[c] - AT3PHIP_TONE_FINE_SPAN;
+        const int fhi = 8 * ck[c] + AT3PHIP_TONE_FINE_SPAN > 1023 ? 1023 : 8 * ck[c] + AT3PHIP_TONE_FINE_SPAN;
         int bf = -1;
-        double bs = 0, bc = 0, bp = 0;
-        for (int f = lo; f <= hi; ++f) {
-            double S = 0, C = 0;
+        double ca = 0, cb = 0, bp = 0;   /* x[t] = ca sin + cb cos, by least squares under the window, at the best f */
+        for (int f = flo; f <= fhi; ++f) {
+            double S = 0, C = 0, a, b, pw;
             for (int t = 0; t < 256; ++t) {
                 const int pos = ((t - 128) * f) & 2047;
                 S = S + (double)y[t] * (double)TT.sine[pos];
                 C = C + (double)y[t] * (double)TT.sine[(pos + 512) & 2047];
             }
-            const double pw = (S * S) * GT.rs[f] + (C * C) * GT.rc[f];
-            if (bf < 0 || pw > bp) { bf = f; bs = S; bc = C; bp = pw; }
+            if (event) {
+                double Gss = 0, Gcc = 0, Gsc = 0;
+                for (int t = t0; t <= t1; ++t) {
+                    const int pos = ((t - 128) * f) & 2047;
+                    const double sn = (double)TT.sine[pos], cs = (double)TT.sine[(pos + 512) & 2047];
+                    Gss = Gss + (double)wnd[t] * (sn * sn);
+                    Gcc = Gcc + (double)wnd[t] * (cs * cs);
+                    Gsc = Gsc + (double)wnd[t] * (sn * cs);
+                }
+                const double det = Gss * Gcc - Gsc * Gsc;
+                if (!(det > 0.0)) continue;
+                a = (S * Gcc - C * Gsc) / det;
+                b = (C * Gss - S * Gsc) / det;
+                pw = a * S + b * C;
+            } else {
+                a = S * GT.rs[f];
+                b = C * GT.rc[f];
+                pw = (S * S) * GT.rs[f] + (C * C) * GT.rc[f];
+            }
+            if (bf < 0 || pw > bp) { bf = f; ca = a; cb = b; bp = pw; }
         }
         if (bf < 0) continue;
-        const double ca = bs * GT.rs[bf], cb = bc * GT.rc[bf];   /* x[t] = ca sin + cb cos, by least squares under the window */
         const double a2 = ca * ca + cb * cb;
         if (!(a2 >= (double)AT3PHIP_TONE_MIN_AMP * (double)AT3PHIP_TONE_MIN_AMP)) continue;
         int sf = 0;
@@ -167,6 +256,35 @@ static void select_waves(gwave* w, int nw, at3phip_tonal_block* blk)
     }
 }
 
+/* W_c(b): the packed words of channel ch's waves in band sb */
+static int band_words(const gwave* w, int nw, int ch, int sb, uint32_t* out)
+{
+    int n = 0;
+    for (int i = 0; i < nw; ++i)
+        if (w[i].ch == ch && w[i].sb == sb) out[n++] = AT3PHIP_TONAL_WAVE(w[i].freq, w[i].amp_sf, w[i].phase);
+    return n;
+}
+
+static int words_within(const uint32_t* a, int na, const uint32_t* b, int nb)
+{
+    for (int i = 0; i < na; ++i) {
+        int found = 0;
+        for (int j = 0; j < nb; ++j) found |= a[i] == b[j];
+        if (!found) return 0;
+    }
+    return 1;
+}
+
+/* S2: W_0(b) = W_1(b) as sets and E_0(b) = E_1(b); a gate byte stands for exactly one point pair of G2, so the bytes compare */
+static int twin_band(const gwave* w, int nw, int g0, int g1, int sb)
+{
+    uint32_t a[AT3PHIP_TONE_MAX_BAND_WAVES], b[AT3PHIP_TONE_MAX_BAND_WAVES];
+    const int na = band_words(w, nw, 0, sb, a), nb = band_words(w, nw, 1, sb, b);
+    return words_within(a, na, b, nb) && words_within(b, nb, a, na) && g0 == g1;
+}
+
+/* the record as the decoder holds it (parse_tonal): the waves, the points in its "-1 / 32 when absent" form, and a shared band of
+ * channel 1 being channel 0's */
 static void block_to_trec(const at3phip_tonal_block* b, trec* r)
 {
     memset(r, 0, sizeof(*r));
@@ -174,17 +292,22 @@ static void block_to_trec(const at3phip_tonal_block* b, trec* r)
     int at = 0;
     for (int ch = 0; ch < 2; ++ch)
         for (int sb = 0; sb < 16; ++sb) {
+            const at3phip_tonal_band* bd = &b->band[ch][sb];
             tband* t = &r->band[ch][sb];
-            t->nw = b->band[ch][sb].n_waves;
+            t->nw = bd->n_waves;
             t->start_index = at;
-            t->pend.start = -1;
-            t->pend.stop = 32;
+            t->pend.has_start = bd->start != 0;
+            t->pend.start = (int)bd->start - 1;
+            t->pend.has_stop = bd->stop != 0;
+            t->pend.stop = bd->stop ? (int)bd->stop - 1 : 32;
             for (int i = 0; i < t->nw; ++i, ++at) {
                 r->freq[at] = (int)(b->wave[at] & 1023u);
                 r->amp_sf[at] = (int)((b->wave[at] >> 10) & 63u);
                 r->phase[at] = (int)((b->wave[at] >> 16) & 31u);
             }
         }
+    for (int sb = 0; sb < b->num_tone_bands && sb < 16; ++sb)
+        if ((b->tone_sharing >> sb) & 1) r->band[1][sb] = r->band[0][sb];
 }
 
 typedef struct {
@@ -200,26 +323,59 @@ void at3pg_reset(void* state)
     memset(state, 0, sizeof(at3pg_stream));
 }
 
-/* at3phip_analyse_tones for one stream: bands [n][C][16][128]; blocks [n]: slot f = the block of (frame f - 1, frame f);
- * residual [n][C][16][128]: slot f = the residual of frame f - 1 (frame -1 of the first call: the zero frame) */
-void at3pg_analyse(void* state, int C, const float* bands, int n, at3phip_tonal_block* blocks, float* residual)
+/* at3phip_analyse_tones with `flags` (AT3PHIP_TONES_GATED, AT3PHIP_TONES_SHARED, both or none) for one stream: bands
+ * [n][C][16][128]; blocks [n]: slot f = the block of (frame f - 1, frame f); residual [n][C][16][128]: slot f = the residual of
+ * frame f - 1 (frame -1 of the first call: the zero frame). intervals [n][C][16][2] (may be null): the cells [lo, hi] of G3 that
+ * slot f's block used per band, 0 and 63 for a band without an event; found [n] (may be null): the waves of step 5 in each
+ * slot, before S3 */
+void at3pg_analyse(void* state, int C, const float* bands, int n, at3phip_tonal_block* blocks, float* residual, uint32_t flags,
+                   int8_t* intervals, int32_t* found)
 {
     at3pg_stream* st = (at3pg_stream*)state;
+    const int gated = (flags & AT3PHIP_TONES_GATED) != 0, shared = (flags & AT3PHIP_TONES_SHARED) != 0 && C == 2;   /* S1 */
     init_gha_tables();
     for (int f = 0; f < n; ++f) {
         gwave w[2 * 16 * AT3PHIP_TONE_MAX_BAND_WAVES];
-        int nw = 0;
+        int nw = 0, gate[2][16] = {{0}}, twin[16] = {0};
         for (int ch = 0; ch < C; ++ch)
             for (int sb = 0; sb < 16; ++sb) {
                 float x[256];
                 memcpy(x, st->x[ch] + sb * 128, 128 * sizeof(float));
                 memcpy(x + 128, bands + (((size_t)f * C + ch) * 16 + sb) * 128, 128 * sizeof(float));
-                const int got = find_band(x, w + nw);
+                const int g0 = gated ? gate_band(x) : 0, g1 = gated ? gate_band(x + 128) : 0;
+                int lo = 0, hi = 63;
+                gate[ch][sb] = g1;
+                if (g0 | g1) gate_interval(g0, g1, &lo, &hi);
+                const int got = find_band(x, (g0 | g1) != 0, lo, hi, w + nw);
+                if (intervals) {
+                    intervals[((size_t)(f * C + ch) * 16 + sb) * 2] = (int8_t)lo;
+                    intervals[((size_t)(f * C + ch) * 16 + sb) * 2 + 1] = (int8_t)hi;
+                }
                 for (int i = 0; i < got; ++i) { w[nw + i].ch = ch; w[nw + i].sb = sb; }
                 nw += got;
             }
+        if (found) found[f] = nw;
+        if (shared) {   /* S2, then S3: channel 1's waves of the twin bands leave the population */
+            for (int sb = 0; sb < 16; ++sb) twin[sb] = twin_band(w, nw, gate[0][sb], gate[1][sb], sb);
+            int kept = 0;
+            for (int i = 0; i < nw; ++i)
+                if (!(w[i].ch == 1 && twin[w[i].sb])) w[kept++] = w[i];
+            nw = kept;
+        }
         select_waves(w, nw, &blocks[f]);
-        /* step 8 on the previous frame: this block fading in, the block before fading out */
+        /* G2: the second frame's event is the block's point pair, with or without a wave in the band; S4: a twin band of
+         * channel 1 stays all zero */
+        for (int ch = 0; ch < C; ++ch)
+            for (int sb = 0; sb < 16; ++sb) {
+                const int g = gate[ch][sb];
+                if (!g || (ch == 1 && twin[sb])) continue;
+                if (g < 0x80) blocks[f].band[ch][sb].start = (uint8_t)(g + 1);
+                else blocks[f].band[ch][sb].stop = (uint8_t)((g & 31) + 1);
+                if (sb + 1 > blocks[f].num_tone_bands) blocks[f].num_tone_bands = (uint8_t)(sb + 1);
+            }
+        for (int sb = 0; sb < blocks[f].num_tone_bands; ++sb)   /* S4 */
+            if (twin[sb]) blocks[f].tone_sharing |= (uint16_t)(1u << sb);
+        /* steps 8, G5, S5 on the previous frame: this block fading in, the block before fading out */
         trec cur;
         block_to_trec(&blocks[f], &cur);
         float* r = residual + (size_t)f * C * 2048;
@@ -229,7 +385,7 @@ void at3pg_analyse(void* state, int C, const float* bands, int n, at3phip_tonal_
                 for (int sb = 0; sb < 16; ++sb)
                     if (cur.band[ch][sb].nw || st->filt.band[ch][sb].nw) generate_tones(&st->filt, &cur, ch, sb, r + ch * 2048 + sb * 128, 1);
         }
-        st->filt = cur;
+        st->filt = cur;   /* (a band's curr_env is read only when the band had waves, and then this frame's call left it) */
         st->last = blocks[f];
         for (int ch = 0; ch < C; ++ch) memcpy(st->x[ch], bands + ((size_t)f * C + ch) * 2048, 2048 * sizeof(float));
     }
@@ -249,4 +405,41 @@ void at3pg_tables(float* sine, float* hann, float* amp_sf, float* tw, double* th
     memcpy(thr, GT.thr, sizeof(GT.thr));
     memcpy(rs, GT.rs, sizeof(GT.rs));
     memcpy(rc, GT.rc, sizeof(GT.rc));
+}
+
+/* at3phip_host_tone_gates: bands [n][C][16][128] -> out [n][C][16] */
+void at3pg_gates(const float* bands, int n, int C, uint8_t* out)
+{
+    for (size_t i = 0; i < (size_t)n * C * 16; ++i) out[i] = (uint8_t)gate_band(bands + i * 128);
+}
+
+/* the envelopes the restated decoder reconstructs from n consecutive unpacked records (at3pt_unpack_frame's flat form, stride
+ * rec_ints): out [n][C][16][2] = the cells [lo, hi] of each record's curr_env */
+void at3pg_decoder_intervals(int C, const int32_t* recs, int rec_ints, int n, int8_t* out)
+{
+    trec prev, cur;
+    memset(&prev, 0, sizeof(prev));
+    for (int f = 0; f < n; ++f) {
+        const int32_t* rec = recs + (size_t)f * rec_ints;
+        memset(&cur, 0, sizeof(cur));
+        int k = 0;
+        cur.present = rec[k++];
+        for (int ch = 0; ch < 2; ++ch)
+            for (int b = 0; b < 16; ++b) {
+                tband* t = &cur.band[ch][b];
+                t->nw = rec[k++]; t->start_index = rec[k++];
+                t->pend.has_start = rec[k++]; t->pend.start = rec[k++]; t->pend.has_stop = rec[k++]; t->pend.stop = rec[k++];
+            }
+        for (int ch = 0; ch < C; ++ch)
+            for (int sb = 0; sb < 16; ++sb) {
+                float scratch[128] = {0};
+                cur.band[ch][sb].nw = 0;    /* the envelope only */
+                prev.band[ch][sb].nw = 0;
+                generate_tones(&prev, &cur, ch, sb, scratch, 0);
+                const tenv* c = &cur.band[ch][sb].curr;
+                out[((size_t)(f * C + ch) * 16 + sb) * 2] = (int8_t)(c->has_start ? c->start : 0);
+                out[((size_t)(f * C + ch) * 16 + sb) * 2 + 1] = (int8_t)(c->has_stop ? c->stop : 63);
+            }
+        prev = cur;
+    }
 }

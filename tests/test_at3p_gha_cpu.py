@@ -272,7 +272,7 @@ def test_host_mirror_equals_the_restatement(tmp_path):
     predicts. The stand-alone program tests/host/test_host_shim_at3p_gha.cpp, built against the harness library."""
     emu = build_strict()
     exe, data = str(tmp_path / "test_host_shim_at3p_gha"), str(tmp_path / "cases.bin")
-    n = G.export_shim_cases(data, emu)
+    n = G.export_shim_cases(data, emu)[0][1]
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", os.path.join(ROOT, "tests", "host", "test_host_shim_at3p_gha.cpp"), "-o", exe,
                            emu, f"-Wl,-rpath,{os.path.dirname(emu)}"])
     out = subprocess.run([exe, data], capture_output=True, text=True, env=dict(os.environ, EMU_STRICT="1"))

@@ -10,7 +10,8 @@ import wave
 import numpy as np
 import pytest
 
-import at3p_gha_gate_lib as GG
+import at3p_gha_lib as G
+
 
 pytestmark = pytest.mark.gpu
 NF = 8
@@ -27,7 +28,7 @@ def _frames(path):
 def test_cli_tones_gate(tmp_path, nch):
     from atracdenc_amd import binding as B
     exe = os.path.join(os.path.dirname(B.LIB_PATH), "at3hipenc")
-    pcm16 = np.clip(np.rint(GG.keyed_pcm(NF, nch) * 32767.0), -32768, 32767).astype("<i2")
+    pcm16 = np.clip(np.rint(G.keyed_pcm(NF, nch) * 32767.0), -32768, 32767).astype("<i2")
     wav_in = str(tmp_path / "in.wav")
     with wave.open(wav_in, "wb") as w:
         w.setnchannels(nch)
@@ -46,7 +47,7 @@ def test_cli_tones_gate(tmp_path, nch):
     x = (pcm16.astype(np.float32) / np.float32(32768.0)).reshape(NF, 2048, nch)
     enc = B.At3pHip(n_streams=1, max_frames=NF, channels=nch)
     try:
-        want = GG.pipeline(x, True, lambda specs, recs: enc.write_frames(specs[None], None, recs[None])[0])[0]
+        want = G.pipeline(x, True, False, lambda specs, recs: enc.write_frames(specs[None], None, recs[None])[0])[0]
         enc.reset()
         want_gpu = enc.encode_frames_tonal(x[None], gated=True)[0]
     finally:

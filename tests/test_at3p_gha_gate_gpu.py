@@ -1,5 +1,5 @@
 """The gated ATRAC3plus tone analysis on the GPU (include/at3phip.h, FINDING TONES, GATES): at3phip_analyse_tones and
-at3phip_encode_frames_tonal(_short) with AT3PHIP_TONES_GATED against the C restatement tests/host/at3p_gha_gate_cpu.c, bit for bit:
+at3phip_encode_frames_tonal(_short) with AT3PHIP_TONES_GATED against the C restatement tests/host/at3p_gha_cpu.c, bit for bit:
 three different streams side by side, host and device buffers, one call against per-frame calls, queued against waiting; and
 the unflagged calls of the same context against the golden of the ungated analysis."""
 import hashlib
@@ -8,7 +8,6 @@ import os
 import numpy as np
 import pytest
 
-import at3p_gha_gate_lib as GG
 import at3p_gha_lib as G
 
 pytestmark = pytest.mark.gpu
@@ -31,8 +30,8 @@ _cache = {}
 def _bands_case(nch):
     """(bands [3][NF][C][16][128], per stream the restatement's (blocks, residual)): the crafted onset at cell 16 as subband input"""
     if ("bands", nch) not in _cache:
-        bands = np.stack([GG.onset_bands(16, nch, NF), G.pqf_bands(G.signal_pcm("burst", NF, nch)), G.pqf_bands(G.signal_pcm("noise", NF, nch))])
-        _cache[("bands", nch)] = (bands, [GG.CpuGatedAnalyser(nch).analyse(bands[s]) for s in range(3)])
+        bands = np.stack([G.onset_bands(16, nch, NF), G.pqf_bands(G.signal_pcm("burst", NF, nch)), G.pqf_bands(G.signal_pcm("noise", NF, nch))])
+        _cache[("bands", nch)] = (bands, [G.CpuToneAnalyser(nch, True).analyse(bands[s]) for s in range(3)])
     return _cache[("bands", nch)]
 
 
@@ -40,16 +39,16 @@ def _pcm_case(B, nch):
     """(pcm [3][NF][2048][C] as the 16-bit call widens it, its int16, per stream the restatement pipeline's frames); the onset
     stream is a 3 kHz sine that starts inside frame 2"""
     if ("pcm", nch) not in _cache:
-        pcm = np.stack([GG.onset_pcm(NF, nch), G.signal_pcm("burst", NF, nch), G.signal_pcm("noise", NF, nch)])
+        pcm = np.stack([G.onset_pcm(NF, nch), G.signal_pcm("burst", NF, nch), G.signal_pcm("noise", NF, nch)])
         s16 = np.round(pcm * 32767.0).astype(np.int16)
         pcm = (s16.astype(np.float32) / np.float32(32768.0)).astype(np.float32)
         enc = B.At3pHip(n_streams=1, max_frames=NF, channels=nch)
         try:
             write = lambda specs, recs: enc.write_frames(specs[None], None, recs[None])[0]
-            want = [GG.pipeline(pcm[s], True, write) for s in range(3)]
+            want = [G.pipeline(pcm[s], True, False, write) for s in range(3)]
         finally:
             enc.close()
-        assert sum(len(GG.points(b, nch)) for b in want[0][1]) > 0 and sum(G.n_waves(b) for b in want[0][1]) > 0
+        assert sum(len(G.points(b, nch)) for b in want[0][1]) > 0 and sum(G.n_waves(b) for b in want[0][1]) > 0
         _cache[("pcm", nch)] = (pcm, s16, np.stack([w[0] for w in want]))
     return _cache[("pcm", nch)]
 
@@ -76,12 +75,12 @@ def test_analyse_tones_gated_equals_restatement(B, nch):
         wb, wr = want[s]
         for how, b, r in (("one call", blocks[s], resid[s]), ("per frame", np.concatenate([p[0][s] for p in per]), np.concatenate([p[1][s] for p in per])),
                           ("device", d_blocks[s], d_resid[s])):
-            assert b.tobytes() == wb.tobytes(), (name, how, [GG.points(x, nch) for x in b], [GG.points(x, nch) for x in wb])
+            assert b.tobytes() == wb.tobytes(), (name, how, [G.points(x, nch) for x in b], [G.points(x, nch) for x in wb])
             assert np.array_equal(r.view(np.uint32), wr.view(np.uint32)), (name, how)
     # the crafted onset: the start points of slot 2, and no pre-echo
-    assert GG.points(blocks[0, 2], nch) == {(ch, b): (17, 0) for ch in range(nch) for b in GG.GATE_BANDS}
+    assert G.points(blocks[0, 2], nch) == {(ch, b): (17, 0) for ch in range(nch) for b in G.GATE_BANDS}
     assert not resid[0, :3].view(np.uint32).any() and not resid[0, 3, :, :, :64].view(np.uint32).any()
-    assert not any(GG.points(b, nch) for b in blocks[2])   # noise: no gate
+    assert not any(G.points(b, nch) for b in blocks[2])   # noise: no gate
 
 
 @pytest.mark.parametrize("nch", [1, 2])

@@ -1,5 +1,5 @@
 """The tone analysis kernels with AT3PHIP_TONES_GATED (at3p_gha.hpp: k_at3p_tone_find<true>, k_at3p_tone_select, k_at3p_tone_sub,
-k_at3p_tone_state) run lane by lane through the CPU SIMT harness against the C restatement tests/host/at3p_gha_gate_cpu.c."""
+k_at3p_tone_state) run lane by lane through the CPU SIMT harness against the C restatement tests/host/at3p_gha_cpu.c."""
 import os
 
 import pytest
@@ -11,13 +11,13 @@ needs_clang = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's
 
 @needs_clang
 def test_harness_driver_equals_the_gated_restatement():
-    """tools/emu/run_emu_at3p_gha_gate.py under the strict harness: records and residuals of the crafted onsets and offsets (mono and
+    """tools/emu/run_emu_at3p_gha.py gated under the strict harness: records and residuals of the crafted onsets and offsets (mono and
     stereo, in one call and in calls of 1, 2 and 3 frames) and of 8 frames of stereo `burst`, the frames of its pipeline in one call
     and in three, and the host gate function equal the restatement's - in ascending and in descending wavefront order, and with
     every device buffer ending at a guard page."""
     build_strict()
     modes = {"plain": {}, "reverse": {"EMU_ORDER": "reverse"}, "fence": {"EMU_FENCE": "high"}}
-    runs = Children({m: ("run_emu_at3p_gha_gate.py", ["--nobuild"], env) for m, env in modes.items()})
+    runs = Children({m: ("run_emu_at3p_gha.py", ["gated", "--nobuild"], env) for m, env in modes.items()})
     try:
         for m in modes:
             out = runs.output(m)

@@ -38,7 +38,7 @@ def _case(B, nch):
         pcm = np.stack([G.signal_pcm(name, NF, nch) for name in STREAMS])
         enc, write = _writer(B, nch, NF)
         try:
-            _cache[nch] = (pcm, [G.pipeline(pcm[s], write) for s in range(len(STREAMS))])
+            _cache[nch] = (pcm, [G.pipeline(pcm[s], write=write) for s in range(len(STREAMS))])
         finally:
             enc.close()
         if nch == 1:   # where the block leaves the frame its quant units the oracle's writer with the block spliced in says the same

@@ -1,13 +1,12 @@
 """The ATRAC3plus tone analysis with shared bands on the GPU (include/at3phip.h, FINDING TONES, SHARING): at3phip_analyse_tones and
 at3phip_encode_frames_tonal(_short) with AT3PHIP_TONES_SHARED, alone and with AT3PHIP_TONES_GATED, against the C restatement
-tests/host/at3p_gha_share_cpu.c byte for byte: two streams side by side over four frames, in one call and split 1 + 3 with the
+tests/host/at3p_gha_cpu.c byte for byte: two streams side by side over four frames, in one call and split 1 + 3 with the
 state carried, host and device buffers; a mono context; the decoder on the flagged frames; a stream of noise beside a stream of
 twin bands. Bytes only: nothing is timed."""
 import numpy as np
 import pytest
 
 import at3p_gha_lib as G
-import at3p_gha_share_lib as GS
 import at3p_tonal_lib as T
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +22,7 @@ def B():
     from atracdenc_amd import binding
     for name in G.NEW_SYMBOLS + ("at3phip_host_tone_flags",):   # a library without the sharing fails every test here
         binding._need(binding.load_library(), name)
-    assert binding.at3p_host_tone_flags() & GS.SHARED
+    assert binding.at3p_host_tone_flags() & G.SHARED
     return binding
 
 
@@ -34,8 +33,8 @@ def _bands_case(key):
     """(bands [2][NF][2][16][128], per stream the restatement's (blocks, residual))"""
     if ("bands", key) not in _cache:
         names, gated = CALLS[key]
-        bands = np.stack([GS.CASES[n][0](NF) for n in names])
-        _cache[("bands", key)] = (bands, [GS.CpuSharedAnalyser(2, gated).analyse(bands[s]) for s in range(2)])
+        bands = np.stack([G.CASES[n][0](NF) for n in names])
+        _cache[("bands", key)] = (bands, [G.CpuToneAnalyser(2, gated, True).analyse(bands[s]) for s in range(2)])
     return _cache[("bands", key)]
 
 
@@ -69,7 +68,7 @@ def _pcm_case(B, key):
         enc = B.At3pHip(n_streams=1, max_frames=NF, channels=2)
         try:
             write = lambda specs, recs: enc.write_frames(specs[None], None, recs[None])[0]
-            want = [GS.pipeline(pcm[s], gated, True, write) for s in range(2)]
+            want = [G.pipeline(pcm[s], gated, True, write) for s in range(2)]
         finally:
             enc.close()
         _cache[("pcm", key)] = (pcm, s16, np.stack([w[0] for w in want]), [w[1] for w in want])
@@ -115,9 +114,9 @@ def test_analyse_tones_shared_equals_restatement(B, key):
             assert int(rec[1]["tone_sharing"]) == 0xffff and G.n_waves(rec[1]) == 48 and not rec[1]["band"][1].tobytes().strip(b"\0")
             assert [len(w) for w in G.band_waves(rec[1], 2)[0]] == [3] * 16
         if name == "differ":
-            assert int(rec[1]["tone_sharing"]) == 0xffff & ~(1 << GS.DIFFER_BAND) and G.n_waves(rec[1]) == 48
+            assert int(rec[1]["tone_sharing"]) == 0xffff & ~(1 << G.DIFFER_BAND) and G.n_waves(rec[1]) == 48
         if name == "onset_one":
-            assert GS.shared_bands(rec[2]) == [b for b in range(16) if b not in (0, 7, 15)]
+            assert G.shared_bands(rec[2]) == [b for b in range(16) if b not in (0, 7, 15)]
         if name == "onset_both":
             assert int(rec[2]["tone_sharing"]) == 0xffff and not rec[2]["band"][1].tobytes().strip(b"\0") and rec[2]["band"][0, 7]["start"] == 17
 
@@ -128,7 +127,7 @@ def test_encode_frames_tonal_shared_equals_restatement_pipeline(B, key):
     import torch
     pcm, s16, exp, blocks = _pcm_case(B, key)
     gated = CALLS[key][1]
-    assert all(sum(len(GS.shared_bands(b)) for b in bl) > 0 for bl in blocks)
+    assert all(sum(len(G.shared_bands(b)) for b in bl) > 0 for bl in blocks)
     enc = B.At3pHip(n_streams=2, max_frames=NF, channels=2)
     got = {}
     try:
@@ -161,7 +160,7 @@ def test_encode_frames_tonal_shared_equals_restatement_pipeline(B, key):
 
 # ---- 2: mono -----------------------------------------------------------------------------------------------------------------------------
 def test_mono_context_ignores_the_flag(B):
-    bands = np.ascontiguousarray(np.stack([GS.budget_bands(NF)[:, :1], GS.onset_bands(True, NF)[:, :1]]))
+    bands = np.ascontiguousarray(np.stack([G.budget_bands(NF)[:, :1], G.stereo_onset_bands(True, NF)[:, :1]]))
     pcm = np.ascontiguousarray(np.stack([_case_pcm("budget", NF)[:, :, :1], _case_pcm("onset_both", NF)[:, :, :1]]))
     enc = B.At3pHip(n_streams=2, max_frames=NF, channels=1)
     try:

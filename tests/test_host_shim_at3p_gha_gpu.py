@@ -14,7 +14,7 @@ def test_host_cpp_shim_at3p_gha(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe, data = str(tmp_path / "test_host_shim_at3p_gha"), str(tmp_path / "cases.bin")
     libdir = os.path.join(root, "atracdenc_amd")
-    n = G.export_shim_cases(data)
+    n = G.export_shim_cases(data)[0][1]
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", os.path.join(root, "tests", "host", "test_host_shim_at3p_gha.cpp"), "-o", exe,
                            f"-L{libdir}", "-lat3hip", f"-Wl,-rpath,{libdir}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"])
     out = subprocess.run([exe, data], capture_output=True, text=True)

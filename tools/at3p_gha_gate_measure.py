@@ -8,24 +8,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import at3p_gha_lib as G
-import at3p_gha_gate_lib as GG
 import at3p_tonal_lib as T
 from at3_testlib import at3p_signal
 
 NF = 14
 
 def signal(name):
-    return GG.keyed_pcm(NF, 1)[:, :, 0] if name == "keyed" else at3p_signal(name, NF, channel=0)
+    return G.keyed_pcm(NF, 1)[:, :, 0] if name == "keyed" else at3p_signal(name, NF, channel=0)
 
 def round_trip(name, gated, ratio):
     x2 = signal(name)
     bands = G.pqf_bands(np.concatenate([x2, np.zeros((1, 2048), np.float32)])[:, :, None])   # and the flushing frame
-    blocks, resid = GG.CpuGatedAnalyser(1, gated, ratio).analyse(bands)
+    blocks, resid = G.CpuToneAnalyser(1, gated, ratio=ratio).analyse(bands)
     base = G.write_residual(resid[1:])
     recs = [None] + list(blocks[1:NF])   # frame j carries the spectrum of residual j and block T_{j-1}
-    pcm, rej = T.cpu_tonal_decode(GG.splice_blocks(base, recs, 1), 1)
+    pcm, rej = T.cpu_tonal_decode(G.splice_blocks(base, recs, 1), 1)
     assert rej.sum() == 0
-    npts = sum(len(GG.points(b, 1)) for b in blocks)
+    npts = sum(len(G.points(b, 1)) for b in blocks)
     return G.snr_db(x2.reshape(-1), pcm[:, :, 0].reshape(-1), NF), float(np.mean([G.n_waves(b) for b in blocks[1:]])), npts
 
 def stationary(ratio):
@@ -33,16 +32,16 @@ def stationary(ratio):
     for name in ("tones", "noise", "silence"):
         for nch in (1, 2):
             bands = G.pqf_bands(G.signal_pcm(name, NF, nch))
-            a, b = GG.CpuGatedAnalyser(nch, True, ratio).analyse(bands), GG.CpuGatedAnalyser(nch, False, ratio).analyse(bands)
+            a, b = G.CpuToneAnalyser(nch, True, ratio=ratio).analyse(bands), G.CpuToneAnalyser(nch, False, ratio=ratio).analyse(bands)
             if a[0].tobytes() != b[0].tobytes() or a[1].tobytes() != b[1].tobytes():
-                bad.append((name, nch, int(np.count_nonzero(GG.cpu_gates(bands, ratio)))))
+                bad.append((name, nch, int(np.count_nonzero(G.cpu_gates(bands, ratio)))))
     return bad
 
 def detection(ratio):
     out = {}
     for s0 in (3, 4, 16, 28, 29):
-        on, off = GG.cpu_gates(GG.onset_bands(s0, 1), ratio)[2, 0], GG.cpu_gates(GG.offset_bands(s0 - 1, 1), ratio)[2, 0]
-        out[s0] = ([int(on[b]) for b in GG.GATE_BANDS], [int(off[b]) for b in GG.GATE_BANDS])
+        on, off = G.cpu_gates(G.onset_bands(s0, 1), ratio)[2, 0], G.cpu_gates(G.offset_bands(s0 - 1, 1), ratio)[2, 0]
+        out[s0] = ([int(on[b]) for b in G.GATE_BANDS], [int(off[b]) for b in G.GATE_BANDS])
     return out
 
 if __name__ == "__main__":
