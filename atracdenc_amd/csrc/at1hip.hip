@@ -87,23 +87,15 @@ int at1hip_create(const at1hip_config* cfg, at1hip_ctx** out)
 void at1hip_destroy(at1hip_ctx* c)
 {
     if (c)
-        at3host::destroy_engine(c, {c->d_tables, c->d_pcm_in, c->d_pcm_s16, c->d_hist, c->d_specs, c->d_values, c->d_energy, c->d_sfi, c->d_mask,
-                                    c->d_loud_ch, c->d_loud_state, c->d_loud_track, c->d_out},
-                                {}, [c] {
-                                    for (hipEvent_t e : c->ev)
-                                        if (e) (void)hipEventDestroy(e);
-                                });
+        at3host::destroy_engine(c, {}, [c] {
+            for (hipEvent_t e : c->ev)
+                if (e) (void)hipEventDestroy(e);
+        });
 }
 
 const char* at1hip_last_error(const at1hip_ctx* c) { return at3host::engine_last_error(c); }
 
-int at1hip_reset(at1hip_ctx* c)
-{
-    if (!c) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    return reset_state(c);
-}
+int at1hip_reset(at1hip_ctx* c) { return at3host::guarded(c, reset_state); }
 
 }  // extern "C"
 
@@ -114,7 +106,6 @@ namespace {
 template <typename T>
 int encode_impl(at1hip_ctx* c, const T* pcm, int32_t n_blocks, uint8_t* out_frames, uint32_t flags)
 {
-    constexpr bool kShort = sizeof(T) == sizeof(int16_t);
     if (!c || !pcm || !out_frames || n_blocks < 1 || n_blocks > c->cfg.max_blocks)
         return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
     at3host::DeviceGuard guard(c->device);
@@ -122,21 +113,10 @@ int encode_impl(at1hip_ctx* c, const T* pcm, int32_t n_blocks, uint8_t* out_fram
     const size_t S = c->cfg.n_streams, C = c->cfg.channels, F = (size_t)n_blocks;
     hipStream_t st = c->stream;
     const bool timed = !(flags & AT3HIP_ASYNC);   // a queued call carries no stage-timing events (not free between the kernels): its timings read zero
-    const T* d_pcm = pcm;
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        T* staging;
-        if constexpr (kShort) {   // 16-bit samples cross the bus as they are (half the bytes) and are widened by the front kernel's loads
-            if (!c->d_pcm_s16) {
-                const int rc = dev_alloc(c, &c->d_pcm_s16, S * (size_t)c->cfg.max_blocks * 512 * C);
-                if (rc != AT3HIP_OK) return rc;
-            }
-            staging = c->d_pcm_s16;
-        } else {
-            staging = c->d_pcm_in;
-        }
-        HIPCHK(c, hipMemcpyAsync(staging, pcm, S * F * 512 * C * sizeof(T), hipMemcpyHostToDevice, st));
-        d_pcm = staging;
-    }
+    // 16-bit samples cross the bus as they are (half the bytes) and are widened by the front kernel's loads
+    T*& staging = at3host::pick<T>(c->d_pcm_in, c->d_pcm_s16);
+    const T* d_pcm = nullptr;
+    if (const int rc = at3host::stage_in(c, staging, S * (size_t)c->cfg.max_blocks * 512 * C, pcm, S * F * 512 * C, flags, &d_pcm)) return rc;
     uint8_t* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? out_frames : c->d_out;
 
     if (timed) HIPCHK(c, hipEventRecord(c->ev[0], st));
@@ -220,18 +200,17 @@ int at1hip_encode_short(at1hip_ctx* c, const int16_t* pcm, int32_t n_blocks, uin
 
 int at1hip_sync(at1hip_ctx* c)
 {
-    if (!c) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->tm_pending) {
-        c->tm_pending = false;
-        (void)hipEventElapsedTime(&c->tm.front_ms, c->ev[0], c->ev[1]);
-        (void)hipEventElapsedTime(&c->tm.scan_ms, c->ev[1], c->ev[2]);
-        (void)hipEventElapsedTime(&c->tm.pack_ms, c->ev[2], c->ev[3]);
-        (void)hipEventElapsedTime(&c->tm.total_ms, c->ev[0], c->ev[3]);
-    }
-    return AT3HIP_OK;
+    return at3host::guarded(c, [](at1hip_ctx* c) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->tm_pending) {
+            c->tm_pending = false;
+            (void)hipEventElapsedTime(&c->tm.front_ms, c->ev[0], c->ev[1]);
+            (void)hipEventElapsedTime(&c->tm.scan_ms, c->ev[1], c->ev[2]);
+            (void)hipEventElapsedTime(&c->tm.pack_ms, c->ev[2], c->ev[3]);
+            (void)hipEventElapsedTime(&c->tm.total_ms, c->ev[0], c->ev[3]);
+        }
+        return AT3HIP_OK;
+    });
 }
 
 int at1hip_host_tables(void* dst, size_t bytes)
@@ -278,15 +257,13 @@ int at1hip_read_tap(at1hip_ctx* c, int32_t kind, void* dst, size_t bytes)
 struct at1hip_decoder : at3host::DecoderBase {
     at1hip_decoder_config cfg;
     DecTables* d_tables = nullptr;
-    uint8_t* d_units = nullptr;    // staging for host units [S][F][C][212]
     float* d_raw = nullptr;        // [S*C][F][512]
     float* d_tails = nullptr;      // [S*C][F][48]
     int32_t* d_modes = nullptr;    // [S*C][F]
     int4* d_lw = nullptr;          // [S*C][F]
     float* d_st_band = nullptr;    // [S*C][512]
     float* d_st_tail = nullptr;    // [S*C][48]
-    void* d_out = nullptr;         // staging for host output [S][F][512][C] float32
-    // (d_rejected: [2])
+    // (d_in: the units [S][F][C][212], d_out: [S][F][512][C], d_rejected: [2])
 };
 
 namespace {
@@ -338,7 +315,7 @@ int at1hip_decoder_create(const at1hip_decoder_config* cfg, at1hip_decoder** out
     return at3host::create_decoder(cfg, out, build_dec_tables, at1hip_decoder_destroy, [](at1hip_decoder* d) {
         const size_t S = d->cfg.n_streams, F = d->cfg.max_frames, C = d->cfg.channels;
         int rc;
-        if ((rc = dev_alloc(d, &d->d_units, S * F * C * kFrame)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_in, S * F * C * kFrame)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_raw, S * C * F * 512)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_tails, S * C * F * kDecTailLen)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_modes, S * C * F)) != AT3HIP_OK) return rc;
@@ -346,31 +323,21 @@ int at1hip_decoder_create(const at1hip_decoder_config* cfg, at1hip_decoder** out
         if ((rc = dev_alloc(d, &d->d_st_band, S * C * 512)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_st_tail, S * C * kDecTailLen)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_rejected, 2)) != AT3HIP_OK) return rc;
-        float* d_out = nullptr;
-        if ((rc = dev_alloc(d, &d_out, S * F * 512 * C)) != AT3HIP_OK) return rc;
-        d->d_out = d_out;
+        if ((rc = dev_alloc(d, &d->d_out, S * F * 512 * C)) != AT3HIP_OK) return rc;
         return dec_reset_state(d);
     });
 }
 
 void at1hip_decoder_destroy(at1hip_decoder* d)
 {
-    if (d)
-        at3host::destroy_engine(d, {d->d_tables, d->d_units, d->d_raw, d->d_tails, d->d_modes, d->d_lw, d->d_st_band, d->d_st_tail,
-                                     d->d_rejected, d->d_out});
+    if (d) at3host::destroy_engine(d);
 }
 
 const char* at1hip_decoder_last_error(const at1hip_decoder* d) { return at3host::engine_last_error(d); }
 
 int at1hip_decoder_sync(at1hip_decoder* d) { return at3host::engine_sync(d); }
 
-int at1hip_decoder_reset(at1hip_decoder* d)
-{
-    if (!d) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    HIPCHK(d, guard.error());
-    return dec_reset_state(d);
-}
+int at1hip_decoder_reset(at1hip_decoder* d) { return at3host::guarded(d, dec_reset_state); }
 
 int at1hip_decoder_set_stream(at1hip_decoder* d, void* hip_stream) { return at3host::engine_set_stream(d, hip_stream); }
 
@@ -384,23 +351,16 @@ int at1hip_decoder_get_counters(at1hip_decoder* d, at1hip_decoder_counters* out,
     out->read_past_end = h[1];
     return AT3HIP_OK;
 }
-int at1hip_decode(at1hip_decoder* d, const uint8_t* units, int32_t n_frames, void* pcm, uint32_t flags)
-{
-    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT1HIP_DECODE_S16;
-    if (!d || !units || !pcm || n_frames < 1 || n_frames > d->cfg.max_frames || (flags & ~known))
-        return d ? fail(d, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    HIPCHK(d, guard.error());
-    const size_t S = d->cfg.n_streams, C = d->cfg.channels, F = (size_t)n_frames, SC = S * C;
-    const bool s16 = flags & AT1HIP_DECODE_S16;
-    hipStream_t st = d->stream;
-    const uint8_t* d_units = units;
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(d, hipMemcpyAsync(d->d_units, units, S * F * C * kFrame, hipMemcpyHostToDevice, st));
-        d_units = d->d_units;
-    }
-    void* d_pcm = (flags & AT3HIP_OUT_ON_DEVICE) ? pcm : d->d_out;
 
+}  // extern "C"
+
+namespace {
+
+// The kernels of one at1hip_decode call: n_frames units per (stream, channel) from d_units into d_pcm, both device memory.
+int dec_launch(at1hip_decoder* d, const uint8_t* d_units, int n_frames, void* d_pcm, bool s16)
+{
+    const size_t C = d->cfg.channels, F = (size_t)n_frames, SC = (size_t)d->cfg.n_streams * C;
+    hipStream_t st = d->stream;
     DecBandsParams bp;
     bp.T = d->d_tables;
     bp.units = d_units;
@@ -430,9 +390,14 @@ int at1hip_decode(at1hip_decoder* d, const uint8_t* units, int32_t n_frames, voi
     hipLaunchKernelGGL(k_at1d_state, dim3((unsigned)SC), dim3(256), 0, st, (const float*)d->d_raw, (const float*)d->d_tails,
                        (const int4*)d->d_lw, d->d_st_band, d->d_st_tail, n_frames);
     HIPCHK(d, hipGetLastError());
-    if (!(flags & AT3HIP_OUT_ON_DEVICE))
-        HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 512 * C * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
-    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::engine_sync(d);
+    return AT3HIP_OK;
 }
 
-}  // extern "C"
+}  // namespace
+
+extern "C" int at1hip_decode(at1hip_decoder* d, const uint8_t* units, int32_t n_frames, void* pcm, uint32_t flags)
+{
+    const size_t C = d ? d->cfg.channels : 0;
+    return at3host::decode_call(d, units, n_frames, pcm, flags, AT1HIP_DECODE_S16, AT1HIP_DECODE_S16, C * kFrame, 512 * C,
+                                [&](const uint8_t* d_units, void* d_pcm) { return dec_launch(d, d_units, n_frames, d_pcm, flags & AT1HIP_DECODE_S16); });
+}

@@ -146,13 +146,61 @@ namespace {
 int stage_reserve(at3hip_ctx* c, size_t bytes)
 {
     if (bytes <= c->stage_bytes) return AT3HIP_OK;
-    if (c->d_stage) (void)hipFree(c->d_stage);
+    at3host::dev_free(c, c->d_stage);
     c->d_stage = nullptr;
     c->stage_bytes = 0;
     const size_t want = bytes + bytes / 2 + 4096;
-    hipError_t e = hipMalloc(&c->d_stage, want);
-    if (e != hipSuccess) return fail(c, AT3HIP_ENOMEM, "hipMalloc (staging)", e);
-    c->stage_bytes = want;
+    const int rc = at3host::dev_alloc_bytes(c, &c->d_stage, want, "hipMalloc (staging)");
+    if (rc == AT3HIP_OK) c->stage_bytes = want;
+    return rc;
+}
+
+// One call's layout of the staging area: the total is reserved first, then consecutive regions are handed out in the order
+// they are asked for, with or without a host array copied into them on the context's stream.
+struct StageLayout {
+    at3hip_ctx* c;
+    size_t at = 0;
+    template <typename T>
+    T* take(size_t count)
+    {
+        T* p = reinterpret_cast<T*>((char*)c->d_stage + at);
+        at += count * sizeof(T);
+        return p;
+    }
+    template <typename T, typename D>
+    int put(const T* host, size_t count, D** d)   // (D: T or const T)
+    {
+        T* p = take<T>(count);
+        HIPCHK(c, hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
+        *d = p;
+        return AT3HIP_OK;
+    }
+    // the three arrays of n_curves gain curves behind each other (absent: their regions stay unused)
+    int put_curves(const int32_t*& n_points, const int32_t*& level, const int32_t*& loc, size_t n_curves)
+    {
+        if (!n_points) return AT3HIP_OK;
+        int rc = put(n_points, n_curves, &n_points);
+        if (rc == AT3HIP_OK) rc = put(level, n_curves * 8, &level);
+        if (rc == AT3HIP_OK) rc = put(loc, n_curves * 8, &loc);
+        return rc;
+    }
+};
+
+// The stage-level entry points take their buffers all from the host or all from the device (*dev), and the three arrays of
+// n_curves gain curves together or not at all; curves in host memory are checked for their ranges.
+int check_buffers(at3hip_ctx* c, uint32_t flags, bool* dev, const int32_t* n_points, const int32_t* level, const int32_t* loc, size_t n_curves)
+{
+    if ((n_points != nullptr) != (level != nullptr) || (n_points != nullptr) != (loc != nullptr))
+        return fail(c, AT3HIP_EINVAL, "n_points/level/loc must be all null or all set");
+    *dev = (flags & AT3HIP_PCM_ON_DEVICE) && (flags & AT3HIP_OUT_ON_DEVICE);
+    if (!*dev && (flags & (AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE))) return fail(c, AT3HIP_EINVAL, "buffers must be all host or all device");
+    if (*dev || !n_points) return AT3HIP_OK;
+    for (size_t i = 0; i < n_curves; ++i) {
+        if (n_points[i] < 0 || n_points[i] > 7) return fail(c, AT3HIP_EINVAL, "n_points out of range");
+        for (int k = 0; k < n_points[i]; ++k)
+            if (level[i * 8 + k] < 0 || level[i * 8 + k] > 15 || loc[i * 8 + k] < 0 || loc[i * 8 + k] > 31)
+                return fail(c, AT3HIP_EINVAL, "gain point out of range");
+    }
     return AT3HIP_OK;
 }
 
@@ -478,16 +526,12 @@ void at3hip_destroy(at3hip_ctx* c)
         (void)c->front_done.host_wait();
     }
     c->stream = c->own_stream;   // (destroy_engine waits for `stream`: it must not be the caller's any more)
-    at3host::destroy_engine(c, {c->d_tables,    c->d_pcm_in,    c->d_hist[0],    c->d_hist[1],    c->d_sub,       c->d_sub_b[1], c->d_rec,   c->d_rec_b[1],
-                                c->d_state,     c->d_curves[0], c->d_curves[1],  c->d_specs[0],   c->d_specs[1],  c->d_ges[0],   c->d_ges[1], c->d_psy,
-                                c->d_loud,      c->d_loud_state, c->d_out,       c->d_quant,      c->d_stage,     c->d_sub_tail, c->d_bins,  c->d_clk,
-                                c->d_counters,  c->d_pcm_in_b[0], c->d_pcm_in_b[1], c->d_s16_b[0], c->d_s16_b[1]},
-                            {c->mid_stream, c->back_stream, c->h2d_stream}, [c] {
-                                for_each_event(c, [](hipEvent_t& e, unsigned) {
-                                    if (e) (void)hipEventDestroy(e);
-                                    return true;
-                                });
-                            });
+    at3host::destroy_engine(c, {c->mid_stream, c->back_stream, c->h2d_stream}, [c] {
+        for_each_event(c, [](hipEvent_t& e, unsigned) {
+            if (e) (void)hipEventDestroy(e);
+            return true;
+        });
+    });
 }
 
 int at3hip_frame_size(const at3hip_ctx* c) { return c ? c->frame_sz : AT3HIP_EINVAL; }
@@ -496,13 +540,11 @@ const char* at3hip_last_error(const at3hip_ctx* c) { return at3host::engine_last
 
 int at3hip_set_stream(at3hip_ctx* c, void* hip_stream)
 {
-    if (!c) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    const int rc = drain(c);
-    if (rc != AT3HIP_OK) return rc;
-    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    return AT3HIP_OK;
+    return at3host::guarded(c, [hip_stream](at3hip_ctx* c) {
+        const int rc = drain(c);
+        if (rc == AT3HIP_OK) c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+        return rc;
+    });
 }
 
 int at3hip_host_alloc(at3hip_ctx* c, size_t bytes, void** out)
@@ -619,8 +661,8 @@ int at3hip_set_option(at3hip_ctx* c, int32_t option, int32_t value)
             const int rc = drain(c);
             if (rc != AT3HIP_OK) return rc;
             if (value && !c->d_quant) return dev_alloc(c, &c->d_quant, (size_t)c->cfg.n_streams * c->cfg.max_blocks * 2);
-            if (!value && c->d_quant) {
-                (void)hipFree(c->d_quant);
+            if (!value) {
+                at3host::dev_free(c, c->d_quant);
                 c->d_quant = nullptr;
             }
             return AT3HIP_OK;
@@ -631,12 +673,10 @@ int at3hip_set_option(at3hip_ctx* c, int32_t option, int32_t value)
 
 int at3hip_reset(at3hip_ctx* c)
 {
-    if (!c) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    const int rc = drain(c);
-    if (rc != AT3HIP_OK) return rc;
-    return reset_state(c);
+    return at3host::guarded(c, [](at3hip_ctx* c) {
+        const int rc = drain(c);
+        return rc != AT3HIP_OK ? rc : reset_state(c);
+    });
 }
 
 int at3hip_get_timings(const at3hip_ctx* c, at3hip_timings* out)
@@ -1043,13 +1083,11 @@ extern "C" {
 
 int at3hip_sync(at3hip_ctx* c)
 {
-    if (!c) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    const int rc = drain(c);
-    if (rc != AT3HIP_OK) return rc;
-    read_timings(c, c->last_slot, &c->tm);
-    return AT3HIP_OK;
+    return at3host::guarded(c, [](at3hip_ctx* c) {
+        const int rc = drain(c);
+        if (rc == AT3HIP_OK) read_timings(c, c->last_slot, &c->tm);
+        return rc;
+    });
 }
 
 int at3hip_read_tap(at3hip_ctx* c, int32_t kind, void* dst, size_t bytes)
@@ -1115,51 +1153,30 @@ int mdct_impl(at3hip_ctx* c, float* bands, float* specs, float* max_levels, cons
               const int32_t* loc, int32_t n_items, uint32_t flags)
 {
     if (!c || !bands || !specs || n_items < 1) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    if ((n_points != nullptr) != (level != nullptr) || (n_points != nullptr) != (loc != nullptr))
-        return fail(c, AT3HIP_EINVAL, "n_points/level/loc must be all null or all set");
+    const size_t n = n_items;
+    bool dev = false;
+    int rc = check_buffers(c, flags, &dev, n_points, level, loc, n * 4);
+    if (rc != AT3HIP_OK) return rc;
     at3host::DeviceGuard guard(c->device);
     HIPCHK(c, guard.error());
     hipStream_t st = c->stream;
-    const bool dev = (flags & AT3HIP_PCM_ON_DEVICE) && (flags & AT3HIP_OUT_ON_DEVICE);
-    if (!dev && (flags & (AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE)))
-        return fail(c, AT3HIP_EINVAL, "mdct buffers must be all host or all device");
-    const size_t n = n_items;
-    if (!dev && n_points) {
-        for (size_t i = 0; i < n * 4; ++i) {
-            if (n_points[i] < 0 || n_points[i] > 7) return fail(c, AT3HIP_EINVAL, "n_points out of range");
-            for (int k = 0; k < n_points[i]; ++k)
-                if (level[i * 8 + k] < 0 || level[i * 8 + k] > 15 || loc[i * 8 + k] < 0 || loc[i * 8 + k] > 31)
-                    return fail(c, AT3HIP_EINVAL, "gain point out of range");
-        }
-    }
     MdctItemsParams mp;
     mp.bands = bands;
     mp.specs = specs;
-    mp.n_points = n_points;
-    mp.level = level;
-    mp.loc = loc;
     mp.max_levels = max_levels;
     if (!dev) {
         // host buffers: one staging block per context, laid out [bands | specs | max_levels | n_points | level | loc]
-        const size_t o_specs = n * 2048 * sizeof(float), o_max = o_specs + n * 1024 * sizeof(float);
-        const size_t o_np = o_max + n * 4 * sizeof(float), o_lv = o_np + n * 4 * sizeof(int32_t), o_lc = o_lv + n * 32 * sizeof(int32_t);
-        const size_t total = o_lc + n * 32 * sizeof(int32_t);
-        const int rc = stage_reserve(c, total);
-        if (rc != AT3HIP_OK) return rc;
-        char* base = (char*)c->d_stage;
-        mp.bands = (float*)base;
-        mp.specs = (float*)(base + o_specs);
-        mp.max_levels = max_levels ? (float*)(base + o_max) : nullptr;
-        HIPCHK(c, hipMemcpyAsync(mp.bands, bands, n * 2048 * sizeof(float), hipMemcpyHostToDevice, st));
-        if (n_points) {
-            mp.n_points = (const int32_t*)(base + o_np);
-            mp.level = (const int32_t*)(base + o_lv);
-            mp.loc = (const int32_t*)(base + o_lc);
-            HIPCHK(c, hipMemcpyAsync(base + o_np, n_points, n * 4 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(base + o_lv, level, n * 32 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(base + o_lc, loc, n * 32 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        }
+        if ((rc = stage_reserve(c, n * (2048 + 1024 + 4) * sizeof(float) + n * (4 + 32 + 32) * sizeof(int32_t))) != AT3HIP_OK) return rc;
+        StageLayout lay{c};
+        if ((rc = lay.put(bands, n * 2048, &mp.bands)) != AT3HIP_OK) return rc;
+        mp.specs = lay.take<float>(n * 1024);
+        mp.max_levels = lay.take<float>(n * 4);
+        if (!max_levels) mp.max_levels = nullptr;
+        if ((rc = lay.put_curves(n_points, level, loc, n * 4)) != AT3HIP_OK) return rc;
     }
+    mp.n_points = n_points;
+    mp.level = level;
+    mp.loc = loc;
     hipLaunchKernelGGL(k_mdct_items, dim3((unsigned)n), dim3(128), 0, st, mp, c->d_tables);
     HIPCHK(c, hipGetLastError());
     if (!dev) {
@@ -1192,54 +1209,31 @@ int at3hip_gain_energy_scale(at3hip_ctx* c, const float* prev_overlap, const flo
 {
     if (!c || !prev_overlap || !cur_input || !prev_overlap_scale || !out || n_items < 1)
         return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    if ((n_points != nullptr) != (level != nullptr) || (n_points != nullptr) != (loc != nullptr))
-        return fail(c, AT3HIP_EINVAL, "n_points/level/loc must be all null or all set");
+    const size_t n = n_items;
+    bool dev = false;
+    int rc = check_buffers(c, flags, &dev, n_points, level, loc, n);
+    if (rc != AT3HIP_OK) return rc;
     at3host::DeviceGuard guard(c->device);
     HIPCHK(c, guard.error());
     hipStream_t st = c->stream;
-    const bool dev = (flags & AT3HIP_PCM_ON_DEVICE) && (flags & AT3HIP_OUT_ON_DEVICE);
-    if (!dev && (flags & (AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE)))
-        return fail(c, AT3HIP_EINVAL, "buffers must be all host or all device");
-    const size_t n = n_items;
-    if (!dev && n_points) {
-        for (size_t i = 0; i < n; ++i) {
-            if (n_points[i] < 0 || n_points[i] > 7) return fail(c, AT3HIP_EINVAL, "n_points out of range");
-            for (int k = 0; k < n_points[i]; ++k)
-                if (level[i * 8 + k] < 0 || level[i * 8 + k] > 15 || loc[i * 8 + k] < 0 || loc[i * 8 + k] > 31)
-                    return fail(c, AT3HIP_EINVAL, "gain point out of range");
-        }
-    }
     GesItemsParams gp;
     gp.prev_overlap = prev_overlap;
     gp.cur_input = cur_input;
-    gp.n_points = n_points;
-    gp.level = level;
-    gp.loc = loc;
     gp.prev_scale = prev_overlap_scale;
     gp.out = out;
     if (!dev) {
-        const size_t o_cur = n * 256 * sizeof(float), o_ps = 2 * o_cur, o_out = o_ps + n * sizeof(float);
-        const size_t o_np = o_out + n * 4 * sizeof(float), o_lv = o_np + n * sizeof(int32_t), o_lc = o_lv + n * 8 * sizeof(int32_t);
-        const size_t total = o_lc + n * 8 * sizeof(int32_t);
-        const int rc = stage_reserve(c, total);
-        if (rc != AT3HIP_OK) return rc;
-        char* base = (char*)c->d_stage;
-        HIPCHK(c, hipMemcpyAsync(base, prev_overlap, n * 256 * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(base + o_cur, cur_input, n * 256 * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(base + o_ps, prev_overlap_scale, n * sizeof(float), hipMemcpyHostToDevice, st));
-        gp.prev_overlap = (const float*)base;
-        gp.cur_input = (const float*)(base + o_cur);
-        gp.prev_scale = (const float*)(base + o_ps);
-        gp.out = (float*)(base + o_out);
-        if (n_points) {
-            HIPCHK(c, hipMemcpyAsync(base + o_np, n_points, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(base + o_lv, level, n * 8 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(base + o_lc, loc, n * 8 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            gp.n_points = (const int32_t*)(base + o_np);
-            gp.level = (const int32_t*)(base + o_lv);
-            gp.loc = (const int32_t*)(base + o_lc);
-        }
+        // host buffers: the staging block laid out [prev_overlap | cur_input | prev_scale | out | n_points | level | loc]
+        if ((rc = stage_reserve(c, n * (256 + 256 + 1 + 4) * sizeof(float) + n * (1 + 8 + 8) * sizeof(int32_t))) != AT3HIP_OK) return rc;
+        StageLayout lay{c};
+        if ((rc = lay.put(prev_overlap, n * 256, &gp.prev_overlap)) != AT3HIP_OK) return rc;
+        if ((rc = lay.put(cur_input, n * 256, &gp.cur_input)) != AT3HIP_OK) return rc;
+        if ((rc = lay.put(prev_overlap_scale, n, &gp.prev_scale)) != AT3HIP_OK) return rc;
+        gp.out = lay.take<float>(n * 4);
+        if ((rc = lay.put_curves(n_points, level, loc, n)) != AT3HIP_OK) return rc;
     }
+    gp.n_points = n_points;
+    gp.level = level;
+    gp.loc = loc;
     hipLaunchKernelGGL(k_ges_items, dim3((unsigned)n), dim3(64), 0, st, gp, c->d_tables);
     HIPCHK(c, hipGetLastError());
     if (!dev) HIPCHK(c, hipMemcpyAsync(out, gp.out, n * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -1375,11 +1369,9 @@ extern "C" __attribute__((visibility("default"))) int at3hip_debug_cell_divisors
 struct at3hip_decoder : at3host::DecoderBase {
     at3hip_decoder_config cfg;
     Dec3Tables* d_tables = nullptr;
-    uint8_t* d_frames = nullptr;   // staging for host frames [S][F][frame_size]
     float* d_raw = nullptr;        // [F + 2][S][2][4][512]: slots 0, 1 = the carried frames -2, -1
     Dec3Gains* d_gains = nullptr;  // [F + 2][S][2]
-    void* d_out = nullptr;         // staging for host output [S][F][1024][2] float32
-    // (d_rejected: [kDec3Reasons])
+    // (d_in: the frames [S][F][frame_size], d_out: [S][F][1024][2], d_rejected: [kDec3Reasons])
 };
 
 namespace {
@@ -1444,33 +1436,25 @@ int at3hip_decoder_create(const at3hip_decoder_config* cfg, at3hip_decoder** out
         if (hipGetLastError() != hipSuccess) return AT3HIP_EDEVICE;
         const size_t S = d->cfg.n_streams, F = d->cfg.max_frames;
         int rc;
-        if ((rc = dev_alloc(d, &d->d_frames, S * F * d->cfg.frame_size)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_in, S * F * d->cfg.frame_size)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_raw, (F + 2) * S * 2 * 2048)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_gains, (F + 2) * S * 2)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_rejected, kDec3Reasons)) != AT3HIP_OK) return rc;
-        float* d_out = nullptr;
-        if ((rc = dev_alloc(d, &d_out, S * F * 2048)) != AT3HIP_OK) return rc;
-        d->d_out = d_out;
+        if ((rc = dev_alloc(d, &d->d_out, S * F * 2048)) != AT3HIP_OK) return rc;
         return dec3_reset_state(d);
     });
 }
 
 void at3hip_decoder_destroy(at3hip_decoder* d)
 {
-    if (d) at3host::destroy_engine(d, {d->d_tables, d->d_frames, d->d_raw, d->d_gains, d->d_rejected, d->d_out});
+    if (d) at3host::destroy_engine(d);
 }
 
 const char* at3hip_decoder_last_error(const at3hip_decoder* d) { return at3host::engine_last_error(d); }
 
 int at3hip_decoder_sync(at3hip_decoder* d) { return at3host::engine_sync(d); }
 
-int at3hip_decoder_reset(at3hip_decoder* d)
-{
-    if (!d) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    HIPCHK(d, guard.error());
-    return dec3_reset_state(d);
-}
+int at3hip_decoder_reset(at3hip_decoder* d) { return at3host::guarded(d, dec3_reset_state); }
 
 int at3hip_decoder_set_stream(at3hip_decoder* d, void* hip_stream) { return at3host::engine_set_stream(d, hip_stream); }
 
@@ -1488,23 +1472,15 @@ int at3hip_decoder_get_counters(at3hip_decoder* d, at3hip_decoder_counters* out,
     out->bad_tonal_quant = h[5];
     return AT3HIP_OK;
 }
-int at3hip_decode(at3hip_decoder* d, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags)
-{
-    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3HIP_DECODE_S16;
-    if (!d || !frames || !pcm || n_frames < 1 || n_frames > d->cfg.max_frames || (flags & ~known))
-        return d ? fail(d, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    HIPCHK(d, guard.error());
-    const size_t S = d->cfg.n_streams, F = (size_t)n_frames, fsz = d->cfg.frame_size;
-    const bool s16 = flags & AT3HIP_DECODE_S16;
-    hipStream_t st = d->stream;
-    const uint8_t* d_frames = frames;
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(d, hipMemcpyAsync(d->d_frames, frames, S * F * fsz, hipMemcpyHostToDevice, st));
-        d_frames = d->d_frames;
-    }
-    void* d_pcm = (flags & AT3HIP_OUT_ON_DEVICE) ? pcm : d->d_out;
+}  // extern "C"
 
+namespace {
+
+// The kernels of one at3hip_decode call: n_frames frames per stream from d_frames into d_pcm, both device memory.
+int dec3_launch(at3hip_decoder* d, const uint8_t* d_frames, int n_frames, void* d_pcm, bool s16)
+{
+    const size_t S = d->cfg.n_streams, F = (size_t)n_frames, fsz = d->cfg.frame_size;
+    hipStream_t st = d->stream;
     Dec3UnpackParams up;
     up.T = d->d_tables;
     up.frames = d_frames;
@@ -1530,9 +1506,13 @@ int at3hip_decode(at3hip_decoder* d, const uint8_t* frames, int32_t n_frames, vo
     HIPCHK(d, hipGetLastError());
     hipLaunchKernelGGL(k_at3d_state, dim3((unsigned)(2 * S)), dim3(256), 0, st, d->d_raw, d->d_gains, n_frames, (int32_t)S);
     HIPCHK(d, hipGetLastError());
-    if (!(flags & AT3HIP_OUT_ON_DEVICE))
-        HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 2048 * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
-    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::engine_sync(d);
+    return AT3HIP_OK;
 }
 
-}  // extern "C"
+}  // namespace
+
+extern "C" int at3hip_decode(at3hip_decoder* d, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags)
+{
+    return at3host::decode_call(d, frames, n_frames, pcm, flags, AT3HIP_DECODE_S16, AT3HIP_DECODE_S16, d ? (size_t)d->cfg.frame_size : 0, 2048,
+                                [&](const uint8_t* d_frames, void* d_pcm) { return dec3_launch(d, d_frames, n_frames, d_pcm, flags & AT3HIP_DECODE_S16); });
+}

@@ -368,25 +368,21 @@ int at3phip_create(const at3phip_config* cfg, at3phip_ctx** out)
 void at3phip_destroy(at3phip_ctx* c)
 {
     if (c)
-        at3host::destroy_engine(c, {c->d_tables, c->d_pcm_in, c->d_pcm_s16, c->d_bands, c->d_specs, c->d_specs_b[1], c->d_flags, c->d_pqf_hist,
-                                    c->d_mdct_hist, c->d_wtables, c->d_frames, c->d_tonal, c->d_tone_tables, c->d_tone_cand, c->d_tone_blocks,
-                                    c->d_tone_writer[0], c->d_tone_writer[1], c->d_tone_resid, c->d_tone_prev, c->d_tone_last},
-                                {c->write_stream}, [c] {
-                                    for (hipEvent_t e : {c->ev[0], c->ev[1], c->ev[2], c->ev[3], c->ev[4], c->ev_specs[0], c->ev_specs[1],
-                                                         c->ev_write_done[0], c->ev_write_done[1]})
-                                        if (e) (void)hipEventDestroy(e);
-                                });
+        at3host::destroy_engine(c, {c->write_stream}, [c] {
+            for (hipEvent_t e : {c->ev[0], c->ev[1], c->ev[2], c->ev[3], c->ev[4], c->ev_specs[0], c->ev_specs[1], c->ev_write_done[0],
+                                 c->ev_write_done[1]})
+                if (e) (void)hipEventDestroy(e);
+        });
 }
 
 const char* at3phip_last_error(const at3phip_ctx* c) { return at3host::engine_last_error(c); }
 
 int at3phip_reset(at3phip_ctx* c)
 {
-    if (!c) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    if (int qrc = quiesce(c)) return qrc;
-    return reset_state(c);
+    return at3host::guarded(c, [](at3phip_ctx* c) {
+        const int qrc = quiesce(c);
+        return qrc != AT3HIP_OK ? qrc : reset_state(c);
+    });
 }
 
 int at3phip_pqf_analyse(at3phip_ctx* c, const float* pcm, int32_t n_frames, float* bands, uint32_t flags)
@@ -463,7 +459,6 @@ namespace {
 template <typename T, bool kTones = false>
 int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
 {
-    constexpr bool kShort = sizeof(T) == sizeof(int16_t);
     if (!c || !pcm || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
     at3host::DeviceGuard guard(c->device);
     HIPCHK(c, guard.error());
@@ -473,21 +468,10 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     }
     const size_t items = (size_t)c->cfg.n_streams * n_frames;
     const size_t n = items * c->cfg.channels * 2048;
-    const T* d_pcm = pcm;
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        T* staging;
-        if constexpr (kShort) {   // 16-bit samples cross the bus as they are (half the bytes) and are widened by the filter bank's loads
-            if (!c->d_pcm_s16) {
-                const int rc = dev_alloc(c, &c->d_pcm_s16, (size_t)c->cfg.n_streams * c->cfg.max_frames * c->cfg.channels * 2048);
-                if (rc != AT3HIP_OK) return rc;
-            }
-            staging = c->d_pcm_s16;
-        } else {
-            staging = c->d_pcm_in;
-        }
-        HIPCHK(c, hipMemcpyAsync(staging, pcm, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-        d_pcm = staging;
-    }
+    const T* d_pcm = nullptr;   // (16-bit samples are widened by the filter bank's loads)
+    int rc = at3host::stage_in(c, at3host::pick<T>(c->d_pcm_in, c->d_pcm_s16), (size_t)c->cfg.n_streams * c->cfg.max_frames * c->cfg.channels * 2048,
+                               pcm, n, flags, &d_pcm);
+    if (rc != AT3HIP_OK) return rc;
     uint8_t* d_frames = (flags & AT3HIP_OUT_ON_DEVICE) ? frames : c->d_frames;
     const int par = (int)(c->enc_calls & 1);
     float* d_specs = c->d_specs_b[par];
@@ -498,7 +482,7 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     // a call that is only queued carries none - its timings read zero -, a synchronous one carries all five
     const bool timed = !(flags & AT3HIP_ASYNC);
     if (timed) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    int rc = launch_pqf(c, d_pcm, n_frames, c->d_bands);
+    rc = launch_pqf(c, d_pcm, n_frames, c->d_bands);
     if (rc != AT3HIP_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     const float* d_mdct_in = c->d_bands;
@@ -560,11 +544,8 @@ int at3phip_analyse_tones(at3phip_ctx* c, const float* bands, int32_t n_frames, 
     if (rc != AT3HIP_OK) return rc;
     const size_t items = (size_t)c->cfg.n_streams * n_frames;
     const size_t bytes = items * c->cfg.channels * 2048 * sizeof(float);
-    const float* d_bands = bands;
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(c, hipMemcpyAsync(c->d_bands, bands, bytes, hipMemcpyHostToDevice, c->stream));
-        d_bands = c->d_bands;
-    }
+    const float* d_bands = nullptr;
+    if ((rc = at3host::stage_in(c, c->d_bands, 0, bands, bytes / sizeof(float), flags, &d_bands)) != AT3HIP_OK) return rc;
     const bool out_dev = (flags & AT3HIP_OUT_ON_DEVICE) != 0;
     float* d_resid = (out_dev && residual) ? residual : c->d_tone_resid;
     c->ev_from_encode = false;
@@ -634,21 +615,20 @@ uint32_t at3phip_host_tone_flags(void)
 
 int at3phip_sync(at3phip_ctx* c)
 {
-    if (!c) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(c->device);
-    HIPCHK(c, guard.error());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->write_stream));
-    if (c->ev_from_encode) {
-        float a = 0.0f, b = 0.0f, w = 0.0f;
-        if (hipEventElapsedTime(&a, c->ev[0], c->ev[1]) == hipSuccess && hipEventElapsedTime(&b, c->ev[1], c->ev[2]) == hipSuccess &&
-            hipEventElapsedTime(&w, c->ev[4], c->ev[3]) == hipSuccess) {
-            c->pqf_ms = a;
-            c->mdct_ms = b;
-            c->write_ms = w;
+    return at3host::guarded(c, [](at3phip_ctx* c) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->write_stream));
+        if (c->ev_from_encode) {
+            float a = 0.0f, b = 0.0f, w = 0.0f;
+            if (hipEventElapsedTime(&a, c->ev[0], c->ev[1]) == hipSuccess && hipEventElapsedTime(&b, c->ev[1], c->ev[2]) == hipSuccess &&
+                hipEventElapsedTime(&w, c->ev[4], c->ev[3]) == hipSuccess) {
+                c->pqf_ms = a;
+                c->mdct_ms = b;
+                c->write_ms = w;
+            }
         }
-    }
-    return AT3HIP_OK;
+        return AT3HIP_OK;
+    });
 }
 
 int at3phip_get_write_timing(const at3phip_ctx* c, float* write_ms)
@@ -694,13 +674,11 @@ static_assert(sizeof(DecToneTables) == AT3PHIP_DECODER_TONE_TABLES_BYTES, "at3ph
 struct at3phip_decoder : at3host::DecoderBase {
     at3phip_decoder_config cfg;
     DecTables* d_tables = nullptr;
-    uint8_t* d_frames = nullptr;   // staging for host frames [S][F][2048]
     float* d_raw = nullptr;        // [F + 2][S][C][16][256]: slots 0, 1 = the carried frames -2, -1
     uint16_t* d_flags = nullptr;   // [F + 2][S][C]
     TonalRec* d_tonal = nullptr;   // [F + 3][S]: slots 0 .. 2 = the carried records of frames -3 .. -1
     DecToneTables* d_tone_tables = nullptr;
-    void* d_out = nullptr;         // staging for host output [S][F][2048][C] float32
-    // (d_rejected: [kDecReasons])
+    // (d_in: the frames [S][F][2048], d_out: [S][F][2048][C], d_rejected: [kDecReasons])
 };
 
 namespace {
@@ -790,7 +768,7 @@ int at3phip_decoder_create(const at3phip_decoder_config* cfg, at3phip_decoder** 
     return at3host::create_decoder(cfg, out, build_decp_tables, at3phip_decoder_destroy, [](at3phip_decoder* d) {
         const size_t S = d->cfg.n_streams, F = d->cfg.max_frames, C = d->cfg.channels;
         int rc;
-        if ((rc = dev_alloc(d, &d->d_frames, S * F * 2048)) != AT3HIP_OK) return rc;
+        if ((rc = dev_alloc(d, &d->d_in, S * F * 2048)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_raw, (F + 2) * S * C * 4096)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_flags, (F + 2) * S * C)) != AT3HIP_OK) return rc;
         if ((rc = dev_alloc(d, &d->d_rejected, kDecReasons)) != AT3HIP_OK) return rc;
@@ -805,30 +783,21 @@ int at3phip_decoder_create(const at3phip_decoder_config* cfg, at3phip_decoder** 
             delete h;
             HIPCHK(d, e);
         }
-        float* d_out = nullptr;
-        if ((rc = dev_alloc(d, &d_out, S * F * 2048 * C)) != AT3HIP_OK) return rc;
-        d->d_out = d_out;
+        if ((rc = dev_alloc(d, &d->d_out, S * F * 2048 * C)) != AT3HIP_OK) return rc;
         return decp_reset_state(d);
     });
 }
 
 void at3phip_decoder_destroy(at3phip_decoder* d)
 {
-    if (d) at3host::destroy_engine(d, {d->d_tables, d->d_frames, d->d_raw, d->d_flags, d->d_rejected, d->d_out, d->d_tonal,
-                                            d->d_tone_tables});
+    if (d) at3host::destroy_engine(d);
 }
 
 const char* at3phip_decoder_last_error(const at3phip_decoder* d) { return at3host::engine_last_error(d); }
 
 int at3phip_decoder_sync(at3phip_decoder* d) { return at3host::engine_sync(d); }
 
-int at3phip_decoder_reset(at3phip_decoder* d)
-{
-    if (!d) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    HIPCHK(d, guard.error());
-    return decp_reset_state(d);
-}
+int at3phip_decoder_reset(at3phip_decoder* d) { return at3host::guarded(d, decp_reset_state); }
 
 int at3phip_decoder_set_stream(at3phip_decoder* d, void* hip_stream) { return at3host::engine_set_stream(d, hip_stream); }
 
@@ -847,24 +816,16 @@ int at3phip_decoder_get_counters(at3phip_decoder* d, at3phip_decoder_counters* o
     return AT3HIP_OK;
 }
 
-int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags)
+}  // extern "C"
+
+namespace {
+
+// The kernels of one at3phip_decode call: n_frames frames per stream from d_frames into d_pcm, both device memory.
+int decp_launch(at3phip_decoder* d, const uint8_t* d_frames, int n_frames, void* d_pcm, uint32_t flags)
 {
-    const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES;
-    if (!d || !frames || !pcm || n_frames < 1 || n_frames > d->cfg.max_frames || (flags & ~known))
-        return d ? fail(d, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(d->device);
-    HIPCHK(d, guard.error());
     const size_t S = d->cfg.n_streams, F = (size_t)n_frames, C = d->cfg.channels;
-    const bool s16 = flags & AT3PHIP_DECODE_S16;
     const int tones = (flags & AT3PHIP_DECODE_TONES) ? 1 : 0;
     hipStream_t st = d->stream;
-    const uint8_t* d_frames = frames;
-    if (!(flags & AT3HIP_PCM_ON_DEVICE)) {
-        HIPCHK(d, hipMemcpyAsync(d->d_frames, frames, S * F * 2048, hipMemcpyHostToDevice, st));
-        d_frames = d->d_frames;
-    }
-    void* d_pcm = (flags & AT3HIP_OUT_ON_DEVICE) ? pcm : d->d_out;
-
     DecUnpackParams up;
     up.T = d->d_tables;
     up.frames = d_frames;
@@ -887,7 +848,7 @@ int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, 
     sp.n_frames = n_frames;
     sp.n_streams = (int)S;
     sp.nch = (int)C;
-    sp.s16 = s16 ? 1 : 0;
+    sp.s16 = (flags & AT3PHIP_DECODE_S16) ? 1 : 0;
     sp.tonal = d->d_tonal;
     sp.TT = d->d_tone_tables;
     sp.tones = tones;
@@ -896,9 +857,18 @@ int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, 
     hipLaunchKernelGGL(k_at3pd_state, dim3((unsigned)(S * C)), dim3(256), 0, st, d->d_raw, d->d_flags, d->d_tonal, n_frames, (int32_t)S,
                        (int32_t)C);
     HIPCHK(d, hipGetLastError());
-    if (!(flags & AT3HIP_OUT_ON_DEVICE))
-        HIPCHK(d, hipMemcpyAsync(pcm, d->d_out, S * F * 2048 * C * (s16 ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, st));
-    return (flags & AT3HIP_ASYNC) ? AT3HIP_OK : at3host::engine_sync(d);
+    return AT3HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags)
+{
+    return at3host::decode_call(d, frames, n_frames, pcm, flags, AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES, AT3PHIP_DECODE_S16, 2048,
+                                d ? (size_t)2048 * d->cfg.channels : 0,
+                                [&](const uint8_t* d_frames, void* d_pcm) { return decp_launch(d, d_frames, n_frames, d_pcm, flags); });
 }
 
 int at3phip_decoder_host_tables(void* dst, size_t bytes)

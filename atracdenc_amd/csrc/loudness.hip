@@ -564,33 +564,15 @@ int launch(at3hip_loudness* l, const T* in, int n_in, bool flush)
     return AT3HIP_OK;
 }
 
+// The samples of a call in device memory: the caller's, or the staging of its sample type, allocated by the first call that
+// takes host memory of that type.
 template <typename T>
 int stage_in(at3hip_loudness* l, const T* in, int n_in, uint32_t flags, const T** d_in)
 {
     const size_t S = l->cfg.n_streams, C = l->cfg.channels;
-    *d_in = in;
-    if (n_in == 0) {
-        *d_in = reinterpret_cast<const T*>(l->d_carry[l->cur]);   // (never read)
-        return AT3HIP_OK;
-    }
-    if (flags & AT3HIP_PCM_ON_DEVICE) return AT3HIP_OK;
-    T* staging;   // staging for host memory, allocated by the first call that takes host memory of its kind
-    if constexpr (sizeof(T) == sizeof(int16_t)) {   // 16-bit samples cross the bus as they are and are widened by the kernels' loads
-        if (!l->d_in_s16) {
-            const int rc = dev_alloc(l, &l->d_in_s16, S * (size_t)l->cfg.max_in * C);
-            if (rc != AT3HIP_OK) return rc;
-        }
-        staging = l->d_in_s16;
-    } else {
-        if (!l->d_in) {
-            const int rc = dev_alloc(l, &l->d_in, S * (size_t)l->cfg.max_in * C);
-            if (rc != AT3HIP_OK) return rc;
-        }
-        staging = l->d_in;
-    }
-    HIPCHK(l, hipMemcpyAsync(staging, in, S * n_in * C * sizeof(T), hipMemcpyHostToDevice, l->stream));
-    *d_in = staging;
-    return AT3HIP_OK;
+    *d_in = reinterpret_cast<const T*>(l->d_carry[l->cur]);   // (no input: never read)
+    if (n_in == 0) return AT3HIP_OK;
+    return at3host::stage_in(l, at3host::pick<T>(l->d_in, l->d_in_s16), S * (size_t)l->cfg.max_in * C, in, S * n_in * C, flags, d_in);
 }
 
 // at3hip_loudness_process (T = float) and at3hip_loudness_process_s16 (T = int16_t)
@@ -625,16 +607,10 @@ int apply_impl(at3hip_loudness* l, const T* in, int32_t n_in, const float* gains
     HIPCHK(l, guard.error());
     const size_t S = l->cfg.n_streams, C = l->cfg.channels;
     const T* d_in = nullptr;
-    const int rc = stage_in(l, in, n_in, flags, &d_in);
+    float* d_out = nullptr;
+    int rc = stage_in(l, in, n_in, flags, &d_in);
+    if (rc == AT3HIP_OK) rc = at3host::stage_out(l, l->d_out, S * (size_t)l->cfg.max_in * C, out, flags, &d_out);
     if (rc != AT3HIP_OK) return rc;
-    float* d_out = out;
-    if (!(flags & AT3HIP_OUT_ON_DEVICE)) {
-        if (!l->d_out) {
-            const int rc2 = dev_alloc(l, &l->d_out, S * (size_t)l->cfg.max_in * C);
-            if (rc2 != AT3HIP_OK) return rc2;
-        }
-        d_out = l->d_out;
-    }
     HIPCHK(l, hipMemcpyAsync(l->d_gain, gains, S * sizeof(float), hipMemcpyHostToDevice, l->stream));
     const long long n = (long long)n_in * C;
     const int vec = n % 4 == 0 && (uintptr_t)d_in % (4 * sizeof(T)) == 0 && (uintptr_t)d_out % 16 == 0;
@@ -692,20 +668,18 @@ int at3hip_loudness_create(const at3hip_loudness_config* cfg, at3hip_loudness** 
 
 void at3hip_loudness_destroy(at3hip_loudness* l)
 {
-    if (l) at3host::destroy_engine(l, {l->d_carry[0], l->d_carry[1], l->d_z, l->d_peaks, l->d_hp, l->d_gain, l->d_in, l->d_in_s16, l->d_out,
-                                       l->d_lim_q[0], l->d_lim_q[1], l->d_lim_x[0], l->d_lim_x[1], l->d_lim_gain, l->d_lim_stats, l->d_lim_out});
+    if (l) at3host::destroy_engine(l);
 }
 
 const char* at3hip_loudness_last_error(const at3hip_loudness* l) { return at3host::engine_last_error(l); }
 
 int at3hip_loudness_reset(at3hip_loudness* l)
 {
-    if (!l) return AT3HIP_EINVAL;
-    at3host::DeviceGuard guard(l->device);
-    HIPCHK(l, guard.error());
-    // the carry is read only for samples the counters say were received: the counters and the peaks are the state
-    l->lim_on = false;   // (a limiter run ends here; its statistics stay readable)
-    return clear_state(l);
+    return at3host::guarded(l, [](at3hip_loudness* l) {
+        // the carry is read only for samples the counters say were received: the counters and the peaks are the state
+        l->lim_on = false;   // (a limiter run ends here; its statistics stay readable)
+        return clear_state(l);
+    });
 }
 
 int at3hip_loudness_process(at3hip_loudness* l, const float* in, int32_t n_in, uint32_t flags) { return process_impl(l, in, n_in, flags); }

@@ -351,15 +351,9 @@ int limit_impl(at3hip_loudness* l, const T* in, int32_t n_in, float* out, int32_
         const int rc = stage_in(l, in, n_in, flags, &d_in);
         if (rc != AT3HIP_OK) return rc;
     }
-    float* d_out = out;
-    if (!(flags & AT3HIP_OUT_ON_DEVICE)) {
-        if (!l->d_lim_out) {
-            const size_t most = (size_t)(l->cfg.max_in > kLimXCarry ? l->cfg.max_in : kLimXCarry);
-            const int rc = dev_alloc(l, &l->d_lim_out, S * most * C);
-            if (rc != AT3HIP_OK) return rc;
-        }
-        d_out = l->d_lim_out;
-    }
+    float* d_out = nullptr;
+    const size_t most = (size_t)(l->cfg.max_in > kLimXCarry ? l->cfg.max_in : kLimXCarry);
+    if (const int rc = at3host::stage_out(l, l->d_lim_out, S * most * C, out, flags, &d_out)) return rc;
     LimitParams p;
     p.xc = l->d_lim_x[l->lim_cur];
     p.xc_next = l->d_lim_x[l->lim_cur ^ 1];

@@ -300,7 +300,6 @@ int finish(at3hip_resampler* r, void* out, int n_out, uint32_t flags)
 template <typename TI>
 int process_impl(at3hip_resampler* r, const TI* in, int32_t n_in, void* out, int32_t* n_out, uint32_t flags)
 {
-    constexpr bool kShort = sizeof(TI) == sizeof(int16_t);
     const uint32_t known = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | AT3HIP_ASYNC | AT3HIP_RESAMPLE_OUT_S16;
     if (!r) return AT3HIP_EINVAL;
     if (!out || !n_out || (n_in > 0 && !in) || n_in < 0 || n_in > r->cfg.max_in || (flags & ~known))
@@ -310,36 +309,16 @@ int process_impl(at3hip_resampler* r, const TI* in, int32_t n_in, void* out, int
     const int C = r->cfg.channels;
     const size_t S = r->cfg.n_streams;
     // staging for host memory, allocated by the first call that takes or gives host memory: device buffers never need it
-    const TI* d_in = in;
-    if (n_in > 0 && !(flags & AT3HIP_PCM_ON_DEVICE)) {
-        TI* staging;
-        if constexpr (kShort) {   // 16-bit samples cross the bus as they are and are widened by the kernel's loads
-            if (!r->d_in_s16) {
-                const int rc = dev_alloc(r, &r->d_in_s16, S * (size_t)r->cfg.max_in * C);
-                if (rc != AT3HIP_OK) return rc;
-            }
-            staging = r->d_in_s16;
-        } else {
-            if (!r->d_in) {
-                const int rc = dev_alloc(r, &r->d_in, S * (size_t)r->cfg.max_in * C);
-                if (rc != AT3HIP_OK) return rc;
-            }
-            staging = r->d_in;
-        }
-        HIPCHK(r, hipMemcpyAsync(staging, in, S * n_in * C * sizeof(TI), hipMemcpyHostToDevice, r->stream));
-        d_in = staging;
-    }
-    if (!(flags & AT3HIP_OUT_ON_DEVICE) && !r->d_out) {
-        const int rc = dev_alloc(r, &r->d_out, S * (size_t)r->max_out * C);
-        if (rc != AT3HIP_OK) return rc;
-    }
-    if (n_in == 0) d_in = reinterpret_cast<const TI*>(r->d_hist[r->cur]);   // (never read)
+    const TI* d_in = reinterpret_cast<const TI*>(r->d_hist[r->cur]);   // (no input: never read)
+    float* d_out = nullptr;
+    int rc = AT3HIP_OK;
+    if (n_in > 0) rc = at3host::stage_in(r, at3host::pick<TI>(r->d_in, r->d_in_s16), S * (size_t)r->cfg.max_in * C, in, S * n_in * C, flags, &d_in);
+    if (rc == AT3HIP_OK) rc = at3host::stage_out(r, r->d_out, S * (size_t)r->max_out * C, (float*)out, flags, &d_out);
+    if (rc != AT3HIP_OK) return rc;
     const long long n_end_new = outputs_below(r->t_in + n_in - r->sh.K / 2, r->sh);
     const long long n_end = n_end_new > r->t_out ? n_end_new : r->t_out;
     const int count = (int)(n_end - r->t_out);
-    void* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? out : (void*)r->d_out;
-    const int rc = launch(r, d_in, n_in, n_end, d_out, (flags & AT3HIP_RESAMPLE_OUT_S16) != 0);
-    if (rc != AT3HIP_OK) return rc;
+    if ((rc = launch(r, d_in, n_in, n_end, d_out, (flags & AT3HIP_RESAMPLE_OUT_S16) != 0)) != AT3HIP_OK) return rc;
     *n_out = count;
     return finish(r, out, count, flags);
 }
@@ -414,7 +393,7 @@ int at3hip_resampler_create(const at3hip_resampler_config* cfg, at3hip_resampler
 
 void at3hip_resampler_destroy(at3hip_resampler* r)
 {
-    if (r) at3host::destroy_engine(r, {r->d_hp, r->d_hist[0], r->d_hist[1], r->d_in, r->d_in_s16, r->d_out});
+    if (r) at3host::destroy_engine(r);
 }
 
 const char* at3hip_resampler_last_error(const at3hip_resampler* r) { return at3host::engine_last_error(r); }
@@ -449,12 +428,9 @@ int at3hip_resampler_flush(at3hip_resampler* r, float* out, int32_t* n_out, uint
     HIPCHK(r, guard.error());
     const long long n_end = outputs_below(r->t_in, r->sh);
     const int count = (int)(n_end - r->t_out);
-    if (!(flags & AT3HIP_OUT_ON_DEVICE) && !r->d_out) {
-        const int rc = dev_alloc(r, &r->d_out, (size_t)r->cfg.n_streams * r->max_out * r->cfg.channels);
-        if (rc != AT3HIP_OK) return rc;
-    }
-    void* d_out = (flags & AT3HIP_OUT_ON_DEVICE) ? (void*)out : (void*)r->d_out;
-    const int rc = launch(r, (const float*)r->d_hist[r->cur], 0, n_end, d_out, (flags & AT3HIP_RESAMPLE_OUT_S16) != 0);   // (no input: never read)
+    float* d_out = nullptr;
+    int rc = at3host::stage_out(r, r->d_out, (size_t)r->cfg.n_streams * r->max_out * r->cfg.channels, out, flags, &d_out);
+    if (rc == AT3HIP_OK) rc = launch(r, (const float*)r->d_hist[r->cur], 0, n_end, d_out, (flags & AT3HIP_RESAMPLE_OUT_S16) != 0);   // (no input: never read)
     if (rc != AT3HIP_OK) return rc;
     *n_out = count;
     r->t_in = 0;

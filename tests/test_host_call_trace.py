@@ -1,8 +1,9 @@
-"""The HOST code of the three encoders (at3hip.hip, at1hip.hip, at3phip.hip over at3_host_util.hpp) makes the runtime calls
-it made before it was put on the shared engine core: which call, in which order, on which stream, with which event, byte
-count and launch geometry. The sources are compiled for the host and run through the SIMT harness of tools/emu with its call
+"""The HOST code of every engine (at3hip.hip, at1hip.hip, at3phip.hip, resample.hip, loudness.hip over at3_host_util.hpp and
+at3_decoder_host.hpp) makes the runtime calls it made before it was put on the shared engine core and the shared host
+staging: which call, in which order, on which stream, with which event, byte count and launch geometry, and which
+allocations with how many bytes - each destroy releases exactly what was allocated. The sources are compiled for the host and run through the SIMT harness of tools/emu with its call
 trace on (EMU_TRACE); tools/emu/run_emu_trace.py runs one fixed script of calls per case and compares the trace with
-tests/golden/host_trace/<case>.txt, which were written from the sources of the commit before that change. How streams land on
+tests/golden/host_trace/<case>.txt, which were written from the sources of the commit before each change. How streams land on
 the few hardware queues, and with that the pipelined rates, depends on the order they are created in; the overlap of
 consecutive calls on which event is recorded and waited for where."""
 import os
@@ -28,8 +29,10 @@ def children():
 
 
 def test_every_case_has_a_golden():
-    """the ATRAC3 variants (LP2 / LP4, with and without gain control, one channel, the priming call), ATRAC1, ATRAC3plus"""
-    assert len(CASES) == 9, CASES
+    """the ATRAC3 variants (LP2 / LP4, with and without gain control, one channel, the priming call), ATRAC1, ATRAC3plus; the
+    three decoders, the resampler, the meter without and with the true peak, the limiter, the ATRAC3plus tone analysis and
+    the ATRAC3 stage-level entry points (mdct, gain_energy_scale, the quant tap's early release)"""
+    assert len(CASES) == 18, CASES
 
 
 @pytest.mark.parametrize("case", CASES)
