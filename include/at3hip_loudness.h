@@ -75,7 +75,9 @@
  *     NaN at the sample itself and +-0 around it. In true-peak mode the filter turns an infinity into infinities or (inf - inf)
  *     NaNs at the 144 n around it: q = 0 where the largest magnitude is an infinity, r = 1 where it is a NaN. With g = 0,
  *     e = 0 * inf = NaN and r = 1. Finite samples whose product with g overflows give e's exact double, q = 0 or close to it,
- *     and t = +-inf * s, clamped to +-c unless s is 0 (then NaN). No stream affects another.
+ *     and t = +-inf * s, clamped to +-c unless s is 0 (then NaN). No stream affects another. Samples (floats as bit patterns; where
+ *     they are NaN, a NaN of unspecified sign and payload) and statistics are the restatement's for each stream alone
+ *     (tests/test_float_domain_gpu.py, tests/test_float_domain_cpu.py; no exception known).
  *
  * The meter is part of ABI 1.6 (see at3hip.h): a host that needs it looks for the symbol at3hip_loudness_create.
  */

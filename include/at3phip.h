@@ -276,7 +276,10 @@ int at3phip_encode_frames_short(at3phip_ctx* ctx, const int16_t* pcm, int32_t n_
  * State carried per stream between calls, of this function and of at3phip_encode_frames_tonal alike: the last frame's subband
  * samples and the last block; at3phip_reset clears it. Its buffers and tables are set up by the first call that needs them, not
  * by at3phip_create. Any float is accepted: every table index is masked, comparisons with a NaN are false (no candidate, no
- * wave). Added under ABI 1.6: a host looks for this symbol. */
+ * wave); records, residuals (floats as bit patterns; a NaN where the definition gives one) and the frames of
+ * at3phip_encode_frames_tonal are the definition's for each stream alone under every flag combination, and the analysis is
+ * itself again two slots after the last non-finite sample (tests/test_float_domain_gpu.py, tests/test_float_domain_cpu.py; no
+ * exception known). Added under ABI 1.6: a host looks for this symbol. */
 int at3phip_analyse_tones(at3phip_ctx* ctx, const float* bands, int32_t n_frames, at3phip_tonal_block* blocks, float* residual,
                           uint32_t flags);
 

@@ -3,7 +3,7 @@
 One table of named patterns. A pattern is a function that writes into block 3 (1024 stereo samples) of an otherwise ordinary
 stream, SIGNALS["mix"] over 12 blocks: the blocks before it fill the carried state, the blocks after it show the recovery.
 The same 12 blocks are every other layout too: 24 ATRAC1 blocks of 512, 6 ATRAC3plus frames of 2048 (mono and stereo), and
-one flat [T][C] stream for the resampler and the meter.
+one flat [T][C] stream for the resampler, the meter and the limiter. The ATRAC3plus tone analysis takes the 6 frames too.
 
 Used by tests/test_float_domain_cpu.py (oracle and restatements, sanitized, and the oracle against the reference build), by
 the `domain` family of the tools/emu drivers (kernel sources on the CPU) and by tests/test_float_domain_gpu.py.
@@ -102,7 +102,8 @@ COMPULSORY = ("clean", "e15", "subnormal", "max1")
 
 # The one exception table: (engine, pattern) -> reason. An entry replaces bit parity for that stream by the weaker contract of
 # tests/test_float_domain_gpu.py (the call succeeds, the result repeats, every other stream equals its oracle, the stream
-# equals the oracle again once the oracle equals its own clean encode). Engines: "at3", "at1", "at3p", "resample", "loudness".
+# equals the oracle again once the oracle equals its own clean encode). Engines: "at3", "at1", "at3p", "resample", "loudness",
+# "limiter" (the look-ahead limiter) and "tones" (the ATRAC3plus tone analysis: at3phip_analyse_tones, at3phip_encode_frames_tonal).
 EXCEPTIONS = {}
 assert not any(p in COMPULSORY for _, p in EXCEPTIONS)
 
@@ -440,6 +441,166 @@ def meter_bad(got, exp, names=NAMES):
     return {"z": [n for i, n in live if floats_match(z[i], ez[i]).any()],
             "results": [f"{n}:{','.join(result_mismatch(res[i], eres[i]))}" for i, n in live if result_mismatch(res[i], eres[i])],
             "apply": [n for i, n in live if floats_match(out[i], eout[i]).any()]}
+
+
+LIMITER_T = 6000
+LIMITER_CUTS = (3100, 3100 + 71, LIMITER_T)
+TINY = np.float32(1.4e-45)                     # the smallest subnormal
+LIMITER_CEIL = np.float32(10.0 ** (-1.0 / 20.0))   # -1 dBFS (limiter_lib.CEIL)
+# (gain, ceiling): no gain, an ordinary one, one whose every product overflows, the smallest and the largest ceiling, the smallest gain
+LIMITER_PAIRS = ((np.float32(0.0), LIMITER_CEIL), (np.float32(2.0), LIMITER_CEIL), (FLT_MAX, LIMITER_CEIL),
+                 (np.float32(2.0), TINY), (np.float32(2.0), FLT_MAX), (TINY, LIMITER_CEIL))
+LIMITER_CEILINGS = tuple(dict.fromkeys(c for _, c in LIMITER_PAIRS))
+
+
+def limiter_streams(nch, ceiling, names=NAMES):
+    """(xs [S, 6000, nch], gains [S], labels [S]) of the run with this ceiling: the gain is per stream and the ceiling per run, so
+    flat_batch() is repeated once for every gain that LIMITER_PAIRS pairs with the ceiling"""
+    gains = [g for g, c in LIMITER_PAIRS if c == ceiling]
+    assert gains, ceiling
+    one = flat_batch(nch, LIMITER_T, names)
+    xs = np.ascontiguousarray(np.concatenate([one] * len(gains)))
+    return xs, np.repeat(np.array(gains, np.float32), len(names)), [f"{n}@g={float(g):g}" for g in gains for n in names]
+
+
+def limiter_run(lib_path, nch, true_peak, ceiling, names=NAMES, cuts=(LIMITER_T,)):
+    """(samples [S, 6000, nch], [(min S, limited count)] per stream) of one limiter run: calls ending at `cuts`, then the flush"""
+    from atracdenc_amd.binding import HipLoudness
+    xs, gains, _ = limiter_streams(nch, ceiling, names)
+    S, T = xs.shape[:2]
+    m = HipLoudness(channels=nch, n_streams=S, max_in=T, max_hops=1, lib_path=lib_path)
+    try:
+        m.limit_start(gains, ceiling, true_peak)
+        parts, at = [], 0
+        for cut in tuple(cuts) + (None,):
+            out = _sent((S * T * nch,), np.float32)
+            if cut is None:
+                n = m.limit_flush_ptr(out.ctypes.data, 0)
+            else:
+                piece = np.ascontiguousarray(xs[:, at:cut])
+                n = m.limit_ptr(piece.ctypes.data, cut - at, out.ctypes.data, 0)
+                at = cut
+            assert (out[S * n * nch:].view(np.uint32) == SENT_F32).all(), "samples past the outputs were written"
+            parts.append(out[:S * n * nch].reshape(S, n, nch))
+        st = m.limit_stats()
+        assert all(s.n_out == T for s in st), [s.n_out for s in st]
+    finally:
+        m.close()
+    return np.concatenate(parts, axis=1), [(s.min_sum, s.n_limited) for s in st]
+
+
+def limiter_expect(nch, true_peak, ceiling, names=NAMES):
+    """(samples [S, 6000, nch], [(min S, limited count)]) of tests/host/limiter_cpu.c, each stream alone"""
+    import limiter_lib as LM
+
+    def make():
+        xs, gains, _ = limiter_streams(nch, ceiling, names)
+        return LM.restate_all(xs, gains, ceiling, true_peak)
+    return _once(("limiter", nch, bool(true_peak), float(ceiling), names), make)
+
+
+def limiter_bad(got, exp, nch, ceiling, names=NAMES):
+    """the labels (pattern@g=gain) of the streams whose samples (bit patterns, a NaN against a NaN) or statistics differ"""
+    import limiter_lib as LM
+    labels = limiter_streams(nch, ceiling, names)[2]
+    return [labels[i] for i in LM.bad_streams(got[0], got[1], *exp) if ("limiter", labels[i].split("@")[0]) not in EXCEPTIONS]
+
+
+TONES_SPLIT = (2, 1, 3)
+
+
+def tones_modes(nch):
+    """(gated, shared) of the runs: sharing is a stereo tool; one mono run shows that the flag changes nothing there"""
+    return ((False, False), (True, False), (False, True), (True, True)) if nch == 2 else ((False, False), (True, False), (False, True))
+
+
+def _tones_writer(lib_path):
+    """the frame writer of at3p_gha_lib.pipeline that prices the block (at3phip_write_frames_tonal, pinned to the reference by
+    tests/test_at3p_tonal_*), one stream at a time"""
+    from atracdenc_amd.binding import At3pHip
+
+    def write(specs, recs):
+        one = At3pHip(n_streams=1, max_frames=specs.shape[0], channels=specs.shape[1], lib_path=lib_path)
+        try:
+            return one.write_frames(specs[None], None, recs[None])[0]
+        finally:
+            one.close()
+    return write
+
+
+def tones_run(lib_path, nch, gated, shared, names=NAMES, split=None):
+    """(records [S, 6], residuals [S, 6, nch, 16, 128], frames [S, 6, 2048]) of one context over at3p_batch(nch): analyse_tones on
+    its own pqf(), then after a reset encode_frames_tonal, both fed whole or as `split`"""
+    from atracdenc_amd.binding import AT3P_TONAL_BLOCK_DTYPE, At3pHip, _tone_flags
+    pcm = at3p_batch(nch, names)
+    S, nf = pcm.shape[:2]
+    fl = _tone_flags(gated, shared)
+    enc = At3pHip(n_streams=S, max_frames=nf, channels=nch, lib_path=lib_path)
+    try:
+        bands = enc.pqf(pcm)
+        recs, resid, frames, at = [], [], [], 0
+        for k in (split or (nf,)):
+            piece = np.ascontiguousarray(bands[:, at:at + k])
+            b = _sent((S, k, AT3P_TONAL_BLOCK_DTYPE.itemsize), np.uint8)
+            r = _sent(piece.shape, np.float32)
+            enc.analyse_tones_ptr(piece.ctypes.data, k, b.ctypes.data, r.ctypes.data, fl)
+            recs.append(b.view(AT3P_TONAL_BLOCK_DTYPE).reshape(S, k))
+            resid.append(r)
+            at += k
+        enc.reset()
+        at = 0
+        for k in (split or (nf,)):
+            piece = np.ascontiguousarray(pcm[:, at:at + k])
+            out = _sent((S, k, 2048), np.uint8)
+            enc.encode_frames_tonal_ptr(piece.ctypes.data, k, out.ctypes.data, fl)
+            frames.append(out)
+            at += k
+    finally:
+        enc.close()
+    return np.concatenate(recs, axis=1), np.concatenate(resid, axis=1), np.concatenate(frames, axis=1)
+
+
+def tones_analysis(nch, gated, shared, names=NAMES):
+    """(records [S, 6], residuals [S, 6, nch, 16, 128]) of tests/host/at3p_gha_cpu.c on the oracle's subbands, each stream alone"""
+    import at3p_gha_lib as G
+
+    def make():
+        res = [G.CpuToneAnalyser(nch, gated, shared).analyse(G.pqf_bands(pcm)) for pcm in at3p_batch(nch, names)]
+        return np.stack([r[0] for r in res]), np.stack([r[1] for r in res])
+    return _once(("tones", nch, bool(gated), bool(shared), names), make)
+
+
+def tones_expect(lib_path, nch, gated, shared, names=NAMES):
+    """(records, residuals, frames [S, 6, 2048]): tones_analysis(), and the frames at3p_gha_lib.pipeline builds from them (the
+    division by 32768 / 1.122018, the oracle's MDCT and writer, the block spliced in), each stream alone. Where a block does not
+    fit beside the oracle's quant units (stereo e15: 48 waves at the largest AmpSf), the stream's frames come from the writer of
+    `lib_path`, which prices the block."""
+    import at3p_gha_lib as G
+
+    def make():
+        recs, resid = tones_analysis(nch, gated, shared, names)
+        frames = []
+        for i in range(len(names)):
+            with np.errstate(all="ignore"):
+                specs = G.residual_specs(resid[i])
+            wrecs, out = G.writer_records(recs[i]), []
+            for fr, rec in zip(G.at3p_write_frames(specs), wrecs):
+                b = G.block_dict(rec, nch)
+                out.append(fr if b is None else G.splice_tonal(fr, G.tonal_bits(nch, b)))
+            priced = any(fr is None for fr in out)
+            assert not priced or (nch == 2 and names[i] == "e15"), (names[i], nch)
+            frames.append(_tones_writer(lib_path)(specs, wrecs) if priced else np.stack(out))
+        return recs, resid, np.stack(frames)
+    return _once(("tones frames", lib_path, nch, bool(gated), bool(shared), names), make)
+
+
+def tones_bad(got, exp, names=NAMES):
+    """{"records" | "residuals" | "frames": the names of the streams that differ from the restatement of that stream alone}:
+    records and frames byte for byte, residuals by floats_match"""
+    live = [(i, n) for i, n in enumerate(names) if ("tones", n) not in EXCEPTIONS]
+    return {"records": [n for i, n in live if got[0][i].tobytes() != exp[0][i].tobytes()],
+            "residuals": [n for i, n in live if floats_match(got[1][i], exp[1][i]).any()],
+            "frames": [n for i, n in live if not np.array_equal(got[2][i], exp[2][i])]}
 
 
 # ---- the real reference build on the patterns, in a child process ----------------------------------------------------------

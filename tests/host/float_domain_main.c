@@ -7,7 +7,8 @@
  *     int32 n_patterns, int32 n_blocks (12), int32 meter_samples (52920)
  *     per pattern: char name[16], float pcm[n_blocks][1024][2], float meter[meter_samples][2]
  * Every pattern goes through every CPU definition a GPU engine is compared with: the three encoder oracles (oracle/*.c) in
- * the settings of tests/test_float_domain_gpu.py, tests/host/resample_cpu.c and tests/host/loudness_cpu.c. Each run is
+ * the settings of tests/test_float_domain_gpu.py, tests/host/resample_cpu.c, tests/host/loudness_cpu.c, tests/host/limiter_cpu.c
+ * (both detectors, six pairs of gain and ceiling) and tests/host/at3p_gha_cpu.c (every flag combination). Each run is
  * made twice and must give the same bytes (a read of uninitialised memory that no sanitizer of this build sees shows as
  * a difference). Exit status 0 and no sanitizer report is a pass; the program itself reports only nondeterminism. */
 #include <stdint.h>
@@ -15,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "../../include/at3phip.h"
 #include "../../oracle/at3_oracle.h"
 
 int at1o_encode(const float* pcm, int nch, int n_blocks, int window_auto, int window_mask, int bfu_idx_const, uint8_t* out,
@@ -37,6 +39,15 @@ typedef struct ld_result {
 } ld_result;
 void ld_hops(const float* x, int64_t T, int C, double* z);
 void ld_measure(const float* x, int64_t T, int C, int true_peak, ld_result* r);
+
+void ld_tp_table(float* out);
+void lim_run(const float* x, int64_t T, int C, float g, float c, const float* hp, float* y, int64_t* S_out, double* r_out,
+             int64_t* stats);
+
+size_t at3pg_state_bytes(void);
+void at3pg_reset(void* state);
+void at3pg_analyse(void* state, int C, const float* bands, int n, at3phip_tonal_block* blocks, float* residual, uint32_t flags,
+                   int8_t* intervals, int32_t* found);
 
 enum { kBlock = 1024, kMaxBlocks = 64 };
 
@@ -177,6 +188,69 @@ static void run_meter(const char* pat, const float* meter2, int T)
     free(x); free(z[0]); free(z[1]);
 }
 
+/* tests/host/limiter_cpu.c on the first 6000 samples, both detectors, float_domain_lib.LIMITER_PAIRS */
+static void run_limiter(const char* pat, const float* pcm2)
+{
+    enum { T = 6000 };
+    const float ceil1 = 0.8912509381337456f, tiny = 1.4e-45f, big = 3.4028234663852886e38f;   /* -1 dBFS, the smallest subnormal, FLT_MAX */
+    const float pairs[6][2] = {{0.0f, ceil1}, {2.0f, ceil1}, {big, ceil1}, {2.0f, tiny}, {2.0f, big}, {tiny, ceil1}};
+    static float hp[4 * 144];
+    ld_tp_table(hp);
+    float* x = xmalloc(sizeof(float) * T * 2);
+    float* y[2];
+    for (int k = 0; k < 2; ++k) y[k] = xmalloc(sizeof(float) * T * 2);
+    for (int nch = 1; nch <= 2; ++nch) {
+        channel_of(pcm2, T, nch, x);
+        for (int tp = 0; tp < 2; ++tp)
+            for (int p = 0; p < 6; ++p) {
+                int64_t stats[2][2];
+                for (int k = 0; k < 2; ++k) {
+                    memset(y[k], 0xA5, sizeof(float) * T * 2);
+                    lim_run(x, T, nch, pairs[p][0], pairs[p][1], tp ? hp : NULL, y[k], NULL, NULL, stats[k]);
+                }
+                same(pat, "limited samples", y[0], y[1], sizeof(float) * T * nch);
+                same(pat, "limiter statistics", stats[0], stats[1], sizeof(stats[0]));
+            }
+    }
+    free(x); free(y[0]); free(y[1]);
+}
+
+/* tests/host/at3p_gha_cpu.c on the oracle's subbands of the 6 frames, every combination of the two flags */
+static void run_tones(const char* pat, const float* pcm2, int nb)
+{
+    const int nf = nb / 2;
+    float* x = xmalloc(sizeof(float) * nf * 2048);
+    float* one = xmalloc(sizeof(float) * nf * 2048);
+    float* bands = xmalloc(sizeof(float) * nf * 2 * 2048);
+    void* state = xmalloc(at3pg_state_bytes());
+    at3phip_tonal_block* blocks[2];
+    float* resid[2];
+    for (int k = 0; k < 2; ++k) {
+        blocks[k] = xmalloc(sizeof(at3phip_tonal_block) * nf);
+        resid[k] = xmalloc(sizeof(float) * nf * 2 * 2048);
+    }
+    for (int nch = 1; nch <= 2; ++nch) {
+        for (int c = 0; c < nch; ++c) {
+            for (int i = 0; i < nf * 2048; ++i) x[i] = pcm2[2 * i + c];
+            at3po_pqf_analyse(x, nf, one);
+            for (int f = 0; f < nf; ++f) memcpy(bands + ((size_t)f * nch + c) * 2048, one + (size_t)f * 2048, sizeof(float) * 2048);
+        }
+        for (uint32_t flags = 0; flags < 4; ++flags) {
+            const uint32_t fl = ((flags & 1) ? AT3PHIP_TONES_GATED : 0) | ((flags & 2) ? AT3PHIP_TONES_SHARED : 0);
+            for (int k = 0; k < 2; ++k) {
+                memset(blocks[k], 0, sizeof(at3phip_tonal_block) * nf);
+                memset(resid[k], 0xA5, sizeof(float) * nf * 2 * 2048);
+                at3pg_reset(state);
+                at3pg_analyse(state, nch, bands, nf, blocks[k], resid[k], fl, NULL, NULL);
+            }
+            same(pat, "tonal records", blocks[0], blocks[1], sizeof(at3phip_tonal_block) * nf);
+            same(pat, "tone residuals", resid[0], resid[1], sizeof(float) * nf * nch * 2048);
+        }
+    }
+    free(x); free(one); free(bands); free(state);
+    for (int k = 0; k < 2; ++k) { free(blocks[k]); free(resid[k]); }
+}
+
 int main(int argc, char** argv)
 {
     if (argc != 2) { fprintf(stderr, "usage: %s FILE\n", argv[0]); return 2; }
@@ -202,6 +276,8 @@ int main(int argc, char** argv)
         run_at3p(name, pcm, nb);
         run_resample(name, pcm);
         run_meter(name, meter, T);
+        run_limiter(name, pcm);
+        run_tones(name, pcm, nb);
         printf("%s done\n", name);
     }
     free(pcm); free(meter);

@@ -5,6 +5,7 @@
   * the signals of the property tests, and the batch, the cuts and the driver that the GPU tests and the SIMT-harness driver
     share: a run through binding.HipLoudness against the restatement of every stream alone.
 """
+import concurrent.futures
 import ctypes
 import os
 import subprocess
@@ -123,6 +124,32 @@ def batch(channels, true_peak):
     xs[2, 0] = -0.9
     # (+ 0.0: a 16-bit zero has no sign)
     return np.ascontiguousarray(np.round(np.clip(xs, -1.0, 32767.0 / 32768.0) * 32768.0) / 32768.0 + 0.0, np.float32)
+
+
+SEVEN = (("clicks", 4.0), ("noise", 0.25), ("burst", 4.0), ("fs4", 1.0), ("tone40", 2.0), ("tone997", 3.0), ("clicks", 1.5))
+SEVEN_FIRST = 3400
+
+
+def seven(T, channels):
+    """(xs float32 [7][T][channels], gains [7]): seven distinct streams of any length for the tests that choose their own sizes,
+    samples 3400 .. 3400 + T of signal()'s stereo form, mono taking its channel 0 (the first click of `clicks` falls near sample
+    600 and `burst` is loud up to 2600, so that stream 0 of 3000 samples is limited, and not everywhere); stream 1 is never
+    limited"""
+    n = max(SEVEN_FIRST + T, 2 * RATE)   # (signal() places its clicks by the length it is asked for)
+    xs = np.stack([signal(kind, n, 2, 5 + i)[SEVEN_FIRST:SEVEN_FIRST + T, :channels] for i, (kind, _) in enumerate(SEVEN)])
+    return np.ascontiguousarray(xs), np.array([g for _, g in SEVEN], np.float32)
+
+
+def restate_all(xs, gains, c, true_peak):
+    """the restatement of every stream alone: (ys [S][T][C], [(min S, limited count)]). The streams run side by side on up to
+    eight threads (the C call holds no lock): the naive window minimum is 2426 steps per sample."""
+    cpu_lib(), tp_table()   # compiled and loaded before the threads start
+    cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():   # (the SIMT-harness drivers run as children of one core each)
+        cores = min(cores, int(os.environ["OMP_NUM_THREADS"]))
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(8, cores, xs.shape[0]))) as pool:
+        res = list(pool.map(lambda i: restate(xs[i], gains[i], c, true_peak), range(xs.shape[0])))
+    return np.stack([r[0] for r in res]), [r[3] for r in res]
 
 
 def cuts_for(rng, T, true_peak):

@@ -1,5 +1,7 @@
 """The tone analysis kernels with AT3PHIP_TONES_GATED (at3p_gha.hpp: k_at3p_tone_find<true>, k_at3p_tone_select, k_at3p_tone_sub,
-k_at3p_tone_state) run lane by lane through the CPU SIMT harness against the C restatement tests/host/at3p_gha_cpu.c."""
+k_at3p_tone_state) run lane by lane through the CPU SIMT harness against the C restatement tests/host/at3p_gha_cpu.c; and the
+analysis under every flag combination on tests/float_domain_lib.py's streams (NaN, infinities, +-FLT_MAX, overflowing and
+subnormal samples)."""
 import os
 
 import pytest
@@ -26,3 +28,29 @@ def test_harness_driver_equals_the_gated_restatement():
             assert "points [0, 0, 6, 0, 0, 0]" in out   # the stereo crafted cases: three bands of two channels in the record of slot 2
     finally:
         runs.close()
+
+
+DOMAIN = {"domain:1": 3 * 2 * 3, "domain:2": 4 * 2 * 3}   # flag combinations x call patterns x (records, residuals, frames)
+DOMAIN_ENV = {"high": {"EMU_FENCE": "high"}, "reverse": {"EMU_ORDER": "reverse"}}
+
+
+@pytest.fixture(scope="module")
+def domain_children():
+    build_strict()
+    c = Children({(m, case): ("run_emu_at3p_gha.py", [case, "--nobuild"], env) for case in DOMAIN for m, env in DOMAIN_ENV.items()})
+    yield c
+    c.close()
+
+
+@needs_clang
+@pytest.mark.parametrize("mode", list(DOMAIN_ENV))
+@pytest.mark.parametrize("case", list(DOMAIN))
+def test_float_domain(domain_children, mode, case):
+    """domain:C: one stream per pattern of tests/float_domain_lib.py (NaN, infinities, +-FLT_MAX, overflowing and subnormal samples
+    in frame 1 of 6) side by side, plain, gated, shared and gated + shared (mono: sharing once, where it changes nothing), whole
+    and split 2 + 1 + 3: the records of analyse_tones byte for byte, its residuals as bit patterns (a NaN against a NaN) and the
+    frames of encode_frames_tonal against the restatement of each stream alone - with every device buffer ending at a guard
+    page, and with the wavefronts of a workgroup in descending order."""
+    out = domain_children.output((mode, case))
+    assert_clean(out, DOMAIN[case])
+    assert out.count(f"domain nch={case[-1]}") == DOMAIN[case] // 3

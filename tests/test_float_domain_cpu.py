@@ -5,6 +5,9 @@ overflow f32, subnormals in block 3 of an ordinary stream).
     tests/host/float_domain_main.c, built with -fsanitize=address,undefined,float-cast-overflow, runs them all as a child
     process and must exit 0 without a report (a float -> int cast of a NaN or of an out-of-range value, which x86 answers
     with INT_MIN and the GPU with 0 or a saturated value, is a report);
+  * what the limiter's and the tone analysis' restatements give on the patterns is enough to compare on (streams are limited,
+    and not everywhere; the 48-wave budget binds; NaN residuals are followed by finite slots that hold waves), and the
+    sentences of their headers about NaN and infinite samples that can be read off a restatement's output hold;
   * where the reference build exists (oracle/_ref), the oracle equals the real reference on every pattern: ATRAC3 at LP2
     and LP4 and ATRAC1. The reference runs in a child process, twice per setting.
 
@@ -25,7 +28,8 @@ from at3_testlib import at1_oracle_encode, have_ref
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SOURCES = [os.path.join(HERE, "host", "float_domain_main.c"), os.path.join(HERE, "host", "resample_cpu.c"),
-           os.path.join(HERE, "host", "loudness_cpu.c")] + [os.path.join(ROOT, "oracle", n) for n in
+           os.path.join(HERE, "host", "loudness_cpu.c"), os.path.join(HERE, "host", "limiter_cpu.c"),
+           os.path.join(HERE, "host", "at3p_gha_cpu.c")] + [os.path.join(ROOT, "oracle", n) for n in
                                                              ("at3_oracle.c", "at1_oracle.c", "at3p_oracle.c", "at3p_frame_oracle.c")]
 SANITIZE = "-fsanitize=address,undefined,float-cast-overflow"
 
@@ -73,6 +77,112 @@ def test_oracles_and_restatements_sanitized(tmp_path):
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     assert f"FLOAT DOMAIN OK: {len(FD.NAMES)} patterns" in r.stdout
     assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
+@pytest.mark.parametrize("nch", [1, 2], ids=["mono", "stereo"])
+def test_limiter_restatement_properties(nch):
+    """What tests/host/limiter_cpu.c gives on the patterns, from the restatement alone: the comparisons of the harness and of the
+    GPU with it are not vacuous (streams are limited, and not everywhere; NaNs reach the output), and the sentences of step 8 of
+    include/at3hip_loudness.h that can be read off the output hold."""
+    import limiter_lib as LM
+    xs = FD.flat_batch(nch, FD.LIMITER_T)
+    ix = {n: i for i, n in enumerate(FD.NAMES)}
+    T, at = FD.LIMITER_T, FD.BAD_BLOCK * 1024 + 500   # (_nan1, _inf_pair and _max1 write sample 500 of the block, channel 0)
+
+    def run(name, g, c, tp):
+        return LM.restate(xs[ix[name]], g, c, tp)
+
+    def stats(g, c, tp):
+        return {n: run(n, g, c, tp)[3] for n in FD.NAMES}
+
+    def nans(name, g, c, tp):
+        return int(np.isnan(run(name, g, c, tp)[0]).sum())
+
+    c1 = FD.LIMITER_CEIL
+    for tp in (False, True):
+        # g = 2 at -1 dBFS: the ordinary stream is limited about half of the time, an infinity takes S to 0
+        st = stats(2.0, c1, tp)
+        assert st["clean"][1] == (2935 if tp else 2934) and 0 < st["clean"][0] < LM.FULL, st["clean"]
+        assert st["inf_pair"][0] == 0
+        # g = 0: e = 0 * inf = NaN, r = 1: nothing is limited, an infinity least of all; inf * 0 is the output's only NaN
+        st = stats(0.0, c1, tp)
+        assert all(v == (LM.FULL, 0) for v in st.values()), st
+        assert nans("inf_pair", 0.0, c1, tp) == 2
+        # g = FLT_MAX: every product overflows or nearly so, all outputs are limited; where s is 0 the product is inf * 0
+        st = stats(FD.FLT_MAX, c1, tp)
+        assert all(v[1] == T for v in st.values()), st
+        assert nans("e15", FD.FLT_MAX, c1, tp) == nans("e19_alt", FD.FLT_MAX, c1, tp) == 1024 * nch
+        # the ceiling FLT_MAX: only an infinity or 2 * FLT_MAX passes it: inf_pair and max1 with either detector, max_alt, inf_left
+        # and mixed with the sample detector at least (the filter turns some of theirs into NaN); 2 * FLT_MAX needs exactly 1 / 2
+        st = stats(2.0, FD.FLT_MAX, tp)
+        limited = {n for n, v in st.items() if v[1]}
+        assert {"inf_pair", "max1"} <= limited <= {"inf_pair", "max1", "max_alt", "inf_left", "mixed"}, limited
+        assert tp or len(limited) == 5
+        assert st["max1"][0] * 2 == LM.FULL and 0 < st["max1"][1] < T
+        # the smallest ceiling limits everything, the smallest gain only where a sample is infinite
+        assert all(v[1] == T for v in stats(2.0, FD.TINY, tp).values())
+        st = stats(FD.TINY, c1, tp)
+        assert st["inf_pair"][0] == 0 and st["clean"] == st["max1"] == st["e15"] == (LM.FULL, 0), st
+        # a NaN sample does not limit, whether one or a whole block of them, read by the true-peak filter or not
+        assert st["nan1"] == st["nan_block"] == st["nan_bits"] == (LM.FULL, 0), st
+    # ... and with the sample detector it leaves S what it is for the ordinary stream, and passes through as the only NaN
+    y, S, _, _ = run("nan1", 2.0, c1, False)
+    assert np.array_equal(S, run("clean", 2.0, c1, False)[1])
+    assert np.isnan(y[at, 0]) and int(np.isnan(y).sum()) == 1
+    # the sample detector around an infinity: S = 0 from the sample to the end of the hold, NaN at the sample itself (inf * 0)
+    # and +-0 with the input's sign around it
+    y, S, _, _ = run("inf_pair", 2.0, c1, False)
+    assert S[at - 1] > 0 and (S[at:at + LM.H + 1] == 0).all()
+    assert np.isnan(y[at, 0]) and np.isnan(y[at + 2, 0]) and int(np.isnan(y).sum()) == 2
+    rest, x = np.ones((LM.H + 1, nch), bool), xs[ix["inf_pair"], at:at + LM.H + 1]
+    rest[0, 0] = rest[2, 0] = False
+    zeros = y[at:at + LM.H + 1][rest]
+    assert (zeros == 0).all() and np.array_equal(np.signbit(zeros), np.signbit(x[rest])) and np.signbit(zeros).any() and not np.signbit(zeros).all()
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
+@pytest.mark.parametrize("nch", [1, 2], ids=["mono", "stereo"])
+def test_tones_restatement_properties(oracle, nch):
+    """What tests/host/at3p_gha_cpu.c gives on the patterns (12 streams x 6 frames, the pattern in frame 1), from the restatement
+    alone: waves, envelope points, sharing bits and non-finite residuals are there for the harness and the GPU to be compared on,
+    the 48-wave budget binds, the analysis recovers, and a band that holds a NaN gets no wave."""
+    import at3p_gha_lib as G
+    ix = {n: i for i, n in enumerate(FD.NAMES)}
+    non_finite = ("nan1", "inf_pair", "nan_block", "inf_left", "mixed", "nan_bits")
+    whole_block = ("nan_block", "inf_left", "mixed")
+    bands = [G.pqf_bands(pcm) for pcm in FD.at3p_batch(nch)]
+    for gated, shared in FD.tones_modes(nch):
+        recs, resid = FD.tones_analysis(nch, gated, shared)
+        waves = {n: [G.n_waves(b) for b in recs[i]] for n, i in ix.items()}
+        assert waves["clean"] == [nch * k for k in (1, 2, 1, 1, 1, 2)], waves["clean"]
+        assert waves["e15"] == [nch, 0, 48, 0, nch, 2 * nch], waves["e15"]           # the frame budget binds
+        amp = [sf for row in G.band_waves(recs[ix["e15"], 2], nch) for b in row for _, sf, _ in b]
+        assert max(amp) == 63                                                       # AmpSf saturates
+        for n in non_finite:
+            i = ix[n]
+            assert np.isnan(resid[i, 2]).any(), n
+            assert np.isnan(resid[i, 3]).any() == (n in whole_block), n
+            assert np.isfinite(resid[i, 4:]).all() and waves[n][4:] == [nch, 2 * nch], (n, waves[n])   # the recovery
+        if gated:
+            pts = [len(G.points(b, nch)) for b in recs[ix["clean"]]]
+            assert pts[1] > 0 and pts[3] > 0, pts
+        if shared and nch == 2:
+            assert all(len(G.shared_bands(b)) > 0 for b in recs[ix["clean"]])
+        if shared and nch == 1:
+            plain = FD.tones_analysis(nch, gated, False)
+            assert recs.tobytes() == plain[0].tobytes() and resid.tobytes() == plain[1].tobytes()   # the flag changes nothing
+        # "comparisons with a NaN are false (no candidate, no wave)": slot f is the block of frames f - 1 and f
+        holds, beside = 0, 0
+        for n, i in ix.items():
+            nan = np.isnan(bands[i]).any(axis=3)                                     # [6][C][16]
+            for f in range(1, 6):
+                got = np.array([[len(b) for b in row] for row in G.band_waves(recs[i, f], nch)])   # [C][16]
+                either = nan[f - 1] | nan[f]
+                assert not got[either].any(), (n, f, got[either])
+                holds += int(either.sum())
+                beside += int(either.any() and got.any())
+        assert holds > 0 and (beside > 0 or nch == 1)   # (stereo inf_left: channel 1 keeps its waves beside channel 0's NaNs)
 
 
 @pytest.fixture(scope="module")

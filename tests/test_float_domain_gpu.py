@@ -8,7 +8,8 @@ bad one) at once.
 Byte outputs (frames, sound units, 16-bit samples) are compared exactly, float outputs by float_domain_lib.floats_match
 (bit patterns; a NaN must meet a NaN, sign and payload not compared). Every output is filled with a sentinel before the
 call. An (engine, pattern) pair listed in float_domain_lib.EXCEPTIONS is held to the weaker contract stated there instead;
-the table is empty.
+the table is empty. The limiter and the ATRAC3plus tone analysis, which take any float by their headers' word, are held to
+their C restatements in the same way.
 
 The same inputs go through the kernel sources on the CPU first (the `domain` family of the tools/emu drivers, with guard
 pages around every buffer: tests/test_*_simt_harness.py), so an index that leaves its table shows there, not here.
@@ -28,7 +29,7 @@ def _clean(exp, names):
 def test_exception_table():
     assert not any(p in FD.COMPULSORY for _, p in FD.EXCEPTIONS)
     assert all(isinstance(r, str) and r for r in FD.EXCEPTIONS.values())
-    assert all(e in ("at3", "at1", "at3p", "resample", "loudness") and p in FD.NAMES for e, p in FD.EXCEPTIONS)
+    assert all(e in ("at3", "at1", "at3p", "resample", "loudness", "limiter", "tones") and p in FD.NAMES for e, p in FD.EXCEPTIONS)
 
 
 @pytest.mark.parametrize("br,ng,nt,nch,names", FD.AT3_CASES,
@@ -97,3 +98,44 @@ def test_meter(oracle, nch):
     for cuts in ((FD.METER_T,), FD.METER_CUTS):
         bad = FD.meter_bad(FD.meter_run(None, nch, cuts=cuts), exp)
         assert not any(bad.values()), (cuts, bad)
+
+
+def _same_floats(a, b):
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+@pytest.mark.parametrize("nch", [1, 2], ids=["mono", "stereo"])
+def test_limiter(oracle, nch):
+    """6000 samples per stream, one stream per pattern and per gain of float_domain_lib.LIMITER_PAIRS (gains 0, 2, FLT_MAX and
+    the smallest subnormal at -1 dBFS; gain 2 under the smallest subnormal and under FLT_MAX as the ceiling), both detectors:
+    samples and statistics are tests/host/limiter_cpu.c's (step 8 of the limiter's definition in include/at3hip_loudness.h), in
+    one call and in three, and a second run gives the bits of the first, NaN payloads included."""
+    for ceiling in FD.LIMITER_CEILINGS:
+        for tp in (False, True):
+            exp = FD.limiter_expect(nch, tp, ceiling)
+            assert np.isnan(exp[0]).any()                                      # (the patterns reach the output)
+            assert ceiling != FD.LIMITER_CEIL or (0 < exp[1][len(FD.NAMES)][1] < FD.LIMITER_T and min(st[0] for st in exp[1]) == 0)
+            for cuts in ((FD.LIMITER_T,), FD.LIMITER_CUTS):
+                got = FD.limiter_run(None, nch, tp, ceiling, cuts=cuts)
+                again = FD.limiter_run(None, nch, tp, ceiling, cuts=cuts)
+                assert _same_floats(got[0], again[0]) and got[1] == again[1], "the result does not repeat"
+                bad = FD.limiter_bad(got, exp, nch, ceiling)
+                assert not bad, (float(ceiling), tp, cuts, bad)
+
+
+@pytest.mark.parametrize("nch", [1, 2], ids=["mono", "stereo"])
+def test_tones(oracle, nch):
+    """12 streams x 6 frames, plain, gated, shared and gated + shared (mono: sharing once, where it changes nothing): the records
+    of analyse_tones are tests/host/at3p_gha_cpu.c's byte for byte and its residuals bit for bit (a NaN against a NaN), the
+    frames of encode_frames_tonal are those of at3p_gha_lib.pipeline, whole and split 2 + 1 + 3, and a second run repeats the
+    first ("Any float is accepted", include/at3phip.h)."""
+    for gated, shared in FD.tones_modes(nch):
+        exp = FD.tones_expect(None, nch, gated, shared)
+        assert np.isnan(exp[1]).any() and exp[0]["band"]["n_waves"].sum(axis=(2, 3)).max() == 48   # (NaN residuals; the budget binds)
+        for split in (None, FD.TONES_SPLIT):
+            got = FD.tones_run(None, nch, gated, shared, split=split)
+            again = FD.tones_run(None, nch, gated, shared, split=split)
+            assert got[0].tobytes() == again[0].tobytes() and _same_floats(got[1], again[1]) and np.array_equal(got[2], again[2]), \
+                "the result does not repeat"
+            bad = FD.tones_bad(got, exp)
+            assert not any(bad.values()), (gated, shared, split, bad)

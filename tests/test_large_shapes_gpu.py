@@ -13,7 +13,7 @@ import os
 import numpy as np
 import pytest
 
-from atracdenc_amd import At1Hip, At1HipDecoder, At3Hip, At3HipDecoder, At3HipError, At3pHip, At3pHipDecoder
+from atracdenc_amd import At1Hip, At1HipDecoder, At3Hip, At3HipDecoder, At3HipError, At3pHip, At3pHipDecoder, HipLoudness
 from atracdenc_amd.binding import AT3HIP_OUT_ON_DEVICE, AT3HIP_PCM_ON_DEVICE
 from at3_testlib import (LP2, LP4, ROOT, SIGNALS, at1_blocks, at1_oracle_encode, at3p_mdct, at3p_pqf, at3p_signal, at3p_specs,
                          at3p_write_frames, oracle_diag_counts, pcm_hot, pcm_stress)
@@ -338,6 +338,159 @@ def test_at3p_pqf_mdct_past_4gib(mem):
         enc.close()
     _assert_replicas(out, small, "ATRAC3plus spectra")
     del big_in, out, small_in, small
+
+
+def test_at3p_tonal_encode_full_grid(mem):
+    """encode_frames_tonal, mono S = 65535 x 9 frames: gridDim.y = 65535 in k_at3p_tone_find and k_at3p_tone_sub; the caller's PCM
+    and the internal subbands, residuals and spectra S * 9 * 2048 floats, 4.83e9 bytes each."""
+    import torch
+    import at3p_gha_lib as G
+    _need(48)
+    S, nf, nch = 65535, 9, 1
+    pcm = _at3p_pcm(nf, nch)                                                # [P, 9, 2048, 1]
+    want = [G.pipeline(p) for p in pcm]
+    exp = np.stack([w[0] for w in want])
+    assert sum(any(G.n_waves(b) for b in w[1]) for w in want) >= 3           # the blocks carry waves
+    small_in = _dev(pcm)
+    enc7 = At3pHip(n_streams=P, max_frames=nf, channels=nch)
+    small = _filled((P, nf, 2048), torch.uint8)
+    _sync()
+    enc7.encode_frames_tonal_device(small_in.data_ptr(), nf, small.data_ptr())
+    enc7.close()
+    assert np.array_equal(small.cpu().numpy(), exp)
+
+    big_in = _tile(small_in, S)
+    assert S * nch == 65535 and big_in.numel() * 4 > 2 ** 32
+    enc = mem.create(At3pHip, n_streams=S, max_frames=nf, channels=nch)
+    out = _filled((S, nf, 2048), torch.uint8)
+    _sync()
+    try:
+        enc.encode_frames_tonal_device(big_in.data_ptr(), nf, out.data_ptr())
+        mem.probe()
+    finally:
+        enc.close()
+    _assert_replicas(out, small, "ATRAC3plus tonal frames")
+    del big_in, out, small_in, small
+
+
+def test_at3p_analyse_tones_past_4gib(mem):
+    """analyse_tones with AT3PHIP_TONES_GATED | AT3PHIP_TONES_SHARED on device buffers, stereo S = 32767 x 9 frames: gridDim.y =
+    65534; the caller's subbands and residuals S * 9 * 2 * 2048 floats, 4.83e9 bytes each; the records of all S * 9 slots in host
+    memory."""
+    import torch
+    import at3p_gha_lib as G
+    from atracdenc_amd.binding import AT3P_TONAL_BLOCK_DTYPE
+    _need(48)
+    S, nf, nch = 32767, 9, 2
+    flags = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE | G.GATED | G.SHARED
+    pcm = [G.twin_pcm("tones", nf), G.keyed_pcm(nf, nch), G.twin_pcm("burst", nf), G.signal_pcm("mix", nf, nch), G.signal_pcm("noise", nf, nch),
+           G.signal_pcm("burst", nf, nch), G.signal_pcm("tones", nf, nch, 0.25)]
+    bands = np.stack([G.pqf_bands(p) for p in pcm])                          # [P, 9, 2, 16, 128]
+    want = [G.CpuToneAnalyser(nch, True, True).analyse(b) for b in bands]
+    exp_recs, exp_resid = np.stack([w[0] for w in want]), np.stack([w[1] for w in want])
+    assert sum(len(G.shared_bands(b)) for b in exp_recs.reshape(-1)) > 0     # sharing bits ...
+    assert sum(len(G.points(b, nch)) for b in exp_recs.reshape(-1)) > 0      # ... and envelope points are there
+    assert sum(G.n_waves(b) for b in exp_recs.reshape(-1)) > 0
+
+    def run(enc, d_bands, n):
+        recs = np.full((n, nf, AT3P_TONAL_BLOCK_DTYPE.itemsize), SENTINEL_U8, np.uint8)
+        resid = _filled((n, nf, nch, 16, 128), torch.float32)
+        _sync()
+        enc.analyse_tones_ptr(d_bands.data_ptr(), nf, recs.ctypes.data, resid.data_ptr(), flags)
+        return recs.reshape(n, -1), resid
+
+    small_in = _dev(bands)
+    enc7 = At3pHip(n_streams=P, max_frames=nf, channels=nch)
+    recs7, resid7 = run(enc7, small_in, P)
+    enc7.close()
+    assert recs7.tobytes() == exp_recs.tobytes()
+    assert np.array_equal(resid7.cpu().numpy().view(np.uint32), exp_resid.view(np.uint32))
+
+    big_in = _tile(small_in, S)
+    assert S * nch == 65534 and big_in.numel() * 4 > 2 ** 32
+    enc = mem.create(At3pHip, n_streams=S, max_frames=nf, channels=nch)
+    try:
+        recs, resid = run(enc, big_in, S)
+        mem.probe()
+    finally:
+        enc.close()
+    assert resid.numel() * 4 > 2 ** 32
+    for r in range(P):
+        bad = np.nonzero((recs[r::P] != recs7[r]).any(axis=1))[0]
+        assert bad.size == 0, f"records of streams {(r + P * bad[:4]).tolist()} differ from the small run's stream {r}"
+    _assert_replicas(resid, resid7, "ATRAC3plus tone residuals")
+    del big_in, resid, small_in, resid7
+
+
+# ---- the limiter ----------------------------------------------------------------------------------------------------------------
+def _limit_large(mem, S, nch, true_peak, T, max_in, calls):
+    """The recipe for the limiter: limiter_lib.seven() through a context of P streams (checked against the restatement) and, tiled,
+    through one of S streams, in calls ending at `calls` and the flush: every replica's samples, limit_stats of every stream
+    and n_out. Returns (bytes of the large input, bytes of its outputs without the flush)."""
+    import torch
+    import limiter_lib as LM
+    xs, gains = LM.seven(T, nch)
+    want_y, want_st = LM.restate_all(xs, gains, LM.CEIL, true_peak)
+    assert 0.1 < want_st[0][1] / T < 0.95, want_st[0]                       # stream 0 is limited, and not everywhere
+    assert want_st[1] == (LM.FULL, 0)                                        # stream 1 never
+    d = LM.delay(true_peak)
+    assert max(b - a for a, b in zip((0,) + calls, calls)) <= max_in
+
+    def run(n, d_in, create):
+        m = create(HipLoudness, channels=nch, n_streams=n, max_in=max_in, max_hops=1)
+        try:
+            m.limit_start(np.resize(gains, n), LM.CEIL, true_peak)
+            outs, at = [], 0
+            for cut in calls:
+                piece = d_in[:, at:cut].contiguous() if (at, cut) != (0, T) else d_in
+                out = _filled((n * (cut - at) * nch,), torch.float32)
+                k = m.limit_device(piece, out)
+                assert k == max(0, cut - d) - max(0, at - d)
+                assert bool(torch.isnan(out[n * k * nch:]).all())            # nothing past the outputs
+                outs.append(out[:n * k * nch].view(n, k, nch))
+                del piece
+                at = cut
+            tail = _filled((n, d, nch), torch.float32)
+            assert m.limit_flush_device(tail) == d
+            st = m.limit_stats()
+            mem.probe()
+        finally:
+            m.close()
+        return outs, tail, st
+
+    small_in = _dev(xs)
+    outs7, tail7, st7 = run(P, small_in, lambda f, **kw: f(**kw))
+    y7 = np.concatenate([o.cpu().numpy() for o in outs7] + [tail7.cpu().numpy()], axis=1)
+    assert LM.bad_streams(y7, [(s.min_sum, s.n_limited) for s in st7], want_y, want_st) == []
+    assert all(s.n_out == T for s in st7)
+
+    big_in = _tile(small_in, S)
+    outs, tail, st = run(S, big_in, mem.create)
+    for o, o7 in zip(outs, outs7):
+        if o7.shape[1]:
+            _assert_replicas(o, o7, "limited samples")
+    _assert_replicas(tail, tail7, "the limiter's flush")
+    got = np.array([(s.min_sum, s.n_limited, s.n_out) for s in st], np.int64)
+    exp = np.array([want_st[r] + (T,) for r in range(P)], np.int64)[np.arange(S) % P]
+    assert np.array_equal(got, exp), np.nonzero((got != exp).any(axis=1))[0][:8]
+    return big_in.numel() * 4, [o.numel() * 4 for o in outs]
+
+
+def test_limiter_past_4gib(mem):
+    """stereo, true-peak detector, S = 4200 x 131072 samples in one call: the caller's input and output past 4 GiB even without
+    their last stream ((S - 1) * n_in * 8 and (S - 1) * (n_in - 292) * 8 bytes); two q rows of 2645 + n_in words per stream."""
+    _need(20)
+    S, n_in = 4200, 131072
+    assert (S - 1) * n_in * 8 > 2 ** 32 and (S - 1) * (n_in - 292) * 8 > 2 ** 32
+    in_bytes, out_bytes = _limit_large(mem, S, 2, True, n_in, n_in, (n_in,))
+    assert in_bytes == S * n_in * 8 and out_bytes == [S * (n_in - 292) * 8]
+
+
+def test_limiter_full_grid(mem):
+    """mono, sample detector, S = 65535 (gridDim.y at its limit in every kernel), max_in = 3000, 3000 samples in calls of 1500"""
+    _need(4)
+    S = 65535
+    _limit_large(mem, S, 1, False, 3000, 3000, (1500, 3000))
 
 
 # ---- decoders: shared driver --------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 to the C restatement tests/host/limiter_cpu.c on limiter_lib.batch() - 3 streams of two gain-kernel tiles plus 1237 samples, a
 gain per stream (one stream never limited), peaks on both sides of the tile edge and within the look-ahead of the stream's start
 and end - from float and 16-bit input, in one call and in cuts; device tensors and streams, the overlap rule, independence of
-the meter, bad arguments."""
+the meter, bad arguments; contexts whose max_in is smaller than the filter and the carries, and k_limit_gain's scalar path behind
+device pointers that are only 4-byte (16-bit input: 2-byte) aligned."""
 import ctypes
 
 import numpy as np
@@ -86,6 +87,83 @@ def test_device_tensors(side_stream):
         assert LM.bad_streams(y, st, want_y, want_st) == []
     finally:
         m.close()
+
+
+@pytest.mark.parametrize("true_peak", [False, True], ids=["sample", "true_peak"])
+@pytest.mark.parametrize("max_in,T", [(1, 330), (71, 3000), (293, 3000)])
+def test_limiter_small_max_in(max_in, T, true_peak):
+    """contexts whose max_in is below the filter's half length (72), below the carried samples (292) and just above them, fed in
+    calls of max_in samples: the q rows, the output staging and the carries are sized by the larger of max_in and the carry"""
+    C = 2
+    xs, gains = LM.seven(T, C)
+    want_y, want_st = LM.restate_all(xs, gains, LM.CEIL, true_peak)
+    if max_in == 293:
+        assert 0.1 < want_st[0][1] / T < 0.95, want_st[0]                      # limited, and not everywhere
+    assert want_st[1] == (LM.FULL, 0)
+    m = HipLoudness(channels=C, n_streams=xs.shape[0], max_in=max_in, max_hops=1)
+    try:
+        cuts = list(range(max_in, T, max_in)) + [T]
+        assert max(b - a for a, b in zip([0] + cuts, cuts)) == max_in
+        m.limit_start(gains, LM.CEIL, true_peak)
+        with pytest.raises(At3HipError, match="max_in"):
+            m.limit(xs[:, :max_in + 1])
+        m.reset()
+        y, st = LM.run_engine(m, xs, gains, LM.CEIL, true_peak, cuts)
+        assert LM.bad_streams(y, st, want_y, want_st) == [], (st, want_st)
+    finally:
+        m.close()
+
+
+def _device_window(values, offset, dtype):
+    """a device tensor of values.size + 4 elements filled with a sentinel, `values` at `offset`: (whole tensor, the window)"""
+    import torch
+    n = values.size
+    sent = 0x5A5A if dtype == torch.int16 else float("nan")
+    whole = torch.full((n + 4,), sent, dtype=dtype, device="cuda")
+    if n:
+        whole[offset:offset + n] = torch.from_numpy(np.ascontiguousarray(values).reshape(-1)).cuda()
+    return whole, whole[offset:offset + n]
+
+
+def _untouched(whole, offset, n):
+    import torch
+    rest = torch.cat([whole[:offset], whole[offset + n:]])
+    return bool(torch.isnan(rest).all()) if whole.dtype == torch.float32 else bool((rest == 0x5A5A).all())
+
+
+@pytest.mark.parametrize("true_peak", [False, True], ids=["sample", "true_peak"])
+@pytest.mark.parametrize("case", ["in", "out", "both", "s16"])
+def test_limiter_unaligned_device_buffers(case, true_peak):
+    """stereo float input and / or output one float past an 8-byte boundary (k_limit_gain's scalar loads and stores instead of
+    the 8-byte ones), and mono 16-bit input at an odd 2-byte offset: device buffers of exactly the call's size, the elements
+    around them untouched"""
+    import torch
+    s16 = case == "s16"
+    C = 1 if s16 else 2
+    xs, (want_y, want_st) = LM.batch(C, true_peak), LM.expect(C, true_peak)
+    S, T, d = xs.shape[0], LM.T_GPU, LM.delay(true_peak)
+    src = np.round(xs * 32768.0).astype(np.int16) if s16 else xs
+    off_in = 1 if case in ("in", "both", "s16") else 2
+    off_out = 1 if case in ("out", "both") else 2
+    x_all, x_dev = _device_window(src, off_in, torch.int16 if s16 else torch.float32)
+    y_all, y_dev = _device_window(np.full(S * (T - d) * C, np.nan, np.float32), off_out, torch.float32)
+    t_all, t_dev = _device_window(np.full(S * d * C, np.nan, np.float32), off_out, torch.float32)
+    assert x_dev.data_ptr() % (4 if s16 else 8) == (2 if s16 else 4 if off_in == 1 else 0)
+    assert y_dev.data_ptr() % 8 == (4 if off_out == 1 else 0) and t_dev.data_ptr() % 8 == y_dev.data_ptr() % 8
+    torch.cuda.synchronize()
+    m = meter(C)
+    try:
+        m.limit_start(LM.GAINS, LM.CEIL, true_peak)
+        n = m.limit_ptr(x_dev.data_ptr(), T, y_dev.data_ptr(), AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE, s16=s16)
+        k = m.limit_flush_ptr(t_dev.data_ptr(), AT3HIP_OUT_ON_DEVICE)
+        assert (n, k) == (T - d, d)
+        st = [(s.min_sum, s.n_limited) for s in m.limit_stats()]
+    finally:
+        m.close()
+    y = np.concatenate([y_dev.cpu().numpy().reshape(S, n, C), t_dev.cpu().numpy().reshape(S, k, C)], axis=1)
+    assert LM.bad_streams(y, st, want_y, want_st) == []
+    assert _untouched(x_all, off_in, src.size) and _untouched(y_all, off_out, S * n * C) and _untouched(t_all, off_out, S * k * C)
+    assert np.array_equal(x_dev.cpu().numpy().reshape(src.shape), src)        # the input is only read
 
 
 def test_overlapping_device_buffers_are_refused():

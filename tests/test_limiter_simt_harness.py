@@ -15,7 +15,8 @@ pytestmark = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's 
 
 CASES = {"parity:1:0": 3, "parity:1:1": 3, "parity:2:0": 3, "parity:2:1": 3, "edges": 2}   # comparisons per case
 ENV = {"default": {}, "high": {"EMU_FENCE": "high"}, "low": {"EMU_FENCE": "low"}, "reverse": {"EMU_ORDER": "reverse"}}
-DOMAIN = {"domain:1": 4, "domain:2": 4}   # tests/float_domain_lib.py's streams: NaN, infinities, +-FLT_MAX, overflow, subnormals
+# tests/float_domain_lib.py's streams: NaN, infinities, +-FLT_MAX, overflow, subnormals; 3 ceilings x 2 detectors x 2 call patterns
+DOMAIN = {"domain:1": 12, "domain:2": 12}
 JOBS = [(m, c) for c in DOMAIN for m in ("high", "reverse")] + [(m, c) for c in CASES for m in ENV]
 CASES_ALL = dict(CASES, **DOMAIN)
 
@@ -55,6 +56,8 @@ def test_reversed_wavefront_order(children, case):
 @pytest.mark.parametrize("mode", ["high", "reverse"])
 @pytest.mark.parametrize("case", list(DOMAIN))
 def test_float_domain(children, mode, case):
-    """domain:C: one stream per pattern of tests/float_domain_lib.py side by side, both detectors, one call and three: samples
-    (floats as bit patterns, a NaN against a NaN) and statistics against the restatement of each stream alone."""
+    """domain:C: one stream per pattern of tests/float_domain_lib.py and per gain side by side (float_domain_lib.LIMITER_PAIRS:
+    gains 0, 2, FLT_MAX and the smallest subnormal at -1 dBFS; gain 2 under the smallest subnormal and under FLT_MAX as the
+    ceiling), both detectors, one call and three: samples (floats as bit patterns, a NaN against a NaN) and statistics against
+    the restatement of each stream alone."""
     check(children, mode, case)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """DEVELOPMENT HARNESS: the tone analysis kernels (k_at3p_tone_find, k_at3p_tone_select, k_at3p_tone_sub, k_at3p_tone_state behind
 at3phip_analyse_tones and at3phip_encode_frames_tonal) through the CPU SIMT emulator, lane by lane, against the C restatement
-tests/host/at3p_gha_cpu.c.  usage: run_emu_at3p_gha.py [plain|gated|shared] [--nobuild]   (default: plain)
+tests/host/at3p_gha_cpu.c.  usage: run_emu_at3p_gha.py [plain|gated|shared|domain:1|domain:2] [--nobuild]   (default: plain)
   plain   records and residuals of three different streams side by side, the frames of the restatement's pipeline in one call and in
           two, the 16-bit entry point, the frame budget's crafted frame, and sines next to both ends of a subband
   gated   AT3PHIP_TONES_GATED (k_at3p_tone_find<true>): records and residuals of the crafted onsets and offsets in one call and in
@@ -9,7 +9,11 @@ tests/host/at3p_gha_cpu.c.  usage: run_emu_at3p_gha.py [plain|gated|shared] [--n
           three), and the host gate function
   shared  AT3PHIP_TONES_SHARED (k_at3p_tone_select<true>, k_at3p_tone_sub<., true>): two stereo streams side by side over 4 slots -
           one band of channel 1 differing in stream 0, an onset in stream 1 -, with and without the gates, in one call and split
-          1 + 3; and a mono stream, where the flag changes nothing"""
+          1 + 3; and a mono stream, where the flag changes nothing
+  domain:C  tests/float_domain_lib.py's 12 streams (NaN, infinities, +-FLT_MAX, overflowing and subnormal samples in frame 1) of C
+          channels side by side over 6 frames, in every flag combination (mono: sharing once, where it changes nothing), whole and
+          split 2 + 1 + 3: records, residuals (a NaN against a NaN) and the frames of encode_frames_tonal against the restatement of
+          each stream alone"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
@@ -141,8 +145,18 @@ def shared():
             shared_stereo(gated, split)
     shared_mono()
 
+def domain(nch):
+    import float_domain_lib as FD
+    for gated, shared in FD.tones_modes(nch):
+        want = FD.tones_expect(run_emu.EMU, nch, gated, shared)
+        for split in (None, FD.TONES_SPLIT):
+            t = time.time()
+            bad = FD.tones_bad(FD.tones_run(run_emu.EMU, nch, gated, shared, split=split), want)
+            print(f"domain nch={nch} gated={int(gated)} shared={int(shared)} split {split or 'whole'}: records bad {len(bad['records'])}; residuals bad {len(bad['residuals'])}; "
+                  f"frames bad {len(bad['frames'])} {({k: v for k, v in bad.items() if v}) or ''} ({time.time()-t:.1f}s)", flush=True)
+
 if __name__ == "__main__":
-    part = {"plain": plain, "gated": gated, "shared": shared}.get(next((a for a in sys.argv[1:] if not a.startswith("--")), "plain"))
+    part = {"plain": plain, "gated": gated, "shared": shared, "domain:1": lambda: domain(1), "domain:2": lambda: domain(2)}.get(next((a for a in sys.argv[1:] if not a.startswith("--")), "plain"))
     if part is None: sys.exit(__doc__)
     if "--nobuild" not in sys.argv: run_emu.build()
     part()

@@ -64,22 +64,16 @@ def edges():
 
 def domain(channels):
     """tests/float_domain_lib.py's streams (NaN, infinities, +-FLT_MAX, overflowing and subnormal samples at 3072 .. 4095) side by
-    side, 6000 samples each, both detectors, one call and three: samples (a NaN against a NaN) and statistics against the
-    restatement of each stream alone"""
+    side, 6000 samples each, under its six (gain, ceiling) pairs (one run per ceiling, a gain per stream), both detectors, one
+    call and three: samples (a NaN against a NaN) and statistics against the restatement of each stream alone"""
     import float_domain_lib as FD
-    T = 6000
-    xs = FD.flat_batch(channels, T)
-    gains = np.full(xs.shape[0], 2.0, np.float32)
-    m = HipLoudness(channels=channels, n_streams=xs.shape[0], max_in=T, max_hops=1, lib_path=EMU)
-    for true_peak in (False, True):
-        res = [LM.restate(xs[i], 2.0, LM.CEIL, true_peak) for i in range(xs.shape[0])]
-        want = (np.stack([r[0] for r in res]), [r[3] for r in res])
-        for cuts in ([T], [3100, 3100 + 71, T]):
-            t0 = time.time()
-            y, st = LM.run_engine(m, xs, gains, LM.CEIL, true_peak, cuts)
-            bad = LM.bad_streams(y, st, *want)
-            report(f"limiter domain ch{channels} tp{true_peak} cuts {cuts} {[FD.NAMES[i] for i in bad]}", len(bad), t0)
-    m.close()
+    for ceiling in FD.LIMITER_CEILINGS:
+        for true_peak in (False, True):
+            want = FD.limiter_expect(channels, true_peak, ceiling)
+            for cuts in ((FD.LIMITER_T,), FD.LIMITER_CUTS):
+                t0 = time.time()
+                bad = FD.limiter_bad(FD.limiter_run(EMU, channels, true_peak, ceiling, cuts=cuts), want, channels, ceiling)
+                report(f"limiter domain ch{channels} c={float(ceiling):g} tp{true_peak} cuts {list(cuts)} {bad}", len(bad), t0)
 
 
 CASES = {"parity:1:0": parity, "parity:1:1": parity, "parity:2:0": parity, "parity:2:1": parity, "edges": edges,
