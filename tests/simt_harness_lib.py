@@ -2,8 +2,8 @@
 
   * build_strict: the strict harness (tools/emu/run_emu.build(strict=True)), built once per test session whichever module asks
     first, and the oracle library that some drivers load.
-  * Children: the drivers under tools/emu run as child processes - the harness reads EMU_STRICT, EMU_FENCE and EMU_ORDER when
-    its library loads - several at a time, each on one core, so that the GPU-less suite stays short enough to be run.
+  * Children: the drivers under tools/emu run as child processes - the harness reads EMU_STRICT, EMU_FENCE, EMU_ORDER and EMU_STREAMS
+    when its library loads - several at a time, each on one core, so that the GPU-less suite stays short enough to be run.
 """
 import concurrent.futures
 import os
@@ -33,7 +33,7 @@ def run_script(script, args, env=None, timeout=900):
     """(exit status, output) of tools/emu/<script> under EMU_STRICT=1 and `env`; a child ended by a signal (a guard page that
     was touched, an abort of the strict checks) has a negative status"""
     e = dict(os.environ, EMU_STRICT="1", OMP_NUM_THREADS="1", **(env or {}))
-    for k in ("EMU_FENCE", "EMU_ORDER"):
+    for k in ("EMU_FENCE", "EMU_ORDER", "EMU_STREAMS"):
         if k not in (env or {}):
             e.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "emu", script), *args], capture_output=True, text=True,

@@ -5,7 +5,8 @@ allocations with how many bytes - each destroy releases exactly what was allocat
 trace on (EMU_TRACE); tools/emu/run_emu_trace.py runs one fixed script of calls per case and compares the trace with
 tests/golden/host_trace/<case>.txt, which were written from the sources of the commit before each change. How streams land on
 the few hardware queues, and with that the pipelined rates, depends on the order they are created in; the overlap of
-consecutive calls on which event is recorded and waited for where."""
+consecutive calls on which event is recorded and waited for where. The traces pin that graph as it is;
+tests/test_stream_order_simt_harness.py tests that the graph suffices."""
 import os
 import re
 

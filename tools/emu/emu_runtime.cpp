@@ -5,7 +5,9 @@
 #include <unistd.h>
 
 #include <cstdarg>
+#include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 // k_alloc_pack's harness-only counters (at3_k_alloc.hpp: AT3_STAT)
@@ -144,6 +146,7 @@ void emu_device_free(void* p)
 // ---- streams, events, copies: objects of their own, and the EMU_TRACE call trace (hip/hip_runtime.h) ----
 struct emu_event {
     int ordinal;
+    unsigned long long last_rec;   // (EMU_STREAMS) the most recent record of this event that was called, 0: none yet
 };
 namespace {
 std::mutex g_trace_mu;
@@ -179,6 +182,167 @@ std::string sname(hipStream_t s)
 std::string ename(hipEvent_t e) { return e ? "e" + std::to_string(e->ordinal) : std::string("null"); }
 const char* kname(hipMemcpyKind k) { return k == hipMemcpyHostToDevice ? "h2d" : k == hipMemcpyDeviceToHost ? "d2h" : "d2d"; }
 
+// ---- EMU_STREAMS=lazy | lazy:SEED: every stream is a queue, executed in a legal order that is not program order ----
+// (hip/hip_runtime.h has the semantics.) One lock guards all of it; an operation's body never calls back into the runtime.
+struct StreamsMode {
+    int mode = 0;   // 0 eager (today's behaviour), 1 lazy, 2 lazy with a seeded scheduler
+    unsigned long long rng = 0;
+};
+const StreamsMode& streams_mode_init()
+{
+    static const StreamsMode m = [] {
+        StreamsMode r;
+        const char* e = getenv("EMU_STREAMS");
+        if (!e || !*e) return r;
+        if (!strcmp(e, "lazy")) { r.mode = 1; return r; }
+        char* end = nullptr;
+        if (!strncmp(e, "lazy:", 5) && e[5]) {
+            r.rng = strtoull(e + 5, &end, 10) * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
+            if (end && !*end) { r.mode = 2; return r; }
+        }
+        fprintf(stderr, "emu: EMU_STREAMS must be lazy or lazy:SEED, not '%s'\n", e);
+        abort();
+    }();
+    return m;
+}
+unsigned long long g_rng = 0;
+unsigned rnd(unsigned n)   // splitmix64
+{
+    unsigned long long z = (g_rng += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return (unsigned)((z ^ (z >> 31)) >> 16) % n;
+}
+struct Op {
+    enum Kind { WORK, RECORD, WAIT } kind;
+    std::function<void()> run;        // WORK: a launch, a copy or a fill
+    unsigned long long rec = 0;       // RECORD: its id; WAIT: the record captured when the wait was called (never 0 in a queue)
+    std::string what;                 // as the trace line names it
+};
+struct Queue {
+    std::deque<Op> ops;
+    bool blocking = false;   // made without hipStreamNonBlocking, or the null stream: a blocking hipMemcpy / hipMemset waits for it
+    bool forcing = false;    // its head wait is being served further up the call stack
+    std::string name;
+};
+std::recursive_mutex g_lazy_mu;
+std::map<void*, Queue> g_queues;                     // stream handle (nullptr: the null stream) -> queue, made on first use
+std::map<unsigned long long, void*> g_pending_recs;  // records that are queued and have not executed -> their stream
+unsigned long long g_n_recs = 0;
+std::map<char*, size_t> g_pinned;                    // the hipHostMalloc ranges
+
+int lazy_mode()
+{
+    static const int mode = [] { const StreamsMode& m = streams_mode_init(); g_rng = m.rng; return m.mode; }();
+    return mode;
+}
+FILE* order_log()   // EMU_STREAMS_LOG=<file>: one line per operation when it executes, i.e. the order that was explored
+{
+    static FILE* f = [] {
+        const char* e = getenv("EMU_STREAMS_LOG");
+        return (e && *e) ? fopen(e, "a") : (FILE*)nullptr;
+    }();
+    return f;
+}
+Queue& queue_of(hipStream_t s)
+{
+    auto it = g_queues.find(s);
+    if (it != g_queues.end()) return it->second;
+    Queue& q = g_queues[s];
+    q.name = sname(s);
+    q.blocking = s == nullptr;   // a caller's stream counts as non-blocking: nothing waits for it that was not told to
+    return q;
+}
+bool pinned(const void* p, size_t n)
+{
+    auto it = g_pinned.upper_bound((char*)p);
+    if (it == g_pinned.begin()) return false;
+    --it;
+    return (char*)p + n <= it->first + it->second;
+}
+void force_record(unsigned long long rec, const Queue& for_q);
+// executes the head of q; a head that waits for a record still queued runs that record's stream first, as far as the record
+void step(Queue& q)
+{
+    Op& head = q.ops.front();
+    if (head.kind == Op::WAIT && g_pending_recs.count(head.rec)) {
+        q.forcing = true;
+        force_record(head.rec, q);
+        q.forcing = false;
+    }
+    Op op = std::move(q.ops.front());
+    q.ops.pop_front();
+    if (FILE* f = order_log()) { fprintf(f, "run %s: %s\n", q.name.c_str(), op.what.c_str()); fflush(f); }
+    if (op.kind == Op::WORK) op.run();
+    else if (op.kind == Op::RECORD) g_pending_recs.erase(op.rec);
+}
+void force_record(unsigned long long rec, const Queue& for_q)
+{
+    auto it = g_pending_recs.find(rec);
+    if (it == g_pending_recs.end()) return;
+    Queue& q = g_queues[it->second];
+    if (q.forcing) {   // the record sits behind a wait that (transitively) waits for the asking stream: it can never execute
+        fprintf(stderr, "emu: deadlock: stream %s waits (%s) for a record on stream %s, which itself waits for stream %s\n", for_q.name.c_str(),
+                for_q.ops.empty() ? "host" : for_q.ops.front().what.c_str(), q.name.c_str(), for_q.name.c_str());
+        abort();
+    }
+    while (g_pending_recs.count(rec)) step(q);
+}
+void drain(Queue& q) { while (!q.ops.empty()) step(q); }
+void drain_all()
+{
+    for (bool any = true; any;) {
+        any = false;
+        for (auto& kv : g_queues) if (!kv.second.ops.empty()) { drain(kv.second); any = true; }
+    }
+}
+void drain_blocking()
+{
+    for (auto& kv : g_queues) if (kv.second.blocking) drain(kv.second);
+}
+// lazy:SEED, before every enqueue: a random number of runnable operations from random streams
+void scheduler_turn()
+{
+    if (lazy_mode() != 2) return;
+    // (fewer on average than are queued, and all of one turn from one stream: streams fall behind and run ahead of each other,
+    // where a turn that kept up with the host would all but restore program order)
+    static const unsigned burst[8] = {0, 0, 0, 0, 1, 1, 2, 9};
+    unsigned n = burst[rnd(8)];
+    if (n == 0) return;
+    auto ready = [](const Queue& q) { return !q.ops.empty() && !(q.ops.front().kind == Op::WAIT && g_pending_recs.count(q.ops.front().rec)); };
+    std::vector<Queue*> all;
+    for (auto& kv : g_queues) if (ready(kv.second)) all.push_back(&kv.second);
+    if (all.empty()) return;
+    Queue& q = *all[rnd((unsigned)all.size())];
+    for (; n > 0 && ready(q); --n) step(q);
+}
+void enqueue(hipStream_t s, Op op)
+{
+    scheduler_turn();
+    Queue& q = queue_of(s);
+    // the null stream and the blocking streams order themselves against each other: (a legal order) each runs dry before the
+    // other takes an operation
+    if (s == nullptr) drain_blocking();
+    else if (q.blocking) { auto it = g_queues.find(nullptr); if (it != g_queues.end()) drain(it->second); }
+    q.ops.push_back(std::move(op));
+}
+void enqueue_work(hipStream_t s, std::string what, std::function<void()> run)
+{
+    Op op;
+    op.kind = Op::WORK; op.run = std::move(run); op.what = std::move(what);
+    enqueue(s, std::move(op));
+}
+struct ExitReport {
+    ~ExitReport()
+    {
+        if (!lazy_mode()) return;
+        for (auto& kv : g_queues)
+            if (!kv.second.ops.empty())
+                fprintf(stderr, "emu: at exit stream %s still holds %zu operations, the first one: %s\n", kv.second.name.c_str(), kv.second.ops.size(), kv.second.ops.front().what.c_str());
+    }
+} g_exit_report;
+#define LAZY_LOCK std::lock_guard<std::recursive_mutex> lazy_lock(g_lazy_mu)
+
 hipError_t make_stream(hipStream_t* s, unsigned flags, const int* priority)
 {
     *s = malloc(8);
@@ -188,6 +352,7 @@ hipError_t make_stream(hipStream_t* s, unsigned flags, const int* priority)
         std::lock_guard<std::mutex> lock(g_trace_mu);
         n = g_streams[*s] = g_n_streams++;
     }
+    if (lazy_mode()) { LAZY_LOCK; queue_of(*s).blocking = !(flags & hipStreamNonBlocking); }
     if (priority) trace("stream_create s%d flags=%u priority=%d", n, flags, *priority);
     else trace("stream_create s%d flags=%u priority=default", n, flags);
     return hipSuccess;
@@ -200,12 +365,23 @@ hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned flags, int prior
 hipError_t hipStreamDestroy(hipStream_t s)
 {
     trace("stream_destroy %s", sname(s).c_str());
+    if (lazy_mode()) { LAZY_LOCK; auto it = g_queues.find(s); if (it != g_queues.end()) { drain(it->second); g_queues.erase(it); } }
     std::lock_guard<std::mutex> lock(g_trace_mu);
     if (g_streams.erase(s)) free(s);
     return hipSuccess;
 }
-hipError_t hipStreamSynchronize(hipStream_t s) { trace("stream_sync %s", sname(s).c_str()); return hipSuccess; }
-hipError_t hipDeviceSynchronize() { trace("device_sync"); return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t s)
+{
+    trace("stream_sync %s", sname(s).c_str());
+    if (lazy_mode()) { LAZY_LOCK; drain(queue_of(s)); if (s == nullptr) drain_blocking(); }
+    return hipSuccess;
+}
+hipError_t hipDeviceSynchronize()
+{
+    trace("device_sync");
+    if (lazy_mode()) { LAZY_LOCK; drain_all(); }
+    return hipSuccess;
+}
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags)
 {
     *e = (hipEvent_t)malloc(sizeof(emu_event));
@@ -213,15 +389,43 @@ hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags)
     {
         std::lock_guard<std::mutex> lock(g_trace_mu);
         (*e)->ordinal = g_n_events++;
+        (*e)->last_rec = 0;
     }
     trace("event_create %s flags=%u", ename(*e).c_str(), flags);
     return hipSuccess;
 }
 hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, 0); }
 hipError_t hipEventDestroy(hipEvent_t e) { trace("event_destroy %s", ename(e).c_str()); free(e); return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { trace("event_record %s %s", ename(e).c_str(), sname(s).c_str()); return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t e) { trace("event_sync %s", ename(e).c_str()); return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { trace("stream_wait %s %s", sname(s).c_str(), ename(e).c_str()); return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
+{
+    trace("event_record %s %s", ename(e).c_str(), sname(s).c_str());
+    if (lazy_mode()) {
+        LAZY_LOCK;
+        Op op;
+        op.kind = Op::RECORD; op.rec = ++g_n_recs; op.what = "event_record " + ename(e);
+        enqueue(s, std::move(op));
+        g_pending_recs[g_n_recs] = s;
+        e->last_rec = g_n_recs;
+    }
+    return hipSuccess;
+}
+hipError_t hipEventSynchronize(hipEvent_t e)
+{
+    trace("event_sync %s", ename(e).c_str());
+    if (lazy_mode()) { LAZY_LOCK; static const Queue host = [] { Queue q; q.name = "host"; return q; }(); force_record(e->last_rec, host); }
+    return hipSuccess;
+}
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned)
+{
+    trace("stream_wait %s %s", sname(s).c_str(), ename(e).c_str());
+    if (lazy_mode() && e->last_rec) {   // (a wait for an event that was never recorded is no operation)
+        LAZY_LOCK;
+        Op op;
+        op.kind = Op::WAIT; op.rec = e->last_rec; op.what = "stream_wait " + ename(e);
+        enqueue(s, std::move(op));
+    }
+    return hipSuccess;
+}
 
 hipError_t hipMalloc(void** p, size_t n)
 {
@@ -244,17 +448,87 @@ hipError_t hipFree(void* p)
         }
         trace("free %zu", n);
     }
+    if (lazy_mode()) { LAZY_LOCK; drain_all(); }
     emu_device_free(p);
     return hipSuccess;
 }
-hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind kind) { trace("memcpy %s %zu", kname(kind), n); memcpy(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t st)
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind kind)
 {
-    trace("memcpy_async %s %zu %s", kname(kind), n, sname(st).c_str());
+    trace("memcpy %s %zu", kname(kind), n);
+    if (lazy_mode()) { LAZY_LOCK; drain_blocking(); }   // and for no non-blocking stream
     memcpy(d, s, n);
     return hipSuccess;
 }
-hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) { trace("memset_async %zu %s", n, sname(st).c_str()); memset(d, v, n); return hipSuccess; }
+hipError_t hipMemset(void* d, int v, size_t n)
+{
+    if (lazy_mode()) { LAZY_LOCK; drain_blocking(); }
+    memset(d, v, n);
+    return hipSuccess;
+}
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t st)
+{
+    trace("memcpy_async %s %zu %s", kname(kind), n, sname(st).c_str());
+    if (lazy_mode()) {
+        LAZY_LOCK;
+        const std::string what = std::string("memcpy_async ") + kname(kind) + " " + std::to_string(n);
+        if (kind == hipMemcpyHostToDevice && !pinned(s, n)) {   // pageable source: staged when the call is made
+            auto snap = std::make_shared<std::vector<char>>((const char*)s, (const char*)s + n);
+            enqueue_work(st, what + " (pageable, staged at the call)", [d, snap, n] { memcpy(d, snap->data(), n); });
+        } else if (kind == hipMemcpyDeviceToHost && !pinned(d, n)) {   // pageable destination: done when the call returns
+            enqueue_work(st, what + " (pageable, complete at the call)", [d, s, n] { memcpy(d, s, n); });
+            drain(queue_of(st));
+        } else {
+            enqueue_work(st, what, [d, s, n] { memcpy(d, s, n); });
+        }
+        return hipSuccess;
+    }
+    memcpy(d, s, n);
+    return hipSuccess;
+}
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st)
+{
+    trace("memset_async %zu %s", n, sname(st).c_str());
+    if (lazy_mode()) { LAZY_LOCK; enqueue_work(st, "memset_async " + std::to_string(n), [d, v, n] { memset(d, v, n); }); return hipSuccess; }
+    memset(d, v, n);
+    return hipSuccess;
+}
+hipError_t hipHostMalloc(void** p, size_t n, unsigned)
+{
+    *p = malloc(n);
+    if (*p && lazy_mode()) { LAZY_LOCK; g_pinned[(char*)*p] = n; }
+    return *p ? hipSuccess : hipErrorUnknown;
+}
+hipError_t hipHostFree(void* p)
+{
+    if (lazy_mode()) { LAZY_LOCK; drain_all(); g_pinned.erase((char*)p); }
+    free(p);
+    return hipSuccess;
+}
+
+// A caller's side of a stream, for a Python driver (tools/emu/run_emu_streams.py): a stream the engines did not make (traced
+// as `caller`), a copy queued on it that is deferred whatever memory it touches (the caller's producer), and its waits.
+extern "C" int emu_streams_mode() { return lazy_mode(); }
+extern "C" void* emu_caller_stream_create() { return malloc(8); }
+extern "C" void emu_caller_stream_destroy(void* s)
+{
+    if (lazy_mode()) { LAZY_LOCK; auto it = g_queues.find(s); if (it != g_queues.end()) { drain(it->second); g_queues.erase(it); } }
+    free(s);
+}
+extern "C" void emu_caller_copy(void* d, const void* s, size_t n, void* stream)
+{
+    if (lazy_mode()) { LAZY_LOCK; enqueue_work(stream, "caller copy " + std::to_string(n), [d, s, n] { memcpy(d, s, n); }); return; }
+    memcpy(d, s, n);
+}
+extern "C" void emu_caller_stream_sync(void* stream)
+{
+    if (lazy_mode()) { LAZY_LOCK; drain(queue_of(stream)); }
+}
+extern "C" size_t emu_streams_queued()   // operations that have not executed yet, over all streams
+{
+    size_t n = 0;
+    if (lazy_mode()) { LAZY_LOCK; for (auto& kv : g_queues) n += kv.second.ops.size(); }
+    return n;
+}
 
 #define EMU_WAIT(what) do { Fiber& f_ = g_fibers[g_cur]; f_.wait = what; f_.wait_pc = __builtin_return_address(0); f_.hist[++f_.hist_n % 16] = f_.wait_pc; } while (0)
 
@@ -352,12 +626,24 @@ __attribute__((noinline)) int emu_update_dpp(int old, int src, int ctrl, int row
     return (int)all[row * 16 + srcpos];
 }
 
+static void run_kernel(const char* name, dim3 grid, dim3 block, const std::function<void()>& body);
+
 void emu_launch(const char* name, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const std::function<void()>& body)
+{
+    trace("launch %s grid=(%u,%u,%u) block=(%u,%u,%u) lds=%zu %s", name, grid.x, grid.y, grid.z, block.x, block.y, block.z, lds_bytes, sname(stream).c_str());
+    if (lazy_mode()) {
+        LAZY_LOCK;
+        enqueue_work(stream, std::string("launch ") + name, [name, grid, block, body] { run_kernel(name, grid, block, body); });
+        return;
+    }
+    run_kernel(name, grid, block, body);
+}
+
+static void run_kernel(const char* name, dim3 grid, dim3 block, const std::function<void()>& body)
 {
     // one kernel at a time: the scheduler's state is global, and a host program may launch from several threads
     static std::mutex launch_mu;
     std::lock_guard<std::mutex> launch_lock(launch_mu);
-    trace("launch %s grid=(%u,%u,%u) block=(%u,%u,%u) lds=%zu %s", name, grid.x, grid.y, grid.z, block.x, block.y, block.z, lds_bytes, sname(stream).c_str());
     const unsigned nthr = block.x * block.y * block.z;
     if (g_fibers.size() < nthr) {
         const size_t old = g_fibers.size();

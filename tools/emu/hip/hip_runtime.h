@@ -22,6 +22,33 @@
 //     inside a wavefront stay ascending: the hardware runs them in lockstep and the sources rely on it). A missing
 //     __syncthreads() between a low-numbered producer wavefront and a high-numbered consumer shows in one of the two
 //     orders; results must have identical bits in both.
+//   * EMU_STREAMS=lazy | lazy:SEED (read when the library loads; off by default): deferred streams. Unset, every launch, copy
+//     and fill runs at its call, in program order, and events and waits do nothing: a wait between two streams can be missing
+//     and nothing shows. With the mode on, each stream made here, the null stream and every foreign handle is a FIFO of
+//     operations (launch, memcpy_async, memset_async, event record, stream wait), executed in a legal order that is not
+//     program order:
+//       - launch arguments are evaluated at the call and held by value (emu_launch_by_value, in every mode);
+//       - hipEventRecord queues a record; hipStreamWaitEvent takes the event's latest record AT THE CALL and is runnable once
+//         that record has executed: a later record of the event does not move it, an event never recorded holds nobody up;
+//       - hipStreamSynchronize(s) runs s dry and, transitively, whatever its waits need - nothing else; hipEventSynchronize
+//         runs up to the record taken at the call; hipDeviceSynchronize, hipFree and hipHostFree run everything;
+//         hipStreamDestroy runs that stream dry;
+//       - blocking hipMemcpy / hipMemset run at once, behind the streams made WITHOUT hipStreamNonBlocking and the null stream,
+//         and wait for no non-blocking stream (a caller's handle counts as non-blocking); the null stream and the blocking
+//         streams run each other dry before either takes an operation;
+//       - host memory: a host-to-device hipMemcpyAsync from memory that is not hipHostMalloc's is staged at the call, a
+//         device-to-host one into such memory is complete, with all ahead of it on its stream, when the call returns; copies
+//         from or to hipHostMalloc ranges (tracked) are deferred like a launch.
+//     `lazy` executes nothing until a host-blocking call forces it. `lazy:SEED` also runs, before every enqueue, a seeded random
+//     number of runnable operations of one seeded random stream, so streams run ahead of and fall behind each other. A wait
+//     whose record sits behind a wait for the asking stream aborts with both streams and the event named; operations still
+//     queued at exit are reported on stderr; EMU_STREAMS_LOG=<file> records each operation when it executes. EMU_TRACE lines are
+//     written at the call in every mode. extern "C" emu_caller_stream_create / _destroy / _sync and emu_caller_copy give a
+//     Python driver a caller's stream with a deferred copy on it (tools/emu/run_emu_streams.py); tests/host/
+//     emu_streams_selftest.cpp shows on toy programs that each missing wait changes a result. LIMITS: the mode explores
+//     ORDERS of whole operations - kernels never overlap, nothing has a duration - and knows nothing of hardware queues,
+//     priorities or which schedule a device would really take; a clean run says that the waits suffice for the orders it
+//     took (one for `lazy`, one per seed), not for all legal ones.
 #pragma once
 #define AT3_EMU_HOST 1
 #include <ucontext.h>
@@ -32,6 +59,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <string>
+#include <tuple>
 #include <vector>
 
 using std::isfinite;
@@ -132,13 +161,13 @@ extern "C" void emu_device_free(void* p);
 extern "C" void emu_fail_alloc_after(long n);   // n more allocations succeed, the later ones are refused (n < 0: none is)
 hipError_t hipMalloc(void** p, size_t n);
 #define hipHostMallocDefault 0u
-static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n); return *p ? hipSuccess : hipErrorUnknown; }
-static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+hipError_t hipHostMalloc(void** p, size_t n, unsigned);   // (EMU_STREAMS tracks these ranges: copies from or to them are deferred)
+hipError_t hipHostFree(void* p);
 hipError_t hipFree(void* p);
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind kind);
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t st);
 hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st);
-static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
+hipError_t hipMemset(void* d, int v, size_t n);
 struct hipDeviceProp_t { int multiProcessorCount; size_t maxSharedMemoryPerMultiProcessor; };
 static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { p->multiProcessorCount = 4; p->maxSharedMemoryPerMultiProcessor = 160u * 1024u; return hipSuccess; }
 static inline hipError_t hipGetLastError() { return hipSuccess; }
@@ -188,5 +217,13 @@ static inline int __popcll(unsigned long long x) { return __builtin_popcountll(x
 static inline int __popc(unsigned x) { return __builtin_popcount(x); }
 
 void emu_launch(const char* name, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const std::function<void()>& body);
+// The arguments are evaluated and converted to the kernel's parameter types when the launch is called and travel by value: under
+// EMU_STREAMS the body runs later, when the caller's locals are gone. (`kernel` may be a parenthesised template name.)
+template <typename... P, typename... A>
+static inline void emu_launch_by_value(const char* name, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, void (*kernel)(P...), A&&... args)
+{
+    std::tuple<std::decay_t<P>...> held(std::forward<A>(args)...);
+    emu_launch(name, grid, block, lds_bytes, stream, [kernel, held]() { std::apply(kernel, held); });
+}
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    emu_launch(#kernel, (grid), (block), (shmem), (stream), [&]() { kernel(__VA_ARGS__); })
+    emu_launch_by_value(#kernel, (grid), (block), (shmem), (stream), kernel, ##__VA_ARGS__)
