@@ -19,8 +19,13 @@
 //                  block 0, rebuilds frame n-1's part of the histories and runs the two QMF stages, clamps, writes PCM
 //   k_at1d_state   carries the last frame's band buffer [64, bufSz) and tails into the next call
 // Every float operation is the reference's, in its order, without contraction; no scratch.
+// Shared with the other decoders: the sign extension (at3_bits.hpp: sext), the TMIDCT rotations and the clamped output store
+// (at3_common.hpp: midct_pre, midct_post, store_pcm). The unit is read at computed positions by 128 lanes at once (dec_bits),
+// not in sequence, so the sequential MsbReader has no place here; of Buf[N] only the middle half is kept, so neither has
+// midct_unfold.
 #pragma once
 #include "at1_kernels.hpp"
+#include "at3_bits.hpp"
 
 namespace at1 {
 
@@ -133,7 +138,7 @@ __global__ __launch_bounds__(128) void k_at1d_bands(DecBandsParams p)
             if (b < s_nbfu && w) {
                 const int i = t - c_start_long[b];
                 const uint32_t v = dec_bits(s_unit, s_off[b] + i * w, w);
-                const int m = (int32_t)(v << (32 - w)) >> (32 - w);   // MakeSign
+                const int m = at3::sext(v, w);   // MakeSign
                 const float sfq = T->scale[s_sf[b]] * T->maxq[w];
                 const int lcb = b < 20 ? lc[0] : b < 36 ? lc[1] : lc[2];
                 s_spec[(lcb ? c_start_short[b] : c_start_long[b]) + i] = sfq * (float)m;
@@ -160,10 +165,7 @@ __global__ __launch_bounds__(128) void k_at1d_bands(DecBandsParams p)
             const float* in = s_spec + pos[band] + k * bsz;
             const float r0 = band ? in[bsz - 1 - n] : in[n];
             const float i0 = band ? in[n] : in[bsz - 1 - n];
-            const float cc = cs[n], ss = cs[n + 1];
-            cpx v;
-            v.r = -2.0f * (i0 * ss + r0 * cc);
-            v.i = -2.0f * (i0 * cc - r0 * ss);
+            const cpx v = at3::midct_pre(r0, i0, cs[n], cs[n + 1]);
             const int leaf = n4 == 128 ? at3::fft_leaf_pos<128>(k2) : n4 == 64 ? at3::fft_leaf_pos<64>(k2) : at3::fft_leaf_pos<16>(k2);
             F[k * n4 + leaf] = v;
         }
@@ -189,10 +191,8 @@ __global__ __launch_bounds__(128) void k_at1d_bands(DecBandsParams p)
         float* inv = s_inv + (band == 0 ? 0 : band == 1 ? 128 : 256);
         for (int j = tid; j < nblk * n4; j += 128) {
             const int k = j / n4, k2 = j % n4, n = 2 * k2;
-            const cpx v = F[j];
-            const float cc = cs[n], ss = cs[n + 1];
-            const float r1 = v.r * cc + v.i * ss;
-            const float i1 = v.r * ss - v.i * cc;
+            float r1, i1;
+            at3::midct_post(F[j], cs[n], cs[n + 1], r1, i1);
             inv[k * bsz + bsz - 1 - n] = r1;
             inv[k * bsz + n] = i1;
         }
@@ -395,23 +395,14 @@ __global__ __launch_bounds__(256) void k_at1d_synth(DecSynthParams p)
             s2 += w[i + 1] * QW[i + 1];
         }
         // clamp to [PcmValueMin, PcmValueMax] and interleave (atrac1denc.cpp:166-173)
-        float o0 = s2, o1 = s1;
-        o0 = o0 > 1.0f ? 1.0f : o0;
-        o0 = o0 < -1.0f ? -1.0f : o0;
-        o1 = o1 > 1.0f ? 1.0f : o1;
-        o1 = o1 < -1.0f ? -1.0f : o1;
         const int s = sc / p.nch, c = sc % p.nch;
         const size_t base = (((size_t)s * F + f) * 512 + 2 * tid) * p.nch + c;
-        if (p.s16) {
-            // libsndfile's float -> PCM_16 with normalisation: lrintf(x * 32767.0f) (round to nearest even)
-            int16_t* out = (int16_t*)p.out;
-            out[base] = (int16_t)__float2int_rn(o0 * 32767.0f);
-            out[base + p.nch] = (int16_t)__float2int_rn(o1 * 32767.0f);
-        } else {
-            float* out = (float*)p.out;
-            out[base] = o0;
-            out[base + p.nch] = o1;
-        }
+        auto pair = [&](bool s16) {
+            at3::store_pcm(p.out, base, s2, s16);
+            at3::store_pcm(p.out, base + p.nch, s1, s16);
+        };
+        if (p.s16) pair(true);   // one branch for the pair, as in k_at3d_synth
+        else pair(false);
     }
 }
 

@@ -9,6 +9,7 @@
 // Every float operation is the reference's, in its order, without contraction; integer work is free to reassociate.
 #pragma once
 #include "at1_tables.hpp"
+#include "at3_bits.hpp"
 #include "at3_common.hpp"
 #include "at3_pcm_in.hpp"
 
@@ -837,16 +838,7 @@ __global__ __launch_bounds__(256) void k_at1_alloc_pack(PackParams p)
     }
 
     // Dump: MSB-first bit string into big-endian words
-    auto put = [&](int off, uint32_t val, int nb) {
-        const int w = off >> 5, sft = off & 31;
-        const int room = 32 - sft;
-        if (nb <= room) {
-            atomicOr(&W[w], val << (room - nb));
-        } else {
-            atomicOr(&W[w], val >> (nb - room));
-            atomicOr(&W[w + 1], val << (32 - (nb - room)));
-        }
-    };
+    auto put = [&](int off, uint32_t val, int nb) { at3::or_bits_msb(W, off, val, nb); };
     wave_sync();
     if (lane == 0) {
         const int lc0 = (mask & 1) ? 2 : 0, lc1 = (mask & 2) ? 2 : 0, lc2 = (mask & 4) ? 3 : 0;

@@ -197,7 +197,9 @@ __device__ __forceinline__ float at3_log2f(const Tables* T, float x)   // tables
     return at3_log2f(reinterpret_cast<const Log2fTab*>(&T->log2f_tab[0][0]), x);
 }
 
-__device__ __forceinline__ void wave_sync_fwd()
+// Wave-level rendezvous for data exchanged through LDS between lanes of ONE wavefront: the LDS pipeline
+// executes a wave's DS instructions in issue order, so only compiler reordering has to be fenced.
+__device__ __forceinline__ void wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -232,7 +234,7 @@ __device__ __forceinline__ void fft_lds(cpx* F, int NS, int nfft, const cpx* tw,
     // WAVE: all participating threads are the lanes of ONE wavefront (nthr = 64, tid = lane): the stages are separated by
     // wave-level rendezvous instead of workgroup barriers
     auto stage_sync = [] {
-        if (WAVE) wave_sync_fwd();
+        if (WAVE) wave_sync();
         else __syncthreads();
     };
     // number of radix-4 stages and whether a radix-2 leaf stage exists; LEAF_DONE: the caller already stored
@@ -272,6 +274,49 @@ __device__ __forceinline__ void fft_lds(cpx* F, int NS, int nfft, const cpx* tw,
     }
 }
 
+// ---- TMIDCT (mdct.h) around a forward fft_lds of N/4 points -------------------------------------------
+// The helpers take values; which spectral lines (r0, i0) are - band mirroring, block sizes - and where the point goes
+// (fft_leaf_pos) stay with the kernel. n = 2 k is even, (c, s) = (SinCos[n], SinCos[n + 1]). The operand order is the
+// reference's: under -ffp-contract=off these expressions are the bit pattern.
+__device__ __forceinline__ cpx midct_pre(float r0, float i0, float c, float s)   // FFT input k
+{
+    cpx v;
+    v.r = -2.0f * (i0 * s + r0 * c);
+    v.i = -2.0f * (i0 * c - r0 * s);
+    return v;
+}
+__device__ __forceinline__ void midct_post(cpx v, float c, float s, float& r1, float& i1)   // v = FFT output k
+{
+    r1 = v.r * c + v.i * s;
+    i1 = v.r * s - v.i * c;
+}
+// The four places of Buf[N], N = 4 H, that r1 and i1 of an even n < 2 H reach, through the caller's put(index, value).
+template <int H, typename Put>
+__device__ __forceinline__ void midct_unfold(int n, float r1, float i1, Put put)
+{
+    if (n < H) {
+        put(3 * H - 1 - n, r1);
+        put(3 * H + n, r1);
+        put(H + n, i1);
+        put(H - 1 - n, -i1);
+    } else {
+        put(3 * H - 1 - n, r1);
+        put(n - H, -r1);
+        put(H + n, i1);
+        put(5 * H - 1 - n, i1);
+    }
+}
+
+// The decoders' output sample: clamped to [-1, 1], then as it is or as lrintf(v * 32767.0f) (libsndfile's float -> PCM_16 with
+// normalisation: round to nearest even).
+__device__ __forceinline__ void store_pcm(void* out, size_t idx, float v, bool s16)
+{
+    v = v > 1.0f ? 1.0f : v;
+    v = v < -1.0f ? -1.0f : v;
+    if (s16) ((int16_t*)out)[idx] = (int16_t)__float2int_rn(v * 32767.0f);
+    else ((float*)out)[idx] = v;
+}
+
 // ---- wavefront (64 lanes) cross-lane helpers on DPP / readlane; call from wave-uniform code only ----
 #define AT3_DPP(v, ctrl, bc) __builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), 0xf, 0xf, (bc))
 
@@ -300,15 +345,6 @@ __device__ __forceinline__ int wave_inclusive_scan(int v, int lane)
     if (lane >= 32) v += r1;
     if (lane >= 48) v += r2;
     return v;
-}
-
-// Wave-level rendezvous for data exchanged through LDS between lanes of ONE wavefront: the LDS pipeline
-// executes a wave's DS instructions in issue order, so only compiler reordering has to be fenced.
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // GainLevel[l] = 2^(4 - l) (atrac3.h:192-194): exact powers of two, formed from the exponent field.

@@ -13,7 +13,10 @@
 //                   f32 or s16 output
 //   k_at3d_state    the call's last two frames become frames -2 and -1 of the next call
 // Every float operation is the definition's, in its order, without contraction; no scratch.
+// Shared with the other decoders: the bit reader and sign extension (at3_bits.hpp: MsbReader, sext), the TMIDCT rotations and
+// unfold and the clamped output store (at3_common.hpp: midct_pre, midct_post, midct_unfold, store_pcm).
 #pragma once
+#include "at3_bits.hpp"
 #include "at3_common.hpp"
 
 namespace at3 {
@@ -73,60 +76,30 @@ struct Dec3UnpackParams {
     unsigned long long* rejected; // [6]
 };
 
-// MSB-first reader over the unit staged in LDS as big-endian words (zero past the unit); reads must end within `limit` bits.
-// The two words around the read position are kept in a register (`win` = words wi, wi + 1): a read of <= 8 bits costs no LDS
-// access but the one refill when it crosses into the next word.
-struct Dec3Bits {
-    const uint32_t* w;
-    int pos, limit, bad, wi;
-    uint64_t win;
-    __device__ __forceinline__ Dec3Bits(const uint32_t* words, int limit_bits)
-        : w(words), pos(0), limit(limit_bits), bad(0), wi(0), win(((uint64_t)words[0] << 32) | words[1]) {}
-    __device__ __forceinline__ uint32_t peek(int n) const { return (uint32_t)((win << (pos - 32 * wi)) >> (64 - n)); }
-    __device__ __forceinline__ void advance(int n)
-    {
-        pos += n;
-        if ((pos >> 5) != wi) {   // n <= 8: at most one word further
-            ++wi;
-            win = (win << 32) | w[wi + 1];
-        }
-    }
-    __device__ __forceinline__ uint32_t rd(int n)
-    {
-        if (bad || pos + n > limit) {
-            bad = 1;
-            return 0;
-        }
-        const uint32_t v = peek(n);
-        advance(n);
-        return v;
-    }
-    __device__ __forceinline__ int vlc(const uint16_t* lut)
-    {
-        if (bad) return 0;
-        const uint32_t e = lut[peek(8)];
-        const int len = (int)(e >> 8);
-        if (pos + len > limit) {
-            bad = 1;
-            return 0;
-        }
-        advance(len);
-        return (int)(e & 0xff);
-    }
-};
-
-__device__ __forceinline__ int dec3_sext(uint32_t v, int n) { return (int)(v << (32 - n)) >> (32 - n); }
-
-__device__ __forceinline__ int dec3_mantissa(Dec3Bits& b, const uint16_t (*lut)[256], bool vlc_mode, int s)
+// One symbol of a selector's code through its 256-entry look-up (Dec3Tables::vlc): the next 8 bits give symbol and length.
+__device__ __forceinline__ int dec3_vlc(MsbReader& b, const uint16_t* lut)
 {
-    if (!vlc_mode) return dec3_sext(b.rd(clc_len(s)), clc_len(s));
-    const int i = b.vlc(lut[s]);
+    if (b.bad) return 0;
+    const uint32_t e = lut[b.peek(8)];
+    const int len = (int)(e >> 8);
+    if (b.pos + len > b.limit) {
+        b.bad = 1;
+        return 0;
+    }
+    b.advance(len);
+    return (int)(e & 0xff);
+}
+
+__device__ __forceinline__ int dec3_mantissa(MsbReader& b, const uint16_t (*lut)[256], bool vlc_mode, int s)
+{
+    if (!vlc_mode) return sext(b.rd(clc_len(s)), clc_len(s));
+    const int i = dec3_vlc(b, lut[s]);
     return (i & 1) ? (i + 1) >> 1 : -(i >> 1);
 }
 
 // the unit's syntax (include/at3hip.h, step 1) and its dequantisation (step 2) on one lane: g, base and tonal are zero on
 // entry; wls / sfs are work space (LDS, like everything it writes: no scratch)
-__device__ __forceinline__ int dec3_parse(Dec3Bits& b, const uint16_t (*lut)[256], const float* scale, const float* inv_maxq, bool js_second, Dec3Gains& g,
+__device__ __forceinline__ int dec3_parse(MsbReader& b, const uint16_t (*lut)[256], const float* scale, const float* inv_maxq, bool js_second, Dec3Gains& g,
                                           float* base, float* tonal, uint8_t* wls, uint8_t* sfs)
 {
 #define DEC3_CHK()                              \
@@ -204,11 +177,11 @@ __device__ __forceinline__ int dec3_parse(Dec3Bits& b, const uint16_t (*lut)[256
                 int a, c;
                 if (!vlc_mode) {
                     const uint32_t code = b.rd(4);
-                    a = dec3_sext(code >> 2, 2);
-                    c = dec3_sext(code & 3, 2);
+                    a = sext(code >> 2, 2);
+                    c = sext(code & 3, 2);
                 } else {
                     // inverse of MantissasToVlcIndex: symbols 0..8 -> (a, b)
-                    const int sym = b.vlc(lut[1]);
+                    const int sym = dec3_vlc(b, lut[1]);
                     a = sym == 3 || sym == 5 || sym == 6 ? 1 : sym == 4 || sym == 7 || sym == 8 ? -1 : 0;
                     c = sym == 1 || sym == 5 || sym == 7 ? 1 : sym == 2 || sym == 6 || sym == 8 ? -1 : 0;
                 }
@@ -262,7 +235,7 @@ __global__ __launch_bounds__(kDec3UnpackThreads) void k_at3d_unpack(Dec3UnpackPa
     for (int i = tid; i < (int)sizeof(Dec3Gains); i += NT) ((uint8_t*)&s_g)[i] = 0;
     __syncthreads();
     if (tid == 0) {
-        Dec3Bits b(s_w, limit * 8);
+        MsbReader b(s_w, limit * 8);
         const int why = dec3_parse(b, s_lut, T->scale, T->inv_maxq, p.js && u == 1, s_g, s_base, s_tonal, s_wl, s_sf);
         s_reason = why;
         if (why) atomicAdd(&p.rejected[why - 1], 1ull);
@@ -282,11 +255,7 @@ __global__ __launch_bounds__(kDec3UnpackThreads) void k_at3d_unpack(Dec3UnpackPa
         const int a = band & 1 ? 255 - n : n, bb = band & 1 ? n : 255 - n;
         const float r0 = s_base[256 * band + a];
         const float i0 = s_base[256 * band + bb];
-        const float c = cs[n], sn = cs[n + 1];
-        cpx v;
-        v.r = -2.0f * (i0 * sn + r0 * c);
-        v.i = -2.0f * (i0 * c - r0 * sn);
-        s_f[band * 128 + fft_leaf_pos<128>(k2)] = v;
+        s_f[band * 128 + fft_leaf_pos<128>(k2)] = midct_pre(r0, i0, cs[n], cs[n + 1]);
     }
     __syncthreads();
     fft_lds<128, false>(s_f, 128, 4, T->tw128, tid, NT);
@@ -295,22 +264,10 @@ __global__ __launch_bounds__(kDec3UnpackThreads) void k_at3d_unpack(Dec3UnpackPa
     const float* W = T->dwin2;
     for (int j = tid; j < 512; j += NT) {
         const int band = j >> 7, k2 = j & 127, n = 2 * k2;
-        const cpx v = s_f[j];
-        const float c = cs[n], sn = cs[n + 1];
-        const float r1 = v.r * c + v.i * sn, i1 = v.r * sn - v.i * c;
+        float r1, i1;
+        midct_post(s_f[j], cs[n], cs[n + 1], r1, i1);
         float* o = raw + band * 512;
-        auto put = [&](int x, float v) { o[x] = v * W[x < 256 ? x : 511 - x]; };
-        if (n < 128) {
-            put(383 - n, r1);
-            put(384 + n, r1);
-            put(128 + n, i1);
-            put(127 - n, -i1);
-        } else {
-            put(383 - n, r1);
-            put(n - 128, -r1);
-            put(128 + n, i1);
-            put(639 - n, i1);
-        }
+        midct_unfold<128>(n, r1, i1, [&](int x, float v) { o[x] = v * W[x < 256 ? x : 511 - x]; });
     }
 }
 
@@ -460,20 +417,13 @@ __global__ __launch_bounds__(256) void k_at3d_synth(Dec3SynthParams p)
         const int c = i >> 9, j = i & 511;
         float o0, o1;
         dec3_qmf_pair(&s_m2[c][2 * j], QW, o0, o1);
-        o0 = o0 > 1.0f ? 1.0f : o0;
-        o0 = o0 < -1.0f ? -1.0f : o0;
-        o1 = o1 > 1.0f ? 1.0f : o1;
-        o1 = o1 < -1.0f ? -1.0f : o1;
         const size_t base = (((size_t)s * F + f) * 1024 + 2 * j) * 2 + c;
-        if (p.s16) {
-            int16_t* out = (int16_t*)p.out;
-            out[base] = (int16_t)__float2int_rn(o0 * 32767.0f);
-            out[base + 2] = (int16_t)__float2int_rn(o1 * 32767.0f);
-        } else {
-            float* out = (float*)p.out;
-            out[base] = o0;
-            out[base + 2] = o1;
-        }
+        auto pair = [&](bool s16) {
+            store_pcm(p.out, base, o0, s16);
+            store_pcm(p.out, base + 2, o1, s16);
+        };
+        if (p.s16) pair(true);   // one branch for the pair: two in a row cost this loop 17 VGPRs and a wave of occupancy
+        else pair(false);
     }
 }
 

@@ -11,6 +11,7 @@
 //   lib/bs_encode/encode.cpp:57-129         bisection driver (Start / Continue / Submit / Repeat)
 //   lib/bitstream/bitstream.cpp:40-63       MSB-first bit writer
 #pragma once
+#include "at3_bits.hpp"
 #include "at3_common.hpp"
 
 namespace at3 {
@@ -608,14 +609,7 @@ __device__ inline void put_bits(uint32_t* words, int pos, uint32_t val, int n)
     // n in 1..23. Bits beyond the buffer are dropped (they are truncated away by the frame size anyway).
     if (n <= 0 || pos + n > kBitWords * 32) return;
     val &= (n >= 32) ? 0xffffffffu : ((1u << n) - 1u);
-    const int w = pos >> 5, off = pos & 31;
-    const int room = 32 - off;
-    if (n <= room) {
-        atomicOr(&words[w], val << (room - n));
-    } else {
-        atomicOr(&words[w], val >> (n - room));
-        atomicOr(&words[w + 1], val << (32 - (n - room)));
-    }
+    or_bits_msb(words, pos, val, n);
 }
 
 __device__ inline uint32_t huff_entry(int sel, uint32_t idx) { return c_huff[huff_off(sel) + idx]; }

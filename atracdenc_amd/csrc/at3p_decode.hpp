@@ -16,7 +16,11 @@
 // runs in k_at3pd_synth. Frame n's samples need the records of frames n, n-1 (waves) and n-2 (frame n-1's envelope); frame n-1's
 // last 23 samples need those of frames n-1 .. n-3, so four records are read and three are carried.
 // Every float and double operation is the definition's, in its order, without contraction; no scratch.
+// Shared with the other decoders: the bit reader, the linear code scan and the sign extension (at3_bits.hpp: MsbReader,
+// prefix_scan, sext), the TMIDCT rotations and unfold and the clamped output store (at3_common.hpp: midct_pre, midct_post,
+// midct_unfold, store_pcm).
 #pragma once
+#include "at3_bits.hpp"
 #include "at3_common.hpp"
 #include "at3p_tone_synth.hpp"
 
@@ -85,55 +89,10 @@ struct DecUnpackParams {
     int32_t tones;                // AT3PHIP_DECODE_TONES
 };
 
-// MSB-first reader over the frame staged in LDS as big-endian words (zero past the frame); reads must end within 16384 bits.
-// The two words around the read position are kept in a register.
-struct DecpBits {
-    const uint32_t* w;
-    int pos, bad, wi;
-    uint64_t win;
-    __device__ __forceinline__ explicit DecpBits(const uint32_t* words)
-        : w(words), pos(0), bad(0), wi(0), win(((uint64_t)words[0] << 32) | words[1]) {}
-    __device__ __forceinline__ uint32_t peek(int n) const { return (uint32_t)((win << (pos - 32 * wi)) >> (64 - n)); }
-    __device__ __forceinline__ void advance(int n)   // n <= 32
-    {
-        pos += n;
-        if ((pos >> 5) != wi) {
-            ++wi;
-            win = (win << 32) | w[wi + 1];
-        }
-    }
-    __device__ __forceinline__ uint32_t rd(int n)
-    {
-        if (bad || pos + n > 2048 * 8) {
-            bad = 1;
-            return 0;
-        }
-        const uint32_t v = peek(n);
-        advance(n);
-        return v;
-    }
-};
+using at3::MsbReader;   // over the frame staged in LDS as big-endian words; constructed with the frame's 2048 * 8 bits
 
-__device__ __forceinline__ int decp_wl_vlc(DecpBits& b, const uint16_t* tab, int& invalid)
-{
-    if (b.bad) return 0;
-    const uint32_t v = b.peek(8);
-    for (int sym = 0; sym < 8; ++sym) {
-        const int len = tab[sym] >> 12, code = tab[sym] & 0xfff;
-        if (len && (int)(v >> (8 - len)) == code) {
-            if (b.pos + len > 2048 * 8) {
-                b.bad = 1;
-                return 0;
-            }
-            b.advance(len);
-            return sym;
-        }
-    }
-    invalid = 1;
-    return 0;
-}
-
-__device__ __forceinline__ int decp_spec_vlc(DecpBits& b, const DecTables* T, int t, int& invalid)
+// One symbol of spectra table t through the two-level look-up (DecTables::lut1, lut2) over the next 12 bits.
+__device__ __forceinline__ int decp_spec_vlc(MsbReader& b, const DecTables* T, int t, int& invalid)
 {
     if (b.bad) return 0;
     const uint32_t v = b.peek(12);
@@ -144,7 +103,7 @@ __device__ __forceinline__ int decp_spec_vlc(DecpBits& b, const DecTables* T, in
         invalid = 1;
         return 0;
     }
-    if (b.pos + len > 2048 * 8) {
+    if (b.pos + len > b.limit) {
         b.bad = 1;
         return 0;
     }
@@ -154,29 +113,9 @@ __device__ __forceinline__ int decp_spec_vlc(DecpBits& b, const DecTables* T, in
 
 __device__ __forceinline__ int decp_bits_for(uint32_t x) { return x ? 32 - __builtin_clz(x) : 1; }   // GetFirstSetBit(x) + 1
 
-// A code of AT3P_TONE_BANDS_VLC (16 symbols, at most 6 bits, a complete prefix code).
-__device__ __forceinline__ int decp_tone_vlc(DecpBits& b, const uint16_t* tab, int& invalid)
-{
-    if (b.bad) return 0;
-    const uint32_t v = b.peek(8);
-    for (int sym = 0; sym < 16; ++sym) {
-        const int len = tab[sym] >> 12, code = tab[sym] & 0xfff;
-        if (len && (int)(v >> (8 - len)) == code) {
-            if (b.pos + len > 2048 * 8) {
-                b.bad = 1;
-                return 0;
-            }
-            b.advance(len);
-            return sym;
-        }
-    }
-    invalid = 1;
-    return 0;
-}
-
 // The tonal block (include/at3phip.h, step 1 with AT3PHIP_DECODE_TONES) into r, which is zero on entry; r holds
 // the block after ApplyFilter's bookkeeping (start indices, shared bands, the leader swap) when kRpOk is returned.
-__device__ __forceinline__ int decp_tonal(DecpBits& b, const uint16_t* tone_vlc, int C, TonalRec* r)
+__device__ __forceinline__ int decp_tonal(MsbReader& b, const uint16_t* tone_vlc, int C, TonalRec* r)
 {
     int invalid = 0;
 #define DECP_CHK()                              \
@@ -191,7 +130,7 @@ __device__ __forceinline__ int decp_tonal(DecpBits& b, const uint16_t* tone_vlc,
         if (v_ != (uint32_t)(val)) return kRpUnsupported;   \
     } while (0)
     DECP_MUST(1, 1);   // amplitude mode 1
-    const int nb = decp_tone_vlc(b, tone_vlc, invalid) + 1;
+    const int nb = at3::prefix_scan<16>(b, tone_vlc, invalid) + 1;   // AT3P_TONE_BANDS_VLC: at most 6 bits, a complete code
     DECP_CHK();
     uint32_t shared = 0;
     int leader = 0;
@@ -292,7 +231,7 @@ __device__ __forceinline__ int decp_tonal(DecpBits& b, const uint16_t* tone_vlc,
 
 // The frame's syntax (include/at3phip.h, step 1) and its dequantisation (step 2) on one lane; spec (LDS) is zero on entry.
 // With tonal_rec (AT3PHIP_DECODE_TONES) a tonal block is parsed into it, else it rejects the frame.
-__device__ __forceinline__ int decp_parse(DecpBits& b, const DecTables* T, int C, float* spec, uint8_t (*wl)[32], uint8_t (*sf)[32],
+__device__ __forceinline__ int decp_parse(MsbReader& b, const DecTables* T, int C, float* spec, uint8_t (*wl)[32], uint8_t (*sf)[32],
                                        uint8_t (*tab)[32], uint16_t* winf, const uint16_t* tone_vlc, TonalRec* tonal_rec)
 {
     int invalid = 0;
@@ -311,7 +250,7 @@ __device__ __forceinline__ int decp_parse(DecpBits& b, const DecTables* T, int C
         int w = (int)b.rd(3);
         wl[0][0] = (uint8_t)w;
         for (int i = 1; i < nqu; ++i) {
-            w = (w + decp_wl_vlc(b, T->wl_vlc[idx], invalid)) & 7;
+            w = (w + at3::prefix_scan<8>(b, T->wl_vlc[idx], invalid)) & 7;
             wl[0][i] = (uint8_t)w;
         }
         DECP_CHK();
@@ -319,7 +258,7 @@ __device__ __forceinline__ int decp_parse(DecpBits& b, const DecTables* T, int C
     if (C == 2) {
         if (b.rd(2) != 1 || b.rd(2) != 0) return kRpUnsupported;
         const int idx = (int)b.rd(2);
-        for (int i = 0; i < nqu; ++i) wl[1][i] = (uint8_t)((wl[0][i] + decp_wl_vlc(b, T->wl_vlc[idx], invalid)) & 7);
+        for (int i = 0; i < nqu; ++i) wl[1][i] = (uint8_t)((wl[0][i] + at3::prefix_scan<8>(b, T->wl_vlc[idx], invalid)) & 7);
         DECP_CHK();
     }
     for (int ch = 0; ch < C; ++ch)
@@ -356,7 +295,7 @@ __device__ __forceinline__ int decp_parse(DecpBits& b, const DecTables* T, int C
                     for (int i = 0; i < nc; ++i, ++pos) {
                         int m = (val >> (cbits * i)) & ((1 << cbits) - 1);
                         if (is_signed) {
-                            m = (int)((uint32_t)m << (32 - cbits)) >> (32 - cbits);
+                            m = at3::sext((uint32_t)m, cbits);
                         } else if (m != 0 && b.rd(1)) {
                             m = -m;
                         }
@@ -440,7 +379,7 @@ __global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack(DecUnpackPar
     for (int i = tid; i < kTonalWords; i += NT) ((uint32_t*)&s_tone)[i] = 0u;
     __syncthreads();
     if (tid == 0) {
-        DecpBits b(s_w);
+        MsbReader b(s_w, 2048 * 8);
         const int why = decp_parse(b, T, C, &s_spec[0][0], s_wl, s_sf, s_tab, s_win, p.tone_vlc, p.tones ? &s_tone : nullptr);
         s_reason = why;
         if (why) atomicAdd(&p.rejected[why - 1], 1ull);
@@ -461,32 +400,17 @@ __global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack(DecUnpackPar
         const float* sp = &s_spec[ch][band * 128];
         const float r0 = rejected ? 0.0f : sp[a];
         const float i0 = rejected ? 0.0f : sp[bb];
-        const float c = cs[n], sn = cs[n + 1];
-        cpx v;
-        v.r = -2.0f * (i0 * sn + r0 * c);
-        v.i = -2.0f * (i0 * c - r0 * sn);
-        s_f[(ch * 16 + band) * 64 + at3::fft_leaf_pos<64>(k2)] = v;
+        s_f[(ch * 16 + band) * 64 + at3::fft_leaf_pos<64>(k2)] = at3::midct_pre(r0, i0, cs[n], cs[n + 1]);
     }
     __syncthreads();
     at3::fft_lds<64, false>(s_f, 64, 16 * C, T->tw64, tid, NT);
     // post-rotation (mdct.h): the whole Buf[256] of each subband
     for (int j = tid; j < C * 1024; j += NT) {
         const int ch = j >> 10, band = (j >> 6) & 15, k2 = j & 63, n = 2 * k2;
-        const cpx v = s_f[j];
-        const float c = cs[n], sn = cs[n + 1];
-        const float r1 = v.r * c + v.i * sn, i1 = v.r * sn - v.i * c;
+        float r1, i1;
+        at3::midct_post(s_f[j], cs[n], cs[n + 1], r1, i1);
         float* o = p.raw + decp_rec(f + 2, s, ch, p.n_streams, C) * 4096 + band * 256;
-        if (n < 64) {
-            o[191 - n] = r1;
-            o[192 + n] = r1;
-            o[64 + n] = i1;
-            o[63 - n] = -i1;
-        } else {
-            o[191 - n] = r1;
-            o[n - 64] = -r1;
-            o[64 + n] = i1;
-            o[319 - n] = i1;
-        }
+        at3::midct_unfold<64>(n, r1, i1, [&](int x, float v) { o[x] = v; });
     }
 }
 
@@ -614,11 +538,7 @@ __global__ __launch_bounds__(256) void k_at3pd_synth(DecSynthParams p)
                 acc = acc + (e + g);
             }
         }
-        acc = acc > 1.0f ? 1.0f : acc;
-        acc = acc < -1.0f ? -1.0f : acc;
-        const size_t idx = (((size_t)s * F + f) * 2048 + o) * C + ch;
-        if (p.s16) ((int16_t*)p.out)[idx] = (int16_t)__float2int_rn(acc * 32767.0f);
-        else ((float*)p.out)[idx] = acc;
+        at3::store_pcm(p.out, (((size_t)s * F + f) * 2048 + o) * C + ch, acc, p.s16);
     }
 }
 

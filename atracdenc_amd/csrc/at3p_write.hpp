@@ -11,6 +11,7 @@
 // that fits is found from one prefix sum. What does not depend on the spectrum at all - the three leading bits,
 // TConfigure and TWordLenEncoder for each (channels, units) - is formed on the host (WriteTables::head).
 #pragma once
+#include "at3_bits.hpp"
 #include "at3_common.hpp"
 
 namespace at3p {
@@ -167,13 +168,7 @@ __device__ __forceinline__ void frame_put(uint32_t* words, int pos, uint32_t val
 {
     if (pos + n > kFrameBytes * 8) return;
     val &= (1u << n) - 1u;
-    const int w = pos >> 5, off = pos & 31, room = 32 - off;
-    if (n <= room) {
-        atomicOr(&words[w], val << (room - n));
-    } else {
-        atomicOr(&words[w], val >> (n - room));
-        atomicOr(&words[w + 1], val << (32 - (n - room)));
-    }
+    at3::or_bits_msb(words, pos, val, n);
 }
 
 // a lane's run of codes strung together in registers, handed to the shared frame one 32-bit word at a time
