@@ -191,7 +191,7 @@ PROTOTYPES = {
     "at3phip_get_timings": (_RC, [_VP, _F32P, _F32P]), "at3phip_get_write_timing": (_RC, [_VP, _F32P]),
     "at3phip_host_tables": (_RC, [_VP, _SZ]), "at3phip_host_write_tables": (_RC, [_VP, _SZ]),
     "at3phip_host_tone_find_tables": (_RC, [_VP, _SZ]), "at3phip_host_tone_gates": (_RC, [_VP, _I32, _I32, _VP]),
-    "at3phip_host_tone_flags": (_U32, []),
+    "at3phip_host_tone_flags": (_U32, []), "at3phip_host_allocate": (_RC, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     # include/at3phip.h: the ATRAC3plus decoder
     "at3phip_decoder_create": (_RC, [_P(At3pDecoderConfig), _P(_VP)]), "at3phip_decoder_destroy": (None, [_VP]),
     "at3phip_decoder_last_error": (_STR, [_VP]), "at3phip_decoder_reset": (_RC, [_VP]), "at3phip_decoder_sync": (_RC, [_VP]),
@@ -208,7 +208,7 @@ def build_library(verbose=False):
     """Compile libat3hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fvisibility=hidden", "-fPIC", "-shared",
            "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-o", LIB_PATH, os.path.join(CSRC, "at3hip.hip"), os.path.join(CSRC, "at1hip.hip"), os.path.join(CSRC, "at3phip.hip"),
-           os.path.join(CSRC, "resample.hip"), os.path.join(CSRC, "loudness.hip"), os.path.join(CSRC, "at3_tables.cpp")]
+           os.path.join(CSRC, "at3p_alloc.hip"), os.path.join(CSRC, "resample.hip"), os.path.join(CSRC, "loudness.hip"), os.path.join(CSRC, "at3_tables.cpp")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -798,6 +798,7 @@ def at3p_host_tone_gates(bands, lib_path=None):
     return out
 
 
+AT3PHIP_ALLOC_ADAPTIVE = 128   # flag of the frame-writing calls: word lengths chosen per frame (include/at3phip.h, ADAPTIVE WORD LENGTHS)
 AT3PHIP_TONES_SHARED = 64   # flag of the tonal calls: twin bands of a stereo frame are written once (include/at3phip.h, SHARING)
 
 
@@ -809,6 +810,23 @@ def at3p_host_tone_flags(lib_path=None):
 
 def _tone_flags(gated, shared):
     return (AT3PHIP_TONES_GATED if gated else 0) | (AT3PHIP_TONES_SHARED if shared else 0)
+
+
+def _alloc_flag(adaptive):
+    return AT3PHIP_ALLOC_ADAPTIVE if adaptive else 0
+
+
+def at3p_host_allocate(sfi, bits, tail_bits, lib_path=None):
+    """at3phip_host_allocate (no GPU): steps A3-A5 of include/at3phip.h, ADAPTIVE WORD LENGTHS, on a cost table: sfi uint8 [C, 32],
+    bits uint16 [C, 32, 8] (entry w = the unit's bits at word length w) -> (wl uint8 [C, 32], N, t*, k*)."""
+    sfi, bits = np.ascontiguousarray(sfi, np.uint8), np.ascontiguousarray(bits, np.uint16)
+    C = sfi.shape[0]
+    assert sfi.shape == (C, 32) and bits.shape == (C, 32, 8), (sfi.shape, bits.shape)
+    wl, out = np.zeros((C, 32), np.uint8), np.zeros(3, np.int32)
+    rc = _need(load_library(lib_path), "at3phip_host_allocate")(_vp(sfi), _vp(bits), C, int(tail_bits), _vp(wl), _vp(out[0:1]), _vp(out[1:2]), _vp(out[2:3]))
+    if rc != 0:
+        raise At3HipError(f"at3phip_host_allocate failed ({rc})")
+    return wl, int(out[0]), int(out[1]), int(out[2])
 
 
 class At3pHip(_Context):
@@ -900,21 +918,21 @@ class At3pHip(_Context):
     def pqf_mdct_device(self, pcm_ptr, n_frames, specs_ptr):
         self.pqf_mdct_ptr(pcm_ptr, n_frames, None, None, specs_ptr, _device_flags(False))
 
-    def write_frames(self, specs, win_flags=None, tonal=None):
+    def write_frames(self, specs, win_flags=None, tonal=None, adaptive=False):
         """ScaleFrame + WriteFrame: specs [S, F, C, 2048], win_flags uint16 [S, F, C] or None, tonal records of
         AT3P_TONAL_BLOCK_DTYPE [S, F] (pack_tonal_blocks) or None: no frame carries a tonal block (at3phip_write_frames)
-        -> frames uint8 [S, F, 2048]."""
+        -> frames uint8 [S, F, 2048]. adaptive: AT3PHIP_ALLOC_ADAPTIVE, word lengths chosen per frame to fill it."""
         specs = np.ascontiguousarray(specs, dtype=np.float32)
         assert specs.ndim == 4 and specs.shape[0] == self.n_streams and specs.shape[2:] == (self.channels, 2048), specs.shape
         nf = specs.shape[1]
         fl, flp = self._flags(win_flags, nf)
         out = np.zeros((self.n_streams, nf, 2048), np.uint8)
         if tonal is None:
-            self.write_frames_ptr(specs.ctypes.data, nf, flp, out.ctypes.data, 0)
+            self.write_frames_ptr(specs.ctypes.data, nf, flp, out.ctypes.data, _alloc_flag(adaptive))
         else:
             tonal = np.ascontiguousarray(tonal, dtype=AT3P_TONAL_BLOCK_DTYPE)
             assert tonal.shape == (self.n_streams, nf), tonal.shape
-            self.write_frames_tonal_ptr(specs.ctypes.data, nf, flp, tonal.ctypes.data, out.ctypes.data, 0)
+            self.write_frames_tonal_ptr(specs.ctypes.data, nf, flp, tonal.ctypes.data, out.ctypes.data, _alloc_flag(adaptive))
         return out
 
     def _encode_frames_host(self, pcm, dtype, raw, flags=0):
@@ -925,15 +943,16 @@ class At3pHip(_Context):
         raw(pcm.ctypes.data, nf, out.ctypes.data, flags)
         return out
 
-    def encode_frames(self, pcm):
-        """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, 2048] (tonal analysis finding nothing; no look-ahead delay)."""
-        return self._encode_frames_host(pcm, np.float32, self.encode_frames_ptr)
+    def encode_frames(self, pcm, adaptive=False):
+        """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, 2048] (tonal analysis finding nothing; no look-ahead delay).
+        adaptive (here and in the encode calls below): AT3PHIP_ALLOC_ADAPTIVE, word lengths chosen per frame to fill it."""
+        return self._encode_frames_host(pcm, np.float32, self.encode_frames_ptr, _alloc_flag(adaptive))
 
-    def encode_frames_s16(self, pcm):
+    def encode_frames_s16(self, pcm, adaptive=False):
         """pcm int16 [S, F, 2048, C] (host) -> frames uint8 [S, F, 2048] (at3phip_encode_frames_short): the frames of
         encode_frames() on pcm / 32768 as float32, bit for bit; the samples cross the bus as 16-bit and are widened by the
         filter bank. Calls of both kinds may alternate."""
-        return self._encode_frames_host(pcm, np.int16, self.encode_frames_s16_ptr)
+        return self._encode_frames_host(pcm, np.int16, self.encode_frames_s16_ptr, _alloc_flag(adaptive))
 
     def analyse_tones(self, bands, gated=False, shared=False):
         """bands float32 [S, F, C, 16, 128] (what pqf() returns) -> (blocks of AT3P_TONAL_BLOCK_DTYPE [S, F], residual
@@ -956,34 +975,34 @@ class At3pHip(_Context):
         self.analyse_tones_ptr(bands_ptr, n_frames, blocks.ctypes.data, residual_ptr, _device_flags(False) | _tone_flags(gated, shared))
         return blocks
 
-    def encode_frames_tonal(self, pcm, gated=False, shared=False):
+    def encode_frames_tonal(self, pcm, gated=False, shared=False, adaptive=False):
         """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, 2048] with the tone analysis (at3phip_encode_frames_tonal): frame f
         of the stream holds the residual of input frame f-1 and the block of frame f-2, so one trailing frame of silence flushes.
         gated: AT3PHIP_TONES_GATED, shared: AT3PHIP_TONES_SHARED, as in analyse_tones()."""
-        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr, _tone_flags(gated, shared))
+        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr, _tone_flags(gated, shared) | _alloc_flag(adaptive))
 
-    def encode_frames_tonal_s16(self, pcm, gated=False, shared=False):
+    def encode_frames_tonal_s16(self, pcm, gated=False, shared=False, adaptive=False):
         """The same for int16 PCM (at3phip_encode_frames_tonal_short): the frames of encode_frames_tonal() on pcm / 32768."""
-        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr, _tone_flags(gated, shared))
+        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr, _tone_flags(gated, shared) | _alloc_flag(adaptive))
 
-    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False):
+    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False, adaptive=False):
         """Device-resident float32 PCM / frames; ordering and what stays untouched until sync() as in encode_frames_device."""
-        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared))
+        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared) | _alloc_flag(adaptive))
 
-    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False):
+    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False, adaptive=False):
         """Device-resident int16 PCM / frames, as encode_frames_tonal_device."""
-        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared))
+        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared) | _alloc_flag(adaptive))
 
-    def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
+    def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, adaptive=False):
         """asynchronous=True only queues the call (AT3HIP_ASYNC): sync() before the frames are read, and both buffers stay
         untouched until then. The context's streams are non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): they wait for no
         other stream, so whatever produces the PCM must be complete before the call."""
-        self.encode_frames_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous))
+        self.encode_frames_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _alloc_flag(adaptive))
 
-    def encode_frames_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False):
+    def encode_frames_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, adaptive=False):
         """Device-resident int16 PCM / frames (raw pointers; the PCM needs only 2-byte alignment). Stream ordering and what
         stays untouched until sync() as in encode_frames_device."""
-        self.encode_frames_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous))
+        self.encode_frames_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _alloc_flag(adaptive))
 
     def timings(self):
         a, b, w = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()

@@ -1,0 +1,477 @@
+// ATRAC3plus frame writer with adaptive word lengths (gfx950): include/at3phip.h, ADAPTIVE WORD LENGTHS, steps A1-A6.
+//   k_at3p_write_adaptive        the fixed writer's scaler and quantiser (at3p_write.hpp), then per frame the cost table of
+//                                every (channel, unit, word length), the two full scans over the candidate allocations and the
+//                                frame in the fixed writer's layout, one (stream, frame) per workgroup;
+//   k_at3p_write_adaptive_tonal  the same with a record per frame, whose block counts in every candidate's bits.
+// The word lengths are no longer the reference's table, so the word-length section (TWordLenEncoder, at3p_bitstream.cpp:
+// 170-252) is priced and written here and WriteTables::head is not used. Spectra, tail and tonal block go through the fixed
+// writer's emit_chunk, tonal_price and tonal_emit. host_allocate is steps A3-A5 on the host (at3phip_host_allocate).
+#pragma once
+#include "at3p_write.hpp"
+
+namespace at3p {
+
+constexpr int kAllocTMin = -21, kAllocTMax = 63, kAllocKMax = 64;
+
+// A3: clamp(floor((sfi - t) / 3), 0, 7)
+__host__ __device__ inline int alloc_want(int sfi, int t)
+{
+    const int d = sfi - t;
+    return d <= 0 ? 0 : d >= 21 ? 7 : d / 3;
+}
+// FindBestWlDeltaEncode's range for an OR-accumulated largest delta: first table | last table << 2
+__host__ __device__ inline int alloc_wl_range(int max_delta) { return max_delta >= 3 ? (2 | 3 << 2) : max_delta == 2 ? (1 | 1 << 2) : 0; }
+
+// ---- host: steps A3-A5 on a cost table ---------------------------------------------------------------------------------
+// sfi [channels][32], bits [channels][32][8] (entry w = the unit's bits at word length w, entry 0 unused) -> wl [channels][32]
+// (0 at and above N), N, t*, k*; returns Bits(A(t*, k*)).
+inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels, int tail_bits, uint8_t* wl_out, int* n_units, int* t_out, int* k_out)
+{
+    int wl[2][32];
+    int N = 1, took = 0;
+    auto form = [&](int t, int k) {   // A(t, k) into wl and N; took: the units that took the t - 1 value
+        int top = -1;
+        for (int qu = 0; qu < 32; ++qu)
+            for (int ch = 0; ch < channels; ++ch) {
+                wl[ch][qu] = alloc_want(sfi[ch * 32 + qu], t);
+                if (wl[ch][qu]) top = qu;
+            }
+        N = top < 0 ? 1 : top + 1;
+        if (N >= 29 && N <= 31) N = 32;
+        took = 0;
+        for (int qu = 0, left = k; qu < 32; ++qu)
+            for (int ch = 0; ch < channels; ++ch) {
+                if (qu >= N) {
+                    wl[ch][qu] = 0;
+                    continue;
+                }
+                const int up = alloc_want(sfi[ch * 32 + qu], t - 1);
+                if (left > 0 && up > wl[ch][qu]) {
+                    wl[ch][qu] = up;
+                    --left;
+                    ++took;
+                }
+                if (wl[ch][qu] == 0) wl[ch][qu] = 1;
+            }
+    };
+    auto count = [&]() {   // Bits(A)
+        long total = 6 + tail_bits + channels * (2 + 6 * N) + 1 + channels * (4 + 3 * N) + channels * 4 * AT3P_SB_POWGRPS[AT3P_QU_TO_SB[N - 1]];
+        for (int ch = 0; ch < channels; ++ch) {
+            // (FindBestWlDeltaEncode sums from the list's second entry in both modes: channel 1's first code counts in the
+            // largest delta and in the bits, not in the choice of the table)
+            int len[4] = {0, 0, 0, 0}, mx = 0;
+            for (int qu = ch ? 0 : 1; qu < N; ++qu) {
+                const int d = wl[ch][qu] - (ch ? wl[0][qu] : wl[0][qu - 1]);
+                mx |= d < 0 ? -d : d;
+                if (qu)
+                    for (int i = 0; i < 4; ++i) len[i] += AT3P_WL_VLC[i][d & 7] >> 12;
+            }
+            const int r = alloc_wl_range(mx), a = r & 3, b = r >> 2, idx = len[b] < len[a] ? b : a;
+            total += (ch ? 6 + (AT3P_WL_VLC[idx][(wl[1][0] - wl[0][0]) & 7] >> 12) : 11) + len[idx];
+            for (int qu = 0; qu < N; ++qu) total += bits[(ch * 32 + qu) * 8 + wl[ch][qu]];
+        }
+        return total > 0x7fffffffl ? 0x7fffffff : (int)total;
+    };
+    int ts = kAllocTMax + 1, ks = 0;
+    for (int t = kAllocTMax; t >= kAllocTMin; --t) {   // every t: the smallest that fits
+        form(t, 0);
+        if (count() <= kSizeBits) ts = t;
+    }
+    if (ts > kAllocTMax) ts = kAllocTMax;              // nothing fits (a caller's table only)
+    for (int k = 0; k <= kAllocKMax; ++k) {            // every k: the largest that fits
+        form(ts, k);
+        if (count() <= kSizeBits) ks = k;
+    }
+    form(ts, ks);
+    for (int ch = 0; ch < channels; ++ch)
+        for (int qu = 0; qu < 32; ++qu) wl_out[ch * 32 + qu] = (uint8_t)wl[ch][qu];
+    *n_units = N;
+    *t_out = ts;
+    *k_out = took;   // k* as reported: a k beyond the units that can take the t - 1 value gives the same allocation
+    return count();
+}
+
+// ---- device ----------------------------------------------------------------------------------------------------------
+// The fixed writer's parameters and the word-length code tables (code | length << 12 per delta & 7), which the fixed writer
+// only needs on the host: nothing is allocated or uploaded for the adaptive path.
+template <typename P>
+struct AdaptiveParams : P {
+    uint16_t wl_vlc[4][8];
+};
+
+// TUnit::GetOrCompute's pricing of one 16-line chunk under one code table, as k_at3p_write_with has it: the symbols are formed
+// once per packing and only looked up per table.
+struct ChunkPricer {
+    uint32_t vals[16];
+    uint32_t prev_packing;
+    int n_signs;
+    __device__ __forceinline__ void reset()
+    {
+        prev_packing = 0xffffffffu;
+        n_signs = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) vals[k] = 0u;
+    }
+    __device__ __forceinline__ int price(const int (&q)[16], uint32_t d, const uint32_t* len4)
+    {
+        const int off = (int)(d & 0xffffu), group_size = (int)((d >> 16) & 15u), num_coeffs = (int)((d >> 20) & 15u);
+        if ((d >> 20) != prev_packing) {   // num_coeffs, bits, is_signed
+            prev_packing = d >> 20;
+            const int cbits = (int)((d >> 24) & 15u), is_signed = (int)(d >> 28);
+            if (num_coeffs == 1) n_signs = pack_symbols<1>(q, cbits, is_signed, vals);
+            else if (num_coeffs == 2) n_signs = pack_symbols<2>(q, cbits, is_signed, vals);
+            else n_signs = pack_symbols<4>(q, cbits, is_signed, vals);
+        }
+        const int n_sym = 16 / num_coeffs;
+        int bits = n_signs + (group_size != 1 ? n_sym / group_size : 0);   // one flag bit per group
+        auto len_of = [&](int sidx) {
+            const int e = off + (int)vals[sidx];
+            return (int)((len4[e >> 3] >> (4 * (e & 7))) & 15u);
+        };
+#pragma unroll
+        for (int sidx = 0; sidx < 4; ++sidx) bits += len_of(sidx);
+        if (num_coeffs <= 2) {
+#pragma unroll
+            for (int sidx = 4; sidx < 8; ++sidx) bits += len_of(sidx);
+            if (num_coeffs == 1) {
+#pragma unroll
+                for (int sidx = 8; sidx < 16; ++sidx) bits += len_of(sidx);
+            }
+        }
+        return bits;
+    }
+};
+
+// QuantMantisas without the energy pass (atrac_scale.cpp:46-54): the multiplication and the rounding of the fixed writer
+__device__ __forceinline__ void alloc_quantise(const float (&v)[16], float mul, int (&q)[16])
+{
+#pragma unroll
+    for (int k = 0; k < 16; ++k) q[k] = __float2int_rn(v[k] * mul);
+}
+
+__device__ __forceinline__ int alloc_wave_sum(int v, int lane) { return __builtin_amdgcn_readlane(at3::wave_inclusive_scan(v, lane), 63); }
+
+// One candidate A(t, k) on a wavefront, lane = 2 * unit + channel (the order of A3's walk). Wave-uniform: N, the two code
+// tables, the section's VLC bits per channel and Bits(A); per lane: the word length and its VLC under its channel's table.
+struct AllocEval {
+    int wl, N, idx0, idx1, sum0, sum1, total;
+    int delta, len;       // the lane's delta & 7 and its code's length (0: the lane writes no code)
+};
+__device__ __forceinline__ AllocEval alloc_eval(int t, int k, int sfi, bool act, int lane, int nch, const uint16_t* s_B, const uint16_t* s_wlv,
+                                                const uint8_t* s_pw, int tail_bits)
+{
+    AllocEval r;
+    const int qu = lane >> 1, ch = lane & 1;
+    const int w0 = alloc_want(sfi, t), w1 = alloc_want(sfi, t - 1);
+    const unsigned long long has = __ballot(act && w0 >= 1);
+    int N = has ? ((63 - __builtin_clzll(has)) >> 1) + 1 : 1;
+    if (N >= 29 && N <= 31) N = 32;   // the syntax has no 29..31
+    const bool below = act && qu < N;
+    const bool up = below && w1 > w0;
+    const unsigned long long upm = __ballot(up);
+    const int rank = __builtin_popcountll(upm & ((1ull << lane) - 1ull));
+    int wl = (up && rank < k) ? w1 : w0;
+    if (wl == 0) wl = 1;
+    if (!below) wl = 0;
+    // TWordLenEncoder: channel 0 against the previous unit (two lanes down), channel 1 against channel 0 (one lane down)
+    const int src = lane - (ch ? 1 : 2);
+    const int ref = __builtin_amdgcn_ds_bpermute(4 * (src < 0 ? 0 : src), wl);
+    const bool coded = below && (ch == 1 || qu >= 1);
+    const int d = coded ? wl - ref : 0, ad = d < 0 ? -d : d;
+    int m0 = 0, m1 = 0;   // the OR-accumulated largest deltas
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        const unsigned long long bm = __ballot(coded && ((ad >> b) & 1));
+        if (bm & 0x5555555555555555ull) m0 |= 1 << b;
+        if (bm & 0xaaaaaaaaaaaaaaaaull) m1 |= 1 << b;
+    }
+    const int r0 = alloc_wl_range(m0), r1 = alloc_wl_range(m1);
+    const int ta = ch ? (r1 & 3) : (r0 & 3), tb = ch ? (r1 >> 2) : (r0 >> 2);
+    const int la = coded ? (int)(s_wlv[ta * 8 + (d & 7)] >> 12) : 0, lb = coded ? (int)(s_wlv[tb * 8 + (d & 7)] >> 12) : 0;
+    // one sum for the four lists: a code has at most 5 bits and a list at most 32 codes, so 8 bits each
+    // (FindBestWlDeltaEncode sums from the list's second entry in both modes: channel 1's first code, lane 1's, counts in the
+    // largest delta and in the bits, not in the choice of the table)
+    const uint32_t sums = (uint32_t)alloc_wave_sum(qu >= 1 ? (la | (lb << 8)) << (16 * ch) : 0, lane);
+    const int s0a = (int)(sums & 0xffu), s0b = (int)((sums >> 8) & 0xffu), s1a = (int)((sums >> 16) & 0xffu), s1b = (int)(sums >> 24);
+    r.idx0 = s0b < s0a ? (r0 >> 2) : (r0 & 3);   // the first table with the fewest bits
+    r.idx1 = s1b < s1a ? (r1 >> 2) : (r1 & 3);
+    r.sum0 = s0b < s0a ? s0b : s0a;
+    r.len = ch ? (s1b < s1a ? lb : la) : (s0b < s0a ? lb : la);
+    r.sum1 = (s1b < s1a ? s1b : s1a) + __builtin_amdgcn_readlane(r.len, 1);
+    const int bsum = alloc_wave_sum(below ? (int)s_B[(ch * 32 + qu) * 8 + wl] : 0, lane);
+    r.total = 6 + 11 + r.sum0 + (nch == 2 ? 6 + r.sum1 : 0) + nch * (2 + 6 * N) + 1 + nch * (4 + 3 * N) + bsum + nch * (int)s_pw[N - 1] + tail_bits;
+    r.wl = wl;
+    r.N = N;
+    r.delta = d & 7;
+    return r;
+}
+
+template <typename P>
+__global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams<P> p)
+{
+    constexpr bool kTonal = P::kTonal;
+    __shared__ uint32_t s_out[kFrameBytes / 4];
+    __shared__ uint32_t s_qbits[2][32][7][8];  // A2: the bits of each unit at each word length under each of its eight tables
+    __shared__ uint16_t s_B[2][32][8];         // B[ch][qu][w], entry 0 unused
+    __shared__ uint8_t s_tabw[2][32][8];       // tab[ch][qu][w]
+    __shared__ uint32_t s_max[2][32];
+    __shared__ float s_scale[64], s_inv[8];
+    __shared__ uint8_t s_sfi[2][32], s_wl[2][32], s_pw[32];
+    __shared__ uint16_t s_wlv[32];
+    __shared__ uint32_t s_wsum[4];
+    __shared__ int s_tfit[4], s_kfit[4];       // per wavefront: the smallest t and the largest k of its share that fit
+    __shared__ int s_n, s_pos_sf;
+    __shared__ uint16_t s_cb[256];             // the chosen table's bits per chunk, in stream order (channel, chunk)
+    __shared__ uint32_t s_off[256];            // and their exclusive prefix sums per channel
+    __shared__ uint32_t s_info[56];
+    __shared__ uint32_t s_len4[(kLenEntries + 7) / 8];
+    __shared__ uint32_t s_rec[kTonal ? kTonalBlockWords : 1];
+
+    const WriteTables* W = p.W;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nch = p.nch;
+    const size_t item = blockIdx.x;
+    // The thread's chunk in stream order: every thread walks all seven word lengths, so nothing is gained by dealing the
+    // threads by word length as the fixed writer does.
+    const int ch = tid >> 7, c = tid & 127;
+    const bool active = ch < nch;
+    const int qu = at3p_qu_of_line(16 * c);
+
+    s_out[tid] = 0u;
+    s_out[256 + tid] = 0u;
+#pragma unroll
+    for (int i = 0; i < 14; ++i) (&s_qbits[0][0][0][0])[tid + 256 * i] = 0u;
+    constexpr int kLenWords = (kLenEntries + 7) / 8, kLenIt = (kLenWords + 255) / 256;
+    float x[16];
+    {
+        const float4* src = reinterpret_cast<const float4*>(p.specs + (item * nch + (active ? ch : 0)) * 2048 + 16 * c);
+        float4 xv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) xv[k] = src[k];
+        const float scale_v = W->scale[tid & 63];
+        const uint32_t info_v = W->info56[(tid >= 64 && tid < 120) ? tid - 64 : 0];
+        const float inv_v = W->inv_mant[tid & 7];
+        const uint32_t pw_v = 4u * W->sb_powgrps[W->qu_to_sb[tid & 31]];
+        const uint16_t wlv_v = (&p.wl_vlc[0][0])[tid & 31];
+        uint32_t len_v[kLenIt];
+#pragma unroll
+        for (int i = 0; i < kLenIt; ++i) len_v[i] = W->len4[tid + 256 * i < kLenWords ? tid + 256 * i : kLenWords - 1];
+        if (tid < 64) {
+            (&s_max[0][0])[tid] = 0u;
+            s_scale[tid] = scale_v;
+        }
+        if (tid >= 64 && tid < 120) s_info[tid - 64] = info_v;
+        if (tid >= 120 && tid < 128) s_inv[tid - 120] = inv_v;
+        if (tid >= 192 && tid < 224) s_pw[tid - 192] = (uint8_t)pw_v;
+        if (tid >= 224) s_wlv[tid - 224] = wlv_v;
+        if constexpr (kTonal) {
+            if (tid >= 128 && tid < 128 + kTonalBlockWords) s_rec[tid - 128] = reinterpret_cast<const uint32_t*>(p.tonal + item)[tid - 128];
+        }
+#pragma unroll
+        for (int i = 0; i < kLenIt; ++i)
+            if (tid + 256 * i < kLenWords) s_len4[tid + 256 * i] = len_v[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4 v = active ? xv[k] : float4{0.0f, 0.0f, 0.0f, 0.0f};
+            x[4 * k] = v.x; x[4 * k + 1] = v.y; x[4 * k + 2] = v.z; x[4 * k + 3] = v.w;
+        }
+    }
+    __syncthreads();
+    // ---- A1, TScaler::Scale: the unit's largest magnitude (order-free), its scale factor, the scaled values ----
+    {
+        float m = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) m = fmaxf(m, fabsf(x[k]));
+        if (active) atomicMax(&s_max[ch][qu], __float_as_uint(m));
+    }
+    __syncthreads();
+    if (tid < 64) {
+        float maxAbs = __uint_as_float((&s_max[0][0])[tid]);
+        if (maxAbs > 1.0f) maxAbs = 1.0f;
+        int lo = 0, hi = 63;   // map::lower_bound: the first entry >= maxAbs
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_scale[mid] < maxAbs) lo = mid + 1;
+            else hi = mid;
+        }
+        (&s_sfi[0][0])[tid] = (uint8_t)lo;
+    }
+    __syncthreads();
+    {
+        const float sf = s_scale[s_sfi[active ? ch : 0][qu]];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            float v = x[k] / sf;
+            if (fabsf(v) >= 1.0f) v = (v > 0) ? 0.99999f : -0.99999f;
+            x[k] = v;
+        }
+    }
+    // ---- A2: every word length's mantissas and their bits under its eight code tables ----
+    int qv[16];
+    ChunkPricer pricer;
+    if (active) {
+#pragma unroll 1
+        for (int w = 1; w <= 7; ++w) {
+            alloc_quantise(x, s_inv[w], qv);
+            pricer.reset();
+            for (int i = 0; i < 8; ++i) atomicAdd(&s_qbits[ch][qu][w - 1][i], (uint32_t)pricer.price(qv, s_info[w - 1 + 7 * i], s_len4));
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < 2 * 32 * 7; e += 256) {   // the first table with the fewest bits
+        const uint32_t* b = &s_qbits[0][0][0][0] + 8 * e;
+        uint32_t best = b[0];
+        int bi = 0;
+        for (int i = 1; i < 8; ++i)
+            if (b[i] < best) {
+                best = b[i];
+                bi = i;
+            }
+        const int u = e / 7, w = e % 7 + 1;
+        (&s_B[0][0][0])[u * 8 + w] = (uint16_t)best;
+        (&s_tabw[0][0][0])[u * 8 + w] = (uint8_t)bi;
+    }
+    __syncthreads();
+    // ---- the tail's bits (formed once, as in the fixed writer), then A3-A5: every wavefront evaluates its share of the
+    //      candidates, lanes are units ----
+    uint32_t fl[2] = {0u, 0u};
+    int win_bits[2] = {0, 0};
+    for (int k = 0; k < nch; ++k) {
+        fl[k] = p.flags ? p.flags[item * nch + k] : 0u;
+        win_bits[k] = fl[k] == 0u ? 1 : ((fl[k] & 0xffu) == 0xffu ? 2 : 18);   // IsAllSteep keeps its mask in a uint8_t
+    }
+    int tail_bits = (nch == 2 ? 2 : 0) + win_bits[0] + win_bits[1] + nch + 1 + 1 + 2;
+    [[maybe_unused]] TonalPlan plan;
+    if constexpr (kTonal) {   // (priced by every wavefront: each needs the block's bits, wavefront 0 writes it)
+        tonal_price(s_rec, nch, lane, p.tone_vlc, &plan);
+        tail_bits += plan.bits;
+    }
+    const bool u_act = (lane & 1) < nch;
+    const int u_sfi = s_sfi[lane & 1][lane >> 1];
+    {
+        int tfit = kAllocTMax + 1;
+        for (int t = kAllocTMax - wave; t >= kAllocTMin; t -= 4) {   // descending: the last one that fits is the smallest
+            const AllocEval e = alloc_eval(t, 0, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+            if (e.total <= kSizeBits) tfit = t;
+        }
+        if (lane == 0) s_tfit[wave] = tfit;
+    }
+    __syncthreads();
+    int t_star = kAllocTMax;   // (nothing fits: a caller's table only, see host_allocate)
+    for (int w = 0; w < 4; ++w)
+        if (s_tfit[w] < t_star) t_star = s_tfit[w];
+    {
+        int kfit = 0;
+        for (int k = wave; k <= kAllocKMax; k += 4) {
+            const AllocEval e = alloc_eval(t_star, k, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+            if (e.total <= kSizeBits) kfit = k;
+        }
+        if (lane == 0) s_kfit[wave] = kfit;
+    }
+    __syncthreads();
+    // ---- A6: the frame's first bits, the unit count and the word-length section, by wavefront 0 ----
+    if (wave == 0) {
+        int k_star = 0;
+        for (int w = 0; w < 4; ++w)
+            if (s_kfit[w] > k_star) k_star = s_kfit[w];
+        const AllocEval e = alloc_eval(t_star, k_star, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+        s_wl[lane & 1][lane >> 1] = (uint8_t)e.wl;
+        const int incl = at3::wave_inclusive_scan(e.len << (16 * (lane & 1)), lane);
+        const int before = ((incl >> (16 * (lane & 1))) & 0xffff) - e.len;
+        const int pos1 = 20 + e.sum0;   // channel 1's list
+        if (e.len) {
+            const int idx = (lane & 1) ? e.idx1 : e.idx0;
+            frame_put(s_out, ((lane & 1) ? pos1 + 6 : 20) + before, s_wlv[idx * 8 + e.delta] & 0xfffu, e.len);
+        }
+        if (lane == 0) {
+            frame_put(s_out, 1, (uint32_t)nch - 1u, 2);
+            frame_put(s_out, 3, (uint32_t)e.N - 1u, 5);     // (then the mute bit, 0)
+            frame_put(s_out, 9, 3u, 2);                     // channel 0: mode 3, no flags, no position
+            frame_put(s_out, 15, (uint32_t)e.idx0, 2);
+            frame_put(s_out, 17, (uint32_t)e.wl, 3);
+            if (nch == 2) {
+                frame_put(s_out, pos1, 1u, 2);              // channel 1: mode 1, no flags
+                frame_put(s_out, pos1 + 4, (uint32_t)e.idx1, 2);
+            }
+            s_n = e.N;
+            s_pos_sf = pos1 + (nch == 2 ? 6 + e.sum1 : 0);
+        }
+    }
+    __syncthreads();
+    const int N = s_n;
+    // ---- scale factor indices, code table indices, spectra and power groups per channel, tail: the fixed writer's layout ----
+    const int pos_sf = s_pos_sf;
+    const int pos_ct = pos_sf + nch * (2 + 6 * N);
+    const int pos_data = pos_ct + 1 + nch * (4 + 3 * N);
+    if (tid < 64) {
+        const int k = tid >> 5, q = tid & 31;
+        if (k < nch && q < N) {
+            frame_put(s_out, pos_sf + k * (2 + 6 * N) + 2 + 6 * q, s_sfi[k][q], 6);
+            frame_put(s_out, pos_ct + 1 + k * (4 + 3 * N) + 4 + 3 * q, s_tabw[k][q][s_wl[k][q]], 3);
+        }
+    }
+    if (tid == 64) frame_put(s_out, pos_ct, 1u, 1);   // "use full table"
+    const bool coded = active && qu < N;
+    const int wl = coded ? s_wl[ch][qu] : 1;
+    const uint32_t d = s_info[wl - 1 + 7 * s_tabw[active ? ch : 0][qu][wl]];
+    alloc_quantise(x, s_inv[wl], qv);
+    pricer.reset();
+    s_cb[tid] = (uint16_t)(coded ? pricer.price(qv, d, s_len4) : 0);
+    __syncthreads();
+    {   // prefix sums in stream order: entry u = channel u / 128, chunk u % 128
+        const int v = (int)s_cb[tid];
+        const int incl = at3::wave_inclusive_scan(v, lane);
+        if (lane == 63) s_wsum[wave] = (uint32_t)incl;
+        __syncthreads();
+        s_off[tid] = (uint32_t)(incl - v) + ((wave & 1) ? s_wsum[wave - 1] : 0u);
+    }
+    __syncthreads();
+    const int ch_total[2] = {(int)(s_wsum[0] + s_wsum[1]), (int)(s_wsum[2] + s_wsum[3])};
+    const int pw = s_pw[N - 1];
+    const int ch_base[2] = {pos_data, pos_data + ch_total[0] + pw};
+    if (coded) {
+        BitRun run;
+        run.start(s_out, ch_base[ch] + (int)s_off[tid]);
+        const int num_coeffs = (int)((d >> 20) & 15u);
+        if (num_coeffs == 1) emit_chunk<1>(W, qv, d, &run);
+        else if (num_coeffs == 2) emit_chunk<2>(W, qv, d, &run);
+        else emit_chunk<4>(W, qv, d, &run);
+        run.finish();
+    }
+    if (c == 0 && active) frame_put(s_out, ch_base[ch] + ch_total[ch], (1u << pw) - 1u, pw);   // (15, 4) per power group
+    if (kTonal ? tid == 50 : tid == 65) {
+        int pos = ch_base[nch - 1] + ch_total[nch - 1] + pw;
+        if (nch == 2) pos += 2;   // swap_channels, negate_coeffs
+        for (int k = 0; k < nch; ++k) {
+            if (win_bits[k] == 2) {
+                frame_put(s_out, pos, 2u, 2);
+            } else if (win_bits[k] == 18) {
+                frame_put(s_out, pos, 3u, 2);
+                for (int i = 0; i < 16; ++i) frame_put(s_out, pos + 2 + i, (fl[k] >> i) & 1u, 1);
+            }
+            pos += win_bits[k];
+        }
+        if constexpr (kTonal) {
+            pos += nch;           // gain compensation per channel
+            if (plan.bits) frame_put(s_out, pos, 1u, 1);
+            pos += 1 + plan.bits + 1;   // the tonal flag and block, no noise info
+        } else {
+            pos += nch + 1 + 1;   // gain compensation per channel, no tonal block, no noise info
+        }
+        frame_put(s_out, pos, 3u, 2);
+    }
+    if constexpr (kTonal) {
+        if (wave == 0)
+            tonal_emit(s_out, ch_base[nch - 1] + ch_total[nch - 1] + pw + (nch == 2 ? 2 : 0) + win_bits[0] + win_bits[1] + nch + 1, s_rec, nch,
+                       lane, p.tone_vlc, plan);
+    }
+    __syncthreads();
+    uint32_t* dst = reinterpret_cast<uint32_t*>(p.out + item * kFrameBytes);
+    dst[tid] = __builtin_bswap32(s_out[tid]);
+    dst[256 + tid] = __builtin_bswap32(s_out[256 + tid]);
+}
+// the two instantiations under the names they are launched by
+constexpr auto k_at3p_write_adaptive = k_at3p_write_adaptive_with<WriteParams>;
+constexpr auto k_at3p_write_adaptive_tonal = k_at3p_write_adaptive_with<WriteParamsTonal>;
+
+}  // namespace at3p

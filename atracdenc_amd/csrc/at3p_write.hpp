@@ -682,8 +682,7 @@ __global__ __launch_bounds__(256) void k_at3p_write_with(P p)
     dst[tid] = __builtin_bswap32(s_out[tid]);
     dst[256 + tid] = __builtin_bswap32(s_out[256 + tid]);
 }
-// the two instantiations under the names they are launched by
-constexpr auto k_at3p_write = k_at3p_write_with<WriteParams>;
-constexpr auto k_at3p_write_tonal = k_at3p_write_with<WriteParamsTonal>;
+// (instantiated, under the names k_at3p_write and k_at3p_write_tonal, by at3phip.hip alone: a second translation unit that
+// includes this file for the shared device functions gets no copy of the two kernels)
 
 }  // namespace at3p

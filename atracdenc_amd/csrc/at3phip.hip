@@ -62,6 +62,18 @@ struct at3phip_ctx : at3host::EngineBase {   // (no at3phip_set_stream: stream =
     float pqf_ms = 0.0f, mdct_ms = 0.0f, write_ms = 0.0f;
 };
 
+namespace at3p {
+// The fixed writer's two instantiations under the names they are launched by. Here and not in at3p_write.hpp: at3p_alloc.hip
+// includes that header too, and must not hold a second copy of these kernels.
+constexpr auto k_at3p_write = k_at3p_write_with<WriteParams>;
+constexpr auto k_at3p_write_tonal = k_at3p_write_with<WriteParamsTonal>;
+
+// The adaptive writer's launch (wp.tonal null: without records). Its kernels are a translation unit of their own, at3p_alloc.hip,
+// so that this one's device code stays instruction for instruction what it was; weak, because the stand-alone host programs
+// that link this file without that one (tests/test_owned_alloc_cpu.py) must still link: there the flag is an error.
+__attribute__((weak, visibility("default"))) void launch_write_adaptive(const WriteParamsTonal& wp, hipStream_t on);
+}
+
 namespace {
 
 #include "at3p_tone_vlc.inc"
@@ -128,8 +140,9 @@ int launch_mdct(at3phip_ctx* c, const float* d_bands, int n_frames, const uint16
 
 // tonal: the call's records [S][n_frames] in host memory, already checked (check_tonal), or null: the writer without records.
 // d_records: the same in device memory, as the tone analysis left them (valid by construction).
+// adaptive: AT3PHIP_ALLOC_ADAPTIVE, the writer of at3p_alloc.hpp.
 int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint16_t* win_flags, uint8_t* d_frames, hipStream_t on = nullptr,
-                 const at3phip_tonal_block* tonal = nullptr, const TonalBlock* d_records = nullptr)
+                 const at3phip_tonal_block* tonal = nullptr, const TonalBlock* d_records = nullptr, bool adaptive = false)
 {
     const size_t S = c->cfg.n_streams, C = c->cfg.channels;
     if (!on) on = c->stream;
@@ -141,17 +154,19 @@ int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint1
     wp.out = d_frames;
     wp.nch = (int)C;
     wp.n_items = (int)(S * n_frames);
-    if (d_records) {
-        wp.tonal = d_records;
-        memcpy(wp.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(wp.tone_vlc));
-        hipLaunchKernelGGL(k_at3p_write_tonal, dim3((unsigned)(S * n_frames)), dim3(256), 0, on, wp);
-    } else if (tonal) {
+    if (adaptive && !launch_write_adaptive) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_ADAPTIVE: this build has no adaptive writer (at3p_alloc.hip)");
+    if (tonal && !d_records) {
         if (!c->d_tonal) {
             const int rc = dev_alloc(c, &c->d_tonal, S * (size_t)c->cfg.max_frames);
             if (rc != AT3HIP_OK) return rc;
         }
         HIPCHK(c, hipMemcpyAsync(c->d_tonal, tonal, S * n_frames * sizeof(TonalBlock), hipMemcpyHostToDevice, on));
-        wp.tonal = c->d_tonal;
+        d_records = c->d_tonal;
+    }
+    wp.tonal = d_records;
+    if (adaptive) {
+        launch_write_adaptive(wp, on);
+    } else if (d_records) {
         memcpy(wp.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(wp.tone_vlc));
         hipLaunchKernelGGL(k_at3p_write_tonal, dim3((unsigned)(S * n_frames)), dim3(256), 0, on, wp);
     } else {
@@ -445,7 +460,7 @@ int at3phip_write_frames_tonal(at3phip_ctx* c, const float* specs, int32_t n_fra
     const float* d_specs = (flags & AT3HIP_PCM_ON_DEVICE) ? specs : c->d_specs;
     uint8_t* d_frames = (flags & AT3HIP_OUT_ON_DEVICE) ? frames : c->d_frames;
     const Stage stage = {specs, c->d_specs, items * c->cfg.channels * 2048 * sizeof(float), {{frames, c->d_frames, items * kFrameBytes}}, 2, {&at3phip_ctx::write_ms}};
-    return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames, nullptr, tonal); });
+    return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames, nullptr, tonal, nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0); });
 }
 
 }  // extern "C"
@@ -497,7 +512,7 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     HIPCHK(c, hipEventRecord(c->ev_specs[par], c->stream));
     HIPCHK(c, hipStreamWaitEvent(ws, c->ev_specs[par], 0));
     if (timed) HIPCHK(c, hipEventRecord(c->ev[4], ws));
-    rc = launch_write(c, d_specs, n_frames, nullptr, d_frames, ws, nullptr, kTones ? c->d_tone_writer[par] : nullptr);
+    rc = launch_write(c, d_specs, n_frames, nullptr, d_frames, ws, nullptr, kTones ? c->d_tone_writer[par] : nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0);
     if (rc != AT3HIP_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[3], ws));
     if (!(flags & AT3HIP_OUT_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(frames, c->d_frames, items * kFrameBytes, hipMemcpyDeviceToHost, ws));

@@ -1000,10 +1000,14 @@ public:
     // host: byte for byte the frames of this class around TAt3PToneAnalyser with UseGha = GHA_ENABLED. `gha` must then be null.
     // deviceGated: that analysis with AT3PHIP_TONES_GATED, byte for byte TAt3PToneAnalyser(channels, true)'s frames.
     // deviceShared: with AT3PHIP_TONES_SHARED, byte for byte TAt3PToneAnalyser(channels, deviceGated, true)'s frames.
+    // adaptive: every frame-writing call carries AT3PHIP_ALLOC_ADAPTIVE (include/at3phip.h, ADAPTIVE WORD LENGTHS): the word
+    // lengths are chosen on the device, with a host analyser too; the mirror has no allocator of its own.
     TAt3PEncoder(TCompressedOutputPtr&& out, int channels, int batchFrames = 64, int deviceId = 0, TAt3PSettings settings = TAt3PSettings(),
-                 IAt3PGhaProcessor* gha = nullptr, bool deviceTones = false, bool deviceGated = false, bool deviceShared = false)
+                 IAt3PGhaProcessor* gha = nullptr, bool deviceTones = false, bool deviceGated = false, bool deviceShared = false,
+                 bool adaptive = false)
         : Out(std::move(out)), Channels((size_t)channels), BatchFrames(batchFrames), FrameFloats((size_t)AT3PHIP_FRAME * (size_t)channels),
-          Settings(settings), Gha(gha), DeviceTones(deviceTones), ToneFlags((deviceGated ? AT3PHIP_TONES_GATED : 0u) | (deviceShared ? AT3PHIP_TONES_SHARED : 0u))
+          Settings(settings), Gha(gha), DeviceTones(deviceTones), ToneFlags((deviceGated ? AT3PHIP_TONES_GATED : 0u) | (deviceShared ? AT3PHIP_TONES_SHARED : 0u)),
+          AllocFlag(adaptive ? AT3PHIP_ALLOC_ADAPTIVE : 0u)
     {
         if (deviceTones && gha) throw std::invalid_argument("TAt3PEncoder: deviceTones takes no host analyser");
         if (deviceGated && !deviceTones) throw std::invalid_argument("TAt3PEncoder: deviceGated needs deviceTones");
@@ -1059,8 +1063,8 @@ public:
         std::vector<uint8_t> frames((size_t)BatchFrames * AT3PHIP_FRAME_BYTES);
         for (int at = 0; at < nFrames; at += BatchFrames) {
             const int nf = std::min(BatchFrames, nFrames - at);
-            if (DeviceTones) Chk(at3phip_encode_frames_tonal_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), ToneFlags), "at3phip_encode_frames_tonal_short");
-            else Chk(at3phip_encode_frames_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), 0), "at3phip_encode_frames_short");
+            if (DeviceTones) Chk(at3phip_encode_frames_tonal_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), ToneFlags | AllocFlag), "at3phip_encode_frames_tonal_short");
+            else Chk(at3phip_encode_frames_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), AllocFlag), "at3phip_encode_frames_short");
             for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES);
             Calls += (size_t)nf;
             Flush();
@@ -1078,8 +1082,8 @@ public:
         }
         if (nf > 0) {
             std::vector<uint8_t> frames((size_t)nf * AT3PHIP_FRAME_BYTES);
-            if (DeviceTones) Chk(at3phip_encode_frames_tonal(Ctx, Pending.data(), nf, frames.data(), ToneFlags), "at3phip_encode_frames_tonal");
-            else Chk(at3phip_encode_frames(Ctx, Pending.data(), nf, frames.data(), 0), "at3phip_encode_frames");
+            if (DeviceTones) Chk(at3phip_encode_frames_tonal(Ctx, Pending.data(), nf, frames.data(), ToneFlags | AllocFlag), "at3phip_encode_frames_tonal");
+            else Chk(at3phip_encode_frames(Ctx, Pending.data(), nf, frames.data(), AllocFlag), "at3phip_encode_frames");
             Pending.clear();
             for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES);
         }
@@ -1141,7 +1145,7 @@ private:
         std::vector<float> specs(prevs.size());
         std::vector<uint8_t> frames((size_t)calls * AT3PHIP_FRAME_BYTES);
         Chk(at3phip_mdct(Ctx, prevs.data(), calls, nullptr, specs.data(), AT3PHIP_RESIDUAL_SCALE), "at3phip_mdct");
-        Chk(at3phip_write_frames_tonal(Ctx, specs.data(), calls, nullptr, blocks.data(), frames.data(), 0), "at3phip_write_frames_tonal");
+        Chk(at3phip_write_frames_tonal(Ctx, specs.data(), calls, nullptr, blocks.data(), frames.data(), AllocFlag), "at3phip_write_frames_tonal");
         for (int i = 0; i < calls; ++i)
             Out->WriteFrame(std::vector<char>(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES));
         Written += (size_t)calls;
@@ -1150,7 +1154,7 @@ private:
     {
         std::vector<float> specs(FrameFloats, 0.0f);
         std::vector<uint8_t> frame(AT3PHIP_FRAME_BYTES);
-        Chk(at3phip_write_frames(Ctx, specs.data(), 1, nullptr, frame.data(), 0), "at3phip_write_frames");
+        Chk(at3phip_write_frames(Ctx, specs.data(), 1, nullptr, frame.data(), AllocFlag), "at3phip_write_frames");
         return std::vector<char>(frame.begin(), frame.end());
     }
     TCompressedOutputPtr Out;
@@ -1165,6 +1169,7 @@ private:
     IAt3PGhaProcessor* const Gha;                 // not owned; null: the analysis finds nothing
     const bool DeviceTones;                       // the analysis runs on the GPU
     const uint32_t ToneFlags;                     // and with these flags (AT3PHIP_TONES_GATED, AT3PHIP_TONES_SHARED)
+    const uint32_t AllocFlag;                     // AT3PHIP_ALLOC_ADAPTIVE or 0, on every frame-writing call
     std::vector<float> PrevBuf, CurBuf, RawCur;   // [C][16][128] / [C][2048]: TChannelCtx's PrevBuf, CurBuf and RawCurBuf
     at3phip_tonal_block Delay{};                  // `delay`: the block the next call writes
 };

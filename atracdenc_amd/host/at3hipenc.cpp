@@ -7,7 +7,7 @@
 //             [--nogaincontrol] [--container oma|riff|raw] [--nostdout] [--batch blocks] [--device n]
 //   at3hipenc -e atrac1 -i in.wav -o out.{aea|raw|dat} [--bfuidxconst 1..8] [--notransient[=mask]]
 //             [--container aea|raw] [--nostdout] [--batch blocks] [--device n]
-//   at3hipenc -e atrac3plus -i in.wav -o out.{oma|at3|wav|raw|dat} [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout]
+//   at3hipenc -e atrac3plus -i in.wav -o out.{oma|at3|wav|raw|dat} [--adaptive] [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout]
 //             [--batch frames] [--device n]
 //   --resample (all three encoders): a WAV at 8 .. 192 kHz (at3hip_resample.h's list) is converted to 44.1 kHz on the GPU
 //             first; the container headers count ceil(N 44100 / rate) samples. A 44.1 kHz input is encoded as without it.
@@ -225,7 +225,7 @@ private:
 struct TOptions {
     std::string inFile, outFile, codec, container, rateArg;
     uint32_t bitrate = 0, bfuIdxConst = 0, winMask = 0;
-    bool tones = false, gate = false, share = false, noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false, resample = false, measure = false, peakGiven = false;
+    bool tones = false, gate = false, share = false, adaptive = false, noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false, resample = false, measure = false, peakGiven = false;
     int batch = 256, device = 0, rate = 0;
     TLevel level;
 };
@@ -660,7 +660,7 @@ struct TAtrac3PlusEncode {
     std::string CodecLines() const { return "ATRAC3Plus"; }
     TAt3PEncoder Encoder(TCompressedOutputPtr&& out, const TOptions& o)
     {   // --tones: the tone analysis of at3phip_encode_frames_tonal (--gate: with AT3PHIP_TONES_GATED, --share: with AT3PHIP_TONES_SHARED); the frame count is the plain encode's
-        return TAt3PEncoder(std::move(out), (int)Channels, o.batch > 64 ? 64 : o.batch, o.device, TAt3PSettings(), nullptr, o.tones, o.gate, o.share);
+        return TAt3PEncoder(std::move(out), (int)Channels, o.batch > 64 ? 64 : o.batch, o.device, TAt3PSettings(), nullptr, o.tones, o.gate, o.share, o.adaptive);
     }
     void Report(TAt3PEncoder&, const TOptions&) const {}
 };
@@ -706,7 +706,8 @@ static int usage()
                  "                 [--container oma|riff|raw] [--nostdout] [--batch blocks] [--device n]\n"
                  "       at3hipenc -e atrac1 -i in.wav -o out.aea [--bfuidxconst 1..8] [--notransient[=mask]]\n"
                  "                 [--container aea|raw] [--nostdout] [--batch blocks] [--device n]\n"
-                 "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
+                 "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--adaptive] [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
+                 "                 (--adaptive: word lengths chosen per frame on the GPU to fill the 2048-byte frame, instead of the fixed table)\n"
                  "                 (--tones: find sine waves on the GPU and write them as tonal blocks; --gate: with envelope points at\n"
                  "                  their onsets and offsets; --share: a band that both channels of a stereo input hold identically is\n"
                  "                  written once)\n"
@@ -742,6 +743,7 @@ int main(int argc, char** argv)
         else if (a == "--tones") o.tones = true;
         else if (a == "--gate") o.gate = true;
         else if (a == "--share") o.share = true;
+        else if (a == "--adaptive") o.adaptive = true;
         else if (a == "--nogaincontrol") o.noGain = true;
         else if (a == "--nostdout") o.noStdOut = true;
         else if (a == "--resample") o.resample = true;
@@ -774,7 +776,7 @@ int main(int argc, char** argv)
     }
     o.level.NoStdOut = o.noStdOut;
     if (o.measure) {   // prints the meter's result, writes nothing
-        if (o.decode || !o.codec.empty() || o.inFile.empty() || !o.outFile.empty() || o.level.On || o.level.Limit || o.peakGiven || o.rate) return usage();
+        if (o.decode || !o.codec.empty() || o.inFile.empty() || !o.outFile.empty() || o.level.On || o.level.Limit || o.peakGiven || o.rate || o.adaptive) return usage();
         try {
             const at3hip_loudness_result r = measure_input(o.inFile, o.resample, o.device, o.level.TruePeak);
             char line[256];
@@ -789,7 +791,7 @@ int main(int argc, char** argv)
         return 0;
     }
     if (o.decode) {
-        if (!o.codec.empty() || o.inFile.empty() || o.outFile.empty() || o.level.On || o.level.Limit || o.peakGiven || o.level.TruePeak) return usage();
+        if (!o.codec.empty() || o.inFile.empty() || o.outFile.empty() || o.level.On || o.level.Limit || o.peakGiven || o.level.TruePeak || o.adaptive) return usage();
         TAt3Input at3;
         const EInput kind = probe_input(o.inFile, at3);
         if (kind == EInput::REFUSED) return 1;
@@ -809,6 +811,7 @@ int main(int argc, char** argv)
     if (!o.level.On && (o.peakGiven || o.level.TruePeak || o.level.Limit)) return usage();   // --peak, --truepeak and --limit belong to --loudness (--truepeak also to --measure)
     if ((o.gate || o.share) && !o.tones) return usage();      // the gates and the sharing are the tone analysis'
     if (o.tones && o.codec != "atrac3plus") return usage();   // the tone analysis is ATRAC3plus'
+    if (o.adaptive && o.codec != "atrac3plus") return usage();   // and so are the adaptive word lengths
     if (o.codec == "atrac3plus") return encode<TAtrac3PlusEncode>(o);
     if (o.codec == "atrac1") return encode<TAtrac1Encode>(o);
     return encode<TAtrac3Encode>(o);

@@ -415,6 +415,8 @@ int at3hip_decoder_set_stream(at3hip_decoder* dec, void* hip_stream);
  *        and, added later under the same number, the look-ahead limiter on the meter's context (at3hip_loudness.h):
  *        at3hip_loudness_limit_start(), at3hip_loudness_limit(), at3hip_loudness_limit_s16(), at3hip_loudness_limit_flush(),
  *        at3hip_loudness_limit_stats(), at3hip_loudness_limit_delay() (detected by the symbol at3hip_loudness_limit_start)
+ *        and, added later under the same number, adaptive ATRAC3plus word lengths (at3phip.h, ADAPTIVE WORD LENGTHS): the flag
+ *        AT3PHIP_ALLOC_ADAPTIVE of the six frame-writing calls and at3phip_host_allocate, by whose symbol the flag is detected
  * A host layer compiled against this header checks at3hip_version() >= AT3HIP_VERSION before it relies on them
  * (atracdenc_amd/host/at3hip_host.hpp and the ctypes stub do). */
 #define AT3HIP_VERSION_MAJOR 1

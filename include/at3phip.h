@@ -312,6 +312,59 @@ int at3phip_host_tone_gates(const float* bands, int32_t n_frames, int32_t channe
  * without this symbol predates AT3PHIP_TONES_SHARED. */
 uint32_t at3phip_host_tone_flags(void);
 
+/* ADAPTIVE WORD LENGTHS (AT3PHIP_ALLOC_ADAPTIVE in `flags` of at3phip_write_frames, at3phip_write_frames_tonal,
+ * at3phip_encode_frames, at3phip_encode_frames_short, at3phip_encode_frames_tonal and at3phip_encode_frames_tonal_short, alone or
+ * with the flags each of them takes; without the flag no output changes by a byte). The reference gives every quant unit a fixed
+ * word length (TConfigure's allocTable: 7 bits for units 0-16, falling to 1 bit for unit 31) and searches only the number of
+ * units, so a 2048-byte frame codes the top of the spectrum with 1-4 bits whatever the signal is, a loud stereo frame loses units
+ * 28-31 and a quiet frame leaves thousands of bits unused. With the flag the word lengths are chosen per frame to fill it. The
+ * syntax is unchanged (TWordLenEncoder codes arbitrary word lengths as deltas) and the decoder below decodes the frames as they
+ * are. The reference has no such allocation: this is the project's definition, stated here and nowhere else, pinned bit for bit
+ * to the C restatement tests/host/at3p_alloc_cpu.c. A1 is the fixed writer's float code, every decision after it is integer
+ * arithmetic, so any float is accepted exactly as by the fixed writer. Frames do not depend on one another: any split of a stream
+ * into calls gives the same bytes. Per frame:
+ *  A1. Scale exactly as the fixed writer does (TScaler::Scale): sfi[ch][qu] in 0..63 and the scaled values. One step of sfi is a
+ *      factor 2^(1/3), so three steps are one mantissa bit.
+ *  A2. Cost table. For every channel, unit and word length w = 1..7 the mantissas are rint(v * inv_mant[w]) (the fixed writer's
+ *      operation; no energy-adaptive pass); tab[ch][qu][w] is the cheapest of the eight code tables w - 1 + 7 i, i = 0..7, the
+ *      first one on a tie, and B[ch][qu][w] that table's bits (EncodeQuSpectra's: codes, group flags, sign bits).
+ *  A3. Candidate allocation A(t, k) for t in -21..63 and k in 0..64. want(ch, qu; t) = clamp(floor((sfi - t) / 3), 0, 7). N is
+ *      1 plus the highest qu with want >= 1 in any channel, or 1 if there is none; an N of 29, 30 or 31 becomes 32 (the syntax
+ *      has no 29..31, which is why the reference steps from 32 to 28). Then the units below N are walked with qu ascending,
+ *      channel 0 before channel 1 within a qu: the first k units whose want at t - 1 exceeds their want at t take the t - 1
+ *      value. Then every unit below N that still has 0 takes 1: a word length of 0 is never written, and the decoder's rule about
+ *      it stands. A mono frame has one channel.
+ *  A4. Bits(A): everything in the frame but its three leading bits: the unit count (5) and the mute bit (1); the word-length
+ *      section exactly as TWordLenEncoder codes these word lengths - channel 0 in mode 3 as deltas to the previous unit
+ *      (2 + 2 + 2 + 2 + 3 bits, then a code per unit from the second on), channel 1 in mode 1 as deltas to channel 0 (2 + 2 + 2
+ *      bits, then a code per unit), each list under the table FindBestWlDeltaEncode picks (the first with the fewest bits) from
+ *      the range its OR-accumulated largest delta m allows (m >= 3: tables 2 and 3; m = 2: table 1; else table 0); the scale
+ *      factor indices (2 + 6 N per channel) and the code-table indices (1, then 4 + 3 N per channel); the sum of B over the coded
+ *      units; the power groups for N (4 bits each, per channel); and the tail, formed once as in the fixed writer: two bits in
+ *      stereo, window shapes, a gain-compensation bit per channel, tonal flag and block, noise flag, terminator. A fits when
+ *      Bits(A) <= 16381.
+ *  A5. Choice. t* is the smallest t in -21..63 whose A(t, 0) fits; t = 63 always fits (one unit per channel at word length 1 and
+ *      the tail, which at3phip_write_frames_tonal's bound on the tail covers). k* is the largest k in 0..64 whose A(t*, k) fits.
+ *      Both are defined by the full scan and not by bisection: code lengths are not provably monotone in the word length, and
+ *      the scan is the definition whether they are or not. A k beyond the number of units that can take the t - 1 value gives
+ *      the allocation of that number, so k* is reported as that number: 0 for a frame that fits at t = -21.
+ *  A6. The frame is A(t*, k*) in the fixed writer's layout, with tab[ch][qu][wl] as the unit's code-table index.
+ * Out of this definition: a word length of 0 inside the coded range, psychoacoustic weighting, frame sizes other than 2048 bytes.
+ * The tone analysis is unaffected by the flag; a stream may change it from call to call. Still ABI 1.6: a library that has the
+ * symbol at3phip_host_allocate takes the flag. */
+#define AT3PHIP_ALLOC_ADAPTIVE 128u
+
+/* Steps A3-A5 on a caller-supplied cost table, on the host (no GPU needed).
+ *   sfi        [channels][32] scale factor indices, each 0..63
+ *   bits       [channels][32][8] uint16: entry w = B[ch][qu][w]; entry 0 is not read
+ *   tail_bits  the tail's bits (A4), 0..16381
+ *   wl_out     [channels][32]: the word lengths of A(t*, k*), 0 at and above N
+ *   n_units, t, k   N, t*, k*
+ * Where no t fits (possible only with a table that no spectrum gives) t* = 63 and k* = 0 are reported. AT3HIP_EINVAL on a null
+ * pointer, a channel count other than 1 or 2, an sfi above 63 or tail_bits out of range. */
+int at3phip_host_allocate(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, uint8_t* wl_out, int32_t* n_units,
+                          int32_t* t, int32_t* k);
+
 /* With AT3HIP_ASYNC in `flags` at3phip_encode_frames only queues the call (pcm must stay valid, frames must not be read)
  * and the frame writer of one call runs beside the filter bank and transform of the next (its own stream, spectra
  * double-buffered); at3phip_sync waits for everything queued. Without the flag the call waits itself. A queued call records no
