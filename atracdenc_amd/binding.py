@@ -43,6 +43,8 @@ AT3HIP_DECODE_S16 = 8
 AT3HIP_RESAMPLE_OUT_S16 = 8                        # include/at3hip_resample.h: 16-bit output of the resampler
 AT1HIP_DECODE_S16 = 8                              # include/at1hip.h
 AT3PHIP_DECODE_S16 = 8                             # include/at3phip.h
+AT3PHIP_FRAME_BYTES = 2048                         # the default frame size
+AT3PHIP_MIN_FRAME_BYTES_MONO, AT3PHIP_MIN_FRAME_BYTES_STEREO = 176, 224   # the smallest admissible sizes (FRAME SIZE)
 AT3PHIP_DECODE_TONES = 16
 AT3PHIP_DECODER_TABLES_BYTES = 67328
 AT3PHIP_DECODER_TONE_TABLES_BYTES = 9504
@@ -192,6 +194,9 @@ PROTOTYPES = {
     "at3phip_host_tables": (_RC, [_VP, _SZ]), "at3phip_host_write_tables": (_RC, [_VP, _SZ]),
     "at3phip_host_tone_find_tables": (_RC, [_VP, _SZ]), "at3phip_host_tone_gates": (_RC, [_VP, _I32, _I32, _VP]),
     "at3phip_host_tone_flags": (_U32, []), "at3phip_host_allocate": (_RC, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "at3phip_host_allocate_sized": (_RC, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "at3phip_set_frame_bytes": (_RC, [_VP, _I32]), "at3phip_get_frame_bytes": (_RC, [_VP, _I32P]),
+    "at3phip_decoder_set_frame_bytes": (_RC, [_VP, _I32]), "at3phip_decoder_get_frame_bytes": (_RC, [_VP, _I32P]),
     # include/at3phip.h: the ATRAC3plus decoder
     "at3phip_decoder_create": (_RC, [_P(At3pDecoderConfig), _P(_VP)]), "at3phip_decoder_destroy": (None, [_VP]),
     "at3phip_decoder_last_error": (_STR, [_VP]), "at3phip_decoder_reset": (_RC, [_VP]), "at3phip_decoder_sync": (_RC, [_VP]),
@@ -682,14 +687,30 @@ class At3pHipDecoder(_Decoder):
 
     _CODEC, _PREFIX, _COUNTERS = "at3phip", "at3phip_decoder", At3pDecoderCounters
 
-    def __init__(self, n_streams=1, channels=2, max_frames=64, device_id=0, lib_path=None):
+    def __init__(self, n_streams=1, channels=2, max_frames=64, device_id=0, lib_path=None, frame_bytes=None):
+        """frame_bytes: the frames' size (at3phip_decoder_set_frame_bytes); None: 2048, and the setter is not called"""
         self.lib = load_library(lib_path)
         self.n_streams, self.channels, self.max_frames = int(n_streams), int(channels), int(max_frames)
         self._create(At3pDecoderConfig(self.channels, self.n_streams, self.max_frames, int(device_id)),
                      "bad configuration, or no usable MI355X / HIP runtime")
+        self._frame_bytes = AT3PHIP_FRAME_BYTES
+        if frame_bytes is not None:
+            self.set_frame_bytes(frame_bytes)
+
+    def set_frame_bytes(self, frame_bytes):
+        """at3phip_decoder_set_frame_bytes: waits for queued work; from then on frames are [n_streams, n_frames, frame_bytes]"""
+        self._call("set_frame_bytes", int(frame_bytes))
+        self._frame_bytes = int(frame_bytes)
+
+    @property
+    def frame_bytes(self):
+        """at3phip_decoder_get_frame_bytes"""
+        v = _I32()
+        self._call("get_frame_bytes", ctypes.byref(v))
+        return int(v.value)
 
     def _shapes(self):
-        return (2048,), (2048, self.channels)
+        return (self._frame_bytes,), (2048, self.channels)
 
     def _tones_flag(self, tones):
         """AT3PHIP_DECODE_TONES for `tones`; a library has tonal-block decoding if it has the tone tables"""
@@ -699,12 +720,12 @@ class At3pHipDecoder(_Decoder):
         return AT3PHIP_DECODE_TONES
 
     def decode(self, frames, s16=False, tones=False):
-        """frames uint8 [n_streams, n_frames, 2048] (host) -> float32 (int16 with s16) [n_streams, n_frames, 2048, channels].
+        """frames uint8 [n_streams, n_frames, frame_bytes] (host) -> float32 (int16 with s16) [n_streams, n_frames, 2048, channels].
         tones: decode tonal blocks (AT3PHIP_DECODE_TONES) instead of rejecting their frames."""
         return self._decode(frames, s16, self._tones_flag(tones))
 
     def decode_device(self, frames, out, asynchronous=False, ordered=True, tones=False):
-        """Torch tensors on this decoder's device: frames uint8 [n_streams, n, 2048] -> out float32 / int16 (s16 output)
+        """Torch tensors on this decoder's device: frames uint8 [n_streams, n, frame_bytes] -> out float32 / int16 (s16 output)
         [n_streams, n, 2048, channels]. Ordered behind torch's current stream by default, as At1HipDecoder.decode_device.
         tones as in decode."""
         self._decode_device(frames, out, asynchronous, ordered, self._tones_flag(tones))
@@ -816,16 +837,22 @@ def _alloc_flag(adaptive):
     return AT3PHIP_ALLOC_ADAPTIVE if adaptive else 0
 
 
-def at3p_host_allocate(sfi, bits, tail_bits, lib_path=None):
+def at3p_host_allocate(sfi, bits, tail_bits, lib_path=None, frame_bytes=None):
     """at3phip_host_allocate (no GPU): steps A3-A5 of include/at3phip.h, ADAPTIVE WORD LENGTHS, on a cost table: sfi uint8 [C, 32],
-    bits uint16 [C, 32, 8] (entry w = the unit's bits at word length w) -> (wl uint8 [C, 32], N, t*, k*)."""
+    bits uint16 [C, 32, 8] (entry w = the unit's bits at word length w) -> (wl uint8 [C, 32], N, t*, k*). frame_bytes: the
+    budget's frame size through at3phip_host_allocate_sized; None: the 2048-byte entry point."""
     sfi, bits = np.ascontiguousarray(sfi, np.uint8), np.ascontiguousarray(bits, np.uint16)
     C = sfi.shape[0]
     assert sfi.shape == (C, 32) and bits.shape == (C, 32, 8), (sfi.shape, bits.shape)
     wl, out = np.zeros((C, 32), np.uint8), np.zeros(3, np.int32)
-    rc = _need(load_library(lib_path), "at3phip_host_allocate")(_vp(sfi), _vp(bits), C, int(tail_bits), _vp(wl), _vp(out[0:1]), _vp(out[1:2]), _vp(out[2:3]))
+    outs = (_vp(wl), _vp(out[0:1]), _vp(out[1:2]), _vp(out[2:3]))
+    if frame_bytes is None:
+        rc, name = _need(load_library(lib_path), "at3phip_host_allocate")(_vp(sfi), _vp(bits), C, int(tail_bits), *outs), "at3phip_host_allocate"
+    else:
+        name = "at3phip_host_allocate_sized"
+        rc = _need(load_library(lib_path), name)(_vp(sfi), _vp(bits), C, int(tail_bits), int(frame_bytes), *outs)
     if rc != 0:
-        raise At3HipError(f"at3phip_host_allocate failed ({rc})")
+        raise At3HipError(f"{name} failed ({rc})")
     return wl, int(out[0]), int(out[1]), int(out[2])
 
 
@@ -834,10 +861,27 @@ class At3pHip(_Context):
 
     _PREFIX = "at3phip"
 
-    def __init__(self, n_streams=1, max_frames=32, channels=2, device_id=0, lib_path=None):
+    def __init__(self, n_streams=1, max_frames=32, channels=2, device_id=0, lib_path=None, frame_bytes=None):
+        """frame_bytes: the size of the frames the context writes (at3phip_set_frame_bytes; other than 2048 only with adaptive=True);
+        None: 2048, and the setter is not called"""
         self.lib = load_library(lib_path)
         self.channels, self.n_streams = int(channels), int(n_streams)
         self._create(At3pConfig(int(channels), int(n_streams), int(max_frames), int(device_id)), "no usable MI355X / HIP runtime?")
+        self._frame_bytes = AT3PHIP_FRAME_BYTES
+        if frame_bytes is not None:
+            self.set_frame_bytes(frame_bytes)
+
+    def set_frame_bytes(self, frame_bytes):
+        """at3phip_set_frame_bytes: waits for queued work; from then on every frame-writing call gives [S, F, frame_bytes]"""
+        self._call("set_frame_bytes", int(frame_bytes))
+        self._frame_bytes = int(frame_bytes)
+
+    @property
+    def frame_bytes(self):
+        """at3phip_get_frame_bytes"""
+        v = _I32()
+        self._call("get_frame_bytes", ctypes.byref(v))
+        return int(v.value)
 
     # one raw method per entry point: pointers (None: absent), a frame count and the function's flags
     def pqf_ptr(self, pcm_ptr, n_frames, bands_ptr, flags):
@@ -921,12 +965,12 @@ class At3pHip(_Context):
     def write_frames(self, specs, win_flags=None, tonal=None, adaptive=False):
         """ScaleFrame + WriteFrame: specs [S, F, C, 2048], win_flags uint16 [S, F, C] or None, tonal records of
         AT3P_TONAL_BLOCK_DTYPE [S, F] (pack_tonal_blocks) or None: no frame carries a tonal block (at3phip_write_frames)
-        -> frames uint8 [S, F, 2048]. adaptive: AT3PHIP_ALLOC_ADAPTIVE, word lengths chosen per frame to fill it."""
+        -> frames uint8 [S, F, frame_bytes]. adaptive: AT3PHIP_ALLOC_ADAPTIVE, word lengths chosen per frame to fill it."""
         specs = np.ascontiguousarray(specs, dtype=np.float32)
         assert specs.ndim == 4 and specs.shape[0] == self.n_streams and specs.shape[2:] == (self.channels, 2048), specs.shape
         nf = specs.shape[1]
         fl, flp = self._flags(win_flags, nf)
-        out = np.zeros((self.n_streams, nf, 2048), np.uint8)
+        out = np.zeros((self.n_streams, nf, self._frame_bytes), np.uint8)
         if tonal is None:
             self.write_frames_ptr(specs.ctypes.data, nf, flp, out.ctypes.data, _alloc_flag(adaptive))
         else:
@@ -939,12 +983,12 @@ class At3pHip(_Context):
         pcm = np.ascontiguousarray(pcm, dtype=dtype)
         assert pcm.ndim == 4 and pcm.shape[0] == self.n_streams and pcm.shape[2:] == (2048, self.channels), pcm.shape
         nf = pcm.shape[1]
-        out = np.zeros((self.n_streams, nf, 2048), np.uint8)
+        out = np.zeros((self.n_streams, nf, self._frame_bytes), np.uint8)
         raw(pcm.ctypes.data, nf, out.ctypes.data, flags)
         return out
 
     def encode_frames(self, pcm, adaptive=False):
-        """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, 2048] (tonal analysis finding nothing; no look-ahead delay).
+        """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, frame_bytes] (tonal analysis finding nothing; no look-ahead delay).
         adaptive (here and in the encode calls below): AT3PHIP_ALLOC_ADAPTIVE, word lengths chosen per frame to fill it."""
         return self._encode_frames_host(pcm, np.float32, self.encode_frames_ptr, _alloc_flag(adaptive))
 

@@ -15,35 +15,49 @@ namespace {
 }
 
 // wp: the fixed writer's parameters as at3phip.hip's launch_write fills them; wp.tonal null: the writer without records. The
-// word-length code tables travel in the kernel's arguments: nothing is allocated or uploaded for the adaptive path.
-__attribute__((visibility("default"))) void launch_write_adaptive(const WriteParamsTonal& wp, hipStream_t on)
+// word-length code tables and the frame size travel in the kernel's arguments: nothing is allocated or uploaded for the adaptive
+// path. wp.out is [n_items][frame_bytes].
+__attribute__((visibility("default"))) void launch_write_adaptive(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on)
 {
     if (wp.tonal) {
         AdaptiveParams<WriteParamsTonal> ap;
         static_cast<WriteParamsTonal&>(ap) = wp;
         memcpy(ap.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(ap.tone_vlc));
         memcpy(ap.wl_vlc, AT3P_WL_VLC, sizeof(ap.wl_vlc));
+        ap.frame_bytes = frame_bytes;
         hipLaunchKernelGGL(k_at3p_write_adaptive_tonal, dim3((unsigned)wp.n_items), dim3(256), 0, on, ap);
     } else {
         AdaptiveParams<WriteParams> ap;
         static_cast<WriteParams&>(ap) = static_cast<const WriteParams&>(wp);
         memcpy(ap.wl_vlc, AT3P_WL_VLC, sizeof(ap.wl_vlc));
+        ap.frame_bytes = frame_bytes;
         hipLaunchKernelGGL(k_at3p_write_adaptive, dim3((unsigned)wp.n_items), dim3(256), 0, on, ap);
     }
 }
 
 }  // namespace at3p
 
-extern "C" int at3phip_host_allocate(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, uint8_t* wl_out, int32_t* n_units,
-                                     int32_t* t, int32_t* k)
+extern "C" int at3phip_host_allocate_sized(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, int32_t frame_bytes,
+                                           uint8_t* wl_out, int32_t* n_units, int32_t* t, int32_t* k)
 {
-    if (!sfi || !bits || !wl_out || !n_units || !t || !k || channels < 1 || channels > 2 || tail_bits < 0 || tail_bits > at3p::kSizeBits) return AT3HIP_EINVAL;
+    if (!sfi || !bits || !wl_out || !n_units || !t || !k || channels < 1 || channels > 2) return AT3HIP_EINVAL;
+    if (frame_bytes % 8 || frame_bytes > AT3PHIP_FRAME_BYTES ||
+        frame_bytes < (channels == 2 ? AT3PHIP_MIN_FRAME_BYTES_STEREO : AT3PHIP_MIN_FRAME_BYTES_MONO))
+        return AT3HIP_EINVAL;
+    const int size_bits = 8 * frame_bytes - 3;
+    if (tail_bits < 0 || tail_bits > size_bits) return AT3HIP_EINVAL;
     for (int i = 0; i < 32 * channels; ++i)
         if (sfi[i] > 63) return AT3HIP_EINVAL;
     int n = 0, ts = 0, ks = 0;
-    at3p::host_allocate(sfi, bits, channels, tail_bits, wl_out, &n, &ts, &ks);
+    at3p::host_allocate(sfi, bits, channels, tail_bits, size_bits, wl_out, &n, &ts, &ks);
     *n_units = n;
     *t = ts;
     *k = ks;
     return AT3HIP_OK;
+}
+
+extern "C" int at3phip_host_allocate(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, uint8_t* wl_out, int32_t* n_units,
+                                     int32_t* t, int32_t* k)
+{
+    return at3phip_host_allocate_sized(sfi, bits, channels, tail_bits, AT3PHIP_FRAME_BYTES, wl_out, n_units, t, k);
 }

@@ -24,8 +24,9 @@ __host__ __device__ inline int alloc_wl_range(int max_delta) { return max_delta 
 
 // ---- host: steps A3-A5 on a cost table ---------------------------------------------------------------------------------
 // sfi [channels][32], bits [channels][32][8] (entry w = the unit's bits at word length w, entry 0 unused) -> wl [channels][32]
-// (0 at and above N), N, t*, k*; returns Bits(A(t*, k*)).
-inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels, int tail_bits, uint8_t* wl_out, int* n_units, int* t_out, int* k_out)
+// (0 at and above N), N, t*, k*; returns Bits(A(t*, k*)). size_bits: the budget of A4, 8 * frame_bytes - 3.
+inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels, int tail_bits, int size_bits, uint8_t* wl_out, int* n_units, int* t_out,
+                         int* k_out)
 {
     int wl[2][32];
     int N = 1, took = 0;
@@ -75,12 +76,12 @@ inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels,
     int ts = kAllocTMax + 1, ks = 0;
     for (int t = kAllocTMax; t >= kAllocTMin; --t) {   // every t: the smallest that fits
         form(t, 0);
-        if (count() <= kSizeBits) ts = t;
+        if (count() <= size_bits) ts = t;
     }
     if (ts > kAllocTMax) ts = kAllocTMax;              // nothing fits (a caller's table only)
     for (int k = 0; k <= kAllocKMax; ++k) {            // every k: the largest that fits
         form(ts, k);
-        if (count() <= kSizeBits) ks = k;
+        if (count() <= size_bits) ks = k;
     }
     form(ts, ks);
     for (int ch = 0; ch < channels; ++ch)
@@ -97,6 +98,7 @@ inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels,
 template <typename P>
 struct AdaptiveParams : P {
     uint16_t wl_vlc[4][8];
+    int32_t frame_bytes;   // a multiple of 8 in AT3PHIP_MIN_FRAME_BYTES_* .. 2048: P::out is [items][frame_bytes]
 };
 
 // TUnit::GetOrCompute's pricing of one 16-line chunk under one code table, as k_at3p_write_with has it: the symbols are formed
@@ -231,14 +233,17 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nch = p.nch;
     const size_t item = blockIdx.x;
+    // The frame's size: its budget (A4), its bits and its 32-bit words. s_out holds the largest frame; the words past this frame's
+    // are neither zeroed, written nor stored.
+    const int size_bits = 8 * p.frame_bytes - 3, limit_bits = 8 * p.frame_bytes, n_words = p.frame_bytes >> 2;
     // The thread's chunk in stream order: every thread walks all seven word lengths, so nothing is gained by dealing the
     // threads by word length as the fixed writer does.
     const int ch = tid >> 7, c = tid & 127;
     const bool active = ch < nch;
     const int qu = at3p_qu_of_line(16 * c);
 
-    s_out[tid] = 0u;
-    s_out[256 + tid] = 0u;
+    if (tid < n_words) s_out[tid] = 0u;
+    if (256 + tid < n_words) s_out[256 + tid] = 0u;
 #pragma unroll
     for (int i = 0; i < 14; ++i) (&s_qbits[0][0][0][0])[tid + 256 * i] = 0u;
     constexpr int kLenWords = (kLenEntries + 7) / 8, kLenIt = (kLenWords + 255) / 256;
@@ -352,7 +357,7 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
         int tfit = kAllocTMax + 1;
         for (int t = kAllocTMax - wave; t >= kAllocTMin; t -= 4) {   // descending: the last one that fits is the smallest
             const AllocEval e = alloc_eval(t, 0, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
-            if (e.total <= kSizeBits) tfit = t;
+            if (e.total <= size_bits) tfit = t;
         }
         if (lane == 0) s_tfit[wave] = tfit;
     }
@@ -364,7 +369,7 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
         int kfit = 0;
         for (int k = wave; k <= kAllocKMax; k += 4) {
             const AllocEval e = alloc_eval(t_star, k, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
-            if (e.total <= kSizeBits) kfit = k;
+            if (e.total <= size_bits) kfit = k;
         }
         if (lane == 0) s_kfit[wave] = kfit;
     }
@@ -381,17 +386,17 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
         const int pos1 = 20 + e.sum0;   // channel 1's list
         if (e.len) {
             const int idx = (lane & 1) ? e.idx1 : e.idx0;
-            frame_put(s_out, ((lane & 1) ? pos1 + 6 : 20) + before, s_wlv[idx * 8 + e.delta] & 0xfffu, e.len);
+            frame_put(s_out, ((lane & 1) ? pos1 + 6 : 20) + before, s_wlv[idx * 8 + e.delta] & 0xfffu, e.len, limit_bits);
         }
         if (lane == 0) {
-            frame_put(s_out, 1, (uint32_t)nch - 1u, 2);
-            frame_put(s_out, 3, (uint32_t)e.N - 1u, 5);     // (then the mute bit, 0)
-            frame_put(s_out, 9, 3u, 2);                     // channel 0: mode 3, no flags, no position
-            frame_put(s_out, 15, (uint32_t)e.idx0, 2);
-            frame_put(s_out, 17, (uint32_t)e.wl, 3);
+            frame_put(s_out, 1, (uint32_t)nch - 1u, 2, limit_bits);
+            frame_put(s_out, 3, (uint32_t)e.N - 1u, 5, limit_bits);     // (then the mute bit, 0)
+            frame_put(s_out, 9, 3u, 2, limit_bits);                     // channel 0: mode 3, no flags, no position
+            frame_put(s_out, 15, (uint32_t)e.idx0, 2, limit_bits);
+            frame_put(s_out, 17, (uint32_t)e.wl, 3, limit_bits);
             if (nch == 2) {
-                frame_put(s_out, pos1, 1u, 2);              // channel 1: mode 1, no flags
-                frame_put(s_out, pos1 + 4, (uint32_t)e.idx1, 2);
+                frame_put(s_out, pos1, 1u, 2, limit_bits);              // channel 1: mode 1, no flags
+                frame_put(s_out, pos1 + 4, (uint32_t)e.idx1, 2, limit_bits);
             }
             s_n = e.N;
             s_pos_sf = pos1 + (nch == 2 ? 6 + e.sum1 : 0);
@@ -406,11 +411,11 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     if (tid < 64) {
         const int k = tid >> 5, q = tid & 31;
         if (k < nch && q < N) {
-            frame_put(s_out, pos_sf + k * (2 + 6 * N) + 2 + 6 * q, s_sfi[k][q], 6);
-            frame_put(s_out, pos_ct + 1 + k * (4 + 3 * N) + 4 + 3 * q, s_tabw[k][q][s_wl[k][q]], 3);
+            frame_put(s_out, pos_sf + k * (2 + 6 * N) + 2 + 6 * q, s_sfi[k][q], 6, limit_bits);
+            frame_put(s_out, pos_ct + 1 + k * (4 + 3 * N) + 4 + 3 * q, s_tabw[k][q][s_wl[k][q]], 3, limit_bits);
         }
     }
-    if (tid == 64) frame_put(s_out, pos_ct, 1u, 1);   // "use full table"
+    if (tid == 64) frame_put(s_out, pos_ct, 1u, 1, limit_bits);   // "use full table"
     const bool coded = active && qu < N;
     const int wl = coded ? s_wl[ch][qu] : 1;
     const uint32_t d = s_info[wl - 1 + 7 * s_tabw[active ? ch : 0][qu][wl]];
@@ -431,44 +436,45 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     const int ch_base[2] = {pos_data, pos_data + ch_total[0] + pw};
     if (coded) {
         BitRun run;
-        run.start(s_out, ch_base[ch] + (int)s_off[tid]);
+        run.start(s_out, ch_base[ch] + (int)s_off[tid], n_words);
         const int num_coeffs = (int)((d >> 20) & 15u);
         if (num_coeffs == 1) emit_chunk<1>(W, qv, d, &run);
         else if (num_coeffs == 2) emit_chunk<2>(W, qv, d, &run);
         else emit_chunk<4>(W, qv, d, &run);
         run.finish();
     }
-    if (c == 0 && active) frame_put(s_out, ch_base[ch] + ch_total[ch], (1u << pw) - 1u, pw);   // (15, 4) per power group
+    if (c == 0 && active) frame_put(s_out, ch_base[ch] + ch_total[ch], (1u << pw) - 1u, pw, limit_bits);   // (15, 4) per power group
     if (kTonal ? tid == 50 : tid == 65) {
         int pos = ch_base[nch - 1] + ch_total[nch - 1] + pw;
         if (nch == 2) pos += 2;   // swap_channels, negate_coeffs
         for (int k = 0; k < nch; ++k) {
             if (win_bits[k] == 2) {
-                frame_put(s_out, pos, 2u, 2);
+                frame_put(s_out, pos, 2u, 2, limit_bits);
             } else if (win_bits[k] == 18) {
-                frame_put(s_out, pos, 3u, 2);
-                for (int i = 0; i < 16; ++i) frame_put(s_out, pos + 2 + i, (fl[k] >> i) & 1u, 1);
+                frame_put(s_out, pos, 3u, 2, limit_bits);
+                for (int i = 0; i < 16; ++i) frame_put(s_out, pos + 2 + i, (fl[k] >> i) & 1u, 1, limit_bits);
             }
             pos += win_bits[k];
         }
         if constexpr (kTonal) {
             pos += nch;           // gain compensation per channel
-            if (plan.bits) frame_put(s_out, pos, 1u, 1);
+            if (plan.bits) frame_put(s_out, pos, 1u, 1, limit_bits);
             pos += 1 + plan.bits + 1;   // the tonal flag and block, no noise info
         } else {
             pos += nch + 1 + 1;   // gain compensation per channel, no tonal block, no noise info
         }
-        frame_put(s_out, pos, 3u, 2);
+        frame_put(s_out, pos, 3u, 2, limit_bits);
     }
     if constexpr (kTonal) {
         if (wave == 0)
             tonal_emit(s_out, ch_base[nch - 1] + ch_total[nch - 1] + pw + (nch == 2 ? 2 : 0) + win_bits[0] + win_bits[1] + nch + 1, s_rec, nch,
-                       lane, p.tone_vlc, plan);
+                       lane, p.tone_vlc, plan, limit_bits);
     }
     __syncthreads();
-    uint32_t* dst = reinterpret_cast<uint32_t*>(p.out + item * kFrameBytes);
-    dst[tid] = __builtin_bswap32(s_out[tid]);
-    dst[256 + tid] = __builtin_bswap32(s_out[256 + tid]);
+    // (word stores: frame_bytes is a multiple of 8, so every frame of a 4-byte aligned [items][frame_bytes] buffer is word-aligned)
+    uint32_t* dst = reinterpret_cast<uint32_t*>(p.out + item * (size_t)p.frame_bytes);
+    if (tid < n_words) dst[tid] = __builtin_bswap32(s_out[tid]);
+    if (256 + tid < n_words) dst[256 + tid] = __builtin_bswap32(s_out[256 + tid]);
 }
 // the two instantiations under the names they are launched by
 constexpr auto k_at3p_write_adaptive = k_at3p_write_adaptive_with<WriteParams>;

@@ -79,7 +79,7 @@ __device__ __forceinline__ size_t decp_rec(int slot, int s, int ch, int S, int C
 
 struct DecUnpackParams {
     const DecTables* T;
-    const uint8_t* frames;        // [S][F][2048]
+    const uint8_t* frames;        // [S][F][frame_bytes]
     int32_t n_frames, n_streams, nch;
     float* raw;                   // records of [16][256] floats: the TMIDCT<256> output per subband
     uint16_t* flags;              // records: steep-window bits
@@ -87,9 +87,10 @@ struct DecUnpackParams {
     TonalRec* tonal;              // [F + 3][S]: record f + 3 = frame f
     const uint16_t* tone_vlc;     // AT3P_TONE_BANDS_VLC
     int32_t tones;                // AT3PHIP_DECODE_TONES
+    int32_t frame_bytes;          // k_at3pd_unpack_sized only: a multiple of 8 up to 2048 (at3phip_decoder_set_frame_bytes)
 };
 
-using at3::MsbReader;   // over the frame staged in LDS as big-endian words; constructed with the frame's 2048 * 8 bits
+using at3::MsbReader;   // over the frame staged in LDS as big-endian words; constructed with the frame's 8 * frame_bytes bits
 
 // One symbol of spectra table t through the two-level look-up (DecTables::lut1, lut2) over the next 12 bits.
 __device__ __forceinline__ int decp_spec_vlc(MsbReader& b, const DecTables* T, int t, int& invalid)
@@ -354,7 +355,10 @@ __device__ __forceinline__ int decp_parse(MsbReader& b, const DecTables* T, int 
 
 constexpr int kDecUnpackThreads = 64;   // one wavefront per frame: the parse is one lane, so frames in flight per CU count
 
-__global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack(DecUnpackParams p)
+// kSized: the frame size is the parameter block's; otherwise it is 2048 and every limit folds to the constant it was before
+// frames had a size (the parse is one lane's serial code, and a limit held in a register instead of an immediate costs it 2 %).
+template <bool kSized>
+__global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack_with(DecUnpackParams p)
 {
     constexpr int NT = kDecUnpackThreads;
     __shared__ uint32_t s_w[512 + 2];                              // the frame, big-endian words, two zero words behind
@@ -367,10 +371,12 @@ __global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack(DecUnpackPar
 
     const DecTables* T = p.T;
     const int f = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, C = p.nch;
-    const uint8_t* frame = p.frames + ((size_t)s * p.n_frames + f) * 2048;
+    // s_w holds the largest frame; the words behind this frame's are zero and no read reaches them (the reader's limit)
+    const int frame_bytes = kSized ? p.frame_bytes : 2048, n_words = frame_bytes >> 2;
+    const uint8_t* frame = p.frames + ((size_t)s * p.n_frames + f) * (size_t)frame_bytes;
     for (int i = tid; i < 512 + 2; i += NT) {   // byte loads: a caller's device buffer need not be word-aligned
         uint32_t w = 0;
-        if (i < 512)
+        if (i < n_words)
             for (int k = 0; k < 4; ++k) w = (w << 8) | frame[4 * i + k];
         s_w[i] = w;
     }
@@ -379,7 +385,7 @@ __global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack(DecUnpackPar
     for (int i = tid; i < kTonalWords; i += NT) ((uint32_t*)&s_tone)[i] = 0u;
     __syncthreads();
     if (tid == 0) {
-        MsbReader b(s_w, 2048 * 8);
+        MsbReader b(s_w, 8 * frame_bytes);
         const int why = decp_parse(b, T, C, &s_spec[0][0], s_wl, s_sf, s_tab, s_win, p.tone_vlc, p.tones ? &s_tone : nullptr);
         s_reason = why;
         if (why) atomicAdd(&p.rejected[why - 1], 1ull);
@@ -413,6 +419,10 @@ __global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack(DecUnpackPar
         at3::midct_unfold<64>(n, r1, i1, [&](int x, float v) { o[x] = v; });
     }
 }
+
+// the two instantiations under the names they are launched by
+constexpr auto k_at3pd_unpack = k_at3pd_unpack_with<false>;
+constexpr auto k_at3pd_unpack_sized = k_at3pd_unpack_with<true>;
 
 struct DecSynthParams {
     const DecTables* T;

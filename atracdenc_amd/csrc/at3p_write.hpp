@@ -164,9 +164,11 @@ struct WriteParamsTonal : WriteParams {
     static constexpr bool kTonal = true;
 };
 
-__device__ __forceinline__ void frame_put(uint32_t* words, int pos, uint32_t val, int n)   // n in 1..23
+// limit_bits: the frame's size in bits. The fixed writers leave it at the constant, the adaptive ones (at3p_alloc.hpp) pass the
+// context's frame size.
+__device__ __forceinline__ void frame_put(uint32_t* words, int pos, uint32_t val, int n, int limit_bits = kFrameBytes * 8)   // n in 1..23
 {
-    if (pos + n > kFrameBytes * 8) return;
+    if (pos + n > limit_bits) return;
     val &= (1u << n) - 1u;
     at3::or_bits_msb(words, pos, val, n);
 }
@@ -175,15 +177,15 @@ __device__ __forceinline__ void frame_put(uint32_t* words, int pos, uint32_t val
 struct BitRun {
     uint32_t* words;
     uint64_t acc;
-    int cur, fill;
-    __device__ __forceinline__ void start(uint32_t* w, int pos) { words = w; acc = 0; cur = pos >> 5; fill = pos & 31; }
+    int cur, fill, limit_words;   // limit_words: the frame's size in words (see frame_put)
+    __device__ __forceinline__ void start(uint32_t* w, int pos, int lim = kFrameBytes / 4) { words = w; acc = 0; cur = pos >> 5; fill = pos & 31; limit_words = lim; }
     __device__ __forceinline__ void add(uint32_t v, int n)   // n <= 12
     {
         if (n == 0) return;
         acc |= (uint64_t)(v & ((1u << n) - 1u)) << (64 - fill - n);
         fill += n;
         if (fill >= 32) {
-            if (cur < kFrameBytes / 4) atomicOr(&words[cur], (uint32_t)(acc >> 32));
+            if (cur < limit_words) atomicOr(&words[cur], (uint32_t)(acc >> 32));
             acc <<= 32;
             fill -= 32;
             ++cur;
@@ -191,7 +193,7 @@ struct BitRun {
     }
     __device__ __forceinline__ void finish()
     {
-        if (fill > 0 && cur < kFrameBytes / 4) atomicOr(&words[cur], (uint32_t)(acc >> 32));
+        if (fill > 0 && cur < limit_words) atomicOr(&words[cur], (uint32_t)(acc >> 32));
     }
 };
 
@@ -378,7 +380,8 @@ __device__ __forceinline__ void tonal_price(const uint32_t* rec, int nch, int la
 
 // The block at bit `at` of the frame (behind the tonal flag). Mode fields, channel 1's envelope-copy and delta flags and the
 // invert-phase flag are zero bits: the frame starts zeroed.
-__device__ __forceinline__ void tonal_emit(uint32_t* out, int at, const uint32_t* rec, int nch, int lane, const uint16_t* tone_vlc, const TonalPlan& pl)
+__device__ __forceinline__ void tonal_emit(uint32_t* out, int at, const uint32_t* rec, int nch, int lane, const uint16_t* tone_vlc, const TonalPlan& pl,
+                                           int limit_bits = kFrameBytes * 8)
 {
     if (pl.bits == 0) return;
     const uint32_t w0 = rec[0];
@@ -387,39 +390,39 @@ __device__ __forceinline__ void tonal_emit(uint32_t* out, int at, const uint32_t
         const uint32_t bw = rec[1 + lane];
         if (pl.env_pos >= 0) {
             const int sp = (int)((bw >> 8) & 0xffu), ep = (int)((bw >> 16) & 0xffu);
-            if (sp) frame_put(out, at + pl.env_pos, 0x20u | (uint32_t)(sp - 1), 6);
-            if (ep) frame_put(out, at + pl.env_pos + (sp ? 6 : 1), 0x20u | (uint32_t)(ep - 1), 6);
+            if (sp) frame_put(out, at + pl.env_pos, 0x20u | (uint32_t)(sp - 1), 6, limit_bits);
+            if (ep) frame_put(out, at + pl.env_pos + (sp ? 6 : 1), 0x20u | (uint32_t)(ep - 1), 6, limit_bits);
             const uint32_t nw = (bw & 0xffu) > (uint32_t)kTonalMaxBandWaves ? (uint32_t)kTonalMaxBandWaves : (bw & 0xffu);
-            frame_put(out, at + pl.cnt_pos, nw, 4);
+            frame_put(out, at + pl.cnt_pos, nw, 4, limit_bits);
         }
-        if (pl.ord_pos >= 0) frame_put(out, at + pl.ord_pos, (uint32_t)pl.desc, 1);
+        if (pl.ord_pos >= 0) frame_put(out, at + pl.ord_pos, (uint32_t)pl.desc, 1, limit_bits);
     }
     if (pl.f_pos >= 0) {
         const uint32_t w = rec[33 + lane];
-        frame_put(out, at + pl.f_pos, pl.f_code, pl.f_bits);
-        frame_put(out, at + pl.a_pos, (w >> 10) & 63u, 6);
-        frame_put(out, at + pl.p_pos, (w >> 16) & 31u, 5);
+        frame_put(out, at + pl.f_pos, pl.f_code, pl.f_bits, limit_bits);
+        frame_put(out, at + pl.a_pos, (w >> 10) & 63u, 6, limit_bits);
+        frame_put(out, at + pl.p_pos, (w >> 16) & 31u, 5, limit_bits);
     }
     if (lane == 48) {   // amplitude mode 1, NumToneBands
         const uint32_t e = tone_vlc[nb - 1];
-        frame_put(out, at, 1u, 1);
-        frame_put(out, at + 1, e & 0xfffu, (int)(e >> 12));
+        frame_put(out, at, 1u, 1, limit_bits);
+        frame_put(out, at + 1, e & 0xfffu, (int)(e >> 12), limit_bits);
     }
     if (lane == 49 && nch == 2) {   // WriteSubbandFlags (:487-507) for the sharing flags and the leader flag
         const uint32_t share = (w0 >> 16) & ((1u << nb) - 1u);
         const int n_share = __builtin_popcount(share);
         int pos = at + pl.pos_share;
         if (n_share == nb) {
-            frame_put(out, pos, 2u, 2);
+            frame_put(out, pos, 2u, 2, limit_bits);
             pos += 2;
         } else if (n_share) {
-            frame_put(out, pos, 3u, 2);
-            for (int i = 0; i < nb; ++i) frame_put(out, pos + 2 + i, (share >> i) & 1u, 1);
+            frame_put(out, pos, 3u, 2, limit_bits);
+            for (int i = 0; i < nb; ++i) frame_put(out, pos + 2 + i, (share >> i) & 1u, 1, limit_bits);
             pos += 2 + nb;
         } else {
             pos += 1;
         }
-        if ((w0 >> 8) & 0xffu) frame_put(out, pos, 2u, 2);
+        if ((w0 >> 8) & 0xffu) frame_put(out, pos, 2u, 2, limit_bits);
     }
 }
 

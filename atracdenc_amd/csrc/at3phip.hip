@@ -60,6 +60,7 @@ struct at3phip_ctx : at3host::EngineBase {   // (no at3phip_set_stream: stream =
     long long enc_calls = 0;
     bool ev_from_encode = false;   // the timing events were last recorded by at3phip_encode_frames (at3phip_sync may read all of them)
     float pqf_ms = 0.0f, mdct_ms = 0.0f, write_ms = 0.0f;
+    int32_t frame_bytes = kFrameBytes;   // at3phip_set_frame_bytes: `frames` of every frame-writing call is [S][F][frame_bytes]; d_frames is sized for 2048
 };
 
 namespace at3p {
@@ -71,7 +72,7 @@ constexpr auto k_at3p_write_tonal = k_at3p_write_with<WriteParamsTonal>;
 // The adaptive writer's launch (wp.tonal null: without records). Its kernels are a translation unit of their own, at3p_alloc.hip,
 // so that this one's device code stays instruction for instruction what it was; weak, because the stand-alone host programs
 // that link this file without that one (tests/test_owned_alloc_cpu.py) must still link: there the flag is an error.
-__attribute__((weak, visibility("default"))) void launch_write_adaptive(const WriteParamsTonal& wp, hipStream_t on);
+__attribute__((weak, visibility("default"))) void launch_write_adaptive(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
 }
 
 namespace {
@@ -96,6 +97,31 @@ int reset_state(at3phip_ctx* c)
 int quiesce(at3phip_ctx* c)
 {
     if (c->write_stream) HIPCHK(c, hipStreamSynchronize(c->write_stream));
+    return AT3HIP_OK;
+}
+
+// The smallest admissible frame size for a channel count (include/at3phip.h, ADAPTIVE WORD LENGTHS, A5)
+int min_frame_bytes(int channels) { return channels == 2 ? AT3PHIP_MIN_FRAME_BYTES_STEREO : AT3PHIP_MIN_FRAME_BYTES_MONO; }
+bool admissible_frame_bytes(int32_t fb, int channels) { return fb >= min_frame_bytes(channels) && fb <= kFrameBytes && fb % 8 == 0; }
+// the setters' last-error text for a size that is not
+struct FrameBytesError {
+    char text[96];
+};
+FrameBytesError frame_bytes_error(int32_t fb, int channels)
+{
+    FrameBytesError e;
+    snprintf(e.text, sizeof(e.text), "frame_bytes %d: not a multiple of 8 in %d..%d", (int)fb, min_frame_bytes(channels), kFrameBytes);
+    return e;
+}
+
+// A frame-writing call at the context's frame size: the fixed table is the reference's and fills 2048 bytes only, so at any other
+// size the call needs AT3PHIP_ALLOC_ADAPTIVE. Checked before anything is queued or any state moves.
+int check_frame_size(at3phip_ctx* c, uint32_t flags)
+{
+    if (c->frame_bytes != kFrameBytes && !(flags & AT3PHIP_ALLOC_ADAPTIVE))
+        return fail(c, AT3HIP_EINVAL, "the fixed table is defined for 2048-byte frames only: this context's frame size needs AT3PHIP_ALLOC_ADAPTIVE");
+    if ((flags & AT3PHIP_ALLOC_ADAPTIVE) && !launch_write_adaptive)
+        return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_ADAPTIVE: this build has no adaptive writer (at3p_alloc.hip)");
     return AT3HIP_OK;
 }
 
@@ -165,7 +191,7 @@ int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint1
     }
     wp.tonal = d_records;
     if (adaptive) {
-        launch_write_adaptive(wp, on);
+        launch_write_adaptive(wp, c->frame_bytes, on);
     } else if (d_records) {
         memcpy(wp.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(wp.tone_vlc));
         hipLaunchKernelGGL(k_at3p_write_tonal, dim3((unsigned)(S * n_frames)), dim3(256), 0, on, wp);
@@ -443,6 +469,10 @@ int at3phip_write_frames_tonal(at3phip_ctx* c, const float* specs, int32_t n_fra
                                uint8_t* frames, uint32_t flags)
 {
     if (!c || !specs || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
+    if (c->frame_bytes != kFrameBytes)
+        if (const int rc = check_frame_size(c, flags)) return rc;
+    // (The records' contract is all that is checked here at every frame size: the smallest admissible sizes,
+    // AT3PHIP_MIN_FRAME_BYTES_*, hold the largest tail a record can give beside one unit per channel, so no record needs a tail check.)
     bool any = false;   // records without a block are the writer without records
     if (tonal)
         for (int s = 0; s < c->cfg.n_streams; ++s)
@@ -459,7 +489,7 @@ int at3phip_write_frames_tonal(at3phip_ctx* c, const float* specs, int32_t n_fra
     const size_t items = (size_t)c->cfg.n_streams * n_frames;
     const float* d_specs = (flags & AT3HIP_PCM_ON_DEVICE) ? specs : c->d_specs;
     uint8_t* d_frames = (flags & AT3HIP_OUT_ON_DEVICE) ? frames : c->d_frames;
-    const Stage stage = {specs, c->d_specs, items * c->cfg.channels * 2048 * sizeof(float), {{frames, c->d_frames, items * kFrameBytes}}, 2, {&at3phip_ctx::write_ms}};
+    const Stage stage = {specs, c->d_specs, items * c->cfg.channels * 2048 * sizeof(float), {{frames, c->d_frames, items * (size_t)c->frame_bytes}}, 2, {&at3phip_ctx::write_ms}};
     return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames, nullptr, tonal, nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0); });
 }
 
@@ -475,6 +505,8 @@ template <typename T, bool kTones = false>
 int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
 {
     if (!c || !pcm || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
+    if (c->frame_bytes != kFrameBytes)
+        if (const int rc = check_frame_size(c, flags)) return rc;
     at3host::DeviceGuard guard(c->device);
     HIPCHK(c, guard.error());
     if constexpr (kTones) {
@@ -515,7 +547,7 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     rc = launch_write(c, d_specs, n_frames, nullptr, d_frames, ws, nullptr, kTones ? c->d_tone_writer[par] : nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0);
     if (rc != AT3HIP_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[3], ws));
-    if (!(flags & AT3HIP_OUT_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(frames, c->d_frames, items * kFrameBytes, hipMemcpyDeviceToHost, ws));
+    if (!(flags & AT3HIP_OUT_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(frames, c->d_frames, items * (size_t)c->frame_bytes, hipMemcpyDeviceToHost, ws));
     HIPCHK(c, hipEventRecord(c->ev_write_done[par], ws));
     c->write_done_valid[par] = true;
     c->enc_calls++;
@@ -646,6 +678,25 @@ int at3phip_sync(at3phip_ctx* c)
     });
 }
 
+// An admissible size: waits for queued work (a queued call still writes frames of the old size), then only stores the size: the
+// staging buffers are sized for 2048 bytes, the upper bound, and stream state does not depend on the size.
+int at3phip_set_frame_bytes(at3phip_ctx* c, int32_t frame_bytes)
+{
+    if (!c) return AT3HIP_EINVAL;
+    if (!admissible_frame_bytes(frame_bytes, c->cfg.channels)) return fail(c, AT3HIP_EINVAL, frame_bytes_error(frame_bytes, c->cfg.channels).text);
+    const int rc = at3phip_sync(c);
+    if (rc != AT3HIP_OK) return rc;
+    c->frame_bytes = frame_bytes;
+    return AT3HIP_OK;
+}
+
+int at3phip_get_frame_bytes(const at3phip_ctx* c, int32_t* frame_bytes)
+{
+    if (!c || !frame_bytes) return AT3HIP_EINVAL;
+    *frame_bytes = c->frame_bytes;
+    return AT3HIP_OK;
+}
+
 int at3phip_get_write_timing(const at3phip_ctx* c, float* write_ms)
 {
     if (!c) return AT3HIP_EINVAL;
@@ -693,6 +744,7 @@ struct at3phip_decoder : at3host::DecoderBase {
     uint16_t* d_flags = nullptr;   // [F + 2][S][C]
     TonalRec* d_tonal = nullptr;   // [F + 3][S]: slots 0 .. 2 = the carried records of frames -3 .. -1
     DecToneTables* d_tone_tables = nullptr;
+    int32_t frame_bytes = 2048;    // at3phip_decoder_set_frame_bytes: `frames` of at3phip_decode is [S][F][frame_bytes]; d_in is sized for 2048
     // (d_in: the frames [S][F][2048], d_out: [S][F][2048][C], d_rejected: [kDecReasons])
 };
 
@@ -844,6 +896,7 @@ int decp_launch(at3phip_decoder* d, const uint8_t* d_frames, int n_frames, void*
     DecUnpackParams up;
     up.T = d->d_tables;
     up.frames = d_frames;
+    up.frame_bytes = d->frame_bytes;
     up.n_frames = n_frames;
     up.n_streams = (int)S;
     up.nch = (int)C;
@@ -853,7 +906,8 @@ int decp_launch(at3phip_decoder* d, const uint8_t* d_frames, int n_frames, void*
     up.tonal = d->d_tonal;
     up.tone_vlc = d->d_tone_tables->vlc;
     up.tones = tones;
-    hipLaunchKernelGGL(k_at3pd_unpack, dim3((unsigned)F, (unsigned)S), dim3(kDecUnpackThreads), 0, st, up);
+    if (d->frame_bytes == 2048) hipLaunchKernelGGL(k_at3pd_unpack, dim3((unsigned)F, (unsigned)S), dim3(kDecUnpackThreads), 0, st, up);
+    else hipLaunchKernelGGL(k_at3pd_unpack_sized, dim3((unsigned)F, (unsigned)S), dim3(kDecUnpackThreads), 0, st, up);
     HIPCHK(d, hipGetLastError());
     DecSynthParams sp;
     sp.T = d->d_tables;
@@ -881,9 +935,27 @@ extern "C" {
 
 int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags)
 {
-    return at3host::decode_call(d, frames, n_frames, pcm, flags, AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES, AT3PHIP_DECODE_S16, 2048,
-                                d ? (size_t)2048 * d->cfg.channels : 0,
+    return at3host::decode_call(d, frames, n_frames, pcm, flags, AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES, AT3PHIP_DECODE_S16,
+                                d ? (size_t)d->frame_bytes : 0, d ? (size_t)2048 * d->cfg.channels : 0,
                                 [&](const uint8_t* d_frames, void* d_pcm) { return decp_launch(d, d_frames, n_frames, d_pcm, flags); });
+}
+
+// As at3phip_set_frame_bytes: an admissible size waits for queued work, then is stored.
+int at3phip_decoder_set_frame_bytes(at3phip_decoder* d, int32_t frame_bytes)
+{
+    if (!d) return AT3HIP_EINVAL;
+    if (!admissible_frame_bytes(frame_bytes, d->cfg.channels)) return fail(d, AT3HIP_EINVAL, frame_bytes_error(frame_bytes, d->cfg.channels).text);
+    const int rc = at3host::engine_sync(d);
+    if (rc != AT3HIP_OK) return rc;
+    d->frame_bytes = frame_bytes;
+    return AT3HIP_OK;
+}
+
+int at3phip_decoder_get_frame_bytes(const at3phip_decoder* d, int32_t* frame_bytes)
+{
+    if (!d || !frame_bytes) return AT3HIP_EINVAL;
+    *frame_bytes = d->frame_bytes;
+    return AT3HIP_OK;
 }
 
 int at3phip_decoder_host_tables(void* dst, size_t bytes)

@@ -1002,12 +1002,14 @@ public:
     // deviceShared: with AT3PHIP_TONES_SHARED, byte for byte TAt3PToneAnalyser(channels, deviceGated, true)'s frames.
     // adaptive: every frame-writing call carries AT3PHIP_ALLOC_ADAPTIVE (include/at3phip.h, ADAPTIVE WORD LENGTHS): the word
     // lengths are chosen on the device, with a host analyser too; the mirror has no allocator of its own.
+    // frameBytes: the size of the frames written (at3phip_set_frame_bytes; the caller gives CreateAtrac3PlusOutput the same
+    // size). Other than AT3PHIP_FRAME_BYTES it needs `adaptive`: the library refuses the fixed table at any other size.
     TAt3PEncoder(TCompressedOutputPtr&& out, int channels, int batchFrames = 64, int deviceId = 0, TAt3PSettings settings = TAt3PSettings(),
                  IAt3PGhaProcessor* gha = nullptr, bool deviceTones = false, bool deviceGated = false, bool deviceShared = false,
-                 bool adaptive = false)
+                 bool adaptive = false, int frameBytes = AT3PHIP_FRAME_BYTES)
         : Out(std::move(out)), Channels((size_t)channels), BatchFrames(batchFrames), FrameFloats((size_t)AT3PHIP_FRAME * (size_t)channels),
           Settings(settings), Gha(gha), DeviceTones(deviceTones), ToneFlags((deviceGated ? AT3PHIP_TONES_GATED : 0u) | (deviceShared ? AT3PHIP_TONES_SHARED : 0u)),
-          AllocFlag(adaptive ? AT3PHIP_ALLOC_ADAPTIVE : 0u)
+          AllocFlag(adaptive ? AT3PHIP_ALLOC_ADAPTIVE : 0u), FrameBytes((size_t)frameBytes)
     {
         if (deviceTones && gha) throw std::invalid_argument("TAt3PEncoder: deviceTones takes no host analyser");
         if (deviceGated && !deviceTones) throw std::invalid_argument("TAt3PEncoder: deviceGated needs deviceTones");
@@ -1019,6 +1021,14 @@ public:
         cfg.device_id = deviceId;
         const int rc = at3phip_create(&cfg, &Ctx);
         if (rc != AT3HIP_OK) throw std::runtime_error("at3phip_create failed: " + std::to_string(rc));
+        if (frameBytes != AT3PHIP_FRAME_BYTES) {   // (a context at the default size is never told so: its calls stay what they were)
+            const int src = at3phip_set_frame_bytes(Ctx, frameBytes);
+            if (src != AT3HIP_OK) {
+                const std::string why = at3phip_last_error(Ctx);
+                at3phip_destroy(Ctx);
+                throw std::runtime_error("at3phip_set_frame_bytes: " + why);
+            }
+        }
         Pending.reserve((size_t)BatchFrames * FrameFloats);
     }
     ~TAt3PEncoder()
@@ -1060,12 +1070,12 @@ public:
             }
             return first;
         }
-        std::vector<uint8_t> frames((size_t)BatchFrames * AT3PHIP_FRAME_BYTES);
+        std::vector<uint8_t> frames((size_t)BatchFrames * FrameBytes);
         for (int at = 0; at < nFrames; at += BatchFrames) {
             const int nf = std::min(BatchFrames, nFrames - at);
             if (DeviceTones) Chk(at3phip_encode_frames_tonal_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), ToneFlags | AllocFlag), "at3phip_encode_frames_tonal_short");
             else Chk(at3phip_encode_frames_short(Ctx, pcm + (size_t)at * FrameFloats, nf, frames.data(), AllocFlag), "at3phip_encode_frames_short");
-            for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES);
+            for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * FrameBytes, frames.begin() + (size_t)(i + 1) * FrameBytes);
             Calls += (size_t)nf;
             Flush();
         }
@@ -1081,11 +1091,11 @@ public:
             return;
         }
         if (nf > 0) {
-            std::vector<uint8_t> frames((size_t)nf * AT3PHIP_FRAME_BYTES);
+            std::vector<uint8_t> frames((size_t)nf * FrameBytes);
             if (DeviceTones) Chk(at3phip_encode_frames_tonal(Ctx, Pending.data(), nf, frames.data(), ToneFlags | AllocFlag), "at3phip_encode_frames_tonal");
             else Chk(at3phip_encode_frames(Ctx, Pending.data(), nf, frames.data(), AllocFlag), "at3phip_encode_frames");
             Pending.clear();
-            for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES);
+            for (int i = 0; i < nf; ++i) Ready.emplace_back(frames.begin() + (size_t)i * FrameBytes, frames.begin() + (size_t)(i + 1) * FrameBytes);
         }
         // call k (0-based) is answered with: nothing (k = 0), silence (k = 1), input frame k - 2; with deviceTones the analysis lags
         // one frame itself (its frame f holds the residual of input frame f - 1), so call k >= 1 is answered with its frame k - 1
@@ -1143,17 +1153,17 @@ private:
         if (calls == 0) return;
         if (!(Settings.UseGha & TAt3PSettings::GHA_WRITE_RESIUDAL)) std::fill(prevs.begin(), prevs.end(), 0.0f);
         std::vector<float> specs(prevs.size());
-        std::vector<uint8_t> frames((size_t)calls * AT3PHIP_FRAME_BYTES);
+        std::vector<uint8_t> frames((size_t)calls * FrameBytes);
         Chk(at3phip_mdct(Ctx, prevs.data(), calls, nullptr, specs.data(), AT3PHIP_RESIDUAL_SCALE), "at3phip_mdct");
         Chk(at3phip_write_frames_tonal(Ctx, specs.data(), calls, nullptr, blocks.data(), frames.data(), AllocFlag), "at3phip_write_frames_tonal");
         for (int i = 0; i < calls; ++i)
-            Out->WriteFrame(std::vector<char>(frames.begin() + (size_t)i * AT3PHIP_FRAME_BYTES, frames.begin() + (size_t)(i + 1) * AT3PHIP_FRAME_BYTES));
+            Out->WriteFrame(std::vector<char>(frames.begin() + (size_t)i * FrameBytes, frames.begin() + (size_t)(i + 1) * FrameBytes));
         Written += (size_t)calls;
     }
     std::vector<char> SilentFrame()   // an all-zero spectrum through the frame writer (the encoder's PrevBuf starts zeroed)
     {
         std::vector<float> specs(FrameFloats, 0.0f);
-        std::vector<uint8_t> frame(AT3PHIP_FRAME_BYTES);
+        std::vector<uint8_t> frame(FrameBytes);
         Chk(at3phip_write_frames(Ctx, specs.data(), 1, nullptr, frame.data(), AllocFlag), "at3phip_write_frames");
         return std::vector<char>(frame.begin(), frame.end());
     }
@@ -1170,6 +1180,7 @@ private:
     const bool DeviceTones;                       // the analysis runs on the GPU
     const uint32_t ToneFlags;                     // and with these flags (AT3PHIP_TONES_GATED, AT3PHIP_TONES_SHARED)
     const uint32_t AllocFlag;                     // AT3PHIP_ALLOC_ADAPTIVE or 0, on every frame-writing call
+    const size_t FrameBytes;                      // the context's frame size
     std::vector<float> PrevBuf, CurBuf, RawCur;   // [C][16][128] / [C][2048]: TChannelCtx's PrevBuf, CurBuf and RawCurBuf
     at3phip_tonal_block Delay{};                  // `delay`: the block the next call writes
 };

@@ -7,8 +7,11 @@
 //             [--nogaincontrol] [--container oma|riff|raw] [--nostdout] [--batch blocks] [--device n]
 //   at3hipenc -e atrac1 -i in.wav -o out.{aea|raw|dat} [--bfuidxconst 1..8] [--notransient[=mask]]
 //             [--container aea|raw] [--nostdout] [--batch blocks] [--device n]
-//   at3hipenc -e atrac3plus -i in.wav -o out.{oma|at3|wav|raw|dat} [--adaptive] [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout]
-//             [--batch frames] [--device n]
+//   at3hipenc -e atrac3plus -i in.wav -o out.{oma|at3|wav|raw|dat} [--adaptive [--bitrate kbit]] [--tones [--gate] [--share]]
+//             [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]
+//             --bitrate: one of kAt3pRates' rows (32 .. 352 kbit/s); below 352 the frames are smaller than the 2048 bytes the
+//             fixed word-length table fills, so it needs --adaptive. -d decodes an ATRAC3plus file of any of these frame sizes
+//             and names the bitrate in its "Codec:" line for every size but 2048 bytes, whose line stays the text it always was.
 //   --resample (all three encoders): a WAV at 8 .. 192 kHz (at3hip_resample.h's list) is converted to 44.1 kHz on the GPU
 //             first; the container headers count ceil(N 44100 / rate) samples. A 44.1 kHz input is encoded as without it.
 //   --loudness LUFS [--peak dBFS] [--truepeak] (all three encoders): pass one meters the 44.1 kHz samples the encoder will see
@@ -73,6 +76,34 @@ const char* at1_unit_fault(const uint8_t* u)
         end += (wl ? wl + 1 : 0) * spb[b];
     }
     return end > AT1HIP_FRAME_SIZE * 8 ? "read past the end of the bitstream" : nullptr;   // TBitStream::Read, bitstream.cpp:73-74
+}
+
+// ATRAC3plus at 44.1 kHz: --bitrate kbit and the frame size it stands for. A frame is 2048 samples per channel, so
+// bytes * 8 * 44100 / 2048 is the bit rate: 192 -> 33.1 kbit/s, 376 -> 64.8, 2048 -> 352.8. The sizes are the ones remembered
+// from Sony's players; nobody here could check them against a device. 32 kbit/s is a mono rate.
+struct TAt3pRate {
+    int kbit, frameBytes;
+};
+const TAt3pRate kAt3pRates[] = {{32, 192}, {48, 280}, {64, 376}, {96, 560}, {128, 744}, {160, 936}, {192, 1120}, {256, 1488}, {320, 1864}, {352, 2048}};
+
+const TAt3pRate* at3p_rate_of_kbit(int kbit)
+{
+    for (const TAt3pRate& r : kAt3pRates)
+        if (r.kbit == kbit) return &r;
+    return nullptr;
+}
+const TAt3pRate* at3p_rate_of_bytes(int frameBytes)
+{
+    for (const TAt3pRate& r : kAt3pRates)
+        if (r.frameBytes == frameBytes) return &r;
+    return nullptr;
+}
+std::string at3p_rate_table()
+{
+    std::string t;
+    for (const TAt3pRate& r : kAt3pRates)
+        t += (t.empty() ? "" : ", ") + std::to_string(r.kbit) + (r.kbit == 32 ? " (mono only)" : "") + " -> " + std::to_string(r.frameBytes) + " bytes";
+    return t;
 }
 
 int fatal(const std::string& what)
@@ -236,6 +267,7 @@ struct TOptions {
 //   Samples per frame and channel, FrameBytes per frame (every channel), Channels, Config(batch, device)
 //   S16 / Float, the decode flags of the 16-bit output and of the float output that feeds --rate
 //   InputLines, the banner's lines about the input, FrameText for "Can't read <FrameText>" (and Skipped, Reasons(counters))
+//   Setup(decoder), run once on the new decoder: null, or the name of the call that failed
 // nOut frames are decoded, nRead >= nOut are read, B at a time (0: an empty file, nothing to create); inspect(frames, n) sees
 // every batch read, report(decoder) runs after the last one and ends the run with status 1 when it returns false.
 template <typename D, typename TInspect, typename TReport>
@@ -260,6 +292,10 @@ int run_decode(const D& d, std::ifstream& in, const TOptions& o, int64_t nOut, i
     int rc = D::Create(&cfg, &made);
     if (rc != AT3HIP_OK) return fatal(std::string(D::Api) + "_decoder_create failed (" + std::to_string(rc) + ")");
     const std::unique_ptr<typename D::THandle, void (*)(typename D::THandle*)> dec(made, D::Destroy);
+    if (const char* failed = d.Setup(dec.get())) {   // what the description sets on the new decoder; the name of the call that failed
+        std::cerr << "Fatal error: " << failed << ": " << D::LastError(dec.get()) << std::endl;
+        return 1;
+    }
     std::vector<uint8_t> frames((size_t)B * d.FrameBytes);
     std::vector<int16_t> pcm((size_t)B * D::Samples * nch);
     std::vector<float> pcmf(rw ? (size_t)B * D::Samples * nch : 0);
@@ -322,6 +358,7 @@ struct TAt1Decode {
     int Channels, FrameBytes;
     std::string InputLines;
     at1hip_decoder_config Config(int batch, int device) const { return {Channels, 1, batch, device}; }
+    const char* Setup(THandle*) const { return nullptr; }
 };
 
 int decode_aea(std::ifstream& in, const TOptions& o)
@@ -400,16 +437,16 @@ EInput probe_input(const std::string& inFile, TAt3Input& at3)
         const uint32_t id = word >> 24;
         if (id == 1) {   // ATRAC3plus: channel id in bits 10-12, (FrameSz - 8) / 8 in the low 10 bits
             const int chId = (int)((word >> 10) & 7), frameBytes = (int)(word & 0x3FF) * 8 + 8;
-            if ((chId != 1 && chId != 2) || frameBytes != 2048) {
+            if ((chId != 1 && chId != 2) || !at3p_rate_of_bytes(frameBytes) || (frameBytes == 192 && chId != 1)) {
                 std::cerr << "Fatal error: ATRAC3plus decoding is not supported for channel id " << chId << ", frame size "
                           << frameBytes << std::endl;
                 return EInput::REFUSED;
             }
             at3.container = "OMA";
             at3.offset = 96;
-            at3.frameSize = 2048;
+            at3.frameSize = frameBytes;
             at3.channels = chId;
-            at3.frames = (fileSize - 96) / 2048;
+            at3.frames = (fileSize - 96) / frameBytes;
             return EInput::ATRAC3PLUS;
         }
         if (id != 0) {
@@ -444,7 +481,7 @@ EInput probe_input(const std::string& inFile, TAt3Input& at3)
             pos += 8 + sz + (sz & 1);
         }
         if (tag == 0xFFFE) {
-            if (!at3pGuid || at3.frameSize != 2048 || (at3.channels != 1 && at3.channels != 2)) {
+            if (!at3pGuid || !at3p_rate_of_bytes(at3.frameSize) || (at3.channels != 1 && at3.channels != 2) || (at3.frameSize == 192 && at3.channels != 1)) {
                 std::cerr << "Fatal error: ATRAC3plus decoding is not supported for " << (at3pGuid ? "" : "a sub-format other than ATRAC3plus, ")
                           << at3.channels << " channels, block align " << at3.frameSize << std::endl;
                 return EInput::REFUSED;
@@ -455,7 +492,7 @@ EInput probe_input(const std::string& inFile, TAt3Input& at3)
             }
             at3.container = "RIFF";
             at3.offset = dataPos;
-            at3.frames = std::min<int64_t>(dataLen, fileSize - dataPos) / 2048;
+            at3.frames = std::min<int64_t>(dataLen, fileSize - dataPos) / at3.frameSize;
             return EInput::ATRAC3PLUS;
         }
         if (tag != 0x270) return EInput::AEA;
@@ -503,6 +540,7 @@ struct TAt3Decode {
     {
     }
     at3hip_decoder_config Config(int batch, int device) const { return {1, FrameBytes, Js, batch, device}; }
+    const char* Setup(THandle*) const { return nullptr; }
     static TReasons Reasons(const TCounters& c)
     {
         return {{"wrong unit id", c.bad_id}, {"unsupported joint-stereo parameters", c.unsupported_js}, {"read past the end of the unit", c.read_past_end},
@@ -510,7 +548,7 @@ struct TAt3Decode {
     }
 };
 
-// `-d` on an ATRAC3plus OMA / RIFF file: a 16-bit WAV with the stream's channel count, 2048 samples per frame, the codec delay
+// `-d` on an ATRAC3plus OMA / RIFF file whose frame size is one of kAt3pRates': a 16-bit WAV with the stream's channel count, 2048 samples per frame, the codec delay
 // (2416 samples) not trimmed; rejected frames are counted and reported per reason.
 struct TAt3pDecode {
     using THandle = at3phip_decoder;
@@ -523,15 +561,21 @@ struct TAt3pDecode {
     static constexpr auto Destroy = at3phip_decoder_destroy;
     static constexpr int Samples = 2048;
     static constexpr uint32_t S16 = AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES, Float = AT3PHIP_DECODE_TONES;
-    int Channels, FrameBytes = 2048;
+    int Channels, FrameBytes;
     std::string InputLines;
 
     explicit TAt3pDecode(const TAt3Input& f)
-        : Channels(f.channels), InputLines(" Container: " + f.container + "\n Codec: ATRAC3plus, " + std::to_string(f.channels) +
-                                           (f.channels == 1 ? " channel" : " channels"))
-    {
+        : Channels(f.channels), FrameBytes(f.frameSize),
+          InputLines(" Container: " + f.container + "\n Codec: ATRAC3plus, " + std::to_string(f.channels) + (f.channels == 1 ? " channel" : " channels"))
+    {   // the bitrate, for every size but the one the line never named (a 2048-byte file prints what it always printed)
+        if (f.frameSize != AT3PHIP_FRAME_BYTES)
+            InputLines += ", " + std::to_string(at3p_rate_of_bytes(f.frameSize)->kbit) + " kbit/s (" + std::to_string(f.frameSize) + "-byte frames)";
     }
     at3phip_decoder_config Config(int batch, int device) const { return {Channels, 1, batch, device}; }
+    const char* Setup(THandle* dec) const   // (a decoder at the default size is never told so)
+    {
+        return FrameBytes == AT3PHIP_FRAME_BYTES || at3phip_decoder_set_frame_bytes(dec, FrameBytes) == AT3HIP_OK ? nullptr : "at3phip_decoder_set_frame_bytes";
+    }
     static TReasons Reasons(const TCounters& c)
     {
         return {{"bad header or block type", c.bad_header}, {"unsupported syntax element", c.unsupported_syntax},
@@ -648,19 +692,42 @@ struct TAtrac3PlusEncode {
     static constexpr size_t Block = 2048;
     static constexpr const char* InputLine = "Input:";
     static uint64_t NumFrames(uint64_t samples, size_t) { return samples / 2048; }   // main.cpp:440
-    static bool CheckOptions(const TOptions&) { return true; }
+    static bool CheckOptions(const TOptions& o)
+    {
+        if (!o.bitrate) return true;
+        const TAt3pRate* r = at3p_rate_of_kbit((int)o.bitrate);
+        if (!r) {
+            std::cerr << "ATRAC3plus mode, --bitrate takes one of: " << at3p_rate_table() << "\n";
+            return false;
+        }
+        if (r->frameBytes != AT3PHIP_FRAME_BYTES && !o.adaptive) {
+            std::cerr << "--bitrate " << r->kbit << " needs --adaptive: the fixed word-length table is defined for 2048-byte frames (352 kbit/s) only, "
+                      << "and only the adaptive writer chooses word lengths that fit a frame of " << r->frameBytes << " bytes\n";
+            return false;
+        }
+        return true;
+    }
     size_t Channels;
+    const TAt3pRate* Rate;   // null: no --bitrate, 2048-byte frames
 
-    TAtrac3PlusEncode(const TOptions&, size_t channels) : Channels(channels) {}
+    TAtrac3PlusEncode(const TOptions& o, size_t channels) : Channels(channels), Rate(o.bitrate ? at3p_rate_of_kbit((int)o.bitrate) : nullptr)
+    {
+        if (Rate && Rate->kbit == 32 && channels != 1) throw std::runtime_error("--bitrate 32 is a mono rate: the input has " + std::to_string(channels) + " channels");
+    }
+    uint32_t FrameBytes() const { return Rate ? (uint32_t)Rate->frameBytes : (uint32_t)AT3PHIP_FRAME_BYTES; }
     TCompressedOutputPtr Output(const TOptions& o, size_t channels, uint32_t numFrames) const
     {
         const EContainer c = container_of(o, SelectAtrac3PlusContainer, {EContainer::OMA, EContainer::RIFF, EContainer::RAW});
-        return CreateAtrac3PlusOutput(c, o.outFile, channels, numFrames, 2048);
+        return CreateAtrac3PlusOutput(c, o.outFile, channels, numFrames, FrameBytes());
     }
-    std::string CodecLines() const { return "ATRAC3Plus"; }
+    std::string CodecLines() const
+    {
+        return Rate ? "ATRAC3Plus\n Bitrate: " + std::to_string(Rate->kbit) + " kbit/s (" + std::to_string(Rate->frameBytes) + "-byte frames)" : "ATRAC3Plus";
+    }
     TAt3PEncoder Encoder(TCompressedOutputPtr&& out, const TOptions& o)
     {   // --tones: the tone analysis of at3phip_encode_frames_tonal (--gate: with AT3PHIP_TONES_GATED, --share: with AT3PHIP_TONES_SHARED); the frame count is the plain encode's
-        return TAt3PEncoder(std::move(out), (int)Channels, o.batch > 64 ? 64 : o.batch, o.device, TAt3PSettings(), nullptr, o.tones, o.gate, o.share, o.adaptive);
+        return TAt3PEncoder(std::move(out), (int)Channels, o.batch > 64 ? 64 : o.batch, o.device, TAt3PSettings(), nullptr, o.tones, o.gate, o.share, o.adaptive,
+                            (int)FrameBytes());
     }
     void Report(TAt3PEncoder&, const TOptions&) const {}
 };
@@ -706,8 +773,9 @@ static int usage()
                  "                 [--container oma|riff|raw] [--nostdout] [--batch blocks] [--device n]\n"
                  "       at3hipenc -e atrac1 -i in.wav -o out.aea [--bfuidxconst 1..8] [--notransient[=mask]]\n"
                  "                 [--container aea|raw] [--nostdout] [--batch blocks] [--device n]\n"
-                 "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--adaptive] [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
-                 "                 (--adaptive: word lengths chosen per frame on the GPU to fill the 2048-byte frame, instead of the fixed table)\n"
+                 "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--adaptive [--bitrate kbit]] [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
+                 "                 (--adaptive: word lengths chosen per frame on the GPU to fill the frame, instead of the fixed table)\n"
+                 "                 (--bitrate: 32 (mono), 48, 64, 96, 128, 160, 192, 256, 320 or 352 kbit/s; below 352 with --adaptive only)\n"
                  "                 (--tones: find sine waves on the GPU and write them as tonal blocks; --gate: with envelope points at\n"
                  "                  their onsets and offsets; --share: a band that both channels of a stereo input hold identically is\n"
                  "                  written once)\n"
@@ -717,6 +785,7 @@ static int usage()
                  "       at3hipenc --measure -i in.wav [--resample] [--truepeak]   (prints loudness and peaks, writes nothing)\n"
                  "       at3hipenc -d -i in.aea -o out.wav [--nostdout] [--batch frames] [--device n]\n"
                  "       at3hipenc -d -i in.{oma|at3|wav} -o out.wav [--nostdout] [--batch frames] [--device n]   (ATRAC3 / ATRAC3plus, by content)\n"
+                 "                 (ATRAC3plus: any frame size of the --bitrate table; the codec line names the bitrate except at 352 kbit/s)\n"
                  "       (every decoder: --rate hz writes the WAV at 8 .. 192 kHz instead of 44.1 kHz)\n";
     return 1;
 }

@@ -70,7 +70,7 @@ int at3phip_pqf_mdct(at3phip_ctx* ctx, const float* pcm, int32_t n_frames, const
  *   specs     [n_streams][n_frames][channels][2048] float32 (flags & AT3HIP_PCM_ON_DEVICE: device memory)
  *   win_flags [n_streams][n_frames][channels] uint16 as in at3phip_mdct (TSubbandInfos::Win); NULL = all sine. Host memory.
  *   frames    [n_streams][n_frames][2048] bytes, each what ICompressedOutput::WriteFrame receives
- *             (flags & AT3HIP_OUT_ON_DEVICE: device memory)
+ *             (flags & AT3HIP_OUT_ON_DEVICE: device memory); [n_streams][n_frames][frame_bytes] after at3phip_set_frame_bytes
  * Frames do not depend on one another. */
 #define AT3PHIP_FRAME_BYTES 2048
 int at3phip_write_frames(at3phip_ctx* ctx, const float* specs, int32_t n_frames, const uint16_t* win_flags, uint8_t* frames,
@@ -341,15 +341,29 @@ uint32_t at3phip_host_tone_flags(void);
  *      the range its OR-accumulated largest delta m allows (m >= 3: tables 2 and 3; m = 2: table 1; else table 0); the scale
  *      factor indices (2 + 6 N per channel) and the code-table indices (1, then 4 + 3 N per channel); the sum of B over the coded
  *      units; the power groups for N (4 bits each, per channel); and the tail, formed once as in the fixed writer: two bits in
- *      stereo, window shapes, a gain-compensation bit per channel, tonal flag and block, noise flag, terminator. A fits when
- *      Bits(A) <= 16381.
- *  A5. Choice. t* is the smallest t in -21..63 whose A(t, 0) fits; t = 63 always fits (one unit per channel at word length 1 and
- *      the tail, which at3phip_write_frames_tonal's bound on the tail covers). k* is the largest k in 0..64 whose A(t*, k) fits.
+ *      stereo, window shapes, a gain-compensation bit per channel, tonal flag and block, noise flag, terminator. A frame is
+ *      frame_bytes bytes (FRAME SIZE below; 2048 unless at3phip_set_frame_bytes was called) and A fits when
+ *      Bits(A) <= 8 * frame_bytes - 3 (16381 at 2048 bytes).
+ *  A5. Choice. t* is the smallest t in -21..63 whose A(t, 0) fits; t = 63 always fits at every admissible frame size: A(63, 0) is
+ *      one unit per channel at word length 1, at most 77 bits in mono and 147 in stereo in front of the tail, and the tail is at
+ *      most 1320 bits in mono and 1624 in stereo (FRAME SIZE below derives the smallest sizes from these). k* is the largest k
+ *      in 0..64 whose A(t*, k) fits.
  *      Both are defined by the full scan and not by bisection: code lengths are not provably monotone in the word length, and
  *      the scan is the definition whether they are or not. A k beyond the number of units that can take the t - 1 value gives
  *      the allocation of that number, so k* is reported as that number: 0 for a frame that fits at t = -21.
  *  A6. The frame is A(t*, k*) in the fixed writer's layout, with tab[ch][qu][wl] as the unit's code-table index.
- * Out of this definition: a word length of 0 inside the coded range, psychoacoustic weighting, frame sizes other than 2048 bytes.
+ * FRAME SIZE. frame_bytes is a property of the context: 2048 (352.8 kbit/s at 44.1 kHz, the one size the reference writes) until
+ * at3phip_set_frame_bytes changes it. Admissible are the multiples of 8 from AT3PHIP_MIN_FRAME_BYTES_MONO (mono contexts) or
+ * AT3PHIP_MIN_FRAME_BYTES_STEREO (stereo contexts) to 2048. The minimum is the smallest multiple of 8 at which A(63, 0) fits
+ * whatever the spectrum and the tonal record are. Upper bounds from the tables, formed as tests/test_at3p_tonal_write_cpu.py forms
+ * the 16-unit bound: in front of the tail 5 + 1 bits, the word-length section with every code at AT3P_WL_VLC's longest length,
+ * scale factor and code-table indices and one power group per channel for N = 1, and unit 0's 16 lines at word length 1 under the
+ * cheapest-in-the-worst-case of its eight tables (40 bits) - 77 bits in mono, 147 in stereo; the tail with 18 bits per window
+ * shape, the long sharing form, every band with both envelope points, 48 waves of 10 + 6 + 5 bits and 24 order bits - 1320 bits
+ * in mono, 1624 in stereo. 77 + 1320 = 1397 <= 8 * 176 - 3 and > 8 * 168 - 3; 147 + 1624 = 1771 <= 8 * 224 - 3 and > 8 * 216 - 3.
+ * Everything else in A1-A6 stands at every size, "a word length of 0 is never written" included. Only 2048 bytes has a fixed
+ * table: at any other size a frame-writing call without AT3PHIP_ALLOC_ADAPTIVE is refused, never served by another path.
+ * Out of this definition: a word length of 0 inside the coded range, psychoacoustic weighting.
  * The tone analysis is unaffected by the flag; a stream may change it from call to call. Still ABI 1.6: a library that has the
  * symbol at3phip_host_allocate takes the flag. */
 #define AT3PHIP_ALLOC_ADAPTIVE 128u
@@ -364,6 +378,32 @@ uint32_t at3phip_host_tone_flags(void);
  * pointer, a channel count other than 1 or 2, an sfi above 63 or tail_bits out of range. */
 int at3phip_host_allocate(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, uint8_t* wl_out, int32_t* n_units,
                           int32_t* t, int32_t* k);
+
+/* The smallest admissible frame sizes (FRAME SIZE above); tests/test_at3p_rate_cpu.py derives them from the tables. */
+#define AT3PHIP_MIN_FRAME_BYTES_MONO 176
+#define AT3PHIP_MIN_FRAME_BYTES_STEREO 224
+
+/* The same against the budget 8 * frame_bytes - 3; tail_bits in 0..8 * frame_bytes - 3. at3phip_host_allocate is this call at
+ * 2048. Also AT3HIP_EINVAL for a frame size that is not admissible for the channel count. Still ABI 1.6: a library that has this
+ * symbol has the frame-size setters below. */
+int at3phip_host_allocate_sized(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, int32_t frame_bytes,
+                                uint8_t* wl_out, int32_t* n_units, int32_t* t, int32_t* k);
+
+/* The context's frame size (FRAME SIZE above). Given an admissible size the setter first waits for everything queued on the
+ * context, as at3phip_sync does (a queued call still writes frames of the old size), then stores the size: it allocates and
+ * uploads nothing (the staging buffers are sized for 2048 bytes, the upper bound) and does
+ * not touch stream state - frames do not depend on one another, so a stream may change its size between calls. From then on
+ * `frames` of at3phip_write_frames, at3phip_write_frames_tonal, at3phip_encode_frames, at3phip_encode_frames_short,
+ * at3phip_encode_frames_tonal and at3phip_encode_frames_tonal_short is [n_streams][n_frames][frame_bytes], dense; a frame is
+ * 4-byte aligned in it whenever the buffer is, which the writer's word stores rely on. At a size other than 2048 each of the six
+ * is refused with AT3HIP_EINVAL unless `flags` has AT3PHIP_ALLOC_ADAPTIVE ("the fixed table is defined for 2048-byte frames
+ * only"), before anything is queued: no output byte is written and no stream state moves. AT3HIP_EINVAL with a last-error text,
+ * and the size unchanged, for a size that is not admissible; AT3HIP_EINVAL for a null context. A context on which the setter was
+ * never called behaves byte for byte as before. Still ABI 1.6: a host looks for the symbol.
+ * (The command-line tool, at3hipenc: --bitrate chooses among ten of these sizes; `-d` names the bitrate in its codec line for
+ * every size but 2048, whose line stays the text it always was.) */
+int at3phip_set_frame_bytes(at3phip_ctx* ctx, int32_t frame_bytes);
+int at3phip_get_frame_bytes(const at3phip_ctx* ctx, int32_t* frame_bytes);
 
 /* With AT3HIP_ASYNC in `flags` at3phip_encode_frames only queues the call (pcm must stay valid, frames must not be read)
  * and the frame writer of one call runs beside the filter bank and transform of the next (its own stream, spectra
@@ -391,8 +431,8 @@ int at3phip_host_write_tables(void* dst, size_t bytes);
  * 101-726) -> PCM, for a batch of independent streams, every frame of a call in parallel. The reference has no ATRAC3plus decoder;
  * steps 1, 2 and 4 are this project's definition, steps 3 and 5 restate the reference's synthesis half bit for bit.
  *
- * Definition. A frame is AT3PHIP_FRAME_BYTES (2048) bytes holding one channel unit of `channels` channels; it gives 2048 samples
- * per channel.
+ * Definition. A frame is frame_bytes bytes (AT3PHIP_FRAME_BYTES, 2048, unless at3phip_decoder_set_frame_bytes was called) holding
+ * one channel unit of `channels` channels; it gives 2048 samples per channel.
  *   1. Unpack, MSB first, in the writer's order (every "must" failing rejects the frame, rule 7):
  *      - 1 bit, must be 0; block type (2 bits), must be channels - 1; quant units - 1 (5 bits) = nqu - 1; mute (1 bit), must be 0.
  *      - Word lengths (TWordLenEncoder, :170-252). Channel 0: mode (2 bits, must be 3), weight index and coded values (2 bits
@@ -433,7 +473,7 @@ int at3phip_host_write_tables(void* dst, size_t bytes);
  *   7. A frame is rejected (counted per reason, at3phip_decoder_counters) for: a bad first bit or block type; a syntax element
  *      outside what the writer emits (mute, modes, power levels other than 15, swap / negate, gain compensation, noise); a
  *      tonal block (unless AT3PHIP_DECODE_TONES); an invalid code or an out-of-range value (every code table is complete, so this is a word length of 0);
- *      a read past the frame's 2048 bytes; a terminator other than 3. A rejected frame decodes as a zero spectrum in every
+ *      a read past the frame's frame_bytes bytes; a terminator other than 3. A rejected frame decodes as a zero spectrum in every
  *      channel with all-sine windows, and those are the flags frame n+1 pairs with. */
 /* TONAL BLOCKS (AT3PHIP_DECODE_TONES). The sine waves the reference encoder's GHA analysis subtracted from the subband signal
  * (at3p.cpp:118-170, TGhaProcessorBase::ApplyFilter) are added back. Without the flag every step above stands as written.
@@ -487,12 +527,18 @@ const char* at3phip_decoder_last_error(const at3phip_decoder* dec);
 #define AT3PHIP_DECODE_S16 8u   /* the bit of AT3HIP_DECODE_S16 */
 #define AT3PHIP_DECODE_TONES 16u   /* decode tonal blocks: rule 7 no longer rejects them (TONAL BLOCKS below) */
 
-/*   frames [n_streams][n_frames][2048] bytes
+/*   frames [n_streams][n_frames][frame_bytes] bytes (2048 by default)
  *   pcm    [n_streams][n_frames][2048][channels]: float32, or int16 with AT3PHIP_DECODE_S16
  * flags: AT3HIP_PCM_ON_DEVICE (frames are device memory), AT3HIP_OUT_ON_DEVICE, AT3HIP_ASYNC (only queue the call: buffers stay
  * valid until at3phip_decoder_sync), AT3PHIP_DECODE_S16. Stream state (the last two frames' IMDCT outputs and window flags)
  * carries across calls: any split of a stream into calls gives the same output as one call. */
 int at3phip_decode(at3phip_decoder* dec, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags);
+
+/* The decoder's frame size, with the rules of at3phip_set_frame_bytes: admissible sizes for the channel count, waits for queued
+ * work, allocates nothing, leaves stream state and counters alone, AT3HIP_EINVAL and no change otherwise. After it `frames` of
+ * at3phip_decode is [n_streams][n_frames][frame_bytes] (any alignment: the unpack kernel loads bytes). */
+int at3phip_decoder_set_frame_bytes(at3phip_decoder* dec, int32_t frame_bytes);
+int at3phip_decoder_get_frame_bytes(const at3phip_decoder* dec, int32_t* frame_bytes);
 
 /* Waits for everything queued on the decoder. */
 int at3phip_decoder_sync(at3phip_decoder* dec);
