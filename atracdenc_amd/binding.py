@@ -46,6 +46,8 @@ AT3PHIP_DECODE_S16 = 8                             # include/at3phip.h
 AT3PHIP_FRAME_BYTES = 2048                         # the default frame size
 AT3PHIP_MIN_FRAME_BYTES_MONO, AT3PHIP_MIN_FRAME_BYTES_STEREO = 176, 224   # the smallest admissible sizes (FRAME SIZE)
 AT3PHIP_DECODE_TONES = 16
+AT3PHIP_DECODE_SPARSE = 32   # at3phip_decode: word length 0 inside the coded range (include/at3phip.h, SPARSE WORD LENGTHS)
+AT3PHIP_ALLOC_SPARSE = 256   # the frame-writing calls, with AT3PHIP_ALLOC_ADAPTIVE: a unit inside the coded range may keep word length 0
 AT3PHIP_DECODER_TABLES_BYTES = 67328
 AT3PHIP_DECODER_TONE_TABLES_BYTES = 9504
 
@@ -195,6 +197,7 @@ PROTOTYPES = {
     "at3phip_host_tone_find_tables": (_RC, [_VP, _SZ]), "at3phip_host_tone_gates": (_RC, [_VP, _I32, _I32, _VP]),
     "at3phip_host_tone_flags": (_U32, []), "at3phip_host_allocate": (_RC, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     "at3phip_host_allocate_sized": (_RC, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "at3phip_host_allocate_sparse": (_RC, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
     "at3phip_set_frame_bytes": (_RC, [_VP, _I32]), "at3phip_get_frame_bytes": (_RC, [_VP, _I32P]),
     "at3phip_decoder_set_frame_bytes": (_RC, [_VP, _I32]), "at3phip_decoder_get_frame_bytes": (_RC, [_VP, _I32P]),
     # include/at3phip.h: the ATRAC3plus decoder
@@ -213,7 +216,7 @@ def build_library(verbose=False):
     """Compile libat3hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fvisibility=hidden", "-fPIC", "-shared",
            "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-o", LIB_PATH, os.path.join(CSRC, "at3hip.hip"), os.path.join(CSRC, "at1hip.hip"), os.path.join(CSRC, "at3phip.hip"),
-           os.path.join(CSRC, "at3p_alloc.hip"), os.path.join(CSRC, "resample.hip"), os.path.join(CSRC, "loudness.hip"), os.path.join(CSRC, "at3_tables.cpp")]
+           os.path.join(CSRC, "at3p_alloc.hip"), os.path.join(CSRC, "at3p_sparse.hip"), os.path.join(CSRC, "resample.hip"), os.path.join(CSRC, "loudness.hip"), os.path.join(CSRC, "at3_tables.cpp")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -712,23 +715,30 @@ class At3pHipDecoder(_Decoder):
     def _shapes(self):
         return (self._frame_bytes,), (2048, self.channels)
 
-    def _tones_flag(self, tones):
-        """AT3PHIP_DECODE_TONES for `tones`; a library has tonal-block decoding if it has the tone tables"""
-        if not tones:
-            return 0
-        _need(self.lib, "at3phip_decoder_host_tone_tables")
-        return AT3PHIP_DECODE_TONES
+    def _decode_flags(self, tones, sparse=False):
+        """at3phip_decode's flags beside the buffer ones: AT3PHIP_DECODE_TONES for `tones` (a library has tonal-block decoding if it
+        has the tone tables) and AT3PHIP_DECODE_SPARSE for `sparse` (include/at3phip.h names at3phip_host_allocate_sparse as the
+        symbol that tells a library with SPARSE WORD LENGTHS, encoder and decoder flag alike)."""
+        flags = 0
+        if sparse:
+            _need(self.lib, "at3phip_host_allocate_sparse")
+            flags |= AT3PHIP_DECODE_SPARSE
+        if tones:
+            _need(self.lib, "at3phip_decoder_host_tone_tables")
+            flags |= AT3PHIP_DECODE_TONES
+        return flags
 
-    def decode(self, frames, s16=False, tones=False):
+    def decode(self, frames, s16=False, tones=False, sparse=False):
         """frames uint8 [n_streams, n_frames, frame_bytes] (host) -> float32 (int16 with s16) [n_streams, n_frames, 2048, channels].
-        tones: decode tonal blocks (AT3PHIP_DECODE_TONES) instead of rejecting their frames."""
-        return self._decode(frames, s16, self._tones_flag(tones))
+        tones: decode tonal blocks (AT3PHIP_DECODE_TONES) instead of rejecting their frames. sparse: decode word length 0 inside the
+        coded range (AT3PHIP_DECODE_SPARSE), which AT3PHIP_ALLOC_SPARSE writes, instead of rejecting its frames."""
+        return self._decode(frames, s16, self._decode_flags(tones, sparse))
 
-    def decode_device(self, frames, out, asynchronous=False, ordered=True, tones=False):
+    def decode_device(self, frames, out, asynchronous=False, ordered=True, tones=False, sparse=False):
         """Torch tensors on this decoder's device: frames uint8 [n_streams, n, frame_bytes] -> out float32 / int16 (s16 output)
         [n_streams, n, 2048, channels]. Ordered behind torch's current stream by default, as At1HipDecoder.decode_device.
-        tones as in decode."""
-        self._decode_device(frames, out, asynchronous, ordered, self._tones_flag(tones))
+        tones and sparse as in decode."""
+        self._decode_device(frames, out, asynchronous, ordered, self._decode_flags(tones, sparse))
 
 
 def at3p_decoder_host_tables(lib_path=None):
@@ -833,20 +843,27 @@ def _tone_flags(gated, shared):
     return (AT3PHIP_TONES_GATED if gated else 0) | (AT3PHIP_TONES_SHARED if shared else 0)
 
 
-def _alloc_flag(adaptive):
-    return AT3PHIP_ALLOC_ADAPTIVE if adaptive else 0
+def _alloc_flag(adaptive, sparse=False):
+    """the allocation flags of a frame-writing call; sparse (AT3PHIP_ALLOC_SPARSE) needs adaptive: checked here, before the C call"""
+    if sparse and not adaptive:
+        raise ValueError("sparse=True needs adaptive=True (AT3PHIP_ALLOC_SPARSE is valid only together with AT3PHIP_ALLOC_ADAPTIVE)")
+    return (AT3PHIP_ALLOC_ADAPTIVE if adaptive else 0) | (AT3PHIP_ALLOC_SPARSE if sparse else 0)
 
 
-def at3p_host_allocate(sfi, bits, tail_bits, lib_path=None, frame_bytes=None):
+def at3p_host_allocate(sfi, bits, tail_bits, lib_path=None, frame_bytes=None, sparse=False):
     """at3phip_host_allocate (no GPU): steps A3-A5 of include/at3phip.h, ADAPTIVE WORD LENGTHS, on a cost table: sfi uint8 [C, 32],
     bits uint16 [C, 32, 8] (entry w = the unit's bits at word length w) -> (wl uint8 [C, 32], N, t*, k*). frame_bytes: the
-    budget's frame size through at3phip_host_allocate_sized; None: the 2048-byte entry point."""
+    budget's frame size through at3phip_host_allocate_sized; None: the 2048-byte entry point. sparse: A3s and A4s (SPARSE WORD LENGTHS)
+    through at3phip_host_allocate_sparse, at frame_bytes or 2048."""
     sfi, bits = np.ascontiguousarray(sfi, np.uint8), np.ascontiguousarray(bits, np.uint16)
     C = sfi.shape[0]
     assert sfi.shape == (C, 32) and bits.shape == (C, 32, 8), (sfi.shape, bits.shape)
     wl, out = np.zeros((C, 32), np.uint8), np.zeros(3, np.int32)
     outs = (_vp(wl), _vp(out[0:1]), _vp(out[1:2]), _vp(out[2:3]))
-    if frame_bytes is None:
+    if sparse:
+        name = "at3phip_host_allocate_sparse"
+        rc = _need(load_library(lib_path), name)(_vp(sfi), _vp(bits), C, int(tail_bits), int(AT3PHIP_FRAME_BYTES if frame_bytes is None else frame_bytes), *outs)
+    elif frame_bytes is None:
         rc, name = _need(load_library(lib_path), "at3phip_host_allocate")(_vp(sfi), _vp(bits), C, int(tail_bits), *outs), "at3phip_host_allocate"
     else:
         name = "at3phip_host_allocate_sized"
@@ -962,7 +979,7 @@ class At3pHip(_Context):
     def pqf_mdct_device(self, pcm_ptr, n_frames, specs_ptr):
         self.pqf_mdct_ptr(pcm_ptr, n_frames, None, None, specs_ptr, _device_flags(False))
 
-    def write_frames(self, specs, win_flags=None, tonal=None, adaptive=False):
+    def write_frames(self, specs, win_flags=None, tonal=None, adaptive=False, sparse=False):
         """ScaleFrame + WriteFrame: specs [S, F, C, 2048], win_flags uint16 [S, F, C] or None, tonal records of
         AT3P_TONAL_BLOCK_DTYPE [S, F] (pack_tonal_blocks) or None: no frame carries a tonal block (at3phip_write_frames)
         -> frames uint8 [S, F, frame_bytes]. adaptive: AT3PHIP_ALLOC_ADAPTIVE, word lengths chosen per frame to fill it."""
@@ -972,11 +989,11 @@ class At3pHip(_Context):
         fl, flp = self._flags(win_flags, nf)
         out = np.zeros((self.n_streams, nf, self._frame_bytes), np.uint8)
         if tonal is None:
-            self.write_frames_ptr(specs.ctypes.data, nf, flp, out.ctypes.data, _alloc_flag(adaptive))
+            self.write_frames_ptr(specs.ctypes.data, nf, flp, out.ctypes.data, _alloc_flag(adaptive, sparse))
         else:
             tonal = np.ascontiguousarray(tonal, dtype=AT3P_TONAL_BLOCK_DTYPE)
             assert tonal.shape == (self.n_streams, nf), tonal.shape
-            self.write_frames_tonal_ptr(specs.ctypes.data, nf, flp, tonal.ctypes.data, out.ctypes.data, _alloc_flag(adaptive))
+            self.write_frames_tonal_ptr(specs.ctypes.data, nf, flp, tonal.ctypes.data, out.ctypes.data, _alloc_flag(adaptive, sparse))
         return out
 
     def _encode_frames_host(self, pcm, dtype, raw, flags=0):
@@ -987,16 +1004,16 @@ class At3pHip(_Context):
         raw(pcm.ctypes.data, nf, out.ctypes.data, flags)
         return out
 
-    def encode_frames(self, pcm, adaptive=False):
+    def encode_frames(self, pcm, adaptive=False, sparse=False):
         """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, frame_bytes] (tonal analysis finding nothing; no look-ahead delay).
         adaptive (here and in the encode calls below): AT3PHIP_ALLOC_ADAPTIVE, word lengths chosen per frame to fill it."""
-        return self._encode_frames_host(pcm, np.float32, self.encode_frames_ptr, _alloc_flag(adaptive))
+        return self._encode_frames_host(pcm, np.float32, self.encode_frames_ptr, _alloc_flag(adaptive, sparse))
 
-    def encode_frames_s16(self, pcm, adaptive=False):
+    def encode_frames_s16(self, pcm, adaptive=False, sparse=False):
         """pcm int16 [S, F, 2048, C] (host) -> frames uint8 [S, F, 2048] (at3phip_encode_frames_short): the frames of
         encode_frames() on pcm / 32768 as float32, bit for bit; the samples cross the bus as 16-bit and are widened by the
         filter bank. Calls of both kinds may alternate."""
-        return self._encode_frames_host(pcm, np.int16, self.encode_frames_s16_ptr, _alloc_flag(adaptive))
+        return self._encode_frames_host(pcm, np.int16, self.encode_frames_s16_ptr, _alloc_flag(adaptive, sparse))
 
     def analyse_tones(self, bands, gated=False, shared=False):
         """bands float32 [S, F, C, 16, 128] (what pqf() returns) -> (blocks of AT3P_TONAL_BLOCK_DTYPE [S, F], residual
@@ -1019,34 +1036,34 @@ class At3pHip(_Context):
         self.analyse_tones_ptr(bands_ptr, n_frames, blocks.ctypes.data, residual_ptr, _device_flags(False) | _tone_flags(gated, shared))
         return blocks
 
-    def encode_frames_tonal(self, pcm, gated=False, shared=False, adaptive=False):
+    def encode_frames_tonal(self, pcm, gated=False, shared=False, adaptive=False, sparse=False):
         """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, 2048] with the tone analysis (at3phip_encode_frames_tonal): frame f
         of the stream holds the residual of input frame f-1 and the block of frame f-2, so one trailing frame of silence flushes.
         gated: AT3PHIP_TONES_GATED, shared: AT3PHIP_TONES_SHARED, as in analyse_tones()."""
-        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr, _tone_flags(gated, shared) | _alloc_flag(adaptive))
+        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr, _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse))
 
-    def encode_frames_tonal_s16(self, pcm, gated=False, shared=False, adaptive=False):
+    def encode_frames_tonal_s16(self, pcm, gated=False, shared=False, adaptive=False, sparse=False):
         """The same for int16 PCM (at3phip_encode_frames_tonal_short): the frames of encode_frames_tonal() on pcm / 32768."""
-        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr, _tone_flags(gated, shared) | _alloc_flag(adaptive))
+        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr, _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse))
 
-    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False, adaptive=False):
+    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False, adaptive=False, sparse=False):
         """Device-resident float32 PCM / frames; ordering and what stays untouched until sync() as in encode_frames_device."""
-        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared) | _alloc_flag(adaptive))
+        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse))
 
-    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False, adaptive=False):
+    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False, adaptive=False, sparse=False):
         """Device-resident int16 PCM / frames, as encode_frames_tonal_device."""
-        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared) | _alloc_flag(adaptive))
+        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse))
 
-    def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, adaptive=False):
+    def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, adaptive=False, sparse=False):
         """asynchronous=True only queues the call (AT3HIP_ASYNC): sync() before the frames are read, and both buffers stay
         untouched until then. The context's streams are non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): they wait for no
         other stream, so whatever produces the PCM must be complete before the call."""
-        self.encode_frames_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _alloc_flag(adaptive))
+        self.encode_frames_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _alloc_flag(adaptive, sparse))
 
-    def encode_frames_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, adaptive=False):
+    def encode_frames_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, adaptive=False, sparse=False):
         """Device-resident int16 PCM / frames (raw pointers; the PCM needs only 2-byte alignment). Stream ordering and what
         stays untouched until sync() as in encode_frames_device."""
-        self.encode_frames_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _alloc_flag(adaptive))
+        self.encode_frames_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _alloc_flag(adaptive, sparse))
 
     def timings(self):
         a, b, w = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()

@@ -14,6 +14,10 @@ namespace {
 #include "at3p_tone_vlc.inc"
 }
 
+// the two unflagged instantiations under the names they are launched by
+constexpr auto k_at3p_write_adaptive = k_at3p_write_adaptive_with<WriteParams>;
+constexpr auto k_at3p_write_adaptive_tonal = k_at3p_write_adaptive_with<WriteParamsTonal>;
+
 // wp: the fixed writer's parameters as at3phip.hip's launch_write fills them; wp.tonal null: the writer without records. The
 // word-length code tables and the frame size travel in the kernel's arguments: nothing is allocated or uploaded for the adaptive
 // path. wp.out is [n_items][frame_bytes].
@@ -40,20 +44,7 @@ __attribute__((visibility("default"))) void launch_write_adaptive(const WritePar
 extern "C" int at3phip_host_allocate_sized(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, int32_t frame_bytes,
                                            uint8_t* wl_out, int32_t* n_units, int32_t* t, int32_t* k)
 {
-    if (!sfi || !bits || !wl_out || !n_units || !t || !k || channels < 1 || channels > 2) return AT3HIP_EINVAL;
-    if (frame_bytes % 8 || frame_bytes > AT3PHIP_FRAME_BYTES ||
-        frame_bytes < (channels == 2 ? AT3PHIP_MIN_FRAME_BYTES_STEREO : AT3PHIP_MIN_FRAME_BYTES_MONO))
-        return AT3HIP_EINVAL;
-    const int size_bits = 8 * frame_bytes - 3;
-    if (tail_bits < 0 || tail_bits > size_bits) return AT3HIP_EINVAL;
-    for (int i = 0; i < 32 * channels; ++i)
-        if (sfi[i] > 63) return AT3HIP_EINVAL;
-    int n = 0, ts = 0, ks = 0;
-    at3p::host_allocate(sfi, bits, channels, tail_bits, size_bits, wl_out, &n, &ts, &ks);
-    *n_units = n;
-    *t = ts;
-    *k = ks;
-    return AT3HIP_OK;
+    return at3p::host_allocate_checked(sfi, bits, channels, tail_bits, frame_bytes, wl_out, n_units, t, k, false);
 }
 
 extern "C" int at3phip_host_allocate(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, uint8_t* wl_out, int32_t* n_units,

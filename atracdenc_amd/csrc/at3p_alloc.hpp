@@ -6,7 +6,13 @@
 // The word lengths are no longer the reference's table, so the word-length section (TWordLenEncoder, at3p_bitstream.cpp:
 // 170-252) is priced and written here and WriteTables::head is not used. Spectra, tail and tonal block go through the fixed
 // writer's emit_chunk, tonal_price and tonal_emit. host_allocate is steps A3-A5 on the host (at3phip_host_allocate).
+//   k_at3p_write_adaptive_sparse, k_at3p_write_adaptive_tonal_sparse  the same two with SPARSE WORD LENGTHS (A3s, A4s, A6s): a unit
+//                                inside the coded range may keep word length 0, and then has no code-table index and no spectrum.
+//                                Instantiations of their own in a translation unit of their own, at3p_sparse.hip: next to the two
+//                                above they change how the compiler inlines the device functions all four share, and with that
+//                                the code of the two above.
 #pragma once
+#include "../../include/at3phip.h"
 #include "at3p_write.hpp"
 
 namespace at3p {
@@ -24,13 +30,38 @@ __host__ __device__ inline int alloc_wl_range(int max_delta) { return max_delta 
 
 // ---- host: steps A3-A5 on a cost table ---------------------------------------------------------------------------------
 // sfi [channels][32], bits [channels][32][8] (entry w = the unit's bits at word length w, entry 0 unused) -> wl [channels][32]
-// (0 at and above N), N, t*, k*; returns Bits(A(t*, k*)). size_bits: the budget of A4, 8 * frame_bytes - 3.
+// (0 at and above N), N, t*, k*; returns Bits(A(t*, k*)). size_bits: the budget of A4, 8 * frame_bytes - 3. sparse: A3s and A4s.
 inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels, int tail_bits, int size_bits, uint8_t* wl_out, int* n_units, int* t_out,
-                         int* k_out)
+                         int* k_out, bool sparse = false)
 {
-    int wl[2][32];
+    int wl[2][32] = {};
     int N = 1, took = 0;
+    auto form_sparse = [&](int t, int k) {   // A3s: every unit is walked, nothing is raised from 0 to 1, N follows the raise
+        int top = -1;
+        took = 0;
+        for (int qu = 0, left = k; qu < 32; ++qu)
+            for (int ch = 0; ch < channels; ++ch) {
+                const int w0 = alloc_want(sfi[ch * 32 + qu], t), up = alloc_want(sfi[ch * 32 + qu], t - 1);
+                wl[ch][qu] = w0;
+                if (left > 0 && up > w0) {
+                    wl[ch][qu] = up;
+                    --left;
+                    ++took;
+                }
+                if (wl[ch][qu]) top = qu;
+            }
+        N = top + 1;
+        if (N == 0) {
+            N = 1;
+            wl[0][0] = 1;
+        }
+        if (N >= 29 && N <= 31) {   // (unit 31 then has 0 in every channel)
+            N = 32;
+            wl[0][31] = 1;
+        }
+    };
     auto form = [&](int t, int k) {   // A(t, k) into wl and N; took: the units that took the t - 1 value
+        if (sparse) return form_sparse(t, k);
         int top = -1;
         for (int qu = 0; qu < 32; ++qu)
             for (int ch = 0; ch < channels; ++ch) {
@@ -69,7 +100,10 @@ inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels,
             }
             const int r = alloc_wl_range(mx), a = r & 3, b = r >> 2, idx = len[b] < len[a] ? b : a;
             total += (ch ? 6 + (AT3P_WL_VLC[idx][(wl[1][0] - wl[0][0]) & 7] >> 12) : 11) + len[idx];
-            for (int qu = 0; qu < N; ++qu) total += bits[(ch * 32 + qu) * 8 + wl[ch][qu]];
+            for (int qu = 0; qu < N; ++qu) {
+                if (wl[ch][qu]) total += bits[(ch * 32 + qu) * 8 + wl[ch][qu]];
+                else total -= (ch && wl[0][qu]) ? 2 : 3;   // A4s (A3 leaves no 0 below N): no index; channel 1's clone flag
+            }
         }
         return total > 0x7fffffffl ? 0x7fffffff : (int)total;
     };
@@ -90,6 +124,26 @@ inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels,
     *t_out = ts;
     *k_out = took;   // k* as reported: a k beyond the units that can take the t - 1 value gives the same allocation
     return count();
+}
+
+// at3phip_host_allocate_sized and at3phip_host_allocate_sparse: the arguments' checks, then host_allocate
+inline int host_allocate_checked(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, int32_t frame_bytes, uint8_t* wl_out,
+                                 int32_t* n_units, int32_t* t, int32_t* k, bool sparse)
+{
+    if (!sfi || !bits || !wl_out || !n_units || !t || !k || channels < 1 || channels > 2) return AT3HIP_EINVAL;
+    if (frame_bytes % 8 || frame_bytes > AT3PHIP_FRAME_BYTES ||
+        frame_bytes < (channels == 2 ? AT3PHIP_MIN_FRAME_BYTES_STEREO : AT3PHIP_MIN_FRAME_BYTES_MONO))
+        return AT3HIP_EINVAL;
+    const int size_bits = 8 * frame_bytes - 3;
+    if (tail_bits < 0 || tail_bits > size_bits) return AT3HIP_EINVAL;
+    for (int i = 0; i < 32 * channels; ++i)
+        if (sfi[i] > 63) return AT3HIP_EINVAL;
+    int n = 0, ts = 0, ks = 0;
+    host_allocate(sfi, bits, channels, tail_bits, size_bits, wl_out, &n, &ts, &ks, sparse);
+    *n_units = n;
+    *t = ts;
+    *k = ks;
+    return AT3HIP_OK;
 }
 
 // ---- device ----------------------------------------------------------------------------------------------------------
@@ -159,22 +213,47 @@ struct AllocEval {
     int wl, N, idx0, idx1, sum0, sum1, total;
     int delta, len;       // the lane's delta & 7 and its code's length (0: the lane writes no code)
 };
+// kSparse: A3s and A4s (SPARSE WORD LENGTHS). The "up" ballot is over all active lanes, N is the highest lane whose word length is
+// non-zero after the raise, lane 0 (unit 0 of channel 0) carries the empty frame and lane 62 (unit 31 of channel 0) the step from
+// 29..31 to 32; the code-table section counts 3 bits per non-zero unit and a clone flag per odd lane with 0 whose even neighbour is
+// non-zero. s_B[..][0] must read as 0.
+template <bool kSparse>
 __device__ __forceinline__ AllocEval alloc_eval(int t, int k, int sfi, bool act, int lane, int nch, const uint16_t* s_B, const uint16_t* s_wlv,
                                                 const uint8_t* s_pw, int tail_bits)
 {
     AllocEval r;
     const int qu = lane >> 1, ch = lane & 1;
     const int w0 = alloc_want(sfi, t), w1 = alloc_want(sfi, t - 1);
-    const unsigned long long has = __ballot(act && w0 >= 1);
-    int N = has ? ((63 - __builtin_clzll(has)) >> 1) + 1 : 1;
-    if (N >= 29 && N <= 31) N = 32;   // the syntax has no 29..31
-    const bool below = act && qu < N;
-    const bool up = below && w1 > w0;
-    const unsigned long long upm = __ballot(up);
-    const int rank = __builtin_popcountll(upm & ((1ull << lane) - 1ull));
-    int wl = (up && rank < k) ? w1 : w0;
-    if (wl == 0) wl = 1;
-    if (!below) wl = 0;
+    int N, wl, ct_less = 0;   // ct_less: what the code-table section has less than 3 bits per unit below N
+    bool below;
+    if constexpr (kSparse) {
+        const bool up = act && w1 > w0;
+        const unsigned long long upm = __ballot(up);
+        const int rank = __builtin_popcountll(upm & ((1ull << lane) - 1ull));
+        wl = !act ? 0 : (up && rank < k) ? w1 : w0;
+        const unsigned long long has = __ballot(wl >= 1);
+        N = has ? ((63 - __builtin_clzll(has)) >> 1) + 1 : 1;
+        if (!has && lane == 0) wl = 1;
+        if (N >= 29 && N <= 31) {   // the syntax has no 29..31; unit 31 then has 0 in every channel
+            N = 32;
+            if (lane == 62) wl = 1;
+        }
+        below = act && qu < N;
+        const unsigned long long nz = __ballot(wl >= 1), zero = __ballot(below && wl == 0);
+        const unsigned long long clone = zero & (nz << 1) & 0xaaaaaaaaaaaaaaaaull;
+        ct_less = 3 * __builtin_popcountll(zero) - __builtin_popcountll(clone);
+    } else {
+        const unsigned long long has = __ballot(act && w0 >= 1);
+        N = has ? ((63 - __builtin_clzll(has)) >> 1) + 1 : 1;
+        if (N >= 29 && N <= 31) N = 32;   // the syntax has no 29..31
+        below = act && qu < N;
+        const bool up = below && w1 > w0;
+        const unsigned long long upm = __ballot(up);
+        const int rank = __builtin_popcountll(upm & ((1ull << lane) - 1ull));
+        wl = (up && rank < k) ? w1 : w0;
+        if (wl == 0) wl = 1;
+        if (!below) wl = 0;
+    }
     // TWordLenEncoder: channel 0 against the previous unit (two lanes down), channel 1 against channel 0 (one lane down)
     const int src = lane - (ch ? 1 : 2);
     const int ref = __builtin_amdgcn_ds_bpermute(4 * (src < 0 ? 0 : src), wl);
@@ -202,16 +281,44 @@ __device__ __forceinline__ AllocEval alloc_eval(int t, int k, int sfi, bool act,
     r.sum1 = (s1b < s1a ? s1b : s1a) + __builtin_amdgcn_readlane(r.len, 1);
     const int bsum = alloc_wave_sum(below ? (int)s_B[(ch * 32 + qu) * 8 + wl] : 0, lane);
     r.total = 6 + 11 + r.sum0 + (nch == 2 ? 6 + r.sum1 : 0) + nch * (2 + 6 * N) + 1 + nch * (4 + 3 * N) + bsum + nch * (int)s_pw[N - 1] + tail_bits;
+    if constexpr (kSparse) r.total -= ct_less;
     r.wl = wl;
     r.N = N;
     r.delta = d & 7;
     return r;
 }
 
+// the parameter types of the sparse instantiations: the fixed writer's, marked
+struct WriteParamsSparse : WriteParams {};
+struct WriteParamsTonalSparse : WriteParamsTonal {};
+template <typename P> struct alloc_is_sparse { static constexpr bool value = false; };
+template <> struct alloc_is_sparse<WriteParamsSparse> { static constexpr bool value = true; };
+template <> struct alloc_is_sparse<WriteParamsTonalSparse> { static constexpr bool value = true; };
+
+// A6s: the scale-factor indices and the code-table section of a sparse frame. Every wavefront forms the section's two ballots for its
+// length, lane = 32 * channel + unit; wavefront 0 writes, a lane's position being the bits of the lanes below it: 3 per non-zero
+// unit, 1 per clone flag. Returns what the section has less than 3 bits per unit below N.
+__device__ __forceinline__ int alloc_sparse_head(uint32_t* s_out, const uint8_t* s_wl, const uint8_t* s_sfi, const uint8_t* s_tabw, int N, int nch,
+                                                 int lane, int wave, int pos_sf, int pos_ct, int limit_bits)
+{
+    const int k = lane >> 5, q = lane & 31;
+    const bool present = k < nch && q < N;
+    const int w = present ? (int)s_wl[lane] : 0;
+    const unsigned long long nz = __ballot(w > 0), cl = __ballot(present && k == 1 && w == 0 && s_wl[q] > 0);
+    if (wave == 0 && present) {
+        frame_put(s_out, pos_sf + k * (2 + 6 * N) + 2 + 6 * q, s_sfi[lane], 6, limit_bits);
+        const unsigned long long lower = (1ull << lane) - 1ull;
+        const int at = pos_ct + 1 + 4 * (k + 1) + 3 * __builtin_popcountll(nz & lower) + __builtin_popcountll(cl & lower);
+        if (w > 0) frame_put(s_out, at, s_tabw[lane * 8 + w], 3, limit_bits);
+        else if ((cl >> lane) & 1ull) frame_put(s_out, at, 1u, 1, limit_bits);   // "do not copy from channel 0"
+    }
+    return 3 * (nch * N - __builtin_popcountll(nz)) - __builtin_popcountll(cl);
+}
+
 template <typename P>
 __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams<P> p)
 {
-    constexpr bool kTonal = P::kTonal;
+    constexpr bool kTonal = P::kTonal, kSparse = alloc_is_sparse<P>::value;
     __shared__ uint32_t s_out[kFrameBytes / 4];
     __shared__ uint32_t s_qbits[2][32][7][8];  // A2: the bits of each unit at each word length under each of its eight tables
     __shared__ uint16_t s_B[2][32][8];         // B[ch][qu][w], entry 0 unused
@@ -336,6 +443,12 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
         (&s_B[0][0][0])[u * 8 + w] = (uint16_t)best;
         (&s_tabw[0][0][0])[u * 8 + w] = (uint8_t)bi;
     }
+    if constexpr (kSparse) {   // a unit at word length 0 has no bits and no table
+        if (tid < 64) {
+            (&s_B[0][0][0])[tid * 8] = 0;
+            (&s_tabw[0][0][0])[tid * 8] = 0;
+        }
+    }
     __syncthreads();
     // ---- the tail's bits (formed once, as in the fixed writer), then A3-A5: every wavefront evaluates its share of the
     //      candidates, lanes are units ----
@@ -356,7 +469,7 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     {
         int tfit = kAllocTMax + 1;
         for (int t = kAllocTMax - wave; t >= kAllocTMin; t -= 4) {   // descending: the last one that fits is the smallest
-            const AllocEval e = alloc_eval(t, 0, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+            const AllocEval e = alloc_eval<kSparse>(t, 0, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
             if (e.total <= size_bits) tfit = t;
         }
         if (lane == 0) s_tfit[wave] = tfit;
@@ -368,7 +481,7 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     {
         int kfit = 0;
         for (int k = wave; k <= kAllocKMax; k += 4) {
-            const AllocEval e = alloc_eval(t_star, k, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+            const AllocEval e = alloc_eval<kSparse>(t_star, k, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
             if (e.total <= size_bits) kfit = k;
         }
         if (lane == 0) s_kfit[wave] = kfit;
@@ -379,7 +492,7 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
         int k_star = 0;
         for (int w = 0; w < 4; ++w)
             if (s_kfit[w] > k_star) k_star = s_kfit[w];
-        const AllocEval e = alloc_eval(t_star, k_star, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+        const AllocEval e = alloc_eval<kSparse>(t_star, k_star, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
         s_wl[lane & 1][lane >> 1] = (uint8_t)e.wl;
         const int incl = at3::wave_inclusive_scan(e.len << (16 * (lane & 1)), lane);
         const int before = ((incl >> (16 * (lane & 1))) & 0xffff) - e.len;
@@ -407,8 +520,9 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     // ---- scale factor indices, code table indices, spectra and power groups per channel, tail: the fixed writer's layout ----
     const int pos_sf = s_pos_sf;
     const int pos_ct = pos_sf + nch * (2 + 6 * N);
-    const int pos_data = pos_ct + 1 + nch * (4 + 3 * N);
-    if (tid < 64) {
+    int pos_data = pos_ct + 1 + nch * (4 + 3 * N);
+    if constexpr (kSparse) pos_data -= alloc_sparse_head(s_out, &s_wl[0][0], &s_sfi[0][0], &s_tabw[0][0][0], N, nch, lane, wave, pos_sf, pos_ct, limit_bits);
+    else if (tid < 64) {
         const int k = tid >> 5, q = tid & 31;
         if (k < nch && q < N) {
             frame_put(s_out, pos_sf + k * (2 + 6 * N) + 2 + 6 * q, s_sfi[k][q], 6, limit_bits);
@@ -416,7 +530,8 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
         }
     }
     if (tid == 64) frame_put(s_out, pos_ct, 1u, 1, limit_bits);   // "use full table"
-    const bool coded = active && qu < N;
+    bool coded = active && qu < N;
+    if constexpr (kSparse) coded = coded && s_wl[ch][qu] > 0;   // a unit at word length 0 prices and emits nothing
     const int wl = coded ? s_wl[ch][qu] : 1;
     const uint32_t d = s_info[wl - 1 + 7 * s_tabw[active ? ch : 0][qu][wl]];
     alloc_quantise(x, s_inv[wl], qv);
@@ -476,8 +591,7 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     if (tid < n_words) dst[tid] = __builtin_bswap32(s_out[tid]);
     if (256 + tid < n_words) dst[256 + tid] = __builtin_bswap32(s_out[256 + tid]);
 }
-// the two instantiations under the names they are launched by
-constexpr auto k_at3p_write_adaptive = k_at3p_write_adaptive_with<WriteParams>;
-constexpr auto k_at3p_write_adaptive_tonal = k_at3p_write_adaptive_with<WriteParamsTonal>;
+// (the instantiations are named where they are launched, at3p_alloc.hip and at3p_sparse.hip: naming one instantiates it, and a
+// translation unit must hold only its own)
 
 }  // namespace at3p

@@ -232,6 +232,10 @@ __device__ __forceinline__ int decp_tonal(MsbReader& b, const uint16_t* tone_vlc
 
 // The frame's syntax (include/at3phip.h, step 1) and its dequantisation (step 2) on one lane; spec (LDS) is zero on entry.
 // With tonal_rec (AT3PHIP_DECODE_TONES) a tonal block is parsed into it, else it rejects the frame.
+// kSparse (AT3PHIP_DECODE_SPARSE): a word length of 0 is a unit without a code-table index and without a spectrum; in channel 1 it
+// carries the "copy from channel 0" flag where channel 0's unit is coded, which must be 1; the highest unit must be coded in some
+// channel. A compile-time parameter: the parse is one lane's serial code and the unflagged one stays what it was.
+template <bool kSparse>
 __device__ __forceinline__ int decp_parse(MsbReader& b, const DecTables* T, int C, float* spec, uint8_t (*wl)[32], uint8_t (*sf)[32],
                                        uint8_t (*tab)[32], uint16_t* winf, const uint16_t* tone_vlc, TonalRec* tonal_rec)
 {
@@ -262,9 +266,13 @@ __device__ __forceinline__ int decp_parse(MsbReader& b, const DecTables* T, int 
         for (int i = 0; i < nqu; ++i) wl[1][i] = (uint8_t)((wl[0][i] + at3::prefix_scan<8>(b, T->wl_vlc[idx], invalid)) & 7);
         DECP_CHK();
     }
-    for (int ch = 0; ch < C; ++ch)
-        for (int i = 0; i < nqu; ++i)
-            if (wl[ch][i] == 0) return kRpBadCode;
+    if constexpr (kSparse) {
+        if (wl[0][nqu - 1] == 0 && wl[C - 1][nqu - 1] == 0) return kRpUnsupported;
+    } else {
+        for (int ch = 0; ch < C; ++ch)
+            for (int i = 0; i < nqu; ++i)
+                if (wl[ch][i] == 0) return kRpBadCode;
+    }
     for (int ch = 0; ch < C; ++ch) {
         if (b.rd(2) != 0) return kRpUnsupported;
         for (int i = 0; i < nqu; ++i) sf[ch][i] = (uint8_t)b.rd(6);
@@ -273,12 +281,27 @@ __device__ __forceinline__ int decp_parse(MsbReader& b, const DecTables* T, int 
     const int full = (int)b.rd(1);
     for (int ch = 0; ch < C; ++ch) {
         if (b.rd(1) != 0 || b.rd(2) != 0 || b.rd(1) != 0) return kRpUnsupported;
-        for (int i = 0; i < nqu; ++i) tab[ch][i] = (uint8_t)b.rd(full + 2);
+        if constexpr (kSparse) {
+            for (int i = 0; i < nqu; ++i) {
+                if (wl[ch][i]) {
+                    tab[ch][i] = (uint8_t)b.rd(full + 2);
+                } else if (ch && wl[0][i]) {
+                    const uint32_t keep = b.rd(1);
+                    DECP_CHK();
+                    if (keep != 1) return kRpUnsupported;
+                }
+            }
+        } else {
+            for (int i = 0; i < nqu; ++i) tab[ch][i] = (uint8_t)b.rd(full + 2);
+        }
         DECP_CHK();
     }
     for (int ch = 0; ch < C; ++ch) {
         float* sp = spec + 2048 * ch;
         for (int qu = 0; qu < nqu; ++qu) {
+            if constexpr (kSparse) {
+                if (wl[ch][qu] == 0) continue;   // the unit's lines stay +0.0f
+            }
             const int w = wl[ch][qu], t = w - 1 + 7 * tab[ch][qu];
             const int gsz = T->spec_tab[t][0] & 15, nc = T->spec_tab[t][0] >> 4;
             const int cbits = T->spec_tab[t][1] & 15, is_signed = T->spec_tab[t][1] >> 4;
@@ -355,74 +378,23 @@ __device__ __forceinline__ int decp_parse(MsbReader& b, const DecTables* T, int 
 
 constexpr int kDecUnpackThreads = 64;   // one wavefront per frame: the parse is one lane, so frames in flight per CU count
 
-// kSized: the frame size is the parameter block's; otherwise it is 2048 and every limit folds to the constant it was before
-// frames had a size (the parse is one lane's serial code, and a limit held in a register instead of an immediate costs it 2 %).
-template <bool kSized>
-__global__ __launch_bounds__(kDecUnpackThreads) void k_at3pd_unpack_with(DecUnpackParams p)
-{
-    constexpr int NT = kDecUnpackThreads;
-    __shared__ uint32_t s_w[512 + 2];                              // the frame, big-endian words, two zero words behind
-    __shared__ __attribute__((aligned(16))) float s_spec[2][2048];   // the dequantised spectra
-    __shared__ __attribute__((aligned(16))) cpx s_f[32 * 64];       // the 16 x C 64-point FFTs
-    __shared__ uint8_t s_wl[2][32], s_sf[2][32], s_tab[2][32];
-    __shared__ uint16_t s_win[2];
-    __shared__ int s_reason;
-    __shared__ TonalRec s_tone;
+// k_at3pd_unpack_with<kSized> and, for AT3PHIP_DECODE_SPARSE, k_at3pd_unpack_sparse_with<kSized>: one body, two parses
+#define DECP_UNPACK_KERNEL k_at3pd_unpack_with
+#define DECP_UNPACK_SPARSE false
+#include "at3p_decode_unpack.inc"
+#undef DECP_UNPACK_KERNEL
+#undef DECP_UNPACK_SPARSE
+#define DECP_UNPACK_KERNEL k_at3pd_unpack_sparse_with
+#define DECP_UNPACK_SPARSE true
+#include "at3p_decode_unpack.inc"
+#undef DECP_UNPACK_KERNEL
+#undef DECP_UNPACK_SPARSE
 
-    const DecTables* T = p.T;
-    const int f = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, C = p.nch;
-    // s_w holds the largest frame; the words behind this frame's are zero and no read reaches them (the reader's limit)
-    const int frame_bytes = kSized ? p.frame_bytes : 2048, n_words = frame_bytes >> 2;
-    const uint8_t* frame = p.frames + ((size_t)s * p.n_frames + f) * (size_t)frame_bytes;
-    for (int i = tid; i < 512 + 2; i += NT) {   // byte loads: a caller's device buffer need not be word-aligned
-        uint32_t w = 0;
-        if (i < n_words)
-            for (int k = 0; k < 4; ++k) w = (w << 8) | frame[4 * i + k];
-        s_w[i] = w;
-    }
-    for (int i = tid; i < 2 * 2048; i += NT) (&s_spec[0][0])[i] = 0.0f;
-    if (tid < 2) s_win[tid] = 0;
-    for (int i = tid; i < kTonalWords; i += NT) ((uint32_t*)&s_tone)[i] = 0u;
-    __syncthreads();
-    if (tid == 0) {
-        MsbReader b(s_w, 8 * frame_bytes);
-        const int why = decp_parse(b, T, C, &s_spec[0][0], s_wl, s_sf, s_tab, s_win, p.tone_vlc, p.tones ? &s_tone : nullptr);
-        s_reason = why;
-        if (why) atomicAdd(&p.rejected[why - 1], 1ull);
-    }
-    __syncthreads();
-    const bool rejected = s_reason != kRpOk;
-    if (tid < C) p.flags[decp_rec(f + 2, s, tid, p.n_streams, C)] = rejected ? (uint16_t)0 : s_win[tid];
-    {   // the frame's tonal record; none for a rejected frame
-        uint32_t* rec = (uint32_t*)decp_tonal_rec(p.tonal, f, s, p.n_streams);
-        for (int i = tid; i < kTonalWords; i += NT) rec[i] = rejected ? 0u : ((const uint32_t*)&s_tone)[i];
-    }
-    // TMIDCT<256> pre-rotation per subband (odd subbands: SwapArray folded into the index), into the FFT's leaf order; a
-    // rejected frame has a zero spectrum
-    const float* cs = T->cs256;
-    for (int j = tid; j < C * 1024; j += NT) {
-        const int ch = j >> 10, band = (j >> 6) & 15, k2 = j & 63, n = 2 * k2;
-        const int a = band & 1 ? 127 - n : n, bb = band & 1 ? n : 127 - n;
-        const float* sp = &s_spec[ch][band * 128];
-        const float r0 = rejected ? 0.0f : sp[a];
-        const float i0 = rejected ? 0.0f : sp[bb];
-        s_f[(ch * 16 + band) * 64 + at3::fft_leaf_pos<64>(k2)] = at3::midct_pre(r0, i0, cs[n], cs[n + 1]);
-    }
-    __syncthreads();
-    at3::fft_lds<64, false>(s_f, 64, 16 * C, T->tw64, tid, NT);
-    // post-rotation (mdct.h): the whole Buf[256] of each subband
-    for (int j = tid; j < C * 1024; j += NT) {
-        const int ch = j >> 10, band = (j >> 6) & 15, k2 = j & 63, n = 2 * k2;
-        float r1, i1;
-        at3::midct_post(s_f[j], cs[n], cs[n + 1], r1, i1);
-        float* o = p.raw + decp_rec(f + 2, s, ch, p.n_streams, C) * 4096 + band * 256;
-        at3::midct_unfold<64>(n, r1, i1, [&](int x, float v) { o[x] = v; });
-    }
-}
+// (the instantiations are named where they are launched, at3phip.hip and at3p_sparse.hip: naming one instantiates it, and a
+// translation unit must hold only its own)
 
-// the two instantiations under the names they are launched by
-constexpr auto k_at3pd_unpack = k_at3pd_unpack_with<false>;
-constexpr auto k_at3pd_unpack_sized = k_at3pd_unpack_with<true>;
+// at3p_sparse.hip needs the unpack kernel alone: what follows are kernels that are no templates and belong to one translation unit.
+#ifndef AT3P_DECODE_UNPACK_ONLY
 
 struct DecSynthParams {
     const DecTables* T;
@@ -577,5 +549,7 @@ __global__ __launch_bounds__(256) void k_at3pd_state(float* raw, uint16_t* flags
             ((uint32_t*)decp_tonal_rec(tonal, k - kTonalCarry, s, n_streams))[i - k * kTonalWords] = s_tone[k][i - k * kTonalWords];
         }
 }
+
+#endif  // AT3P_DECODE_UNPACK_ONLY
 
 }  // namespace at3p

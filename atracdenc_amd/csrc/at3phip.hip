@@ -73,6 +73,9 @@ constexpr auto k_at3p_write_tonal = k_at3p_write_with<WriteParamsTonal>;
 // so that this one's device code stays instruction for instruction what it was; weak, because the stand-alone host programs
 // that link this file without that one (tests/test_owned_alloc_cpu.py) must still link: there the flag is an error.
 __attribute__((weak, visibility("default"))) void launch_write_adaptive(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
+// The same with AT3PHIP_ALLOC_SPARSE (SPARSE WORD LENGTHS): the sparse instantiations, in at3p_sparse.hip for the same reason and weak
+// for the same reason.
+__attribute__((weak, visibility("default"))) void launch_write_adaptive_sparse(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
 }
 
 namespace {
@@ -125,6 +128,16 @@ int check_frame_size(at3phip_ctx* c, uint32_t flags)
     return AT3HIP_OK;
 }
 
+// AT3PHIP_ALLOC_SPARSE on a frame-writing call: only together with AT3PHIP_ALLOC_ADAPTIVE, and only in a build that has the sparse
+// writer. Checked before anything is queued or any state moves.
+int check_sparse(at3phip_ctx* c, uint32_t flags)
+{
+    if (!(flags & AT3PHIP_ALLOC_SPARSE)) return AT3HIP_OK;
+    if (!(flags & AT3PHIP_ALLOC_ADAPTIVE)) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_SPARSE needs AT3PHIP_ALLOC_ADAPTIVE in the same call");
+    if (!launch_write_adaptive_sparse) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_SPARSE: this build has no sparse writer (at3p_alloc.hip, at3p_sparse.hip)");
+    return AT3HIP_OK;
+}
+
 template <typename T>
 int launch_pqf(at3phip_ctx* c, const T* d_pcm, int n_frames, float* d_bands)
 {
@@ -168,7 +181,7 @@ int launch_mdct(at3phip_ctx* c, const float* d_bands, int n_frames, const uint16
 // d_records: the same in device memory, as the tone analysis left them (valid by construction).
 // adaptive: AT3PHIP_ALLOC_ADAPTIVE, the writer of at3p_alloc.hpp.
 int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint16_t* win_flags, uint8_t* d_frames, hipStream_t on = nullptr,
-                 const at3phip_tonal_block* tonal = nullptr, const TonalBlock* d_records = nullptr, bool adaptive = false)
+                 const at3phip_tonal_block* tonal = nullptr, const TonalBlock* d_records = nullptr, bool adaptive = false, bool sparse = false)
 {
     const size_t S = c->cfg.n_streams, C = c->cfg.channels;
     if (!on) on = c->stream;
@@ -190,7 +203,9 @@ int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint1
         d_records = c->d_tonal;
     }
     wp.tonal = d_records;
-    if (adaptive) {
+    if (adaptive && sparse) {
+        launch_write_adaptive_sparse(wp, c->frame_bytes, on);
+    } else if (adaptive) {
         launch_write_adaptive(wp, c->frame_bytes, on);
     } else if (d_records) {
         memcpy(wp.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(wp.tone_vlc));
@@ -471,6 +486,7 @@ int at3phip_write_frames_tonal(at3phip_ctx* c, const float* specs, int32_t n_fra
     if (!c || !specs || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
     if (c->frame_bytes != kFrameBytes)
         if (const int rc = check_frame_size(c, flags)) return rc;
+    if (const int rc = check_sparse(c, flags)) return rc;
     // (The records' contract is all that is checked here at every frame size: the smallest admissible sizes,
     // AT3PHIP_MIN_FRAME_BYTES_*, hold the largest tail a record can give beside one unit per channel, so no record needs a tail check.)
     bool any = false;   // records without a block are the writer without records
@@ -490,7 +506,7 @@ int at3phip_write_frames_tonal(at3phip_ctx* c, const float* specs, int32_t n_fra
     const float* d_specs = (flags & AT3HIP_PCM_ON_DEVICE) ? specs : c->d_specs;
     uint8_t* d_frames = (flags & AT3HIP_OUT_ON_DEVICE) ? frames : c->d_frames;
     const Stage stage = {specs, c->d_specs, items * c->cfg.channels * 2048 * sizeof(float), {{frames, c->d_frames, items * (size_t)c->frame_bytes}}, 2, {&at3phip_ctx::write_ms}};
-    return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames, nullptr, tonal, nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0); });
+    return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames, nullptr, tonal, nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0, (flags & AT3PHIP_ALLOC_SPARSE) != 0); });
 }
 
 }  // extern "C"
@@ -507,6 +523,7 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     if (!c || !pcm || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
     if (c->frame_bytes != kFrameBytes)
         if (const int rc = check_frame_size(c, flags)) return rc;
+    if (const int rc = check_sparse(c, flags)) return rc;
     at3host::DeviceGuard guard(c->device);
     HIPCHK(c, guard.error());
     if constexpr (kTones) {
@@ -544,7 +561,8 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     HIPCHK(c, hipEventRecord(c->ev_specs[par], c->stream));
     HIPCHK(c, hipStreamWaitEvent(ws, c->ev_specs[par], 0));
     if (timed) HIPCHK(c, hipEventRecord(c->ev[4], ws));
-    rc = launch_write(c, d_specs, n_frames, nullptr, d_frames, ws, nullptr, kTones ? c->d_tone_writer[par] : nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0);
+    rc = launch_write(c, d_specs, n_frames, nullptr, d_frames, ws, nullptr, kTones ? c->d_tone_writer[par] : nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0,
+                      (flags & AT3PHIP_ALLOC_SPARSE) != 0);
     if (rc != AT3HIP_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[3], ws));
     if (!(flags & AT3HIP_OUT_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(frames, c->d_frames, items * (size_t)c->frame_bytes, hipMemcpyDeviceToHost, ws));
@@ -734,6 +752,15 @@ int at3phip_host_tables(void* dst, size_t bytes)
 #include "at3_decoder_host.hpp"
 #include "at3p_decode.hpp"
 
+namespace at3p {
+// The unpack kernel's two unflagged instantiations under the names they are launched by (here and not in at3p_decode.hpp, which
+// at3p_sparse.hip includes too).
+constexpr auto k_at3pd_unpack = k_at3pd_unpack_with<false>;
+constexpr auto k_at3pd_unpack_sized = k_at3pd_unpack_with<true>;
+// The unpack kernels of AT3PHIP_DECODE_SPARSE, in at3p_sparse.hip as the sparse writer is; sized: the frame size is not 2048.
+__attribute__((weak, visibility("default"))) void launch_unpack_sparse(const DecUnpackParams& up, bool sized, dim3 grid, hipStream_t on);
+}
+
 static_assert(sizeof(DecTables) == AT3PHIP_DECODER_TABLES_BYTES, "at3phip.h documents the decoder's table block size");
 static_assert(sizeof(DecToneTables) == AT3PHIP_DECODER_TONE_TABLES_BYTES, "at3phip.h documents the tone table block size");
 
@@ -906,7 +933,9 @@ int decp_launch(at3phip_decoder* d, const uint8_t* d_frames, int n_frames, void*
     up.tonal = d->d_tonal;
     up.tone_vlc = d->d_tone_tables->vlc;
     up.tones = tones;
-    if (d->frame_bytes == 2048) hipLaunchKernelGGL(k_at3pd_unpack, dim3((unsigned)F, (unsigned)S), dim3(kDecUnpackThreads), 0, st, up);
+    // (the parse is one lane's serial code: AT3PHIP_DECODE_SPARSE selects instantiations of its own here and is no test in the kernel)
+    if (flags & AT3PHIP_DECODE_SPARSE) launch_unpack_sparse(up, d->frame_bytes != 2048, dim3((unsigned)F, (unsigned)S), st);
+    else if (d->frame_bytes == 2048) hipLaunchKernelGGL(k_at3pd_unpack, dim3((unsigned)F, (unsigned)S), dim3(kDecUnpackThreads), 0, st, up);
     else hipLaunchKernelGGL(k_at3pd_unpack_sized, dim3((unsigned)F, (unsigned)S), dim3(kDecUnpackThreads), 0, st, up);
     HIPCHK(d, hipGetLastError());
     DecSynthParams sp;
@@ -935,7 +964,9 @@ extern "C" {
 
 int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags)
 {
-    return at3host::decode_call(d, frames, n_frames, pcm, flags, AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES, AT3PHIP_DECODE_S16,
+    if (d && (flags & AT3PHIP_DECODE_SPARSE) && !launch_unpack_sparse)
+        return fail(d, AT3HIP_EINVAL, "AT3PHIP_DECODE_SPARSE: this build has no sparse unpack kernels (at3p_sparse.hip)");
+    return at3host::decode_call(d, frames, n_frames, pcm, flags, AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES | AT3PHIP_DECODE_SPARSE, AT3PHIP_DECODE_S16,
                                 d ? (size_t)d->frame_bytes : 0, d ? (size_t)2048 * d->cfg.channels : 0,
                                 [&](const uint8_t* d_frames, void* d_pcm) { return decp_launch(d, d_frames, n_frames, d_pcm, flags); });
 }

@@ -1004,13 +1004,16 @@ public:
     // lengths are chosen on the device, with a host analyser too; the mirror has no allocator of its own.
     // frameBytes: the size of the frames written (at3phip_set_frame_bytes; the caller gives CreateAtrac3PlusOutput the same
     // size). Other than AT3PHIP_FRAME_BYTES it needs `adaptive`: the library refuses the fixed table at any other size.
+    // sparse: with `adaptive`, every such call also carries AT3PHIP_ALLOC_SPARSE (SPARSE WORD LENGTHS): a unit inside the coded range
+    // may keep word length 0. Without `adaptive` it is an error here, as it is one in the library.
     TAt3PEncoder(TCompressedOutputPtr&& out, int channels, int batchFrames = 64, int deviceId = 0, TAt3PSettings settings = TAt3PSettings(),
                  IAt3PGhaProcessor* gha = nullptr, bool deviceTones = false, bool deviceGated = false, bool deviceShared = false,
-                 bool adaptive = false, int frameBytes = AT3PHIP_FRAME_BYTES)
+                 bool adaptive = false, int frameBytes = AT3PHIP_FRAME_BYTES, bool sparse = false)
         : Out(std::move(out)), Channels((size_t)channels), BatchFrames(batchFrames), FrameFloats((size_t)AT3PHIP_FRAME * (size_t)channels),
           Settings(settings), Gha(gha), DeviceTones(deviceTones), ToneFlags((deviceGated ? AT3PHIP_TONES_GATED : 0u) | (deviceShared ? AT3PHIP_TONES_SHARED : 0u)),
-          AllocFlag(adaptive ? AT3PHIP_ALLOC_ADAPTIVE : 0u), FrameBytes((size_t)frameBytes)
+          AllocFlag((adaptive ? AT3PHIP_ALLOC_ADAPTIVE : 0u) | (sparse ? AT3PHIP_ALLOC_SPARSE : 0u)), FrameBytes((size_t)frameBytes)
     {
+        if (sparse && !adaptive) throw std::invalid_argument("TAt3PEncoder: sparse needs adaptive");
         if (deviceTones && gha) throw std::invalid_argument("TAt3PEncoder: deviceTones takes no host analyser");
         if (deviceGated && !deviceTones) throw std::invalid_argument("TAt3PEncoder: deviceGated needs deviceTones");
         if (deviceShared && !deviceTones) throw std::invalid_argument("TAt3PEncoder: deviceShared needs deviceTones");
@@ -1179,7 +1182,7 @@ private:
     IAt3PGhaProcessor* const Gha;                 // not owned; null: the analysis finds nothing
     const bool DeviceTones;                       // the analysis runs on the GPU
     const uint32_t ToneFlags;                     // and with these flags (AT3PHIP_TONES_GATED, AT3PHIP_TONES_SHARED)
-    const uint32_t AllocFlag;                     // AT3PHIP_ALLOC_ADAPTIVE or 0, on every frame-writing call
+    const uint32_t AllocFlag;                     // AT3PHIP_ALLOC_ADAPTIVE (| AT3PHIP_ALLOC_SPARSE) or 0, on every frame-writing call
     const size_t FrameBytes;                      // the context's frame size
     std::vector<float> PrevBuf, CurBuf, RawCur;   // [C][16][128] / [C][2048]: TChannelCtx's PrevBuf, CurBuf and RawCurBuf
     at3phip_tonal_block Delay{};                  // `delay`: the block the next call writes

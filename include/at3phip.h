@@ -368,6 +368,44 @@ uint32_t at3phip_host_tone_flags(void);
  * symbol at3phip_host_allocate takes the flag. */
 #define AT3PHIP_ALLOC_ADAPTIVE 128u
 
+/* SPARSE WORD LENGTHS (AT3PHIP_ALLOC_SPARSE in `flags` of the same six calls, only together with AT3PHIP_ALLOC_ADAPTIVE; given alone
+ * the call returns AT3HIP_EINVAL with a last-error text before anything is queued: no output byte is written and no stream state
+ * moves. Without the flag nothing above changes: no byte, no PCM sample, no runtime call). A3's last step gives every unit below N at
+ * least one bit, so one step of t that gives any high unit a bit raises N to that unit and pays for every unit below it at once; a
+ * small frame cannot afford the step and leaves its bits unused. With the flag a unit inside the coded range may keep word length
+ * 0. A1, A2, the budget 8 * frame_bytes - 3 and A5's two full scans stand; these steps replace A3, A4 and A6:
+ *  A3s. Candidate A(t, k). want(ch, qu; t) as in A3. All 32 units are walked, qu ascending, channel 0 before channel 1: every unit
+ *      takes its want at t, and the first k units whose want at t - 1 exceeds their want at t take the t - 1 value. No unit is
+ *      raised from 0 to 1 afterwards. N is then 1 plus the highest qu whose word length is >= 1 in any channel: it is computed
+ *      after the k-raise, so k extends the coded range one unit at a time (a flat spectrum, whose wants all step at the same t,
+ *      needs that). If no unit has a word length >= 1, N = 1 and unit 0 of channel 0 takes 1. If N is 29, 30 or 31 it becomes 32
+ *      and, unit 31 then having 0 in every channel, unit 31 of channel 0 takes 1. So the highest coded unit always carries a
+ *      non-zero word length in some channel: "number of units" and "number of units with coded spectrum" never differ, and every
+ *      later section's length is a function of N alone. Units at and above N have 0. k* is reported as in A5: the number of units
+ *      that took the t - 1 value.
+ *  A4s. Bits(A) as A4, except: the code-table section per channel is its 4 header bits plus 3 bits per unit below N whose word
+ *      length is non-zero; in channel 1, one more bit for each unit below N with word length 0 whose channel-0 word length is
+ *      non-zero: the syntax's "copy from channel 0" flag, written as 1 ("do not copy"; 0, copy, is never written). A unit with word
+ *      length 0 contributes no mantissa bits; it still contributes its word-length code and its 6 scale-factor bits (the
+ *      scale-factor mode stays 0, the index written is A1's). Word-length section, power groups and tail as in A4.
+ *  A6s. The frame is A(t*, k*) in the fixed writer's layout with the code-table section as in A4s - per channel the 4 header bits,
+ *      then unit by unit below N either the 3-bit index, or channel 1's flag, or nothing - and no spectrum for a unit at 0.
+ * Where this syntax comes from: it is the layout FFmpeg's ATRAC3plus decoder reads (libavcodec/atrac3plus.c: the code-table index
+ * is read only for units with a non-zero word length, and for a channel-1 unit at 0 under a coded channel-0 unit one bit says
+ * whether channel 0's spectrum is copied), taken from that decoder AS RECALLED: the file was not at hand, the reference carries
+ * only the trace of it (the fields qu_tab_idx / used_quant_units in its atrac3plus.h). This text, not FFmpeg, is what the tests pin.
+ * FFmpeg's other differences from the reference writer (power levels at N <= 2, the window-shape bit count) are left alone.
+ * Smallest sizes: A(63, 0) under A3s is unit 0 of channel 0 at word length 1 and nothing else, which costs no more than A3's one
+ * unit per channel (at most 77 bits in mono and 147 in stereo in front of the tail; tests/test_at3p_sparse_cpu.py re-derives the
+ * bound), so AT3PHIP_MIN_FRAME_BYTES_* and the admissible sizes are unchanged.
+ * Property: at t = -21 every want is 7, so a frame that fits at t = -21 is byte for byte the frame AT3PHIP_ALLOC_ADAPTIVE alone
+ * writes.
+ * Decoding: any decoder of the full syntax; this project's with AT3PHIP_DECODE_SPARSE (decoder section). Out of this definition:
+ * the copy value of the clone flag, scale-factor modes other than 0, noise filling and power compensation in the decoder.
+ * Still ABI 1.6: a library that has the symbol at3phip_host_allocate_sparse takes the flag; a build without the adaptive writer
+ * refuses it as it refuses AT3PHIP_ALLOC_ADAPTIVE. */
+#define AT3PHIP_ALLOC_SPARSE 256u
+
 /* Steps A3-A5 on a caller-supplied cost table, on the host (no GPU needed).
  *   sfi        [channels][32] scale factor indices, each 0..63
  *   bits       [channels][32][8] uint16: entry w = B[ch][qu][w]; entry 0 is not read
@@ -388,6 +426,11 @@ int at3phip_host_allocate(const uint8_t* sfi, const uint16_t* bits, int32_t chan
  * symbol has the frame-size setters below. */
 int at3phip_host_allocate_sized(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, int32_t frame_bytes,
                                 uint8_t* wl_out, int32_t* n_units, int32_t* t, int32_t* k);
+
+/* A3s, A4s and A5 (SPARSE WORD LENGTHS) on a caller-supplied cost table, on the host (no GPU needed): arguments, results and errors
+ * as at3phip_host_allocate_sized; wl_out may hold 0 below N. Entry 0 of `bits` is not read. */
+int at3phip_host_allocate_sparse(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, int32_t frame_bytes,
+                                 uint8_t* wl_out, int32_t* n_units, int32_t* t, int32_t* k);
 
 /* The context's frame size (FRAME SIZE above). Given an admissible size the setter first waits for everything queued on the
  * context, as at3phip_sync does (a queued call still writes frames of the old size), then stores the size: it allocates and
@@ -510,6 +553,16 @@ int at3phip_host_write_tables(void* dst, size_t bytes);
  *      (at3phip_decoder_host_tone_tables).
  *   Stream state gains the last three frames' tonal records; calls without the flag leave records without waves, and step 4b
  *   runs only in calls with the flag. */
+/* SPARSE WORD LENGTHS (AT3PHIP_DECODE_SPARSE in `flags` of at3phip_decode, alone or with the other decoder flags; without it rule 7
+ * stands as written and the rejection counters are what they were). Frames written with AT3PHIP_ALLOC_SPARSE:
+ *   1. Step 1's "a word length of 0 rejects the frame" no longer holds. After the word lengths: a frame whose highest unit
+ *      (nqu - 1) has word length 0 in every channel is unsupported_syntax. The code-table index is read only for units with a
+ *      non-zero word length; for a channel-1 unit with 0 whose channel-0 unit is non-zero, one bit is read in its place, which must
+ *      be 1 (0, "copy channel 0's spectrum", is an element the writer does not emit: unsupported_syntax); any other unit with 0
+ *      has nothing in the section. Spectra are read only for non-zero units.
+ *   2. A unit with word length 0 dequantises to +0.0f in every line.
+ *   Frames without a word length of 0 decode exactly as without the flag. Still ABI 1.6: a library that has the symbol
+ *   at3phip_host_allocate_sparse takes this flag as it takes AT3PHIP_ALLOC_SPARSE. */
 typedef struct at3phip_decoder at3phip_decoder;
 
 typedef struct at3phip_decoder_config {
@@ -526,6 +579,7 @@ const char* at3phip_decoder_last_error(const at3phip_decoder* dec);
 
 #define AT3PHIP_DECODE_S16 8u   /* the bit of AT3HIP_DECODE_S16 */
 #define AT3PHIP_DECODE_TONES 16u   /* decode tonal blocks: rule 7 no longer rejects them (TONAL BLOCKS below) */
+#define AT3PHIP_DECODE_SPARSE 32u  /* decode word length 0 inside the coded range (SPARSE WORD LENGTHS, decoder); alone or with the others */
 
 /*   frames [n_streams][n_frames][frame_bytes] bytes (2048 by default)
  *   pcm    [n_streams][n_frames][2048][channels]: float32, or int16 with AT3PHIP_DECODE_S16
