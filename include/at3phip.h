@@ -320,9 +320,16 @@ uint32_t at3phip_host_tone_flags(void);
  * 28-31 and a quiet frame leaves thousands of bits unused. With the flag the word lengths are chosen per frame to fill it. The
  * syntax is unchanged (TWordLenEncoder codes arbitrary word lengths as deltas) and the decoder below decodes the frames as they
  * are. The reference has no such allocation: this is the project's definition, stated here and nowhere else, pinned bit for bit
- * to the C restatement tests/host/at3p_alloc_cpu.c. A1 is the fixed writer's float code, every decision after it is integer
- * arithmetic, so any float is accepted exactly as by the fixed writer. Frames do not depend on one another: any split of a stream
- * into calls gives the same bytes. Per frame:
+ * to the C restatement tests/host/at3p_alloc_cpu.c, and, for everything but the choice of the allocation, to the reference's own
+ * coders: given the spectra and the word lengths A5 chose, the reference's TWordLenEncoder, TSfIdxEncoder, TQuantUnitsEncoder and
+ * TTonalComponentEncoder under TBitStreamEncoder write the frame of A6 byte for byte and count Bits(A) + 3 bits
+ * (tests/at3p_ref_parts_lib.py puts a configure part of its own, which holds the word lengths, in front of them;
+ * tests/test_at3p_ref_parts_cpu.py compares where the reference is built, tests/golden/at3p_ref_parts.npz keeps frames it wrote
+ * and tests/test_at3p_ref_parts_gpu.py holds the kernels to them). So A1, A2's quantiser and table choice, A4's word-length
+ * section and A6's layout are the reference's; A3 and A5, which word lengths to ask for, are this text's alone. Not pinned to
+ * anything outside the project: what FFmpeg's decoder makes of these frames (no such decoder was at hand). A1 is the fixed
+ * writer's float code, every decision after it is integer arithmetic, so any float is accepted exactly as by the fixed writer.
+ * Frames do not depend on one another: any split of a stream into calls gives the same bytes. Per frame:
  *  A1. Scale exactly as the fixed writer does (TScaler::Scale): sfi[ch][qu] in 0..63 and the scaled values. One step of sfi is a
  *      factor 2^(1/3), so three steps are one mantissa bit.
  *  A2. Cost table. For every channel, unit and word length w = 1..7 the mantissas are rint(v * inv_mant[w]) (the fixed writer's
@@ -394,6 +401,12 @@ uint32_t at3phip_host_tone_flags(void);
  * is read only for units with a non-zero word length, and for a channel-1 unit at 0 under a coded channel-0 unit one bit says
  * whether channel 0's spectrum is copied), taken from that decoder AS RECALLED: the file was not at hand, the reference carries
  * only the trace of it (the fields qu_tab_idx / used_quant_units in its atrac3plus.h). This text, not FFmpeg, is what the tests pin.
+ * What the reference's code does pin (tests/at3p_ref_parts_lib.py, as under ADAPTIVE WORD LENGTHS): the word-length section with
+ * zeros in it (TWordLenEncoder), the scale factor indices, every unit's mantissas, code-table choice and codes
+ * (TQuantUnitsEncoder::TUnit, which cannot be asked for word length 0 and is not), the power groups and the tail; frames put
+ * together from these are the sparse writer's byte for byte and Bits(A) + 3 bits long. What it cannot pin is the code-table section
+ * of A4s / A6s, the one part the reference has no code for: there the comparison's driver writes this text, and a difference would
+ * be settled by this text. And no decoder other than this project's has read these frames: FFmpeg's was not at hand.
  * FFmpeg's other differences from the reference writer (power levels at N <= 2, the window-shape bit count) are left alone.
  * Smallest sizes: A(63, 0) under A3s is unit 0 of channel 0 at word length 1 and nothing else, which costs no more than A3's one
  * unit per channel (at most 77 bits in mono and 147 in stereo in front of the tail; tests/test_at3p_sparse_cpu.py re-derives the
