@@ -205,18 +205,121 @@ __global__ __launch_bounds__(256) void k_loud_sum(BackParams p, const Tables* T,
     if (chain && c0 + lane < n_cf) p.psy[c0 + lane].loud_ch = l;
 }
 
-// Flatness, tonal extraction and TScaler::Scale for kPsyCf channel-frames per workgroup. The per-BFU jobs (21 flatness
-// measures, 32 scale/energy chains per channel-frame) are one lane each and cost as many steps as the BFU has lines, so
-// the jobs of the four channel-frames are dealt to the wavefronts BY LENGTH: a wavefront's pass is as long as its
-// longest job, and a pass over 64-line BFUs next to 16-line ones would idle most lanes most of the time.
+// Flatness, tonal extraction and TScaler::Scale for kPsyCf channel-frames per workgroup. The scale/energy chains (32 per
+// channel-frame) are one lane each and cost as many steps as the BFU has lines, so the jobs of the four channel-frames are
+// dealt to the wavefronts BY LENGTH: a wavefront's pass is as long as its longest job, and a pass over 64-line BFUs next
+// to 16-line ones would idle most lanes most of the time. The flatness sums (21 BFUs per channel-frame) are dealt in chunks
+// of sixteen lines instead (flat_sums).
 constexpr int kPsyCf = 4;
-__device__ __forceinline__ bool psy_flat_job(int wave, int lane, int& k, int& b)
+// The flatness sums of a BFU are dealt out in CHUNKS of sixteen lines, a chunk per lane: four lanes for a 64-line BFU, two for a
+// 32-line one, one for a 16-line one - 160 jobs of sixteen steps for the workgroup's 4 x 21 BFUs (the same deal as the tonal
+// search's below). The lanes of a BFU are neighbours inside one quad of lanes; its first lane (chunk 0) is its LEADER.
+__device__ __forceinline__ bool psy_flat_job(int tid, int& k, int& b, int& chunk, int& nch)
 {
-    if (wave == 0) { k = lane / 3; b = 26 + lane % 3; return lane < 12; }      // 64 lines
-    if (wave == 1) { k = lane / 10; b = 16 + lane % 10; return lane < 40; }    // 32 lines
-    if (wave == 2) { k = lane / 8; b = 8 + lane % 8; return lane < 32; }       // 16 lines
-    k = 0; b = 8;
+    if (tid < 48) { k = tid / 12; b = 26 + (tid % 12) / 4; chunk = tid % 4; nch = 4; return true; }                       // 64 lines
+    if (tid < 128) { k = (tid - 48) / 20; b = 16 + ((tid - 48) % 20) / 2; chunk = (tid - 48) % 2; nch = 2; return true; }   // 32 lines
+    if (tid < 160) { k = (tid - 128) / 8; b = 8 + (tid - 128) % 8; chunk = 0; nch = 1; return true; }                     // 16 lines
+    k = 0; b = 8; chunk = 0; nch = 1;
     return false;
+}
+
+// ---- the two sums of CalcSpectralFlatnessPerBfu over one BFU, split over the lanes of a quad ------------------------------------
+// The reference adds the BFU's energies up as ONE chain in line order (atrac_psy_common.cpp:167-178), in f64. The energies are
+// e = (double)fmaxf(0, x * x) with x * x an f32: non-negative, 24 significant bits. Splitting that chain changes nothing when
+// EVERY addition in EVERY order is exact, and that is decided per BFU from its actual values:
+//   let q = the ulp of the smallest non-zero energy AS AN F32 (2^(E_min - 23); 2^-149 for a denormal). Every energy is a multiple of
+//   q (a larger f32 has a larger ulp, a power-of-two multiple of q; zeros are multiples too), so every partial sum in any order is
+//   a multiple of q. Every energy is below 2^(E_max + 1), so every partial sum of the n lines is below n 2^(E_max + 1). A multiple of
+//   q that does not exceed 2^53 q is an f64 (q >= 2^-149 is far above the f64 underflow range), so for
+//       log2 n + E_max + 1 <= 53 + E_min - 23,   i.e.   E_max - E_min <= 29 - log2 n      (23 for 64 lines, 24 for 32 lines)
+//   no addition rounds: chunk sums added together are the serial chain's sum, bit for bit. (E: the biased exponent field, a
+//   denormal counting as 1. An infinite energy - field 255 - is outside the argument and takes the serial chain.)
+// Where the condition fails (a tone next to silence: a fifth of the BFUs of `tones`, 3 % of white noise) the BFU's leader walks
+// the serial chain as before. The product of the mantissas that the short form of the geometric mean uses is not the reference's
+// computation in the first place: any association of its 63 multiplications stays inside the error bound that guards it (k_psy).
+struct FlatPart {
+    double arith;        // energies added in line order
+    double prod;         // product of the energies' f64 mantissas, each in [0.5, 1), the floor 1e-12f standing in for smaller energies
+    int esum;            // sum of the matching exponents
+    uint32_t lo, hi;     // smallest non-zero and largest f32 bit pattern among the energies (0xffffffff / 0 when all are zero)
+};
+__device__ __forceinline__ void flat_part_add(FlatPart& p, float x)
+{
+    const double floor_ = (double)1e-12f;
+    const float ef = fmaxf(0.0f, x * x);
+    const uint32_t fb = __float_as_uint(ef);
+    p.lo = (fb != 0u && fb < p.lo) ? fb : p.lo;
+    p.hi = fb > p.hi ? fb : p.hi;
+    const double e = (double)ef;
+    p.arith += e;
+    const double d = e > floor_ ? e : floor_;
+    const uint64_t bits = (uint64_t)__double_as_longlong(d);
+    p.esum += (int)((bits >> 52) & 0x7ffu) - 1022;
+    p.prod *= __longlong_as_double((long long)((bits & 0x800fffffffffffffull) | 0x3fe0000000000000ull));
+}
+__device__ __forceinline__ FlatPart flat_part16(const float* sp)   // sixteen lines, 16-byte aligned
+{
+    FlatPart p{0.0, 1.0, 0, 0xffffffffu, 0u};
+#pragma unroll
+    for (int i0 = 0; i0 < 16; i0 += 8) {
+        const float4 xa = *reinterpret_cast<const float4*>(sp + i0), xb = *reinterpret_cast<const float4*>(sp + i0 + 4);
+        const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) flat_part_add(p, x[k]);
+    }
+    return p;
+}
+template <int CTRL>   // quad_perm: the part of another lane of the quad
+__device__ __forceinline__ FlatPart flat_part_from(const FlatPart& p)
+{
+    auto f64 = [](double v) {
+        const uint64_t b = (uint64_t)__double_as_longlong(v);
+        const uint32_t lo = (uint32_t)AT3_DPP((uint32_t)b, CTRL, false), hi = (uint32_t)AT3_DPP((uint32_t)(b >> 32), CTRL, false);
+        return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+    };
+    return FlatPart{f64(p.arith), f64(p.prod), (int)AT3_DPP(p.esum, CTRL, false), (uint32_t)AT3_DPP(p.lo, CTRL, false), (uint32_t)AT3_DPP(p.hi, CTRL, false)};
+}
+// The order-independence condition above for n = 16 nch lines whose smallest non-zero / largest energies have the bit patterns lo / hi
+__device__ __forceinline__ bool flat_sum_is_order_free(uint32_t lo, uint32_t hi, int nch)
+{
+    if (hi == 0u) return true;   // (all zero)
+    const int e_max = (int)(hi >> 23) > 1 ? (int)(hi >> 23) : 1, e_min = (int)(lo >> 23) > 1 ? (int)(lo >> 23) : 1;
+    const int log2n = nch == 4 ? 6 : (nch == 2 ? 5 : 4);
+    return e_max < 255 && e_max - e_min <= 29 - log2n;
+}
+// Wave-uniform call: every lane passes the first line of ITS chunk (`chunk` of `nch`, nch in {1, 2, 4}; the chunks of a BFU in
+// neighbouring lanes of one quad, chunk 0 first). The leader gets the BFU's sums: arith = what the reference's chain over all
+// 16 nch lines gives, bit for bit; prod, esum for the short form; split = the chunks' sums were added (false: serial chain walked).
+__device__ __forceinline__ void flat_sums(const float* sp, int chunk, int nch, double& arith, double& prod, int& esum, bool& split)
+{
+    FlatPart p = flat_part16(sp);
+    const FlatPart q1 = flat_part_from<0x39>(p), q2 = flat_part_from<0x4E>(p), q3 = flat_part_from<0x93>(p);   // lanes + 1, + 2, + 3 of the quad
+    const bool h1 = nch >= 2, h2 = nch == 4;
+    uint32_t lo = p.lo, hi = p.hi;
+    lo = (h1 && q1.lo < lo) ? q1.lo : lo;
+    lo = (h2 && q2.lo < lo) ? q2.lo : lo;
+    lo = (h2 && q3.lo < lo) ? q3.lo : lo;
+    hi = (h1 && q1.hi > hi) ? q1.hi : hi;
+    hi = (h2 && q2.hi > hi) ? q2.hi : hi;
+    hi = (h2 && q3.hi > hi) ? q3.hi : hi;
+    // (an absent chunk enters as +0.0 / 1.0 / 0: x + 0.0 is x for the non-negative sums here, x * 1.0 is x)
+    double a = p.arith;
+    a += h1 ? q1.arith : 0.0;
+    a += h2 ? q2.arith : 0.0;
+    a += h2 ? q3.arith : 0.0;
+    prod = p.prod * (h1 ? q1.prod : 1.0) * (h2 ? q2.prod : 1.0) * (h2 ? q3.prod : 1.0);
+    esum = p.esum + (h1 ? q1.esum : 0) + (h2 ? q2.esum : 0) + (h2 ? q3.esum : 0);
+    split = nch == 1 || flat_sum_is_order_free(lo, hi, nch);
+    if (chunk == 0 && !split) {   // the reference's chain, as one lane
+        a = 0.0;
+        for (int i0 = 0; i0 < 16 * nch; i0 += 8) {
+            const float4 xa = *reinterpret_cast<const float4*>(sp + i0), xb = *reinterpret_cast<const float4*>(sp + i0 + 4);
+            const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) a += (double)fmaxf(0.0f, x[k] * x[k]);
+        }
+    }
+    arith = a;
 }
 __device__ __forceinline__ bool psy_scale_job(int wave, int lane, int& k, int& b)
 {
@@ -288,15 +391,21 @@ __global__ __launch_bounds__(256) AT3_WAVES_PER_EU(8) void k_psy(BackParams p, c
     if (tid >= 128 && tid < 192) s_scale[tid - 128] = scale_v;
     __syncthreads();
 
-    int fk, fb;
-    const bool flat_job = !p.no_tonal && psy_flat_job(wave, lane, fk, fb) && fk < ncf;
+    // the sums of every BFU, a chunk of sixteen lines per lane (flat_sums above; wave-uniform: a lane without a job reads BFU 8 of
+    // channel-frame 0), then the BFU's leader closes the measure
+    int fk, fb, fchunk, fnch;
+    const bool chunk_job = psy_flat_job(tid, fk, fb, fchunk, fnch);
+    const bool flat_job = !p.no_tonal && chunk_job && fchunk == 0 && fk < ncf;
     float flat = 1.0f;
-    double arith = 0.0;
+    double arith = 0.0, prod = 1.0;
+    int esum = 0;
+    if (!p.no_tonal && wave < 3) {   // (wave-uniform)
+        bool split;
+        flat_sums(s_spec[fk] + bfu_start(fb) + 16 * fchunk, fchunk, fnch, arith, prod, esum, split);
+    }
     bool want_literal = false;
     if (flat_job) {
-        const int b = fb;
-        const float* sp = s_spec[fk];
-        const int start = bfu_start(b), end = bfu_start(b + 1), len = end - start;
+        const int len = 16 * fnch;
         // CalcSpectralFlatnessPerBfu (atrac_psy_common.cpp:158-199): flat = exp(mean(log(max(e, floor)))) / mean(e) in f64
         // with glibc's log and exp, narrowed to f32. Two forms, same bits:
         //  * literal: one restated glibc log per line (at3_libm64.hpp), the reference's ordered sums, the restated exp;
@@ -308,22 +417,7 @@ __global__ __launch_bounds__(256) AT3_WAVES_PER_EU(8) void k_psy(BackParams p, c
         //    1e-15: relative distance below 2e-13. When BOTH ends of [ratio (1 - 1e-12), ratio (1 + 1e-12)] narrow to the
         //    same f32 after the clamp, that f32 is the reference's value; otherwise (about 3 in 100 000 BFUs) the literal
         //    form runs. Any device log / exp within a few hundred ulp serves the short form.
-        double prod = 1.0;
-        int esum = 0;
         const double floor_ = (double)1e-12f;
-        for (int i0 = start; i0 < end; i0 += 8) {
-            const float4 xa = *reinterpret_cast<const float4*>(sp + i0), xb = *reinterpret_cast<const float4*>(sp + i0 + 4);
-            const float ev[8] = {xa.x * xa.x, xa.y * xa.y, xa.z * xa.z, xa.w * xa.w, xb.x * xb.x, xb.y * xb.y, xb.z * xb.z, xb.w * xb.w};
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const double e = (double)fmaxf(0.0f, ev[k]);
-                arith += e;
-                const double d = e > floor_ ? e : floor_;
-                const uint64_t bits = (uint64_t)__double_as_longlong(d);
-                esum += (int)((bits >> 52) & 0x7ffu) - 1022;
-                prod *= __longlong_as_double((long long)((bits & 0x800fffffffffffffull) | 0x3fe0000000000000ull));
-            }
-        }
         arith /= (double)len;
         if (!(arith <= floor_)) {
             const double meanLog = (log(prod) + (double)esum * 0.69314718055994530942) / (double)len;

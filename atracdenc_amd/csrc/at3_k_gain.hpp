@@ -943,13 +943,30 @@ __global__ __launch_bounds__(64) AT3_WAVES_PER_EU(4) void k_gain_analysis1(GainP
     }
 }
 
+// Lane `src`'s value of v (ds_bpermute: every lane names its own source)
+__device__ __forceinline__ float lane_read_f(float v, int src)
+{
+    return __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute(4 * src, (int)__float_as_uint(v)));
+}
+// fmaxf over the 32 lanes of the wavefront's half that contains the lane (every lane gets it): four DPP steps inside the rows of
+// sixteen, one exchange between the two rows. fmaxf keeps the operand that is not a NaN, so the result is the maximum of the
+// non-NaN values in any order (a NaN only when all 32 are).
+__device__ __forceinline__ float half_wave_max(float v, int lane)
+{
+    v = fmaxf(v, __uint_as_float((uint32_t)AT3_DPP(__float_as_uint(v), 0xB1, false)));    // quad_perm [1,0,3,2]
+    v = fmaxf(v, __uint_as_float((uint32_t)AT3_DPP(__float_as_uint(v), 0x4E, false)));    // quad_perm [2,3,0,1]
+    v = fmaxf(v, __uint_as_float((uint32_t)AT3_DPP(__float_as_uint(v), 0x124, false)));   // row_ror:4
+    v = fmaxf(v, __uint_as_float((uint32_t)AT3_DPP(__float_as_uint(v), 0x128, false)));   // row_ror:8
+    return fmaxf(v, lane_read_f(v, lane ^ 16));
+}
+
 // CalcCurve's target for one item: the plateau target (transient_detector.cpp:178-238, 284-297), the mean gain (the quartiles
 // of the micro-chunk values are k_gain_analysis' since round 3: the 256 values no longer cross HBM). 32 lanes per item,
 // eight items per workgroup; items below the 5 % gate have no data and are skipped like k_gain_analysis skipped them.
 __global__ __launch_bounds__(256) void k_gain_tail(GainParams p, int n_items)
 {
-    __shared__ float s_g[8][32], s_f[8][32], s_m[8][32];
-    const int tid = threadIdx.x, grp = tid >> 5, j = tid & 31, half = grp & 1;
+    __shared__ __attribute__((aligned(16))) float s_g[8][32];
+    const int tid = threadIdx.x, grp = tid >> 5, j = tid & 31, half = grp & 1, lane = tid & 63;
     const int nfr = p.n_blocks - p.f0;
     int item = blockIdx.x * 8 + grp;
     const bool valid = item < n_items;
@@ -967,39 +984,47 @@ __global__ __launch_bounds__(256) void k_gain_tail(GainParams p, int n_items)
     asm volatile("" ::"v"(g_j));   // (keeps the second request in front of the gate: the compiler sinks it behind the branch otherwise)
     const bool active = valid && !(hfr < 0.05f);
     if (__ballot(active) == 0ull) return;
-    float* s_gain = s_g[grp];
-    float* s_filt = s_f[grp];
-    float* s_minv = s_m[grp];
     const float in_j = active ? g_j : 0.0f;
-    s_gain[j] = in_j;
-    wave_sync();
-    // plateau target of CalcCurve (transient_detector.cpp:178-238, 284-297) with ballots
+    s_g[grp][j] = in_j;   // (for the ordered sum below: the only values that cross LDS storage)
+    // plateau target of CalcCurve (transient_detector.cpp:178-238, 284-297) with ballots.
+    // The kernel is a chain of latencies, not of work, so the chain is kept short: the neighbours of the median and of the three-window
+    // minimum come through the LDS crossbar (ds_bpermute: no store, no rendezvous), and what the reference's loops over the 32
+    // sub-frames leave behind is taken in closed form - max(0, gains) and max(0, window minima) are order-free (fmaxf drops a NaN
+    // operand wherever it stands, as the loops' `>` and fmaxf do), and a loop that replaces its best on `>` alone ends at the FIRST
+    // sub-frame that holds the maximum: a ballot. (Three store / rendezvous / load round trips and a 32-step loop of dependent
+    // compares before.)
+    const int gl = 32 * half;   // the item's first lane
     float filt_j;
     {
-        const float a = s_gain[j > 0 ? j - 1 : 0], c = s_gain[j < 31 ? j + 1 : 31];
+        const float a = lane_read_f(in_j, gl + (j > 0 ? j - 1 : 0)), c = lane_read_f(in_j, gl + (j < 31 ? j + 1 : 31));
         if (j == 0) filt_j = fmaxf(in_j, c);
         else if (j == 31) filt_j = fmaxf(a, in_j);
         else filt_j = fmaxf(fminf(a, in_j), fminf(fmaxf(a, in_j), c));
     }
-    s_filt[j] = filt_j;
+    const float f1 = lane_read_f(filt_j, gl + (j < 30 ? j + 1 : 31)), f2 = lane_read_f(filt_j, gl + (j < 30 ? j + 2 : 31));
+    const float mv = (j <= 29) ? fminf(fminf(filt_j, f1), f2) : -1.0f;
+    const float maxRaw = fmaxf(0.0f, half_wave_max(in_j, lane));
+    const float bestLevel = fmaxf(0.0f, half_wave_max(mv, lane));
+    const uint32_t at_best = (uint32_t)(__ballot(j <= 29 && mv == bestLevel) >> (32 * half));
+    int bestEnd = at_best ? __builtin_ctz(at_best) + 2 : -1;   // (read only when bestLevel >= 1e-6: then some window holds it)
     wave_sync();
-    s_minv[j] = (j <= 29) ? fminf(fminf(filt_j, s_filt[j < 30 ? j + 1 : 31]), s_filt[j < 30 ? j + 2 : 31]) : -1.0f;
-    wave_sync();
-    float maxRaw = 0.0f, sum = 0.0f, bestLevel = 0.0f;
-    int bestEnd = -1;
-    for (int k = 0; k < 32; ++k) {
-        const float g = s_gain[k];
-        maxRaw = fmaxf(maxRaw, g);
-        sum += g;
-        const float mv = s_minv[k];
-        if (k <= 29 && mv > bestLevel) {
-            bestLevel = mv;
-            bestEnd = k + 2;
+    float sum = 0.0f, last;
+    {
+        const float4* g4 = reinterpret_cast<const float4*>(s_g[grp]);
+        float4 v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = g4[q];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            sum += v[q].x;
+            sum += v[q].y;
+            sum += v[q].z;
+            sum += v[q].w;
         }
+        last = v[7].w;
     }
     const uint32_t ge = (uint32_t)(__ballot(filt_j >= bestLevel) >> (32 * half));
     const uint32_t high = (uint32_t)(__ballot(in_j >= bestLevel * 0.7f) >> (32 * half));
-    const float last = s_gain[31];
     float plateau = 0.0f;
     bool release = false;
     if (!(bestLevel < 1e-6f)) {
@@ -1021,12 +1046,14 @@ __global__ __launch_bounds__(256) void k_gain_tail(GainParams p, int n_items)
 // Context chain (TCurveBuilderCtx): one wavefront per (stream, channel, band<3). Frames with hfr < 0.05 reset
 // LastLevel and leave LastTarget / LastHpfEnergy untouched (atrac3denc.cpp:319-327); otherwise
 // LastHpfEnergy = mean(gain) (:342-346), LastLevel = gain[31], LastTarget = target (transient_detector.cpp:307-310).
-// The lanes fetch the per-frame inputs in parallel, lane 0 walks the chain out of LDS, all lanes store the
-// context each frame starts from.
-constexpr int kScanChunk = 512;
+// The chain has a closed form, so nobody walks it: the level a frame starts from is set by the frame before it alone (its
+// gain[31], or 0 when that frame was below the gate), the target and energy it starts from are those of the LAST frame before
+// it that passed the gate - the highest set bit below the lane in the ballot of passing frames - or, when none did, what the
+// call (or the 64 frames before) left behind. Lane i takes frame i of a run of 64; the inputs of the first run are requested
+// together with the carried state: one round trip to memory, one ballot, three crossbar reads. (One lane used to walk the frames
+// through LDS, 63 dependent steps at the headline size, between two rendezvous.)
 __global__ __launch_bounds__(64) void k_gain_scan(GainParams p, int n_streams)
 {
-    __shared__ float s_hfr[kScanChunk], s_g31[kScanChunk], s_tgt[kScanChunk], s_hpf[kScanChunk];
     const int lane = threadIdx.x;
     const int idx = blockIdx.x;
     if (idx >= n_streams * 6) return;
@@ -1034,39 +1061,29 @@ __global__ __launch_bounds__(64) void k_gain_scan(GainParams p, int n_streams)
     BandState* st = p.state + (size_t)s * 8 + ch * 4 + band;
     float lvl = st->last_level, tgt = st->last_target, hpf = st->last_hpf;
     const int nfr = p.n_blocks - p.f0;
-    for (int base = 0; base < nfr; base += kScanChunk) {
-        const int cnt = (nfr - base < kScanChunk) ? nfr - base : kScanChunk;
-        for (int i = lane; i < cnt; i += 64) {
-            const GainRec* rec = p.rec + (((size_t)s * p.n_blocks + p.f0 + base + i) * 2 + ch) * 3 + band;
-            s_hfr[i] = rec->hfr;
-            s_g31[i] = rec->gain[31];
-            s_tgt[i] = rec->target;
-            s_hpf[i] = rec->cur_hpf;
+    for (int base = 0; base < nfr; base += 64) {
+        const int cnt = (nfr - base < 64) ? nfr - base : 64;
+        const bool in = lane < cnt;
+        GainRec* rec = p.rec + (((size_t)s * p.n_blocks + p.f0 + base + (in ? lane : cnt - 1)) * 2 + ch) * 3 + band;
+        const float h = rec->hfr, g = rec->gain[31], t = rec->target, e = rec->cur_hpf;
+        const unsigned long long pass = __ballot(in && !(h < 0.05f));
+        const unsigned long long below = pass & ((1ull << lane) - 1ull);   // passing frames before this one
+        const int src = below ? 63 - __builtin_clzll(below) : lane;
+        const float gp = lane_read_f(g, lane > 0 ? lane - 1 : 0), tp = lane_read_f(t, src), ep = lane_read_f(e, src);
+        const bool prev_passed = lane > 0 && ((pass >> (lane - 1)) & 1ull);
+        if (in) {   // context before this frame
+            rec->ctx_level = lane == 0 ? lvl : (prev_passed ? gp : 0.0f);
+            rec->ctx_target = below ? tp : tgt;
+            rec->ctx_hpf = below ? ep : hpf;
         }
-        __syncthreads();
-        if (lane == 0) {
-            for (int i = 0; i < cnt; ++i) {
-                const float h = s_hfr[i], g = s_g31[i], t = s_tgt[i], e = s_hpf[i];
-                s_g31[i] = lvl;    // context before this frame
-                s_tgt[i] = tgt;
-                s_hpf[i] = hpf;
-                if (h < 0.05f) {
-                    lvl = 0.0f;
-                } else {
-                    lvl = g;
-                    tgt = t;
-                    hpf = e;
-                }
-            }
+        // what the run leaves behind (wave-uniform)
+        if (pass != 0ull) {
+            const int top = 63 - __builtin_clzll(pass);
+            tgt = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(t), top));
+            hpf = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(e), top));
         }
-        __syncthreads();
-        for (int i = lane; i < cnt; i += 64) {
-            GainRec* rec = p.rec + (((size_t)s * p.n_blocks + p.f0 + base + i) * 2 + ch) * 3 + band;
-            rec->ctx_level = s_g31[i];
-            rec->ctx_target = s_tgt[i];
-            rec->ctx_hpf = s_hpf[i];
-        }
-        __syncthreads();
+        const float g_last = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g), cnt - 1));
+        lvl = ((pass >> (cnt - 1)) & 1ull) ? g_last : 0.0f;
     }
     if (lane == 0) {
         st->last_level = lvl;
@@ -1124,48 +1141,45 @@ __device__ __forceinline__ int grp_readlane_i(int v, int idx, int half)
     return half ? b : a;
 }
 
-struct CurvePts {   // register-resident curve (redundant in every lane of the item)
-    int n;
-    int level[7];
-    int loc[7];
+// Register-resident curve (redundant in every lane of the item), PACKED like a Curve in memory: lo = n | level[i] << 8 (i + 1),
+// hi = loc[i] << 8 i - the form cell_divisors_packed walks. Levels are 0 .. 15, locations 0 .. 31, n <= 7: a byte each. As fifteen
+// ints a curve was fifteen VGPRs, and the kernel keeps two of them (before and after the point-0 logic) across the scoring:
+// thirty registers of its ninety. Inserting or dropping point 0 is a shift of the two words.
+struct CurvePts {
+    uint64_t lo, hi;
+    __device__ __forceinline__ int n() const { return (int)(lo & 0xffu); }
+    __device__ __forceinline__ int level(int i) const { return (int)((lo >> (8 * (i + 1))) & 0xffu); }
+    __device__ __forceinline__ int loc(int i) const { return (int)((hi >> (8 * i)) & 0xffu); }
+    __device__ __forceinline__ void set_n(int n) { lo = (lo & ~0xffull) | (uint64_t)(uint32_t)n; }
 };
 
-// CalcCurveEarlyMismatchScore (atrac3denc.cpp:228-297); in_j / in_next are this lane's gain[j], gain[j+1].
-
 // CalcCurveEarlyMismatchScore (atrac3denc.cpp:259-297) for TWO curves of one item at once (the curve before and after the point-0
-// logic: the reference calls it twice):
-// the two evaluations share every LDS rendezvous and their chains interleave - the kernel's slowest wavefronts are the ones that
-// score, and a wavefront that waits on one dependent chain at a time is what sets the kernel's duration. A's lists live in
-// s_tmpA (128 floats) / s_ptsA, B's in aB (32 floats) + sqB / ltB (32 floats each) / s_ptsB; the weights list is A's.
+// logic: the reference calls it twice); in_j / in_next are this lane's gain[j], gain[j+1].
+// The two evaluations share every LDS rendezvous. A's lists live in s_tmpA (128 floats), B's in aB (32 floats) + sqB / ltB
+// (32 floats each); the weights list of B is the first 32 floats of s_tmpA.
 __device__ __forceinline__ void early_mismatch_score_pair(const Log2fTab* L2, const float* gain_interp, float in_j, float in_next, float target,
-                                                          const CurvePts& cpA, const CurvePts& cpB, float* s_tmpA, uint8_t* s_ptsA,
-                                                          float* aB, float* sqB, float* ltB, uint8_t* s_ptsB, int j, float& scoreA, float& scoreB)
+                                                          const CurvePts& cpA, const CurvePts& cpB, float* s_tmpA,
+                                                          float* aB, float* sqB, float* ltB, int j, int half, float& scoreA, float& scoreB)
 {
     // BuildSampleDivisors restricted to sub-frame j (samples 8j .. 8j+7): level boundaries and ramps are aligned to these cells, so
     // the eight divisors are all 1, all one level, or one running-product ramp (same values as curve_divisor sample by sample). The
-    // point list is packed into two 8-byte words from its registers (static indices) and walked by selects (cell_divisors_packed,
-    // at3_k_frontend.hpp): as a loop with lane conditions over a list in LDS this walk was the slowest part of a scoring wavefront.
+    // packed point list is walked by selects (cell_divisors_packed, at3_k_frontend.hpp): as a loop with lane conditions over a list
+    // in LDS this walk was the slowest part of a scoring wavefront.
     auto cell_div = [&](const CurvePts& cp) -> float {
-        uint64_t lo = (uint64_t)(uint32_t)cp.n, hi = 0;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            lo |= (uint64_t)((uint32_t)cp.level[i] & 0xffu) << (8 * (i + 1));
-            hi |= (uint64_t)((uint32_t)cp.loc[i] & 0xffu) << (8 * i);
-        }
         float d[8];
-        cell_divisors_packed(lo, hi, gain_interp, 8 * j, d);
+        cell_divisors_packed(cp.lo, cp.hi, gain_interp, 8 * j, d);
         float dsum = 0.0f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) dsum += d[k];
         return dsum / 8.0f;
     };
-    (void)s_ptsA; (void)s_ptsB;
     const float divA = cell_div(cpA), divB = cell_div(cpB);
     int maxLocA = 0, maxLocB = 0;
+    const int nA = cpA.n(), nB = cpB.n();
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
-        if (i < cpA.n && cpA.loc[i] > maxLocA) maxLocA = cpA.loc[i];
-        if (i < cpB.n && cpB.loc[i] > maxLocB) maxLocB = cpB.loc[i];
+        if (i < nA && cpA.loc(i) > maxLocA) maxLocA = cpA.loc(i);
+        if (i < nB && cpB.loc(i) > maxLocB) maxLocB = cpB.loc(i);
     }
     int evalA = maxLocA + 3 > 3 ? maxLocA + 3 : 3, evalB = maxLocB + 3 > 3 ? maxLocB + 3 : 3;
     if (evalA > 32) evalA = 32;
@@ -1195,34 +1209,27 @@ __device__ __forceinline__ void early_mismatch_score_pair(const Log2fTab* L2, co
     ltB[j] = j + 1 < evalB ? ltermB : 0.0f;
     s_tmpA[j] = j + 1 < evalB ? w : 0.0f;
     wave_sync();
-    float fitA = 0.0f, leakA = 0.0f, wsumA = 0.0f, fitB = 0.0f, leakB = 0.0f, wsumB = 0.0f;
+    // Six ordered 32-term sums per item. Every lane of the item used to add up all six (192 dependent adds and forty-eight 16-byte
+    // reads per lane, the same in all 32 lanes); now lane c < 6 of the item walks list c alone - the same terms in the same order
+    // from the same +0.0f, 32 adds and eight reads - and the item's lanes fetch the six sums from those lanes.
+    // chain 0: B's weights, 1 .. 3: A's fit, leak, weights (s_tmpA is the four lists in this order), 4: B's fit, 5: B's leak
+    float acc = 0.0f;
     {
-        const float4* a4 = reinterpret_cast<const float4*>(st);
-        const float4* s4 = reinterpret_cast<const float4*>(sqB);
-        const float4* l4 = reinterpret_cast<const float4*>(ltB);
-        const float4* w4 = reinterpret_cast<const float4*>(s_tmpA);
-        // (sixteen terms of each of the six lists per step, the next step's requested ahead by the compiler's schedule: holding all
-        // forty-eight 16-byte words at once cost the kernel a wavefront per SIMD)
+        const int c = j < 6 ? j : 0;
+        const float* list = c < 4 ? s_tmpA + 32 * c : (c == 4 ? sqB : ltB);
+        const float4* l4 = reinterpret_cast<const float4*>(list);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            const float4 va = a4[q], vl = a4[8 + q], vw = a4[16 + q], vb = s4[q], vm = l4[q], vx = w4[q];
-            const float v[4] = {va.x, va.y, va.z, va.w};
-            const float lt[4] = {vl.x, vl.y, vl.z, vl.w};
-            const float ww[4] = {vw.x, vw.y, vw.z, vw.w};
-            const float vB[4] = {vb.x, vb.y, vb.z, vb.w};
-            const float lB[4] = {vm.x, vm.y, vm.z, vm.w};
-            const float wB[4] = {vx.x, vx.y, vx.z, vx.w};
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                fitA += v[t];
-                leakA += lt[t];
-                wsumA += ww[t];
-                fitB += vB[t];
-                leakB += lB[t];
-                wsumB += wB[t];
-            }
+            const float4 v = l4[q];
+            acc += v.x;
+            acc += v.y;
+            acc += v.z;
+            acc += v.w;
         }
     }
+    const float wsumB = grp_readlane_f(acc, 0, half), wsumA = grp_readlane_f(acc, 3, half);
+    float fitA = grp_readlane_f(acc, 1, half), leakA = grp_readlane_f(acc, 2, half);
+    float fitB = grp_readlane_f(acc, 4, half), leakB = grp_readlane_f(acc, 5, half);
     wave_sync();   // the scratch is rewritten by the next user
     fitA /= (float)evalA;
     fitB /= (float)evalB;
@@ -1232,17 +1239,22 @@ __device__ __forceinline__ void early_mismatch_score_pair(const Log2fTab* L2, co
     scoreB = (target <= 1e-9f) ? 0.0f : fitB + 0.25f * leakB;
 }
 
+// A curve leaves as one 16-byte store (the curves' buffer is read in 16-byte words by k_gain_energy_scale and k_mdct_sub too)
+__device__ __forceinline__ void store_curve(Curve* dst, uint64_t lo, uint64_t hi)
+{
+    static_assert(offsetof(Curve, level) == 1 && offsetof(Curve, loc) == 8, "Curve layout");
+    *reinterpret_cast<uint4*>(dst) = uint4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+}
+
 // 256 threads = 8 items per workgroup.
 __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* T, int n_streams)
 {
-    __shared__ float s_in[8][32];
+    __shared__ __attribute__((aligned(16))) float s_in[8][32];
     __shared__ __attribute__((aligned(16))) float s_filt[8][32];   // (after the boundary scores: the paired evaluation's second a-list)
     __shared__ __attribute__((aligned(16))) float s_tmp[8][128];   // per item: 32 floats + three 32-term lists of the early-mismatch score
     __shared__ __attribute__((aligned(16))) int s_tloc[8][32];     // (after the curve points are formed: the paired evaluation's
     __shared__ __attribute__((aligned(16))) int s_tdelta[8][32];   //  second term lists)
     __shared__ int s_tlev[8][32];
-    __shared__ uint8_t s_pts[8][16];  // per item: levels [0..6], locations [8..14] of the curve being scored
-    __shared__ uint8_t s_pts2[8][16]; // the same for the second curve of the paired evaluation
     __shared__ Log2fTab s_l2[4];      // per wavefront: the log2f tables and GainInterpolation, so that the rare long
     __shared__ float s_gi4[4][32];    // path (a few items with curves set the kernel's duration) has no dependent global loads
     const int tid = threadIdx.x;
@@ -1292,17 +1304,7 @@ __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* 
     // An item without curve points after CalcCurve ends as "no_curve" whatever the later stages say
     // (atrac3denc.cpp:395-400), and most items are like that: a wavefront whose two items are both out stops here.
     if (__ballot(active) == 0ull) {
-        if (valid && j == 0) {
-            Curve out;
-            out.pad = 0;
-            out.n = 0;
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                out.level[i] = 0;
-                out.loc[i] = 0;
-            }
-            *dst = out;
-        }
+        if (valid && j == 0) store_curve(dst, 0ull, 0ull);
         return;
     }
     const float intraRatio = maxGain / fmaxf(target, 1e-9f);
@@ -1314,17 +1316,7 @@ __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* 
     // the raw one, so every level stays 4, no transition exists and the items end as "no_curve" (the exit further down) -
     // the rule on stationary material, taken here before the quartile ratios, the chain and the boundary scores are formed.
     if (__ballot(active && j <= 30 && raw != 4) == 0ull) {
-        if (valid && j == 0) {
-            Curve out;
-            out.pad = 0;
-            out.n = 0;
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                out.level[i] = 0;
-                out.loc[i] = 0;
-            }
-            *dst = out;
-        }
+        if (valid && j == 0) store_curve(dst, 0ull, 0ull);
         return;
     }
     int minIdx = 0, maxIdx = 0;
@@ -1360,13 +1352,24 @@ __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* 
     const uint32_t gm = (uint32_t)(nzm >> (32 * half));
     const int targetSf = gm ? 32 - __builtin_clz(gm) : 0;
     // BoundaryTransientScore for loc = j (:255-274)
+    // (the two windows as five reads at clamped indices, asked for together, and selects: a neighbour outside the frame enters
+    // its maximum as +0.0f, which changes no maximum that started at +0.0f. As two loops with lane-dependent bounds this was six
+    // dependent LDS round trips under lane conditions.)
     float bs = 1.0f;
-    if (j >= 1) {
+    {
+        const float* fl = s_filt[grp];
+        const float l3 = fl[j >= 3 ? j - 3 : 0], l2 = fl[j >= 2 ? j - 2 : 0], l1 = fl[j >= 1 ? j - 1 : 0];
+        const float r1 = fl[j < 31 ? j + 1 : 31], r2 = fl[j < 30 ? j + 2 : 31];
         float leftMax = 0.0f, rightMax = 0.0f;
-        for (int i = (j - 3 > 0 ? j - 3 : 0); i < j; ++i) leftMax = fmaxf(leftMax, s_filt[grp][i]);
-        for (int i = j; i < (j + 3 < 32 ? j + 3 : 32); ++i) rightMax = fmaxf(rightMax, s_filt[grp][i]);
+        leftMax = fmaxf(leftMax, j >= 3 ? l3 : 0.0f);
+        leftMax = fmaxf(leftMax, j >= 2 ? l2 : 0.0f);
+        leftMax = fmaxf(leftMax, j >= 1 ? l1 : 0.0f);
+        rightMax = fmaxf(rightMax, filt_j);
+        rightMax = fmaxf(rightMax, j < 31 ? r1 : 0.0f);
+        rightMax = fmaxf(rightMax, j < 30 ? r2 : 0.0f);
         const float eps = 1e-9f;
-        bs = fmaxf((rightMax + eps) / (leftMax + eps), (leftMax + eps) / (rightMax + eps));
+        const float v = fmaxf((rightMax + eps) / (leftMax + eps), (leftMax + eps) / (rightMax + eps));
+        bs = j >= 1 ? v : 1.0f;
     }
     // right-to-left transition scan (:404-450). Sub-frames whose level equals the running `prev` are no-ops, so the
     // scan jumps from one differing sub-frame to the next lower one (ballot + find-first-set) instead of visiting all 31.
@@ -1436,25 +1439,20 @@ __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* 
     wave_sync();
     if (nt > 6) nt = 6;
     CurvePts pts;
-    pts.n = (active && targetSf > 0) ? nt : 0;
+    {
+        const int n = (active && targetSf > 0) ? nt : 0;
+        pts.lo = (uint64_t)(uint32_t)n;
+        pts.hi = 0;
 #pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        pts.level[i] = (i < pts.n) ? s_tlev[grp][i] : 0;
-        pts.loc[i] = (i < pts.n) ? s_tloc[grp][i] : 0;
-    }
-    const bool have = pts.n > 0;   // else "skip: no_curve" (atrac3denc.cpp:395-400)
-    if (__ballot(have) == 0ull) {
-        if (valid && j == 0) {
-            Curve out;
-            out.pad = 0;
-            out.n = 0;
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                out.level[i] = 0;
-                out.loc[i] = 0;
-            }
-            *dst = out;
+        for (int i = 0; i < 6; ++i) {   // (at most six transitions are kept)
+            const int lev = (i < n) ? s_tlev[grp][i] : 0, loc = (i < n) ? s_tloc[grp][i] : 0;
+            pts.lo |= (uint64_t)((uint32_t)lev & 0xffu) << (8 * (i + 1));
+            pts.hi |= (uint64_t)((uint32_t)loc & 0xffu) << (8 * i);
         }
+    }
+    const bool have = pts.n() > 0;   // else "skip: no_curve" (atrac3denc.cpp:395-400)
+    if (__ballot(have) == 0ull) {
+        if (valid && j == 0) store_curve(dst, 0ull, 0ull);
         return;
     }
 
@@ -1467,57 +1465,59 @@ __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* 
         if (ln < 32) s_gi4[wv][ln] = giv;
         wave_sync();
     }
-    if (maxGain < 1e-4f) pts.n = 0;
-    if (hfr < 0.3f) pts.n = 0;
+    // (an emptied curve: every later read of a level or a location is behind a test of n, so the whole curve is cleared)
+    if (maxGain < 1e-4f || hfr < 0.3f) pts.lo = pts.hi = 0;
     const CurvePts before = pts;
     bool changed = false;
     float hpfRmsNextMod = 0.0f;
     bool validMod = false;
     {
-        const int nBefore = (pts.n > 0) ? pts.loc[0] : 32;
+        const int nBefore = (pts.n() > 0) ? pts.loc(0) : 32;
+        // ordered sum of the first nBefore gains: the gains behind them enter as +0.0f (x + 0.0f is x for a sum that started at
+        // +0.0f), eight 16-byte reads asked for together instead of 32 reads and 32 lane conditions
         float sum = 0.0f;
-        for (int sf = 0; sf < 32; ++sf) {   // ordered sum of the first nBefore gains
-            const float v = s_in[grp][sf];
-            if (sf < nBefore) sum += v;
+        const float4* g4 = reinterpret_cast<const float4*>(s_in[grp]);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const float4 v = g4[q];
+            sum += (4 * q < nBefore) ? v.x : 0.0f;
+            sum += (4 * q + 1 < nBefore) ? v.y : 0.0f;
+            sum += (4 * q + 2 < nBefore) ? v.z : 0.0f;
+            sum += (4 * q + 3 < nBefore) ? v.w : 0.0f;
         }
-        if (pts.n > 0 && pts.loc[0] > 0) {
-            hpfRmsNextMod = (sum / (float)nBefore) / gain_level_of(pts.level[0]);
+        if (pts.n() > 0 && pts.loc(0) > 0) {
+            hpfRmsNextMod = (sum / (float)nBefore) / gain_level_of(pts.level(0));
             validMod = true;
-        } else if (pts.n == 0) {
+        } else if (pts.n() == 0) {
             hpfRmsNextMod = sum / 32;
             validMod = true;
         }
     }
     const bool p0ok = validMod && prevTarget > 1e-6f && hpfRmsNextMod > 1e-6f;
     if (p0ok) {
-        const int p0 = relation_to_idx_hdr(prevTarget / hpfRmsNextMod);
+        const int p0 = relation_to_idx_hdr(prevTarget / hpfRmsNextMod);   // 0 .. 15
+        const int n = pts.n();
         int it = -1;
 #pragma unroll
         for (int i = 6; i >= 0; --i)
-            if (i < pts.n && pts.loc[i] == 0) it = i;
+            if (i < n && pts.loc(i) == 0) it = i;
         if (it >= 0) {
-#pragma unroll
-            for (int i = 0; i < 7; ++i)
-                if (i == it && pts.level[i] != p0) {
-                    pts.level[i] = p0;
-                    changed = true;
-                }
-        } else if (p0 != 4 || pts.n > 0) {
-#pragma unroll
-            for (int i = 6; i > 0; --i) {
-                pts.level[i] = pts.level[i - 1];
-                pts.loc[i] = pts.loc[i - 1];
+            if (pts.level(it) != p0) {
+                const int sh = 8 * (it + 1);
+                pts.lo = (pts.lo & ~(0xffull << sh)) | ((uint64_t)(uint32_t)p0 << sh);
+                changed = true;
             }
-            pts.level[0] = p0;
-            pts.loc[0] = 0;
-            pts.n++;
+        } else if (p0 != 4 || n > 0) {
+            // point 0 goes in front: levels and locations move up one byte (n <= 6 here: nothing falls off the end)
+            pts.lo = ((pts.lo & ~0xffull) << 8) | ((uint64_t)(uint32_t)p0 << 8) | (uint64_t)(uint32_t)(n + 1);
+            pts.hi = pts.hi << 8;
             changed = true;
         }
     }
     // both scores are evaluated unconditionally (wave-uniform control flow) and TOGETHER; used only when `changed`
     float scoreBefore, scoreAfter;
-    early_mismatch_score_pair(L2, gi, in_j, in_next, target, before, pts, s_tmp[grp], s_pts[grp], s_filt[grp], reinterpret_cast<float*>(s_tloc[grp]),
-                              reinterpret_cast<float*>(s_tdelta[grp]), s_pts2[grp], j, scoreBefore, scoreAfter);
+    early_mismatch_score_pair(L2, gi, in_j, in_next, target, before, pts, s_tmp[grp], s_filt[grp], reinterpret_cast<float*>(s_tloc[grp]),
+                              reinterpret_cast<float*>(s_tdelta[grp]), j, half, scoreBefore, scoreAfter);
     // (both scores are complete here: left free, the compiler interleaves the scoring with the decision below, and the kernel
     // needs 231 VGPRs - two wavefronts per SIMD instead of five)
     scoreBefore = __uint_as_float((uint32_t)opaque_lane_value((int)__float_as_uint(scoreBefore)));
@@ -1527,8 +1527,8 @@ __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* 
         if (p0ok) {
             const float x = prevTarget / hpfRmsNextMod;
             const float desired = fminf(fmaxf(x, gain_level_of(15)), gain_level_of(0));
-            const float scaleBefore = gain_level_of(before.n == 0 ? 4 : before.level[0]);
-            const float scaleAfter = gain_level_of(pts.n == 0 ? 4 : pts.level[0]);
+            const float scaleBefore = gain_level_of(before.n() == 0 ? 4 : before.level(0));
+            const float scaleAfter = gain_level_of(pts.n() == 0 ? 4 : pts.level(0));
             const float eps = 1e-9f;
             const float errBefore = fabsf(at3_log2f(L2, fmaxf(scaleBefore, eps) / fmaxf(desired, eps)));
             const float errAfter = fabsf(at3_log2f(L2, fmaxf(scaleAfter, eps) / fmaxf(desired, eps)));
@@ -1536,25 +1536,17 @@ __global__ __launch_bounds__(256) void k_gain_curve(GainParams p, const Tables* 
         }
         if (!keepByBoundary && scoreAfter > scoreBefore * (1.0f + 0.02f)) pts = before;
     }
-    if (pts.n >= 2 && pts.loc[0] == 0 && pts.level[0] == pts.level[1]) {
-#pragma unroll
-        for (int i = 1; i < 7; ++i) {
-            pts.level[i - 1] = pts.level[i];
-            pts.loc[i - 1] = pts.loc[i];
-        }
-        pts.n--;
+    if (pts.n() >= 2 && pts.loc(0) == 0 && pts.level(0) == pts.level(1)) {
+        // point 0 is dropped: levels and locations move down one byte
+        pts.lo = ((pts.lo >> 16) << 8) | (uint64_t)(uint32_t)(pts.n() - 1);
+        pts.hi = pts.hi >> 8;
     }
     if (valid && j == 0) {
-        Curve out;
-        out.pad = 0;
-        out.n = (uint8_t)(have ? pts.n : 0);
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            const bool on = have && i < pts.n;
-            out.level[i] = (uint8_t)(on ? pts.level[i] : 0);
-            out.loc[i] = (uint8_t)(on ? pts.loc[i] : 0);
-        }
-        *dst = out;
+        // the curve's sixteen bytes are the two words, with the bytes behind point n - 1 (and the pad) cleared
+        const int n = have ? pts.n() : 0;
+        const uint64_t keep_lo = n >= 7 ? ~0ull : ((1ull << (8 * (n + 1))) - 1ull);
+        const uint64_t keep_hi = (1ull << (8 * (n < 7 ? n : 7))) - 1ull;
+        store_curve(dst, n > 0 ? pts.lo & keep_lo : 0ull, n > 0 ? pts.hi & keep_hi : 0ull);
     }
 }
 

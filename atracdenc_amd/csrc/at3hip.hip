@@ -1360,6 +1360,67 @@ extern "C" __attribute__((visibility("default"))) int at3hip_debug_cell_divisors
     (void)hipFree(d_out);
     return rc;
 }
+
+// SIMT HARNESS BUILDS ONLY: k_psy's split flatness sum (flat_sums, at3_k_backend.hpp) over n BFUs of `len` lines (32 or 64) given as
+// their spectral lines: per BFU the sum flat_sums hands the leader, the reference's chain over the same energies restated as a plain
+// loop, and whether the chunks' sums were added (1) or the serial chain was walked (0). tests/test_flatness_split_simt_harness.py.
+namespace {
+__global__ __launch_bounds__(64) void k_debug_flat_sums(const float* lines, int len, double* out_sum, double* out_chain, int32_t* out_split, int n)
+{
+    __shared__ __attribute__((aligned(16))) float s_x[64 * 16];
+    const int lane = threadIdx.x;
+    const int nch = len / 16, per_wave = 64 / nch;
+    const int first = blockIdx.x * per_wave;
+    for (int i = lane; i < 64 * 16; i += 64) {
+        const int bfu = first + i / len;
+        s_x[i] = bfu < n ? lines[(size_t)bfu * len + i % len] : 0.0f;
+    }
+    __syncthreads();
+    const int chunk = lane % nch;
+    double arith, prod;
+    int esum;
+    bool split;
+    flat_sums(s_x + 16 * lane, chunk, nch, arith, prod, esum, split);
+    const int bfu = first + lane / nch;
+    if (chunk == 0 && bfu < n) {
+        double chain = 0.0;
+        const float* x = s_x + 16 * lane;
+        for (int i = 0; i < len; ++i) chain += (double)fmaxf(0.0f, x[i] * x[i]);
+        out_sum[bfu] = arith;
+        out_chain[bfu] = chain;
+        out_split[bfu] = split ? 1 : 0;
+    }
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("default"))) int at3hip_debug_flat_sums(at3hip_ctx* c, const float* lines, int32_t len, int32_t n, double* out_sum, double* out_chain, int32_t* out_split)
+{
+    if (!c || !lines || (len != 32 && len != 64) || n < 1 || !out_sum || !out_chain || !out_split) return AT3HIP_EINVAL;
+    at3host::DeviceGuard guard(c->device);
+    float* d_x = nullptr;
+    double* d_out = nullptr;
+    int32_t* d_split = nullptr;
+    const size_t xb = (size_t)n * len * sizeof(float), ob = (size_t)n * sizeof(double);
+    if (hipMalloc((void**)&d_x, xb) != hipSuccess || hipMalloc((void**)&d_out, 2 * ob) != hipSuccess || hipMalloc((void**)&d_split, (size_t)n * sizeof(int32_t)) != hipSuccess) {
+        (void)hipFree(d_x);
+        (void)hipFree(d_out);
+        return AT3HIP_EDEVICE;
+    }
+    int rc = AT3HIP_OK;
+    if (hipMemcpy(d_x, lines, xb, hipMemcpyHostToDevice) != hipSuccess) rc = AT3HIP_EDEVICE;
+    if (rc == AT3HIP_OK) {
+        const int per_wave = 64 / (len / 16);
+        hipLaunchKernelGGL(k_debug_flat_sums, dim3((unsigned)((n + per_wave - 1) / per_wave)), dim3(64), 0, c->stream, d_x, (int)len, d_out, d_out + n, d_split, (int)n);
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out_sum, d_out, ob, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out_chain, d_out + n, ob, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out_split, d_split, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = AT3HIP_EDEVICE;
+    }
+    (void)hipFree(d_x);
+    (void)hipFree(d_out);
+    (void)hipFree(d_split);
+    return rc;
+}
 #endif
 
 // ---- decoder (include/at3hip.h, decoder section) -------------------------------------------------------------------------------
