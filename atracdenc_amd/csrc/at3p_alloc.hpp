@@ -11,9 +11,14 @@
 //                                Instantiations of their own in a translation unit of their own, at3p_sparse.hip: next to the two
 //                                above they change how the compiler inlines the device functions all four share, and with that
 //                                the code of the two above.
+//   k_at3p_write_adaptive_with<WriteParamsRd>, <WriteParamsTonalRd>  the sparse two with RATE-DISTORTION WORD LENGTHS (R1-R5): a distortion
+//                                table beside the cost table, every unit's pick per lambda, the scans over j and k beside those over
+//                                t and k, and the guard that keeps the sparse allocation where it has less distortion. at3p_rd.hpp
+//                                holds their arithmetic, at3p_rd.hip instantiates them, for the same reason.
 #pragma once
 #include "../../include/at3phip.h"
 #include "at3p_write.hpp"
+#include "at3p_rd.hpp"
 
 namespace at3p {
 
@@ -27,6 +32,44 @@ __host__ __device__ inline int alloc_want(int sfi, int t)
 }
 // FindBestWlDeltaEncode's range for an OR-accumulated largest delta: first table | last table << 2
 __host__ __device__ inline int alloc_wl_range(int max_delta) { return max_delta >= 3 ? (2 | 3 << 2) : max_delta == 2 ? (1 | 1 << 2) : 0; }
+
+// ---- host: Bits(A) of A4 / A4s for word lengths wl (0 at and above N), and A3s's closing rules --------------------------------
+inline int host_alloc_bits(const int (&wl)[2][32], int N, const uint16_t* bits, int channels, int tail_bits)
+{
+    long total = 6 + tail_bits + channels * (2 + 6 * N) + 1 + channels * (4 + 3 * N) + channels * 4 * AT3P_SB_POWGRPS[AT3P_QU_TO_SB[N - 1]];
+    for (int ch = 0; ch < channels; ++ch) {
+        // (FindBestWlDeltaEncode sums from the list's second entry in both modes: channel 1's first code counts in the
+        // largest delta and in the bits, not in the choice of the table)
+        int len[4] = {0, 0, 0, 0}, mx = 0;
+        for (int qu = ch ? 0 : 1; qu < N; ++qu) {
+            const int d = wl[ch][qu] - (ch ? wl[0][qu] : wl[0][qu - 1]);
+            mx |= d < 0 ? -d : d;
+            if (qu)
+                for (int i = 0; i < 4; ++i) len[i] += AT3P_WL_VLC[i][d & 7] >> 12;
+        }
+        const int r = alloc_wl_range(mx), a = r & 3, b = r >> 2, idx = len[b] < len[a] ? b : a;
+        total += (ch ? 6 + (AT3P_WL_VLC[idx][(wl[1][0] - wl[0][0]) & 7] >> 12) : 11) + len[idx];
+        for (int qu = 0; qu < N; ++qu) {
+            if (wl[ch][qu]) total += bits[(ch * 32 + qu) * 8 + wl[ch][qu]];
+            else total -= (ch && wl[0][qu]) ? 2 : 3;   // A4s (A3 leaves no 0 below N): no index; channel 1's clone flag
+        }
+    }
+    return total > 0x7fffffffl ? 0x7fffffff : (int)total;
+}
+// A3s: N after the raise, the empty frame, the step from 29..31 to 32; top: the highest unit with a non-zero word length, or -1
+inline int host_sparse_close(int (&wl)[2][32], int top)
+{
+    int N = top + 1;
+    if (N == 0) {
+        N = 1;
+        wl[0][0] = 1;
+    }
+    if (N >= 29 && N <= 31) {   // (unit 31 then has 0 in every channel)
+        N = 32;
+        wl[0][31] = 1;
+    }
+    return N;
+}
 
 // ---- host: steps A3-A5 on a cost table ---------------------------------------------------------------------------------
 // sfi [channels][32], bits [channels][32][8] (entry w = the unit's bits at word length w, entry 0 unused) -> wl [channels][32]
@@ -50,15 +93,7 @@ inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels,
                 }
                 if (wl[ch][qu]) top = qu;
             }
-        N = top + 1;
-        if (N == 0) {
-            N = 1;
-            wl[0][0] = 1;
-        }
-        if (N >= 29 && N <= 31) {   // (unit 31 then has 0 in every channel)
-            N = 32;
-            wl[0][31] = 1;
-        }
+        N = host_sparse_close(wl, top);
     };
     auto form = [&](int t, int k) {   // A(t, k) into wl and N; took: the units that took the t - 1 value
         if (sparse) return form_sparse(t, k);
@@ -86,27 +121,7 @@ inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels,
                 if (wl[ch][qu] == 0) wl[ch][qu] = 1;
             }
     };
-    auto count = [&]() {   // Bits(A)
-        long total = 6 + tail_bits + channels * (2 + 6 * N) + 1 + channels * (4 + 3 * N) + channels * 4 * AT3P_SB_POWGRPS[AT3P_QU_TO_SB[N - 1]];
-        for (int ch = 0; ch < channels; ++ch) {
-            // (FindBestWlDeltaEncode sums from the list's second entry in both modes: channel 1's first code counts in the
-            // largest delta and in the bits, not in the choice of the table)
-            int len[4] = {0, 0, 0, 0}, mx = 0;
-            for (int qu = ch ? 0 : 1; qu < N; ++qu) {
-                const int d = wl[ch][qu] - (ch ? wl[0][qu] : wl[0][qu - 1]);
-                mx |= d < 0 ? -d : d;
-                if (qu)
-                    for (int i = 0; i < 4; ++i) len[i] += AT3P_WL_VLC[i][d & 7] >> 12;
-            }
-            const int r = alloc_wl_range(mx), a = r & 3, b = r >> 2, idx = len[b] < len[a] ? b : a;
-            total += (ch ? 6 + (AT3P_WL_VLC[idx][(wl[1][0] - wl[0][0]) & 7] >> 12) : 11) + len[idx];
-            for (int qu = 0; qu < N; ++qu) {
-                if (wl[ch][qu]) total += bits[(ch * 32 + qu) * 8 + wl[ch][qu]];
-                else total -= (ch && wl[0][qu]) ? 2 : 3;   // A4s (A3 leaves no 0 below N): no index; channel 1's clone flag
-            }
-        }
-        return total > 0x7fffffffl ? 0x7fffffff : (int)total;
-    };
+    auto count = [&]() { return host_alloc_bits(wl, N, bits, channels, tail_bits); };   // Bits(A)
     int ts = kAllocTMax + 1, ks = 0;
     for (int t = kAllocTMax; t >= kAllocTMin; --t) {   // every t: the smallest that fits
         form(t, 0);
@@ -217,13 +232,14 @@ struct AllocEval {
 // non-zero after the raise, lane 0 (unit 0 of channel 0) carries the empty frame and lane 62 (unit 31 of channel 0) the step from
 // 29..31 to 32; the code-table section counts 3 bits per non-zero unit and a clone flag per odd lane with 0 whose even neighbour is
 // non-zero. s_B[..][0] must read as 0.
+// alloc_eval_from: the candidate from the lane's two word lengths, w0 the one every unit takes and w1 the one the first k units take
+// whose w1 exceeds their w0 (A3's wants at t and t - 1; RATE-DISTORTION WORD LENGTHS' picks at j and j - 1, at3p_rd.hpp).
 template <bool kSparse>
-__device__ __forceinline__ AllocEval alloc_eval(int t, int k, int sfi, bool act, int lane, int nch, const uint16_t* s_B, const uint16_t* s_wlv,
-                                                const uint8_t* s_pw, int tail_bits)
+__device__ __forceinline__ AllocEval alloc_eval_from(int w0, int w1, int k, bool act, int lane, int nch, const uint16_t* s_B, const uint16_t* s_wlv,
+                                                     const uint8_t* s_pw, int tail_bits)
 {
     AllocEval r;
     const int qu = lane >> 1, ch = lane & 1;
-    const int w0 = alloc_want(sfi, t), w1 = alloc_want(sfi, t - 1);
     int N, wl, ct_less = 0;   // ct_less: what the code-table section has less than 3 bits per unit below N
     bool below;
     if constexpr (kSparse) {
@@ -287,6 +303,12 @@ __device__ __forceinline__ AllocEval alloc_eval(int t, int k, int sfi, bool act,
     r.delta = d & 7;
     return r;
 }
+template <bool kSparse>
+__device__ __forceinline__ AllocEval alloc_eval(int t, int k, int sfi, bool act, int lane, int nch, const uint16_t* s_B, const uint16_t* s_wlv,
+                                                const uint8_t* s_pw, int tail_bits)
+{
+    return alloc_eval_from<kSparse>(alloc_want(sfi, t), alloc_want(sfi, t - 1), k, act, lane, nch, s_B, s_wlv, s_pw, tail_bits);
+}
 
 // the parameter types of the sparse instantiations: the fixed writer's, marked
 struct WriteParamsSparse : WriteParams {};
@@ -318,7 +340,8 @@ __device__ __forceinline__ int alloc_sparse_head(uint32_t* s_out, const uint8_t*
 template <typename P>
 __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams<P> p)
 {
-    constexpr bool kTonal = P::kTonal, kSparse = alloc_is_sparse<P>::value;
+    // kRd: RATE-DISTORTION WORD LENGTHS (at3p_rd.hpp), which are sparse frames
+    constexpr bool kTonal = P::kTonal, kRd = alloc_is_rd<P>::value, kSparse = alloc_is_sparse<P>::value || kRd;
     __shared__ uint32_t s_out[kFrameBytes / 4];
     __shared__ uint32_t s_qbits[2][32][7][8];  // A2: the bits of each unit at each word length under each of its eight tables
     __shared__ uint16_t s_B[2][32][8];         // B[ch][qu][w], entry 0 unused
@@ -335,6 +358,11 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     __shared__ uint32_t s_info[56];
     __shared__ uint32_t s_len4[(kLenEntries + 7) / 8];
     __shared__ uint32_t s_rec[kTonal ? kTonalBlockWords : 1];
+    // kRd only (the others never name them): R1's S and D, every unit's pick at j = kRdJMin - 1 .. kRdJMax, R3's scan results
+    __shared__ unsigned long long s_S[kRd ? 2 * 32 * 8 : 1];
+    __shared__ double s_D[kRd ? 2 * 32 * 8 : 1];
+    __shared__ uint8_t s_pick[kRd ? (kRdJCount + 1) * 64 : 1];
+    __shared__ int s_jfit[4], s_krfit[4];
 
     const WriteTables* W = p.W;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -353,6 +381,7 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     if (256 + tid < n_words) s_out[256 + tid] = 0u;
 #pragma unroll
     for (int i = 0; i < 14; ++i) (&s_qbits[0][0][0][0])[tid + 256 * i] = 0u;
+    if constexpr (kRd) s_S[tid] = s_S[256 + tid] = 0ull;
     constexpr int kLenWords = (kLenEntries + 7) / 8, kLenIt = (kLenWords + 255) / 256;
     float x[16];
     {
@@ -422,9 +451,28 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     int qv[16];
     ChunkPricer pricer;
     if (active) {
+        if constexpr (kRd) {   // R1 at w = 0: no mantissa, e = v
+            unsigned long long acc = 0ull;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const float e = x[k] - 0.0f * p.mant[0];
+                acc += rd_dist_u(e * e);
+            }
+            atomicAdd(&s_S[(ch * 32 + qu) * 8], acc);
+        }
 #pragma unroll 1
         for (int w = 1; w <= 7; ++w) {
             alloc_quantise(x, s_inv[w], qv);
+            if constexpr (kRd) {   // R1: the chunk's share of S[ch][qu][w], an integer and so free of the order
+                const float mant = p.mant[w];
+                unsigned long long acc = 0ull;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const float e = x[k] - (float)qv[k] * mant;
+                    acc += rd_dist_u(e * e);
+                }
+                atomicAdd(&s_S[(ch * 32 + qu) * 8 + w], acc);
+            }
             pricer.reset();
             for (int i = 0; i < 8; ++i) atomicAdd(&s_qbits[ch][qu][w - 1][i], (uint32_t)pricer.price(qv, s_info[w - 1 + 7 * i], s_len4));
         }
@@ -449,6 +497,13 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
             (&s_tabw[0][0][0])[tid * 8] = 0;
         }
     }
+    if constexpr (kRd) {   // R1: D = (double)S * G[sfi]
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e = tid + 256 * i;
+            s_D[e] = rd_d(s_S[e], rd_g(s_scale[(&s_sfi[0][0])[e >> 3]]));
+        }
+    }
     __syncthreads();
     // ---- the tail's bits (formed once, as in the fixed writer), then A3-A5: every wavefront evaluates its share of the
     //      candidates, lanes are units ----
@@ -466,6 +521,24 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     }
     const bool u_act = (lane & 1) < nch;
     const int u_sfi = s_sfi[lane & 1][lane >> 1];
+    if constexpr (kRd) {   // R2: the lane's unit's pick at every j the scans ask for, the rows dealt to the wavefronts
+        double D[8];
+        uint16_t B[8];
+#pragma unroll
+        for (int w = 0; w < 8; ++w) {
+            D[w] = s_D[((lane & 1) * 32 + (lane >> 1)) * 8 + w];
+            B[w] = s_B[lane & 1][lane >> 1][w];
+        }
+        for (int i = wave; i <= kRdJCount; i += 4) s_pick[i * 64 + lane] = (uint8_t)(u_act ? rd_pick(D, B, rd_lambda(kRdJMin - 1 + i, s_scale)) : 0);
+        __syncthreads();
+        int jfit = kRdJMax + 1;
+        for (int j = kRdJMax - wave; j >= kRdJMin; j -= 4) {   // R3, as the scan over t below
+            const int row = (j - kRdJMin) * 64 + lane;
+            const AllocEval e = alloc_eval_from<true>(s_pick[row + 64], s_pick[row], 0, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+            if (e.total <= size_bits) jfit = j;
+        }
+        if (lane == 0) s_jfit[wave] = jfit;
+    }
     {
         int tfit = kAllocTMax + 1;
         for (int t = kAllocTMax - wave; t >= kAllocTMin; t -= 4) {   // descending: the last one that fits is the smallest
@@ -486,13 +559,42 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
         }
         if (lane == 0) s_kfit[wave] = kfit;
     }
+    [[maybe_unused]] int j_row = 0;   // j* as the row of its picks at j* - 1
+    if constexpr (kRd) {
+        int j_star = kRdJMax;   // (nothing fits: a caller's table only)
+        for (int w = 0; w < 4; ++w)
+            if (s_jfit[w] < j_star) j_star = s_jfit[w];
+        j_row = (j_star - kRdJMin) * 64 + lane;
+        int kfit = 0;
+        for (int k = wave; k <= kAllocKMax; k += 4) {
+            const AllocEval e = alloc_eval_from<true>(s_pick[j_row + 64], s_pick[j_row], k, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+            if (e.total <= size_bits) kfit = k;
+        }
+        if (lane == 0) s_krfit[wave] = kfit;
+    }
     __syncthreads();
     // ---- A6: the frame's first bits, the unit count and the word-length section, by wavefront 0 ----
     if (wave == 0) {
         int k_star = 0;
         for (int w = 0; w < 4; ++w)
             if (s_kfit[w] > k_star) k_star = s_kfit[w];
-        const AllocEval e = alloc_eval<kSparse>(t_star, k_star, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+        AllocEval e = alloc_eval<kSparse>(t_star, k_star, u_sfi, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+        if constexpr (kRd) {   // R4: R(j*, k*) unless its distortion exceeds that of A(t*, k*), the sparse frame in e
+            int kr_star = 0;
+            for (int w = 0; w < 4; ++w)
+                if (s_krfit[w] > kr_star) kr_star = s_krfit[w];
+            const AllocEval r = alloc_eval_from<true>(s_pick[j_row + 64], s_pick[j_row], kr_star, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+            double t_a = 0.0, t_r = 0.0;   // T: the serial sums in the order of the walk, the same in every lane
+#pragma unroll
+            for (int u = 0; u < 64; ++u) {
+                const int wa = __builtin_amdgcn_readlane(e.wl, u), wr = __builtin_amdgcn_readlane(r.wl, u);
+                if ((u & 1) < nch) {
+                    t_a += s_D[((u & 1) * 32 + (u >> 1)) * 8 + wa];
+                    t_r += s_D[((u & 1) * 32 + (u >> 1)) * 8 + wr];
+                }
+            }
+            if (t_r <= t_a) e = r;
+        }
         s_wl[lane & 1][lane >> 1] = (uint8_t)e.wl;
         const int incl = at3::wave_inclusive_scan(e.len << (16 * (lane & 1)), lane);
         const int before = ((incl >> (16 * (lane & 1))) & 0xffff) - e.len;
@@ -591,7 +693,7 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     if (tid < n_words) dst[tid] = __builtin_bswap32(s_out[tid]);
     if (256 + tid < n_words) dst[256 + tid] = __builtin_bswap32(s_out[256 + tid]);
 }
-// (the instantiations are named where they are launched, at3p_alloc.hip and at3p_sparse.hip: naming one instantiates it, and a
+// (the instantiations are named where they are launched, at3p_alloc.hip, at3p_sparse.hip and at3p_rd.hip: naming one instantiates it, and a
 // translation unit must hold only its own)
 
 }  // namespace at3p

@@ -76,6 +76,8 @@ __attribute__((weak, visibility("default"))) void launch_write_adaptive(const Wr
 // The same with AT3PHIP_ALLOC_SPARSE (SPARSE WORD LENGTHS): the sparse instantiations, in at3p_sparse.hip for the same reason and weak
 // for the same reason.
 __attribute__((weak, visibility("default"))) void launch_write_adaptive_sparse(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
+// And with AT3PHIP_ALLOC_RD (RATE-DISTORTION WORD LENGTHS): at3p_rd.hip, as the two above.
+__attribute__((weak, visibility("default"))) void launch_write_adaptive_rd(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
 }
 
 namespace {
@@ -130,8 +132,14 @@ int check_frame_size(at3phip_ctx* c, uint32_t flags)
 
 // AT3PHIP_ALLOC_SPARSE on a frame-writing call: only together with AT3PHIP_ALLOC_ADAPTIVE, and only in a build that has the sparse
 // writer. Checked before anything is queued or any state moves.
+// AT3PHIP_ALLOC_RD: only together with both, and only in a build that has the rate-distortion writer.
 int check_sparse(at3phip_ctx* c, uint32_t flags)
 {
+    if (flags & AT3PHIP_ALLOC_RD) {
+        if ((flags & (AT3PHIP_ALLOC_ADAPTIVE | AT3PHIP_ALLOC_SPARSE)) != (AT3PHIP_ALLOC_ADAPTIVE | AT3PHIP_ALLOC_SPARSE))
+            return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_RD needs AT3PHIP_ALLOC_ADAPTIVE and AT3PHIP_ALLOC_SPARSE in the same call");
+        if (!launch_write_adaptive_rd) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_RD: this build has no rate-distortion writer (at3p_rd.hip)");
+    }
     if (!(flags & AT3PHIP_ALLOC_SPARSE)) return AT3HIP_OK;
     if (!(flags & AT3PHIP_ALLOC_ADAPTIVE)) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_SPARSE needs AT3PHIP_ALLOC_ADAPTIVE in the same call");
     if (!launch_write_adaptive_sparse) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_SPARSE: this build has no sparse writer (at3p_alloc.hip, at3p_sparse.hip)");
@@ -181,7 +189,7 @@ int launch_mdct(at3phip_ctx* c, const float* d_bands, int n_frames, const uint16
 // d_records: the same in device memory, as the tone analysis left them (valid by construction).
 // adaptive: AT3PHIP_ALLOC_ADAPTIVE, the writer of at3p_alloc.hpp.
 int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint16_t* win_flags, uint8_t* d_frames, hipStream_t on = nullptr,
-                 const at3phip_tonal_block* tonal = nullptr, const TonalBlock* d_records = nullptr, bool adaptive = false, bool sparse = false)
+                 const at3phip_tonal_block* tonal = nullptr, const TonalBlock* d_records = nullptr, bool adaptive = false, bool sparse = false, bool rd = false)
 {
     const size_t S = c->cfg.n_streams, C = c->cfg.channels;
     if (!on) on = c->stream;
@@ -203,7 +211,9 @@ int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint1
         d_records = c->d_tonal;
     }
     wp.tonal = d_records;
-    if (adaptive && sparse) {
+    if (adaptive && sparse && rd) {
+        launch_write_adaptive_rd(wp, c->frame_bytes, on);
+    } else if (adaptive && sparse) {
         launch_write_adaptive_sparse(wp, c->frame_bytes, on);
     } else if (adaptive) {
         launch_write_adaptive(wp, c->frame_bytes, on);
@@ -506,7 +516,7 @@ int at3phip_write_frames_tonal(at3phip_ctx* c, const float* specs, int32_t n_fra
     const float* d_specs = (flags & AT3HIP_PCM_ON_DEVICE) ? specs : c->d_specs;
     uint8_t* d_frames = (flags & AT3HIP_OUT_ON_DEVICE) ? frames : c->d_frames;
     const Stage stage = {specs, c->d_specs, items * c->cfg.channels * 2048 * sizeof(float), {{frames, c->d_frames, items * (size_t)c->frame_bytes}}, 2, {&at3phip_ctx::write_ms}};
-    return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames, nullptr, tonal, nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0, (flags & AT3PHIP_ALLOC_SPARSE) != 0); });
+    return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames, nullptr, tonal, nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0, (flags & AT3PHIP_ALLOC_SPARSE) != 0, (flags & AT3PHIP_ALLOC_RD) != 0); });
 }
 
 }  // extern "C"
@@ -562,7 +572,7 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     HIPCHK(c, hipStreamWaitEvent(ws, c->ev_specs[par], 0));
     if (timed) HIPCHK(c, hipEventRecord(c->ev[4], ws));
     rc = launch_write(c, d_specs, n_frames, nullptr, d_frames, ws, nullptr, kTones ? c->d_tone_writer[par] : nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0,
-                      (flags & AT3PHIP_ALLOC_SPARSE) != 0);
+                      (flags & AT3PHIP_ALLOC_SPARSE) != 0, (flags & AT3PHIP_ALLOC_RD) != 0);
     if (rc != AT3HIP_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[3], ws));
     if (!(flags & AT3HIP_OUT_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(frames, c->d_frames, items * (size_t)c->frame_bytes, hipMemcpyDeviceToHost, ws));

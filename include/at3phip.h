@@ -419,6 +419,58 @@ uint32_t at3phip_host_tone_flags(void);
  * refuses it as it refuses AT3PHIP_ALLOC_ADAPTIVE. */
 #define AT3PHIP_ALLOC_SPARSE 256u
 
+/* RATE-DISTORTION WORD LENGTHS (AT3PHIP_ALLOC_RD in `flags` of the same six calls, only together with AT3PHIP_ALLOC_ADAPTIVE and
+ * AT3PHIP_ALLOC_SPARSE, because it needs word length 0; given without either the call returns AT3HIP_EINVAL with a last-error text
+ * before anything is queued: no output byte is written and no stream state moves. Without the flag nothing above changes: no byte, no
+ * PCM sample, no runtime call). A3 asks for a word length from the unit's scale factor, its peak, alone: a unit with one loud line
+ * among quiet ones gets the word length of a flat unit, and the cost table B is used to check a candidate, never to choose one.
+ * With the flag every unit takes the word length that minimises distortion + lambda * bits, lambda is scanned as t is, and the frame is
+ * filled as k fills it. The frames are sparse frames: no syntax changes, and they decode with AT3PHIP_DECODE_SPARSE. This project's
+ * definition, stated here and nowhere else, pinned bit for bit to the C restatement tests/host/at3p_rd_cpu.c. A1, A2, A4s, A6s, the
+ * budget 8 * frame_bytes - 3 and the tail stand; these steps replace A3s and A5:
+ *  R1. Distortion table, integer, order-free. For every channel, unit, word length w = 0..7 and line of the unit, with v A1's scaled
+ *      and clamped value and m A2's mantissa at w (m = 0 at w = 0): e = v - (float)m * atrac3p_mant_tab[w] (a float multiply, then a
+ *      float subtract, each rounded on its own), d = e * e in float, u = (uint64)(d * 0x1p40f) truncated, u = 0 when d is NaN.
+ *      S[ch][qu][w] is the sum of u over the unit's lines: integer addition is exact, so the order of the lines is free (d < 1, so
+ *      S < 2^47). D[ch][qu][w] = (double)S * G[sfi] with G[i] = (double)ScaleTable[i] * (double)ScaleTable[i]: that product of two
+ *      floats is exact in double and S converts exactly, so D is one rounded double multiply. No libm enters.
+ *  R2. Candidate R(j, k). lambda_j = 0x1p40 * G[j mod 3] * 4^floor(j / 3), floor division and a non-negative remainder;
+ *      ScaleTable[i + 3] is exactly 2 ScaleTable[i], so lambda_j = 2^40 G[j] inside 0..63 and continues by exact factors of 4 outside.
+ *      pick(ch, qu; j) is the w in 0..7 with the smallest D[w] + lambda_j * (double)(B[w] + (w > 0 ? 3 : 0)), B[0] = 0, multiply and
+ *      add rounded separately; w is walked ascending and a tie keeps the smaller w. The 3 is the code-table index a non-zero unit pays
+ *      in A4s. All 32 units are walked, qu ascending, channel 0 before channel 1: every unit takes pick(.; j), and the first k units
+ *      whose pick at j - 1 exceeds their pick at j take the j - 1 value. Then A3s's closing rules apply unchanged: N follows the
+ *      raise, an empty frame gives unit 0 of channel 0 word length 1, an N of 29..31 becomes 32 and unit 31 of channel 0 takes 1.
+ *      Bits(R) is A4s. (The raise list is walked by unit, not ordered by distortion gained per bit: the walk by unit is A3s's.)
+ *  R3. Choice, by full scans as in A5. j* is the smallest j in J_MIN..J_MAX = -30..69 whose R(j, 0) fits (J_MAX where none does: a
+ *      caller's table only); k* the largest k in 0..64 whose R(j*, k) fits, reported as the number of units that took the j - 1 value.
+ *      J_MAX makes every unit pick 0 whatever the spectrum: D[0] <= lines * 2^40 * G[sfi] <= lines * 2^40 (G[63] = 1), and a unit of
+ *      `lines` lines costs at least lines / 16 bits at any w > 0 (every one of its 16-line chunks costs at least one bit under every
+ *      code table; tests/test_at3p_rd_cpu.py re-derives that from at3p_vlc.inc), so w > 0 costs at least lambda * (lines / 16 + 3)
+ *      more than w = 0 saves when lambda_j / 2^40 >= lines / (lines / 16 + 3), at most 128 / 11 < 16 = lambda_69 / 2^40
+ *      (lambda_68 / 2^40 is 10.08: 69 is the smallest). So R(69, 0) is A3s's smallest frame, unit 0 of channel 0 at word length 1,
+ *      and fits at every admissible size. (The tables give more: no chunk costs less than 4 bits, which makes 66 the smallest such
+ *      j; 69 follows from the weaker premise and makes the count of j a multiple of 4.) J_MIN = -30: lambda_-30 = 2^-22, a bit then
+ *      costs the squared error of one line that is 2^-11 off at the highest scale factor. It only has to lie below every j* of a
+ *      frame with less room than its spectrum can use: on the project's signals (noise, mix, stress, tones, burst and full-scale
+ *      noise, mono and stereo, 376 to 2048 bytes) the lowest j* of a frame that does not fit at -30 is -10. A frame that fits at
+ *      -30 is written with the picks at -30 - word length 7 wherever a shorter one has 2^-22 more distortion per bit saved, nothing
+ *      for a silent unit - and R4 puts A(t*, k*) in its place where that has less distortion. 100 values of j: the four wavefronts
+ *      of the kernel share the scan evenly.
+ *  R4. Guard. A(t*, k*) of A3s / A5, the frame AT3PHIP_ALLOC_SPARSE alone writes, is formed as well. T(X) is the sum of
+ *      D[ch][qu][wl_X[ch][qu]] over all 32 units of every channel present in the order of the walk, a serial double sum from +0.0
+ *      (units at and above N have word length 0 and count with D[0]). The frame is R(j*, k*) if T(R) <= T(A), else A(t*, k*), byte for
+ *      byte today's sparse frame. Property, exact: the written allocation's T never exceeds the sparse allocation's. T is squared
+ *      error on the spectrum, per frame: it bounds nothing about the time-domain signal after the decoder's overlap.
+ *  R5. Floats outside the domain. A1 is the fixed writer's: an infinite line is clamped to +-0.99999, a NaN line stays NaN. A NaN
+ *      scaled value gives a NaN d at every w and so u = 0: it adds no distortion and never asks for bits. The mantissa of a NaN is
+ *      the conversion tests/host/at3p_alloc_cpu.c documents at quantise(). Every decision after R1's float operations is integer or
+ *      double arithmetic on finite numbers, so any float is accepted, frames do not depend on one another, and no stream affects
+ *      another.
+ * Out of this definition: psychoacoustic weighting (a weight on D is one table from here). Still ABI 1.6: a library that has the
+ * symbol at3phip_host_allocate_rd takes the flag; a build without the rate-distortion writer (at3p_rd.hip) has neither. */
+#define AT3PHIP_ALLOC_RD 512u
+
 /* Steps A3-A5 on a caller-supplied cost table, on the host (no GPU needed).
  *   sfi        [channels][32] scale factor indices, each 0..63
  *   bits       [channels][32][8] uint16: entry w = B[ch][qu][w]; entry 0 is not read
@@ -444,6 +496,14 @@ int at3phip_host_allocate_sized(const uint8_t* sfi, const uint16_t* bits, int32_
  * as at3phip_host_allocate_sized; wl_out may hold 0 below N. Entry 0 of `bits` is not read. */
 int at3phip_host_allocate_sparse(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, int32_t frame_bytes,
                                  uint8_t* wl_out, int32_t* n_units, int32_t* t, int32_t* k);
+
+/* R2-R4 (RATE-DISTORTION WORD LENGTHS) on caller-supplied tables, on the host (no GPU needed): sfi, bits, channels, tail_bits,
+ * frame_bytes, wl_out and n_units as at3phip_host_allocate_sparse; dist [channels][32][8] uint64 is S of R1 (every entry is read,
+ * each at most 2^47). j and k receive j* and k* of R3 whichever allocation is written; chose_rd receives 1 when wl_out is R(j*, k*)
+ * and 0 when the guard of R4 fell back to A(t*, k*). Errors as at3phip_host_allocate_sparse, also for a null dist or chose_rd and
+ * an S above 2^47. */
+int at3phip_host_allocate_rd(const uint8_t* sfi, const uint16_t* bits, const uint64_t* dist, int32_t channels, int32_t tail_bits,
+                             int32_t frame_bytes, uint8_t* wl_out, int32_t* n_units, int32_t* j, int32_t* k, int32_t* chose_rd);
 
 /* The context's frame size (FRAME SIZE above). Given an admissible size the setter first waits for everything queued on the
  * context, as at3phip_sync does (a queued call still writes frames of the old size), then stores the size: it allocates and

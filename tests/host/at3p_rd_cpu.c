@@ -1,0 +1,240 @@
+/* TEST INFRASTRUCTURE ONLY - CPU restatement of the ATRAC3plus adaptive writer with RATE-DISTORTION WORD LENGTHS (include/at3phip.h,
+ * R1-R5). A1, A2, A4s, the frame's layout (A6s) and the decoder are tests/host/at3p_sparse_cpu.c's, included here as that file
+ * includes its predecessors; R1-R4, the distortion table, the candidates, the two scans and the guard, are written out here in
+ * plain scalar C from the header's text. Compiled by the tests with gcc -O2 -fPIC -ffp-contract=off -fno-fast-math. */
+#include "at3p_sparse_cpu.c"
+
+#define J_MIN (-30)
+#define J_MAX 69
+
+/* R1: S[ch][qu][w], from A1's scaled values (values [channels][2048]) */
+static void rd_dist_table(const float* values, int channels, uint64_t* dist)
+{
+    int mant[128];
+    for (int ch = 0; ch < channels; ++ch)
+        for (int qu = 0; qu < 32; ++qu) {
+            const int start = kQuStart[qu], n = kSpecsPerBlock[qu];
+            const float* v = values + ch * 2048 + start;
+            for (int w = 0; w < 8; ++w) {
+                if (w) r_quantise(v, n, w, mant);
+                else memset(mant, 0, sizeof(mant));
+                uint64_t S = 0;
+                for (int i = 0; i < n; ++i) {
+                    const float q = (float)mant[i] * AT3P_MANT[w];
+                    const float e = v[i] - q;
+                    const float d = e * e;
+                    if (d == d) S += (uint64_t)(d * 0x1p40f);   /* NaN: u = 0 */
+                }
+                dist[(ch * 32 + qu) * 8 + w] = S;
+            }
+        }
+}
+
+/* A1 + A2 + R1 of one frame */
+int at3prd_tables(const float* specs, int channels, uint8_t* sfi, uint16_t* bits, uint8_t* tab, uint64_t* dist, float* values_out)
+{
+    float values[2 * 2048];
+    if (at3ps_cost_table(specs, channels, sfi, bits, tab, values) != 0) return -1;
+    rd_dist_table(values, channels, dist);
+    if (values_out) memcpy(values_out, values, sizeof(float) * 2048 * (size_t)channels);
+    return 0;
+}
+
+static double rd_G(int i) { return (double)AT3P_SCALE[i] * (double)AT3P_SCALE[i]; }
+
+/* R2: lambda_j = 2^40 G[j mod 3] 4^floor(j / 3) */
+static double rd_lam(int j)
+{
+    int q = j / 3, r = j % 3;
+    if (r < 0) {
+        r += 3;
+        q -= 1;
+    }
+    return ldexp(rd_G(r), 40 + 2 * q);   /* (exact: a power of two) */
+}
+
+static int rd_pick_w(const uint64_t* S, const uint16_t* B, int sfi, int j)
+{
+    const double lam = rd_lam(j), G = rd_G(sfi);
+    int best = 0;
+    double least = 0;
+    for (int w = 0; w < 8; ++w) {
+        const double D = (double)S[w] * G;
+        const double rate = lam * (double)(w ? B[w] + 3 : 0);
+        const double cost = D + rate;
+        if (w == 0 || cost < least) {
+            least = cost;
+            best = w;
+        }
+    }
+    return best;
+}
+
+/* R2: the candidate R(j, k); returns N, and in *took how many units took the j - 1 value */
+static int rd_candidate(const uint8_t* sfi, const uint16_t* bits, const uint64_t* dist, int channels, int j, int k, uint8_t wl[2][32], int* took)
+{
+    memset(wl, 0, 64);
+    int taken = 0;
+    for (int qu = 0; qu < 32; ++qu)
+        for (int ch = 0; ch < channels; ++ch) {
+            const int u = ch * 32 + qu;
+            const int w0 = rd_pick_w(dist + u * 8, bits + u * 8, sfi[u], j), up = rd_pick_w(dist + u * 8, bits + u * 8, sfi[u], j - 1);
+            wl[ch][qu] = (uint8_t)w0;
+            if (up > w0 && taken < k) {
+                wl[ch][qu] = (uint8_t)up;
+                ++taken;
+            }
+        }
+    if (took) *took = taken;
+    int N = 0;
+    for (int qu = 0; qu < 32; ++qu)
+        for (int ch = 0; ch < channels; ++ch)
+            if (wl[ch][qu] >= 1) N = qu + 1;
+    if (N == 0) {
+        N = 1;
+        wl[0][0] = 1;
+    }
+    if (N >= 29 && N <= 31) {
+        N = 32;
+        if (wl[0][31] == 0 && wl[1][31] == 0) wl[0][31] = 1;
+    }
+    return N;
+}
+
+/* R4: T(X) */
+static double rd_total(const uint8_t* sfi, const uint64_t* dist, int channels, uint8_t wl[2][32])
+{
+    double T = 0.0;
+    for (int qu = 0; qu < 32; ++qu)
+        for (int ch = 0; ch < channels; ++ch) T += (double)dist[(ch * 32 + qu) * 8 + wl[ch][qu]] * rd_G(sfi[ch * 32 + qu]);
+    return T;
+}
+
+typedef struct {
+    int32_t j, k, num_quant_units, bits;   /* j*, k* of R3; N and Bits of the allocation written */
+    int32_t chose_rd, t, k_sparse, pad;    /* R4: 1 = R(j*, k*), 0 = A(t*, k*); t*, k* of the sparse allocation */
+    double T_rd, T_sparse;
+    uint8_t wl[2][32], sfi[2][32], tab[2][32];
+} at3prd_frame_info;
+
+/* R2-R4 on the tables against the budget 8 * frame_bytes - 3; returns Bits of the allocation written. rec (optional): j, k,
+ * chose_rd, t, k_sparse, T_rd and T_sparse are filled. */
+int at3prd_allocate(const uint8_t* sfi, const uint16_t* bits, const uint64_t* dist, int channels, int tail_bits, int frame_bytes, uint8_t* wl_out,
+                    int32_t* n_units, void* rec)
+{
+    const int size_bits = 8 * frame_bytes - 3;
+    uint8_t wl[2][32], wa[2][32];
+    int js = J_MAX, ks = 0;
+    for (int j = J_MIN; j <= J_MAX; ++j) {
+        const int N = rd_candidate(sfi, bits, dist, channels, j, 0, wl, NULL);
+        if (r_alloc_bits(bits, channels, tail_bits, wl, N, 1) <= size_bits) {
+            js = j;
+            break;
+        }
+    }
+    for (int k = 0; k <= K_MAX; ++k) {
+        const int N = rd_candidate(sfi, bits, dist, channels, js, k, wl, NULL);
+        if (r_alloc_bits(bits, channels, tail_bits, wl, N, 1) <= size_bits) ks = k;
+    }
+    int N = rd_candidate(sfi, bits, dist, channels, js, ks, wl, &ks);
+    int32_t Na, ta, ka;
+    memset(wa, 0, sizeof(wa));
+    at3ps_allocate(sfi, bits, channels, tail_bits, frame_bytes, 1, &wa[0][0], &Na, &ta, &ka);
+    if (channels == 1) memset(wa[1], 0, 32);
+    const double Tr = rd_total(sfi, dist, channels, wl), Ta = rd_total(sfi, dist, channels, wa);
+    const int rd = Tr <= Ta;
+    if (!rd) {
+        memcpy(wl, wa, sizeof(wl));
+        N = Na;
+    }
+    memcpy(wl_out, wl, (size_t)channels * 32);
+    *n_units = N;
+    if (rec) {
+        at3prd_frame_info* r = (at3prd_frame_info*)rec;
+        r->j = js;
+        r->k = ks;
+        r->chose_rd = rd;
+        r->t = ta;
+        r->k_sparse = ka;
+        r->T_rd = Tr;
+        r->T_sparse = Ta;
+    }
+    return r_alloc_bits(bits, channels, tail_bits, wl, N, 1);
+}
+
+/* A6s with the allocation of R4 */
+static void rd_write_frame(const float* specs, int channels, int frame_bytes, const uint8_t* tail, int tail_bits, uint8_t* out, at3prd_frame_info* info)
+{
+    uint8_t sfi[2][32], tab[2][32][8], wl[2][32];
+    uint16_t bits[2][32][8];
+    uint64_t dist[2][32][8];
+    float values[2][2048];
+    int mant[128];
+    at3prd_frame_info rec;
+    memset(sfi, 0, sizeof(sfi));
+    memset(tab, 0, sizeof(tab));
+    memset(bits, 0, sizeof(bits));
+    memset(dist, 0, sizeof(dist));
+    memset(wl, 0, sizeof(wl));
+    memset(&rec, 0, sizeof(rec));
+    at3prd_tables(specs, channels, &sfi[0][0], &bits[0][0][0], &tab[0][0][0], &dist[0][0][0], &values[0][0]);
+    int32_t N;
+    const int total = at3prd_allocate(&sfi[0][0], &bits[0][0][0], &dist[0][0][0], channels, tail_bits, frame_bytes, &wl[0][0], &N, &rec);
+    if (channels == 1) memset(wl[1], 0, 32);
+    memset(out, 0, (size_t)frame_bytes);
+    wbits b = {out, 0, 8 * frame_bytes};
+    wput(&b, 0, 1);
+    wput(&b, (uint32_t)channels - 1, 2);
+    wput(&b, (uint32_t)N - 1, 5);
+    wput(&b, 0, 1);
+    r_wordlen_section(&b, wl[0], wl[1], N, channels);
+    for (int ch = 0; ch < channels; ++ch) {
+        wput(&b, 0, 2);
+        for (int i = 0; i < N; ++i) wput(&b, sfi[ch][i], 6);
+    }
+    wput(&b, 1, 1);
+    for (int ch = 0; ch < channels; ++ch) {
+        wput(&b, 0, 1);
+        wput(&b, 0, 2);
+        wput(&b, 0, 1);
+        for (int i = 0; i < N; ++i) {
+            if (wl[ch][i]) wput(&b, tab[ch][i][wl[ch][i]], 3);
+            else if (ch && wl[0][i]) wput(&b, 1, 1);   /* A4s: "do not copy from channel 0" */
+        }
+    }
+    for (int ch = 0; ch < channels; ++ch) {
+        for (int qu = 0; qu < N; ++qu) {
+            if (wl[ch][qu] == 0) continue;
+            r_quantise(values[ch] + kQuStart[qu], kSpecsPerBlock[qu], wl[ch][qu], mant);
+            r_qu_spectra(mant, kSpecsPerBlock[qu], wl[ch][qu] - 1 + 7 * tab[ch][qu][wl[ch][qu]], &b);
+        }
+        const int numPwrSpec = AT3P_SB_POWGRPS[AT3P_QU_TO_SB[N - 1]];
+        for (int i = 0; i < numPwrSpec; ++i) wput(&b, 15, 4);
+    }
+    for (int i = 0; i < tail_bits; ++i) wput(&b, (tail[i >> 3] >> (7 - (i & 7))) & 1u, 1);
+    if (info) {
+        rec.num_quant_units = N;
+        rec.bits = total;
+        memcpy(rec.wl, wl, sizeof(wl));
+        memcpy(rec.sfi, sfi, sizeof(sfi));
+        for (int ch = 0; ch < 2; ++ch)
+            for (int qu = 0; qu < 32; ++qu) rec.tab[ch][qu] = qu < N && ch < channels && wl[ch][qu] ? tab[ch][qu][wl[ch][qu]] : 0;
+        *info = rec;
+    }
+}
+
+/* specs [n_frames][channels][2048], tails [n_frames][TAIL_BYTES], tail_bits [n_frames] -> out [n_frames][frame_bytes]; info optional */
+int at3prd_write_frames(const float* specs, int channels, int n_frames, int frame_bytes, const uint8_t* tails, const int32_t* tail_bits, uint8_t* out,
+                        void* info)
+{
+    if (channels < 1 || channels > 2 || frame_bytes < 8 || frame_bytes > MAX_FRAME_SZ || frame_bytes % 8) return -1;
+    for (int f = 0; f < n_frames; ++f) {
+        if (tail_bits[f] < 0 || tail_bits[f] > TAIL_BYTES * 8) return -1;
+        rd_write_frame(specs + (size_t)f * channels * 2048, channels, frame_bytes, tails + (size_t)f * TAIL_BYTES, tail_bits[f],
+                       out + (size_t)f * frame_bytes, info ? (at3prd_frame_info*)info + f : NULL);
+    }
+    return n_frames;
+}
+int at3prd_frame_info_size(void) { return (int)sizeof(at3prd_frame_info); }
+int at3prd_j_min(void) { return J_MIN; }
+int at3prd_j_max(void) { return J_MAX; }

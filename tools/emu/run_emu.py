@@ -23,6 +23,7 @@ def build(strict=False):
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3phip.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3p_alloc.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3p_sparse.hip"),
+                           os.path.join(ROOT, "atracdenc_amd/csrc/at3p_rd.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/resample.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/loudness.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3_tables.cpp"),
