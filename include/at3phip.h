@@ -320,7 +320,7 @@ uint32_t at3phip_host_tone_flags(void);
  * 28-31 and a quiet frame leaves thousands of bits unused. With the flag the word lengths are chosen per frame to fill it. The
  * syntax is unchanged (TWordLenEncoder codes arbitrary word lengths as deltas) and the decoder below decodes the frames as they
  * are. The reference has no such allocation: this is the project's definition, stated here and nowhere else, pinned bit for bit
- * to the C restatement tests/host/at3p_alloc_cpu.c, and, for everything but the choice of the allocation, to the reference's own
+ * to the C restatement tests/host/at3p_writer_cpu.c, and, for everything but the choice of the allocation, to the reference's own
  * coders: given the spectra and the word lengths A5 chose, the reference's TWordLenEncoder, TSfIdxEncoder, TQuantUnitsEncoder and
  * TTonalComponentEncoder under TBitStreamEncoder write the frame of A6 byte for byte and count Bits(A) + 3 bits
  * (tests/at3p_ref_parts_lib.py puts a configure part of its own, which holds the word lengths, in front of them;
@@ -464,7 +464,7 @@ uint32_t at3phip_host_tone_flags(void);
  *      error on the spectrum, per frame: it bounds nothing about the time-domain signal after the decoder's overlap.
  *  R5. Floats outside the domain. A1 is the fixed writer's: an infinite line is clamped to +-0.99999, a NaN line stays NaN. A NaN
  *      scaled value gives a NaN d at every w and so u = 0: it adds no distortion and never asks for bits. The mantissa of a NaN is
- *      the conversion tests/host/at3p_alloc_cpu.c documents at quantise(). Every decision after R1's float operations is integer or
+ *      the conversion tests/host/at3p_writer_cpu.c documents at quantise(). Every decision after R1's float operations is integer or
  *      double arithmetic on finite numbers, so any float is accepted, frames do not depend on one another, and no stream affects
  *      another.
  * Out of this definition: psychoacoustic weighting (a weight on D is one table from here). Still ABI 1.6: a library that has the

@@ -25,9 +25,7 @@ import tempfile
 
 import numpy as np
 
-import at3p_alloc_lib as L
-import at3p_rate_lib as R
-import at3p_sparse_lib as SP
+import at3p_writer_lib as W
 import at3p_tonal_write_lib as TW
 from at3p_tonal_lib import _block_ints
 
@@ -278,28 +276,25 @@ WRITERS = ("alloc", "rate", "sparse_off", "sparse_on")
 
 
 def write_restatement(writer, specs, frame_bytes, win=None, blocks=None):
-    """(frames, info records) of tests/host/at3p_alloc_cpu.c (2048 bytes only), at3p_rate_cpu.c or at3p_sparse_cpu.c"""
-    if writer == "alloc":
-        assert frame_bytes == 2048
-        return L.write_adaptive(specs, win, blocks, info=True)
-    if writer == "rate":
-        return R.write_adaptive(specs, frame_bytes, win, blocks, info=True)
-    return SP.write_adaptive(specs, frame_bytes, writer == "sparse_on", win, blocks, info=True)[:2]
+    """(frames, info records) of tests/host/at3p_writer_cpu.c; the writers' names are those of the restatements it was folded from
+    (`alloc`: 2048 bytes only; `alloc`, `rate` and `sparse_off` are one writer now, and the tests keep their cases' names)"""
+    assert writer in WRITERS and (writer != "alloc" or frame_bytes == 2048)
+    return W.write_adaptive(specs, frame_bytes, writer == "sparse_on", win, blocks, info=True)[:2]
 
 
 # ---- spectra ------------------------------------------------------------------------------------------------------------------------
 def edge_spectra(nch):
     """{name: (spectra [n, C, 2048], blocks [n] or None)}: the float domain's and the allocation's edges"""
     rng = np.random.RandomState(40 + nch)
-    e_sp, e_bl = SP.edge_specs(nch)
-    out = {"fullscale": (L.full_scale_noise(2, nch), None), "odd": (L.odd_specs(nch), None), "silence": (np.zeros((1, nch, 2048), np.float32), None),
+    e_sp, e_bl = W.edge_specs(nch)
+    out = {"fullscale": (W.full_scale_noise(2, nch), None), "odd": (W.odd_specs(nch), None), "silence": (np.zeros((1, nch, 2048), np.float32), None),
            "edge0": (e_sp[:1], e_bl[:1]), "edge123": (e_sp[1:], None),
            "loud3": ((3.0 * rng.standard_normal((2, nch, 2048))).astype(np.float32), None),
            "tiny": ((1e-7 * rng.standard_normal((2, nch, 2048))).astype(np.float32), None)}
     if nch == 1:
-        out["quiet"] = (L.quiet_mono(2), None)
+        out["quiet"] = (W.quiet_mono(2), None)
     else:   # channel 1 two mantissa bits under channel 0: every difference between the channels' word lengths is 0 or 2
-        q = L.specs_of("mix", 2, 2)
+        q = W.specs_of("mix", 2, 2)
         q[:, 1] = q[:, 0] * np.float32(0.25)
         out["quarter"] = (q, None)
     return out
@@ -313,7 +308,7 @@ def steps_specs(nch, n=4, seed=77):
     for f in range(n):
         for ch in range(nch):
             for q in range(32):
-                x[f, ch, L.QU_START[q]:L.QU_START[q + 1]] *= 2.0 ** -((3 * q + 5 * f + 2 * ch + (q * q) % 7) % 9 + (f % 2) * (q % 3))
+                x[f, ch, W.QU_START[q]:W.QU_START[q + 1]] *= 2.0 ** -((3 * q + 5 * f + 2 * ch + (q * q) % 7) % 9 + (f % 2) * (q % 3))
     return (0.4 * x).astype(np.float32)
 
 
@@ -339,7 +334,7 @@ def table7_specs(nch, n=6, base=50):
     m = np.array(TABLE7_PAIRS, np.float64).reshape(-1)
     inv, scale = float_table("AT3P_INV_MANT"), float_table("AT3P_SCALE")
     for f in range(n):
-        sp[f, :, L.QU_START[24]:L.QU_START[25]] = (m / float(inv[6]) * float(scale[base + f])).astype(np.float32)
+        sp[f, :, W.QU_START[24]:W.QU_START[25]] = (m / float(inv[6]) * float(scale[base + f])).astype(np.float32)
     return sp
 
 
@@ -358,17 +353,17 @@ G_TONAL_BYTES = 744
 def golden_streams(nch):
     """spectra [3, 4, C, 2048]: noise and tones; the float domain's edges beside mix; the allocation's special cases"""
     e = edge_spectra(nch)
-    s1 = np.concatenate([L.odd_specs(nch, 2), e["fullscale"][0][:1], L.specs_of("mix", nch, 1)])
+    s1 = np.concatenate([W.odd_specs(nch, 2), e["fullscale"][0][:1], W.specs_of("mix", nch, 1)])
     s2 = np.concatenate([e["edge123"][0], e["silence"][0]])
-    return np.stack([np.concatenate([L.specs_of("noise", nch, 2), L.specs_of("tones", nch, 2)]), s1, s2])
+    return np.stack([np.concatenate([W.specs_of("noise", nch, 2), W.specs_of("tones", nch, 2)]), s1, s2])
 
 
 def golden_tonal(nch):
     """(spectra [3, 4, C, 2048], window flags [3, 4, C], blocks [3][4]): the `steep` case's six frames, then the largest block beside
     silence with one loud unit, the largest block on noise, and four frames of steps_specs under the flags of the first four"""
     sp, fl, bl = tonal_case(nch)
-    e_sp, e_bl = SP.edge_specs(nch)
-    sp = np.concatenate([sp, e_sp[:1], L.specs_of("noise", nch, 1), steps_specs(nch)])
+    e_sp, e_bl = W.edge_specs(nch)
+    sp = np.concatenate([sp, e_sp[:1], W.specs_of("noise", nch, 1), steps_specs(nch)])
     fl = np.concatenate([fl, np.zeros((2, nch), np.uint16), fl[:4]])
     bl = bl + [e_bl[0], TW.largest_block(nch), None, None, None, None]
     return sp.reshape(G_S, G_F, nch, 2048), fl.reshape(G_S, G_F, nch), [bl[4 * s:4 * s + 4] for s in range(G_S)]

@@ -1,8 +1,8 @@
 /* TEST INFRASTRUCTURE ONLY - CPU restatement of the ATRAC3plus adaptive writer with RATE-DISTORTION WORD LENGTHS (include/at3phip.h,
- * R1-R5). A1, A2, A4s, the frame's layout (A6s) and the decoder are tests/host/at3p_sparse_cpu.c's, included here as that file
+ * R1-R5). A1, A2, A4s, the frame's layout (A6s) and the decoder are tests/host/at3p_writer_cpu.c's, included here as that file
  * includes its predecessors; R1-R4, the distortion table, the candidates, the two scans and the guard, are written out here in
  * plain scalar C from the header's text. Compiled by the tests with gcc -O2 -fPIC -ffp-contract=off -fno-fast-math. */
-#include "at3p_sparse_cpu.c"
+#include "at3p_writer_cpu.c"
 
 #define J_MIN (-30)
 #define J_MAX 69
@@ -16,7 +16,7 @@ static void rd_dist_table(const float* values, int channels, uint64_t* dist)
             const int start = kQuStart[qu], n = kSpecsPerBlock[qu];
             const float* v = values + ch * 2048 + start;
             for (int w = 0; w < 8; ++w) {
-                if (w) r_quantise(v, n, w, mant);
+                if (w) quantise(v, n, w, mant);
                 else memset(mant, 0, sizeof(mant));
                 uint64_t S = 0;
                 for (int i = 0; i < n; ++i) {
@@ -34,7 +34,7 @@ static void rd_dist_table(const float* values, int channels, uint64_t* dist)
 int at3prd_tables(const float* specs, int channels, uint8_t* sfi, uint16_t* bits, uint8_t* tab, uint64_t* dist, float* values_out)
 {
     float values[2 * 2048];
-    if (at3ps_cost_table(specs, channels, sfi, bits, tab, values) != 0) return -1;
+    if (at3pw_cost_table(specs, channels, sfi, bits, tab, values) != 0) return -1;
     rd_dist_table(values, channels, dist);
     if (values_out) memcpy(values_out, values, sizeof(float) * 2048 * (size_t)channels);
     return 0;
@@ -86,19 +86,7 @@ static int rd_candidate(const uint8_t* sfi, const uint16_t* bits, const uint64_t
             }
         }
     if (took) *took = taken;
-    int N = 0;
-    for (int qu = 0; qu < 32; ++qu)
-        for (int ch = 0; ch < channels; ++ch)
-            if (wl[ch][qu] >= 1) N = qu + 1;
-    if (N == 0) {
-        N = 1;
-        wl[0][0] = 1;
-    }
-    if (N >= 29 && N <= 31) {
-        N = 32;
-        if (wl[0][31] == 0 && wl[1][31] == 0) wl[0][31] = 1;
-    }
-    return N;
+    return close_sparse(wl, channels);
 }
 
 /* R4: T(X) */
@@ -114,7 +102,7 @@ typedef struct {
     int32_t j, k, num_quant_units, bits;   /* j*, k* of R3; N and Bits of the allocation written */
     int32_t chose_rd, t, k_sparse, pad;    /* R4: 1 = R(j*, k*), 0 = A(t*, k*); t*, k* of the sparse allocation */
     double T_rd, T_sparse;
-    uint8_t wl[2][32], sfi[2][32], tab[2][32];
+    frame_alloc used;
 } at3prd_frame_info;
 
 /* R2-R4 on the tables against the budget 8 * frame_bytes - 3; returns Bits of the allocation written. rec (optional): j, k,
@@ -127,19 +115,19 @@ int at3prd_allocate(const uint8_t* sfi, const uint16_t* bits, const uint64_t* di
     int js = J_MAX, ks = 0;
     for (int j = J_MIN; j <= J_MAX; ++j) {
         const int N = rd_candidate(sfi, bits, dist, channels, j, 0, wl, NULL);
-        if (r_alloc_bits(bits, channels, tail_bits, wl, N, 1) <= size_bits) {
+        if (alloc_bits(bits, channels, tail_bits, wl, N, 1) <= size_bits) {
             js = j;
             break;
         }
     }
     for (int k = 0; k <= K_MAX; ++k) {
         const int N = rd_candidate(sfi, bits, dist, channels, js, k, wl, NULL);
-        if (r_alloc_bits(bits, channels, tail_bits, wl, N, 1) <= size_bits) ks = k;
+        if (alloc_bits(bits, channels, tail_bits, wl, N, 1) <= size_bits) ks = k;
     }
     int N = rd_candidate(sfi, bits, dist, channels, js, ks, wl, &ks);
     int32_t Na, ta, ka;
     memset(wa, 0, sizeof(wa));
-    at3ps_allocate(sfi, bits, channels, tail_bits, frame_bytes, 1, &wa[0][0], &Na, &ta, &ka);
+    at3pw_allocate(sfi, bits, channels, tail_bits, frame_bytes, 1, &wa[0][0], &Na, &ta, &ka);
     if (channels == 1) memset(wa[1], 0, 32);
     const double Tr = rd_total(sfi, dist, channels, wl), Ta = rd_total(sfi, dist, channels, wa);
     const int rd = Tr <= Ta;
@@ -159,17 +147,16 @@ int at3prd_allocate(const uint8_t* sfi, const uint16_t* bits, const uint64_t* di
         r->T_rd = Tr;
         r->T_sparse = Ta;
     }
-    return r_alloc_bits(bits, channels, tail_bits, wl, N, 1);
+    return alloc_bits(bits, channels, tail_bits, wl, N, 1);
 }
 
-/* A6s with the allocation of R4 */
+/* A1, A2, R1-R4 of one frame: the allocation of R4, then the frame (A6s) */
 static void rd_write_frame(const float* specs, int channels, int frame_bytes, const uint8_t* tail, int tail_bits, uint8_t* out, at3prd_frame_info* info)
 {
     uint8_t sfi[2][32], tab[2][32][8], wl[2][32];
     uint16_t bits[2][32][8];
     uint64_t dist[2][32][8];
     float values[2][2048];
-    int mant[128];
     at3prd_frame_info rec;
     memset(sfi, 0, sizeof(sfi));
     memset(tab, 0, sizeof(tab));
@@ -179,48 +166,11 @@ static void rd_write_frame(const float* specs, int channels, int frame_bytes, co
     memset(&rec, 0, sizeof(rec));
     at3prd_tables(specs, channels, &sfi[0][0], &bits[0][0][0], &tab[0][0][0], &dist[0][0][0], &values[0][0]);
     int32_t N;
-    const int total = at3prd_allocate(&sfi[0][0], &bits[0][0][0], &dist[0][0][0], channels, tail_bits, frame_bytes, &wl[0][0], &N, &rec);
+    rec.bits = at3prd_allocate(&sfi[0][0], &bits[0][0][0], &dist[0][0][0], channels, tail_bits, frame_bytes, &wl[0][0], &N, &rec);
+    rec.num_quant_units = N;
     if (channels == 1) memset(wl[1], 0, 32);
-    memset(out, 0, (size_t)frame_bytes);
-    wbits b = {out, 0, 8 * frame_bytes};
-    wput(&b, 0, 1);
-    wput(&b, (uint32_t)channels - 1, 2);
-    wput(&b, (uint32_t)N - 1, 5);
-    wput(&b, 0, 1);
-    r_wordlen_section(&b, wl[0], wl[1], N, channels);
-    for (int ch = 0; ch < channels; ++ch) {
-        wput(&b, 0, 2);
-        for (int i = 0; i < N; ++i) wput(&b, sfi[ch][i], 6);
-    }
-    wput(&b, 1, 1);
-    for (int ch = 0; ch < channels; ++ch) {
-        wput(&b, 0, 1);
-        wput(&b, 0, 2);
-        wput(&b, 0, 1);
-        for (int i = 0; i < N; ++i) {
-            if (wl[ch][i]) wput(&b, tab[ch][i][wl[ch][i]], 3);
-            else if (ch && wl[0][i]) wput(&b, 1, 1);   /* A4s: "do not copy from channel 0" */
-        }
-    }
-    for (int ch = 0; ch < channels; ++ch) {
-        for (int qu = 0; qu < N; ++qu) {
-            if (wl[ch][qu] == 0) continue;
-            r_quantise(values[ch] + kQuStart[qu], kSpecsPerBlock[qu], wl[ch][qu], mant);
-            r_qu_spectra(mant, kSpecsPerBlock[qu], wl[ch][qu] - 1 + 7 * tab[ch][qu][wl[ch][qu]], &b);
-        }
-        const int numPwrSpec = AT3P_SB_POWGRPS[AT3P_QU_TO_SB[N - 1]];
-        for (int i = 0; i < numPwrSpec; ++i) wput(&b, 15, 4);
-    }
-    for (int i = 0; i < tail_bits; ++i) wput(&b, (tail[i >> 3] >> (7 - (i & 7))) & 1u, 1);
-    if (info) {
-        rec.num_quant_units = N;
-        rec.bits = total;
-        memcpy(rec.wl, wl, sizeof(wl));
-        memcpy(rec.sfi, sfi, sizeof(sfi));
-        for (int ch = 0; ch < 2; ++ch)
-            for (int qu = 0; qu < 32; ++qu) rec.tab[ch][qu] = qu < N && ch < channels && wl[ch][qu] ? tab[ch][qu][wl[ch][qu]] : 0;
-        *info = rec;
-    }
+    emit_frame(out, frame_bytes, channels, 1, sfi, tab, wl, N, values, tail, tail_bits, &rec.used);
+    if (info) *info = rec;
 }
 
 /* specs [n_frames][channels][2048], tails [n_frames][TAIL_BYTES], tail_bits [n_frames] -> out [n_frames][frame_bytes]; info optional */

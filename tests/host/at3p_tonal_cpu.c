@@ -1,255 +1,8 @@
-/* TEST INFRASTRUCTURE ONLY - a C restatement of the ATRAC3plus decoder's tonal blocks (include/at3phip.h, TONAL BLOCKS): the
- * tonal block's syntax and ApplyFilter's per-frame bookkeeping, and step 4b run as the reference runs it, frame after frame with
- * tones_info / tones_info_prev and their curr_env kept between frames (the GPU reconstructs those from three records). Steps 1-2
- * (up to the tonal flag), 3, 5 and 6 are tests/host/at3p_decode_cpu.c, included here. Compiled by the tests with
- * gcc -O2 -fPIC -ffp-contract=off -fno-fast-math. */
+/* TEST INFRASTRUCTURE ONLY - the entry points of the C restatement of the ATRAC3plus decoder with tonal blocks (include/at3phip.h,
+ * TONAL BLOCKS) at 2048 bytes, and the encoder's ApplyFilter. The tonal block's syntax, step 4b and the frame loop are
+ * tests/host/at3p_decode_cpu.c's, included here; a stream of this file keeps frame n - 1's record beside that file's state. Compiled
+ * by the tests with gcc -O2 -fPIC -ffp-contract=off -fno-fast-math. */
 #include "at3p_decode_cpu.c"
-#include "../../atracdenc_amd/csrc/at3p_tone_vlc.inc"
-
-typedef struct { int has_start, start, has_stop, stop; } tenv;
-typedef struct { int nw, start_index; tenv pend, curr; } tband;
-typedef struct {
-    int present;
-    tband band[2][16];
-    int freq[48], amp_sf[48], phase[48];
-} trec;
-
-static struct { float sine[2048], hann[256], amp_sf[64]; int init; } TT;
-
-static void init_tone_tables(void)
-{
-    if (TT.init) return;
-    for (int i = 0; i < 2048; ++i) TT.sine[i] = (float)sin(2 * M_PI * i / 2048);
-    for (int i = 0; i < 256; ++i) TT.hann[i] = (float)((1.0f - cos(2 * M_PI * i / 256.0f)) * 0.5f);
-    for (int i = 0; i < 64; ++i) TT.amp_sf[i] = exp2f((i - 3) / 4.0f);
-    TT.init = 1;
-}
-
-static int first_set_bit_plus1(uint32_t x)
-{
-    int n = 0;
-    while (x >> n) ++n;
-    return n ? n : 1;
-}
-
-/* the tonal block after its flag; r is zero on entry */
-static int parse_tonal(bits* b, int C, trec* r)
-{
-    int invalid = 0;
-#define CHK() do { if (b->bad) return R_READ_PAST_END; if (invalid) return R_BAD_CODE; } while (0)
-#define MUST(n, val) do { const uint32_t v_ = rd(b, n); CHK(); if (v_ != (uint32_t)(val)) return R_UNSUPPORTED; } while (0)
-    MUST(1, 1);
-    int nb = -1;
-    {   /* the tone-band code: a complete prefix code, searched symbol by symbol */
-        for (int sym = 0; sym < 16 && nb < 0; ++sym) {
-            const int len = AT3P_TONE_BANDS_VLC[sym] >> 12, code = AT3P_TONE_BANDS_VLC[sym] & 0xfff;
-            int v = 0;
-            for (int k = 0; k < len; ++k) v = (v << 1) | bit_at(b, b->pos + k);
-            if (v == code) {
-                rd(b, len);
-                nb = sym + 1;
-            }
-        }
-        if (nb < 0) invalid = 1;
-        CHK();
-    }
-    int shared[16] = {0}, leader = 0;
-    if (C == 2) {
-        if (rd(b, 1)) {
-            if (rd(b, 1) == 0) {
-                for (int i = 0; i < nb; ++i) shared[i] = 1;
-            } else {
-                for (int i = 0; i < nb; ++i) shared[i] = (int)rd(b, 1);
-            }
-        }
-        CHK();
-        if (rd(b, 1)) {
-            MUST(1, 0);
-            leader = 1;
-        }
-        MUST(1, 0);
-    }
-    int idx = 0;
-    for (int ch = 0; ch < C; ++ch) {
-        tband* bd = r->band[ch];
-        if (ch) MUST(1, 0);
-        for (int i = 0; i < nb; ++i) {
-            if (ch && shared[i]) continue;
-            bd[i].pend.start = -1;
-            bd[i].pend.stop = 32;
-            if (rd(b, 1)) { bd[i].pend.has_start = 1; bd[i].pend.start = (int)rd(b, 5); }
-            if (rd(b, 1)) { bd[i].pend.has_stop = 1; bd[i].pend.stop = (int)rd(b, 5); }
-        }
-        MUST(ch + 1, 0);
-        for (int i = 0; i < nb; ++i) {
-            if (ch && shared[i]) continue;
-            bd[i].nw = (int)rd(b, 4);
-        }
-        CHK();
-        for (int i = 0; i < nb; ++i) {
-            if ((ch && shared[i]) || !bd[i].nw) continue;
-            bd[i].start_index = idx;
-            idx += bd[i].nw;
-        }
-        if (idx > 48) return R_BAD_CODE;
-        if (ch) MUST(1, 0);
-        for (int i = 0; i < nb; ++i) {
-            const int n = bd[i].nw;
-            if ((ch && shared[i]) || !n) continue;
-            int* fq = r->freq + bd[i].start_index;
-            const int desc = n > 1 ? (int)rd(b, 1) : 0;
-            if (!desc) {
-                fq[0] = (int)rd(b, 10);
-                for (int j = 1; j < n; ++j) {
-                    const int p = fq[j - 1];
-                    if (p < 512) {
-                        fq[j] = (int)rd(b, 10);
-                    } else {
-                        const int nbits = first_set_bit_plus1((uint32_t)(1023 - p));
-                        fq[j] = (int)rd(b, nbits) + 1024 - (1 << nbits);
-                    }
-                }
-            } else {
-                fq[n - 1] = (int)rd(b, 10);
-                for (int j = n - 2; j >= 0; --j) fq[j] = (int)rd(b, first_set_bit_plus1((uint32_t)fq[j + 1]));
-            }
-            CHK();
-        }
-        MUST(ch + 1, 0);
-        for (int i = 0; i < nb; ++i)
-            if (!(ch && shared[i]))
-                for (int j = 0; j < bd[i].nw; ++j) r->amp_sf[bd[i].start_index + j] = (int)rd(b, 6);
-        CHK();
-        for (int i = 0; i < nb; ++i)
-            if (!(ch && shared[i]))
-                for (int j = 0; j < bd[i].nw; ++j) r->phase[bd[i].start_index + j] = (int)rd(b, 5);
-        CHK();
-    }
-    if (C == 2)
-        for (int i = 0; i < nb; ++i) {
-            if (shared[i]) r->band[1][i] = r->band[0][i];
-            if (leader) {
-                const tband t = r->band[0][i];
-                r->band[0][i] = r->band[1][i];
-                r->band[1][i] = t;
-            }
-        }
-    r->present = 1;
-#undef MUST
-#undef CHK
-    return R_OK;
-}
-
-/* steps 1-2 with tonal blocks: spec [C][2048], win [C], r (zeroed here); returns the reason */
-static int unpack_tonal(const uint8_t* frame, int C, float* spec, uint16_t* win, trec* r, at3pd_fields* f)
-{
-    memset(r, 0, sizeof(*r));
-    int why = at3pd_unpack_frame(frame, C, spec, win, f);
-    if (why != R_TONAL) return why;
-    /* parse_frame stops right after the tonal flag: find that flag as the last bit whose zeroing (with everything after it)
-     * stops the frame from reaching it - a frame cut at q reaches the flag if and only if q is past it */
-    static uint8_t cut[2048];
-    static float scratch[2][2048];
-    uint16_t w2[2];
-    at3pd_fields f2;
-    int lo = 0, hi = FRAME_BITS;   /* cut at hi reaches the flag, cut at lo does not */
-    while (hi - lo > 1) {
-        const int q = (lo + hi) / 2;
-        memcpy(cut, frame, 2048);
-        for (int p = q; p < FRAME_BITS; ++p) cut[p >> 3] &= (uint8_t)~(0x80 >> (p & 7));
-        if (parse_frame(cut, C, &scratch[0][0], w2, &f2) == R_TONAL) hi = q; else lo = q;
-    }
-    bits b = {frame, hi, 0};
-    why = parse_tonal(&b, C, r);
-    if (!why) {
-        const uint32_t noise = rd(&b, 1);
-        if (b.bad) why = R_READ_PAST_END;
-        else if (noise) why = R_UNSUPPORTED;
-    }
-    if (!why) {
-        const uint32_t term = rd(&b, 2);
-        if (b.bad) why = R_READ_PAST_END;
-        else if (term != 3) why = R_NO_TERMINATOR;
-    }
-    if (why) {
-        memset(r, 0, sizeof(*r));
-        memset(spec, 0, sizeof(float) * 2048 * C);
-        for (int ch = 0; ch < C; ++ch) win[ch] = 0;
-    } else {
-        /* the spectra and flags of a frame that parse_frame rejected as tonal: parse again with the tonal block replaced by
-         * a tonal flag of 0, no noise and the terminator */
-        memcpy(cut, frame, 2048);
-        for (int p = hi - 1; p < FRAME_BITS; ++p) cut[p >> 3] &= (uint8_t)~(0x80 >> (p & 7));
-        for (int p = hi + 1; p < hi + 3 && p < FRAME_BITS; ++p) cut[p >> 3] |= (uint8_t)(0x80 >> (p & 7));
-        const int again = parse_frame(cut, C, spec, win, &f2);
-        (void)again;   /* R_OK: the bits up to the flag are the frame's own; a flag at the very end was caught above */
-        f2.reason = 0;
-    }
-    if (f) { *f = f2; f->reason = why; }
-    return why;
-}
-
-/* ---- step 4b, as ff_atrac3p_generate_tones runs it ---- */
-static void waves_synth(const trec* r, const tband* t, const tenv* e, int reg, float* out)
-{
-    for (int wn = 0; wn < t->nw; ++wn) {
-        const int k = t->start_index + wn;
-        const double amp = (double)TT.amp_sf[r->amp_sf[k]];
-        const int inc = r->freq[k];
-        int pos = (((r->phase[k] & 31) << 6) - (reg ^ 128) * inc) & 2047;
-        for (int i = 0; i < 128; ++i) {
-            out[i] = (float)((double)out[i] + (double)TT.sine[pos] * amp);
-            pos = (pos + inc) & 2047;
-        }
-    }
-    if (e->has_start) {
-        const int pos = (e->start << 2) - reg;
-        if (pos > 0 && pos <= 128) {
-            for (int i = 0; i < pos; ++i) out[i] = 0.0f;
-            if (!e->has_stop || e->start != e->stop)
-                for (int k = 0; k < 4; ++k) out[pos + k] = out[pos + k] * TT.hann[32 * k];
-        }
-    }
-    if (e->has_stop) {
-        const int pos = ((e->stop + 1) << 2) - reg;
-        if (pos > 0 && pos <= 128) {
-            for (int k = 0; k < 4; ++k) out[pos - 4 + k] = out[pos - 4 + k] * TT.hann[96 - 32 * k];
-            for (int i = pos; i < 128; ++i) out[i] = 0.0f;
-        }
-    }
-}
-
-/* encoder = 0: the decoder's step 4b (s - g, g = 0.0f - (wavreg1 + wavreg2)); encoder = 1: ApplyFilter's out -= wavreg1 + wavreg2 */
-static void generate_tones(const trec* prev, trec* cur, int ch, int sb, float* out, int encoder)
-{
-    const tband* now = &prev->band[ch][sb];
-    tband* next = &cur->band[ch][sb];
-    tenv* c = &next->curr;
-    if (next->pend.has_start && next->pend.start < next->pend.stop) { c->has_start = 1; c->start = next->pend.start + 32; }
-    else if (now->pend.has_start) { c->has_start = 1; c->start = now->pend.start; }
-    else { c->has_start = 0; c->start = 0; }
-    if (now->pend.has_stop && now->pend.stop >= c->start) { c->has_stop = 1; c->stop = now->pend.stop; }
-    else if (next->pend.has_stop) { c->has_stop = 1; c->stop = next->pend.stop + 32; }
-    else { c->has_stop = 0; c->stop = 64; }
-    const int reg1 = now->curr.stop < 32 ? 0 : 1, reg2 = c->start >= 32 ? 0 : 1;
-    float w1[128] = {0}, w2[128] = {0};
-    if (now->nw && reg1) waves_synth(prev, now, &now->curr, 128, w1);
-    if (next->nw && reg2) waves_synth(cur, next, c, 0, w2);
-    if (now->nw && next->nw && reg1 && reg2) {
-        for (int i = 0; i < 128; ++i) { w1[i] = w1[i] * TT.hann[128 + i]; w2[i] = w2[i] * TT.hann[i]; }
-    } else {
-        if (now->nw && !now->curr.has_stop) for (int i = 0; i < 128; ++i) w1[i] = w1[i] * TT.hann[128 + i];
-        if (next->nw && !c->has_start) for (int i = 0; i < 128; ++i) w2[i] = w2[i] * TT.hann[i];
-    }
-    for (int i = 0; i < 128; ++i) {
-        if (encoder) {
-            out[i] -= w1[i] + w2[i];
-        } else {
-            const float g = 0.0f - (w1[i] + w2[i]);
-            out[i] = out[i] - g;
-        }
-    }
-}
 
 typedef struct {
     at3pd_stream base;
@@ -268,43 +21,16 @@ void at3pt_reset(void* state)
 void at3pt_decode(void* state, int C, const uint8_t* frames, int n_frames, float* pcm, uint64_t* rejected, int tones)
 {
     at3pt_stream* st = (at3pt_stream*)state;
-    init_tables();
-    init_tone_tables();
-    for (int fr = 0; fr < n_frames; ++fr) {
-        float spec[2][2048];
-        uint16_t win[2] = {0, 0};
-        trec cur;
-        at3pd_fields f;
-        const int why = tones ? unpack_tonal(frames + (size_t)fr * 2048, C, &spec[0][0], win, &cur, &f)
-                              : (memset(&cur, 0, sizeof(cur)), at3pd_unpack_frame(frames + (size_t)fr * 2048, C, &spec[0][0], win, &f));
-        if (why) rejected[why - 1]++;
-        for (int ch = 0; ch < C; ++ch) {
-            float sub[2048], out[2048];
-            midct(&st->base.ch[ch], spec[ch], win[ch], sub);
-            for (int i = 0; i < 2048; ++i) sub[i] = sub[i] * kRescale;
-            if (tones && (cur.present || st->prev.present))
-                for (int sb = 0; sb < 16; ++sb)
-                    if (cur.band[ch][sb].nw || st->prev.band[ch][sb].nw) generate_tones(&st->prev, &cur, ch, sb, sub + sb * 128, 0);
-            ipqf(&st->base.ch[ch], sub, out);
-            for (int i = 0; i < 2048; ++i) {
-                float v = out[i];
-                v = v > 1.0f ? 1.0f : v;
-                v = v < -1.0f ? -1.0f : v;
-                pcm[((size_t)fr * 2048 + i) * C + ch] = v;
-            }
-        }
-        st->prev = cur;
-    }
+    decode_frames(&st->base, &st->prev, C, frames, 2048, n_frames, pcm, rejected, NULL, tones, 0);
 }
 
 /* steps 1-2 with tonal blocks for the golden generator: specs [C][2048], win [C] and the record as flat ints:
  * present, then per (ch, band) nw, start_index, has_start, start, has_stop, stop, then freq[48], amp_sf[48], phase[48] */
 int at3pt_unpack_frame(const uint8_t* frame, int C, float* specs, uint16_t* win, int32_t* rec)
 {
-    init_tables();
     trec r;
     at3pd_fields f;
-    const int why = unpack_tonal(frame, C, specs, win, &r, &f);
+    const int why = unpack(frame, 2048, C, specs, win, &r, &f, 0);
     int k = 0;
     rec[k++] = r.present;
     for (int ch = 0; ch < 2; ++ch)

@@ -1,5 +1,5 @@
 """Adaptive ATRAC3plus word lengths (include/at3phip.h, ADAPTIVE WORD LENGTHS) without a GPU: the C restatement
-tests/host/at3p_alloc_cpu.c writes frames the restated decoder decodes, fills the frame, gains what the definition's prototype
+tests/host/at3p_writer_cpu.c writes frames the restated decoder decodes, fills the frame, gains what the definition's prototype
 measured over the fixed word-length table, and holds at its edges; at3phip_host_allocate (the host-compiled library) equals its
 steps A3-A5 on real and on random cost tables; the golden pins (t*, k*, N) and the frames; the kernel runs through the CPU SIMT
 harness against it."""
@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-import at3p_alloc_lib as L
+import at3p_writer_lib as W
 import at3p_gha_lib as G
 import at3p_tonal_lib as T
 import at3p_tonal_write_lib as TW
@@ -16,7 +16,7 @@ from at3_testlib import at3p_signal, at3p_write_frames
 from simt_harness_lib import CLANG, ROOT, Children, assert_clean, build_strict
 
 needs_clang = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's clang++ to compile the kernel sources for the host")
-NF = L.SNR_FRAMES
+NF = W.SNR_FRAMES
 # adaptive minus fixed, dB per channel: the floors the definition's prototype set (DESIGN.md section 19 lists what is measured)
 SNR_FLOORS = {"noise": 12.0, "mix": 8.0, "stress": 6.0, "tones": 2.0, "burst": -0.1}
 
@@ -26,13 +26,13 @@ _frames = {}
 def _written(name, nch):
     """(specs, frames, per-frame records) of the restatement for a signal, computed once"""
     if (name, nch) not in _frames:
-        sp = L.specs_of(name, nch, NF)
-        _frames[(name, nch)] = (sp,) + L.write_adaptive(sp, info=True)
+        sp = W.specs_of(name, nch, NF)
+        _frames[(name, nch)] = (sp,) + W.write_adaptive(sp, info=True)[:2]
     return _frames[(name, nch)]
 
 
 @pytest.mark.parametrize("nch", [1, 2])
-@pytest.mark.parametrize("name", L.SIGNALS)
+@pytest.mark.parametrize("name", W.SIGNALS)
 def test_restatement_writes_decodable_full_frames(name, nch):
     """14 frames of each signal: the restated decoder rejects none; every frame parses to N outside 29..31 and word lengths 1..7;
     the terminator lies inside the frame; Bits(A), recounted from the parsed fields with the oracle's at3po_wordlen_bits for the
@@ -40,21 +40,21 @@ def test_restatement_writes_decodable_full_frames(name, nch):
     sp, frames, rec = _written(name, nch)
     pcm, rej = T.cpu_tonal_decode(frames, nch)
     assert rej.sum() == 0, rej
-    tail = sum(n for _, n in L.tail_bits_list(nch))
+    tail = sum(n for _, n in W.tail_bits_list(nch))
     for f in range(NF):
-        p = L.parse_frame(frames[f], nch)
+        p = W.parse_head(frames[f], nch)
         assert p["N"] not in (29, 30, 31) and p["N"] == rec["num_quant_units"][f]
         assert all(1 <= w <= 7 for row in p["wl"] for w in row), p["wl"]
         assert [list(rec["wl"][f][ch][:p["N"]]) for ch in range(nch)] == p["wl"]
-        assert [list(rec["sfi"][f][ch][:p["N"]]) for ch in range(nch)] == p["sfi"]
-        _, bits, tab = L.cost_table(sp[f])
+        assert [list(rec["sfi"][f][ch][:p["N"]]) for ch in range(nch)] == p["sf"]
+        _, bits, tab = W.cost_table(sp[f])
         assert p["tab"] == [[int(tab[ch][q][p["wl"][ch][q]]) for q in range(p["N"])] for ch in range(nch)]
-        total, _ = L.recount_bits(p, nch, bits, tail)
-        assert total == rec["bits"][f] and total <= L.SIZE_BITS, (total, rec["bits"][f])
-        assert L.terminator_pos(frames[f]) == 3 + total - 1 < 2048 * 8
+        total, _ = W.recount_bits(p, nch, bits, tail)
+        assert total == rec["bits"][f] and total <= W.SIZE_BITS, (total, rec["bits"][f])
+        assert W.terminator_pos(frames[f]) == 3 + total - 1 < 2048 * 8
 
 
-@pytest.mark.parametrize("name", L.SIGNALS)
+@pytest.mark.parametrize("name", W.SIGNALS)
 def test_round_trip_snr_over_the_fixed_table(name):
     """encoder and restated decoder, adaptive against the fixed-table writer on the same spectra, per channel"""
     for nch in (1, 2):
@@ -83,7 +83,7 @@ def test_tones_with_adaptive_word_lengths():
     # frame j carries the spectrum of residual j and block T_{j-1}: the alignment of tests/test_at3p_gha_cpu.py's round trip
     specs, recs = G.residual_specs(resid[1:]), [tones[j - 1] if j else None for j in range(NF)]
     fixed = G.splice_blocks(at3p_write_frames(specs), recs, 1)
-    adaptive = L.write_adaptive(specs, None, [None if r is None else G.block_dict(r, 1) for r in recs])
+    adaptive = W.write_adaptive(specs, blocks=[None if r is None else G.block_dict(r, 1) for r in recs])
     out = []
     for fr in (fixed, adaptive):
         y, rej = T.cpu_tonal_decode(fr, 1)
@@ -95,20 +95,20 @@ def test_tones_with_adaptive_word_lengths():
 
 # ---- edge frames ----------------------------------------------------------------------------------------------------------------
 def test_silence_takes_every_bit_of_word_length():
-    frames, rec = L.write_adaptive(np.zeros((1, 2, 2048), np.float32), info=True)
-    assert rec["t"][0] == L.T_MIN and rec["num_quant_units"][0] == 32 and (rec["wl"][0] == 7).all()
-    assert L.parse_frame(frames[0], 2)["wl"] == [[7] * 32] * 2
+    frames, rec, _ = W.write_adaptive(np.zeros((1, 2, 2048), np.float32), info=True)
+    assert rec["t"][0] == W.T_MIN and rec["num_quant_units"][0] == 32 and (rec["wl"][0] == 7).all()
+    assert W.parse_head(frames[0], 2)["wl"] == [[7] * 32] * 2
 
 
 def test_quiet_mono_frame_leaves_bits_unused():
-    frames, rec = L.write_adaptive(L.quiet_mono(), info=True)
-    assert rec["t"][0] == L.T_MIN and rec["k"][0] == 0 and rec["bits"][0] < L.SIZE_BITS and (rec["wl"][0][0] == 7).all()
+    frames, rec, _ = W.write_adaptive(W.quiet_mono(), info=True)
+    assert rec["t"][0] == W.T_MIN and rec["k"][0] == 0 and rec["bits"][0] < W.SIZE_BITS and (rec["wl"][0][0] == 7).all()
 
 
 def test_full_scale_stereo_noise_fills_the_frame():
-    frames, rec = L.write_adaptive(L.full_scale_noise(3, 2), info=True)
-    assert (rec["t"] > L.T_MIN).all(), rec["t"]
-    assert ((rec["bits"] >= L.SIZE_BITS - 200) & (rec["bits"] <= L.SIZE_BITS)).all(), rec["bits"]
+    frames, rec, _ = W.write_adaptive(W.full_scale_noise(3, 2), info=True)
+    assert (rec["t"] > W.T_MIN).all(), rec["t"]
+    assert ((rec["bits"] >= W.SIZE_BITS - 200) & (rec["bits"] <= W.SIZE_BITS)).all(), rec["bits"]
     assert T.cpu_tonal_decode(frames, 2)[1].sum() == 0
 
 
@@ -118,17 +118,17 @@ def test_largest_tonal_record_still_fits(nch):
     decodes with its tones, the block's bits are counted, the stereo frame is full on the loud spectrum"""
     big = TW.largest_block(nch)
     part = TW.case_blocks("share_a_2")[0][2] if nch == 2 else TW.case_blocks("small_1")[1][0]   # partial sharing / 15 waves in a band
-    sp = np.concatenate([L.full_scale_noise(2, nch), np.zeros((1, nch, 2048), np.float32)])
-    frames, rec = L.write_adaptive(sp, None, [big, part, big], info=True)
-    tails = [sum(n for _, n in L.tail_bits_list(nch, None, b)) for b in (big, part, big)]
+    sp = np.concatenate([W.full_scale_noise(2, nch), np.zeros((1, nch, 2048), np.float32)])
+    frames, rec, _ = W.write_adaptive(sp, blocks=[big, part, big], info=True)
+    tails = [sum(n for _, n in W.tail_bits_list(nch, None, b)) for b in (big, part, big)]
     assert tails[0] > 1000
     pcm, rej = T.cpu_tonal_decode(frames, nch, tones=True)
     assert rej.sum() == 0, rej
     for f in range(3):
-        p = L.parse_frame(frames[f], nch)
-        total, _ = L.recount_bits(p, nch, L.cost_table(sp[f])[1], tails[f])
-        assert total == rec["bits"][f] <= L.SIZE_BITS and L.terminator_pos(frames[f]) == 3 + total - 1
-    assert nch == 1 or rec["bits"][0] >= L.SIZE_BITS - 200   # (a mono frame of full-scale noise fits at t = -21 even with the block)
+        p = W.parse_head(frames[f], nch)
+        total, _ = W.recount_bits(p, nch, W.cost_table(sp[f])[1], tails[f])
+        assert total == rec["bits"][f] <= W.SIZE_BITS and W.terminator_pos(frames[f]) == 3 + total - 1
+    assert nch == 1 or rec["bits"][0] >= W.SIZE_BITS - 200   # (a mono frame of full-scale noise fits at t = -21 even with the block)
     specs, win, recs, why = T.unpack_tonal(frames, nch)
     assert (why == 0).all() and (recs[:, 0] == 1).all()
     for f, b in enumerate((big, part, big)):
@@ -145,13 +145,13 @@ def _host():
 def test_host_allocate_equals_the_restatement_on_the_signals():
     B, path = _host()
     n = 0
-    for name in L.SIGNALS + ("silence", "fullscale"):
+    for name in W.SIGNALS + ("silence", "fullscale"):
         for nch in (1, 2):
-            sp = L.specs_of(name, nch, 4)
+            sp = W.specs_of(name, nch, 4)
             for f in (0, 3):
-                sfi, bits, _ = L.cost_table(sp[f])
+                sfi, bits, _ = W.cost_table(sp[f])
                 for tail in (8, 700, 1624):
-                    wl, N, t, k, _ = L.allocate(sfi, bits, tail)
+                    wl, N, t, k, _ = W.allocate(sfi, bits, tail)
                     gwl, gN, gt, gk = B.at3p_host_allocate(sfi, bits, tail, path)
                     assert (gN, gt, gk) == (N, t, k) and np.array_equal(gwl, wl), (name, nch, f, tail)
                     n += 1
@@ -164,16 +164,16 @@ def test_host_allocate_equals_the_restatement_on_random_tables():
     fit again as t rises (counted here: the case exists in the set), where the full scan and a bisection differ"""
     B, path = _host()
     refit = nonmono = 0
-    for i, (sfi, bits, tail) in enumerate(L.random_cost_tables()):
-        wl, N, t, k, total = L.allocate(sfi, bits, tail)
+    for i, (sfi, bits, tail) in enumerate(W.random_cost_tables()):
+        wl, N, t, k, total = W.allocate(sfi, bits, tail)
         gwl, gN, gt, gk = B.at3p_host_allocate(sfi, bits, tail, path)
         assert (gN, gt, gk) == (N, t, k) and np.array_equal(gwl, wl), i
         nonmono += bool((np.diff(bits[:, :, 1:].astype(np.int64), axis=2) < 0).any())
         if i % 4 >= 2 and i < 400:   # the fit pattern over t, from the restatement's own pieces
-            fits = [_fits(sfi, bits, tail, tt) for tt in range(L.T_MIN, L.T_MAX + 1)]
+            fits = [_fits(sfi, bits, tail, tt) for tt in range(W.T_MIN, W.T_MAX + 1)]
             first = fits.index(True)
             refit += not all(fits[first:])
-            assert t == L.T_MIN + first
+            assert t == W.T_MIN + first
     assert nonmono >= 500 and refit >= 5, (nonmono, refit)
 
 
@@ -186,7 +186,7 @@ def _fits(sfi, bits, tail, t):
     N = 32 if N in (29, 30, 31) else N
     wl = np.maximum(want[:, :N], 1)
     p = {"N": N, "wl": [list(map(int, wl[ch])) for ch in range(nch)]}
-    return L.recount_bits(p, nch, bits, tail)[0] <= L.SIZE_BITS
+    return W.recount_bits(p, nch, bits, tail)[0] <= W.SIZE_BITS
 
 
 def test_host_allocate_symbol_and_flag():
@@ -218,10 +218,10 @@ def test_a_build_without_the_adaptive_writer_refuses_the_flag(tmp_path):
 def test_golden_choices_and_frame_digests():
     """tests/golden/at3p_alloc.npz (tools/gen_golden_at3p_alloc.py): (t*, k*, N) per frame and the SHA-256 of the restatement's
     frames: the definition does not drift"""
-    g = np.load(L.GOLDEN)
-    assert os.path.getsize(L.GOLDEN) < 100 * 1024
-    for name, nch in L.GOLDEN_CASES:
-        choice, digest = L.golden_entry(name, nch)
+    g = np.load(W.ALLOC_GOLDEN)
+    assert os.path.getsize(W.ALLOC_GOLDEN) < 100 * 1024
+    for name, nch in W.ALLOC_GOLDEN_CASES:
+        choice, digest = W.alloc_golden_entry(name, nch)
         assert np.array_equal(choice, g[f"{name}_{nch}_choice"]), (name, nch, choice.tolist())
         assert digest == str(g[f"{name}_{nch}_sha256"]), (name, nch)
 

@@ -1,5 +1,5 @@
 """Adaptive ATRAC3plus word lengths on the GPU (AT3PHIP_ALLOC_ADAPTIVE; include/at3phip.h, ADAPTIVE WORD LENGTHS): the frames of
-k_at3p_write_adaptive and k_at3p_write_adaptive_tonal equal the restatement tests/host/at3p_alloc_cpu.c bit for bit through
+k_at3p_write_adaptive and k_at3p_write_adaptive_tonal equal the restatement tests/host/at3p_writer_cpu.c bit for bit through
 every call that takes the flag, however the stream is split into calls, from host and device buffers, waiting and queued;
 without the flag the calls give the fixed writer's bytes; non-finite spectra stay in their stream; the decoder decodes the
 frames; the command-line tool writes them. 2 streams x 3 frames unless said otherwise."""
@@ -10,7 +10,7 @@ import wave
 import numpy as np
 import pytest
 
-import at3p_alloc_lib as L
+import at3p_writer_lib as W
 import at3p_gha_lib as G
 import at3p_tonal_lib as T
 import at3p_tonal_write_lib as TW
@@ -28,11 +28,11 @@ def B():
 
 def _specs(name, nch):
     """[S, F, C, 2048]: six frames of a signal's spectra, three per stream"""
-    return np.ascontiguousarray(L.specs_of(name, nch, S * F).reshape(S, F, nch, 2048))
+    return np.ascontiguousarray(W.specs_of(name, nch, S * F).reshape(S, F, nch, 2048))
 
 
 def _expect(specs, win=None, blocks=None):
-    return np.stack([L.write_adaptive(specs[s], None if win is None else win[s], None if blocks is None else blocks[s]) for s in range(specs.shape[0])])
+    return np.stack([W.write_adaptive(specs[s], win=None if win is None else win[s], blocks=None if blocks is None else blocks[s]) for s in range(specs.shape[0])])
 
 
 def _pcm(names, nch, n=F):
@@ -71,7 +71,7 @@ def test_write_frames_equal_the_restatement(B, name, nch, with_win):
 def test_write_frames_tonal_equal_the_restatement(B, nch):
     """records beside frames without one, the largest record on full-scale noise among them, with window flags"""
     blocks = [[TW.largest_block(nch), None, TW.case_blocks(f"small_{nch}")[0][0]], [TW.case_blocks(f"random_{nch}")[0][0], TW.largest_block(nch, 1), None]]
-    specs = np.stack([L.full_scale_noise(F, nch, seed=4), L.specs_of("mix", nch, F)])
+    specs = np.stack([W.full_scale_noise(F, nch, seed=4), W.specs_of("mix", nch, F)])
     win = np.ascontiguousarray(WIN[:, :, :nch])
     recs = np.stack([B.pack_tonal_blocks(row, nch) for row in blocks])
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch)
@@ -98,8 +98,8 @@ def test_encode_frames_and_s16_equal_the_restatement(B, nch):
         got16 = enc.encode_frames_s16(p16, adaptive=True)
     finally:
         enc.close()
-    assert np.array_equal(got, np.stack([L.write_adaptive(_specs_of_pcm(pcm[s])) for s in range(S)]))
-    assert np.array_equal(got16, np.stack([L.write_adaptive(_specs_of_pcm(as_float[s])) for s in range(S)]))
+    assert np.array_equal(got, np.stack([W.write_adaptive(_specs_of_pcm(pcm[s])) for s in range(S)]))
+    assert np.array_equal(got16, np.stack([W.write_adaptive(_specs_of_pcm(as_float[s])) for s in range(S)]))
 
 
 @pytest.mark.parametrize("gated,shared", [(False, False), (True, False), (False, True), (True, True)])
@@ -115,7 +115,7 @@ def test_encode_frames_tonal_equal_the_restatement(B, nch, gated, shared):
         enc.close()
     waves = 0
     for s in range(S):
-        frames, blocks, _ = G.pipeline(pcm[s], gated, shared, write=lambda specs, recs: L.write_adaptive(specs, None, recs))
+        frames, blocks, _ = G.pipeline(pcm[s], gated, shared, write=lambda specs, recs: W.write_adaptive(specs, blocks=recs))
         waves += sum(G.n_waves(b) for b in blocks[:-1])
         assert np.array_equal(got[s], frames), s
     assert waves > 0
@@ -145,7 +145,7 @@ def test_call_splits_device_buffers_and_queued_calls(B, nch):
         enc.close()
     assert np.array_equal(whole, parts) and np.array_equal(w_whole, w_parts)
     assert np.array_equal(d_out.cpu().numpy(), whole) and np.array_equal(d_q.cpu().numpy(), whole)
-    assert np.array_equal(whole, np.stack([L.write_adaptive(_specs_of_pcm(pcm[s])) for s in range(S)]))
+    assert np.array_equal(whole, np.stack([W.write_adaptive(_specs_of_pcm(pcm[s])) for s in range(S)]))
 
 
 @pytest.mark.parametrize("nch", [1, 2])
@@ -213,16 +213,16 @@ def test_without_the_flag_encode_frames_tonal_gives_the_parents_bytes(B, nch, ga
 def test_non_finite_spectra_stay_in_their_stream(B, nch):
     """NaN, +-inf and +-FLT_MAX, a unit of nothing but NaN, beside a normal stream: the call returns, the normal stream's frames are
     what they are alone, the odd stream's frames equal the restatement's"""
-    normal = L.specs_of("noise", nch, F)
-    specs = np.stack([L.odd_specs(nch, F), normal])
+    normal = W.specs_of("noise", nch, F)
+    specs = np.stack([W.odd_specs(nch, F), normal])
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch)
     try:
         got = enc.write_frames(specs, adaptive=True)
         alone = enc.write_frames(np.stack([normal, normal]), adaptive=True)
     finally:
         enc.close()
-    assert np.array_equal(got[1], alone[0]) and np.array_equal(got[1], L.write_adaptive(normal))
-    assert np.array_equal(got[0], L.write_adaptive(specs[0]))
+    assert np.array_equal(got[1], alone[0]) and np.array_equal(got[1], W.write_adaptive(normal))
+    assert np.array_equal(got[0], W.write_adaptive(specs[0]))
 
 
 @pytest.mark.parametrize("nch", [1, 2])
@@ -266,7 +266,7 @@ def test_cli_adaptive(B, tmp_path, nch):
     got = _oma_frames(oma)
     # the tool's schedule: the silent frame of the look-ahead, then the input's frames; its reader hands over int16 / 32768
     x = (pcm16.astype(np.float32) / np.float32(32768.0)).reshape(NF, 2048, nch)
-    want = np.concatenate([L.write_adaptive(np.zeros((1, nch, 2048), np.float32)), L.write_adaptive(_specs_of_pcm(x))[:NF - 1]])
+    want = np.concatenate([W.write_adaptive(np.zeros((1, nch, 2048), np.float32)), W.write_adaptive(_specs_of_pcm(x))[:NF - 1]])
     assert got.shape == (NF, 2048) and np.array_equal(got, want)
     r = subprocess.run([exe, "-d", "-i", oma, "-o", wav_out], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "Skipped" not in r.stdout + r.stderr, r.stdout + r.stderr
@@ -293,7 +293,7 @@ def test_cli_adaptive_with_tones(B, tmp_path, nch, extra):
     r = subprocess.run([exe, "-e", "atrac3plus", "-i", wav_in, "-o", oma, "--nostdout", "--adaptive", *extra, "--batch", "3"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     x = (pcm16.astype(np.float32) / np.float32(32768.0)).reshape(NF, 2048, nch)
-    want, blocks, _ = G.pipeline(x, "--gate" in extra, "--share" in extra, lambda specs, recs: L.write_adaptive(specs, None, recs))
+    want, blocks, _ = G.pipeline(x, "--gate" in extra, "--share" in extra, lambda specs, recs: W.write_adaptive(specs, blocks=recs))
     assert sum(G.n_waves(b) for b in blocks[:-1]) > 0
     assert np.array_equal(_oma_frames(oma), want)
     r = subprocess.run([exe, "-d", "-i", oma, "-o", wav_out], capture_output=True, text=True, timeout=300)
@@ -321,7 +321,7 @@ def test_largest_shape(B):
         enc.encode_frames_device(big_in.data_ptr(), nf, out.data_ptr(), adaptive=True)
     finally:
         enc.close()
-    want = np.stack([L.write_adaptive(_specs_of_pcm(pcm[r])) for r in range(P)])
+    want = np.stack([W.write_adaptive(_specs_of_pcm(pcm[r])) for r in range(P)])
     assert np.array_equal(out[0].cpu().numpy(), want[0]) and np.array_equal(out[big_s - 1].cpu().numpy(), want[(big_s - 1) % P])
     ref = torch.from_numpy(want).cuda()
     for r in range(P):

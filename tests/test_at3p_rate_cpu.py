@@ -1,5 +1,6 @@
 """ATRAC3plus at frame sizes other than 2048 bytes (include/at3phip.h, FRAME SIZE) without a GPU: the restatement
-tests/host/at3p_rate_cpu.c against the two older restatements at 2048 bytes; at3phip_host_allocate_sized against it; the two
+tests/host/at3p_writer_cpu.c against what the older restatements gave at 2048 bytes before they were folded into it
+(tests/golden/at3p_writer_fold.npz); at3phip_host_allocate_sized against it; the two
 smallest admissible sizes derived from the tables; every frame it writes at every size parsed, counted and decoded; the round trip
 per standard bitrate; the kernels through the CPU SIMT harness against it; a build without the adaptive writer; the containers'
 bytes and the command line's refusals."""
@@ -12,16 +13,15 @@ import subprocess
 import numpy as np
 import pytest
 
-import at3p_alloc_lib as L
+import at3p_writer_lib as W
 import at3p_decode_lib as D
 import at3p_gha_lib as G
-import at3p_rate_lib as R
 import at3p_tonal_lib as T
 import at3p_tonal_write_lib as TW
 from simt_harness_lib import CLANG, ROOT, Children, assert_clean, build_strict
 
 needs_clang = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's clang++ to compile the kernel sources for the host")
-NF = L.SNR_FRAMES
+NF = W.SNR_FRAMES
 HEADER = open(os.path.join(ROOT, "include", "at3phip.h")).read()
 
 _specs = {}
@@ -29,51 +29,63 @@ _specs = {}
 
 def _sp(name, nch):
     if (name, nch) not in _specs:
-        _specs[(name, nch)] = L.specs_of(name, nch, NF)
+        _specs[(name, nch)] = W.specs_of(name, nch, NF)
     return _specs[(name, nch)]
 
 
 # ---- the new restatement against the two old ones at 2048 bytes --------------------------------------------------------------------
 @pytest.mark.parametrize("nch", [1, 2])
 def test_restatement_equals_the_old_ones_at_2048_bytes(nch):
-    """frames: at3p_alloc_cpu.c on the signals, silence, full-scale noise, non-finite spectra, window flags and tonal records;
-    PCM and rejection counters: at3p_decode_cpu.c (no tones) and at3p_tonal_cpu.c (tones) on those frames, on frames with
-    flipped bits and on the crafted malformed frames of at3p_decode_lib"""
-    cases = [(L.specs_of(n, nch, 4), None, None) for n in L.SIGNALS + ("silence", "fullscale")]
-    cases.append((L.odd_specs(nch, 3), None, None))
-    cases.append((L.specs_of("noise", nch, 2), np.array([[0x01ef] * nch, [0xffff] * nch], np.uint16), None))
-    cases.append((np.concatenate([L.full_scale_noise(2, nch), _sp("mix", nch)[:1]]), None,
+    """tests/golden/at3p_writer_fold.npz holds, as SHA-256, what the restatements gave while each stated the writer and the decoder
+    for itself (at3p_alloc_cpu.c, at3p_rate_cpu.c; at3p_decode_cpu.c without tones, at3p_tonal_cpu.c with them), all equal then.
+    frames: on the signals, silence, full-scale noise, non-finite spectra, window flags and tonal records; PCM and rejection
+    counters: of the at3pd_*, at3pt_* and at3pw_* entry points on those frames, on frames with flipped bits and on the crafted
+    malformed frames of at3p_decode_lib"""
+    gold = W.fold_golden(nch)
+    cases = [(W.specs_of(n, nch, 4), None, None) for n in W.SIGNALS + ("silence", "fullscale")]
+    cases.append((W.odd_specs(nch, 3), None, None))
+    cases.append((W.specs_of("noise", nch, 2), np.array([[0x01ef] * nch, [0xffff] * nch], np.uint16), None))
+    cases.append((np.concatenate([W.full_scale_noise(2, nch), _sp("mix", nch)[:1]]), None,
                   [TW.largest_block(nch), None, TW.case_blocks(f"small_{nch}")[0][0]]))
+
+    def same(label, *got):
+        assert np.array_equal(W.sha(*got), gold[label]), label
+
     rng = np.random.default_rng(11)
-    for sp, win, blocks in cases:
-        old = L.write_adaptive(sp, win, blocks)
-        new = R.write_adaptive(sp, 2048, win, blocks)
-        assert np.array_equal(old, new)
+    for i, (sp, win, blocks) in enumerate(cases):
+        new = W.write_adaptive(sp, 2048, False, win, blocks)
+        same(f"a{i}_2048_frames", new)
         flipped = D.mutate_frames(new, rng, n_flips=2)
-        for frames in (new, flipped):
+        same(f"a{i}_2048_flipped_in", flipped)
+        for kind, frames in (("plain", new), ("flipped", flipped)):
             for tones in (False, True):
                 a, ra = T.cpu_tonal_decode(frames, nch, tones=tones)
-                b, rb = R.decode(frames, nch, tones)
-                assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.array_equal(ra, rb), (tones, ra, rb)
+                b, rb = W.decode(frames, nch, tones)
+                same(f"a{i}_2048_{kind}_tones{int(tones)}", a.view(np.uint32), ra)
+                same(f"a{i}_2048_{kind}_tones{int(tones)}", b.view(np.uint32), rb)
             a, ra = D.cpu_decode(frames, nch)
-            b, rb = R.decode(frames, nch, False)
-            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.array_equal(ra, rb)
+            same(f"a{i}_2048_{kind}_tones0", a.view(np.uint32), ra)
     crafted, _ = D.crafted_frames(nch, 3)
+    same("b_in", crafted)
     a, ra = D.cpu_decode(crafted, nch)
-    b, rb = R.decode(crafted, nch, False)
-    assert (ra[[0, 1, 2, 3, 4, 5]] > 0).all() and np.array_equal(ra, rb) and np.array_equal(a.view(np.uint32), b.view(np.uint32)), (ra, rb)
+    b, rb = W.decode(crafted, nch, False)
+    assert (ra[[0, 1, 2, 3, 4, 5]] > 0).all()
+    same("b_tones0", a.view(np.uint32), ra)
+    same("b_tones0", b.view(np.uint32), rb)
     a, ra = T.cpu_tonal_decode(crafted, nch, tones=True)
-    b, rb = R.decode(crafted, nch, True)
-    assert np.array_equal(ra, rb) and np.array_equal(a.view(np.uint32), b.view(np.uint32)), (ra, rb)
+    b, rb = W.decode(crafted, nch, True)
+    same("b_tones1", a.view(np.uint32), ra)
+    same("b_tones1", b.view(np.uint32), rb)
     # the fields of every frame, accepted or not
     _, _, fo = D.unpack(crafted, nch)
-    _, _, fn = R.unpack(crafted, nch)
-    assert np.array_equal(fo["reason"], fn["reason"])
+    _, _, fn = W.unpack(crafted, nch)
+    same("b_fields0", fo.view(np.uint8))
+    same("b_fields0", fn.view(np.uint8))
 
 
 # ---- at3phip_host_allocate_sized ---------------------------------------------------------------------------------------------------
 def _budgets(nch):
-    return (R.MIN_BYTES[nch], 376, 2048)
+    return (W.MIN_BYTES[nch], 376, 2048)
 
 
 @needs_clang
@@ -81,14 +93,14 @@ def test_host_allocate_sized_equals_the_restatement_on_the_signals():
     from atracdenc_amd import binding as B
     path = build_strict()
     n = 0
-    for name in L.SIGNALS + ("silence", "fullscale"):
+    for name in W.SIGNALS + ("silence", "fullscale"):
         for nch in (1, 2):
-            sp = L.specs_of(name, nch, 4)
+            sp = W.specs_of(name, nch, 4)
             for f in (0, 3):
-                sfi, bits, _ = L.cost_table(sp[f])
+                sfi, bits, _ = W.cost_table(sp[f])
                 for fb in _budgets(nch):
-                    for tail in (8, 700, R.worst_tail(nch)):
-                        wl, N, t, k, _ = R.allocate(sfi, bits, tail, fb)
+                    for tail in (8, 700, W.worst_tail(nch)):
+                        wl, N, t, k, _ = W.allocate(sfi, bits, tail, fb)
                         gwl, gN, gt, gk = B.at3p_host_allocate(sfi, bits, tail, path, frame_bytes=fb)
                         assert (gN, gt, gk) == (N, t, k) and np.array_equal(gwl, wl), (name, nch, f, fb, tail)
                         n += 1
@@ -101,7 +113,7 @@ def test_host_allocate_sized_equals_the_restatement_on_random_tables():
     tests/test_at3p_alloc_cpu.py builds them; at3phip_host_allocate is the sized call at 2048, and the old restatement's too"""
     from atracdenc_amd import binding as B
     path = build_strict()
-    tables = L.random_cost_tables()
+    tables = W.random_cost_tables()
     nonmono = sum(bool((np.diff(b[:, :, 1:].astype(np.int64), axis=2) < 0).any()) for _, b, _ in tables)
     assert len(tables) == 1000 and nonmono >= 500
     differ = 0
@@ -110,13 +122,13 @@ def test_host_allocate_sized_equals_the_restatement_on_random_tables():
         got = {}
         for fb in _budgets(nch):
             tb = min(tail, 8 * fb - 3)
-            wl, N, t, k, _ = R.allocate(sfi, bits, tb, fb)
+            wl, N, t, k, _ = W.allocate(sfi, bits, tb, fb)
             gwl, gN, gt, gk = B.at3p_host_allocate(sfi, bits, tb, path, frame_bytes=fb)
             assert (gN, gt, gk) == (N, t, k) and np.array_equal(gwl, wl), (i, fb)
             got[fb] = (gwl, gN, gt, gk)
         pwl, pN, pt, pk = B.at3p_host_allocate(sfi, bits, tail, path)
         assert (pN, pt, pk) == got[2048][1:] and np.array_equal(pwl, got[2048][0]), i
-        owl, oN, ot, ok, _ = L.allocate(sfi, bits, tail)
+        owl, oN, ot, ok, _ = W.allocate(sfi, bits, tail)
         assert (oN, ot, ok) == got[2048][1:] and np.array_equal(owl, got[2048][0]), i
         differ += got[376][1:] != got[2048][1:]
     assert differ >= 500, differ   # (the budget matters on these tables)
@@ -126,15 +138,15 @@ def test_host_allocate_sized_equals_the_restatement_on_random_tables():
 def test_host_allocate_sized_refuses_what_is_not_admissible():
     from atracdenc_amd import binding as B
     path = build_strict()
-    sfi, bits, _ = L.cost_table(_sp("mix", 2)[0])
-    for fb in (0, 7, 2056, R.MIN_BYTES[2] - 8, 380):
+    sfi, bits, _ = W.cost_table(_sp("mix", 2)[0])
+    for fb in (0, 7, 2056, W.MIN_BYTES[2] - 8, 380):
         with pytest.raises(B.At3HipError):
             B.at3p_host_allocate(sfi, bits, 8, path, frame_bytes=fb)
     with pytest.raises(B.At3HipError):
         B.at3p_host_allocate(sfi, bits, 8 * 376 - 2, path, frame_bytes=376)     # a tail beyond the budget
-    B.at3p_host_allocate(sfi[:1], bits[:1], 8, path, frame_bytes=R.MIN_BYTES[1])   # (mono's minimum is below stereo's)
+    B.at3p_host_allocate(sfi[:1], bits[:1], 8, path, frame_bytes=W.MIN_BYTES[1])   # (mono's minimum is below stereo's)
     with pytest.raises(B.At3HipError):
-        B.at3p_host_allocate(sfi, bits, 8, path, frame_bytes=R.MIN_BYTES[1])
+        B.at3p_host_allocate(sfi, bits, 8, path, frame_bytes=W.MIN_BYTES[1])
 
 
 # ---- the smallest admissible sizes -------------------------------------------------------------------------------------------------
@@ -142,16 +154,16 @@ def test_min_frame_bytes_follow_from_the_tables():
     """front of A(63, 0) at its worst + the tail at its worst <= 8 * bytes - 3, smallest multiple of 8: the header's constants, its
     figures, the binding's constants and this module's"""
     from atracdenc_amd import binding as B
-    assert (R.worst_front_one_unit(1), R.worst_tail(1), R.worst_front_one_unit(2), R.worst_tail(2)) == (77, 1320, 147, 1624)
+    assert (W.worst_front_one_unit(1), W.worst_tail(1), W.worst_front_one_unit(2), W.worst_tail(2)) == (77, 1320, 147, 1624)
     for nch, macro in ((1, "AT3PHIP_MIN_FRAME_BYTES_MONO"), (2, "AT3PHIP_MIN_FRAME_BYTES_STEREO")):
-        m = R.min_frame_bytes(nch)
-        need = R.worst_front_one_unit(nch) + R.worst_tail(nch)
+        m = W.min_frame_bytes(nch)
+        need = W.worst_front_one_unit(nch) + W.worst_tail(nch)
         assert m % 8 == 0 and need <= 8 * m - 3 and need > 8 * (m - 8) - 3
-        assert int(re.search(rf"#define {macro} (\d+)", HEADER).group(1)) == m == R.MIN_BYTES[nch] == getattr(B, macro)
+        assert int(re.search(rf"#define {macro} (\d+)", HEADER).group(1)) == m == W.MIN_BYTES[nch] == getattr(B, macro)
     for fig in ("77 bits in mono, 147 in stereo", "1320 bits\n * in mono, 1624 in stereo", "77 + 1320 = 1397", "147 + 1624 = 1771"):
         assert fig in HEADER, fig
     # every size of the command line's table is admissible for the channel counts it serves
-    assert all(fb >= R.MIN_BYTES[2] or kb == 32 for kb, fb in R.BITRATES.items()) and R.BITRATES[32] >= R.MIN_BYTES[1]
+    assert all(fb >= W.MIN_BYTES[2] or kb == 32 for kb, fb in W.BITRATES.items()) and W.BITRATES[32] >= W.MIN_BYTES[1]
 
 
 @pytest.mark.parametrize("nch", [1, 2])
@@ -159,15 +171,15 @@ def test_largest_record_on_full_scale_fits_the_smallest_frame(nch):
     """48 waves, both envelope points everywhere, (in stereo) the long sharing form, on full-scale noise, at the smallest
     admissible size: t* = 63 is never needed past its definition, the frame fits, decodes with its tones, and the record is
     found again field for field"""
-    fb, big = R.MIN_BYTES[nch], TW.largest_block(nch)
-    sp = L.full_scale_noise(2, nch)
-    frames, rec = R.write_adaptive(sp, fb, None, [big, big], info=True)
-    tail = sum(n for _, n in L.tail_bits_list(nch, None, big))
-    assert tail > 1000 and (rec["bits"] <= 8 * fb - 3).all() and (rec["t"] <= L.T_MAX).all()
-    pcm, rej = R.decode(frames, nch, True)
+    fb, big = W.MIN_BYTES[nch], TW.largest_block(nch)
+    sp = W.full_scale_noise(2, nch)
+    frames, rec, _ = W.write_adaptive(sp, fb, blocks=[big, big], info=True)
+    tail = sum(n for _, n in W.tail_bits_list(nch, None, big))
+    assert tail > 1000 and (rec["bits"] <= 8 * fb - 3).all() and (rec["t"] <= W.T_MAX).all()
+    pcm, rej = W.decode(frames, nch, True)
     assert rej.sum() == 0, rej
     for f in range(2):
-        assert L.terminator_pos(frames[f]) == 3 + rec["bits"][f] - 1 < 8 * fb
+        assert W.terminator_pos(frames[f]) == 3 + rec["bits"][f] - 1 < 8 * fb
     padded = np.zeros((2, 2048), np.uint8)
     padded[:, :fb] = frames
     specs, win, recs, why = T.unpack_tonal(padded, nch)
@@ -176,25 +188,25 @@ def test_largest_record_on_full_scale_fits_the_smallest_frame(nch):
 
 # ---- every frame at every size -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nch", [1, 2])
-@pytest.mark.parametrize("name", L.SIGNALS)
+@pytest.mark.parametrize("name", W.SIGNALS)
 def test_frames_parse_count_and_decode_at_every_size(name, nch):
-    """14 frames of each signal at every test size: the independent head parser of at3p_alloc_lib reads N outside 29..31 and word
+    """14 frames of each signal at every test size: the independent head parser of at3p_writer_lib reads N outside 29..31 and word
     lengths 1..7; Bits(A), recounted from the parsed fields, is the restatement's figure and at most 8 * frame_bytes - 3; the
     terminator sits where the count says; the decoder restatement rejects no frame"""
     sp = _sp(name, nch)
-    tail = sum(n for _, n in L.tail_bits_list(nch))
-    costs = [L.cost_table(sp[f])[1] for f in range(NF)]
-    for fb in R.SIZES[nch]:
-        frames, rec = R.write_adaptive(sp, fb, info=True)
+    tail = sum(n for _, n in W.tail_bits_list(nch))
+    costs = [W.cost_table(sp[f])[1] for f in range(NF)]
+    for fb in W.SIZES[nch]:
+        frames, rec, _ = W.write_adaptive(sp, fb, info=True)
         assert frames.shape == (NF, fb)
-        assert R.decode(frames, nch)[1].sum() == 0
+        assert W.decode(frames, nch)[1].sum() == 0
         for f in range(NF):
-            p = L.parse_frame(frames[f], nch)
+            p = W.parse_head(frames[f], nch)
             assert p["N"] not in (29, 30, 31) and p["N"] == rec["num_quant_units"][f]
             assert all(1 <= w <= 7 for row in p["wl"] for w in row)
-            total, _ = L.recount_bits(p, nch, costs[f], tail)
+            total, _ = W.recount_bits(p, nch, costs[f], tail)
             assert total == rec["bits"][f] <= 8 * fb - 3, (fb, f, total)
-            assert L.terminator_pos(frames[f]) == 3 + total - 1 < 8 * fb
+            assert W.terminator_pos(frames[f]) == 3 + total - 1 < 8 * fb
 
 
 # ---- round trip per standard bitrate -------------------------------------------------------------------------------------------------
@@ -229,15 +241,15 @@ SECTION_19 = {("noise", 1): [29.97], ("noise", 2): [19.98, 20.04], ("mix", 1): [
 
 
 @pytest.mark.parametrize("nch", [1, 2])
-@pytest.mark.parametrize("name", L.SIGNALS)
+@pytest.mark.parametrize("name", W.SIGNALS)
 def test_round_trip_snr_per_bitrate(name, nch):
     sp, x = _sp(name, nch), G.signal_pcm(name, NF, nch)
     row = {}
-    for kbit, fb in R.BITRATES.items():
-        if fb < R.MIN_BYTES[nch]:
+    for kbit, fb in W.BITRATES.items():
+        if fb < W.MIN_BYTES[nch]:
             continue     # 32 kbit/s is a mono rate
-        frames, rec = R.write_adaptive(sp, fb, info=True)
-        y, rej = R.decode(frames, nch)
+        frames, rec, _ = W.write_adaptive(sp, fb, info=True)
+        y, rej = W.decode(frames, nch)
         assert rej.sum() == 0
         row[fb] = [G.snr_db(x[:, :, c].reshape(-1), y[:, :, c].reshape(-1), NF) for c in range(nch)]
         print(f"round trip {name} x{nch} {kbit} kbit/s ({fb} bytes): {' / '.join(f'{v:.2f}' for v in row[fb])} dB, mean bits {rec['bits'].mean():.0f} "
@@ -331,10 +343,10 @@ def test_container_bytes_per_bitrate(host_io, tmp_path, nch):
     """the writers of at3hip_io.hpp at every table size, parsed here: the OMA codec word's (frame_bytes - 8) / 8 and channel id, the
     RIFF block_align, byte_rate, fact samples and data size, and the three files' lengths"""
     n = 3
-    for kbit, fb in R.BITRATES.items():
-        if fb < R.MIN_BYTES[nch]:
+    for kbit, fb in W.BITRATES.items():
+        if fb < W.MIN_BYTES[nch]:
             continue
-        frames = R.write_adaptive(_sp("mix", nch)[:n], fb)
+        frames = W.write_adaptive(_sp("mix", nch)[:n], fb)
         body = frames.tobytes()
         files = {}
         for kind, ext in ((5, "oma"), (6, "at3"), (7, "raw")):
@@ -379,11 +391,11 @@ def test_cli_refusals(tmp_path):
     r = _cli("-e", "atrac3plus", "-i", stereo, "-o", out, "--bitrate", "64")
     assert r.returncode != 0 and "--bitrate 64 needs --adaptive" in r.stderr and "fixed word-length table is defined for 2048-byte frames" in r.stderr
     r = _cli("-e", "atrac3plus", "-i", stereo, "-o", out, "--adaptive", "--bitrate", "100")
-    assert r.returncode != 0 and all(f"{kb}" in r.stderr and f"-> {fb} bytes" in r.stderr for kb, fb in R.BITRATES.items()), r.stderr
+    assert r.returncode != 0 and all(f"{kb}" in r.stderr and f"-> {fb} bytes" in r.stderr for kb, fb in W.BITRATES.items()), r.stderr
     r = _cli("-e", "atrac3plus", "-i", stereo, "-o", out, "--adaptive", "--bitrate", "32")
     assert r.returncode != 0 and r.stderr.startswith("Fatal error: --bitrate 32 is a mono rate"), r.stderr
     assert not os.path.exists(out) or os.path.getsize(out) == 0
-    frames = R.write_adaptive(_sp("mix", 2)[:2], 376)
+    frames = W.write_adaptive(_sp("mix", 2)[:2], 376)
     p = tmp_path / "odd.oma"
     p.write_bytes(D.oma_bytes(np.zeros((2, 384), np.uint8), 2, frame_bytes=384))
     r = _cli("-d", "-i", str(p), "-o", str(tmp_path / "z.wav"))

@@ -1,5 +1,5 @@
 """ATRAC3plus at frame sizes other than 2048 bytes on the GPU (at3phip_set_frame_bytes, at3phip_decoder_set_frame_bytes; include/
-at3phip.h, FRAME SIZE): the adaptive writers' frames and the decoder's PCM equal the restatement tests/host/at3p_rate_cpu.c bit for
+at3phip.h, FRAME SIZE): the adaptive writers' frames and the decoder's PCM equal the restatement tests/host/at3p_writer_cpu.c bit for
 bit at every test size through every call, from host and device buffers, queued and waiting, however the stream is split; the
 fixed table is refused at any size but 2048; the setter refuses what is not admissible; a context that never changes its size, or
 changes back, gives the bytes it always gave; the command line writes and reads the standard bitrates.
@@ -13,15 +13,14 @@ import wave
 import numpy as np
 import pytest
 
-import at3p_alloc_lib as L
+import at3p_writer_lib as W
 import at3p_gha_lib as G
-import at3p_rate_lib as R
 import at3p_tonal_write_lib as TW
 from at3_testlib import at3p_mdct, at3p_pqf, at3p_write_frames
 
 pytestmark = pytest.mark.gpu
 S, F = 3, 4
-CASES = [(nch, fb) for nch in (1, 2) for fb in R.SIZES[nch]]
+CASES = [(nch, fb) for nch in (1, 2) for fb in W.SIZES[nch]]
 IDS = [f"{'mono' if nch == 1 else 'stereo'}_{fb}" for nch, fb in CASES]
 SENTINEL = 0xA5
 
@@ -98,7 +97,7 @@ def test_six_calls_equal_the_restatement(B, nch, fb):
     p16, pcm, specs = _plain(nch)
     t16, tpcm, tspecs, trecs = _tonal(nch)
     win, blocks = np.ascontiguousarray(WIN[:, :, :nch]), _records(nch)
-    wspecs = np.stack([L.full_scale_noise(F, nch, seed=4), L.specs_of("mix", nch, F), L.specs_of("silence", nch, F)])
+    wspecs = np.stack([W.full_scale_noise(F, nch, seed=4), W.specs_of("mix", nch, F), W.specs_of("silence", nch, F)])
     recs = np.stack([B.pack_tonal_blocks(row, nch) for row in blocks])
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch, frame_bytes=fb)
     try:
@@ -116,11 +115,11 @@ def test_six_calls_equal_the_restatement(B, nch, fb):
         enc.close()
     for g in (got_w, got_t, got_e, got_e16, got_a, got_a16):
         assert g.shape == (S, F, fb)
-    assert np.array_equal(got_w, R.write_streams(wspecs, fb, win))
-    assert np.array_equal(got_t, np.stack([R.write_adaptive(wspecs[s], fb, win[s], blocks[s]) for s in range(S)]))
-    want_e = R.write_streams(specs, fb)
+    assert np.array_equal(got_w, W.write_streams(wspecs, fb, win=win))
+    assert np.array_equal(got_t, np.stack([W.write_adaptive(wspecs[s], fb, win=win[s], blocks=blocks[s]) for s in range(S)]))
+    want_e = W.write_streams(specs, fb)
     assert np.array_equal(got_e, want_e) and np.array_equal(got_e16, want_e)
-    want_a = np.stack([R.write_adaptive(tspecs[s], fb, None, trecs[s]) for s in range(S)])
+    want_a = np.stack([W.write_adaptive(tspecs[s], fb, blocks=trecs[s]) for s in range(S)])
     assert np.array_equal(got_a, want_a) and np.array_equal(got_a16, want_a)
 
 
@@ -130,7 +129,7 @@ def test_device_buffers_queued_calls_and_splits(B, nch, fb):
     directly behind every [S][F][frame_bytes] output stay what they were"""
     import torch
     p16, pcm, specs = _plain(nch)
-    want = R.write_streams(specs, fb)
+    want = W.write_streams(specs, fb)
     n = S * F * fb
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch, frame_bytes=fb)
     try:
@@ -179,8 +178,8 @@ def test_device_buffers_queued_calls_and_splits(B, nch, fb):
         assert (g[n:] == SENTINEL).all()
     for k in range(3):
         assert np.array_equal(got[k][:n].reshape(S, F, fb), want), k
-    t_want = np.stack([R.write_adaptive(tspecs[s], fb, None, trecs[s]) for s in range(S)])
-    wt_want = np.stack([R.write_adaptive(specs[s], fb, None, blocks[s]) for s in range(S)])
+    t_want = np.stack([W.write_adaptive(tspecs[s], fb, blocks=trecs[s]) for s in range(S)])
+    wt_want = np.stack([W.write_adaptive(specs[s], fb, blocks=blocks[s]) for s in range(S)])
     assert np.array_equal(got[3][:n].reshape(S, F, fb), t_want) and np.array_equal(got[4][:n].reshape(S, F, fb), t_want)
     assert np.array_equal(got[5][:n].reshape(S, F, fb), want) and np.array_equal(got[6][:n].reshape(S, F, fb), wt_want)
     assert np.array_equal(parts, want) and np.array_equal(parts16, want) and np.array_equal(w_parts, want)
@@ -191,7 +190,7 @@ def test_odd_stride_mono_192_from_device_buffers(B):
     """mono, 5 streams x 3 frames of 192 bytes: frame offsets that are no multiple of 2048 or 256"""
     import torch
     S5, F3, fb = 5, 3, 192
-    specs = np.ascontiguousarray(L.specs_of("mix", 1, S5 * F3).reshape(S5, F3, 1, 2048))
+    specs = np.ascontiguousarray(W.specs_of("mix", 1, S5 * F3).reshape(S5, F3, 1, 2048))
     enc = B.At3pHip(n_streams=S5, max_frames=F3, channels=1, frame_bytes=fb)
     dec = B.At3pHipDecoder(n_streams=S5, channels=1, max_frames=F3, frame_bytes=fb)
     try:
@@ -207,9 +206,9 @@ def test_odd_stride_mono_192_from_device_buffers(B):
     finally:
         enc.close()
         dec.close()
-    want = R.write_streams(specs, fb)
+    want = W.write_streams(specs, fb)
     assert (got[S5 * F3 * fb:] == SENTINEL).all() and np.array_equal(got[:S5 * F3 * fb].reshape(S5, F3, fb), want)
-    epcm, _ = R.decode_streams(want, 1)
+    epcm, _ = W.decode_streams(want, 1)
     assert np.array_equal(pcm.view(np.uint32), epcm.view(np.uint32))
 
 
@@ -237,7 +236,7 @@ def test_unflagged_calls_are_refused_at_376_and_write_nothing(B, nch):
         got = enc.encode_frames(pcm, adaptive=True)
     finally:
         enc.close()
-    assert np.array_equal(got, R.write_streams(specs, 376))
+    assert np.array_equal(got, W.write_streams(specs, 376))
 
 
 @pytest.mark.parametrize("nch", [1, 2])
@@ -246,12 +245,12 @@ def test_setter_refuses_inadmissible_sizes(B, nch):
     dec = B.At3pHipDecoder(n_streams=1, channels=nch, max_frames=1, frame_bytes=376)
     try:
         for obj in (enc, dec):
-            for bad in (0, 7, 2056, R.MIN_BYTES[nch] - 8, -8, 380):
+            for bad in (0, 7, 2056, W.MIN_BYTES[nch] - 8, -8, 380):
                 with pytest.raises(B.At3HipError, match=r"\(-1\).*frame_bytes"):
                     obj.set_frame_bytes(bad)
                 assert obj.frame_bytes == 376
-            obj.set_frame_bytes(R.MIN_BYTES[nch])
-            assert obj.frame_bytes == R.MIN_BYTES[nch]
+            obj.set_frame_bytes(W.MIN_BYTES[nch])
+            assert obj.frame_bytes == W.MIN_BYTES[nch]
         lib = enc.lib
         assert lib.at3phip_set_frame_bytes(None, 376) == -1 and lib.at3phip_decoder_set_frame_bytes(None, 376) == -1
         v = ctypes.c_int32(5)
@@ -276,7 +275,7 @@ def test_explicit_2048_equals_an_untouched_context(B, nch):
     for x, y in zip(*got):
         assert np.array_equal(x, y)
     assert np.array_equal(got[1][0], np.stack([at3p_write_frames(specs[s]) for s in range(S)]))
-    assert np.array_equal(got[1][1], np.stack([L.write_adaptive(specs[s]) for s in range(S)]))
+    assert np.array_equal(got[1][1], np.stack([W.write_adaptive(specs[s]) for s in range(S)]))
 
 
 @pytest.mark.parametrize("nch", [1, 2])
@@ -305,21 +304,21 @@ def test_a_stream_may_change_its_size_between_calls(B, nch):
             e.close()
     assert second.shape == (S, 1, 376) and third.shape == (S, 2, 2048)
     assert np.array_equal(first, whole[2048][:, :2]) and np.array_equal(second, whole[376][:, 2:3]) and np.array_equal(third, whole[2048][:, 3:])
-    assert np.array_equal(whole[376], R.write_streams(specs, 376)) and np.array_equal(whole[2048], R.write_streams(specs, 2048))
+    assert np.array_equal(whole[376], W.write_streams(specs, 376)) and np.array_equal(whole[2048], W.write_streams(specs, 2048))
 
 
 @pytest.mark.parametrize("nch", [1, 2])
 def test_non_finite_spectra_stay_in_their_stream_at_376(B, nch):
-    normal = L.specs_of("noise", nch, F)
-    specs = np.stack([L.odd_specs(nch, F), normal, L.specs_of("mix", nch, F)])
+    normal = W.specs_of("noise", nch, F)
+    specs = np.stack([W.odd_specs(nch, F), normal, W.specs_of("mix", nch, F)])
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch, frame_bytes=376)
     try:
         got = enc.write_frames(specs, adaptive=True)
         alone = enc.write_frames(np.stack([normal, normal, normal]), adaptive=True)
     finally:
         enc.close()
-    assert np.array_equal(got[1], alone[0]) and np.array_equal(got[1], R.write_adaptive(normal, 376))
-    assert np.array_equal(got, R.write_streams(specs, 376))
+    assert np.array_equal(got[1], alone[0]) and np.array_equal(got[1], W.write_adaptive(normal, 376))
+    assert np.array_equal(got, W.write_streams(specs, 376))
 
 
 # ---- the decoder -------------------------------------------------------------------------------------------------------------------
@@ -328,13 +327,13 @@ def test_decoder_equals_the_restatement(B, nch, fb):
     """the frames of the writer tests (records among them) through at3phip_decode: float and int16, tones on and off (off: the
     frames with a block are rejected and counted), one call against 1 + 3"""
     win, blocks = np.ascontiguousarray(WIN[:, :, :nch]), _records(nch)
-    wspecs = np.stack([L.full_scale_noise(F, nch, seed=4), L.specs_of("mix", nch, F), L.specs_of("silence", nch, F)])
-    frames = np.stack([R.write_adaptive(wspecs[s], fb, win[s], blocks[s]) for s in range(S)])
+    wspecs = np.stack([W.full_scale_noise(F, nch, seed=4), W.specs_of("mix", nch, F), W.specs_of("silence", nch, F)])
+    frames = np.stack([W.write_adaptive(wspecs[s], fb, win=win[s], blocks=blocks[s]) for s in range(S)])
     dec = B.At3pHipDecoder(n_streams=S, channels=nch, max_frames=F, frame_bytes=fb)
     try:
         assert dec.frame_bytes == fb
         for tones in (True, False):
-            want, rej = R.decode_streams(frames, nch, tones)
+            want, rej = W.decode_streams(frames, nch, tones)
             dec.reset()
             got = dec.decode(frames, tones=tones)
             cnt = dec.counters(reset=True)
@@ -356,8 +355,8 @@ def test_decoder_may_change_its_size_between_queued_calls(B, nch):
     """a queued at3phip_decode at 2048 bytes, at3phip_decoder_set_frame_bytes(376) - which waits for it -, a queued decode at 376 on
     the same streams, and back: the restatement's PCM for the stream as a whole (the synthesis state carries over the changes)"""
     import torch
-    specs = np.stack([L.specs_of(name, nch, 6) for name in ("mix", "noise", "tones")])
-    parts = [R.write_streams(specs[:, :2], 2048), R.write_streams(specs[:, 2:4], 376), R.write_streams(specs[:, 4:], 2048)]
+    specs = np.stack([W.specs_of(name, nch, 6) for name in ("mix", "noise", "tones")])
+    parts = [W.write_streams(specs[:, :2], 2048), W.write_streams(specs[:, 2:4], 376), W.write_streams(specs[:, 4:], 2048)]
     dec = B.At3pHipDecoder(n_streams=S, channels=nch, max_frames=2)
     try:
         d_in = [torch.from_numpy(p).cuda() for p in parts]
@@ -373,7 +372,7 @@ def test_decoder_may_change_its_size_between_queued_calls(B, nch):
     finally:
         dec.close()
     for s in range(S):
-        ref = R.RateDecoder(nch)
+        ref = W.Decoder(nch)
         want = np.concatenate([ref.decode(p[s]) for p in parts])
         assert np.array_equal(got[s].view(np.uint32), want.view(np.uint32)), s
 
@@ -382,8 +381,8 @@ def test_decoder_may_change_its_size_between_queued_calls(B, nch):
 def test_decoder_at_376_on_the_first_bytes_of_2048_byte_frames(B, nch):
     """frames written at 2048 bytes, cut to their first 376: the rejection counters per reason and the PCM equal the restatement's
     (full frames run past the end; a frame that ends early enough still decodes)"""
-    specs = np.stack([L.specs_of("mix", nch, F), L.specs_of("silence", nch, F), L.quiet_mono(F).repeat(nch, axis=1) * np.float32(2.0 ** -6)])
-    full = R.write_streams(specs, 2048)
+    specs = np.stack([W.specs_of("mix", nch, F), W.specs_of("silence", nch, F), W.quiet_mono(F).repeat(nch, axis=1) * np.float32(2.0 ** -6)])
+    full = W.write_streams(specs, 2048)
     cut = np.ascontiguousarray(full[:, :, :376])
     dec = B.At3pHipDecoder(n_streams=S, channels=nch, max_frames=F, frame_bytes=376)
     try:
@@ -391,7 +390,7 @@ def test_decoder_at_376_on_the_first_bytes_of_2048_byte_frames(B, nch):
         cnt = dec.counters()
     finally:
         dec.close()
-    want, rej = R.decode_streams(cut, nch, True)
+    want, rej = W.decode_streams(cut, nch, True)
     assert list(cnt.values()) == rej.tolist() and rej[4] >= F, (cnt, rej)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
@@ -433,7 +432,7 @@ def test_cli_bitrate_64(B, tmp_path, container):
         body = data[pos + 8:]
     got = np.frombuffer(body, np.uint8).reshape(NF, fb)
     x = (pcm16.astype(np.float32) / np.float32(32768.0)).reshape(NF, 2048, nch)
-    want = np.concatenate([R.write_adaptive(np.zeros((1, nch, 2048), np.float32), fb), R.write_adaptive(_specs_of_pcm(x), fb)[:NF - 1]])
+    want = np.concatenate([W.write_adaptive(np.zeros((1, nch, 2048), np.float32), fb), W.write_adaptive(_specs_of_pcm(x), fb)[:NF - 1]])
     assert np.array_equal(got, want)
     r = _run(exe, "-d", "-i", out, "-o", wav_out)
     assert r.returncode == 0 and "Skipped" not in r.stdout + r.stderr, r.stdout + r.stderr
@@ -459,7 +458,7 @@ def test_cli_bitrate_with_tones_gate_share(B, tmp_path):
     r = _run(exe, "-e", "atrac3plus", "-i", wav_in, "-o", oma, "--nostdout", "--adaptive", "--bitrate", "96", "--tones", "--gate", "--share", "--batch", "3")
     assert r.returncode == 0, r.stderr
     x = (pcm16.astype(np.float32) / np.float32(32768.0)).reshape(NF, 2048, nch)
-    want, blocks, _ = G.pipeline(x, True, True, lambda specs, recs: R.write_adaptive(specs, fb, None, recs))
+    want, blocks, _ = G.pipeline(x, True, True, lambda specs, recs: W.write_adaptive(specs, fb, blocks=recs))
     assert sum(G.n_waves(b) for b in blocks[:-1]) > 0
     data = open(oma, "rb").read()
     assert len(data) == 96 + NF * fb and np.array_equal(np.frombuffer(data[96:], np.uint8).reshape(NF, fb), want)
@@ -470,7 +469,7 @@ def test_cli_bitrate_with_tones_gate_share(B, tmp_path):
     r = _run(exe, "-e", "atrac3plus", "-i", wav_in, "-o", oma, "--nostdout", "--adaptive", "--bitrate", "32")
     assert r.returncode == 0, r.stderr
     xm = (mono16.astype(np.float32) / np.float32(32768.0)).reshape(NF, 2048, 1)
-    wm = np.concatenate([R.write_adaptive(np.zeros((1, 1, 2048), np.float32), 192), R.write_adaptive(_specs_of_pcm(xm), 192)[:NF - 1]])
+    wm = np.concatenate([W.write_adaptive(np.zeros((1, 1, 2048), np.float32), 192), W.write_adaptive(_specs_of_pcm(xm), 192)[:NF - 1]])
     data = open(oma, "rb").read()
     assert len(data) == 96 + NF * 192 and np.array_equal(np.frombuffer(data[96:], np.uint8).reshape(NF, 192), wm)
     r = _run(exe, "-d", "-i", oma, "-o", wav_out)

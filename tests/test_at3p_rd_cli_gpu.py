@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import at3p_gha_lib as G
-import at3p_rd_lib as RD
+import at3p_writer_lib as W
 
 pytestmark = pytest.mark.gpu
 NF, FB = 9, 376
@@ -45,7 +45,7 @@ def test_cli_rd(tmp_path, nch):
     dec = B.At3pHipDecoder(n_streams=1, channels=nch, max_frames=NF, frame_bytes=FB)
     try:
         lib_frames = enc.encode_frames(x, adaptive=True, sparse=True, rd=True)[0]
-        want = np.concatenate([RD.write_rd(np.zeros((1, nch, 2048), np.float32), FB), lib_frames[:NF - 1]])   # the host's one-frame lead-in
+        want = np.concatenate([W.write_rd(np.zeros((1, nch, 2048), np.float32), FB), lib_frames[:NF - 1]])   # the host's one-frame lead-in
         assert np.array_equal(got, want)
         lib_pcm = dec.decode(want[None], s16=True, tones=True, sparse=True)[0]
         assert sum(dec.counters().values()) == 0

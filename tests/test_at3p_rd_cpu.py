@@ -10,10 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
-import at3p_alloc_lib as L
-import at3p_rd_lib as RD
+import at3p_writer_lib as W
 import at3p_ref_parts_lib as P
-import at3p_sparse_lib as SP
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "at3phip.h")).read()
@@ -28,40 +26,40 @@ def _written(name, nch, fb):
     """(spectra, frames, records, tail bits) of the restatement on 3 frames of a signal"""
     key = (name, nch, fb)
     if key not in _cache:
-        sp = L.specs_of(name, nch, N_FRAMES)
-        _cache[key] = (sp,) + RD.write_rd(sp, fb, info=True)
+        sp = W.specs_of(name, nch, N_FRAMES)
+        _cache[key] = (sp,) + W.write_rd(sp, fb, info=True)
     return _cache[key]
 
 
-CELLS = [(name, nch, fb) for name in L.SIGNALS for nch in (1, 2) for fb in SIZES[nch]]
+CELLS = [(name, nch, fb) for name in W.SIGNALS for nch in (1, 2) for fb in SIZES[nch]]
 
 
 # ---- 1. golden -------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,nch,fb", RD.GOLDEN_CASES, ids=[f"{n}_{c}_{fb}" for n, c, fb in RD.GOLDEN_CASES])
+@pytest.mark.parametrize("name,nch,fb", W.RD_GOLDEN_CASES, ids=[f"{n}_{c}_{fb}" for n, c, fb in W.RD_GOLDEN_CASES])
 def test_restatement_equals_the_golden_file(name, nch, fb):
     """tests/golden/at3p_rd.npz (tools/gen_golden_at3p_rd.py): frames, j*, k*, N, the guard's outcome, word lengths and both T, bit for
     bit; and on each of its frames the guard's property, T recomputed here from the tables: the written allocation's never exceeds the
     sparse allocation's"""
-    gold = np.load(RD.GOLDEN)
-    got = RD.golden_entry(name, nch, fb)
+    gold = np.load(W.RD_GOLDEN)
+    got = W.rd_golden_entry(name, nch, fb)
     for k, v in got.items():
         want = gold[f"{name}_{nch}_{fb}_{k}"]
         assert want.shape == np.asarray(v).shape and np.array_equal(want, v), (name, nch, fb, k)
-    sp = L.specs_of(name, nch, RD.GOLDEN_FRAMES)
-    nbits = RD.write_rd(sp, fb, info=True)[2]
-    for f in range(RD.GOLDEN_FRAMES):
-        sfi, bits, dist = RD.tables(sp[f])
-        wl_a = SP.allocate(sfi, bits, nbits[f], fb, True)[0]
-        t_written, t_sparse = RD.total_distortion(sfi, dist, got["wl"][f][:nch]), RD.total_distortion(sfi, dist, wl_a)
+    sp = W.specs_of(name, nch, W.RD_GOLDEN_FRAMES)
+    nbits = W.write_rd(sp, fb, info=True)[2]
+    for f in range(W.RD_GOLDEN_FRAMES):
+        sfi, bits, dist = W.tables(sp[f])
+        wl_a = W.allocate(sfi, bits, nbits[f], fb, True)[0]
+        t_written, t_sparse = W.total_distortion(sfi, dist, got["wl"][f][:nch]), W.total_distortion(sfi, dist, wl_a)
         assert t_written <= t_sparse
         assert t_sparse == got["T"][f, 1] and t_written == (got["T"][f, 0] if got["choice"][f, 3] else t_sparse)
 
 
 def test_golden_file_holds_what_it_should():
-    gold = np.load(RD.GOLDEN)
-    assert sorted(gold.files) == sorted(f"{n}_{c}_{fb}_{k}" for n, c, fb in RD.GOLDEN_CASES for k in ("frames", "choice", "wl", "T"))
-    assert os.path.getsize(RD.GOLDEN) < 64 * 1024
-    chose = np.concatenate([gold[f"{n}_{c}_{fb}_choice"][:, 3] for n, c, fb in RD.GOLDEN_CASES])
+    gold = np.load(W.RD_GOLDEN)
+    assert sorted(gold.files) == sorted(f"{n}_{c}_{fb}_{k}" for n, c, fb in W.RD_GOLDEN_CASES for k in ("frames", "choice", "wl", "T"))
+    assert os.path.getsize(W.RD_GOLDEN) < 64 * 1024
+    chose = np.concatenate([gold[f"{n}_{c}_{fb}_choice"][:, 3] for n, c, fb in W.RD_GOLDEN_CASES])
     assert (chose == 1).sum() >= 6 and (chose == 0).sum() >= 3   # both outcomes of the guard
 
 
@@ -77,8 +75,8 @@ def test_host_allocate_rd_equals_the_restatement_on_the_signals():
     for name, nch, fb in CELLS:
         sp, frames, rec, nbits = _written(name, nch, fb)
         for f in range(N_FRAMES):
-            sfi, bits, dist = RD.tables(sp[f])
-            wl, N, r = RD.allocate(sfi, bits, dist, nbits[f], fb)
+            sfi, bits, dist = W.tables(sp[f])
+            wl, N, r = W.allocate_rd(sfi, bits, dist, nbits[f], fb)
             assert _same(at3p_host_allocate_rd(sfi, bits, dist, nbits[f], fb), wl, N, r), (name, nch, fb, f)
             assert np.array_equal(wl, rec["wl"][f][:nch]) and N == rec["num_quant_units"][f]
             seen.add(int(r["chose_rd"]))
@@ -90,15 +88,15 @@ def test_guard_property_and_host_function_on_2000_random_tables():
     has more distortion than the sparse allocation of the same tables (T recomputed here)"""
     from atracdenc_amd.binding import at3p_host_allocate, at3p_host_allocate_rd
     fell = 0
-    for i, (sfi, bits, dist, tail) in enumerate(RD.random_dist_tables(L.random_cost_tables(2000))):
+    for i, (sfi, bits, dist, tail) in enumerate(W.random_dist_tables(W.random_cost_tables(2000))):
         nch = sfi.shape[0]
         fb = SIZES[nch][i % 4]
         tail = min(tail, 8 * fb - 3)   # (the argument's range)
         host = at3p_host_allocate_rd(sfi, bits, dist, tail, fb)
-        wl, N, r = RD.allocate(sfi, bits, dist, tail, fb)
+        wl, N, r = W.allocate_rd(sfi, bits, dist, tail, fb)
         assert _same(host, wl, N, r), i
         wl_a = at3p_host_allocate(sfi, bits, tail, frame_bytes=fb, sparse=True)[0]
-        t_w, t_a = RD.total_distortion(sfi, dist, host[0]), RD.total_distortion(sfi, dist, wl_a)
+        t_w, t_a = W.total_distortion(sfi, dist, host[0]), W.total_distortion(sfi, dist, wl_a)
         assert t_w <= t_a, i
         assert t_a == r["T_sparse"] and (t_w == r["T_rd"] if host[4] else np.array_equal(host[0], wl_a)), i
         fell += not host[4]
@@ -107,18 +105,18 @@ def test_guard_property_and_host_function_on_2000_random_tables():
 
 def test_the_guard_fires_on_the_table_built_for_it():
     from atracdenc_amd.binding import at3p_host_allocate, at3p_host_allocate_rd
-    sfi, bits, dist, tail, fb = RD.guard_table()
-    wl, N, r = RD.allocate(sfi, bits, dist, tail, fb)
+    sfi, bits, dist, tail, fb = W.guard_table()
+    wl, N, r = W.allocate_rd(sfi, bits, dist, tail, fb)
     assert r["chose_rd"] == 0 and r["T_rd"] > r["T_sparse"] and wl[0, 0] == 3 and not wl[0, 1:].any() and N == 1
     assert _same(at3p_host_allocate_rd(sfi, bits, dist, tail, fb), wl, N, r)
     assert np.array_equal(wl, at3p_host_allocate(sfi, bits, tail, frame_bytes=fb, sparse=True)[0])
     # R(j*, k*) itself: the empty frame, whose closing rule gives unit 0 word length 1
-    assert r["T_rd"] == RD.total_distortion(sfi, dist, np.eye(1, 32, dtype=np.uint8))
+    assert r["T_rd"] == W.total_distortion(sfi, dist, np.eye(1, 32, dtype=np.uint8))
 
 
 def test_host_allocate_rd_checks_its_arguments():
     from atracdenc_amd.binding import At3HipError, at3p_host_allocate_rd
-    sfi, bits, dist, tail, fb = RD.guard_table()
+    sfi, bits, dist, tail, fb = W.guard_table()
     big = dist.copy()
     big[0, 5, 2] = (1 << 47) + 1
     for bad in ((sfi, bits, big, tail, fb), (sfi, bits, dist, tail, 168), (sfi, bits, dist, -1, fb), (sfi + 64, bits, dist, tail, fb)):
@@ -130,34 +128,34 @@ def test_host_allocate_rd_checks_its_arguments():
 def test_a_frame_that_fits_with_every_word_length_7_is_the_sparse_frame():
     """quiet white noise in 2048 bytes fits at t = -21 and at J_MIN, both rules give word length 7 everywhere: byte for byte the frame
     AT3PHIP_ALLOC_SPARSE writes (and AT3PHIP_ALLOC_ADAPTIVE alone)"""
-    sp = L.quiet_mono(2)
-    frames, rec, _ = RD.write_rd(sp, 2048, info=True)
-    assert (rec["j"] == RD.J_MIN).all() and (rec["t"] == L.T_MIN).all() and (rec["wl"][:, 0] == 7).all() and (rec["chose_rd"] == 1).all()
-    assert np.array_equal(frames, SP.write_adaptive(sp, 2048, True)) and np.array_equal(frames, SP.write_adaptive(sp, 2048, False))
+    sp = W.quiet_mono(2)
+    frames, rec, _ = W.write_rd(sp, 2048, info=True)
+    assert (rec["j"] == W.J_MIN).all() and (rec["t"] == W.T_MIN).all() and (rec["wl"][:, 0] == 7).all() and (rec["chose_rd"] == 1).all()
+    assert np.array_equal(frames, W.write_adaptive(sp, 2048, True)) and np.array_equal(frames, W.write_adaptive(sp, 2048, False))
 
 
 def test_j_max_bound_from_the_code_tables():
     """R3: at J_MAX every unit picks 0. Re-derived from at3p_vlc.inc: the fewest bits of a 16-line chunk under any table, then the
     smallest j with lambda_j / 2^40 >= lines / (chunks * that + 3) for every unit size; and the header's weaker premise (one bit per
     chunk) gives J_MAX itself. Then the scan on the tables at their worst: full-scale distortion at w = 0, none above, the cheapest bits."""
-    cmin = RD.min_chunk_bits()
-    assert cmin >= 1 and RD.j_max_bound() <= RD.J_MAX
-    sc = RD.scale_table().astype(np.float64)
+    cmin = W.min_chunk_bits()
+    assert cmin >= 1 and W.j_max_bound() <= W.J_MAX
+    sc = W.scale_table().astype(np.float64)
     assert all(sc[i + 3] == 2 * sc[i] for i in range(61)) and sc[63] == 1.0
     lam = lambda j: sc[j % 3] ** 2 * 4.0 ** (j // 3)
     need = max(n / (n // 16 + 3) for n in (16, 32, 64, 128))
-    assert lam(RD.J_MAX) >= need > lam(RD.J_MAX - 1)
-    assert (RD.J_MAX - RD.J_MIN + 1) % 4 == 0
+    assert lam(W.J_MAX) >= need > lam(W.J_MAX - 1)
+    assert (W.J_MAX - W.J_MIN + 1) % 4 == 0
     from atracdenc_amd.binding import at3p_host_allocate_rd
     sfi = np.full((2, 32), 63, np.uint8)
     bits = np.zeros((2, 32, 8), np.uint16)
-    bits[:, :, 1:] = (RD.LINES // 16 * cmin)[None, :, None]
+    bits[:, :, 1:] = (W.LINES // 16 * cmin)[None, :, None]
     dist = np.zeros((2, 32, 8), np.uint64)
-    dist[:, :, 0] = RD.LINES.astype(np.uint64)[None, :] << np.uint64(40)
+    dist[:, :, 0] = W.LINES.astype(np.uint64)[None, :] << np.uint64(40)
     wl, N, j, k, rd = at3p_host_allocate_rd(sfi, bits, dist, 1624, 224)   # the largest stereo tail at the smallest stereo size
     # 165 bits are left: nothing but R's smallest frame fits, and the scan finds it first where the bound says every pick is 0 (what
     # is written is A(t*, k*): the guard prefers its one coded unit to none)
-    assert (j, k) == (RD.j_max_bound(), 0) and not rd and N >= 1
+    assert (j, k) == (W.j_max_bound(), 0) and not rd and N >= 1
 
 
 def test_symbols_and_flags():
@@ -174,19 +172,19 @@ def test_symbols_and_flags():
 # ---- 4. the frames are sparse frames -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nch", [1, 2])
 def test_frames_parse_recount_and_decode_as_sparse_frames(nch):
-    """every frame of the signals at four sizes: the head read back by at3p_sparse_lib.parse_head holds the record's allocation,
+    """every frame of the signals at four sizes: the head read back by at3p_writer_lib.parse_head holds the record's allocation,
     count_bits of it equals the reported bits, which fit; the sparse restatement decoder rejects none"""
     for name, c, fb in CELLS:
         if c != nch:
             continue
         sp, frames, rec, nbits = _written(name, nch, fb)
         for f in range(N_FRAMES):
-            head = SP.parse_head(frames[f], nch)
+            head = W.parse_head(frames[f], nch)
             N = int(rec["num_quant_units"][f])
             assert head["N"] == N and all(head["wl"][ch] == rec["wl"][f][ch][:N].tolist() for ch in range(nch)), (name, fb, f)
-            unit_bits = RD.tables(sp[f])[1]
-            assert SP.count_bits(head, nch, unit_bits, int(nbits[f])) == rec["bits"][f] <= 8 * fb - 3, (name, fb, f)
-        assert SP.decode(frames, nch, False, True)[1].sum() == 0, (name, fb)
+            unit_bits = W.tables(sp[f])[1]
+            assert W.count_bits(head, nch, unit_bits, int(nbits[f])) == rec["bits"][f] <= 8 * fb - 3, (name, fb, f)
+        assert W.decode(frames, nch, False, True)[1].sum() == 0, (name, fb)
 
 
 @needs_ref

@@ -6,10 +6,8 @@ counter zero. 3 streams x 3 frames; what does not depend on the frame size (spec
 import numpy as np
 import pytest
 
-import at3p_alloc_lib as L
+import at3p_writer_lib as W
 import at3p_gha_lib as G
-import at3p_rd_lib as RD
-import at3p_sparse_lib as SP
 import at3p_tonal_write_lib as TW
 from at3_testlib import at3p_mdct, at3p_pqf
 
@@ -79,7 +77,7 @@ def _tonal(nch):
 
 def _wspecs(nch):
     """the sparse tests' signals for the writer calls: noise, mix, tones"""
-    return _memo(("wspecs", nch), lambda: np.stack([L.specs_of(n, nch, F) for n in ("noise", "mix", "tones")]))
+    return _memo(("wspecs", nch), lambda: np.stack([W.specs_of(n, nch, F) for n in ("noise", "mix", "tones")]))
 
 
 def _corner_specs(nch):
@@ -88,8 +86,8 @@ def _corner_specs(nch):
         sp = np.zeros((S, F, nch, 2048), np.float32)
         sp[0, 1, nch - 1, 777] = 0.3
         sp[0, 2] = np.where(np.random.default_rng(3).integers(0, 2, (nch, 2048)) > 0, 1.0, -1.0)
-        sp[1] = L.full_scale_noise(F, nch)
-        sp[2] = SP.edge_specs(nch)[0][1:4]
+        sp[1] = W.full_scale_noise(F, nch)
+        sp[2] = W.edge_specs(nch)[0][1:4]
         return sp
     return _memo(("corner", nch), make)
 
@@ -100,7 +98,7 @@ def _records(nch):
 
 
 def _rd(specs, fb, blocks=None):
-    return np.stack([RD.write_rd(specs[s], fb, None, None if blocks is None else blocks[s]) for s in range(specs.shape[0])])
+    return np.stack([W.write_rd(specs[s], fb, None, None if blocks is None else blocks[s]) for s in range(specs.shape[0])])
 
 
 # ---- the writers -----------------------------------------------------------------------------------------------------------------
@@ -134,20 +132,20 @@ def test_six_calls_equal_the_restatement(B, nch, fb):
     assert np.array_equal(got_ct, _rd(corner, fb, blocks))
     want_e = _rd(specs, fb)
     assert np.array_equal(got_e, want_e) and np.array_equal(got_e16, want_e)
-    want_a = np.stack([RD.write_rd(tspecs[s], fb, None, trecs[s]) for s in range(S)])
+    want_a = np.stack([W.write_rd(tspecs[s], fb, None, trecs[s]) for s in range(S)])
     assert np.array_equal(got_a, want_a) and np.array_equal(got_a16, want_a)
     if fb < 2048:   # the flag matters at these sizes
-        assert not np.array_equal(want_w, SP.write_streams(wspecs, fb, True))
+        assert not np.array_equal(want_w, W.write_streams(wspecs, fb, True))
 
 
 @pytest.mark.parametrize("nch,fb", CASES, ids=IDS)
 def test_a_nan_and_an_infinity_in_one_stream_leave_the_others_alone(B, nch, fb):
-    """stream 1 holds a NaN and an infinity (and, a frame on, at3p_alloc_lib.odd_specs' whole units of them): every stream equals the
+    """stream 1 holds a NaN and an infinity (and, a frame on, at3p_writer_lib.odd_specs' whole units of them): every stream equals the
     restatement, and streams 0 and 2 equal their encode beside a clean stream 1"""
     clean = _wspecs(nch)
     dirty = clean.copy()
     dirty[1, 0, 0, 100], dirty[1, 0, nch - 1, 1500] = np.nan, np.inf
-    dirty[1, 1:] = L.odd_specs(nch, F - 1)
+    dirty[1, 1:] = W.odd_specs(nch, F - 1)
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch, frame_bytes=fb)
     try:
         got, got_clean = enc.write_frames(dirty, **KW), enc.write_frames(clean, **KW)
@@ -164,8 +162,8 @@ def test_device_buffers_queued_calls_splits_and_flag_switches(B, nch, fb):
     import torch
     p16, pcm, specs = _plain(nch)
     t16, tpcm, tspecs, trecs = _tonal(nch)
-    want, want_sparse = _rd(specs, fb), SP.write_streams(specs, fb, True)
-    t_want = np.stack([RD.write_rd(tspecs[s], fb, None, trecs[s]) for s in range(S)])
+    want, want_sparse = _rd(specs, fb), W.write_streams(specs, fb, True)
+    t_want = np.stack([W.write_rd(tspecs[s], fb, None, trecs[s]) for s in range(S)])
     n = S * F * fb
     DEV = B.AT3HIP_PCM_ON_DEVICE | B.AT3HIP_OUT_ON_DEVICE | B.AT3PHIP_ALLOC_ADAPTIVE | B.AT3PHIP_ALLOC_SPARSE | B.AT3PHIP_ALLOC_RD
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch, frame_bytes=fb)
@@ -263,6 +261,6 @@ def test_gpu_written_frames_decode_on_the_gpu_with_every_counter_zero(B, nch, fb
     finally:
         enc.close()
         dec.close()
-    want, rej = SP.decode_streams(frames, nch, True, True)
+    want, rej = W.decode_streams(frames, nch, True, True)
     assert sum(cnt.values()) == 0 == rej.sum(), (cnt, rej)
     assert np.array_equal(pcm.view(np.uint32), want.view(np.uint32))

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-import at3p_alloc_lib as L
+import at3p_writer_lib as W
 from simt_harness_lib import CLANG, Children, assert_clean, build_strict
 
 pytestmark = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's clang++ to compile the kernel sources for the host")
@@ -15,7 +15,7 @@ SENTINEL = 0xA5
 
 def test_harness_driver_equals_the_restatement():
     """tools/emu/run_emu_at3p_rd.py under the strict harness: the two kernels against the restatement on the signals at 376, 2048 and
-    192 bytes, at3p_sparse_lib.edge_specs at the smallest frame sizes (the closing rules of A3s), non-finite spectra and the largest
+    192 bytes, at3p_writer_lib.edge_specs at the smallest frame sizes (the closing rules of A3s), non-finite spectra and the largest
     tonal record at 224 bytes - both outcomes of the guard among them, which the driver checks -, in ascending and descending wavefront
     order and with a guard page behind every buffer"""
     build_strict()
@@ -36,7 +36,7 @@ def test_the_flag_without_the_other_two_is_refused_and_writes_nothing(nch):
     emu = build_strict()
     from atracdenc_amd import binding as B
     S, F = 1, 2
-    specs = L.specs_of("mix", nch, F)[None]
+    specs = W.specs_of("mix", nch, F)[None]
     pcm = np.zeros((S, F, 2048, nch), np.float32)
     p16 = np.zeros((S, F, 2048, nch), np.int16)
     recs = np.zeros((S, F), B.AT3P_TONAL_BLOCK_DTYPE)
@@ -55,7 +55,6 @@ def test_the_flag_without_the_other_two_is_refused_and_writes_nothing(nch):
                 with pytest.raises(B.At3HipError, match="AT3PHIP_ALLOC_RD needs AT3PHIP_ALLOC_ADAPTIVE and AT3PHIP_ALLOC_SPARSE"):
                     call()
                 assert (out == SENTINEL).all(), (extra, k)
-        import at3p_rd_lib as RD
-        assert np.array_equal(enc.write_frames(specs, adaptive=True, sparse=True, rd=True)[0], RD.write_rd(specs[0], 2048))
+        assert np.array_equal(enc.write_frames(specs, adaptive=True, sparse=True, rd=True)[0], W.write_rd(specs[0], 2048))
     finally:
         enc.close()

@@ -1,5 +1,5 @@
 """The adaptive and sparse ATRAC3plus writers against the REFERENCE's part coders (tests/at3p_ref_parts_lib.py): the restatements
-tests/host/at3p_alloc_cpu.c, at3p_rate_cpu.c and at3p_sparse_cpu.c choose an allocation (N, word lengths) and write the frame; the
+tests/host/at3p_writer_cpu.c, under each of its writers' names, chooses an allocation (N, word lengths) and write the frame; the
 reference's TWordLenEncoder, TSfIdxEncoder, TQuantUnitsEncoder and TTonalComponentEncoder, given the same spectra and allocation,
 must write the same bytes and count the same bits. Coverage of what the comparison met is asserted. The restatement's unpack is held
 to the reference's integer mantissas on allocations no writer of the project chose. tests/golden/at3p_ref_parts.npz holds frames the
@@ -11,24 +11,22 @@ import itertools
 import numpy as np
 import pytest
 
-import at3p_alloc_lib as L
-import at3p_rate_lib as R
+import at3p_writer_lib as W
 import at3p_ref_parts_lib as P
-import at3p_sparse_lib as SP
 import at3p_tonal_write_lib as TW
 
 needs_ref = pytest.mark.skipif(not P.have_ref(), reason="oracle/_ref not built")
 SIG_FRAMES = 6
-SPARSE_SIZES = {nch: (R.MIN_BYTES[nch], 376, 744, 2048) for nch in (1, 2)}
-EDGE_SIZES = {nch: (R.MIN_BYTES[nch], 2048) for nch in (1, 2)}
-TONAL_SIZES = {nch: (R.MIN_BYTES[nch], 376, 2048) for nch in (1, 2)}
+SPARSE_SIZES = {nch: (W.MIN_BYTES[nch], 376, 744, 2048) for nch in (1, 2)}
+EDGE_SIZES = {nch: (W.MIN_BYTES[nch], 2048) for nch in (1, 2)}
+TONAL_SIZES = {nch: (W.MIN_BYTES[nch], 376, 2048) for nch in (1, 2)}
 
 
 def _writers_at(fb):
     return (("alloc",) if fb == 2048 else ()) + ("rate", "sparse_on")
 
 
-SIGNAL_CASES = [("signals", w, nch, fb) for nch in (1, 2) for w, sizes in (("alloc", (2048,)), ("rate", R.SIZES[nch]), ("sparse_off", SPARSE_SIZES[nch]),
+SIGNAL_CASES = [("signals", w, nch, fb) for nch in (1, 2) for w, sizes in (("alloc", (2048,)), ("rate", W.SIZES[nch]), ("sparse_off", SPARSE_SIZES[nch]),
                                                                            ("sparse_on", SPARSE_SIZES[nch])) for fb in sizes]
 EDGE_CASES = [("edges", w, nch, fb) for nch in (1, 2) for fb in EDGE_SIZES[nch] for w in _writers_at(fb)]
 TONAL_CASES = [("tonal", w, nch, fb) for nch in (1, 2) for fb in TONAL_SIZES[nch] for w in _writers_at(fb)]
@@ -44,7 +42,7 @@ def _id(case):
 def _inputs(kind, nch):
     """(spectra [n, C, 2048], window flags [n, C] or None, blocks [n] or None)"""
     if kind == "signals":
-        return np.concatenate([L.specs_of(name, nch, SIG_FRAMES) for name in L.SIGNALS]), None, None
+        return np.concatenate([W.specs_of(name, nch, SIG_FRAMES) for name in W.SIGNALS]), None, None
     if kind == "edges":
         e = P.edge_spectra(nch)
         return np.concatenate([sp for sp, _ in e.values()]), None, [b for sp, bl in e.values() for b in (bl or [None] * len(sp))]
@@ -52,7 +50,7 @@ def _inputs(kind, nch):
         return P.table7_specs(nch), None, None
     # every case of the tonal writer's tests with its window flags and blocks, then the largest block on noise and on tones
     ids = [c for c in TW.writer_case_ids() if c.endswith(f"_{nch}")]
-    sp = [TW.case_specs(c).reshape(6, nch, 2048) for c in ids] + [L.specs_of("noise", nch, 1), L.specs_of("tones", nch, 1)]
+    sp = [TW.case_specs(c).reshape(6, nch, 2048) for c in ids] + [W.specs_of("noise", nch, 1), W.specs_of("tones", nch, 1)]
     fl = [np.zeros((6, nch), np.uint16) if TW.case_flags(c) is None else TW.case_flags(c).reshape(6, nch) for c in ids] + [np.zeros((2, nch), np.uint16)]
     bl = [b for c in ids for row in TW.case_blocks(c) for b in row] + [TW.largest_block(nch), TW.largest_block(nch, 1)]
     return np.concatenate(sp), np.concatenate(fl), bl
@@ -89,7 +87,7 @@ def test_frames_equal_the_references(case):
 @needs_ref
 def test_an_allocation_that_does_not_fit_is_refused_not_shrunk():
     """word length 7 everywhere on noise at 376 bytes: the reference asks for a repeat, and the driver ends with its own status"""
-    sp = L.specs_of("noise", 2, 1)
+    sp = W.specs_of("noise", 2, 1)
     with pytest.raises(P.RefRepeat):
         P.ref_write(sp, 376, [32], np.full((1, 2, 32), 7, np.uint8), False)
     P.ref_write(sp, 2048, [32], np.full((1, 2, 32), 4, np.uint8), False)
@@ -98,7 +96,7 @@ def test_an_allocation_that_does_not_fit_is_refused_not_shrunk():
 # ---- what the comparison met ---------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _wl_code_lengths():
-    return [[e >> 12 for e in R.inc_tables()["AT3P_WL_VLC"][8 * i:8 * i + 8]] for i in range(4)]
+    return [[e >> 12 for e in W.inc_tables()["AT3P_WL_VLC"][8 * i:8 * i + 8]] for i in range(4)]
 
 
 def _wl_table_indices(frame, nch, N, wl):
@@ -170,7 +168,7 @@ def _block_costs(wl, block):
     """[8][len(blocks)] bits of every block of `block` mantissas under the eight code tables of a word length, a table's group flags
     shared out evenly (in quarter bits, as integers x 4), and the blocks; mantissas range over what rint(v * inv_mant[wl]) gives for
     |v| <= 1"""
-    tb = R.inc_tables()
+    tb = W.inc_tables()
     mx = int(np.rint(P.float_table("AT3P_INV_MANT")[wl]))
     blocks = list(itertools.product(range(-mx, mx + 1), repeat=block))
     out = []
@@ -244,7 +242,7 @@ def test_unpack_gives_the_references_mantissas(nch, sparse):
     to (float)m * atrac3p_mant_tab[wl] * ScaleTable[sf] (step 2 of the decoder's definition, left to right in float) with m the
     reference's integer mantissa and sf ScaleFrame's index; a unit at 0 and every line from unit N on is +0.0f"""
     n = 8
-    sp = np.concatenate([L.specs_of("mix", nch, n // 2), L.specs_of("burst", nch, n // 2)])
+    sp = np.concatenate([W.specs_of("mix", nch, n // 2), W.specs_of("burst", nch, n // 2)])
     N, wl = _random_allocation(np.random.RandomState(11 + nch + 2 * sparse), n, nch, sparse)
     frames, bits, mant, sf = P.ref_write(sp, 2048, N, wl, sparse, mant=True)
     MANT, SCALE = P.float_table("AT3P_MANT"), P.float_table("AT3P_SCALE")
@@ -252,17 +250,15 @@ def test_unpack_gives_the_references_mantissas(nch, sparse):
     for f in range(n):
         for ch in range(nch):
             for q in range(N[f]):
-                a, b = L.QU_START[q], L.QU_START[q + 1]
+                a, b = W.QU_START[q], W.QU_START[q + 1]
                 if wl[f, ch, q]:
                     want[f, ch, a:b] = (mant[f, ch, a:b].astype(np.float32) * MANT[wl[f, ch, q]]) * SCALE[sf[f, ch, q]]
     assert np.abs(mant).max() >= 20 and (np.abs(mant).reshape(n, -1).max(axis=1) > 0).all()
-    unpackers = [lambda fr: SP.unpack(fr, nch, sparse=sparse)] + ([] if sparse else [lambda fr: R.unpack(fr, nch)])
-    for unpack in unpackers:
-        got, win, fields = unpack(frames)
-        assert (fields["reason"] == 0).all() and np.array_equal(fields["n_qu"], N)
-        for f in range(n):
-            assert np.array_equal(fields["wl"][f, :nch, :N[f]], wl[f, :nch, :N[f]]) and np.array_equal(fields["sf"][f, :nch, :N[f]], sf[f, :, :N[f]])
-        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    got, win, fields = W.unpack(frames, nch, sparse=sparse)
+    assert (fields["reason"] == 0).all() and np.array_equal(fields["n_qu"], N)
+    for f in range(n):
+        assert np.array_equal(fields["wl"][f, :nch, :N[f]], wl[f, :nch, :N[f]]) and np.array_equal(fields["sf"][f, :nch, :N[f]], sf[f, :, :N[f]])
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
     if sparse:
         assert any((wl[f, :nch, :N[f]] == 0).any() for f in range(n))
 
@@ -271,8 +267,8 @@ def test_unpack_gives_the_references_mantissas(nch, sparse):
 @pytest.mark.parametrize("cell", P.cells(), ids=lambda c: c[0])
 def test_restatements_reproduce_the_golden_frames(cell):
     """tests/golden/at3p_ref_parts.npz holds frames the reference's code wrote (tools/gen_golden_at3p_ref_parts.py); the inputs are
-    regenerated and their hash checked; at3p_sparse_cpu.c with the flag on for the sparse cells, and with it off, at3p_rate_cpu.c and
-    at 2048 bytes at3p_alloc_cpu.c for the adaptive ones, give the same frames, N, word lengths and bit counts"""
+    regenerated and their hash checked; at3p_writer_cpu.c with the flag on for the sparse cells, and with it off under every writer name
+    for the adaptive ones, gives the same frames, N, word lengths and bit counts"""
     key, nch, fb, sparse, tonal = cell
     g, meta = P.golden_load()
     sp, fl, bl, sha = P.cell_inputs(nch, tonal)

@@ -1,6 +1,7 @@
 """ATRAC3plus sparse word lengths (include/at3phip.h, SPARSE WORD LENGTHS) without a GPU: the restatement
-tests/host/at3p_sparse_cpu.c with its flags off against tests/host/at3p_rate_cpu.c; at3phip_host_allocate_sparse against it; every
-frame it writes parsed by an independent parser (at3p_sparse_lib.parse_head, written from the header's text), recounted and decoded;
+tests/host/at3p_writer_cpu.c with its flags off against what tests/host/at3p_rate_cpu.c gave before the two were folded into one
+(tests/golden/at3p_writer_fold.npz); at3phip_host_allocate_sparse against it; every frame it writes parsed by an independent parser
+(at3p_writer_lib.parse_head, written from the header's text), recounted and decoded;
 the t = -21 property; the smallest frame sizes re-derived; crafted decoder frames; the round trip per standard bitrate beside
 DESIGN.md section 20's; the kernels through the CPU SIMT harness; a build without the adaptive writer."""
 import os
@@ -10,17 +11,15 @@ import subprocess
 import numpy as np
 import pytest
 
-import at3p_alloc_lib as L
+import at3p_writer_lib as W
 import at3p_decode_lib as D
 import at3p_gha_lib as G
-import at3p_rate_lib as R
-import at3p_sparse_lib as SP
 import at3p_tonal_write_lib as TW
 from simt_harness_lib import CLANG, ROOT, Children, assert_clean, build_strict
 from test_at3p_rate_cpu import SNR as SECTION_20
 
 needs_clang = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's clang++ to compile the kernel sources for the host")
-NF = L.SNR_FRAMES
+NF = W.SNR_FRAMES
 HEADER = open(os.path.join(ROOT, "include", "at3phip.h")).read()
 SIZES = {1: (192, 280, 376, 744, 2048), 2: (280, 376, 744, 2048)}
 REASON = {name: i for i, name in enumerate(D.REASONS)}
@@ -30,48 +29,60 @@ _specs = {}
 
 def _sp(name, nch):
     if (name, nch) not in _specs:
-        _specs[(name, nch)] = L.specs_of(name, nch, NF)
+        _specs[(name, nch)] = W.specs_of(name, nch, NF)
     return _specs[(name, nch)]
 
 
 # ---- 1. flags off --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nch", [1, 2])
 def test_flags_off_equals_the_rate_restatement(nch):
-    """frames, PCM and counters of at3p_rate_cpu.c at 2048 bytes, 376 and the smallest size, on that file's test inputs: the signals,
-    silence, full-scale noise, non-finite spectra, window flags, tonal records, flipped bits and the crafted malformed frames"""
-    cases = [(L.specs_of(n, nch, 4), None, None) for n in L.SIGNALS + ("silence", "fullscale")]
-    cases.append((L.odd_specs(nch, 3), None, None))
-    cases.append((L.specs_of("noise", nch, 2), np.array([[0x01ef] * nch, [0xffff] * nch], np.uint16), None))
-    cases.append((np.concatenate([L.full_scale_noise(2, nch), _sp("mix", nch)[:1]]), None,
+    """tests/golden/at3p_writer_fold.npz holds, as SHA-256, what at3p_rate_cpu.c gave while it stated the writer and the decoder's
+    unpack beside this restatement, equal to it with the flags off: frames, records, PCM and counters at 2048 bytes, 376 and the
+    smallest size, on that file's test inputs: the signals, silence, full-scale noise, non-finite spectra, window flags, tonal
+    records, flipped bits and the crafted malformed frames; and its allocations on the first 100 random cost tables"""
+    gold = W.fold_golden(nch)
+
+    def same(label, *got):
+        assert np.array_equal(W.sha(*got), gold[label]), label
+
+    cases = [(W.specs_of(n, nch, 4), None, None) for n in W.SIGNALS + ("silence", "fullscale")]
+    cases.append((W.odd_specs(nch, 3), None, None))
+    cases.append((W.specs_of("noise", nch, 2), np.array([[0x01ef] * nch, [0xffff] * nch], np.uint16), None))
+    cases.append((np.concatenate([W.full_scale_noise(2, nch), _sp("mix", nch)[:1]]), None,
                   [TW.largest_block(nch), None, TW.case_blocks(f"small_{nch}")[0][0]]))
     rng = np.random.default_rng(11)
-    for fb in (2048, 376, R.MIN_BYTES[nch]):
-        for sp, win, blocks in cases:
-            old, oi = R.write_adaptive(sp, fb, win, blocks, info=True)
-            new, ni, _ = SP.write_adaptive(sp, fb, False, win, blocks, info=True)
-            assert np.array_equal(old, new) and old.tobytes() == new.tobytes() and oi.tobytes() == ni.tobytes()
-            for frames in (new, D.mutate_frames(new, rng, n_flips=2)):
+    for fb in (2048, 376, W.MIN_BYTES[nch]):
+        for i, (sp, win, blocks) in enumerate(cases):
+            new, ni, _ = W.write_adaptive(sp, fb, False, win, blocks, info=True)
+            same(f"a{i}_{fb}_frames", new)
+            same(f"a{i}_{fb}_info", ni.view(np.uint8))
+            flipped = D.mutate_frames(new, rng, n_flips=2)
+            same(f"a{i}_{fb}_flipped_in", flipped)
+            for kind, frames in (("plain", new), ("flipped", flipped)):
                 for tones in (False, True):
-                    a, ra = R.decode(frames, nch, tones)
-                    b, rb = SP.decode(frames, nch, tones, sparse=False)
-                    assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.array_equal(ra, rb), (fb, tones, ra, rb)
+                    b, rb = W.decode(frames, nch, tones, sparse=False)
+                    same(f"a{i}_{fb}_{kind}_tones{int(tones)}", b.view(np.uint32), rb)
     crafted, _ = D.crafted_frames(nch, 3)
+    same("b_in", crafted)
     for tones in (False, True):
-        a, ra = R.decode(crafted, nch, tones)
-        b, rb = SP.decode(crafted, nch, tones, sparse=False)
-        assert np.array_equal(ra, rb) and np.array_equal(a.view(np.uint32), b.view(np.uint32)), (ra, rb)
-    assert np.array_equal(R.unpack(crafted, nch)[2], SP.unpack(crafted, nch, sparse=False)[2])
-    for sfi, bits, tail in L.random_cost_tables()[:100]:
+        b, rb = W.decode(crafted, nch, tones, sparse=False)
+        same(f"b_tones{int(tones)}", b.view(np.uint32), rb)
+    same("b_fields0", W.unpack(crafted, nch, sparse=False)[2].view(np.uint8))
+    n = 0
+    for i, (sfi, bits, tail) in enumerate(W.random_cost_tables()[:100]):
         if sfi.shape[0] == nch:
-            for fb in (R.MIN_BYTES[nch], 2048):
+            same(f"c{i}_in", sfi, bits, tail)
+            for fb in (W.MIN_BYTES[nch], 2048):
                 tb = min(tail, 8 * fb - 3)
-                a, b = R.allocate(sfi, bits, tb, fb), SP.allocate(sfi, bits, tb, fb, False)
-                assert np.array_equal(a[0], b[0]) and a[1:] == b[1:]
+                wl, *rest = W.allocate(sfi, bits, tb, fb, False)
+                same(f"c{i}_{fb}", wl, rest)
+            n += 1
+    assert n == sum(k.startswith("c") and k.endswith("_in") for k in gold) >= 30
 
 
 # ---- 2. at3phip_host_allocate_sparse ---------------------------------------------------------------------------------------------------
 def _same(B, path, sfi, bits, tail, fb, what):
-    wl, N, t, k, total = SP.allocate(sfi, bits, tail, fb, True)
+    wl, N, t, k, total = W.allocate(sfi, bits, tail, fb, True)
     gwl, gN, gt, gk = B.at3p_host_allocate(sfi, bits, tail, path, frame_bytes=fb, sparse=True)
     assert (gN, gt, gk) == (N, t, k) and np.array_equal(gwl, wl), (what, (N, t, k), (gN, gt, gk))
     return wl, N, t, k, total
@@ -82,11 +93,11 @@ def test_host_allocate_sparse_equals_the_restatement_on_the_signals():
     from atracdenc_amd import binding as B
     path = build_strict()
     n = zeros = 0
-    for name in L.SIGNALS:
+    for name in W.SIGNALS:
         for nch in (1, 2):
             sp = _sp(name, nch)
             for f in (0, 5, 13):
-                sfi, bits = SP.cost_table(sp[f])
+                sfi, bits, _ = W.cost_table(sp[f])
                 for fb in SIZES[nch]:
                     wl, N, _, _, total = _same(B, path, sfi, bits, 8, fb, (name, nch, f, fb))
                     assert total <= 8 * fb - 3 and N not in (29, 30, 31) and wl[:, N - 1].any() and not wl[:, N:].any()
@@ -101,15 +112,15 @@ def test_host_allocate_sparse_equals_the_restatement_on_random_tables():
     size, 376 and 2048"""
     from atracdenc_amd import binding as B
     path = build_strict()
-    tables = L.random_cost_tables()
+    tables = W.random_cost_tables()
     assert len(tables) == 1000
     differ = 0
     for i, (sfi, bits, tail) in enumerate(tables):
         nch = sfi.shape[0]
-        for fb in (R.MIN_BYTES[nch], 376, 2048):
+        for fb in (W.MIN_BYTES[nch], 376, 2048):
             tb = min(tail, 8 * fb - 3)
             got = _same(B, path, sfi, bits, tb, fb, (i, fb))
-            differ += fb == 376 and not np.array_equal(got[0], R.allocate(sfi, bits, tb, fb)[0])
+            differ += fb == 376 and not np.array_equal(got[0], W.allocate(sfi, bits, tb, fb)[0])
     assert differ >= 300, differ   # (the flag matters on these tables)
 
 
@@ -117,7 +128,7 @@ def test_host_allocate_sparse_equals_the_restatement_on_random_tables():
 def test_host_allocate_sparse_on_the_hand_built_cases():
     from atracdenc_amd import binding as B
     path = build_strict()
-    cases = SP.edge_tables()
+    cases = W.edge_tables()
     got = {name: _same(B, path, *case, name) for name, case in cases.items()}
     wl, N, t, k, _ = got["nothing_wanted"]        # no unit wanted: unit 0 of channel 0 becomes 1
     assert (N, t, k) == (1, 3, 0) and wl[0, 0] == 1 and wl.sum() == 1
@@ -129,44 +140,44 @@ def test_host_allocate_sparse_on_the_hand_built_cases():
     clones = int(((wl[1, :N] == 0) & (wl[0, :N] > 0)).sum())
     assert clones >= 10
     head = {"N": N, "wl": [[int(w) for w in wl[0, :N]], [int(w) for w in wl[1, :N]]]}
-    assert SP.count_bits(head, 2, bits, tail) == total
+    assert W.count_bits(head, 2, bits, tail) == total
     for name in ("flat", "flat_mono"):            # a flat sfi: A(t*, 0) is empty, k alone extends N
         sfi, bits, tail, fb = cases[name]
         wl, N, t, k, _ = got[name]
-        assert SP.allocate(sfi, bits, tail, fb, True)[1:4] == (N, t, k) and k > 1 and N > 1
+        assert W.allocate(sfi, bits, tail, fb, True)[1:4] == (N, t, k) and k > 1 and N > 1
         w0 = np.maximum(0, np.minimum(7, (sfi.astype(int) - t) // 3))
         assert not w0.any() and int((wl > 0).sum()) == k and N == (k + sfi.shape[0] - 1) // sfi.shape[0]
     sfi, bits, tail, fb = cases["flat"]
-    for bad_fb in (0, 7, 2056, R.MIN_BYTES[2] - 8):
+    for bad_fb in (0, 7, 2056, W.MIN_BYTES[2] - 8):
         with pytest.raises(B.At3HipError):
             B.at3p_host_allocate(sfi, bits, tail, path, frame_bytes=bad_fb, sparse=True)
 
 
 # ---- 3. every frame ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nch", [1, 2])
-@pytest.mark.parametrize("name", L.SIGNALS)
+@pytest.mark.parametrize("name", W.SIGNALS)
 def test_frames_parse_count_and_decode(name, nch):
     """14 frames of each signal at each size: the independent head parser reads them; Bits(A) recounted from the parsed fields is
     the restatement's figure and within the budget; the terminator sits where the count says; every clone flag is 1; the sparse
     decoder rejects none, and the decoder without the flag rejects exactly the frames with a zero inside the range, as bad_code"""
     sp = _sp(name, nch)
-    tail = sum(n for _, n in L.tail_bits_list(nch))
-    costs = [SP.cost_table(sp[f])[1] for f in range(NF)]
+    tail = sum(n for _, n in W.tail_bits_list(nch))
+    costs = [W.cost_table(sp[f])[1] for f in range(NF)]
     for fb in SIZES[nch]:
-        frames, rec, _ = SP.write_adaptive(sp, fb, True, info=True)
-        assert SP.decode(frames, nch)[1].sum() == 0
+        frames, rec, _ = W.write_adaptive(sp, fb, True, info=True)
+        assert W.decode(frames, nch, sparse=True)[1].sum() == 0
         zero_frames = 0
         for f in range(NF):
-            p = SP.parse_head(frames[f], nch)
+            p = W.parse_head(frames[f], nch)
             N = p["N"]
             assert N not in (29, 30, 31) and N == rec["num_quant_units"][f]
             assert all(p["wl"][c] == list(rec["wl"][f, c, :N]) for c in range(nch)) and any(p["wl"][c][N - 1] for c in range(nch))
             assert all(v == 1 for v in p["clone"].values())
-            total = SP.count_bits(p, nch, costs[f], tail)
+            total = W.count_bits(p, nch, costs[f], tail)
             assert total == rec["bits"][f] <= 8 * fb - 3, (fb, f, total)
-            assert L.terminator_pos(frames[f]) == 3 + total - 1 < 8 * fb
+            assert W.terminator_pos(frames[f]) == 3 + total - 1 < 8 * fb
             zero_frames += any(0 in p["wl"][c] for c in range(nch))
-        rej = SP.decode(frames, nch, sparse=False)[1]
+        rej = W.decode(frames, nch, sparse=False)[1]
         assert rej[REASON["bad_code"]] == zero_frames == rej.sum(), (fb, rej, zero_frames)
 
 
@@ -175,11 +186,11 @@ def test_frames_parse_count_and_decode(name, nch):
 def test_a_frame_that_fits_at_t_minus_21_is_the_adaptive_writers(nch):
     """at t = -21 every want is 7: where the unflagged allocation fits there (quiet mono `tones`-like material at 2048 bytes, section
     19's edge case), the sparse frame is the same bytes"""
-    sp = np.concatenate([L.quiet_mono(4).repeat(nch, axis=1), L.specs_of("silence", nch, 2)])
-    plain, rec = R.write_adaptive(sp, 2048, info=True)
-    assert (rec["t"] == L.T_MIN).sum() >= 2
-    sparse = SP.write_adaptive(sp, 2048, True)
-    fits = rec["t"] == L.T_MIN
+    sp = np.concatenate([W.quiet_mono(4).repeat(nch, axis=1), W.specs_of("silence", nch, 2)])
+    plain, rec, _ = W.write_adaptive(sp, 2048, info=True)
+    assert (rec["t"] == W.T_MIN).sum() >= 2
+    sparse = W.write_adaptive(sp, 2048, True)
+    fits = rec["t"] == W.T_MIN
     assert np.array_equal(plain[fits], sparse[fits])
 
 
@@ -190,21 +201,21 @@ def test_min_frame_bytes_still_follow_from_the_tables():
     with one index (channel 1's unit at 0 under a coded channel-0 unit carries the clone flag), and unit 0's 16 lines under the
     cheapest-in-the-worst-case table - never more than A3's one unit per channel, so the header's 77 and 147 bits bound it and
     176 and 224 bytes still admit the largest tonal record"""
-    tb = R.inc_tables()
-    worst_unit = R.worst_front_one_unit(1) - (5 + 1 + 11 + (2 + 6) + 1 + (4 + 3) + 4 * tb["AT3P_SB_POWGRPS"][tb["AT3P_QU_TO_SB"][0]])
+    tb = W.inc_tables()
+    worst_unit = W.worst_front_one_unit(1) - (5 + 1 + 11 + (2 + 6) + 1 + (4 + 3) + 4 * tb["AT3P_SB_POWGRPS"][tb["AT3P_QU_TO_SB"][0]])
     longest_wl = max(e >> 12 for e in tb["AT3P_WL_VLC"])
     front = {}
     for nch in (1, 2):
         bits = 5 + 1 + 11 + (nch == 2) * (6 + longest_wl) + nch * (2 + 6) + 1 + nch * 4 + 3 + (nch == 2) * 1
         bits += nch * 4 * tb["AT3P_SB_POWGRPS"][tb["AT3P_QU_TO_SB"][0]] + worst_unit
         front[nch] = bits
-        assert bits <= R.worst_front_one_unit(nch)
-        assert bits + R.worst_tail(nch) <= 8 * R.MIN_BYTES[nch] - 3
+        assert bits <= W.worst_front_one_unit(nch)
+        assert bits + W.worst_tail(nch) <= 8 * W.MIN_BYTES[nch] - 3
     assert front[1] <= 77 and front[2] <= 147, front
     for nch in (1, 2):   # and in fact: the largest record on full-scale noise at the smallest size
-        fb, big = R.MIN_BYTES[nch], TW.largest_block(nch)
-        frames, rec, nb = SP.write_adaptive(L.full_scale_noise(2, nch), fb, True, None, [big, big], info=True)
-        assert (nb > 1000).all() and (rec["bits"] <= 8 * fb - 3).all() and SP.decode(frames, nch, True)[1].sum() == 0
+        fb, big = W.MIN_BYTES[nch], TW.largest_block(nch)
+        frames, rec, nb = W.write_adaptive(W.full_scale_noise(2, nch), fb, True, None, [big, big], info=True)
+        assert (nb > 1000).all() and (rec["bits"] <= 8 * fb - 3).all() and W.decode(frames, nch, True, True)[1].sum() == 0
     assert "#define AT3PHIP_ALLOC_SPARSE 256u" in HEADER and "#define AT3PHIP_DECODE_SPARSE 32u" in HEADER
 
 
@@ -213,21 +224,21 @@ def test_min_frame_bytes_still_follow_from_the_tables():
 def test_crafted_frames(nch):
     """top unit zero in every channel and (stereo) a cleared clone flag are unsupported_syntax; without the flag both are bad_code
     (a word length of 0); a frame cut inside the code-table section is read_past_end"""
-    bad = SP.crafted_frames(nch, 376)
+    bad = W.crafted_frames(nch, 376)
     assert len(bad) == nch
-    _, _, fl = SP.unpack(bad, nch, True, True)
+    _, _, fl = W.unpack(bad, nch, True, True)
     assert (fl["reason"] == REASON["unsupported_syntax"] + 1).all()
-    _, _, fl = SP.unpack(bad, nch, True, False)
+    _, _, fl = W.unpack(bad, nch, True, False)
     assert (fl["reason"] == REASON["bad_code"] + 1).all()
-    pcm, rej = SP.decode(bad, nch, True, True)
+    pcm, rej = W.decode(bad, nch, True, True)
     assert rej[REASON["unsupported_syntax"]] == nch == rej.sum() and not pcm.any()
-    good = SP.write_adaptive(_sp("tones", nch)[:1], 376, True)[0]
-    head = SP.parse_head(good, nch)
+    good = W.write_adaptive(_sp("tones", nch)[:1], 376, True)[0]
+    head = W.parse_head(good, nch)
     sf_end = head["pos"] - (1 + 4 * nch + 3 * sum(w > 0 for row in head["wl"] for w in row) + len(head["clone"]))
     for cut_bits in (sf_end + 8, head["pos"] - 2):
         cut = np.ascontiguousarray(good[:cut_bits // 8])
         assert 8 * len(cut) > sf_end and 8 * len(cut) < head["pos"]
-        assert SP.unpack(cut[None], nch, True, True)[2]["reason"][0] == REASON["read_past_end"] + 1
+        assert W.unpack(cut[None], nch, True, True)[2]["reason"][0] == REASON["read_past_end"] + 1
 
 
 # ---- 7. round trip per standard bitrate ----------------------------------------------------------------------------------------------------
@@ -260,15 +271,15 @@ BELOW_SECTION_20 = {("burst", 2, 744, 1), ("burst", 2, 936, 1)}
 
 
 @pytest.mark.parametrize("nch", [1, 2])
-@pytest.mark.parametrize("name", L.SIGNALS)
+@pytest.mark.parametrize("name", W.SIGNALS)
 def test_round_trip_snr_per_bitrate(name, nch):
     sp, x = _sp(name, nch), G.signal_pcm(name, NF, nch)
     row, used = {}, {}
-    for kbit, fb in R.BITRATES.items():
-        if fb < R.MIN_BYTES[nch]:
+    for kbit, fb in W.BITRATES.items():
+        if fb < W.MIN_BYTES[nch]:
             continue     # 32 kbit/s is a mono rate
-        frames, rec, _ = SP.write_adaptive(sp, fb, True, info=True)
-        y, rej = SP.decode(frames, nch)
+        frames, rec, _ = W.write_adaptive(sp, fb, True, info=True)
+        y, rej = W.decode(frames, nch, sparse=True)
         assert rej.sum() == 0
         row[fb] = [G.snr_db(x[:, :, c].reshape(-1), y[:, :, c].reshape(-1), NF) for c in range(nch)]
         used[fb] = float(rec["bits"].mean())
@@ -299,32 +310,59 @@ def test_design_lists_the_round_trip_table():
 
 
 # ---- 8. golden -------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,nch,fb", SP.GOLDEN_CASES, ids=[f"{n}_{c}_{fb}" for n, c, fb in SP.GOLDEN_CASES])
+@pytest.mark.parametrize("name,nch,fb", W.SPARSE_GOLDEN_CASES, ids=[f"{n}_{c}_{fb}" for n, c, fb in W.SPARSE_GOLDEN_CASES])
 def test_restatement_equals_the_golden_file(name, nch, fb):
     """tests/golden/at3p_sparse.npz (tools/gen_golden_at3p_sparse.py): the restatement's frames, t*, k*, N, word lengths and PCM on 3
     frames of `noise` and `tones`, mono and stereo, at 376 and 2048 bytes. Everything sparse is pinned to the restatement; this pins
     the restatement, so that an edit to it or another compiler cannot move every expectation at once."""
-    gold = np.load(SP.GOLDEN)
-    got = SP.golden_entry(name, nch, fb)
+    gold = np.load(W.SPARSE_GOLDEN)
+    got = W.sparse_golden_entry(name, nch, fb)
     for k, v in got.items():
         want = gold[f"{name}_{nch}_{fb}_{k}"]
         assert want.shape == np.asarray(v).shape and np.array_equal(want, v), (name, nch, fb, k)
 
 
 def test_golden_file_holds_what_it_should():
-    gold = np.load(SP.GOLDEN)
-    assert sorted(gold.files) == sorted(f"{n}_{c}_{fb}_{k}" for n, c, fb in SP.GOLDEN_CASES for k in ("frames", "choice", "wl", "pcm_sha256"))
-    assert os.path.getsize(SP.GOLDEN) < 64 * 1024
-    zeros = sum(bool((gold[f"{n}_{c}_376_wl"][f, :c, :gold[f"{n}_{c}_376_choice"][f, 2]] == 0).any()) for n, c, fb in SP.GOLDEN_CASES if fb == 376
-                for f in range(SP.GOLDEN_FRAMES))
+    gold = np.load(W.SPARSE_GOLDEN)
+    assert sorted(gold.files) == sorted(f"{n}_{c}_{fb}_{k}" for n, c, fb in W.SPARSE_GOLDEN_CASES for k in ("frames", "choice", "wl", "pcm_sha256"))
+    assert os.path.getsize(W.SPARSE_GOLDEN) < 64 * 1024
+    zeros = sum(bool((gold[f"{n}_{c}_376_wl"][f, :c, :gold[f"{n}_{c}_376_choice"][f, 2]] == 0).any()) for n, c, fb in W.SPARSE_GOLDEN_CASES if fb == 376
+                for f in range(W.SPARSE_GOLDEN_FRAMES))
     assert zeros >= 6   # (the file holds word length 0 inside the coded range)
+
+
+@pytest.mark.parametrize("nch", [1, 2])
+def test_frozen_sparse_and_rd_edge_cases(nch):
+    """tests/golden/at3p_writer_fold.npz, part d: what the sparse and the rate-distortion restatements gave, before the restatements
+    were folded into one, where the definition has special cases: edge_specs written sparse and with rate-distortion word lengths at
+    the smallest size and at 2048 bytes, edge_tables and guard_table allocated, crafted_frames decoded with sparse on"""
+    gold, got = W.fold_golden(nch), W.fold_entries(nch, "d")
+    assert len(got) >= 15 and set(got) == {k for k in gold if k.startswith("d")}
+    assert [k for k in got if not np.array_equal(got[k], gold[k])] == []
+
+
+def test_fold_golden_file_holds_what_it_should():
+    """labels and SHA-256 digests per channel count, nothing else; every part present; and every input the digests were taken on
+    (spectra and tails, flipped frames, crafted frames, cost tables) is still what this tree builds: a change in how numpy draws, or in
+    a signal, shows here and not as a failure of the restatement"""
+    gold = np.load(W.FOLD_GOLDEN)
+    assert sorted(gold.files) == ["labels_1", "labels_2", "sha256_1", "sha256_2"] and os.path.getsize(W.FOLD_GOLDEN) < 64 * 1024
+    for nch in (1, 2):
+        labels, g = gold[f"labels_{nch}"].tolist(), W.fold_golden(nch)
+        assert gold[f"sha256_{nch}"].shape == (len(labels), 32) and gold[f"sha256_{nch}"].dtype == np.uint8 and len(set(labels)) == len(labels)
+        got = W.fold_entries(nch)
+        assert list(got) == labels
+        for part, least in (("a", 10 * (1 + 3 * 7)), ("b", 5), ("c", 3 * 30), ("d", 15)):
+            assert sum(k.startswith(part) for k in labels) >= least, part
+        inputs = [k for k in labels if k.endswith("_in")]
+        assert len(inputs) >= 10 + 30 + 30 + 1 + 4 and [k for k in inputs if not np.array_equal(got[k], g[k])] == []
 
 
 # ---- 9. the kernels through the CPU SIMT harness -----------------------------------------------------------------------------------------
 @needs_clang
 def test_harness_driver_equals_the_restatement():
     """tools/emu/run_emu_at3p_sparse.py under the strict harness: the sparse writer kernels (plain and tonal) and the sparse unpack
-    kernels (2048 and sized) against the restatement, on the signals at 280 and 2048 bytes, at3p_sparse_lib.edge_specs at the
+    kernels (2048 and sized) against the restatement, on the signals at 280 and 2048 bytes, at3p_writer_lib.edge_specs at the
     smallest frame sizes - whose restatement records the driver checks for the empty frame (A3s' first fix-up), N = 32 with unit 31
     of channel 0 at 1 above zeros (mono and stereo), the clone flags and the flat case, one `bad` line per channel count -,
     non-finite spectra and the largest tonal record at 224 bytes, in ascending and descending wavefront order and with a guard

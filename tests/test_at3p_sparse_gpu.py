@@ -1,6 +1,6 @@
 """ATRAC3plus sparse word lengths on the GPU (AT3PHIP_ALLOC_SPARSE, AT3PHIP_DECODE_SPARSE; include/at3phip.h, SPARSE WORD LENGTHS):
 the six frame-writing calls with ADAPTIVE | SPARSE and at3phip_decode with the decoder flag equal the restatement
-tests/host/at3p_sparse_cpu.c bit for bit - host and device buffers, queued and waiting, however the stream is split -; SPARSE
+tests/host/at3p_writer_cpu.c bit for bit - host and device buffers, queued and waiting, however the stream is split -; SPARSE
 without ADAPTIVE is refused and moves nothing; crafted frames are counted as the restatement counts them; a context that wrote
 sparse frames writes the unflagged ones it always wrote; the command line composes --sparse with --bitrate and the tone analysis.
 3 streams x 5 frames; what does not depend on the frame size (spectra, tone analysis) is computed once."""
@@ -11,10 +11,8 @@ import wave
 import numpy as np
 import pytest
 
-import at3p_alloc_lib as L
+import at3p_writer_lib as W
 import at3p_gha_lib as G
-import at3p_rate_lib as R
-import at3p_sparse_lib as SP
 import at3p_tonal_write_lib as TW
 from at3_testlib import at3p_mdct, at3p_pqf
 
@@ -77,7 +75,7 @@ def _tonal(nch):
 
 def _wspecs(nch):
     """spectra for the writer calls: noise, a stream with NaN, infinities and FLT_MAX beside normal ones, tones"""
-    return np.stack([L.specs_of("noise", nch, F), np.concatenate([L.odd_specs(nch, 3), L.specs_of("mix", nch, F - 3)]), L.specs_of("tones", nch, F)])
+    return np.stack([W.specs_of("noise", nch, F), np.concatenate([W.odd_specs(nch, 3), W.specs_of("mix", nch, F - 3)]), W.specs_of("tones", nch, F)])
 
 
 def _records(nch):
@@ -90,7 +88,7 @@ def _sparse_frames(nch, fb):
     key = ("frames", nch, fb)
     if key not in _cache:
         w, blocks = _wspecs(nch), _records(nch)
-        out = [SP.write_adaptive(w[s], fb, True, None, blocks[s], info=True) for s in range(S)]
+        out = [W.write_adaptive(w[s], fb, True, None, blocks[s], info=True) for s in range(S)]
         _cache[key] = (np.stack([o[0] for o in out]), np.stack([o[1] for o in out]))
     return _cache[key]
 
@@ -117,15 +115,15 @@ def test_six_calls_equal_the_restatement(B, nch, fb):
         got_a16 = enc.encode_frames_tonal_s16(t16, gated=True, shared=True, **kw)
     finally:
         enc.close()
-    want_w, info = SP.write_streams(wspecs, fb, True), _sparse_frames(nch, fb)[1]
+    want_w, info = W.write_streams(wspecs, fb, True), _sparse_frames(nch, fb)[1]
     assert np.array_equal(got_w, want_w)
     assert np.array_equal(got_t, _sparse_frames(nch, fb)[0])
-    want_e = SP.write_streams(specs, fb, True)
+    want_e = W.write_streams(specs, fb, True)
     assert np.array_equal(got_e, want_e) and np.array_equal(got_e16, want_e)
-    want_a = np.stack([SP.write_adaptive(tspecs[s], fb, True, None, trecs[s]) for s in range(S)])
+    want_a = np.stack([W.write_adaptive(tspecs[s], fb, True, None, trecs[s]) for s in range(S)])
     assert np.array_equal(got_a, want_a) and np.array_equal(got_a16, want_a)
     if fb < 2048:   # the flag matters at these sizes: the frames are not the adaptive writer's, and hold zeros inside the range
-        assert not np.array_equal(want_e, R.write_streams(specs, fb))
+        assert not np.array_equal(want_e, W.write_streams(specs, fb))
         assert any((info["wl"][s, f, c, :info["num_quant_units"][s, f]] == 0).any() for s in range(S) for f in range(F) for c in range(nch))
 
 
@@ -135,8 +133,8 @@ def test_device_buffers_queued_calls_and_splits(B, nch, fb):
     import torch
     p16, pcm, specs = _plain(nch)
     t16, tpcm, tspecs, trecs = _tonal(nch)
-    want = SP.write_streams(specs, fb, True)
-    t_want = np.stack([SP.write_adaptive(tspecs[s], fb, True, None, trecs[s]) for s in range(S)])
+    want = W.write_streams(specs, fb, True)
+    t_want = np.stack([W.write_adaptive(tspecs[s], fb, True, None, trecs[s]) for s in range(S)])
     n = S * F * fb
     DEV = B.AT3HIP_PCM_ON_DEVICE | B.AT3HIP_OUT_ON_DEVICE | B.AT3PHIP_ALLOC_ADAPTIVE | B.AT3PHIP_ALLOC_SPARSE
     kw = dict(adaptive=True, sparse=True)
@@ -173,13 +171,13 @@ def test_device_buffers_queued_calls_and_splits(B, nch, fb):
 
 @pytest.mark.parametrize("nch", [1, 2])
 def test_special_cases_of_the_allocation(B, nch):
-    """at3p_sparse_lib.edge_specs at the smallest frame size: the empty frame (unit 0 of channel 0 takes 1), N = 32 with unit 31 of
+    """at3p_writer_lib.edge_specs at the smallest frame size: the empty frame (unit 0 of channel 0 takes 1), N = 32 with unit 31 of
     channel 0 at 1 above zeros, clone flags, the flat case - each checked to have occurred in the restatement's record - written
     by at3phip_write_frames_tonal and decoded by at3phip_decode, against the restatement"""
-    fb = R.MIN_BYTES[nch]
-    sp, blocks = SP.edge_specs(nch)
-    want, rec, _ = SP.write_adaptive(sp, fb, True, None, blocks, info=True)
-    assert SP.edge_cases_reached(rec, nch) == []
+    fb = W.MIN_BYTES[nch]
+    sp, blocks = W.edge_specs(nch)
+    want, rec, _ = W.write_adaptive(sp, fb, True, None, blocks, info=True)
+    assert W.edge_cases_reached(rec, nch) == []
     enc = B.At3pHip(n_streams=1, max_frames=4, channels=nch, frame_bytes=fb)
     dec = B.At3pHipDecoder(n_streams=1, channels=nch, max_frames=4, frame_bytes=fb)
     try:
@@ -190,7 +188,7 @@ def test_special_cases_of_the_allocation(B, nch):
         enc.close()
         dec.close()
     assert np.array_equal(got[0], want)
-    wpcm, rej = SP.decode(want, nch, True, True)
+    wpcm, rej = W.decode(want, nch, True, True)
     assert rej.sum() == 0 == sum(cnt.values()) and np.array_equal(pcm[0].view(np.uint32), wpcm.view(np.uint32))
 
 
@@ -227,7 +225,7 @@ def test_sparse_alone_is_refused_and_moves_nothing(B, nch):
         want_t = fresh.encode_frames_tonal(pcm, adaptive=True, sparse=True)
     finally:
         fresh.close()
-    assert np.array_equal(got, SP.write_streams(specs, 2048, True)) and np.array_equal(got_t, want_t)
+    assert np.array_equal(got, W.write_streams(specs, 2048, True)) and np.array_equal(got_t, want_t)
 
 
 @pytest.mark.parametrize("nch", [1, 2])
@@ -253,7 +251,7 @@ def test_unflagged_frames_after_sparse_ones_equal_a_fresh_context(B, nch):
         assert np.array_equal(w_fixed, fresh.write_frames(specs)) and np.array_equal(w_adaptive, fresh.write_frames(specs, adaptive=True))
     finally:
         fresh.close()
-    assert np.array_equal(adaptive, R.write_streams(specs, 2048))
+    assert np.array_equal(adaptive, W.write_streams(specs, 2048))
 
 
 # ---- the decoder ---------------------------------------------------------------------------------------------------------------------
@@ -266,7 +264,7 @@ def test_decoder_equals_the_restatement(B, nch, fb):
     try:
         for tones in (True, False):
             for sparse in (True, False):
-                want, rej = SP.decode_streams(frames, nch, tones, sparse)
+                want, rej = W.decode_streams(frames, nch, tones, sparse)
                 dec.reset()
                 got = dec.decode(frames, tones=tones, sparse=sparse)
                 cnt = dec.counters(reset=True)
@@ -276,7 +274,7 @@ def test_decoder_equals_the_restatement(B, nch, fb):
                     assert rej.sum() == 0
                 if not sparse and fb < 2048:
                     assert rej[3] > 0   # bad_code: a word length of 0
-            want, _ = SP.decode_streams(frames, nch, tones, True)
+            want, _ = W.decode_streams(frames, nch, tones, True)
             dec.reset()
             parts = np.concatenate([dec.decode(frames[:, :2], tones=tones, sparse=True), dec.decode(frames[:, 2:], tones=tones, sparse=True)], axis=1)
             assert np.array_equal(parts.view(np.uint32), want.view(np.uint32))
@@ -294,9 +292,9 @@ def test_crafted_frames_beside_good_ones(B, nch):
     at3phip_decoder_set_frame_bytes does not admit.)"""
     fb = 376
     good = _sparse_frames(nch, fb)[0][0]
-    bad = SP.crafted_frames(nch, fb)
+    bad = W.crafted_frames(nch, fb)
     frames = np.stack([good, np.concatenate([bad, good[:F - len(bad)]])[:F], good[::-1].copy()])
-    want, rej = SP.decode_streams(frames, nch, True, True)
+    want, rej = W.decode_streams(frames, nch, True, True)
     dec = B.At3pHipDecoder(n_streams=S, channels=nch, max_frames=F, frame_bytes=fb)
     try:
         got = dec.decode(frames, tones=True, sparse=True)
@@ -340,9 +338,9 @@ def test_cli_sparse(B, tmp_path):
     dec = B.At3pHipDecoder(n_streams=1, channels=nch, max_frames=NF, frame_bytes=fb)
     try:
         lib_frames = enc.encode_frames(x, adaptive=True, sparse=True)[0]
-        want = np.concatenate([SP.write_adaptive(np.zeros((1, nch, 2048), np.float32), fb, True), lib_frames[:NF - 1]])   # the host's one-frame lead-in
+        want = np.concatenate([W.write_adaptive(np.zeros((1, nch, 2048), np.float32), fb, True), lib_frames[:NF - 1]])   # the host's one-frame lead-in
         assert np.array_equal(got, want)
-        assert SP.decode(want, nch, True, False)[1][3] > 0   # the file holds word length 0 inside the range
+        assert W.decode(want, nch, True, False)[1][3] > 0   # the file holds word length 0 inside the range
         lib_pcm = dec.decode(want[None], s16=True, tones=True, sparse=True)[0]
     finally:
         enc.close()

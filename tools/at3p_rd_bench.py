@@ -32,30 +32,29 @@ T_SIGNALS, T_KBIT = ("mix", "noise"), (64, 128, 352)
 
 
 def quality_restatement():
-    import at3p_rd_lib as RD
-    import at3p_sparse_lib as SP
-    from at3p_rate_lib import MIN_BYTES
+    import at3p_writer_lib as W
+    from at3p_writer_lib import MIN_BYTES
     out = {}
     for name in SIGNALS:
         for nch in (1, 2):
             x = G.signal_pcm(name, NF, nch)
-            sp = RD.specs_of_pcm(x)
+            sp = W.specs_of_pcm(x)
             for kbit, fb in KBIT.items():
                 if fb < MIN_BYTES[nch]:
                     continue
                 cell = {}
-                for key, frames in (("sparse", SP.write_adaptive(sp, fb, True)), ("rd", RD.write_rd(sp, fb))):
-                    y, rej = SP.decode(frames, nch)
+                for key, frames in (("sparse", W.write_adaptive(sp, fb, True)), ("rd", W.write_rd(sp, fb))):
+                    y, rej = W.decode(frames, nch, sparse=True)
                     assert rej.sum() == 0
                     cell[key] = [round(G.snr_db(x[:, :, c].reshape(-1), y[:, :, c].reshape(-1), NF), 2) for c in range(nch)]
-                rec = RD.write_rd(sp, fb, info=True)[1]
+                rec = W.write_rd(sp, fb, info=True)[1]
                 cell["frames_rd_of"] = [int(rec["chose_rd"].sum()), NF]
                 out[f"{name}_{nch}_{kbit}"] = cell
     return out
 
 
 def quality_library(B):
-    from at3p_rate_lib import MIN_BYTES
+    from at3p_writer_lib import MIN_BYTES
     out = {}
     for name in SIGNALS:
         for nch in (1, 2):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """DEVELOPMENT HARNESS: the ATRAC3plus adaptive writer (k_at3p_write_adaptive, k_at3p_write_adaptive_tonal) and the decoder's
-kernels at frame sizes other than 2048 bytes through the CPU SIMT emulator, against the restatement tests/host/at3p_rate_cpu.c.
+kernels at frame sizes other than 2048 bytes through the CPU SIMT emulator, against the restatement tests/host/at3p_writer_cpu.c.
 Driver of tests/test_at3p_rate_cpu.py, which runs it in child processes because the harness reads EMU_STRICT, EMU_FENCE, EMU_ORDER
 and EMU_STREAMS when the library loads.
 
@@ -13,8 +13,7 @@ import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
 import numpy as np
-import at3p_alloc_lib as L
-import at3p_rate_lib as R
+import at3p_writer_lib as W
 import at3p_tonal_write_lib as TW
 from atracdenc_amd.binding import (AT3HIP_ASYNC, AT3HIP_OUT_ON_DEVICE, AT3HIP_PCM_ON_DEVICE, AT3PHIP_ALLOC_ADAPTIVE, AT3PHIP_DECODE_TONES,
                                    AT3PHIP_TONES_GATED, AT3PHIP_TONES_SHARED, At3pHip, At3pHipDecoder, pack_tonal_blocks)
@@ -22,7 +21,7 @@ import run_emu
 from run_emu_decode import DevBuf, bits, report
 
 DEV = AT3HIP_PCM_ON_DEVICE | AT3HIP_OUT_ON_DEVICE
-SIZES = {1: (R.MIN_BYTES[1], 376, 2040), 2: (R.MIN_BYTES[2], 376, 2040)}
+SIZES = {1: (W.MIN_BYTES[1], 376, 2040), 2: (W.MIN_BYTES[2], 376, 2040)}
 
 
 def write_exact(enc, specs, fb, recs=None):
@@ -58,13 +57,13 @@ def run(name, nch, fb, specs, blocks=None):
     recs = None if blocks is None else np.stack([pack_tonal_blocks(row, nch) for row in blocks])
     got = write_exact(enc, specs, fb, recs)
     enc.close()
-    exp = np.stack([R.write_adaptive(specs[s], fb, None, None if blocks is None else blocks[s]) for s in range(S)])
+    exp = np.stack([W.write_adaptive(specs[s], fb, blocks=None if blocks is None else blocks[s]) for s in range(S)])
     report(f"{name} nch={nch} size={fb} writer", (got != exp).any(axis=2).sum())
     dec = At3pHipDecoder(n_streams=S, channels=nch, max_frames=F, lib_path=run_emu.EMU, frame_bytes=fb)
     pcm = decode_exact(dec, exp, True)
     cnt = dec.counters()
     dec.close()
-    epcm, erej = R.decode_streams(exp, nch, True)
+    epcm, erej = W.decode_streams(exp, nch, True)
     report(f"{name} nch={nch} size={fb} decoder", (bits(pcm) != bits(epcm)).reshape(S, F, -1).any(axis=2).sum())
     report(f"{name} nch={nch} size={fb} counters {list(cnt.values())}", list(cnt.values()) != erej.tolist(), t)
 
@@ -99,9 +98,9 @@ def queued(nch, fb=376):
     t = time.time()
     x = np.stack([at3p_signal("mix", 2 * F, channel=c) for c in range(nch)], axis=-1)[None].astype(np.float32)
     got = two_calls(lambda e: e.encode_frames_ptr, x, ASY)
-    sp = L.specs_of("mix", nch, 2 * F)
-    report(f"queued nch={nch} encode, first call at 2048", (got[0] != R.write_adaptive(sp[:F], 2048)).any(axis=1).sum())
-    report(f"queued nch={nch} encode, second call at {fb}", (got[1] != R.write_adaptive(sp[F:], fb)).any(axis=1).sum(), t)
+    sp = W.specs_of("mix", nch, 2 * F)
+    report(f"queued nch={nch} encode, first call at 2048", (got[0] != W.write_adaptive(sp[:F], 2048)).any(axis=1).sum())
+    report(f"queued nch={nch} encode, second call at {fb}", (got[1] != W.write_adaptive(sp[F:], fb)).any(axis=1).sum(), t)
 
     t = time.time()
     xt = (G.twin_pcm("tones", 2 * F) if nch == 2 else G.signal_pcm("tones", 2 * F, 1))[None].astype(np.float32)
@@ -113,7 +112,7 @@ def queued(nch, fb=376):
         return np.zeros((specs.shape[0], 2048), np.uint8)
     _, blocks, _ = G.pipeline(xt[0], True, True, grab)
     assert sum(G.n_waves(b) for b in blocks[:-1]) > 0
-    exp = [R.write_adaptive(kept["specs"][:F], 2048, None, kept["recs"][:F]), R.write_adaptive(kept["specs"][F:], fb, None, kept["recs"][F:])]
+    exp = [W.write_adaptive(kept["specs"][:F], 2048, blocks=kept["recs"][:F]), W.write_adaptive(kept["specs"][F:], fb, blocks=kept["recs"][F:])]
     report(f"queued nch={nch} tonal encode, first call at 2048", (got[0] != exp[0]).any(axis=1).sum())
     report(f"queued nch={nch} tonal encode, second call at {fb}", (got[1] != exp[1]).any(axis=1).sum(), t)
 
@@ -130,7 +129,7 @@ def queued(nch, fb=376):
     dec.close()
     for b in src + dst:
         b.free()
-    ref = R.RateDecoder(nch, True)
+    ref = W.Decoder(nch, True)
     want = [ref.decode(exp[0]), ref.decode(exp[1])]
     report(f"queued nch={nch} decode, first call at 2048", (bits(pcm[0]) != bits(want[0])).reshape(F, -1).any(axis=1).sum())
     report(f"queued nch={nch} decode, second call at {fb}", (bits(pcm[1]) != bits(want[1])).reshape(F, -1).any(axis=1).sum())
@@ -143,12 +142,12 @@ if __name__ == "__main__":
     for nch in (2, 1):
         for fb in SIZES[nch]:
             if not want or "signals" in want:    # a loud signal and silence beside full-scale noise
-                run("signals", nch, fb, np.stack([np.concatenate([L.specs_of("mix", nch, 1), L.specs_of("silence", nch, 1)]),
-                                                  L.full_scale_noise(2, nch)]))
+                run("signals", nch, fb, np.stack([np.concatenate([W.specs_of("mix", nch, 1), W.specs_of("silence", nch, 1)]),
+                                                  W.full_scale_noise(2, nch)]))
             if not want or "tonal" in want:      # the largest record on a full-scale frame and on silence, beside no record and a small one
-                sp = np.stack([np.concatenate([L.full_scale_noise(1, nch, seed=4), np.zeros((1, nch, 2048), np.float32)]), L.specs_of("mix", nch, 2)])
+                sp = np.stack([np.concatenate([W.full_scale_noise(1, nch, seed=4), np.zeros((1, nch, 2048), np.float32)]), W.specs_of("mix", nch, 2)])
                 run("tonal", nch, fb, sp, [[TW.largest_block(nch), TW.largest_block(nch)], [None, TW.case_blocks(f"small_{nch}")[0][0]]])
             if not want or "odd" in want:
-                run("odd", nch, fb, np.stack([L.odd_specs(nch, 2), L.specs_of("noise", nch, 2)]))
+                run("odd", nch, fb, np.stack([W.odd_specs(nch, 2), W.specs_of("noise", nch, 2)]))
         if "queued" in want:
             queued(nch)

@@ -13,9 +13,7 @@ import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
 import numpy as np
-import at3p_alloc_lib as L
-import at3p_rd_lib as RD
-import at3p_sparse_lib as SP
+import at3p_writer_lib as W
 import at3p_tonal_write_lib as TW
 from atracdenc_amd.binding import (AT3HIP_OUT_ON_DEVICE, AT3HIP_PCM_ON_DEVICE, AT3PHIP_ALLOC_ADAPTIVE, AT3PHIP_ALLOC_RD, AT3PHIP_ALLOC_SPARSE, At3pHip,
                                    pack_tonal_blocks)
@@ -44,7 +42,7 @@ def run(name, nch, fb, specs, blocks=None):
     enc.close()
     exp = []
     for s in range(S):
-        fr, rec, _ = RD.write_rd(specs[s], fb, None, None if blocks is None else blocks[s], info=True)
+        fr, rec, _ = W.write_rd(specs[s], fb, None, None if blocks is None else blocks[s], info=True)
         seen.update(int(c) for c in rec["chose_rd"])
         exp.append(fr)
     report(f"{name} nch={nch} size={fb} writer", (got != np.stack(exp)).any(axis=2).sum(), t)
@@ -52,15 +50,15 @@ def run(name, nch, fb, specs, blocks=None):
 
 def main():
     if "--nobuild" not in sys.argv: run_emu.build("--strict" in sys.argv)
-    sig = lambda nch: np.stack([np.stack([L.specs_of(n, nch, 1)[0] for n in ("noise", "tones")]), np.stack([L.specs_of(n, nch, 1)[0] for n in ("mix", "burst")])])
+    sig = lambda nch: np.stack([np.stack([W.specs_of(n, nch, 1)[0] for n in ("noise", "tones")]), np.stack([W.specs_of(n, nch, 1)[0] for n in ("mix", "burst")])])
     run("signals", 2, 376, sig(2))
     run("signals", 2, 2048, sig(2))
     run("signals", 1, 192, sig(1))
     for nch in (2, 1):   # the special cases of A3s' closing rules, where the budget binds
-        sp, blocks = SP.edge_specs(nch)
+        sp, blocks = W.edge_specs(nch)
         run("edge", nch, R_MIN[nch], sp[None], [blocks])
-    run("odd", 2, 280, np.stack([L.odd_specs(2, 2), L.specs_of("noise", 2, 2)]))
-    run("tonal", 2, 224, np.stack([L.full_scale_noise(2, 2), L.specs_of("tones", 2, 2)]),
+    run("odd", 2, 280, np.stack([W.odd_specs(2, 2), W.specs_of("noise", 2, 2)]))
+    run("tonal", 2, 224, np.stack([W.full_scale_noise(2, 2), W.specs_of("tones", 2, 2)]),
         [[TW.largest_block(2), TW.largest_block(2)], [None, TW.case_blocks("small_2")[0][0]]])
     report(f"guard outcomes seen {sorted(seen)}", seen != {0, 1})
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Writes tests/golden/at3p_ref_parts.npz: adaptive and sparse ATRAC3plus frames written by the REFERENCE's part coders
 (TWordLenEncoder, TSfIdxEncoder, TQuantUnitsEncoder, TTonalComponentEncoder) through the driver of tests/at3p_ref_parts_lib.py, under
-the allocation (N, word lengths) the restatement tests/host/at3p_sparse_cpu.c chooses. Runs only where the reference and
+the allocation (N, word lengths) the restatement tests/host/at3p_writer_cpu.c chooses. Runs only where the reference and
 oracle/_ref/libat3ref.so are. Per cell of at3p_ref_parts_lib.cells() - mono at 176, 376 and 2048 bytes, stereo at 224, 376 and
 2048, and one cell with tonal blocks and window flags per channel count, each adaptive and sparse; 3 streams x 4 frames - the file
 holds the frames, N, the word lengths and the reference's bit count, and in one JSON string the cells' parameters and the SHA-256 of
