@@ -16,7 +16,9 @@
 //                                t and k, and the guard that keeps the sparse allocation where it has less distortion. at3p_rd.hpp
 //                                holds their arithmetic, at3p_rd.hip instantiates them, for the same reason.
 #pragma once
-#include "../../include/at3phip.h"
+#include <cstring>
+#include <type_traits>
+
 #include "at3p_write.hpp"
 #include "at3p_rd.hpp"
 
@@ -141,20 +143,25 @@ inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels,
     return count();
 }
 
+// The argument checks every host allocator of include/at3phip.h makes (t: the scan's first result, t* or j*)
+inline int host_allocate_args(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, int32_t frame_bytes, const uint8_t* wl_out,
+                              const int32_t* n_units, const int32_t* t, const int32_t* k)
+{
+    if (!sfi || !bits || !wl_out || !n_units || !t || !k || channels < 1 || channels > 2) return AT3HIP_EINVAL;
+    if (!admissible_frame_bytes(frame_bytes, channels)) return AT3HIP_EINVAL;
+    if (tail_bits < 0 || tail_bits > 8 * frame_bytes - 3) return AT3HIP_EINVAL;
+    for (int i = 0; i < 32 * channels; ++i)
+        if (sfi[i] > 63) return AT3HIP_EINVAL;
+    return AT3HIP_OK;
+}
+
 // at3phip_host_allocate_sized and at3phip_host_allocate_sparse: the arguments' checks, then host_allocate
 inline int host_allocate_checked(const uint8_t* sfi, const uint16_t* bits, int32_t channels, int32_t tail_bits, int32_t frame_bytes, uint8_t* wl_out,
                                  int32_t* n_units, int32_t* t, int32_t* k, bool sparse)
 {
-    if (!sfi || !bits || !wl_out || !n_units || !t || !k || channels < 1 || channels > 2) return AT3HIP_EINVAL;
-    if (frame_bytes % 8 || frame_bytes > AT3PHIP_FRAME_BYTES ||
-        frame_bytes < (channels == 2 ? AT3PHIP_MIN_FRAME_BYTES_STEREO : AT3PHIP_MIN_FRAME_BYTES_MONO))
-        return AT3HIP_EINVAL;
-    const int size_bits = 8 * frame_bytes - 3;
-    if (tail_bits < 0 || tail_bits > size_bits) return AT3HIP_EINVAL;
-    for (int i = 0; i < 32 * channels; ++i)
-        if (sfi[i] > 63) return AT3HIP_EINVAL;
+    if (const int rc = host_allocate_args(sfi, bits, channels, tail_bits, frame_bytes, wl_out, n_units, t, k)) return rc;
     int n = 0, ts = 0, ks = 0;
-    host_allocate(sfi, bits, channels, tail_bits, size_bits, wl_out, &n, &ts, &ks, sparse);
+    host_allocate(sfi, bits, channels, tail_bits, 8 * frame_bytes - 3, wl_out, &n, &ts, &ks, sparse);
     *n_units = n;
     *t = ts;
     *k = ks;
@@ -695,5 +702,27 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
 }
 // (the instantiations are named where they are launched, at3p_alloc.hip, at3p_sparse.hip and at3p_rd.hip: naming one instantiates it, and a
 // translation unit must hold only its own)
+
+// ---- host: the launch of a unit's two instantiations, P without records and PT with them ------------------------------------------
+// wp: the fixed writer's parameters as at3phip.hip's launch_write fills them, tone_vlc included; wp.tonal null: the writer without
+// records. The word-length code tables, the mantissa steps of a rate-distortion type and the frame size travel in the kernel's
+// arguments: nothing is allocated or uploaded for the adaptive path. wp.out is [n_items][frame_bytes].
+template <typename P>
+void launch_write_adaptive_kernel(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on)
+{
+    using Fixed = std::conditional_t<P::kTonal, WriteParamsTonal, WriteParams>;
+    AdaptiveParams<P> ap;
+    static_cast<Fixed&>(ap) = wp;
+    if constexpr (alloc_is_rd<P>::value) memcpy(ap.mant, AT3P_MANT, sizeof(ap.mant));
+    memcpy(ap.wl_vlc, AT3P_WL_VLC, sizeof(ap.wl_vlc));
+    ap.frame_bytes = frame_bytes;
+    hipLaunchKernelGGL(k_at3p_write_adaptive_with<P>, dim3((unsigned)wp.n_items), dim3(256), 0, on, ap);
+}
+template <typename P, typename PT>
+void launch_write_adaptive_as(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on)
+{
+    if (wp.tonal) launch_write_adaptive_kernel<PT>(wp, frame_bytes, on);
+    else launch_write_adaptive_kernel<P>(wp, frame_bytes, on);
+}
 
 }  // namespace at3p

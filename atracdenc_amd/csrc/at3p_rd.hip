@@ -3,8 +3,6 @@
 // at3p_sparse.hip is one: the instantiations share device functions with the other four writer kernels, and compiled next to them
 // they change the code the compiler makes for those. at3phip.hip finds the launch as a weak symbol; a build without this file
 // refuses AT3PHIP_ALLOC_RD and has no at3phip_host_allocate_rd, the symbol by which a host detects the flag.
-#include <cstring>
-
 #include <hip/hip_runtime.h>
 
 #include "../../include/at3phip.h"
@@ -13,33 +11,12 @@
 
 namespace at3p {
 
-namespace {
-#include "at3p_tone_vlc.inc"
-#include "at3p_mant.inc"
-}
-
 constexpr auto k_at3p_write_adaptive_rd = k_at3p_write_adaptive_with<WriteParamsRd>;
 constexpr auto k_at3p_write_adaptive_tonal_rd = k_at3p_write_adaptive_with<WriteParamsTonalRd>;
 
-// as launch_write_adaptive (at3p_alloc.hip)
 __attribute__((visibility("default"))) void launch_write_adaptive_rd(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on)
 {
-    if (wp.tonal) {
-        AdaptiveParams<WriteParamsTonalRd> ap;
-        static_cast<WriteParamsTonal&>(ap) = wp;
-        memcpy(ap.mant, AT3P_MANT, sizeof(ap.mant));
-        memcpy(ap.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(ap.tone_vlc));
-        memcpy(ap.wl_vlc, AT3P_WL_VLC, sizeof(ap.wl_vlc));
-        ap.frame_bytes = frame_bytes;
-        hipLaunchKernelGGL(k_at3p_write_adaptive_tonal_rd, dim3((unsigned)wp.n_items), dim3(256), 0, on, ap);
-    } else {
-        AdaptiveParams<WriteParamsRd> ap;
-        static_cast<WriteParams&>(ap) = static_cast<const WriteParams&>(wp);
-        memcpy(ap.mant, AT3P_MANT, sizeof(ap.mant));
-        memcpy(ap.wl_vlc, AT3P_WL_VLC, sizeof(ap.wl_vlc));
-        ap.frame_bytes = frame_bytes;
-        hipLaunchKernelGGL(k_at3p_write_adaptive_rd, dim3((unsigned)wp.n_items), dim3(256), 0, on, ap);
-    }
+    launch_write_adaptive_as<WriteParamsRd, WriteParamsTonalRd>(wp, frame_bytes, on);
 }
 
 // R2-R4 on the host. dist: S [channels][32][8]. Returns Bits of the allocation written.
@@ -114,18 +91,12 @@ static int host_allocate_rd(const uint8_t* sfi, const uint16_t* bits, const uint
 extern "C" int at3phip_host_allocate_rd(const uint8_t* sfi, const uint16_t* bits, const uint64_t* dist, int32_t channels, int32_t tail_bits,
                                         int32_t frame_bytes, uint8_t* wl_out, int32_t* n_units, int32_t* j, int32_t* k, int32_t* chose_rd)
 {
-    if (!dist || !chose_rd || !sfi || !bits || !wl_out || !n_units || !j || !k || channels < 1 || channels > 2) return AT3HIP_EINVAL;
-    if (frame_bytes % 8 || frame_bytes > AT3PHIP_FRAME_BYTES ||
-        frame_bytes < (channels == 2 ? AT3PHIP_MIN_FRAME_BYTES_STEREO : AT3PHIP_MIN_FRAME_BYTES_MONO))
-        return AT3HIP_EINVAL;
-    const int size_bits = 8 * frame_bytes - 3;
-    if (tail_bits < 0 || tail_bits > size_bits) return AT3HIP_EINVAL;
-    for (int i = 0; i < 32 * channels; ++i)
-        if (sfi[i] > 63) return AT3HIP_EINVAL;
+    if (!dist || !chose_rd) return AT3HIP_EINVAL;
+    if (const int rc = at3p::host_allocate_args(sfi, bits, channels, tail_bits, frame_bytes, wl_out, n_units, j, k)) return rc;
     for (int i = 0; i < 256 * channels; ++i)
         if (dist[i] > (1ull << 47)) return AT3HIP_EINVAL;   // 128 lines of at most 2^40 each
     int n = 0, js = 0, ks = 0, rd = 0;
-    at3p::host_allocate_rd(sfi, bits, dist, channels, tail_bits, size_bits, wl_out, &n, &js, &ks, &rd);
+    at3p::host_allocate_rd(sfi, bits, dist, channels, tail_bits, 8 * frame_bytes - 3, wl_out, &n, &js, &ks, &rd);
     *n_units = n;
     *j = js;
     *k = ks;

@@ -15,6 +15,7 @@ static_assert(kRdJCount % 4 == 0, "the four wavefronts share the scan evenly");
 
 // the parameter types of the rate-distortion instantiations: the fixed writer's, marked (as WriteParamsSparse in at3p_alloc.hpp),
 // with atrac3p_mant_tab, which the writers' tables hold only inverted, in the kernel's arguments
+#include "at3p_mant.inc"
 struct WriteParamsRd : WriteParams { float mant[8]; };
 struct WriteParamsTonalRd : WriteParamsTonal { float mant[8]; };
 template <typename P> struct alloc_is_rd { static constexpr bool value = false; };

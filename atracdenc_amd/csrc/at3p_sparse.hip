@@ -3,8 +3,6 @@
 // reason at3p_alloc.hip is one: the instantiations share device functions with the unflagged kernels, and compiled next to them they
 // change the code the compiler makes for those. at3phip.hip finds the launches as weak symbols; a build without this file refuses
 // AT3PHIP_ALLOC_SPARSE and AT3PHIP_DECODE_SPARSE.
-#include <cstring>
-
 #include <hip/hip_runtime.h>
 
 #include "../../include/at3phip.h"
@@ -15,32 +13,14 @@
 
 namespace at3p {
 
-namespace {
-#include "at3p_tone_vlc.inc"
-}
-
 constexpr auto k_at3p_write_adaptive_sparse = k_at3p_write_adaptive_with<WriteParamsSparse>;
 constexpr auto k_at3p_write_adaptive_tonal_sparse = k_at3p_write_adaptive_with<WriteParamsTonalSparse>;
 constexpr auto k_at3pd_unpack_sparse = k_at3pd_unpack_sparse_with<false>;
 constexpr auto k_at3pd_unpack_sparse_sized = k_at3pd_unpack_sparse_with<true>;
 
-// as launch_write_adaptive (at3p_alloc.hip)
 __attribute__((visibility("default"))) void launch_write_adaptive_sparse(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on)
 {
-    if (wp.tonal) {
-        AdaptiveParams<WriteParamsTonalSparse> ap;
-        static_cast<WriteParamsTonal&>(ap) = wp;
-        memcpy(ap.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(ap.tone_vlc));
-        memcpy(ap.wl_vlc, AT3P_WL_VLC, sizeof(ap.wl_vlc));
-        ap.frame_bytes = frame_bytes;
-        hipLaunchKernelGGL(k_at3p_write_adaptive_tonal_sparse, dim3((unsigned)wp.n_items), dim3(256), 0, on, ap);
-    } else {
-        AdaptiveParams<WriteParamsSparse> ap;
-        static_cast<WriteParams&>(ap) = static_cast<const WriteParams&>(wp);
-        memcpy(ap.wl_vlc, AT3P_WL_VLC, sizeof(ap.wl_vlc));
-        ap.frame_bytes = frame_bytes;
-        hipLaunchKernelGGL(k_at3p_write_adaptive_sparse, dim3((unsigned)wp.n_items), dim3(256), 0, on, ap);
-    }
+    launch_write_adaptive_as<WriteParamsSparse, WriteParamsTonalSparse>(wp, frame_bytes, on);
 }
 
 __attribute__((visibility("default"))) void launch_unpack_sparse(const DecUnpackParams& up, bool sized, dim3 grid, hipStream_t on)

@@ -11,6 +11,7 @@
 // that fits is found from one prefix sum. What does not depend on the spectrum at all - the three leading bits,
 // TConfigure and TWordLenEncoder for each (channels, units) - is formed on the host (WriteTables::head).
 #pragma once
+#include "../../include/at3phip.h"
 #include "at3_bits.hpp"
 #include "at3_common.hpp"
 
@@ -20,6 +21,14 @@ namespace at3p {
 
 constexpr int kFrameBytes = 2048;                  // TAt3PBitStream(out, 2048) (at3p.cpp:40)
 constexpr int kSizeBits = kFrameBytes * 8 - 3;     // FrameSzToAllocBits (at3p_bitstream.cpp:481)
+
+// An admissible frame size (include/at3phip.h, ADAPTIVE WORD LENGTHS, A5): a multiple of 8 between the channel count's minimum and
+// 2048. The setters of the context and of the decoder and the host allocators all ask here.
+inline int min_frame_bytes(int channels) { return channels == 2 ? AT3PHIP_MIN_FRAME_BYTES_STEREO : AT3PHIP_MIN_FRAME_BYTES_MONO; }
+inline bool admissible_frame_bytes(int frame_bytes, int channels)
+{
+    return frame_bytes >= min_frame_bytes(channels) && frame_bytes <= kFrameBytes && frame_bytes % 8 == 0;
+}
 
 struct WriteHead {
     uint32_t words[8];     // the frame's first bits, most significant bit first

@@ -69,15 +69,15 @@ namespace at3p {
 constexpr auto k_at3p_write = k_at3p_write_with<WriteParams>;
 constexpr auto k_at3p_write_tonal = k_at3p_write_with<WriteParamsTonal>;
 
-// The adaptive writer's launch (wp.tonal null: without records). Its kernels are a translation unit of their own, at3p_alloc.hip,
-// so that this one's device code stays instruction for instruction what it was; weak, because the stand-alone host programs
-// that link this file without that one (tests/test_owned_alloc_cpu.py) must still link: there the flag is an error.
+// The launches of the adaptive writer's kernels (wp.tonal null: without records) and of the sparse unpack kernels (sized: the frame
+// size is not 2048). The kernels are translation units of their own - at3p_alloc.hip, at3p_sparse.hip, at3p_rd.hip - so that this
+// one's device code stays instruction for instruction what it was; weak, because the stand-alone host programs that link this file
+// without them (tests/test_owned_alloc_cpu.py) must still link: there resolve_alloc_mode and choose_unpack refuse the flags.
 __attribute__((weak, visibility("default"))) void launch_write_adaptive(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
-// The same with AT3PHIP_ALLOC_SPARSE (SPARSE WORD LENGTHS): the sparse instantiations, in at3p_sparse.hip for the same reason and weak
-// for the same reason.
 __attribute__((weak, visibility("default"))) void launch_write_adaptive_sparse(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
-// And with AT3PHIP_ALLOC_RD (RATE-DISTORTION WORD LENGTHS): at3p_rd.hip, as the two above.
 __attribute__((weak, visibility("default"))) void launch_write_adaptive_rd(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
+struct DecUnpackParams;
+__attribute__((weak, visibility("default"))) void launch_unpack_sparse(const DecUnpackParams& up, bool sized, dim3 grid, hipStream_t on);
 }
 
 namespace {
@@ -105,10 +105,7 @@ int quiesce(at3phip_ctx* c)
     return AT3HIP_OK;
 }
 
-// The smallest admissible frame size for a channel count (include/at3phip.h, ADAPTIVE WORD LENGTHS, A5)
-int min_frame_bytes(int channels) { return channels == 2 ? AT3PHIP_MIN_FRAME_BYTES_STEREO : AT3PHIP_MIN_FRAME_BYTES_MONO; }
-bool admissible_frame_bytes(int32_t fb, int channels) { return fb >= min_frame_bytes(channels) && fb <= kFrameBytes && fb % 8 == 0; }
-// the setters' last-error text for a size that is not
+// the setters' last-error text for a size that is not admissible (admissible_frame_bytes, at3p_write.hpp)
 struct FrameBytesError {
     char text[96];
 };
@@ -119,30 +116,47 @@ FrameBytesError frame_bytes_error(int32_t fb, int channels)
     return e;
 }
 
-// A frame-writing call at the context's frame size: the fixed table is the reference's and fills 2048 bytes only, so at any other
-// size the call needs AT3PHIP_ALLOC_ADAPTIVE. Checked before anything is queued or any state moves.
-int check_frame_size(at3phip_ctx* c, uint32_t flags)
-{
-    if (c->frame_bytes != kFrameBytes && !(flags & AT3PHIP_ALLOC_ADAPTIVE))
-        return fail(c, AT3HIP_EINVAL, "the fixed table is defined for 2048-byte frames only: this context's frame size needs AT3PHIP_ALLOC_ADAPTIVE");
-    if ((flags & AT3PHIP_ALLOC_ADAPTIVE) && !launch_write_adaptive)
-        return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_ADAPTIVE: this build has no adaptive writer (at3p_alloc.hip)");
-    return AT3HIP_OK;
-}
+// How a frame-writing call chooses its word lengths: the fixed table, or one of the adaptive writer's three units.
+enum AllocMode { kAllocFixed, kAllocAdaptive, kAllocSparse, kAllocRd };
+struct AllocWriter {
+    void (*launch)(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);   // null: this build was linked without the unit
+    const char *flag, *name, *unit;   // for the refusal's text
+};
+const AllocWriter kAllocWriters[] = {
+    {nullptr, nullptr, nullptr, nullptr},   // kAllocFixed: k_at3p_write, k_at3p_write_tonal
+    {launch_write_adaptive, "AT3PHIP_ALLOC_ADAPTIVE", "adaptive", "at3p_alloc.hip"},
+    {launch_write_adaptive_sparse, "AT3PHIP_ALLOC_SPARSE", "sparse", "at3p_alloc.hip, at3p_sparse.hip"},
+    {launch_write_adaptive_rd, "AT3PHIP_ALLOC_RD", "rate-distortion", "at3p_rd.hip"},
+};
 
-// AT3PHIP_ALLOC_SPARSE on a frame-writing call: only together with AT3PHIP_ALLOC_ADAPTIVE, and only in a build that has the sparse
-// writer. Checked before anything is queued or any state moves.
-// AT3PHIP_ALLOC_RD: only together with both, and only in a build that has the rate-distortion writer.
-int check_sparse(at3phip_ctx* c, uint32_t flags)
+// The allocation mode of a frame-writing call with these flags at the context's frame size, or the call's refusal. The fixed table is
+// the reference's and fills 2048 bytes only, so at any other size the call needs AT3PHIP_ALLOC_ADAPTIVE; AT3PHIP_ALLOC_SPARSE counts
+// only together with it, AT3PHIP_ALLOC_RD only together with both; each needs its writer in the build. Every frame-writing call asks
+// directly after its argument checks: a refused call queues nothing, allocates nothing and moves no state.
+int resolve_alloc_mode(at3phip_ctx* c, uint32_t flags, AllocMode* mode)
 {
-    if (flags & AT3PHIP_ALLOC_RD) {
-        if ((flags & (AT3PHIP_ALLOC_ADAPTIVE | AT3PHIP_ALLOC_SPARSE)) != (AT3PHIP_ALLOC_ADAPTIVE | AT3PHIP_ALLOC_SPARSE))
-            return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_RD needs AT3PHIP_ALLOC_ADAPTIVE and AT3PHIP_ALLOC_SPARSE in the same call");
-        if (!launch_write_adaptive_rd) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_RD: this build has no rate-distortion writer (at3p_rd.hip)");
+    const bool adaptive = flags & AT3PHIP_ALLOC_ADAPTIVE, sparse = flags & AT3PHIP_ALLOC_SPARSE, rd = flags & AT3PHIP_ALLOC_RD;
+    auto missing = [c](AllocMode m) {
+        const AllocWriter& w = kAllocWriters[m];
+        char msg[128];
+        snprintf(msg, sizeof(msg), "%s: this build has no %s writer (%s)", w.flag, w.name, w.unit);
+        return fail(c, AT3HIP_EINVAL, msg);
+    };
+    if (c->frame_bytes != kFrameBytes) {
+        if (!adaptive)
+            return fail(c, AT3HIP_EINVAL, "the fixed table is defined for 2048-byte frames only: this context's frame size needs AT3PHIP_ALLOC_ADAPTIVE");
+        if (!kAllocWriters[kAllocAdaptive].launch) return missing(kAllocAdaptive);
     }
-    if (!(flags & AT3PHIP_ALLOC_SPARSE)) return AT3HIP_OK;
-    if (!(flags & AT3PHIP_ALLOC_ADAPTIVE)) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_SPARSE needs AT3PHIP_ALLOC_ADAPTIVE in the same call");
-    if (!launch_write_adaptive_sparse) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_SPARSE: this build has no sparse writer (at3p_alloc.hip, at3p_sparse.hip)");
+    if (rd) {
+        if (!adaptive || !sparse) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_RD needs AT3PHIP_ALLOC_ADAPTIVE and AT3PHIP_ALLOC_SPARSE in the same call");
+        if (!kAllocWriters[kAllocRd].launch) return missing(kAllocRd);
+    }
+    if (sparse) {
+        if (!adaptive) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_SPARSE needs AT3PHIP_ALLOC_ADAPTIVE in the same call");
+        if (!kAllocWriters[kAllocSparse].launch) return missing(kAllocSparse);
+    }
+    if (adaptive && !kAllocWriters[kAllocAdaptive].launch) return missing(kAllocAdaptive);
+    *mode = rd ? kAllocRd : sparse ? kAllocSparse : adaptive ? kAllocAdaptive : kAllocFixed;
     return AT3HIP_OK;
 }
 
@@ -185,44 +199,42 @@ int launch_mdct(at3phip_ctx* c, const float* d_bands, int n_frames, const uint16
     return AT3HIP_OK;
 }
 
-// tonal: the call's records [S][n_frames] in host memory, already checked (check_tonal), or null: the writer without records.
-// d_records: the same in device memory, as the tone analysis left them (valid by construction).
-// adaptive: AT3PHIP_ALLOC_ADAPTIVE, the writer of at3p_alloc.hpp.
-int launch_write(at3phip_ctx* c, const float* d_specs, int n_frames, const uint16_t* win_flags, uint8_t* d_frames, hipStream_t on = nullptr,
-                 const at3phip_tonal_block* tonal = nullptr, const TonalBlock* d_records = nullptr, bool adaptive = false, bool sparse = false, bool rd = false)
+// What a frame-writing call hands to the writer, all device memory but win_flags and tonal.
+struct WriteCall {
+    const float* d_specs;
+    int n_frames;
+    const uint16_t* win_flags;           // host memory, or null: sine windows
+    uint8_t* d_frames;
+    hipStream_t on;
+    const at3phip_tonal_block* tonal;    // the call's records [S][n_frames] in host memory, already checked (check_tonal), or null
+    const TonalBlock* d_records;         // the same in device memory, as the tone analysis left them (valid by construction), or null
+};
+
+// mode: what resolve_alloc_mode gave the call. Without records from either source: the writer without records.
+int launch_write(at3phip_ctx* c, AllocMode mode, const WriteCall& w)
 {
     const size_t S = c->cfg.n_streams, C = c->cfg.channels;
-    if (!on) on = c->stream;
-    if (win_flags) HIPCHK(c, hipMemcpyAsync(c->d_flags, win_flags, S * n_frames * C * sizeof(uint16_t), hipMemcpyHostToDevice, on));
+    if (w.win_flags) HIPCHK(c, hipMemcpyAsync(c->d_flags, w.win_flags, S * w.n_frames * C * sizeof(uint16_t), hipMemcpyHostToDevice, w.on));
     WriteParamsTonal wp;
     wp.W = c->d_wtables;
-    wp.specs = d_specs;
-    wp.flags = win_flags ? c->d_flags : nullptr;
-    wp.out = d_frames;
+    wp.specs = w.d_specs;
+    wp.flags = w.win_flags ? c->d_flags : nullptr;
+    wp.out = w.d_frames;
     wp.nch = (int)C;
-    wp.n_items = (int)(S * n_frames);
-    if (adaptive && !launch_write_adaptive) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_ADAPTIVE: this build has no adaptive writer (at3p_alloc.hip)");
-    if (tonal && !d_records) {
+    wp.n_items = (int)(S * w.n_frames);
+    wp.tonal = w.d_records;
+    if (w.tonal && !w.d_records) {
         if (!c->d_tonal) {
             const int rc = dev_alloc(c, &c->d_tonal, S * (size_t)c->cfg.max_frames);
             if (rc != AT3HIP_OK) return rc;
         }
-        HIPCHK(c, hipMemcpyAsync(c->d_tonal, tonal, S * n_frames * sizeof(TonalBlock), hipMemcpyHostToDevice, on));
-        d_records = c->d_tonal;
+        HIPCHK(c, hipMemcpyAsync(c->d_tonal, w.tonal, S * w.n_frames * sizeof(TonalBlock), hipMemcpyHostToDevice, w.on));
+        wp.tonal = c->d_tonal;
     }
-    wp.tonal = d_records;
-    if (adaptive && sparse && rd) {
-        launch_write_adaptive_rd(wp, c->frame_bytes, on);
-    } else if (adaptive && sparse) {
-        launch_write_adaptive_sparse(wp, c->frame_bytes, on);
-    } else if (adaptive) {
-        launch_write_adaptive(wp, c->frame_bytes, on);
-    } else if (d_records) {
-        memcpy(wp.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(wp.tone_vlc));
-        hipLaunchKernelGGL(k_at3p_write_tonal, dim3((unsigned)(S * n_frames)), dim3(256), 0, on, wp);
-    } else {
-        hipLaunchKernelGGL(k_at3p_write, dim3((unsigned)(S * n_frames)), dim3(256), 0, on, static_cast<const WriteParams&>(wp));
-    }
+    if (wp.tonal) memcpy(wp.tone_vlc, AT3P_TONE_BANDS_VLC, sizeof(wp.tone_vlc));
+    if (mode != kAllocFixed) kAllocWriters[mode].launch(wp, c->frame_bytes, w.on);
+    else if (wp.tonal) hipLaunchKernelGGL(k_at3p_write_tonal, dim3(wp.n_items), dim3(256), 0, w.on, wp);
+    else hipLaunchKernelGGL(k_at3p_write, dim3(wp.n_items), dim3(256), 0, w.on, static_cast<const WriteParams&>(wp));
     HIPCHK(c, hipGetLastError());
     return AT3HIP_OK;
 }
@@ -494,9 +506,8 @@ int at3phip_write_frames_tonal(at3phip_ctx* c, const float* specs, int32_t n_fra
                                uint8_t* frames, uint32_t flags)
 {
     if (!c || !specs || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    if (c->frame_bytes != kFrameBytes)
-        if (const int rc = check_frame_size(c, flags)) return rc;
-    if (const int rc = check_sparse(c, flags)) return rc;
+    AllocMode mode;
+    if (const int rc = resolve_alloc_mode(c, flags, &mode)) return rc;
     // (The records' contract is all that is checked here at every frame size: the smallest admissible sizes,
     // AT3PHIP_MIN_FRAME_BYTES_*, hold the largest tail a record can give beside one unit per channel, so no record needs a tail check.)
     bool any = false;   // records without a block are the writer without records
@@ -516,7 +527,8 @@ int at3phip_write_frames_tonal(at3phip_ctx* c, const float* specs, int32_t n_fra
     const float* d_specs = (flags & AT3HIP_PCM_ON_DEVICE) ? specs : c->d_specs;
     uint8_t* d_frames = (flags & AT3HIP_OUT_ON_DEVICE) ? frames : c->d_frames;
     const Stage stage = {specs, c->d_specs, items * c->cfg.channels * 2048 * sizeof(float), {{frames, c->d_frames, items * (size_t)c->frame_bytes}}, 2, {&at3phip_ctx::write_ms}};
-    return run_stage(c, flags, stage, [&](int) { return launch_write(c, d_specs, n_frames, win_flags, d_frames, nullptr, tonal, nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0, (flags & AT3PHIP_ALLOC_SPARSE) != 0, (flags & AT3PHIP_ALLOC_RD) != 0); });
+    const WriteCall call = {d_specs, n_frames, win_flags, d_frames, c->stream, tonal, nullptr};
+    return run_stage(c, flags, stage, [&](int) { return launch_write(c, mode, call); });
 }
 
 }  // extern "C"
@@ -531,9 +543,8 @@ template <typename T, bool kTones = false>
 int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* frames, uint32_t flags)
 {
     if (!c || !pcm || !frames || n_frames < 1 || n_frames > c->cfg.max_frames) return c ? fail(c, AT3HIP_EINVAL, "bad argument") : AT3HIP_EINVAL;
-    if (c->frame_bytes != kFrameBytes)
-        if (const int rc = check_frame_size(c, flags)) return rc;
-    if (const int rc = check_sparse(c, flags)) return rc;
+    AllocMode mode;
+    if (const int mrc = resolve_alloc_mode(c, flags, &mode)) return mrc;
     at3host::DeviceGuard guard(c->device);
     HIPCHK(c, guard.error());
     if constexpr (kTones) {
@@ -571,8 +582,7 @@ int encode_frames_impl(at3phip_ctx* c, const T* pcm, int32_t n_frames, uint8_t* 
     HIPCHK(c, hipEventRecord(c->ev_specs[par], c->stream));
     HIPCHK(c, hipStreamWaitEvent(ws, c->ev_specs[par], 0));
     if (timed) HIPCHK(c, hipEventRecord(c->ev[4], ws));
-    rc = launch_write(c, d_specs, n_frames, nullptr, d_frames, ws, nullptr, kTones ? c->d_tone_writer[par] : nullptr, (flags & AT3PHIP_ALLOC_ADAPTIVE) != 0,
-                      (flags & AT3PHIP_ALLOC_SPARSE) != 0, (flags & AT3PHIP_ALLOC_RD) != 0);
+    rc = launch_write(c, mode, {d_specs, n_frames, nullptr, d_frames, ws, nullptr, kTones ? c->d_tone_writer[par] : nullptr});
     if (rc != AT3HIP_OK) return rc;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[3], ws));
     if (!(flags & AT3HIP_OUT_ON_DEVICE)) HIPCHK(c, hipMemcpyAsync(frames, c->d_frames, items * (size_t)c->frame_bytes, hipMemcpyDeviceToHost, ws));
@@ -767,8 +777,6 @@ namespace at3p {
 // at3p_sparse.hip includes too).
 constexpr auto k_at3pd_unpack = k_at3pd_unpack_with<false>;
 constexpr auto k_at3pd_unpack_sized = k_at3pd_unpack_with<true>;
-// The unpack kernels of AT3PHIP_DECODE_SPARSE, in at3p_sparse.hip as the sparse writer is; sized: the frame size is not 2048.
-__attribute__((weak, visibility("default"))) void launch_unpack_sparse(const DecUnpackParams& up, bool sized, dim3 grid, hipStream_t on);
 }
 
 static_assert(sizeof(DecTables) == AT3PHIP_DECODER_TABLES_BYTES, "at3phip.h documents the decoder's table block size");
@@ -924,8 +932,21 @@ int at3phip_decoder_get_counters(at3phip_decoder* d, at3phip_decoder_counters* o
 
 namespace {
 
+// The unpack kernel of an at3phip_decode call. The parse is one lane's serial code, so AT3PHIP_DECODE_SPARSE and a frame size other
+// than 2048 select instantiations of their own and are no tests in the kernel; the sparse two are in at3p_sparse.hip as the sparse
+// writer is, and a build without it refuses the flag.
+enum Unpack { kUnpack, kUnpackSized, kUnpackSparse, kUnpackSparseSized };
+int choose_unpack(at3phip_decoder* d, uint32_t flags, Unpack* unpack)
+{
+    const bool sized = d->frame_bytes != 2048;
+    if (!(flags & AT3PHIP_DECODE_SPARSE)) *unpack = sized ? kUnpackSized : kUnpack;
+    else if (launch_unpack_sparse) *unpack = sized ? kUnpackSparseSized : kUnpackSparse;
+    else return fail(d, AT3HIP_EINVAL, "AT3PHIP_DECODE_SPARSE: this build has no sparse unpack kernels (at3p_sparse.hip)");
+    return AT3HIP_OK;
+}
+
 // The kernels of one at3phip_decode call: n_frames frames per stream from d_frames into d_pcm, both device memory.
-int decp_launch(at3phip_decoder* d, const uint8_t* d_frames, int n_frames, void* d_pcm, uint32_t flags)
+int decp_launch(at3phip_decoder* d, const uint8_t* d_frames, int n_frames, void* d_pcm, uint32_t flags, Unpack unpack)
 {
     const size_t S = d->cfg.n_streams, F = (size_t)n_frames, C = d->cfg.channels;
     const int tones = (flags & AT3PHIP_DECODE_TONES) ? 1 : 0;
@@ -943,10 +964,10 @@ int decp_launch(at3phip_decoder* d, const uint8_t* d_frames, int n_frames, void*
     up.tonal = d->d_tonal;
     up.tone_vlc = d->d_tone_tables->vlc;
     up.tones = tones;
-    // (the parse is one lane's serial code: AT3PHIP_DECODE_SPARSE selects instantiations of its own here and is no test in the kernel)
-    if (flags & AT3PHIP_DECODE_SPARSE) launch_unpack_sparse(up, d->frame_bytes != 2048, dim3((unsigned)F, (unsigned)S), st);
-    else if (d->frame_bytes == 2048) hipLaunchKernelGGL(k_at3pd_unpack, dim3((unsigned)F, (unsigned)S), dim3(kDecUnpackThreads), 0, st, up);
-    else hipLaunchKernelGGL(k_at3pd_unpack_sized, dim3((unsigned)F, (unsigned)S), dim3(kDecUnpackThreads), 0, st, up);
+    const dim3 grid((unsigned)F, (unsigned)S);
+    if (unpack == kUnpack) hipLaunchKernelGGL(k_at3pd_unpack, grid, dim3(kDecUnpackThreads), 0, st, up);
+    else if (unpack == kUnpackSized) hipLaunchKernelGGL(k_at3pd_unpack_sized, grid, dim3(kDecUnpackThreads), 0, st, up);
+    else launch_unpack_sparse(up, unpack == kUnpackSparseSized, grid, st);
     HIPCHK(d, hipGetLastError());
     DecSynthParams sp;
     sp.T = d->d_tables;
@@ -974,11 +995,12 @@ extern "C" {
 
 int at3phip_decode(at3phip_decoder* d, const uint8_t* frames, int32_t n_frames, void* pcm, uint32_t flags)
 {
-    if (d && (flags & AT3PHIP_DECODE_SPARSE) && !launch_unpack_sparse)
-        return fail(d, AT3HIP_EINVAL, "AT3PHIP_DECODE_SPARSE: this build has no sparse unpack kernels (at3p_sparse.hip)");
+    Unpack unpack = kUnpack;
+    if (d)
+        if (const int rc = choose_unpack(d, flags, &unpack)) return rc;
     return at3host::decode_call(d, frames, n_frames, pcm, flags, AT3PHIP_DECODE_S16 | AT3PHIP_DECODE_TONES | AT3PHIP_DECODE_SPARSE, AT3PHIP_DECODE_S16,
                                 d ? (size_t)d->frame_bytes : 0, d ? (size_t)2048 * d->cfg.channels : 0,
-                                [&](const uint8_t* d_frames, void* d_pcm) { return decp_launch(d, d_frames, n_frames, d_pcm, flags); });
+                                [&](const uint8_t* d_frames, void* d_pcm) { return decp_launch(d, d_frames, n_frames, d_pcm, flags, unpack); });
 }
 
 // As at3phip_set_frame_bytes: an admissible size waits for queued work, then is stored.

@@ -4,6 +4,7 @@
     first, and the oracle library that some drivers load.
   * Children: the drivers under tools/emu run as child processes - the harness reads EMU_STRICT, EMU_FENCE, EMU_ORDER and EMU_STREAMS
     when its library loads - several at a time, each on one core, so that the GPU-less suite stays short enough to be run.
+  * run_alloc_modes: tests/host/at3p_alloc_modes_main.cpp, the ATRAC3plus engine linked with some of the adaptive writer's units.
 """
 import concurrent.futures
 import os
@@ -63,3 +64,27 @@ def assert_clean(out, min_cases):
     counts = re.findall(r"(?:mismatching frames|bad) (\d+)", out)
     assert len(counts) >= min_cases, out[-4000:]
     assert all(c == "0" for c in counts), "\n".join(ln for ln in out.splitlines() if re.search(r"(?:mismatching frames|bad) [1-9]", ln))[-4000:]
+
+
+ALLOC_MODE_UNITS = {"none": (), "alloc": ("at3p_alloc.hip",), "alloc+sparse": ("at3p_alloc.hip", "at3p_sparse.hip"),
+                    "all": ("at3p_alloc.hip", "at3p_sparse.hip", "at3p_rd.hip")}
+
+
+_alloc_modes = {}
+
+
+def run_alloc_modes(tmp_path, *configs):
+    """tests/host/at3p_alloc_modes_main.cpp in each of `configs`: built with at3phip.hip and the configuration's units, compiled for
+    the host with the harness's runtime, run as a child (once per session and configuration), and every check of it held"""
+    csrc, emu = os.path.join(ROOT, "atracdenc_amd", "csrc"), os.path.join(ROOT, "tools", "emu")
+    for units in configs:
+        if units not in _alloc_modes:
+            exe = str(tmp_path / ("at3p_alloc_modes_" + units))
+            subprocess.check_call([CLANG, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-I", emu, "-include", os.path.join(emu, "at3_pk_emu.hpp"),
+                                   "-x", "c++", os.path.join(csrc, "at3phip.hip"), *(os.path.join(csrc, u) for u in ALLOC_MODE_UNITS[units]),
+                                   os.path.join(csrc, "at3_tables.cpp"), os.path.join(emu, "emu_runtime.cpp"),
+                                   os.path.join(ROOT, "tests", "host", "at3p_alloc_modes_main.cpp"), "-o", exe, "-ldl", "-lpthread"])
+            env = {k: v for k, v in os.environ.items() if not k.startswith("EMU_")}
+            _alloc_modes[units] = subprocess.run([exe, units], capture_output=True, text=True, env=env, timeout=300)
+        r = _alloc_modes[units]
+        assert r.returncode == 0 and f"ALLOCATION MODES OK ({units})" in r.stdout, (units, r.returncode, r.stdout[-2000:], r.stderr[-2000:])

@@ -13,7 +13,7 @@ import at3p_gha_lib as G
 import at3p_tonal_lib as T
 import at3p_tonal_write_lib as TW
 from at3_testlib import at3p_signal, at3p_write_frames
-from simt_harness_lib import CLANG, ROOT, Children, assert_clean, build_strict
+from simt_harness_lib import CLANG, ROOT, Children, assert_clean, build_strict, run_alloc_modes
 
 needs_clang = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's clang++ to compile the kernel sources for the host")
 NF = W.SNR_FRAMES
@@ -200,18 +200,10 @@ def test_host_allocate_symbol_and_flag():
 
 @needs_clang
 def test_a_build_without_the_adaptive_writer_refuses_the_flag(tmp_path):
-    """tests/host/at3p_no_alloc_main.cpp: at3phip.hip linked without at3p_alloc.hip (the weak symbol's other case, which the
-    stand-alone host programs with their own source lists have): all six calls refuse the flag with AT3HIP_EINVAL and write
-    nothing; without the flag the context works"""
-    import subprocess
-    csrc, emu = os.path.join(ROOT, "atracdenc_amd", "csrc"), os.path.join(ROOT, "tools", "emu")
-    exe = str(tmp_path / "at3p_no_alloc_main")
-    subprocess.check_call([CLANG, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-I", emu, "-include", os.path.join(emu, "at3_pk_emu.hpp"), "-x", "c++",
-                           os.path.join(csrc, "at3phip.hip"), os.path.join(csrc, "at3_tables.cpp"), os.path.join(emu, "emu_runtime.cpp"),
-                           os.path.join(ROOT, "tests", "host", "at3p_no_alloc_main.cpp"), "-o", exe, "-ldl", "-lpthread"])
-    env = {k: v for k, v in os.environ.items() if not k.startswith("EMU_")}
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and "NO ADAPTIVE WRITER OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    """tests/host/at3p_alloc_modes_main.cpp, `none`: at3phip.hip linked without at3p_alloc.hip (the weak symbol's other case, which
+    the stand-alone host programs with their own source lists have): all six calls refuse the flag with AT3HIP_EINVAL, write
+    nothing and move no state; without the flag the context works"""
+    run_alloc_modes(tmp_path, "none")
 
 
 # ---- the golden -------------------------------------------------------------------------------------------------------------------

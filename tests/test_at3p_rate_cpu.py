@@ -18,7 +18,7 @@ import at3p_decode_lib as D
 import at3p_gha_lib as G
 import at3p_tonal_lib as T
 import at3p_tonal_write_lib as TW
-from simt_harness_lib import CLANG, ROOT, Children, assert_clean, build_strict
+from simt_harness_lib import CLANG, ROOT, Children, assert_clean, build_strict, run_alloc_modes
 
 needs_clang = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's clang++ to compile the kernel sources for the host")
 NF = W.SNR_FRAMES
@@ -303,16 +303,10 @@ def test_harness_driver_equals_the_restatement():
 
 @needs_clang
 def test_a_build_without_the_adaptive_writer_refuses_every_call_at_another_size(tmp_path):
-    """tests/host/at3p_rate_no_alloc_main.cpp: at3phip.hip linked without at3p_alloc.hip; the setter to 376 succeeds, all six
-    frame-writing calls are refused with and without the flag and write nothing, inadmissible sizes change nothing"""
-    csrc, emu = os.path.join(ROOT, "atracdenc_amd", "csrc"), os.path.join(ROOT, "tools", "emu")
-    exe = str(tmp_path / "at3p_rate_no_alloc_main")
-    subprocess.check_call([CLANG, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-I", emu, "-include", os.path.join(emu, "at3_pk_emu.hpp"), "-x", "c++",
-                           os.path.join(csrc, "at3phip.hip"), os.path.join(csrc, "at3_tables.cpp"), os.path.join(emu, "emu_runtime.cpp"),
-                           os.path.join(ROOT, "tests", "host", "at3p_rate_no_alloc_main.cpp"), "-o", exe, "-ldl", "-lpthread"])
-    env = {k: v for k, v in os.environ.items() if not k.startswith("EMU_")}
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and "FRAME SIZE WITHOUT THE ADAPTIVE WRITER OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    """tests/host/at3p_alloc_modes_main.cpp, `none`: at3phip.hip linked without at3p_alloc.hip; the setter to 376 succeeds, all six
+    frame-writing calls are refused with and without the flag and write nothing, inadmissible sizes change nothing. `alloc`: with
+    at3p_alloc.hip alone the calls at 376 work with AT3PHIP_ALLOC_ADAPTIVE alone and are refused with every other combination"""
+    run_alloc_modes(tmp_path, "none", "alloc")
 
 
 # ---- symbols -------------------------------------------------------------------------------------------------------------------------

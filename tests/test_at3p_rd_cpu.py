@@ -12,6 +12,7 @@ import pytest
 
 import at3p_writer_lib as W
 import at3p_ref_parts_lib as P
+import simt_harness_lib as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "at3phip.h")).read()
@@ -167,6 +168,14 @@ def test_symbols_and_flags():
         with pytest.raises(ValueError):
             B._alloc_flag(*bad)
     assert B._alloc_flag(True, True, True) == 896 and B._alloc_flag(True, True) == 384 and B._alloc_flag(True) == 128 and B._alloc_flag(False) == 0
+
+
+@pytest.mark.skipif(not os.path.exists(H.CLANG), reason="needs ROCm's clang++ to compile the kernel sources for the host")
+def test_a_build_without_the_rate_distortion_writer_refuses_the_flag(tmp_path):
+    """tests/host/at3p_alloc_modes_main.cpp, `alloc+sparse`: at3phip.hip linked with at3p_alloc.hip and at3p_sparse.hip but not
+    at3p_rd.hip; the adaptive and the sparse calls work at both sizes, all six calls refuse ADAPTIVE | SPARSE | RD because the build
+    has no rate-distortion writer, write nothing and move no state"""
+    H.run_alloc_modes(tmp_path, "alloc+sparse")
 
 
 # ---- 4. the frames are sparse frames -------------------------------------------------------------------------------------------------

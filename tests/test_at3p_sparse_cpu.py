@@ -15,7 +15,7 @@ import at3p_writer_lib as W
 import at3p_decode_lib as D
 import at3p_gha_lib as G
 import at3p_tonal_write_lib as TW
-from simt_harness_lib import CLANG, ROOT, Children, assert_clean, build_strict
+from simt_harness_lib import CLANG, ROOT, Children, assert_clean, build_strict, run_alloc_modes
 from test_at3p_rate_cpu import SNR as SECTION_20
 
 needs_clang = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs ROCm's clang++ to compile the kernel sources for the host")
@@ -381,16 +381,10 @@ def test_harness_driver_equals_the_restatement():
 # ---- 10. a build without the adaptive writer ---------------------------------------------------------------------------------------------
 @needs_clang
 def test_a_build_without_the_adaptive_writer_refuses_the_flag(tmp_path):
-    """tests/host/at3p_sparse_no_alloc_main.cpp: at3phip.hip linked without at3p_alloc.hip and at3p_sparse.hip; all six frame-writing
-    calls refuse ADAPTIVE | SPARSE and SPARSE alone and write nothing, at3phip_decode refuses AT3PHIP_DECODE_SPARSE"""
-    csrc, emu = os.path.join(ROOT, "atracdenc_amd", "csrc"), os.path.join(ROOT, "tools", "emu")
-    exe = str(tmp_path / "at3p_sparse_no_alloc_main")
-    subprocess.check_call([CLANG, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-I", emu, "-include", os.path.join(emu, "at3_pk_emu.hpp"), "-x", "c++",
-                           os.path.join(csrc, "at3phip.hip"), os.path.join(csrc, "at3_tables.cpp"), os.path.join(emu, "emu_runtime.cpp"),
-                           os.path.join(ROOT, "tests", "host", "at3p_sparse_no_alloc_main.cpp"), "-o", exe, "-ldl", "-lpthread"])
-    env = {k: v for k, v in os.environ.items() if not k.startswith("EMU_")}
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and "SPARSE WITHOUT THE ADAPTIVE WRITER OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    """tests/host/at3p_alloc_modes_main.cpp, `none`: at3phip.hip linked without at3p_alloc.hip and at3p_sparse.hip; all six
+    frame-writing calls refuse ADAPTIVE | SPARSE and SPARSE alone and write nothing, at3phip_decode refuses AT3PHIP_DECODE_SPARSE.
+    `all`: with every unit each mode's calls are accepted at both sizes, SPARSE without ADAPTIVE is still refused"""
+    run_alloc_modes(tmp_path, "none", "all")
 
 
 def test_symbols_and_flags():
