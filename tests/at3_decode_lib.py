@@ -7,6 +7,7 @@ imports this module).
     TGainProcessor::Demodulate and TQmf::Synthesis (steps 3-6), run by a small driver compiled at generation time against
     oracle/_ref/libat3ref.so and the reference's headers (atrac3denc.h, which includes gain_processor.h and qmf/qmf.h). Nothing of the reference is stored in the repository.
   * crafted_frames / mutate_frames: malformed and extreme inputs.
+  * code_corpus / corpus_expected_spectrum: every mantissa code of the seven selectors at every bit position mod 32 of its unit.
 """
 import ctypes
 import os
@@ -256,16 +257,46 @@ class BitWriter:
             self.pos += 1
 
 
+_VLC = None
+
+
+def vlc_tables():
+    """{selector 1..7: [(code, length)] by symbol} parsed from c_huff, c_huff_off (csrc/at3_common.hpp) and c_huff_size
+    (csrc/at3_decode.hpp): the 130 entries the decoder's look-up is expanded from (selectors 1 and 4 share their nine)"""
+    global _VLC
+    if _VLC is None:
+        import re
+        csrc = os.path.join(HERE, "..", "atracdenc_amd", "csrc")
+        common, dec = open(os.path.join(csrc, "at3_common.hpp")).read(), open(os.path.join(csrc, "at3_decode.hpp")).read()
+        body = common[common.index("c_huff[130] = {"):]
+        flat = [(int(c, 16), int(n)) for c, n in re.findall(r"HE\((0x[0-9A-Fa-f]+), (\d+)\)", body[:body.index("};")])]
+        off = [int(x) for x in re.search(r"c_huff_off\[7\] = \{([^}]*)\}", common).group(1).split(",")]
+        size = [int(x) for x in re.search(r"c_huff_size\[7\] = \{([^}]*)\}", dec).group(1).split(",")]
+        assert len(flat) == 130
+        _VLC = {s: flat[off[s - 1]:off[s - 1] + size[s - 1]] for s in range(1, 8)}
+    return _VLC
+
+
+# what a symbol stands for: a pair of mantissas at selector 1, else symbols 0, 1, 2, 3, 4 .. = mantissas 0, 1, -1, 2, -2 ..
+VLC_PAIRS = [(0, 0), (0, 1), (0, -1), (1, 0), (-1, 0), (1, 1), (1, -1), (-1, 1), (-1, -1)]
+
+
+def vlc_mantissas(selector, sym):
+    return VLC_PAIRS[sym] if selector == 1 else ((sym + 1) >> 1 if sym & 1 else -(sym >> 1),)
+
+
 HUFF = {1: [(0x0, 1), (0x4, 3), (0x5, 3), (0xC, 4), (0xD, 4), (0x1C, 5), (0x1D, 5), (0x1E, 5), (0x1F, 5)],
         2: [(0x0, 1), (0x4, 3), (0x5, 3), (0x6, 3), (0x7, 3)],
         3: [(0x0, 1), (0x4, 3), (0x5, 3), (0xC, 4), (0xD, 4), (0xE, 4), (0xF, 4)]}
 
 
 def make_unit(nbytes, js_second=False, js_params=(0, 7, 3, 3, 3, 3), unit_id=None, gains=((),), tonal=None, nbfu=32,
-              coding_mode=1, wl=None, sf=None, mant=None):
+              coding_mode=1, wl=None, sf=None, mant=None, trace=None):
     """A unit from its fields. gains: per QMF band a list of (level, location); tonal: (mode, [(flags, coded_values, quant,
     [(block, [(sf, rel_pos, [raw mantissa bits])])])]) written with CLC (mode 1) or as raw words; wl / sf per BFU;
-    mant(bfu, i, bits) -> raw CLC word (CLC mode only). Bits past nbytes are dropped."""
+    mant(bfu, i, bits) -> raw CLC word with coding_mode 1 (CLC), the symbol of selector wl[bfu] with coding_mode 0 (VLC: bits is
+    then the position of the code in the unit; a symbol of selector 1 is a pair of lines). trace: a list that receives (selector,
+    symbol, bit position, length) of every VLC code. Bits past nbytes are dropped."""
     w = BitWriter(nbytes)
     if js_second:
         weight, delay, *mats = js_params
@@ -316,7 +347,14 @@ def make_unit(nbytes, js_second=False, js_params=(0, 7, 3, 3, 3, 3), unit_id=Non
         if wl[i]:
             cnt = (start[i + 1] - start[i]) // (2 if wl[i] == 1 else 1)
             for k in range(cnt):
-                w.put(mant(i, k, clc[wl[i]]) if mant else 0, clc[wl[i]])
+                if coding_mode == 0:
+                    sym = mant(i, k, w.pos) if mant else 0
+                    code, n = vlc_tables()[wl[i]][sym]
+                    if trace is not None:
+                        trace.append((wl[i], sym, w.pos, n))
+                    w.put(code, n)
+                else:
+                    w.put(mant(i, k, clc[wl[i]]) if mant else 0, clc[wl[i]])
     return bytes(w.buf)
 
 
@@ -416,6 +454,113 @@ def cpu_ref(frames, fsz, js):
         outs.append(d.decode(frames[s]))
         rej += d.rejected.astype(np.int64)
     return np.stack(outs), rej.tolist()
+
+
+# ---- the exhaustive code corpus ---------------------------------------------------------------------------------------------
+# Every code of the seven selectors at every bit position mod 32 of its unit, in a plain unit and in the byte-reversed second unit of a
+# joint-stereo frame. A unit of (selector s, shift r) has r % 4 gain points in its first band, a prefix BFU 0 of selector 7 whose
+# eight symbols are searched so that BFU 1's first code starts at r mod 32, and behind it BFUs of selector s that carry the
+# selector's symbols in symbol order, again and again to the end of the last BFU. Frame (s, r) holds the units (s, r) and (8 - s, r).
+BFU_START = [0, 8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 144, 160, 176, 192, 224, 256, 288, 320, 352, 384, 416, 448, 480, 512,
+             576, 640, 704, 768, 896, 1024]
+CORPUS_SHIFTS = 32
+_PREFIX_FILLS = None
+
+
+def _prefix_fills():
+    """{bits: eight symbols of selector 7}, one way per total"""
+    global _PREFIX_FILLS
+    if _PREFIX_FILLS is None:
+        by_len = {}
+        for sym, (_, n) in enumerate(vlc_tables()[7]):
+            by_len.setdefault(n, sym)
+        reach = {0: ()}
+        for _ in range(8):
+            reach = {t + n: syms + (sym,) for t, syms in reversed(list(reach.items())) for n, sym in by_len.items()}
+        _PREFIX_FILLS = reach
+        assert len({b % 32 for b in reach}) == 32
+    return _PREFIX_FILLS
+
+
+def corpus_unit(nbytes, selector, r, js_second):
+    """(unit bytes, trace [(selector, symbol, position, length)], mantissas int [1024], wl [32], sf [32])"""
+    table = vlc_tables()[selector]
+    per = 2 if selector == 1 else 1
+    nbfu = next(n for n in range(2, 33) if BFU_START[n] - 8 >= len(table) * per)
+    wl = [7] + [selector] * (nbfu - 1)
+    sf = [(2 * r + 5 * selector + b) % 64 for b in range(nbfu)]
+    prefix = {}
+
+    def mant(bfu, k, pos):
+        if bfu:
+            return ((BFU_START[bfu] - 8) // per + k) % len(table)
+        if not prefix:   # k == 0: pos is where BFU 0 starts
+            need = (r - pos) % 32
+            prefix["syms"] = next(v for b, v in sorted(_prefix_fills().items()) if b % 32 == need)
+        return prefix["syms"][k]
+
+    trace = []
+    gains = [[(4 + i, 3 + 5 * i) for i in range(r % 4)]]
+    unit = make_unit(nbytes, js_second=js_second, gains=gains, nbfu=nbfu, coding_mode=0, wl=wl, sf=sf, mant=mant, trace=trace)
+    assert trace[8][2] % 32 == r and trace[-1][2] + trace[-1][3] <= 8 * nbytes, (selector, r, trace[8], trace[-1])
+    lines = np.zeros(1024, np.int32)
+    k = 0
+    for sel, sym, _, _ in trace:
+        m = vlc_mantissas(sel, sym)
+        lines[k:k + len(m)] = m
+        k += len(m)
+    assert k == BFU_START[nbfu]
+    wl32, sf32 = np.zeros(32, np.int32), np.zeros(32, np.int32)
+    wl32[:nbfu], sf32[:nbfu] = wl, sf
+    return unit, trace, lines, wl32, sf32
+
+
+_CORPUS = {}
+
+
+def code_corpus(js):
+    """The corpus of plain units (js False) or joint-stereo frames (js True), built once per process: a dict of frame_sz (the
+    smallest container row of that kind that holds every frame), frames [32][7][frame_sz] uint8 (stream = shift, frame = selector - 1),
+    mant int32 [32][7][2][1024], wl / sf int32 [32][7][2][32]. Its own assertion: each of the 130 + 9 (selector, symbol) codes at every
+    bit position mod 32, in unit 0 and in unit 1."""
+    if js in _CORPUS:
+        return _CORPUS[js]
+    for _, fsz, row_js in ROWS:
+        if row_js != js:
+            continue
+        nb = fsz if js else fsz // 2
+        frames = np.zeros((CORPUS_SHIFTS, 7, fsz), np.uint8)
+        mant, wl, sf = (np.zeros((CORPUS_SHIFTS, 7, 2) + tail, np.int32) for tail in ((1024,), (32,), (32,)))
+        seen = set()
+        try:
+            for r in range(CORPUS_SHIFTS):
+                for s in range(1, 8):
+                    units, bits = [], 0
+                    for u, sel in enumerate((s, 8 - s)):
+                        unit, trace, mant[r, s - 1, u], wl[r, s - 1, u], sf[r, s - 1, u] = corpus_unit(nb, sel, r, js and u == 1)
+                        units.append(unit)
+                        bits += trace[-1][2] + trace[-1][3]
+                        seen.update((u, sel, sym, pos % 32) for sel, sym, pos, _ in trace)
+                    assert bits <= 8 * fsz
+                    frames[r, s - 1] = frame_of(units, fsz, js)
+        except AssertionError:
+            continue   # the row is too small
+        every = {(u, s, sym, ph) for u in range(2) for s in range(1, 8) for sym in range(len(vlc_tables()[s])) for ph in range(32)}
+        assert seen == every and len(every) == 2 * 139 * 32
+        _CORPUS[js] = dict(frame_sz=fsz, frames=frames, mant=mant, wl=wl, sf=sf)
+        return _CORPUS[js]
+    raise AssertionError(js)
+
+
+def corpus_expected_spectrum(corpus):
+    """(float32(m) * ScaleTable[sf]) * InvMaxQuant[wl], two roundings left to right, with ScaleTable[i] = 2^(i / 3 - 21) and
+    InvMaxQuant[wl] = 1 / (1.5, 2.5, 3.5, 4.5, 7.5, 15.5, 31.5)[wl - 1] rounded once to float: [32][7][2][1024] float32"""
+    scale = np.array([2.0 ** (i / 3.0 - 21.0) for i in range(64)]).astype(np.float32)
+    inv = np.array([0.0] + [1.0 / q for q in (1.5, 2.5, 3.5, 4.5, 7.5, 15.5, 31.5)]).astype(np.float32)
+    bfu_of_line = np.repeat(np.arange(32), np.diff(BFU_START))
+    wl_line, sf_line = corpus["wl"][..., bfu_of_line], corpus["sf"][..., bfu_of_line]
+    q = (corpus["mant"].astype(np.float32) * scale[sf_line]).astype(np.float32)
+    return (q * inv[wl_line]).astype(np.float32)
 
 
 # ---- files -----------------------------------------------------------------------------------------------------------------

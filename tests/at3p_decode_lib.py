@@ -8,8 +8,11 @@ imports this module).
     between and after them. TAt3pMIDCT::Do is run by a small driver compiled at generation time against the reference's headers
     and oracle/_ref/libat3ref.so. Nothing of the reference is stored in the repository.
   * FrameWriter / crafted_frames / mutate_frames: frames from their fields, malformed and extreme inputs.
+  * code_corpus / corpus_expected_spectrum: every code of the 56 spectrum tables at every bit position mod 32, with the spectrum
+    its frames stand for; hits: the restatement's per-code counter; steered_spectra: spectra that bring the fixed writer to each table.
 """
 import ctypes
+import functools
 import os
 import subprocess
 import tempfile
@@ -113,6 +116,16 @@ def unpack(frames, channels, lib=None):
     for f in range(n):
         lib.at3pd_unpack_frame(_vp(frames[f]), channels, _vp(specs[f]), _vp(win[f]), _vp(fl[f:f + 1]))
     return specs, win, fl
+
+
+def hits(lib=None, reset=True):
+    """the restatement's test-only counter: how often each spectrum code was decoded since the last reset, uint32 [56][256] by
+    (table, symbol); `lib` is cpu_lib() or at3p_writer_lib.writer_lib() (each library counts for itself)"""
+    lib = lib or cpu_lib()
+    out = np.zeros((56, 256), np.uint32)
+    lib.at3pd_hits.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.at3pd_hits(_vp(out), int(reset))
+    return out
 
 
 def host_tables(lib=None):
@@ -248,22 +261,34 @@ def vlc_tables():
 
 
 class BitWriter:
+    """MSB-first bits into a buffer of nbytes bytes; bits past its end are dropped. put() appends to one integer (word-wise, not bit
+    by bit: the code corpus writes some ten million bits); `buf` is the buffer so far."""
+
     def __init__(self, nbytes=FRAME):
-        self.buf = bytearray(nbytes)
+        self.nbytes = nbytes
+        self.acc = 0
         self.pos = 0
 
     def put(self, v, n):
-        for k in range(n - 1, -1, -1):
-            if self.pos < len(self.buf) * 8 and (v >> k) & 1:
-                self.buf[self.pos >> 3] |= 0x80 >> (self.pos & 7)
-            self.pos += 1
+        self.acc = (self.acc << n) | (v & ((1 << n) - 1))
+        self.pos += n
+
+    @property
+    def buf(self):
+        total = self.nbytes * 8
+        a = self.acc << (total - self.pos) if self.pos <= total else self.acc >> (self.pos - total)
+        return bytearray(a.to_bytes(self.nbytes, "big"))
 
 
 def make_frame(channels, nqu=4, wl=None, sf=None, tab=None, mant=None, full_table=1, win=(0, 0), first_bit=0, block_type=None,
                mute=0, wl_modes=None, sf_mode=0, ct_fields=(0, 0, 0), zero_groups=False, powlev=15, swap_negate=0, gain=0,
-               tonal=0, noise=0, term=3, win_bits=None, truncate=None):
+               tonal=0, noise=0, term=3, win_bits=None, truncate=None, unit_mant=None, wl_idx=None, trace=None, nbytes=FRAME):
     """One frame from its fields (include/at3phip.h, step 1). wl / sf / tab: [channels][nqu]; mant(ch, qu, k) -> the integer
     mantissa of line k of the unit (must fit the unit's table); zero_groups: code every group with a group flag as all zero.
+    unit_mant(ch, qu, bitpos) -> the unit's mantissas as a list, given the bit position of the unit's first code (instead of mant).
+    wl_idx: per channel the AT3P_WL_VLC table that codes the word-length deltas (None: the first that can). trace: a dict that
+    receives "codes": [(ch, qu, table, symbol, bit position, length)] of every spectrum code, "wl": [(table, symbol)] of every
+    word-length delta, "mant": {(ch, qu): mantissas} and "bits": the frame's length. nbytes: the frame's size.
     win: per channel a flag word (0 -> '0', 0xffff -> '1 0', else '1 1' + 16 bits) unless win_bits gives the raw bits.
     truncate: drop every bit from this position on (a frame that ends early). The remaining arguments override what the writer
     emits, for the rejection cases."""
@@ -271,7 +296,9 @@ def make_frame(channels, nqu=4, wl=None, sf=None, tab=None, mant=None, full_tabl
     wl = wl if wl is not None else [[4] * nqu for _ in range(channels)]
     sf = sf if sf is not None else [[40] * nqu for _ in range(channels)]
     tab = tab if tab is not None else [[0] * nqu for _ in range(channels)]
-    w = BitWriter()
+    w = BitWriter(nbytes)
+    if trace is not None:
+        trace.update(codes=[], wl=[], mant={})
     w.put(first_bit, 1)
     w.put(channels - 1 if block_type is None else block_type, 2)
     w.put(nqu - 1, 5)
@@ -279,21 +306,25 @@ def make_frame(channels, nqu=4, wl=None, sf=None, tab=None, mant=None, full_tabl
     modes = wl_modes or ((3, 0, 0), (1, 0))
     # channel 0: deltas to the previous unit, with the table that codes them all
     d0 = [(wl[0][i] - wl[0][i - 1]) & 7 for i in range(1, nqu)]
-    idx0 = next(i for i in range(4) if all(d in wl_t[i] for d in d0))
+    idx0 = wl_idx[0] if wl_idx is not None else next(i for i in range(4) if all(d in wl_t[i] for d in d0))
     for m in modes[0]:
         w.put(m, 2)
     w.put(idx0, 2)
     w.put(wl[0][0], 3)
     for d in d0:
         w.put(*wl_t[idx0][d])
+        if trace is not None:
+            trace["wl"].append((idx0, d))
     if channels == 2:
         d1 = [(wl[1][i] - wl[0][i]) & 7 for i in range(nqu)]
-        idx1 = next(i for i in range(4) if all(d in wl_t[i] for d in d1))
+        idx1 = wl_idx[1] if wl_idx is not None else next(i for i in range(4) if all(d in wl_t[i] for d in d1))
         for m in modes[1]:
             w.put(m, 2)
         w.put(idx1, 2)
         for d in d1:
             w.put(*wl_t[idx1][d])
+            if trace is not None:
+                trace["wl"].append((idx1, d))
     for ch in range(channels):
         w.put(sf_mode, 2)
         for i in range(nqu):
@@ -312,7 +343,10 @@ def make_frame(channels, nqu=4, wl=None, sf=None, tab=None, mant=None, full_tabl
             t = wl[ch][qu] - 1 + 7 * tab[ch][qu]
             gs, nc, cb, signed = info[t]
             n = QU_START[qu + 1] - QU_START[qu]
-            vals = [mant(ch, qu, k) if mant else 0 for k in range(n)]
+            vals = unit_mant(ch, qu, w.pos) if unit_mant else [mant(ch, qu, k) if mant else 0 for k in range(n)]
+            assert len(vals) == n
+            if trace is not None:
+                trace["mant"][ch, qu] = vals
             pos = 0
             while pos < n:
                 if gs != 1:
@@ -335,6 +369,8 @@ def make_frame(channels, nqu=4, wl=None, sf=None, tab=None, mant=None, full_tabl
                             sym |= abs(m) << (cb * i)
                             if m:
                                 signs.append(1 if m < 0 else 0)
+                    if trace is not None:
+                        trace["codes"].append((ch, qu, t, sym, w.pos, spec_t[t][sym][1]))
                     w.put(*spec_t[t][sym])
                     for s in signs:
                         w.put(s, 1)
@@ -359,9 +395,11 @@ def make_frame(channels, nqu=4, wl=None, sf=None, tab=None, mant=None, full_tabl
     w.put(tonal, 1)
     w.put(noise, 1)
     w.put(term, 2)
+    if trace is not None:
+        trace["bits"] = w.pos
     buf = bytearray(w.buf)
     if truncate is not None:
-        for p in range(truncate, FRAME * 8):
+        for p in range(truncate, nbytes * 8):
             buf[p >> 3] &= ~(0x80 >> (p & 7)) & 0xff
     return np.frombuffer(bytes(buf), np.uint8)
 
@@ -460,6 +498,310 @@ def fuzz_streams(g, names, nch, seed=None, n_streams=4, n_plain=12, n_head=12, n
         streams.append(np.concatenate([mutate_frames(pick[:n_plain], rng, n_flips=1 + k % 4), mutate_frames(pick[n_plain:], rng, 2, span=600),
                                        crafted[rng.integers(0, crafted.shape[0], n_crafted)]]))
     return np.stack(streams)
+
+
+# ---- the exhaustive code corpus ---------------------------------------------------------------------------------------------
+# Every code of the 56 spectrum tables at every bit position mod 32 (what at3::MsbReader's refill and the decoder's two-level look-up
+# depend on), written by make_frame straight from the table file. One frame per (table t, shift r): unit 0 is a prefix whose symbols
+# are searched so that unit 1's first code starts at a bit position = r mod 32; the units behind it, of word length t % 7 + 1 and
+# table index t // 7, carry the table's symbols in symbol order, again and again to the end of the last unit. Stereo frames carry
+# table t in channel 0 and table 55 - t in channel 1, each behind a prefix of its own. The 32 shifts are 32 streams of the same
+# frame order: the 56 tables, one frame per table with a group flag in which every second group is all zero, and one frame that
+# ends on the last bit of the corpus' frame size (code_corpus: "bytes").
+CORPUS_SHIFTS = 32
+STANDARD_BYTES = (192, 280, 376, 560, 744, 936, 1120, 1488, 1864, 2048)   # the command line's frame sizes (kAt3pRates)
+
+
+def table_codes():
+    """[(table, symbol, code, length)] of the 56 spectrum tables, in table and symbol order: the 4915 codes"""
+    spec_t = vlc_tables()[0]
+    return [(t, s, *spec_t[t][s]) for t in range(56) for s in sorted(spec_t[t])]
+
+
+def symbol_mantissas(t, sym, flip=0):
+    """the mantissas a symbol of table t stands for; bit i of `flip` makes coefficient i of a table with sign bits negative"""
+    return _symbol_mantissas(t, sym, flip & 15)
+
+
+@functools.lru_cache(maxsize=None)
+def _symbol_mantissas(t, sym, flip):
+    _, nc, cb, signed = vlc_tables()[2][t]
+    out = []
+    for i in range(nc):
+        m = (sym >> (cb * i)) & ((1 << cb) - 1)
+        if signed:
+            m -= (m >> (cb - 1)) << cb
+        elif (flip >> i) & 1:
+            m = -m
+        out.append(m)
+    return tuple(out)
+
+
+def _code_bits(t, sym):
+    """a code's bits in the frame: its length and, in a table with sign bits, one bit per non-zero coefficient"""
+    spec_t, _, info = vlc_tables()
+    _, nc, cb, signed = info[t]
+    return spec_t[t][sym][1] + (0 if signed else sum(1 for m in symbol_mantissas(t, sym) if m))
+
+
+_FILLS = {}
+
+
+def _unit_fills(t, n_lines):
+    """{bits: symbols} of every way found to fill n_lines lines with codes of table t (no group flags), one per total"""
+    if (t, n_lines) not in _FILLS:
+        gs, nc, _, _ = vlc_tables()[2][t]
+        assert gs == 1
+        by_cost = {}
+        for s in sorted(vlc_tables()[0][t]):
+            by_cost.setdefault(_code_bits(t, s), s)
+        reach = {0: ()}
+        for _ in range(n_lines // nc):
+            nxt = {}
+            for total, syms in reach.items():
+                for c, s in by_cost.items():
+                    nxt.setdefault(total + c, syms + (s,))
+            reach = nxt
+        _FILLS[t, n_lines] = reach
+    return _FILLS[t, n_lines]
+
+
+def _prefix_table(wl):
+    """the first table of word length wl without group flags whose 16-line units reach every bit count mod 32"""
+    for tab in range(8):
+        t = wl - 1 + 7 * tab
+        if vlc_tables()[2][t][0] == 1 and len({b % 32 for b in _unit_fills(t, 16)}) == 32:
+            return tab
+    raise AssertionError(wl)
+
+
+def _mantissas_of(t, syms, flip0=0):
+    return [m for k, s in enumerate(syms) for m in symbol_mantissas(t, s, (flip0 + k) * 0x9e37 >> 4)]
+
+
+def corpus_frame(tables, r, zero_groups=False, fill=None, end_bits=None):
+    """One corpus frame of len(tables) channels: (frame [2048], trace). fill(ch, code index) -> symbol overrides the symbol order;
+    end_bits: the last channel's last unit is searched so that the frame is exactly end_bits long (the channel's table has no
+    group flags)."""
+    spec_t, wl_t, info = vlc_tables()
+    C = len(tables)
+    syms = [sorted(spec_t[t]) for t in tables]
+    lines = max(len(syms[ch]) * info[tables[ch]][1] for ch in range(C))
+    nqu = max(3, next(n for n in range(2, 33) if QU_START[n] - 16 >= lines)) if fill is None else fill.nqu
+    body_wl = [t % 7 + 1 for t in tables]
+    pre_wl = [1 + (r + 3 * ch + tables[0] // 7) % 7 for ch in range(C)]
+    wl = [[pre_wl[ch]] + [body_wl[ch]] * (nqu - 1) for ch in range(C)]
+    tab = [[_prefix_table(pre_wl[ch])] + [tables[ch] // 7] * (nqu - 1) for ch in range(C)]
+    sf = [[(2 * r + 8 * (tables[ch] // 7) + qu - 1 + 32 * ch) % 64 for qu in range(nqu)] for ch in range(C)]
+    deltas = [[(wl[0][i] - wl[0][i - 1]) & 7 for i in range(1, nqu)]] + [[(wl[ch][i] - wl[0][i]) & 7 for i in range(nqu)] for ch in range(1, C)]
+    wl_idx = []
+    for ch in range(C):
+        fits = [i for i in range(4) if all(d in wl_t[i] for d in deltas[ch])]
+        wl_idx.append(fits[(r // 7 + tables[0]) % len(fits)])
+    tail_bits = 4 * SB_POWGRPS[QU_TO_SB[nqu - 1]] + (2 if C == 2 else 0) + 2 * C + 4
+
+    def unit_mant(ch, qu, pos):
+        t = tables[ch]
+        gs, nc, _, _ = info[t]
+        n = QU_START[qu + 1] - QU_START[qu]
+        if qu == 0:   # the prefix: unit 1's first code (behind its group flag, if it has one) starts at r mod 32
+            pt = pre_wl[ch] - 1 + 7 * tab[ch][0]
+            fills = _unit_fills(pt, 16)
+            need = (r - (gs != 1) - pos) % 32
+            return _mantissas_of(pt, next(v for b, v in sorted(fills.items()) if b % 32 == need), r)
+        if end_bits is not None and ch == C - 1 and qu == nqu - 1:
+            return _mantissas_of(t, _unit_fills(t, n)[end_bits - tail_bits - pos], r)
+        first = (QU_START[qu] - 16) // nc
+        out, zeros = [], [0] * nc
+        for ci in range(first, first + n // nc):
+            if fill is not None:
+                s = fill(ch, ci)
+            elif zero_groups:
+                g = ci // gs
+                s = None if g & 1 else syms[ch][((g // 2) * gs + ci % gs) % len(syms[ch])]
+            else:
+                s = syms[ch][ci % len(syms[ch])]
+            out += zeros if s is None else _symbol_mantissas(t, s, ((ci + r) * 0x9e37 >> 4) & 15)
+        return out
+
+    trace = {}
+    frame = make_frame(C, nqu=nqu, wl=wl, sf=sf, tab=tab, unit_mant=unit_mant, zero_groups=zero_groups, wl_idx=wl_idx, trace=trace)
+    trace.update(nqu=nqu, wl_units=wl, sf_units=sf, tables=tuple(tables))
+    for ch in range(C):
+        first = next(c for c in trace["codes"] if c[0] == ch and c[1] == 1)
+        assert first[4] % 32 == r, (tables, r, first)
+    assert trace["bits"] <= 8 * FRAME
+    return frame, trace
+
+
+class _Fill:
+    """the symbol order of the frame that ends on its limit: the table's symbols in order up to unit `cut`, its shortest code behind"""
+
+    def __init__(self, tables, nqu, cut):
+        spec_t, _, info = vlc_tables()
+        self.nqu, self.cut = nqu, cut
+        self.syms = [sorted(spec_t[t]) for t in tables]
+        self.short = [min(sy, key=lambda s, t=t: (_code_bits(t, s), s)) for sy, t in zip(self.syms, tables)]
+        self.nc = [info[t][1] for t in tables]
+
+    def __call__(self, ch, ci):
+        return self.syms[ch][ci % len(self.syms[ch])] if ci * self.nc[ch] < QU_START[self.cut] - 16 else self.short[ch]
+
+
+def limit_frame(channels, r, nbytes):
+    """A frame of table 6 (word length 7, table index 0: one line per code, 2 to 10 bits) whose terminator ends on the last bit of
+    nbytes bytes. At the unit count such a frame needs, 20 bits of power groups and the tail lie between the last code and the
+    limit, so it is the reader's look-ahead of a word, not a code's 12-bit look-up, that reaches past the limit."""
+    tables = [6] * channels
+    order = [(nqu, cut) for nqu in range(3, 33) for cut in range(nqu, 0, -1)]
+    last = _LIMIT_FOUND.get((channels, nbytes))
+    for nqu, cut in ([last] if last else []) + order:
+        try:
+            out = corpus_frame(tables, r, fill=_Fill(tables, nqu, cut), end_bits=8 * nbytes)
+        except KeyError:   # no filling of the last unit has the bits that are left
+            continue
+        _LIMIT_FOUND[channels, nbytes] = (nqu, cut)
+        return out
+    raise AssertionError((channels, r, nbytes))
+
+
+_CORPUS = {}
+_LIMIT_FOUND = {}
+
+
+def code_corpus(channels):
+    """The corpus of `channels` channels, built once per process: a dict of
+         frames [32][F][2048] uint8 (stream = shift), what [F] (labels), bytes (the smallest standard frame size that
+         holds every frame; each frame is valid at that size and at 2048), mant int16 [32][F][C][2048] (the intended mantissas),
+         wl / sf uint8 [32][F][C][32] (per unit; word length 0 past the frame's units), hits {(table, symbol): count}.
+       Its own assertions: every one of the 4915 codes at every bit position mod 32, every code of 9..12 bits at every split over a
+       word boundary, every (word length, scale factor) pair, and (stereo) every symbol of the four word-length tables."""
+    if channels in _CORPUS:
+        return _CORPUS[channels]
+    info = vlc_tables()[2]
+    codes = table_codes()
+    index = {(t, s): i for i, (t, s, _, _) in enumerate(codes)}
+    group_tables = [t for t in range(56) if info[t][0] != 1]
+    jobs = [(f"table{t}", t, False) for t in range(56)] + [(f"groups{t}", t, True) for t in group_tables]
+    what = [j[0] for j in jobs] + ["limit"]
+    F = len(what)
+    frames = np.zeros((CORPUS_SHIFTS, F, FRAME), np.uint8)
+    mant = np.zeros((CORPUS_SHIFTS, F, channels, FRAME), np.int16)
+    wl = np.zeros((CORPUS_SHIFTS, F, channels, 32), np.uint8)
+    sf = np.zeros((CORPUS_SHIFTS, F, channels, 32), np.uint8)
+    seen = np.zeros((len(codes), 32), bool)
+    wl_seen, pairs, max_bits = set(), set(), 0
+
+    def keep(r, f, frame, tr):
+        frames[r, f] = frame
+        for (ch, qu), v in tr["mant"].items():
+            mant[r, f, ch, QU_START[qu]:QU_START[qu + 1]] = v
+        wl[r, f, :, :tr["nqu"]] = tr["wl_units"]
+        sf[r, f, :, :tr["nqu"]] = tr["sf_units"]
+
+    for r in range(CORPUS_SHIFTS):
+        for f, (_, t, zg) in enumerate(jobs):
+            tables = [t, 55 - t][:channels]
+            frame, tr = corpus_frame(tables, r, zero_groups=zg)
+            keep(r, f, frame, tr)
+            max_bits = max(max_bits, tr["bits"])
+            if not zg:
+                for ch, qu, tt, sym, pos, _ in tr["codes"]:
+                    seen[index[tt, sym], pos % 32] = True
+                wl_seen.update(tr["wl"])
+                pairs.update((tr["wl_units"][ch][qu], tr["sf_units"][ch][qu]) for ch in range(channels) for qu in range(1, tr["nqu"]))
+    size = next(b for b in STANDARD_BYTES if 8 * b >= max_bits)
+    for r in range(CORPUS_SHIFTS):
+        frame, tr = limit_frame(channels, r, size)
+        assert tr["bits"] == 8 * size and not frame[size:].any() and frame[size - 1] & 3 == 3
+        keep(r, F - 1, frame, tr)
+    # the generator's self-check
+    assert seen.all(), [codes[i][:2] for i in np.argwhere(~seen.all(axis=1))[:, 0]]
+    for i, (_, _, _, length) in enumerate(codes):
+        if length >= 9:   # `split` bits in one word, the rest in the next
+            assert all(seen[i, 32 - split] for split in range(1, length))
+    assert pairs == {(w, s) for w in range(1, 8) for s in range(64)}, sorted({(w, s) for w in range(1, 8) for s in range(64)} - pairs)
+    if channels == 2:
+        every = {(i, s) for i in range(4) for s in vlc_tables()[1][i]}
+        assert wl_seen == every, sorted(every - wl_seen)
+    _CORPUS[channels] = dict(frames=frames, what=what, bytes=size, mant=mant, wl=wl, sf=sf, max_bits=max_bits, n_codes=len(codes))
+    return _CORPUS[channels]
+
+
+def corpus_expected_spectrum(corpus):
+    """(float32(m) * AT3P_MANT[wl]) * AT3P_SCALE[sf] of the intended mantissas, two roundings left to right: [32][F][C][2048] float32"""
+    from at3p_ref_parts_lib import float_table
+    mant_t, scale_t = float_table("AT3P_MANT"), float_table("AT3P_SCALE")
+    unit_of_line = np.repeat(np.arange(32), np.diff(QU_START))
+    wl_line = corpus["wl"][..., unit_of_line]
+    sf_line = corpus["sf"][..., unit_of_line]
+    q = (corpus["mant"].astype(np.float32) * mant_t[wl_line]).astype(np.float32)
+    return np.where(wl_line > 0, (q * scale_t[sf_line]).astype(np.float32), np.float32(0.0))
+
+
+# ---- spectra that steer the fixed writer through the tables --------------------------------------------------------------------
+# The fixed writer (at3p_write.hpp: at3p_wordlen) gives unit qu the word length 7, 6, 5, 4, 3, 2, 1 from its index alone and codes it
+# with the first of the eight tables that takes the fewest bits. A unit whose codes are drawn with p = 2^-length from table t's own
+# symbols is coded most cheaply by t in expectation, so such units bring the writer to tables (and codes) the test signals never
+# reach. What no spectrum can make it write are mantissas beyond lrintf(0.99999f * AT3P_INV_MANT[wl]) = 1, 2, 3, 5, 7, 14, 28 (the
+# scaler clips a scaled value at 0.99999): symbols with a larger one (up to 15 at word length 6, 32 at 7) are left out of the draw.
+# A mantissa m is the line float32(v * AT3P_SCALE[STEER_SF]) with v = m * AT3P_MANT[wl], the exact grid point, or 0.995 where that
+# is 1 or more (it still rounds to m); each coded unit holds one line at the largest mantissa, so its scale factor index is
+# STEER_SF (STEER_SF - 1 at word length 1, whose largest grid point 0.748 lies under the next scale factor) whatever else was drawn.
+STEER_SEED = 20261021
+STEER_SF = 40
+STEER_STREAMS, STEER_FRAMES = 8, 32
+FIXED_WL = [7] * 17 + [6] * 9 + [5, 5, 4, 3, 2, 1]
+STEER_TOP = (0, 1, 2, 3, 5, 7, 14, 28)
+
+
+def steered_spectra(channels):
+    """(specs float32 [8][32][C][2048], mant int16 of the same shape, target int8 [8][32][C][32]: the table index each unit aims at,
+    -1 for a unit left at zero). In stereo frames every second unit below unit 26 stays zero, alternating between the channels and
+    from frame to frame, so that all 32 units fit the frame."""
+    from at3p_ref_parts_lib import float_table
+    spec_t, _, info = vlc_tables()
+    mant_t, scale = float_table("AT3P_MANT"), float_table("AT3P_SCALE")[STEER_SF]
+    rng = np.random.Generator(np.random.PCG64(STEER_SEED + channels))
+    shape = (STEER_STREAMS, STEER_FRAMES, channels)
+    mant, target = np.zeros(shape + (FRAME,), np.int16), np.full(shape + (32,), -1, np.int8)
+    draw = {}
+    for t in range(56):
+        top = STEER_TOP[t % 7 + 1]
+        syms = [sy for sy in sorted(spec_t[t]) if max(map(abs, _symbol_mantissas(t, sy, 0))) <= top]
+        cum = np.cumsum([2.0 ** -spec_t[t][sy][1] for sy in syms])
+        first = min((sy for sy in syms if top in map(abs, _symbol_mantissas(t, sy, 0))), key=lambda sy: (spec_t[t][sy][1], sy))
+        draw[t] = (syms, cum / cum[-1], first)
+    for st in range(STEER_STREAMS):
+        for f in range(STEER_FRAMES):
+            for ch in range(channels):
+                for qu in range(32):
+                    if channels == 2 and qu < 26 and (qu + ch + f) % 2:
+                        continue
+                    tab = (f + qu + 3 * ch + 5 * st) % 8
+                    t = FIXED_WL[qu] - 1 + 7 * tab
+                    _, nc, _, signed = info[t]
+                    syms, cum, first = draw[t]
+                    n = (QU_START[qu + 1] - QU_START[qu]) // nc
+                    drawn = [syms[min(k, len(syms) - 1)] for k in np.searchsorted(cum, rng.random(n), side="right")]
+                    flips = rng.integers(0, 16, n)
+                    drawn[0] = first
+                    mant[st, f, ch, QU_START[qu]:QU_START[qu + 1]] = [m for sy, fl in zip(drawn, flips)
+                                                                      for m in _symbol_mantissas(t, sy, 0 if signed else int(fl))]
+                    target[st, f, ch, qu] = tab
+    wl_line = np.repeat(np.array(FIXED_WL), np.diff(QU_START))
+    v = (mant.astype(np.float32) * mant_t[wl_line]).astype(np.float32)
+    v = np.where(np.abs(v) >= 1, np.copysign(np.float32(0.995), v), v).astype(np.float32)
+    return (v * scale).astype(np.float32), mant, target
+
+
+def steered_expectation(mant, sfi):
+    """the spectrum a decoder gives for the written frames: mant [n][C][2048], sfi [n][C][32] as the writer chose them"""
+    from at3p_ref_parts_lib import float_table
+    wl_line = np.repeat(np.array(FIXED_WL), np.diff(QU_START))
+    unit = np.repeat(np.arange(32), np.diff(QU_START))
+    q = (mant.astype(np.float32) * float_table("AT3P_MANT")[wl_line]).astype(np.float32)
+    return (q * float_table("AT3P_SCALE")[sfi[:, :, unit]]).astype(np.float32)
 
 
 # ---- files -----------------------------------------------------------------------------------------------------------------

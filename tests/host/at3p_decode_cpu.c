@@ -175,6 +175,9 @@ static int vlc(bits* b, const uint16_t* table, int n_sym, int* invalid)
     *invalid = 1;
     return 0;
 }
+/* test-only: how often each spectrum code (table, symbol) was decoded since the last reset (at3pd_hits) */
+static uint32_t g_hits[56][256];
+
 /* the same for a spectrum code, through the table's 12-bit look-up */
 static int spec_vlc(bits* b, int table, int* invalid)
 {
@@ -186,6 +189,7 @@ static int spec_vlc(bits* b, int table, int* invalid)
     if (!len) { *invalid = 1; return 0; }
     if (b->pos + len > b->limit) { b->bad = 1; return 0; }
     b->pos += len;
+    g_hits[table][e & 0xff]++;
     return e & 0xff;
 }
 
@@ -675,6 +679,14 @@ int at3pd_unpack_frame(const uint8_t* frame, int channels, float* specs, uint16_
 void at3pd_decode(void* state, int channels, const uint8_t* frames, int n_frames, float* pcm, uint64_t* rejected, void* fields)
 {
     decode_frames((at3pd_stream*)state, NULL, channels, frames, 2048, n_frames, pcm, rejected, (at3pd_fields*)fields, 0, 0);
+}
+
+/* test-only: the spectrum codes decoded so far by every entry point that parses frames, counts [56][256] by (table, symbol) (NULL:
+ * none copied); reset != 0 zeroes the counters afterwards */
+void at3pd_hits(uint32_t* counts, int reset)
+{
+    if (counts) memcpy(counts, g_hits, sizeof(g_hits));
+    if (reset) memset(g_hits, 0, sizeof(g_hits));
 }
 
 /* the host-built tables the decoder needs, for the tests: cos16 [16][16] ([k][n]), sine128, sine64 */

@@ -30,6 +30,7 @@ RESAMPLE = ["resample_pairs:0", "resample_pairs:1", "resample_edges"]
 SINGLE = ["at1_single", "at3_single", "at3p_single"]
 FUZZ_AT3 = ["at3_fuzz:0", "at3_fuzz:1"]
 FUZZ_AT3P = ["at3p_fuzz:1", "at3p_fuzz:2"]
+CODEBOOK = ["at3p_codebook:1", "at3p_codebook:2", "at3_codebook"]
 
 LARGE = ["at1_fuzz_large:2", "at1_fuzz_large:1", "at3p_fuzz_large:2", "at3p_fuzz_large:1", "at3_fuzz_large:0", "at3_fuzz_large:1"]
 FUZZ = ["at1_fuzz:2", "at1_fuzz:1"] + FUZZ_AT3 + FUZZ_AT3P
@@ -39,7 +40,8 @@ JOBS = ([(m, "at1_fuzz:2") for m in ("default", "reverse")] + [("default", c) fo
         [(m, c) for c in FUZZ[1:] + GOLDENS + RESAMPLE for m in ("default", "reverse")] +
         [(m, c) for c in GOLDENS + RESAMPLE + SINGLE for m in ("high", "low")] +
         [("default", c) for c in ("at3_state", "at3p_state", "at1_s16", "at3_s16", "at3p_s16")] +
-        [(m, "resample_domain") for m in ("high", "low", "reverse")])
+        [(m, "resample_domain") for m in ("high", "low", "reverse")] +
+        [(m, c) for c in CODEBOOK for m in ("high", "low", "reverse")])
 assert len(set(JOBS)) == len(JOBS)
 
 
@@ -147,3 +149,20 @@ def test_reversed_wavefront_order(children, case):
     n = N_GOLDEN.get(case) or {"resample_edges": 6, "at1_fuzz:1": 2, "at1_fuzz:2": 2, "at3_fuzz:0": 8, "at3_fuzz:1": 8, "at3p_fuzz:1": 6,
                                "at3p_fuzz:2": 6}.get(case, 22)
     check(children, "reverse", case, n)
+
+
+# ---- 8. every code at every bit phase -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["high", "low", "reverse"])
+@pytest.mark.parametrize("case,n", [("at3p_codebook:1", 8), ("at3p_codebook:2", 8), ("at3_codebook", 4)])
+def test_codebook_corpus(children, mode, case, n):
+    """A slice of the exhaustive code corpora (tests/at3p_decode_lib.code_corpus, tests/at3_decode_lib.code_corpus): every table or
+    selector at shifts 0, 7 and 31, with guard pages on either side of every buffer and in both wavefront orders (the guard-page
+    runs are in the default order). ATRAC3plus: mono and stereo through the four instantiations of k_at3pd_unpack (plain / sparse
+    parse x 2048 bytes / the corpus' frame size), each named in the output; ATRAC3: plain units and joint-stereo frames."""
+    out = check(children, mode, case, n)
+    if case.startswith("at3p"):
+        nch = case[-1]
+        sizes = {"1": ("2048", "560"), "2": ("2048", "1488")}[nch]
+        for sparse in "01":
+            for fb in sizes:
+                assert f"at3p codebook ch{nch} sparse={sparse} bytes={fb} (186 frames): bad 0" in out

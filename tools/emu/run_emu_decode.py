@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The decoders (ATRAC1, ATRAC3, ATRAC3plus with and without tonal blocks) and the sample-rate converter through the CPU SIMT
-harness (tools/emu), against the committed goldens and the C restatements under tests/host. Driver of
+harness (tools/emu), against the committed goldens and the C restatements under tests/host, and (the `codebook` family) a slice of
+the corpora that hold every code of the ATRAC3 and ATRAC3plus tables at every bit phase. Driver of
 tests/test_decoders_simt_harness.py, which runs it in child processes because the harness reads EMU_STRICT, EMU_FENCE and
 EMU_ORDER when the library loads.
 
@@ -510,6 +511,47 @@ def at3p_single():
             report(f"{what} counters", c != rej.tolist())
 
 
+# ---- every code at every bit phase --------------------------------------------------------------------------------------------
+CODEBOOK_SHIFTS = (0, 7, 31)
+
+
+def at3p_codebook(nch):
+    """A slice of tests/at3p_decode_lib.code_corpus: every table's frame, the group-flag frames and the frame that ends on its
+    limit at shifts 0, 7 and 31, through the four instantiations of the unpack kernel (plain / sparse parse x 2048 bytes / the
+    corpus' own frame size), against the restatement with the same arguments. Every frame is valid: nothing is rejected."""
+    import at3p_writer_lib as W
+    c = AP.code_corpus(nch)
+    for sparse in (False, True):
+        for sized in (False, True):
+            t0 = time.time()
+            fb = c["bytes"] if sized else AP.FRAME
+            frames = np.ascontiguousarray(c["frames"][list(CODEBOOK_SHIFTS), :, :fb])
+            exp, rej = W.decode_streams(frames, nch, sparse=sparse)
+            dec = At3pHipDecoder(n_streams=frames.shape[0], channels=nch, max_frames=frames.shape[1], lib_path=EMU, frame_bytes=fb if sized else None)
+            got = dec.decode(frames, sparse=sparse)
+            cnt = at3p_counts(dec)
+            dec.close()
+            what = f"at3p codebook ch{nch} sparse={int(sparse)} bytes={fb} ({frames.shape[0] * frames.shape[1]} frames)"
+            report(what, frames_bad(got, exp), t0)
+            report(f"{what} counters", any(cnt) or rej.any())
+
+
+def at3_codebook():
+    """the same slice of tests/at3_decode_lib.code_corpus for k_at3d_unpack: every selector's frame at shifts 0, 7 and 31, plain
+    units and joint-stereo frames (the second unit byte-reversed)"""
+    for js in (False, True):
+        t0 = time.time()
+        c = A3.code_corpus(js)
+        frames = np.ascontiguousarray(c["frames"][list(CODEBOOK_SHIFTS)])
+        exp, rej = A3.cpu_ref(frames, c["frame_sz"], js)
+        dec = At3HipDecoder(n_streams=frames.shape[0], frame_size=c["frame_sz"], max_frames=frames.shape[1], lib_path=EMU)
+        got = dec.decode(frames)
+        cnt = at3_counts(dec)
+        dec.close()
+        report(f"at3 codebook js={int(js)} ({frames.shape[0] * frames.shape[1]} frames)", frames_bad(got, exp), t0)
+        report(f"at3 codebook js={int(js)} counters", any(cnt) or any(rej))
+
+
 # ---- the sample-rate converter ------------------------------------------------------------------------------------------------
 def restated(pair, x, channels):
     return RS.CpuResampler(*pair, channels).whole(x)
@@ -658,7 +700,8 @@ CASES = {"at1_goldens": at1_goldens, "at3_goldens": at3_goldens, "at3p_goldens":
          "at1_s16": at1_s16, "at3_s16": at3_s16, "at3p_s16": at3p_s16,
          "at1_single": at1_single, "at3_single": at3_single, "at3p_single": at3p_single,
          "resample_pairs:0": resample_pairs, "resample_pairs:1": resample_pairs, "resample_edges": resample_edges,
-         "resample_domain": resample_domain}
+         "resample_domain": resample_domain, "at3p_codebook:1": at3p_codebook, "at3p_codebook:2": at3p_codebook,
+         "at3_codebook": at3_codebook}
 
 if __name__ == "__main__":
     names = [a for a in sys.argv[1:] if not a.startswith("--")]
