@@ -49,6 +49,7 @@ AT3PHIP_DECODE_TONES = 16
 AT3PHIP_DECODE_SPARSE = 32   # at3phip_decode: word length 0 inside the coded range (include/at3phip.h, SPARSE WORD LENGTHS)
 AT3PHIP_ALLOC_SPARSE = 256   # the frame-writing calls, with AT3PHIP_ALLOC_ADAPTIVE: a unit inside the coded range may keep word length 0
 AT3PHIP_ALLOC_RD = 512       # the frame-writing calls, with both of the above: word lengths chosen by rate and distortion
+AT3PHIP_ALLOC_PSY = 1024     # the frame-writing calls, with all three of the above: lambda shifted per unit by its masking threshold
 AT3PHIP_DECODER_TABLES_BYTES = 67328
 AT3PHIP_DECODER_TONE_TABLES_BYTES = 9504
 
@@ -200,6 +201,7 @@ PROTOTYPES = {
     "at3phip_host_allocate_sized": (_RC, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
     "at3phip_host_allocate_sparse": (_RC, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
     "at3phip_host_allocate_rd": (_RC, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    "at3phip_host_allocate_psy": (_RC, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "at3phip_set_frame_bytes": (_RC, [_VP, _I32]), "at3phip_get_frame_bytes": (_RC, [_VP, _I32P]),
     "at3phip_decoder_set_frame_bytes": (_RC, [_VP, _I32]), "at3phip_decoder_get_frame_bytes": (_RC, [_VP, _I32P]),
     # include/at3phip.h: the ATRAC3plus decoder
@@ -218,7 +220,7 @@ def build_library(verbose=False):
     """Compile libat3hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fvisibility=hidden", "-fPIC", "-shared",
            "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-o", LIB_PATH, os.path.join(CSRC, "at3hip.hip"), os.path.join(CSRC, "at1hip.hip"), os.path.join(CSRC, "at3phip.hip"),
-           os.path.join(CSRC, "at3p_alloc.hip"), os.path.join(CSRC, "at3p_sparse.hip"), os.path.join(CSRC, "at3p_rd.hip"), os.path.join(CSRC, "resample.hip"), os.path.join(CSRC, "loudness.hip"), os.path.join(CSRC, "at3_tables.cpp")]
+           os.path.join(CSRC, "at3p_alloc.hip"), os.path.join(CSRC, "at3p_sparse.hip"), os.path.join(CSRC, "at3p_rd.hip"), os.path.join(CSRC, "at3p_psy.hip"), os.path.join(CSRC, "resample.hip"), os.path.join(CSRC, "loudness.hip"), os.path.join(CSRC, "at3_tables.cpp")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -845,14 +847,36 @@ def _tone_flags(gated, shared):
     return (AT3PHIP_TONES_GATED if gated else 0) | (AT3PHIP_TONES_SHARED if shared else 0)
 
 
-def _alloc_flag(adaptive, sparse=False, rd=False):
-    """the allocation flags of a frame-writing call; sparse (AT3PHIP_ALLOC_SPARSE) needs adaptive, and rd (AT3PHIP_ALLOC_RD) needs both:
-    checked here, before the C call"""
+def _alloc_flag(adaptive, sparse=False, rd=False, psy=False):
+    """the allocation flags of a frame-writing call; sparse (AT3PHIP_ALLOC_SPARSE) needs adaptive, rd (AT3PHIP_ALLOC_RD) needs both and psy
+    (AT3PHIP_ALLOC_PSY) all three: checked here, before the C call"""
+    if psy and not (adaptive and sparse and rd):
+        raise ValueError("psy=True needs adaptive=True, sparse=True and rd=True (AT3PHIP_ALLOC_PSY is valid only together with all three)")
     if sparse and not adaptive:
         raise ValueError("sparse=True needs adaptive=True (AT3PHIP_ALLOC_SPARSE is valid only together with AT3PHIP_ALLOC_ADAPTIVE)")
     if rd and not (adaptive and sparse):
         raise ValueError("rd=True needs adaptive=True and sparse=True (AT3PHIP_ALLOC_RD is valid only together with both)")
-    return (AT3PHIP_ALLOC_ADAPTIVE if adaptive else 0) | (AT3PHIP_ALLOC_SPARSE if sparse else 0) | (AT3PHIP_ALLOC_RD if rd else 0)
+    return ((AT3PHIP_ALLOC_ADAPTIVE if adaptive else 0) | (AT3PHIP_ALLOC_SPARSE if sparse else 0) | (AT3PHIP_ALLOC_RD if rd else 0)
+            | (AT3PHIP_ALLOC_PSY if psy else 0))
+
+
+def at3p_host_allocate_psy(sfi, bits, dist, tail_bits, frame_bytes=None, offsets=None, lib_path=None):
+    """at3phip_host_allocate_psy (no GPU): M1-M6 of include/at3phip.h, MASKING-WEIGHTED WORD LENGTHS, on a cost table and a distortion
+    table as at3p_host_allocate_rd takes them; offsets uint8 [C, 32] (each 0..32) are used as given, None: M1-M3 form them
+    -> (wl uint8 [C, 32], N, j*, k*, chose_psy, offsets uint8 [C, 32])."""
+    sfi, bits, dist = np.ascontiguousarray(sfi, np.uint8), np.ascontiguousarray(bits, np.uint16), np.ascontiguousarray(dist, np.uint64)
+    C = sfi.shape[0]
+    assert sfi.shape == (C, 32) and bits.shape == (C, 32, 8) and dist.shape == (C, 32, 8), (sfi.shape, bits.shape, dist.shape)
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, np.uint8)
+        assert offsets.shape == (C, 32), offsets.shape
+    wl, out, used = np.zeros((C, 32), np.uint8), np.zeros(4, np.int32), np.zeros((C, 32), np.uint8)
+    rc = _need(load_library(lib_path), "at3phip_host_allocate_psy")(_vp(sfi), _vp(bits), _vp(dist), None if offsets is None else _vp(offsets), C,
+                                                                    int(tail_bits), int(AT3PHIP_FRAME_BYTES if frame_bytes is None else frame_bytes),
+                                                                    _vp(wl), _vp(out[0:1]), _vp(out[1:2]), _vp(out[2:3]), _vp(out[3:4]), _vp(used))
+    if rc != 0:
+        raise At3HipError(f"at3phip_host_allocate_psy failed ({rc})")
+    return wl, int(out[0]), int(out[1]), int(out[2]), bool(out[3]), used
 
 
 def at3p_host_allocate_rd(sfi, bits, dist, tail_bits, frame_bytes=None, lib_path=None):
@@ -999,7 +1023,7 @@ class At3pHip(_Context):
     def pqf_mdct_device(self, pcm_ptr, n_frames, specs_ptr):
         self.pqf_mdct_ptr(pcm_ptr, n_frames, None, None, specs_ptr, _device_flags(False))
 
-    def write_frames(self, specs, win_flags=None, tonal=None, adaptive=False, sparse=False, rd=False):
+    def write_frames(self, specs, win_flags=None, tonal=None, adaptive=False, sparse=False, rd=False, psy=False):
         """ScaleFrame + WriteFrame: specs [S, F, C, 2048], win_flags uint16 [S, F, C] or None, tonal records of
         AT3P_TONAL_BLOCK_DTYPE [S, F] (pack_tonal_blocks) or None: no frame carries a tonal block (at3phip_write_frames)
         -> frames uint8 [S, F, frame_bytes]. adaptive: AT3PHIP_ALLOC_ADAPTIVE, word lengths chosen per frame to fill it."""
@@ -1009,11 +1033,11 @@ class At3pHip(_Context):
         fl, flp = self._flags(win_flags, nf)
         out = np.zeros((self.n_streams, nf, self._frame_bytes), np.uint8)
         if tonal is None:
-            self.write_frames_ptr(specs.ctypes.data, nf, flp, out.ctypes.data, _alloc_flag(adaptive, sparse, rd))
+            self.write_frames_ptr(specs.ctypes.data, nf, flp, out.ctypes.data, _alloc_flag(adaptive, sparse, rd, psy))
         else:
             tonal = np.ascontiguousarray(tonal, dtype=AT3P_TONAL_BLOCK_DTYPE)
             assert tonal.shape == (self.n_streams, nf), tonal.shape
-            self.write_frames_tonal_ptr(specs.ctypes.data, nf, flp, tonal.ctypes.data, out.ctypes.data, _alloc_flag(adaptive, sparse, rd))
+            self.write_frames_tonal_ptr(specs.ctypes.data, nf, flp, tonal.ctypes.data, out.ctypes.data, _alloc_flag(adaptive, sparse, rd, psy))
         return out
 
     def _encode_frames_host(self, pcm, dtype, raw, flags=0):
@@ -1024,16 +1048,16 @@ class At3pHip(_Context):
         raw(pcm.ctypes.data, nf, out.ctypes.data, flags)
         return out
 
-    def encode_frames(self, pcm, adaptive=False, sparse=False, rd=False):
+    def encode_frames(self, pcm, adaptive=False, sparse=False, rd=False, psy=False):
         """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, frame_bytes] (tonal analysis finding nothing; no look-ahead delay).
         adaptive (here and in the encode calls below): AT3PHIP_ALLOC_ADAPTIVE, word lengths chosen per frame to fill it."""
-        return self._encode_frames_host(pcm, np.float32, self.encode_frames_ptr, _alloc_flag(adaptive, sparse, rd))
+        return self._encode_frames_host(pcm, np.float32, self.encode_frames_ptr, _alloc_flag(adaptive, sparse, rd, psy))
 
-    def encode_frames_s16(self, pcm, adaptive=False, sparse=False, rd=False):
+    def encode_frames_s16(self, pcm, adaptive=False, sparse=False, rd=False, psy=False):
         """pcm int16 [S, F, 2048, C] (host) -> frames uint8 [S, F, 2048] (at3phip_encode_frames_short): the frames of
         encode_frames() on pcm / 32768 as float32, bit for bit; the samples cross the bus as 16-bit and are widened by the
         filter bank. Calls of both kinds may alternate."""
-        return self._encode_frames_host(pcm, np.int16, self.encode_frames_s16_ptr, _alloc_flag(adaptive, sparse, rd))
+        return self._encode_frames_host(pcm, np.int16, self.encode_frames_s16_ptr, _alloc_flag(adaptive, sparse, rd, psy))
 
     def analyse_tones(self, bands, gated=False, shared=False):
         """bands float32 [S, F, C, 16, 128] (what pqf() returns) -> (blocks of AT3P_TONAL_BLOCK_DTYPE [S, F], residual
@@ -1056,34 +1080,34 @@ class At3pHip(_Context):
         self.analyse_tones_ptr(bands_ptr, n_frames, blocks.ctypes.data, residual_ptr, _device_flags(False) | _tone_flags(gated, shared))
         return blocks
 
-    def encode_frames_tonal(self, pcm, gated=False, shared=False, adaptive=False, sparse=False, rd=False):
+    def encode_frames_tonal(self, pcm, gated=False, shared=False, adaptive=False, sparse=False, rd=False, psy=False):
         """pcm float32 [S, F, 2048, C] -> frames uint8 [S, F, 2048] with the tone analysis (at3phip_encode_frames_tonal): frame f
         of the stream holds the residual of input frame f-1 and the block of frame f-2, so one trailing frame of silence flushes.
         gated: AT3PHIP_TONES_GATED, shared: AT3PHIP_TONES_SHARED, as in analyse_tones()."""
-        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr, _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse, rd))
+        return self._encode_frames_host(pcm, np.float32, self.encode_frames_tonal_ptr, _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse, rd, psy))
 
-    def encode_frames_tonal_s16(self, pcm, gated=False, shared=False, adaptive=False, sparse=False, rd=False):
+    def encode_frames_tonal_s16(self, pcm, gated=False, shared=False, adaptive=False, sparse=False, rd=False, psy=False):
         """The same for int16 PCM (at3phip_encode_frames_tonal_short): the frames of encode_frames_tonal() on pcm / 32768."""
-        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr, _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse, rd))
+        return self._encode_frames_host(pcm, np.int16, self.encode_frames_tonal_s16_ptr, _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse, rd, psy))
 
-    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False, adaptive=False, sparse=False, rd=False):
+    def encode_frames_tonal_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False, adaptive=False, sparse=False, rd=False, psy=False):
         """Device-resident float32 PCM / frames; ordering and what stays untouched until sync() as in encode_frames_device."""
-        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse, rd))
+        self.encode_frames_tonal_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse, rd, psy))
 
-    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False, adaptive=False, sparse=False, rd=False):
+    def encode_frames_tonal_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, gated=False, shared=False, adaptive=False, sparse=False, rd=False, psy=False):
         """Device-resident int16 PCM / frames, as encode_frames_tonal_device."""
-        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse, rd))
+        self.encode_frames_tonal_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _tone_flags(gated, shared) | _alloc_flag(adaptive, sparse, rd, psy))
 
-    def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, adaptive=False, sparse=False, rd=False):
+    def encode_frames_device(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, adaptive=False, sparse=False, rd=False, psy=False):
         """asynchronous=True only queues the call (AT3HIP_ASYNC): sync() before the frames are read, and both buffers stay
         untouched until then. The context's streams are non-blocking (at3hip.h, DEVICE BUFFERS AND STREAMS): they wait for no
         other stream, so whatever produces the PCM must be complete before the call."""
-        self.encode_frames_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _alloc_flag(adaptive, sparse, rd))
+        self.encode_frames_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _alloc_flag(adaptive, sparse, rd, psy))
 
-    def encode_frames_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, adaptive=False, sparse=False, rd=False):
+    def encode_frames_device_s16(self, pcm_ptr, n_frames, frames_ptr, asynchronous=False, adaptive=False, sparse=False, rd=False, psy=False):
         """Device-resident int16 PCM / frames (raw pointers; the PCM needs only 2-byte alignment). Stream ordering and what
         stays untouched until sync() as in encode_frames_device."""
-        self.encode_frames_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _alloc_flag(adaptive, sparse, rd))
+        self.encode_frames_s16_ptr(pcm_ptr, n_frames, frames_ptr, _device_flags(asynchronous) | _alloc_flag(adaptive, sparse, rd, psy))
 
     def timings(self):
         a, b, w = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()

@@ -15,12 +15,17 @@
 //                                table beside the cost table, every unit's pick per lambda, the scans over j and k beside those over
 //                                t and k, and the guard that keeps the sparse allocation where it has less distortion. at3p_rd.hpp
 //                                holds their arithmetic, at3p_rd.hip instantiates them, for the same reason.
+//   k_at3p_write_adaptive_with<WriteParamsPsy>, <WriteParamsTonalPsy>  the rate-distortion two with MASKING-WEIGHTED WORD LENGTHS (M1-M7):
+//                                a masking threshold per unit from the distortion table's first column, its offset to the frame's
+//                                lowest as a shift of lambda in the unit's picks, up to 32 more values of j, and the guard's sums
+//                                weighted. at3p_psy.hpp holds their arithmetic and tables, at3p_psy.hip instantiates them.
 #pragma once
 #include <cstring>
 #include <type_traits>
 
 #include "at3p_write.hpp"
 #include "at3p_rd.hpp"
+#include "at3p_psy.hpp"
 
 namespace at3p {
 
@@ -348,7 +353,8 @@ template <typename P>
 __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams<P> p)
 {
     // kRd: RATE-DISTORTION WORD LENGTHS (at3p_rd.hpp), which are sparse frames
-    constexpr bool kTonal = P::kTonal, kRd = alloc_is_rd<P>::value, kSparse = alloc_is_sparse<P>::value || kRd;
+    // kPsy: MASKING-WEIGHTED WORD LENGTHS (at3p_psy.hpp), which are rate-distortion frames with lambda shifted per unit
+    constexpr bool kTonal = P::kTonal, kRd = alloc_is_rd<P>::value, kSparse = alloc_is_sparse<P>::value || kRd, kPsy = alloc_is_psy<P>::value;
     __shared__ uint32_t s_out[kFrameBytes / 4];
     __shared__ uint32_t s_qbits[2][32][7][8];  // A2: the bits of each unit at each word length under each of its eight tables
     __shared__ uint16_t s_B[2][32][8];         // B[ch][qu][w], entry 0 unused
@@ -368,8 +374,11 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     // kRd only (the others never name them): R1's S and D, every unit's pick at j = kRdJMin - 1 .. kRdJMax, R3's scan results
     __shared__ unsigned long long s_S[kRd ? 2 * 32 * 8 : 1];
     __shared__ double s_D[kRd ? 2 * 32 * 8 : 1];
-    __shared__ uint8_t s_pick[kRd ? (kRdJCount + 1) * 64 : 1];
+    __shared__ uint8_t s_pick[kRd && !kPsy ? (kRdJCount + 1) * 64 : 1];
     __shared__ int s_jfit[4], s_krfit[4];
+    // kPsy only: M2's two tables
+    __shared__ uint32_t s_spread[kPsy ? 256 : 1];
+    __shared__ uint8_t s_ath[kPsy ? 32 : 1];
 
     const WriteTables* W = p.W;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -414,6 +423,10 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
         if (tid >= 224) s_wlv[tid - 224] = wlv_v;
         if constexpr (kTonal) {
             if (tid >= 128 && tid < 128 + kTonalBlockWords) s_rec[tid - 128] = reinterpret_cast<const uint32_t*>(p.tonal + item)[tid - 128];
+        }
+        if constexpr (kPsy) {
+            s_spread[tid] = reinterpret_cast<const uint32_t*>(&p.psy.spread[0][0])[tid];
+            if (tid < 32) s_ath[tid] = p.psy.ath[tid];
         }
 #pragma unroll
         for (int i = 0; i < kLenIt; ++i)
@@ -528,6 +541,41 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     }
     const bool u_act = (lane & 1) < nch;
     const int u_sfi = s_sfi[lane & 1][lane >> 1];
+    // M3: the lane's unit's offset o and the frame's largest, O; both 0 without kPsy, and the code below is then R2-R4 as written
+    [[maybe_unused]] int psy_o = 0, psy_O = 0;
+    if constexpr (kPsy) {   // every wavefront forms them: each fills its rows of the pick table with its lanes' own shifts
+        const int pq = lane >> 1, pc = lane & 1;
+        const uint8_t* spread = reinterpret_cast<const uint8_t*>(s_spread);
+        double th = rd_lambda(s_ath[pq], s_scale);   // M2: the threshold in quiet, then the 32 maskers of the lane's channel
+        for (int m = 0; m < 32; ++m) {
+            const int s = spread[m * 32 + pq];
+            const double cast = s_D[(pc * 32 + m) * 8] * rd_g(s_scale[63 - (s & 63)]);
+            if (s <= 63 && cast > th) th = cast;
+        }
+        const int mu = psy_mu(th, s_scale);
+        const bool live = u_act && s_S[(pc * 32 + pq) * 8] > 0ull;
+        // mu_min over the live lanes and O over all, bit by bit from the top with ballots: wave-uniform, no cross-lane data moves
+        unsigned long long cand = __ballot(live);
+        int mu_min = 0;
+        for (int b = 6; b >= 0; --b) {
+            const unsigned long long z = __ballot(live && !((mu >> b) & 1)) & cand;
+            if (z) cand = z;
+            else mu_min |= 1 << b;
+        }
+        psy_o = live ? (mu - mu_min < kPsyMaxOffset ? mu - mu_min : kPsyMaxOffset) : 0;
+        cand = ~0ull;
+        for (int b = 5; b >= 0; --b) {
+            const unsigned long long o = __ballot((psy_o >> b) & 1) & cand;
+            if (o) {
+                cand = o;
+                psy_O |= 1 << b;
+            }
+        }
+    }
+    // kPsy: up to kPsyMaxOffset more rows, in s_qbits, which nothing reads after B and tab were formed from it
+    static_assert(sizeof(s_qbits) >= (kRdJCount + 1 + kPsyMaxOffset) * 64, "the masking-weighted pick table fits in s_qbits");
+    [[maybe_unused]] uint8_t* const pick = kPsy ? reinterpret_cast<uint8_t*>(&s_qbits[0][0][0][0]) : s_pick;
+    [[maybe_unused]] const int j_lo = kPsy ? kRdJMin - psy_O : kRdJMin;   // M5: the scan's lower end; row i of s_pick holds the picks at j_lo - 1 + i
     if constexpr (kRd) {   // R2: the lane's unit's pick at every j the scans ask for, the rows dealt to the wavefronts
         double D[8];
         uint16_t B[8];
@@ -536,12 +584,13 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
             D[w] = s_D[((lane & 1) * 32 + (lane >> 1)) * 8 + w];
             B[w] = s_B[lane & 1][lane >> 1][w];
         }
-        for (int i = wave; i <= kRdJCount; i += 4) s_pick[i * 64 + lane] = (uint8_t)(u_act ? rd_pick(D, B, rd_lambda(kRdJMin - 1 + i, s_scale)) : 0);
+        for (int i = wave; i <= kRdJMax - j_lo + 1; i += 4)
+            pick[i * 64 + lane] = (uint8_t)(u_act ? rd_pick(D, B, rd_lambda(j_lo - 1 + i + psy_o, s_scale)) : 0);
         __syncthreads();
         int jfit = kRdJMax + 1;
-        for (int j = kRdJMax - wave; j >= kRdJMin; j -= 4) {   // R3, as the scan over t below
-            const int row = (j - kRdJMin) * 64 + lane;
-            const AllocEval e = alloc_eval_from<true>(s_pick[row + 64], s_pick[row], 0, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+        for (int j = kRdJMax - wave; j >= j_lo; j -= 4) {   // R3, as the scan over t below
+            const int row = (j - j_lo) * 64 + lane;
+            const AllocEval e = alloc_eval_from<true>(pick[row + 64], pick[row], 0, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
             if (e.total <= size_bits) jfit = j;
         }
         if (lane == 0) s_jfit[wave] = jfit;
@@ -571,10 +620,10 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
         int j_star = kRdJMax;   // (nothing fits: a caller's table only)
         for (int w = 0; w < 4; ++w)
             if (s_jfit[w] < j_star) j_star = s_jfit[w];
-        j_row = (j_star - kRdJMin) * 64 + lane;
+        j_row = (j_star - j_lo) * 64 + lane;
         int kfit = 0;
         for (int k = wave; k <= kAllocKMax; k += 4) {
-            const AllocEval e = alloc_eval_from<true>(s_pick[j_row + 64], s_pick[j_row], k, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+            const AllocEval e = alloc_eval_from<true>(pick[j_row + 64], pick[j_row], k, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
             if (e.total <= size_bits) kfit = k;
         }
         if (lane == 0) s_krfit[wave] = kfit;
@@ -590,14 +639,20 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
             int kr_star = 0;
             for (int w = 0; w < 4; ++w)
                 if (s_krfit[w] > kr_star) kr_star = s_krfit[w];
-            const AllocEval r = alloc_eval_from<true>(s_pick[j_row + 64], s_pick[j_row], kr_star, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
+            const AllocEval r = alloc_eval_from<true>(pick[j_row + 64], pick[j_row], kr_star, u_act, lane, nch, &s_B[0][0][0], s_wlv, s_pw, tail_bits);
             double t_a = 0.0, t_r = 0.0;   // T: the serial sums in the order of the walk, the same in every lane
 #pragma unroll
             for (int u = 0; u < 64; ++u) {
                 const int wa = __builtin_amdgcn_readlane(e.wl, u), wr = __builtin_amdgcn_readlane(r.wl, u);
                 if ((u & 1) < nch) {
-                    t_a += s_D[((u & 1) * 32 + (u >> 1)) * 8 + wa];
-                    t_r += s_D[((u & 1) * 32 + (u >> 1)) * 8 + wr];
+                    if constexpr (kPsy) {   // M6: each term weighted by G[63 - o]
+                        const double g = rd_g(s_scale[63 - __builtin_amdgcn_readlane(psy_o, u)]);
+                        t_a += s_D[((u & 1) * 32 + (u >> 1)) * 8 + wa] * g;
+                        t_r += s_D[((u & 1) * 32 + (u >> 1)) * 8 + wr] * g;
+                    } else {
+                        t_a += s_D[((u & 1) * 32 + (u >> 1)) * 8 + wa];
+                        t_r += s_D[((u & 1) * 32 + (u >> 1)) * 8 + wr];
+                    }
                 }
             }
             if (t_r <= t_a) e = r;
@@ -700,7 +755,7 @@ __global__ __launch_bounds__(256) void k_at3p_write_adaptive_with(AdaptiveParams
     if (tid < n_words) dst[tid] = __builtin_bswap32(s_out[tid]);
     if (256 + tid < n_words) dst[256 + tid] = __builtin_bswap32(s_out[256 + tid]);
 }
-// (the instantiations are named where they are launched, at3p_alloc.hip, at3p_sparse.hip and at3p_rd.hip: naming one instantiates it, and a
+// (the instantiations are named where they are launched, at3p_alloc.hip, at3p_sparse.hip, at3p_rd.hip and at3p_psy.hip: naming one instantiates it, and a
 // translation unit must hold only its own)
 
 // ---- host: the launch of a unit's two instantiations, P without records and PT with them ------------------------------------------
@@ -714,6 +769,10 @@ void launch_write_adaptive_kernel(const WriteParamsTonal& wp, int32_t frame_byte
     AdaptiveParams<P> ap;
     static_cast<Fixed&>(ap) = wp;
     if constexpr (alloc_is_rd<P>::value) memcpy(ap.mant, AT3P_MANT, sizeof(ap.mant));
+    if constexpr (alloc_is_psy<P>::value) {
+        memcpy(ap.psy.spread, AT3P_PSY_SPREAD, sizeof(ap.psy.spread));
+        memcpy(ap.psy.ath, AT3P_PSY_ATH, sizeof(ap.psy.ath));
+    }
     memcpy(ap.wl_vlc, AT3P_WL_VLC, sizeof(ap.wl_vlc));
     ap.frame_bytes = frame_bytes;
     hipLaunchKernelGGL(k_at3p_write_adaptive_with<P>, dim3((unsigned)wp.n_items), dim3(256), 0, on, ap);

@@ -70,12 +70,13 @@ constexpr auto k_at3p_write = k_at3p_write_with<WriteParams>;
 constexpr auto k_at3p_write_tonal = k_at3p_write_with<WriteParamsTonal>;
 
 // The launches of the adaptive writer's kernels (wp.tonal null: without records) and of the sparse unpack kernels (sized: the frame
-// size is not 2048). The kernels are translation units of their own - at3p_alloc.hip, at3p_sparse.hip, at3p_rd.hip - so that this
+// size is not 2048). The kernels are translation units of their own - at3p_alloc.hip, at3p_sparse.hip, at3p_rd.hip, at3p_psy.hip - so that this
 // one's device code stays instruction for instruction what it was; weak, because the stand-alone host programs that link this file
 // without them (tests/test_owned_alloc_cpu.py) must still link: there resolve_alloc_mode and choose_unpack refuse the flags.
 __attribute__((weak, visibility("default"))) void launch_write_adaptive(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
 __attribute__((weak, visibility("default"))) void launch_write_adaptive_sparse(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
 __attribute__((weak, visibility("default"))) void launch_write_adaptive_rd(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
+__attribute__((weak, visibility("default"))) void launch_write_adaptive_psy(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);
 struct DecUnpackParams;
 __attribute__((weak, visibility("default"))) void launch_unpack_sparse(const DecUnpackParams& up, bool sized, dim3 grid, hipStream_t on);
 }
@@ -116,8 +117,8 @@ FrameBytesError frame_bytes_error(int32_t fb, int channels)
     return e;
 }
 
-// How a frame-writing call chooses its word lengths: the fixed table, or one of the adaptive writer's three units.
-enum AllocMode { kAllocFixed, kAllocAdaptive, kAllocSparse, kAllocRd };
+// How a frame-writing call chooses its word lengths: the fixed table, or one of the adaptive writer's four units.
+enum AllocMode { kAllocFixed, kAllocAdaptive, kAllocSparse, kAllocRd, kAllocPsy };
 struct AllocWriter {
     void (*launch)(const WriteParamsTonal& wp, int32_t frame_bytes, hipStream_t on);   // null: this build was linked without the unit
     const char *flag, *name, *unit;   // for the refusal's text
@@ -127,15 +128,17 @@ const AllocWriter kAllocWriters[] = {
     {launch_write_adaptive, "AT3PHIP_ALLOC_ADAPTIVE", "adaptive", "at3p_alloc.hip"},
     {launch_write_adaptive_sparse, "AT3PHIP_ALLOC_SPARSE", "sparse", "at3p_alloc.hip, at3p_sparse.hip"},
     {launch_write_adaptive_rd, "AT3PHIP_ALLOC_RD", "rate-distortion", "at3p_rd.hip"},
+    {launch_write_adaptive_psy, "AT3PHIP_ALLOC_PSY", "masking-weighted", "at3p_psy.hip"},
 };
 
 // The allocation mode of a frame-writing call with these flags at the context's frame size, or the call's refusal. The fixed table is
 // the reference's and fills 2048 bytes only, so at any other size the call needs AT3PHIP_ALLOC_ADAPTIVE; AT3PHIP_ALLOC_SPARSE counts
-// only together with it, AT3PHIP_ALLOC_RD only together with both; each needs its writer in the build. Every frame-writing call asks
+// only together with it, AT3PHIP_ALLOC_RD only together with both, AT3PHIP_ALLOC_PSY only together with all three; each needs its writer in the build. Every frame-writing call asks
 // directly after its argument checks: a refused call queues nothing, allocates nothing and moves no state.
 int resolve_alloc_mode(at3phip_ctx* c, uint32_t flags, AllocMode* mode)
 {
-    const bool adaptive = flags & AT3PHIP_ALLOC_ADAPTIVE, sparse = flags & AT3PHIP_ALLOC_SPARSE, rd = flags & AT3PHIP_ALLOC_RD;
+    const bool adaptive = flags & AT3PHIP_ALLOC_ADAPTIVE, sparse = flags & AT3PHIP_ALLOC_SPARSE, rd = flags & AT3PHIP_ALLOC_RD,
+               psy = flags & AT3PHIP_ALLOC_PSY;
     auto missing = [c](AllocMode m) {
         const AllocWriter& w = kAllocWriters[m];
         char msg[128];
@@ -147,6 +150,11 @@ int resolve_alloc_mode(at3phip_ctx* c, uint32_t flags, AllocMode* mode)
             return fail(c, AT3HIP_EINVAL, "the fixed table is defined for 2048-byte frames only: this context's frame size needs AT3PHIP_ALLOC_ADAPTIVE");
         if (!kAllocWriters[kAllocAdaptive].launch) return missing(kAllocAdaptive);
     }
+    if (psy) {
+        if (!adaptive || !sparse || !rd)
+            return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_PSY needs AT3PHIP_ALLOC_ADAPTIVE, AT3PHIP_ALLOC_SPARSE and AT3PHIP_ALLOC_RD in the same call");
+        if (!kAllocWriters[kAllocPsy].launch) return missing(kAllocPsy);
+    }
     if (rd) {
         if (!adaptive || !sparse) return fail(c, AT3HIP_EINVAL, "AT3PHIP_ALLOC_RD needs AT3PHIP_ALLOC_ADAPTIVE and AT3PHIP_ALLOC_SPARSE in the same call");
         if (!kAllocWriters[kAllocRd].launch) return missing(kAllocRd);
@@ -156,7 +164,7 @@ int resolve_alloc_mode(at3phip_ctx* c, uint32_t flags, AllocMode* mode)
         if (!kAllocWriters[kAllocSparse].launch) return missing(kAllocSparse);
     }
     if (adaptive && !kAllocWriters[kAllocAdaptive].launch) return missing(kAllocAdaptive);
-    *mode = rd ? kAllocRd : sparse ? kAllocSparse : adaptive ? kAllocAdaptive : kAllocFixed;
+    *mode = psy ? kAllocPsy : rd ? kAllocRd : sparse ? kAllocSparse : adaptive ? kAllocAdaptive : kAllocFixed;
     return AT3HIP_OK;
 }
 

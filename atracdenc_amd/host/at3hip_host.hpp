@@ -1007,15 +1007,17 @@ public:
     // sparse: with `adaptive`, every such call also carries AT3PHIP_ALLOC_SPARSE (SPARSE WORD LENGTHS): a unit inside the coded range
     // may keep word length 0. Without `adaptive` it is an error here, as it is one in the library.
     // rd: with both, every such call also carries AT3PHIP_ALLOC_RD (RATE-DISTORTION WORD LENGTHS); an error without either.
+    // psy: with all three, every such call also carries AT3PHIP_ALLOC_PSY (MASKING-WEIGHTED WORD LENGTHS); an error without `rd`.
     TAt3PEncoder(TCompressedOutputPtr&& out, int channels, int batchFrames = 64, int deviceId = 0, TAt3PSettings settings = TAt3PSettings(),
                  IAt3PGhaProcessor* gha = nullptr, bool deviceTones = false, bool deviceGated = false, bool deviceShared = false,
-                 bool adaptive = false, int frameBytes = AT3PHIP_FRAME_BYTES, bool sparse = false, bool rd = false)
+                 bool adaptive = false, int frameBytes = AT3PHIP_FRAME_BYTES, bool sparse = false, bool rd = false, bool psy = false)
         : Out(std::move(out)), Channels((size_t)channels), BatchFrames(batchFrames), FrameFloats((size_t)AT3PHIP_FRAME * (size_t)channels),
           Settings(settings), Gha(gha), DeviceTones(deviceTones), ToneFlags((deviceGated ? AT3PHIP_TONES_GATED : 0u) | (deviceShared ? AT3PHIP_TONES_SHARED : 0u)),
-          AllocFlag((adaptive ? AT3PHIP_ALLOC_ADAPTIVE : 0u) | (sparse ? AT3PHIP_ALLOC_SPARSE : 0u) | (rd ? AT3PHIP_ALLOC_RD : 0u)), FrameBytes((size_t)frameBytes)
+          AllocFlag((adaptive ? AT3PHIP_ALLOC_ADAPTIVE : 0u) | (sparse ? AT3PHIP_ALLOC_SPARSE : 0u) | (rd ? AT3PHIP_ALLOC_RD : 0u) | (psy ? AT3PHIP_ALLOC_PSY : 0u)), FrameBytes((size_t)frameBytes)
     {
         if (sparse && !adaptive) throw std::invalid_argument("TAt3PEncoder: sparse needs adaptive");
         if (rd && !(adaptive && sparse)) throw std::invalid_argument("TAt3PEncoder: rd needs adaptive and sparse");
+        if (psy && !rd) throw std::invalid_argument("TAt3PEncoder: psy needs rd");
         if (deviceTones && gha) throw std::invalid_argument("TAt3PEncoder: deviceTones takes no host analyser");
         if (deviceGated && !deviceTones) throw std::invalid_argument("TAt3PEncoder: deviceGated needs deviceTones");
         if (deviceShared && !deviceTones) throw std::invalid_argument("TAt3PEncoder: deviceShared needs deviceTones");
@@ -1184,7 +1186,7 @@ private:
     IAt3PGhaProcessor* const Gha;                 // not owned; null: the analysis finds nothing
     const bool DeviceTones;                       // the analysis runs on the GPU
     const uint32_t ToneFlags;                     // and with these flags (AT3PHIP_TONES_GATED, AT3PHIP_TONES_SHARED)
-    const uint32_t AllocFlag;                     // AT3PHIP_ALLOC_ADAPTIVE (| AT3PHIP_ALLOC_SPARSE (| AT3PHIP_ALLOC_RD)) or 0, on every frame-writing call
+    const uint32_t AllocFlag;                     // AT3PHIP_ALLOC_ADAPTIVE (| AT3PHIP_ALLOC_SPARSE (| AT3PHIP_ALLOC_RD (| AT3PHIP_ALLOC_PSY))) or 0, on every frame-writing call
     const size_t FrameBytes;                      // the context's frame size
     std::vector<float> PrevBuf, CurBuf, RawCur;   // [C][16][128] / [C][2048]: TChannelCtx's PrevBuf, CurBuf and RawCurBuf
     at3phip_tonal_block Delay{};                  // `delay`: the block the next call writes

@@ -7,7 +7,7 @@
 //             [--nogaincontrol] [--container oma|riff|raw] [--nostdout] [--batch blocks] [--device n]
 //   at3hipenc -e atrac1 -i in.wav -o out.{aea|raw|dat} [--bfuidxconst 1..8] [--notransient[=mask]]
 //             [--container aea|raw] [--nostdout] [--batch blocks] [--device n]
-//   at3hipenc -e atrac3plus -i in.wav -o out.{oma|at3|wav|raw|dat} [--adaptive [--sparse [--rd]] [--bitrate kbit]] [--tones [--gate] [--share]]
+//   at3hipenc -e atrac3plus -i in.wav -o out.{oma|at3|wav|raw|dat} [--adaptive [--sparse [--rd [--psy]]] [--bitrate kbit]] [--tones [--gate] [--share]]
 //             [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]
 //             --bitrate: one of kAt3pRates' rows (32 .. 352 kbit/s); below 352 the frames are smaller than the 2048 bytes the
 //             fixed word-length table fills, so it needs --adaptive. -d decodes an ATRAC3plus file of any of these frame sizes
@@ -256,7 +256,7 @@ private:
 struct TOptions {
     std::string inFile, outFile, codec, container, rateArg;
     uint32_t bitrate = 0, bfuIdxConst = 0, winMask = 0;
-    bool tones = false, gate = false, share = false, adaptive = false, sparse = false, rd = false, noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false, resample = false, measure = false, peakGiven = false;
+    bool tones = false, gate = false, share = false, adaptive = false, sparse = false, rd = false, psy = false, noTonal = false, noGain = false, noStdOut = false, noTransient = false, decode = false, resample = false, measure = false, peakGiven = false;
     int batch = 256, device = 0, rate = 0;
     TLevel level;
 };
@@ -729,7 +729,7 @@ struct TAtrac3PlusEncode {
     TAt3PEncoder Encoder(TCompressedOutputPtr&& out, const TOptions& o)
     {   // --tones: the tone analysis of at3phip_encode_frames_tonal (--gate: with AT3PHIP_TONES_GATED, --share: with AT3PHIP_TONES_SHARED); the frame count is the plain encode's
         return TAt3PEncoder(std::move(out), (int)Channels, o.batch > 64 ? 64 : o.batch, o.device, TAt3PSettings(), nullptr, o.tones, o.gate, o.share, o.adaptive,
-                            (int)FrameBytes(), o.sparse, o.rd);
+                            (int)FrameBytes(), o.sparse, o.rd, o.psy);
     }
     void Report(TAt3PEncoder&, const TOptions&) const {}
 };
@@ -775,10 +775,11 @@ static int usage()
                  "                 [--container oma|riff|raw] [--nostdout] [--batch blocks] [--device n]\n"
                  "       at3hipenc -e atrac1 -i in.wav -o out.aea [--bfuidxconst 1..8] [--notransient[=mask]]\n"
                  "                 [--container aea|raw] [--nostdout] [--batch blocks] [--device n]\n"
-                 "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--adaptive [--sparse [--rd]] [--bitrate kbit]] [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
+                 "       at3hipenc -e atrac3plus -i in.wav -o out.oma [--adaptive [--sparse [--rd [--psy]]] [--bitrate kbit]] [--tones [--gate] [--share]] [--container oma|riff|raw] [--nostdout] [--batch frames] [--device n]\n"
                  "                 (--adaptive: word lengths chosen per frame on the GPU to fill the frame, instead of the fixed table)\n"
                  "                 (--sparse: with --adaptive, a quant unit inside the coded range may get no bits at all; for the low bitrates)\n"
                  "                 (--rd: with --adaptive --sparse, each unit's word length is chosen by rate and distortion instead of by its peak)\n"
+                 "                 (--psy: with --adaptive --sparse --rd, a unit under the threshold in quiet or next to a loud one pays more for a bit)\n"
                  "                 (--bitrate: 32 (mono), 48, 64, 96, 128, 160, 192, 256, 320 or 352 kbit/s; below 352 with --adaptive only)\n"
                  "                 (--tones: find sine waves on the GPU and write them as tonal blocks; --gate: with envelope points at\n"
                  "                  their onsets and offsets; --share: a band that both channels of a stereo input hold identically is\n"
@@ -819,6 +820,7 @@ int main(int argc, char** argv)
         else if (a == "--adaptive") o.adaptive = true;
         else if (a == "--sparse") o.sparse = true;
         else if (a == "--rd") o.rd = true;
+        else if (a == "--psy") o.psy = true;
         else if (a == "--nogaincontrol") o.noGain = true;
         else if (a == "--nostdout") o.noStdOut = true;
         else if (a == "--resample") o.resample = true;
@@ -851,7 +853,7 @@ int main(int argc, char** argv)
     }
     o.level.NoStdOut = o.noStdOut;
     if (o.measure) {   // prints the meter's result, writes nothing
-        if (o.decode || !o.codec.empty() || o.inFile.empty() || !o.outFile.empty() || o.level.On || o.level.Limit || o.peakGiven || o.rate || o.adaptive || o.sparse || o.rd) return usage();
+        if (o.decode || !o.codec.empty() || o.inFile.empty() || !o.outFile.empty() || o.level.On || o.level.Limit || o.peakGiven || o.rate || o.adaptive || o.sparse || o.rd || o.psy) return usage();
         try {
             const at3hip_loudness_result r = measure_input(o.inFile, o.resample, o.device, o.level.TruePeak);
             char line[256];
@@ -866,7 +868,7 @@ int main(int argc, char** argv)
         return 0;
     }
     if (o.decode) {
-        if (!o.codec.empty() || o.inFile.empty() || o.outFile.empty() || o.level.On || o.level.Limit || o.peakGiven || o.level.TruePeak || o.adaptive || o.sparse || o.rd) return usage();
+        if (!o.codec.empty() || o.inFile.empty() || o.outFile.empty() || o.level.On || o.level.Limit || o.peakGiven || o.level.TruePeak || o.adaptive || o.sparse || o.rd || o.psy) return usage();
         TAt3Input at3;
         const EInput kind = probe_input(o.inFile, at3);
         if (kind == EInput::REFUSED) return 1;
@@ -887,6 +889,10 @@ int main(int argc, char** argv)
     if ((o.gate || o.share) && !o.tones) return usage();      // the gates and the sharing are the tone analysis'
     if (o.tones && o.codec != "atrac3plus") return usage();   // the tone analysis is ATRAC3plus'
     if (o.adaptive && o.codec != "atrac3plus") return usage();   // and so are the adaptive word lengths
+    if (o.psy && !(o.adaptive && o.sparse && o.rd)) {
+        std::cerr << "--psy needs --adaptive --sparse --rd: the masking threshold weights the rate-distortion choice and is nothing without it\n";
+        return usage();
+    }
     if (o.rd && !(o.adaptive && o.sparse)) {
         std::cerr << "--rd needs --adaptive --sparse: the rate-distortion choice may give a quant unit inside the coded range word length 0\n";
         return usage();

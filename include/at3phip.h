@@ -467,9 +467,87 @@ uint32_t at3phip_host_tone_flags(void);
  *      the conversion tests/host/at3p_writer_cpu.c documents at quantise(). Every decision after R1's float operations is integer or
  *      double arithmetic on finite numbers, so any float is accepted, frames do not depend on one another, and no stream affects
  *      another.
- * Out of this definition: psychoacoustic weighting (a weight on D is one table from here). Still ABI 1.6: a library that has the
- * symbol at3phip_host_allocate_rd takes the flag; a build without the rate-distortion writer (at3p_rd.hip) has neither. */
+ * Out of this definition: psychoacoustic weighting, which MASKING-WEIGHTED WORD LENGTHS below adds under a flag of its own. Still ABI
+ * 1.6: a library that has the symbol at3phip_host_allocate_rd takes the flag; a build without the rate-distortion writer (at3p_rd.hip)
+ * has neither. */
 #define AT3PHIP_ALLOC_RD 512u
+
+/* MASKING-WEIGHTED WORD LENGTHS (AT3PHIP_ALLOC_PSY in `flags` of the same six calls, only together with AT3PHIP_ALLOC_ADAPTIVE,
+ * AT3PHIP_ALLOC_SPARSE and AT3PHIP_ALLOC_RD; given without any of the three the call returns AT3HIP_EINVAL with a last-error text before
+ * anything is queued: no output byte is written and no stream state moves. Without the flag nothing above changes: no byte, no PCM
+ * sample, no runtime call). R2 minimises plain squared error, so it spends bits on noise nobody would hear: in units under the
+ * threshold in quiet and in units next to a loud one. With the flag every unit sees lambda shifted by how far its masking threshold
+ * lies above the frame's lowest: a unit masked 2 dB more pays for a bit what the others pay one step of j later. The frames are sparse
+ * frames: no syntax changes, the decoder flag is AT3PHIP_DECODE_SPARSE. This project's definition, stated here and nowhere else, pinned
+ * bit for bit to the C restatement tests/host/at3p_psy_cpu.c. A1, A2, A4s, A6s, R1, the budget and the tail stand; lambda_i is R2's
+ * for any integer i, G is R1's table; one step of either index is a factor 2^(2/3) of energy, 2.007 dB.
+ *  M1. Energy. E[ch][qu] = D[ch][qu][0] of R1: the unit's energy on D's scale (2^40 times the sum of its squared lines), exact and
+ *      order-free already. A unit is live when S[ch][qu][0] > 0.
+ *  M2. Threshold index. Th[ch][qu] = max(lambda_{ath[qu]}, max over q' in 0..31 with spread[q'][qu] <= 63 of E[ch][q'] *
+ *      G[63 - spread[q'][qu]]): each product one rounded double multiply, the maxima exact. Maskers come from the same channel only
+ *      (cross-channel masking is unsafe under binaural unmasking). mu[ch][qu] is the largest i in 0..MU_HI with lambda_i <= Th; it
+ *      exists because Th >= lambda_{ath[qu]}. MU_HI = 73, the larger of 73 and the largest ath entry: lambda_73 is the largest lambda_i
+ *      not above 2^47, and D[0] cannot exceed 2^47.
+ *  M3. Offsets. mu_min is the minimum of mu over the live units of every channel in the frame. o[ch][qu] = min(mu - mu_min, 32) for a
+ *      live unit and 0 for a unit that is not live (it picks 0 at every lambda); 0 everywhere when no unit is live. O is the largest
+ *      o of the frame. 32 steps are 64 dB: the range over which the weighting tells units apart.
+ *  M4. Candidate P(j, k): R2 with one change. pick(ch, qu; j) minimises D[w] + lambda_{j + o[ch][qu]} * (double)(B[w] + (w > 0 ? 3 : 0)),
+ *      the j - 1 value likewise with lambda_{j - 1 + o[ch][qu]}. No new multiply enters the pick. The walk, the raise list, the closing
+ *      rules and Bits are R2's.
+ *  M5. Choice. j* is the smallest j in -30 - O .. 69 whose P(j, 0) fits (69 where none does: a caller's table only); k* as in R3. At
+ *      j = 69 every unit sees an index of at least 69 and picks 0 by R3's bound, which holds for every larger lambda, so the smallest
+ *      frame fits at every admissible size. The lower end moves with O so that the most-masked unit can still reach lambda_-30 before
+ *      the scan gives up; a frame with room would otherwise be left underfilled.
+ *  M6. Guard. Tw(X) is the serial double sum from +0.0, in the walk's order, of D[ch][qu][wl_X[ch][qu]] * G[63 - o[ch][qu]]: one rounded
+ *      multiply per term. The frame is P(j*, k*) if Tw(P) <= Tw(A), else A(t*, k*), the sparse frame byte for byte. Property, exact:
+ *      the written allocation's Tw never exceeds the sparse allocation's.
+ *  M7. Floats outside the domain. R5 stands: a NaN line adds nothing to S. Everything in M1-M6 is integer or double arithmetic on
+ *      finite numbers (E <= 2^47, G <= 1); no stream affects another.
+ * Consequence: with every offset 0 the frame is the rate-distortion frame byte for byte (G[63] = 1.0, the scan starts at -30).
+ * The two tables are integers, so no libm result is part of a frame; atracdenc_amd/csrc/at3p_psy.inc holds them, written by
+ * tools/gen_at3p_psy.py, which says how they were formed: spread from the Bark distance of the units' centre frequencies with a
+ * 12 dB signal-to-mask distance and slopes of 10 dB per Bark upwards and 27 dB per Bark downwards, ath from the threshold in quiet
+ * against the spectrum energy of a full-scale sine. These integers are the definition.
+ *  spread[q'][q], row q' = 0..31 (255: no masking):
+ *     6  14  22  30  36  42  48  53  59 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255
+ *    29   6  14  21  28  34  39  44  50  57  62 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255
+ *    50  27   6  13  20  26  31  36  42  49  54  59  62 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255
+ *   255  47  26   6  13  19  24  29  35  42  47  51  55  58  61 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255
+ *   255 255  44  24   6  12  17  22  28  35  40  45  48  52  54  57  61 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255
+ *   255 255  60  40  22   6  11  16  22  29  34  39  42  46  48  51  54  59  62 255 255 255 255 255 255 255 255 255 255 255 255 255
+ *   255 255 255  55  37  20   6  11  17  23  29  33  37  40  43  46  49  53  57  60  63 255 255 255 255 255 255 255 255 255 255 255
+ *   255 255 255 255  50  33  19   6  12  19  24  28  32  35  38  41  44  49  52  55  58  61 255 255 255 255 255 255 255 255 255 255
+ *   255 255 255 255 255  50  35  22   6  13  18  22  26  29  32  35  38  42  46  49  52  55  58  62 255 255 255 255 255 255 255 255
+ *   255 255 255 255 255 255  53  40  24   6  11  16  19  23  26  28  32  36  39  43  46  48  51  55  58  60  61  62  63 255 255 255
+ *   255 255 255 255 255 255 255  55  38  20   6  10  14  17  20  23  26  30  34  37  40  43  46  50  52  54  56  57  58  59  60  60
+ *   255 255 255 255 255 255 255 255  50  32  18   6  10  13  16  18  22  26  30  33  36  38  42  45  48  50  51  53  54  54  55  56
+ *   255 255 255 255 255 255 255 255  60  42  28  16   6   9  12  15  18  22  26  29  32  35  38  41  44  46  48  49  50  51  51  52
+ *   255 255 255 255 255 255 255 255 255  51  37  25  15   6   9  11  15  19  23  26  29  31  35  38  41  43  44  46  47  47  48  49
+ *   255 255 255 255 255 255 255 255 255  59  44  33  22  14   6   9  12  16  20  23  26  29  32  35  38  40  42  43  44  45  45  46
+ *   255 255 255 255 255 255 255 255 255 255  51  40  29  21  13   6   9  14  17  21  23  26  29  33  35  37  39  40  41  42  43  43
+ *   255 255 255 255 255 255 255 255 255 255  61  49  39  30  22  15   6  10  14  17  20  23  26  29  32  34  35  37  38  39  39  40
+ *   255 255 255 255 255 255 255 255 255 255 255  60  50  41  33  27  17   6  10  13  16  18  22  25  28  30  31  33  34  34  35  36
+ *   255 255 255 255 255 255 255 255 255 255 255 255  60  51  43  36  27  16   6   9  12  15  18  21  24  26  28  29  30  31  31  32
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255  60  52  45  36  25  15   6   9  11  15  18  21  23  24  26  27  27  28  29
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255  60  53  44  33  23  14   6   9  12  15  18  20  22  23  24  25  25  26
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  60  51  39  30  21  13   6   9  13  15  17  19  20  21  22  23  23
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  59  48  39  30  22  15   6   9  12  14  16  17  18  19  19  20
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  58  48  39  31  24  15   6   9  11  12  13  14  15  16  17
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  55  46  38  31  22  13   6   8  10  11  12  13  13  14
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  60  52  44  37  28  18  11   6   8   9  10  11  11  12
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  56  48  41  32  23  16  10   6   7   8   9  10  10
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  59  51  44  35  26  19  14   9   6   7   8   8   9
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  62  54  47  38  29  22  16  12   9   6   7   7   8
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  56  49  40  31  24  18  14  11   8   6   7   7
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  58  51  42  33  26  20  16  13  10   8   6   7
+ *   255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255 255  60  53  44  34  27  22  18  14  12   9   8   6
+ *  ath[q], q = 0..31:
+ *    19  14  13  12  12  12  11  11  10   9   9   8   8   8   7   7   8   9  11  13  14  15  16  16  15  15  17  21  29  35  41  47
+ * Known limits. With the tone analysis the written spectrum is the residual, so the extracted sines do not count as maskers: the
+ * threshold is then too low, never too high, which costs gain and not quality. No temporal masking, no tonality estimate: every
+ * masker is taken for noise-like. Still ABI 1.6: a library that has the symbol at3phip_host_allocate_psy takes the flag; a build
+ * without the masking-weighted writer (at3p_psy.hip) has neither. */
+#define AT3PHIP_ALLOC_PSY 1024u
 
 /* Steps A3-A5 on a caller-supplied cost table, on the host (no GPU needed).
  *   sfi        [channels][32] scale factor indices, each 0..63
@@ -504,6 +582,15 @@ int at3phip_host_allocate_sparse(const uint8_t* sfi, const uint16_t* bits, int32
  * an S above 2^47. */
 int at3phip_host_allocate_rd(const uint8_t* sfi, const uint16_t* bits, const uint64_t* dist, int32_t channels, int32_t tail_bits,
                              int32_t frame_bytes, uint8_t* wl_out, int32_t* n_units, int32_t* j, int32_t* k, int32_t* chose_rd);
+
+/* M1-M6 (MASKING-WEIGHTED WORD LENGTHS) on caller-supplied tables, on the host (no GPU needed): sfi, bits, dist, channels, tail_bits,
+ * frame_bytes, wl_out, n_units, j and k as at3phip_host_allocate_rd. offsets_in null: the offsets are M1-M3's, from dist and sfi;
+ * offsets_in [channels][32], each 0..32: they are used as given (O is their largest). chose_psy receives 1 when wl_out is P(j*, k*)
+ * and 0 when the guard of M6 fell back to A(t*, k*); offsets_out [channels][32], which may be null, the offsets used. Errors as
+ * at3phip_host_allocate_rd, also for an offset above 32. */
+int at3phip_host_allocate_psy(const uint8_t* sfi, const uint16_t* bits, const uint64_t* dist, const uint8_t* offsets_in, int32_t channels,
+                              int32_t tail_bits, int32_t frame_bytes, uint8_t* wl_out, int32_t* n_units, int32_t* j, int32_t* k,
+                              int32_t* chose_psy, uint8_t* offsets_out);
 
 /* The context's frame size (FRAME SIZE above). Given an admissible size the setter first waits for everything queued on the
  * context, as at3phip_sync does (a queued call still writes frames of the old size), then stores the size: it allocates and

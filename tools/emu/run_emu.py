@@ -24,6 +24,7 @@ def build(strict=False):
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3p_alloc.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3p_sparse.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3p_rd.hip"),
+                           os.path.join(ROOT, "atracdenc_amd/csrc/at3p_psy.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/resample.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/loudness.hip"),
                            os.path.join(ROOT, "atracdenc_amd/csrc/at3_tables.cpp"),
