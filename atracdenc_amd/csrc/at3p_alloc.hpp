@@ -5,7 +5,8 @@
 //   k_at3p_write_adaptive_tonal  the same with a record per frame, whose block counts in every candidate's bits.
 // The word lengths are no longer the reference's table, so the word-length section (TWordLenEncoder, at3p_bitstream.cpp:
 // 170-252) is priced and written here and WriteTables::head is not used. Spectra, tail and tonal block go through the fixed
-// writer's emit_chunk, tonal_price and tonal_emit. host_allocate is steps A3-A5 on the host (at3phip_host_allocate).
+// writer's emit_chunk, tonal_price and tonal_emit. host_allocate is steps A3-A5 on the host (at3phip_host_allocate), host_allocate_rd
+// R2-R4 and, with offsets, M4-M6 (at3phip_host_allocate_rd, at3phip_host_allocate_psy).
 //   k_at3p_write_adaptive_sparse, k_at3p_write_adaptive_tonal_sparse  the same two with SPARSE WORD LENGTHS (A3s, A4s, A6s): a unit
 //                                inside the coded range may keep word length 0, and then has no code-table index and no spectrum.
 //                                Instantiations of their own in a translation unit of their own, at3p_sparse.hip: next to the two
@@ -78,6 +79,41 @@ inline int host_sparse_close(int (&wl)[2][32], int top)
     return N;
 }
 
+// A3s's walk, which R2 and M4 share: every unit has a pair (w0, up), given by pair(ch, qu, &w0, &up); the first k units whose up exceeds
+// their w0 take it; then A3s's closing rules. Returns N; took: the units that took their up.
+template <typename Pair>
+inline int host_sparse_walk(int (&wl)[2][32], int channels, int k, int* took, Pair pair)
+{
+    int top = -1;
+    *took = 0;
+    for (int qu = 0, left = k; qu < 32; ++qu)
+        for (int ch = 0; ch < channels; ++ch) {
+            int w0 = 0, up = 0;
+            pair(ch, qu, &w0, &up);
+            wl[ch][qu] = w0;
+            if (left > 0 && up > w0) {
+                wl[ch][qu] = up;
+                --left;
+                ++*took;
+            }
+            if (wl[ch][qu]) top = qu;
+        }
+    return host_sparse_close(wl, top);
+}
+// The two scans of A4 and A5 (R3, M5): the smallest first parameter in lo..hi whose candidate fits with k = 0 (hi where none does: a
+// caller's table only), then the largest k that fits. fits(p, k) forms the candidate and tells; (p*, k*) is left formed.
+template <typename Fits>
+inline void host_scan(int lo, int hi, int* p_star, Fits fits)
+{
+    int ps = hi, ks = 0;
+    for (int p = hi; p >= lo; --p)
+        if (fits(p, 0)) ps = p;
+    for (int k = 0; k <= kAllocKMax; ++k)
+        if (fits(ps, k)) ks = k;
+    fits(ps, ks);
+    *p_star = ps;
+}
+
 // ---- host: steps A3-A5 on a cost table ---------------------------------------------------------------------------------
 // sfi [channels][32], bits [channels][32][8] (entry w = the unit's bits at word length w, entry 0 unused) -> wl [channels][32]
 // (0 at and above N), N, t*, k*; returns Bits(A(t*, k*)). size_bits: the budget of A4, 8 * frame_bytes - 3. sparse: A3s and A4s.
@@ -86,24 +122,7 @@ inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels,
 {
     int wl[2][32] = {};
     int N = 1, took = 0;
-    auto form_sparse = [&](int t, int k) {   // A3s: every unit is walked, nothing is raised from 0 to 1, N follows the raise
-        int top = -1;
-        took = 0;
-        for (int qu = 0, left = k; qu < 32; ++qu)
-            for (int ch = 0; ch < channels; ++ch) {
-                const int w0 = alloc_want(sfi[ch * 32 + qu], t), up = alloc_want(sfi[ch * 32 + qu], t - 1);
-                wl[ch][qu] = w0;
-                if (left > 0 && up > w0) {
-                    wl[ch][qu] = up;
-                    --left;
-                    ++took;
-                }
-                if (wl[ch][qu]) top = qu;
-            }
-        N = host_sparse_close(wl, top);
-    };
-    auto form = [&](int t, int k) {   // A(t, k) into wl and N; took: the units that took the t - 1 value
-        if (sparse) return form_sparse(t, k);
+    auto form_dense = [&](int t, int k) {   // A(t, k) into wl and N; took: the units that took the t - 1 value
         int top = -1;
         for (int qu = 0; qu < 32; ++qu)
             for (int ch = 0; ch < channels; ++ch) {
@@ -129,23 +148,81 @@ inline int host_allocate(const uint8_t* sfi, const uint16_t* bits, int channels,
             }
     };
     auto count = [&]() { return host_alloc_bits(wl, N, bits, channels, tail_bits); };   // Bits(A)
-    int ts = kAllocTMax + 1, ks = 0;
-    for (int t = kAllocTMax; t >= kAllocTMin; --t) {   // every t: the smallest that fits
-        form(t, 0);
-        if (count() <= size_bits) ts = t;
-    }
-    if (ts > kAllocTMax) ts = kAllocTMax;              // nothing fits (a caller's table only)
-    for (int k = 0; k <= kAllocKMax; ++k) {            // every k: the largest that fits
-        form(ts, k);
-        if (count() <= size_bits) ks = k;
-    }
-    form(ts, ks);
+    int ts = 0;
+    host_scan(kAllocTMin, kAllocTMax, &ts, [&](int t, int k) {
+        if (!sparse) form_dense(t, k);
+        else   // A3s: every unit is walked, nothing is raised from 0 to 1, N follows the raise
+            N = host_sparse_walk(wl, channels, k, &took, [&](int ch, int qu, int* w0, int* up) {
+                *w0 = alloc_want(sfi[ch * 32 + qu], t);
+                *up = alloc_want(sfi[ch * 32 + qu], t - 1);
+            });
+        return count() <= size_bits;
+    });
     for (int ch = 0; ch < channels; ++ch)
         for (int qu = 0; qu < 32; ++qu) wl_out[ch * 32 + qu] = (uint8_t)wl[ch][qu];
     *n_units = N;
     *t_out = ts;
     *k_out = took;   // k* as reported: a k beyond the units that can take the t - 1 value gives the same allocation
     return count();
+}
+
+// ---- host: R2-R4 and, with offsets, M4-M6 on a cost table and a distortion table ------------------------------------------------
+// dist: S [channels][32][8]. o: null for RATE-DISTORTION WORD LENGTHS, or M3's offsets for MASKING-WEIGHTED WORD LENGTHS, which are
+// the same with lambda shifted per unit, the scan reaching down by the largest offset and the guard's sums weighted. Returns Bits of
+// the allocation written; chose: 1 = R(j*, k*) or P(j*, k*), 0 = the sparse allocation A(t*, k*).
+inline int host_allocate_rd(const uint8_t* sfi, const uint16_t* bits, const uint64_t* dist, const int (*o)[32], int channels, int tail_bits,
+                            int size_bits, uint8_t* wl_out, int* n_units, int* j_out, int* k_out, int* chose)
+{
+    double D[2][32][8] = {};
+    uint16_t B[2][32][8] = {};
+    int O = 0;
+    for (int ch = 0; ch < channels; ++ch)
+        for (int qu = 0; qu < 32; ++qu) {
+            for (int w = 0; w < 8; ++w) {
+                D[ch][qu][w] = rd_d(dist[(ch * 32 + qu) * 8 + w], rd_g(AT3P_SCALE[sfi[ch * 32 + qu]]));
+                B[ch][qu][w] = w ? bits[(ch * 32 + qu) * 8 + w] : 0;   // (entry 0 is not read)
+            }
+            if (o && o[ch][qu] > O) O = o[ch][qu];
+        }
+    int wl[2][32] = {};
+    int N = 1, took = 0, js = 0;
+    auto count = [&]() { return host_alloc_bits(wl, N, bits, channels, tail_bits); };
+    host_scan(kRdJMin - O, kRdJMax, &js, [&](int j, int k) {   // R3, M5; R(j, k) or P(j, k) into wl and N
+        N = host_sparse_walk(wl, channels, k, &took, [&](int ch, int qu, int* w0, int* up) {
+            const int shift = o ? o[ch][qu] : 0;
+            *w0 = rd_pick(D[ch][qu], B[ch][qu], rd_lambda(j + shift, AT3P_SCALE));
+            *up = rd_pick(D[ch][qu], B[ch][qu], rd_lambda(j - 1 + shift, AT3P_SCALE));
+        });
+        return count() <= size_bits;
+    });
+    // R4, M6: against the sparse allocation A(t*, k*)
+    uint8_t wl_a[64] = {};
+    int n_a = 0, t_a = 0, k_a = 0;
+    const int bits_a = host_allocate(sfi, bits, channels, tail_bits, size_bits, wl_a, &n_a, &t_a, &k_a, true);
+    double sum_r = 0.0, sum_a = 0.0;
+    for (int qu = 0; qu < 32; ++qu)
+        for (int ch = 0; ch < channels; ++ch) {
+            double d_r = D[ch][qu][wl[ch][qu]], d_a = D[ch][qu][wl_a[ch * 32 + qu]];
+            if (o) {   // M6's weight G[63 - o]. Without offsets it would be G[63], exactly 1.0 (ScaleTable[63] is 2^0): R4's sums as written
+                const double g = rd_g(AT3P_SCALE[63 - o[ch][qu]]);
+                d_r *= g;
+                d_a *= g;
+            }
+            sum_r += d_r;
+            sum_a += d_a;
+        }
+    *j_out = js;
+    *k_out = took;   // k* as reported (A5)
+    *chose = sum_r <= sum_a;
+    if (*chose) {
+        for (int ch = 0; ch < channels; ++ch)
+            for (int qu = 0; qu < 32; ++qu) wl_out[ch * 32 + qu] = (uint8_t)wl[ch][qu];
+        *n_units = N;
+        return count();
+    }
+    memcpy(wl_out, wl_a, (size_t)channels * 32);
+    *n_units = n_a;
+    return bits_a;
 }
 
 // The argument checks every host allocator of include/at3phip.h makes (t: the scan's first result, t* or j*)
@@ -157,6 +234,16 @@ inline int host_allocate_args(const uint8_t* sfi, const uint16_t* bits, int32_t 
     if (tail_bits < 0 || tail_bits > 8 * frame_bytes - 3) return AT3HIP_EINVAL;
     for (int i = 0; i < 32 * channels; ++i)
         if (sfi[i] > 63) return AT3HIP_EINVAL;
+    return AT3HIP_OK;
+}
+// and those of the two that take a distortion table: the above, dist, the guard's outcome, and S's bound
+inline int host_allocate_rd_args(const uint8_t* sfi, const uint16_t* bits, const uint64_t* dist, int32_t channels, int32_t tail_bits, int32_t frame_bytes,
+                                 const uint8_t* wl_out, const int32_t* n_units, const int32_t* j, const int32_t* k, const int32_t* chose)
+{
+    if (!dist || !chose) return AT3HIP_EINVAL;
+    if (const int rc = host_allocate_args(sfi, bits, channels, tail_bits, frame_bytes, wl_out, n_units, j, k)) return rc;
+    for (int i = 0; i < 256 * channels; ++i)
+        if (dist[i] > (1ull << 47)) return AT3HIP_EINVAL;   // 128 lines of at most 2^40 each
     return AT3HIP_OK;
 }
 

@@ -479,7 +479,7 @@ uint32_t at3phip_host_tone_flags(void);
  * threshold in quiet and in units next to a loud one. With the flag every unit sees lambda shifted by how far its masking threshold
  * lies above the frame's lowest: a unit masked 2 dB more pays for a bit what the others pay one step of j later. The frames are sparse
  * frames: no syntax changes, the decoder flag is AT3PHIP_DECODE_SPARSE. This project's definition, stated here and nowhere else, pinned
- * bit for bit to the C restatement tests/host/at3p_psy_cpu.c. A1, A2, A4s, A6s, R1, the budget and the tail stand; lambda_i is R2's
+ * bit for bit to the C restatement tests/host/at3p_rd_cpu.c. A1, A2, A4s, A6s, R1, the budget and the tail stand; lambda_i is R2's
  * for any integer i, G is R1's table; one step of either index is a factor 2^(2/3) of energy, 2.007 dB.
  *  M1. Energy. E[ch][qu] = D[ch][qu][0] of R1: the unit's energy on D's scale (2^40 times the sum of its squared lines), exact and
  *      order-free already. A unit is live when S[ch][qu][0] > 0.

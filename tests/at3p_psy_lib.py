@@ -1,55 +1,27 @@
 """Helpers of the MASKING-WEIGHTED WORD LENGTHS tests (include/at3phip.h, M1-M7), their golden generator, SIMT-harness driver and bench
 tool (TEST INFRASTRUCTURE: nothing under atracdenc_amd/ imports this module).
 
-  * psy_lib: the C restatement tests/host/at3p_psy_cpu.c, which includes at3p_rd_cpu.c and through it every restatement of the adaptive
-    writer; compiled once, on first use, with the reference's arithmetic flags.
-  * write_psy / allocate_psy: the restatement's entry points, as at3p_writer_lib's write_rd / allocate_rd.
+  * write_psy / allocate_psy: at3p_writer_lib's write_rd / allocate_rd with psy: the restatement tests/host/at3p_rd_cpu.c states both.
   * psy_tables: the two integer tables of at3p_psy.inc; weighted_total: Tw of M6 recomputed in Python; offsets_py: M1-M3 in Python.
-  * masked_twin: the spectrum of the one test of behaviour; the cases of tests/golden/at3p_psy.npz.
+  * masked_twin: the spectrum of the one test of behaviour; the cases of tests/golden/at3p_psy.npz; the inputs and digests of
+    tests/golden/at3p_rd_fold.npz.
 """
-import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 
 import at3p_writer_lib as W
-from at3_testlib import _vp
-from at3p_decode_lib import CFLAGS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-PSY_SRC = os.path.join(HERE, "host", "at3p_psy_cpu.c")
 PSY_INC = os.path.join(ROOT, "atracdenc_amd", "csrc", "at3p_psy.inc")
 MU_HI, O_MAX = 73, 32
-PSY_INFO_DTYPE = np.dtype([("j", "<i4"), ("k", "<i4"), ("num_quant_units", "<i4"), ("bits", "<i4"), ("chose_psy", "<i4"), ("t", "<i4"),
-                           ("k_sparse", "<i4"), ("O", "<i4"), ("Tw_psy", "<f8"), ("Tw_sparse", "<f8"), ("o", "u1", (2, 32)), ("mu", "<i4", (2, 32)),
-                           ("wl", "u1", (2, 32)), ("sfi", "u1", (2, 32)), ("tab", "u1", (2, 32))])
-_so = None
-
-
-def psy_lib():
-    global _so
-    if _so is None:
-        d = tempfile.mkdtemp(prefix="at3ppsy_")
-        so = os.path.join(d, "libat3ppsy_cpu.so")
-        subprocess.check_call(["gcc", "-std=gnu11", *CFLAGS, "-shared", "-o", so, PSY_SRC, "-lm"])
-        _so = so
-    lib = ctypes.CDLL(_so)
-    I, P = ctypes.c_int, ctypes.c_void_p
-    lib.at3ppsy_allocate.argtypes = [P, P, P, P, I, I, I, P, P, P]
-    lib.at3ppsy_write_frames.argtypes = [P, I, I, I, P, P, P, P]
-    assert lib.at3ppsy_frame_info_size() == PSY_INFO_DTYPE.itemsize
-    return lib
 
 
 def write_psy(specs, frame_bytes, win=None, blocks=None, info=False):
-    """at3p_writer_lib.write_rd with MASKING-WEIGHTED WORD LENGTHS (records of PSY_INFO_DTYPE)"""
-    psy_lib()
-    return W._write(lambda lib, sp, nch, n, tails, nbits, out, rec: psy_lib().at3ppsy_write_frames(sp, nch, n, int(frame_bytes), tails, nbits, out, rec),
-                    PSY_INFO_DTYPE, specs, frame_bytes, win, blocks, info)
+    """at3p_writer_lib.write_rd with MASKING-WEIGHTED WORD LENGTHS"""
+    return W.write_rd(specs, frame_bytes, win, blocks, info, psy=True)
 
 
 def write_psy_streams(specs, frame_bytes, blocks=None):
@@ -58,14 +30,8 @@ def write_psy_streams(specs, frame_bytes, blocks=None):
 
 
 def allocate_psy(sfi, bits, dist, tail_bits, frame_bytes, offsets=None):
-    """M1-M6 of the restatement: (wl uint8 [C, 32], N, record of PSY_INFO_DTYPE); offsets uint8 [C, 32] replace M1-M3's"""
-    sfi, bits, dist = np.ascontiguousarray(sfi, np.uint8), np.ascontiguousarray(bits, np.uint16), np.ascontiguousarray(dist, np.uint64)
-    nch = sfi.shape[0]
-    off = None if offsets is None else np.ascontiguousarray(offsets, np.uint8)
-    wl, n, rec = np.zeros((nch, 32), np.uint8), np.zeros(1, np.int32), np.zeros(1, PSY_INFO_DTYPE)
-    rec["bits"] = psy_lib().at3ppsy_allocate(_vp(sfi), _vp(bits), _vp(dist), None if off is None else _vp(off), nch, int(tail_bits), int(frame_bytes),
-                                             _vp(wl), _vp(n), _vp(rec))
-    return wl, int(n[0]), rec[0]
+    """M1-M6 of the restatement: (wl uint8 [C, 32], N, record of W.RD_INFO_DTYPE); offsets uint8 [C, 32] replace M1-M3's"""
+    return W.allocate_rd(sfi, bits, dist, tail_bits, frame_bytes, offsets, psy=True)
 
 
 def psy_tables():
@@ -161,5 +127,60 @@ def psy_golden_entry(name, nch, fb):
     """the restatement on 3 frames of a signal: {frames uint8 [3, fb], choice int32 [3, 5] (j*, k*, N, chose_psy, O), o uint8 [3, 2, 32],
     wl uint8 [3, 2, 32], Tw float64 [3, 2] (Tw(P), Tw(A))}"""
     frames, rec, _ = write_psy(W.specs_of(name, nch, PSY_GOLDEN_FRAMES), fb, info=True)
-    return {"frames": frames, "choice": np.stack([rec["j"], rec["k"], rec["num_quant_units"], rec["chose_psy"], rec["O"]], axis=1).astype(np.int32),
-            "o": rec["o"], "wl": rec["wl"], "Tw": np.stack([rec["Tw_psy"], rec["Tw_sparse"]], axis=1)}
+    return {"frames": frames, "choice": np.stack([rec["j"], rec["k"], rec["num_quant_units"], rec["chose"], rec["O"]], axis=1).astype(np.int32),
+            "o": rec["o"], "wl": rec["wl"], "Tw": np.stack([rec["T"], rec["T_sparse"]], axis=1)}
+
+
+# ---- at3p_rd_fold.npz: what the two restatements and the two host allocators gave before they were folded (DESIGN.md, section 24.1) ----
+RD_FOLD_GOLDEN = os.path.join(HERE, "golden", "at3p_rd_fold.npz")
+SIZES = {1: (176, 376, 744, 2048), 2: (224, 376, 744, 2048)}
+CELLS = [(name, nch, fb) for name in ("noise", "tones", "mix", "burst") for nch in (1, 2) for fb in SIZES[nch]]
+_rand = []
+
+
+def random_tables():
+    """2000 x (sfi, bits, dist, tail_bits, offsets, frame_bytes)"""
+    if not _rand:
+        tabs = W.random_dist_tables(W.random_cost_tables(2000))
+        for i, ((sfi, bits, dist, tail), off) in enumerate(zip(tabs, random_offsets(tabs))):
+            fb = SIZES[sfi.shape[0]][i % 4]
+            _rand.append((sfi, bits, dist, min(tail, 8 * fb - 3), off, fb))
+    return _rand
+
+
+def rd_fold_entries():
+    """{label: SHA-256} of tests/golden/at3p_rd_fold.npz, field by field and never a record's bytes. Per hundred of random_tables: the
+    inputs (`in`); wl, N, j*, k*, the guard's outcome, Bits and both T of the restatement (`rest`) and wl, N, j*, k* and the outcome of
+    the host function (`host`) with rate-distortion word lengths (`rd`), masking-weighted with the offsets given (`psy`, with o, O and mu,
+    and the host function's offsets out) and, on every fourth table, with the offsets left to M1-M3 (`m`). Per cell of CELLS: the
+    spectra of 3 frames, and the frames, tail bits and every field of the record of write_rd and of write_psy."""
+    from atracdenc_amd.binding import at3p_host_allocate_psy, at3p_host_allocate_rd
+    rest = lambda wl, N, r, more=(): [wl, N] + [r[f] for f in ("j", "k", "chose", "bits", "T", "T_sparse") + more]
+    out, tabs = {}, random_tables()
+    for g in range(0, len(tabs), 100):
+        parts = {k: [] for k in ("in", "rd_rest", "rd_host", "psy_rest", "psy_host", "m_rest", "m_host")}
+        for i in range(g, g + 100):
+            sfi, bits, dist, tail, off, fb = tabs[i]
+            parts["in"] += [sfi, bits, dist, tail, off, fb]
+            parts["rd_rest"] += rest(*W.allocate_rd(sfi, bits, dist, tail, fb))
+            parts["rd_host"] += list(at3p_host_allocate_rd(sfi, bits, dist, tail, fb))
+            parts["psy_rest"] += rest(*W.allocate_rd(sfi, bits, dist, tail, fb, offsets=off), more=("o", "O", "mu"))
+            parts["psy_host"] += list(at3p_host_allocate_psy(sfi, bits, dist, tail, fb, offsets=off))
+            if i % 4 == 0:
+                parts["m_rest"] += rest(*W.allocate_rd(sfi, bits, dist, tail, fb, psy=True), more=("o", "O", "mu"))
+                parts["m_host"] += list(at3p_host_allocate_psy(sfi, bits, dist, tail, fb))
+        for k, v in parts.items():
+            out[f"t{g // 100:02d}_{k}"] = W.sha(*v)
+    for name, nch, fb in CELLS:
+        sp = W.specs_of(name, nch, 3)
+        out[f"{name}_{nch}_{fb}_in"] = W.sha(sp.view(np.uint32))
+        for mode in ("rd", "psy"):
+            frames, rec, nbits = W.write_rd(sp, fb, info=True, psy=mode == "psy")
+            out[f"{name}_{nch}_{fb}_{mode}"] = W.sha(frames, nbits, *[rec[f] for f in ("j", "k", "num_quant_units", "bits", "chose", "t", "k_sparse", "O", "T",
+                                                                                     "T_sparse", "o", "mu", "wl", "sfi", "tab")])
+    return out
+
+
+def rd_fold_file_arrays():
+    e = rd_fold_entries()
+    return {"labels": np.array(list(e)), "sha256": np.stack(list(e.values()))}

@@ -35,9 +35,11 @@ T_MIN, T_MAX, K_MAX = -21, 63, 64
 J_MIN, J_MAX = -30, 69
 INFO_DTYPE = np.dtype([("t", "<i4"), ("k", "<i4"), ("num_quant_units", "<i4"), ("bits", "<i4"), ("wl", "u1", (2, 32)), ("sfi", "u1", (2, 32)),
                        ("tab", "u1", (2, 32))])
-RD_INFO_DTYPE = np.dtype([("j", "<i4"), ("k", "<i4"), ("num_quant_units", "<i4"), ("bits", "<i4"), ("chose_rd", "<i4"), ("t", "<i4"),
-                          ("k_sparse", "<i4"), ("pad", "<i4"), ("T_rd", "<f8"), ("T_sparse", "<f8"), ("wl", "u1", (2, 32)), ("sfi", "u1", (2, 32)),
-                          ("tab", "u1", (2, 32))])
+# rate-distortion and masking-weighted frames: chose, T and T_sparse are the guard's outcome and its two sums (T of R4, Tw of M6); O, o and
+# mu are M3's and M2's, zero for rate-distortion frames
+RD_INFO_DTYPE = np.dtype([("j", "<i4"), ("k", "<i4"), ("num_quant_units", "<i4"), ("bits", "<i4"), ("chose", "<i4"), ("t", "<i4"),
+                          ("k_sparse", "<i4"), ("O", "<i4"), ("T", "<f8"), ("T_sparse", "<f8"), ("o", "u1", (2, 32)), ("mu", "<i4", (2, 32)),
+                          ("wl", "u1", (2, 32)), ("sfi", "u1", (2, 32)), ("tab", "u1", (2, 32))])
 SIGNALS = ("noise", "mix", "stress", "tones", "burst")
 SNR_FRAMES = 14
 QU_START = [0, 16, 32, 48, 64, 80, 96, 112, 128, 160, 192, 224, 256, 288, 320, 352, 384, 448, 512, 576, 640, 704, 768, 896, 1024, 1152, 1280, 1408,
@@ -71,8 +73,8 @@ def writer_lib():
     lib.at3pw_allocate.argtypes = [P, P, I, I, I, I, P, P, P, P]
     lib.at3pw_cost_table.argtypes = [P, I, P, P, P, P]
     lib.at3prd_tables.argtypes = [P, I, P, P, P, P, P]
-    lib.at3prd_allocate.argtypes = [P, P, P, I, I, I, P, P, P]
-    lib.at3prd_write_frames.argtypes = [P, I, I, I, P, P, P, P]
+    lib.at3prd_allocate.argtypes = [P, P, P, P, I, I, I, I, P, P, P]
+    lib.at3prd_write_frames.argtypes = [P, I, I, I, I, P, P, P, P]
     assert lib.at3pw_frame_info_size() == INFO_DTYPE.itemsize and lib.at3prd_frame_info_size() == RD_INFO_DTYPE.itemsize
     assert (lib.at3prd_j_min(), lib.at3prd_j_max()) == (J_MIN, J_MAX)
     return lib
@@ -134,11 +136,11 @@ def write_adaptive(specs, frame_bytes=2048, sparse=False, win=None, blocks=None,
                                                                                          out, rec), INFO_DTYPE, specs, frame_bytes, win, blocks, info)
 
 
-def write_rd(specs, frame_bytes, win=None, blocks=None, info=False):
-    """the same with RATE-DISTORTION WORD LENGTHS (sparse frames; records of RD_INFO_DTYPE: j*, k*, which of the two allocations was
-    written, both T)"""
-    return _write(lambda lib, sp, nch, n, tails, nbits, out, rec: lib.at3prd_write_frames(sp, nch, n, int(frame_bytes), tails, nbits, out, rec),
-                  RD_INFO_DTYPE, specs, frame_bytes, win, blocks, info)
+def write_rd(specs, frame_bytes, win=None, blocks=None, info=False, psy=False):
+    """the same with RATE-DISTORTION WORD LENGTHS, or with psy MASKING-WEIGHTED WORD LENGTHS (sparse frames; records of RD_INFO_DTYPE: j*,
+    k*, which of the two allocations was written, both T, and with psy the offsets)"""
+    return _write(lambda lib, sp, nch, n, tails, nbits, out, rec: lib.at3prd_write_frames(sp, nch, n, int(frame_bytes), int(bool(psy)), tails, nbits,
+                                                                                          out, rec), RD_INFO_DTYPE, specs, frame_bytes, win, blocks, info)
 
 
 def write_streams(specs, frame_bytes=2048, sparse=False, win=None, blocks=None):
@@ -178,12 +180,15 @@ def allocate(sfi, bits, tail_bits, frame_bytes=2048, sparse=False):
     return wl, int(out[0]), int(out[1]), int(out[2]), int(total)
 
 
-def allocate_rd(sfi, bits, dist, tail_bits, frame_bytes):
-    """R2-R4 of the restatement: (wl uint8 [C, 32], N, record of RD_INFO_DTYPE with j, k, chose_rd, t, k_sparse, T_rd, T_sparse, bits)"""
+def allocate_rd(sfi, bits, dist, tail_bits, frame_bytes, offsets=None, psy=False):
+    """R2-R4 of the restatement, or M1-M6 with psy or with offsets uint8 [C, 32], which replace M1-M3's: (wl uint8 [C, 32], N, record of
+    RD_INFO_DTYPE with j, k, chose, t, k_sparse, O, T, T_sparse, o, mu, bits)"""
     sfi, bits, dist = np.ascontiguousarray(sfi, np.uint8), np.ascontiguousarray(bits, np.uint16), np.ascontiguousarray(dist, np.uint64)
     nch = sfi.shape[0]
+    off = None if offsets is None else np.ascontiguousarray(offsets, np.uint8)
     wl, n, rec = np.zeros((nch, 32), np.uint8), np.zeros(1, np.int32), np.zeros(1, RD_INFO_DTYPE)
-    rec["bits"] = writer_lib().at3prd_allocate(_vp(sfi), _vp(bits), _vp(dist), nch, int(tail_bits), int(frame_bytes), _vp(wl), _vp(n), _vp(rec))
+    rec["bits"] = writer_lib().at3prd_allocate(_vp(sfi), _vp(bits), _vp(dist), None if off is None else _vp(off), int(bool(psy)), nch, int(tail_bits),
+                                               int(frame_bytes), _vp(wl), _vp(n), _vp(rec))
     return wl, int(n[0]), rec[0]
 
 
@@ -684,8 +689,8 @@ def rd_golden_entry(name, nch, fb):
     """the rate-distortion restatement on 3 frames of a signal: {frames uint8 [3, fb], choice int32 [3, 4] (j*, k*, N, chose_rd),
     wl uint8 [3, 2, 32], T float64 [3, 2] (T(R), T(A))}"""
     frames, rec, _ = write_rd(specs_of(name, nch, RD_GOLDEN_FRAMES), fb, info=True)
-    return {"frames": frames, "choice": np.stack([rec["j"], rec["k"], rec["num_quant_units"], rec["chose_rd"]], axis=1).astype(np.int32),
-            "wl": rec["wl"], "T": np.stack([rec["T_rd"], rec["T_sparse"]], axis=1)}
+    return {"frames": frames, "choice": np.stack([rec["j"], rec["k"], rec["num_quant_units"], rec["chose"]], axis=1).astype(np.int32),
+            "wl": rec["wl"], "T": np.stack([rec["T"], rec["T_sparse"]], axis=1)}
 
 
 # ---- at3p_writer_fold.npz: what the six restatements gave before they were folded into one (DESIGN.md, section 22.1) ----------------
@@ -697,6 +702,21 @@ def sha(*parts):
         h.update(f"{a.dtype.str}{a.shape}".encode())
         h.update(a.tobytes())
     return np.frombuffer(h.digest(), np.uint8)
+
+
+_RD_INFO_22 = np.dtype([("j", "<i4"), ("k", "<i4"), ("num_quant_units", "<i4"), ("bits", "<i4"), ("chose_rd", "<i4"), ("t", "<i4"),
+                        ("k_sparse", "<i4"), ("pad", "<i4"), ("T_rd", "<f8"), ("T_sparse", "<f8"), ("wl", "u1", (2, 32)), ("sfi", "u1", (2, 32)),
+                        ("tab", "u1", (2, 32))])
+
+
+def _rd_info_bytes_22(rec):
+    """the bytes of rate-distortion records in the layout they had when at3p_writer_fold.npz was written, whose digests are of those bytes"""
+    rec = np.asarray(rec)
+    old = np.zeros(rec.shape, _RD_INFO_22)
+    for name in _RD_INFO_22.names:
+        if name != "pad":
+            old[name] = rec[{"chose_rd": "chose", "T_rd": "T"}.get(name, name)]
+    return old.reshape(-1).view(np.uint8)
 
 
 def fold_inputs(nch):
@@ -754,7 +774,8 @@ def fold_entries(nch, part="abcd"):
         for fb in (MIN_BYTES[nch], 2048):
             for name, (frames, rec, _) in (("sparse", write_adaptive(sp, fb, True, None, blocks, info=True)),
                                            ("rd", write_rd(sp, fb, None, blocks, info=True))):
-                out[f"d_specs_{name}_{fb}_frames"], out[f"d_specs_{name}_{fb}_info"] = sha(frames), sha(rec.view(np.uint8))
+                out[f"d_specs_{name}_{fb}_frames"] = sha(frames)
+                out[f"d_specs_{name}_{fb}_info"] = sha(rec.view(np.uint8) if name == "sparse" else _rd_info_bytes_22(rec))
         for fb in (MIN_BYTES[nch], 376):                # (at 2048 bytes a stereo frame of `mix` has no clone flag to clear)
             bad = crafted_frames(nch, fb)
             out[f"d_crafted_{fb}_in"] = sha(bad)
@@ -767,7 +788,7 @@ def fold_entries(nch, part="abcd"):
         sfi, bits, dist, tail, fb = guard_table()
         if nch == 1:
             wl, N, rec = allocate_rd(sfi, bits, dist, tail, fb)
-            out["d_guard_in"], out["d_guard"] = sha(sfi, bits, dist, tail, fb), sha(wl, N, np.array(rec).reshape(1).view(np.uint8))
+            out["d_guard_in"], out["d_guard"] = sha(sfi, bits, dist, tail, fb), sha(wl, N, _rd_info_bytes_22(rec))
     return out
 
 

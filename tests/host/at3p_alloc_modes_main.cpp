@@ -1,11 +1,13 @@
 // Builds of the ATRAC3plus engine that lack some or all of the adaptive writer's translation units: at3phip.hip reaches their
 // launches through weak symbols, so such a build links, and a call whose flags need a missing unit is AT3HIP_EINVAL with an error
 // that says so - never another writer's frames in the flag's place - and neither writes a byte nor moves the context's state.
-// The argument, none | alloc | alloc+sparse | all, names the units the program was linked with: none, at3p_alloc.hip, that and
-// at3p_sparse.hip, those and at3p_rd.hip. Mono and stereo, the context's size at 2048 and at 376 bytes, each of the eight
-// combinations of the three allocation flags: all six frame-writing calls against kWriter, and at3phip_decode with
-// AT3PHIP_DECODE_SPARSE against kDecoder. The tables are data, printed by --print from the engine as it stood before the mode was
-// resolved in one place (DESIGN.md 22.2 has the procedure), and not derived here from the rule they test.
+// The argument, none | alloc | alloc+sparse | alloc+sparse+rd | all, names the units the program was linked with: none, at3p_alloc.hip,
+// that and at3p_sparse.hip, those and at3p_rd.hip, those and at3p_psy.hip. Mono and stereo, the context's size at 2048 and at 376
+// bytes, each of the sixteen combinations of the four allocation flags: all six frame-writing calls against kWriter, and
+// at3phip_decode with AT3PHIP_DECODE_SPARSE against kDecoder; at3phip_host_allocate_rd and at3phip_host_allocate_psy, the symbols by
+// which a host detects the two newer flags, are there exactly when their units are. The tables are data, printed by --print from the
+// engine as it stood before the mode was resolved in one place, and for AT3PHIP_ALLOC_PSY before this program took the flag (DESIGN.md
+// 22.2 and 24.1 have the procedure), and not derived here from the rule they test.
 // Built and run by tests/simt_harness_lib.py's run_alloc_modes: the engine compiled for the host with tools/emu's runtime.
 #include <cstdio>
 #include <cstring>
@@ -13,10 +15,15 @@
 
 #include "../../include/at3phip.h"
 
+extern "C" __attribute__((weak)) int at3phip_host_allocate_rd(const uint8_t*, const uint16_t*, const uint64_t*, int32_t, int32_t, int32_t, uint8_t*, int32_t*,
+                                                              int32_t*, int32_t*, int32_t*);
+extern "C" __attribute__((weak)) int at3phip_host_allocate_psy(const uint8_t*, const uint16_t*, const uint64_t*, const uint8_t*, int32_t, int32_t, int32_t,
+                                                               uint8_t*, int32_t*, int32_t*, int32_t*, int32_t*, uint8_t*);
+
 static int fails = 0;
 #define CHECK(x) do { if (!(x)) { std::printf("FAILED line %d: %s\n", __LINE__, #x); ++fails; } } while (0)
 
-static const char* const kConfigs[4] = {"none", "alloc", "alloc+sparse", "all"};
+static const char* const kConfigs[5] = {"none", "alloc", "alloc+sparse", "alloc+sparse+rd", "all"};
 static const int kSizes[2] = {AT3PHIP_FRAME_BYTES, 376};
 static const char* const kCalls[6] = {"write_frames", "write_frames_tonal", "encode_frames", "encode_frames_short", "encode_frames_tonal",
                                       "encode_frames_tonal_short"};
@@ -32,26 +39,41 @@ static const Expect kNoSparse = {AT3HIP_EINVAL, "no sparse writer (at3p_alloc.hi
 static const Expect kNoRd = {AT3HIP_EINVAL, "no rate-distortion writer (at3p_rd.hip)"};
 static const Expect kSparseAlone = {AT3HIP_EINVAL, "AT3PHIP_ALLOC_SPARSE needs AT3PHIP_ALLOC_ADAPTIVE in the same call"};
 static const Expect kRdAlone = {AT3HIP_EINVAL, "AT3PHIP_ALLOC_RD needs AT3PHIP_ALLOC_ADAPTIVE and AT3PHIP_ALLOC_SPARSE in the same call"};
+static const Expect kPsyAlone = {AT3HIP_EINVAL, "AT3PHIP_ALLOC_PSY needs AT3PHIP_ALLOC_ADAPTIVE, AT3PHIP_ALLOC_SPARSE and AT3PHIP_ALLOC_RD in the same call"};
+static const Expect kNoPsy = {AT3HIP_EINVAL, "AT3PHIP_ALLOC_PSY: this build has no masking-weighted writer (at3p_psy.hip)"};
 static const Expect kNoUnpack = {AT3HIP_EINVAL, "no sparse unpack kernels (at3p_sparse.hip)"};
 
-// [units][size][flags]: flags' bit 0 = AT3PHIP_ALLOC_ADAPTIVE, bit 1 = AT3PHIP_ALLOC_SPARSE, bit 2 = AT3PHIP_ALLOC_RD; the same for
-// all six calls and for mono and stereo
-static const Expect kWriter[4][2][8] = {
-    {{kOk, kNoAdaptive, kSparseAlone, kNoSparse, kRdAlone, kRdAlone, kRdAlone, kNoRd},
-     {kFixed, kNoAdaptive, kFixed, kNoAdaptive, kFixed, kNoAdaptive, kFixed, kNoAdaptive}},
-    {{kOk, kOk, kSparseAlone, kNoSparse, kRdAlone, kRdAlone, kRdAlone, kNoRd},
-     {kFixed, kOk, kFixed, kNoSparse, kFixed, kRdAlone, kFixed, kNoRd}},
-    {{kOk, kOk, kSparseAlone, kOk, kRdAlone, kRdAlone, kRdAlone, kNoRd},
-     {kFixed, kOk, kFixed, kOk, kFixed, kRdAlone, kFixed, kNoRd}},
-    {{kOk, kOk, kSparseAlone, kOk, kRdAlone, kRdAlone, kRdAlone, kOk},
-     {kFixed, kOk, kFixed, kOk, kFixed, kRdAlone, kFixed, kOk}},
+// [units][size][flags]: flags' bit 0 = AT3PHIP_ALLOC_ADAPTIVE, bit 1 = AT3PHIP_ALLOC_SPARSE, bit 2 = AT3PHIP_ALLOC_RD, bit 3 =
+// AT3PHIP_ALLOC_PSY; the same for all six calls and for mono and stereo
+static const Expect kWriter[5][2][16] = {
+    {{kOk, kNoAdaptive, kSparseAlone, kNoSparse, kRdAlone, kRdAlone, kRdAlone, kNoRd,
+      kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kNoPsy},
+     {kFixed, kNoAdaptive, kFixed, kNoAdaptive, kFixed, kNoAdaptive, kFixed, kNoAdaptive,
+      kFixed, kNoAdaptive, kFixed, kNoAdaptive, kFixed, kNoAdaptive, kFixed, kNoAdaptive}},
+    {{kOk, kOk, kSparseAlone, kNoSparse, kRdAlone, kRdAlone, kRdAlone, kNoRd,
+      kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kNoPsy},
+     {kFixed, kOk, kFixed, kNoSparse, kFixed, kRdAlone, kFixed, kNoRd,
+      kFixed, kPsyAlone, kFixed, kPsyAlone, kFixed, kPsyAlone, kFixed, kNoPsy}},
+    {{kOk, kOk, kSparseAlone, kOk, kRdAlone, kRdAlone, kRdAlone, kNoRd,
+      kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kNoPsy},
+     {kFixed, kOk, kFixed, kOk, kFixed, kRdAlone, kFixed, kNoRd,
+      kFixed, kPsyAlone, kFixed, kPsyAlone, kFixed, kPsyAlone, kFixed, kNoPsy}},
+    {{kOk, kOk, kSparseAlone, kOk, kRdAlone, kRdAlone, kRdAlone, kOk,
+      kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kNoPsy},
+     {kFixed, kOk, kFixed, kOk, kFixed, kRdAlone, kFixed, kOk,
+      kFixed, kPsyAlone, kFixed, kPsyAlone, kFixed, kPsyAlone, kFixed, kNoPsy}},
+    {{kOk, kOk, kSparseAlone, kOk, kRdAlone, kRdAlone, kRdAlone, kOk,
+      kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kPsyAlone, kOk},
+     {kFixed, kOk, kFixed, kOk, kFixed, kRdAlone, kFixed, kOk,
+      kFixed, kPsyAlone, kFixed, kPsyAlone, kFixed, kPsyAlone, kFixed, kOk}},
 };
 // [units]: at3phip_decode with AT3PHIP_DECODE_SPARSE, at both sizes
-static const Expect kDecoder[4] = {kNoUnpack, kNoUnpack, kOk, kOk};
+static const Expect kDecoder[5] = {kNoUnpack, kNoUnpack, kOk, kOk, kOk};
 
 static uint32_t alloc_flags(int bits)
 {
-    return (bits & 1 ? AT3PHIP_ALLOC_ADAPTIVE : 0u) | (bits & 2 ? AT3PHIP_ALLOC_SPARSE : 0u) | (bits & 4 ? AT3PHIP_ALLOC_RD : 0u);
+    return (bits & 1 ? AT3PHIP_ALLOC_ADAPTIVE : 0u) | (bits & 2 ? AT3PHIP_ALLOC_SPARSE : 0u) | (bits & 4 ? AT3PHIP_ALLOC_RD : 0u) |
+           (bits & 8 ? AT3PHIP_ALLOC_PSY : 0u);
 }
 
 struct Input {
@@ -93,10 +115,12 @@ static at3phip_ctx* create(int channels)
 int main(int argc, char** argv)
 {
     int units = -1;
-    for (int i = 0; i < 4 && argc > 1; ++i)
+    for (int i = 0; i < 5 && argc > 1; ++i)
         if (!std::strcmp(argv[1], kConfigs[i])) units = i;
     const bool print = argc > 2 && !std::strcmp(argv[2], "--print");
-    if (units < 0) return std::printf("usage: %s none|alloc|alloc+sparse|all [--print]\n", argv[0]), 2;
+    if (units < 0) return std::printf("usage: %s none|alloc|alloc+sparse|alloc+sparse+rd|all [--print]\n", argv[0]), 2;
+    CHECK((at3phip_host_allocate_rd != nullptr) == (units >= 3));    // the symbols by which a host detects the flags
+    CHECK((at3phip_host_allocate_psy != nullptr) == (units == 4));
     for (int channels = 1; channels <= 2; ++channels) {
         // `refusing` receives the calls the table refuses, and nothing else but the setter; `accepting` the others
         at3phip_ctx *refusing = create(channels), *accepting = create(channels), *fresh = create(channels);
@@ -110,7 +134,7 @@ int main(int argc, char** argv)
                 CHECK(at3phip_set_frame_bytes(c, kSizes[size]) == AT3HIP_OK);
                 CHECK(at3phip_get_frame_bytes(c, &fb) == AT3HIP_OK && fb == kSizes[size]);
             }
-            for (int bits = 0; bits < 8; ++bits)
+            for (int bits = 0; bits < 16; ++bits)
                 for (int which = 0; which < 6; ++which) {
                     const Expect& e = kWriter[units][size][bits];
                     at3phip_ctx* c = e.rc == AT3HIP_OK ? accepting : refusing;

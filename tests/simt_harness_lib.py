@@ -67,7 +67,8 @@ def assert_clean(out, min_cases):
 
 
 ALLOC_MODE_UNITS = {"none": (), "alloc": ("at3p_alloc.hip",), "alloc+sparse": ("at3p_alloc.hip", "at3p_sparse.hip"),
-                    "all": ("at3p_alloc.hip", "at3p_sparse.hip", "at3p_rd.hip")}
+                    "alloc+sparse+rd": ("at3p_alloc.hip", "at3p_sparse.hip", "at3p_rd.hip"),
+                    "all": ("at3p_alloc.hip", "at3p_sparse.hip", "at3p_rd.hip", "at3p_psy.hip")}
 
 
 _alloc_modes = {}

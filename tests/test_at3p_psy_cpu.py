@@ -1,5 +1,5 @@
 """ATRAC3plus masking-weighted word lengths without a GPU (include/at3phip.h, MASKING-WEIGHTED WORD LENGTHS): the restatement
-tests/host/at3p_psy_cpu.c against its golden file, with the guard's property recomputed on every frame; at3phip_host_allocate_psy against
+tests/host/at3p_rd_cpu.c with psy against its golden file, with the guard's property recomputed on every frame; at3phip_host_allocate_psy against
 the restatement on the signals' tables and on random tables with random offsets; zero offsets give the rate-distortion choice; the masked
 twin, the one test of behaviour; the definition's edges; the table generator; the argument checks; every frame parsed, recounted and
 decoded as the sparse frame it is; and, where the reference is built, its own part coders under the chosen allocation."""
@@ -18,10 +18,8 @@ import at3p_writer_lib as W
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "at3phip.h")).read()
 needs_ref = pytest.mark.skipif(not P.have_ref(), reason="oracle/_ref not built")
-SIZES = {1: (176, 376, 744, 2048), 2: (224, 376, 744, 2048)}
 N_FRAMES = 3
-SIGNALS = ("noise", "tones", "mix", "burst")
-CELLS = [(name, nch, fb) for name in SIGNALS for nch in (1, 2) for fb in SIZES[nch]]
+CELLS = Y.CELLS
 
 _cache = {}
 
@@ -35,30 +33,20 @@ def _written(name, nch, fb):
     return _cache[key]
 
 
-_rand = []
-
-
-def _random_tables():
-    """2000 x (sfi, bits, dist, tail_bits, offsets, frame_bytes)"""
-    if not _rand:
-        tabs = W.random_dist_tables(W.random_cost_tables(2000))
-        for i, ((sfi, bits, dist, tail), off) in enumerate(zip(tabs, Y.random_offsets(tabs))):
-            fb = SIZES[sfi.shape[0]][i % 4]
-            _rand.append((sfi, bits, dist, min(tail, 8 * fb - 3), off, fb))
-    return _rand
+_random_tables = Y.random_tables
 
 
 def _same(host, wl, N, rec):
     hw, hN, hj, hk, hp, ho = host
     nch = hw.shape[0]
-    return (np.array_equal(hw, wl) and (hN, hj, hk, hp) == (N, int(rec["j"]), int(rec["k"]), bool(rec["chose_psy"]))
+    return (np.array_equal(hw, wl) and (hN, hj, hk, hp) == (N, int(rec["j"]), int(rec["k"]), bool(rec["chose"]))
             and np.array_equal(ho, rec["o"][:nch]))
 
 
 # ---- 1. golden -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,nch,fb", Y.PSY_GOLDEN_CASES, ids=[f"{n}_{c}_{fb}" for n, c, fb in Y.PSY_GOLDEN_CASES])
 def test_restatement_equals_the_golden_file(name, nch, fb):
-    """tests/golden/at3p_psy.npz (tools/gen_golden_at3p_psy.py): frames, j*, k*, N, the guard's outcome, O, the offsets, word lengths and
+    """tests/golden/at3p_psy.npz (tools/gen_golden_at3p_rd.py --mode psy): frames, j*, k*, N, the guard's outcome, O, the offsets, word lengths and
     both Tw, bit for bit; and on each of its frames the guard's property, Tw recomputed here from the tables and the offsets, themselves
     recomputed here from M1-M3's text: the written allocation's never exceeds the sparse allocation's"""
     gold = np.load(Y.PSY_GOLDEN)
@@ -114,7 +102,7 @@ def test_guard_property_and_host_function_on_2000_random_tables_with_random_offs
         wl_a = at3p_host_allocate(sfi, bits, tail, frame_bytes=fb, sparse=True)[0]
         t_w, t_a = Y.weighted_total(sfi, dist, host[0], off), Y.weighted_total(sfi, dist, wl_a, off)
         assert t_w <= t_a, i
-        assert t_a == r["Tw_sparse"] and (t_w == r["Tw_psy"] if host[4] else np.array_equal(host[0], wl_a)), i
+        assert t_a == r["T_sparse"] and (t_w == r["T"] if host[4] else np.array_equal(host[0], wl_a)), i
         assert W.J_MIN - int(off.max()) <= host[2] <= W.J_MAX
         fell += not host[4]
     assert 0 < fell < 2000
@@ -140,8 +128,8 @@ def test_zero_offsets_give_the_rate_distortion_choice():
         assert np.array_equal(got[0], want[0]) and got[1:5] == want[1:5] and not got[5].any(), i
         wl, N, r = Y.allocate_psy(sfi, bits, dist, tail, fb, np.zeros(sfi.shape, np.uint8))
         wr, Nr, rr = W.allocate_rd(sfi, bits, dist, tail, fb)
-        assert np.array_equal(wl, wr) and N == Nr and (r["j"], r["k"], r["chose_psy"], r["Tw_psy"], r["Tw_sparse"]) == (
-            rr["j"], rr["k"], rr["chose_rd"], rr["T_rd"], rr["T_sparse"]), i
+        assert np.array_equal(wl, wr) and N == Nr and (r["j"], r["k"], r["chose"], r["T"], r["T_sparse"]) == (
+            rr["j"], rr["k"], rr["chose"], rr["T"], rr["T_sparse"]), i
 
 
 # ---- 4. the masked twin --------------------------------------------------------------------------------------------------------------------
@@ -162,7 +150,7 @@ def test_the_masked_twin_gets_fewer_bits_than_its_unmasked_copy():
         found += 1
         wp, N, r = Y.allocate_psy(sfi, bits, dist, tail, 176)
         print(f"tail {tail}: rd {wr[0, [1, 2, 7]].tolist()} psy {wp[0, [1, 2, 7]].tolist()} o {r['o'][0, [1, 2, 7]].tolist()}")
-        assert wp[0, 2] < wp[0, 7] and r["o"][0, 2] > r["o"][0, 7] and r["chose_psy"] == 1, tail
+        assert wp[0, 2] < wp[0, 7] and r["o"][0, 2] > r["o"][0, 7] and r["chose"] == 1, tail
         assert _same(at3p_host_allocate_psy(sfi, bits, dist, tail, 176), wp, N, r)
     assert found >= 2
 

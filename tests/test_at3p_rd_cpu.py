@@ -64,10 +64,35 @@ def test_golden_file_holds_what_it_should():
     assert (chose == 1).sum() >= 6 and (chose == 0).sum() >= 3   # both outcomes of the guard
 
 
+def test_restatement_and_host_functions_equal_what_they_gave_before_the_fold():
+    """tests/golden/at3p_rd_fold.npz, written before the rate-distortion and the masking-weighted stack became one (DESIGN.md, section
+    24.1): on at3p_psy_lib.random_tables in hundreds and on the signals' cells, every named field of the restatement and of
+    at3phip_host_allocate_rd and at3phip_host_allocate_psy - rate-distortion, masking-weighted with the offsets given and with M1-M3's -
+    and the frames of write_rd and write_psy, digest for digest; the inputs' digests among them"""
+    import at3p_psy_lib as Y
+    gold = np.load(Y.RD_FOLD_GOLDEN)
+    want = dict(zip(gold["labels"].tolist(), gold["sha256"]))
+    got = Y.rd_fold_entries()
+    assert list(got) == list(want)
+    differ = [k for k in got if not np.array_equal(got[k], want[k])]
+    assert not differ, differ
+
+
+def test_fold_golden_file_holds_what_it_should():
+    import at3p_psy_lib as Y
+    gold = np.load(Y.RD_FOLD_GOLDEN)
+    assert sorted(gold.files) == ["labels", "sha256"] and os.path.getsize(Y.RD_FOLD_GOLDEN) < 64 * 1024
+    labels = [f"t{g:02d}_{k}" for g in range(20) for k in ("in", "rd_rest", "rd_host", "psy_rest", "psy_host", "m_rest", "m_host")]
+    labels += [f"{n}_{c}_{fb}_{k}" for n, c, fb in Y.CELLS for k in ("in", "rd", "psy")]
+    assert gold["labels"].tolist() == labels and gold["sha256"].shape == (len(labels), 32) and gold["sha256"].dtype == np.uint8
+    # (a cell's spectra do not depend on its frame size: the 32 cells' `in` digests are 8 different ones; all others differ)
+    assert len({bytes(d) for d in gold["sha256"]}) == len(labels) - 24
+
+
 # ---- 2. the host function, the guard ---------------------------------------------------------------------------------------------------
 def _same(host, wl, N, rec):
     hw, hN, hj, hk, hrd = host
-    return np.array_equal(hw, wl) and (hN, hj, hk, hrd) == (N, int(rec["j"]), int(rec["k"]), bool(rec["chose_rd"]))
+    return np.array_equal(hw, wl) and (hN, hj, hk, hrd) == (N, int(rec["j"]), int(rec["k"]), bool(rec["chose"]))
 
 
 def test_host_allocate_rd_equals_the_restatement_on_the_signals():
@@ -80,7 +105,7 @@ def test_host_allocate_rd_equals_the_restatement_on_the_signals():
             wl, N, r = W.allocate_rd(sfi, bits, dist, nbits[f], fb)
             assert _same(at3p_host_allocate_rd(sfi, bits, dist, nbits[f], fb), wl, N, r), (name, nch, fb, f)
             assert np.array_equal(wl, rec["wl"][f][:nch]) and N == rec["num_quant_units"][f]
-            seen.add(int(r["chose_rd"]))
+            seen.add(int(r["chose"]))
     assert seen == {0, 1}   # R(j*, k*) and the fallback are both reached on the signals
 
 
@@ -99,7 +124,7 @@ def test_guard_property_and_host_function_on_2000_random_tables():
         wl_a = at3p_host_allocate(sfi, bits, tail, frame_bytes=fb, sparse=True)[0]
         t_w, t_a = W.total_distortion(sfi, dist, host[0]), W.total_distortion(sfi, dist, wl_a)
         assert t_w <= t_a, i
-        assert t_a == r["T_sparse"] and (t_w == r["T_rd"] if host[4] else np.array_equal(host[0], wl_a)), i
+        assert t_a == r["T_sparse"] and (t_w == r["T"] if host[4] else np.array_equal(host[0], wl_a)), i
         fell += not host[4]
     assert fell > 0
 
@@ -108,11 +133,11 @@ def test_the_guard_fires_on_the_table_built_for_it():
     from atracdenc_amd.binding import at3p_host_allocate, at3p_host_allocate_rd
     sfi, bits, dist, tail, fb = W.guard_table()
     wl, N, r = W.allocate_rd(sfi, bits, dist, tail, fb)
-    assert r["chose_rd"] == 0 and r["T_rd"] > r["T_sparse"] and wl[0, 0] == 3 and not wl[0, 1:].any() and N == 1
+    assert r["chose"] == 0 and r["T"] > r["T_sparse"] and wl[0, 0] == 3 and not wl[0, 1:].any() and N == 1
     assert _same(at3p_host_allocate_rd(sfi, bits, dist, tail, fb), wl, N, r)
     assert np.array_equal(wl, at3p_host_allocate(sfi, bits, tail, frame_bytes=fb, sparse=True)[0])
     # R(j*, k*) itself: the empty frame, whose closing rule gives unit 0 word length 1
-    assert r["T_rd"] == W.total_distortion(sfi, dist, np.eye(1, 32, dtype=np.uint8))
+    assert r["T"] == W.total_distortion(sfi, dist, np.eye(1, 32, dtype=np.uint8))
 
 
 def test_host_allocate_rd_checks_its_arguments():
@@ -131,7 +156,7 @@ def test_a_frame_that_fits_with_every_word_length_7_is_the_sparse_frame():
     AT3PHIP_ALLOC_SPARSE writes (and AT3PHIP_ALLOC_ADAPTIVE alone)"""
     sp = W.quiet_mono(2)
     frames, rec, _ = W.write_rd(sp, 2048, info=True)
-    assert (rec["j"] == W.J_MIN).all() and (rec["t"] == W.T_MIN).all() and (rec["wl"][:, 0] == 7).all() and (rec["chose_rd"] == 1).all()
+    assert (rec["j"] == W.J_MIN).all() and (rec["t"] == W.T_MIN).all() and (rec["wl"][:, 0] == 7).all() and (rec["chose"] == 1).all()
     assert np.array_equal(frames, W.write_adaptive(sp, 2048, True)) and np.array_equal(frames, W.write_adaptive(sp, 2048, False))
 
 

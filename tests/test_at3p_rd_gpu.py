@@ -1,11 +1,13 @@
-"""ATRAC3plus rate-distortion word lengths on the GPU (AT3PHIP_ALLOC_RD; include/at3phip.h, RATE-DISTORTION WORD LENGTHS): the six
-frame-writing calls with ADAPTIVE | SPARSE | RD equal the restatement tests/host/at3p_rd_cpu.c byte for byte - host and device
-buffers, queued and waiting, however the stream is split, whatever the calls before carried -; non-finite spectra in one stream
-leave the others alone; RD without ADAPTIVE and SPARSE is refused and moves nothing; the frames decode on the GPU decoder with every
-counter zero. 3 streams x 3 frames; what does not depend on the frame size (spectra, tone analysis) is computed once."""
+"""ATRAC3plus rate-distortion and masking-weighted word lengths on the GPU (AT3PHIP_ALLOC_RD, AT3PHIP_ALLOC_PSY; include/at3phip.h,
+RATE-DISTORTION WORD LENGTHS and MASKING-WEIGHTED WORD LENGTHS), every test once per mode: the six frame-writing calls with ADAPTIVE |
+SPARSE | RD (| PSY) equal the restatement tests/host/at3p_rd_cpu.c byte for byte - host and device buffers, queued and waiting, however
+the stream is split, whatever the calls before carried -; non-finite spectra in one stream leave the others alone; the mode's flag
+without the flags it needs is refused and moves nothing; the frames decode on the GPU decoder with every counter zero. 3 streams x 3
+frames; what does not depend on the frame size (spectra, tone analysis) is computed once."""
 import numpy as np
 import pytest
 
+import at3p_psy_lib as Y
 import at3p_writer_lib as W
 import at3p_gha_lib as G
 import at3p_tonal_write_lib as TW
@@ -13,10 +15,38 @@ from at3_testlib import at3p_mdct, at3p_pqf
 
 pytestmark = pytest.mark.gpu
 S, F = 3, 3
-CASES = [(1, 176), (1, 376), (1, 744), (1, 2048), (2, 224), (2, 376), (2, 744), (2, 2048)]
-IDS = [f"{'mono' if nch == 1 else 'stereo'}_{fb}" for nch, fb in CASES]
 SENTINEL = 0xA5
-KW = dict(adaptive=True, sparse=True, rd=True)
+MODES = ("rd", "psy")
+# per mode: the binding's keywords; the older mode that "switched between calls" and "frames differ from" compare with; the sizes of the
+# writer tests and of the decoder test; the flag's name, every flag set without all it needs, the refusal's text and the keyword sets the
+# binding itself refuses
+KWS = {"rd": dict(adaptive=True, sparse=True, rd=True), "psy": dict(adaptive=True, sparse=True, rd=True, psy=True)}
+OLDER_KW = {"rd": dict(adaptive=True, sparse=True), "psy": dict(adaptive=True, sparse=True, rd=True)}
+CASES = {"rd": [(1, 176), (1, 376), (1, 744), (1, 2048), (2, 224), (2, 376), (2, 744), (2, 2048)],
+         "psy": [(1, 176), (1, 376), (1, 2048), (2, 224), (2, 376), (2, 2048)]}
+DECODE_CASES = {"rd": [(1, 176), (2, 224), (2, 376), (2, 744)], "psy": [(1, 176), (2, 224), (2, 376)]}
+DEVICE_CASES = [(1, 176), (2, 376), (2, 2048)]
+FLAG = {"rd": "AT3PHIP_ALLOC_RD", "psy": "AT3PHIP_ALLOC_PSY"}
+LACKING = {"rd": [(), ("ADAPTIVE",), ("SPARSE",)],
+           "psy": [(), ("ADAPTIVE",), ("SPARSE",), ("RD",), ("ADAPTIVE", "SPARSE"), ("ADAPTIVE", "RD"), ("SPARSE", "RD")]}
+REFUSAL = {"rd": "AT3PHIP_ALLOC_RD needs AT3PHIP_ALLOC_ADAPTIVE and AT3PHIP_ALLOC_SPARSE",
+           "psy": "AT3PHIP_ALLOC_PSY needs AT3PHIP_ALLOC_ADAPTIVE, AT3PHIP_ALLOC_SPARSE and AT3PHIP_ALLOC_RD"}
+BAD_KW = {"rd": (dict(rd=True), dict(adaptive=True, rd=True)), "psy": (dict(psy=True), dict(adaptive=True, sparse=True, psy=True))}
+
+
+def _id(mode, rest):
+    """a case's id: rd's are the ids this module had before it took a second mode, psy's carry the mode in front"""
+    return rest if mode == "rd" else f"{mode}-{rest}"
+
+
+def _per_mode(cases):
+    """parametrize("mode,nch,fb") over a list of (nch, fb), or one list per mode"""
+    rows = [(m, nch, fb) for m in MODES for nch, fb in (cases[m] if isinstance(cases, dict) else cases)]
+    return pytest.mark.parametrize("mode,nch,fb", rows, ids=[_id(m, f"{'mono' if nch == 1 else 'stereo'}_{fb}") for m, nch, fb in rows])
+
+
+_per_mode_and_channels = pytest.mark.parametrize("mode,nch", [(m, nch) for m in MODES for nch in (1, 2)],
+                                                 ids=[_id(m, str(nch)) for m in MODES for nch in (1, 2)])
 
 
 @pytest.fixture(scope="module")
@@ -80,16 +110,21 @@ def _wspecs(nch):
     return _memo(("wspecs", nch), lambda: np.stack([W.specs_of(n, nch, F) for n in ("noise", "mix", "tones")]))
 
 
-def _corner_specs(nch):
-    """stream 0: an all-zero spectrum, a single non-zero line, a full-scale spectrum; stream 1: full-scale noise; stream 2: one level"""
+def _corner_specs(mode, nch):
+    """stream 0: an all-zero spectrum, a single non-zero line, a full-scale spectrum; stream 1: full-scale noise; stream 2: three of
+    at3p_writer_lib.edge_specs' frames for rd, for psy two of them and then the masked twin (in the last channel)"""
     def make():
         sp = np.zeros((S, F, nch, 2048), np.float32)
         sp[0, 1, nch - 1, 777] = 0.3
         sp[0, 2] = np.where(np.random.default_rng(3).integers(0, 2, (nch, 2048)) > 0, 1.0, -1.0)
         sp[1] = W.full_scale_noise(F, nch)
-        sp[2] = W.edge_specs(nch)[0][1:4]
+        if mode == "rd":
+            sp[2] = W.edge_specs(nch)[0][1:4]
+        else:
+            sp[2, :2] = W.edge_specs(nch)[0][1:3]
+            sp[2, 2, nch - 1] = Y.masked_twin()[0, 0]
         return sp
-    return _memo(("corner", nch), make)
+    return _memo(("corner", mode, nch), make)
 
 
 def _records(nch):
@@ -97,18 +132,25 @@ def _records(nch):
     return [[TW.largest_block(nch), None, small], [None, TW.largest_block(nch), small], [None, small, None]]
 
 
-def _rd(specs, fb, blocks=None):
-    return np.stack([W.write_rd(specs[s], fb, None, None if blocks is None else blocks[s]) for s in range(specs.shape[0])])
+def _want(mode, specs, fb, blocks=None):
+    """the restatement's frames in the mode, [S, F, fb]; blocks [S][F] or None"""
+    return np.stack([W.write_rd(specs[s], fb, None, None if blocks is None else blocks[s], psy=mode == "psy") for s in range(specs.shape[0])])
+
+
+def _older(mode, specs, fb):
+    """the restatement's frames in the mode's older mode: sparse for rd, rd for psy"""
+    return W.write_streams(specs, fb, True) if mode == "rd" else _want("rd", specs, fb)
 
 
 # ---- the writers -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nch,fb", CASES, ids=IDS)
-def test_six_calls_equal_the_restatement(B, nch, fb):
+@_per_mode(CASES)
+def test_six_calls_equal_the_restatement(B, mode, nch, fb):
     """host buffers: at3phip_write_frames, at3phip_write_frames_tonal, at3phip_encode_frames(_short), at3phip_encode_frames_tonal(_short)
-    with gates and sharing; the corner spectra; and the frames are not the sparse writer's at the sizes where the budget binds"""
+    with gates and sharing; the corner spectra; and the frames are not the older mode's at the sizes where the budget binds"""
+    KW = KWS[mode]
     p16, pcm, specs = _plain(nch)
     t16, tpcm, tspecs, trecs = _tonal(nch)
-    wspecs, corner, blocks = _wspecs(nch), _corner_specs(nch), _records(nch)
+    wspecs, corner, blocks = _wspecs(nch), _corner_specs(mode, nch), _records(nch)
     recs = np.stack([B.pack_tonal_blocks(row, nch) for row in blocks])
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch, frame_bytes=fb)
     try:
@@ -125,23 +167,28 @@ def test_six_calls_equal_the_restatement(B, nch, fb):
         got_a16 = enc.encode_frames_tonal_s16(t16, gated=True, shared=True, **KW)
     finally:
         enc.close()
-    want_w = _rd(wspecs, fb)
+    want_w = _want(mode, wspecs, fb)
     assert np.array_equal(got_w, want_w)
-    assert np.array_equal(got_c, _rd(corner, fb))
-    assert np.array_equal(got_t, _rd(wspecs, fb, blocks))
-    assert np.array_equal(got_ct, _rd(corner, fb, blocks))
-    want_e = _rd(specs, fb)
+    assert np.array_equal(got_c, _want(mode, corner, fb))
+    assert np.array_equal(got_t, _want(mode, wspecs, fb, blocks))
+    assert np.array_equal(got_ct, _want(mode, corner, fb, blocks))
+    want_e = _want(mode, specs, fb)
     assert np.array_equal(got_e, want_e) and np.array_equal(got_e16, want_e)
-    want_a = np.stack([W.write_rd(tspecs[s], fb, None, trecs[s]) for s in range(S)])
+    want_a = _want(mode, tspecs, fb, trecs)
     assert np.array_equal(got_a, want_a) and np.array_equal(got_a16, want_a)
-    if fb < 2048:   # the flag matters at these sizes
-        assert not np.array_equal(want_w, W.write_streams(wspecs, fb, True))
+    if fb < 2048:   # the flag matters where the budget binds
+        older = _older(mode, wspecs, fb)
+        if mode == "rd":
+            assert not np.array_equal(want_w, older)
+        else:       # no stream's frames are the rate-distortion writer's
+            assert all(not np.array_equal(want_w[s], older[s]) for s in range(S))
 
 
-@pytest.mark.parametrize("nch,fb", CASES, ids=IDS)
-def test_a_nan_and_an_infinity_in_one_stream_leave_the_others_alone(B, nch, fb):
+@_per_mode(CASES)
+def test_a_nan_and_an_infinity_in_one_stream_leave_the_others_alone(B, mode, nch, fb):
     """stream 1 holds a NaN and an infinity (and, a frame on, at3p_writer_lib.odd_specs' whole units of them): every stream equals the
     restatement, and streams 0 and 2 equal their encode beside a clean stream 1"""
+    KW = KWS[mode]
     clean = _wspecs(nch)
     dirty = clean.copy()
     dirty[1, 0, 0, 100], dirty[1, 0, nch - 1, 1500] = np.nan, np.inf
@@ -151,21 +198,24 @@ def test_a_nan_and_an_infinity_in_one_stream_leave_the_others_alone(B, nch, fb):
         got, got_clean = enc.write_frames(dirty, **KW), enc.write_frames(clean, **KW)
     finally:
         enc.close()
-    assert np.array_equal(got, _rd(dirty, fb))
+    assert np.array_equal(got, _want(mode, dirty, fb))
     assert np.array_equal(got[0], got_clean[0]) and np.array_equal(got[2], got_clean[2]) and not np.array_equal(got[1], got_clean[1])
 
 
-@pytest.mark.parametrize("nch,fb", [(1, 176), (2, 376), (2, 2048)], ids=["mono_176", "stereo_376", "stereo_2048"])
-def test_device_buffers_queued_calls_splits_and_flag_switches(B, nch, fb):
+@_per_mode(DEVICE_CASES)
+def test_device_buffers_queued_calls_splits_and_flag_switches(B, mode, nch, fb):
     """device buffers waiting and queued equal host buffers; one call of 3 frames equals calls of 1 + 2; a stream that switches the
     flag between calls gets each call's own frames; the bytes behind every output stay"""
     import torch
     p16, pcm, specs = _plain(nch)
     t16, tpcm, tspecs, trecs = _tonal(nch)
-    want, want_sparse = _rd(specs, fb), W.write_streams(specs, fb, True)
-    t_want = np.stack([W.write_rd(tspecs[s], fb, None, trecs[s]) for s in range(S)])
+    KW = KWS[mode]
+    want, want_older = _want(mode, specs, fb), _older(mode, specs, fb)
+    t_want = _want(mode, tspecs, fb, trecs)
     n = S * F * fb
     DEV = B.AT3HIP_PCM_ON_DEVICE | B.AT3HIP_OUT_ON_DEVICE | B.AT3PHIP_ALLOC_ADAPTIVE | B.AT3PHIP_ALLOC_SPARSE | B.AT3PHIP_ALLOC_RD
+    if mode == "psy":
+        DEV |= B.AT3PHIP_ALLOC_PSY
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch, frame_bytes=fb)
     try:
         d_pcm, d_specs, d_t16 = torch.from_numpy(pcm).cuda(), torch.from_numpy(specs).cuda(), torch.from_numpy(t16).cuda()
@@ -187,7 +237,7 @@ def test_device_buffers_queued_calls_splits_and_flag_switches(B, nch, fb):
         t_parts = split(enc.encode_frames_tonal, tpcm, gated=True, shared=True, **KW)
         w_parts = np.concatenate([enc.write_frames(specs[:, :1], **KW), enc.write_frames(specs[:, 1:], **KW)], axis=1)
         enc.reset()
-        switched = np.concatenate([enc.encode_frames(pcm[:, :1], **KW), enc.encode_frames(pcm[:, 1:2], adaptive=True, sparse=True),
+        switched = np.concatenate([enc.encode_frames(pcm[:, :1], **KW), enc.encode_frames(pcm[:, 1:2], **OLDER_KW[mode]),
                                    enc.encode_frames(pcm[:, 2:], **KW)], axis=1)
     finally:
         enc.close()
@@ -198,12 +248,13 @@ def test_device_buffers_queued_calls_splits_and_flag_switches(B, nch, fb):
         assert np.array_equal(got[k][:n].reshape(S, F, fb), want), k
     assert np.array_equal(got[3][:n].reshape(S, F, fb), t_want)
     assert np.array_equal(parts, want) and np.array_equal(w_parts, want) and np.array_equal(t_parts, t_want)
-    assert np.array_equal(switched[:, 0], want[:, 0]) and np.array_equal(switched[:, 1], want_sparse[:, 1]) and np.array_equal(switched[:, 2], want[:, 2])
+    assert np.array_equal(switched[:, 0], want[:, 0]) and np.array_equal(switched[:, 1], want_older[:, 1]) and np.array_equal(switched[:, 2], want[:, 2])
 
 
-@pytest.mark.parametrize("nch", [1, 2])
-def test_pcm_in(B, nch):
+@_per_mode_and_channels
+def test_pcm_in(B, mode, nch):
     """2 streams x 4 frames of PCM through at3phip_encode_frames and its 16-bit twin at 64 kbit/s per channel pair (376 bytes)"""
+    KW = KWS[mode]
     p16, pcm, specs = _plain(nch, 4)
     enc = B.At3pHip(n_streams=2, max_frames=4, channels=nch, frame_bytes=376)
     try:
@@ -212,21 +263,24 @@ def test_pcm_in(B, nch):
         got16 = enc.encode_frames_s16(p16, **KW)
     finally:
         enc.close()
-    want = _rd(specs, 376)
+    want = _want(mode, specs, 376)
     assert np.array_equal(got, want) and np.array_equal(got16, want)
 
 
-@pytest.mark.parametrize("nch", [1, 2])
-def test_rd_without_adaptive_and_sparse_is_refused_and_moves_nothing(B, nch):
-    """AT3PHIP_ALLOC_RD alone, with ADAPTIVE only and with SPARSE only, on all six calls: AT3HIP_EINVAL with a last-error text, the
-    output untouched, and the next valid call gives the bytes of a fresh stream (no filter-bank or analysis state moved)"""
+@_per_mode_and_channels
+def test_the_flag_without_the_flags_it_needs_is_refused_and_moves_nothing(B, mode, nch):
+    """AT3PHIP_ALLOC_RD alone, with ADAPTIVE only and with SPARSE only, AT3PHIP_ALLOC_PSY with any of ADAPTIVE, SPARSE and RD missing, on
+    all six calls: AT3HIP_EINVAL with a last-error text, the output untouched, and the next valid call gives the bytes of a fresh stream
+    (no filter-bank or analysis state moved)"""
+    KW = KWS[mode]
     p16, pcm, specs = _plain(nch)
     recs = np.zeros((S, F), B.AT3P_TONAL_BLOCK_DTYPE)
     out = np.full((S, F, 2048), SENTINEL, np.uint8)
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch)
     try:
-        for extra in (0, B.AT3PHIP_ALLOC_ADAPTIVE, B.AT3PHIP_ALLOC_SPARSE):
-            flag = B.AT3PHIP_ALLOC_RD | extra
+        for names in LACKING[mode]:
+            extra = sum(getattr(B, "AT3PHIP_ALLOC_" + n) for n in names)
+            flag = getattr(B, FLAG[mode]) | extra
             calls = [lambda: enc.write_frames_ptr(specs.ctypes.data, F, None, out.ctypes.data, flag),
                      lambda: enc.write_frames_tonal_ptr(specs.ctypes.data, F, None, recs.ctypes.data, out.ctypes.data, flag),
                      lambda: enc.encode_frames_ptr(pcm.ctypes.data, F, out.ctypes.data, flag),
@@ -234,22 +288,23 @@ def test_rd_without_adaptive_and_sparse_is_refused_and_moves_nothing(B, nch):
                      lambda: enc.encode_frames_tonal_ptr(pcm.ctypes.data, F, out.ctypes.data, flag),
                      lambda: enc.encode_frames_tonal_s16_ptr(p16.ctypes.data, F, out.ctypes.data, flag)]
             for k, call in enumerate(calls):
-                with pytest.raises(B.At3HipError, match="AT3PHIP_ALLOC_RD needs AT3PHIP_ALLOC_ADAPTIVE and AT3PHIP_ALLOC_SPARSE"):
+                with pytest.raises(B.At3HipError, match=REFUSAL[mode]):
                     call()
                 assert (out == SENTINEL).all(), (extra, k)
-        for bad in (dict(rd=True), dict(adaptive=True, rd=True)):
+        for bad in BAD_KW[mode]:
             with pytest.raises(ValueError):
                 enc.encode_frames(pcm, **bad)
         got = enc.encode_frames(pcm, **KW)
     finally:
         enc.close()
-    assert np.array_equal(got, _rd(specs, 2048))
+    assert np.array_equal(got, _want(mode, specs, 2048))
 
 
-@pytest.mark.parametrize("nch,fb", [(1, 176), (2, 224), (2, 376), (2, 744)], ids=["mono_176", "stereo_224", "stereo_376", "stereo_744"])
-def test_gpu_written_frames_decode_on_the_gpu_with_every_counter_zero(B, nch, fb):
+@_per_mode(DECODE_CASES)
+def test_gpu_written_frames_decode_on_the_gpu_with_every_counter_zero(B, mode, nch, fb):
     """the writer's frames (records among them) through at3phip_decode with AT3PHIP_DECODE_TONES | AT3PHIP_DECODE_SPARSE: no frame
     rejected, and the PCM is the restatement decoder's"""
+    KW = KWS[mode]
     wspecs, blocks = _wspecs(nch), _records(nch)
     recs = np.stack([B.pack_tonal_blocks(row, nch) for row in blocks])
     enc = B.At3pHip(n_streams=S, max_frames=F, channels=nch, frame_bytes=fb)

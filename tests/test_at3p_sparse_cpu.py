@@ -383,8 +383,8 @@ def test_harness_driver_equals_the_restatement():
 def test_a_build_without_the_adaptive_writer_refuses_the_flag(tmp_path):
     """tests/host/at3p_alloc_modes_main.cpp, `none`: at3phip.hip linked without at3p_alloc.hip and at3p_sparse.hip; all six
     frame-writing calls refuse ADAPTIVE | SPARSE and SPARSE alone and write nothing, at3phip_decode refuses AT3PHIP_DECODE_SPARSE.
-    `all`: with every unit each mode's calls are accepted at both sizes, SPARSE without ADAPTIVE is still refused"""
-    run_alloc_modes(tmp_path, "none", "all")
+    `alloc+sparse+rd`: with these units each of their modes' calls is accepted at both sizes, SPARSE without ADAPTIVE is still refused"""
+    run_alloc_modes(tmp_path, "none", "alloc+sparse+rd")
 
 
 def test_symbols_and_flags():

@@ -96,7 +96,7 @@ def quality_restatement():
                     cell[key] = {"snr_db": [round(G.snr_db(a, b, NF), 2) for a, b in chans], "nmr_db": [nmr(a, b, NF)[0] for a, b in chans],
                                  "above": [nmr(a, b, NF)[1] for a, b in chans]}
                 rec = Y.write_psy(sp, fb, info=True)[1]
-                cell["frames_psy_of"] = [int(rec["chose_psy"].sum()), NF]
+                cell["frames_psy_of"] = [int(rec["chose"].sum()), NF]
                 out[f"{name}_{nch}_{kbit}"] = cell
     summary = {}
     for kbit in KBIT:

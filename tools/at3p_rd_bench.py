@@ -48,7 +48,7 @@ def quality_restatement():
                     assert rej.sum() == 0
                     cell[key] = [round(G.snr_db(x[:, :, c].reshape(-1), y[:, :, c].reshape(-1), NF), 2) for c in range(nch)]
                 rec = W.write_rd(sp, fb, info=True)[1]
-                cell["frames_rd_of"] = [int(rec["chose_rd"].sum()), NF]
+                cell["frames_rd_of"] = [int(rec["chose"].sum()), NF]
                 out[f"{name}_{nch}_{kbit}"] = cell
     return out
 
